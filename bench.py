@@ -5,11 +5,14 @@ local).  One process per GPU; for N > 1 every rank runs its own utterance on its
 engine (the path shards over independent utterances, SURVEY.md §8e: "B=1 multi-GPU = replicas"), no
 data-path collective, weak scaling.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
 A step = one encoder forward (feat, feat_len resident in HBM -> logits in HBM), replayed as a hipGraph.
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run only sets up, warms up, times exactly K steps
+(`value`, `ms_per_step`) and, with --dump-outputs DIR, writes the logits of the last timed step to DIR/logits.npy (fp32; inputs
+are seeded, so two builds can be compared output for output).  --full adds everything else, each with runs of its own:
+  repeats         : the timed region repeated --repeats (default 5) times, value = median repeat; a 200-step region beside it;
   roofline        : the kernel family that holds the largest share of the forward's GPU time (picked from the in-run
                     per-stage HIP-event timings, m3_engine_stage_info gives each stage's kernel and algorithmic bytes /
                     FLOPs) -- algorithmic bytes (or FLOPs) / measured duration vs the 8 TB/s HBM (or MFMA) peak;
@@ -17,7 +20,9 @@ Prints ONE JSON line on rank 0 (contract in the task statement), including
   forward         : whole-forward fractions -- algorithmic bytes / one-stream latency / HBM peak, FLOPs / MFMA peak --
                     and the p50 / p99 latency of >= 50 hipEvent-timed forwards;
   cpu_baseline    : the oracle's plain-torch fp32 forward of the same workload timed on the host cores
-                    (kind "port": the reference's CUDA/TensorRT path cannot be built here).
+                    (kind "port": the reference's CUDA/TensorRT path cannot be built here);
+  build           : ABI version, hipcc version and packed-FP32 count read off the built library;
+  ep probe        : N > 1 replica runs end with a short expert-parallel forward (see --no-ep-probe).
 """
 import argparse
 import json
@@ -60,6 +65,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: repeats, latency percentiles, rooflines, CPU baseline + oracle check, build "
+                         "info, the N > 1 expert-parallel probe (a plain run times exactly --steps forwards and stops)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, rank 0 writes the logits of its last timed step to DIR/logits.npy (fp32; "
+                         "above 60 MB a fixed, seeded sample of frames instead)")
     ap.add_argument("--frames", type=int, default=206)
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--layers", type=int, default=18)
@@ -88,7 +99,7 @@ def parse():
                     help="with --weight-dtype fp8: fp8 ARITHMETIC in the grouped expert FFN (e4m3 activations, fp8 MFMA); the "
                          "per-layer H scales are calibrated on the benchmark batch before timing (m3asr.calibrate)")
     ap.add_argument("--varlen", default="", help="LO-HI: utterance lengths drawn from U[LO,HI] frames (configs[2]: 50-500)")
-    ap.add_argument("--profile-stages", action="store_true", help="print per-stage HIP-event times to stderr")
+    ap.add_argument("--profile-stages", action="store_true", help="print per-stage HIP-event times to stderr (implies --full)")
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
                     help="torch.distributed backend of the N > 1 runs (nccl = RCCL; gloo: rehearsal of the multi-rank path "
                          "on a box with fewer GPUs than ranks -- ranks then share devices)")
@@ -97,15 +108,16 @@ def parse():
                          "E / N per rank, every rank keeps --batch utterances, tokens travel by all-to-all (RCCL with "
                          "--dist-backend nccl); value = frames of all ranks / max-over-ranks time")
     ap.add_argument("--no-ep-probe", action="store_true",
-                    help="N > 1 replica runs end with a short expert-parallel forward over the same process group, reported "
+                    help="with --full, N > 1 replica runs end with a short expert-parallel forward over the same process group, reported "
                          "on stderr and in gpurun_out/ep_probe_nN.json AFTER the JSON line; this switches it off")
     ap.add_argument("--pmc-safe", action="store_true",
                     help="for `rocprofv3 --pmc ... -- python3 bench.py --pmc-safe` (set automatically when counter collection is "
                          "detected): one execution context, plain launches, a device synchronise per forward -- the profiler's "
                          "counter-collection thread aborts when thousands of un-synchronised dispatches are in flight (DESIGN.md 6)")
-    ap.add_argument("--repeats", type=int, default=5,
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed loop of --steps forwards is run this many times (each bracketed by barrier + synchronize); "
-                         "value / ms_per_step are the MEDIAN repeat, every repeat is listed in config.ms_per_step_repeats")
+                         "value / ms_per_step are the MEDIAN repeat, every repeat is listed in config.ms_per_step_repeats "
+                         "(default: 5 with --full, else 1)")
     ap.add_argument("--ep-probe-strict", action="store_true",
                     help="N > 1 replica runs: exit non-zero when the expert-parallel probe after the headline line fails or times "
                          "out (default: the outcome is recorded in gpurun_out/ep_probe_nN.json and on stderr, exit code 0)")
@@ -119,7 +131,31 @@ def parse():
                     help="--ep: every wire chunk holds ALL rows of the largest rank (the round-2/3 shape) instead of the bounded wire")
     ap.add_argument("--ep-probe-inject-failure", action="store_true",
                     help="diagnostic (tests): make the expert-parallel probe raise, to show that a failing probe is visible")
-    return ap.parse_args()
+    args = ap.parse_args()
+    args.full = args.full or args.profile_stages
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
+
+
+DUMP_LIMIT = 60 * 1000 * 1000       # bytes of array data: with the .npy headers, under 64 MB in either sense of "MB"
+
+
+def dump_outputs(out_dir, name, x, limit=DUMP_LIMIT):
+    """--dump-outputs: the array a caller of the timed path receives, as out_dir/<name>.npy in float32.  Above `limit` bytes, a
+    fixed, seeded sample of its rows (leading axes flattened) as <name>_sample.npy and their flat row numbers as
+    <name>_sample_rows.npy (float64): the same rows for the same shape, so two builds remain comparable.  Returns the files."""
+    os.makedirs(out_dir, exist_ok=True)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.nbytes <= limit:
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+        return [name + ".npy"]
+    rows = x.reshape(-1, x.shape[-1])
+    k = max(1, min(rows.shape[0], limit // (rows.shape[1] * 4 + 8)))
+    idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], size=k, replace=False))
+    np.save(os.path.join(out_dir, name + "_sample.npy"), rows[idx])
+    np.save(os.path.join(out_dir, name + "_sample_rows.npy"), idx.astype(np.float64))
+    return [name + "_sample.npy", name + "_sample_rows.npy"]
 
 
 def stage_times(eng, passes=20):
@@ -175,9 +211,10 @@ def balance_router(eng, cpu_weights):
     eng.stream.synchronize()
 
 
-def run_ep(args, rank, world, dev, dist, weights_full, steps, warmup, wdt, B, varlen, frames, balanced=True):
+def run_ep(args, rank, world, dev, dist, weights_full, steps, warmup, wdt, B, varlen, frames, balanced=True, dump_dir=None):
     """Expert-parallel forwards (m3asr/ep.py): experts sharded E / world per rank, batch sharded B per rank, two fixed-shape
-    all-to-alls per MoE layer, no host synchronisation inside a forward.  Returns a dict (rank 0: the measurement)."""
+    all-to-alls per MoE layer, no host synchronisation inside a forward.  Returns a dict (rank 0: the measurement).
+    dump_dir: rank 0 writes the logits of the last timed forward there (--dump-outputs)."""
     from m3asr.config import EncoderConfig
     from m3asr.engine import Engine
     from m3asr.ep import ExpertParallelEncoder
@@ -252,6 +289,8 @@ def run_ep(args, rank, world, dev, dist, weights_full, steps, warmup, wdt, B, va
     eng.stream.synchronize()
     sync()
     dt = time.perf_counter() - t0
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, "logits", ep._bound[0].cpu().numpy())
     frames_all = torch.tensor([float(lengths.sum())], dtype=torch.float64, device="cpu" if (on_host or world == 1) else dev)
     tmax = torch.tensor([dt], dtype=torch.float64, device=frames_all.device)
     if world > 1:
@@ -315,7 +354,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     # (rank 0 disassembles the built library for the JSON line's `build` entry NOW, ~3 s: not between the timed region and the
     #  headline line, where a peer that has already left would get this rank killed by the launcher before it prints)
-    build = build_info() if rank == 0 else None
+    build = build_info() if rank == 0 and args.full else None
     assert world == args.gpus, "--gpus %d but WORLD_SIZE=%d" % (args.gpus, world)
     if args.dist_backend == "gloo":          # rehearsal: more ranks than devices is fine, they share
         local_rank %= torch.cuda.device_count()
@@ -351,7 +390,7 @@ def main():
 
     if args.ep:
         r = run_ep(args, rank, world, dev, dist if world > 1 else None, weights, args.steps, args.warmup, args.weight_dtype,
-                   args.batch, args.varlen, args.frames, balanced=args.routing == "balanced")
+                   args.batch, args.varlen, args.frames, balanced=args.routing == "balanced", dump_dir=args.dump_outputs)
         if rank == 0:
             full18 = args.layers == 18
             if full18 and args.weight_dtype == "bf16" and args.experts == 32 and world == 8 and args.batch == 2 and args.varlen == "50-500":
@@ -412,7 +451,7 @@ def main():
         del eng
         torch.cuda.empty_cache()
         eng = Engine.from_state_dict(cfg, weights, device=dev, fold_pos_proj=args.fold_pos, fuse_route=route, packed_rows=packed, fork_embed=fork)
-    if not ((rank == 0 and world == 1 and not args.no_cpu_baseline) or (world > 1 and not args.no_ep_probe)):
+    if not (args.full and ((rank == 0 and world == 1 and not args.no_cpu_baseline) or (world > 1 and not args.no_ep_probe))):
         weights = None
     eng.bind(feat, feat_len)
     eng.forward(use_graph=False)
@@ -439,8 +478,8 @@ def main():
     phase("warm-up enqueued")
     barrier()
     phase("warm-up done (device synchronised)")
-    # the timed region: EXACTLY --steps forwards between barrier + synchronize on both sides, max over ranks; repeated
-    # --repeats times so that a short run (the driver's 20 steps = 20 ms) is not a single 20 ms sample: value = median repeat
+    # the timed region: EXACTLY --steps forwards between barrier + synchronize on both sides, max over ranks; with --full (or an
+    # explicit --repeats) repeated so that a short run (20 steps = 20 ms) is not a single 20 ms sample: value = median repeat
     rep_dt = []
     for _ in range(max(1, 1 if args.pmc_safe else args.repeats)):
         barrier()
@@ -461,10 +500,12 @@ def main():
     dt = float(np.median(rep_dt))
     ms_per_step = dt / args.steps * 1e3
     phase("timed region done")
+    if args.dump_outputs and rank == 0:      # the last timed step ran on context (steps - 1) % contexts; nothing has run since
+        dump_outputs(args.dump_outputs, "logits", ctxs[(args.steps - 1) % len(ctxs)]._bound[2].cpu().numpy())
     # the driver's default run times 20 forwards per repeat (20 ms samples): a 200-forward region beside it, same contexts, same
     # bracketing, reported as config.value_200_steps (never as `value`)
     long_dt = []
-    if args.steps < 200 and not args.pmc_safe and world == 1:
+    if args.full and args.steps < 200 and not args.pmc_safe and world == 1:
         for _ in range(3):
             barrier()
             t0 = time.perf_counter()
@@ -476,31 +517,33 @@ def main():
             long_dt.append(time.perf_counter() - t0)
     # latency of one forward when it has the GPU to itself (one context): back-to-back mean, and the distribution of
     # individually hipEvent-timed forwards (events recorded on the engine's own stream, one forward in flight at a time)
-    t1 = time.perf_counter()
-    n_lat = 5 if args.pmc_safe else 50
-    for _ in range(n_lat):
-        eng.forward(use_graph=use_graph)
-        if args.pmc_safe:          # counter collection: keep the dispatches in flight bounded
-            eng.stream.synchronize()
-    eng.stream.synchronize()
-    latency_ms = (time.perf_counter() - t1) / n_lat * 1e3
-    phase("back-to-back forwards done")
-    lat = []
-    for _ in range(max(50, args.latency_iters)):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(eng.stream)
-        eng.forward(use_graph=use_graph)
-        e1.record(eng.stream)
-        e1.synchronize()
-        lat.append(e0.elapsed_time(e1))
-    lat = np.sort(np.array(lat))
-    phase("hipEvent-timed forwards done")
+    latency_ms = lat = None
+    if args.full:
+        t1 = time.perf_counter()
+        n_lat = 5 if args.pmc_safe else 50
+        for _ in range(n_lat):
+            eng.forward(use_graph=use_graph)
+            if args.pmc_safe:          # counter collection: keep the dispatches in flight bounded
+                eng.stream.synchronize()
+        eng.stream.synchronize()
+        latency_ms = (time.perf_counter() - t1) / n_lat * 1e3
+        phase("back-to-back forwards done")
+        lat = []
+        for _ in range(max(50, args.latency_iters)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(eng.stream)
+            eng.forward(use_graph=use_graph)
+            e1.record(eng.stream)
+            e1.synchronize()
+            lat.append(e0.elapsed_time(e1))
+        lat = np.sort(np.array(lat))
+        phase("hipEvent-timed forwards done")
     frames_per_step = world * n_frames
     value = frames_per_step / (dt / args.steps)
 
     # ---- rooflines, measured live with HIP events on the engine's stream ----
     roofline = roofline_expert = forward = None
-    if rank == 0:
+    if rank == 0 and args.full:
         D, F, E, S = cfg.attention_dim, cfg.hidden_units, cfg.num_experts, B * subsampled_len(T)
         info = eng.stage_info()
         names, ms = stage_times(eng)
@@ -647,7 +690,7 @@ def main():
 
     # ---- CPU baseline: the oracle (plain-torch fp32 restatement) on the host cores, rank 0, N=1 only ----
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from oracle.encoder_ref import encoder_forward
         fl_cpu = torch.from_numpy(lengths.astype(np.int32))
         cores = args.cpu_threads if args.cpu_threads > 0 else min(32, os.cpu_count() or 1)
@@ -719,8 +762,8 @@ def main():
                           "parallelism": "replicas x%d" % world, "streams_per_gpu": len(ctxs),
                           "value_is": "%d concurrent batch-%d requests per GPU (execution contexts sharing one copy of the "
                                       "weights); one request alone: latency_ms_one_stream" % (len(ctxs), B),
-                          "latency_ms_one_stream": round(latency_ms, 4),
-                          "frames_per_s_one_stream": round(n_frames / (latency_ms * 1e-3), 1), "hip_graph": use_graph,
+                          "latency_ms_one_stream": round(latency_ms, 4) if latency_ms else None,
+                          "frames_per_s_one_stream": round(n_frames / (latency_ms * 1e-3), 1) if latency_ms else None, "hip_graph": use_graph,
                           "h_scale_min_max": fp8_h_scales, "kernels_per_forward": eng.num_kernels(), "fold_pos_proj": bool(args.fold_pos),
                           "routing": args.routing, "route_mode": ["staged", "fused", "split"][route],
                           "packed_rows": bool(B > 1 and eng.packed_rows()), "fork_embed": args.fork_embed,
@@ -732,7 +775,7 @@ def main():
                           "h_scale_calibrated_on": ("the benchmark batch itself (untimed set-up)" if args.fp8_activations else None)},
                "roofline": roofline, "roofline_expert": roofline_expert, "forward": forward, "cpu_baseline": cpu}
         print(json.dumps(out), flush=True)
-    if world > 1 and not args.no_ep_probe and weights is not None:
+    if world > 1 and args.full and not args.no_ep_probe and weights is not None:
         # After the headline line: a short expert-parallel run over the same process group (configs[3]-shaped: bf16, 2
         # ragged utterances per GPU, experts sharded E / N), so that a multi-GPU run also exercises the all-to-all path.
         # The outcome -- status ok / failed / timeout, the measurement or the exception -- goes to stderr and to

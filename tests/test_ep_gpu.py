@@ -80,7 +80,7 @@ def test_bench_expert_parallel_rehearsal_two_ranks_one_gpu(tmp_path):
     # (the gloo rehearsal stages every exchange through the host: 2 synchronisations per layer; RCCL: none)
     assert line["config"]["wire"]["host_syncs_per_forward"] == 4 and line["config"]["wire"]["collectives_per_forward"] == 4
     assert line["config"]["forward_graph"].startswith("eager: the gloo transport")
-    r = subprocess.run(base_cmd() + ["--streams", "2"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+    r = subprocess.run(base_cmd() + ["--full", "--streams", "2"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["config"]["parallelism"] == "replicas x2"
@@ -88,7 +88,7 @@ def test_bench_expert_parallel_rehearsal_two_ranks_one_gpu(tmp_path):
     probe = json.load(open(os.path.join(root, "gpurun_out", "ep_probe_n2.json")))
     assert probe["status"] == "ok" and probe["value"] > 0
     # a failing probe is visible: status "failed" + the exception on stderr and in the file, exit code non-zero when strict
-    r = subprocess.run(base_cmd() + ["--streams", "2", "--ep-probe-inject-failure", "--ep-probe-strict"], capture_output=True, text=True,
+    r = subprocess.run(base_cmd() + ["--full", "--streams", "2", "--ep-probe-inject-failure", "--ep-probe-strict"], capture_output=True, text=True,
                        timeout=600, env=env, cwd=root)
     assert r.returncode != 0
     assert [l for l in r.stdout.splitlines() if l.startswith("{")], "the headline line must still be printed; stderr: " + r.stderr[-3000:]

@@ -27,21 +27,21 @@ while [ $# -gt 0 ]; do
     tests)
       timeout -k 10 1700 python -m pytest tests -m gpu -x -q "$@" > $O/pytest.log 2>&1; rc=$?; echo "pytest rc=$rc"; tail -15 $O/pytest.log
       exit $rc ;;
-    bench)      python bench.py --steps 200 --warmup 20 > $O/bench_n1.json 2> $O/bench_n1.err; echo "rc=$?"; tail -c 600 $O/bench_n1.json ;;
-    bench_cfg3) python bench.py $CFG3 --steps 100 --warmup 10 > $O/bench_cfg3_bf16.json 2> $O/bench_cfg3.err; echo "rc=$?"; tail -c 400 $O/bench_cfg3_bf16.json ;;
-    bench_cfg5) python bench.py $CFG5 --steps 60 --warmup 6 > $O/bench_cfg5share_fp8a8.json 2> $O/bench_cfg5.err; echo "rc=$?"; tail -c 400 $O/bench_cfg5share_fp8a8.json ;;
+    bench)      python bench.py --full --steps 200 --warmup 20 > $O/bench_n1.json 2> $O/bench_n1.err; echo "rc=$?"; tail -c 600 $O/bench_n1.json ;;
+    bench_cfg3) python bench.py --full $CFG3 --steps 100 --warmup 10 > $O/bench_cfg3_bf16.json 2> $O/bench_cfg3.err; echo "rc=$?"; tail -c 400 $O/bench_cfg3_bf16.json ;;
+    bench_cfg5) python bench.py --full $CFG5 --steps 60 --warmup 6 > $O/bench_cfg5share_fp8a8.json 2> $O/bench_cfg5.err; echo "rc=$?"; tail -c 400 $O/bench_cfg5share_fp8a8.json ;;
     bench_ep)
       python bench.py --ep --weight-dtype bf16 --batch 16 --varlen 50-500 --steps 60 --warmup 6 > $O/bench_ep_world1.json 2> $O/bench_ep.err; echo "rc=$?"; tail -c 700 $O/bench_ep_world1.json
       python bench.py --ep --no-graph --weight-dtype bf16 --batch 16 --varlen 50-500 --steps 60 --warmup 6 > $O/bench_ep_world1_eager.json 2>> $O/bench_ep.err; echo "rc=$?"
-      python bench.py --weight-dtype bf16 --batch 16 --varlen 50-500 --streams 1 --steps 60 --warmup 6 --no-cpu-baseline > $O/bench_cfg3_one_stream.json 2>> $O/bench_ep.err; echo "rc=$?" ;;
+      python bench.py --full --weight-dtype bf16 --batch 16 --varlen 50-500 --streams 1 --steps 60 --warmup 6 --no-cpu-baseline > $O/bench_cfg3_one_stream.json 2>> $O/bench_ep.err; echo "rc=$?" ;;
     kt|kt_cfg3|kt_cfg5)
       case $step in kt) A="--steps 200 --warmup 20";; kt_cfg3) A="$CFG3 --steps 60 --warmup 6";; kt_cfg5) A="$CFG5 --steps 40 --warmup 4";; esac
-      ( cd /tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/$step -- python3 $R/bench.py $A --no-cpu-baseline > $R/$O/$step.json 2> $R/$O/$step.err; echo "rc=$?" )
+      ( cd "$TMPDIR" && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/$step -- python3 $R/bench.py --full $A --no-cpu-baseline > $R/$O/$step.json 2> $R/$O/$step.err; echo "rc=$?" )
       f=$(find $O/$step -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $O/${step}_kernel_stats.csv && head -12 $O/${step}_kernel_stats.csv
       find $O/$step -name "*kernel_trace.csv" -delete ;;
     pmc)
       for C in FETCH_SIZE WRITE_SIZE; do
-        ( cd /tmp && timeout -k 10 400 rocprofv3 --pmc $C --output-format csv -d $R/$O/pmc_$C -- python3 $R/bench.py --pmc-safe --steps 6 --warmup 1 --no-cpu-baseline > $R/$O/pmc_$C.json 2> $R/$O/pmc_$C.err; echo "pmc_$C rc=$?" )
+        ( cd "$TMPDIR" && timeout -k 10 400 rocprofv3 --pmc $C --output-format csv -d $R/$O/pmc_$C -- python3 $R/bench.py --full --pmc-safe --steps 6 --warmup 1 --no-cpu-baseline > $R/$O/pmc_$C.json 2> $R/$O/pmc_$C.err; echo "pmc_$C rc=$?" )
       done
       python3 tools/pmc_summarize.py $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE $O/pmc_bench.json f32 1 206 18 32 --bench-line $O/pmc_FETCH_SIZE.json
       find $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE -name "*.csv" -size +20M -delete ;;
@@ -75,7 +75,7 @@ PY
       for rep in 1 2; do
         for v in base fork_off nt0 nt0_fork_off; do
           case $v in base) E=""; A="";; fork_off) E=""; A="--fork-embed off";; nt0) E="M3ASR_LIB=$R/tools/_ab_nt0.so"; A="";; nt0_fork_off) E="M3ASR_LIB=$R/tools/_ab_nt0.so"; A="--fork-embed off";; esac
-          env $E python bench.py --steps 200 --warmup 20 --no-cpu-baseline $A > $O/ab_${v}_$rep.json 2> $O/ab_${v}_$rep.err
+          env $E python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline $A > $O/ab_${v}_$rep.json 2> $O/ab_${v}_$rep.err
           python3 -c "import json,sys; d=json.loads([l for l in open('$O/ab_${v}_$rep.json') if l.startswith('{')][-1]); print('$v rep $rep: value %.0f  one-stream %.4f ms  p50 %.4f' % (d['value'], d['config']['latency_ms_one_stream'], d['forward']['latency_ms']['p50']))"
         done
       done ;;
