@@ -315,6 +315,30 @@ int m3_ctc_prefix_beam_search(const float* top_logp, const int32_t* top_idx, int
                               int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score, int32_t* n_hyps) {
   return ctc_prefix_beam_search_host(top_logp, top_idx, T, k, beam, blank, hyp_tokens, hyp_len, hyp_score, n_hyps);
 }
+size_t m3_ctc_beam_state_size(const m3_ctc_beam_desc* desc) { return ctc_beam_state_size(desc); }
+int m3_ctc_beam_reset(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, m3_stream stream) {
+  return launch_ctc_beam_reset(desc, state, state_bytes, (hipStream_t)stream);
+}
+int m3_ctc_beam_advance(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const float* top_logp,
+                        const int32_t* top_idx, int T_chunk, const int32_t* n_frames, m3_stream stream) {
+  return launch_ctc_beam_advance(desc, state, state_bytes, top_logp, top_idx, T_chunk, n_frames, (hipStream_t)stream);
+}
+int m3_ctc_beam_nbest(const m3_ctc_beam_desc* desc, const void* state, size_t state_bytes, int32_t* hyp_tokens,
+                      int32_t* hyp_len, float* hyp_score, int32_t* n_hyps, m3_stream stream) {
+  return launch_ctc_beam_nbest(desc, state, state_bytes, hyp_tokens, hyp_len, hyp_score, n_hyps, (hipStream_t)stream);
+}
+size_t m3_ctc_greedy_stream_state_size(const m3_ctc_greedy_desc* desc) { return ctc_greedy_stream_state_size(desc); }
+int m3_ctc_greedy_stream_reset(const m3_ctc_greedy_desc* desc, void* state, size_t state_bytes, m3_stream stream) {
+  return launch_ctc_greedy_stream_reset(desc, state, state_bytes, (hipStream_t)stream);
+}
+int m3_ctc_greedy_stream_advance(const m3_ctc_greedy_desc* desc, void* state, size_t state_bytes, const float* logits,
+                                 int T_chunk, int V, const int32_t* n_frames, int32_t* frame_ids, m3_stream stream) {
+  return launch_ctc_greedy_stream_advance(desc, state, state_bytes, logits, T_chunk, V, n_frames, frame_ids, (hipStream_t)stream);
+}
+int m3_ctc_greedy_stream_tokens(const m3_ctc_greedy_desc* desc, const void* state, size_t state_bytes, int32_t* tokens,
+                                int32_t* n_tokens, m3_stream stream) {
+  return launch_ctc_greedy_stream_tokens(desc, state, state_bytes, tokens, n_tokens, (hipStream_t)stream);
+}
 int m3_cat_split_cache(const void* in_cache, const void* input, int B, int cache_dim, int input_dim, void* output,
                        void* out_cache, m3_stream stream) {
   return launch_cat_split_cache(in_cache, input, B, cache_dim, input_dim, output, out_cache, (hipStream_t)stream);

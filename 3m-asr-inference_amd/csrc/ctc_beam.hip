@@ -1,0 +1,560 @@
+// Batched, resumable CTC prefix beam search on the device (trainer_3m_fix/model/encoder.py:182-275), and the streaming
+// form of the greedy search (:156-180).
+//
+// Prefix beam search.  The input is m3_ctc_topk's (top_logp, top_idx) [B][T_chunk][k]; the recursion is the host routine's
+// (decode.hip, ctc_prefix_beam_search_host) term for term, in double: the same log_add2 / log_add3 calls on the same operands in
+// the same order, so that prefixes, their order and their scores come out as the host's.  One work-group per utterance; all
+// frames of a call run inside one launch; the whole search state lives in caller-owned device memory, so a search can be
+// resumed at any frame boundary (chunk by chunk gives the bits of one call over the concatenated frames).
+//
+// Per frame, with n beam entries and k candidate symbols, the host's slots are touched in the order
+//   touch = (j * n + h) * 2 + sub      (j: top-k rank, h: beam position, sub = 1 only for the extension of "s == last")
+// and a slot keeps its first touch as its tie-break in the stable second prune.  Two facts make the grouping small:
+//   * an extension p + s can only coincide with a beam entry q (whose parent is p and whose last symbol is s) -- two
+//     extensions never coincide, because the beam entries are distinct prefixes and the k symbols are distinct;
+//   * so the slot of beam entry q receives at most three touches: the blank at rank jb (pb), the repeat of its last symbol
+//     at rank jl (pnb), and its parent's extension by that same symbol (pnb); every other extension is a slot of its own.
+// Candidates: the n beam-entry slots (if touched) and the n * k extension slots that did not merge.  The prune keeps the
+// `beam` best by (score desc, first touch asc): each candidate counts the candidates ahead of it (its rank).
+//
+// Prefix identity.  Prefixes are nodes of a per-utterance trie (parent, token, depth).  Nodes are CANONICAL: a device hash
+// table (parent, token) -> node holds every node ever made for the utterance, so a prefix that dropped out of the beam and
+// is re-created later gets its old node back.  That is what makes "q's parent is p" (node compare) the same as "q == p + s"
+// (prefix compare); with a fresh node per extension a re-created p would not be the parent of q and the same prefix would
+// appear twice.  Only survivors of the prune get nodes: at most `beam` per frame, so the pool holds 1 + max_frames * beam.
+#include <algorithm>
+#include <cmath>
+
+#include "common.h"
+#include "kernels.h"
+
+namespace m3 {
+
+namespace {
+
+constexpr int kBeamMax = 32, kTopkMax = 32;
+constexpr int kCandMax = kBeamMax + kBeamMax * kTopkMax;
+constexpr int kBeamThreads = 256;
+constexpr unsigned long long kEmptyKey = ~0ull;
+// header words of one utterance's state
+enum { H_STATUS = 0, H_FRAMES = 1, H_NCUR = 2, H_NNODES = 3, H_WORDS = 16 };
+
+struct BeamLayout {       // byte offsets inside one utterance's slice of the state
+  size_t beam_node, beam_pb, beam_pnb, parent, token, depth, hkey, hval, stride;
+  int pool, hcap;
+};
+
+BeamLayout beam_layout(int beam, int max_frames) {
+  BeamLayout L;
+  L.pool = 1 + max_frames * beam;
+  L.hcap = 16;
+  while (L.hcap < 2 * L.pool) L.hcap <<= 1;
+  size_t off = H_WORDS * 4;
+  L.beam_node = off; off = align_up(off + (size_t)beam * 4, 8);
+  L.beam_pb = off;   off += (size_t)beam * 8;
+  L.beam_pnb = off;  off += (size_t)beam * 8;
+  L.parent = off;    off = align_up(off + (size_t)L.pool * 4, 8);
+  L.token = off;     off = align_up(off + (size_t)L.pool * 4, 8);
+  L.depth = off;     off = align_up(off + (size_t)L.pool * 4, 8);
+  L.hkey = off;      off += (size_t)L.hcap * 8;
+  L.hval = off;      off += (size_t)L.hcap * 4;
+  L.stride = align_up(off, 256);
+  return L;
+}
+
+int check_beam_desc(const m3_ctc_beam_desc* d) {
+  M3_REQUIRE(d != nullptr, "ctc_beam: null descriptor");
+  M3_REQUIRE(d->B >= 0, "ctc_beam: B = %d < 0", d->B);
+  M3_REQUIRE(d->beam >= 1 && d->beam <= kBeamMax, "ctc_beam: beam = %d outside [1, %d]", d->beam, kBeamMax);
+  M3_REQUIRE(d->k >= 1 && d->k <= kTopkMax, "ctc_beam: k = %d outside [1, %d]", d->k, kTopkMax);
+  M3_REQUIRE(d->max_frames >= 0 && (int64_t)d->max_frames * d->beam < (1 << 28), "ctc_beam: max_frames = %d out of range",
+             d->max_frames);
+  M3_REQUIRE(d->blank >= 0, "ctc_beam: blank = %d < 0", d->blank);
+  return 0;
+}
+
+// utils/common.py:148-156 in the form of decode.hip's host routine (std::max order, no contraction: -ffp-contract=off)
+__device__ __forceinline__ double dmax(double a, double b) { return a < b ? b : a; }
+__device__ __forceinline__ double log_add3(double a, double b, double c) {
+  if (a == -INFINITY && b == -INFINITY && c == -INFINITY) return -INFINITY;
+  const double m = dmax(a, dmax(b, c));
+  return m + log(exp(a - m) + exp(b - m) + exp(c - m));
+}
+__device__ __forceinline__ double log_add2(double a, double b) {
+  if (a == -INFINITY && b == -INFINITY) return -INFINITY;
+  const double m = dmax(a, b);
+  return m + log(exp(a - m) + exp(b - m));
+}
+
+__device__ __forceinline__ unsigned long long node_key(int parent, int token) {
+  return ((unsigned long long)(uint32_t)parent << 32) | (uint32_t)token;
+}
+__device__ __forceinline__ int hash_slot(unsigned long long key, int hcap) {
+  key ^= key >> 33;
+  key *= 0xff51afd7ed558ccdull;
+  key ^= key >> 33;
+  return (int)(key & (unsigned long long)(hcap - 1));
+}
+
+struct BeamPtrs {
+  int32_t* hdr;
+  int32_t* node;
+  double* pb;
+  double* pnb;
+  int32_t* parent;
+  int32_t* token;
+  int32_t* depth;
+  unsigned long long* hkey;
+  int32_t* hval;
+};
+__device__ __forceinline__ BeamPtrs beam_ptrs(const BeamLayout& L, char* state, int b) {
+  char* s = state + (size_t)b * L.stride;
+  return BeamPtrs{(int32_t*)s, (int32_t*)(s + L.beam_node), (double*)(s + L.beam_pb), (double*)(s + L.beam_pnb),
+                  (int32_t*)(s + L.parent), (int32_t*)(s + L.token), (int32_t*)(s + L.depth),
+                  (unsigned long long*)(s + L.hkey), (int32_t*)(s + L.hval)};
+}
+
+// grid (x: hash-table blocks, y: utterance): empty hash table, root node, beam = {empty prefix: pb = 0, pnb = -inf}
+__global__ __launch_bounds__(256) void ctc_beam_reset_kernel(BeamLayout L, char* state) {
+  const BeamPtrs p = beam_ptrs(L, state, blockIdx.y);
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < L.hcap; i += gridDim.x * 256) {
+    p.hkey[i] = kEmptyKey;
+    p.hval[i] = -1;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    for (int w = 0; w < H_WORDS; ++w) p.hdr[w] = 0;
+    p.hdr[H_NCUR] = 1;
+    p.hdr[H_NNODES] = 1;
+    p.parent[0] = -1;
+    p.token[0] = -1;
+    p.depth[0] = 0;
+    p.node[0] = 0;
+    p.pb[0] = 0.0;
+    p.pnb[0] = -INFINITY;
+  }
+}
+
+__global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayout L, int beam, int k, int blank, int max_frames,
+                                                                        char* state, const float* __restrict__ top_logp,
+                                                                        const int32_t* __restrict__ top_idx, int T_chunk,
+                                                                        const int32_t* __restrict__ n_frames) {
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const BeamPtrs p = beam_ptrs(L, state, b);
+  // current beam (best first) and its nodes
+  __shared__ int s_node[kBeamMax], s_par[kBeamMax], s_tok[kBeamMax], s_dep[kBeamMax];
+  __shared__ double s_pb[kBeamMax], s_pnb[kBeamMax];
+  // this frame's candidates
+  __shared__ int f_s[kTopkMax];
+  __shared__ double f_ps[kTopkMax];
+  __shared__ unsigned char merged[kBeamMax * kTopkMax];
+  __shared__ double c_score[kCandMax], c_pb[kCandMax], c_pnb[kCandMax];
+  __shared__ int c_first[kCandMax];
+  // survivors, in rank order
+  __shared__ int n_src[kBeamMax], n_node[kBeamMax], n_par[kBeamMax], n_tok[kBeamMax], n_dep[kBeamMax];
+  __shared__ double n_pb[kBeamMax], n_pnb[kBeamMax];
+  __shared__ int sh_status, sh_nf, sh_ncur, sh_nnodes, sh_nvalid;
+
+  if (tid == 0) {
+    int status = p.hdr[H_STATUS];
+    const int frames = p.hdr[H_FRAMES];
+    const int nf = min(max(n_frames[b], 0), T_chunk);
+    if (status == 0 && frames + nf > max_frames) {     // nothing of this call is consumed; the state stays in bounds
+      status = 1;
+      p.hdr[H_STATUS] = status;
+    }
+    sh_status = status;
+    sh_nf = nf;
+    sh_ncur = p.hdr[H_NCUR];
+    sh_nnodes = p.hdr[H_NNODES];
+  }
+  __syncthreads();
+  if (sh_status != 0 || sh_nf == 0) return;
+  const int nf = sh_nf;
+  if (tid < sh_ncur) {
+    const int nd = p.node[tid];
+    s_node[tid] = nd;
+    s_par[tid] = p.parent[nd];
+    s_tok[tid] = p.token[nd];
+    s_dep[tid] = p.depth[nd];
+    s_pb[tid] = p.pb[tid];
+    s_pnb[tid] = p.pnb[tid];
+  }
+  int t = 0;
+  for (; t < nf; ++t) {
+    const int n = sh_ncur;
+    const size_t row = ((size_t)b * T_chunk + t) * k;
+    if (tid < k) {
+      f_s[tid] = top_idx[row + tid];
+      f_ps[tid] = (double)top_logp[row + tid];
+    }
+    for (int i = tid; i < n * k; i += kBeamThreads) merged[i] = 0;
+    if (tid == 0) sh_nvalid = 0;
+    __syncthreads();
+    // the slot of beam entry q: blank touch (pb), repeat touch and the parent's extension (pnb), in touch order
+    if (tid < n) {
+      const int q = tid, tok = s_tok[q];
+      int jb = -1, jl = -1, ph = -1;
+      for (int j = 0; j < k; ++j) {
+        if (f_s[j] == blank) jb = j;
+        if (f_s[j] == tok) jl = j;              // tok = -1 (root) never matches
+      }
+      for (int h = 0; h < n; ++h)
+        if (s_node[h] == s_par[q]) ph = h;      // the root's parent (-1) never matches
+      double pb = -INFINITY, pnb = -INFINITY;
+      int first = 0x7fffffff;
+      if (jb >= 0) {
+        const double ps = f_ps[jb];
+        pb = log_add3(pb, s_pb[q] + ps, s_pnb[q] + ps);
+        first = (jb * n + q) * 2;
+      }
+      if (jl >= 0) {
+        const double ps = f_ps[jl];
+        const int rep = (jl * n + q) * 2;
+        first = min(first, rep);
+        if (ph >= 0) {
+          const int sub = tok == s_tok[ph] ? 1 : 0;
+          const int ext = (jl * n + ph) * 2 + sub;
+          merged[ph * k + jl] = 1;
+          first = min(first, ext);
+          if (ext < rep) {
+            pnb = sub ? log_add2(pnb, s_pb[ph] + ps) : log_add3(pnb, s_pb[ph] + ps, s_pnb[ph] + ps);
+            pnb = log_add2(pnb, s_pnb[q] + ps);
+          } else {
+            pnb = log_add2(pnb, s_pnb[q] + ps);
+            pnb = sub ? log_add2(pnb, s_pb[ph] + ps) : log_add3(pnb, s_pb[ph] + ps, s_pnb[ph] + ps);
+          }
+        } else {
+          pnb = log_add2(pnb, s_pnb[q] + ps);
+        }
+      }
+      c_pb[q] = pb;
+      c_pnb[q] = pnb;
+      c_first[q] = first;
+      if (first != 0x7fffffff) c_score[q] = log_add2(pb, pnb);
+    }
+    __syncthreads();
+    // the extensions that are slots of their own
+    const int N = n + n * k;
+    for (int i = tid; i < n * k; i += kBeamThreads) {
+      const int h = i / k, j = i - h * k, c = n + i;
+      const int s = f_s[j];
+      if (s == blank || merged[i]) {
+        c_first[c] = 0x7fffffff;
+        continue;
+      }
+      const double ps = f_ps[j];
+      double pnb;
+      int sub;
+      if (s == s_tok[h]) {
+        sub = 1;
+        pnb = log_add2(-INFINITY, s_pb[h] + ps);
+      } else {
+        sub = 0;
+        pnb = log_add3(-INFINITY, s_pb[h] + ps, s_pnb[h] + ps);
+      }
+      c_pb[c] = -INFINITY;
+      c_pnb[c] = pnb;
+      c_first[c] = (j * n + h) * 2 + sub;
+      c_score[c] = log_add2(-INFINITY, pnb);
+    }
+    __syncthreads();
+    // second prune: rank = number of candidates ahead in (score desc, first touch asc); ranks < beam survive
+    for (int i = tid; i < N; i += kBeamThreads) {
+      const int fi = c_first[i];
+      if (fi == 0x7fffffff) continue;
+      atomicAdd(&sh_nvalid, 1);
+      const double si = c_score[i];
+      int r = 0;
+      for (int c = 0; c < N && r < beam; ++c) {
+        const int fc = c_first[c];
+        if (fc == 0x7fffffff) continue;
+        const double sc = c_score[c];
+        r += (sc > si || (sc == si && fc < fi)) ? 1 : 0;
+      }
+      if (r < beam) {
+        n_src[r] = i;
+        n_pb[r] = c_pb[i];
+        n_pnb[r] = c_pnb[i];
+      }
+    }
+    __syncthreads();
+    // nodes of the survivors: a beam entry keeps its node; an extension looks (parent, token) up, or gets a new node
+    if (tid < 64) {
+      const int n_next = min(sh_nvalid, beam);
+      int node = -1, par = -1, tok = -1, dep = 0;
+      unsigned long long key = 0;
+      if (tid < n_next) {
+        const int src = n_src[tid];
+        if (src < n) {
+          node = s_node[src];
+          par = s_par[src];
+          tok = s_tok[src];
+          dep = s_dep[src];
+        } else {
+          const int h = (src - n) / k, j = (src - n) - h * k;
+          par = s_node[h];
+          tok = f_s[j];
+          dep = s_dep[h] + 1;
+          key = node_key(par, tok);
+          int slot = hash_slot(key, L.hcap);
+          for (int probe = 0; probe < L.hcap; ++probe) {
+            const unsigned long long kk = p.hkey[slot];
+            if (kk == key) {
+              node = p.hval[slot];
+              break;
+            }
+            if (kk == kEmptyKey) break;
+            slot = (slot + 1) & (L.hcap - 1);
+          }
+        }
+      }
+      const bool fresh = tid < n_next && node < 0;
+      const unsigned long long m = __ballot(fresh);
+      const int base = sh_nnodes;
+      if (base + __popcll(m) > L.pool) {            // cannot happen while frames <= max_frames; never write past the pool
+        if (tid == 0) sh_status = 2;
+      } else if (fresh) {
+        node = base + __popcll(m & ((1ull << tid) - 1ull));
+        p.parent[node] = par;
+        p.token[node] = tok;
+        p.depth[node] = dep;
+        int slot = hash_slot(key, L.hcap);
+        for (int probe = 0; probe < L.hcap; ++probe) {
+          if (atomicCAS(&p.hkey[slot], kEmptyKey, key) == kEmptyKey) {
+            p.hval[slot] = node;
+            break;
+          }
+          slot = (slot + 1) & (L.hcap - 1);
+        }
+      }
+      if (tid < n_next) {
+        n_node[tid] = node;
+        n_par[tid] = par;
+        n_tok[tid] = tok;
+        n_dep[tid] = dep;
+      }
+      if (tid == 0) {
+        sh_nnodes = base + (sh_status == 0 ? __popcll(m) : 0);
+        sh_ncur = n_next;
+      }
+    }
+    __syncthreads();
+    if (sh_status != 0) break;
+    if (tid < sh_ncur) {
+      s_node[tid] = n_node[tid];
+      s_par[tid] = n_par[tid];
+      s_tok[tid] = n_tok[tid];
+      s_dep[tid] = n_dep[tid];
+      s_pb[tid] = n_pb[tid];
+      s_pnb[tid] = n_pnb[tid];
+    }
+    __syncthreads();
+  }
+  if (tid < sh_ncur && sh_status == 0) {
+    p.node[tid] = s_node[tid];
+    p.pb[tid] = s_pb[tid];
+    p.pnb[tid] = s_pnb[tid];
+  }
+  if (tid == 0) {
+    p.hdr[H_STATUS] = sh_status;
+    if (sh_status == 0) {
+      p.hdr[H_FRAMES] += nf;
+      p.hdr[H_NCUR] = sh_ncur;
+      p.hdr[H_NNODES] = sh_nnodes;
+    }
+  }
+}
+
+// one wave per utterance; lane r < n_cur walks hypothesis r's trie path
+__global__ __launch_bounds__(64) void ctc_beam_nbest_kernel(BeamLayout L, int beam, int max_frames, const char* state,
+                                                            int32_t* __restrict__ hyp_tokens, int32_t* __restrict__ hyp_len,
+                                                            float* __restrict__ hyp_score, int32_t* __restrict__ n_hyps) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const BeamPtrs p = beam_ptrs(L, (char*)state, b);
+  const int status = p.hdr[H_STATUS];
+  const int n = status ? 0 : min(p.hdr[H_NCUR], beam);
+  int32_t* toks = hyp_tokens + (size_t)b * beam * max_frames;
+  int L_r = 0;
+  if (lane < beam) {
+    float score = -INFINITY;
+    if (lane < n) {
+      int nd = p.node[lane];
+      L_r = min(p.depth[nd], max_frames);
+      for (int i = L_r - 1; i >= 0 && nd > 0; --i) {
+        toks[(size_t)lane * max_frames + i] = p.token[nd];
+        nd = p.parent[nd];
+      }
+      score = (float)log_add2(p.pb[lane], p.pnb[lane]);
+    }
+    hyp_len[(size_t)b * beam + lane] = L_r;
+    hyp_score[(size_t)b * beam + lane] = score;
+  }
+  for (int r = 0; r < beam; ++r) {
+    const int Lr = __shfl(L_r, r, 64);
+    for (int i = Lr + lane; i < max_frames; i += 64) toks[(size_t)r * max_frames + i] = -1;
+  }
+  if (lane == 0) n_hyps[b] = status ? -1 : n;
+}
+
+// ---------------------------------------------------------------- streaming greedy search
+// state per stream: [status, frames, previous frame's argmax (-1 before the first frame), token count] + tokens[max_frames]
+enum { G_STATUS = 0, G_FRAMES = 1, G_PREV = 2, G_COUNT = 3, G_WORDS = 4 };
+
+size_t greedy_stride(int max_frames) { return align_up((size_t)(G_WORDS + max_frames) * 4, 256) / 4; }
+
+int check_greedy_desc(const m3_ctc_greedy_desc* d) {
+  M3_REQUIRE(d != nullptr, "ctc_greedy_stream: null descriptor");
+  M3_REQUIRE(d->B >= 0 && d->max_frames >= 0 && d->blank >= 0, "ctc_greedy_stream: bad descriptor B=%d max_frames=%d blank=%d",
+             d->B, d->max_frames, d->blank);
+  return 0;
+}
+
+__global__ __launch_bounds__(256) void ctc_greedy_stream_reset_kernel(int32_t* state, size_t stride, int B) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  int32_t* st = state + (size_t)b * stride;
+  st[G_STATUS] = 0;
+  st[G_FRAMES] = 0;
+  st[G_PREV] = -1;
+  st[G_COUNT] = 0;
+}
+
+// one wave per stream: ctc_collapse_kernel with the previous frame's id carried across calls
+__global__ __launch_bounds__(64) void ctc_greedy_stream_kernel(const int32_t* __restrict__ ids, int T_chunk,
+                                                               const int32_t* __restrict__ n_frames, int blank, int max_frames,
+                                                               int32_t* state, size_t stride) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  int32_t* st = state + (size_t)b * stride;
+  int32_t* out = st + G_WORDS;
+  const int nf = min(max(n_frames[b], 0), T_chunk);
+  const int status = st[G_STATUS], frames = st[G_FRAMES], prev = st[G_PREV];
+  int count = st[G_COUNT];
+  if (status != 0 || frames + nf > max_frames) {
+    if (lane == 0) st[G_STATUS] = status ? status : 1;
+    return;
+  }
+  const int32_t* row = ids + (size_t)b * T_chunk;
+  for (int t0 = 0; t0 < nf; t0 += 64) {
+    const int t = t0 + lane;
+    bool keep = false;
+    int id = blank;
+    if (t < nf) {
+      id = row[t];
+      keep = id != blank && id != (t == 0 ? prev : row[t - 1]);
+    }
+    const unsigned long long m = __ballot(keep);
+    if (keep) out[count + __popcll(m & ((1ull << lane) - 1ull))] = id;
+    count += __popcll(m);
+  }
+  if (lane == 0) {
+    st[G_FRAMES] = frames + nf;
+    if (nf > 0) st[G_PREV] = row[nf - 1];
+    st[G_COUNT] = count;
+  }
+}
+
+__global__ __launch_bounds__(64) void ctc_greedy_stream_tokens_kernel(const int32_t* state, size_t stride, int max_frames,
+                                                                      int32_t* __restrict__ tokens, int32_t* __restrict__ n_tokens) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int32_t* st = state + (size_t)b * stride;
+  const int status = st[G_STATUS];
+  const int count = status ? 0 : st[G_COUNT];
+  for (int i = lane; i < max_frames; i += 64) tokens[(size_t)b * max_frames + i] = i < count ? st[G_WORDS + i] : -1;
+  if (lane == 0) n_tokens[b] = status ? -1 : count;
+}
+
+}  // namespace
+
+size_t ctc_beam_state_size(const m3_ctc_beam_desc* d) {
+  if (check_beam_desc(d)) return 0;
+  return (size_t)d->B * beam_layout(d->beam, d->max_frames).stride;
+}
+
+int launch_ctc_beam_reset(const m3_ctc_beam_desc* d, void* state, size_t bytes, hipStream_t stream) {
+  if (int rc = check_beam_desc(d)) return rc;
+  const BeamLayout L = beam_layout(d->beam, d->max_frames);
+  M3_REQUIRE(state != nullptr && bytes >= (size_t)d->B * L.stride, "ctc_beam_reset: state %zu bytes < required %zu", bytes,
+             (size_t)d->B * L.stride);
+  if (d->B == 0) return 0;
+  const unsigned gx = (unsigned)std::min((L.hcap + 255) / 256, 64);
+  hipLaunchKernelGGL(ctc_beam_reset_kernel, dim3(gx, d->B), dim3(256), 0, stream, L, (char*)state);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_ctc_beam_advance(const m3_ctc_beam_desc* d, void* state, size_t bytes, const float* top_logp, const int32_t* top_idx,
+                            int T_chunk, const int32_t* n_frames, hipStream_t stream) {
+  if (int rc = check_beam_desc(d)) return rc;
+  const BeamLayout L = beam_layout(d->beam, d->max_frames);
+  M3_REQUIRE(state != nullptr && bytes >= (size_t)d->B * L.stride, "ctc_beam_advance: state %zu bytes < required %zu", bytes,
+             (size_t)d->B * L.stride);
+  M3_REQUIRE(T_chunk >= 0, "ctc_beam_advance: T_chunk = %d < 0", T_chunk);
+  if (d->B == 0 || T_chunk == 0) return 0;
+  M3_REQUIRE(top_logp && top_idx && n_frames, "ctc_beam_advance: null pointer");
+  hipLaunchKernelGGL(ctc_beam_advance_kernel, dim3(d->B), dim3(kBeamThreads), 0, stream, L, d->beam, d->k, d->blank,
+                     d->max_frames, (char*)state, top_logp, top_idx, T_chunk, n_frames);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_ctc_beam_nbest(const m3_ctc_beam_desc* d, const void* state, size_t bytes, int32_t* hyp_tokens, int32_t* hyp_len,
+                          float* hyp_score, int32_t* n_hyps, hipStream_t stream) {
+  if (int rc = check_beam_desc(d)) return rc;
+  const BeamLayout L = beam_layout(d->beam, d->max_frames);
+  M3_REQUIRE(state != nullptr && bytes >= (size_t)d->B * L.stride, "ctc_beam_nbest: state %zu bytes < required %zu", bytes,
+             (size_t)d->B * L.stride);
+  if (d->B == 0) return 0;
+  M3_REQUIRE(hyp_len && hyp_score && n_hyps && (hyp_tokens || d->max_frames == 0), "ctc_beam_nbest: null pointer");
+  hipLaunchKernelGGL(ctc_beam_nbest_kernel, dim3(d->B), dim3(64), 0, stream, L, d->beam, d->max_frames, (const char*)state,
+                     hyp_tokens, hyp_len, hyp_score, n_hyps);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+size_t ctc_greedy_stream_state_size(const m3_ctc_greedy_desc* d) {
+  if (check_greedy_desc(d)) return 0;
+  return (size_t)d->B * greedy_stride(d->max_frames) * 4;
+}
+
+int launch_ctc_greedy_stream_reset(const m3_ctc_greedy_desc* d, void* state, size_t bytes, hipStream_t stream) {
+  if (int rc = check_greedy_desc(d)) return rc;
+  const size_t stride = greedy_stride(d->max_frames);
+  M3_REQUIRE(state != nullptr && bytes >= (size_t)d->B * stride * 4, "ctc_greedy_stream_reset: state %zu bytes < required %zu",
+             bytes, (size_t)d->B * stride * 4);
+  if (d->B == 0) return 0;
+  hipLaunchKernelGGL(ctc_greedy_stream_reset_kernel, dim3((d->B + 255) / 256), dim3(256), 0, stream, (int32_t*)state, stride, d->B);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_ctc_greedy_stream_advance(const m3_ctc_greedy_desc* d, void* state, size_t bytes, const float* logits, int T_chunk,
+                                     int V, const int32_t* n_frames, int32_t* frame_ids, hipStream_t stream) {
+  if (int rc = check_greedy_desc(d)) return rc;
+  const size_t stride = greedy_stride(d->max_frames);
+  M3_REQUIRE(state != nullptr && bytes >= (size_t)d->B * stride * 4, "ctc_greedy_stream_advance: state %zu bytes < required %zu",
+             bytes, (size_t)d->B * stride * 4);
+  M3_REQUIRE(T_chunk >= 0 && V > 0, "ctc_greedy_stream_advance: bad shape T_chunk=%d V=%d", T_chunk, V);
+  if (d->B == 0 || T_chunk == 0) return 0;
+  M3_REQUIRE(logits && n_frames && frame_ids, "ctc_greedy_stream_advance: null pointer");
+  if (int rc = launch_ctc_argmax(logits, (size_t)d->B * T_chunk, V, frame_ids, stream)) return rc;
+  hipLaunchKernelGGL(ctc_greedy_stream_kernel, dim3(d->B), dim3(64), 0, stream, frame_ids, T_chunk, n_frames, d->blank,
+                     d->max_frames, (int32_t*)state, stride);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_ctc_greedy_stream_tokens(const m3_ctc_greedy_desc* d, const void* state, size_t bytes, int32_t* tokens,
+                                    int32_t* n_tokens, hipStream_t stream) {
+  if (int rc = check_greedy_desc(d)) return rc;
+  const size_t stride = greedy_stride(d->max_frames);
+  M3_REQUIRE(state != nullptr && bytes >= (size_t)d->B * stride * 4, "ctc_greedy_stream_tokens: state %zu bytes < required %zu",
+             bytes, (size_t)d->B * stride * 4);
+  if (d->B == 0) return 0;
+  M3_REQUIRE(n_tokens && (tokens || d->max_frames == 0), "ctc_greedy_stream_tokens: null pointer");
+  hipLaunchKernelGGL(ctc_greedy_stream_tokens_kernel, dim3(d->B), dim3(64), 0, stream, (const int32_t*)state, stride,
+                     d->max_frames, tokens, n_tokens);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace m3

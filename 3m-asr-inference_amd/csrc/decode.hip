@@ -98,6 +98,14 @@ int launch_ctc_greedy(const float* logits, const int32_t* len, int B, int T, int
   return 0;
 }
 
+int launch_ctc_argmax(const float* logits, size_t rows, int V, int32_t* ids, hipStream_t stream) {
+  M3_REQUIRE(V > 0, "ctc_argmax: V = %d", V);
+  if (rows == 0) return 0;
+  hipLaunchKernelGGL(ctc_argmax_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, logits, rows, V, ids);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
 // ---------------------------------------------------------------- per-frame log-softmax + top-k (first beam prune)
 // One wave per frame.  Selection order is (value desc, index asc); round r picks the best element strictly after the
 // previous pick in that order, so nothing is mutated and the row is only re-read (from L1/L2) k times.

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/m3asr.h"
+
 namespace m3 {
 
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2, ACT_GLU = 3 };
@@ -276,6 +278,20 @@ int launch_ctc_greedy(const float* logits, const int32_t* len, int B, int T, int
 int launch_ctc_topk(const float* logits, size_t rows, int V, int k, float* top_logp, int32_t* top_idx, hipStream_t stream);
 int ctc_prefix_beam_search_host(const float* top_logp, const int32_t* top_idx, int T, int k, int beam, int blank,
                                 int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score, int32_t* n_hyps);
+int launch_ctc_argmax(const float* logits, size_t rows, int V, int32_t* ids, hipStream_t stream);
+// ctc_beam.hip: batched resumable prefix beam search and the streaming greedy search on the device
+size_t ctc_beam_state_size(const m3_ctc_beam_desc* d);
+int launch_ctc_beam_reset(const m3_ctc_beam_desc* d, void* state, size_t bytes, hipStream_t stream);
+int launch_ctc_beam_advance(const m3_ctc_beam_desc* d, void* state, size_t bytes, const float* top_logp, const int32_t* top_idx,
+                            int T_chunk, const int32_t* n_frames, hipStream_t stream);
+int launch_ctc_beam_nbest(const m3_ctc_beam_desc* d, const void* state, size_t bytes, int32_t* hyp_tokens, int32_t* hyp_len,
+                          float* hyp_score, int32_t* n_hyps, hipStream_t stream);
+size_t ctc_greedy_stream_state_size(const m3_ctc_greedy_desc* d);
+int launch_ctc_greedy_stream_reset(const m3_ctc_greedy_desc* d, void* state, size_t bytes, hipStream_t stream);
+int launch_ctc_greedy_stream_advance(const m3_ctc_greedy_desc* d, void* state, size_t bytes, const float* logits, int T_chunk,
+                                     int V, const int32_t* n_frames, int32_t* frame_ids, hipStream_t stream);
+int launch_ctc_greedy_stream_tokens(const m3_ctc_greedy_desc* d, const void* state, size_t bytes, int32_t* tokens,
+                                    int32_t* n_tokens, hipStream_t stream);
 int launch_cat_split_cache(const void* in_cache, const void* input, int B, int cache_dim, int input_dim, void* output,
                            void* out_cache, hipStream_t stream);
 int launch_att_stream_softmax(const float* scores, const int32_t* decode_frame_num, const int32_t* mask_idx, int B, int N,

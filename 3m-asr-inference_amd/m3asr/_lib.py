@@ -53,6 +53,14 @@ class StreamDesc(C.Structure):  # m3_stream_desc
     _fields_ = [("B", C.c_int32), ("history_frames", C.c_int32), ("max_frames", C.c_int32)]
 
 
+class CtcBeamDesc(C.Structure):  # m3_ctc_beam_desc
+    _fields_ = [("B", C.c_int32), ("beam", C.c_int32), ("k", C.c_int32), ("max_frames", C.c_int32), ("blank", C.c_int32)]
+
+
+class CtcGreedyDesc(C.Structure):  # m3_ctc_greedy_desc
+    _fields_ = [("B", C.c_int32), ("max_frames", C.c_int32), ("blank", C.c_int32)]
+
+
 class WeightEntry(C.Structure):  # m3_weight_entry
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64), ("dtype", C.c_int32)]
 
@@ -128,6 +136,14 @@ SIGNATURES = {
     "m3_ctc_greedy": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "m3_ctc_topk": (_i, [_vp, _sz, _i, _i, _vp, _vp, _vp]),
     "m3_ctc_prefix_beam_search": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "m3_ctc_beam_state_size": (_sz, [_P(CtcBeamDesc)]),
+    "m3_ctc_beam_reset": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp]),
+    "m3_ctc_beam_advance": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp, _vp, _i, _vp, _vp]),
+    "m3_ctc_beam_nbest": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "m3_ctc_greedy_stream_state_size": (_sz, [_P(CtcGreedyDesc)]),
+    "m3_ctc_greedy_stream_reset": (_i, [_P(CtcGreedyDesc), _vp, _sz, _vp]),
+    "m3_ctc_greedy_stream_advance": (_i, [_P(CtcGreedyDesc), _vp, _sz, _vp, _i, _i, _vp, _vp, _vp]),
+    "m3_ctc_greedy_stream_tokens": (_i, [_P(CtcGreedyDesc), _vp, _sz, _vp, _vp, _vp]),
     "m3_cat_split_cache": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "m3_att_stream_softmax": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
     "m3_rel_positional_encoding": (_i, [_vp, _vp, _i, _vp, _i, _f, _i, _i, _i, _vp, _vp, _vp, _vp]),

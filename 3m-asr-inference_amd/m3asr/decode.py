@@ -6,6 +6,13 @@ and return types), running on the device through libm3asr_hip.so:
                 lists (B x T' int32 + counts) are copied back.
   prefix beam   per-frame log-softmax + top-`beam` on the GPU (m3_ctc_topk), T' x beam pairs copied back, the prefix
                 recursion in the library's host routine (m3_ctc_prefix_beam_search).
+  batched beam  B utterances in one device search (m3_ctc_topk + m3_ctc_beam_advance + m3_ctc_beam_nbest): CtcBeamSearch,
+                CtcDecoder.batch_prefix_beam_search; resumable chunk by chunk, which StreamingCtcDecoder uses on top of the
+                chunk-by-chunk engine (with the streaming greedy search, m3_ctc_greedy_stream_*).
+
+Chunked decoding (decoding_chunk_size > 0) is accepted when the engine was built for exactly that chunk mask
+(cfg.static_chunk_size == decoding_chunk_size, same num_decoding_left_chunks): its ordinary forward is then the reference's
+chunk-masked forward (encoder.py:100-140).
 
 There is no CPU fallback: without the HIP library every call raises.
 """
@@ -13,7 +20,70 @@ from typing import List, Tuple
 
 import torch
 
-from . import ops
+from . import _lib, ops
+from .config import subsampled_len
+
+
+class CtcBeamSearch:
+    """B prefix beam searches on the device, resumable at any frame boundary (m3_ctc_beam_*).
+
+        search = CtcBeamSearch(B, beam, max_frames)
+        search.advance(logits_chunk, n_frames)      # (B, Tc, V) device logits, (B,) frames of each row that count
+        ...
+        search.nbest()                              # [[(prefix tuple, score)], ...] per utterance, best first
+
+    The result equals the host routine (ops.ctc_prefix_beam_search_host) on each utterance's frames, however the frames are
+    cut into chunks.  max_frames bounds the frames one utterance may consume between resets; past it nbest() raises."""
+
+    def __init__(self, B, beam, max_frames, blank=0, device="cuda", k=None):
+        """k: candidate symbols per frame (default beam, as the reference's logp.topk(beam_size)); needs k <= V."""
+        self.desc = ops.ctc_beam_desc(B, beam, max_frames, blank, k)
+        self.device = torch.device(device)
+        n = ops.ctc_beam_state_size(self.desc)
+        self.state = torch.empty(max(n, 1), dtype=torch.uint8, device=self.device)
+        self.reset()
+
+    @property
+    def B(self):
+        return self.desc.B
+
+    @property
+    def beam(self):
+        return self.desc.beam
+
+    def reset(self, stream=None):
+        with torch.cuda.stream(stream or torch.cuda.current_stream(self.device)):
+            ops.ctc_beam_reset(self.desc, self.state)
+
+    def advance(self, logits, n_frames, stream=None):
+        """logits (B, Tc, V) on the device; n_frames (B,) how many of each row's Tc frames are real.  Enqueues m3_ctc_topk and
+        the advance on `stream` (default: the current stream) without a host sync."""
+        st = stream or torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(st):
+            B, Tc, V = logits.shape
+            assert B == self.B
+            if Tc == 0:
+                return
+            nf = n_frames.reshape(-1).to(self.device, torch.int32, non_blocking=True)
+            top_logp, top_idx = ops.ctc_topk(logits.contiguous(), self.desc.k)
+            ops.ctc_beam_advance(self.desc, self.state, top_logp, top_idx, nf)
+
+    def nbest_tensors(self, stream=None):
+        """(hyp_tokens (B,beam,max_frames), hyp_len (B,beam), hyp_score (B,beam), n_hyps (B,)) on the device."""
+        with torch.cuda.stream(stream or torch.cuda.current_stream(self.device)):
+            return ops.ctc_beam_nbest(self.desc, self.state)
+
+    def nbest(self, stream=None):
+        with torch.cuda.stream(stream or torch.cuda.current_stream(self.device)):   # the copies wait for the search's stream
+            toks, hlen, score, n = (t.cpu() for t in ops.ctc_beam_nbest(self.desc, self.state))
+        out = []
+        for b in range(self.B):
+            nb = int(n[b])
+            if nb < 0:
+                raise _lib.M3Error("ctc beam search: utterance %d consumed more than max_frames = %d frames"
+                                   % (b, self.desc.max_frames))
+            out.append([(tuple(toks[b, i, :int(hlen[b, i])].tolist()), float(score[b, i])) for i in range(nb)])
+        return out
 
 
 class CtcDecoder:
@@ -32,13 +102,19 @@ class CtcDecoder:
         out_lens = self.engine.buffer("lens", torch.int32)[:feat.shape[0]].clone()
         return {"out_nosm": logits, "out_lens": out_lens}
 
-    @staticmethod
-    def _full_context(decoding_chunk_size, num_decoding_left_chunks):
-        # the Conformer-MoE encoder is full-context (non-causal conv, unmasked attention): only the reference's
-        # "use full chunk" setting (< 0) describes what the engine computes
+    def _full_context(self, decoding_chunk_size, num_decoding_left_chunks):
+        # the engine computes one attention mask, fixed when it was built: the reference's "use full chunk" setting (< 0)
+        # describes a full-context engine, a chunk size > 0 only an engine built with that static chunk mask
         assert decoding_chunk_size != 0, "decoding does not support dynamic chunks"
         if decoding_chunk_size > 0:
-            raise NotImplementedError("chunked decoding: the full-context encoder has no chunk mask")
+            cfg = getattr(self.engine, "cfg", None)
+            chunk = int(getattr(cfg, "static_chunk_size", 0) or 0)
+            left = int(getattr(cfg, "num_decoding_left_chunks", -1))
+            if chunk <= 0:
+                raise NotImplementedError("chunked decoding: the full-context encoder has no chunk mask")
+            if decoding_chunk_size != chunk or num_decoding_left_chunks != left:
+                raise NotImplementedError("chunked decoding: the engine was built for chunk %d / %d left chunks, asked for %d / %d"
+                                          % (chunk, left, decoding_chunk_size, num_decoding_left_chunks))
 
     def ctc_greedy_search(self, xs: torch.Tensor, xs_lens: torch.Tensor, decoding_chunk_size: int = -1,
                           num_decoding_left_chunks: int = -1) -> List[List[int]]:
@@ -67,3 +143,109 @@ class CtcDecoder:
         x = logits.reshape(-1, logits.shape[-1])
         top_logp, top_idx = ops.ctc_topk(x, beam_size)
         return ops.ctc_prefix_beam_search_host(top_logp.cpu().numpy(), top_idx.cpu().numpy(), beam_size, self.blank_idx)
+
+    def batch_prefix_beam_search(self, xs: torch.Tensor, xs_lens: torch.Tensor, beam_size: int,
+                                 decoding_chunk_size: int = -1, num_decoding_left_chunks: int = -1
+                                 ) -> Tuple[List[List[Tuple[Tuple[int, ...], float]]], torch.Tensor]:
+        """B utterances in one device search: -> ([n-best [(prefix, ctc score)] per utterance], logits (B,T',V))."""
+        self._full_context(decoding_chunk_size, num_decoding_left_chunks)
+        res = self.forward(xs, xs_lens)
+        return self.batch_prefix_beam_from_logits(res["out_nosm"], res["out_lens"], beam_size), res["out_nosm"]
+
+    def batch_prefix_beam_from_logits(self, logits: torch.Tensor, lens: torch.Tensor, beam_size: int):
+        """logits (B,T',V) on the device, lens (B,) valid frames per utterance -> n-best per utterance (device search)."""
+        B, T = int(logits.shape[0]), int(logits.shape[1])
+        search = CtcBeamSearch(B, beam_size, T, self.blank_idx, logits.device)
+        search.advance(logits, lens)
+        return search.nbest()
+
+
+class StreamingCtcDecoder:
+    """CTC decoding chunk by chunk on top of a StreamingEncoder: every step() runs the chunk forward, then log-softmax +
+    top-k, the prefix beam search advance and the streaming greedy search, all on the engine's stream; partial() reads the
+    current best hypotheses, finish() the n-best.
+
+        dec = StreamingCtcDecoder(engine.streaming(B, max_frames), beam=10)
+        for n in range(n_chunks):
+            dec.step(window_n, valid_n)
+            best, greedy = dec.partial()
+        nbest = dec.finish()
+
+    The output frames of a chunk that count for a stream follow StreamingEncoder.decode: frames t < T'(len) of an utterance of
+    len >= 7 feature frames.  step() derives them from `valid` (min(T'(valid), c), 0 for valid < 7); a caller that knows
+    the utterance lengths passes them as n_out (decode() does)."""
+
+    def __init__(self, streaming_encoder, beam, blank=0):
+        self.st = streaming_encoder
+        e = streaming_encoder.eng
+        self.c = streaming_encoder.c
+        B, max_frames = int(streaming_encoder.desc.B), int(streaming_encoder.desc.max_frames)
+        self.beam = CtcBeamSearch(B, beam, max_frames, blank, e.device)
+        self.gdesc = ops.ctc_greedy_stream_desc(B, max_frames, blank)
+        self.gstate = torch.empty(max(ops.ctc_greedy_stream_state_size(self.gdesc), 1), dtype=torch.uint8, device=e.device)
+        self.frame_ids = torch.empty(B, self.c, dtype=torch.int32, device=e.device)
+        self.n_out = torch.zeros(B, dtype=torch.int32, device=e.device)
+        self.reset()
+
+    def reset(self):
+        e = self.st.eng
+        self.st.reset()
+        with torch.cuda.stream(e.stream):
+            self.beam.reset(e.stream)
+            ops.ctc_greedy_stream_reset(self.gdesc, self.gstate)
+
+    def frames_of(self, valid):
+        """Output frames of this chunk that count, from the real feature frames in its window."""
+        v = torch.as_tensor(valid).reshape(-1).to("cpu", torch.int64)
+        return torch.tensor([min(subsampled_len(int(x)), self.c) if x >= 7 else 0 for x in v], dtype=torch.int32)
+
+    def step(self, window, valid, n_out=None, use_graph=True):
+        """One chunk: window (B, 4c+3, idim), valid (B,) as for StreamingEncoder.step; n_out (B,) output frames of this chunk
+        that count (default: frames_of(valid)).  Returns the chunk's logits buffer (B, c, V)."""
+        e = self.st.eng
+        if n_out is None:
+            n_out = self.frames_of(valid)
+        logits = self.st.step(window, valid, use_graph=use_graph)
+        with torch.cuda.stream(e.stream):
+            self.n_out.copy_(torch.as_tensor(n_out).reshape(-1).to(torch.int32), non_blocking=True)
+            self.beam.advance(logits, self.n_out, e.stream)
+            ops.ctc_greedy_stream_advance(self.gdesc, self.gstate, logits, self.n_out, self.frame_ids)
+        return logits
+
+    def greedy(self):
+        """Greedy hypotheses of the frames so far: [[token, ...]] per stream."""
+        e = self.st.eng
+        with torch.cuda.stream(e.stream):
+            toks, n = ops.ctc_greedy_stream_tokens(self.gdesc, self.gstate)
+        e.stream.synchronize()
+        toks, n = toks.cpu(), n.cpu().tolist()
+        if min(n, default=0) < 0:
+            raise _lib.M3Error("streaming greedy search: a stream ran past max_frames")
+        return [toks[b, :k].tolist() for b, k in enumerate(n)]
+
+    def partial(self):
+        """(best prefix beam hypothesis (prefix, score) per stream, greedy tokens per stream) after the chunks so far."""
+        e = self.st.eng
+        nb = self.beam.nbest(e.stream)
+        return [h[0] for h in nb], self.greedy()
+
+    def finish(self):
+        """n-best [(prefix, score)] per stream, best first."""
+        return self.beam.nbest(self.st.eng.stream)
+
+    def decode(self, feat, feat_len, use_graph=True):
+        """Whole utterances chunk by chunk (the windows and frame counts of StreamingEncoder.decode) -> finish()."""
+        c, st = self.c, self.st
+        B, T = int(feat.shape[0]), int(feat.shape[1])
+        lens = feat_len.reshape(-1).to("cpu", torch.int64)
+        n_chunks = -(-subsampled_len(T) // c)
+        total = torch.tensor([subsampled_len(int(v)) if v >= 7 else 0 for v in lens], dtype=torch.int64)
+        self.reset()
+        st.eng.stream.wait_stream(torch.cuda.current_stream())
+        padded = torch.zeros(B, max(T, 4 * c * n_chunks + 3), feat.shape[2], dtype=torch.float32, device=st.eng.device)
+        padded[:, :T] = feat.to(st.eng.device)
+        for n in range(n_chunks):
+            left = (lens - 4 * c * n).clamp(min=0, max=st.window)
+            left = torch.where(left >= 7, left, torch.zeros_like(left))
+            self.step(padded[:, 4 * c * n: 4 * c * n + st.window], left, (total - n * c).clamp(min=0, max=c), use_graph)
+        return self.finish()

@@ -369,6 +369,86 @@ def ctc_prefix_beam_search_host(top_logp, top_idx, beam, blank=0):
     return [(tuple(int(v) for v in toks[i, :hlen[i]]), float(score[i])) for i in range(n.value)]
 
 
+def ctc_beam_desc(B, beam, max_frames, blank=0, k=None):
+    """m3_ctc_beam_desc for B utterances (k = beam unless given); raises M3Error on sizes the device search rejects."""
+    d = _lib.CtcBeamDesc(int(B), int(beam), int(beam if k is None else k), int(max_frames), int(blank))
+    one = _lib.CtcBeamDesc(1, d.beam, d.k, d.max_frames, d.blank)      # B = 0 is a valid (empty) size
+    if _lib.load().m3_ctc_beam_state_size(C.byref(one)) == 0:
+        raise _lib.M3Error("m3_ctc_beam_state_size failed: " + _lib.last_error())
+    return d
+
+
+def ctc_beam_state_size(desc):
+    """bytes of device state for desc (host-only call); M3Error on a bad descriptor."""
+    n = _lib.load().m3_ctc_beam_state_size(C.byref(desc))
+    if n == 0 and desc.B > 0:
+        raise _lib.M3Error("m3_ctc_beam_state_size failed: " + _lib.last_error())
+    return n
+
+
+def ctc_beam_reset(desc, state):
+    check(_lib.load().m3_ctc_beam_reset(C.byref(desc), _p(state), state.numel() * state.element_size(), _stream()),
+          "m3_ctc_beam_reset")
+
+
+def ctc_beam_advance(desc, state, top_logp, top_idx, n_frames):
+    """top_logp / top_idx (B, T_chunk, k) from ctc_topk, n_frames (B,) int32 on the device: enqueue, no host sync."""
+    B, Tc, k = top_logp.shape
+    assert B == desc.B and k == desc.k and tuple(top_idx.shape) == (B, Tc, k) and n_frames.numel() == B
+    check(_lib.load().m3_ctc_beam_advance(C.byref(desc), _p(state), state.numel() * state.element_size(), _f32(top_logp),
+                                          _i32(top_idx), Tc, _i32(n_frames), _stream()), "m3_ctc_beam_advance")
+
+
+def ctc_beam_nbest(desc, state):
+    """-> (hyp_tokens (B,beam,max_frames) -1 padded, hyp_len (B,beam), hyp_score (B,beam), n_hyps (B,) -1 = failed), device."""
+    dev = state.device
+    B, beam, F = desc.B, desc.beam, desc.max_frames
+    toks = torch.empty(B, beam, F, dtype=torch.int32, device=dev)
+    hlen = torch.empty(B, beam, dtype=torch.int32, device=dev)
+    score = torch.empty(B, beam, dtype=torch.float32, device=dev)
+    n = torch.empty(B, dtype=torch.int32, device=dev)
+    check(_lib.load().m3_ctc_beam_nbest(C.byref(desc), _p(state), state.numel() * state.element_size(), _p(toks), _p(hlen),
+                                        _p(score), _p(n), _stream()), "m3_ctc_beam_nbest")
+    return toks, hlen, score, n
+
+
+def ctc_greedy_stream_desc(B, max_frames, blank=0):
+    d = _lib.CtcGreedyDesc(int(B), int(max_frames), int(blank))
+    if _lib.load().m3_ctc_greedy_stream_state_size(C.byref(_lib.CtcGreedyDesc(1, d.max_frames, d.blank))) == 0:
+        raise _lib.M3Error("m3_ctc_greedy_stream_state_size failed: " + _lib.last_error())
+    return d
+
+
+def ctc_greedy_stream_state_size(desc):
+    return _lib.load().m3_ctc_greedy_stream_state_size(C.byref(desc))
+
+
+def ctc_greedy_stream_reset(desc, state):
+    check(_lib.load().m3_ctc_greedy_stream_reset(C.byref(desc), _p(state), state.numel() * state.element_size(), _stream()),
+          "m3_ctc_greedy_stream_reset")
+
+
+def ctc_greedy_stream_advance(desc, state, logits, n_frames, frame_ids=None):
+    """logits (B, T_chunk, V) f32, n_frames (B,) int32 on the device; frame_ids: optional (B, T_chunk) int32 scratch."""
+    B, Tc, V = logits.shape
+    assert B == desc.B and n_frames.numel() == B
+    if frame_ids is None:
+        frame_ids = torch.empty(B, Tc, dtype=torch.int32, device=logits.device)
+    check(_lib.load().m3_ctc_greedy_stream_advance(C.byref(desc), _p(state), state.numel() * state.element_size(), _f32(logits),
+                                                   Tc, V, _i32(n_frames), _i32(frame_ids), _stream()),
+          "m3_ctc_greedy_stream_advance")
+    return frame_ids
+
+
+def ctc_greedy_stream_tokens(desc, state):
+    """-> (tokens (B, max_frames) -1 padded, n_tokens (B,) -1 = failed), device int32."""
+    tokens = torch.empty(desc.B, desc.max_frames, dtype=torch.int32, device=state.device)
+    n = torch.empty(desc.B, dtype=torch.int32, device=state.device)
+    check(_lib.load().m3_ctc_greedy_stream_tokens(C.byref(desc), _p(state), state.numel() * state.element_size(), _p(tokens),
+                                                  _p(n), _stream()), "m3_ctc_greedy_stream_tokens")
+    return tokens, n
+
+
 # ---------------------------------------------------------------------------------------- streaming operators
 def cat_split_cache(in_cache, inp):
     """CatSplitCache plugin: (output (B, cache+input), out_cache (B, cache)); f32 or i32 rows."""

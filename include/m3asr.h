@@ -305,6 +305,49 @@ int m3_ctc_topk(const float* logits, size_t rows, int V, int k, float* top_logp,
  * hyp_len [beam], hyp_score [beam] = log(p_blank + p_non_blank), *n_hyps. */
 int m3_ctc_prefix_beam_search(const float* top_logp, const int32_t* top_idx, int T, int k, int beam, int blank,
                               int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score, int32_t* n_hyps);
+/* The same search on the DEVICE, for B utterances at once and resumable at any frame boundary (csrc/ctc_beam.hip).  The
+ * result equals m3_ctc_prefix_beam_search on each utterance's frames: same prefixes in the same order, scores from the same
+ * double-precision recursion.  One work-group per utterance; the search state (beam, prefix trie, canonical-node hash
+ * table) lives in caller-owned device memory of m3_ctc_beam_state_size bytes.  Limits: 1 <= beam <= 32, 1 <= k <= 32
+ * (the reference uses k = beam); max_frames bounds the frames one search may consume over its lifetime.
+ * m3_ctc_beam_state_size: host-only; 0 (and m3_last_error) on a bad descriptor.
+ * m3_ctc_beam_reset: every utterance back to the empty prefix (pb = 0, pnb = -inf), no frame consumed.
+ * m3_ctc_beam_advance: top_logp / top_idx [B][T_chunk][k] (m3_ctc_topk's output), n_frames [B] (device) = how many of
+ *   utterance b's T_chunk rows are real (clamped to [0, T_chunk]; the rest is padding).  All frames run in one launch, no
+ *   host sync.  An advance that would take an utterance past max_frames consumes nothing and marks it failed (nothing is
+ *   written outside the state); the failure is sticky until the next reset.
+ * m3_ctc_beam_nbest: hyp_tokens [B][beam][max_frames] (-1 padded), hyp_len [B][beam], hyp_score [B][beam] =
+ *   log(p_blank + p_non_blank) (-inf for unused rows), n_hyps [B] (-1 for a failed utterance); best first.  All device. */
+typedef struct m3_ctc_beam_desc {
+  int32_t B;
+  int32_t beam;
+  int32_t k;
+  int32_t max_frames;
+  int32_t blank;
+} m3_ctc_beam_desc;
+size_t m3_ctc_beam_state_size(const m3_ctc_beam_desc* desc);
+int m3_ctc_beam_reset(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, m3_stream stream);
+int m3_ctc_beam_advance(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const float* top_logp,
+                        const int32_t* top_idx, int T_chunk, const int32_t* n_frames, m3_stream stream);
+int m3_ctc_beam_nbest(const m3_ctc_beam_desc* desc, const void* state, size_t state_bytes, int32_t* hyp_tokens,
+                      int32_t* hyp_len, float* hyp_score, int32_t* n_hyps, m3_stream stream);
+/* Greedy search chunk by chunk: per stream the previous frame's argmax is carried across calls and the collapsed tokens are
+ * appended to a buffer inside the state (m3_ctc_greedy_stream_state_size bytes, device).  After any sequence of advances the
+ * tokens equal m3_ctc_greedy on the concatenation of the frames each stream was given.
+ * m3_ctc_greedy_stream_advance: logits [B][T_chunk][V], n_frames [B] (device) real rows per stream, frame_ids [B*T_chunk]
+ *   device scratch (receives the per-frame argmax).  Past max_frames the stream consumes nothing and is marked failed.
+ * m3_ctc_greedy_stream_tokens: tokens [B][max_frames] (-1 padded), n_tokens [B] (-1 for a failed stream).  All device. */
+typedef struct m3_ctc_greedy_desc {
+  int32_t B;
+  int32_t max_frames;
+  int32_t blank;
+} m3_ctc_greedy_desc;
+size_t m3_ctc_greedy_stream_state_size(const m3_ctc_greedy_desc* desc);
+int m3_ctc_greedy_stream_reset(const m3_ctc_greedy_desc* desc, void* state, size_t state_bytes, m3_stream stream);
+int m3_ctc_greedy_stream_advance(const m3_ctc_greedy_desc* desc, void* state, size_t state_bytes, const float* logits,
+                                 int T_chunk, int V, const int32_t* n_frames, int32_t* frame_ids, m3_stream stream);
+int m3_ctc_greedy_stream_tokens(const m3_ctc_greedy_desc* desc, const void* state, size_t state_bytes, int32_t* tokens,
+                                int32_t* n_tokens, m3_stream stream);
 
 /* Streaming operators of the reference's plugin library (built there but not registered, trt_plugin_plus.cpp:155-156).
  * CatSplitCachePluginDynamic (cat_split_cache_kernel.cu:30-107), 4-byte elements: output [B][cache_dim+input_dim] =

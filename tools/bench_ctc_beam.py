@@ -1,0 +1,75 @@
+#!/usr/bin/env python3
+"""The device prefix beam search (m3_ctc_beam_advance) against the host routine (m3_ctc_prefix_beam_search) on a configs[2]-like
+batch: B = 16 utterances of T' = 125 output frames, V = 1434, beam = k = 10, synthetic logits.
+
+  python tools/bench_ctc_beam.py [--batch 16] [--frames 125] [--beam 10] [--chunk 16] [--reps 5]
+
+Device: one advance over all frames, and the same frames in chunks of --chunk (one advance per chunk), timed with hipEvents
+(top-k excluded: it is the same launch for both searches); run under `rocprofv3 --kernel-trace --stats` for kernel times.
+Host: the 16 host searches one after another (what CtcDecoder.ctc_prefix_beam_search does per utterance), wall time, with
+the device top-k and the copy of its pairs excluded.  Prints one JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "3m-asr-inference_amd"))
+import numpy as np
+import torch
+
+from m3asr import ops
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--frames", type=int, default=125)
+    ap.add_argument("--vocab", type=int, default=1434)
+    ap.add_argument("--beam", type=int, default=10)
+    ap.add_argument("--chunk", type=int, default=16)
+    ap.add_argument("--reps", type=int, default=5)
+    args = ap.parse_args()
+    B, T, V, beam = args.batch, args.frames, args.vocab, args.beam
+    g = torch.Generator().manual_seed(0)
+    x = (torch.randn(B, T, V, generator=g) * 2.5).cuda()
+    lp, ix = ops.ctc_topk(x, beam)
+    nf = torch.full((B,), T, dtype=torch.int32, device="cuda")
+    desc = ops.ctc_beam_desc(B, beam, T, 0)
+    state = torch.empty(ops.ctc_beam_state_size(desc), dtype=torch.uint8, device="cuda")
+    chunks = [(t0, min(args.chunk, T - t0)) for t0 in range(0, T, args.chunk)]
+    nfc = [torch.full((B,), c, dtype=torch.int32, device="cuda") for _, c in chunks]
+    lpc = [(lp[:, t0:t0 + c].contiguous(), ix[:, t0:t0 + c].contiguous()) for t0, c in chunks]
+
+    def timed(fn):
+        ts = []
+        for _ in range(args.reps + 1):
+            ops.ctc_beam_reset(desc, state)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return float(np.median(ts[1:]))
+
+    one = timed(lambda: ops.ctc_beam_advance(desc, state, lp, ix, nf))
+    per = timed(lambda: [ops.ctc_beam_advance(desc, state, a, b, n) for (a, b), n in zip(lpc, nfc)])
+    lph, ixh = lp.cpu().numpy(), ix.cpu().numpy()
+    hs = []
+    for _ in range(args.reps):
+        t0 = time.perf_counter()
+        for b in range(B):
+            ops.ctc_prefix_beam_search_host(lph[b], ixh[b], beam, 0)
+        hs.append((time.perf_counter() - t0) * 1e3)
+    print(json.dumps({"metric": "CTC prefix beam search, B %d x T' %d, V %d, beam = k = %d" % (B, T, V, beam),
+                      "device_one_advance_ms": round(one, 4),
+                      "device_chunked_ms": {"chunk": args.chunk, "advances": len(chunks), "total": round(per, 4),
+                                            "per_advance": round(per / len(chunks), 4)},
+                      "host_routine_ms": round(float(np.median(hs)), 4), "data": "synthetic"}))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """Chunk-by-chunk decoding (m3_engine_forward_chunk) timed: latency of one chunk step and the real-time factor it implies.
 
-  python tools/bench_streaming.py [--chunk 16] [--left-chunks 4] [--batch 1] [--weight-dtype f32] [--seconds 20]
+  python tools/bench_streaming.py [--chunk 16] [--left-chunks 4] [--batch 1] [--weight-dtype f32] [--seconds 20] [--beam N]
 
 18L x 32e encoder with causal conv modules in both encoders, static_chunk_size = chunk (output frames; one chunk = 4 x chunk
 input frames of 10 ms), synthetic weights and features.  Every step after the first is a hipGraph replay (the chunk counter
 lives on the device).  Prints one JSON line: ms per chunk (p50 / p99 over all steps, hipEvent pairs on the engine stream),
 audio seconds per chunk, real-time factor = compute time / audio time, streams one GPU could serve in real time.
+--beam N (> 0): also time the CTC decode of every chunk (StreamingCtcDecoder: top-k + prefix beam advance + streaming greedy,
+on the engine stream behind the chunk forward) and add "decode_ms_per_chunk" to the line.
 """
 import argparse
 import json
@@ -19,6 +21,7 @@ sys.path.insert(0, os.path.join(ROOT, "3m-asr-inference_amd"))
 import numpy as np
 import torch
 
+from m3asr import ops
 from m3asr.config import EncoderConfig
 from m3asr.engine import Engine
 from m3asr.weights import make_weights
@@ -32,6 +35,7 @@ def main():
     ap.add_argument("--weight-dtype", default="f32")
     ap.add_argument("--layers", type=int, default=18)
     ap.add_argument("--seconds", type=float, default=20.0, help="audio per stream")
+    ap.add_argument("--beam", type=int, default=0, help="> 0: decode every chunk with a prefix beam search of this width")
     args = ap.parse_args()
     cfg = EncoderConfig(num_blocks=args.layers, causal=True, embed_causal=True, static_chunk_size=args.chunk,
                         num_decoding_left_chunks=args.left_chunks, weight_dtype=args.weight_dtype)
@@ -42,17 +46,31 @@ def main():
     rng = np.random.default_rng(1234)
     win = torch.from_numpy(rng.random((args.batch, st.window, cfg.input_dim), dtype=np.float32)).to(eng.device)
     valid = torch.full((args.batch,), st.window, dtype=torch.int32, device=eng.device)
-    times = []
+    dec = None
+    if args.beam > 0:
+        from m3asr.decode import StreamingCtcDecoder
+        dec = StreamingCtcDecoder(st, args.beam)
+        n_out = torch.full((args.batch,), args.chunk, dtype=torch.int32, device=eng.device)
+    times, dtimes = [], []
     for rep in range(3):
-        st.reset()
+        if dec is not None:
+            dec.reset()
+        else:
+            st.reset()
         for n in range(n_chunks):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
             e0.record(eng.stream)
             st.step(win, valid)
             e1.record(eng.stream)
-            e1.synchronize()
+            if dec is not None:
+                with torch.cuda.stream(eng.stream):
+                    dec.beam.advance(st.logits, n_out, eng.stream)
+                    ops.ctc_greedy_stream_advance(dec.gdesc, dec.gstate, st.logits, n_out, dec.frame_ids)
+            e2.record(eng.stream)
+            e2.synchronize()
             if rep > 0:
                 times.append(e0.elapsed_time(e1))
+                dtimes.append(e1.elapsed_time(e2))
     t = np.sort(np.array(times))
     audio_s = 4 * args.chunk * 0.01
     p50 = float(np.median(t))
@@ -63,6 +81,10 @@ def main():
            "real_time_factor": round(p50 * 1e-3 / audio_s, 5),
            "streams_in_real_time_one_context": int(args.batch * audio_s / (p50 * 1e-3)),
            "state_MB": round(st.state.numel() / 2 ** 20, 1), "graph_captures": eng.num_captures(), "data": "synthetic"}
+    if dec is not None:
+        d = np.sort(np.array(dtimes))
+        out["decode_ms_per_chunk"] = {"beam": args.beam, "p50": round(float(np.median(d)), 4),
+                                      "p99": round(float(d[int(0.99 * (len(d) - 1))]), 4), "min": round(float(d[0]), 4)}
     print(json.dumps(out))
 
 
