@@ -10,6 +10,7 @@
 // once per (shape, buffers) into a hipGraph and replayed.  The residual stream x (S x D) is updated in
 // place by GEMM / combine epilogues; LayerNorms ride in GEMM prologues except where their output is a
 // tensor of its own (MoE input, block output).
+#include <assert.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -53,16 +54,19 @@ struct BlockW {
 
 struct SubW { const float* c1w; const float* c1b; const float* c2w; const float* c2b; Lin out; };
 
+// what horizontal fusion pairs up (fuse_independent_pairs): a plain launch_gemm_f32 stage (Stage::gemm), the conv module's
+// depthwise conv + LayerNorm + SiLU (Stage::dw), the fp32 rel-pos attention core (Stage::att)
+enum class FuseKind { None, Gemm, Dwconv, Attention };
+
 struct Stage {
   std::string name;
   std::function<int(hipStream_t)> run;
   m3_stage_info info;   // kernel label + algorithmic bytes / FLOPs of the stage (m3_engine_stage_info)
-  // what horizontal fusion pairs up (fuse_independent_pairs): 1 = a plain launch_gemm_f32 stage (`gemm`), 2 = the conv module's
-  // depthwise conv + LayerNorm + SiLU (`dw`)
-  int fuse_kind = 0;
+  bool reads_embed = false;   // reads the embed encoder's output (pl.emb, or pl.eall computed from it): where the chains join
+  FuseKind fuse_kind = FuseKind::None;
   GemmParams gemm;
   DwArgs dw;
-  AttArgs att;          // 3 = the fp32 rel-pos attention core
+  AttArgs att;
 };
 
 m3_stage_info stage_info(const char* kernel, int launches, double bytes, double flops, bool per_row = true) {
@@ -110,7 +114,7 @@ struct m3_engine {
     // K / V history and the causal depthwise conv its K-1 frame cache, both in the caller-owned state (m3_engine_forward_chunk)
     void* sstate = nullptr; int s_hist = 0, s_maxf = 0;
     // fork_embed: stages [fork_first, fork_mid) = the embed encoder (side branch of the captured graph), [fork_mid, join_at) =
-    // what the main encoder does before it needs the embedding; -1 = one linear chain
+    // what the main encoder does before it needs the embedding (embed_join); -1 = one linear chain
     int fork_first = -1, fork_mid = -1, join_at = -1;
     // fold_pos_proj: linear_pos(pe[:T']) of every block, computed once per T'.  ENGINE-owned device memory (shared by all
     // bindings of the same T', freed with the last of them): a caller that reuses one workspace for several shapes, as a
@@ -140,18 +144,49 @@ struct m3_engine {
 
 namespace {
 
-// rows up to which SoftmaxTopK + ScatterMapping run as ONE single-work-group launch (beyond: row-parallel top-1 + index kernel).
-// M3_GATE_INDEX_MAX_ROWS overrides (read once).  A/B at configs[2] (1984 padded rows): 2048 -> 315 instead of 333 launches but
-// 3.856 vs 3.794 ms per forward (one work-group walks 1984 x 32 logits): the default stays 512.
-int gate_index_max_rows() {
-  static const int v = [] { const char* e = getenv("M3_GATE_INDEX_MAX_ROWS"); return e ? atoi(e) : 512; }();
-  return v;
-}
-
-// M3_SELF_ROUTE=0 puts the single-work-group SoftmaxTopK + ScatterMapping launch back in front of the B = 1 expert launch (read once)
-bool self_route_enabled() {
-  static const bool v = [] { const char* e = getenv("M3_SELF_ROUTE"); return !(e && atoi(e) == 0); }();
-  return v;
+// The engine's run-time switches: environment variables read once per process, when the first stage list is built.
+struct Switches {
+  // M3_GATE_INDEX_MAX_ROWS (512): rows up to which SoftmaxTopK + ScatterMapping run as ONE single-work-group launch (beyond:
+  // row-parallel top-1 + index kernel).  A/B at configs[2] (1984 padded rows): 2048 -> 315 instead of 333 launches but 3.856 vs
+  // 3.794 ms per forward (one work-group walks 1984 x 32 logits): the default stays 512.
+  int gate_index_max_rows;
+  // M3_SELF_ROUTE (1): 0 puts the single-work-group SoftmaxTopK + ScatterMapping launch back in front of the short-input fp32
+  // expert launch, which otherwise routes for itself (staged and split route)
+  bool self_route;
+  // M3_HFUSE (1): 0 = no horizontal fusion of the embed encoder with the main encoder's prefix (fuse_independent_pairs)
+  bool hfuse;
+  // M3_ROUTER_MIN_ROWS (2048): the dedicated router kernel from this many rows on.  A/B at the three BASELINE shapes, one
+  // device: configs[4]-share 46.0 -> 29.1 us per layer, forward 8.83 -> 8.52 ms; configs[2] 14.1 vs 14.9 us and B = 1 +1.5 us
+  // per layer: there the 16-column work-groups of gemm.hip spread the 128-KB weight pull over more CUs.
+  int router_min_rows;
+  // M3_ROUTER_XQ (1): fp8 arithmetic, all experts local, the fused expert kernel next: the router kernel also leaves the rows
+  // quantised (e4m3 + a scale per row), the expert kernel reads 512 B per row instead of 2 KB.  0: as before
+  bool router_xq;
+  // M3_ROUTER_SKIP_XN (0): 1 = ... and the router kernel no longer writes the fp32 rows (the "xn" buffer, which the
+  // calibration tools read, is then not offered)
+  bool router_skip_xn;
+  // M3_FUSED8_ADAPT (0): 1 = all experts local, fused fp8 kernel: the kernel may split F finer than the host's choice when the
+  // routing leaves CUs without an item (the expert-parallel receive side always keeps the host's split: its result stays
+  // comparable bit for bit with any other grouping of the same rows under the same split).  A latency / throughput trade, OFF
+  // by default: measured at configs[4]'s share on one box, the launch 38.5 -> 27.8 us and one forward alone 6.70 -> 6.57 ms,
+  // but 4.58 -> 4.45 M frames/s at four contexts (twice the partial-output slabs; the idle CUs were being used by the other
+  // contexts' kernels)
+  bool fused8_adapt;
+};
+const Switches& switches() {
+  static const Switches sw = [] {
+    auto num = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
+    Switches w;
+    w.gate_index_max_rows = num("M3_GATE_INDEX_MAX_ROWS", 512);
+    w.self_route = num("M3_SELF_ROUTE", 1) != 0;
+    w.hfuse = num("M3_HFUSE", 1) != 0;
+    w.router_min_rows = num("M3_ROUTER_MIN_ROWS", 2048);
+    w.router_xq = num("M3_ROUTER_XQ", 1) != 0;
+    w.router_skip_xn = num("M3_ROUTER_SKIP_XN", 0) != 0;
+    w.fused8_adapt = num("M3_FUSED8_ADAPT", 0) != 0;
+    return w;
+  }();
+  return sw;
 }
 
 // dtype: what the engine will read the tensor as (GEMM weights follow cfg.weight_dtype, everything else is fp32)
@@ -319,8 +354,7 @@ bool use_packed_rows(const m3_engine_config& c, int B) {
 // horizontal fusion of the embed encoder with the main encoder's independent prefix (fuse_independent_gemm_pairs): fp32 plans
 // whose block GEMMs are 16-row-tile launches (S <= 128 rows).  Needs the embed chain's scratch apart from the main chain's.
 bool use_hfuse(const m3_engine_config& c, int B, int S) {
-  static const int on = [] { const char* ev = getenv("M3_HFUSE"); return ev ? atoi(ev) : 1; }();
-  return on && !c.debug_taps && c.weight_dtype == M3_F32 && c.embed_blocks > 0 && c.num_blocks > 0 && S <= 128 && c.fork_embed <= 0 &&
+  return switches().hfuse && !c.debug_taps && c.weight_dtype == M3_F32 && c.embed_blocks > 0 && c.num_blocks > 0 && S <= 128 && c.fork_embed <= 0 &&
          !use_packed_rows(c, B);
 }
 
@@ -452,6 +486,66 @@ Plan embed_view(const Plan& pl) {
   return q;
 }
 
+// How one MoE layer routes its rows (positionwise_feed_forward.py:209-265: router, SoftmaxTopK, ScatterMapping), decided once
+// per layer by choose_moe_route; the stage builders of build_block follow it.
+enum class RouterForm {
+  Gemm,     // staged: router GEMM on cat([embed, x]) with norm_ff as its prologue, which also writes xn
+  Kernel,   // the dedicated router kernel: one work-group per 16 rows and all experts, every activation byte read once (moe_router.hip)
+  Fused,    // fuse_route = 1: router (x half, norm_ff folded) + SoftmaxTopK + ScatterMapping in ONE launch ("moe_route")
+  Split,    // fuse_route = 2: a K = D GEMM on x with norm_ff folded, the embed half added as its epilogue residual
+};
+enum class GateForm {   // where SoftmaxTopK (top-1) + ScatterMapping (index) happen
+  RouterTail,   // top-1 in the router kernel's tail, then the index launch
+  GateIndex,    // both in one single-work-group launch ("moe_gate_index")
+  Top1Index,    // row-parallel top-1 launch, then the index launch
+  InExpert,     // inside the expert launch: every work-group derives its expert's rows from the router logits
+  InRoute,      // inside "moe_route"
+};
+struct MoeRoute {
+  RouterForm router = RouterForm::Gemm;
+  GateForm gate = GateForm::Top1Index;
+  bool ep = false;            // expert parallel ("moe_ep.*": rows cross the wire) instead of all experts local ("moe_local.*")
+  bool router_top1 = false;   // the router kernel writes gate_idx / gate_value in its tail (gate == RouterTail; with forced
+                              // switches also in front of a self-routing expert launch)
+  bool use_xq = false;        // the router kernel also leaves the rows quantised for the fused fp8 expert kernel
+  bool skip_xn = false;       // ... and does not write the fp32 rows xn
+  bool fs_dev = false;        // the fused fp8 kernel chooses its F split on the device (the combine reads the slab count)
+  bool needs_e_all = false;   // the embed half of the router product comes from the once-per-forward "router_e_all" GEMM
+  // fused / split route: no xn; the expert kernel reads the raw residual stream and applies norm_ff while it gathers rows
+  bool norm_in_expert() const { return router == RouterForm::Fused || router == RouterForm::Split; }
+};
+
+MoeRoute choose_moe_route(const m3_engine_config& c, int S, const BlockW& w, const Plan& pl) {
+  const Switches& sw = switches();
+  const int world = c.ep_world_size > 0 ? c.ep_world_size : 1;
+  const int E = c.num_experts, Etot = E * world, D = c.attention_dim, De = c.embed_dim, F = c.hidden_units;
+  const bool one_wg_experts = Etot == 8 || Etot == 16 || Etot == 32 || Etot == 64;   // what the single-work-group kernels take
+  // S <= 256 rows, all experts local, fp32: the expert launch can route for itself
+  const bool self_routing = sw.self_route && c.weight_dtype == M3_F32 && expert_ffn_f32_self_routing(S, Etot) &&
+                            !expert_ffn_f32_tiled(S, E, D, F);
+  MoeRoute r;
+  r.ep = world > 1 || c.ep_stages > 0;
+  if (c.fuse_route == 2 && world == 1 && S < 1024 && one_wg_experts) {
+    r.router = RouterForm::Split;
+    r.gate = self_routing ? GateForm::InExpert : GateForm::GateIndex;
+  } else if (c.fuse_route == 1 && world == 1 && S <= 256 && (E == 16 || E == 32 || E == 64)) {
+    r.router = RouterForm::Fused;
+    r.gate = GateForm::InRoute;
+  } else {
+    r.router = moe_router_supports(De, D, Etot) && S >= sw.router_min_rows ? RouterForm::Kernel : RouterForm::Gemm;
+    r.router_top1 = r.router == RouterForm::Kernel && moe_router_fuses_top1(Etot) && S > sw.gate_index_max_rows;
+    if (self_routing && c.fuse_route == 0 && !r.ep) r.gate = GateForm::InExpert;
+    else if (S <= sw.gate_index_max_rows && one_wg_experts) r.gate = GateForm::GateIndex;
+    else r.gate = r.router_top1 ? GateForm::RouterTail : GateForm::Top1Index;
+  }
+  const bool fused8 = c.weight_dtype == M3_FP8 && w.h_scale > 0.f && !r.ep && expert_ffn_w8a8_fused(S, E, D, F);
+  r.use_xq = r.router == RouterForm::Kernel && sw.router_xq && fused8 && pl.xq != nullptr;
+  r.skip_xn = r.use_xq && sw.router_skip_xn && !c.debug_taps;
+  r.fs_dev = sw.fused8_adapt && fused8 && pl.moe_fs != nullptr && !c.debug_taps;
+  r.needs_e_all = r.norm_in_expert();
+  return r;
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
@@ -487,7 +581,7 @@ static void add_gemm(m3_engine* e, const std::string& name, GemmParams p, bool f
     return;
   }
   add_stage(e, name, 1, [p](hipStream_t s) { return launch_gemm_f32(p, s); }, gemm_info(p, false));
-  e->cur.stages.back().fuse_kind = 1;
+  e->cur.stages.back().fuse_kind = FuseKind::Gemm;
   e->cur.stages.back().gemm = p;
 }
 
@@ -498,21 +592,21 @@ static void add_gemm(m3_engine* e, const std::string& name, GemmParams p, bool f
 // later kernel reads) is guaranteed to stay in front of every main-prefix stage.  Arithmetic per problem is unchanged: results
 // are bit-identical.  M3_HFUSE=0: off.
 static bool stages_fusable(const Stage& a, const Stage& b) {
-  if (a.fuse_kind == 0 || a.fuse_kind != b.fuse_kind) return false;
-  if (a.fuse_kind == 1) return gemm_f32_dual_fusable(a.gemm, b.gemm);
-  if (a.fuse_kind == 2) return dwconv_dual_fusable(a.dw, b.dw);
-  if (a.fuse_kind == 3) return relpos_attention_dual_fusable(a.att, b.att);
+  if (a.fuse_kind == FuseKind::None || a.fuse_kind != b.fuse_kind) return false;
+  if (a.fuse_kind == FuseKind::Gemm) return gemm_f32_dual_fusable(a.gemm, b.gemm);
+  if (a.fuse_kind == FuseKind::Dwconv) return dwconv_dual_fusable(a.dw, b.dw);
+  if (a.fuse_kind == FuseKind::Attention) return relpos_attention_dual_fusable(a.att, b.att);
   return false;
 }
 static Stage fused_stage(const Stage& a, const Stage& b) {
   Stage d;
   d.name = a.name + "+" + b.name;
   const char* label = "";
-  if (a.fuse_kind == 1) {
+  if (a.fuse_kind == FuseKind::Gemm) {
     const GemmParams pa = a.gemm, pb = b.gemm;
     d.run = [pa, pb](hipStream_t s) { return launch_gemm_f32_dual(pa, pb, s); };
     label = "gemm_f32_dual_kernel";
-  } else if (a.fuse_kind == 2) {
+  } else if (a.fuse_kind == FuseKind::Dwconv) {
     const DwArgs pa = a.dw, pb = b.dw;
     d.run = [pa, pb](hipStream_t s) { return launch_dwconv_ln_silu_dual(pa, pb, s); };
     label = "dwconv_ln_silu_dual_kernel";
@@ -531,8 +625,9 @@ static void fuse_independent_pairs(m3_engine* e, int first, int mid, int join) {
   std::vector<Stage> pending;                         // main-prefix stages waiting for the next pair they precede
   int i = first, saved = 0;
   for (int m = mid; m < join; ++m) {
+    assert(!st[m].reads_embed);                       // (moved ahead of embed stages: must not need the embedding)
     int partner = -1;
-    if (st[m].fuse_kind)
+    if (st[m].fuse_kind != FuseKind::None)
       for (int k = std::max(i, first + 1); k < mid; ++k)
         if (stages_fusable(st[k], st[m])) { partner = k; break; }
     if (partner < 0) { pending.push_back(st[m]); continue; }
@@ -548,6 +643,14 @@ static void fuse_independent_pairs(m3_engine* e, int first, int mid, int join) {
   for (int k = join; k < (int)st.size(); ++k) out.push_back(st[k]);
   st.swap(out);
   e->cur.n_kernels -= saved;
+}
+
+// the first stage from `from` on that reads the embedding: where the main encoder joins the embed encoder (-1: none).  The forked
+// capture runs [main start, join) beside the embed chain, horizontal fusion interleaves the two.
+static int embed_join(const std::vector<Stage>& st, int from) {
+  for (int i = from; i < (int)st.size(); ++i)
+    if (st[i].reads_embed) return i;
+  return -1;
 }
 
 static void build_subsample(m3_engine* e, const std::string& pfx, const SubW& w, int D, const Plan& pl, float* xout) {
@@ -596,6 +699,205 @@ static void build_subsample(m3_engine* e, const std::string& pfx, const SubW& w,
     add_stage(e, pfx + "row_stats", 1, [=](hipStream_t s) { return launch_row_stats_bf16(xbv, S, D, xs, s); },
               stage_info("row_stats_bf16_kernel", 1, (double)S * D * 2 + 32.0 * S, 3.0 * S * D));
   }
+}
+
+// ---- the MoE half of a main block: the stages of one route (choose_moe_route), one builder per stage kind ----
+// What the MoE stages of one layer work on
+struct MoeLayer {
+  std::string pfx;
+  const BlockW* w;
+  int S, Tp, D, F, De, E, Etot, world;   // E local experts, Etot = E * world router outputs
+  float eps;
+  float *x, *xn, *rl;
+  int32_t* gidx; float* gval;
+  const float* gv;                       // gate values the combine scales by (null: keep_expert_output)
+  const int32_t *lens, *live_len; int live_rpb;   // which rows are padding (padded or packed layout)
+  const int32_t* pdev;                   // packed rows: the live-row count on the device (else null)
+  const float* eall; int ld_eall;        // this layer's columns of router_e_all's output
+  void* xb_out; float* xstats_out;       // 16-bit modes: the combine also writes the bf16 copy of x / its row statistics
+  void* ws; MoeWorkspace mw;             // the layer's MoE workspace, carved for the S local rows
+};
+
+static void add_moe_router(m3_engine* e, const MoeLayer& m, const MoeRoute& r, const Plan& pl) {
+  const BlockW& w = *m.w;
+  const int S = m.S, D = m.D, De = m.De, E = m.E, Etot = m.Etot;
+  if (r.router == RouterForm::Fused) {
+    add_stage(e, m.pfx + "moe_route", 1, [m](hipStream_t s) {
+      const BlockW& w = *m.w;
+      return launch_moe_route(m.x, m.D, m.D, w.router_x.w, w.router_x.wsum, w.router_x.b, m.eall, m.ld_eall, m.eps, m.lens, m.Tp,
+                              m.S, m.E, m.gidx, m.gval, m.mw.mapping, m.mw.acc, m.mw.pos, s);
+    }, stage_info("moe_route_kernel", 1, (double)E * D * 4 + (double)S * (D + E) * 4 + 16.0 * S, 2.0 * S * E * D));
+  } else if (r.router == RouterForm::Kernel) {
+    void* xq = r.use_xq ? pl.xq : nullptr; float* xqs = r.use_xq ? pl.xq_scale : nullptr;
+    float* xn_out = r.skip_xn ? nullptr : m.xn;
+    if (r.skip_xn) e->cur.xn_skipped = true;   // ("xn" is then not offered as a buffer: a reader fails instead of reading stale rows)
+    int32_t* gidx = r.router_top1 ? m.gidx : nullptr; float* gval = r.router_top1 ? m.gval : nullptr;
+    const float* emb = pl.emb;
+    add_stage(e, m.pfx + "moe_router", 1, [=](hipStream_t s) {
+      const BlockW& w = *m.w;
+      return launch_moe_router(emb, m.De, m.De, m.x, m.D, m.D, w.router.w, w.router.b, w.n_ff.g, w.n_ff.b, m.eps, xn_out, m.D, m.rl,
+                               m.Etot, m.S, m.Etot, m.pdev, s, gidx, gval, m.live_len, m.live_rpb, xq, xqs);
+    }, stage_info("moe_router_kernel", 1, (double)Etot * (De + D) * 4 + (double)S * (De + 2 * D + Etot) * 4, 2.0 * S * Etot * (De + D)));
+  } else {
+    GemmParams g;
+    g.Y = m.rl; g.ldy = Etot; g.M = S; g.N = Etot; g.m_dev = m.pdev;
+    if (r.router == RouterForm::Split) {   // norm_ff folded into the x-half weight (output-side LayerNorm), embed half as residual
+      g.A = m.x; g.lda = D; g.W = w.router_x.w; g.bias = w.router_x.b; g.ln_wsum = w.router_x.wsum; g.ln_eps = m.eps; g.K = D;
+      g.resid = m.eall; g.ldr = m.ld_eall;
+    } else {   // LayerNorm(norm_ff) on the x half of cat([embed, x]) as the prologue, written out once as xn (the expert FFN's input)
+      g.mode = GEMM_A_CONCAT2; g.A = pl.emb; g.lda = De; g.K1 = De; g.A2 = m.x; g.lda2 = D; g.K = De + D;
+      g.W = w.router.w; g.bias = w.router.b;
+      g.ln_gamma = w.n_ff.g; g.ln_beta = w.n_ff.b; g.ln_eps = m.eps; g.ln_on_a2 = 1; g.ln_out = m.xn; g.ld_ln_out = D;
+    }
+    add_gemm(e, m.pfx + "moe_router", g, true);
+  }
+  e->cur.stages.back().reads_embed = true;
+}
+
+// SoftmaxTopK plugin + ScatterMapping kernel of the reference in ONE launch (a single work-group: right for a few hundred rows);
+// the index over the local (map, acc, pos) or, expert parallel, over the global expert ids
+static void add_moe_gate_index(m3_engine* e, const MoeLayer& m, int32_t* map, int32_t* acc, int32_t* pos) {
+  add_stage(e, m.pfx + "moe_gate_index", 1, [=](hipStream_t s) {
+    return launch_moe_gate_index(m.rl, m.Etot, m.live_len, m.live_rpb, m.S, m.gidx, m.gval, map, acc, pos, s);
+  }, stage_info("moe_index_kernel", 1, (double)m.S * (m.Etot * 4 + 16) + 4.0 * (m.Etot + 1), 0.0));
+}
+
+static void add_moe_top1(m3_engine* e, const MoeLayer& m) {
+  add_stage(e, m.pfx + "moe_top1", 1, [m](hipStream_t s) {
+    return launch_softmax_top1(m.rl, m.Etot, m.live_len, m.live_rpb, m.S, m.Etot, m.gidx, m.gval, s);
+  }, stage_info("softmax_top1_kernel", 1, (double)m.S * (m.Etot * 4 + 8), 0.0));
+}
+
+static void add_moe_local_index(m3_engine* e, const MoeLayer& m) {
+  add_stage(e, m.pfx + "moe_local.index", 1, [m](hipStream_t s) {
+    return launch_moe_index(m.gidx, m.S, m.E, m.mw.mapping, m.mw.acc, m.mw.pos, s);
+  }, stage_info("moe_index_kernel", 1, 12.0 * m.S + 4.0 * (m.E + 1), 0.0));
+}
+
+// The form the grouped expert FFN takes on R rows, and where the combine finds its result
+struct ExpertForm {
+  int wmode;            // 0 fp32, 1 bf16, 2 fp8 weights, 3 fp8 arithmetic (the wmode of expert_ffn_w16_*)
+  int launches;
+  const char* kernel;
+  float* rows;          // the expert outputs: sorted rows or partial-output slabs ...
+  int slices;           // ... this many of them per row
+};
+// norm_in_expert: the kernel applies norm_ff while it gathers rows (fused / split route): the fp32 slab form, never tiled
+static ExpertForm expert_form(const m3_engine_config& c, float h_scale, float* slab, int R, int E, int D, int F, bool norm_in_expert) {
+  ExpertForm f;
+  if (c.weight_dtype == M3_F32) {   // long batches: two grouped GEMMs whose result is ONE slab of sorted rows
+    const bool tiled = !norm_in_expert && expert_ffn_f32_tiled(R, E, D, F);
+    f.wmode = 0;
+    f.launches = tiled ? 2 : 1;
+    f.kernel = tiled ? "expert_gemm_f32_tiled_kernel" : "expert_ffn_f32_kernel";
+    f.rows = tiled ? expert_ffn_f32_rows(slab, R, E, D, F) : slab;
+    f.slices = tiled ? 1 : F / kExpertSlice;
+  } else {
+    f.wmode = c.weight_dtype == M3_FP8 ? (h_scale > 0.f ? 3 : 2) : 1;
+    f.launches = expert_ffn_w16_launches(f.wmode, R, E, D, F);
+    f.kernel = expert_ffn_w16_kernel(f.wmode, R, E, D, F);
+    f.rows = expert_ffn_w16_rows(f.wmode, slab, R, E, D, F);
+    f.slices = expert_ffn_w16_slices(f.wmode, R, E, D, F);
+  }
+  return f;
+}
+
+// the grouped expert FFN in form f on the R rows of x that (mw.pos, mw.acc) sort by expert; its result into mw.slab
+static int launch_expert(const ExpertForm& f, const BlockW& w, const float* x, const MoeWorkspace& mw, int R, int E, int D, int F,
+                         hipStream_t s, const float* ln_g = nullptr, const float* ln_b = nullptr, float ln_eps = 0.f,
+                         const void* xq = nullptr, const float* xq_scale = nullptr, int32_t* fs_dev = nullptr) {
+  if (f.wmode >= 2)
+    return launch_expert_ffn_w8a8(x, D, mw.pos, mw.acc, R, E, D, F, w.ew1, w.es1, w.eb1, w.ew2, w.es2, 1, w.h_scale, mw.slab, s,
+                                  xq, xq_scale, fs_dev);
+  if (f.wmode == 1) return launch_expert_ffn_bf16w(x, D, mw.pos, mw.acc, R, E, D, F, w.ew1, w.eb1, w.ew2, 1, mw.slab, s);
+  return launch_expert_ffn_f32(x, D, mw.pos, mw.acc, R, E, D, F, w.ew1, w.eb1, w.ew2, 1, mw.slab, ln_g, ln_b, ln_eps, s);
+}
+
+static void add_moe_local_expert(m3_engine* e, const MoeLayer& m, const MoeRoute& r, const ExpertForm& f, const Plan& pl) {
+  const bool norm = r.norm_in_expert();
+  const float* xin = norm ? m.x : m.xn;
+  const bool self_route = r.gate == GateForm::InExpert;
+  const void* xq = r.use_xq ? pl.xq : nullptr; const float* xqs = r.use_xq ? pl.xq_scale : nullptr;
+  int32_t* fs = r.fs_dev ? pl.moe_fs : nullptr;
+  add_stage(e, m.pfx + "moe_local.expert", f.launches, [=](hipStream_t s) {
+    const BlockW& w = *m.w;
+    const float* ln_g = norm ? w.n_ff.g : nullptr; const float* ln_b = norm ? w.n_ff.b : nullptr; const float ln_eps = norm ? m.eps : 0.f;
+    // short inputs, fp32: SoftmaxTopK + ScatterMapping happen inside the expert launch (every work-group derives its expert's
+    // rows from the router logits; moe_expert.hip "self-routing form"); its slabs hold ORIGINAL rows, b2 inside
+    if (self_route)
+      return launch_expert_route_ffn_f32(xin, m.D, m.rl, m.live_len, m.live_rpb, m.S, m.E, m.D, m.F, w.ew1, w.eb1, w.ew2, 1, w.eb2,
+                                         m.mw.slab, m.gidx, m.gval, m.mw.mapping, m.mw.acc, m.mw.pos, s, ln_g, ln_b, ln_eps);
+    return launch_expert(f, w, xin, m.mw, m.S, m.E, m.D, m.F, s, ln_g, ln_b, ln_eps, xq, xqs, fs);
+  }, stage_info(f.kernel, 1, -1.0, 4.0 * m.D * m.F * m.S));
+}
+
+// local_gather + b2 + gate + residual + LayerNorm(norm_final) over the expert outputs
+static void add_moe_local_combine(m3_engine* e, const MoeLayer& m, const MoeRoute& r, const ExpertForm& f, const Plan& pl) {
+  // (self-routing expert launch: slabs hold ORIGINAL rows with b2 already in slice 0 -> no mapping, no b2 here)
+  const bool self_route = r.gate == GateForm::InExpert;
+  const int32_t* cmap = self_route ? nullptr : m.mw.mapping;
+  const float* cb2 = self_route ? nullptr : m.w->eb2;
+  const int32_t* fs = r.fs_dev ? pl.moe_fs : nullptr;
+  const double S = m.S, D = m.D;
+  add_stage(e, m.pfx + "moe_local.combine", 1, [=](hipStream_t s) {
+    const BlockW& w = *m.w;
+    return launch_moe_combine(f.rows, fs ? 4 : f.slices, cmap, m.gidx, m.gv, cb2, m.x, 0.5f, w.n_final.g, w.n_final.b, m.eps, m.x,
+                              m.S, m.D, s, m.xb_out, m.xstats_out, fs);
+  }, stage_info("moe_combine_kernel", 1, S * D * 4 * (f.slices + 2) + (m.xb_out ? 2.0 * S * D : 0.0), S * D * (f.slices + 10)));
+}
+
+// Expert parallel (m3asr/ep.py drives the two all-to-alls between these stages; FastMoE semantics
+// trainer_3m_fix/fmoe/functions.py:13-86,175-199): nothing returns to the host, the exchange has a fixed shape
+// wire [world][1 + C][D]: chunk j = what goes to / came from rank j, header row = E_loc row counts
+static void add_moe_ep(m3_engine* e, const MoeLayer& m, const MoeRoute& r, const Plan& pl) {
+  const int S = m.S, E = m.E, Etot = m.Etot, D = m.D, F = m.F, world = m.world;
+  const int cap = pl.ep_cap, R = pl.ep_rows;
+  int32_t *g_acc = pl.ep_acc, *g_map = pl.ep_mapping, *g_pos = pl.ep_pos, *map_send = pl.ep_map_send, *gate_recv = pl.ep_gate_recv;
+  int32_t* ep_overflow = pl.ep_overflow;
+  float *wire_a = pl.wire_a, *wire_b = pl.wire_b;
+  const MoeWorkspace rw = carve_moe_workspace(m.ws, R, E, D, F);     // receive side: R wire rows over the E local experts
+  // top-1 + index over GLOBAL expert ids (the same kernel choice by row count as with all experts local)
+  if (r.gate == GateForm::GateIndex) add_moe_gate_index(e, m, g_map, g_acc, g_pos);
+  if (r.gate == GateForm::Top1Index) add_moe_top1(e, m);
+  // wire row of every token (+ count headers), rows scattered straight into the send wire
+  const bool one_launch = r.gate == GateForm::GateIndex;
+  const int32_t* gidx = m.gidx; const float* xn = m.xn;
+  add_stage(e, m.pfx + "moe_ep.send", one_launch ? 1 : 2, [=](hipStream_t s) {
+    if (!one_launch)
+      if (int rc = launch_moe_index(gidx, S, Etot, g_map, g_acc, g_pos, s)) return rc;
+    return launch_ep_send_rows(gidx, g_map, g_acc, S, world, E, cap, map_send, xn, wire_a, D * 4, s, ep_overflow);
+  }, stage_info("ep_send_rows_kernel", 1, (double)S * D * 8 + 24.0 * S, 0.0));
+  auto exchange = [=](const char* name) {   // one rank: the all-to-all is a copy
+    if (world == 1) add_stage(e, m.pfx + name, 0, [=](hipStream_t s) {
+      M3_CHECK_HIP(hipMemcpyAsync(wire_b, wire_a, (size_t)R * D * 4, hipMemcpyDeviceToDevice, s));
+      return 0;
+    });
+  };
+  exchange("moe_ep.exchange1");
+  // this rank's experts on everything it received (its own stable index puts the rows in FastMoE's receive order: by local
+  // expert, then source rank, then wire order); results return to wire_a at the wire rows they came in on
+  const ExpertForm f = expert_form(e->cfg, m.w->h_scale, rw.slab, R, E, D, F, false);
+  // bf16 experts in the tiled two-GEMM form: GEMM-2's epilogue adds b2 and puts every row straight back on its wire row
+  // (no un-permuting combine launch; wire rows nobody sent keep stale bytes -- no rank ever reads them back)
+  const bool scatter2 = f.wmode == 1 && expert_ffn_bf16_tiled(R, E, D, F);
+  const BlockW* wp = m.w;
+  add_stage(e, m.pfx + "moe_ep.expert", (scatter2 ? 2 : 3) + f.launches, [=](hipStream_t s) {
+    const BlockW& w = *wp;
+    if (int rc = launch_ep_recv_gate(wire_b, world, E, cap, D * 4, gate_recv, s)) return rc;
+    if (int rc = launch_moe_index(gate_recv, R, E, rw.mapping, rw.acc, rw.pos, s)) return rc;
+    if (scatter2) return launch_expert_ffn_bf16w(wire_b, D, rw.pos, rw.acc, R, E, D, F, w.ew1, w.eb1, w.ew2, 1, rw.slab, s, w.eb2, wire_a);
+    if (int rc = launch_expert(f, w, wire_b, rw, R, E, D, F, s)) return rc;
+    return launch_moe_combine(f.rows, f.slices, rw.mapping, gate_recv, nullptr, w.eb2, nullptr, 1.f, nullptr, nullptr, 0.f, wire_a, R, D, s);
+  }, stage_info(f.kernel, 1, -1.0, 4.0 * D * F * S));
+  exchange("moe_ep.exchange2");
+  // local_gather + gate + residual + LayerNorm: token s reads its result at the wire row it was sent from
+  add_stage(e, m.pfx + "moe_ep.combine", 1, [=](hipStream_t s) {
+    const BlockW& w = *wp;
+    return launch_moe_combine(wire_b, 1, map_send, nullptr, m.gv, nullptr, m.x, 0.5f, w.n_final.g, w.n_final.b, m.eps, m.x, S, D, s,
+                              m.xb_out, m.xstats_out);
+  }, stage_info("moe_combine_kernel", 1, (double)S * D * 12 + (m.xb_out ? 2.0 * S * D : 0.0), (double)S * D * 11));
+  e->cur.buffers["ep.wire_a"] = Buf{wire_a, (size_t)R * D * 4};
+  e->cur.buffers["ep.wire_b"] = Buf{wire_b, (size_t)R * D * 4};
 }
 
 static void build_block(m3_engine* e, const std::string& pfx, const BlockW& w, int D, int F, int H, int K, bool cnn_ln,
@@ -682,7 +984,7 @@ static void build_block(m3_engine* e, const std::string& pfx, const BlockW& w, i
       AttArgs aa;
       aa.qkv = qkv; aa.ldq = 3 * D; aa.pmat = pmat; aa.ldp = ldp; aa.pos_u = pu; aa.pos_v = pv; aa.row_len = lens; aa.B = B; aa.T = Tp; aa.H = H;
       aa.dk = dk; aa.scale = scale; aa.out = ctx; aa.ldo = D; aa.out_bf16 = a16; aa.row0 = row0; aa.chunk = chunk; aa.left_chunks = left_chunks;
-      e->cur.stages.back().fuse_kind = 3;
+      e->cur.stages.back().fuse_kind = FuseKind::Attention;
       e->cur.stages.back().att = aa;
     }
     }
@@ -718,7 +1020,7 @@ static void build_block(m3_engine* e, const std::string& pfx, const BlockW& w, i
       da.out = dw; da.out_bf16 = a16; da.pad_of = pad_of; da.row0 = row0; da.row_len = lens; da.causal_left_fill = lfill;
       add_stage(e, pfx + "conv.dw_ln_silu", 1, [da](hipStream_t s) { return launch_dwconv_ln_silu_args(da, s); },
                 stage_info("dwconv_ln_silu_kernel", 1, (double)S * D * (4 + (a16 ? 2 : 4)) + (double)K * D * 4, 2.0 * K * D * S));
-      e->cur.stages.back().fuse_kind = 2;
+      e->cur.stages.back().fuse_kind = FuseKind::Dwconv;
       e->cur.stages.back().dw = da;
     }
     GemmParams h;
@@ -748,231 +1050,34 @@ static void build_block(m3_engine* e, const std::string& pfx, const BlockW& w, i
     add_stage(e, pfx + "norm_final", 1, [=](hipStream_t s) { return launch_layernorm(x, fg, fb, eps, x, S, D, s, xbo, xso, g2, b2, eps2, y2); },
               stage_info("layernorm_kernel", 1, (double)S * D * (a16 ? 10 : 8) + (g2 ? 4.0 * S * D : 0.0), (g2 ? 16.0 : 8.0) * S * D));
   } else {  // x = LN_final(x + 0.5 * gate * Expert_g(LN(x)))     (positionwise_feed_forward.py:209-265)
-    const int world = c.ep_world_size > 0 ? c.ep_world_size : 1;
-    const int Etot = c.num_experts * world, E = c.num_experts, De = c.embed_dim;
-    float* xn = pl.xn; float* rl = pl.rl;
-    int32_t* gidx = pl.gate_idx + (size_t)layer * S;
-    float* gval = pl.gate_val + (size_t)layer * S;
-    const float* ng = w.n_ff.g; const float* nb = w.n_ff.b;
-    void* mws = (char*)pl.moe_ws + (c.debug_taps ? (size_t)layer * pl.moe_ws_bytes : 0);
-    const MoeWorkspace mw = carve_moe_workspace(mws, S, E, D, F);
-    const float *ew1 = w.ew1, *eb1 = w.eb1, *ew2 = w.ew2, *eb2 = w.eb2;
-    const float* fg = w.n_final.g; const float* fb = w.n_final.b;
-    const float* gv = c.keep_expert_output ? nullptr : gval;
-    // S <= 256 rows, all experts local, fp32, staged route: the expert launch routes for itself (M3_SELF_ROUTE=0: index launch as before)
-    const bool self_route = self_route_enabled() && c.fuse_route == 0 && world == 1 && c.ep_stages <= 0 && c.weight_dtype == M3_F32 &&
-                            expert_ffn_f32_self_routing(S, Etot) && !expert_ffn_f32_tiled(S, E, D, F);
-    const bool fused_route = c.fuse_route == 1 && world == 1 && S <= 256 && (E == 16 || E == 32 || E == 64);
-    // fuse_route = 2 ("split route"): the embed half of every layer's router product comes from one GEMM per forward
-    // ("router_e_all"), the x half is a K = D GEMM with norm_ff folded in (output-side LayerNorm, the embed half added as
-    // the epilogue residual) instead of the K = De + D GEMM with a LayerNorm prologue, and the expert kernel applies
-    // norm_ff while it gathers rows, so xn is never materialised
-    const bool split_route = c.fuse_route == 2 && world == 1 && S < 1024 && (Etot == 8 || Etot == 16 || Etot == 32 || Etot == 64);
-    bool router_gate = false;   // the dedicated router kernel also did SoftmaxTopK (no moe_top1 stage)
-    bool use_xq = false;        // ... and left the rows quantised for the fused fp8 expert kernel
-    bool split_self = false;    // split route whose expert launch routes for itself (slabs hold ORIGINAL rows, b2 inside)
-    int32_t* fs_dev = nullptr;  // the fused fp8 kernel's device-side F split (slab count), when it is allowed to choose
-    if (split_route) {
-      GemmParams r;
-      r.A = x; r.lda = D; r.W = w.router_x.w; r.bias = w.router_x.b; r.ln_wsum = w.router_x.wsum; r.ln_eps = eps;
-      r.Y = rl; r.ldy = Etot; r.M = S; r.N = Etot; r.K = D;
-      r.resid = pl.eall + (size_t)layer * E; r.ldr = c.num_blocks * E;
-      add_gemm(e, pfx + "moe_router", r, true);
-      // (the expert launch routes for itself here too: no index launch; M3_SELF_ROUTE=0 puts it back)
-      split_self = self_route_enabled() && c.weight_dtype == M3_F32 && expert_ffn_f32_self_routing(S, Etot) && !expert_ffn_f32_tiled(S, E, D, F);
-      if (split_self) {
-        add_stage(e, pfx + "moe_local.expert", 1, [=](hipStream_t s) {
-          return launch_expert_route_ffn_f32(x, D, rl, live_len, live_rpb, S, E, D, F, ew1, eb1, ew2, 1, eb2, mw.slab, gidx, gval,
-                                             mw.mapping, mw.acc, mw.pos, s, ng, nb, eps);
-        }, stage_info("expert_ffn_f32_kernel", 1, -1.0, 4.0 * D * F * S));
-      } else {
-      add_stage(e, pfx + "moe_gate_index", 1, [=](hipStream_t s) {
-        return launch_moe_gate_index(rl, Etot, live_len, live_rpb, S, gidx, gval, mw.mapping, mw.acc, mw.pos, s);
-      }, stage_info("moe_index_kernel", 1, (double)S * (Etot * 4 + 16) + 4.0 * (E + 1), 0.0));
-      add_stage(e, pfx + "moe_local.expert", 1, [=](hipStream_t s) {
-        return launch_expert_ffn_f32(x, D, mw.pos, mw.acc, S, E, D, F, ew1, eb1, ew2, 1, mw.slab, ng, nb, eps, s);
-      }, stage_info("expert_ffn_f32_kernel", 1, -1.0, 4.0 * D * F * S));
-      }
-    } else if (fused_route) {
-      // router (x half, norm_ff folded; embed half precomputed for all layers by "router_e_all") + SoftmaxTopK +
-      // ScatterMapping in ONE launch; the expert kernel applies norm_ff itself while it gathers rows
-      const float* wx = w.router_x.w; const float* wsum = w.router_x.wsum; const float* rb = w.router_x.b;
-      const float* eall = pl.eall + (size_t)layer * E;
-      const int ld_e = c.num_blocks * E;
-      add_stage(e, pfx + "moe_route", 1, [=](hipStream_t s) {
-        return launch_moe_route(x, D, D, wx, wsum, rb, eall, ld_e, eps, lens, Tp, S, E, gidx, gval, mw.mapping, mw.acc,
-                                mw.pos, s);
-      }, stage_info("moe_route_kernel", 1, (double)E * D * 4 + (double)S * (D + E) * 4 + 16.0 * S, 2.0 * S * E * D));
-      add_stage(e, pfx + "moe_local.expert", 1, [=](hipStream_t s) {
-        return launch_expert_ffn_f32(x, D, mw.pos, mw.acc, S, E, D, F, ew1, eb1, ew2, 1, mw.slab, ng, nb, eps, s);
-      }, stage_info("expert_ffn_f32_kernel", 1, -1.0, 4.0 * D * F * S));
-    } else {
-    GemmParams r;
-    r.mode = GEMM_A_CONCAT2; r.A = pl.emb; r.lda = De; r.K1 = De; r.A2 = x; r.lda2 = D;
-    r.W = w.router.w; r.bias = w.router.b; r.Y = rl; r.ldy = Etot; r.M = S; r.N = Etot; r.K = De + D;
-    // LayerNorm(norm_ff) rides in the router GEMM: applied to the x half of cat([embed, x]) and written
-    // out once as xn, the expert FFN's input
-    r.ln_gamma = ng; r.ln_beta = nb; r.ln_eps = eps; r.ln_on_a2 = 1; r.ln_out = xn; r.ld_ln_out = D;
-    // from 2048 rows on (A/B at the three BASELINE shapes, one device: configs[4]-share 46.0 -> 29.1 us per layer, forward
-    // 8.83 -> 8.52 ms; configs[2] 14.1 vs 14.9 us and B = 1 +1.5 us per layer: there the 16-column work-groups of gemm.hip
-    // spread the 128-KB weight pull over more CUs).  M3_ROUTER_MIN_ROWS overrides (read once).
-    static const int router_min_rows = [] { const char* ev = getenv("M3_ROUTER_MIN_ROWS"); return ev ? atoi(ev) : 2048; }();
-    router_gate = moe_router_supports(De, D, Etot) && S >= router_min_rows && moe_router_fuses_top1(Etot) && S > gate_index_max_rows();
-    if (moe_router_supports(De, D, Etot) && S >= router_min_rows) {
-      // the dedicated kernel: one work-group per 16 rows and all experts, every activation byte read once (moe_router.hip)
-      const float* emb = pl.emb; const float* rw = w.router.w; const float* rb = w.router.b;
-      // fp8 arithmetic, all experts local, the fused expert kernel next: the rows ALSO leave the router kernel quantised (e4m3 + a
-      // scale per row): the expert kernel reads 512 B per row instead of 2 KB.  M3_ROUTER_XQ=0: as before
-      static const int xq_on = [] { const char* ev = getenv("M3_ROUTER_XQ"); return ev ? atoi(ev) : 1; }();
-      use_xq = xq_on && pl.xq != nullptr && world == 1 && c.ep_stages <= 0 && c.weight_dtype == M3_FP8 && w.h_scale > 0.f &&
-               expert_ffn_w8a8_fused(S, E, D, F);     // (the form launch_expert_ffn_w8a8 will take)
-      unsigned char* xq = use_xq ? pl.xq : nullptr; float* xqs = use_xq ? pl.xq_scale : nullptr;
-      // (the fp32 rows stay available as the "xn" buffer -- the calibration tools read them -- unless M3_ROUTER_SKIP_XN=1)
-      static const int skip_xn = [] { const char* ev = getenv("M3_ROUTER_SKIP_XN"); return ev ? atoi(ev) : 0; }();
-      float* xn_out = (use_xq && skip_xn && !c.debug_taps) ? nullptr : xn;
-      if (xn_out == nullptr) e->cur.xn_skipped = true;   // ("xn" is then not offered as a buffer: a reader fails instead of reading stale rows)
-      add_stage(e, pfx + "moe_router", 1, [=](hipStream_t s) {
-        // (+ SoftmaxTopK in its tail when the row-parallel top-1 launch would follow: gate_idx / gate_value come from here)
-        return launch_moe_router(emb, De, De, x, D, D, rw, rb, ng, nb, eps, xn_out, D, rl, Etot, S, Etot, pdev, s,
-                                 router_gate ? gidx : nullptr, router_gate ? gval : nullptr, live_len, live_rpb, xq, xqs);
-      }, stage_info("moe_router_kernel", 1, (double)Etot * (De + D) * 4 + (double)S * (De + 2 * D + Etot) * 4, 2.0 * S * Etot * (De + D)));
-    } else {
-      add_gemm(e, pfx + "moe_router", r, true);
-    }
-    const bool ep = world > 1 || c.ep_stages > 0;
-    if (ep) {
-      // ---- expert parallel (m3asr/ep.py drives the two all-to-alls between these stages; FastMoE semantics
-      //      trainer_3m_fix/fmoe/functions.py:13-86,175-199): nothing returns to the host, the exchange has a fixed shape
-      //      wire [world][1 + C][D]: chunk j = what goes to / came from rank j, header row = E_loc row counts ----
-      const int cap = pl.ep_cap, R = pl.ep_rows;
-      int32_t *g_acc = pl.ep_acc, *g_map = pl.ep_mapping, *g_pos = pl.ep_pos, *map_send = pl.ep_map_send, *gate_recv = pl.ep_gate_recv;
-      int32_t* ep_overflow = pl.ep_overflow;
-      float *wire_a = pl.wire_a, *wire_b = pl.wire_b;
-      const MoeWorkspace rw = carve_moe_workspace(mws, R, E, D, F);     // receive side: R wire rows over the E local experts
-      // top-1 + local index over GLOBAL expert ids (the same kernel choice by row count as with all experts local)
-      const bool one_launch = S <= gate_index_max_rows() && (Etot == 8 || Etot == 16 || Etot == 32 || Etot == 64);
-      if (one_launch) {
-        add_stage(e, pfx + "moe_gate_index", 1, [=](hipStream_t s) {
-          return launch_moe_gate_index(rl, Etot, live_len, live_rpb, S, gidx, gval, g_map, g_acc, g_pos, s);
-        }, stage_info("moe_index_kernel", 1, (double)S * (Etot * 4 + 16) + 4.0 * (Etot + 1), 0.0));
-      } else if (!router_gate) {
-        add_stage(e, pfx + "moe_top1", 1, [=](hipStream_t s) {
-          return launch_softmax_top1(rl, Etot, live_len, live_rpb, S, Etot, gidx, gval, s);
-        }, stage_info("softmax_top1_kernel", 1, (double)S * (Etot * 4 + 8), 0.0));
-      }
-      // wire row of every token (+ count headers), rows scattered straight into the send wire
-      add_stage(e, pfx + "moe_ep.send", one_launch ? 1 : 2, [=](hipStream_t s) {
-        if (!one_launch)
-          if (int rc = launch_moe_index(gidx, S, Etot, g_map, g_acc, g_pos, s)) return rc;
-        return launch_ep_send_rows(gidx, g_map, g_acc, S, world, E, cap, map_send, xn, wire_a, D * 4, s, ep_overflow);
-      }, stage_info("ep_send_rows_kernel", one_launch ? 1 : 2, (double)S * D * 8 + 24.0 * S, 0.0));
-      if (world == 1) add_stage(e, pfx + "moe_ep.exchange1", 0, [=](hipStream_t s) {   // one rank: the all-to-all is a copy
-        M3_CHECK_HIP(hipMemcpyAsync(wire_b, wire_a, (size_t)R * D * 4, hipMemcpyDeviceToDevice, s));
-        return 0;
-      });
-      // this rank's experts on everything it received (its own stable index puts the rows in FastMoE's receive order: by
-      // local expert, then source rank, then wire order); results return to wire_a at the wire rows they came in on
-      const bool e16 = c.weight_dtype != M3_F32, e8 = c.weight_dtype == M3_FP8;
-      const float *es1 = w.es1, *es2 = w.es2;
-      const float h_scale = w.h_scale;
-      const int wmode = e8 ? (h_scale > 0.f ? 3 : 2) : (e16 ? 1 : 0);
-      const int elaunches = e16 ? expert_ffn_w16_launches(wmode, R, E, D, F) : (expert_ffn_f32_tiled(R, E, D, F) ? 2 : 1);
-      const float* erows = e16 ? expert_ffn_w16_rows(wmode, rw.slab, R, E, D, F) : expert_ffn_f32_rows(rw.slab, R, E, D, F);
-      const int eslices = e16 ? expert_ffn_w16_slices(wmode, R, E, D, F) : expert_ffn_f32_slices(R, E, D, F);
-      // bf16 experts in the tiled two-GEMM form: GEMM-2's epilogue adds b2 and puts every row straight back on its wire row
-      // (no un-permuting combine launch; wire rows nobody sent keep stale bytes -- no rank ever reads them back)
-      const bool scatter2 = wmode == 1 && expert_ffn_bf16_tiled(R, E, D, F);
-      add_stage(e, pfx + "moe_ep.expert", (scatter2 ? 2 : 3) + elaunches, [=](hipStream_t s) {
-        if (int rc = launch_ep_recv_gate(wire_b, world, E, cap, D * 4, gate_recv, s)) return rc;
-        if (int rc = launch_moe_index(gate_recv, R, E, rw.mapping, rw.acc, rw.pos, s)) return rc;
-        if (scatter2) return launch_expert_ffn_bf16w(wire_b, D, rw.pos, rw.acc, R, E, D, F, ew1, eb1, ew2, 1, rw.slab, s, eb2, wire_a);
-        int rc;
-        if (e8) rc = launch_expert_ffn_w8a8(wire_b, D, rw.pos, rw.acc, R, E, D, F, ew1, es1, eb1, ew2, es2, 1, h_scale, rw.slab, s);
-        else if (e16) rc = launch_expert_ffn_bf16w(wire_b, D, rw.pos, rw.acc, R, E, D, F, ew1, eb1, ew2, 1, rw.slab, s);
-        else rc = launch_expert_ffn_f32(wire_b, D, rw.pos, rw.acc, R, E, D, F, ew1, eb1, ew2, 1, rw.slab, nullptr, nullptr, 0.f, s);
-        if (rc) return rc;
-        return launch_moe_combine(erows, eslices, rw.mapping, gate_recv, nullptr, eb2, nullptr, 1.f, nullptr, nullptr, 0.f, wire_a, R, D, s);
-      }, stage_info(e16 ? expert_ffn_w16_kernel(wmode, R, E, D, F)
-                        : (expert_ffn_f32_tiled(R, E, D, F) ? "expert_gemm_f32_tiled_kernel" : "expert_ffn_f32_kernel"),
-                    1, -1.0, 4.0 * D * F * S));
-      if (world == 1) add_stage(e, pfx + "moe_ep.exchange2", 0, [=](hipStream_t s) {
-        M3_CHECK_HIP(hipMemcpyAsync(wire_b, wire_a, (size_t)R * D * 4, hipMemcpyDeviceToDevice, s));
-        return 0;
-      });
-      // local_gather + gate + residual + LayerNorm: token s reads its result at the wire row it was sent from
-      add_stage(e, pfx + "moe_ep.combine", 1, [=](hipStream_t s) {
-        return launch_moe_combine(wire_b, 1, map_send, nullptr, gv, nullptr, x, 0.5f, fg, fb, eps, x, S, D, s, a16 ? xb : nullptr,
-                                  dma ? xstats : nullptr);
-      }, stage_info("moe_combine_kernel", 1, (double)S * D * 12 + (a16 ? 2.0 * S * D : 0.0), (double)S * D * 11));
-      e->cur.buffers["ep.wire_a"] = Buf{wire_a, (size_t)R * D * 4};
-      e->cur.buffers["ep.wire_b"] = Buf{wire_b, (size_t)R * D * 4};
-    } else {
-    // "moe_local.*": index + grouped expert FFN + combine with all experts local
-    if (self_route) {
-      // short inputs, fp32: SoftmaxTopK + ScatterMapping happen inside the expert launch (every work-group derives its
-      // expert's rows from the router logits; moe_expert.hip "self-routing form") -- no index launch
-      add_stage(e, pfx + "moe_local.expert", 1, [=](hipStream_t s) {
-        return launch_expert_route_ffn_f32(xn, D, rl, live_len, live_rpb, S, E, D, F, ew1, eb1, ew2, 1, eb2, mw.slab, gidx, gval,
-                                           mw.mapping, mw.acc, mw.pos, s);
-      }, stage_info("expert_ffn_f32_kernel", 1, -1.0, 4.0 * D * F * S));
-    } else {
-    if (S <= gate_index_max_rows() && (Etot == 8 || Etot == 16 || Etot == 32 || Etot == 64)) {
-      // SoftmaxTopK plugin + ScatterMapping kernel of the reference in ONE launch (a single workgroup: right for a
-      // few hundred rows; long batches take the row-parallel top-1 kernel + the index kernel below)
-      add_stage(e, pfx + "moe_gate_index", 1, [=](hipStream_t s) {
-        return launch_moe_gate_index(rl, Etot, live_len, live_rpb, S, gidx, gval, mw.mapping, mw.acc, mw.pos, s);
-      }, stage_info("moe_index_kernel", 1, (double)S * (Etot * 4 + 16) + 4.0 * (E + 1), 0.0));
-    } else {
-      if (!router_gate)
-      add_stage(e, pfx + "moe_top1", 1, [=](hipStream_t s) {
-        return launch_softmax_top1(rl, Etot, live_len, live_rpb, S, Etot, gidx, gval, s);
-      }, stage_info("softmax_top1_kernel", 1, (double)S * (Etot * 4 + 8), 0.0));
-      add_stage(e, pfx + "moe_local.index", 1, [=](hipStream_t s) {
-        return launch_moe_index(gidx, S, E, mw.mapping, mw.acc, mw.pos, s);
-      }, stage_info("moe_index_kernel", 1, 12.0 * S + 4.0 * (E + 1), 0.0));
-    }
-    const bool e16 = c.weight_dtype != M3_F32, e8 = c.weight_dtype == M3_FP8;
-    const float *es1 = w.es1, *es2 = w.es2;
-    const float h_scale = w.h_scale;
-    // all experts local, fused fp8 kernel, M3_FUSED8_ADAPT=1: the kernel may split F finer than the host's choice when the routing
-    // leaves CUs without an item (the expert-parallel receive side always keeps the host's split: its result stays comparable bit
-    // for bit with any other grouping of the same rows under the same split).  A latency / throughput trade, OFF by default:
-    // measured at configs[4]'s share on one box, the launch 38.5 -> 27.8 us and one forward alone 6.70 -> 6.57 ms, but 4.58 -> 4.45 M
-    // frames/s at four contexts (twice the partial-output slabs; the idle CUs were being used by the other contexts' kernels)
-    static const int adapt_on = [] { const char* ev = getenv("M3_FUSED8_ADAPT"); return ev ? atoi(ev) : 0; }();
-    fs_dev = (adapt_on && e8 && h_scale > 0.f && pl.moe_fs != nullptr && !c.debug_taps && expert_ffn_w8a8_fused(S, E, D, F)) ? pl.moe_fs : nullptr;
-    const int wmode = e8 ? (h_scale > 0.f ? 3 : 2) : (e16 ? 1 : 0);
-    const int elaunches = e16 ? expert_ffn_w16_launches(wmode, S, E, D, F) : (expert_ffn_f32_tiled(S, E, D, F) ? 2 : 1);
-    add_stage(e, pfx + "moe_local.expert", elaunches, [=](hipStream_t s) {
-      if (e8) return launch_expert_ffn_w8a8(xn, D, mw.pos, mw.acc, S, E, D, F, ew1, es1, eb1, ew2, es2, 1, h_scale, mw.slab, s,
-                                            use_xq ? pl.xq : nullptr, use_xq ? pl.xq_scale : nullptr, fs_dev);
-      if (e16) return launch_expert_ffn_bf16w(xn, D, mw.pos, mw.acc, S, E, D, F, ew1, eb1, ew2, 1, mw.slab, s);
-      return launch_expert_ffn_f32(xn, D, mw.pos, mw.acc, S, E, D, F, ew1, eb1, ew2, 1, mw.slab, nullptr, nullptr, 0.f, s);
-    }, stage_info(e16 ? expert_ffn_w16_kernel(wmode, S, E, D, F)
-                      : (expert_ffn_f32_tiled(S, E, D, F) ? "expert_gemm_f32_tiled_kernel" : "expert_ffn_f32_kernel"),
-                  1, -1.0, 4.0 * D * F * S));
-    }
-    }
-    }
-    if (!(world > 1 || c.ep_stages > 0)) {
-    // long batches run the expert FFN as two grouped GEMMs whose result is ONE slab of sorted rows (never with fused_route: S <= 256)
-    const bool e16c = c.weight_dtype != M3_F32;
-    const int wmode_c = c.weight_dtype == M3_FP8 ? (w.h_scale > 0.f ? 3 : 2) : 1;
-    const float* erows = (fused_route || split_route) ? mw.slab : (e16c ? expert_ffn_w16_rows(wmode_c, mw.slab, S, E, D, F) : expert_ffn_f32_rows(mw.slab, S, E, D, F));
-    const int eslices = (fused_route || split_route) ? F / kExpertSlice : (e16c ? expert_ffn_w16_slices(wmode_c, S, E, D, F) : expert_ffn_f32_slices(S, E, D, F));
-    // (self-routing expert launch: slabs hold ORIGINAL rows with b2 already in slice 0 -> no mapping, no b2 here)
-    const int32_t* cmap = (self_route || split_self) ? nullptr : mw.mapping;
-    const float* cb2 = (self_route || split_self) ? nullptr : eb2;
-    add_stage(e, pfx + "moe_local.combine", 1, [=](hipStream_t s) {
-      return launch_moe_combine(erows, fs_dev ? 4 : eslices, cmap, gidx, gv, cb2, x, 0.5f, fg, fb, eps, x, S, D, s, a16 ? xb : nullptr,
-                                dma ? xstats : nullptr, fs_dev);
-    }, stage_info("moe_combine_kernel", 1, (double)S * D * 4 * (eslices + 2) + (a16 ? 2.0 * S * D : 0.0), (double)S * D * (eslices + 10)));
+    MoeLayer m;
+    m.pfx = pfx; m.w = &w; m.S = S; m.Tp = Tp; m.D = D; m.F = F; m.De = c.embed_dim; m.E = c.num_experts;
+    m.world = c.ep_world_size > 0 ? c.ep_world_size : 1; m.Etot = m.E * m.world; m.eps = eps;
+    m.x = x; m.xn = pl.xn; m.rl = pl.rl;
+    m.gidx = pl.gate_idx + (size_t)layer * S; m.gval = pl.gate_val + (size_t)layer * S;
+    m.gv = c.keep_expert_output ? nullptr : m.gval;
+    m.lens = lens; m.live_len = live_len; m.live_rpb = live_rpb; m.pdev = pdev;
+    m.eall = pl.eall + (size_t)layer * m.E; m.ld_eall = c.num_blocks * m.E;
+    m.xb_out = a16 ? xb : nullptr; m.xstats_out = dma ? xstats : nullptr;
+    m.ws = (char*)pl.moe_ws + (c.debug_taps ? (size_t)layer * pl.moe_ws_bytes : 0);
+    m.mw = carve_moe_workspace(m.ws, S, m.E, D, F);
+    const MoeRoute r = choose_moe_route(c, S, w, pl);
+    add_moe_router(e, m, r, pl);
+    if (r.ep) {
+      add_moe_ep(e, m, r, pl);
+    } else {   // "moe_local.*": index + grouped expert FFN + combine with all experts local
+      if (r.gate == GateForm::GateIndex) add_moe_gate_index(e, m, m.mw.mapping, m.mw.acc, m.mw.pos);
+      if (r.gate == GateForm::Top1Index) add_moe_top1(e, m);
+      if (r.gate == GateForm::Top1Index || r.gate == GateForm::RouterTail) add_moe_local_index(e, m);
+      const ExpertForm f = expert_form(c, w.h_scale, m.mw.slab, S, m.E, D, F, r.norm_in_expert());
+      add_moe_local_expert(e, m, r, f, pl);
+      add_moe_local_combine(e, m, r, f, pl);
     }
     const std::string b = pfx.substr(0, pfx.size() - 1);
-    e->cur.buffers[b + ".gate_idx"] = Buf{gidx, (size_t)S * 4};
-    e->cur.buffers[b + ".gate_value"] = Buf{gval, (size_t)S * 4};
-    e->cur.buffers[b + ".mapping"] = Buf{mw.mapping, (size_t)S * 4};
-    e->cur.buffers[b + ".acc_histogram"] = Buf{mw.acc, (size_t)(E + 1) * 4};
+    e->cur.buffers[b + ".gate_idx"] = Buf{m.gidx, (size_t)S * 4};
+    e->cur.buffers[b + ".gate_value"] = Buf{m.gval, (size_t)S * 4};
+    e->cur.buffers[b + ".mapping"] = Buf{m.mw.mapping, (size_t)S * 4};
+    e->cur.buffers[b + ".acc_histogram"] = Buf{m.mw.acc, (size_t)(m.E + 1) * 4};
   }
   if (c.debug_taps) {
     float* tap = pl.taps + (size_t)tap_index * S * D;
@@ -1219,8 +1324,7 @@ static int prepare_impl(m3_engine* e, const float* feat, const int32_t* feat_len
   }
   // ---- embed encoder (conformer_embed_domain_acc.py:149-181) ----
   const Plan ple = embed_view(pl);
-  const int hf_first = (int)e->cur.stages.size();       // (horizontal fusion: the embed chain starts here ...)
-  if (pl.fork) e->cur.fork_first = (int)e->cur.stages.size();
+  const int embed_start = (int)e->cur.stages.size();    // the embed chain starts here ...
   e->cur.splitk_ws = ple.splitk;
   build_subsample(e, "embed.subsample.", e->sub_e, De, ple, ple.x);
   for (int i = 0; i < c.embed_blocks; ++i) {
@@ -1238,17 +1342,15 @@ static int prepare_impl(m3_engine* e, const float* feat, const int32_t* feat_len
               stage_info("layernorm_kernel", 1, 8.0 * S * De, 8.0 * S * De));
   }
   // embed half of every layer's router product in one GEMM: emb does not change across the main blocks
-  if ((c.fuse_route == 2 && c.ep_world_size <= 1 && S < 1024) ||
-      (c.fuse_route == 1 && (c.ep_world_size <= 1) && S <= 256 &&
-       (c.num_experts == 16 || c.num_experts == 32 || c.num_experts == 64))) {
+  if (choose_moe_route(c, S, e->mblocks.empty() ? BlockW() : e->mblocks[0], pl).needs_e_all) {
     GemmParams g;
     g.A = pl.emb; g.lda = De; g.W = e->router_e_all; g.Y = pl.eall; g.ldy = c.num_blocks * c.num_experts;
     g.M = S; g.N = c.num_blocks * c.num_experts; g.K = De;
     add_gemm(e, "router_e_all", g, true);
+    e->cur.stages.back().reads_embed = true;
   }
   // ---- main MoE encoder (conformer_fmoe_localComm_catEmbed_domain_acc_hier.py:198-234) ----
-  if (pl.fork) e->cur.fork_mid = (int)e->cur.stages.size();
-  const int hf_mid = (int)e->cur.stages.size();         // (... and the main encoder's independent prefix here)
+  const int main_start = (int)e->cur.stages.size();     // ... and the main encoder here
   build_subsample(e, "subsample.", e->sub_m, D, pl, pl.x);
   for (int i = 0; i < c.num_blocks; ++i)
     build_block(e, "blocks." + std::to_string(i) + ".", e->mblocks[i], D, c.hidden_units, c.attention_heads,
@@ -1279,22 +1381,13 @@ static int prepare_impl(m3_engine* e, const float* feat, const int32_t* feat_len
                 stage_info("unpack_rows_kernel", 1, 8.0 * S * V, 0.0, false));
     }
   }
-  if (pl.fork) {     // the main branch joins the embed branch at the first stage that reads the embedding: blocks.0's router
-    for (size_t i = 0; i < e->cur.stages.size(); ++i)
-      if (e->cur.stages[i].name == "blocks.0.moe_router" || e->cur.stages[i].name == "blocks.0.moe_route") {
-        e->cur.join_at = (int)i;
-        break;
-      }
-    if (e->cur.join_at < 0 || c.num_blocks < 1) e->cur.fork_first = e->cur.fork_mid = e->cur.join_at = -1;
+  // the main encoder first needs the embedding at blocks.0's router: the forked capture joins its two branches there, horizontal
+  // fusion interleaves the two chains up to there
+  const int join = embed_join(e->cur.stages, main_start);
+  if (pl.fork && join >= 0 && c.num_blocks >= 1) {
+    e->cur.fork_first = embed_start; e->cur.fork_mid = main_start; e->cur.join_at = join;
   }
-  if (pl.hfuse && !streaming && hf_first >= 0) {
-    int join = -1;
-    for (size_t i = (size_t)hf_mid; i < e->cur.stages.size(); ++i) {
-      const std::string& n = e->cur.stages[i].name;
-      if (n == "blocks.0.moe_router" || n == "blocks.0.moe_route" || n == "blocks.0.moe_gate_index") { join = (int)i; break; }
-    }
-    if (join > 0) fuse_independent_pairs(e, hf_first, hf_mid, join);
-  }
+  if (pl.hfuse && !streaming && join > 0) fuse_independent_pairs(e, embed_start, main_start, join);
   if (streaming) {   // the chunk counter moves on the device: the same captured graph serves every chunk of the stream
     int32_t* step = carve_stream_state(c, sstate, B, s_hist).step;
     add_stage(e, "stream.advance", 1, [=](hipStream_t s) { return launch_advance_counter(step, 1, s); },
