@@ -319,6 +319,11 @@ size_t m3_ctc_beam_state_size(const m3_ctc_beam_desc* desc) { return ctc_beam_st
 int m3_ctc_beam_reset(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, m3_stream stream) {
   return launch_ctc_beam_reset(desc, state, state_bytes, (hipStream_t)stream);
 }
+int m3_ctc_beam_reset_slots(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const int32_t* slots, int n, m3_stream stream) {
+  M3_REQUIRE(n == 0 || slots != nullptr, "ctc_beam_reset_slots: null slot list");
+  if (n == 0) return 0;
+  return launch_ctc_beam_reset(desc, state, state_bytes, (hipStream_t)stream, slots, n);
+}
 int m3_ctc_beam_advance(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const float* top_logp,
                         const int32_t* top_idx, int T_chunk, const int32_t* n_frames, m3_stream stream) {
   return launch_ctc_beam_advance(desc, state, state_bytes, top_logp, top_idx, T_chunk, n_frames, (hipStream_t)stream);
@@ -330,6 +335,12 @@ int m3_ctc_beam_nbest(const m3_ctc_beam_desc* desc, const void* state, size_t st
 size_t m3_ctc_greedy_stream_state_size(const m3_ctc_greedy_desc* desc) { return ctc_greedy_stream_state_size(desc); }
 int m3_ctc_greedy_stream_reset(const m3_ctc_greedy_desc* desc, void* state, size_t state_bytes, m3_stream stream) {
   return launch_ctc_greedy_stream_reset(desc, state, state_bytes, (hipStream_t)stream);
+}
+int m3_ctc_greedy_stream_reset_slots(const m3_ctc_greedy_desc* desc, void* state, size_t state_bytes, const int32_t* slots, int n,
+                                     m3_stream stream) {
+  M3_REQUIRE(n == 0 || slots != nullptr, "ctc_greedy_stream_reset_slots: null slot list");
+  if (n == 0) return 0;
+  return launch_ctc_greedy_stream_reset(desc, state, state_bytes, (hipStream_t)stream, slots, n);
 }
 int m3_ctc_greedy_stream_advance(const m3_ctc_greedy_desc* desc, void* state, size_t state_bytes, const float* logits,
                                  int T_chunk, int V, const int32_t* n_frames, int32_t* frame_ids, m3_stream stream) {

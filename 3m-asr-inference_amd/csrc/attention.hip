@@ -279,14 +279,18 @@ int launch_relpos_attention(const float* qkv, int ldq, const float* pmat, int ld
 // a hipGraph.  Key tiles sit at absolute multiples of 16 and wave w owns tiles w, w + 4, ... exactly as in the full-utterance
 // kernel above; tiles left of every row's window are skipped (there they leave the softmax state untouched), so a chunk's
 // context equals the rows the full-utterance kernel computes under the same static chunk mask bit for bit.
-template <int DK>
+// SLOTS (slot mode, m3_engine_forward_chunk_slots): `step` is an array, one chunk counter per utterance slot, and a slot that
+// is not live in this chunk (stream_slot_live: nothing to decode, or its chunk would end past max_frames) appends nothing,
+// sees no key and gets zero context rows -- no address is formed from a counter that failed the test.  The lockstep
+// instantiation (SLOTS = false) is the kernel as it was: max_chunks is never read there.
+template <int DK, bool SLOTS = false>
 __global__ __launch_bounds__(256) void relpos_attention_stream_kernel(const float* __restrict__ qkv, int ldq,
                                                                      float* __restrict__ hist, int cap,
                                                                      const float* __restrict__ pmat, int ldp,
                                                                      const float* __restrict__ pos_u, const float* __restrict__ pos_v,
                                                                      const int32_t* __restrict__ chunk_len, const int32_t* __restrict__ step,
                                                                      int C, int D, float scale, float* __restrict__ out, int ldo,
-                                                                     int QT, int H, int left_chunks) {
+                                                                     int QT, int H, int left_chunks, int max_chunks) {
   constexpr int KS = DK / 16;
   asm volatile("" ::"s"(qkv), "s"(ldq), "s"(hist), "s"(cap), "s"(pmat), "s"(ldp), "s"(pos_u), "s"(pos_v), "s"(chunk_len), "s"(step),
                "s"(C), "s"(D), "s"(scale), "s"(out), "s"(ldo), "s"(QT), "s"(H), "s"(left_chunks));
@@ -297,8 +301,17 @@ __global__ __launch_bounds__(256) void relpos_attention_stream_kernel(const floa
   float (*ps)[20] = ps_all[wave];
   const int bh = blockIdx.x / QT, qt = blockIdx.x - bh * QT;
   const int b = bh / H, h = bh - b * H, q0 = qt * 16;
-  const int off = *step * C;                              // absolute index of the chunk's first frame
-  const int nlive = min(max(chunk_len[b], 0), C);         // valid frames of utterance b in this chunk
+  bool slot_live = true;
+  int pos = 0;
+  if (SLOTS) {
+    pos = step[b];
+    slot_live = stream_slot_live(chunk_len[b], pos, max_chunks);
+    if (!slot_live) pos = 0;
+  } else {
+    pos = *step;
+  }
+  const int off = pos * C;                                // absolute index of the chunk's first frame
+  const int nlive = slot_live ? min(max(chunk_len[b], 0), C) : 0;   // valid frames of utterance b in this chunk
   const int len = off + nlive;                            // keys the utterance has so far
   const size_t brow = (size_t)b * C;
   const float* hb = hist + (size_t)b * cap * 2 * D;
@@ -306,7 +319,7 @@ __global__ __launch_bounds__(256) void relpos_attention_stream_kernel(const floa
   // ---- this work-group's share of the history append: K | V of head h, frames q0 .. q0 + 15 of the chunk ----
   for (int idx = threadIdx.x; idx < 16 * 2 * (DK / 4); idx += 256) {
     const int r = idx / (2 * (DK / 4)), rem = idx - r * 2 * (DK / 4), kv = rem / (DK / 4), c4 = (rem - kv * (DK / 4)) * 4;
-    if (q0 + r < C) {
+    if (q0 + r < C && slot_live) {
       const f32x4 val = ldg4(qkv + (brow + q0 + r) * ldq + (1 + kv) * D + h * DK + c4);
       stg4(hist + ((size_t)b * cap + (size_t)((off + q0 + r) % cap)) * 2 * D + kv * D + h * DK + c4, val);
     }
@@ -413,7 +426,7 @@ __global__ __launch_bounds__(256) void relpos_attention_stream_kernel(const floa
 
 int launch_relpos_attention_stream(const float* qkv, int ldq, float* hist, int cap, const float* pmat, int ldp, const float* pos_u,
                                    const float* pos_v, const int32_t* chunk_len, const int32_t* step, int B, int C, int H, int dk,
-                                   float scale, float* out, int ldo, int left_chunks, hipStream_t stream) {
+                                   float scale, float* out, int ldo, int left_chunks, hipStream_t stream, int slot_max_chunks) {
   M3_REQUIRE(B > 0 && C > 0 && H > 0 && cap >= C, "attention (stream): empty problem or history shorter than a chunk");
   M3_REQUIRE(left_chunks < 0 || cap >= (left_chunks + 1) * C, "attention (stream): a history of %d frames cannot hold %d left chunks of %d", cap, left_chunks, C);
   M3_REQUIRE((ldq & 3) == 0 && (ldp & 3) == 0 && (dk & 3) == 0, "attention (stream): row strides must be multiples of 4");
@@ -421,9 +434,14 @@ int launch_relpos_attention_stream(const float* qkv, int ldq, float* hist, int c
   const int QT = cdiv(C, 16);
   dim3 grid(QT * H * B);
   const int D = H * dk;
-#define M3_ATT_CASE(DK_)                                                                                            \
-  hipLaunchKernelGGL((relpos_attention_stream_kernel<DK_>), grid, dim3(256), 0, stream, qkv, ldq, hist, cap, pmat, ldp, \
-                     pos_u, pos_v, chunk_len, step, C, D, scale, out, ldo, QT, H, left_chunks)
+  // slot_max_chunks >= 0: slot mode, `step` holds B counters (one per utterance slot)
+#define M3_ATT_CASE(DK_)                                                                                                           \
+  if (slot_max_chunks >= 0)                                                                                                        \
+    hipLaunchKernelGGL((relpos_attention_stream_kernel<DK_, true>), grid, dim3(256), 0, stream, qkv, ldq, hist, cap, pmat, ldp,    \
+                       pos_u, pos_v, chunk_len, step, C, D, scale, out, ldo, QT, H, left_chunks, slot_max_chunks);                 \
+  else                                                                                                                             \
+    hipLaunchKernelGGL((relpos_attention_stream_kernel<DK_, false>), grid, dim3(256), 0, stream, qkv, ldq, hist, cap, pmat, ldp,   \
+                       pos_u, pos_v, chunk_len, step, C, D, scale, out, ldo, QT, H, left_chunks, 0)
   switch (dk) {
     case 16: M3_ATT_CASE(16); break;
     case 32: M3_ATT_CASE(32); break;

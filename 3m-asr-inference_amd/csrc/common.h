@@ -76,6 +76,11 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 __device__ __forceinline__ float silu(float x) { return x / (1.f + __expf(-x)); }
 __device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + __expf(-x)); }
+// Streaming in slot mode (every stream of the batch has its own chunk counter): THE test of "slot b takes part in this chunk".
+// n = output frames slot b has in the chunk, pos = its chunk counter, max_chunks = max_frames / c.  A slot with nothing to
+// decode is idle; so is one whose next chunk would end past max_frames (the advance kernel marks that one).  Every slot-mode
+// kernel applies this test before it derives an address from pos.
+__device__ __forceinline__ bool stream_slot_live(int n, int pos, int max_chunks) { return n > 0 && pos >= 0 && pos < max_chunks; }
 
 // ---- host-side per-device state.  hipFuncSetAttribute and the CU count belong to a device, not to the process: a process that
 //      drives several devices (tests, a server with one engine per GPU) must set kernel attributes once on EACH of them. ----

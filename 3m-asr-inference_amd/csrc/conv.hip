@@ -32,13 +32,16 @@ struct DwCausal {
   const int32_t* step = nullptr;           // streaming: device-side chunk counter; `left` then is the [2][B][K-1][D] ping-pong pair
   long half = 0;                           // floats in one half of the pair
   const int32_t* chunk_len = nullptr;      // streaming: valid frames of this chunk per utterance
+  int max_chunks = 0;                      // streaming in slot mode (SLOTS kernels only): `step` is [B], one counter per utterance
 };
 
 // CAUSAL is a template parameter: the symmetric form is the round-3 kernel instruction for instruction (making it a run-time
 // field of one kernel cost 4.9 -> 8.3 us per launch at B = 1: a pointer select in front of every tap load).
 // (the body as a device function of the work-group's row: dwconv_ln_silu_dual_kernel runs two independent problems in one launch,
 //  see gemm.hip / engine.hip "horizontal fusion")
-template <int KT, bool CAUSAL>
+// SLOTS is a template parameter for the same reason: the lockstep streaming form reads ONE counter, slot mode utterance b's own
+// (cs.step[b]); a slot that is not live in this chunk (stream_slot_live) leaves its cache pair alone.
+template <int KT, bool CAUSAL, bool SLOTS = false>
 __device__ __forceinline__ void dwconv_ln_silu_body(const float* __restrict__ z, const float* __restrict__ w_kc,
                                                     const float* __restrict__ bias, const float* __restrict__ gamma,
                                                     const float* __restrict__ beta, float eps, int T, int D, int K,
@@ -53,7 +56,15 @@ __device__ __forceinline__ void dwconv_ln_silu_body(const float* __restrict__ z,
   const bool live = c < D;
   const float* leftp = cs.left;
   if (CAUSAL && cs.step != nullptr) {                         // streaming: read half (step & 1), write the other one
-    const int par = *cs.step & 1;
+    int par;
+    if (SLOTS) {                                    // the parity of this row's slot; only a parity is taken from the counter
+      const int sb = row >= n_rows ? (row - n_rows) / (K - 1) : row / T;
+      const int pos = cs.step[sb];
+      if (row >= n_rows && !stream_slot_live(cs.chunk_len[sb], pos, cs.max_chunks)) return;
+      par = pos & 1;
+    } else {
+      par = *cs.step & 1;
+    }
     leftp = cs.left + (size_t)par * cs.half;
     if (row >= n_rows) {                            // cache update: row i of utterance b <- frame i + len of [cache | z]
       const int i = row - n_rows, b = i / (K - 1), ci = i - b * (K - 1);
@@ -153,7 +164,7 @@ __device__ __forceinline__ void dwconv_ln_silu_body(const float* __restrict__ z,
   }
 }
 
-template <int KT, bool CAUSAL>
+template <int KT, bool CAUSAL, bool SLOTS = false>
 __global__ __launch_bounds__(1024) void dwconv_ln_silu_kernel(const float* __restrict__ z, const float* __restrict__ w_kc,
                                                               const float* __restrict__ bias,
                                                               const float* __restrict__ gamma,
@@ -162,7 +173,7 @@ __global__ __launch_bounds__(1024) void dwconv_ln_silu_kernel(const float* __res
                                                               const int32_t* __restrict__ pad_of,
                                                               const int32_t* __restrict__ row0,
                                                               const int32_t* __restrict__ row_len, int n_rows, DwCausal cs) {
-  dwconv_ln_silu_body<KT, CAUSAL>(z, w_kc, bias, gamma, beta, eps, T, D, K, out, out_bf16, pad_of, row0, row_len, n_rows, cs, (int)blockIdx.x);
+  dwconv_ln_silu_body<KT, CAUSAL, SLOTS>(z, w_kc, bias, gamma, beta, eps, T, D, K, out, out_bf16, pad_of, row0, row_len, n_rows, cs, (int)blockIdx.x);
 }
 struct DwKernArgs {
   const float *z, *w_kc, *bias, *gamma, *beta; float eps; int T, D, K; float* out; int out_bf16;
@@ -180,7 +191,8 @@ __global__ __launch_bounds__(1024) void dwconv_ln_silu_dual_kernel(const DwKernA
 
 static int launch_dwconv_impl(const float* z, const float* w_kc, const float* bias, const float* gamma, const float* beta, float eps,
                               int B, int T, int D, int K, float* out, hipStream_t stream, int out_bf16, const int32_t* pad_of,
-                              const int32_t* row0, const int32_t* row_len, const DwCausal& cs) {
+                              const int32_t* row0, const int32_t* row_len, const DwCausal& cs, bool slots = false) {
+  M3_REQUIRE(!slots || (cs.causal && cs.step != nullptr && cs.max_chunks > 0), "dwconv (slot mode): needs the streaming causal form");
   M3_REQUIRE((D & 3) == 0 && D <= 4096, "dwconv: channels=%d must be a multiple of 4 (<=4096)", D);
   M3_REQUIRE(cs.causal || (K & 1) == 1, "dwconv: kernel size %d must be odd (non-causal)", K);
   M3_REQUIRE(!cs.causal || (cs.left != nullptr && K >= 2), "dwconv (causal): the frames left of frame 0 must be supplied (left_fill / cache)");
@@ -191,8 +203,13 @@ static int launch_dwconv_impl(const float* z, const float* w_kc, const float* bi
 #define M3_DW_CASE(KT_, C_)                                                                                                  \
   hipLaunchKernelGGL((dwconv_ln_silu_kernel<KT_, C_>), dim3(grid), dim3(threads), 0, stream, z, w_kc, bias, gamma, beta, eps, T, \
                      D, K, out, out_bf16, pad_of, row0, row_len, rows, cs)
-  if (K <= 15) { if (cs.causal) M3_DW_CASE(15, true); else M3_DW_CASE(15, false); }
+#define M3_DW_SLOTS(KT_)                                                                                                        \
+  hipLaunchKernelGGL((dwconv_ln_silu_kernel<KT_, true, true>), dim3(grid), dim3(threads), 0, stream, z, w_kc, bias, gamma, beta, eps, \
+                     T, D, K, out, out_bf16, pad_of, row0, row_len, rows, cs)
+  if (slots) { if (K <= 15) M3_DW_SLOTS(15); else M3_DW_SLOTS(8); }
+  else if (K <= 15) { if (cs.causal) M3_DW_CASE(15, true); else M3_DW_CASE(15, false); }
   else { if (cs.causal) M3_DW_CASE(8, true); else M3_DW_CASE(8, false); }
+#undef M3_DW_SLOTS
 #undef M3_DW_CASE
   M3_LAUNCH_CHECK();
   return 0;
@@ -238,12 +255,14 @@ int launch_dwconv_ln_silu_dual(const DwArgs& a, const DwArgs& b, hipStream_t str
 // chunk-by-chunk (streaming) form of the causal conv: cache_pair [2][B][K-1][D], chunk counter and valid frames on the device
 int launch_dwconv_ln_silu_stream(const float* z, const float* w_kc, const float* bias, const float* gamma, const float* beta,
                                  float eps, int B, int T, int D, int K, float* out, float* cache_pair, const int32_t* step,
-                                 const int32_t* chunk_len, hipStream_t stream, int out_bf16) {
+                                 const int32_t* chunk_len, hipStream_t stream, int out_bf16, int slot_max_chunks) {
   M3_REQUIRE(cache_pair && step && chunk_len, "dwconv (stream): null state");
   DwCausal cs;
   cs.causal = 1; cs.left = cache_pair; cs.left_b_stride = (long)(K - 1) * D; cs.left_t_stride = D;
   cs.step = step; cs.half = (long)B * (K - 1) * D; cs.chunk_len = chunk_len;
-  return launch_dwconv_impl(z, w_kc, bias, gamma, beta, eps, B, T, D, K, out, stream, out_bf16, nullptr, nullptr, nullptr, cs);
+  cs.max_chunks = slot_max_chunks > 0 ? slot_max_chunks : 0;
+  return launch_dwconv_impl(z, w_kc, bias, gamma, beta, eps, B, T, D, K, out, stream, out_bf16, nullptr, nullptr, nullptr, cs,
+                            slot_max_chunks >= 0);
 }
 
 // feat [B][T][idim] -> out [B][T1][F1][C] (channel-last), w9c [9][C] (repacked from (C,1,3,3)), ReLU.

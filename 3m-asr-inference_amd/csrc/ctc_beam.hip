@@ -115,8 +115,11 @@ __device__ __forceinline__ BeamPtrs beam_ptrs(const BeamLayout& L, char* state, 
 }
 
 // grid (x: hash-table blocks, y: utterance): empty hash table, root node, beam = {empty prefix: pb = 0, pnb = -inf}
-__global__ __launch_bounds__(256) void ctc_beam_reset_kernel(BeamLayout L, char* state) {
-  const BeamPtrs p = beam_ptrs(L, state, blockIdx.y);
+// slots != null: y indexes a device list of utterances (entries outside [0, B) are skipped)
+__global__ __launch_bounds__(256) void ctc_beam_reset_kernel(BeamLayout L, char* state, const int32_t* __restrict__ slots, int B) {
+  const int utt = slots != nullptr ? slots[blockIdx.y] : (int)blockIdx.y;
+  if (utt < 0 || utt >= B) return;
+  const BeamPtrs p = beam_ptrs(L, state, utt);
   for (int i = blockIdx.x * 256 + threadIdx.x; i < L.hcap; i += gridDim.x * 256) {
     p.hkey[i] = kEmptyKey;
     p.hval[i] = -1;
@@ -409,8 +412,14 @@ int check_greedy_desc(const m3_ctc_greedy_desc* d) {
   return 0;
 }
 
-__global__ __launch_bounds__(256) void ctc_greedy_stream_reset_kernel(int32_t* state, size_t stride, int B) {
-  const int b = blockIdx.x * 256 + threadIdx.x;
+__global__ __launch_bounds__(256) void ctc_greedy_stream_reset_kernel(int32_t* state, size_t stride, int B,
+                                                                      const int32_t* __restrict__ slots, int n) {
+  int b = blockIdx.x * 256 + threadIdx.x;
+  if (slots != nullptr) {                         // a device list of n streams (entries outside [0, B) are skipped)
+    if (b >= n) return;
+    b = slots[b];
+    if (b < 0) return;
+  }
   if (b >= B) return;
   int32_t* st = state + (size_t)b * stride;
   st[G_STATUS] = 0;
@@ -470,14 +479,16 @@ size_t ctc_beam_state_size(const m3_ctc_beam_desc* d) {
   return (size_t)d->B * beam_layout(d->beam, d->max_frames).stride;
 }
 
-int launch_ctc_beam_reset(const m3_ctc_beam_desc* d, void* state, size_t bytes, hipStream_t stream) {
+int launch_ctc_beam_reset(const m3_ctc_beam_desc* d, void* state, size_t bytes, hipStream_t stream, const int32_t* slots, int n) {
   if (int rc = check_beam_desc(d)) return rc;
+  M3_REQUIRE(n >= 0 && (slots != nullptr || n == 0), "ctc_beam_reset: bad slot list");
+  if (slots != nullptr && n == 0) return 0;
   const BeamLayout L = beam_layout(d->beam, d->max_frames);
   M3_REQUIRE(state != nullptr && bytes >= (size_t)d->B * L.stride, "ctc_beam_reset: state %zu bytes < required %zu", bytes,
              (size_t)d->B * L.stride);
   if (d->B == 0) return 0;
   const unsigned gx = (unsigned)std::min((L.hcap + 255) / 256, 64);
-  hipLaunchKernelGGL(ctc_beam_reset_kernel, dim3(gx, d->B), dim3(256), 0, stream, L, (char*)state);
+  hipLaunchKernelGGL(ctc_beam_reset_kernel, dim3(gx, slots ? n : d->B), dim3(256), 0, stream, L, (char*)state, slots, d->B);
   M3_LAUNCH_CHECK();
   return 0;
 }
@@ -516,13 +527,17 @@ size_t ctc_greedy_stream_state_size(const m3_ctc_greedy_desc* d) {
   return (size_t)d->B * greedy_stride(d->max_frames) * 4;
 }
 
-int launch_ctc_greedy_stream_reset(const m3_ctc_greedy_desc* d, void* state, size_t bytes, hipStream_t stream) {
+int launch_ctc_greedy_stream_reset(const m3_ctc_greedy_desc* d, void* state, size_t bytes, hipStream_t stream, const int32_t* slots,
+                                   int n) {
   if (int rc = check_greedy_desc(d)) return rc;
+  M3_REQUIRE(n >= 0 && (slots != nullptr || n == 0), "ctc_greedy_stream_reset: bad slot list");
+  if (slots != nullptr && n == 0) return 0;
   const size_t stride = greedy_stride(d->max_frames);
   M3_REQUIRE(state != nullptr && bytes >= (size_t)d->B * stride * 4, "ctc_greedy_stream_reset: state %zu bytes < required %zu",
              bytes, (size_t)d->B * stride * 4);
   if (d->B == 0) return 0;
-  hipLaunchKernelGGL(ctc_greedy_stream_reset_kernel, dim3((d->B + 255) / 256), dim3(256), 0, stream, (int32_t*)state, stride, d->B);
+  hipLaunchKernelGGL(ctc_greedy_stream_reset_kernel, dim3(((slots ? n : d->B) + 255) / 256), dim3(256), 0, stream, (int32_t*)state,
+                     stride, d->B, slots, n);
   M3_LAUNCH_CHECK();
   return 0;
 }

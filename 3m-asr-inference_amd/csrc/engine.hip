@@ -113,6 +113,7 @@ struct m3_engine {
     // chunk-by-chunk (streaming) binding: T = 4 c + 3 input frames -> the c frames of one chunk; attention reads / extends the
     // K / V history and the causal depthwise conv its K-1 frame cache, both in the caller-owned state (m3_engine_forward_chunk)
     void* sstate = nullptr; int s_hist = 0, s_maxf = 0;
+    bool s_slots = false;   // slot mode (m3_engine_forward_chunk_slots): every utterance slot of the state has its own chunk counter
     // fork_embed: stages [fork_first, fork_mid) = the embed encoder (side branch of the captured graph), [fork_mid, join_at) =
     // what the main encoder does before it needs the embedding (embed_join); -1 = one linear chain
     int fork_first = -1, fork_mid = -1, join_at = -1;
@@ -127,9 +128,9 @@ struct m3_engine {
     bool graph_valid = false;
     uint64_t last_use = 0;
     bool matches(int b, int t, const float* f, const int32_t* fl, const float* lg, const void* w, size_t wb, int cap,
-                 const void* st = nullptr, int hist = 0, int maxf = 0) const {
+                 const void* st = nullptr, int hist = 0, int maxf = 0, bool slots = false) const {
       return !stages.empty() && B == b && T == t && feat == f && feat_len == fl && logits == lg && ws == w && ws_bytes == wb &&
-             ep_cap == cap && sstate == st && s_hist == hist && s_maxf == maxf;
+             ep_cap == cap && sstate == st && s_hist == hist && s_maxf == maxf && s_slots == slots;
     }
   };
   Bound cur;
@@ -461,10 +462,13 @@ Plan make_plan(const m3_engine_config& c, void* base, int B, int T, int ep_capac
 // Layout of the caller-owned streaming state (identical code computes the size and the addresses): the device-side chunk
 // counter, then per block (embed blocks first) the K | V history [B][hist][2 D] and the depthwise conv's ping-pong cache
 // [2][B][K-1][D] (post-GLU frames; the reference caches the module's INPUT and re-runs pointwise_conv1 + GLU on it,
-// convolution.py:118-123 -- the same numbers, since both are per-frame operations).
+// convolution.py:118-123 -- the same numbers, since both are per-frame operations).  Behind them, so that every offset above
+// is what it was before slot mode existed, three words per utterance slot: chunks decoded, status (1 = asked to run past
+// max_frames), output frames decoded.  Lockstep calls never touch them except m3_engine_stream_reset, which zeroes them.
 struct StreamState {
   int32_t* step = nullptr;
   std::vector<float*> kv, conv;
+  int32_t *slot_pos = nullptr, *slot_status = nullptr, *slot_frames = nullptr;   // [B] each, one allocation of 3 B words
   size_t bytes = 0;
 };
 StreamState carve_stream_state(const m3_engine_config& c, void* base, int B, int hist) {
@@ -474,6 +478,9 @@ StreamState carve_stream_state(const m3_engine_config& c, void* base, int B, int
   const int nb = c.embed_blocks + c.num_blocks, D = c.attention_dim, K = c.cnn_module_kernel;
   for (int i = 0; i < nb; ++i) st.kv.push_back(cv.take<float>((size_t)B * hist * 2 * D));
   for (int i = 0; i < nb; ++i) st.conv.push_back(cv.take<float>((size_t)2 * B * (K - 1) * D));
+  st.slot_pos = cv.take<int32_t>((size_t)3 * B);
+  st.slot_status = st.slot_pos ? st.slot_pos + B : nullptr;
+  st.slot_frames = st.slot_pos ? st.slot_pos + 2 * B : nullptr;
   st.bytes = cv.off;
   return st;
 }
@@ -969,9 +976,13 @@ static void build_block(m3_engine* e, const std::string& pfx, const BlockW& w, i
     const int chunk = c.static_chunk_size, left_chunks = c.num_left_chunks;   // static chunk mask (0 = full context)
     if (e->cur.sstate != nullptr) {   // chunk-by-chunk: keys = K / V history + this chunk, positions absolute, history appended in place
       const StreamState st = carve_stream_state(c, e->cur.sstate, B, e->cur.s_hist);
-      float* hist = st.kv[tap_index]; const int cap = e->cur.s_hist; const int32_t* step = st.step;
+      float* hist = st.kv[tap_index]; const int cap = e->cur.s_hist;
+      // slot mode: the counter of utterance b is slot_pos[b]; max_frames / c chunks fit (the kernels test a slot against it)
+      const int32_t* step = e->cur.s_slots ? st.slot_pos : st.step;
+      const int slot_chunks = e->cur.s_slots ? e->cur.s_maxf / Tp : -1;
       add_stage(e, pfx + "att.core", 1, [=](hipStream_t s) {
-        return launch_relpos_attention_stream(qkv, 3 * D, hist, cap, pmat, ldp, pu, pv, lens, step, B, Tp, H, dk, scale, ctx, D, left_chunks, s);
+        return launch_relpos_attention_stream(qkv, 3 * D, hist, cap, pmat, ldp, pu, pv, lens, step, B, Tp, H, dk, scale, ctx, D, left_chunks, s,
+                                              slot_chunks);
       }, stage_info("relpos_attention_stream_kernel", 1, (double)S * D * 24 + (double)Tp * D * 4, 6.0 * Tp * D * S));
     } else
     {
@@ -1009,9 +1020,11 @@ static void build_block(m3_engine* e, const std::string& pfx, const BlockW& w, i
     const float* lfill = causal ? w.left_fill : nullptr;   // causal conv module (convolution.py:43-49,118-123)
     if (e->cur.sstate != nullptr) {
       const StreamState st = carve_stream_state(c, e->cur.sstate, B, e->cur.s_hist);
-      float* cpair = st.conv[tap_index]; const int32_t* step = st.step;
+      float* cpair = st.conv[tap_index];
+      const int32_t* step = e->cur.s_slots ? st.slot_pos : st.step;
+      const int slot_chunks = e->cur.s_slots ? e->cur.s_maxf / Tp : -1;
       add_stage(e, pfx + "conv.dw_ln_silu", 1, [=](hipStream_t s) {
-        return launch_dwconv_ln_silu_stream(glu, dww, dwb, ng, nb, 1e-5f, B, Tp, D, K, dw, cpair, step, lens, s, a16);
+        return launch_dwconv_ln_silu_stream(glu, dww, dwb, ng, nb, 1e-5f, B, Tp, D, K, dw, cpair, step, lens, s, a16, slot_chunks);
       }, stage_info("dwconv_ln_silu_kernel", 1, (double)S * D * 8 + (double)K * D * 4 + 8.0 * B * (K - 1) * D, 2.0 * K * D * S));
     } else
     {
@@ -1190,7 +1203,7 @@ size_t m3_engine_workspace_size(const m3_engine* engine, int B, int T) {
 }
 
 static int prepare_impl(m3_engine* e, const float* feat, const int32_t* feat_len, int B, int T, float* logits,
-                        void* workspace, size_t workspace_bytes, void* sstate, int s_hist, int s_maxf) {
+                        void* workspace, size_t workspace_bytes, void* sstate, int s_hist, int s_maxf, bool s_slots = false) {
   M3_REQUIRE(e && feat && feat_len && logits && workspace, "engine_prepare: null argument");
   M3_REQUIRE(B > 0 && T >= 7, "engine_prepare: need B > 0 and T >= 7 frames (got B=%d T=%d)", B, T);
   const m3_engine_config& c = e->cfg;
@@ -1211,7 +1224,7 @@ static int prepare_impl(m3_engine* e, const float* feat, const int32_t* feat_len
   Plan pl = make_plan(c, workspace, B, T, e->ep_capacity);
   M3_REQUIRE(workspace_bytes >= pl.bytes, "engine_prepare: workspace %zu bytes < required %zu", workspace_bytes, pl.bytes);
   // ---- shape cache: park the current binding, revive a parked one with the same (shape, buffers) ----
-  if (e->cur.matches(B, T, feat, feat_len, logits, workspace, workspace_bytes, e->ep_capacity, sstate, s_hist, s_maxf)) {
+  if (e->cur.matches(B, T, feat, feat_len, logits, workspace, workspace_bytes, e->ep_capacity, sstate, s_hist, s_maxf, s_slots)) {
     e->cur.last_use = ++e->use_clock;
     return (int)e->cur.stages.size();
   }
@@ -1232,7 +1245,7 @@ static int prepare_impl(m3_engine* e, const float* feat, const int32_t* feat_len
     e->cur = m3_engine::Bound();
   }
   for (size_t i = 0; i < e->parked.size(); ++i)
-    if (e->parked[i].matches(B, T, feat, feat_len, logits, workspace, workspace_bytes, e->ep_capacity, sstate, s_hist, s_maxf)) {
+    if (e->parked[i].matches(B, T, feat, feat_len, logits, workspace, workspace_bytes, e->ep_capacity, sstate, s_hist, s_maxf, s_slots)) {
       e->cur = std::move(e->parked[i]);
       e->parked.erase(e->parked.begin() + i);
       e->cur.last_use = ++e->use_clock;
@@ -1242,7 +1255,7 @@ static int prepare_impl(m3_engine* e, const float* feat, const int32_t* feat_len
   e->cur.B = B; e->cur.T = T; e->cur.Tp = Tp; e->cur.S = B * Tp;
   e->cur.feat = feat; e->cur.feat_len = feat_len; e->cur.logits = logits; e->cur.ws = workspace; e->cur.ws_bytes = workspace_bytes;
   e->cur.ep_cap = e->ep_capacity;
-  e->cur.sstate = sstate; e->cur.s_hist = s_hist; e->cur.s_maxf = s_maxf;
+  e->cur.sstate = sstate; e->cur.s_hist = s_hist; e->cur.s_maxf = s_maxf; e->cur.s_slots = s_slots;
   const bool streaming = sstate != nullptr;
   e->cur.stages.clear(); e->cur.buffers.clear(); e->cur.n_kernels = 0; e->cur.graph_valid = false; e->cur.xn_skipped = false;
   e->cur.splitk_ws = pl.splitk; e->cur.splitk_bytes = pl.splitk_bytes;
@@ -1389,7 +1402,14 @@ static int prepare_impl(m3_engine* e, const float* feat, const int32_t* feat_len
   }
   if (pl.hfuse && !streaming && join > 0) fuse_independent_pairs(e, embed_start, main_start, join);
   if (streaming) {   // the chunk counter moves on the device: the same captured graph serves every chunk of the stream
-    int32_t* step = carve_stream_state(c, sstate, B, s_hist).step;
+    const StreamState st = carve_stream_state(c, sstate, B, s_hist);
+    int32_t* step = st.step;
+    if (s_slots) {   // one counter per utterance slot; a slot moves only if it was live in this chunk
+      int32_t *pos = st.slot_pos, *status = st.slot_status, *frames = st.slot_frames;
+      const int32_t* lens = pl.lens; const int max_chunks = s_maxf / Tp;
+      add_stage(e, "stream.advance", 1, [=](hipStream_t s) { return launch_advance_slots(pos, status, frames, lens, B, Tp, max_chunks, s); },
+                stage_info("advance_slots_kernel", 1, 20.0 * B, 0.0, false));
+    } else
     add_stage(e, "stream.advance", 1, [=](hipStream_t s) { return launch_advance_counter(step, 1, s); },
               stage_info("advance_counter_kernel", 1, 8.0, 0.0, false));
   }
@@ -1552,6 +1572,7 @@ int m3_engine_stream_reset(m3_engine* e, const m3_stream_desc* desc, void* state
   M3_REQUIRE(state != nullptr && state_bytes >= st.bytes, "engine_stream_reset: state %zu bytes < required %zu", state_bytes, st.bytes);
   hipStream_t stream = (hipStream_t)stream_;
   M3_CHECK_HIP(hipMemsetAsync(st.step, 0, 64 * sizeof(int32_t), stream));
+  M3_CHECK_HIP(hipMemsetAsync(st.slot_pos, 0, (size_t)3 * desc->B * sizeof(int32_t), stream));
   // the K-1 frames left of frame 0 are what the conv module's zero padding becomes behind pointwise_conv1 + GLU
   const int K = c.cnn_module_kernel, D = c.attention_dim, nb = c.embed_blocks + c.num_blocks;
   for (int i = 0; i < nb; ++i) {
@@ -1561,19 +1582,15 @@ int m3_engine_stream_reset(m3_engine* e, const m3_stream_desc* desc, void* state
   return 0;
 }
 
-int m3_engine_forward_chunk(m3_engine* e, const m3_stream_desc* desc, void* state, size_t state_bytes, const float* feat_chunk,
-                            const int32_t* chunk_feat_len, float* logits, void* workspace, size_t workspace_bytes, int chunk_index,
-                            int use_graph, m3_stream stream_) {
-  if (int rc = stream_check(e, desc)) return rc;
-  const m3_engine_config& c = e->cfg;
-  const int C = c.static_chunk_size, T = 4 * C + 3, B = desc->B;
-  const size_t need = carve_stream_state(c, nullptr, B, desc->history_frames).bytes;
-  M3_REQUIRE(state != nullptr && state_bytes >= need, "engine_forward_chunk: state %zu bytes < required %zu", state_bytes, need);
-  M3_REQUIRE(chunk_index >= 0 && (long)(chunk_index + 1) * C <= desc->max_frames,
-             "engine_forward_chunk: chunk %d ends past max_frames=%d (the stream is longer than the state was sized for)", chunk_index, desc->max_frames);
+// bind (or revive) the chunk binding of this (state, buffers, mode) and run it: eagerly, or as one hipGraph replay
+static int run_chunk(m3_engine* e, const m3_stream_desc* desc, void* state, const float* feat_chunk, const int32_t* chunk_feat_len,
+                     float* logits, void* workspace, size_t workspace_bytes, bool slots, int use_graph, m3_stream stream_) {
+  const int T = 4 * e->cfg.static_chunk_size + 3, B = desc->B;
   hipStream_t stream = (hipStream_t)stream_;
-  if (!e->cur.matches(B, T, feat_chunk, chunk_feat_len, logits, workspace, workspace_bytes, e->ep_capacity, state, desc->history_frames, desc->max_frames)) {
-    int rc = prepare_impl(e, feat_chunk, chunk_feat_len, B, T, logits, workspace, workspace_bytes, state, desc->history_frames, desc->max_frames);
+  if (!e->cur.matches(B, T, feat_chunk, chunk_feat_len, logits, workspace, workspace_bytes, e->ep_capacity, state, desc->history_frames,
+                      desc->max_frames, slots)) {
+    int rc = prepare_impl(e, feat_chunk, chunk_feat_len, B, T, logits, workspace, workspace_bytes, state, desc->history_frames,
+                          desc->max_frames, slots);
     if (rc < 0) return rc;
   }
   e->cur.last_use = ++e->use_clock;
@@ -1594,6 +1611,61 @@ int m3_engine_forward_chunk(m3_engine* e, const m3_stream_desc* desc, void* stat
   }
   M3_CHECK_HIP(hipGraphLaunch(e->cur.graph_exec, stream));
   return 0;
+}
+
+int m3_engine_forward_chunk(m3_engine* e, const m3_stream_desc* desc, void* state, size_t state_bytes, const float* feat_chunk,
+                            const int32_t* chunk_feat_len, float* logits, void* workspace, size_t workspace_bytes, int chunk_index,
+                            int use_graph, m3_stream stream_) {
+  if (int rc = stream_check(e, desc)) return rc;
+  const m3_engine_config& c = e->cfg;
+  const int C = c.static_chunk_size, B = desc->B;
+  const size_t need = carve_stream_state(c, nullptr, B, desc->history_frames).bytes;
+  M3_REQUIRE(state != nullptr && state_bytes >= need, "engine_forward_chunk: state %zu bytes < required %zu", state_bytes, need);
+  M3_REQUIRE(chunk_index >= 0 && (long)(chunk_index + 1) * C <= desc->max_frames,
+             "engine_forward_chunk: chunk %d ends past max_frames=%d (the stream is longer than the state was sized for)", chunk_index, desc->max_frames);
+  return run_chunk(e, desc, state, feat_chunk, chunk_feat_len, logits, workspace, workspace_bytes, false, use_graph, stream_);
+}
+
+// ---- slot mode: the B streams of a state start, pause and end independently ------------------------------------------------
+// Position is a property of the slot: the attention core, the depthwise conv and stream.advance read utterance b's own chunk
+// counter (StreamState::slot_pos), and a slot with no output frame in a chunk (or one that would run past max_frames) is left
+// exactly as it was.  Which slots are live is device data (chunk_feat_len), so every chunk is still one replay of one graph.
+int m3_engine_forward_chunk_slots(m3_engine* e, const m3_stream_desc* desc, void* state, size_t state_bytes, const float* feat_chunk,
+                                  const int32_t* chunk_feat_len, float* logits, void* workspace, size_t workspace_bytes,
+                                  int use_graph, m3_stream stream_) {
+  if (int rc = stream_check(e, desc)) return rc;
+  const size_t need = carve_stream_state(e->cfg, nullptr, desc->B, desc->history_frames).bytes;
+  M3_REQUIRE(state != nullptr && state_bytes >= need, "engine_forward_chunk_slots: state %zu bytes < required %zu", state_bytes, need);
+  return run_chunk(e, desc, state, feat_chunk, chunk_feat_len, logits, workspace, workspace_bytes, true, use_graph, stream_);
+}
+
+int m3_engine_stream_reset_slots(m3_engine* e, const m3_stream_desc* desc, void* state, size_t state_bytes, const int32_t* slots,
+                                 int n, m3_stream stream_) {
+  if (int rc = stream_check(e, desc)) return rc;
+  const m3_engine_config& c = e->cfg;
+  const StreamState st = carve_stream_state(c, state, desc->B, desc->history_frames);
+  M3_REQUIRE(state != nullptr && state_bytes >= st.bytes, "engine_stream_reset_slots: state %zu bytes < required %zu", state_bytes, st.bytes);
+  M3_REQUIRE(n >= 0 && (n == 0 || slots != nullptr), "engine_stream_reset_slots: bad slot list (n=%d)", n);
+  const int nb = c.embed_blocks + c.num_blocks;
+  M3_REQUIRE(nb <= kMaxStreamBlocks, "engine_stream_reset_slots: %d blocks > %d", nb, kMaxStreamBlocks);
+  SlotResetArgs a;
+  a.pos = st.slot_pos; a.status = st.slot_status; a.frames = st.slot_frames; a.slots = slots; a.n = n;
+  a.B = desc->B; a.K = c.cnn_module_kernel; a.D = c.attention_dim; a.n_blocks = nb;
+  for (int i = 0; i < kMaxStreamBlocks; ++i) { a.conv[i] = nullptr; a.fill[i] = nullptr; }
+  for (int i = 0; i < nb; ++i) {
+    a.conv[i] = st.conv[i];
+    a.fill[i] = (i < c.embed_blocks ? e->eblocks[i] : e->mblocks[i - c.embed_blocks]).left_fill;
+  }
+  return launch_reset_slots(a, (hipStream_t)stream_);
+}
+
+int m3_engine_stream_positions(m3_engine* e, const m3_stream_desc* desc, const void* state, size_t state_bytes, int32_t* frames,
+                               m3_stream stream_) {
+  if (int rc = stream_check(e, desc)) return rc;
+  const StreamState st = carve_stream_state(e->cfg, const_cast<void*>(state), desc->B, desc->history_frames);
+  M3_REQUIRE(state != nullptr && state_bytes >= st.bytes && frames != nullptr, "engine_stream_positions: null pointer or state %zu bytes < required %zu",
+             state_bytes, st.bytes);
+  return launch_slot_positions(st.slot_status, st.slot_frames, desc->B, frames, (hipStream_t)stream_);
 }
 
 }  // extern "C"

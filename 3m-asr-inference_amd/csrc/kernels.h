@@ -233,7 +233,8 @@ int launch_relpos_attention_dual(const AttArgs& a, const AttArgs& b, hipStream_t
 // chunk-by-chunk form: C query frames per utterance, K / V history [B][cap][2D] appended to in place, device-side chunk counter
 int launch_relpos_attention_stream(const float* qkv, int ldq, float* hist, int cap, const float* pmat, int ldp, const float* pos_u,
                                    const float* pos_v, const int32_t* chunk_len, const int32_t* step, int B, int C, int H, int dk,
-                                   float scale, float* out, int ldo, int left_chunks, hipStream_t stream);
+                                   float scale, float* out, int ldo, int left_chunks, hipStream_t stream,
+                                   int slot_max_chunks = -1);   // >= 0: slot mode, step [B] = one counter per slot, max_frames / C
 
 // the same on bf16 rows (16-bit modes, T' <= 128): qkv bf16 [B*T][ldq], out bf16; one work-group per (utterance, head)
 bool relpos_attention_bf16_supports(int T, int dk);
@@ -250,6 +251,19 @@ int launch_dwconv_ln_silu(const float* z, const float* w_kc, const float* bias, 
 int launch_pad2d(const float* x, size_t outer, int H, int W, int pre_h, int post_h, int pre_w, int post_w, float* y, hipStream_t stream);
 int launch_advance_counter(int32_t* counter, int by, hipStream_t stream);
 int launch_fill_rows(const float* row, int D, float* out, size_t rows, hipStream_t stream);
+// streaming in slot mode (rowops.hip): per-slot words pos / status / frames [B] each
+int launch_advance_slots(int32_t* pos, int32_t* status, int32_t* frames, const int32_t* chunk_len, int B, int C, int max_chunks,
+                         hipStream_t stream);
+constexpr int kMaxStreamBlocks = 64;      // conformer blocks (embed + main) one restart launch covers
+struct SlotResetArgs {
+  int32_t *pos = nullptr, *status = nullptr, *frames = nullptr;
+  const int32_t* slots = nullptr; int n = 0;      // device list of the slots to restart (values outside [0, B) are skipped)
+  int B = 0, K = 0, D = 0, n_blocks = 0;
+  float* conv[kMaxStreamBlocks];                  // per block the ping-pong conv cache [2][B][K-1][D]
+  const float* fill[kMaxStreamBlocks];            // per block its left_fill row [D]
+};
+int launch_reset_slots(const SlotResetArgs& a, hipStream_t stream);
+int launch_slot_positions(const int32_t* status, const int32_t* frames, int B, int32_t* out, hipStream_t stream);
 // the same as a value (what the engine keeps per stage so that two independent conv modules can share a launch)
 struct DwArgs {
   const float *z = nullptr, *w_kc = nullptr, *bias = nullptr, *gamma = nullptr, *beta = nullptr; float eps = 1e-5f;
@@ -261,7 +275,8 @@ bool dwconv_dual_fusable(const DwArgs& a, const DwArgs& b);
 int launch_dwconv_ln_silu_dual(const DwArgs& a, const DwArgs& b, hipStream_t stream);
 int launch_dwconv_ln_silu_stream(const float* z, const float* w_kc, const float* bias, const float* gamma, const float* beta,
                                  float eps, int B, int T, int D, int K, float* out, float* cache_pair, const int32_t* step,
-                                 const int32_t* chunk_len, hipStream_t stream, int out_bf16 = 0);
+                                 const int32_t* chunk_len, hipStream_t stream, int out_bf16 = 0,
+                                 int slot_max_chunks = -1);     // >= 0: slot mode, step [B]
 // packed (padding-free) rows of a ragged batch (rowops.hip): plan from the valid lengths; padded output from packed rows
 int launch_pack_plan(int32_t* len, int B, int T, int32_t* row0, int32_t* pad_of, hipStream_t stream,
                      const int32_t* feat_len = nullptr);   // feat_len: form the subsampled lengths here too (len becomes an output)
@@ -281,13 +296,15 @@ int ctc_prefix_beam_search_host(const float* top_logp, const int32_t* top_idx, i
 int launch_ctc_argmax(const float* logits, size_t rows, int V, int32_t* ids, hipStream_t stream);
 // ctc_beam.hip: batched resumable prefix beam search and the streaming greedy search on the device
 size_t ctc_beam_state_size(const m3_ctc_beam_desc* d);
-int launch_ctc_beam_reset(const m3_ctc_beam_desc* d, void* state, size_t bytes, hipStream_t stream);
+int launch_ctc_beam_reset(const m3_ctc_beam_desc* d, void* state, size_t bytes, hipStream_t stream,
+                          const int32_t* slots = nullptr, int n = 0);   // slots (device, n entries): only those utterances
 int launch_ctc_beam_advance(const m3_ctc_beam_desc* d, void* state, size_t bytes, const float* top_logp, const int32_t* top_idx,
                             int T_chunk, const int32_t* n_frames, hipStream_t stream);
 int launch_ctc_beam_nbest(const m3_ctc_beam_desc* d, const void* state, size_t bytes, int32_t* hyp_tokens, int32_t* hyp_len,
                           float* hyp_score, int32_t* n_hyps, hipStream_t stream);
 size_t ctc_greedy_stream_state_size(const m3_ctc_greedy_desc* d);
-int launch_ctc_greedy_stream_reset(const m3_ctc_greedy_desc* d, void* state, size_t bytes, hipStream_t stream);
+int launch_ctc_greedy_stream_reset(const m3_ctc_greedy_desc* d, void* state, size_t bytes, hipStream_t stream,
+                                   const int32_t* slots = nullptr, int n = 0);
 int launch_ctc_greedy_stream_advance(const m3_ctc_greedy_desc* d, void* state, size_t bytes, const float* logits, int T_chunk,
                                      int V, const int32_t* n_frames, int32_t* frame_ids, hipStream_t stream);
 int launch_ctc_greedy_stream_tokens(const m3_ctc_greedy_desc* d, const void* state, size_t bytes, int32_t* tokens,

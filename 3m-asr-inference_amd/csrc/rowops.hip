@@ -511,6 +511,71 @@ int launch_fill_rows(const float* row, int D, float* out, size_t rows, hipStream
   return 0;
 }
 
+// ---- slot mode: every utterance slot of a streaming state has its own words pos (chunks decoded), status (1 = it was asked
+//      to run past max_frames) and frames (output frames decoded).  A slot moves only when it was live in the chunk.
+__global__ void advance_slots_kernel(int32_t* __restrict__ pos, int32_t* __restrict__ status, int32_t* __restrict__ frames,
+                                     const int32_t* __restrict__ chunk_len, int B, int C, int max_chunks) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int n = chunk_len[b], p = pos[b];
+  if (n <= 0) return;                                        // idle: nothing moves
+  if (stream_slot_live(n, p, max_chunks)) {
+    pos[b] = p + 1;
+    frames[b] += min(n, C);
+  } else {
+    status[b] = 1;                                           // its chunk would end past max_frames: every kernel left it alone
+  }
+}
+int launch_advance_slots(int32_t* pos, int32_t* status, int32_t* frames, const int32_t* chunk_len, int B, int C, int max_chunks,
+                         hipStream_t stream) {
+  M3_REQUIRE(pos && status && frames && chunk_len && B > 0 && C > 0 && max_chunks > 0, "advance_slots: bad argument");
+  hipLaunchKernelGGL(advance_slots_kernel, dim3(cdiv(B, 64)), dim3(64), 0, stream, pos, status, frames, chunk_len, B, C, max_chunks);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+// Restart of the listed slots in one launch: grid (n * 2 * (K-1), blocks); work-group (j, half, frame) of block i refills one
+// cache row of slot slots[j] with that block's left_fill row, the first work-group also zeroes the slots' words.
+__global__ __launch_bounds__(128) void reset_slots_kernel(const SlotResetArgs a) {
+  const int rows = 2 * (a.K - 1);
+  const int j = blockIdx.x / rows, r = blockIdx.x - j * rows, half = r / (a.K - 1), ci = r - half * (a.K - 1);
+  const int i = blockIdx.y;
+  if (blockIdx.x == 0 && i == 0) {
+    for (int t = threadIdx.x; t < a.n; t += blockDim.x) {
+      const int sb = a.slots[t];
+      if (sb >= 0 && sb < a.B) {
+        a.pos[sb] = 0;
+        a.status[sb] = 0;
+        a.frames[sb] = 0;
+      }
+    }
+  }
+  const int b = a.slots[j];
+  if (b < 0 || b >= a.B) return;
+  float* dst = a.conv[i] + (((size_t)half * a.B + b) * (a.K - 1) + ci) * a.D;
+  const float* src = a.fill[i];
+  for (int c = threadIdx.x * 4; c < a.D; c += blockDim.x * 4) stg4(dst + c, ldg4(src + c));
+}
+int launch_reset_slots(const SlotResetArgs& a, hipStream_t stream) {
+  M3_REQUIRE(a.pos && a.status && a.frames && a.n >= 0 && a.B > 0 && a.K >= 2 && (a.D & 3) == 0 && a.n_blocks > 0 &&
+             a.n_blocks <= kMaxStreamBlocks, "reset_slots: bad argument (at most %d blocks)", kMaxStreamBlocks);
+  if (a.n == 0) return 0;
+  M3_REQUIRE(a.slots != nullptr, "reset_slots: null slot list");
+  hipLaunchKernelGGL(reset_slots_kernel, dim3((unsigned)(a.n * 2 * (a.K - 1)), (unsigned)a.n_blocks), dim3(128), 0, stream, a);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+__global__ void slot_positions_kernel(const int32_t* __restrict__ status, const int32_t* __restrict__ frames, int B,
+                                      int32_t* __restrict__ out) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) out[b] = status[b] != 0 ? -1 : frames[b];
+}
+int launch_slot_positions(const int32_t* status, const int32_t* frames, int B, int32_t* out, hipStream_t stream) {
+  M3_REQUIRE(status && frames && out && B > 0, "slot_positions: bad argument");
+  hipLaunchKernelGGL(slot_positions_kernel, dim3(cdiv(B, 64)), dim3(64), 0, stream, status, frames, B, out);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
 // both MaskConv2dSample applications of Conv2dSubsampling4 in one launch (subsampling.py:119-137)
 __global__ void subsample_lens_kernel(const int32_t* __restrict__ in, int B, int32_t* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

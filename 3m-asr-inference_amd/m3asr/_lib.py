@@ -138,10 +138,12 @@ SIGNATURES = {
     "m3_ctc_prefix_beam_search": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "m3_ctc_beam_state_size": (_sz, [_P(CtcBeamDesc)]),
     "m3_ctc_beam_reset": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp]),
+    "m3_ctc_beam_reset_slots": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp, _i, _vp]),
     "m3_ctc_beam_advance": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp, _vp, _i, _vp, _vp]),
     "m3_ctc_beam_nbest": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     "m3_ctc_greedy_stream_state_size": (_sz, [_P(CtcGreedyDesc)]),
     "m3_ctc_greedy_stream_reset": (_i, [_P(CtcGreedyDesc), _vp, _sz, _vp]),
+    "m3_ctc_greedy_stream_reset_slots": (_i, [_P(CtcGreedyDesc), _vp, _sz, _vp, _i, _vp]),
     "m3_ctc_greedy_stream_advance": (_i, [_P(CtcGreedyDesc), _vp, _sz, _vp, _i, _i, _vp, _vp, _vp]),
     "m3_ctc_greedy_stream_tokens": (_i, [_P(CtcGreedyDesc), _vp, _sz, _vp, _vp, _vp]),
     "m3_cat_split_cache": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
@@ -170,6 +172,9 @@ SIGNATURES = {
     "m3_engine_stream_state_size": (_sz, [_vp, _P(StreamDesc)]),
     "m3_engine_stream_reset": (_i, [_vp, _P(StreamDesc), _vp, _sz, _vp]),
     "m3_engine_forward_chunk": (_i, [_vp, _P(StreamDesc), _vp, _sz, _vp, _vp, _vp, _vp, _sz, _i, _i, _vp]),
+    "m3_engine_stream_reset_slots": (_i, [_vp, _P(StreamDesc), _vp, _sz, _vp, _i, _vp]),
+    "m3_engine_forward_chunk_slots": (_i, [_vp, _P(StreamDesc), _vp, _sz, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
+    "m3_engine_stream_positions": (_i, [_vp, _P(StreamDesc), _vp, _sz, _vp, _vp]),
     "m3_engine_set_ep_capacity": (_i, [_vp, _i]),
     "m3_engine_num_captures": (_i, [_vp]),
     "m3_engine_num_stages": (_i, [_vp]),

@@ -51,9 +51,13 @@ class CtcBeamSearch:
     def beam(self):
         return self.desc.beam
 
-    def reset(self, stream=None):
+    def reset(self, stream=None, slots=None):
+        """slots: None = all B searches; else the utterances to restart (a list, or an int32 device tensor)."""
         with torch.cuda.stream(stream or torch.cuda.current_stream(self.device)):
-            ops.ctc_beam_reset(self.desc, self.state)
+            if slots is not None and not torch.is_tensor(slots):
+                slots = torch.tensor([int(b) for b in slots], dtype=torch.int32).to(self.device)
+            if slots is None or slots.numel() > 0:
+                ops.ctc_beam_reset(self.desc, self.state, slots)
 
     def advance(self, logits, n_frames, stream=None):
         """logits (B, Tc, V) on the device; n_frames (B,) how many of each row's Tc frames are real.  Enqueues m3_ctc_topk and
@@ -73,11 +77,12 @@ class CtcBeamSearch:
         with torch.cuda.stream(stream or torch.cuda.current_stream(self.device)):
             return ops.ctc_beam_nbest(self.desc, self.state)
 
-    def nbest(self, stream=None):
+    def nbest(self, stream=None, slots=None):
+        """slots: None = every utterance; else only the listed ones, in that order (the others may have failed or be idle)."""
         with torch.cuda.stream(stream or torch.cuda.current_stream(self.device)):   # the copies wait for the search's stream
             toks, hlen, score, n = (t.cpu() for t in ops.ctc_beam_nbest(self.desc, self.state))
         out = []
-        for b in range(self.B):
+        for b in (range(self.B) if slots is None else [int(x) for x in slots]):
             nb = int(n[b])
             if nb < 0:
                 raise _lib.M3Error("ctc beam search: utterance %d consumed more than max_frames = %d frames"
@@ -173,7 +178,10 @@ class StreamingCtcDecoder:
 
     The output frames of a chunk that count for a stream follow StreamingEncoder.decode: frames t < T'(len) of an utterance of
     len >= 7 feature frames.  step() derives them from `valid` (min(T'(valid), c), 0 for valid < 7); a caller that knows
-    the utterance lengths passes them as n_out (decode() does)."""
+    the utterance lengths passes them as n_out (decode() does).
+
+    Over a slot-mode encoder (engine.streaming(..., independent=True)) the streams are independent here too: a slot that is
+    idle in a step consumes no frame in either search, and reset / partial / finish take `slots=[...]`."""
 
     def __init__(self, streaming_encoder, beam, blank=0):
         self.st = streaming_encoder
@@ -187,12 +195,21 @@ class StreamingCtcDecoder:
         self.n_out = torch.zeros(B, dtype=torch.int32, device=e.device)
         self.reset()
 
-    def reset(self):
+    def reset(self, slots=None):
+        """Restart all streams, or (slot-mode encoder) the listed slots: encoder state, beam search and greedy search."""
         e = self.st.eng
-        self.st.reset()
+        if slots is None:
+            self.st.reset()
+        else:
+            self.st.reset(slots=slots)
         with torch.cuda.stream(e.stream):
-            self.beam.reset(e.stream)
-            ops.ctc_greedy_stream_reset(self.gdesc, self.gstate)
+            if slots is None:
+                self.beam.reset(e.stream)
+                ops.ctc_greedy_stream_reset(self.gdesc, self.gstate)
+            elif len(slots) > 0:
+                lst = torch.tensor([int(b) for b in slots], dtype=torch.int32).to(e.device)
+                self.beam.reset(e.stream, slots=lst)
+                ops.ctc_greedy_stream_reset(self.gdesc, self.gstate, lst)
 
     def frames_of(self, valid):
         """Output frames of this chunk that count, from the real feature frames in its window."""
@@ -212,26 +229,27 @@ class StreamingCtcDecoder:
             ops.ctc_greedy_stream_advance(self.gdesc, self.gstate, logits, self.n_out, self.frame_ids)
         return logits
 
-    def greedy(self):
-        """Greedy hypotheses of the frames so far: [[token, ...]] per stream."""
+    def greedy(self, slots=None):
+        """Greedy hypotheses of the frames so far: [[token, ...]] per stream (slots: only the listed streams)."""
         e = self.st.eng
         with torch.cuda.stream(e.stream):
             toks, n = ops.ctc_greedy_stream_tokens(self.gdesc, self.gstate)
         e.stream.synchronize()
         toks, n = toks.cpu(), n.cpu().tolist()
-        if min(n, default=0) < 0:
+        which = list(range(len(n))) if slots is None else [int(b) for b in slots]
+        if min((n[b] for b in which), default=0) < 0:
             raise _lib.M3Error("streaming greedy search: a stream ran past max_frames")
-        return [toks[b, :k].tolist() for b, k in enumerate(n)]
+        return [toks[b, :n[b]].tolist() for b in which]
 
-    def partial(self):
+    def partial(self, slots=None):
         """(best prefix beam hypothesis (prefix, score) per stream, greedy tokens per stream) after the chunks so far."""
         e = self.st.eng
-        nb = self.beam.nbest(e.stream)
-        return [h[0] for h in nb], self.greedy()
+        nb = self.beam.nbest(e.stream, slots=slots)
+        return [h[0] for h in nb], self.greedy(slots)
 
-    def finish(self):
-        """n-best [(prefix, score)] per stream, best first."""
-        return self.beam.nbest(self.st.eng.stream)
+    def finish(self, slots=None):
+        """n-best [(prefix, score)] per stream, best first (slots: only the listed streams, in that order)."""
+        return self.beam.nbest(self.st.eng.stream, slots=slots)
 
     def decode(self, feat, feat_len, use_graph=True):
         """Whole utterances chunk by chunk (the windows and frame counts of StreamingEncoder.decode) -> finish()."""

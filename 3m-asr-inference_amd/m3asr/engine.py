@@ -194,9 +194,10 @@ class Engine:
         self.stream.synchronize()
         return out
 
-    def streaming(self, B, max_frames, history_frames=None):
-        """A set of B streams decoded chunk by chunk (see StreamingEncoder)."""
-        return StreamingEncoder(self, B, max_frames, history_frames)
+    def streaming(self, B, max_frames, history_frames=None, independent=False):
+        """A set of B streams decoded chunk by chunk (see StreamingEncoder).  independent=True: slot mode, every stream starts,
+        pauses and ends on its own."""
+        return StreamingEncoder(self, B, max_frames, history_frames, independent)
 
     # ---- staged execution / taps ---------------------------------------------------------
     def stage_names(self):
@@ -267,10 +268,16 @@ class StreamingEncoder:
         for n in range(n_chunks):
             logits_chunk = st.step(window_n, valid_n)      # (B, c, V); window_n (B, 4c+3, idim), valid_n (B,) real frames in it
 
-    `decode(feat, feat_len)` cuts whole utterances into windows itself and returns (B, T', V) like Engine.__call__."""
+    `decode(feat, feat_len)` cuts whole utterances into windows itself and returns (B, T', V) like Engine.__call__.
 
-    def __init__(self, engine, B, max_frames, history_frames=None):
+    independent=True (slot mode, m3_engine_forward_chunk_slots): position is a property of the slot.  A slot whose `valid` is 0
+    in a step is idle: its counter, history and conv cache stay as they are, so its stream pauses, and `reset(slots=[...])`
+    restarts single slots while the others go on.  The window handed over for slot b is the one at ITS next position;
+    `positions()` tells where every slot stands.  Every step is still one replay of one graph."""
+
+    def __init__(self, engine, B, max_frames, history_frames=None, independent=False):
         self.eng, cfg = engine, engine.cfg
+        self.independent = bool(independent)
         self.c = int(cfg.static_chunk_size)
         if self.c <= 0 or not (cfg.causal and cfg.embed_causal):
             raise _lib.M3Error("StreamingEncoder needs static_chunk_size > 0 and causal conv modules in both encoders")
@@ -290,18 +297,79 @@ class StreamingEncoder:
         self.logits = torch.empty(B, self.c, cfg.output_dim, dtype=torch.float32, device=dev)
         self.ws = torch.empty(engine.workspace_size(B, self.window), dtype=torch.uint8, device=dev)
         self.chunks = 0
+        self.slot_chunks = None           # slot mode: host mirror of the per-slot chunk counters (None: not known)
         self.reset()
 
-    def reset(self):
+    def reset(self, slots=None):
+        """Restart all B streams, or (slot mode) the listed slots only: one launch, the other slots go on untouched."""
         e = self.eng
-        check(e.lib.m3_engine_stream_reset(e.handle, C.byref(self.desc), self.state.data_ptr(), self.state.numel(),
-                                           C.c_void_p(e.stream.cuda_stream)), "m3_engine_stream_reset")
-        self.chunks = 0
+        if slots is None:
+            check(e.lib.m3_engine_stream_reset(e.handle, C.byref(self.desc), self.state.data_ptr(), self.state.numel(),
+                                               C.c_void_p(e.stream.cuda_stream)), "m3_engine_stream_reset")
+            self.chunks = 0
+            self.slot_chunks = [0] * int(self.desc.B) if self.independent else None
+            return
+        if not self.independent:
+            raise _lib.M3Error("StreamingEncoder.reset(slots=...): the lockstep state restarts all streams together "
+                               "(use engine.streaming(..., independent=True))")
+        slots = [int(b) for b in slots]
+        if any(b < 0 or b >= self.desc.B for b in slots):
+            raise _lib.M3Error("StreamingEncoder.reset: slots %s outside [0, %d)" % (slots, self.desc.B))
+        if not slots:
+            return
+        with torch.cuda.stream(e.stream):
+            self._reset_list = torch.tensor(slots, dtype=torch.int32).to(e.device)    # kept alive until the next restart
+        check(e.lib.m3_engine_stream_reset_slots(e.handle, C.byref(self.desc), self.state.data_ptr(), self.state.numel(),
+                                                 self._reset_list.data_ptr(), len(slots), C.c_void_p(e.stream.cuda_stream)),
+              "m3_engine_stream_reset_slots")
+        if self.slot_chunks is not None:
+            for b in slots:
+                self.slot_chunks[b] = 0
+
+    def positions(self):
+        """Slot mode: output frames every slot has decoded since its restart, (B,) int32 on the host; -1 for a slot that was
+        asked to run past max_frames."""
+        e = self.eng
+        if not self.independent:
+            raise _lib.M3Error("StreamingEncoder.positions: only in slot mode (independent=True)")
+        out = torch.empty(int(self.desc.B), dtype=torch.int32, device=e.device)
+        check(e.lib.m3_engine_stream_positions(e.handle, C.byref(self.desc), self.state.data_ptr(), self.state.numel(),
+                                               out.data_ptr(), C.c_void_p(e.stream.cuda_stream)), "m3_engine_stream_positions")
+        e.stream.synchronize()
+        return out.cpu()
+
+    def _step_slots(self, window, valid, use_graph):
+        e = self.eng
+        valid = torch.as_tensor(valid)
+        if valid.device.type == "cpu":      # the host knows who is live: refuse BEFORE launching, as the lockstep path does
+            live = [int(v) >= 7 for v in valid.reshape(-1)]
+            valid = torch.where(valid >= 7, valid, torch.zeros_like(valid))
+            if self.slot_chunks is not None:
+                over = [b for b, l in enumerate(live) if l and (self.slot_chunks[b] + 1) * self.c > self.desc.max_frames]
+                if over:
+                    raise _lib.M3Error("StreamingEncoder.step: slots %s would run past max_frames=%d (the streams are longer than "
+                                       "the state was sized for)" % (over, self.desc.max_frames))
+                for b, l in enumerate(live):
+                    self.slot_chunks[b] += int(l)
+        else:
+            self.slot_chunks = None         # liveness is device data: the kernels' own test holds (positions() reports -1)
+        with torch.cuda.stream(e.stream):
+            self.feat.copy_(window, non_blocking=True)
+            self.valid.copy_(valid.to(torch.int32).reshape(-1), non_blocking=True)
+        check(e.lib.m3_engine_forward_chunk_slots(e.handle, C.byref(self.desc), self.state.data_ptr(), self.state.numel(),
+                                                  self.feat.data_ptr(), self.valid.data_ptr(), self.logits.data_ptr(),
+                                                  self.ws.data_ptr(), self.ws.numel(), int(use_graph),
+                                                  C.c_void_p(e.stream.cuda_stream)), "m3_engine_forward_chunk_slots")
+        self.chunks += 1
+        return self.logits
 
     def step(self, window, valid, use_graph=True):
         """One chunk: window (B, 4c+3, idim) feature frames starting at input frame 4 c n, valid (B,) how many of them are
         real (pass 0 for an utterance with fewer than 7 frames left: no output frame fits).  Returns this object's logits
-        buffer (B, c, V), valid until the next step."""
+        buffer (B, c, V), valid until the next step.  Slot mode: n is slot b's own chunk count, valid[b] = 0 leaves slot b
+        where it is; with a host `valid` a live slot that would pass max_frames raises before anything is launched."""
+        if self.independent:
+            return self._step_slots(window, valid, use_graph)
         e = self.eng
         with torch.cuda.stream(e.stream):
             self.feat.copy_(window, non_blocking=True)

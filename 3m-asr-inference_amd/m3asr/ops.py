@@ -386,7 +386,12 @@ def ctc_beam_state_size(desc):
     return n
 
 
-def ctc_beam_reset(desc, state):
+def ctc_beam_reset(desc, state, slots=None):
+    """slots: None = every utterance; else an int32 device tensor listing the utterances to restart."""
+    if slots is not None:
+        check(_lib.load().m3_ctc_beam_reset_slots(C.byref(desc), _p(state), state.numel() * state.element_size(), _i32(slots),
+                                                  slots.numel(), _stream()), "m3_ctc_beam_reset_slots")
+        return
     check(_lib.load().m3_ctc_beam_reset(C.byref(desc), _p(state), state.numel() * state.element_size(), _stream()),
           "m3_ctc_beam_reset")
 
@@ -423,7 +428,11 @@ def ctc_greedy_stream_state_size(desc):
     return _lib.load().m3_ctc_greedy_stream_state_size(C.byref(desc))
 
 
-def ctc_greedy_stream_reset(desc, state):
+def ctc_greedy_stream_reset(desc, state, slots=None):
+    if slots is not None:
+        check(_lib.load().m3_ctc_greedy_stream_reset_slots(C.byref(desc), _p(state), state.numel() * state.element_size(),
+                                                           _i32(slots), slots.numel(), _stream()), "m3_ctc_greedy_stream_reset_slots")
+        return
     check(_lib.load().m3_ctc_greedy_stream_reset(C.byref(desc), _p(state), state.numel() * state.element_size(), _stream()),
           "m3_ctc_greedy_stream_reset")
 

@@ -1,0 +1,168 @@
+"""Sessions that come and go on one batched streaming state: StreamPool, what a live service calls.
+
+A pool owns the B slots of a slot-mode StreamingCtcDecoder (engine.streaming(B, max_frames, independent=True)).  Audio
+arrives per session in pieces of any size; every `step()` is ONE engine call in which each session that has a window ready is
+live and every other slot idle.
+
+    pool = StreamPool(StreamingCtcDecoder(engine.streaming(B, max_frames, independent=True), beam=10))
+    sid = pool.open()                       # takes a free slot, restarts it
+    pool.push(sid, frames)                  # (n, idim) feature frames, any n
+    pool.end(sid)                           # no more audio for this session
+    live = pool.step()                      # sids that moved one chunk
+    best, greedy = pool.partial(sid)
+    nbest = pool.close(sid)                 # frees the slot
+
+The window rule is the one StreamingEncoder.decode applies to whole utterances (window n of a stream starts at its input
+frame 4 c n, holds 4 c + 3 frames, overlaps the next by 3; fewer than 7 real frames count as none).  It lives in
+`next_window_valid` / `WindowBuffer`, host-only code.
+"""
+import torch
+
+from . import _lib
+
+
+def next_window_valid(buffered, chunks_done, chunk, ended):
+    """Real frames in the next window of a stream, or 0 when that window cannot run yet (or never will).
+
+    buffered: feature frames the stream has received since it began; chunks_done: windows already taken; chunk: c, output
+    frames per chunk; ended: no more frames will come.  A window runs when it is full (4 c + 3 frames), or when the stream
+    has ended and at least 7 frames remain from the window's start (the last, short window)."""
+    window = 4 * chunk + 3
+    left = buffered - 4 * chunk * chunks_done
+    if left >= window:
+        return window
+    if ended and left >= 7:
+        return left
+    return 0
+
+
+class WindowBuffer:
+    """Feature frames of one stream, pushed in arbitrary pieces, handed back as the windows of chunked decoding."""
+
+    def __init__(self, chunk, input_dim):
+        self.c, self.idim = int(chunk), int(input_dim)
+        self.window = 4 * self.c + 3
+        self.buf = torch.zeros(0, self.idim)      # frames from input frame self.base on
+        self.base = 0
+        self.total = 0
+        self.chunks = 0
+        self.ended = False
+
+    def push(self, frames):
+        if self.ended:
+            raise ValueError("push after end")
+        frames = torch.as_tensor(frames, dtype=torch.float32).reshape(-1, self.idim).cpu()
+        self.buf = torch.cat([self.buf, frames])
+        self.total += int(frames.shape[0])
+
+    def end(self):
+        self.ended = True
+
+    def ready(self):
+        """Real frames of the next window if it can run now, else 0."""
+        return next_window_valid(self.total, self.chunks, self.c, self.ended)
+
+    def drained(self):
+        """The stream has ended and no further window will run."""
+        return self.ended and self.ready() == 0
+
+    def take(self, out=None):
+        """The next window as (window (4c+3, idim) zero padded behind its real frames, valid); advances by one chunk."""
+        valid = self.ready()
+        if valid == 0:
+            raise ValueError("no window ready")
+        start = 4 * self.c * self.chunks - self.base
+        win = torch.zeros(self.window, self.idim) if out is None else out
+        win.zero_()
+        win[:valid] = self.buf[start:start + valid]
+        self.chunks += 1
+        drop = 4 * self.c * self.chunks - self.base          # frames left of the next window are never read again
+        if drop > 0:
+            self.buf = self.buf[min(drop, self.buf.shape[0]):]
+            self.base += drop
+        return win, valid
+
+
+class StreamPool:
+    """B slots of a slot-mode streaming decoder shared by sessions that open and close at any time.
+
+    decoder: a StreamingCtcDecoder over a slot-mode StreamingEncoder, or any object with `step(window (B, 4c+3, idim), valid
+    (B,))`, `reset(slots=[...])`, `partial(slots=[...])`, `finish(slots=[...])`; B, chunk and input_dim are read from
+    `decoder.st` unless given."""
+
+    def __init__(self, decoder, B=None, chunk=None, input_dim=None):
+        self.dec = decoder
+        st = getattr(decoder, "st", None)
+        if st is not None and not getattr(st, "independent", False):
+            raise _lib.M3Error("StreamPool needs a slot-mode encoder: engine.streaming(B, max_frames, independent=True)")
+        self.B = int(B if B is not None else st.desc.B)
+        self.c = int(chunk if chunk is not None else st.c)
+        self.idim = int(input_dim if input_dim is not None else st.feat.shape[2])
+        self.window = 4 * self.c + 3
+        self.slot_sid = [None] * self.B          # who holds slot b
+        self.streams = {}                        # sid -> (slot, WindowBuffer)
+        self.next_sid = 0
+        self.win = torch.zeros(self.B, self.window, self.idim)
+        self.steps = 0
+
+    def _get(self, sid):
+        if sid not in self.streams:
+            raise KeyError("StreamPool: no open stream %r" % (sid,))
+        return self.streams[sid]
+
+    def free_slots(self):
+        return sum(1 for s in self.slot_sid if s is None)
+
+    def slot_of(self, sid):
+        return self._get(sid)[0]
+
+    def open(self):
+        """Take a free slot and restart it; -> stream id.  Raises M3Error when all B slots are taken."""
+        for b, holder in enumerate(self.slot_sid):
+            if holder is None:
+                self.dec.reset(slots=[b])
+                sid = self.next_sid
+                self.next_sid += 1
+                self.slot_sid[b] = sid
+                self.streams[sid] = (b, WindowBuffer(self.c, self.idim))
+                return sid
+        raise _lib.M3Error("StreamPool.open: all %d slots are taken" % self.B)
+
+    def push(self, sid, frames):
+        self._get(sid)[1].push(frames)
+
+    def end(self, sid):
+        self._get(sid)[1].end()
+
+    def pending(self, sid):
+        """True while the stream has a window that step() would run."""
+        return self._get(sid)[1].ready() > 0
+
+    def step(self):
+        """ONE engine call: every stream with a full window buffered (or ended with >= 7 frames left) moves one chunk, every
+        other slot is idle.  -> the sids that were live (no call at all when there is none)."""
+        valid = torch.zeros(self.B, dtype=torch.int32)
+        live = []
+        for sid, (b, wb) in self.streams.items():
+            if wb.ready() > 0:
+                _, v = wb.take(out=self.win[b])
+                valid[b] = v
+                live.append(sid)
+        if live:
+            self.dec.step(self.win, valid)
+            self.steps += 1
+        return live
+
+    def partial(self, sid):
+        """(best beam hypothesis (prefix, score), greedy tokens) of the stream so far."""
+        b = self.slot_of(sid)
+        best, greedy = self.dec.partial(slots=[b])
+        return best[0], greedy[0]
+
+    def close(self, sid):
+        """n-best [(prefix, score)] of what the stream has decoded; the slot is free again."""
+        b = self.slot_of(sid)
+        nbest = self.dec.finish(slots=[b])[0]
+        del self.streams[sid]
+        self.slot_sid[b] = None
+        return nbest

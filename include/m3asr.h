@@ -327,6 +327,10 @@ typedef struct m3_ctc_beam_desc {
 } m3_ctc_beam_desc;
 size_t m3_ctc_beam_state_size(const m3_ctc_beam_desc* desc);
 int m3_ctc_beam_reset(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, m3_stream stream);
+/* The same for the n utterances listed in `slots` (device int32[n]; entries outside [0, B) are skipped), one launch: the
+ * other searches of the state go on untouched. */
+int m3_ctc_beam_reset_slots(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const int32_t* slots, int n,
+                            m3_stream stream);
 int m3_ctc_beam_advance(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const float* top_logp,
                         const int32_t* top_idx, int T_chunk, const int32_t* n_frames, m3_stream stream);
 int m3_ctc_beam_nbest(const m3_ctc_beam_desc* desc, const void* state, size_t state_bytes, int32_t* hyp_tokens,
@@ -344,6 +348,8 @@ typedef struct m3_ctc_greedy_desc {
 } m3_ctc_greedy_desc;
 size_t m3_ctc_greedy_stream_state_size(const m3_ctc_greedy_desc* desc);
 int m3_ctc_greedy_stream_reset(const m3_ctc_greedy_desc* desc, void* state, size_t state_bytes, m3_stream stream);
+int m3_ctc_greedy_stream_reset_slots(const m3_ctc_greedy_desc* desc, void* state, size_t state_bytes, const int32_t* slots,
+                                     int n, m3_stream stream); /* only the n streams listed in `slots` (device int32[n]) */
 int m3_ctc_greedy_stream_advance(const m3_ctc_greedy_desc* desc, void* state, size_t state_bytes, const float* logits,
                                  int T_chunk, int V, const int32_t* n_frames, int32_t* frame_ids, m3_stream stream);
 int m3_ctc_greedy_stream_tokens(const m3_ctc_greedy_desc* desc, const void* state, size_t state_bytes, int32_t* tokens,
@@ -508,6 +514,31 @@ int m3_engine_stream_reset(m3_engine* engine, const m3_stream_desc* desc, void* 
 int m3_engine_forward_chunk(m3_engine* engine, const m3_stream_desc* desc, void* state, size_t state_bytes,
                             const float* feat_chunk, const int32_t* chunk_feat_len, float* logits, void* workspace,
                             size_t workspace_bytes, int chunk_index, int use_graph, m3_stream stream);
+/* ---- slot mode: the B streams of one state start, pause and end independently ---------------------------------------------
+ * The calls above move all B streams in lockstep (one chunk counter).  In slot mode every utterance slot b has its own
+ * counter in the state (three int32 words per slot behind the caches: chunks decoded, status, output frames decoded; all
+ * earlier bytes of the state keep their offsets, and m3_engine_stream_state_size covers them).
+ * m3_engine_forward_chunk_slots: one chunk for every slot that is LIVE in this call, i.e. whose chunk_feat_len[b] yields at
+ *   least one output frame (pass 0 for fewer than 7 feature frames, as above).  Slot b's window is the one that starts
+ *   at ITS input frame 4 c (chunks slot b has decoded).  An idle slot (chunk_feat_len[b] = 0) keeps its counter, K / V history and conv cache
+ *   exactly as they were, so a stream may pause for any number of calls; its logits rows are undefined.  A slot whose chunk
+ *   would end past max_frames is treated as idle by every kernel (no address is formed from its counter) and its status
+ *   word is set until the slot is restarted.  Which slots are live is device data: every call replays the same hipGraph.
+ *   The binding is separate from the lockstep binding of the same buffers (same stage names; "stream.advance" is per slot).
+ * m3_engine_stream_reset_slots: restarts the n slots listed in `slots` (device int32[n], entries outside [0, B) skipped)
+ *   in one launch: counter 0, status cleared, both halves of every block's conv cache refilled.  The K / V history is not
+ *   cleared: no kernel reads a position the slot's current stream has not written.
+ * m3_engine_stream_positions: frames[b] (device int32[B]) = output frames slot b has decoded since its restart, -1 for a
+ *   slot whose status word is set (the convention of m3_ctc_greedy_stream_tokens).
+ * m3_engine_stream_reset initialises the slot words too.  One state is driven in ONE mode between two full resets: the
+ * lockstep counter and the slot counters do not follow each other. */
+int m3_engine_stream_reset_slots(m3_engine* engine, const m3_stream_desc* desc, void* state, size_t state_bytes,
+                                 const int32_t* slots, int n, m3_stream stream);
+int m3_engine_forward_chunk_slots(m3_engine* engine, const m3_stream_desc* desc, void* state, size_t state_bytes,
+                                  const float* feat_chunk, const int32_t* chunk_feat_len, float* logits, void* workspace,
+                                  size_t workspace_bytes, int use_graph, m3_stream stream);
+int m3_engine_stream_positions(m3_engine* engine, const m3_stream_desc* desc, const void* state, size_t state_bytes,
+                               int32_t* frames, m3_stream stream);
 /* Expert parallel: rows per wire chunk for the bindings made from now on (what the ranks agreed on: the largest row
  * count B*T' of any rank, so that a rank may send all of its rows to one peer; 0 = this rank's own row count).  The wire
  * buffers "ep.wire_a" / "ep.wire_b" ([world][1 + rows_per_chunk][D] fp32 each, inside the workspace) are what the host

@@ -2,6 +2,7 @@
 """Chunk-by-chunk decoding (m3_engine_forward_chunk) timed: latency of one chunk step and the real-time factor it implies.
 
   python tools/bench_streaming.py [--chunk 16] [--left-chunks 4] [--batch 1] [--weight-dtype f32] [--seconds 20] [--beam N]
+                                  [--independent [--stagger N]]
 
 18L x 32e encoder with causal conv modules in both encoders, static_chunk_size = chunk (output frames; one chunk = 4 x chunk
 input frames of 10 ms), synthetic weights and features.  Every step after the first is a hipGraph replay (the chunk counter
@@ -9,6 +10,9 @@ lives on the device).  Prints one JSON line: ms per chunk (p50 / p99 over all st
 audio seconds per chunk, real-time factor = compute time / audio time, streams one GPU could serve in real time.
 --beam N (> 0): also time the CTC decode of every chunk (StreamingCtcDecoder: top-k + prefix beam advance + streaming greedy,
 on the engine stream behind the chunk forward) and add "decode_ms_per_chunk" to the line.
+--independent: slot mode (m3_engine_forward_chunk_slots), every stream with its own position; --stagger N: stream b starts N
+steps after stream b - 1 and ends as many steps later (idle slots before and after).  The line then also carries "mode" and
+the mean number of live slots per timed step.
 """
 import argparse
 import json
@@ -36,13 +40,19 @@ def main():
     ap.add_argument("--layers", type=int, default=18)
     ap.add_argument("--seconds", type=float, default=20.0, help="audio per stream")
     ap.add_argument("--beam", type=int, default=0, help="> 0: decode every chunk with a prefix beam search of this width")
+    ap.add_argument("--independent", action="store_true", help="slot mode: every stream has its own chunk counter")
+    ap.add_argument("--stagger", type=int, default=0, help="slot mode: stream b starts this many steps after stream b - 1")
     args = ap.parse_args()
+    if args.stagger and not args.independent:
+        ap.error("--stagger needs --independent")
     cfg = EncoderConfig(num_blocks=args.layers, causal=True, embed_causal=True, static_chunk_size=args.chunk,
                         num_decoding_left_chunks=args.left_chunks, weight_dtype=args.weight_dtype)
     w = make_weights(cfg, seed=0)
     eng = Engine.from_state_dict(cfg, w, packed_rows=False)
     n_chunks = max(4, int(args.seconds * 100 / (4 * args.chunk)))
-    st = eng.streaming(args.batch, n_chunks * args.chunk)
+    st = eng.streaming(args.batch, n_chunks * args.chunk, independent=args.independent)
+    n_steps = n_chunks + args.stagger * (args.batch - 1)          # every stream decodes n_chunks chunks
+    starts = torch.arange(args.batch) * args.stagger
     rng = np.random.default_rng(1234)
     win = torch.from_numpy(rng.random((args.batch, st.window, cfg.input_dim), dtype=np.float32)).to(eng.device)
     valid = torch.full((args.batch,), st.window, dtype=torch.int32, device=eng.device)
@@ -51,13 +61,22 @@ def main():
         from m3asr.decode import StreamingCtcDecoder
         dec = StreamingCtcDecoder(st, args.beam)
         n_out = torch.full((args.batch,), args.chunk, dtype=torch.int32, device=eng.device)
-    times, dtimes = [], []
+    times, dtimes, live = [], [], []
     for rep in range(3):
         if dec is not None:
             dec.reset()
         else:
             st.reset()
-        for n in range(n_chunks):
+        for n in range(n_steps):
+            if args.stagger:
+                on = (starts <= n) & (n < starts + n_chunks)
+                valid = (on.to(torch.int32) * st.window).to(eng.device)
+                if dec is not None:
+                    n_out = (on.to(torch.int32) * args.chunk).to(eng.device)
+                if rep > 0:
+                    live.append(int(on.sum()))
+            elif rep > 0:
+                live.append(args.batch)
             e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
             e0.record(eng.stream)
             st.step(win, valid)
@@ -80,7 +99,10 @@ def main():
            "kernels_per_chunk": eng.num_kernels(), "audio_s_per_chunk": audio_s,
            "real_time_factor": round(p50 * 1e-3 / audio_s, 5),
            "streams_in_real_time_one_context": int(args.batch * audio_s / (p50 * 1e-3)),
-           "state_MB": round(st.state.numel() / 2 ** 20, 1), "graph_captures": eng.num_captures(), "data": "synthetic"}
+           "state_MB": round(st.state.numel() / 2 ** 20, 1), "graph_captures": eng.num_captures(), "data": "synthetic",
+           "mode": "slots" if args.independent else "lockstep", "mean_live_slots": round(float(np.mean(live)), 3)}
+    if args.stagger:
+        out["stagger_steps"] = args.stagger
     if dec is not None:
         d = np.sort(np.array(dtimes))
         out["decode_ms_per_chunk"] = {"beam": args.beam, "p50": round(float(np.median(d)), 4),
