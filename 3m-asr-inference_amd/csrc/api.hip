@@ -75,6 +75,8 @@ int moe_expert_ffn(const float* x, const int32_t* gate_idx, const float* w1, con
 
 using namespace m3;
 
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }   // (NULL counts as aligned)
+
 extern "C" {
 
 int m3_abi_version(void) { return M3ASR_ABI_VERSION; }
@@ -147,6 +149,8 @@ int m3_moe_expert_ffn_fp8a8_xq(const float* x, const void* xq, const float* xq_s
                            (hipStream_t)stream, 3, w1_scale, w2_scale, h_scale, xq, xq_scale);
 }
 int m3_quantize_rows_e4m3(const float* x, int ldx, int S, int idim, void* xq, float* scale, m3_stream stream) {
+  M3_REQUIRE(S <= 1 || ldx >= idim, "quantize_rows_e4m3: ldx=%d is shorter than a row of %d", ldx, idim);
+  M3_REQUIRE(aligned16(x) && aligned16(xq), "quantize_rows_e4m3: x / xq must be 16-byte aligned");
   return launch_quantize_rows_e4m3(x, ldx, S, idim, xq, scale, (hipStream_t)stream);
 }
 int m3_moe_expert_ffn_fp8a8_active(int S, int num_expert, int idim, int hidden_units) {
@@ -179,12 +183,27 @@ int m3_ep_recv_gate(const void* wire, int world, int e_loc, int capacity, int ro
 int m3_moe_router(const float* embed, int ld_embed, int embed_dim, const float* x, int ldx, int idim, const float* w,
                   const float* bias, const float* ln_gamma, const float* ln_beta, float ln_eps, float* xn, int ld_xn,
                   float* logits, int ld_logits, int S, int num_expert, m3_stream stream) {
+  // row strides (include/m3asr.h): rows may not overlap; the 16-byte accesses of embed / x / xn need multiples of 4 (launcher)
+  M3_REQUIRE(S <= 1 || (ld_embed >= embed_dim && ldx >= idim), "moe_router: ld_embed=%d / ldx=%d shorter than the rows (%d / %d)",
+             ld_embed, ldx, embed_dim, idim);
+  M3_REQUIRE(S <= 1 || xn == nullptr || ld_xn >= idim, "moe_router: ld_xn=%d is shorter than a row of %d", ld_xn, idim);
+  M3_REQUIRE(S <= 1 || ld_logits >= num_expert, "moe_router: ld_logits=%d is shorter than a row of %d", ld_logits, num_expert);
+  M3_REQUIRE(aligned16(embed) && aligned16(x) && aligned16(xn), "moe_router: embed / x / xn must be 16-byte aligned");
   return launch_moe_router(embed, ld_embed, embed_dim, x, ldx, idim, w, bias, ln_gamma, ln_beta, ln_eps, xn, ld_xn, logits,
                            ld_logits, S, num_expert, nullptr, (hipStream_t)stream);
 }
 int m3_softmax_top1(const float* logits, int ld, const int32_t* len, int rows_per_batch, int S, int width,
                     int32_t* idx, float* value, m3_stream stream) {
+  M3_REQUIRE(S <= 1 || ld >= width, "softmax_topk: ld=%d is shorter than a row of %d", ld, width);
   return launch_softmax_top1(logits, ld, len, rows_per_batch, S, width, idx, value, (hipStream_t)stream);
+}
+
+// what the three attention entry points ask of their row operands besides the multiples the launchers check (include/m3asr.h)
+static int attention_operands(const void* qkv, int ldq, const void* p, int ldp, const void* out, int ldo, int B, int T, int H, int dk) {
+  M3_REQUIRE(B * T <= 1 || (ldq >= 3 * H * dk && ldo >= H * dk), "attention: ldq=%d / ldo=%d shorter than the rows (%d / %d)", ldq, ldo, 3 * H * dk, H * dk);
+  M3_REQUIRE(T <= 1 || ldp >= H * dk, "attention: ldp=%d is shorter than a row of %d", ldp, H * dk);
+  M3_REQUIRE(aligned16(qkv) && aligned16(p) && aligned16(out), "attention: qkv / p / out must be 16-byte aligned");
+  return 0;
 }
 
 static int linear_params(const m3_linear_desc* d, GemmParams* out) {
@@ -208,12 +227,40 @@ static int linear_params(const m3_linear_desc* d, GemmParams* out) {
   p.a_bf16 = d->a_dtype == M3_BF16; p.y_bf16 = d->y_dtype == M3_BF16;
   p.Yb = d->y_copy_bf16; p.ldyb = d->ld_copy; p.Yb_stats = d->y_copy_stats;
   p.ln_stats = d->ln_stats; p.ln_stat_parts = d->ln_stat_parts;
+  // Row strides (include/m3asr.h).  Multiples: the 16-byte loads of `a` / `a2` and the 8-byte stores of bf16 rows need them (the
+  // fp32 `y` / `resid` paths fall back to element accesses on other strides).  Minimum: rows of an operand may not overlap.
+  {
+    const int n_out = d->act == M3_ACT_GLU ? d->N / 2 : d->N;
+    const int k1 = d->a2 ? d->k1 : d->K, a_mult = p.a_bf16 ? 8 : 4;
+    const bool rows = d->M > 1;   // with one row a stride is never used
+    M3_REQUIRE(d->lda % a_mult == 0 && (!rows || d->lda >= k1), "linear: lda=%d must be a multiple of %d and >= %d", d->lda, a_mult, k1);
+    if (d->a2) M3_REQUIRE(d->lda2 % 4 == 0 && (!rows || d->lda2 >= d->K - k1), "linear: lda2=%d must be a multiple of 4 and >= %d", d->lda2, d->K - k1);
+    M3_REQUIRE(!rows || d->ldy >= n_out, "linear: ldy=%d is shorter than an output row of %d", d->ldy, n_out);
+    if (p.y_bf16) M3_REQUIRE(d->ldy % 4 == 0, "linear: ldy=%d must be a multiple of 4 for a bf16 y", d->ldy);
+    if (d->resid) M3_REQUIRE(!rows || d->ldr >= n_out, "linear: ldr=%d is shorter than an output row of %d", d->ldr, n_out);
+    if (d->y_copy_bf16) M3_REQUIRE(d->ld_copy % 4 == 0 && (!rows || d->ld_copy >= n_out), "linear: ld_copy=%d must be a multiple of 4 and >= %d", d->ld_copy, n_out);
+  }
   *out = p;
   return 0;
+}
+// the operands a launch dereferences (m3_linear_workspace_size only reads sizes): rows accessed 16 bytes at a time start on a
+// 16-byte boundary, and an in-place residual update walks y and resid with one stride
+static int linear_pointers(const m3_linear_desc* d) {
+  M3_REQUIRE(d->a && d->w && d->y, "linear: null a / w / y");
+  M3_REQUIRE(aligned16(d->a) && aligned16(d->a2) && aligned16(d->y) && aligned16(d->resid) && aligned16(d->y_copy_bf16),
+             "linear: a / a2 / y / resid / y_copy_bf16 must be 16-byte aligned");
+  M3_REQUIRE((const void*)d->resid != (const void*)d->y || d->ldr == d->ldy, "linear: y == resid (in-place) needs ldr=%d == ldy=%d", d->ldr, d->ldy);
+  return 0;
+}
+const char* m3_linear_kernel(const m3_linear_desc* d, int with_workspace) {
+  GemmParams p;
+  if (linear_params(d, &p)) return nullptr;
+  return gemm_kernel_label(p, with_workspace && gemm_f32_splitk_plan(p, nullptr) >= 2);
 }
 int m3_linear(const m3_linear_desc* d, m3_stream stream) {
   GemmParams p;
   if (int rc = linear_params(d, &p)) return rc;
+  if (int rc = linear_pointers(d)) return rc;
   return launch_gemm_f32(p, (hipStream_t)stream);
 }
 size_t m3_linear_workspace_size(const m3_linear_desc* d) {
@@ -225,6 +272,7 @@ size_t m3_linear_workspace_size(const m3_linear_desc* d) {
 int m3_linear_ws(const m3_linear_desc* d, void* workspace, size_t workspace_bytes, m3_stream stream) {
   GemmParams p;
   if (int rc = linear_params(d, &p)) return rc;
+  if (int rc = linear_pointers(d)) return rc;
   size_t need = 0;
   if (gemm_f32_splitk_plan(p, &need) >= 2 && workspace != nullptr && workspace_bytes >= need)
     return launch_gemm_f32_splitk(p, (float*)workspace, workspace_bytes, (hipStream_t)stream);
@@ -238,18 +286,21 @@ int m3_layer_norm(const float* x, const float* gamma, const float* beta, float e
 int m3_relpos_attention(const float* qkv, int ldq, const float* p, int ldp, const float* pos_u, const float* pos_v,
                         const int32_t* len, int B, int T, int H, int dk, float scale, float* out, int ldo,
                         m3_stream stream) {
+  if (int rc = attention_operands(qkv, ldq, p, ldp, out, ldo, B, T, H, dk)) return rc;
   return launch_relpos_attention(qkv, ldq, p, ldp, pos_u, pos_v, len, B, T, H, dk, scale, out, ldo,
                                  (hipStream_t)stream);
 }
 int m3_relpos_attention_bf16(const void* qkv, int ldq, const float* p, int ldp, const float* pos_u, const float* pos_v,
                              const int32_t* len, int B, int T, int H, int dk, float scale, int chunk, int left_chunks,
                              void* out, int ldo, m3_stream stream) {
+  if (int rc = attention_operands(qkv, ldq, p, ldp, out, ldo, B, T, H, dk)) return rc;
   return launch_relpos_attention_bf16(qkv, ldq, p, ldp, pos_u, pos_v, len, B, T, H, dk, scale, out, ldo, (hipStream_t)stream,
                                       nullptr, chunk, left_chunks);
 }
 int m3_relpos_attention_chunk(const float* qkv, int ldq, const float* p, int ldp, const float* pos_u, const float* pos_v,
                               const int32_t* len, int B, int T, int H, int dk, float scale, int chunk, int left_chunks,
                               float* out, int ldo, m3_stream stream) {
+  if (int rc = attention_operands(qkv, ldq, p, ldp, out, ldo, B, T, H, dk)) return rc;
   return launch_relpos_attention(qkv, ldq, p, ldp, pos_u, pos_v, len, B, T, H, dk, scale, out, ldo, (hipStream_t)stream, 0,
                                  nullptr, chunk, left_chunks);
 }

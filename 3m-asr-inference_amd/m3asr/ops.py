@@ -30,6 +30,13 @@ def _i32(t):
     return _p(t)
 
 
+def _rows(t, dtype=torch.float32):
+    """(pointer, row stride in elements) of a 2-D operand the ABI takes with a leading dimension: any row-strided view with
+    unit column stride (a column slice of a wider buffer, q|k|v, a GLU half); the launcher checks the stride itself."""
+    assert t.is_cuda and t.dim() == 2 and t.stride(1) == 1 and t.dtype == dtype, "row-strided 2-D %s device tensor expected" % dtype
+    return C.c_void_p(t.data_ptr()), t.stride(0)
+
+
 # ---------------------------------------------------------------------------------------- MoE
 def moe_scatter_mapping(gate_idx, num_expert, want_pos=True):
     lib = _lib.load()
@@ -95,11 +102,11 @@ def quantize_rows_e4m3(x):
     """x (S, 512) f32 -> (xq (S, 512) uint8 holding OCP e4m3, scale (S,) f32): scale = amax / 448 per row, round to nearest even,
     saturating -- what the fused fp8 expert kernel does to its input rows (m3_quantize_rows_e4m3)."""
     lib = _lib.load()
-    assert x.dim() == 2 and x.dtype == torch.float32 and x.stride(1) == 1
     S, D = x.shape
+    xp, ldx = _rows(x)
     xq = torch.empty(S, D, dtype=torch.uint8, device=x.device)
     scale = torch.empty(S, dtype=torch.float32, device=x.device)
-    check(lib.m3_quantize_rows_e4m3(_p(x), x.stride(0), S, D, _p(xq), _p(scale), _stream()), "m3_quantize_rows_e4m3")
+    check(lib.m3_quantize_rows_e4m3(xp, ldx, S, D, _p(xq), _p(scale), _stream()), "m3_quantize_rows_e4m3")
     return xq, scale
 
 
@@ -162,28 +169,33 @@ def moe_combine(rows, mapping, gate_value=None, resid=None, alpha=1.0, ln=None, 
     return y
 
 
-def moe_router(embed, x, w, ln, bias=None, want_xn=True):
-    """logits (S, E) = cat([embed, LayerNorm(x)]) @ w^T (+ bias), xn = LayerNorm(x); w (E, De + D) fp32, ln = (gamma, beta, eps)."""
+def moe_router(embed, x, w, ln, bias=None, want_xn=True, out=None, xn_out=None):
+    """logits (S, E) = cat([embed, LayerNorm(x)]) @ w^T (+ bias), xn = LayerNorm(x); w (E, De + D) fp32, ln = (gamma, beta, eps).
+    embed / x and the optional result buffers out (S, E) / xn_out (S, D) may be row-strided views."""
     lib = _lib.load()
     S, De = embed.shape
     D = x.shape[1]
     E = w.shape[0]
-    assert w.shape[1] == De + D and w.is_contiguous() and embed.is_contiguous() and x.is_contiguous()
-    logits = torch.empty(S, E, dtype=torch.float32, device=x.device)
-    xn = torch.empty_like(x) if want_xn else None
-    check(lib.m3_moe_router(_f32(embed), De, De, _f32(x), D, D, _f32(w), _f32(bias), _f32(ln[0]), _f32(ln[1]), float(ln[2]),
-                            _f32(xn), D, _p(logits), E, S, E, _stream()), "m3_moe_router")
+    assert w.shape[1] == De + D and w.is_contiguous()
+    logits = out if out is not None else torch.empty(S, E, dtype=torch.float32, device=x.device)
+    xn = xn_out if xn_out is not None else (torch.empty(S, D, dtype=torch.float32, device=x.device) if want_xn else None)
+    assert tuple(logits.shape) == (S, E) and (xn is None or tuple(xn.shape) == (S, D))
+    (ep, lde), (xp, ldx), (lp, ldl) = _rows(embed), _rows(x), _rows(logits)
+    xnp, ldxn = _rows(xn) if xn is not None else (None, D)
+    check(lib.m3_moe_router(ep, lde, De, xp, ldx, D, _f32(w), _f32(bias), _f32(ln[0]), _f32(ln[1]), float(ln[2]),
+                            xnp, ldxn, lp, ldl, S, E, _stream()), "m3_moe_router")
     return logits, xn
 
 
 def softmax_top1(logits, lens=None, rows_per_batch=0):
     lib = _lib.load()
     E = logits.shape[-1]
-    l2 = logits.reshape(-1, E)
+    l2 = logits if logits.dim() == 2 else logits.reshape(-1, E)      # a 2-D operand may be a row-strided view
     S = l2.shape[0]
     idx = torch.empty(S, dtype=torch.int32, device=logits.device)
     val = torch.empty(S, dtype=torch.float32, device=logits.device)
-    check(lib.m3_softmax_top1(_f32(l2), E, _i32(lens), rows_per_batch, S, E, _p(idx), _p(val), _stream()),
+    lp, ld = _rows(l2)
+    check(lib.m3_softmax_top1(lp, ld, _i32(lens), rows_per_batch, S, E, _p(idx), _p(val), _stream()),
           "m3_softmax_top1")
     return val, idx
 
@@ -191,18 +203,23 @@ def softmax_top1(logits, lens=None, rows_per_batch=0):
 # ---------------------------------------------------------------------------------------- dense
 def linear(a, w, bias=None, act=_lib.ACT_NONE, a2=None, ln=None, lens=None, rows_per_batch=0, mask_in=False,
            mask_out=False, alpha=1.0, resid=None, out=None, ln_folded=None, split_k=False, out_dtype=torch.float32,
-           copy_bf16=None, copy_stats=None, ln_stats=None):
+           copy_bf16=None, copy_stats=None, ln_stats=None, workspace=None, _kernel_only=False):
     """y = resid + alpha * mask_out(act(LN(mask_in(cat[a,a2])) @ w^T + bias)); a (M,K1), w (N,K).
     ln = (gamma, beta, eps): affine LayerNorm prologue.  ln_folded = (wsum, wbeta or None, eps): w / bias already
     contain the LayerNorm affine (plan.fold_layernorm) and the kernel normalises its output.
     bf16 activation operands (bf16 weights only): `a` may be a bf16 tensor; out_dtype=torch.bfloat16 writes y as bf16;
     copy_bf16 (M, n_out) bf16 receives an extra bf16 copy of y, copy_stats (M, n_out/128, 2) f32 its per-tile row statistics;
-    ln_stats (M, parts, 2): such statistics of a bf16 `a`, which the folded LayerNorm then uses."""
+    ln_stats (M, parts, 2): such statistics of a bf16 `a`, which the folded LayerNorm then uses.
+    a, a2, y (= out), resid and copy_bf16 may be row-strided views (unit column stride); their row strides go to the ABI.
+    workspace (split_k only): caller-owned uint8 scratch of at least m3_linear_workspace_size bytes."""
     lib = _lib.load()
     M, K1 = a.shape
     N, K = w.shape
     n_out = N // 2 if act == _lib.ACT_GLU else N
     y = out if out is not None else torch.empty(M, n_out, dtype=out_dtype, device=a.device)
+    for t in (a, a2, y, resid, copy_bf16):
+        assert t is None or (t.is_cuda and t.dim() == 2 and t.stride(1) == 1), "row-strided 2-D device tensor expected"
+    assert tuple(y.shape) == (M, n_out) and (resid is None or tuple(resid.shape) == (M, n_out))
     d = _lib.LinearDesc()
     d.a, d.lda = a.data_ptr(), a.stride(0)
     assert a.dtype in (torch.float32, torch.bfloat16) and y.dtype in (torch.float32, torch.bfloat16)
@@ -239,13 +256,22 @@ def linear(a, w, bias=None, act=_lib.ACT_NONE, a2=None, ln=None, lens=None, rows
     d.act, d.alpha = act, float(alpha)
     if resid is not None:
         d.resid, d.ldr = resid.data_ptr(), resid.stride(0)
+    if _kernel_only:
+        name = lib.m3_linear_kernel(C.byref(d), int(bool(split_k)))
+        return name.decode() if name else None
     if split_k:        # deep-K / few-tile problems: split-K kernel + reduce through a scratch workspace
         need = lib.m3_linear_workspace_size(C.byref(d))
-        ws = torch.empty(max(need, 1), dtype=torch.uint8, device=a.device)
+        ws = workspace if workspace is not None else torch.empty(max(need, 1), dtype=torch.uint8, device=a.device)
+        assert ws.dtype == torch.uint8 and ws.numel() >= need
         check(lib.m3_linear_ws(C.byref(d), _p(ws), need, _stream()), "m3_linear_ws")
         return y
     check(lib.m3_linear(C.byref(d), _stream()), "m3_linear")
     return y
+
+
+def linear_kernel(*args, **kw):
+    """name of the device kernel linear(*args, **kw) would run (host-only query, m3_linear_kernel); None if it is rejected"""
+    return linear(*args, _kernel_only=True, **kw)
 
 
 def layer_norm(x, gamma, beta, eps):
@@ -257,31 +283,36 @@ def layer_norm(x, gamma, beta, eps):
     return y
 
 
-def relpos_attention(qkv, p, pos_u, pos_v, lens, B, T, H, dk, chunk=0, left_chunks=-1):
+def relpos_attention(qkv, p, pos_u, pos_v, lens, B, T, H, dk, chunk=0, left_chunks=-1, out=None):
     """chunk > 0: static chunk mask (utils/mask.py:42-75): query i sees keys of its chunk and of `left_chunks` chunks to the
-    left (< 0: all) -- besides the padding mask."""
+    left (< 0: all) -- besides the padding mask.  qkv (B*T, 3*H*dk), p (T, H*dk) and out (B*T, H*dk) may be row-strided views."""
     lib = _lib.load()
     D = H * dk
-    out = torch.empty(B * T, D, dtype=torch.float32, device=qkv.device)
+    if out is None:
+        out = torch.empty(B * T, D, dtype=torch.float32, device=qkv.device)
+    assert tuple(qkv.shape) == (B * T, 3 * D) and tuple(p.shape)[1] == D and p.shape[0] >= T and tuple(out.shape) == (B * T, D)
+    (qp, ldq), (pp, ldp), (op, ldo) = _rows(qkv), _rows(p), _rows(out)
     if chunk > 0:
-        check(lib.m3_relpos_attention_chunk(_f32(qkv), qkv.stride(0), _f32(p), p.stride(0), _f32(pos_u), _f32(pos_v), _i32(lens),
-                                            B, T, H, dk, 1.0 / math.sqrt(dk), int(chunk), int(left_chunks), _p(out), D, _stream()),
+        check(lib.m3_relpos_attention_chunk(qp, ldq, pp, ldp, _f32(pos_u), _f32(pos_v), _i32(lens),
+                                            B, T, H, dk, 1.0 / math.sqrt(dk), int(chunk), int(left_chunks), op, ldo, _stream()),
               "m3_relpos_attention_chunk")
         return out
-    check(lib.m3_relpos_attention(_f32(qkv), qkv.stride(0), _f32(p), p.stride(0), _f32(pos_u), _f32(pos_v),
-                                  _i32(lens), B, T, H, dk, 1.0 / math.sqrt(dk), _p(out), D, _stream()),
+    check(lib.m3_relpos_attention(qp, ldq, pp, ldp, _f32(pos_u), _f32(pos_v),
+                                  _i32(lens), B, T, H, dk, 1.0 / math.sqrt(dk), op, ldo, _stream()),
           "m3_relpos_attention")
     return out
 
 
-def relpos_attention_bf16(qkv, p, pos_u, pos_v, lens, B, T, H, dk, chunk=0, left_chunks=-1):
+def relpos_attention_bf16(qkv, p, pos_u, pos_v, lens, B, T, H, dk, chunk=0, left_chunks=-1, out=None):
     """the same on bf16 rows: qkv (B*T, 3*H*dk) bf16 -> ctx (B*T, H*dk) bf16 (T <= 128)"""
     lib = _lib.load()
-    assert qkv.dtype == torch.bfloat16 and qkv.is_contiguous()
     D = H * dk
-    out = torch.empty(B * T, D, dtype=torch.bfloat16, device=qkv.device)
-    check(lib.m3_relpos_attention_bf16(_p(qkv), 3 * D, _f32(p), p.stride(0), _f32(pos_u), _f32(pos_v), _i32(lens), B, T, H, dk,
-                                       1.0 / math.sqrt(dk), int(chunk), int(left_chunks), _p(out), D, _stream()), "m3_relpos_attention_bf16")
+    if out is None:
+        out = torch.empty(B * T, D, dtype=torch.bfloat16, device=qkv.device)
+    assert tuple(qkv.shape) == (B * T, 3 * D) and tuple(out.shape) == (B * T, D)
+    (qp, ldq), (pp, ldp), (op, ldo) = _rows(qkv, torch.bfloat16), _rows(p), _rows(out, torch.bfloat16)
+    check(lib.m3_relpos_attention_bf16(qp, ldq, pp, ldp, _f32(pos_u), _f32(pos_v), _i32(lens), B, T, H, dk,
+                                       1.0 / math.sqrt(dk), int(chunk), int(left_chunks), op, ldo, _stream()), "m3_relpos_attention_bf16")
     return out
 
 

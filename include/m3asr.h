@@ -13,6 +13,14 @@
  *     m3_last_error() (reference only logs, common/common.h:26-38);
  *   - dtype codes 0/1/2 = the reference's HelperConfig.plugin_data_type (builder_helper.py:47-57).
  * Row layouts are row-major; "S" = B*T' tokens, D = idim, F = hidden_units, E = num_expert.
+ *
+ * Row strides.  Every `ld*` argument is the distance between two rows of its operand IN ELEMENTS of that operand.  Each entry
+ * point states what it needs of them; anything else is rejected on the host, before a kernel is launched (non-zero status).
+ * Two rules hold everywhere: a stride is at least the row width it belongs to (rows never overlap; not required of an operand
+ * with a single row), and a row that a kernel reads or writes 16 bytes at a time needs a stride that keeps every row as
+ * aligned as the first one: a multiple of 4 fp32 or 8 bf16 elements (4 for bf16 rows written 8 bytes at a time).  The base
+ * pointer of every strided operand must be 16-byte aligned (checked with the strides).  Operands without a stride argument
+ * are dense.  The whole-encoder engine builds its own operands inside the workspace and does not pass through these checks.
  */
 #ifndef M3ASR_H_
 #define M3ASR_H_
@@ -157,7 +165,7 @@ int m3_moe_expert_ffn_fp8a8_xq(const float* x, const void* xq, const float* xq_s
                                const float* resid, float alpha, const float* ln_gamma, const float* ln_beta, float ln_eps,
                                float* y, void* workspace, size_t workspace_bytes, m3_stream stream);
 /* rows -> OCP e4m3 with one dynamic scale per row: scale[s] = amax(x[s]) / 448 (1e-30 floor), xq = round-to-nearest-even,
- * saturating (x[s] / scale[s]).  idim must be 512 (one wave per row). */
+ * saturating (x[s] / scale[s]).  idim must be 512 (one wave per row).  ldx: multiple of 4, >= idim; xq / scale are dense. */
 int m3_quantize_rows_e4m3(const float* x, int ldx, int S, int idim, void* xq, float* scale, m3_stream stream);
 /* The tail of the MoE layer on rows that are already in scattered (expert-sorted) order, e.g. rows that came back
  * from the expert-parallel all-to-all:  out[s] = LayerNorm( resid[s] + alpha * gate_value[s] * rows[mapping[s]] )
@@ -188,12 +196,15 @@ int m3_ep_send_map(const int32_t* gate_idx, const int32_t* mapping, const int32_
 int m3_ep_recv_gate(const void* wire, int world, int e_loc, int capacity, int row_bytes, int32_t* gate_recv, m3_stream stream);
 /* Router of the MoE feed-forward (positionwise_feed_forward.py:169-180,225 + norm_ff, fmoe_transformer.py:138-141):
  * logits[S][num_expert] = cat([embed (S, embed_dim), LayerNorm(x) (S, idim)]) . w^T (+ bias), w [num_expert][embed_dim + idim]
- * fp32 row-major; xn (may be NULL) receives LayerNorm(x), the expert FFN's input.  num_expert <= 64, dims multiples of 64. */
+ * fp32 row-major; xn (may be NULL) receives LayerNorm(x), the expert FFN's input.  num_expert <= 64, dims multiples of 64.
+ * Strides: ld_embed >= embed_dim, ldx >= idim, ld_xn >= idim, each a multiple of 4 (16-byte row accesses); ld_logits >=
+ * num_expert, any value (the logits are stored element by element). */
 int m3_moe_router(const float* embed, int ld_embed, int embed_dim, const float* x, int ldx, int idim, const float* w,
                   const float* bias, const float* ln_gamma, const float* ln_beta, float ln_eps, float* xn, int ld_xn,
                   float* logits, int ld_logits, int S, int num_expert, m3_stream stream);
 /* Replaces ComputeSoftmaxAndTop1 (softmax_topk_kernel.cu:88-120): logits [S][ld] -> idx[S], value[S];
- * frames t >= len[b] (t = s % rows_per_batch, b = s / rows_per_batch) get idx -1 / value 0; len may be NULL. */
+ * frames t >= len[b] (t = s % rows_per_batch, b = s / rows_per_batch) get idx -1 / value 0; len may be NULL.
+ * ld >= width, any value (element loads); idx / value are dense. */
 int m3_softmax_top1(const float* logits, int ld, const int32_t* len, int rows_per_batch, int S, int width,
                     int32_t* idx, float* value, m3_stream stream);
 
@@ -204,7 +215,14 @@ int m3_softmax_top1(const float* logits, int ld, const int32_t* len, int rows_pe
  * addConv1d k=1 (:199-225), LayerNorm plugin (layer_norm_plugin.cpp:78-113), masked_fill, GLU, SiLU/ReLU,
  * addScale + addAdd.   y[M][ldy] = resid + alpha * mask_out( act( LN(mask_in(a))[M][K] . w[N][K]^T + bias ) ).
  * a2 != NULL: A = cat([a (K1 cols), a2 (K-K1 cols)], -1) (router input, positionwise_feed_forward.py:225).
- * act = M3_ACT_GLU halves the output width (columns n and n+N/2 are paired, torch GLU dim=-1). */
+ * act = M3_ACT_GLU halves the output width (columns n and n+N/2 are paired, torch GLU dim=-1): n_out = N / 2, else N.
+ * Strides (M > 1):
+ *   lda  >= k1 (K without a2), multiple of 4 (fp32 a) or 8 (bf16 a);   lda2 >= K - k1, multiple of 4;
+ *   ldy  >= n_out; any value for an fp32 y (the tiled kernels store 16 bytes at a time when ldy and ldr are multiples of 4
+ *        and element by element otherwise: same values either way), a multiple of 4 for a bf16 y;
+ *   ldr  >= n_out, any value; y == resid (in-place update) needs ldr == ldy;
+ *   ld_copy >= n_out, multiple of 4.
+ * w, bias, the LayerNorm vectors, y_copy_stats and ln_stats are dense. */
 typedef struct m3_linear_desc {
   const float* a; int32_t lda;
   const float* a2; int32_t lda2; int32_t k1;
@@ -243,18 +261,24 @@ int m3_linear(const m3_linear_desc* desc, m3_stream stream);
  * a single utterance) run as a split-K tiled kernel + fixed-order reduce when m3_linear_workspace_size(desc) > 0 bytes
  * are provided; otherwise identical to m3_linear. */
 size_t m3_linear_workspace_size(const m3_linear_desc* desc);
+/* Host only: name of the device kernel m3_linear (with_workspace = 0) or m3_linear_ws given its workspace (1) runs for desc
+ * (sizes, strides, dtypes and modes are read, no pointer is dereferenced); NULL for a descriptor m3_linear rejects. */
+const char* m3_linear_kernel(const m3_linear_desc* desc, int with_workspace);
 int m3_linear_ws(const m3_linear_desc* desc, void* workspace, size_t workspace_bytes, m3_stream stream);
 
 /* LayerNormPluginDynamic (layer_norm_plugin.cpp:78-113) -- with eps, as PyTorch. */
 int m3_layer_norm(const float* x, const float* gamma, const float* beta, float eps, float* y, int rows, int dim,
                   m3_stream stream);
 /* Fused rel-pos attention core; replaces attention.py:347-384 + :199-236 (shuffles, 3 batched matmuls,
- * AttMaskedSoftmaxPluginDynamic).  qkv [B*T][ldq] = (q|k|v), p [T][ldp], pos_u/pos_v [H][dk], out [B*T][ldo]. */
+ * AttMaskedSoftmaxPluginDynamic).  qkv [B*T][ldq] = (q|k|v), p [T][ldp], pos_u/pos_v [H][dk], out [B*T][ldo].
+ * Strides (D = H * dk): ldq >= 3 D and ldp >= D, multiples of 4 (16-byte row loads); ldo >= D, any value (element stores).
+ * The same holds for m3_relpos_attention_chunk. */
 int m3_relpos_attention(const float* qkv, int ldq, const float* p, int ldp, const float* pos_u,
                         const float* pos_v, const int32_t* len, int B, int T, int H, int dk, float scale,
                         float* out, int ldo, m3_stream stream);
 /* The same operator on bf16 rows (16-bit modes of long batches): qkv and out are bf16 ([B*T][ldq] / [B*T][ldo], strides in
- * elements), p / pos_u / pos_v stay fp32; bf16 MFMA, fp32 softmax; T <= 128 keys, dk 64 or 128. */
+ * elements), p / pos_u / pos_v stay fp32; bf16 MFMA, fp32 softmax; T <= 128 keys, dk 64 or 128.
+ * Strides: ldq >= 3 D, multiple of 8; ldp >= D, multiple of 4; ldo >= D, multiple of 4 (8-byte row stores). */
 int m3_relpos_attention_bf16(const void* qkv, int ldq, const float* p, int ldp, const float* pos_u, const float* pos_v,
                              const int32_t* len, int B, int T, int H, int dk, float scale, int chunk, int left_chunks,
                              void* out, int ldo, m3_stream stream);
