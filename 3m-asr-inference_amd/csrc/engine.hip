@@ -77,6 +77,24 @@ m3_stage_info stage_info(const char* kernel, int launches, double bytes, double 
 
 struct Buf { void* ptr; size_t bytes; };
 
+// What identifies a binding: the shape, the caller's buffers and the mode.  Two forwards with equal keys run the same stage
+// list; everything else in a binding is derived from its key (and the engine's weights and config).
+struct BindKey {
+  int B = 0, T = 0;
+  const float* feat = nullptr; const int32_t* feat_len = nullptr; float* logits = nullptr;
+  void* ws = nullptr; size_t ws_bytes = 0;
+  int ep_cap = 0;        // expert parallel: rows per wire chunk (m3_engine_set_ep_capacity at the time of binding)
+  // chunk-by-chunk (streaming) binding: T = 4 c + 3 input frames -> the c frames of one chunk; attention reads / extends the
+  // K / V history and the causal depthwise conv its K-1 frame cache, both in the caller-owned state (m3_engine_forward_chunk)
+  void* sstate = nullptr; int s_hist = 0, s_maxf = 0;
+  bool s_slots = false;   // slot mode (m3_engine_forward_chunk_slots): every utterance slot of the state has its own chunk counter
+  bool operator==(const BindKey& o) const {
+    return B == o.B && T == o.T && feat == o.feat && feat_len == o.feat_len && logits == o.logits && ws == o.ws &&
+           ws_bytes == o.ws_bytes && ep_cap == o.ep_cap && sstate == o.sstate && s_hist == o.s_hist && s_maxf == o.s_maxf &&
+           s_slots == o.s_slots;
+  }
+};
+
 }  // namespace
 
 struct m3_engine {
@@ -97,23 +115,12 @@ struct m3_engine {
   // state of the bound shape (buffers + stage list + captured graph); up to cfg.shape_cache more are parked, so a server
   // that alternates between a few (B, T) buckets with static I/O buffers replays graphs instead of re-capturing them
   struct Bound {
-    int B = 0, T = 0, Tp = 0, S = 0;
-    const float* feat = nullptr; const int32_t* feat_len = nullptr; float* logits = nullptr;
-    void* ws = nullptr; size_t ws_bytes = 0;
-    float* splitk_ws = nullptr; size_t splitk_bytes = 0;   // partial tiles of the split-K front-end GEMMs (inside ws)
+    BindKey key;
+    int Tp = 0, S = 0;   // subsampled frames per utterance, rows of the residual stream (B * T')
     bool a16 = false;   // activations that only feed GEMMs are kept as bf16 (h1, ctx, dw, c1, c2) + a bf16 copy of x
     bool dma = false;   // a16 and the block GEMMs run on the LDS-DMA kernel: every kernel that writes xb also leaves its row statistics
     bool packed = false;   // ragged batch: the blocks run on the packed valid rows (cfg.packed_rows)
     bool xn_skipped = false;   // the router kernel was told not to write the fp32 MoE input rows (M3_ROUTER_SKIP_XN=1)
-    // (build-time scratch of the stage list) the next conv1 stage also forms the subsampled lengths; a second LayerNorm
-    // for the next norm_final stage
-    bool lens_in_conv1 = false;
-    const float *tail_ln_g = nullptr, *tail_ln_b = nullptr; float tail_ln_eps = 0.f; float* tail_ln_out = nullptr;
-    int ep_cap = 0;        // expert parallel: rows per wire chunk this binding was built for (m3_engine_set_ep_capacity)
-    // chunk-by-chunk (streaming) binding: T = 4 c + 3 input frames -> the c frames of one chunk; attention reads / extends the
-    // K / V history and the causal depthwise conv its K-1 frame cache, both in the caller-owned state (m3_engine_forward_chunk)
-    void* sstate = nullptr; int s_hist = 0, s_maxf = 0;
-    bool s_slots = false;   // slot mode (m3_engine_forward_chunk_slots): every utterance slot of the state has its own chunk counter
     // fork_embed: stages [fork_first, fork_mid) = the embed encoder (side branch of the captured graph), [fork_mid, join_at) =
     // what the main encoder does before it needs the embedding (embed_join); -1 = one linear chain
     int fork_first = -1, fork_mid = -1, join_at = -1;
@@ -127,11 +134,7 @@ struct m3_engine {
     hipGraphExec_t graph_exec = nullptr;
     bool graph_valid = false;
     uint64_t last_use = 0;
-    bool matches(int b, int t, const float* f, const int32_t* fl, const float* lg, const void* w, size_t wb, int cap,
-                 const void* st = nullptr, int hist = 0, int maxf = 0, bool slots = false) const {
-      return !stages.empty() && B == b && T == t && feat == f && feat_len == fl && logits == lg && ws == w && ws_bytes == wb &&
-             ep_cap == cap && sstate == st && s_hist == hist && s_maxf == maxf && s_slots == slots;
-    }
+    bool matches(const BindKey& k) const { return !stages.empty() && key == k; }
   };
   Bound cur;
   std::vector<Bound> parked;
@@ -553,14 +556,27 @@ MoeRoute choose_moe_route(const m3_engine_config& c, int S, const BlockW& w, con
   return r;
 }
 
+// What the stage list of one binding is built with.  The binding under construction is a local of build_binding: the engine
+// sees it only once it is complete (bind), so a build that fails leaves the engine as it was.
+struct StageBuilder {
+  const m3_engine& eng;     // weights, config
+  Plan pl;                  // the buffer plan over the key's workspace (the main encoder's view; embed_view for the embed chain)
+  m3_engine::Bound& bd;     // the binding under construction
+  StreamState st;           // streaming keys: the caller-owned state, carved once
+  // what one build_* call hands to the next:
+  bool lens_in_conv1 = false;   // the next conv1 stage also forms the subsampled lengths
+  const float *tail_ln_g = nullptr, *tail_ln_b = nullptr; float tail_ln_eps = 0.f; float* tail_ln_out = nullptr;   // a second LayerNorm for the next norm_final stage
+  float* splitk_ws = nullptr; size_t splitk_bytes = 0;   // partial tiles of the split-K front-end GEMMs now being added (inside the workspace)
+};
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------
-static void add_stage(m3_engine* e, const std::string& name, int kernels, std::function<int(hipStream_t)> fn,
+static void add_stage(StageBuilder& sb, const std::string& name, int kernels, std::function<int(hipStream_t)> fn,
                       m3_stage_info info = stage_info("", 0, 0.0, 0.0)) {
   info.launches = kernels;
-  e->cur.stages.push_back(Stage{name, std::move(fn), info});
-  e->cur.n_kernels += kernels;
+  sb.bd.stages.push_back(Stage{name, std::move(fn), info});
+  sb.bd.n_kernels += kernels;
 }
 
 // algorithmic traffic of one GEMM: weights once, A rows once, result once (+ the residual it adds, + side outputs)
@@ -579,17 +595,17 @@ static m3_stage_info gemm_info(const GemmParams& p, bool splitk) {
 }
 
 // fp32_weights: the router GEMMs keep fp32 weights in every mode (a flipped top-1 is a discrete error)
-static void add_gemm(m3_engine* e, const std::string& name, GemmParams p, bool fp32_weights = false) {
-  p.w_bf16 = (!fp32_weights && e->cfg.weight_dtype != M3_F32) ? 1 : 0;
+static void add_gemm(StageBuilder& sb, const std::string& name, GemmParams p, bool fp32_weights = false) {
+  p.w_bf16 = (!fp32_weights && sb.eng.cfg.weight_dtype != M3_F32) ? 1 : 0;
   size_t need = 0;
-  if (gemm_f32_splitk_plan(p, &need) >= 2 && e->cur.splitk_ws != nullptr && need <= e->cur.splitk_bytes) {
-    float* ws = e->cur.splitk_ws; const size_t wsb = e->cur.splitk_bytes;
-    add_stage(e, name, 2, [p, ws, wsb](hipStream_t s) { return launch_gemm_f32_splitk(p, ws, wsb, s); }, gemm_info(p, true));
+  if (gemm_f32_splitk_plan(p, &need) >= 2 && sb.splitk_ws != nullptr && need <= sb.splitk_bytes) {
+    float* ws = sb.splitk_ws; const size_t wsb = sb.splitk_bytes;
+    add_stage(sb, name, 2, [p, ws, wsb](hipStream_t s) { return launch_gemm_f32_splitk(p, ws, wsb, s); }, gemm_info(p, true));
     return;
   }
-  add_stage(e, name, 1, [p](hipStream_t s) { return launch_gemm_f32(p, s); }, gemm_info(p, false));
-  e->cur.stages.back().fuse_kind = FuseKind::Gemm;
-  e->cur.stages.back().gemm = p;
+  add_stage(sb, name, 1, [p](hipStream_t s) { return launch_gemm_f32(p, s); }, gemm_info(p, false));
+  sb.bd.stages.back().fuse_kind = FuseKind::Gemm;
+  sb.bd.stages.back().gemm = p;
 }
 
 // Horizontal fusion (B = 1-sized fp32 plans): the embed encoder and the main encoder's prefix -- its subsampling and block 0 up to
@@ -625,9 +641,9 @@ static Stage fused_stage(const Stage& a, const Stage& b) {
   d.info = stage_info(label, 1, a.info.alg_bytes + b.info.alg_bytes, a.info.flops + b.info.flops);
   return d;
 }
-static void fuse_independent_pairs(m3_engine* e, int first, int mid, int join) {
+static void fuse_independent_pairs(StageBuilder& sb, int first, int mid, int join) {
   if (first < 0 || mid <= first + 1 || join <= mid) return;
-  std::vector<Stage>& st = e->cur.stages;
+  std::vector<Stage>& st = sb.bd.stages;
   std::vector<Stage> out(st.begin(), st.begin() + first);
   std::vector<Stage> pending;                         // main-prefix stages waiting for the next pair they precede
   int i = first, saved = 0;
@@ -649,7 +665,7 @@ static void fuse_independent_pairs(m3_engine* e, int first, int mid, int join) {
   for (Stage& q : pending) out.push_back(q);
   for (int k = join; k < (int)st.size(); ++k) out.push_back(st[k]);
   st.swap(out);
-  e->cur.n_kernels -= saved;
+  sb.bd.n_kernels -= saved;
 }
 
 // the first stage from `from` on that reads the embedding: where the main encoder joins the embed encoder (-1: none).  The forked
@@ -660,50 +676,50 @@ static int embed_join(const std::vector<Stage>& st, int from) {
   return -1;
 }
 
-static void build_subsample(m3_engine* e, const std::string& pfx, const SubW& w, int D, const Plan& pl, float* xout) {
-  const m3_engine_config& c = e->cfg;
-  const int B = e->cur.B, T = e->cur.T;
+static void build_subsample(StageBuilder& sb, const std::string& pfx, const SubW& w, int D, const Plan& pl, float* xout) {
+  const m3_engine_config& c = sb.eng.cfg;
+  const int B = sb.bd.key.B, T = sb.bd.key.T;
   const int T1 = (T - 3) / 2 + 1, F1 = (c.input_dim - 3) / 2 + 1, F2 = (F1 - 3) / 2 + 1, T2 = (T1 - 3) / 2 + 1;
-  const float* feat = e->cur.feat;
+  const float* feat = sb.bd.key.feat;
   float* c1 = pl.c1; float* c2 = pl.c2;
   const int idim = c.input_dim;
-  const float* cm = e->cmvn_mean; const float* ci = e->cmvn_istd;
-  const bool a16 = e->cur.a16;    // c1, c2 only feed GEMMs: kept as bf16; the Linear also writes the bf16 copy of x
+  const float* cm = sb.eng.cmvn_mean; const float* ci = sb.eng.cmvn_istd;
+  const bool a16 = sb.bd.a16;    // c1, c2 only feed GEMMs: kept as bf16; the Linear also writes the bf16 copy of x
   // (the forward's first conv1 also forms the subsampled lengths when no stage in front of it needs them: see "lens" below)
-  const int32_t* flen = e->cur.lens_in_conv1 ? e->cur.feat_len : nullptr;
+  const int32_t* flen = sb.lens_in_conv1 ? sb.bd.key.feat_len : nullptr;
   int32_t* lens_out = pl.lens;
-  e->cur.lens_in_conv1 = false;
-  add_stage(e, pfx + "conv1", 1, [=](hipStream_t s) { return launch_conv1_relu(feat, w.c1w, w.c1b, cm, ci, B, T, idim, D, c1, s, 1, a16, flen, lens_out); },
+  sb.lens_in_conv1 = false;
+  add_stage(sb, pfx + "conv1", 1, [=](hipStream_t s) { return launch_conv1_relu(feat, w.c1w, w.c1b, cm, ci, B, T, idim, D, c1, s, 1, a16, flen, lens_out); },
             stage_info("conv1_relu_kernel", 1, (double)B * T * idim * 4 + (double)B * T1 * F1 * D * (a16 ? 2 : 4), 18.0 * B * T1 * F1 * D, false));
   GemmParams g;
   g.a_bf16 = a16; g.y_bf16 = a16;
   g.mode = GEMM_A_CONV3X3S2; g.A = c1; g.lda = 4;
   g.conv_T1 = T1; g.conv_F1 = F1; g.conv_T2 = T2; g.conv_F2 = F2; g.conv_C = D;
   g.W = w.c2w; g.bias = w.c2b; g.Y = c2; g.ldy = D; g.M = B * T2 * F2; g.N = D; g.K = 9 * D; g.act = ACT_RELU;
-  if (e->cur.packed) g.conv_len = pl.lens;   // tiles of padded frames only: skipped (never gathered into the packed rows)
-  add_gemm(e, pfx + "conv2", g);
+  if (sb.bd.packed) g.conv_len = pl.lens;   // tiles of padded frames only: skipped (never gathered into the packed rows)
+  add_gemm(sb, pfx + "conv2", g);
   // Linear(C*F2 -> D) on the (f, c)-ordered flatten, with the positional-encoding scale sqrt(D)
   // (rel_positional_encoding_kernel.cu:62-69) folded into the epilogue.
   // packed ragged batch: the subsampler works on the padded (B, T) input; its rows are packed right after it
-  const bool packed = e->cur.packed;
+  const bool packed = sb.bd.packed;
   GemmParams l;
   l.A = c2; l.lda = F2 * D; l.W = w.out.w; l.bias = w.out.b; l.Y = packed ? pl.xpad : xout; l.ldy = D;
   l.M = B * T2; l.N = D; l.K = F2 * D; l.alpha = sqrtf((float)D);
   l.a_bf16 = a16;
   if (a16) { l.Yb = packed ? pl.xbpad : pl.xb; l.ldyb = D; }
-  add_gemm(e, pfx + "linear", l);
+  add_gemm(sb, pfx + "linear", l);
   if (packed) {
     const float* xpad = pl.xpad; const void* xbpad = pl.xbpad; void* xb = pl.xb; const int32_t* pad_of = pl.pad_of;
     const int S = B * T2;
-    add_stage(e, pfx + "pack", a16 ? 2 : 1, [=](hipStream_t s) {
+    add_stage(sb, pfx + "pack", a16 ? 2 : 1, [=](hipStream_t s) {
       if (int rc = launch_local_gather(xpad, pad_of, S, D * 4, xout, s)) return rc;
       return a16 ? launch_local_gather(xbpad, pad_of, S, D * 2, xb, s) : 0;
     }, stage_info("row_permute_kernel", 1, (double)S * D * (a16 ? 12 : 8) + 4.0 * S, 0.0));
   }
-  if (e->cur.dma) {   // the first block's folded-LayerNorm GEMM takes the row statistics of xb from its producer: here a pass of its own
+  if (sb.bd.dma) {   // the first block's folded-LayerNorm GEMM takes the row statistics of xb from its producer: here a pass of its own
     const void* xbv = pl.xb; float* xs = pl.xstats;
     const int S = B * T2;
-    add_stage(e, pfx + "row_stats", 1, [=](hipStream_t s) { return launch_row_stats_bf16(xbv, S, D, xs, s); },
+    add_stage(sb, pfx + "row_stats", 1, [=](hipStream_t s) { return launch_row_stats_bf16(xbv, S, D, xs, s); },
               stage_info("row_stats_bf16_kernel", 1, (double)S * D * 2 + 32.0 * S, 3.0 * S * D));
   }
 }
@@ -725,11 +741,11 @@ struct MoeLayer {
   void* ws; MoeWorkspace mw;             // the layer's MoE workspace, carved for the S local rows
 };
 
-static void add_moe_router(m3_engine* e, const MoeLayer& m, const MoeRoute& r, const Plan& pl) {
+static void add_moe_router(StageBuilder& sb, const MoeLayer& m, const MoeRoute& r, const Plan& pl) {
   const BlockW& w = *m.w;
   const int S = m.S, D = m.D, De = m.De, E = m.E, Etot = m.Etot;
   if (r.router == RouterForm::Fused) {
-    add_stage(e, m.pfx + "moe_route", 1, [m](hipStream_t s) {
+    add_stage(sb, m.pfx + "moe_route", 1, [m](hipStream_t s) {
       const BlockW& w = *m.w;
       return launch_moe_route(m.x, m.D, m.D, w.router_x.w, w.router_x.wsum, w.router_x.b, m.eall, m.ld_eall, m.eps, m.lens, m.Tp,
                               m.S, m.E, m.gidx, m.gval, m.mw.mapping, m.mw.acc, m.mw.pos, s);
@@ -737,10 +753,10 @@ static void add_moe_router(m3_engine* e, const MoeLayer& m, const MoeRoute& r, c
   } else if (r.router == RouterForm::Kernel) {
     void* xq = r.use_xq ? pl.xq : nullptr; float* xqs = r.use_xq ? pl.xq_scale : nullptr;
     float* xn_out = r.skip_xn ? nullptr : m.xn;
-    if (r.skip_xn) e->cur.xn_skipped = true;   // ("xn" is then not offered as a buffer: a reader fails instead of reading stale rows)
+    if (r.skip_xn) sb.bd.xn_skipped = true;   // ("xn" is then not offered as a buffer: a reader fails instead of reading stale rows)
     int32_t* gidx = r.router_top1 ? m.gidx : nullptr; float* gval = r.router_top1 ? m.gval : nullptr;
     const float* emb = pl.emb;
-    add_stage(e, m.pfx + "moe_router", 1, [=](hipStream_t s) {
+    add_stage(sb, m.pfx + "moe_router", 1, [=](hipStream_t s) {
       const BlockW& w = *m.w;
       return launch_moe_router(emb, m.De, m.De, m.x, m.D, m.D, w.router.w, w.router.b, w.n_ff.g, w.n_ff.b, m.eps, xn_out, m.D, m.rl,
                                m.Etot, m.S, m.Etot, m.pdev, s, gidx, gval, m.live_len, m.live_rpb, xq, xqs);
@@ -756,27 +772,27 @@ static void add_moe_router(m3_engine* e, const MoeLayer& m, const MoeRoute& r, c
       g.W = w.router.w; g.bias = w.router.b;
       g.ln_gamma = w.n_ff.g; g.ln_beta = w.n_ff.b; g.ln_eps = m.eps; g.ln_on_a2 = 1; g.ln_out = m.xn; g.ld_ln_out = D;
     }
-    add_gemm(e, m.pfx + "moe_router", g, true);
+    add_gemm(sb, m.pfx + "moe_router", g, true);
   }
-  e->cur.stages.back().reads_embed = true;
+  sb.bd.stages.back().reads_embed = true;
 }
 
 // SoftmaxTopK plugin + ScatterMapping kernel of the reference in ONE launch (a single work-group: right for a few hundred rows);
 // the index over the local (map, acc, pos) or, expert parallel, over the global expert ids
-static void add_moe_gate_index(m3_engine* e, const MoeLayer& m, int32_t* map, int32_t* acc, int32_t* pos) {
-  add_stage(e, m.pfx + "moe_gate_index", 1, [=](hipStream_t s) {
+static void add_moe_gate_index(StageBuilder& sb, const MoeLayer& m, int32_t* map, int32_t* acc, int32_t* pos) {
+  add_stage(sb, m.pfx + "moe_gate_index", 1, [=](hipStream_t s) {
     return launch_moe_gate_index(m.rl, m.Etot, m.live_len, m.live_rpb, m.S, m.gidx, m.gval, map, acc, pos, s);
   }, stage_info("moe_index_kernel", 1, (double)m.S * (m.Etot * 4 + 16) + 4.0 * (m.Etot + 1), 0.0));
 }
 
-static void add_moe_top1(m3_engine* e, const MoeLayer& m) {
-  add_stage(e, m.pfx + "moe_top1", 1, [m](hipStream_t s) {
+static void add_moe_top1(StageBuilder& sb, const MoeLayer& m) {
+  add_stage(sb, m.pfx + "moe_top1", 1, [m](hipStream_t s) {
     return launch_softmax_top1(m.rl, m.Etot, m.live_len, m.live_rpb, m.S, m.Etot, m.gidx, m.gval, s);
   }, stage_info("softmax_top1_kernel", 1, (double)m.S * (m.Etot * 4 + 8), 0.0));
 }
 
-static void add_moe_local_index(m3_engine* e, const MoeLayer& m) {
-  add_stage(e, m.pfx + "moe_local.index", 1, [m](hipStream_t s) {
+static void add_moe_local_index(StageBuilder& sb, const MoeLayer& m) {
+  add_stage(sb, m.pfx + "moe_local.index", 1, [m](hipStream_t s) {
     return launch_moe_index(m.gidx, m.S, m.E, m.mw.mapping, m.mw.acc, m.mw.pos, s);
   }, stage_info("moe_index_kernel", 1, 12.0 * m.S + 4.0 * (m.E + 1), 0.0));
 }
@@ -820,13 +836,13 @@ static int launch_expert(const ExpertForm& f, const BlockW& w, const float* x, c
   return launch_expert_ffn_f32(x, D, mw.pos, mw.acc, R, E, D, F, w.ew1, w.eb1, w.ew2, 1, mw.slab, ln_g, ln_b, ln_eps, s);
 }
 
-static void add_moe_local_expert(m3_engine* e, const MoeLayer& m, const MoeRoute& r, const ExpertForm& f, const Plan& pl) {
+static void add_moe_local_expert(StageBuilder& sb, const MoeLayer& m, const MoeRoute& r, const ExpertForm& f, const Plan& pl) {
   const bool norm = r.norm_in_expert();
   const float* xin = norm ? m.x : m.xn;
   const bool self_route = r.gate == GateForm::InExpert;
   const void* xq = r.use_xq ? pl.xq : nullptr; const float* xqs = r.use_xq ? pl.xq_scale : nullptr;
   int32_t* fs = r.fs_dev ? pl.moe_fs : nullptr;
-  add_stage(e, m.pfx + "moe_local.expert", f.launches, [=](hipStream_t s) {
+  add_stage(sb, m.pfx + "moe_local.expert", f.launches, [=](hipStream_t s) {
     const BlockW& w = *m.w;
     const float* ln_g = norm ? w.n_ff.g : nullptr; const float* ln_b = norm ? w.n_ff.b : nullptr; const float ln_eps = norm ? m.eps : 0.f;
     // short inputs, fp32: SoftmaxTopK + ScatterMapping happen inside the expert launch (every work-group derives its expert's
@@ -839,14 +855,14 @@ static void add_moe_local_expert(m3_engine* e, const MoeLayer& m, const MoeRoute
 }
 
 // local_gather + b2 + gate + residual + LayerNorm(norm_final) over the expert outputs
-static void add_moe_local_combine(m3_engine* e, const MoeLayer& m, const MoeRoute& r, const ExpertForm& f, const Plan& pl) {
+static void add_moe_local_combine(StageBuilder& sb, const MoeLayer& m, const MoeRoute& r, const ExpertForm& f, const Plan& pl) {
   // (self-routing expert launch: slabs hold ORIGINAL rows with b2 already in slice 0 -> no mapping, no b2 here)
   const bool self_route = r.gate == GateForm::InExpert;
   const int32_t* cmap = self_route ? nullptr : m.mw.mapping;
   const float* cb2 = self_route ? nullptr : m.w->eb2;
   const int32_t* fs = r.fs_dev ? pl.moe_fs : nullptr;
   const double S = m.S, D = m.D;
-  add_stage(e, m.pfx + "moe_local.combine", 1, [=](hipStream_t s) {
+  add_stage(sb, m.pfx + "moe_local.combine", 1, [=](hipStream_t s) {
     const BlockW& w = *m.w;
     return launch_moe_combine(f.rows, fs ? 4 : f.slices, cmap, m.gidx, m.gv, cb2, m.x, 0.5f, w.n_final.g, w.n_final.b, m.eps, m.x,
                               m.S, m.D, s, m.xb_out, m.xstats_out, fs);
@@ -856,7 +872,7 @@ static void add_moe_local_combine(m3_engine* e, const MoeLayer& m, const MoeRout
 // Expert parallel (m3asr/ep.py drives the two all-to-alls between these stages; FastMoE semantics
 // trainer_3m_fix/fmoe/functions.py:13-86,175-199): nothing returns to the host, the exchange has a fixed shape
 // wire [world][1 + C][D]: chunk j = what goes to / came from rank j, header row = E_loc row counts
-static void add_moe_ep(m3_engine* e, const MoeLayer& m, const MoeRoute& r, const Plan& pl) {
+static void add_moe_ep(StageBuilder& sb, const MoeLayer& m, const MoeRoute& r, const Plan& pl) {
   const int S = m.S, E = m.E, Etot = m.Etot, D = m.D, F = m.F, world = m.world;
   const int cap = pl.ep_cap, R = pl.ep_rows;
   int32_t *g_acc = pl.ep_acc, *g_map = pl.ep_mapping, *g_pos = pl.ep_pos, *map_send = pl.ep_map_send, *gate_recv = pl.ep_gate_recv;
@@ -864,18 +880,18 @@ static void add_moe_ep(m3_engine* e, const MoeLayer& m, const MoeRoute& r, const
   float *wire_a = pl.wire_a, *wire_b = pl.wire_b;
   const MoeWorkspace rw = carve_moe_workspace(m.ws, R, E, D, F);     // receive side: R wire rows over the E local experts
   // top-1 + index over GLOBAL expert ids (the same kernel choice by row count as with all experts local)
-  if (r.gate == GateForm::GateIndex) add_moe_gate_index(e, m, g_map, g_acc, g_pos);
-  if (r.gate == GateForm::Top1Index) add_moe_top1(e, m);
+  if (r.gate == GateForm::GateIndex) add_moe_gate_index(sb, m, g_map, g_acc, g_pos);
+  if (r.gate == GateForm::Top1Index) add_moe_top1(sb, m);
   // wire row of every token (+ count headers), rows scattered straight into the send wire
   const bool one_launch = r.gate == GateForm::GateIndex;
   const int32_t* gidx = m.gidx; const float* xn = m.xn;
-  add_stage(e, m.pfx + "moe_ep.send", one_launch ? 1 : 2, [=](hipStream_t s) {
+  add_stage(sb, m.pfx + "moe_ep.send", one_launch ? 1 : 2, [=](hipStream_t s) {
     if (!one_launch)
       if (int rc = launch_moe_index(gidx, S, Etot, g_map, g_acc, g_pos, s)) return rc;
     return launch_ep_send_rows(gidx, g_map, g_acc, S, world, E, cap, map_send, xn, wire_a, D * 4, s, ep_overflow);
   }, stage_info("ep_send_rows_kernel", 1, (double)S * D * 8 + 24.0 * S, 0.0));
-  auto exchange = [=](const char* name) {   // one rank: the all-to-all is a copy
-    if (world == 1) add_stage(e, m.pfx + name, 0, [=](hipStream_t s) {
+  auto exchange = [=, &sb](const char* name) {   // one rank: the all-to-all is a copy
+    if (world == 1) add_stage(sb, m.pfx + name, 0, [=](hipStream_t s) {
       M3_CHECK_HIP(hipMemcpyAsync(wire_b, wire_a, (size_t)R * D * 4, hipMemcpyDeviceToDevice, s));
       return 0;
     });
@@ -883,12 +899,12 @@ static void add_moe_ep(m3_engine* e, const MoeLayer& m, const MoeRoute& r, const
   exchange("moe_ep.exchange1");
   // this rank's experts on everything it received (its own stable index puts the rows in FastMoE's receive order: by local
   // expert, then source rank, then wire order); results return to wire_a at the wire rows they came in on
-  const ExpertForm f = expert_form(e->cfg, m.w->h_scale, rw.slab, R, E, D, F, false);
+  const ExpertForm f = expert_form(sb.eng.cfg, m.w->h_scale, rw.slab, R, E, D, F, false);
   // bf16 experts in the tiled two-GEMM form: GEMM-2's epilogue adds b2 and puts every row straight back on its wire row
   // (no un-permuting combine launch; wire rows nobody sent keep stale bytes -- no rank ever reads them back)
   const bool scatter2 = f.wmode == 1 && expert_ffn_bf16_tiled(R, E, D, F);
   const BlockW* wp = m.w;
-  add_stage(e, m.pfx + "moe_ep.expert", (scatter2 ? 2 : 3) + f.launches, [=](hipStream_t s) {
+  add_stage(sb, m.pfx + "moe_ep.expert", (scatter2 ? 2 : 3) + f.launches, [=](hipStream_t s) {
     const BlockW& w = *wp;
     if (int rc = launch_ep_recv_gate(wire_b, world, E, cap, D * 4, gate_recv, s)) return rc;
     if (int rc = launch_moe_index(gate_recv, R, E, rw.mapping, rw.acc, rw.pos, s)) return rc;
@@ -898,33 +914,39 @@ static void add_moe_ep(m3_engine* e, const MoeLayer& m, const MoeRoute& r, const
   }, stage_info(f.kernel, 1, -1.0, 4.0 * D * F * S));
   exchange("moe_ep.exchange2");
   // local_gather + gate + residual + LayerNorm: token s reads its result at the wire row it was sent from
-  add_stage(e, m.pfx + "moe_ep.combine", 1, [=](hipStream_t s) {
+  add_stage(sb, m.pfx + "moe_ep.combine", 1, [=](hipStream_t s) {
     const BlockW& w = *wp;
     return launch_moe_combine(wire_b, 1, map_send, nullptr, m.gv, nullptr, m.x, 0.5f, w.n_final.g, w.n_final.b, m.eps, m.x, S, D, s,
                               m.xb_out, m.xstats_out);
   }, stage_info("moe_combine_kernel", 1, (double)S * D * 12 + (m.xb_out ? 2.0 * S * D : 0.0), (double)S * D * 11));
-  e->cur.buffers["ep.wire_a"] = Buf{wire_a, (size_t)R * D * 4};
-  e->cur.buffers["ep.wire_b"] = Buf{wire_b, (size_t)R * D * 4};
+  sb.bd.buffers["ep.wire_a"] = Buf{wire_a, (size_t)R * D * 4};
+  sb.bd.buffers["ep.wire_b"] = Buf{wire_b, (size_t)R * D * 4};
 }
 
-static void build_block(m3_engine* e, const std::string& pfx, const BlockW& w, int D, int F, int H, int K, bool cnn_ln,
+static void build_block(StageBuilder& sb, const std::string& pfx, const BlockW& w, int D, int F, int H, int K, bool cnn_ln,
                         bool moe, int layer, int tap_index, const Plan& pl, bool causal) {
   // every GEMM of a block is row-wise over the S rows of the batch: packed batches pass the live-row count
-  auto add_gemm = [&](m3_engine* e_, const std::string& name, GemmParams g, bool fp32_weights = false) {
-    if (e_->cur.packed) g.m_dev = pl.row0 + e_->cur.B;
-    ::add_gemm(e_, name, g, fp32_weights);
+  auto add_gemm = [&](StageBuilder&, const std::string& name, GemmParams g, bool fp32_weights = false) {
+    if (sb.bd.packed) g.m_dev = pl.row0 + sb.bd.key.B;
+    ::add_gemm(sb, name, g, fp32_weights);
   };
-  const m3_engine_config& c = e->cfg;
-  const int B = e->cur.B, Tp = e->cur.Tp, S = e->cur.S;
+  const m3_engine_config& c = sb.eng.cfg;
+  const BindKey& key = sb.bd.key;
+  const int B = key.B, Tp = sb.bd.Tp, S = sb.bd.S;
+  // chunk-by-chunk binding: the chunk counter the attention core and the depthwise conv read.  Slot mode: the counter of
+  // utterance b is slot_pos[b]; max_frames / c chunks fit (the kernels test a slot against it)
+  const bool streaming = key.sstate != nullptr;
+  const int32_t* step = key.s_slots ? sb.st.slot_pos : sb.st.step;
+  const int slot_chunks = key.s_slots ? key.s_maxf / Tp : -1;
   float* x = pl.x;
   const int32_t* lens = pl.lens;
   const float eps = 1e-12f;  // all block LayerNorms (fmoe_transformer.py:54-65)
 
   // 16-bit modes, long batches: GEMM A operands come as bf16 -- the copy xb of the residual stream (written by every
   // kernel that writes x) and bf16 h1 / ctx / dw -- because these GEMMs are bound by the traffic of their fp32 A operand
-  const bool a16 = e->cur.a16;
+  const bool a16 = sb.bd.a16;
   void* xb = pl.xb;
-  const bool dma = e->cur.dma;
+  const bool dma = sb.bd.dma;
   float* xstats = pl.xstats;
   auto from_xb = [&](GemmParams& g) {
     if (a16) { g.A = (const float*)xb; g.a_bf16 = 1; }
@@ -936,7 +958,7 @@ static void build_block(m3_engine* e, const std::string& pfx, const BlockW& w, i
   };
   // packed ragged batch: rows [0, P) are the valid frames of all utterances back to back, P = row0[B] on the device;
   // row-wise kernels skip the tiles beyond P, attention and the depthwise conv find their utterance through row0 / pad_of
-  const bool packed = e->cur.packed;
+  const bool packed = sb.bd.packed;
   const int32_t* row0 = packed ? pl.row0 : nullptr;
   const int32_t* pad_of = packed ? pl.pad_of : nullptr;
   const int32_t* pdev = packed ? pl.row0 + B : nullptr;
@@ -948,12 +970,12 @@ static void build_block(m3_engine* e, const std::string& pfx, const BlockW& w, i
     g.A = x; g.lda = D; g.W = w.mac1.w; g.bias = w.mac1.b; g.Y = pl.h1; g.ldy = F; g.M = S; g.N = F; g.K = D;
     g.ln_wsum = w.mac1.wsum; g.ln_eps = eps; g.act = ACT_SILU;   // norm_ff_macaron is folded into w_1 (plan.py)
     from_xb(g); g.y_bf16 = a16;
-    add_gemm(e, pfx + "ffn_macaron.w1", g);
+    add_gemm(sb, pfx + "ffn_macaron.w1", g);
     GemmParams h;
     h.A = pl.h1; h.lda = F; h.W = w.mac2.w; h.bias = w.mac2.b; h.Y = x; h.ldy = D; h.M = S; h.N = D; h.K = F;
     h.alpha = 0.5f; h.resid = x; h.ldr = D;
     h.a_bf16 = a16; also_xb(h);
-    add_gemm(e, pfx + "ffn_macaron.w2", h);
+    add_gemm(sb, pfx + "ffn_macaron.w2", h);
   }
   {  // x += MHA(LN(x))
     GemmParams g;
@@ -964,7 +986,7 @@ static void build_block(m3_engine* e, const std::string& pfx, const BlockW& w, i
     // K / P / V of a head staged once per (utterance, head) (attention.hip, second kernel)
     const bool att16 = a16 && relpos_attention_bf16_supports(Tp, D / H);
     g.y_bf16 = att16;
-    add_gemm(e, pfx + "att.qkv", g);
+    add_gemm(sb, pfx + "att.qkv", g);
     // p = linear_pos(pos_emb) of all blocks comes from ONE GEMM per forward ("pos_all" stage):
     // block i's slice is columns [i*D, (i+1)*D) of pbuf [T'][n_blocks*D]
     const int ldp = (c.num_blocks + c.embed_blocks) * D;
@@ -974,19 +996,15 @@ static void build_block(m3_engine* e, const std::string& pfx, const BlockW& w, i
     const int dk = D / H;
     const float scale = 1.f / sqrtf((float)dk);
     const int chunk = c.static_chunk_size, left_chunks = c.num_left_chunks;   // static chunk mask (0 = full context)
-    if (e->cur.sstate != nullptr) {   // chunk-by-chunk: keys = K / V history + this chunk, positions absolute, history appended in place
-      const StreamState st = carve_stream_state(c, e->cur.sstate, B, e->cur.s_hist);
-      float* hist = st.kv[tap_index]; const int cap = e->cur.s_hist;
-      // slot mode: the counter of utterance b is slot_pos[b]; max_frames / c chunks fit (the kernels test a slot against it)
-      const int32_t* step = e->cur.s_slots ? st.slot_pos : st.step;
-      const int slot_chunks = e->cur.s_slots ? e->cur.s_maxf / Tp : -1;
-      add_stage(e, pfx + "att.core", 1, [=](hipStream_t s) {
+    if (streaming) {   // chunk-by-chunk: keys = K / V history + this chunk, positions absolute, history appended in place
+      float* hist = sb.st.kv[tap_index]; const int cap = key.s_hist;
+      add_stage(sb, pfx + "att.core", 1, [=](hipStream_t s) {
         return launch_relpos_attention_stream(qkv, 3 * D, hist, cap, pmat, ldp, pu, pv, lens, step, B, Tp, H, dk, scale, ctx, D, left_chunks, s,
                                               slot_chunks);
       }, stage_info("relpos_attention_stream_kernel", 1, (double)S * D * 24 + (double)Tp * D * 4, 6.0 * Tp * D * S));
     } else
     {
-    add_stage(e, pfx + "att.core", 1, [=](hipStream_t s) {
+    add_stage(sb, pfx + "att.core", 1, [=](hipStream_t s) {
       if (att16) return launch_relpos_attention_bf16(qkv, 3 * D, pmat, ldp, pu, pv, lens, B, Tp, H, dk, scale, ctx, D, s, row0, chunk, left_chunks);
       return launch_relpos_attention(qkv, 3 * D, pmat, ldp, pu, pv, lens, B, Tp, H, dk, scale, ctx, D, s, a16, row0, chunk, left_chunks);
     }, stage_info(att16 ? "relpos_attention_bf16_kernel" : "relpos_attention_kernel", 1,
@@ -995,15 +1013,15 @@ static void build_block(m3_engine* e, const std::string& pfx, const BlockW& w, i
       AttArgs aa;
       aa.qkv = qkv; aa.ldq = 3 * D; aa.pmat = pmat; aa.ldp = ldp; aa.pos_u = pu; aa.pos_v = pv; aa.row_len = lens; aa.B = B; aa.T = Tp; aa.H = H;
       aa.dk = dk; aa.scale = scale; aa.out = ctx; aa.ldo = D; aa.out_bf16 = a16; aa.row0 = row0; aa.chunk = chunk; aa.left_chunks = left_chunks;
-      e->cur.stages.back().fuse_kind = FuseKind::Attention;
-      e->cur.stages.back().att = aa;
+      sb.bd.stages.back().fuse_kind = FuseKind::Attention;
+      sb.bd.stages.back().att = aa;
     }
     }
     GemmParams o;
     o.A = pl.ctx; o.lda = D; o.W = w.out.w; o.bias = w.out.b; o.Y = x; o.ldy = D; o.M = S; o.N = D; o.K = D;
     o.resid = x; o.ldr = D;
     o.a_bf16 = a16; also_xb(o);
-    add_gemm(e, pfx + "att.out", o);
+    add_gemm(sb, pfx + "att.out", o);
   }
   {  // x += ConvModule(LN(x))
     GemmParams g;
@@ -1013,17 +1031,14 @@ static void build_block(m3_engine* e, const std::string& pfx, const BlockW& w, i
     // row P thereby receives the constant a zeroed frame produces -- the depthwise conv reads it for taps len <= t < T'
     g.row_len = live_len; g.rows_per_batch = live_rpb; g.mask_in = 1;
     from_xb(g);
-    add_gemm(e, pfx + "conv.pw1_glu", g);
+    add_gemm(sb, pfx + "conv.pw1_glu", g);
     const float* glu = pl.glu; float* dw = pl.dw;
     const float* dww = w.dw_w; const float* dwb = w.dw_b;
     const float* ng = cnn_ln ? w.n_cnn.g : nullptr; const float* nb = cnn_ln ? w.n_cnn.b : nullptr;
     const float* lfill = causal ? w.left_fill : nullptr;   // causal conv module (convolution.py:43-49,118-123)
-    if (e->cur.sstate != nullptr) {
-      const StreamState st = carve_stream_state(c, e->cur.sstate, B, e->cur.s_hist);
-      float* cpair = st.conv[tap_index];
-      const int32_t* step = e->cur.s_slots ? st.slot_pos : st.step;
-      const int slot_chunks = e->cur.s_slots ? e->cur.s_maxf / Tp : -1;
-      add_stage(e, pfx + "conv.dw_ln_silu", 1, [=](hipStream_t s) {
+    if (streaming) {
+      float* cpair = sb.st.conv[tap_index];
+      add_stage(sb, pfx + "conv.dw_ln_silu", 1, [=](hipStream_t s) {
         return launch_dwconv_ln_silu_stream(glu, dww, dwb, ng, nb, 1e-5f, B, Tp, D, K, dw, cpair, step, lens, s, a16, slot_chunks);
       }, stage_info("dwconv_ln_silu_kernel", 1, (double)S * D * 8 + (double)K * D * 4 + 8.0 * B * (K - 1) * D, 2.0 * K * D * S));
     } else
@@ -1031,36 +1046,36 @@ static void build_block(m3_engine* e, const std::string& pfx, const BlockW& w, i
       DwArgs da;
       da.z = glu; da.w_kc = dww; da.bias = dwb; da.gamma = ng; da.beta = nb; da.eps = 1e-5f; da.B = B; da.T = Tp; da.D = D; da.K = K;
       da.out = dw; da.out_bf16 = a16; da.pad_of = pad_of; da.row0 = row0; da.row_len = lens; da.causal_left_fill = lfill;
-      add_stage(e, pfx + "conv.dw_ln_silu", 1, [da](hipStream_t s) { return launch_dwconv_ln_silu_args(da, s); },
+      add_stage(sb, pfx + "conv.dw_ln_silu", 1, [da](hipStream_t s) { return launch_dwconv_ln_silu_args(da, s); },
                 stage_info("dwconv_ln_silu_kernel", 1, (double)S * D * (4 + (a16 ? 2 : 4)) + (double)K * D * 4, 2.0 * K * D * S));
-      e->cur.stages.back().fuse_kind = FuseKind::Dwconv;
-      e->cur.stages.back().dw = da;
+      sb.bd.stages.back().fuse_kind = FuseKind::Dwconv;
+      sb.bd.stages.back().dw = da;
     }
     GemmParams h;
     h.A = pl.dw; h.lda = D; h.W = w.pw2.w; h.bias = w.pw2.b; h.Y = x; h.ldy = D; h.M = S; h.N = D; h.K = D;
     h.row_len = live_len; h.rows_per_batch = live_rpb; h.mask_out = 1; h.resid = x; h.ldr = D;
     h.a_bf16 = a16; also_xb(h);
-    add_gemm(e, pfx + "conv.pw2", h);
+    add_gemm(sb, pfx + "conv.pw2", h);
   }
   if (!moe) {  // x = LN_final(x + 0.5 * FFN(LN(x)))
     GemmParams g;
     g.A = x; g.lda = D; g.W = w.ff1.w; g.bias = w.ff1.b; g.Y = pl.h1; g.ldy = F; g.M = S; g.N = F; g.K = D;
     g.ln_wsum = w.ff1.wsum; g.ln_eps = eps; g.act = ACT_SILU;   // norm_ff is folded into w_1
     from_xb(g); g.y_bf16 = a16;
-    add_gemm(e, pfx + "ffn.w1", g);
+    add_gemm(sb, pfx + "ffn.w1", g);
     GemmParams h;
     h.A = pl.h1; h.lda = F; h.W = w.ff2.w; h.bias = w.ff2.b; h.Y = x; h.ldy = D; h.M = S; h.N = D; h.K = F;
     h.alpha = 0.5f; h.resid = x; h.ldr = D;
     h.a_bf16 = a16;                                   // (x is rewritten by norm_final below: no bf16 copy here)
-    add_gemm(e, pfx + "ffn.w2", h);
+    add_gemm(sb, pfx + "ffn.w2", h);
     const float* fg = w.n_final.g; const float* fb = w.n_final.b;
     void* xbo = a16 ? xb : nullptr;
     float* xso = dma ? xstats : nullptr;
     // (the embed encoder's last block: after_norm rides in the same launch, conformer_embed_domain_acc.py:171-181)
-    const float* g2 = e->cur.tail_ln_g; const float* b2 = e->cur.tail_ln_b; float* y2 = e->cur.tail_ln_out;
-    const float eps2 = e->cur.tail_ln_eps;
-    e->cur.tail_ln_g = nullptr;
-    add_stage(e, pfx + "norm_final", 1, [=](hipStream_t s) { return launch_layernorm(x, fg, fb, eps, x, S, D, s, xbo, xso, g2, b2, eps2, y2); },
+    const float* g2 = sb.tail_ln_g; const float* b2 = sb.tail_ln_b; float* y2 = sb.tail_ln_out;
+    const float eps2 = sb.tail_ln_eps;
+    sb.tail_ln_g = nullptr;
+    add_stage(sb, pfx + "norm_final", 1, [=](hipStream_t s) { return launch_layernorm(x, fg, fb, eps, x, S, D, s, xbo, xso, g2, b2, eps2, y2); },
               stage_info("layernorm_kernel", 1, (double)S * D * (a16 ? 10 : 8) + (g2 ? 4.0 * S * D : 0.0), (g2 ? 16.0 : 8.0) * S * D));
   } else {  // x = LN_final(x + 0.5 * gate * Expert_g(LN(x)))     (positionwise_feed_forward.py:209-265)
     MoeLayer m;
@@ -1075,30 +1090,30 @@ static void build_block(m3_engine* e, const std::string& pfx, const BlockW& w, i
     m.ws = (char*)pl.moe_ws + (c.debug_taps ? (size_t)layer * pl.moe_ws_bytes : 0);
     m.mw = carve_moe_workspace(m.ws, S, m.E, D, F);
     const MoeRoute r = choose_moe_route(c, S, w, pl);
-    add_moe_router(e, m, r, pl);
+    add_moe_router(sb, m, r, pl);
     if (r.ep) {
-      add_moe_ep(e, m, r, pl);
+      add_moe_ep(sb, m, r, pl);
     } else {   // "moe_local.*": index + grouped expert FFN + combine with all experts local
-      if (r.gate == GateForm::GateIndex) add_moe_gate_index(e, m, m.mw.mapping, m.mw.acc, m.mw.pos);
-      if (r.gate == GateForm::Top1Index) add_moe_top1(e, m);
-      if (r.gate == GateForm::Top1Index || r.gate == GateForm::RouterTail) add_moe_local_index(e, m);
+      if (r.gate == GateForm::GateIndex) add_moe_gate_index(sb, m, m.mw.mapping, m.mw.acc, m.mw.pos);
+      if (r.gate == GateForm::Top1Index) add_moe_top1(sb, m);
+      if (r.gate == GateForm::Top1Index || r.gate == GateForm::RouterTail) add_moe_local_index(sb, m);
       const ExpertForm f = expert_form(c, w.h_scale, m.mw.slab, S, m.E, D, F, r.norm_in_expert());
-      add_moe_local_expert(e, m, r, f, pl);
-      add_moe_local_combine(e, m, r, f, pl);
+      add_moe_local_expert(sb, m, r, f, pl);
+      add_moe_local_combine(sb, m, r, f, pl);
     }
     const std::string b = pfx.substr(0, pfx.size() - 1);
-    e->cur.buffers[b + ".gate_idx"] = Buf{m.gidx, (size_t)S * 4};
-    e->cur.buffers[b + ".gate_value"] = Buf{m.gval, (size_t)S * 4};
-    e->cur.buffers[b + ".mapping"] = Buf{m.mw.mapping, (size_t)S * 4};
-    e->cur.buffers[b + ".acc_histogram"] = Buf{m.mw.acc, (size_t)(m.E + 1) * 4};
+    sb.bd.buffers[b + ".gate_idx"] = Buf{m.gidx, (size_t)S * 4};
+    sb.bd.buffers[b + ".gate_value"] = Buf{m.gval, (size_t)S * 4};
+    sb.bd.buffers[b + ".mapping"] = Buf{m.mw.mapping, (size_t)S * 4};
+    sb.bd.buffers[b + ".acc_histogram"] = Buf{m.mw.acc, (size_t)(m.E + 1) * 4};
   }
   if (c.debug_taps) {
     float* tap = pl.taps + (size_t)tap_index * S * D;
-    add_stage(e, pfx + "tap", 0, [=](hipStream_t s) {
+    add_stage(sb, pfx + "tap", 0, [=](hipStream_t s) {
       M3_CHECK_HIP(hipMemcpyAsync(tap, x, (size_t)S * D * sizeof(float), hipMemcpyDeviceToDevice, s));
       return 0;
     });
-    e->cur.buffers[pfx.substr(0, pfx.size() - 1) + ".out"] = Buf{tap, (size_t)S * D * 4};
+    sb.bd.buffers[pfx.substr(0, pfx.size() - 1) + ".out"] = Buf{tap, (size_t)S * D * 4};
   }
 }
 
@@ -1202,90 +1217,62 @@ size_t m3_engine_workspace_size(const m3_engine* engine, int B, int T) {
   return make_plan(engine->cfg, nullptr, B, T, engine->ep_capacity).bytes;
 }
 
-static int prepare_impl(m3_engine* e, const float* feat, const int32_t* feat_len, int B, int T, float* logits,
-                        void* workspace, size_t workspace_bytes, void* sstate, int s_hist, int s_maxf, bool s_slots = false) {
-  M3_REQUIRE(e && feat && feat_len && logits && workspace, "engine_prepare: null argument");
+// once, outside graph capture (idempotent): the dynamic-LDS opt-ins and the like of every kernel family a stage list can hold
+static int init_engine_kernels() {
+  int (*const inits[])() = {init_expert_ffn_kernels, init_expert_ffn_bf16_kernels, init_expert_ffn_w8_kernels, init_gemm_bf16_tiled_kernels,
+                            init_expert_ffn_f32_tiled_kernels, init_expert_ffn_fused_fp8_kernels, init_gemm_f32_tiled_kernels,
+                            init_gemm_bf16_dma_kernels, init_expert_gemm_g256_kernels, init_moe_router_kernels,
+                            init_relpos_attention_bf16_kernels, init_gemm_f32_splitk_kernels};
+  for (auto init : inits)
+    if (int rc = init()) return rc;
+  return 0;
+}
+
+// The binding of key k, built into bd (a fresh Bound).  Every step that can fail comes before the first one that touches the
+// engine (registering a new folded positional table), so a build that fails leaves the engine exactly as it was.
+static int build_binding(m3_engine* e, const BindKey& k, m3_engine::Bound& bd) {
+  M3_REQUIRE(k.feat && k.feat_len && k.logits && k.ws, "engine_prepare: null argument");
+  const int B = k.B, T = k.T;
   M3_REQUIRE(B > 0 && T >= 7, "engine_prepare: need B > 0 and T >= 7 frames (got B=%d T=%d)", B, T);
   const m3_engine_config& c = e->cfg;
   const int Tp = sub_len(T);
   M3_REQUIRE(Tp < e->pe_rows, "engine_prepare: T'=%d exceeds the positional table (%lld rows)", Tp,
              (long long)e->pe_rows);  // rel_positional_encoding_plugin.cpp:139-142
-  if (int rc = init_expert_ffn_kernels()) return rc;
-  if (int rc = init_expert_ffn_bf16_kernels()) return rc;
-  if (int rc = init_expert_ffn_w8_kernels()) return rc;
-  if (int rc = init_gemm_bf16_tiled_kernels()) return rc;
-  if (int rc = init_expert_ffn_f32_tiled_kernels()) return rc;
-  if (int rc = init_expert_ffn_fused_fp8_kernels()) return rc;
-  if (int rc = init_gemm_f32_tiled_kernels()) return rc;
-  if (int rc = init_gemm_bf16_dma_kernels()) return rc;
-  if (int rc = init_expert_gemm_g256_kernels()) return rc;
-  if (int rc = init_moe_router_kernels()) return rc;
-  if (int rc = init_relpos_attention_bf16_kernels()) return rc;
-  Plan pl = make_plan(c, workspace, B, T, e->ep_capacity);
-  M3_REQUIRE(workspace_bytes >= pl.bytes, "engine_prepare: workspace %zu bytes < required %zu", workspace_bytes, pl.bytes);
-  // ---- shape cache: park the current binding, revive a parked one with the same (shape, buffers) ----
-  if (e->cur.matches(B, T, feat, feat_len, logits, workspace, workspace_bytes, e->ep_capacity, sstate, s_hist, s_maxf, s_slots)) {
-    e->cur.last_use = ++e->use_clock;
-    return (int)e->cur.stages.size();
-  }
-  const int capacity = c.shape_cache > 0 ? c.shape_cache : (c.shape_cache < 0 ? 0 : 7);
-  if (!e->cur.stages.empty()) {
-    if (capacity > 0) {
-      if ((int)e->parked.size() >= capacity) {           // evict the least recently used binding
-        size_t lru = 0;
-        for (size_t i = 1; i < e->parked.size(); ++i)
-          if (e->parked[i].last_use < e->parked[lru].last_use) lru = i;
-        if (e->parked[lru].graph_exec) (void)hipGraphExecDestroy(e->parked[lru].graph_exec);
-        e->parked.erase(e->parked.begin() + lru);
-      }
-      e->parked.push_back(std::move(e->cur));
-    } else if (e->cur.graph_exec) {
-      (void)hipGraphExecDestroy(e->cur.graph_exec);
-    }
-    e->cur = m3_engine::Bound();
-  }
-  for (size_t i = 0; i < e->parked.size(); ++i)
-    if (e->parked[i].matches(B, T, feat, feat_len, logits, workspace, workspace_bytes, e->ep_capacity, sstate, s_hist, s_maxf, s_slots)) {
-      e->cur = std::move(e->parked[i]);
-      e->parked.erase(e->parked.begin() + i);
-      e->cur.last_use = ++e->use_clock;
-      return (int)e->cur.stages.size();
-    }
-  e->cur.last_use = ++e->use_clock;
-  e->cur.B = B; e->cur.T = T; e->cur.Tp = Tp; e->cur.S = B * Tp;
-  e->cur.feat = feat; e->cur.feat_len = feat_len; e->cur.logits = logits; e->cur.ws = workspace; e->cur.ws_bytes = workspace_bytes;
-  e->cur.ep_cap = e->ep_capacity;
-  e->cur.sstate = sstate; e->cur.s_hist = s_hist; e->cur.s_maxf = s_maxf; e->cur.s_slots = s_slots;
-  const bool streaming = sstate != nullptr;
-  e->cur.stages.clear(); e->cur.buffers.clear(); e->cur.n_kernels = 0; e->cur.graph_valid = false; e->cur.xn_skipped = false;
-  e->cur.splitk_ws = pl.splitk; e->cur.splitk_bytes = pl.splitk_bytes;
+  if (int rc = init_engine_kernels()) return rc;
+  const bool streaming = k.sstate != nullptr;
+  StageBuilder sb{*e, make_plan(c, k.ws, B, T, k.ep_cap), bd,
+                  streaming ? carve_stream_state(c, k.sstate, B, k.s_hist) : StreamState()};
+  Plan& pl = sb.pl;
+  M3_REQUIRE(k.ws_bytes >= pl.bytes, "engine_prepare: workspace %zu bytes < required %zu", k.ws_bytes, pl.bytes);
+  const int32_t* feat_len = k.feat_len; float* logits = k.logits;
+  bd.key = k; bd.Tp = Tp; bd.S = B * Tp;
+  sb.splitk_ws = pl.splitk; sb.splitk_bytes = pl.splitk_bytes;
   {
     // bf16 activation operands need every GEMM that reads or rewrites them on the LDS-tiled kernel: the narrowest ones
     // are the D x D projections (the expert-parallel driver's combine op writes the bf16 copy too: m3_moe_combine_bf16)
     GemmParams t;
     t.M = B * Tp; t.N = c.attention_dim; t.K = c.attention_dim; t.w_bf16 = 1;
-    e->cur.a16 = c.weight_dtype != M3_F32 && c.bf16_activations >= 0 && !c.debug_taps && c.embed_dim == c.attention_dim &&
-                 (c.embed_linear_units % 128) == 0 && (c.hidden_units % 128) == 0 && gemm_bf16w_uses_tiled(t);
+    bd.a16 = c.weight_dtype != M3_F32 && c.bf16_activations >= 0 && !c.debug_taps && c.embed_dim == c.attention_dim &&
+             (c.embed_linear_units % 128) == 0 && (c.hidden_units % 128) == 0 && gemm_bf16w_uses_tiled(t);
   }
   {
     GemmParams t;     // the narrowest block GEMM as the LDS-DMA kernel would see it
     t.M = B * Tp; t.N = c.attention_dim; t.K = c.attention_dim; t.lda = c.attention_dim; t.w_bf16 = 1; t.a_bf16 = 1;
-    e->cur.dma = e->cur.a16 && c.attention_dim == 128 * kXbStatParts && gemm_bf16w_uses_dma(t);
+    bd.dma = bd.a16 && c.attention_dim == 128 * kXbStatParts && gemm_bf16w_uses_dma(t);
   }
-  e->cur.packed = use_packed_rows(c, B);
+  bd.packed = use_packed_rows(c, B);
   if (streaming) {   // a chunk is a few rows per utterance: padded layout, fp32 activations (the 16-bit modes keep their bf16 weights)
-    e->cur.a16 = e->cur.dma = e->cur.packed = false;   // (the plan's packed-row buffers stay carved, unused)
+    bd.a16 = bd.dma = bd.packed = false;   // (the plan's packed-row buffers stay carved, unused)
   }
-  if (int rc = init_gemm_f32_splitk_kernels()) return rc;
-  const int S = e->cur.S, D = c.attention_dim, De = c.embed_dim;
+  const int S = bd.S, D = c.attention_dim, De = c.embed_dim;
 
   if (pl.ep_overflow != nullptr) {   // bounded expert-parallel wire: the overflow report of this forward starts at 0
     int32_t* ovf = pl.ep_overflow;
-    add_stage(e, "ep.reset", 0, [=](hipStream_t s) {
+    add_stage(sb, "ep.reset", 0, [=](hipStream_t s) {
       M3_CHECK_HIP(hipMemsetAsync(ovf, 0, sizeof(int32_t), s));
       return 0;
     });
-    e->cur.buffers["ep.overflow"] = Buf{ovf, sizeof(int32_t)};
+    bd.buffers["ep.overflow"] = Buf{ovf, sizeof(int32_t)};
   }
   // valid lengths after the two stride-2 convs (MaskConv2dSample x2, subsampling.py:119-137)
   {
@@ -1294,16 +1281,15 @@ static int prepare_impl(m3_engine* e, const float* feat, const int32_t* feat_len
     // the lengths while the embed branch, whose conv1 would write them, runs beside it) and a positional projection that is
     // not folded (its GEMM would sit in front of conv1 -- harmless, but the stage order of round 1 is kept for it).
     int32_t* lens = pl.lens;
-    e->cur.lens_in_conv1 = false;
-    if (e->cur.packed) {   // row plan of the packed layout: first row of every utterance, packed -> padded row map
+    if (bd.packed) {   // row plan of the packed layout: first row of every utterance, packed -> padded row map
       int32_t* row0 = pl.row0; int32_t* pad_of = pl.pad_of;
-      add_stage(e, "pack_plan", 1, [=](hipStream_t s) { return launch_pack_plan(lens, B, Tp, row0, pad_of, s, feat_len); },
+      add_stage(sb, "pack_plan", 1, [=](hipStream_t s) { return launch_pack_plan(lens, B, Tp, row0, pad_of, s, feat_len); },
                 stage_info("pack_plan_kernel", 1, 12.0 * B + 4.0 * B * Tp, 0.0, false));
     } else if (pl.fork || (!c.fold_pos_proj && !streaming)) {
-      add_stage(e, "lens", 1, [=](hipStream_t s) { return launch_subsample_lens(feat_len, B, lens, s); },
+      add_stage(sb, "lens", 1, [=](hipStream_t s) { return launch_subsample_lens(feat_len, B, lens, s); },
                 stage_info("subsample_lens_kernel", 1, 8.0 * B, 0.0, false));
     } else {
-      e->cur.lens_in_conv1 = true;
+      sb.lens_in_conv1 = true;
     }
   }
   // ---- p = linear_pos(pe[:T']) for all blocks at once (attention.py:345; input-independent, so with
@@ -1313,12 +1299,11 @@ static int prepare_impl(m3_engine* e, const float* feat, const int32_t* feat_len
     GemmParams pp;
     // (streaming: keys carry their ABSOLUTE position, rel_positional_encoding_kernel.cu:108-111 pe[offset : offset + T]: one
     //  table over the s_maxf positions a stream can reach, always folded)
-    const int Tpos = streaming ? s_maxf : Tp;
+    const int Tpos = streaming ? k.s_maxf : Tp;
     pp.A = e->pe; pp.lda = D; pp.W = e->pos_all; pp.Y = pl.pbuf; pp.ldy = nb * D; pp.M = Tpos; pp.N = nb * D; pp.K = D;
     if (c.fold_pos_proj || streaming) {
-      for (auto it = e->pfold_by_tp.begin(); it != e->pfold_by_tp.end();)      // tables no binding holds any more
-        it = it->second.expired() ? e->pfold_by_tp.erase(it) : std::next(it);
-      std::shared_ptr<float> pf = e->pfold_by_tp.count(Tpos) ? e->pfold_by_tp[Tpos].lock() : nullptr;
+      auto known = e->pfold_by_tp.find(Tpos);
+      std::shared_ptr<float> pf = known != e->pfold_by_tp.end() ? known->second.lock() : nullptr;
       if (!pf) {
         float* dev = nullptr;
         M3_CHECK_HIP(hipMalloc((void**)&dev, (size_t)Tpos * nb * D * sizeof(float)));
@@ -1327,31 +1312,34 @@ static int prepare_impl(m3_engine* e, const float* feat, const int32_t* feat_len
         pp.w_bf16 = c.weight_dtype != M3_F32;
         if (int rc = launch_gemm_f32(pp, nullptr)) return rc;
         M3_CHECK_HIP(hipStreamSynchronize(nullptr));
+        // (nothing below can fail: from here on the engine may change)
+        for (auto it = e->pfold_by_tp.begin(); it != e->pfold_by_tp.end();)      // tables no binding holds any more
+          it = it->second.expired() ? e->pfold_by_tp.erase(it) : std::next(it);
         e->pfold_by_tp[Tpos] = pf;
       }
-      e->cur.pfold = pf;
+      bd.pfold = pf;
       pl.pbuf = pf.get();
     } else {
-      add_gemm(e, "pos_all", pp);
+      add_gemm(sb, "pos_all", pp);
     }
   }
   // ---- embed encoder (conformer_embed_domain_acc.py:149-181) ----
   const Plan ple = embed_view(pl);
-  const int embed_start = (int)e->cur.stages.size();    // the embed chain starts here ...
-  e->cur.splitk_ws = ple.splitk;
-  build_subsample(e, "embed.subsample.", e->sub_e, De, ple, ple.x);
+  const int embed_start = (int)bd.stages.size();    // the embed chain starts here ...
+  sb.splitk_ws = ple.splitk;
+  build_subsample(sb, "embed.subsample.", e->sub_e, De, ple, ple.x);
   for (int i = 0; i < c.embed_blocks; ++i) {
     if (i + 1 == c.embed_blocks) {   // after_norm joins the last block's norm_final launch
-      e->cur.tail_ln_g = e->e_after.g; e->cur.tail_ln_b = e->e_after.b; e->cur.tail_ln_eps = 1e-12f; e->cur.tail_ln_out = pl.emb;
+      sb.tail_ln_g = e->e_after.g; sb.tail_ln_b = e->e_after.b; sb.tail_ln_eps = 1e-12f; sb.tail_ln_out = pl.emb;
     }
-    build_block(e, "embed.blocks." + std::to_string(i) + ".", e->eblocks[i], De, c.embed_linear_units, c.embed_heads,
+    build_block(sb, "embed.blocks." + std::to_string(i) + ".", e->eblocks[i], De, c.embed_linear_units, c.embed_heads,
                 c.cnn_module_kernel, c.embed_cnn_layer_norm, false, i, i, ple, c.embed_causal > 0);
   }
-  e->cur.splitk_ws = pl.splitk;
+  sb.splitk_ws = pl.splitk;
   if (c.embed_blocks == 0) {
     float* x = ple.x; float* emb = pl.emb;
     const float* g = e->e_after.g; const float* b = e->e_after.b;
-    add_stage(e, "embed.after_norm", 1, [=](hipStream_t s) { return launch_layernorm(x, g, b, 1e-12f, emb, S, De, s); },
+    add_stage(sb, "embed.after_norm", 1, [=](hipStream_t s) { return launch_layernorm(x, g, b, 1e-12f, emb, S, De, s); },
               stage_info("layernorm_kernel", 1, 8.0 * S * De, 8.0 * S * De));
   }
   // embed half of every layer's router product in one GEMM: emb does not change across the main blocks
@@ -1359,79 +1347,146 @@ static int prepare_impl(m3_engine* e, const float* feat, const int32_t* feat_len
     GemmParams g;
     g.A = pl.emb; g.lda = De; g.W = e->router_e_all; g.Y = pl.eall; g.ldy = c.num_blocks * c.num_experts;
     g.M = S; g.N = c.num_blocks * c.num_experts; g.K = De;
-    add_gemm(e, "router_e_all", g, true);
-    e->cur.stages.back().reads_embed = true;
+    add_gemm(sb, "router_e_all", g, true);
+    bd.stages.back().reads_embed = true;
   }
   // ---- main MoE encoder (conformer_fmoe_localComm_catEmbed_domain_acc_hier.py:198-234) ----
-  const int main_start = (int)e->cur.stages.size();     // ... and the main encoder here
-  build_subsample(e, "subsample.", e->sub_m, D, pl, pl.x);
+  const int main_start = (int)bd.stages.size();     // ... and the main encoder here
+  build_subsample(sb, "subsample.", e->sub_m, D, pl, pl.x);
   for (int i = 0; i < c.num_blocks; ++i)
-    build_block(e, "blocks." + std::to_string(i) + ".", e->mblocks[i], D, c.hidden_units, c.attention_heads,
+    build_block(sb, "blocks." + std::to_string(i) + ".", e->mblocks[i], D, c.hidden_units, c.attention_heads,
                 c.cnn_module_kernel, c.cnn_layer_norm, true, i, c.embed_blocks + i, pl, c.causal > 0);
   {
     GemmParams g;
     g.A = pl.x; g.lda = D; g.W = e->out_linear.w; g.bias = e->out_linear.b; g.Y = logits; g.ldy = c.output_dim;
     g.M = S; g.N = c.output_dim; g.K = D;
     g.ln_wsum = e->out_linear.wsum; g.ln_eps = 1e-12f;       // after_norm is folded into out_linear
-    if (e->cur.a16) { g.A = (const float*)pl.xb; g.a_bf16 = 1; }
-    if (e->cur.dma) { g.ln_stats = pl.xstats; g.ln_stat_parts = kXbStatParts; }
+    if (bd.a16) { g.A = (const float*)pl.xb; g.a_bf16 = 1; }
+    if (bd.dma) { g.ln_stats = pl.xstats; g.ln_stat_parts = kXbStatParts; }
     float* lout = logits;
-    if (e->cur.packed) {   // packed rows -> packed logits; the (B, T', V) output is filled from them at the end
+    if (bd.packed) {   // packed rows -> packed logits; the (B, T', V) output is filled from them at the end
       lout = pl.lpk;
       g.Y = lout;
       g.m_dev = pl.row0 + B;
     }
-    add_gemm(e, "logits", g);
+    add_gemm(sb, "logits", g);
     const float* ob = e->output_bias;
     const int V = c.output_dim;
     if (c.log_softmax_out) {
-      add_stage(e, "log_softmax", 1, [=](hipStream_t s) { return launch_log_softmax_bias(lout, ob, lout, (size_t)S, V, s); },
+      add_stage(sb, "log_softmax", 1, [=](hipStream_t s) { return launch_log_softmax_bias(lout, ob, lout, (size_t)S, V, s); },
                 stage_info("log_softmax_bias_kernel", 1, 8.0 * S * V, 4.0 * S * V));
     }   // without log-softmax a prior is folded into out_linear's bias when the plan is packed (plan.py)
-    if (e->cur.packed) {
+    if (bd.packed) {
       const int32_t* row0 = pl.row0;
-      add_stage(e, "unpack", 1, [=](hipStream_t s) { return launch_unpack_rows(lout, row0, B, Tp, V, logits, s); },
+      add_stage(sb, "unpack", 1, [=](hipStream_t s) { return launch_unpack_rows(lout, row0, B, Tp, V, logits, s); },
                 stage_info("unpack_rows_kernel", 1, 8.0 * S * V, 0.0, false));
     }
   }
   // the main encoder first needs the embedding at blocks.0's router: the forked capture joins its two branches there, horizontal
   // fusion interleaves the two chains up to there
-  const int join = embed_join(e->cur.stages, main_start);
+  const int join = embed_join(bd.stages, main_start);
   if (pl.fork && join >= 0 && c.num_blocks >= 1) {
-    e->cur.fork_first = embed_start; e->cur.fork_mid = main_start; e->cur.join_at = join;
+    bd.fork_first = embed_start; bd.fork_mid = main_start; bd.join_at = join;
   }
-  if (pl.hfuse && !streaming && join > 0) fuse_independent_pairs(e, embed_start, main_start, join);
+  if (pl.hfuse && !streaming && join > 0) fuse_independent_pairs(sb, embed_start, main_start, join);
   if (streaming) {   // the chunk counter moves on the device: the same captured graph serves every chunk of the stream
-    const StreamState st = carve_stream_state(c, sstate, B, s_hist);
+    const StreamState& st = sb.st;
     int32_t* step = st.step;
-    if (s_slots) {   // one counter per utterance slot; a slot moves only if it was live in this chunk
+    if (k.s_slots) {   // one counter per utterance slot; a slot moves only if it was live in this chunk
       int32_t *pos = st.slot_pos, *status = st.slot_status, *frames = st.slot_frames;
-      const int32_t* lens = pl.lens; const int max_chunks = s_maxf / Tp;
-      add_stage(e, "stream.advance", 1, [=](hipStream_t s) { return launch_advance_slots(pos, status, frames, lens, B, Tp, max_chunks, s); },
+      const int32_t* lens = pl.lens; const int max_chunks = k.s_maxf / Tp;
+      add_stage(sb, "stream.advance", 1, [=](hipStream_t s) { return launch_advance_slots(pos, status, frames, lens, B, Tp, max_chunks, s); },
                 stage_info("advance_slots_kernel", 1, 20.0 * B, 0.0, false));
     } else
-    add_stage(e, "stream.advance", 1, [=](hipStream_t s) { return launch_advance_counter(step, 1, s); },
+    add_stage(sb, "stream.advance", 1, [=](hipStream_t s) { return launch_advance_counter(step, 1, s); },
               stage_info("advance_counter_kernel", 1, 8.0, 0.0, false));
   }
-  e->cur.buffers["x"] = Buf{pl.x, (size_t)S * D * 4};
-  if (!e->cur.xn_skipped) e->cur.buffers["xn"] = Buf{pl.xn, (size_t)S * D * 4};
+  bd.buffers["x"] = Buf{pl.x, (size_t)S * D * 4};
+  if (!bd.xn_skipped) bd.buffers["xn"] = Buf{pl.xn, (size_t)S * D * 4};
   if (pl.xq != nullptr) {
-    e->cur.buffers["xq"] = Buf{pl.xq, (size_t)S * D};
-    e->cur.buffers["xq_scale"] = Buf{pl.xq_scale, (size_t)S * 4};
+    bd.buffers["xq"] = Buf{pl.xq, (size_t)S * D};
+    bd.buffers["xq_scale"] = Buf{pl.xq_scale, (size_t)S * 4};
   }
-  e->cur.buffers["embed"] = Buf{pl.emb, (size_t)S * De * 4};
-  if (e->cur.a16) e->cur.buffers["xb"] = Buf{pl.xb, (size_t)S * D * 2};
-  e->cur.buffers["lens"] = Buf{pl.lens, (size_t)B * 4};
-  if (e->cur.packed) e->cur.buffers["row0"] = Buf{pl.row0, (size_t)(B + 1) * 4};
-  if (pl.ep_rows) e->cur.buffers["ep.gate_recv"] = Buf{pl.ep_gate_recv, (size_t)pl.ep_rows * 4};
-  e->cur.buffers["router_logits"] = Buf{pl.rl, (size_t)S * c.num_experts * (c.ep_world_size > 0 ? c.ep_world_size : 1) * 4};
+  bd.buffers["embed"] = Buf{pl.emb, (size_t)S * De * 4};
+  if (bd.a16) bd.buffers["xb"] = Buf{pl.xb, (size_t)S * D * 2};
+  bd.buffers["lens"] = Buf{pl.lens, (size_t)B * 4};
+  if (bd.packed) bd.buffers["row0"] = Buf{pl.row0, (size_t)(B + 1) * 4};
+  if (pl.ep_rows) bd.buffers["ep.gate_recv"] = Buf{pl.ep_gate_recv, (size_t)pl.ep_rows * 4};
+  bd.buffers["router_logits"] = Buf{pl.rl, (size_t)S * c.num_experts * (c.ep_world_size > 0 ? c.ep_world_size : 1) * 4};
 
-  return (int)e->cur.stages.size();
+  return 0;
+}
+
+// ---- shape cache: the current binding plus up to cfg.shape_cache parked ones, least recently used evicted first ----
+static int find_parked(const m3_engine* e, const BindKey& k) {
+  for (size_t i = 0; i < e->parked.size(); ++i)
+    if (e->parked[i].matches(k)) return (int)i;
+  return -1;
+}
+
+static int shape_cache_capacity(const m3_engine* e) { return e->cfg.shape_cache > 0 ? e->cfg.shape_cache : (e->cfg.shape_cache < 0 ? 0 : 7); }
+
+// the parked binding that parking one more evicts: the least recently used one of a full cache (-1: there is room)
+static int park_victim(const m3_engine* e) {
+  if (e->parked.empty() || (int)e->parked.size() < shape_cache_capacity(e)) return -1;
+  size_t lru = 0;
+  for (size_t i = 1; i < e->parked.size(); ++i)
+    if (e->parked[i].last_use < e->parked[lru].last_use) lru = i;
+  return (int)lru;
+}
+
+// the current binding moves to the parked ones (cache capacity 0: it is dropped) and leaves e->cur empty
+static void park_current(m3_engine* e) {
+  if (e->cur.stages.empty()) return;
+  if (shape_cache_capacity(e) > 0) {
+    const int victim = park_victim(e);
+    if (victim >= 0) {
+      if (e->parked[victim].graph_exec) (void)hipGraphExecDestroy(e->parked[victim].graph_exec);
+      e->parked.erase(e->parked.begin() + victim);
+    }
+    e->parked.push_back(std::move(e->cur));
+  } else if (e->cur.graph_exec) {
+    (void)hipGraphExecDestroy(e->cur.graph_exec);
+  }
+  e->cur = m3_engine::Bound();
+}
+
+// Makes the binding of key k the current one: it is the current one already, or a parked one is revived, or it is built.
+// Build, then commit: a new binding is built aside and the engine changes only once it is complete.  (The current binding is
+// parked BEFORE the parked ones are searched, so a wanted binding that this parking evicts is built anew.)
+static int bind(m3_engine* e, const BindKey& k) {
+  if (!e->cur.matches(k)) {
+    int hit = find_parked(e, k);
+    if (hit >= 0 && !e->cur.stages.empty() && hit == park_victim(e)) hit = -1;
+    m3_engine::Bound fresh;
+    if (hit < 0)
+      if (int rc = build_binding(e, k, fresh)) return rc;
+    park_current(e);
+    if (hit >= 0) {
+      hit = find_parked(e, k);
+      fresh = std::move(e->parked[hit]);
+      e->parked.erase(e->parked.begin() + hit);
+    }
+    e->cur = std::move(fresh);
+  }
+  e->cur.last_use = ++e->use_clock;
+  return 0;
+}
+
+// the key of a whole-utterance binding (m3_engine_prepare / m3_engine_forward)
+static BindKey forward_key(const m3_engine* e, const float* feat, const int32_t* feat_len, int B, int T, float* logits,
+                           void* workspace, size_t workspace_bytes) {
+  BindKey k;
+  k.B = B; k.T = T; k.feat = feat; k.feat_len = feat_len; k.logits = logits; k.ws = workspace; k.ws_bytes = workspace_bytes;
+  k.ep_cap = e->ep_capacity;
+  return k;
 }
 
 int m3_engine_prepare(m3_engine* e, const float* feat, const int32_t* feat_len, int B, int T, float* logits,
                       void* workspace, size_t workspace_bytes) {
-  return prepare_impl(e, feat, feat_len, B, T, logits, workspace, workspace_bytes, nullptr, 0, 0);
+  M3_REQUIRE(e != nullptr, "engine_prepare: null argument");
+  if (int rc = bind(e, forward_key(e, feat, feat_len, B, T, logits, workspace, workspace_bytes))) return rc;
+  return (int)e->cur.stages.size();
 }
 
 int m3_engine_set_ep_capacity(m3_engine* engine, int rows_per_chunk) {
@@ -1472,63 +1527,72 @@ int m3_engine_buffer(const m3_engine* engine, const char* name, void** ptr, size
   return 0;
 }
 
+// Captures the current binding's stage list on `stream` and instantiates the graph.  A binding built for fork_embed runs the
+// embed encoder as a side branch.  `who` names the entry point in the messages.
+static int capture_graph(m3_engine* e, hipStream_t stream, const char* who) {
+  m3_engine::Bound& b = e->cur;
+  M3_REQUIRE(stream != nullptr, "%s: graph capture needs a non-default stream", who);
+  if (b.graph_exec) {
+    (void)hipGraphExecDestroy(b.graph_exec);
+    b.graph_exec = nullptr;
+  }
+  hipGraph_t graph = nullptr;
+  const m3_stream stream_ = (m3_stream)stream;
+  const int n_st = (int)b.stages.size();
+  const bool fork = b.fork_first >= 0 && b.fork_mid > b.fork_first && b.join_at > b.fork_mid;
+  if (fork && e->side == nullptr) {
+    M3_CHECK_HIP(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
+    M3_CHECK_HIP(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
+    M3_CHECK_HIP(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
+  }
+  M3_CHECK_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+  int rc = 0;
+  if (!fork) {
+    rc = m3_engine_run(e, 0, n_st, stream_);
+  } else {
+    // two branches between "lens" and blocks.0's router: the embed encoder on the side stream (it joins the capture through
+    // the fork event), the main subsampler + block 0 up to its router on the capture stream
+    hipError_t he = hipSuccess;
+    rc = m3_engine_run(e, 0, b.fork_first, stream_);
+    if (!rc && (he = hipEventRecord(e->ev_fork, stream)) != hipSuccess) rc = -1;
+    if (!rc && (he = hipStreamWaitEvent(e->side, e->ev_fork, 0)) != hipSuccess) rc = -1;
+    if (!rc) rc = m3_engine_run(e, b.fork_first, b.fork_mid, (m3_stream)e->side);
+    if (!rc) rc = m3_engine_run(e, b.fork_mid, b.join_at, stream_);
+    if (!rc && (he = hipEventRecord(e->ev_join, e->side)) != hipSuccess) rc = -1;
+    if (!rc && (he = hipStreamWaitEvent(stream, e->ev_join, 0)) != hipSuccess) rc = -1;
+    if (!rc) rc = m3_engine_run(e, b.join_at, n_st, stream_);
+    if (he != hipSuccess) set_error("%s: forked capture failed: %s", who, hipGetErrorString(he));
+  }
+  hipError_t ce = hipStreamEndCapture(stream, &graph);
+  if (rc) {
+    if (graph) (void)hipGraphDestroy(graph);
+    return rc;
+  }
+  M3_CHECK_HIP(ce);
+  M3_CHECK_HIP(hipGraphInstantiate(&b.graph_exec, graph, nullptr, nullptr, 0));
+  M3_CHECK_HIP(hipGraphDestroy(graph));
+  b.graph_valid = true;
+  ++e->n_captures;
+  return 0;
+}
+
+// the current binding once: stage by stage, or as one replay of its graph (captured on first use)
+static int run_current(m3_engine* e, int use_graph, m3_stream stream_, const char* who) {
+  if (!use_graph) return m3_engine_run(e, 0, (int)e->cur.stages.size(), stream_);
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!e->cur.graph_valid)
+    if (int rc = capture_graph(e, stream, who)) return rc;
+  M3_CHECK_HIP(hipGraphLaunch(e->cur.graph_exec, stream));
+  return 0;
+}
+
 int m3_engine_forward(m3_engine* e, const float* feat, const int32_t* feat_len, int B, int T, float* logits,
                       void* workspace, size_t workspace_bytes, int use_graph, m3_stream stream_) {
   M3_REQUIRE(e != nullptr, "engine_forward: null engine");
-  hipStream_t stream = (hipStream_t)stream_;
-  if (!e->cur.matches(B, T, feat, feat_len, logits, workspace, workspace_bytes, e->ep_capacity)) {
-    int rc = m3_engine_prepare(e, feat, feat_len, B, T, logits, workspace, workspace_bytes);
-    if (rc < 0) return rc;
-  }
-  e->cur.last_use = ++e->use_clock;
+  if (int rc = bind(e, forward_key(e, feat, feat_len, B, T, logits, workspace, workspace_bytes))) return rc;
   M3_REQUIRE(e->cfg.ep_world_size <= 1, "engine_forward: an expert-parallel engine (ep_world_size = %d) is run stage-wise, with the "
              "all-to-all between its moe_ep.* stages (m3asr/ep.py)", (int)e->cfg.ep_world_size);
-  if (!use_graph) return m3_engine_run(e, 0, (int)e->cur.stages.size(), stream_);
-  if (!e->cur.graph_valid) {
-    M3_REQUIRE(stream != nullptr, "engine_forward: graph capture needs a non-default stream");
-    if (e->cur.graph_exec) {
-      (void)hipGraphExecDestroy(e->cur.graph_exec);
-      e->cur.graph_exec = nullptr;
-    }
-    hipGraph_t graph = nullptr;
-    const int n_st = (int)e->cur.stages.size();
-    const bool fork = e->cur.fork_first >= 0 && e->cur.fork_mid > e->cur.fork_first && e->cur.join_at > e->cur.fork_mid;
-    if (fork && e->side == nullptr) {
-      M3_CHECK_HIP(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
-      M3_CHECK_HIP(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-      M3_CHECK_HIP(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
-    }
-    M3_CHECK_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    int rc = 0;
-    if (!fork) {
-      rc = m3_engine_run(e, 0, n_st, stream_);
-    } else {
-      // two branches between "lens" and blocks.0's router: the embed encoder on the side stream (it joins the capture through
-      // the fork event), the main subsampler + block 0 up to its router on the capture stream
-      hipError_t he = hipSuccess;
-      rc = m3_engine_run(e, 0, e->cur.fork_first, stream_);
-      if (!rc && (he = hipEventRecord(e->ev_fork, stream)) != hipSuccess) rc = -1;
-      if (!rc && (he = hipStreamWaitEvent(e->side, e->ev_fork, 0)) != hipSuccess) rc = -1;
-      if (!rc) rc = m3_engine_run(e, e->cur.fork_first, e->cur.fork_mid, (m3_stream)e->side);
-      if (!rc) rc = m3_engine_run(e, e->cur.fork_mid, e->cur.join_at, stream_);
-      if (!rc && (he = hipEventRecord(e->ev_join, e->side)) != hipSuccess) rc = -1;
-      if (!rc && (he = hipStreamWaitEvent(stream, e->ev_join, 0)) != hipSuccess) rc = -1;
-      if (!rc) rc = m3_engine_run(e, e->cur.join_at, n_st, stream_);
-      if (he != hipSuccess) set_error("engine_forward: forked capture failed: %s", hipGetErrorString(he));
-    }
-    hipError_t ce = hipStreamEndCapture(stream, &graph);
-    if (rc) {
-      if (graph) (void)hipGraphDestroy(graph);
-      return rc;
-    }
-    M3_CHECK_HIP(ce);
-    M3_CHECK_HIP(hipGraphInstantiate(&e->cur.graph_exec, graph, nullptr, nullptr, 0));
-    M3_CHECK_HIP(hipGraphDestroy(graph));
-    e->cur.graph_valid = true;
-    ++e->n_captures;
-  }
-  M3_CHECK_HIP(hipGraphLaunch(e->cur.graph_exec, stream));
-  return 0;
+  return run_current(e, use_graph, stream_, "engine_forward");
 }
 
 
@@ -1554,6 +1618,15 @@ static int stream_check(const m3_engine* e, const m3_stream_desc* d) {
   return 0;
 }
 
+// stream_check, then "the caller's state is there and large enough": the state carved into *st.  `who` names the entry point
+static int stream_state(const m3_engine* e, const m3_stream_desc* d, const void* state, size_t state_bytes, const char* who,
+                        StreamState* st) {
+  if (int rc = stream_check(e, d)) return rc;
+  *st = carve_stream_state(e->cfg, const_cast<void*>(state), d->B, d->history_frames);
+  M3_REQUIRE(state != nullptr && state_bytes >= st->bytes, "%s: state %zu bytes < required %zu", who, state_bytes, st->bytes);
+  return 0;
+}
+
 int m3_engine_chunk_input_frames(const m3_engine* engine) {
   // c output frames need input frames [4 j0, 4 (j0 + c - 1) + 6]: 4 c + 3 of them, advancing by 4 c per chunk (7-frame context of
   // the two stride-2 3x3 convs, subsampling.py:103-145)
@@ -1566,10 +1639,9 @@ size_t m3_engine_stream_state_size(const m3_engine* engine, const m3_stream_desc
 }
 
 int m3_engine_stream_reset(m3_engine* e, const m3_stream_desc* desc, void* state, size_t state_bytes, m3_stream stream_) {
-  if (int rc = stream_check(e, desc)) return rc;
+  StreamState st;
+  if (int rc = stream_state(e, desc, state, state_bytes, "engine_stream_reset", &st)) return rc;
   const m3_engine_config& c = e->cfg;
-  const StreamState st = carve_stream_state(c, state, desc->B, desc->history_frames);
-  M3_REQUIRE(state != nullptr && state_bytes >= st.bytes, "engine_stream_reset: state %zu bytes < required %zu", state_bytes, st.bytes);
   hipStream_t stream = (hipStream_t)stream_;
   M3_CHECK_HIP(hipMemsetAsync(st.step, 0, 64 * sizeof(int32_t), stream));
   M3_CHECK_HIP(hipMemsetAsync(st.slot_pos, 0, (size_t)3 * desc->B * sizeof(int32_t), stream));
@@ -1585,43 +1657,18 @@ int m3_engine_stream_reset(m3_engine* e, const m3_stream_desc* desc, void* state
 // bind (or revive) the chunk binding of this (state, buffers, mode) and run it: eagerly, or as one hipGraph replay
 static int run_chunk(m3_engine* e, const m3_stream_desc* desc, void* state, const float* feat_chunk, const int32_t* chunk_feat_len,
                      float* logits, void* workspace, size_t workspace_bytes, bool slots, int use_graph, m3_stream stream_) {
-  const int T = 4 * e->cfg.static_chunk_size + 3, B = desc->B;
-  hipStream_t stream = (hipStream_t)stream_;
-  if (!e->cur.matches(B, T, feat_chunk, chunk_feat_len, logits, workspace, workspace_bytes, e->ep_capacity, state, desc->history_frames,
-                      desc->max_frames, slots)) {
-    int rc = prepare_impl(e, feat_chunk, chunk_feat_len, B, T, logits, workspace, workspace_bytes, state, desc->history_frames,
-                          desc->max_frames, slots);
-    if (rc < 0) return rc;
-  }
-  e->cur.last_use = ++e->use_clock;
-  if (!use_graph) return m3_engine_run(e, 0, (int)e->cur.stages.size(), stream_);
-  if (!e->cur.graph_valid) {
-    M3_REQUIRE(stream != nullptr, "engine_forward_chunk: graph capture needs a non-default stream");
-    if (e->cur.graph_exec) { (void)hipGraphExecDestroy(e->cur.graph_exec); e->cur.graph_exec = nullptr; }
-    hipGraph_t graph = nullptr;
-    M3_CHECK_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-    const int rc = m3_engine_run(e, 0, (int)e->cur.stages.size(), stream_);
-    hipError_t ce = hipStreamEndCapture(stream, &graph);
-    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-    M3_CHECK_HIP(ce);
-    M3_CHECK_HIP(hipGraphInstantiate(&e->cur.graph_exec, graph, nullptr, nullptr, 0));
-    M3_CHECK_HIP(hipGraphDestroy(graph));
-    e->cur.graph_valid = true;
-    ++e->n_captures;
-  }
-  M3_CHECK_HIP(hipGraphLaunch(e->cur.graph_exec, stream));
-  return 0;
+  BindKey k = forward_key(e, feat_chunk, chunk_feat_len, desc->B, 4 * e->cfg.static_chunk_size + 3, logits, workspace, workspace_bytes);
+  k.sstate = state; k.s_hist = desc->history_frames; k.s_maxf = desc->max_frames; k.s_slots = slots;
+  if (int rc = bind(e, k)) return rc;
+  return run_current(e, use_graph, stream_, "engine_forward_chunk");
 }
 
 int m3_engine_forward_chunk(m3_engine* e, const m3_stream_desc* desc, void* state, size_t state_bytes, const float* feat_chunk,
                             const int32_t* chunk_feat_len, float* logits, void* workspace, size_t workspace_bytes, int chunk_index,
                             int use_graph, m3_stream stream_) {
-  if (int rc = stream_check(e, desc)) return rc;
-  const m3_engine_config& c = e->cfg;
-  const int C = c.static_chunk_size, B = desc->B;
-  const size_t need = carve_stream_state(c, nullptr, B, desc->history_frames).bytes;
-  M3_REQUIRE(state != nullptr && state_bytes >= need, "engine_forward_chunk: state %zu bytes < required %zu", state_bytes, need);
-  M3_REQUIRE(chunk_index >= 0 && (long)(chunk_index + 1) * C <= desc->max_frames,
+  StreamState st;
+  if (int rc = stream_state(e, desc, state, state_bytes, "engine_forward_chunk", &st)) return rc;
+  M3_REQUIRE(chunk_index >= 0 && (long)(chunk_index + 1) * e->cfg.static_chunk_size <= desc->max_frames,
              "engine_forward_chunk: chunk %d ends past max_frames=%d (the stream is longer than the state was sized for)", chunk_index, desc->max_frames);
   return run_chunk(e, desc, state, feat_chunk, chunk_feat_len, logits, workspace, workspace_bytes, false, use_graph, stream_);
 }
@@ -1633,18 +1680,16 @@ int m3_engine_forward_chunk(m3_engine* e, const m3_stream_desc* desc, void* stat
 int m3_engine_forward_chunk_slots(m3_engine* e, const m3_stream_desc* desc, void* state, size_t state_bytes, const float* feat_chunk,
                                   const int32_t* chunk_feat_len, float* logits, void* workspace, size_t workspace_bytes,
                                   int use_graph, m3_stream stream_) {
-  if (int rc = stream_check(e, desc)) return rc;
-  const size_t need = carve_stream_state(e->cfg, nullptr, desc->B, desc->history_frames).bytes;
-  M3_REQUIRE(state != nullptr && state_bytes >= need, "engine_forward_chunk_slots: state %zu bytes < required %zu", state_bytes, need);
+  StreamState st;
+  if (int rc = stream_state(e, desc, state, state_bytes, "engine_forward_chunk_slots", &st)) return rc;
   return run_chunk(e, desc, state, feat_chunk, chunk_feat_len, logits, workspace, workspace_bytes, true, use_graph, stream_);
 }
 
 int m3_engine_stream_reset_slots(m3_engine* e, const m3_stream_desc* desc, void* state, size_t state_bytes, const int32_t* slots,
                                  int n, m3_stream stream_) {
-  if (int rc = stream_check(e, desc)) return rc;
+  StreamState st;
+  if (int rc = stream_state(e, desc, state, state_bytes, "engine_stream_reset_slots", &st)) return rc;
   const m3_engine_config& c = e->cfg;
-  const StreamState st = carve_stream_state(c, state, desc->B, desc->history_frames);
-  M3_REQUIRE(state != nullptr && state_bytes >= st.bytes, "engine_stream_reset_slots: state %zu bytes < required %zu", state_bytes, st.bytes);
   M3_REQUIRE(n >= 0 && (n == 0 || slots != nullptr), "engine_stream_reset_slots: bad slot list (n=%d)", n);
   const int nb = c.embed_blocks + c.num_blocks;
   M3_REQUIRE(nb <= kMaxStreamBlocks, "engine_stream_reset_slots: %d blocks > %d", nb, kMaxStreamBlocks);
@@ -1661,10 +1706,9 @@ int m3_engine_stream_reset_slots(m3_engine* e, const m3_stream_desc* desc, void*
 
 int m3_engine_stream_positions(m3_engine* e, const m3_stream_desc* desc, const void* state, size_t state_bytes, int32_t* frames,
                                m3_stream stream_) {
-  if (int rc = stream_check(e, desc)) return rc;
-  const StreamState st = carve_stream_state(e->cfg, const_cast<void*>(state), desc->B, desc->history_frames);
-  M3_REQUIRE(state != nullptr && state_bytes >= st.bytes && frames != nullptr, "engine_stream_positions: null pointer or state %zu bytes < required %zu",
-             state_bytes, st.bytes);
+  StreamState st;
+  if (int rc = stream_state(e, desc, state, state_bytes, "engine_stream_positions", &st)) return rc;
+  M3_REQUIRE(frames != nullptr, "engine_stream_positions: null pointer");
   return launch_slot_positions(st.slot_status, st.slot_frames, desc->B, frames, (hipStream_t)stream_);
 }
 
