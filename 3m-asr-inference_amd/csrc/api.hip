@@ -42,8 +42,7 @@ MoeWorkspace carve_moe_workspace(void* base, int S, int E, int D, int F) {
 int moe_expert_ffn_dt(const float* x, const int32_t* gate_idx, const float* w1, const float* b1, const float* w2,
                       const float* b2, int S, int E, int D, int F, const float* gate_value, const float* resid,
                       float alpha, const float* ln_gamma, const float* ln_beta, float ln_eps, float* y, void* ws,
-                      size_t ws_bytes, hipStream_t stream, int wmode /* 0 fp32, 1 bf16, 2 fp8 weights, 3 fp8 weights + activations */,
-                      const float* s1 = nullptr, const float* s2 = nullptr, float h_scale = 0.f, const void* xq = nullptr,
+                      size_t ws_bytes, hipStream_t stream, ExpertWeights weights, const float* s1 = nullptr, const float* s2 = nullptr, float h_scale = 0.f, const void* xq = nullptr,
                       const float* xq_scale = nullptr) {
   M3_REQUIRE(S >= 0 && E > 0 && D > 0 && F > 0, "fmoe_expert: bad sizes S=%d E=%d D=%d F=%d", S, E, D, F);
   if (S == 0) return 0;
@@ -52,14 +51,13 @@ int moe_expert_ffn_dt(const float* x, const int32_t* gate_idx, const float* w1, 
              w.bytes);
   int rc = launch_moe_index(gate_idx, S, E, w.mapping, w.acc, w.pos, stream);
   if (rc) return rc;
-  if (wmode == 3) rc = launch_expert_ffn_w8a8(x, D, w.pos, w.acc, S, E, D, F, w1, s1, b1, w2, s2, 0, h_scale, w.slab, stream, xq, xq_scale);
-  else if (wmode == 2) rc = launch_expert_ffn_w8(x, D, w.pos, w.acc, S, E, D, F, w1, s1, b1, w2, s2, 0, w.slab, stream);
-  else if (wmode) rc = launch_expert_ffn_bf16w(x, D, w.pos, w.acc, S, E, D, F, w1, b1, w2, 0, w.slab, stream);
-  else rc = launch_expert_ffn_f32(x, D, w.pos, w.acc, S, E, D, F, w1, b1, w2, 0, w.slab, nullptr, nullptr, 0.f, stream);
+  const ExpertFfnPlan plan = plan_expert_ffn(weights, S, E, D, F);
+  ExpertFfnArgs a{};
+  a.x = x; a.ldx = D; a.pos = w.pos; a.acc_hist = w.acc; a.w1 = w1; a.w2 = w2; a.s1 = s1; a.s2 = s2; a.b1 = b1;
+  a.h_scale = h_scale; a.slab = w.slab; a.xq = xq; a.xq_scale = xq_scale;
+  rc = launch_expert_ffn(plan, S, E, D, F, a, stream);
   if (rc) return rc;
-  const float* rows = wmode ? expert_ffn_w16_rows(wmode, w.slab, S, E, D, F) : expert_ffn_f32_rows(w.slab, S, E, D, F);
-  const int n_slices = wmode ? expert_ffn_w16_slices(wmode, S, E, D, F) : expert_ffn_f32_slices(S, E, D, F);
-  return launch_moe_combine(rows, n_slices, w.mapping, gate_idx, gate_value, b2, resid, alpha, ln_gamma, ln_beta, ln_eps,
+  return launch_moe_combine(plan.rows(w.slab), plan.slices, w.mapping, gate_idx, gate_value, b2, resid, alpha, ln_gamma, ln_beta, ln_eps,
                             y, S, D, stream);
 }
 
@@ -68,7 +66,7 @@ int moe_expert_ffn(const float* x, const int32_t* gate_idx, const float* w1, con
                    float alpha, const float* ln_gamma, const float* ln_beta, float ln_eps, float* y, void* ws,
                    size_t ws_bytes, hipStream_t stream) {
   return moe_expert_ffn_dt(x, gate_idx, w1, b1, w2, b2, S, E, D, F, gate_value, resid, alpha, ln_gamma, ln_beta, ln_eps,
-                           y, ws, ws_bytes, stream, 0);
+                           y, ws, ws_bytes, stream, ExpertWeights::F32);
 }
 
 }  // namespace m3
@@ -111,7 +109,7 @@ int m3_moe_expert_ffn_bf16(const float* x, const int32_t* gate_idx, const void* 
                            float* y, void* workspace, size_t workspace_bytes, m3_stream stream) {
   return moe_expert_ffn_dt(x, gate_idx, (const float*)w1, b1, (const float*)w2, b2, S, num_expert, idim, hidden_units,
                            gate_value, resid, alpha, ln_gamma, ln_beta, ln_eps, y, workspace, workspace_bytes,
-                           (hipStream_t)stream, 1);
+                           (hipStream_t)stream, ExpertWeights::BF16);
 }
 int m3_moe_expert_ffn_fp8(const float* x, const int32_t* gate_idx, const void* w1, const float* w1_scale, const float* b1,
                           const void* w2, const float* w2_scale, const float* b2, int S, int num_expert, int idim,
@@ -121,7 +119,7 @@ int m3_moe_expert_ffn_fp8(const float* x, const int32_t* gate_idx, const void* w
   M3_REQUIRE(w1_scale && w2_scale, "fmoe_expert fp8: null scale");
   return moe_expert_ffn_dt(x, gate_idx, (const float*)w1, b1, (const float*)w2, b2, S, num_expert, idim, hidden_units,
                            gate_value, resid, alpha, ln_gamma, ln_beta, ln_eps, y, workspace, workspace_bytes,
-                           (hipStream_t)stream, 2, w1_scale, w2_scale);
+                           (hipStream_t)stream, ExpertWeights::FP8, w1_scale, w2_scale);
 }
 int m3_moe_expert_ffn_fp8a8(const float* x, const int32_t* gate_idx, const void* w1, const float* w1_scale, const float* b1,
                             const void* w2, const float* w2_scale, const float* b2, float h_scale, int S, int num_expert, int idim,
@@ -132,7 +130,7 @@ int m3_moe_expert_ffn_fp8a8(const float* x, const int32_t* gate_idx, const void*
   M3_REQUIRE(h_scale > 0.f, "fmoe_expert fp8a8: h_scale must be positive");
   return moe_expert_ffn_dt(x, gate_idx, (const float*)w1, b1, (const float*)w2, b2, S, num_expert, idim, hidden_units,
                            gate_value, resid, alpha, ln_gamma, ln_beta, ln_eps, y, workspace, workspace_bytes,
-                           (hipStream_t)stream, 3, w1_scale, w2_scale, h_scale);
+                           (hipStream_t)stream, ExpertWeights::FP8A8, w1_scale, w2_scale, h_scale);
 }
 int m3_moe_expert_ffn_fp8a8_xq(const float* x, const void* xq, const float* xq_scale, const int32_t* gate_idx, const void* w1,
                                const float* w1_scale, const float* b1, const void* w2, const float* w2_scale, const float* b2,
@@ -142,11 +140,11 @@ int m3_moe_expert_ffn_fp8a8_xq(const float* x, const void* xq, const float* xq_s
   M3_REQUIRE(w1_scale && w2_scale, "fmoe_expert fp8a8_xq: null scale");
   M3_REQUIRE(h_scale > 0.f, "fmoe_expert fp8a8_xq: h_scale must be positive");
   M3_REQUIRE(xq && xq_scale, "fmoe_expert fp8a8_xq: null quantised rows / scales");
-  M3_REQUIRE(expert_ffn_fused_fp8_applies(S, num_expert, idim, hidden_units) || x != nullptr,
+  M3_REQUIRE(m3_moe_expert_ffn_fp8a8_active(S, num_expert, idim, hidden_units) || x != nullptr,
              "fmoe_expert fp8a8_xq: this shape takes the weight-only form, which needs the fp32 rows (x)");
   return moe_expert_ffn_dt(x, gate_idx, (const float*)w1, b1, (const float*)w2, b2, S, num_expert, idim, hidden_units,
                            gate_value, resid, alpha, ln_gamma, ln_beta, ln_eps, y, workspace, workspace_bytes,
-                           (hipStream_t)stream, 3, w1_scale, w2_scale, h_scale, xq, xq_scale);
+                           (hipStream_t)stream, ExpertWeights::FP8A8, w1_scale, w2_scale, h_scale, xq, xq_scale);
 }
 int m3_quantize_rows_e4m3(const float* x, int ldx, int S, int idim, void* xq, float* scale, m3_stream stream) {
   M3_REQUIRE(S <= 1 || ldx >= idim, "quantize_rows_e4m3: ldx=%d is shorter than a row of %d", ldx, idim);
@@ -154,7 +152,20 @@ int m3_quantize_rows_e4m3(const float* x, int ldx, int S, int idim, void* xq, fl
   return launch_quantize_rows_e4m3(x, ldx, S, idim, xq, scale, (hipStream_t)stream);
 }
 int m3_moe_expert_ffn_fp8a8_active(int S, int num_expert, int idim, int hidden_units) {
-  return expert_ffn_fused_fp8_applies(S, num_expert, idim, hidden_units) ? 1 : 0;
+  return plan_expert_ffn(ExpertWeights::FP8A8, S, num_expert, idim, hidden_units).kernel == ExpertKernel::FusedFp8 ? 1 : 0;
+}
+const char* m3_moe_expert_ffn_kernel(int weight_dtype, int fp8_activations, int S, int num_expert, int idim, int hidden_units,
+                                     int32_t* launches, int32_t* slices) {
+  ExpertWeights w;
+  if (weight_dtype == M3_F32 && !fp8_activations) w = ExpertWeights::F32;
+  else if (weight_dtype == M3_BF16 && !fp8_activations) w = ExpertWeights::BF16;
+  else if (weight_dtype == M3_FP8) w = fp8_activations ? ExpertWeights::FP8A8 : ExpertWeights::FP8;
+  else return nullptr;
+  const ExpertFfnPlan plan = plan_expert_ffn(w, S, num_expert, idim, hidden_units);
+  if (plan.launches == 0) return nullptr;
+  if (launches) *launches = plan.launches;
+  if (slices) *slices = plan.slices;
+  return plan.label;
 }
 int m3_moe_combine(const float* rows, const int32_t* mapping, const float* gate_value, const float* resid, float alpha,
                    const float* ln_gamma, const float* ln_beta, float ln_eps, float* out, int S, int idim,

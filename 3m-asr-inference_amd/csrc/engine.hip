@@ -525,6 +525,13 @@ struct MoeRoute {
   bool norm_in_expert() const { return router == RouterForm::Fused || router == RouterForm::Split; }
 };
 
+// what plan_expert_ffn is asked for: fp8 arithmetic where the layer has a calibrated H scale
+static ExpertWeights expert_weights(const m3_engine_config& c, const BlockW& w) {
+  if (c.weight_dtype == M3_F32) return ExpertWeights::F32;
+  if (c.weight_dtype == M3_BF16) return ExpertWeights::BF16;
+  return w.h_scale > 0.f ? ExpertWeights::FP8A8 : ExpertWeights::FP8;
+}
+
 MoeRoute choose_moe_route(const m3_engine_config& c, int S, const BlockW& w, const Plan& pl) {
   const Switches& sw = switches();
   const int world = c.ep_world_size > 0 ? c.ep_world_size : 1;
@@ -532,7 +539,7 @@ MoeRoute choose_moe_route(const m3_engine_config& c, int S, const BlockW& w, con
   const bool one_wg_experts = Etot == 8 || Etot == 16 || Etot == 32 || Etot == 64;   // what the single-work-group kernels take
   // S <= 256 rows, all experts local, fp32: the expert launch can route for itself
   const bool self_routing = sw.self_route && c.weight_dtype == M3_F32 && expert_ffn_f32_self_routing(S, Etot) &&
-                            !expert_ffn_f32_tiled(S, E, D, F);
+                            plan_expert_ffn(ExpertWeights::F32, S, E, D, F).kernel == ExpertKernel::SlabF32;
   MoeRoute r;
   r.ep = world > 1 || c.ep_stages > 0;
   if (c.fuse_route == 2 && world == 1 && S < 1024 && one_wg_experts) {
@@ -548,7 +555,7 @@ MoeRoute choose_moe_route(const m3_engine_config& c, int S, const BlockW& w, con
     else if (S <= sw.gate_index_max_rows && one_wg_experts) r.gate = GateForm::GateIndex;
     else r.gate = r.router_top1 ? GateForm::RouterTail : GateForm::Top1Index;
   }
-  const bool fused8 = c.weight_dtype == M3_FP8 && w.h_scale > 0.f && !r.ep && expert_ffn_w8a8_fused(S, E, D, F);
+  const bool fused8 = !r.ep && plan_expert_ffn(expert_weights(c, w), S, E, D, F).kernel == ExpertKernel::FusedFp8;
   r.use_xq = r.router == RouterForm::Kernel && sw.router_xq && fused8 && pl.xq != nullptr;
   r.skip_xn = r.use_xq && sw.router_skip_xn && !c.debug_taps;
   r.fs_dev = sw.fused8_adapt && fused8 && pl.moe_fs != nullptr && !c.debug_taps;
@@ -797,46 +804,15 @@ static void add_moe_local_index(StageBuilder& sb, const MoeLayer& m) {
   }, stage_info("moe_index_kernel", 1, 12.0 * m.S + 4.0 * (m.E + 1), 0.0));
 }
 
-// The form the grouped expert FFN takes on R rows, and where the combine finds its result
-struct ExpertForm {
-  int wmode;            // 0 fp32, 1 bf16, 2 fp8 weights, 3 fp8 arithmetic (the wmode of expert_ffn_w16_*)
-  int launches;
-  const char* kernel;
-  float* rows;          // the expert outputs: sorted rows or partial-output slabs ...
-  int slices;           // ... this many of them per row
-};
-// norm_in_expert: the kernel applies norm_ff while it gathers rows (fused / split route): the fp32 slab form, never tiled
-static ExpertForm expert_form(const m3_engine_config& c, float h_scale, float* slab, int R, int E, int D, int F, bool norm_in_expert) {
-  ExpertForm f;
-  if (c.weight_dtype == M3_F32) {   // long batches: two grouped GEMMs whose result is ONE slab of sorted rows
-    const bool tiled = !norm_in_expert && expert_ffn_f32_tiled(R, E, D, F);
-    f.wmode = 0;
-    f.launches = tiled ? 2 : 1;
-    f.kernel = tiled ? "expert_gemm_f32_tiled_kernel" : "expert_ffn_f32_kernel";
-    f.rows = tiled ? expert_ffn_f32_rows(slab, R, E, D, F) : slab;
-    f.slices = tiled ? 1 : F / kExpertSlice;
-  } else {
-    f.wmode = c.weight_dtype == M3_FP8 ? (h_scale > 0.f ? 3 : 2) : 1;
-    f.launches = expert_ffn_w16_launches(f.wmode, R, E, D, F);
-    f.kernel = expert_ffn_w16_kernel(f.wmode, R, E, D, F);
-    f.rows = expert_ffn_w16_rows(f.wmode, slab, R, E, D, F);
-    f.slices = expert_ffn_w16_slices(f.wmode, R, E, D, F);
-  }
-  return f;
+// the plan's arguments on the R rows of x that (mw.pos, mw.acc) sort by expert; the result goes into mw.slab
+static ExpertFfnArgs expert_args(const BlockW& w, const float* x, const MoeWorkspace& mw, int D) {
+  ExpertFfnArgs a{};
+  a.x = x; a.ldx = D; a.pos = mw.pos; a.acc_hist = mw.acc; a.w1 = w.ew1; a.w2 = w.ew2; a.s1 = w.es1; a.s2 = w.es2; a.b1 = w.eb1;
+  a.w2_sliced = 1; a.h_scale = w.h_scale; a.slab = mw.slab;
+  return a;
 }
 
-// the grouped expert FFN in form f on the R rows of x that (mw.pos, mw.acc) sort by expert; its result into mw.slab
-static int launch_expert(const ExpertForm& f, const BlockW& w, const float* x, const MoeWorkspace& mw, int R, int E, int D, int F,
-                         hipStream_t s, const float* ln_g = nullptr, const float* ln_b = nullptr, float ln_eps = 0.f,
-                         const void* xq = nullptr, const float* xq_scale = nullptr, int32_t* fs_dev = nullptr) {
-  if (f.wmode >= 2)
-    return launch_expert_ffn_w8a8(x, D, mw.pos, mw.acc, R, E, D, F, w.ew1, w.es1, w.eb1, w.ew2, w.es2, 1, w.h_scale, mw.slab, s,
-                                  xq, xq_scale, fs_dev);
-  if (f.wmode == 1) return launch_expert_ffn_bf16w(x, D, mw.pos, mw.acc, R, E, D, F, w.ew1, w.eb1, w.ew2, 1, mw.slab, s);
-  return launch_expert_ffn_f32(x, D, mw.pos, mw.acc, R, E, D, F, w.ew1, w.eb1, w.ew2, 1, mw.slab, ln_g, ln_b, ln_eps, s);
-}
-
-static void add_moe_local_expert(StageBuilder& sb, const MoeLayer& m, const MoeRoute& r, const ExpertForm& f, const Plan& pl) {
+static void add_moe_local_expert(StageBuilder& sb, const MoeLayer& m, const MoeRoute& r, const ExpertFfnPlan& f, const Plan& pl) {
   const bool norm = r.norm_in_expert();
   const float* xin = norm ? m.x : m.xn;
   const bool self_route = r.gate == GateForm::InExpert;
@@ -850,12 +826,14 @@ static void add_moe_local_expert(StageBuilder& sb, const MoeLayer& m, const MoeR
     if (self_route)
       return launch_expert_route_ffn_f32(xin, m.D, m.rl, m.live_len, m.live_rpb, m.S, m.E, m.D, m.F, w.ew1, w.eb1, w.ew2, 1, w.eb2,
                                          m.mw.slab, m.gidx, m.gval, m.mw.mapping, m.mw.acc, m.mw.pos, s, ln_g, ln_b, ln_eps);
-    return launch_expert(f, w, xin, m.mw, m.S, m.E, m.D, m.F, s, ln_g, ln_b, ln_eps, xq, xqs, fs);
-  }, stage_info(f.kernel, 1, -1.0, 4.0 * m.D * m.F * m.S));
+    ExpertFfnArgs a = expert_args(w, xin, m.mw, m.D);
+    a.ln_gamma = ln_g; a.ln_beta = ln_b; a.ln_eps = ln_eps; a.xq = xq; a.xq_scale = xqs; a.fs_dev = fs;
+    return launch_expert_ffn(f, m.S, m.E, m.D, m.F, a, s);
+  }, stage_info(f.label, 1, -1.0, 4.0 * m.D * m.F * m.S));
 }
 
 // local_gather + b2 + gate + residual + LayerNorm(norm_final) over the expert outputs
-static void add_moe_local_combine(StageBuilder& sb, const MoeLayer& m, const MoeRoute& r, const ExpertForm& f, const Plan& pl) {
+static void add_moe_local_combine(StageBuilder& sb, const MoeLayer& m, const MoeRoute& r, const ExpertFfnPlan& f, const Plan& pl) {
   // (self-routing expert launch: slabs hold ORIGINAL rows with b2 already in slice 0 -> no mapping, no b2 here)
   const bool self_route = r.gate == GateForm::InExpert;
   const int32_t* cmap = self_route ? nullptr : m.mw.mapping;
@@ -864,7 +842,7 @@ static void add_moe_local_combine(StageBuilder& sb, const MoeLayer& m, const Moe
   const double S = m.S, D = m.D;
   add_stage(sb, m.pfx + "moe_local.combine", 1, [=](hipStream_t s) {
     const BlockW& w = *m.w;
-    return launch_moe_combine(f.rows, fs ? 4 : f.slices, cmap, m.gidx, m.gv, cb2, m.x, 0.5f, w.n_final.g, w.n_final.b, m.eps, m.x,
+    return launch_moe_combine(f.rows(m.mw.slab), fs ? kExpertFusedFp8MaxSplit : f.slices, cmap, m.gidx, m.gv, cb2, m.x, 0.5f, w.n_final.g, w.n_final.b, m.eps, m.x,
                               m.S, m.D, s, m.xb_out, m.xstats_out, fs);
   }, stage_info("moe_combine_kernel", 1, S * D * 4 * (f.slices + 2) + (m.xb_out ? 2.0 * S * D : 0.0), S * D * (f.slices + 10)));
 }
@@ -899,19 +877,21 @@ static void add_moe_ep(StageBuilder& sb, const MoeLayer& m, const MoeRoute& r, c
   exchange("moe_ep.exchange1");
   // this rank's experts on everything it received (its own stable index puts the rows in FastMoE's receive order: by local
   // expert, then source rank, then wire order); results return to wire_a at the wire rows they came in on
-  const ExpertForm f = expert_form(sb.eng.cfg, m.w->h_scale, rw.slab, R, E, D, F, false);
+  const ExpertFfnPlan f = plan_expert_ffn(expert_weights(sb.eng.cfg, *m.w), R, E, D, F, EXPERT_SCATTER_ROWS);
   // bf16 experts in the tiled two-GEMM form: GEMM-2's epilogue adds b2 and puts every row straight back on its wire row
   // (no un-permuting combine launch; wire rows nobody sent keep stale bytes -- no rank ever reads them back)
-  const bool scatter2 = f.wmode == 1 && expert_ffn_bf16_tiled(R, E, D, F);
+  const bool scatter2 = f.kernel == ExpertKernel::TiledBf16;
   const BlockW* wp = m.w;
   add_stage(sb, m.pfx + "moe_ep.expert", (scatter2 ? 2 : 3) + f.launches, [=](hipStream_t s) {
     const BlockW& w = *wp;
     if (int rc = launch_ep_recv_gate(wire_b, world, E, cap, D * 4, gate_recv, s)) return rc;
     if (int rc = launch_moe_index(gate_recv, R, E, rw.mapping, rw.acc, rw.pos, s)) return rc;
-    if (scatter2) return launch_expert_ffn_bf16w(wire_b, D, rw.pos, rw.acc, R, E, D, F, w.ew1, w.eb1, w.ew2, 1, rw.slab, s, w.eb2, wire_a);
-    if (int rc = launch_expert(f, w, wire_b, rw, R, E, D, F, s)) return rc;
-    return launch_moe_combine(f.rows, f.slices, rw.mapping, gate_recv, nullptr, w.eb2, nullptr, 1.f, nullptr, nullptr, 0.f, wire_a, R, D, s);
-  }, stage_info(f.kernel, 1, -1.0, 4.0 * D * F * S));
+    ExpertFfnArgs a = expert_args(w, wire_b, rw, D);
+    if (scatter2) { a.b2 = w.eb2; a.y_scatter = wire_a; }
+    if (int rc = launch_expert_ffn(f, R, E, D, F, a, s)) return rc;
+    if (scatter2) return 0;
+    return launch_moe_combine(f.rows(rw.slab), f.slices, rw.mapping, gate_recv, nullptr, w.eb2, nullptr, 1.f, nullptr, nullptr, 0.f, wire_a, R, D, s);
+  }, stage_info(f.label, 1, -1.0, 4.0 * D * F * S));
   exchange("moe_ep.exchange2");
   // local_gather + gate + residual + LayerNorm: token s reads its result at the wire row it was sent from
   add_stage(sb, m.pfx + "moe_ep.combine", 1, [=](hipStream_t s) {
@@ -1097,7 +1077,7 @@ static void build_block(StageBuilder& sb, const std::string& pfx, const BlockW& 
       if (r.gate == GateForm::GateIndex) add_moe_gate_index(sb, m, m.mw.mapping, m.mw.acc, m.mw.pos);
       if (r.gate == GateForm::Top1Index) add_moe_top1(sb, m);
       if (r.gate == GateForm::Top1Index || r.gate == GateForm::RouterTail) add_moe_local_index(sb, m);
-      const ExpertForm f = expert_form(c, w.h_scale, m.mw.slab, S, m.E, D, F, r.norm_in_expert());
+      const ExpertFfnPlan f = plan_expert_ffn(expert_weights(c, w), S, m.E, D, F, r.norm_in_expert() ? EXPERT_NORM_IN_KERNEL : 0);
       add_moe_local_expert(sb, m, r, f, pl);
       add_moe_local_combine(sb, m, r, f, pl);
     }

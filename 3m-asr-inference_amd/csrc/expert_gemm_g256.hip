@@ -374,17 +374,16 @@ int init_expert_gemm_g256_kernels() {
   return 0;
 }
 
-// rows per expert from which the 256-row tiles pay (M3_G256_MIN_ROWS_PER_EXPERT overrides, read once)
-bool expert_ffn_bf16_g256(int S, int E, int D, int F) {
-  static const int min_rpe = [] { const char* e = getenv("M3_G256_MIN_ROWS_PER_EXPERT"); return e ? atoi(e) : 512; }();
-  return E <= 64 && S / E >= min_rpe && (D % 256) == 0 && (F % 256) == 0 && (size_t)S * F * 2 < ((size_t)1 << 32);
+// what the kernel can run (from how many rows per expert the 256-row tiles pay is plan_expert_ffn's business)
+bool expert_gemm_g256_takes(int S, int E, int D, int F) {
+  return E > 0 && E <= 64 && (D % 256) == 0 && (F % 256) == 0 && (size_t)S * F * 2 < ((size_t)1 << 32);
 }
 
 // xb: bf16 copy of the MoE input rows [S][D] (row stride ldxb elements), gathered through pos by the LDS-DMA fills.
 int launch_expert_ffn_bf16_g256(const void* xb, int ldxb, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D, int F,
                                 const void* w1, const float* b1, const void* w2, int w2_sliced, void* hbuf, float* ybuf,
                                 hipStream_t stream) {
-  M3_REQUIRE(expert_ffn_bf16_g256(S, E, D, F), "expert_ffn g256: needs E <= 64 and D, F multiples of 256 (S=%d E=%d D=%d F=%d)", S, E, D, F);
+  M3_REQUIRE(expert_gemm_g256_takes(S, E, D, F), "expert_ffn g256: needs E <= 64 and D, F multiples of 256 (S=%d E=%d D=%d F=%d)", S, E, D, F);
   M3_REQUIRE((ldxb & 7) == 0, "expert_ffn g256: row stride of the bf16 rows must be a multiple of 8");
   if (int rc = init_expert_gemm_g256_kernels()) return rc;
   const int m_slots = cdiv(cdiv(S, GBM) + E, 8 * kGRun) * 8 * kGRun;   // >= sum_e ceil(cnt_e / 256), padded to 8 XCDs x kGRun

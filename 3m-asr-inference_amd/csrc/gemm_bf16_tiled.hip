@@ -514,76 +514,44 @@ int launch_gemm_bf16w_tiled(const GemmParams& pin, hipStream_t stream) {
 // ---- grouped expert FFN on the tiled core (long batches) ----
 // H = SiLU(X[pos] W1[e]^T + b1[e]) (bf16, sorted rows), Y = H W2[e]^T (fp32, sorted rows; b2, gate, residual and
 // LayerNorm are applied by moe_combine_kernel with one "slab").  hbuf: S*F bf16, ybuf: S*D fp32.
-int launch_expert_ffn_bf16w_tiled(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D,
-                                  int F, const void* w1, const float* b1, const void* w2, int w2_sliced, void* hbuf,
-                                  float* ybuf, hipStream_t stream, const float* b2, float* y_scatter) {
+// w_fp8: fp8 expert weights + per-row scales s1 / s2 (W8A16, see moe_expert_fp8.hip), else bf16 weights.
+int launch_expert_tiled_w16(bool w_fp8, const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D,
+                            int F, const void* w1, const float* s1, const float* b1, const void* w2, const float* s2,
+                            int w2_sliced, void* hbuf, float* ybuf, hipStream_t stream, const float* b2, float* y_scatter) {
   M3_REQUIRE((D & 127) == 0 && (F & 127) == 0, "expert_ffn tiled: idim=%d / hidden=%d must be multiples of 128", D, F);
-  if (y_scatter == nullptr && expert_ffn_bf16_g256(S, E, D, F)) {
-    // saturating row counts: 256 x 256 x 64 LDS-DMA tiles (expert_gemm_g256.hip).  Its A operand is bf16 in memory: the rows are
-    // converted once (behind ybuf in the slab region: S * D * 2 bytes of its F / 64 * S * D * 4) and gathered by the fills
-    void* xb = (char*)ybuf + align_up((size_t)S * D * 4, 256);
-    if (int rc = launch_rows_to_bf16(x, ldx, S, D, xb, stream)) return rc;
-    return launch_expert_ffn_bf16_g256(xb, D, pos, acc_hist, S, E, D, F, w1, b1, w2, w2_sliced, hbuf, ybuf, stream);
-  }
+  M3_REQUIRE(S > 0 && E > 0 && (ldx & 3) == 0, "expert_ffn tiled: empty problem or ldx not a multiple of 4 (S=%d E=%d ldx=%d)", S, E, ldx);
+  M3_REQUIRE(y_scatter == nullptr || !w_fp8, "expert_ffn tiled: the scattering epilogue exists with bf16 weights only");
   if (int rc = init_gemm_bf16_tiled_kernels()) return rc;
   // rows per expert ~ S/E: small tiles (4x the workgroups, half the k-steps) until an expert fills 128-row tiles
   const bool big = S / E >= 192;
   const int bm = big ? 128 : 64, bn = big ? 128 : 64;
   const int m_slots = cdiv(cdiv(S, bm) + E, 8 * kGrpRun) * 8 * kGrpRun;   // >= sum_e ceil(cnt_e / bm), padded to 8 XCDs x kGrpRun
   GemmParams g1;
-  g1.A = x; g1.lda = ldx; g1.W = (const float*)w1; g1.bias = b1; g1.Y = (float*)hbuf; g1.ldy = F;
+  g1.A = x; g1.lda = ldx; g1.W = (const float*)w1; g1.w_scale = w_fp8 ? s1 : nullptr; g1.bias = b1; g1.Y = (float*)hbuf; g1.ldy = F;
   g1.M = S; g1.N = F; g1.K = D; g1.act = ACT_SILU;
   g1.grp_acc = acc_hist; g1.grp_E = E; g1.grp_pos = pos;
   g1.n_tiles = cdiv(F, bn); g1.m_tiles = m_slots;
   GemmParams g2;
-  g2.A = (const float*)hbuf; g2.lda = F; g2.W = (const float*)w2; g2.Y = ybuf; g2.ldy = D;
+  g2.A = (const float*)hbuf; g2.lda = F; g2.W = (const float*)w2; g2.w_scale = w_fp8 ? s2 : nullptr; g2.Y = ybuf; g2.ldy = D;
   g2.M = S; g2.N = D; g2.K = F; g2.w_sliced = w2_sliced;
   g2.grp_acc = acc_hist; g2.grp_E = E;
   g2.n_tiles = cdiv(D, bn); g2.m_tiles = m_slots;
   if (y_scatter != nullptr) {   // the expert-parallel receive side: + b2, and every sorted row straight back to the wire row it came from
     g2.Y = y_scatter; g2.y_rows = pos; g2.bias = b2;
   }
-#define M3_GRP_LAUNCH(BM_, BN_, BK_)                                                                                 \
-  do {                                                                                                               \
-    hipLaunchKernelGGL((gemm_bf16w_tiled_kernel<BM_, BN_, BK_, false, false, false, 1>), dim3(m_slots * g1.n_tiles), \
-                       dim3(256), tiled_lds_bytes(BM_, BN_, BK_), stream, g1);                                       \
-    hipLaunchKernelGGL((gemm_bf16w_tiled_kernel<BM_, BN_, BK_, false, false, false, 2>), dim3(m_slots * g2.n_tiles), \
-                       dim3(256), tiled_lds_bytes(BM_, BN_, BK_), stream, g2);                                       \
+#define M3_GRP_LAUNCH(BM_, BN_, BK_, W8_)                                                                                 \
+  do {                                                                                                                    \
+    hipLaunchKernelGGL((gemm_bf16w_tiled_kernel<BM_, BN_, BK_, false, false, false, 1, W8_>), dim3(m_slots * g1.n_tiles), \
+                       dim3(256), tiled_lds_bytes(BM_, BN_, BK_), stream, g1);                                            \
+    hipLaunchKernelGGL((gemm_bf16w_tiled_kernel<BM_, BN_, BK_, false, false, false, 2, W8_>), dim3(m_slots * g2.n_tiles), \
+                       dim3(256), tiled_lds_bytes(BM_, BN_, BK_), stream, g2);                                            \
   } while (0)
-  if (big) M3_GRP_LAUNCH(128, 128, 64); else M3_GRP_LAUNCH(64, 64, 128);
+  if (w_fp8) {
+    if (big) M3_GRP_LAUNCH(128, 128, 64, true); else M3_GRP_LAUNCH(64, 64, 128, true);
+  } else {
+    if (big) M3_GRP_LAUNCH(128, 128, 64, false); else M3_GRP_LAUNCH(64, 64, 128, false);
+  }
 #undef M3_GRP_LAUNCH
-  M3_LAUNCH_CHECK();
-  return 0;
-}
-
-// the same with fp8 expert weights + per-row scales (W8A16, see moe_expert_fp8.hip)
-int launch_expert_ffn_w8_tiled(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D,
-                               int F, const void* w1, const float* s1, const float* b1, const void* w2, const float* s2,
-                               int w2_sliced, void* hbuf, float* ybuf, hipStream_t stream) {
-  M3_REQUIRE((D & 127) == 0 && (F & 127) == 0, "expert_ffn tiled: idim=%d / hidden=%d must be multiples of 128", D, F);
-  if (int rc = init_gemm_bf16_tiled_kernels()) return rc;
-  const bool big = S / E >= 192;
-  const int bm = big ? 128 : 64, bn = big ? 128 : 64;
-  const int m_slots = cdiv(cdiv(S, bm) + E, 8 * kGrpRun) * 8 * kGrpRun;
-  GemmParams g1;
-  g1.A = x; g1.lda = ldx; g1.W = (const float*)w1; g1.w_scale = s1; g1.bias = b1; g1.Y = (float*)hbuf; g1.ldy = F;
-  g1.M = S; g1.N = F; g1.K = D; g1.act = ACT_SILU;
-  g1.grp_acc = acc_hist; g1.grp_E = E; g1.grp_pos = pos;
-  g1.n_tiles = cdiv(F, bn); g1.m_tiles = m_slots;
-  GemmParams g2;
-  g2.A = (const float*)hbuf; g2.lda = F; g2.W = (const float*)w2; g2.w_scale = s2; g2.Y = ybuf; g2.ldy = D;
-  g2.M = S; g2.N = D; g2.K = F; g2.w_sliced = w2_sliced;
-  g2.grp_acc = acc_hist; g2.grp_E = E;
-  g2.n_tiles = cdiv(D, bn); g2.m_tiles = m_slots;
-#define M3_GRP8_LAUNCH(BM_, BN_, BK_)                                                                                      \
-  do {                                                                                                                     \
-    hipLaunchKernelGGL((gemm_bf16w_tiled_kernel<BM_, BN_, BK_, false, false, false, 1, true>), dim3(m_slots * g1.n_tiles), \
-                       dim3(256), tiled_lds_bytes(BM_, BN_, BK_), stream, g1);                                             \
-    hipLaunchKernelGGL((gemm_bf16w_tiled_kernel<BM_, BN_, BK_, false, false, false, 2, true>), dim3(m_slots * g2.n_tiles), \
-                       dim3(256), tiled_lds_bytes(BM_, BN_, BK_), stream, g2);                                             \
-  } while (0)
-  if (big) M3_GRP8_LAUNCH(128, 128, 64); else M3_GRP8_LAUNCH(64, 64, 128);
-#undef M3_GRP8_LAUNCH
   M3_LAUNCH_CHECK();
   return 0;
 }

@@ -114,76 +114,92 @@ int launch_ep_recv_gate(const void* wire, int world, int e_loc, int capacity, in
 #endif
 constexpr int kExpertSliceW16 = 64;            // the bf16 / e4m3 slab kernels are laid out for 64-wide slices
 constexpr int kExpertSlice = M3_EXPERT_SLICE;  // hidden units per workgroup (16 per wave); m3asr/plan.py EXPERT_SLICE must match
-size_t expert_ffn_slab_bytes(int S, int D, int F);
+size_t expert_ffn_slab_bytes(int S, int D, int F);   // the slab region: F / kExpertSlice partial-result slabs of [S][D] fp32
+// The operator runs in eight forms.  plan_expert_ffn (moe_expert_plan.hip) is the ONE place that says which of them runs for a
+// weight dtype and shape, in how many launches, and where in the slab region its sections are; launch_expert_ffn runs a plan,
+// and the combine step, the launch accounting and the observability entries read the same plan.  First match wins:
+//   FusedFp8   FP8A8, D = 512, F % 128 == 0, F <= 4096, E <= 1024, S >= 4096 (M3_EXPERT_FUSED_FP8_MIN_ROWS), S >= 64 E,
+//              and an F split exists (expert_ffn_fused_fp8_fsplit)          1 launch,   fsplit slabs of sorted rows at offset 0
+//   G256Bf16   BF16, a TiledBf16 shape with E <= 64, S / E >= 512 (M3_G256_MIN_ROWS_PER_EXPERT), D, F % 256 == 0,
+//              not EXPERT_SCATTER_ROWS                                      3 launches, H | sorted rows | bf16 row copy
+//   Tiled*     S >= 1024 (M3_EXPERT_TILED_MIN_ROWS), D, F % 64 == 0 (fp32) or % 128 == 0 (bf16, fp8; FP8A8 where the fused
+//              form does not apply), not EXPERT_NORM_IN_KERNEL              2 launches, H | sorted rows (one slab)
+//   Slab*      everything else                                              1 launch,   F / 64 partial-result slabs at offset 0
+// A form is taken only if all its sections fit into expert_ffn_slab_bytes.  The thresholds are read once per process.
+enum class ExpertWeights { F32, BF16, FP8, FP8A8 };   // FP8A8: fp8 weights + fp8 activations where FusedFp8 applies, else the weight-only forms
+enum class ExpertKernel { SlabF32, TiledF32, SlabBf16, TiledBf16, G256Bf16, SlabW8, TiledW8, FusedFp8 };
+struct ExpertFfnPlan {
+  ExpertWeights weights; ExpertKernel kernel;
+  const char* label;      // the kernel's name as rocprofv3 shows it
+  int launches, slices;   // kernel launches (0: dimensions no form takes, the launcher says which); partial-result slabs the combine sums
+  int fsplit;             // FusedFp8 only
+  size_t h_off, rows_off, xb_off;   // byte offsets inside the slab region (0 where unused): H, the result rows / slabs, the bf16 row copy
+  float* rows(float* slab) const { return (float*)((char*)slab + rows_off); }   // what moe_combine reads
+};
+enum { EXPERT_NORM_IN_KERNEL = 1,    // norm_ff applied while gathering rows: fp32 slab form only
+       EXPERT_SCATTER_ROWS = 2 };    // GEMM-2 writes b2 + rows to y_scatter[pos[i]]: bf16 tiled form only, never g256
+ExpertFfnPlan plan_expert_ffn(ExpertWeights w, int S, int E, int D, int F, unsigned flags = 0);
+// x [S][ldx] fp32 rows, sorted by expert through (pos, acc_hist); w1 [E][F][D], w2 [E][D][F] or slice-major (w2_sliced) in the
+// plan's weight dtype; s1 [E][F] / s2 [E][D]: fp8 per-row scales.  ln_*: SlabF32 under EXPERT_NORM_IN_KERNEL.  h_scale, xq /
+// xq_scale (rows already quantised by the router kernel), fs_dev (the kernel may split F finer than the plan and leaves the
+// slab count there): FusedFp8.  b2 / y_scatter: TiledBf16 under EXPERT_SCATTER_ROWS (the un-permute of the expert-parallel
+// receive side, folded into GEMM-2's epilogue).
+struct ExpertFfnArgs { const float* x; int ldx; const int32_t *pos, *acc_hist; const void *w1, *w2; const float *s1, *s2, *b1, *b2;
+                       int w2_sliced; float h_scale; float* slab; const float *ln_gamma, *ln_beta; float ln_eps;
+                       const void* xq; const float* xq_scale; int32_t* fs_dev; float* y_scatter; };
+int launch_expert_ffn(const ExpertFfnPlan& plan, int S, int E, int D, int F, const ExpertFfnArgs& a, hipStream_t stream);
+// The per-form launchers below launch exactly one form each (their own argument checks and tile sizes, no decision about form).
 int init_expert_ffn_kernels();
-int launch_expert_ffn_f32(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E,
-                          int D, int F, const float* w1, const float* b1, const float* w2, int w2_sliced, float* slab,
-                          const float* ln_gamma, const float* ln_beta, float ln_eps, hipStream_t stream);
-// long batches (S >= 1024): two grouped LDS-tiled fp32 GEMMs (moe_expert_tiled_f32.hip); launch_expert_ffn_f32 switches
-// to it by itself; these tell the combine step where / in how many slabs the result rows are
-bool expert_ffn_f32_tiled(int S, int E, int D, int F);
-float* expert_ffn_f32_rows(float* slab, int S, int E, int D, int F);
-int expert_ffn_f32_slices(int S, int E, int D, int F);
+int launch_expert_ffn_f32_slab(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E,
+                               int D, int F, const float* w1, const float* b1, const float* w2, int w2_sliced, float* slab,
+                               const float* ln_gamma, const float* ln_beta, float ln_eps, hipStream_t stream);
+// long batches: two grouped LDS-tiled fp32 GEMMs (moe_expert_tiled_f32.hip); hbuf S*F fp32, ybuf S*D fp32
 int init_expert_ffn_f32_tiled_kernels();
-int launch_expert_ffn_f32_tiled(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E,
-                                int D, int F, const float* w1, const float* b1, const float* w2, int w2_sliced,
-                                float* hbuf, float* ybuf, hipStream_t stream);
+int launch_expert_tiled_f32(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E,
+                            int D, int F, const float* w1, const float* b1, const float* w2, int w2_sliced,
+                            float* hbuf, float* ybuf, hipStream_t stream);
 // bf16 weights (w1 [E][F][D], w2 as above), fp32 rows in / fp32 slab out (moe_expert_bf16.hip)
 int init_expert_ffn_bf16_kernels();
-int launch_expert_ffn_bf16w(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E,
-                            int D, int F, const void* w1, const float* b1, const void* w2, int w2_sliced, float* slab,
-                            hipStream_t stream, const float* b2 = nullptr, float* y_scatter = nullptr);   // y_scatter: tiled form only (expert_ffn_bf16_tiled)
+int launch_expert_ffn_bf16w_slab(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E,
+                                 int D, int F, const void* w1, const float* b1, const void* w2, int w2_sliced, float* slab,
+                                 hipStream_t stream);
 // fp8 (e4m3) expert weights + per-row scales, dequantised to bf16 at the MFMA input (moe_expert_fp8.hip); same result layout as bf16
 int init_expert_ffn_w8_kernels();
-int launch_expert_ffn_w8(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D, int F,
-                         const void* w1, const float* s1, const float* b1, const void* w2, const float* s2, int w2_sliced,
-                         float* slab, hipStream_t stream);
-// which form launch_expert_ffn_bf16w takes for this shape, and where / in how many slabs its result rows are
-bool expert_ffn_bf16_tiled(int S, int E, int D, int F);
-float* expert_ffn_bf16_rows(float* slab, int S, int E, int D, int F);
-int expert_ffn_bf16_slices(int S, int E, int D, int F);
-// what the 16-bit / fp8 dispatchers above run for a shape (wmode 1 = bf16 weights, 2 = fp8 weights), for the combine
-// step and for launch accounting: where the result rows are, in how many partial slabs, how many kernel launches
-float* expert_ffn_w16_rows(int wmode, float* slab, int S, int E, int D, int F);
-int expert_ffn_w16_slices(int wmode, int S, int E, int D, int F);
-int expert_ffn_w16_launches(int wmode, int S, int E, int D, int F);
-const char* expert_ffn_w16_kernel(int wmode, int S, int E, int D, int F);
+int launch_expert_ffn_w8_slab(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D, int F,
+                              const void* w1, const float* s1, const float* b1, const void* w2, const float* s2, int w2_sliced,
+                              float* slab, hipStream_t stream);
 // fp8 arithmetic (e4m3 weights x e4m3 activations, fp8 MFMA), long batches (D = 512): moe_expert_fused_fp8.hip.
-// wmode 3 in the helpers above = "fp8 weights + fp8 activations where this kernel applies, else the weight-only form"
-bool expert_ffn_fused_fp8_applies(int S, int E, int D, int F);
+// The F split its cost model picks for a shape the kernel takes, 0 where it does not apply (the row threshold is the plan's)
+constexpr int kExpertFusedFp8MaxSplit = 4;     // ... at most this (what the combine allots when the kernel picks the split on the device)
 int expert_ffn_fused_fp8_fsplit(int S, int E, int D, int F);
 int init_expert_ffn_fused_fp8_kernels();
 int launch_expert_ffn_fused_fp8(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D, int F,
                                 const void* w1, const float* s1, const float* b1, const void* w2, const float* s2, int w2_sliced,
-                                float h_scale, float* ybuf, hipStream_t stream, const void* xq = nullptr, const float* xq_scale = nullptr,
-                                int32_t* fs_dev = nullptr);   // fs_dev: the kernel may split F finer than the host's choice and leaves the slab count there
+                                float h_scale, int fsplit, float* ybuf, hipStream_t stream, const void* xq = nullptr,
+                                const float* xq_scale = nullptr, int32_t* fs_dev = nullptr);
 int launch_quantize_rows_e4m3(const float* x, int ldx, int S, int D, void* xq, float* scale, hipStream_t stream);   // moe_expert_fused_fp8.hip
-// fp8 weights, dispatcher: h_scale > 0 asks for fp8 activations (taken where the fused kernel applies)
-bool expert_ffn_w8a8_fused(int S, int E, int D, int F);   // ... i.e. when this holds (moe_expert_bf16.hip)
-int launch_expert_ffn_w8a8(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D, int F,
-                           const void* w1, const float* s1, const float* b1, const void* w2, const float* s2, int w2_sliced,
-                           float h_scale, float* slab, hipStream_t stream, const void* xq = nullptr, const float* xq_scale = nullptr,
-                           int32_t* fs_dev = nullptr);
-// long batches: two grouped GEMMs on the LDS-tiled bf16 core (gemm_bf16_tiled.hip); hbuf S*F bf16, ybuf S*D fp32
-// b2 / y_scatter (optional): GEMM-2 adds the expert's b2 and writes row i of the sorted order to row pos[i] of y_scatter
-// (the un-permute of the expert-parallel receive side, folded into the epilogue)
-int launch_expert_ffn_bf16w_tiled(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E,
-                                  int D, int F, const void* w1, const float* b1, const void* w2, int w2_sliced,
-                                  void* hbuf, float* ybuf, hipStream_t stream, const float* b2 = nullptr, float* y_scatter = nullptr);
-// out[s] = resid[s] + alpha * gate[s] * (b2[g_s] + sum_slices slab[slice][mapping[s]]), optional LayerNorm after
+// long batches, bf16 or fp8 (w_fp8: s1 / s2 per-row scales) weights: two grouped GEMMs on the LDS-tiled bf16 core
+// (gemm_bf16_tiled.hip); hbuf S*F bf16, ybuf S*D fp32.  b2 / y_scatter (optional, bf16 weights): GEMM-2 adds the expert's b2
+// and writes row i of the sorted order to row pos[i] of y_scatter
+int launch_expert_tiled_w16(bool w_fp8, const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E,
+                            int D, int F, const void* w1, const float* s1, const float* b1, const void* w2, const float* s2,
+                            int w2_sliced, void* hbuf, float* ybuf, hipStream_t stream, const float* b2 = nullptr,
+                            float* y_scatter = nullptr);
 // SoftmaxTopK + ScatterMapping + grouped expert FFN in ONE launch (S <= 256 rows, all experts local, fp32): see moe_expert.hip
 bool expert_ffn_f32_self_routing(int S, int E);
 int launch_expert_route_ffn_f32(const float* x, int ldx, const float* logits, const int32_t* row_len, int rows_per_batch, int S, int E,
                                 int D, int F, const float* w1, const float* b1, const float* w2, int w2_sliced, const float* b2,
                                 float* slab, int32_t* gate_idx, float* gate_value, int32_t* mapping, int32_t* acc_hist, int32_t* pos,
                                 hipStream_t stream, const float* ln_gamma = nullptr, const float* ln_beta = nullptr, float ln_eps = 0.f);
-// grouped bf16 expert GEMMs on 256 x 256 x 64 LDS-DMA tiles (expert_gemm_g256.hip): saturating row counts (>= 512 rows per expert)
-bool expert_ffn_bf16_g256(int S, int E, int D, int F);
+// grouped bf16 expert GEMMs on 256 x 256 x 64 LDS-DMA tiles (expert_gemm_g256.hip): saturating row counts (>= 512 rows per expert).
+// xb: bf16 copy of the rows (launch_rows_to_bf16), S*D bf16
+bool expert_gemm_g256_takes(int S, int E, int D, int F);   // what the kernel can run at all (not whether it pays: the plan)
 int init_expert_gemm_g256_kernels();
 int launch_rows_to_bf16(const float* x, int ldx, int S, int D, void* xb, hipStream_t stream);
 int launch_expert_ffn_bf16_g256(const void* xb, int ldxb, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D, int F,
                                 const void* w1, const float* b1, const void* w2, int w2_sliced, void* hbuf, float* ybuf,
                                 hipStream_t stream);
+// out[s] = resid[s] + alpha * gate[s] * (b2[g_s] + sum_slices slab[slice][mapping[s]]), optional LayerNorm after
 int launch_moe_combine(const float* slab, int n_slices, const int32_t* mapping, const int32_t* gate_idx,
                        const float* gate_value, const float* b2, const float* resid, float alpha,
                        const float* ln_gamma, const float* ln_beta, float ln_eps, float* out, int S, int D,

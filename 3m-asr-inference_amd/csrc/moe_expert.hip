@@ -326,16 +326,13 @@ size_t expert_ffn_slab_bytes(int S, int D, int F) {
   return (size_t)(F / kExpertSlice) * (size_t)S * (size_t)D * sizeof(float);
 }
 
-int launch_expert_ffn_f32(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D,
-                          int F, const float* w1, const float* b1, const float* w2, int w2_sliced, float* slab,
-                          const float* ln_gamma, const float* ln_beta, float ln_eps, hipStream_t stream) {
+int launch_expert_ffn_f32_slab(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D,
+                               int F, const float* w1, const float* b1, const float* w2, int w2_sliced, float* slab,
+                               const float* ln_gamma, const float* ln_beta, float ln_eps, hipStream_t stream) {
   M3_REQUIRE(S > 0 && E > 0, "expert_ffn: empty problem S=%d E=%d", S, E);
   M3_REQUIRE((D & 15) == 0 && D <= 2048, "expert_ffn: idim=%d must be a multiple of 16 (<=2048)", D);
   M3_REQUIRE(F % kExpertSlice == 0, "expert_ffn: hidden_units=%d must be a multiple of %d", F, kExpertSlice);
   M3_REQUIRE((ldx & 3) == 0, "expert_ffn: ldx=%d must be a multiple of 4", ldx);
-  if (ln_gamma == nullptr && expert_ffn_f32_tiled(S, E, D, F))   // long batches: two grouped LDS-tiled GEMMs
-    return launch_expert_ffn_f32_tiled(x, ldx, pos, acc_hist, S, E, D, F, w1, b1, w2, w2_sliced, slab,
-                                       expert_ffn_f32_rows(slab, S, E, D, F), stream);
   // rows per tile: small batches keep LDS small (more workgroups per CU -> more bytes in flight)
   const int mt = S <= 64 ? 1 : (S <= 512 ? 2 : 4);
   const size_t lds_bytes = (size_t)16 * mt * ((D + 8) + (kExpertSlice + 8)) * sizeof(float);
@@ -358,7 +355,7 @@ int launch_expert_ffn_f32(const float* x, int ldx, const int32_t* pos, const int
 
 // Self-routing launch (see ExpertRoute): SoftmaxTopK + ScatterMapping + grouped expert FFN in one launch for S <= 256 rows.
 // slab [F/64][S][D] receives the partial outputs at ORIGINAL rows with b2 already added by slice 0: combine with
-// mapping = NULL, b2 = NULL.  Bit-identical to launch_moe_gate_index + launch_expert_ffn_f32 + combine(mapping, b2).
+// mapping = NULL, b2 = NULL.  Bit-identical to launch_moe_gate_index + launch_expert_ffn_f32_slab + combine(mapping, b2).
 bool expert_ffn_f32_self_routing(int S, int E) { return S >= 1 && S <= 64 * (kExpertSlice / 16) && (E == 8 || E == 16 || E == 32 || E == 64); }
 
 int launch_expert_route_ffn_f32(const float* x, int ldx, const float* logits, const int32_t* row_len, int rows_per_batch, int S, int E,

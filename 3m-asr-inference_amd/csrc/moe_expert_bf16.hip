@@ -156,48 +156,8 @@ __global__ __launch_bounds__(64 * (kExpertSliceW16 / 16)) void expert_ffn_bf16w_
 
 // Long batches run as two grouped GEMMs on the LDS-tiled core instead (gemm_bf16_tiled.hip): the slab form writes and
 // re-reads F/64 partial outputs per row (32 KB per row), which bounds it to ~65 TFLOP/s however many rows an expert has.
-// The tiled form keeps H (bf16, S*F) and the sorted output rows (fp32, S*D) in the SAME workspace region the slabs use.
-bool expert_ffn_bf16_tiled(int S, int E, int D, int F) {
-  static const int min_rows = [] {
-    const char* e = getenv("M3_EXPERT_TILED_MIN_ROWS");
-    return e ? atoi(e) : 1024;
-  }();
-  const size_t slab = expert_ffn_slab_bytes(S, D, F);
-  const size_t need = align_up((size_t)S * F * 2, 256) + (size_t)S * D * 4;
-  return S >= min_rows && (D & 127) == 0 && (F & 127) == 0 && need <= slab;
-}
-float* expert_ffn_bf16_rows(float* slab, int S, int E, int D, int F) {   // what moe_combine reads
-  return expert_ffn_bf16_tiled(S, E, D, F) ? (float*)((char*)slab + align_up((size_t)S * F * 2, 256)) : slab;
-}
-int expert_ffn_bf16_slices(int S, int E, int D, int F) { return expert_ffn_bf16_tiled(S, E, D, F) ? 1 : F / kExpertSliceW16; }
-
-// fp8 arithmetic (wmode 3) takes the fused one-kernel form where it applies (its result: fsplit slabs of sorted rows at the
-// start of the slab region); bf16 and fp8 weight-only experts keep the layouts above
-static int w16_fsplit(int wmode, int S, int E, int D, int F) { return expert_ffn_fused_fp8_fsplit(S, E, D, F); }
-static bool w16_fused(int wmode, int S, int E, int D, int F) {
-  return wmode == 3 && expert_ffn_fused_fp8_applies(S, E, D, F) &&
-         (size_t)w16_fsplit(wmode, S, E, D, F) * S * D * 4 <= expert_ffn_slab_bytes(S, D, F);
-}
-bool expert_ffn_w8a8_fused(int S, int E, int D, int F) { return w16_fused(3, S, E, D, F); }
-float* expert_ffn_w16_rows(int wmode, float* slab, int S, int E, int D, int F) {
-  return w16_fused(wmode, S, E, D, F) ? slab : expert_ffn_bf16_rows(slab, S, E, D, F);
-}
-int expert_ffn_w16_slices(int wmode, int S, int E, int D, int F) {
-  return w16_fused(wmode, S, E, D, F) ? w16_fsplit(wmode, S, E, D, F) : expert_ffn_bf16_slices(S, E, D, F);
-}
-int expert_ffn_w16_launches(int wmode, int S, int E, int D, int F) {
-  if (w16_fused(wmode, S, E, D, F)) return 1;
-  if (wmode == 1 && expert_ffn_bf16_tiled(S, E, D, F) && expert_ffn_bf16_g256(S, E, D, F)) return 3;   // rows -> bf16, GEMM-1, GEMM-2
-  return expert_ffn_bf16_tiled(S, E, D, F) ? 2 : 1;
-}
-const char* expert_ffn_w16_kernel(int wmode, int S, int E, int D, int F) {
-  if (w16_fused(wmode, S, E, D, F)) return "expert_ffn_fused_fp8_kernel";
-  if (wmode == 3) wmode = 2;
-  if (wmode == 1 && expert_ffn_bf16_tiled(S, E, D, F) && expert_ffn_bf16_g256(S, E, D, F)) return "expert_gemm_g256_kernel";
-  if (expert_ffn_bf16_tiled(S, E, D, F)) return wmode == 2 ? "gemm_bf16w_tiled_kernel<grouped,fp8>" : "gemm_bf16w_tiled_kernel<grouped>";
-  return wmode == 2 ? "expert_ffn_w8_kernel" : "expert_ffn_bf16w_kernel";
-}
-
+// The tiled form keeps H (bf16, S*F) and the sorted output rows (fp32, S*D) in the SAME workspace region the slabs use
+// (plan_expert_ffn, moe_expert_plan.hip).
 int init_expert_ffn_bf16_kernels() {
   static PerDeviceOnce once;
   if (once.done()) return 0;
@@ -206,17 +166,13 @@ int init_expert_ffn_bf16_kernels() {
   return 0;
 }
 
-int launch_expert_ffn_bf16w(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D,
-                            int F, const void* w1, const float* b1, const void* w2, int w2_sliced, float* slab,
-                            hipStream_t stream, const float* b2, float* y_scatter) {
+int launch_expert_ffn_bf16w_slab(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D,
+                                 int F, const void* w1, const float* b1, const void* w2, int w2_sliced, float* slab,
+                                 hipStream_t stream) {
   M3_REQUIRE(S > 0 && E > 0, "expert_ffn_bf16w: empty problem S=%d E=%d", S, E);
   M3_REQUIRE((D & 31) == 0 && D <= 2048, "expert_ffn_bf16w: idim=%d must be a multiple of 32 (<=2048)", D);
   M3_REQUIRE(F % kExpertSliceW16 == 0, "expert_ffn_bf16w: hidden_units=%d must be a multiple of %d", F, kExpertSliceW16);
   M3_REQUIRE((ldx & 3) == 0, "expert_ffn_bf16w: ldx=%d must be a multiple of 4", ldx);
-  if (expert_ffn_bf16_tiled(S, E, D, F))
-    return launch_expert_ffn_bf16w_tiled(x, ldx, pos, acc_hist, S, E, D, F, w1, b1, w2, w2_sliced, slab,
-                                         expert_ffn_bf16_rows(slab, S, E, D, F), stream, b2, y_scatter);
-  M3_REQUIRE(y_scatter == nullptr, "expert_ffn_bf16w: the scattering epilogue exists in the tiled form only (S=%d E=%d)", S, E);
   const int mt = S <= 64 ? 1 : (S <= 512 ? 2 : 4);
   const size_t lds_bytes = (size_t)16 * mt * ((D + 8) + (kExpertSliceW16 + 8)) * sizeof(bf16_t);
   M3_REQUIRE(lds_bytes <= 160 * 1024, "expert_ffn_bf16w: LDS tile of %zu bytes does not fit", lds_bytes);

@@ -173,23 +173,15 @@ int init_expert_ffn_w8_kernels() {
   return 0;
 }
 
-// tiled (long-batch) form lives in gemm_bf16_tiled.hip
-int launch_expert_ffn_w8_tiled(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D,
-                               int F, const void* w1, const float* s1, const float* b1, const void* w2, const float* s2,
-                               int w2_sliced, void* hbuf, float* ybuf, hipStream_t stream);
-
 // fp8 expert weights: w1 [E][F][D] e4m3 + s1 [E][F]; w2 [E][D][F] (or slice-major) e4m3 + s2 [E][D].  Result layout
-// (slabs / sorted rows) is that of the bf16 form: expert_ffn_bf16_rows / _slices tell the combine step where it is.
-int launch_expert_ffn_w8(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D, int F,
-                         const void* w1, const float* s1, const float* b1, const void* w2, const float* s2,
-                         int w2_sliced, float* slab, hipStream_t stream) {
+// (F / 64 slabs) is that of the bf16 slab form; the tiled (long-batch) form lives in gemm_bf16_tiled.hip.
+int launch_expert_ffn_w8_slab(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D, int F,
+                              const void* w1, const float* s1, const float* b1, const void* w2, const float* s2,
+                              int w2_sliced, float* slab, hipStream_t stream) {
   M3_REQUIRE(S > 0 && E > 0, "expert_ffn_w8: empty problem S=%d E=%d", S, E);
   M3_REQUIRE((D & 63) == 0 && D <= 2048, "expert_ffn_w8: idim=%d must be a multiple of 64 (<=2048)", D);
   M3_REQUIRE(F % kExpertSliceW16 == 0, "expert_ffn_w8: hidden_units=%d must be a multiple of %d", F, kExpertSliceW16);
   M3_REQUIRE((ldx & 3) == 0, "expert_ffn_w8: ldx=%d must be a multiple of 4", ldx);
-  if (expert_ffn_bf16_tiled(S, E, D, F))
-    return launch_expert_ffn_w8_tiled(x, ldx, pos, acc_hist, S, E, D, F, w1, s1, b1, w2, s2, w2_sliced, slab,
-                                      expert_ffn_bf16_rows(slab, S, E, D, F), stream);
   const int mt = S <= 64 ? 1 : (S <= 512 ? 2 : 4);
   const size_t lds_bytes = (size_t)16 * mt * ((D + 8) + (kExpertSliceW16 + 8)) * sizeof(bf16_t);
   M3_REQUIRE(lds_bytes <= 160 * 1024, "expert_ffn_w8: LDS tile of %zu bytes does not fit", lds_bytes);
@@ -206,17 +198,6 @@ int launch_expert_ffn_w8(const float* x, int ldx, const int32_t* pos, const int3
 #undef M3_EXPERT_CASE
   M3_LAUNCH_CHECK();
   return 0;
-}
-
-// fp8 weights with fp8 activations where the fused fp8 kernel applies (long batches, D = 512), else the weight-only form
-bool expert_ffn_w8a8_fused(int S, int E, int D, int F);   // moe_expert_bf16.hip (layout helpers)
-int launch_expert_ffn_w8a8(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D, int F,
-                           const void* w1, const float* s1, const float* b1, const void* w2, const float* s2, int w2_sliced,
-                           float h_scale, float* slab, hipStream_t stream, const void* xq, const float* xq_scale, int32_t* fs_dev) {
-  // (xq / xq_scale: the rows already quantised by the router kernel -- only the fused kernel takes them; x stays valid for the other form)
-  if (h_scale > 0.f && expert_ffn_w8a8_fused(S, E, D, F))
-    return launch_expert_ffn_fused_fp8(x, ldx, pos, acc_hist, S, E, D, F, w1, s1, b1, w2, s2, w2_sliced, h_scale, slab, stream, xq, xq_scale, fs_dev);
-  return launch_expert_ffn_w8(x, ldx, pos, acc_hist, S, E, D, F, w1, s1, b1, w2, s2, w2_sliced, slab, stream);
 }
 
 }  // namespace m3

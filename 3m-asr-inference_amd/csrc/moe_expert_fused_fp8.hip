@@ -763,19 +763,17 @@ __global__ __launch_bounds__(256) void expert_ffn_fused_fp8_kernel(
 }
 
 // ---- host side ----
-static int fused8_min_rows() {   // read once: the engine freezes the form (and the combine's slab layout) when a shape is bound
-  static const int v = [] {
-    const char* e = getenv("M3_EXPERT_FUSED_FP8_MIN_ROWS");
-    return e ? atoi(e) : 4096;
-  }();
-  return v;
-}
 // persistent grid: one work-group per CU, a multiple of 8 (XCDs)
 static int fused8_grid() {
   const int cus = device_cu_count();
   return cus >= 8 ? cus / 8 * 8 : 8;
 }
-int expert_ffn_fused_fp8_fsplit(int S, int E, int D, int F) {
+// the kernel runs this shape with F in fs parts (b1 / s1 of a work item's F range: 1024 floats each in LDS)
+static bool fused8_takes(int S, int E, int D, int F, int fs) {
+  return D == kD && F % 128 == 0 && F <= 4096 && S >= 64 * E && E > 0 && E <= 1024 && (fs == 1 || fs == 2 || fs == 4) &&
+         F % (128 * fs) == 0 && F / fs <= 1024;
+}
+static int fused8_fsplit(int S, int E, int D, int F) {
   static const int forced = [] { const char* e = getenv("M3_FUSED8_FSPLIT"); return e ? atoi(e) : 0; }();
   if (forced == 1 || forced == 2 || forced == 4) return forced;
   // F parts per token tile.  A work item streams its part of the expert's weights (D F / fs bytes of W1 and of W2) plus the
@@ -792,13 +790,14 @@ int expert_ffn_fused_fp8_fsplit(int S, int E, int D, int F) {
     const long cost = (long)cdiv(tiles * f, cus) * (2L * D * F / f + 2L * kTok * D * 4);
     if (best < 0 || cost < best) { best = cost; fs = f; }
   }
-  while (F / fs > 1024 && fs < 4) fs *= 2;                   // b1 / s1 of a work item's F range: 1024 floats each in LDS
+  while (F / fs > 1024 && fs < 4) fs *= 2;
   return fs;
 }
-bool expert_ffn_fused_fp8_applies(int S, int E, int D, int F) {
-  if (!(D == kD && F % 128 == 0 && F <= 4096 && S >= fused8_min_rows() && S >= 64 * E && E <= 1024)) return false;
-  const int fs = expert_ffn_fused_fp8_fsplit(S, E, D, F);
-  return F % (128 * fs) == 0 && F / fs <= 1024;
+static_assert(kExpertFusedFp8MaxSplit == 4, "the cost model above and the kernel's instantiations stop at 4 parts");
+// the F split for a shape this kernel takes, 0 where it does not apply (from how many rows it pays: plan_expert_ffn)
+int expert_ffn_fused_fp8_fsplit(int S, int E, int D, int F) {
+  const int fs = fused8_fsplit(S, E, D, F);
+  return fused8_takes(S, E, D, F, fs) ? fs : 0;
 }
 int init_expert_ffn_fused_fp8_kernels() {
   static PerDeviceOnce once;
@@ -845,13 +844,13 @@ int launch_quantize_rows_e4m3(const float* x, int ldx, int S, int D, void* xq, f
 
 int launch_expert_ffn_fused_fp8(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D, int F,
                                 const void* w1, const float* s1, const float* b1, const void* w2, const float* s2, int w2_sliced,
-                                float h_scale, float* ybuf, hipStream_t stream, const void* xq, const float* xq_scale, int32_t* fs_dev) {
+                                float h_scale, int fsplit, float* ybuf, hipStream_t stream, const void* xq, const float* xq_scale,
+                                int32_t* fs_dev) {
   M3_REQUIRE(xq == nullptr || xq_scale != nullptr, "expert_ffn_fused_fp8: quantised rows without their scales");
-  M3_REQUIRE(expert_ffn_fused_fp8_applies(S, E, D, F), "expert_ffn_fused_fp8: shape S=%d E=%d D=%d F=%d not supported", S, E, D, F);
+  M3_REQUIRE(fused8_takes(S, E, D, F, fsplit), "expert_ffn_fused_fp8: shape S=%d E=%d D=%d F=%d in %d parts not supported", S, E, D, F, fsplit);
   M3_REQUIRE((ldx & 3) == 0, "expert_ffn_fused_fp8: ldx=%d must be a multiple of 4", ldx);
   M3_REQUIRE(h_scale > 0.f, "expert_ffn_fused_fp8: h_scale must be positive (got %g)", (double)h_scale);
   if (int rc = init_expert_ffn_fused_fp8_kernels()) return rc;
-  const int fsplit = expert_ffn_fused_fp8_fsplit(S, E, D, F);
   M3_REQUIRE((size_t)S * ldx * 4 < ((size_t)1 << 32), "expert_ffn_fused_fp8: input of %d rows x %d floats exceeds a 4-GB buffer", S, ldx);
   const int nblk = fused8_grid();
   const int row_stride = w2_sliced ? 64 : F;                 // bytes between consecutive d rows of W2

@@ -189,20 +189,6 @@ __global__ __launch_bounds__(256, 2) void expert_gemm_f32_tiled_kernel(const Gro
   }
 }
 
-bool expert_ffn_f32_tiled(int S, int E, int D, int F) {
-  static const int min_rows = [] {
-    const char* e = getenv("M3_EXPERT_TILED_MIN_ROWS");
-    return e ? atoi(e) : 1024;
-  }();
-  const size_t slab = expert_ffn_slab_bytes(S, D, F);
-  const size_t need = align_up((size_t)S * F * 4, 256) + (size_t)S * D * 4;
-  return S >= min_rows && (D & 63) == 0 && (F & 63) == 0 && need <= slab;
-}
-float* expert_ffn_f32_rows(float* slab, int S, int E, int D, int F) {
-  return expert_ffn_f32_tiled(S, E, D, F) ? (float*)((char*)slab + align_up((size_t)S * F * 4, 256)) : slab;
-}
-int expert_ffn_f32_slices(int S, int E, int D, int F) { return expert_ffn_f32_tiled(S, E, D, F) ? 1 : F / kExpertSlice; }
-
 int init_expert_ffn_f32_tiled_kernels() {
   static PerDeviceOnce once;
   if (once.done()) return 0;
@@ -215,9 +201,9 @@ int init_expert_ffn_f32_tiled_kernels() {
   return 0;
 }
 
-int launch_expert_ffn_f32_tiled(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D,
-                                int F, const float* w1, const float* b1, const float* w2, int w2_sliced, float* hbuf,
-                                float* ybuf, hipStream_t stream) {
+int launch_expert_tiled_f32(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D,
+                            int F, const float* w1, const float* b1, const float* w2, int w2_sliced, float* hbuf,
+                            float* ybuf, hipStream_t stream) {
   M3_REQUIRE((D & 63) == 0 && (F & 63) == 0 && (ldx & 3) == 0, "expert_ffn tiled: idim=%d / hidden=%d must be multiples of 64", D, F);
   if (int rc = init_expert_ffn_f32_tiled_kernels()) return rc;
   const bool big = S / E >= 192;                     // rows per expert fill 128-row tiles

@@ -111,6 +111,7 @@ SIGNATURES = {
     "m3_moe_expert_ffn_fp8a8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _f, _vp,
                                      _vp, _sz, _vp]),
     "m3_moe_expert_ffn_fp8a8_active": (_i, [_i, _i, _i, _i]),
+    "m3_moe_expert_ffn_kernel": (C.c_char_p, [_i, _i, _i, _i, _i, _i, _vp, _vp]),
     "m3_moe_expert_ffn_fp8a8_xq": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp,
                                         _f, _vp, _vp, _sz, _vp]),
     "m3_quantize_rows_e4m3": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),

@@ -153,6 +153,10 @@ int m3_moe_expert_ffn_fp8a8(const float* x, const int32_t* gate_idx, const void*
                             float alpha, const float* ln_gamma, const float* ln_beta, float ln_eps, float* y,
                             void* workspace, size_t workspace_bytes, m3_stream stream);
 int m3_moe_expert_ffn_fp8a8_active(int S, int num_expert, int idim, int hidden_units);
+/* Host only: the kernel the grouped expert FFN runs for this weight dtype (M3_F32 / M3_BF16 / M3_FP8, fp8_activations 0/1) and shape,
+ * its launch count and the number of partial-result slabs; NULL for a shape the operator rejects.  No pointer is dereferenced. */
+const char* m3_moe_expert_ffn_kernel(int weight_dtype, int fp8_activations, int S, int num_expert, int idim, int hidden_units,
+                                     int32_t* launches, int32_t* slices);
 /* ABI 9.  The same operator on rows that are ALREADY quantised the way it quantises them itself: xq [S][idim] e4m3, xq_scale [S]
  * (x = xq * xq_scale per row; what m3_quantize_rows_e4m3 and, inside the engine, the router kernel write).  Where the fused
  * kernel applies (m3_moe_expert_ffn_fp8a8_active) x is not read and may be NULL, and the result is bit-identical to

@@ -113,6 +113,12 @@ def test_linear_bf16_folded_layernorm(M, mean, std):
                                            (40000, 32, 512, 1024, "skewed"), (20000, 8, 512, 1024, "skewed"),
                                            (70000, 64, 512, 1024, "with_dropped")])
 def test_fmoe_expert_bf16(S, E, D, Fh, mode):
+    # the form each case reaches (host-only query of the one plan the operator runs)
+    if S >= 1024 and Fh % 128 == 0:
+        form = b"expert_gemm_g256_kernel" if S // E >= 512 else b"gemm_bf16w_tiled_kernel<grouped>"
+    else:
+        form = b"expert_ffn_bf16w_kernel"
+    assert ops._lib.load().m3_moe_expert_ffn_kernel(4, 0, S, E, D, Fh, None, None) == form
     rng = np.random.default_rng(S + E)
     if mode == "skewed":
         pr = np.ones(E)

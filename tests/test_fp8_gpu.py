@@ -77,6 +77,9 @@ def test_device_e4m3_decoding_matches_torch():
                                            (1090, 32, 512, 1024, "with_dropped"), (2048, 32, 512, 1024, "all_one"),
                                            (8192, 32, 512, 1024, "uniform")])
 def test_fmoe_expert_fp8(S, E, D, Fh, mode):
+    # slab kernel below 1024 rows, then the two grouped tiled GEMMs (host-only query of the one plan the operator runs)
+    form = ops._lib.load().m3_moe_expert_ffn_kernel(5, 0, S, E, D, Fh, None, None)
+    assert form == (b"gemm_bf16w_tiled_kernel<grouped,fp8>" if S >= 1024 else b"expert_ffn_w8_kernel")
     g, x, (w1, b1, w2, b2), (q1, s1, q2, s2) = _expert_case(S, E, D, Fh, mode)
     y = ops.moe_expert_ffn(dev(x), dev(g), dev(q1), dev(b1), dev(q2), dev(b2), w1_scale=dev(s1), w2_scale=dev(s2))
     d1 = q1.double() * s1.double().unsqueeze(-1)             # dequantised weights
@@ -117,6 +120,7 @@ def test_fmoe_expert_fp8_arithmetic(S, E, D, Fh, mode):
     3e-3 of the output scale.  And within e4m3 accuracy (3 mantissa bits on both operands) of the unquantised fp32 FFN."""
     g, x, (w1, b1, w2, b2), (q1, s1, q2, s2) = _expert_case(S, E, D, Fh, mode)
     assert ops._lib.load().m3_moe_expert_ffn_fp8a8_active(S, E, D, Fh) == 1
+    assert ops._lib.load().m3_moe_expert_ffn_kernel(5, 1, S, E, D, Fh, None, None) == b"expert_ffn_fused_fp8_kernel"
     # static H scale as the calibrator would set it: amax of the (unquantised) hidden activations x 1.25 / 448
     hmax = 0.0
     for e in range(E):

@@ -254,6 +254,9 @@ def test_moe_router(S, E, De, D):
                                            (2048, 32, 512, 1024, "all_one"), (8192, 32, 512, 1024, "uniform"),
                                            (6500, 8, 512, 1024, "with_dropped")])
 def test_fmoe_expert(S, E, D, Fh, mode):
+    # the form each row count reaches (host-only query of the one plan the operator runs): slab kernel below 1024 rows
+    form = ops._lib.load().m3_moe_expert_ffn_kernel(0, 0, S, E, D, Fh, None, None)
+    assert form == (b"expert_gemm_f32_tiled_kernel" if S >= 1024 else b"expert_ffn_f32_kernel")
     rng = np.random.default_rng(S + E)
     g = {"uniform": rng.integers(0, E, S), "all_one": np.full(S, 3), "with_dropped": rng.integers(-1, E, S)}[mode]
     g = torch.from_numpy(g.astype(np.int32))
