@@ -208,6 +208,52 @@ int m3_softmax_top1(const float* logits, int ld, const int32_t* len, int rows_pe
   M3_REQUIRE(S <= 1 || ld >= width, "softmax_topk: ld=%d is shorter than a row of %d", ld, width);
   return launch_softmax_top1(logits, ld, len, rows_per_batch, S, width, idx, value, (hipStream_t)stream);
 }
+int m3_moe_gate_index(const float* logits, const int32_t* row_len, int rows_per_batch, int S, int num_expert, int32_t* gate_idx,
+                      float* gate_value, int32_t* mapping, int32_t* acc_histogram, int32_t* pos, m3_stream stream) {
+  M3_REQUIRE(logits && gate_idx && gate_value && mapping && acc_histogram, "moe_gate_index: null pointer");
+  M3_REQUIRE(aligned16(logits), "moe_gate_index: logits must be 16-byte aligned");
+  return launch_moe_gate_index(logits, num_expert, row_len, rows_per_batch, S, gate_idx, gate_value, mapping, acc_histogram, pos,
+                               (hipStream_t)stream);
+}
+int m3_moe_route(const float* x, int ldx, int idim, const float* wx, const float* wsum, const float* bias, const float* eall,
+                 int ld_e, float ln_eps, const int32_t* row_len, int rows_per_batch, int S, int num_expert, int32_t* gate_idx,
+                 float* gate_value, int32_t* mapping, int32_t* acc_histogram, int32_t* pos, m3_stream stream) {
+  M3_REQUIRE(x && wx && wsum && gate_idx && gate_value && mapping && acc_histogram, "moe_route: null pointer");
+  M3_REQUIRE(idim > 0, "moe_route: idim=%d", idim);
+  M3_REQUIRE(S <= 1 || ldx >= idim, "moe_route: ldx=%d is shorter than a row of %d", ldx, idim);
+  M3_REQUIRE(eall == nullptr || S <= 1 || ld_e >= num_expert, "moe_route: ld_e=%d is shorter than a row of %d", ld_e, num_expert);
+  M3_REQUIRE(aligned16(x) && aligned16(wx), "moe_route: x / wx must be 16-byte aligned");
+  return launch_moe_route(x, ldx, idim, wx, wsum, bias, eall, ld_e, ln_eps, row_len, rows_per_batch, S, num_expert, gate_idx,
+                          gate_value, mapping, acc_histogram, pos, (hipStream_t)stream);
+}
+size_t m3_moe_route_expert_workspace_size(int S, int num_expert, int idim, int hidden_units) {
+  if (!expert_ffn_f32_self_routing(S, num_expert) || idim <= 0 || hidden_units <= 0 || hidden_units % kExpertSlice) return 0;
+  return align_up(expert_ffn_slab_bytes(S, idim, hidden_units), 256);
+}
+int m3_moe_route_expert_ffn(const float* x, int ldx, const float* logits, const int32_t* row_len, int rows_per_batch,
+                            const float* w1, const float* b1, const float* w2, int w2_sliced, const float* b2, int S,
+                            int num_expert, int idim, int hidden_units, const float* norm_gamma, const float* norm_beta,
+                            float norm_eps, int use_gate_value, const float* resid, float alpha, const float* ln_gamma,
+                            const float* ln_beta, float ln_eps, int32_t* gate_idx, float* gate_value, int32_t* mapping,
+                            int32_t* acc_histogram, int32_t* pos, float* y, void* workspace, size_t workspace_bytes,
+                            m3_stream stream) {
+  M3_REQUIRE(x && w1 && b1 && w2 && y, "moe_route_expert_ffn: null pointer");
+  M3_REQUIRE((norm_gamma == nullptr) == (norm_beta == nullptr) && (ln_gamma == nullptr) == (ln_beta == nullptr),
+             "moe_route_expert_ffn: a LayerNorm needs both gamma and beta");
+  M3_REQUIRE(idim > 0 && hidden_units > 0, "moe_route_expert_ffn: bad sizes D=%d F=%d", idim, hidden_units);
+  M3_REQUIRE(S <= 1 || ldx >= idim, "moe_route_expert_ffn: ldx=%d is shorter than a row of %d", ldx, idim);
+  M3_REQUIRE(aligned16(x) && aligned16(logits), "moe_route_expert_ffn: x / logits must be 16-byte aligned");
+  const size_t need = m3_moe_route_expert_workspace_size(S, num_expert, idim, hidden_units);
+  M3_REQUIRE(need == 0 || (workspace != nullptr && workspace_bytes >= need), "moe_route_expert_ffn: workspace %zu bytes < required %zu",
+             workspace_bytes, need);      // (need == 0: a shape the launcher rejects, with its own message)
+  float* slab = (float*)workspace;
+  int rc = launch_expert_route_ffn_f32(x, ldx, logits, row_len, rows_per_batch, S, num_expert, idim, hidden_units, w1, b1, w2, w2_sliced,
+                                       b2, slab, gate_idx, gate_value, mapping, acc_histogram, pos, (hipStream_t)stream, norm_gamma,
+                                       norm_beta, norm_eps);
+  if (rc) return rc;
+  return launch_moe_combine(slab, hidden_units / kExpertSlice, nullptr, gate_idx, use_gate_value ? gate_value : nullptr, nullptr, resid,
+                            alpha, ln_gamma, ln_beta, ln_eps, y, S, idim, (hipStream_t)stream);
+}
 
 // what the three attention entry points ask of their row operands besides the multiples the launchers check (include/m3asr.h)
 static int attention_operands(const void* qkv, int ldq, const void* p, int ldp, const void* out, int ldo, int B, int T, int H, int dk) {

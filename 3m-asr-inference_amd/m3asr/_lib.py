@@ -119,6 +119,11 @@ SIGNATURES = {
     "m3_moe_combine_bf16": (_i, [_vp, _vp, _vp, _vp, _f, _vp, _vp, _f, _vp, _vp, _i, _i, _vp]),
     "m3_softmax_top1": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "m3_moe_router": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _i, _vp, _i, _i, _i, _vp]),
+    "m3_moe_gate_index": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "m3_moe_route": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "m3_moe_route_expert_workspace_size": (_sz, [_i, _i, _i, _i]),
+    "m3_moe_route_expert_ffn": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _f,
+                                     _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "m3_linear": (_i, [_P(LinearDesc), _vp]),
     "m3_linear_workspace_size": (_sz, [_P(LinearDesc)]),
     "m3_linear_kernel": (C.c_char_p, [_P(LinearDesc), _i]),

@@ -200,6 +200,76 @@ def softmax_top1(logits, lens=None, rows_per_batch=0):
     return val, idx
 
 
+def _route_taps(S, E, device, taps):
+    """(gate_idx, gate_value, mapping, acc_histogram, pos) of the routing entry points: the caller's buffers or fresh ones"""
+    if taps is None:
+        i32 = lambda n: torch.empty(n, dtype=torch.int32, device=device)   # noqa: E731
+        taps = (i32(S), torch.empty(S, dtype=torch.float32, device=device), i32(S), i32(E + 1), i32(S))
+    gi, gv, mp, acc, pos = taps
+    assert gi.numel() == S and gv.numel() == S and mp.numel() == S and acc.numel() == E + 1 and (pos is None or pos.numel() == S)
+    return taps, (_i32(gi), _f32(gv), _i32(mp), _i32(acc), _i32(pos))
+
+
+def moe_gate_index(logits, row_len=None, rows_per_batch=0, taps=None):
+    """SoftmaxTopK + ScatterMapping in one launch (m3_moe_gate_index): logits (S, E) dense -> (gate_idx, gate_value, mapping,
+    acc_histogram (E + 1), pos); frames t >= row_len[b] of rows_per_batch-frame utterances are dropped."""
+    lib = _lib.load()
+    S, E = logits.shape
+    taps, ptrs = _route_taps(S, E, logits.device, taps)
+    check(lib.m3_moe_gate_index(_f32(logits), _i32(row_len), rows_per_batch, S, E, *ptrs, _stream()), "m3_moe_gate_index")
+    return taps
+
+
+def moe_route(x, wx, wsum, bias=None, eall=None, ln_eps=1e-12, row_len=None, rows_per_batch=0, taps=None):
+    """Router x half with the LayerNorm folded into wx (E, D) / wsum (E) / bias (fold_layernorm of m3asr/plan.py), + the embed
+    half eall (S, E), + SoftmaxTopK + ScatterMapping in one launch (m3_moe_route).  x / eall may be row-strided views.
+    -> (gate_idx, gate_value, mapping, acc_histogram, pos)"""
+    lib = _lib.load()
+    S, D = x.shape
+    E = wx.shape[0]
+    assert tuple(wx.shape) == (E, D) and wsum.numel() == E and (bias is None or bias.numel() == E)
+    xp, ldx = _rows(x)
+    ep, lde = _rows(eall) if eall is not None else (None, E)
+    assert eall is None or tuple(eall.shape) == (S, E)
+    taps, ptrs = _route_taps(S, E, x.device, taps)
+    check(lib.m3_moe_route(xp, ldx, D, _f32(wx), _f32(wsum), _f32(bias), ep, lde, float(ln_eps), _i32(row_len), rows_per_batch,
+                           S, E, *ptrs, _stream()), "m3_moe_route")
+    return taps
+
+
+def moe_route_expert_workspace_size(S, E, D, F):
+    return _lib.load().m3_moe_route_expert_workspace_size(S, E, D, F)
+
+
+def moe_route_expert_ffn(x, logits, w1, b1, w2, b2, row_len=None, rows_per_batch=0, w2_sliced=False, norm=None,
+                         use_gate_value=True, resid=None, alpha=1.0, ln=None, workspace=None, out=None, taps=None):
+    """The self-routing expert launch + its combine (m3_moe_route_expert_ffn): router logits (S, E) -> top-1 routing, grouped
+    fp32 expert FFN, y = LN(resid + alpha * gate * ffn(x)) in two launches, S <= 256.  x (S, D) may be a row-strided view;
+    norm = (gamma, beta, eps): LayerNorm applied to x inside the expert kernel.  w2 (E, D, F); w2_sliced: the kernel reads
+    the slice-major layout of m3asr/plan.py (w2 already 4-D: taken as repacked).  -> (y, (gate_idx, gate_value, mapping,
+    acc_histogram, pos))"""
+    lib = _lib.load()
+    S, D = x.shape
+    E, F = w1.shape[0], w1.shape[1]
+    assert tuple(logits.shape) == (S, E) and w1.is_contiguous()
+    if w2_sliced and w2.dim() == 3:
+        from .plan import slice_major_w2
+        w2 = slice_major_w2(w2)
+    if workspace is None:
+        workspace = torch.empty(max(moe_route_expert_workspace_size(S, E, D, F), 1), dtype=torch.uint8, device=x.device)
+    y = out if out is not None else torch.empty(S, D, dtype=torch.float32, device=x.device)
+    xp, ldx = _rows(x)
+    ng, nb, neps = norm if norm is not None else (None, None, 0.0)
+    g, b, eps = ln if ln is not None else (None, None, 0.0)
+    taps, ptrs = _route_taps(S, E, x.device, taps)
+    check(lib.m3_moe_route_expert_ffn(xp, ldx, _f32(logits), _i32(row_len), rows_per_batch, _f32(w1), _f32(b1), _f32(w2),
+                                      1 if w2_sliced else 0, _f32(b2), S, E, D, F, _f32(ng), _f32(nb), float(neps),
+                                      1 if use_gate_value else 0, _f32(resid), float(alpha), _f32(g), _f32(b), float(eps),
+                                      *ptrs, _p(y), _p(workspace), workspace.numel() * workspace.element_size(), _stream()),
+          "m3_moe_route_expert_ffn")
+    return y, taps
+
+
 # ---------------------------------------------------------------------------------------- dense
 def linear(a, w, bias=None, act=_lib.ACT_NONE, a2=None, ln=None, lens=None, rows_per_batch=0, mask_in=False,
            mask_out=False, alpha=1.0, resid=None, out=None, ln_folded=None, split_k=False, out_dtype=torch.float32,

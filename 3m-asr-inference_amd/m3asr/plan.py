@@ -44,6 +44,13 @@ def positional_table(max_len, d):
     return pe
 
 
+def slice_major_w2(t):
+    """expert w_2 [E, D, F] -> slice-major [E, F/S, D, S] (S = EXPERT_SLICE): the bytes a workgroup of the grouped expert FFN
+    streams in its second GEMM become one contiguous run"""
+    E_, D_, F_ = t.shape
+    return t.reshape(E_, D_, F_ // EXPERT_SLICE, EXPERT_SLICE).permute(0, 2, 1, 3).contiguous()
+
+
 def _pack_subsampling(sd, p, out):
     w0 = sd[p + "conv.0.weight"]                         # (C,1,3,3)
     C = w0.shape[0]
@@ -144,10 +151,7 @@ def _pack_block(sd, p, out, norm, moe, cfg):
                 t = t[lo: lo + cfg.num_experts]
             assert t.shape[0] == cfg.num_experts, "%s: %d experts, config says %d" % (f + n, t.shape[0], cfg.num_experts)
             if n == "experts.w_2.weight":
-                # [E, D, F] -> slice-major [E, F/S, D, S] (S = EXPERT_SLICE): the bytes a workgroup of the grouped expert FFN
-                # streams in its second GEMM become one contiguous run
-                E_, D_, F_ = t.shape
-                out[f + "experts.w_2.weight_sliced"] = t.view(E_, D_, F_ // EXPERT_SLICE, EXPERT_SLICE).permute(0, 2, 1, 3).contiguous()
+                out[f + "experts.w_2.weight_sliced"] = slice_major_w2(t)
             else:
                 out[f + n] = t
 

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define M3ASR_ABI_VERSION 9
+#define M3ASR_ABI_VERSION 10
 
 typedef void* m3_stream; /* hipStream_t */
 
@@ -211,6 +211,43 @@ int m3_moe_router(const float* embed, int ld_embed, int embed_dim, const float* 
  * ld >= width, any value (element loads); idx / value are dense. */
 int m3_softmax_top1(const float* logits, int ld, const int32_t* len, int rows_per_batch, int S, int width,
                     int32_t* idx, float* value, m3_stream stream);
+/* ABI 10.  The routing launches the whole-encoder engine is built from, exposed so that they can be tested at the boundary
+ * (they replace nothing more in the reference than the operators they fuse).  All three leave the same five results:
+ * gate_idx[S] / gate_value[S] as m3_softmax_top1 (frames t >= row_len[b] get -1 / 0; row_len may be NULL), and mapping[S],
+ * acc_histogram[num_expert + 1], pos (may be NULL; entries at and beyond acc_histogram[num_expert] are not written) as
+ * m3_moe_scatter_mapping on that gate_idx.
+ *   m3_moe_gate_index: SoftmaxTopK + ScatterMapping in one single-work-group launch.  logits [S][num_expert] dense,
+ *                      16-byte aligned; num_expert 8 / 16 / 32 / 64, S >= 1. */
+int m3_moe_gate_index(const float* logits, const int32_t* row_len, int rows_per_batch, int S, int num_expert,
+                      int32_t* gate_idx, float* gate_value, int32_t* mapping, int32_t* acc_histogram, int32_t* pos,
+                      m3_stream stream);
+/*   m3_moe_route: the x half of the router product with the layer's LayerNorm folded into the weights,
+ *                 logits[s][e] = (x[s] . wx[e] - mean_s * wsum[e]) * rstd_s + bias[e] + eall[s][e],
+ *                 (wx [num_expert][idim] = w * gamma, wsum[e] = sum_k wx[e][k], bias = w . beta (+ router bias), may be NULL;
+ *                 eall [S][ld_e] = the embed half, may be NULL), then SoftmaxTopK + ScatterMapping, in one single-work-group
+ *                 launch.  1 <= S <= 256, num_expert 16 / 32 / 64, idim a multiple of 16, ldx >= idim a multiple of 4,
+ *                 ld_e >= num_expert; x / wx 16-byte aligned. */
+int m3_moe_route(const float* x, int ldx, int idim, const float* wx, const float* wsum, const float* bias, const float* eall,
+                 int ld_e, float ln_eps, const int32_t* row_len, int rows_per_batch, int S, int num_expert, int32_t* gate_idx,
+                 float* gate_value, int32_t* mapping, int32_t* acc_histogram, int32_t* pos, m3_stream stream);
+/*   m3_moe_route_expert_ffn: SoftmaxTopK + ScatterMapping + the grouped fp32 expert FFN (+ b2) in one launch, then the
+ *                 combine on rows that stayed at their original index:
+ *                   y[s] = LayerNorm( resid[s] + alpha * gate_value[s] * (SiLU(xn[s] W1[g]^T + b1[g]) W2[g]^T + b2[g]) ),  g = gate_idx[s],
+ *                 rows with gate_idx < 0 contribute 0.  xn = x, or LayerNorm(x; norm_gamma, norm_beta, norm_eps) applied while
+ *                 the rows are gathered when norm_gamma != NULL.  use_gate_value = 0: the factor gate_value[s] is left out (the
+ *                 tap is written all the same).  resid / ln_gamma / ln_beta may be NULL.  Weights as m3_moe_expert_ffn;
+ *                 w2_sliced = 1: w2 is slice-major [E][F / slice][D][slice] (m3_moe_expert_slice).  1 <= S <= 256, num_expert
+ *                 8 / 16 / 32 / 64, idim a multiple of 16 (<= 2048; with S > 64 the row tile must fit the LDS), hidden_units a
+ *                 multiple of the slice, ldx >= idim a multiple of 4; x / logits 16-byte aligned.  workspace: the partial
+ *                 results, m3_moe_route_expert_workspace_size bytes (0 for a shape the operator does not take). */
+size_t m3_moe_route_expert_workspace_size(int S, int num_expert, int idim, int hidden_units);
+int m3_moe_route_expert_ffn(const float* x, int ldx, const float* logits, const int32_t* row_len, int rows_per_batch,
+                            const float* w1, const float* b1, const float* w2, int w2_sliced, const float* b2, int S,
+                            int num_expert, int idim, int hidden_units, const float* norm_gamma, const float* norm_beta,
+                            float norm_eps, int use_gate_value, const float* resid, float alpha, const float* ln_gamma,
+                            const float* ln_beta, float ln_eps, int32_t* gate_idx, float* gate_value, int32_t* mapping,
+                            int32_t* acc_histogram, int32_t* pos, float* y, void* workspace, size_t workspace_bytes,
+                            m3_stream stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Dense building blocks (TensorRT-native layers of the reference + the small plugins).

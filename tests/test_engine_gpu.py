@@ -431,3 +431,35 @@ def test_front_and_back_end_cmvn_prior_logsoftmax(tmp_path):
         assert p16["out_linear.ln.bias"].dtype == torch.float32 and p16["cmvn.mean"].dtype == torch.float32
         out16 = Engine(c16, p16)(feat.cuda(), fl.cuda()).cpu()
         assert float((out16 - want).abs()[valid].max()) < 5e-2 * float(want.abs()[valid].max())
+
+
+@pytest.mark.parametrize("T", [206, 1027])       # T' = 50, and 256: the largest S the self-routing expert launch takes
+def test_engine_one_expert_takes_every_frame(T):
+    """B = 1 fp32 with every router weight zeroed and a bias of +50 on one expert: each layer's expert work-groups walk all T'
+    rows tile after tile (4 tiles of 16 rows at T' = 50, 8 of 32 at T' = 256), where make_weights' own routers give an expert
+    about 2 rows.  The expert stage must be the self-routing launch (no separate top-1 / index stage in the block), so the
+    case cannot silently move to another form."""
+    cfg = EncoderConfig(num_blocks=2, embed_blocks=1, router_with_bias=True)
+    w = make_weights(cfg, seed=17)
+    for i in range(cfg.num_blocks):
+        w["blocks.%d.feed_forward.router_weights" % i].zero_()
+        b = torch.zeros(cfg.num_experts)
+        b[(5 + 11 * i) % cfg.num_experts] = 50.0
+        w["blocks.%d.feed_forward.router_bias" % i] = b
+    feat = torch.rand(1, T, cfg.input_dim, generator=torch.Generator().manual_seed(T))
+    fl = torch.tensor([T], dtype=torch.int32)
+    want = encoder_forward(w, cfg, feat, fl)
+    eng, out = _run(cfg, w, feat, fl, debug_taps=True)
+    Tp = int(sub_len(fl.long())[0])
+    assert Tp == {206: 50, 1027: 256}[T] and out.shape[1] == Tp
+    err = _check(out, want, [Tp])
+    print("one expert takes every frame, T' = %d: max abs err %.3e (bound %g + %g |ref|)" % (Tp, err, ATOL, RTOL))
+    info = {s["name"]: s for s in eng.stage_info()}
+    for i in range(cfg.num_blocks):
+        p = "blocks.%d." % i
+        assert info[p + "moe_local.expert"]["kernel"] == "expert_ffn_f32_kernel" and info[p + "moe_local.expert"]["launches"] == 1
+        assert not any(p + n in info for n in ("moe_route", "moe_gate_index", "moe_top1", "moe_local.index")), sorted(info)
+        gi = eng.buffer(p + "gate_idx", torch.int32).cpu()
+        assert bool((gi == (5 + 11 * i) % cfg.num_experts).all())
+        acc = eng.buffer(p + "acc_histogram", torch.int32).cpu().tolist()
+        assert acc[-1] == Tp and sorted(set(np.diff(acc).tolist())) == [0, Tp]
