@@ -2,6 +2,8 @@
 // (include/m3asr.h documents which reference interface each one replaces).
 #include <string.h>
 
+#include <vector>
+
 #include "../../include/m3asr.h"
 #include "common.h"
 #include "kernels.h"
@@ -513,6 +515,48 @@ int m3_pad2d(const float* x, size_t outer, int H, int W, int pre_h, int post_h, 
 int m3_depthwise_conv1d(const float* x, const float* w, const float* bias, int B, int C, int T, int K, int pad,
                         float* y, m3_stream stream) {
   return launch_depthwise_conv1d_nct(x, w, bias, B, C, T, K, pad, y, (hipStream_t)stream);
+}
+
+static int fbank_options_ok(int num_mel_bins, float sample_rate, float low_freq, float high_freq) {
+  M3_REQUIRE(num_mel_bins >= 1 && num_mel_bins <= 128, "fbank: num_mel_bins=%d outside [1, 128]", num_mel_bins);
+  M3_REQUIRE(sample_rate == 16000.f, "fbank: sample_rate=%g (only 16000 Hz)", sample_rate);
+  M3_REQUIRE(low_freq >= 0.f && low_freq < high_freq && high_freq <= 0.5f * sample_rate,
+             "fbank: need 0 <= low_freq=%g < high_freq=%g <= %g", low_freq, high_freq, 0.5f * sample_rate);
+  return 0;
+}
+size_t m3_fbank_tables_bytes(int num_mel_bins) {
+  if (num_mel_bins < 1 || num_mel_bins > 128) {
+    set_error("fbank: num_mel_bins=%d outside [1, 128]", num_mel_bins);
+    return 0;
+  }
+  return fbank_tables_bytes();
+}
+int m3_fbank_tables_host(int num_mel_bins, float sample_rate, float low_freq, float high_freq, void* host_tables) {
+  M3_REQUIRE(host_tables != nullptr, "fbank_tables_host: null pointer");
+  if (int rc = fbank_options_ok(num_mel_bins, sample_rate, low_freq, high_freq)) return rc;
+  return fbank_tables_build(num_mel_bins, sample_rate, low_freq, high_freq, host_tables);
+}
+int m3_fbank_tables_init(int num_mel_bins, float sample_rate, float low_freq, float high_freq, void* tables, m3_stream stream) {
+  M3_REQUIRE(tables != nullptr && aligned16(tables), "fbank_tables_init: tables must be non-null and 16-byte aligned");
+  if (int rc = fbank_options_ok(num_mel_bins, sample_rate, low_freq, high_freq)) return rc;
+  std::vector<char> image(fbank_tables_bytes());
+  if (int rc = fbank_tables_build(num_mel_bins, sample_rate, low_freq, high_freq, image.data())) return rc;
+  M3_CHECK_HIP(hipMemcpyAsync(tables, image.data(), image.size(), hipMemcpyHostToDevice, (hipStream_t)stream));
+  M3_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));     // the host image dies with this call
+  return 0;
+}
+int m3_fbank_num_frames(int n_samples) { return n_samples < 400 ? 0 : 1 + (n_samples - 400) / 160; }
+int m3_fbank(const void* tables, const void* pcm, int pcm_is_int16, int ld_pcm, const int32_t* n_samples, int B, int T,
+             int num_mel_bins, float* feat, int ld_feat, int32_t* feat_len_out, m3_stream stream) {
+  M3_REQUIRE(tables && pcm && n_samples && feat && feat_len_out, "fbank: null pointer");
+  M3_REQUIRE(num_mel_bins >= 1 && num_mel_bins <= 128, "fbank: num_mel_bins=%d outside [1, 128]", num_mel_bins);
+  M3_REQUIRE(B >= 0 && T >= 1, "fbank: bad sizes B=%d T=%d", B, T);
+  M3_REQUIRE(ld_feat >= num_mel_bins, "fbank: ld_feat=%d is shorter than a row of %d", ld_feat, num_mel_bins);
+  const int per16 = pcm_is_int16 ? 8 : 4;
+  M3_REQUIRE(ld_pcm >= 0 && ld_pcm % per16 == 0, "fbank: ld_pcm=%d must be a multiple of %d samples (16 bytes)", ld_pcm, per16);
+  M3_REQUIRE(aligned16(tables) && aligned16(pcm), "fbank: tables / pcm must be 16-byte aligned");
+  return launch_fbank(tables, pcm, pcm_is_int16, ld_pcm, n_samples, B, T, num_mel_bins, feat, ld_feat, feat_len_out,
+                      (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -335,4 +335,10 @@ int launch_rel_positional_encoding(const float* x, const float* pe, int pe_len, 
 int launch_depthwise_conv1d_nct(const float* x, const float* w, const float* bias, int B, int C, int T, int K,
                                 int pad, float* y, hipStream_t stream);
 
+// fbank.hip: Kaldi-style log-Mel filter bank, samples -> feature frames
+size_t fbank_tables_bytes();
+int fbank_tables_build(int num_mel_bins, double sample_rate, double low_freq, double high_freq, void* host_image);
+int launch_fbank(const void* tables, const void* pcm, int pcm_is_int16, int ld_pcm, const int32_t* n_samples, int B, int T,
+                 int num_mel_bins, float* feat, int ld_feat, int32_t* feat_len, hipStream_t stream);
+
 }  // namespace m3

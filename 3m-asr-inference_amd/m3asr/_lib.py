@@ -192,6 +192,11 @@ SIGNATURES = {
     "m3_engine_stage_info": (_i, [_vp, _i, _vp]),
     "m3_ep_send_map": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "m3_ep_recv_gate": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "m3_fbank_tables_bytes": (_sz, [_i]),
+    "m3_fbank_tables_host": (_i, [_i, _f, _f, _f, _vp]),
+    "m3_fbank_tables_init": (_i, [_i, _f, _f, _f, _vp, _vp]),
+    "m3_fbank_num_frames": (_i, [_i]),
+    "m3_fbank": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
 }
 
 _lib = None

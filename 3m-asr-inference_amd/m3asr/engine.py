@@ -184,6 +184,26 @@ class Engine:
         self.stream.synchronize()
         return out
 
+    def infer_audio(self, pcm, n_samples=None):
+        """infer() from samples: pcm (B, N) or (N,) 16 kHz mono, int16 or float32 in the int16 value range, n_samples (B,) real
+        samples per row (default N).  The log-Mel front end (m3asr.frontend.Fbank for cfg.input_dim, one launch on the engine
+        stream) writes the (B, T = num_frames(N)) shape's static input buffers directly, then that shape's graph is replayed
+        exactly as infer() does after its copy.  Returns the shape's logits buffer, valid until the next call of that shape."""
+        from .frontend import Fbank, num_frames
+        if getattr(self, "_fbank", None) is None:
+            self._fbank = Fbank(self.cfg.input_dim, self.device)
+        pcm = torch.as_tensor(pcm)
+        pcm = pcm.unsqueeze(0) if pcm.dim() == 1 else pcm
+        B, T = int(pcm.shape[0]), num_frames(pcm.shape[1])
+        f, l, out = self._lru(self._static, (B, T), lambda: (
+            torch.empty(B, T, self.cfg.input_dim, dtype=torch.float32, device=self.device),
+            torch.empty(1, B, dtype=torch.int32, device=self.device),
+            torch.empty(self.output_shape(B, T), dtype=torch.float32, device=self.device)))
+        self._fbank(pcm, n_samples, out=f, out_len=l, stream=self.stream)
+        self.forward(f, l, out, use_graph=True)
+        self.stream.synchronize()
+        return out
+
     def num_captures(self):
         return self.lib.m3_engine_num_captures(self.handle)
 

@@ -12,6 +12,11 @@ live and every other slot idle.
     best, greedy = pool.partial(sid)
     nbest = pool.close(sid)                 # frees the slot
 
+Audio mode, `StreamPool(decoder, audio=True)`: sessions push SAMPLES (`pool.push_audio(sid, pcm)`, 16 kHz mono, int16 or
+float32 in the int16 range).  step() gathers the live slots' sample windows into one pinned int16 buffer, uploads it once and
+runs the log-Mel front end (m3asr.frontend.Fbank, one launch on the engine stream) straight into the encoder's window
+buffer; the chunk itself is the same graph replay as in feature mode.
+
 The window rule is the one StreamingEncoder.decode applies to whole utterances (window n of a stream starts at its input
 frame 4 c n, holds 4 c + 3 frames, overlaps the next by 3; fewer than 7 real frames count as none).  It lives in
 `next_window_valid` / `WindowBuffer`, host-only code.
@@ -88,9 +93,11 @@ class StreamPool:
 
     decoder: a StreamingCtcDecoder over a slot-mode StreamingEncoder, or any object with `step(window (B, 4c+3, idim), valid
     (B,))`, `reset(slots=[...])`, `partial(slots=[...])`, `finish(slots=[...])`; B, chunk and input_dim are read from
-    `decoder.st` unless given."""
+    `decoder.st` unless given.  audio=True: the sessions are fed samples (push_audio) and step() featurises them on the device;
+    fbank: the front end, `fbank(pcm (B, n) int16, n_samples (B,), out=, out_len=, stream=)` (default: an
+    m3asr.frontend.Fbank for input_dim on the engine's device)."""
 
-    def __init__(self, decoder, B=None, chunk=None, input_dim=None):
+    def __init__(self, decoder, B=None, chunk=None, input_dim=None, audio=False, fbank=None):
         self.dec = decoder
         st = getattr(decoder, "st", None)
         if st is not None and not getattr(st, "independent", False):
@@ -104,6 +111,26 @@ class StreamPool:
         self.next_sid = 0
         self.win = torch.zeros(self.B, self.window, self.idim)
         self.steps = 0
+        self.audio = bool(audio)
+        if self.audio:
+            self._init_audio(st, fbank)
+
+    def _init_audio(self, st, fbank):
+        from .frontend import AudioWindowBuffer, Fbank
+        self._new_audio_buffer = lambda: AudioWindowBuffer(self.c)
+        eng = getattr(st, "eng", None)
+        self.fbank = fbank if fbank is not None else Fbank(self.idim, eng.device)
+        self.stream = eng.stream if eng is not None else None
+        dev = eng.device if eng is not None else torch.device("cpu")
+        pin = dev.type == "cuda"
+        self.window_samples = self._new_audio_buffer().window
+        self.pcm_win = torch.zeros(self.B, self.window_samples, dtype=torch.int16, pin_memory=pin)
+        self.n_real = torch.zeros(self.B, dtype=torch.int32, pin_memory=pin)
+        self.pcm_dev = torch.zeros(self.B, self.window_samples, dtype=torch.int16, device=dev)
+        self.n_real_dev = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self.feat_len_dev = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self.feat = st.feat if st is not None else self.win      # where the frames land: the encoder's own window buffer
+        self.uploaded = torch.cuda.Event() if pin else None     # the pinned buffers may be refilled once this has passed
 
     def _get(self, sid):
         if sid not in self.streams:
@@ -124,12 +151,20 @@ class StreamPool:
                 sid = self.next_sid
                 self.next_sid += 1
                 self.slot_sid[b] = sid
-                self.streams[sid] = (b, WindowBuffer(self.c, self.idim))
+                self.streams[sid] = (b, self._new_audio_buffer() if self.audio else WindowBuffer(self.c, self.idim))
                 return sid
         raise _lib.M3Error("StreamPool.open: all %d slots are taken" % self.B)
 
     def push(self, sid, frames):
+        if self.audio:
+            raise ValueError("StreamPool.push: this pool is fed samples (audio=True), use push_audio")
         self._get(sid)[1].push(frames)
+
+    def push_audio(self, sid, pcm):
+        """Samples of the stream (16 kHz mono, int16 or float32 in the int16 value range), any number."""
+        if not self.audio:
+            raise ValueError("StreamPool.push_audio: this pool is fed feature frames, build it with audio=True")
+        self._get(sid)[1].push(pcm)
 
     def end(self, sid):
         self._get(sid)[1].end()
@@ -141,6 +176,8 @@ class StreamPool:
     def step(self):
         """ONE engine call: every stream with a full window buffered (or ended with >= 7 frames left) moves one chunk, every
         other slot is idle.  -> the sids that were live (no call at all when there is none)."""
+        if self.audio:
+            return self._step_audio()
         valid = torch.zeros(self.B, dtype=torch.int32)
         live = []
         for sid, (b, wb) in self.streams.items():
@@ -151,6 +188,36 @@ class StreamPool:
         if live:
             self.dec.step(self.win, valid)
             self.steps += 1
+        return live
+
+    def _step_audio(self):
+        """step() of a pool fed samples: one small int16 upload, one front-end launch into the encoder's window buffer, then
+        the chunk.  An idle slot has 0 samples: its rows of the window buffer are zeroed and its `valid` is 0."""
+        if self.uploaded is not None:
+            self.uploaded.synchronize()
+        valid = torch.zeros(self.B, dtype=torch.int32)
+        self.n_real.zero_()
+        live = []
+        for sid, (b, ab) in self.streams.items():
+            v = ab.ready()
+            if v > 0:
+                _, n = ab.take(out=self.pcm_win[b])
+                self.n_real[b] = n
+                valid[b] = v
+                live.append(sid)
+        if not live:
+            return live
+        if self.stream is not None:
+            with torch.cuda.stream(self.stream):
+                self.pcm_dev.copy_(self.pcm_win, non_blocking=True)
+                self.n_real_dev.copy_(self.n_real, non_blocking=True)
+                self.uploaded.record(self.stream)
+        else:
+            self.pcm_dev.copy_(self.pcm_win)
+            self.n_real_dev.copy_(self.n_real)
+        self.fbank(self.pcm_dev, self.n_real_dev, out=self.feat, out_len=self.feat_len_dev, stream=self.stream)
+        self.dec.step(self.feat, valid)
+        self.steps += 1
         return live
 
     def partial(self, sid):

@@ -634,6 +634,32 @@ typedef struct m3_stage_info {
 } m3_stage_info;
 int m3_engine_stage_info(const m3_engine* engine, int index, m3_stage_info* info);
 
+/* Audio in: Kaldi-style log-Mel filter bank on the device (csrc/fbank.hip) -- compute-fbank-feats with the
+ * options of a served model.  Mono PCM at 16 kHz, int16 or float32 in the int16 value range (no scaling to +-1); frames of
+ * 400 samples every 160, snip_edges: m3_fbank_num_frames(n) = 0 for n < 400, else 1 + (n - 400) / 160, frame k reads samples
+ * [160 k, 160 k + 400).  Per frame: subtract the mean, pre-emphasis 0.97, Povey window, zero-pad to 512, power spectrum of bins
+ * 0..255, num_mel_bins triangles equally spaced on mel(f) = 1127 ln(1 + f / 700) between low_freq and high_freq with weights
+ * taken in the mel domain (both edges open), log(max(E, FLT_EPSILON)).  No dither, no energy column, no CMVN.
+ * Tables (FFT twiddles, window, mel weights) are built on the HOST in float64 and rounded once to float32; the kernel calls
+ * no sincos / pow, so the result does not depend on the device's math library.
+ * m3_fbank_tables_bytes: size of the table image, host-only; 0 (and m3_last_error) unless 1 <= num_mel_bins <= 128.
+ * m3_fbank_tables_host: builds the image into HOST memory of that size (host-only, needs no device).  sample_rate must be
+ *   16000, 0 <= low_freq < high_freq <= sample_rate / 2.
+ * m3_fbank_tables_init: builds the same image and uploads it to DEVICE memory `tables` (16-byte aligned) on `stream`; the
+ *   upload has finished when the call returns.
+ * m3_fbank: ONE launch featurises a ragged batch.  pcm (B, ld_pcm) int16 (pcm_is_int16 != 0) or float32, 16-byte aligned
+ *   with a row stride of whole 16 bytes (ld_pcm a multiple of 8 / 4 samples); n_samples [B] int32 (device) = samples of
+ *   row b, clamped to [0, ld_pcm].  feat (B, T, ld_feat) float32, ld_feat >= num_mel_bins: frames t < feat_len[b] hold the
+ *   features, frames feat_len[b] <= t < T are written as ZEROS, columns >= num_mel_bins are not touched.  feat_len_out [B]
+ *   int32 (device) = min(m3_fbank_num_frames(n_samples[b]), T).  A frame's result depends on its 400 samples only (not on B,
+ *   T, its place in the batch or on which other frames are live) and is the same bits for int16 and float32 input. */
+size_t m3_fbank_tables_bytes(int num_mel_bins);
+int m3_fbank_tables_host(int num_mel_bins, float sample_rate, float low_freq, float high_freq, void* host_tables);
+int m3_fbank_tables_init(int num_mel_bins, float sample_rate, float low_freq, float high_freq, void* tables, m3_stream stream);
+int m3_fbank_num_frames(int n_samples);
+int m3_fbank(const void* tables, const void* pcm, int pcm_is_int16, int ld_pcm, const int32_t* n_samples, int B, int T,
+             int num_mel_bins, float* feat, int ld_feat, int32_t* feat_len_out, m3_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,7 @@
 """Chunk-by-chunk decoding (m3_engine_forward_chunk) timed: latency of one chunk step and the real-time factor it implies.
 
   python tools/bench_streaming.py [--chunk 16] [--left-chunks 4] [--batch 1] [--weight-dtype f32] [--seconds 20] [--beam N]
-                                  [--independent [--stagger N]]
+                                  [--independent [--stagger N]] [--audio]
 
 18L x 32e encoder with causal conv modules in both encoders, static_chunk_size = chunk (output frames; one chunk = 4 x chunk
 input frames of 10 ms), synthetic weights and features.  Every step after the first is a hipGraph replay (the chunk counter
@@ -13,6 +13,10 @@ on the engine stream behind the chunk forward) and add "decode_ms_per_chunk" to 
 --independent: slot mode (m3_engine_forward_chunk_slots), every stream with its own position; --stagger N: stream b starts N
 steps after stream b - 1 and ends as many steps later (idle slots before and after).  The line then also carries "mode" and
 the mean number of live slots per timed step.
+--audio: time the same chunks fed SAMPLES as well: per step one pinned int16 window per stream ((4 chunk + 2) * 160 + 400
+samples) is uploaded and the log-Mel front end (m3asr.frontend.Fbank, one launch) writes the encoder's window buffer before
+the chunk runs.  Adds "audio_ms_per_chunk" (upload + front end + chunk) next to the feature-fed "ms_per_chunk", and
+"frontend_ms_per_chunk" (upload + front end alone).
 """
 import argparse
 import json
@@ -42,6 +46,7 @@ def main():
     ap.add_argument("--beam", type=int, default=0, help="> 0: decode every chunk with a prefix beam search of this width")
     ap.add_argument("--independent", action="store_true", help="slot mode: every stream has its own chunk counter")
     ap.add_argument("--stagger", type=int, default=0, help="slot mode: stream b starts this many steps after stream b - 1")
+    ap.add_argument("--audio", action="store_true", help="also time the chunks fed samples through the log-Mel front end")
     args = ap.parse_args()
     if args.stagger and not args.independent:
         ap.error("--stagger needs --independent")
@@ -103,6 +108,36 @@ def main():
            "mode": "slots" if args.independent else "lockstep", "mean_live_slots": round(float(np.mean(live)), 3)}
     if args.stagger:
         out["stagger_steps"] = args.stagger
+    if args.audio:
+        from m3asr.frontend import AudioWindowBuffer, Fbank
+        fb = Fbank(cfg.input_dim, eng.device)
+        n_win = AudioWindowBuffer(args.chunk).window
+        host = torch.from_numpy(rng.integers(-3000, 3000, (args.batch, n_win), dtype=np.int16)).pin_memory()
+        pcm = torch.zeros(args.batch, n_win, dtype=torch.int16, device=eng.device)
+        n_real = torch.full((args.batch,), n_win, dtype=torch.int32, device=eng.device)
+        flen = torch.zeros(args.batch, dtype=torch.int32, device=eng.device)
+        full = torch.full((args.batch,), st.window, dtype=torch.int32, device=eng.device)
+        atimes, ftimes = [], []
+        for rep in range(3):
+            st.reset()
+            for n in range(n_chunks):
+                e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+                e0.record(eng.stream)
+                with torch.cuda.stream(eng.stream):
+                    pcm.copy_(host, non_blocking=True)
+                fb(pcm, n_real, out=st.feat, out_len=flen, stream=eng.stream)
+                e1.record(eng.stream)
+                st.step(st.feat, full)
+                e2.record(eng.stream)
+                e2.synchronize()
+                if rep > 0:
+                    ftimes.append(e0.elapsed_time(e1))
+                    atimes.append(e0.elapsed_time(e2))
+        a, f = np.sort(np.array(atimes)), np.sort(np.array(ftimes))
+        out["audio_ms_per_chunk"] = {"p50": round(float(np.median(a)), 4), "p99": round(float(a[int(0.99 * (len(a) - 1))]), 4),
+                                     "min": round(float(a[0]), 4), "n": len(a)}
+        out["frontend_ms_per_chunk"] = {"p50": round(float(np.median(f)), 4), "min": round(float(f[0]), 4),
+                                        "samples_per_window": n_win}
     if dec is not None:
         d = np.sort(np.array(dtimes))
         out["decode_ms_per_chunk"] = {"beam": args.beam, "p50": round(float(np.median(d)), 4),
