@@ -314,28 +314,21 @@ static int linear_pointers(const m3_linear_desc* d) {
 const char* m3_linear_kernel(const m3_linear_desc* d, int with_workspace) {
   GemmParams p;
   if (linear_params(d, &p)) return nullptr;
-  return gemm_kernel_label(p, with_workspace && gemm_f32_splitk_plan(p, nullptr) >= 2);
+  const GemmPlan plan = plan_gemm(p, with_workspace ? SIZE_MAX : 0);
+  if (plan.launches == 0) set_error("%s", plan.reason);
+  return plan.launches ? plan.label : nullptr;
 }
-int m3_linear(const m3_linear_desc* d, m3_stream stream) {
-  GemmParams p;
-  if (int rc = linear_params(d, &p)) return rc;
-  if (int rc = linear_pointers(d)) return rc;
-  return launch_gemm_f32(p, (hipStream_t)stream);
-}
+int m3_linear(const m3_linear_desc* d, m3_stream stream) { return m3_linear_ws(d, nullptr, 0, stream); }
 size_t m3_linear_workspace_size(const m3_linear_desc* d) {
   GemmParams p;
-  size_t need = 0;
-  if (linear_params(d, &p) == 0) gemm_f32_splitk_plan(p, &need);
-  return need;
+  return linear_params(d, &p) == 0 ? plan_gemm(p, SIZE_MAX).ws_bytes : 0;
 }
+// (a missing or too-small workspace: the plan is the one-launch form)
 int m3_linear_ws(const m3_linear_desc* d, void* workspace, size_t workspace_bytes, m3_stream stream) {
   GemmParams p;
   if (int rc = linear_params(d, &p)) return rc;
   if (int rc = linear_pointers(d)) return rc;
-  size_t need = 0;
-  if (gemm_f32_splitk_plan(p, &need) >= 2 && workspace != nullptr && workspace_bytes >= need)
-    return launch_gemm_f32_splitk(p, (float*)workspace, workspace_bytes, (hipStream_t)stream);
-  return launch_gemm_f32(p, (hipStream_t)stream);
+  return launch_gemm(plan_gemm(p, workspace != nullptr ? workspace_bytes : 0), p, (float*)workspace, (hipStream_t)stream);
 }
 
 int m3_layer_norm(const float* x, const float* gamma, const float* beta, float eps, float* y, int rows, int dim,
@@ -407,7 +400,7 @@ int m3_conv2d_3x3s2(const float* in, const float* w, const float* bias, int B, i
   p.W = w; p.bias = bias; p.Y = out; p.ldy = C;
   p.M = B * p.conv_T2 * p.conv_F2; p.N = C; p.K = 9 * C;
   p.act = act;
-  return launch_gemm_f32(p, (hipStream_t)stream);
+  return launch_gemm(plan_gemm(p, 0), p, nullptr, (hipStream_t)stream);
 }
 
 int m3_att_masked_softmax(const float* scores, const int32_t* len, int B, int H, int T1, int T2, float scale,

@@ -54,7 +54,7 @@ struct BlockW {
 
 struct SubW { const float* c1w; const float* c1b; const float* c2w; const float* c2b; Lin out; };
 
-// what horizontal fusion pairs up (fuse_independent_pairs): a plain launch_gemm_f32 stage (Stage::gemm), the conv module's
+// what horizontal fusion pairs up (fuse_independent_pairs): a one-launch dense GEMM stage (Stage::gemm + its plan), the conv module's
 // depthwise conv + LayerNorm + SiLU (Stage::dw), the fp32 rel-pos attention core (Stage::att)
 enum class FuseKind { None, Gemm, Dwconv, Attention };
 
@@ -64,7 +64,7 @@ struct Stage {
   m3_stage_info info;   // kernel label + algorithmic bytes / FLOPs of the stage (m3_engine_stage_info)
   bool reads_embed = false;   // reads the embed encoder's output (pl.emb, or pl.eall computed from it): where the chains join
   FuseKind fuse_kind = FuseKind::None;
-  GemmParams gemm;
+  GemmParams gemm; GemmPlan gemm_plan;
   DwArgs dw;
   AttArgs att;
 };
@@ -419,10 +419,10 @@ Plan make_plan(const m3_engine_config& c, void* base, int B, int T, int ep_capac
     if (c.weight_dtype == M3_F32) {
       GemmParams g;   // conv2 as implicit GEMM
       g.mode = GEMM_A_CONV3X3S2; g.lda = 4; g.conv_C = D; g.M = S * F2; g.N = D; g.K = 9 * D; g.ldy = D;
-      gemm_f32_splitk_plan(g, &n1);
+      n1 = plan_gemm(g, SIZE_MAX).ws_bytes;
       GemmParams l;   // Linear(C*F2 -> D)
       l.lda = F2 * D; l.M = S; l.N = D; l.K = F2 * D; l.ldy = D;
-      gemm_f32_splitk_plan(l, &n2);
+      n2 = plan_gemm(l, SIZE_MAX).ws_bytes;
     }
     p.splitk_bytes = n1 > n2 ? n1 : n2;
     p.splitk = p.splitk_bytes ? cv.take<float>(p.splitk_bytes / sizeof(float)) : nullptr;
@@ -587,7 +587,7 @@ static void add_stage(StageBuilder& sb, const std::string& name, int kernels, st
 }
 
 // algorithmic traffic of one GEMM: weights once, A rows once, result once (+ the residual it adds, + side outputs)
-static m3_stage_info gemm_info(const GemmParams& p, bool splitk) {
+static m3_stage_info gemm_info(const GemmParams& p, const GemmPlan& plan) {
   const bool glu = p.act == ACT_GLU;
   const double M = p.M, N = p.N, K = p.K, Nout = glu ? N / 2 : N;
   const double wsz = p.w_bf16 ? 2 : 4, asz = p.a_bf16 ? 2 : 4, ysz = p.y_bf16 ? 2 : 4;
@@ -598,21 +598,21 @@ static m3_stage_info gemm_info(const GemmParams& p, bool splitk) {
   if (p.resid) bytes += M * Nout * 4;
   if (p.Yb) bytes += M * Nout * 2;
   if (p.ln_out) bytes += M * (K - p.K1) * 4;
-  return stage_info(gemm_kernel_label(p, splitk), 1, bytes, 2.0 * M * N * K, p.mode != GEMM_A_CONV3X3S2);
+  return stage_info(plan.label, 1, bytes, 2.0 * M * N * K, p.mode != GEMM_A_CONV3X3S2);
 }
 
 // fp32_weights: the router GEMMs keep fp32 weights in every mode (a flipped top-1 is a discrete error)
 static void add_gemm(StageBuilder& sb, const std::string& name, GemmParams p, bool fp32_weights = false) {
   p.w_bf16 = (!fp32_weights && sb.eng.cfg.weight_dtype != M3_F32) ? 1 : 0;
-  size_t need = 0;
-  if (gemm_f32_splitk_plan(p, &need) >= 2 && sb.splitk_ws != nullptr && need <= sb.splitk_bytes) {
-    float* ws = sb.splitk_ws; const size_t wsb = sb.splitk_bytes;
-    add_stage(sb, name, 2, [p, ws, wsb](hipStream_t s) { return launch_gemm_f32_splitk(p, ws, wsb, s); }, gemm_info(p, true));
-    return;
+  // planned once, when the shape is bound: the stage runs the plan it captures (a plan no kernel takes fails there, with its reason)
+  float* ws = sb.splitk_ws;
+  const GemmPlan plan = plan_gemm(p, ws != nullptr ? sb.splitk_bytes : 0);
+  add_stage(sb, name, plan.launches ? plan.launches : 1, [plan, p, ws](hipStream_t s) { return launch_gemm(plan, p, ws, s); }, gemm_info(p, plan));
+  if (plan.launches == 1) {
+    sb.bd.stages.back().fuse_kind = FuseKind::Gemm;
+    sb.bd.stages.back().gemm = p;
+    sb.bd.stages.back().gemm_plan = plan;
   }
-  add_stage(sb, name, 1, [p](hipStream_t s) { return launch_gemm_f32(p, s); }, gemm_info(p, false));
-  sb.bd.stages.back().fuse_kind = FuseKind::Gemm;
-  sb.bd.stages.back().gemm = p;
 }
 
 // Horizontal fusion (B = 1-sized fp32 plans): the embed encoder and the main encoder's prefix -- its subsampling and block 0 up to
@@ -623,7 +623,7 @@ static void add_gemm(StageBuilder& sb, const std::string& name, GemmParams p, bo
 // are bit-identical.  M3_HFUSE=0: off.
 static bool stages_fusable(const Stage& a, const Stage& b) {
   if (a.fuse_kind == FuseKind::None || a.fuse_kind != b.fuse_kind) return false;
-  if (a.fuse_kind == FuseKind::Gemm) return gemm_f32_dual_fusable(a.gemm, b.gemm);
+  if (a.fuse_kind == FuseKind::Gemm) return gemm_dual_fusable(a.gemm_plan, b.gemm_plan);
   if (a.fuse_kind == FuseKind::Dwconv) return dwconv_dual_fusable(a.dw, b.dw);
   if (a.fuse_kind == FuseKind::Attention) return relpos_attention_dual_fusable(a.att, b.att);
   return false;
@@ -634,7 +634,8 @@ static Stage fused_stage(const Stage& a, const Stage& b) {
   const char* label = "";
   if (a.fuse_kind == FuseKind::Gemm) {
     const GemmParams pa = a.gemm, pb = b.gemm;
-    d.run = [pa, pb](hipStream_t s) { return launch_gemm_f32_dual(pa, pb, s); };
+    const GemmPlan qa = a.gemm_plan, qb = b.gemm_plan;
+    d.run = [qa, pa, qb, pb](hipStream_t s) { return launch_gemm_f32_dual(qa, pa, qb, pb, s); };
     label = "gemm_f32_dual_kernel";
   } else if (a.fuse_kind == FuseKind::Dwconv) {
     const DwArgs pa = a.dw, pb = b.dw;
@@ -1233,12 +1234,12 @@ static int build_binding(m3_engine* e, const BindKey& k, m3_engine::Bound& bd) {
     GemmParams t;
     t.M = B * Tp; t.N = c.attention_dim; t.K = c.attention_dim; t.w_bf16 = 1;
     bd.a16 = c.weight_dtype != M3_F32 && c.bf16_activations >= 0 && !c.debug_taps && c.embed_dim == c.attention_dim &&
-             (c.embed_linear_units % 128) == 0 && (c.hidden_units % 128) == 0 && gemm_bf16w_uses_tiled(t);
+             (c.embed_linear_units % 128) == 0 && (c.hidden_units % 128) == 0 && plan_gemm(t, 0).kernel == GemmKernel::TiledBf16;
   }
   {
     GemmParams t;     // the narrowest block GEMM as the LDS-DMA kernel would see it
     t.M = B * Tp; t.N = c.attention_dim; t.K = c.attention_dim; t.lda = c.attention_dim; t.w_bf16 = 1; t.a_bf16 = 1;
-    bd.dma = bd.a16 && c.attention_dim == 128 * kXbStatParts && gemm_bf16w_uses_dma(t);
+    bd.dma = bd.a16 && c.attention_dim == 128 * kXbStatParts && plan_gemm(t, 0).kernel == GemmKernel::DmaBf16;
   }
   bd.packed = use_packed_rows(c, B);
   if (streaming) {   // a chunk is a few rows per utterance: padded layout, fp32 activations (the 16-bit modes keep their bf16 weights)
@@ -1290,7 +1291,7 @@ static int build_binding(m3_engine* e, const BindKey& k, m3_engine::Bound& bd) {
         pf = std::shared_ptr<float>(dev, [](float* q) { (void)hipFree(q); });
         pp.Y = dev;
         pp.w_bf16 = c.weight_dtype != M3_F32;
-        if (int rc = launch_gemm_f32(pp, nullptr)) return rc;
+        if (int rc = launch_gemm(plan_gemm(pp, 0), pp, nullptr, nullptr)) return rc;
         M3_CHECK_HIP(hipStreamSynchronize(nullptr));
         // (nothing below can fail: from here on the engine may change)
         for (auto it = e->pfold_by_tp.begin(); it != e->pfold_by_tp.end();)      // tables no binding holds any more

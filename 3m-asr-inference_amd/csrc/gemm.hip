@@ -29,9 +29,8 @@
 //    the A fragments already in registers, so LayerNorm costs no extra memory round trip and no barrier.
 //  * LN_PRO (generic m3_linear with gamma / beta): statistics (two-pass) + affine applied to the A
 //    fragments before the MFMAs; can also write the normalised rows out (ln_out).
-#include <stdlib.h>
-
 #include "common.h"
+#include "gemm_epilogue.h"
 #include "kernels.h"
 
 // -DM3_GEMM_DIAG: phase stamps (s_memtime) of every work-group of gemm_f32_kernel into a debug buffer (tools/diag_gemm_f32.py)
@@ -45,15 +44,7 @@ namespace m3 {
 
 M3_GDIAG(__device__ unsigned long long g_gemm_dbg[2048 * 8];)
 
-// K-steps per in-flight load group: 2 buffers x G x (NT + MT) float4 must fit the per-lane register
-// budget (512 VGPR+AGPR for 4 waves, 256 for 8, 128 for 16 waves per workgroup) without spilling.
-constexpr int gemm_group_steps(int MT, int NT, int NW) {
-  if (NW == 16) return MT == 1 ? (NT == 1 ? 4 : 2) : (MT == 2 ? 2 : 1);
-  if (NW == 8) return MT == 1 ? 8 : (MT == 2 ? (NT == 1 ? 6 : 4) : (NT == 1 ? 3 : 2));
-  return MT == 1 ? 8 : (MT == 2 ? 6 : 4);
-}
-
-enum { LN_NONE = 0, LN_EPI = 1, LN_PRO = 2 };
+enum { LN_NONE = GEMM_LN_NONE, LN_EPI = GEMM_LN_EPI, LN_PRO = GEMM_LN_PRO };
 
 // NW = waves per workgroup = K-split factor (4 / 8 / 16 for K ~ 512 / 1024 / >= 2048).
 // NBUF = 1 when a wave's share of K fits one load group (K <= 16*NW*G: every block GEMM of the model): half the
@@ -215,7 +206,7 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int m = min(m0 + 16 * ep_mt + 4 * kq + r, p.M - 1);
-      pad4[r] = (m % p.rows_per_batch) >= p.row_len[m / p.rows_per_batch];
+      pad4[r] = gemm_row_padded(p, m);
     }
   }
 
@@ -394,6 +385,7 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
         float y0 = v[0][r], y1 = v[NT - 1][r];
         const bool pad = pad4[r];
         if (LN != LN_EPI && p.mask_in && pad) y0 = y1 = 0.f;      // zero A row -> zero accumulator
+        float mean = 0.f, rstd = 1.f;
         if (LN == LN_EPI) {
           float t1 = 0.f, t2 = 0.f;
 #pragma unroll
@@ -401,25 +393,10 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
             t1 += rsum[w][row][0];
             t2 += rsum[w][row][1];
           }
-          const float mean = t1 / (float)Kl;
-          const float var = fmaxf(t2 / (float)Kl - mean * mean, 0.f);
-          const float rstd = rsqrtf(var + p.ln_eps);
-          if (p.mask_in && pad) {   // masked_fill(0) after the LayerNorm: the row contributes the plain bias only
-            y0 = -wbeta0;
-            y1 = -wbeta1;
-          } else {
-            y0 = rstd * (y0 - mean * wsum0);
-            y1 = rstd * (y1 - mean * wsum1);
-          }
+          ln_mean_rstd(t1, t2, Kl, p.ln_eps, mean, rstd);
         }
-        float y = y0 + bias0;
-        if (GLU) y = y * sigmoidf(y1 + bias1);
-        if (p.act == ACT_RELU) y = fmaxf(y, 0.f);
-        if (p.act == ACT_SILU) y = silu(y);
-        if (p.mask_out && pad) y = 0.f;
-        y *= p.alpha;
-        if (p.resid) y += res[r];
-        p.Y[(size_t)m * p.ldy + ep_n] = y;
+        p.Y[(size_t)m * p.ldy + ep_n] =
+            gemm_epilogue<GLU, LN == LN_EPI>(y0, y1, bias0, bias1, wsum0, wsum1, wbeta0, wbeta1, mean, rstd, pad, res[r], p);
       }
     }
   }
@@ -449,129 +426,39 @@ __global__ __launch_bounds__(64 * NW) void gemm_f32_dual_kernel(const GemmParams
   }
 }
 
-int launch_gemm_f32_tiled(const GemmParams& p, hipStream_t stream);   // gemm_f32_tiled.hip
-bool gemm_f32_tiled_supports(const GemmParams& p);
-static int f32_tiled_min_rows() {   // below this many rows the K-split kernel fills the chip better (M3_TILED_MIN_ROWS overrides)
-  static const int v = [] {
-    const char* e = getenv("M3_TILED_MIN_ROWS");
-    return e ? atoi(e) : 384;
-  }();
-  return v;
-}
-
-// long batches: LDS-tiled kernel (everything but the affine-LayerNorm / concat router GEMM, whose output is 32 wide)
-// (needs enough 64 x 64 tiles to occupy the chip: below ~160 the K-split kernel's many small workgroups win)
-static bool gemm_f32_uses_tiled(const GemmParams& p) {
-  const bool glu = p.act == ACT_GLU;
-  return p.M >= f32_tiled_min_rows() && (long)cdiv(p.M, 64) * cdiv(glu ? p.N / 2 : p.N, 64) >= 160 && gemm_f32_tiled_supports(p);
-}
-
-// which kernel launch_gemm_f32 / the engine's split-K front end will run for this problem (sizes / mode only)
-const char* gemm_kernel_label(const GemmParams& p, bool splitk) {
-  if (splitk) return "gemm_f32_splitk_kernel";
-  if (p.w_bf16 && gemm_bf16w_uses_dma(p)) return "gemm_bf16_dma_kernel";
-  if (p.w_bf16) return gemm_bf16w_uses_tiled(p) ? "gemm_bf16w_tiled_kernel" : "gemm_bf16w_kernel";
-  return gemm_f32_uses_tiled(p) ? "gemm_f32_tiled_kernel" : "gemm_f32_kernel";
-}
-
-// The instantiation launch_gemm_f32 runs for a problem (skinny fp32 kernel only): what two problems must share to be launched
-// together.  ok = false: not this kernel (bf16 weights, the LDS-tiled form) or not one of the dual instantiations.
-struct GemmVariant { bool ok; int mt, nw, ln; bool glu; };
-static GemmVariant gemm_f32_variant(const GemmParams& p) {
-  GemmVariant v{false, 0, 0, 0, false};
-  if (p.w_bf16 || p.M <= 0 || p.N <= 0 || p.K <= 0 || (p.K & 15) || p.mode != GEMM_A_PLAIN || p.ln_gamma != nullptr || p.m_dev != nullptr) return v;
-  if (gemm_f32_uses_tiled(p)) return v;
-  v.glu = p.act == ACT_GLU;
-  const int Nout = v.glu ? p.N / 2 : p.N;
-  int mt = p.M <= 128 ? 1 : (p.M <= 512 ? 2 : 4);
-  while (mt < 4 && 16 * mt < p.M && (long)cdiv(Nout, 16) * cdiv(p.M, 16 * mt) > 512) mt *= 2;
-  while (mt > 1 && (long)cdiv(Nout, 16) * cdiv(p.M, 16 * mt) < 256) mt /= 2;
-  v.mt = mt;
-  v.nw = p.K >= 2048 ? 16 : (p.K >= 1024 ? 8 : 4);
-  v.ln = p.ln_wsum ? LN_EPI : LN_NONE;
-  // the dual instantiations: 16-row tiles, 4 / 8 waves, one load group per wave (every block GEMM of the model at B = 1)
-  v.ok = mt == 1 && (v.nw == 4 || v.nw == 8) && (p.K >> 4) <= v.nw * gemm_group_steps(1, v.glu ? 2 : 1, v.nw);
-  return v;
-}
-bool gemm_f32_dual_fusable(const GemmParams& a, const GemmParams& b) {
-  const GemmVariant va = gemm_f32_variant(a), vb = gemm_f32_variant(b);
-  return va.ok && vb.ok && va.mt == vb.mt && va.nw == vb.nw && va.ln == vb.ln && va.glu == vb.glu;
-}
-// two independent problems of one instantiation in ONE launch (gemm_f32_dual_fusable must hold; both validated like single launches)
-int launch_gemm_f32_dual(const GemmParams& a_in, const GemmParams& b_in, hipStream_t stream) {
-  M3_REQUIRE(gemm_f32_dual_fusable(a_in, b_in), "gemm dual: the two problems do not share an instantiation");
+// two independent problems of one instantiation in ONE launch (gemm_dual_fusable holds for the two plans)
+int launch_gemm_f32_dual(const GemmPlan& pa, const GemmParams& a_in, const GemmPlan& pb, const GemmParams& b_in, hipStream_t stream) {
+  M3_REQUIRE(gemm_dual_fusable(pa, pb), "gemm dual: the two problems do not share an instantiation");
   GemmParams q[2] = {a_in, b_in};
-  for (GemmParams& p : q) {
-    M3_REQUIRE((p.lda & 3) == 0, "gemm: lda=%d must be a multiple of 4", p.lda);
-    M3_REQUIRE(!(p.act == ACT_GLU) || (p.N & 1) == 0, "gemm: GLU needs even N");
-    M3_REQUIRE(!(p.ln_wsum && p.mask_in) || p.ln_wbeta, "gemm: folded LayerNorm + input mask needs ln_wbeta");
-    if (p.ln_wsum) M3_REQUIRE(p.K <= 1024, "gemm: LayerNorm supports rows up to 1024 wide");
-    if (p.mask_in || p.mask_out) M3_REQUIRE(p.row_len && p.rows_per_batch > 0, "gemm: mask needs row_len");
-    const int Nout = p.act == ACT_GLU ? p.N / 2 : p.N;
-    p.n_tiles = cdiv(Nout, 16);
-    p.m_tiles = cdiv(p.M, 16);
-    p.xcd_swizzle = (p.n_tiles % 8 == 0) ? 1 : 0;
+  const GemmPlan* const plans[2] = {&pa, &pb};
+  for (int i = 0; i < 2; ++i) {
+    q[i].n_tiles = plans[i]->n_tiles; q[i].m_tiles = plans[i]->m_tiles; q[i].xcd_swizzle = plans[i]->xcd_swizzle;
   }
-  const GemmVariant v = gemm_f32_variant(a_in);
   const int n0 = (int)align_up((size_t)q[0].n_tiles * q[0].m_tiles, 8);
   dim3 grid(n0 + q[1].n_tiles * q[1].m_tiles);
 #define M3_DUAL(GLU_, NW_, LN_)                                                                                             \
   hipLaunchKernelGGL((gemm_f32_dual_kernel<1, GLU_, NW_, LN_>), grid, dim3(64 * NW_), 0, stream, q[0], q[1], n0)
-  if (v.glu) {
-    if (v.nw == 8) { if (v.ln == LN_EPI) M3_DUAL(true, 8, LN_EPI); else M3_DUAL(true, 8, LN_NONE); }
-    else { if (v.ln == LN_EPI) M3_DUAL(true, 4, LN_EPI); else M3_DUAL(true, 4, LN_NONE); }
+  if (pa.glu) {
+    if (pa.nw == 8) { if (pa.ln == LN_EPI) M3_DUAL(true, 8, LN_EPI); else M3_DUAL(true, 8, LN_NONE); }
+    else { if (pa.ln == LN_EPI) M3_DUAL(true, 4, LN_EPI); else M3_DUAL(true, 4, LN_NONE); }
   } else {
-    if (v.nw == 8) { if (v.ln == LN_EPI) M3_DUAL(false, 8, LN_EPI); else M3_DUAL(false, 8, LN_NONE); }
-    else { if (v.ln == LN_EPI) M3_DUAL(false, 4, LN_EPI); else M3_DUAL(false, 4, LN_NONE); }
+    if (pa.nw == 8) { if (pa.ln == LN_EPI) M3_DUAL(false, 8, LN_EPI); else M3_DUAL(false, 8, LN_NONE); }
+    else { if (pa.ln == LN_EPI) M3_DUAL(false, 4, LN_EPI); else M3_DUAL(false, 4, LN_NONE); }
   }
 #undef M3_DUAL
   M3_LAUNCH_CHECK();
   return 0;
 }
 
-int launch_gemm_f32(const GemmParams& pin, hipStream_t stream) {
-  if (pin.w_bf16) return launch_gemm_bf16w(pin, stream);
+int launch_gemm_f32_skinny(const GemmPlan& plan, const GemmParams& pin, hipStream_t stream) {
   GemmParams p = pin;
-  M3_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "gemm: empty problem M=%d N=%d K=%d", p.M, p.N, p.K);
-  M3_REQUIRE((p.K & 15) == 0, "gemm: K=%d must be a multiple of 16", p.K);
-  M3_REQUIRE((p.lda & 3) == 0, "gemm: lda=%d must be a multiple of 4", p.lda);
-  const bool glu = p.act == ACT_GLU;
-  M3_REQUIRE(!glu || (p.N & 1) == 0, "gemm: GLU needs even N");
-  const bool conv = p.mode == GEMM_A_CONV3X3S2;
-  if (p.mode == GEMM_A_CONCAT2)
-    M3_REQUIRE((p.K1 & 15) == 0 && p.A2 != nullptr && (p.lda2 & 3) == 0, "gemm: bad concat operands");
-  if (conv) M3_REQUIRE((p.conv_C & 15) == 0 && p.K == 9 * p.conv_C, "gemm: conv mode needs K=9*C, C%%16==0");
-  const int ln = p.ln_wsum ? LN_EPI : (p.ln_gamma ? LN_PRO : LN_NONE);
-  M3_REQUIRE(!(p.ln_wsum && p.ln_gamma), "gemm: folded (ln_wsum) and affine (ln_gamma) LayerNorm are exclusive");
-  if (ln != LN_NONE) {
-    M3_REQUIRE(p.mode == GEMM_A_PLAIN || (p.mode == GEMM_A_CONCAT2 && p.ln_on_a2),
-               "gemm: LayerNorm needs plain A (or the A2 half of a concat)");
-    M3_REQUIRE((p.ln_on_a2 ? p.K - p.K1 : p.K) <= 1024, "gemm: LayerNorm supports rows up to 1024 wide");
-    M3_REQUIRE(p.K <= 2047, "gemm: LayerNorm variants are built for K < 2048");
-  }
-  M3_REQUIRE(!p.ln_on_a2 || p.mode == GEMM_A_CONCAT2, "gemm: ln_on_a2 needs concat mode");
-  M3_REQUIRE(p.ln_out == nullptr || ln == LN_PRO, "gemm: ln_out needs the affine LayerNorm prologue");
-  M3_REQUIRE(!(ln == LN_EPI && p.mask_in) || p.ln_wbeta, "gemm: folded LayerNorm + input mask needs ln_wbeta");
-  if (p.mask_in || p.mask_out) M3_REQUIRE(p.row_len && p.rows_per_batch > 0, "gemm: mask needs row_len");
-  if (gemm_f32_uses_tiled(p)) return launch_gemm_f32_tiled(p, stream);
-  const int Nout = glu ? p.N / 2 : p.N;
-  // row tile: 16*MT rows per workgroup; short inputs are cut into 16-row tiles to fill the chip, but more
-  // workgroups than fit at once (2 per CU) only serialise: then prefer fatter tiles
-  int mt = p.M <= 128 ? 1 : (p.M <= 512 ? 2 : 4);
-  while (mt < 4 && 16 * mt < p.M && (long)cdiv(Nout, 16) * cdiv(p.M, 16 * mt) > 512) mt *= 2;
-  // narrow outputs over many rows (the router: N = 32 experts, S ~ 2000 rows): fat row tiles would leave most CUs idle
-  while (mt > 1 && (long)cdiv(Nout, 16) * cdiv(p.M, 16 * mt) < 256) mt /= 2;
-  p.n_tiles = cdiv(Nout, 16);
-  p.m_tiles = cdiv(p.M, 16 * mt);
-  p.xcd_swizzle = (p.n_tiles % 8 == 0) ? 1 : 0;
+  p.n_tiles = plan.n_tiles; p.m_tiles = plan.m_tiles; p.xcd_swizzle = plan.xcd_swizzle;
   dim3 grid(p.n_tiles * p.m_tiles);
-  int nw = p.K >= 2048 ? 16 : (p.K >= 1024 ? 8 : 4);
-  if (nw == 16 && (glu || mt == 4)) nw = 8;   // those 16-wave variants would spill registers
-  if (nw == 16 && ln != LN_NONE) nw = 8;
+  const int mt = plan.mt, nw = plan.nw, ln = plan.ln;
 
 #define M3_GEMM_LAUNCH(MT_, GLU_, NW_, CONV_, LN_)                                                              \
   do {                                                                                                          \
-    if ((p.K >> 4) <= NW_ * gemm_group_steps(MT_, GLU_ ? 2 : 1, NW_))                                           \
+    if (plan.nbuf == 1)                                                                                         \
       hipLaunchKernelGGL((gemm_f32_kernel<MT_, GLU_, NW_, CONV_, LN_, 1>), grid, dim3(64 * NW_), 0, stream, p); \
     else                                                                                                        \
       hipLaunchKernelGGL((gemm_f32_kernel<MT_, GLU_, NW_, CONV_, LN_, 2>), grid, dim3(64 * NW_), 0, stream, p); \
@@ -588,13 +475,12 @@ int launch_gemm_f32(const GemmParams& pin, hipStream_t stream) {
     else if (ln == LN_PRO) M3_GEMM_MT(GLU_, NW_, false, LN_PRO);                                       \
     else M3_GEMM_MT(GLU_, NW_, false, LN_NONE);                                                        \
   } while (0)
-  if (conv) {                       // implicit 3x3 conv: no GLU, no LayerNorm
-    M3_REQUIRE(!glu && ln == LN_NONE, "gemm: conv mode supports neither GLU nor LayerNorm");
+  if (plan.conv) {                  // implicit 3x3 conv: no GLU, no LayerNorm
     if (nw == 16) M3_GEMM_MT(false, 16, true, LN_NONE); else if (nw == 8) M3_GEMM_MT(false, 8, true, LN_NONE);
     else M3_GEMM_MT(false, 4, true, LN_NONE);
   } else if (nw == 16) {            // K >= 2048: plain only
     M3_GEMM_MT(false, 16, false, LN_NONE);
-  } else if (glu) {
+  } else if (plan.glu) {
     if (nw == 8) M3_GEMM_LN(true, 8); else M3_GEMM_LN(true, 4);
   } else {
     if (nw == 8) M3_GEMM_LN(false, 8); else M3_GEMM_LN(false, 4);

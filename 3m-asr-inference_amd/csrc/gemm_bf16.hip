@@ -10,45 +10,11 @@
 //   * accumulation is fp32, the epilogue (folded LayerNorm, bias, activation, mask, residual) is fp32.
 // Same work decomposition as gemm.hip (16 output columns x 16*MT rows per workgroup, K split over NW waves in
 // 32-deep steps, fixed-order LDS reduction), so results are bitwise reproducible run to run.
-#include <stdlib.h>
-
 #include "common.h"
+#include "gemm_epilogue.h"
 #include "kernels.h"
 
 namespace m3 {
-
-int launch_gemm_bf16w_tiled(const GemmParams& p, hipStream_t stream);   // gemm_bf16_tiled.hip
-bool gemm_bf16w_tiled_supports(const GemmParams& p);
-// below this many rows the 16-column K-split kernel fills the chip better (M3_TILED_MIN_ROWS overrides, for tuning)
-static int tiled_min_rows() {
-  static const int v = [] {
-    const char* e = getenv("M3_TILED_MIN_ROWS");
-    return e ? atoi(e) : 384;
-  }();
-  return v;
-}
-
-constexpr int gemm16_group_steps(int MT, int NW) { return NW == 16 ? 2 : (MT == 4 ? 2 : 4); }
-
-// bf16 activations x bf16 weights from this many rows on: the LDS-DMA fed kernel (gemm_bf16_dma.hip).  Measured against the
-// register-staged kernel (tools/bench_gemm_bf16.py --a16, profiles/r03_gemm_dma_vs_staged.txt): +12-16 % at 16 384 rows, +0-16 %
-// at 4 480, SLOWER at 1 984 rows (128 x 128 tiles leave most CUs idle there and a CU keeps only ~16 KB of LDS-DMA in
-// flight: a k-step is a full ~1.3 us round trip).  M3_DMA_MIN_ROWS overrides (read once).
-static int dma_min_rows() {
-  static const int v = [] {
-    const char* e = getenv("M3_DMA_MIN_ROWS");
-    return e ? atoi(e) : 4096;
-  }();
-  return v;
-}
-bool gemm_bf16w_uses_dma(const GemmParams& p) { return p.M >= dma_min_rows() && gemm_bf16_dma_supports(p); }
-
-// long batches: LDS-tiled kernel, when there are enough 64 x 64 tiles to occupy the chip
-bool gemm_bf16w_uses_tiled(const GemmParams& p) {
-  const bool glu = p.act == ACT_GLU;
-  return p.M >= tiled_min_rows() && (long)cdiv(p.M, 64) * cdiv(glu ? p.N / 2 : p.N, 64) >= 160 && gemm_bf16w_tiled_supports(p) &&
-         p.mode != GEMM_A_CONCAT2 && p.ln_gamma == nullptr;
-}
 
 template <int MT, bool GLU, int NW, bool CONV, bool LN, int NBUF>
 __global__ __launch_bounds__(64 * NW) void gemm_bf16w_kernel(const GemmParams p) {
@@ -97,7 +63,7 @@ __global__ __launch_bounds__(64 * NW) void gemm_bf16w_kernel(const GemmParams p)
     } else {
       arow[mt] = p.A + (size_t)m * p.lda + 8 * kq;
     }
-    if (p.mask_in) a_zero[mt] = (m % p.rows_per_batch) >= p.row_len[m / p.rows_per_batch];
+    if (p.mask_in) a_zero[mt] = gemm_row_padded(p, m);
   }
   const bf16_t* W = reinterpret_cast<const bf16_t*>(p.W);
   const bf16_t* wrow[NT];
@@ -250,7 +216,8 @@ __global__ __launch_bounds__(64 * NW) void gemm_bf16w_kernel(const GemmParams p)
         if (m >= p.M) continue;
         float y0 = v[0][r], y1 = v[NT - 1][r];
         bool pad = false;
-        if (p.mask_in || p.mask_out) pad = (m % p.rows_per_batch) >= p.row_len[m / p.rows_per_batch];
+        if (p.mask_in || p.mask_out) pad = gemm_row_padded(p, m);
+        float mean = 0.f, rstd = 1.f;
         if (LN) {
           float t1 = 0.f, t2 = 0.f;
 #pragma unroll
@@ -258,66 +225,24 @@ __global__ __launch_bounds__(64 * NW) void gemm_bf16w_kernel(const GemmParams p)
             t1 += rsum[w][row][0];
             t2 += rsum[w][row][1];
           }
-          const float mean = t1 / (float)p.K;
-          const float var = fmaxf(t2 / (float)p.K - mean * mean, 0.f);
-          const float rstd = rsqrtf(var + p.ln_eps);
-          if (p.mask_in && pad) {
-            y0 = -wbeta0;
-            y1 = -wbeta1;
-          } else {
-            y0 = rstd * (y0 - mean * wsum0);
-            y1 = rstd * (y1 - mean * wsum1);
-          }
+          ln_mean_rstd(t1, t2, p.K, p.ln_eps, mean, rstd);
         }
-        float y = y0 + bias0;
-        if (GLU) y = y * sigmoidf(y1 + bias1);
-        if (p.act == ACT_RELU) y = fmaxf(y, 0.f);
-        if (p.act == ACT_SILU) y = silu(y);
-        if (p.mask_out && pad) y = 0.f;
-        y *= p.alpha;
-        if (p.resid) y += res[r];
-        p.Y[(size_t)m * p.ldy + ep_n] = y;
+        p.Y[(size_t)m * p.ldy + ep_n] = gemm_epilogue<GLU, LN>(y0, y1, bias0, bias1, wsum0, wsum1, wbeta0, wbeta1, mean, rstd, pad, res[r], p);
       }
     }
   }
 }
 
-int launch_gemm_bf16w(const GemmParams& pin, hipStream_t stream) {
+int launch_gemm_bf16w_skinny(const GemmPlan& plan, const GemmParams& pin, hipStream_t stream) {
   GemmParams p = pin;
-  M3_REQUIRE(p.M > 0 && p.N > 0 && p.K > 0, "gemm_bf16w: empty problem M=%d N=%d K=%d", p.M, p.N, p.K);
-  M3_REQUIRE((p.K & 31) == 0, "gemm_bf16w: K=%d must be a multiple of 32", p.K);
-  M3_REQUIRE((p.lda & 3) == 0, "gemm_bf16w: lda=%d must be a multiple of 4", p.lda);
-  const bool glu = p.act == ACT_GLU;
-  M3_REQUIRE(!glu || (p.N & 1) == 0, "gemm_bf16w: GLU needs even N");
-  const bool conv = p.mode == GEMM_A_CONV3X3S2;
-  M3_REQUIRE(p.mode != GEMM_A_CONCAT2, "gemm_bf16w: concat operands are fp32-only (the router stays fp32)");
-  M3_REQUIRE(p.ln_gamma == nullptr && p.ln_out == nullptr,
-             "gemm_bf16w: only the folded LayerNorm (ln_wsum) is available with bf16 weights");
-  if (conv) M3_REQUIRE((p.conv_C & 31) == 0 && p.K == 9 * p.conv_C, "gemm_bf16w: conv mode needs K=9*C, C%%32==0");
-  const bool ln = p.ln_wsum != nullptr;
-  if (ln) M3_REQUIRE(p.mode == GEMM_A_PLAIN && p.K <= 2047, "gemm_bf16w: LayerNorm needs plain A with K < 2048");
-  M3_REQUIRE(!(ln && p.mask_in) || p.ln_wbeta, "gemm_bf16w: folded LayerNorm + input mask needs ln_wbeta");
-  if (p.mask_in || p.mask_out) M3_REQUIRE(p.row_len && p.rows_per_batch > 0, "gemm_bf16w: mask needs row_len");
-  if (gemm_bf16w_uses_dma(p)) return launch_gemm_bf16_dma(p, stream);
-  // only the LDS-DMA kernel writes / reads the row-statistic partials: a consumer of y_copy_stats would read stale numbers
-  M3_REQUIRE(p.Yb_stats == nullptr && p.ln_stats == nullptr,
-             "gemm_bf16w: y_copy_stats / ln_stats need the LDS-DMA kernel (M >= %d rows, bf16 A); this problem (M=%d) runs on another one",
-             dma_min_rows(), p.M);
-  if (gemm_bf16w_uses_tiled(p)) return launch_gemm_bf16w_tiled(p, stream);
-  M3_REQUIRE(!p.a_bf16 && !p.y_bf16 && p.Yb == nullptr, "gemm_bf16w: bf16 activations are a feature of the tiled kernel");
-  const int Nout = glu ? p.N / 2 : p.N;
-  int mt = p.M <= 128 ? 1 : (p.M <= 512 ? 2 : 4);
-  while (mt < 4 && 16 * mt < p.M && (long)cdiv(Nout, 16) * cdiv(p.M, 16 * mt) > 512) mt *= 2;
-  p.n_tiles = cdiv(Nout, 16);
-  p.m_tiles = cdiv(p.M, 16 * mt);
-  p.xcd_swizzle = (p.n_tiles % 8 == 0) ? 1 : 0;
+  p.n_tiles = plan.n_tiles; p.m_tiles = plan.m_tiles; p.xcd_swizzle = plan.xcd_swizzle;
   dim3 grid(p.n_tiles * p.m_tiles);
-  int nw = p.K >= 2048 ? 16 : (p.K >= 1024 ? 8 : 4);
-  if (nw == 16 && (glu || mt == 4 || ln)) nw = 8;
+  const int mt = plan.mt, nw = plan.nw;
+  const bool ln = plan.ln == GEMM_LN_EPI;
 
 #define M3_GEMM_LAUNCH(MT_, GLU_, NW_, CONV_, LN_)                                                                 \
   do {                                                                                                             \
-    if ((p.K >> 5) <= NW_ * gemm16_group_steps(MT_, NW_))                                                          \
+    if (plan.nbuf == 1)                                                                                            \
       hipLaunchKernelGGL((gemm_bf16w_kernel<MT_, GLU_, NW_, CONV_, LN_, 1>), grid, dim3(64 * NW_), 0, stream, p);  \
     else                                                                                                           \
       hipLaunchKernelGGL((gemm_bf16w_kernel<MT_, GLU_, NW_, CONV_, LN_, 2>), grid, dim3(64 * NW_), 0, stream, p);  \
@@ -333,13 +258,12 @@ int launch_gemm_bf16w(const GemmParams& pin, hipStream_t stream) {
     if (ln) M3_GEMM_MT(GLU_, NW_, false, true);                    \
     else M3_GEMM_MT(GLU_, NW_, false, false);                      \
   } while (0)
-  if (conv) {
-    M3_REQUIRE(!glu && !ln, "gemm_bf16w: conv mode supports neither GLU nor LayerNorm");
+  if (plan.conv) {
     if (nw == 16) M3_GEMM_MT(false, 16, true, false); else if (nw == 8) M3_GEMM_MT(false, 8, true, false);
     else M3_GEMM_MT(false, 4, true, false);
   } else if (nw == 16) {
     M3_GEMM_MT(false, 16, false, false);
-  } else if (glu) {
+  } else if (plan.glu) {
     if (nw == 8) M3_GEMM_LN(true, 8); else M3_GEMM_LN(true, 4);
   } else {
     if (nw == 8) M3_GEMM_LN(false, 8); else M3_GEMM_LN(false, 4);

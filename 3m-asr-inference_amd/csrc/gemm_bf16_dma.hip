@@ -21,6 +21,7 @@
 // from p.ln_stats -- per row, `ln_stat_parts` partial (sum, sum of squares) pairs written by whichever kernel produced the
 // bf16 operand (this kernel's own epilogue with p.Yb_stats, moe_combine, layernorm) from exactly the bf16 values it stored.
 #include "common.h"
+#include "gemm_epilogue.h"
 #include "kernels.h"
 
 // -DM3_DMA_DIAG: in-kernel phase stamps (s_memtime) of every work-group into a debug buffer, read back with
@@ -216,11 +217,12 @@ __global__ __launch_bounds__(256, STAGES == 2 ? 2 : 1) void gemm_bf16_dma_kernel
         t1 += p.ln_stats[((size_t)m * p.ln_stat_parts + q) * 2];
         t2 += p.ln_stats[((size_t)m * p.ln_stat_parts + q) * 2 + 1];
       }
-      const float mean = t1 / (float)p.K;
+      float mean, rstd;
+      ln_mean_rstd(t1, t2, p.K, p.ln_eps, mean, rstd);
       stats[tid][0] = mean;
-      stats[tid][1] = rsqrtf(fmaxf(t2 / (float)p.K - mean * mean, 0.f) + p.ln_eps);
+      stats[tid][1] = rstd;
     }
-    rowpad[tid] = (p.mask_in || p.mask_out) ? ((m % p.rows_per_batch) >= p.row_len[m / p.rows_per_batch] ? 1 : 0) : 0;
+    rowpad[tid] = (p.mask_in || p.mask_out) ? (gemm_row_padded(p, m) ? 1 : 0) : 0;
   }
   __syncthreads();
   M3_DIAG(dg[4] = __builtin_amdgcn_s_memtime();)
@@ -241,26 +243,8 @@ __global__ __launch_bounds__(256, STAGES == 2 ? 2 : 1) void gemm_bf16_dma_kernel
     const bool live = m < p.M && n < Nout;
     f32x4 y;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float y0 = v0[e], y1 = v1[e];
-      if (LN) {
-        if (p.mask_in && pad) {
-          y0 = -wbeta0[e];
-          y1 = -wbeta1[e];
-        } else {
-          y0 = rstd * (y0 - mean * wsum0[e]);
-          y1 = rstd * (y1 - mean * wsum1[e]);
-        }
-      }
-      float t = y0 + bias0[e];
-      if (GLU) t = t * sigmoidf(y1 + bias1[e]);
-      if (p.act == ACT_RELU) t = fmaxf(t, 0.f);
-      if (p.act == ACT_SILU) t = silu(t);
-      if (p.mask_out && pad) t = 0.f;
-      t *= p.alpha;
-      if (p.resid) t += rv[e];
-      y[e] = t;
-    }
+    for (int e = 0; e < 4; ++e)
+      y[e] = gemm_epilogue<GLU, LN>(v0[e], v1[e], bias0[e], bias1[e], wsum0[e], wsum1[e], wbeta0[e], wbeta1[e], mean, rstd, pad, rv[e], p);
     bf16x4 h;
 #pragma unroll
     for (int e = 0; e < 4; ++e) h[e] = (bf16_t)y[e];
@@ -276,6 +260,7 @@ __global__ __launch_bounds__(256, STAGES == 2 ? 2 : 1) void gemm_bf16_dma_kernel
           t2 += f * f;
         }
       }
+      // (own copy of lanes_sum<LPR>, the two sums interleaved: the shared helper costs the non-GLU instantiations a different VGPR count)
       t1 += dpp_mov<0xB1>(t1); t2 += dpp_mov<0xB1>(t2);
       t1 += dpp_mov<0x4E>(t1); t2 += dpp_mov<0x4E>(t2);
       t1 += dpp_mov<0x141>(t1); t2 += dpp_mov<0x141>(t2);
@@ -398,33 +383,12 @@ int init_gemm_bf16_dma_kernels() {
   return 0;
 }
 
-// plain row-major bf16 A (no implicit conv, no concat, no grouping), K a multiple of the k-step, folded LayerNorm only with
-// the producer's row statistics at hand
-bool gemm_bf16_dma_supports(const GemmParams& p) {
-  if (!p.w_bf16 || !p.a_bf16 || p.mode != GEMM_A_PLAIN || p.grp_acc != nullptr || p.w_scale != nullptr) return false;
-  if ((p.K % DBK) != 0 || (p.lda & 7) != 0 || p.ln_gamma != nullptr) return false;
-  if (p.ln_wsum != nullptr && p.ln_stats == nullptr) return false;
-  if (((size_t)(p.M - 1) * p.lda + p.K) * 2 >= ((size_t)1 << 32) || (size_t)p.N * p.K * 2 >= ((size_t)1 << 32)) return false;
-  return true;
-}
-
-int gemm_bf16_dma_col_tiles(const GemmParams& p) { return cdiv(p.act == ACT_GLU ? p.N / 2 : p.N, p.act == ACT_GLU ? DBN / 2 : DBN); }
-
-int launch_gemm_bf16_dma(const GemmParams& pin, hipStream_t stream) {
+int launch_gemm_bf16_dma(const GemmPlan& plan, const GemmParams& pin, hipStream_t stream) {
   GemmParams p = pin;
-  M3_REQUIRE(gemm_bf16_dma_supports(p), "gemm_bf16_dma: unsupported problem (bf16 A and W, plain mode, K %% 64 == 0)");
   if (int rc = init_gemm_bf16_dma_kernels()) return rc;
-  const bool glu = p.act == ACT_GLU, ln = p.ln_wsum != nullptr;
-  const int Nout = glu ? p.N / 2 : p.N;
-  M3_REQUIRE(!(ln && p.mask_in) || p.ln_wbeta, "gemm_bf16_dma: folded LayerNorm + input mask needs ln_wbeta");
-  if (p.mask_in || p.mask_out) M3_REQUIRE(p.row_len && p.rows_per_batch > 0, "gemm_bf16_dma: mask needs row_len");
-  if (p.y_bf16 || p.Yb) M3_REQUIRE((Nout & 3) == 0 && (p.ldy & 3) == 0 && (p.ldyb & 3) == 0, "gemm_bf16_dma: bf16 output needs N %% 4 == 0");
-  p.m_tiles = cdiv(p.M, DBM);
-  p.n_tiles = gemm_bf16_dma_col_tiles(p);
+  const bool glu = plan.glu, ln = plan.ln == GEMM_LN_EPI, deep = plan.stages == 4;
+  p.m_tiles = plan.m_tiles; p.n_tiles = plan.n_tiles;
   dim3 grid(cdiv(p.m_tiles, 8) * 8 * p.n_tiles);
-  // work-groups that do not outnumber the CUs: one per CU with a 4-stage ring; else two per CU with 2 stages each
-  const int cus = device_cu_count();
-  const bool deep = (long)p.m_tiles * p.n_tiles <= cus && p.K / DBK >= 4;
 #define M3_DMA_LAUNCH(G_, L_)                                                                                              \
   do {                                                                                                                     \
     if (deep) hipLaunchKernelGGL((gemm_bf16_dma_kernel<G_, L_, 4>), grid, dim3(256), dma_lds_bytes(4), stream, p);         \

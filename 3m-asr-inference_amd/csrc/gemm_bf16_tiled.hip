@@ -18,6 +18,7 @@
 //     cost more than the GEMM);
 //   * LayerNorm statistics (sum, sum of squares of the fp32 rows) are accumulated by the threads that stage A.
 #include "common.h"
+#include "gemm_epilogue.h"
 #include "kernels.h"
 
 namespace m3 {
@@ -25,8 +26,7 @@ namespace m3 {
 constexpr int kGrpRun = 4;   // row tiles of a grouped GEMM that run back to back on one XCD
 
 namespace {
-// two tile shapes: 128 x 128 x 64 when the problem has >= ~200 such tiles (MFMA-heavy: conv2), else 64 x 64 x 128 --
-// 4x the workgroups and half the k-steps, because a small GEMM is a chain of k-steps of ~1 us memory latency each
+// three tile shapes, 128 x 128 x 64, 64 x 64 x 128 and 32 x 64 x 128: plan_gemm says which and why
 constexpr int tiled_lds_bytes(int BM, int BN, int BK) {
   const int ring = 2 * (BM + BN) * (BK + 8) * 2, image = BM * (BN + 4) * 4;
   return ring > image ? ring : image;
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16w_tiled_kernel(const GemmPara
     } else {
       aptr[j] = p.A + (size_t)m * p.lda + 4 * ac;
     }
-    a_zero[j] = p.mask_in ? ((m % p.rows_per_batch) >= p.row_len[m / p.rows_per_batch]) : false;
+    a_zero[j] = p.mask_in ? gemm_row_padded(p, m) : false;
   }
   // W: thread t brings 16-B chunk (t % CB) of tile rows (t / CB) + RB j
   const int bc = tid % CB, br0 = tid / CB;
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16w_tiled_kernel(const GemmPara
         for (int e = 0; e < 4; ++e) res_all[it][e] = p.resid[(size_t)m * p.ldr + min(n + e, Nout - 1)];
       }
     }
-    pad_all[it] = (p.mask_in || p.mask_out) ? ((m % p.rows_per_batch) >= p.row_len[m / p.rows_per_batch]) : false;
+    pad_all[it] = (p.mask_in || p.mask_out) ? gemm_row_padded(p, m) : false;
   }
   };
 
@@ -326,19 +326,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16w_tiled_kernel(const GemmPara
   if (LN) {
 #pragma unroll
     for (int j = 0; j < JA; ++j) {
-      // the CA (8 / 16 / 32) consecutive lanes that staged row ar0 + RA j: DPP butterfly of the right width
-      static_assert(CA == 8 || CA == 16 || CA == 32, "row staged by 8, 16 or 32 lanes");
-      float t1 = s1[j], t2 = s2[j];
-      t1 += dpp_mov<0xB1>(t1); t2 += dpp_mov<0xB1>(t2);       // xor 1
-      t1 += dpp_mov<0x4E>(t1); t2 += dpp_mov<0x4E>(t2);       // xor 2
-      t1 += dpp_mov<0x141>(t1); t2 += dpp_mov<0x141>(t2);     // row_half_mirror: 8 lanes
-      if (CA >= 16) {
-        t1 += dpp_mov<0x140>(t1); t2 += dpp_mov<0x140>(t2);   // row_mirror: 16 lanes
-      }
-      if (CA == 32) {
-        t1 += __shfl_xor(t1, 16, 64);
-        t2 += __shfl_xor(t2, 16, 64);
-      }
+      // the CA (8 / 16 / 32) consecutive lanes that staged row ar0 + RA j
+      const float t1 = lanes_sum<CA>(s1[j]), t2 = lanes_sum<CA>(s2[j]);
       if (ac == 0) {
         stats[ar0 + RA * j][0] = t1;
         stats[ar0 + RA * j][1] = t2;
@@ -362,38 +351,16 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16w_tiled_kernel(const GemmPara
     if (m >= m_end || n >= Nout) continue;
     const bool pad = pad_all[it];
     float mean = 0.f, rstd = 1.f;
-    if (LN) {
-      mean = stats[row][0] / (float)p.K;
-      const float var = fmaxf(stats[row][1] / (float)p.K - mean * mean, 0.f);
-      rstd = rsqrtf(var + p.ln_eps);
-    }
+    if (LN) ln_mean_rstd(stats[row][0], stats[row][1], p.K, p.ln_eps, mean, rstd);
     const f32x4 v0 = *reinterpret_cast<const f32x4*>(Cs + row * C_LD + c4);
     f32x4 v1 = f32x4{0.f, 0.f, 0.f, 0.f};
     if (GLU) v1 = *reinterpret_cast<const f32x4*>(Cs + row * C_LD + TBN / 2 + c4);
     const f32x4 res = res_all[it];
     f32x4 y;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float y0 = v0[e], y1 = v1[e];
-      if (W8) y0 *= wsc[e];
-      if (LN) {
-        if (p.mask_in && pad) {
-          y0 = -wbeta0[e];
-          y1 = -wbeta1[e];
-        } else {
-          y0 = rstd * (y0 - mean * wsum0[e]);
-          y1 = rstd * (y1 - mean * wsum1[e]);
-        }
-      }
-      float t = y0 + bias0[e];
-      if (GLU) t = t * sigmoidf(y1 + bias1[e]);
-      if (p.act == ACT_RELU) t = fmaxf(t, 0.f);
-      if (p.act == ACT_SILU) t = silu(t);
-      if (p.mask_out && pad) t = 0.f;
-      t *= p.alpha;
-      if (p.resid) t += res[e];
-      y[e] = t;
-    }
+    for (int e = 0; e < 4; ++e)
+      y[e] = gemm_epilogue<GLU, LN>(W8 ? v0[e] * wsc[e] : v0[e], v1[e], bias0[e], bias1[e], wsum0[e], wsum1[e], wbeta0[e], wbeta1[e], mean, rstd,
+                                    pad, res[e], p);
     if (p.Yb != nullptr && n + 3 < Nout) {          // bf16 copy for the next GEMM's A operand (besides the fp32 output)
       bf16x4 h;
 #pragma unroll
@@ -453,35 +420,12 @@ int init_gemm_bf16_tiled_kernels() {
   return 0;
 }
 
-bool gemm_bf16w_tiled_supports(const GemmParams& p) {
-  return (p.K & 127) == 0 && (p.mode != GEMM_A_CONV3X3S2 || (p.conv_C & 127) == 0);
-}
-
-// caller (launch_gemm_bf16w) has validated the operands; returns 0 / error
-int launch_gemm_bf16w_tiled(const GemmParams& pin, hipStream_t stream) {
+int launch_gemm_bf16w_tiled(const GemmPlan& plan, const GemmParams& pin, hipStream_t stream) {
   GemmParams p = pin;
   if (int rc = init_gemm_bf16_tiled_kernels()) return rc;
-  const bool glu = p.act == ACT_GLU;
-  const bool conv = p.mode == GEMM_A_CONV3X3S2;
-  const bool ln = p.ln_wsum != nullptr;
-  const int Nout = glu ? p.N / 2 : p.N;
-  M3_REQUIRE(!(conv && (glu || ln)), "gemm_bf16w: conv mode supports neither GLU nor LayerNorm");
-  const bool big = (long)cdiv(p.M, 128) * cdiv(p.N, 128) >= 200;
-  // few 64 x 64 tiles (a ragged batch of ~1000 live rows x a 512- or 1024-wide output: 136-272 live tiles on 256 CUs, each
-  // a chain of memory round trips): 32-row tiles double the work-groups.  Measured at configs[2] (M3_TILED_THIN_BELOW=600):
-  // one context alone 3.94 -> 3.72 ms, four contexts 2.42 -> 2.31 M frames/s (W tiles are fetched twice as often) -- a
-  // latency / throughput trade, off by default
-  static const int thin_below = [] { const char* e = getenv("M3_TILED_THIN_BELOW"); return e ? atoi(e) : 0; }();
-  const bool thin = !big && !conv && (long)cdiv(p.M, 64) * cdiv(p.N, 64) < thin_below;
-  // (k-steps of 256 with one work-group per CU were tried for launches of <= 256 tiles: half the round trips, but 13.2 vs
-  //  9.0 us at 1090 x 1024 x 512 and 4.39 vs 3.95 ms per configs[2] forward -- two resident work-groups that overlap each
-  //  other's waits are worth more than fewer, longer steps)
-  const int bm = big ? 128 : (thin ? 32 : 64), bn = big ? 128 : 64;
-  p.m_tiles = cdiv(p.M, bm);
-  p.n_tiles = glu ? cdiv(Nout, bn / 2) : cdiv(p.N, bn);
+  const bool glu = plan.glu, conv = plan.conv, ln = plan.ln == GEMM_LN_EPI, big = plan.bm == 128, thin = plan.bm == 32;
+  p.m_tiles = plan.m_tiles; p.n_tiles = plan.n_tiles;
   dim3 grid(cdiv(p.m_tiles, 8) * 8 * p.n_tiles);   // row tiles in groups of 8 (one per XCD), see the kernel
-  if (p.a_bf16 && !conv) M3_REQUIRE((p.lda & 7) == 0, "gemm_bf16w: bf16 A needs lda %% 8 == 0");
-  if (p.y_bf16 || p.Yb) M3_REQUIRE((Nout & 3) == 0 && (p.ldy & 3) == 0 && (p.ldyb & 3) == 0, "gemm_bf16w: bf16 output needs N %% 4 == 0");
 #define M3_TILED_LAUNCH(G_, C_, L_)                                                                                  \
   if (glu == G_ && conv == C_ && ln == L_) {                                                                         \
     if (big && p.a_bf16)                                                                                             \

@@ -169,36 +169,14 @@ int init_gemm_f32_splitk_kernels() {
   return 0;
 }
 
-// How many K ranges (0 = do not use this path) and the workspace they need.  Used for deep, narrow problems only:
-// few output tiles, long K, plain epilogue (bias / ReLU / SiLU / scale; no LayerNorm, mask, GLU, residual, concat).
-int gemm_f32_splitk_plan(const GemmParams& p, size_t* ws_bytes) {
-  if (ws_bytes) *ws_bytes = 0;
-  if (p.w_bf16 || p.K < 4096 || (p.K & 63) || (p.N & 3) || (p.lda & 3) || (p.ldy & 3)) return 0;
-  if (p.mode == GEMM_A_CONCAT2 || p.ln_wsum || p.ln_gamma || p.mask_in || p.mask_out || p.resid || p.act == ACT_GLU) return 0;
-  if (p.mode == GEMM_A_CONV3X3S2 && (p.conv_C & 63)) return 0;
-  const long tiles = (long)cdiv(p.M, SBM) * cdiv(p.N, SBN);
-  if (tiles > 160) return 0;                          // enough tiles: the other kernels fill the chip
-  const int nsteps = p.K / SBK;
-  int splits = (int)(512 / tiles);                    // ~2 workgroups per CU
-  if (splits > nsteps / 4) splits = nsteps / 4;       // >= 4 k-steps per workgroup
-  if (splits < 2) return 0;
-  const int per = cdiv(nsteps, splits);
-  splits = cdiv(nsteps, per);
-  if (ws_bytes) *ws_bytes = (size_t)splits * p.M * p.N * sizeof(float);
-  return splits;
-}
-
-int launch_gemm_f32_splitk(const GemmParams& pin, float* ws, size_t ws_bytes, hipStream_t stream) {
+int launch_gemm_f32_splitk(const GemmPlan& plan, const GemmParams& pin, float* ws, hipStream_t stream) {
   GemmParams p = pin;
-  size_t need = 0;
-  const int splits = gemm_f32_splitk_plan(p, &need);
-  M3_REQUIRE(splits >= 2 && ws != nullptr && ws_bytes >= need, "gemm split-K: not applicable / workspace %zu < %zu", ws_bytes, need);
   if (int rc = init_gemm_f32_splitk_kernels()) return rc;
-  p.m_tiles = cdiv(p.M, SBM);
-  p.n_tiles = cdiv(p.N, SBN);
+  const int splits = plan.splits;
+  p.m_tiles = plan.m_tiles; p.n_tiles = plan.n_tiles;
   const int per = cdiv(p.K / SBK, splits);
   dim3 grid(p.m_tiles * p.n_tiles, splits);
-  if (p.mode == GEMM_A_CONV3X3S2)
+  if (plan.conv)
     hipLaunchKernelGGL((gemm_f32_splitk_kernel<true>), grid, dim3(256), kSplitLdsBytes, stream, p, ws, per);
   else
     hipLaunchKernelGGL((gemm_f32_splitk_kernel<false>), grid, dim3(256), kSplitLdsBytes, stream, p, ws, per);

@@ -8,6 +8,7 @@
 // the same permutation on both operands (exact).  All epilogues of gemm.hip except the affine LayerNorm prologue / concat
 // (router GEMM: stays on the K-split kernel).
 #include "common.h"
+#include "gemm_epilogue.h"
 #include "kernels.h"
 
 namespace m3 {
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_tiled_kernel(const GemmParams
     } else {
       aptr[j] = p.A + (size_t)m * p.lda + 4 * ac;
     }
-    a_zero[j] = p.mask_in ? ((m % p.rows_per_batch) >= p.row_len[m / p.rows_per_batch]) : false;
+    a_zero[j] = p.mask_in ? gemm_row_padded(p, m) : false;
   }
   // W: same map (float4 chunk ac of tile rows ar0 + RA j)
   const float* bptr[JB];
@@ -157,19 +158,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_tiled_kernel(const GemmParams
   if (LN) {
 #pragma unroll
     for (int j = 0; j < JA; ++j) {
-      // the CA (8 / 16 / 32) consecutive lanes that staged row ar0 + RA j: DPP butterfly of the right width
-      static_assert(CA == 8 || CA == 16 || CA == 32, "row staged by 8, 16 or 32 lanes");
-      float t1 = s1[j], t2 = s2[j];
-      t1 += dpp_mov<0xB1>(t1); t2 += dpp_mov<0xB1>(t2);       // xor 1
-      t1 += dpp_mov<0x4E>(t1); t2 += dpp_mov<0x4E>(t2);       // xor 2
-      t1 += dpp_mov<0x141>(t1); t2 += dpp_mov<0x141>(t2);     // row_half_mirror: 8 lanes
-      if (CA >= 16) {
-        t1 += dpp_mov<0x140>(t1); t2 += dpp_mov<0x140>(t2);   // row_mirror: 16 lanes
-      }
-      if (CA == 32) {
-        t1 += __shfl_xor(t1, 16, 64);
-        t2 += __shfl_xor(t2, 16, 64);
-      }
+      // the CA (8 / 16 / 32) consecutive lanes that staged row ar0 + RA j
+      const float t1 = lanes_sum<CA>(s1[j]), t2 = lanes_sum<CA>(s2[j]);
       if (ac == 0) {
         stats[ar0 + RA * j][0] = t1;
         stats[ar0 + RA * j][1] = t2;
@@ -221,7 +211,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_tiled_kernel(const GemmParams
         for (int e = 0; e < 4; ++e) res_all[it][e] = p.resid[(size_t)m * p.ldr + min(n + e, Nout - 1)];
       }
     }
-    pad_all[it] = (p.mask_in || p.mask_out) ? ((m % p.rows_per_batch) >= p.row_len[m / p.rows_per_batch]) : false;
+    pad_all[it] = (p.mask_in || p.mask_out) ? gemm_row_padded(p, m) : false;
   }
 #pragma unroll
   for (int it = 0; it < IT; ++it) {
@@ -230,37 +220,15 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_tiled_kernel(const GemmParams
     if (m >= m_end || n >= Nout) continue;
     const bool pad = pad_all[it];
     float mean = 0.f, rstd = 1.f;
-    if (LN) {
-      mean = stats[row][0] / (float)p.K;
-      const float var = fmaxf(stats[row][1] / (float)p.K - mean * mean, 0.f);
-      rstd = rsqrtf(var + p.ln_eps);
-    }
+    if (LN) ln_mean_rstd(stats[row][0], stats[row][1], p.K, p.ln_eps, mean, rstd);
     const f32x4 v0 = *reinterpret_cast<const f32x4*>(Cs + row * C_LD + c4);
     f32x4 v1 = f32x4{0.f, 0.f, 0.f, 0.f};
     if (GLU) v1 = *reinterpret_cast<const f32x4*>(Cs + row * C_LD + TBN / 2 + c4);
     const f32x4 res = res_all[it];
     f32x4 y;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float y0 = v0[e], y1 = v1[e];
-      if (LN) {
-        if (p.mask_in && pad) {
-          y0 = -wbeta0[e];
-          y1 = -wbeta1[e];
-        } else {
-          y0 = rstd * (y0 - mean * wsum0[e]);
-          y1 = rstd * (y1 - mean * wsum1[e]);
-        }
-      }
-      float t = y0 + bias0[e];
-      if (GLU) t = t * sigmoidf(y1 + bias1[e]);
-      if (p.act == ACT_RELU) t = fmaxf(t, 0.f);
-      if (p.act == ACT_SILU) t = silu(t);
-      if (p.mask_out && pad) t = 0.f;
-      t *= p.alpha;
-      if (p.resid) t += res[e];
-      y[e] = t;
-    }
+    for (int e = 0; e < 4; ++e)
+      y[e] = gemm_epilogue<GLU, LN>(v0[e], v1[e], bias0[e], bias1[e], wsum0[e], wsum1[e], wbeta0[e], wbeta1[e], mean, rstd, pad, res[e], p);
     if (vec_ok) {
       stg4(p.Y + (size_t)m * p.ldy + n, y);
     } else {
@@ -288,24 +256,11 @@ int init_gemm_f32_tiled_kernels() {
   return 0;
 }
 
-bool gemm_f32_tiled_supports(const GemmParams& p) {
-  return (p.K & 63) == 0 && (p.lda & 3) == 0 && p.mode != GEMM_A_CONCAT2 && p.ln_gamma == nullptr &&
-         (p.mode != GEMM_A_CONV3X3S2 || (p.conv_C & 63) == 0);
-}
-
-// caller (launch_gemm_f32) has validated the operands; returns 0 / error
-int launch_gemm_f32_tiled(const GemmParams& pin, hipStream_t stream) {
+int launch_gemm_f32_tiled(const GemmPlan& plan, const GemmParams& pin, hipStream_t stream) {
   GemmParams p = pin;
   if (int rc = init_gemm_f32_tiled_kernels()) return rc;
-  const bool glu = p.act == ACT_GLU;
-  const bool conv = p.mode == GEMM_A_CONV3X3S2;
-  const bool ln = p.ln_wsum != nullptr;
-  const int Nout = glu ? p.N / 2 : p.N;
-  M3_REQUIRE(!(conv && (glu || ln)), "gemm: conv mode supports neither GLU nor LayerNorm");
-  const bool big = (long)cdiv(p.M, 128) * cdiv(p.N, 128) >= 200;
-  const int bm = big ? 128 : 64, bn = big ? 128 : 64;
-  p.m_tiles = cdiv(p.M, bm);
-  p.n_tiles = glu ? cdiv(Nout, bn / 2) : cdiv(p.N, bn);
+  const bool glu = plan.glu, conv = plan.conv, ln = plan.ln == GEMM_LN_EPI, big = plan.bm == 128;
+  p.m_tiles = plan.m_tiles; p.n_tiles = plan.n_tiles;
   dim3 grid(cdiv(p.m_tiles, 8) * 8 * p.n_tiles);   // row tiles in groups of 8 (one per XCD)
 #define M3_F32D_LAUNCH(G_, C_, L_)                                                                              \
   if (glu == G_ && conv == C_ && ln == L_) {                                                                    \

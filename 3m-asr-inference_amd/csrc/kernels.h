@@ -51,30 +51,67 @@ struct GemmParams {
   // implicit conv on a packed ragged batch: valid output frames per utterance; a tile whose rows (b, t2, f2) all lie past
   // the utterance's last frame is skipped (its output rows are never gathered into the packed layout)
   const int32_t* conv_len = nullptr;
-  // filled by launch_gemm_f32
+  // filled by the launchers from the GemmPlan
   int n_tiles = 0, m_tiles = 0, xcd_swizzle = 0;
 };
-int launch_gemm_f32(const GemmParams& p, hipStream_t stream);
-bool gemm_f32_dual_fusable(const GemmParams& a, const GemmParams& b);   // two independent skinny fp32 GEMMs of one instantiation
-int launch_gemm_f32_dual(const GemmParams& a, const GemmParams& b, hipStream_t stream);   // ... in ONE launch   // dispatches to launch_gemm_bf16w when p.w_bf16
-int launch_gemm_bf16w(const GemmParams& p, hipStream_t stream);
-const char* gemm_kernel_label(const GemmParams& p, bool splitk);   // the kernel these dispatchers will run (observability)
-bool gemm_bf16w_uses_tiled(const GemmParams& p);   // the choice launch_gemm_bf16w makes for this problem (sizes / mode only)
-// deep-K, few-tile fp32 problems (conv2 / subsampling Linear at short inputs): split-K tiled kernel + reduce (gemm_f32_splitk.hip)
-int gemm_f32_splitk_plan(const GemmParams& p, size_t* ws_bytes);   // number of K ranges (0 = not applicable) and workspace
-int launch_gemm_f32_splitk(const GemmParams& p, float* ws, size_t ws_bytes, hipStream_t stream);
+// ---- the dense GEMM family (gemm_plan.hip) ----
+// The family has six kernels.  plan_gemm is the ONE place that checks a problem's operands and says which kernel runs it, in
+// which instantiation, over which grid and with how much workspace; launch_gemm runs a plan, and the engine's stage list, its
+// workspace sizing and the observability entries (m3_linear_kernel, m3_engine_stage_info) read the same plan.  First match wins:
+//   SplitKF32   fp32 W, K >= 4096, K % 64 == 0, N, lda, ldy % 4 == 0, at most 160 tiles of 64 x 64, plain epilogue (bias /
+//               ReLU / SiLU / scale), >= 2 K ranges of >= 4 k-steps, and the caller's workspace holds them      2 launches
+//   DmaBf16     bf16 W and bf16 A, M >= 4096 (M3_DMA_MIN_ROWS), plain A, K % 64 == 0, lda % 8 == 0, operands < 4 GB,
+//               folded LayerNorm only with ln_stats                                                             1 launch
+//   TiledBf16   bf16 W, M >= 384 (M3_TILED_MIN_ROWS), >= 160 tiles of 64 x 64, K (conv: C) % 128 == 0          1 launch
+//   TiledF32    fp32 W, the same row and tile bounds, K (conv: C) % 64 == 0, no concat, no affine LayerNorm    1 launch
+//   SkinnyBf16  bf16 W, fp32 A and Y, no Yb                                                                     1 launch
+//   SkinnyF32   fp32 W, everything else                                                                         1 launch
+// Yb_stats / ln_stats exist on DmaBf16 only; concat operands and the affine LayerNorm on SkinnyF32 only.  A problem no row
+// takes comes back with launches = 0 and the reason as text.  The thresholds are read once per process.
+enum { GEMM_LN_NONE = 0, GEMM_LN_EPI = 1, GEMM_LN_PRO = 2 };   // none / folded, applied in the epilogue (ln_wsum) / affine prologue (ln_gamma)
+enum class GemmKernel { SkinnyF32, SkinnyBf16, TiledF32, TiledBf16, DmaBf16, SplitKF32 };
+struct GemmPlan {
+  GemmKernel kernel;
+  const char* label;      // the kernel's name as rocprofv3 shows it
+  int launches;           // 1, 2 for split-K (+ its reduce), 0: a problem the family does not take (reason says why)
+  bool glu, conv; int ln; // template arguments every kernel shares (GEMM_LN_*)
+  int mt, nw, nbuf;       // skinny kernels: 16 * mt rows per work-group, K split over nw waves, one / two staging buffers
+  bool dual_ok;           // SkinnyF32 in one of the instantiations gemm_f32_dual_kernel has (gemm_dual_fusable)
+  int bm, bn, bk;         // tiled kernels: the tile
+  int stages;             // DmaBf16: depth of the LDS ring
+  int m_tiles, n_tiles, xcd_swizzle;   // what the launcher puts into the kernel's GemmParams; the grid follows from them
+  int splits; size_t ws_bytes;         // SplitKF32: K ranges and the partial tiles they leave in the workspace
+  char reason[192];
+};
+GemmPlan plan_gemm(const GemmParams& p, size_t workspace_bytes_available);
+int launch_gemm(const GemmPlan& plan, const GemmParams& p, float* ws, hipStream_t stream);
+bool gemm_dual_fusable(const GemmPlan& a, const GemmPlan& b);   // two independent skinny fp32 GEMMs of one instantiation
+int launch_gemm_f32_dual(const GemmPlan& pa, const GemmParams& a, const GemmPlan& pb, const GemmParams& b, hipStream_t stream);   // ... in ONE launch
+// K-steps per in-flight load group of the skinny kernels (the planner needs them for nbuf).  fp32: 2 buffers x G x (NT + MT)
+// float4 must fit the per-lane register budget (512 VGPR+AGPR for 4 waves, 256 for 8, 128 for 16 waves per workgroup)
+constexpr int gemm_group_steps(int MT, int NT, int NW) {
+  if (NW == 16) return MT == 1 ? (NT == 1 ? 4 : 2) : (MT == 2 ? 2 : 1);
+  if (NW == 8) return MT == 1 ? 8 : (MT == 2 ? (NT == 1 ? 6 : 4) : (NT == 1 ? 3 : 2));
+  return MT == 1 ? 8 : (MT == 2 ? 6 : 4);
+}
+constexpr int gemm16_group_steps(int MT, int NW) { return NW == 16 ? 2 : (MT == 4 ? 2 : 4); }
+// The per-form launchers launch exactly one form each, in the plan's instantiation: no decision, no operand check.
+int launch_gemm_f32_skinny(const GemmPlan& plan, const GemmParams& p, hipStream_t stream);      // gemm.hip
+int launch_gemm_bf16w_skinny(const GemmPlan& plan, const GemmParams& p, hipStream_t stream);    // gemm_bf16.hip
+int launch_gemm_f32_tiled(const GemmPlan& plan, const GemmParams& p, hipStream_t stream);       // gemm_f32_tiled.hip
+int launch_gemm_bf16w_tiled(const GemmPlan& plan, const GemmParams& p, hipStream_t stream);     // gemm_bf16_tiled.hip
+// bf16 A x bf16 W, LDS-DMA fed 128 x 128 x 64 tiles: the dense GEMMs of long batches in the 16-bit modes
+int launch_gemm_bf16_dma(const GemmPlan& plan, const GemmParams& p, hipStream_t stream);        // gemm_bf16_dma.hip
+// deep-K, few-tile fp32 problems (conv2 / subsampling Linear at short inputs): split-K tiled kernel + reduce
+int launch_gemm_f32_splitk(const GemmPlan& plan, const GemmParams& p, float* ws, hipStream_t stream);   // gemm_f32_splitk.hip
+// once, outside graph capture (dynamic-LDS opt-in of the tiled kernels)
 int init_gemm_f32_splitk_kernels();
 int init_gemm_bf16_tiled_kernels();
-// bf16 A x bf16 W, LDS-DMA fed 128 x 128 x 64 tiles (gemm_bf16_dma.hip): the dense GEMMs of long batches in the 16-bit modes
-constexpr int kXbStatParts = 4;                          // partial row statistics kept per row of a bf16 activation copy
-bool gemm_bf16_dma_supports(const GemmParams& p);
-int gemm_bf16_dma_col_tiles(const GemmParams& p);
-bool gemm_bf16w_uses_dma(const GemmParams& p);           // the choice launch_gemm_bf16w makes
-int launch_gemm_bf16_dma(const GemmParams& p, hipStream_t stream);
+int init_gemm_f32_tiled_kernels();
 int init_gemm_bf16_dma_kernels();
+constexpr int kXbStatParts = 4;                          // partial row statistics kept per row of a bf16 activation copy
 // (sum, sum of squares) of every row of a bf16 matrix -> stats[row][kXbStatParts][2] (total in part 0, zeros elsewhere)
 int launch_row_stats_bf16(const void* xb, int rows, int D, float* stats, hipStream_t stream);
-int init_gemm_f32_tiled_kernels();    // same for the fp32 tiled kernels (gemm_f32_tiled.hip)   // once, outside graph capture (dynamic-LDS opt-in of the tiled kernels)
 
 // ---- MoE indexing / scatter / gather (moe_index.hip) ----
 int launch_moe_index(const int32_t* gate_idx, int S, int E, int32_t* mapping, int32_t* acc_hist,

@@ -303,7 +303,9 @@ int m3_linear(const m3_linear_desc* desc, m3_stream stream);
  * are provided; otherwise identical to m3_linear. */
 size_t m3_linear_workspace_size(const m3_linear_desc* desc);
 /* Host only: name of the device kernel m3_linear (with_workspace = 0) or m3_linear_ws given its workspace (1) runs for desc
- * (sizes, strides, dtypes and modes are read, no pointer is dereferenced); NULL for a descriptor m3_linear rejects. */
+ * (sizes, strides, dtypes and modes are read, no pointer is dereferenced).  NULL for every descriptor m3_linear rejects, whether
+ * the descriptor itself is malformed or no kernel of the family takes the problem (e.g. a bf16 `a` below the tiled kernel's row
+ * count, y_copy_stats below the LDS-DMA kernel's): m3_last_error() then holds the reason m3_linear would give. */
 const char* m3_linear_kernel(const m3_linear_desc* desc, int with_workspace);
 int m3_linear_ws(const m3_linear_desc* desc, void* workspace, size_t workspace_bytes, m3_stream stream);
 

@@ -45,11 +45,11 @@ def dev(t):
 
 # ================================================================================================ m3_linear
 # Kernel families and their row thresholds, read from the dispatch code:
-#   gemm.hip gemm_f32_uses_tiled / gemm_bf16.hip gemm_bf16w_uses_tiled: M >= 384 and cdiv(M, 64) * cdiv(n_out, 64) >= 160 and
+#   gemm_plan.hip plan_gemm, TiledF32 / TiledBf16: M >= 384 and cdiv(M, 64) * cdiv(n_out, 64) >= 160 and
 #     K % 64 == 0 (fp32) / K % 128 == 0 (bf16 weights), no concat, no affine LayerNorm  -> the LDS-tiled kernels
 #     (64-row tiles; 128-row tiles on long batches), else the K-split "skinny" kernels (16 * MT-row tiles, 16 columns);
-#   gemm_bf16.hip gemm_bf16w_uses_dma: M >= 4096, bf16 a, bf16 w, K % 64 == 0, lda % 8 == 0 -> the LDS-DMA kernel (128-row tiles);
-#   gemm_f32_splitk.hip gemm_f32_splitk_plan: fp32, K >= 4096, K % 64 == 0, N % 4 == 0, ldy % 4 == 0, plain epilogue,
+#   gemm_plan.hip plan_gemm, DmaBf16: M >= 4096, bf16 a, bf16 w, K % 64 == 0, lda % 8 == 0 -> the LDS-DMA kernel (128-row tiles);
+#   gemm_plan.hip plan_gemm, SplitKF32: fp32, K >= 4096, K % 64 == 0, N % 4 == 0, ldy % 4 == 0, plain epilogue,
 #     <= 160 tiles of 64 x 64 -> split-K kernel + reduce (m3_linear_ws only).
 def _linear_case(M, N, K, *, wdt=torch.float32, a16=False, act=_lib.ACT_NONE, resid=None, masks=None, ln=None, concat=False,
                  copy=False, stats=False, y16=False, alpha=1.0, tol=3e-5, ldy=None, ldr=None, what=""):
@@ -218,7 +218,7 @@ def test_linear_f32_tiled_strided(name, opt):
 
 def test_linear_f32_large_m_strided():
     """long batch on the tiled kernel's 128-row tiles (4225 = 33 * 128 + 1), and the skinny kernel's 64-row tiles (MT = 4),
-    which concat / affine-LayerNorm problems keep at any M (gemm_f32_uses_tiled excludes them)"""
+    which concat / affine-LayerNorm problems keep at any M (plan_gemm keeps them off the tiled kernel)"""
     _linear_case(4225, 1040, 512, what="gemm_f32_tiled_kernel/128-row tiles", resid="own", alpha=0.5)
     for M in (639, 640, 641):
         _linear_case(M, 80, 512, what="gemm_f32_kernel/MT=4 concat2", concat=True, tol=2e-5)
