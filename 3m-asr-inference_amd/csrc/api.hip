@@ -435,6 +435,35 @@ int m3_ctc_beam_nbest(const m3_ctc_beam_desc* desc, const void* state, size_t st
                       int32_t* hyp_len, float* hyp_score, int32_t* n_hyps, m3_stream stream) {
   return launch_ctc_beam_nbest(desc, state, state_bytes, hyp_tokens, hyp_len, hyp_score, n_hyps, (hipStream_t)stream);
 }
+int m3_ctc_context_validate(const void* image, size_t image_bytes, int V) { return ctc_context_validate(image, image_bytes, V); }
+int m3_ctc_prefix_beam_search_ctx(const float* top_logp, const int32_t* top_idx, int T, int k, int beam, int blank,
+                                  const void* image, size_t image_bytes, int graph, int32_t* hyp_tokens, int32_t* hyp_len,
+                                  float* hyp_score, float* hyp_bonus, int32_t* hyp_state, int32_t* n_hyps) {
+  return ctc_prefix_beam_search_ctx_host(top_logp, top_idx, T, k, beam, blank, image, image_bytes, graph, hyp_tokens, hyp_len,
+                                         hyp_score, hyp_bonus, hyp_state, n_hyps);
+}
+size_t m3_ctc_beam_ctx_state_size(const m3_ctc_beam_desc* desc) { return ctc_beam_ctx_state_size(desc); }
+int m3_ctc_beam_ctx_reset(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, m3_stream stream) {
+  return launch_ctc_beam_ctx_reset(desc, state, state_bytes, (hipStream_t)stream);
+}
+int m3_ctc_beam_ctx_reset_slots(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const int32_t* slots, int n,
+                                m3_stream stream) {
+  M3_REQUIRE(n == 0 || slots != nullptr, "ctc_beam_ctx_reset_slots: null slot list");
+  if (n == 0) return 0;
+  return launch_ctc_beam_ctx_reset(desc, state, state_bytes, (hipStream_t)stream, slots, n);
+}
+int m3_ctc_beam_ctx_advance(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const void* image, size_t image_bytes,
+                            const int32_t* graph_of, const float* top_logp, const int32_t* top_idx, int T_chunk,
+                            const int32_t* n_frames, m3_stream stream) {
+  return launch_ctc_beam_ctx_advance(desc, state, state_bytes, image, image_bytes, graph_of, top_logp, top_idx, T_chunk, n_frames,
+                                     (hipStream_t)stream);
+}
+int m3_ctc_beam_ctx_nbest(const m3_ctc_beam_desc* desc, const void* state, size_t state_bytes, const void* image,
+                          size_t image_bytes, const int32_t* graph_of, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score,
+                          float* hyp_bonus, int32_t* n_hyps, m3_stream stream) {
+  return launch_ctc_beam_ctx_nbest(desc, state, state_bytes, image, image_bytes, graph_of, hyp_tokens, hyp_len, hyp_score,
+                                   hyp_bonus, n_hyps, (hipStream_t)stream);
+}
 size_t m3_ctc_greedy_stream_state_size(const m3_ctc_greedy_desc* desc) { return ctc_greedy_stream_state_size(desc); }
 int m3_ctc_greedy_stream_reset(const m3_ctc_greedy_desc* desc, void* state, size_t state_bytes, m3_stream stream) {
   return launch_ctc_greedy_stream_reset(desc, state, state_bytes, (hipStream_t)stream);

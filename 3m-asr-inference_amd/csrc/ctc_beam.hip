@@ -62,6 +62,19 @@ BeamLayout beam_layout(int beam, int max_frames) {
   return L;
 }
 
+// Context biasing appends, behind the B slices above (which stay as they are, byte for byte), per utterance the context
+// state and the bonus of every trie node: ctx_state[pool] int32, ctx_bonus[pool] double.
+struct CtxLayout {
+  size_t base, bonus, stride;   // base: offset of utterance 0's block in the state; bonus: offset of ctx_bonus in a block
+};
+CtxLayout ctx_layout(const BeamLayout& L, int B) {
+  CtxLayout C;
+  C.base = (size_t)B * L.stride;
+  C.bonus = align_up((size_t)L.pool * 4, 8);
+  C.stride = align_up(C.bonus + (size_t)L.pool * 8, 256);
+  return C;
+}
+
 int check_beam_desc(const m3_ctc_beam_desc* d) {
   M3_REQUIRE(d != nullptr, "ctc_beam: null descriptor");
   M3_REQUIRE(d->B >= 0, "ctc_beam: B = %d < 0", d->B);
@@ -137,12 +150,37 @@ __global__ __launch_bounds__(256) void ctc_beam_reset_kernel(BeamLayout L, char*
   }
 }
 
+// What the biased search (CTX) adds to the advance; the unbiased instantiation takes an empty one and none of the CTX code.
+struct CtxArgs {
+  CtxLayout C;
+  const int32_t* image;
+  long long words;
+  const int32_t* graph_of;
+};
+struct NoCtx {};
+__device__ __forceinline__ int ctx_in_range(int v, int n) { return (unsigned)v < (unsigned)n ? v : 0; }
+
+// CTX: every trie node carries (context state, bonus), pure functions of its prefix; candidates are ranked by
+// log_add2(pb, pnb) + bonus.  An utterance whose graph_of is outside [0, G) runs with state 0 and bonus 0.0 throughout.
+template <bool CTX, class Ctx>
 __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayout L, int beam, int k, int blank, int max_frames,
                                                                         char* state, const float* __restrict__ top_logp,
                                                                         const int32_t* __restrict__ top_idx, int T_chunk,
-                                                                        const int32_t* __restrict__ n_frames) {
+                                                                        const int32_t* __restrict__ n_frames, Ctx cx) {
   const int b = blockIdx.x, tid = threadIdx.x;
   const BeamPtrs p = beam_ptrs(L, state, b);
+  // CTX only: the beam's and the survivors' (state, bonus), the frame's symbol classes, the utterance's graph
+  __shared__ int s_state[CTX ? kBeamMax : 1], n_state[CTX ? kBeamMax : 1], f_cls[CTX ? kTopkMax : 1];
+  __shared__ double s_bonus[CTX ? kBeamMax : 1], n_bonus[CTX ? kBeamMax : 1];
+  __shared__ CtxGraph sh_g;
+  __shared__ int sh_biased;
+  int32_t* cs = nullptr;
+  double* cb = nullptr;
+  if constexpr (CTX) {
+    char* c = state + cx.C.base + (size_t)b * cx.C.stride;
+    cs = (int32_t*)c;
+    cb = (double*)(c + cx.C.bonus);
+  }
   // current beam (best first) and its nodes
   __shared__ int s_node[kBeamMax], s_par[kBeamMax], s_tok[kBeamMax], s_dep[kBeamMax];
   __shared__ double s_pb[kBeamMax], s_pnb[kBeamMax];
@@ -169,6 +207,7 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
     sh_nf = nf;
     sh_ncur = p.hdr[H_NCUR];
     sh_nnodes = p.hdr[H_NNODES];
+    if constexpr (CTX) sh_biased = ctx_graph_view(cx.image, cx.words, cx.graph_of[b], &sh_g) ? 1 : 0;
   }
   __syncthreads();
   if (sh_status != 0 || sh_nf == 0) return;
@@ -181,6 +220,10 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
     s_dep[tid] = p.depth[nd];
     s_pb[tid] = p.pb[tid];
     s_pnb[tid] = p.pnb[tid];
+    if constexpr (CTX) {
+      s_state[tid] = sh_biased ? ctx_in_range(cs[nd], sh_g.n_states) : 0;
+      s_bonus[tid] = cb[nd];
+    }
   }
   int t = 0;
   for (; t < nf; ++t) {
@@ -189,6 +232,10 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
     if (tid < k) {
       f_s[tid] = top_idx[row + tid];
       f_ps[tid] = (double)top_logp[row + tid];
+      if constexpr (CTX) {                        // the frame's symbols are classed once
+        const int s = f_s[tid];
+        f_cls[tid] = sh_biased && (unsigned)s < (unsigned)sh_g.V ? ctx_in_range(sh_g.cls[s], sh_g.A) : 0;
+      }
     }
     for (int i = tid; i < n * k; i += kBeamThreads) merged[i] = 0;
     if (tid == 0) sh_nvalid = 0;
@@ -233,7 +280,10 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
       c_pb[q] = pb;
       c_pnb[q] = pnb;
       c_first[q] = first;
-      if (first != 0x7fffffff) c_score[q] = log_add2(pb, pnb);
+      if (first != 0x7fffffff) {
+        if constexpr (CTX) c_score[q] = log_add2(pb, pnb) + s_bonus[q];     // a beam entry's node holds its bonus
+        else c_score[q] = log_add2(pb, pnb);
+      }
     }
     __syncthreads();
     // the extensions that are slots of their own
@@ -258,7 +308,13 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
       c_pb[c] = -INFINITY;
       c_pnb[c] = pnb;
       c_first[c] = (j * n + h) * 2 + sub;
-      c_score[c] = log_add2(-INFINITY, pnb);
+      if constexpr (CTX) {
+        double bonus = s_bonus[h];
+        if (sh_biased) bonus += (double)sh_g.delta[s_state[h] * sh_g.A + f_cls[j]];
+        c_score[c] = log_add2(-INFINITY, pnb) + bonus;
+      } else {
+        c_score[c] = log_add2(-INFINITY, pnb);
+      }
     }
     __syncthreads();
     // second prune: rank = number of candidates ahead in (score desc, first touch asc); ranks < beam survive
@@ -285,6 +341,8 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
     if (tid < 64) {
       const int n_next = min(sh_nvalid, beam);
       int node = -1, par = -1, tok = -1, dep = 0;
+      int cst = 0, ch = 0, cj = 0;                // CTX: the survivor's state and bonus; its parent and rank if an extension
+      double cbo = 0.0;
       unsigned long long key = 0;
       if (tid < n_next) {
         const int src = n_src[tid];
@@ -293,8 +351,14 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
           par = s_par[src];
           tok = s_tok[src];
           dep = s_dep[src];
+          if constexpr (CTX) {
+            cst = s_state[src];
+            cbo = s_bonus[src];
+          }
         } else {
           const int h = (src - n) / k, j = (src - n) - h * k;
+          ch = h;
+          cj = j;
           par = s_node[h];
           tok = f_s[j];
           dep = s_dep[h] + 1;
@@ -309,6 +373,19 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
             if (kk == kEmptyKey) break;
             slot = (slot + 1) & (L.hcap - 1);
           }
+          if constexpr (CTX) {
+            if (node >= 0) {                      // a prefix that was here before: its node still holds both
+              cst = sh_biased ? ctx_in_range(cs[node], sh_g.n_states) : 0;
+              cbo = cb[node];
+            } else {
+              cbo = s_bonus[ch];
+              if (sh_biased) {
+                const int arc = s_state[ch] * sh_g.A + f_cls[cj];
+                cst = ctx_in_range(sh_g.next[arc], sh_g.n_states);
+                cbo += (double)sh_g.delta[arc];
+              }
+            }
+          }
         }
       }
       const bool fresh = tid < n_next && node < 0;
@@ -321,6 +398,10 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
         p.parent[node] = par;
         p.token[node] = tok;
         p.depth[node] = dep;
+        if constexpr (CTX) {
+          cs[node] = cst;
+          cb[node] = cbo;
+        }
         int slot = hash_slot(key, L.hcap);
         for (int probe = 0; probe < L.hcap; ++probe) {
           if (atomicCAS(&p.hkey[slot], kEmptyKey, key) == kEmptyKey) {
@@ -335,6 +416,10 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
         n_par[tid] = par;
         n_tok[tid] = tok;
         n_dep[tid] = dep;
+        if constexpr (CTX) {
+          n_state[tid] = cst;
+          n_bonus[tid] = cbo;
+        }
       }
       if (tid == 0) {
         sh_nnodes = base + (sh_status == 0 ? __popcll(m) : 0);
@@ -350,6 +435,10 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
       s_dep[tid] = n_dep[tid];
       s_pb[tid] = n_pb[tid];
       s_pnb[tid] = n_pnb[tid];
+      if constexpr (CTX) {
+        s_state[tid] = n_state[tid];
+        s_bonus[tid] = n_bonus[tid];
+      }
     }
     __syncthreads();
   }
@@ -366,6 +455,70 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
       p.hdr[H_NNODES] = sh_nnodes;
     }
   }
+}
+
+// the root's (state 0, bonus 0.0) of the listed utterances (slots == null: utterances 0 .. n - 1)
+__global__ __launch_bounds__(256) void ctc_beam_ctx_reset_kernel(CtxLayout C, char* state, const int32_t* __restrict__ slots, int B,
+                                                                 int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int utt = slots != nullptr ? slots[i] : i;
+  if (utt < 0 || utt >= B) return;
+  char* c = state + C.base + (size_t)utt * C.stride;
+  ((int32_t*)c)[0] = 0;
+  ((double*)(c + C.bonus))[0] = 0.0;
+}
+
+// ctc_beam_nbest_kernel plus the bonus: hypothesis r's final = bonus - pot[state]; rows are written in the order of
+// (CTC score + final) desc, stable on the beam order; hyp_score stays the CTC score
+__global__ __launch_bounds__(64) void ctc_beam_ctx_nbest_kernel(BeamLayout L, CtxLayout C, int beam, int max_frames,
+                                                                const char* state, const int32_t* __restrict__ image,
+                                                                long long words, const int32_t* __restrict__ graph_of,
+                                                                int32_t* __restrict__ hyp_tokens, int32_t* __restrict__ hyp_len,
+                                                                float* __restrict__ hyp_score, float* __restrict__ hyp_bonus,
+                                                                int32_t* __restrict__ n_hyps) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const BeamPtrs p = beam_ptrs(L, (char*)state, b);
+  const char* c = state + C.base + (size_t)b * C.stride;
+  const int32_t* cs = (const int32_t*)c;
+  const double* cb = (const double*)(c + C.bonus);
+  __shared__ double key[kBeamMax];
+  __shared__ int len_of[kBeamMax];
+  const int status = p.hdr[H_STATUS];
+  const int n = status ? 0 : min(p.hdr[H_NCUR], beam);
+  int32_t* toks = hyp_tokens + (size_t)b * beam * max_frames;
+  CtxGraph g;
+  const bool biased = ctx_graph_view(image, words, graph_of[b], &g);
+  double score = -INFINITY, fin = 0.0;
+  int nd = 0;
+  if (lane < n) {
+    nd = p.node[lane];
+    score = log_add2(p.pb[lane], p.pnb[lane]);
+    fin = cb[nd];
+    if (biased) fin -= (double)g.pot[ctx_in_range(cs[nd], g.n_states)];
+    key[lane] = score + fin;
+  }
+  __syncthreads();
+  if (lane < beam) {
+    int r = lane, L_r = 0;
+    if (lane < n) {
+      r = 0;
+      for (int i = 0; i < n; ++i) r += (key[i] > key[lane] || (key[i] == key[lane] && i < lane)) ? 1 : 0;
+      L_r = min(p.depth[nd], max_frames);
+      for (int i = L_r - 1; i >= 0 && nd > 0; --i) {
+        toks[(size_t)r * max_frames + i] = p.token[nd];
+        nd = p.parent[nd];
+      }
+    }
+    len_of[r] = L_r;
+    hyp_len[(size_t)b * beam + r] = L_r;
+    hyp_score[(size_t)b * beam + r] = (float)score;
+    hyp_bonus[(size_t)b * beam + r] = (float)fin;
+  }
+  __syncthreads();
+  for (int r = 0; r < beam; ++r)
+    for (int i = len_of[r] + lane; i < max_frames; i += 64) toks[(size_t)r * max_frames + i] = -1;
+  if (lane == 0) n_hyps[b] = status ? -1 : n;
 }
 
 // one wave per utterance; lane r < n_cur walks hypothesis r's trie path
@@ -502,8 +655,8 @@ int launch_ctc_beam_advance(const m3_ctc_beam_desc* d, void* state, size_t bytes
   M3_REQUIRE(T_chunk >= 0, "ctc_beam_advance: T_chunk = %d < 0", T_chunk);
   if (d->B == 0 || T_chunk == 0) return 0;
   M3_REQUIRE(top_logp && top_idx && n_frames, "ctc_beam_advance: null pointer");
-  hipLaunchKernelGGL(ctc_beam_advance_kernel, dim3(d->B), dim3(kBeamThreads), 0, stream, L, d->beam, d->k, d->blank,
-                     d->max_frames, (char*)state, top_logp, top_idx, T_chunk, n_frames);
+  hipLaunchKernelGGL((ctc_beam_advance_kernel<false, NoCtx>), dim3(d->B), dim3(kBeamThreads), 0, stream, L, d->beam, d->k,
+                     d->blank, d->max_frames, (char*)state, top_logp, top_idx, T_chunk, n_frames, NoCtx{});
   M3_LAUNCH_CHECK();
   return 0;
 }
@@ -518,6 +671,70 @@ int launch_ctc_beam_nbest(const m3_ctc_beam_desc* d, const void* state, size_t b
   M3_REQUIRE(hyp_len && hyp_score && n_hyps && (hyp_tokens || d->max_frames == 0), "ctc_beam_nbest: null pointer");
   hipLaunchKernelGGL(ctc_beam_nbest_kernel, dim3(d->B), dim3(64), 0, stream, L, d->beam, d->max_frames, (const char*)state,
                      hyp_tokens, hyp_len, hyp_score, n_hyps);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+size_t ctc_beam_ctx_state_size(const m3_ctc_beam_desc* d) {
+  if (check_beam_desc(d)) return 0;
+  const BeamLayout L = beam_layout(d->beam, d->max_frames);
+  const CtxLayout C = ctx_layout(L, d->B);
+  return C.base + (size_t)d->B * C.stride;
+}
+
+int launch_ctc_beam_ctx_reset(const m3_ctc_beam_desc* d, void* state, size_t bytes, hipStream_t stream, const int32_t* slots,
+                              int n) {
+  if (int rc = check_beam_desc(d)) return rc;
+  const size_t need = ctc_beam_ctx_state_size(d);
+  M3_REQUIRE(state != nullptr && bytes >= need, "ctc_beam_ctx_reset: state %zu bytes < required %zu", bytes, need);
+  if (int rc = launch_ctc_beam_reset(d, state, bytes, stream, slots, n)) return rc;
+  if (d->B == 0 || (slots != nullptr && n == 0)) return 0;
+  const int cnt = slots ? n : d->B;
+  hipLaunchKernelGGL(ctc_beam_ctx_reset_kernel, dim3((cnt + 255) / 256), dim3(256), 0, stream,
+                     ctx_layout(beam_layout(d->beam, d->max_frames), d->B), (char*)state, slots, d->B, cnt);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+static int check_ctx_image(const char* who, const void* image, size_t image_bytes, const int32_t* graph_of) {
+  M3_REQUIRE(graph_of != nullptr, "%s: null graph_of", who);
+  M3_REQUIRE(image != nullptr || image_bytes == 0, "%s: null image of %zu bytes", who, image_bytes);
+  M3_REQUIRE(image_bytes % 4 == 0 && image_bytes <= kCtxMaxBytes && (image == nullptr || image_bytes >= CTX_HDR_WORDS * 4),
+             "%s: image of %zu bytes (a multiple of 4 in [%d, %zu])", who, image_bytes, CTX_HDR_WORDS * 4, kCtxMaxBytes);
+  return 0;
+}
+
+int launch_ctc_beam_ctx_advance(const m3_ctc_beam_desc* d, void* state, size_t bytes, const void* image, size_t image_bytes,
+                                const int32_t* graph_of, const float* top_logp, const int32_t* top_idx, int T_chunk,
+                                const int32_t* n_frames, hipStream_t stream) {
+  if (int rc = check_beam_desc(d)) return rc;
+  const size_t need = ctc_beam_ctx_state_size(d);
+  M3_REQUIRE(state != nullptr && bytes >= need, "ctc_beam_ctx_advance: state %zu bytes < required %zu", bytes, need);
+  M3_REQUIRE(T_chunk >= 0, "ctc_beam_ctx_advance: T_chunk = %d < 0", T_chunk);
+  if (d->B == 0 || T_chunk == 0) return 0;
+  M3_REQUIRE(top_logp && top_idx && n_frames, "ctc_beam_ctx_advance: null pointer");
+  if (int rc = check_ctx_image("ctc_beam_ctx_advance", image, image_bytes, graph_of)) return rc;
+  const BeamLayout L = beam_layout(d->beam, d->max_frames);
+  const CtxArgs cx{ctx_layout(L, d->B), (const int32_t*)image, (long long)(image_bytes / 4), graph_of};
+  hipLaunchKernelGGL((ctc_beam_advance_kernel<true, CtxArgs>), dim3(d->B), dim3(kBeamThreads), 0, stream, L, d->beam, d->k,
+                     d->blank, d->max_frames, (char*)state, top_logp, top_idx, T_chunk, n_frames, cx);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_ctc_beam_ctx_nbest(const m3_ctc_beam_desc* d, const void* state, size_t bytes, const void* image, size_t image_bytes,
+                              const int32_t* graph_of, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score,
+                              float* hyp_bonus, int32_t* n_hyps, hipStream_t stream) {
+  if (int rc = check_beam_desc(d)) return rc;
+  const size_t need = ctc_beam_ctx_state_size(d);
+  M3_REQUIRE(state != nullptr && bytes >= need, "ctc_beam_ctx_nbest: state %zu bytes < required %zu", bytes, need);
+  if (d->B == 0) return 0;
+  M3_REQUIRE(hyp_len && hyp_score && hyp_bonus && n_hyps && (hyp_tokens || d->max_frames == 0), "ctc_beam_ctx_nbest: null pointer");
+  if (int rc = check_ctx_image("ctc_beam_ctx_nbest", image, image_bytes, graph_of)) return rc;
+  const BeamLayout L = beam_layout(d->beam, d->max_frames);
+  hipLaunchKernelGGL(ctc_beam_ctx_nbest_kernel, dim3(d->B), dim3(64), 0, stream, L, ctx_layout(L, d->B), d->beam, d->max_frames,
+                     (const char*)state, (const int32_t*)image, (long long)(image_bytes / 4), graph_of, hyp_tokens, hyp_len,
+                     hyp_score, hyp_bonus, n_hyps);
   M3_LAUNCH_CHECK();
   return 0;
 }

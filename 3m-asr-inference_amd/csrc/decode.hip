@@ -250,6 +250,157 @@ int ctc_prefix_beam_search_host(const float* top_logp, const int32_t* top_idx, i
   return 0;
 }
 
+// ---------------------------------------------------------------- context biasing, host side
+// Structure of a context image (kernels.h): the header, every graph's tables inside the image, and every table entry that
+// the searches use as an index.  The limits: G <= 1024, n_states <= 65536, A <= min(V + 1, 65536), image <= 64 MiB.
+int ctc_context_validate(const void* image, size_t bytes, int V) {
+  M3_REQUIRE(image != nullptr, "ctc_context_validate: null image");
+  M3_REQUIRE(V >= 1, "ctc_context_validate: V = %d < 1", V);
+  M3_REQUIRE(bytes % 4 == 0 && bytes >= CTX_HDR_WORDS * 4 && bytes <= kCtxMaxBytes,
+             "ctc_context_validate: image of %zu bytes (a multiple of 4 in [%d, %zu])", bytes, CTX_HDR_WORDS * 4, kCtxMaxBytes);
+  const int32_t* w = (const int32_t*)image;
+  const long long words = (long long)(bytes / 4);
+  M3_REQUIRE(w[CTX_MAGIC] == kCtxMagic, "ctc_context_validate: not a context image");
+  M3_REQUIRE(w[CTX_V] == V, "ctc_context_validate: image built for V = %d, asked for V = %d", w[CTX_V], V);
+  M3_REQUIRE(w[CTX_WORDS] == words, "ctc_context_validate: image says %d words, has %lld", w[CTX_WORDS], words);
+  const int G = w[CTX_G];
+  M3_REQUIRE(G >= 0 && G <= kCtxMaxGraphs && CTX_HDR_WORDS + (long long)G * CTXG_WORDS <= words,
+             "ctc_context_validate: G = %d outside [0, %d] or its headers outside the image", G, kCtxMaxGraphs);
+  for (int g = 0; g < G; ++g) {
+    CtxGraph c;
+    M3_REQUIRE(ctx_graph_view(w, words, g, &c),
+               "ctc_context_validate: graph %d: n_states outside [1, %d], A outside [1, min(V + 1, %d)] or a table outside the image",
+               g, kCtxMaxStates, kCtxMaxStates);
+    for (int v = 0; v < V; ++v)
+      M3_REQUIRE(c.cls[v] >= 0 && c.cls[v] < c.A, "ctc_context_validate: graph %d: cls[%d] = %d outside [0, %d)", g, v, c.cls[v], c.A);
+    for (long long i = 0; i < (long long)c.n_states * c.A; ++i) {
+      M3_REQUIRE(c.next[i] >= 0 && c.next[i] < c.n_states, "ctc_context_validate: graph %d: next[%lld] = %d outside [0, %d)", g, i,
+                 c.next[i], c.n_states);
+      M3_REQUIRE(std::isfinite(c.delta[i]), "ctc_context_validate: graph %d: delta[%lld] is not finite", g, i);
+    }
+    for (int s = 0; s < c.n_states; ++s)
+      M3_REQUIRE(std::isfinite(c.pot[s]), "ctc_context_validate: graph %d: pot[%d] is not finite", g, s);
+  }
+  return 0;
+}
+
+// ctc_prefix_beam_search_host with the biased ranking: every prefix carries (state, bonus) of its walk through graph
+// `graph` of the image, the second prune ranks by log_add2(pb, pnb) + bonus, the hypotheses come out ordered by
+// log_add2(pb, pnb) + final (final = bonus - pot[state]), stable on the beam order.  image == null or graph == -1: state 0
+// and bonus 0.0 throughout, and x + 0.0 == x: the unbiased routine's result.
+int ctc_prefix_beam_search_ctx_host(const float* top_logp, const int32_t* top_idx, int T, int k, int beam, int blank,
+                                    const void* image, size_t image_bytes, int graph, int32_t* hyp_tokens, int32_t* hyp_len,
+                                    float* hyp_score, float* hyp_bonus, int32_t* hyp_state, int32_t* n_hyps) {
+  M3_REQUIRE(T >= 0 && k > 0 && beam > 0, "ctc_prefix_beam_search_ctx: bad sizes T=%d k=%d beam=%d", T, k, beam);
+  M3_REQUIRE(top_logp && top_idx && hyp_tokens && hyp_len && hyp_score && hyp_bonus && hyp_state && n_hyps,
+             "ctc_prefix_beam_search_ctx: null pointer");
+  CtxGraph g{};
+  const bool biased = image != nullptr && graph != -1;
+  if (biased) {
+    M3_REQUIRE(image_bytes >= CTX_HDR_WORDS * 4, "ctc_prefix_beam_search_ctx: image of %zu bytes", image_bytes);
+    if (int rc = ctc_context_validate(image, image_bytes, ((const int32_t*)image)[CTX_V])) return rc;
+    M3_REQUIRE(ctx_graph_view((const int32_t*)image, (long long)(image_bytes / 4), graph, &g),
+               "ctc_prefix_beam_search_ctx: graph %d is not in the image", graph);
+  }
+  struct CHyp {
+    std::vector<int32_t> prefix;
+    double pb, pnb;
+    int state;
+    double bonus;
+  };
+  std::vector<CHyp> cur(1);
+  cur[0].pb = 0.0;
+  cur[0].pnb = NEG_INF;
+  cur[0].state = 0;
+  cur[0].bonus = 0.0;
+  std::vector<CHyp> next;
+  std::map<std::vector<int32_t>, int> where;
+  std::vector<int> order;
+  std::vector<double> key;
+  auto slot = [&](const std::vector<int32_t>& p, int state, double bonus) -> CHyp& {
+    auto it = where.find(p);
+    if (it == where.end()) {
+      it = where.emplace(p, (int)next.size()).first;
+      next.push_back(CHyp{p, NEG_INF, NEG_INF, state, bonus});
+    }
+    return next[it->second];
+  };
+  std::vector<int32_t> ext;
+  for (int t = 0; t < T; ++t) {
+    next.clear();
+    where.clear();
+    for (int j = 0; j < k; ++j) {
+      const int32_t s = top_idx[(size_t)t * k + j];
+      const double ps = (double)top_logp[(size_t)t * k + j];
+      const int col = biased && s >= 0 && s < g.V ? g.cls[s] : 0;
+      for (size_t h = 0; h < cur.size(); ++h) {
+        const double pb = cur[h].pb, pnb = cur[h].pnb, bonus = cur[h].bonus;
+        const int state = cur[h].state;
+        const std::vector<int32_t>& prefix = cur[h].prefix;
+        const bool has_last = !prefix.empty();
+        int e_state = 0;
+        double e_bonus = bonus;
+        if (biased) {
+          e_state = g.next[(size_t)state * g.A + col];
+          e_bonus = bonus + (double)g.delta[(size_t)state * g.A + col];
+        }
+        if (s == blank) {
+          CHyp& n = slot(prefix, state, bonus);
+          n.pb = log_add3(n.pb, pb + ps, pnb + ps);
+        } else if (has_last && s == prefix.back()) {
+          {
+            CHyp& n = slot(prefix, state, bonus);
+            n.pnb = log_add2(n.pnb, pnb + ps);
+          }
+          ext = prefix;
+          ext.push_back(s);
+          CHyp& n = slot(ext, e_state, e_bonus);
+          n.pnb = log_add2(n.pnb, pb + ps);
+        } else {
+          ext = prefix;
+          ext.push_back(s);
+          CHyp& n = slot(ext, e_state, e_bonus);
+          n.pnb = log_add3(n.pnb, pb + ps, pnb + ps);
+        }
+      }
+    }
+    order.resize(next.size());
+    key.resize(next.size());
+    for (size_t i = 0; i < next.size(); ++i) {
+      order[i] = (int)i;
+      key[i] = log_add2(next[i].pb, next[i].pnb) + next[i].bonus;
+    }
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key[a] > key[b]; });
+    const size_t keep = std::min(order.size(), (size_t)beam);
+    std::vector<CHyp> pruned;
+    pruned.reserve(keep);
+    for (size_t i = 0; i < keep; ++i) pruned.push_back(std::move(next[order[i]]));
+    cur.swap(pruned);
+  }
+  const int n = (int)std::min(cur.size(), (size_t)beam);
+  order.resize(n);
+  key.resize(n);
+  std::vector<double> fin(n);
+  for (int i = 0; i < n; ++i) {
+    order[i] = i;
+    fin[i] = cur[i].bonus - (biased ? (double)g.pot[cur[i].state] : 0.0);
+    key[i] = log_add2(cur[i].pb, cur[i].pnb) + fin[i];
+  }
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key[a] > key[b]; });
+  for (int r = 0; r < n; ++r) {
+    const CHyp& hyp = cur[order[r]];
+    const int L = (int)hyp.prefix.size();
+    hyp_len[r] = L;
+    for (int j = 0; j < L; ++j) hyp_tokens[(size_t)r * T + j] = hyp.prefix[j];
+    for (int j = L; j < T; ++j) hyp_tokens[(size_t)r * T + j] = -1;
+    hyp_score[r] = (float)log_add2(hyp.pb, hyp.pnb);
+    hyp_bonus[r] = (float)fin[order[r]];
+    hyp_state[r] = hyp.state;
+  }
+  *n_hyps = n;
+  return 0;
+}
+
 // ---------------------------------------------------------------- CatSplitCache
 // output[b] = in_cache[b] ++ input[b]  (cache_dim + input_dim values);  out_cache[b] = the last cache_dim values of
 // output[b] (cat_split_cache_kernel.cu:30-107: both of the reference's branches, input_dim >= cache_dim and

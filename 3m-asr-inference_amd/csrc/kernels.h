@@ -355,6 +355,56 @@ int launch_ctc_beam_advance(const m3_ctc_beam_desc* d, void* state, size_t bytes
                             int T_chunk, const int32_t* n_frames, hipStream_t stream);
 int launch_ctc_beam_nbest(const m3_ctc_beam_desc* d, const void* state, size_t bytes, int32_t* hyp_tokens, int32_t* hyp_len,
                           float* hyp_score, int32_t* n_hyps, hipStream_t stream);
+// Context biasing of the prefix beam search (include/m3asr.h, "context set"): one image of 4-byte words,
+//   [magic, G, V, words] then G x [n_states, A, cls, next, delta, pot (word offsets of the tables), 0, 0] then the tables.
+constexpr int32_t kCtxMagic = 0x5843334d;   // "M3CX"
+constexpr int kCtxMaxGraphs = 1024, kCtxMaxStates = 65536;
+constexpr size_t kCtxMaxBytes = (size_t)64 << 20;
+enum { CTX_MAGIC = 0, CTX_G = 1, CTX_V = 2, CTX_WORDS = 3, CTX_HDR_WORDS = 4 };
+enum { CTXG_STATES = 0, CTXG_A = 1, CTXG_CLS = 2, CTXG_NEXT = 3, CTXG_DELTA = 4, CTXG_POT = 5, CTXG_WORDS = 8 };
+struct CtxGraph {
+  const int32_t* cls;    // [V]
+  const int32_t* next;   // [n_states][A]
+  const float* delta;    // [n_states][A]
+  const float* pot;      // [n_states]
+  int n_states, A, V;
+};
+// Graph g of an image of `words` words, for the host and the device alike.  False unless the header, g and all four tables
+// lie inside the image and the limits hold: no address is formed from a value that failed its check.  (Table ENTRIES are
+// checked by ctc_context_validate on the host, and once more where the device search uses one as an index.)
+__host__ __device__ inline bool ctx_graph_view(const int32_t* image, long long words, int g, CtxGraph* out) {
+  if (image == nullptr || words < CTX_HDR_WORDS || image[CTX_MAGIC] != kCtxMagic) return false;
+  const long long G = image[CTX_G], V = image[CTX_V];
+  if (G < 0 || G > kCtxMaxGraphs || V < 1 || CTX_HDR_WORDS + G * CTXG_WORDS > words || g < 0 || g >= G) return false;
+  const int32_t* h = image + CTX_HDR_WORDS + (long long)g * CTXG_WORDS;
+  const long long ns = h[CTXG_STATES], A = h[CTXG_A], first = CTX_HDR_WORDS + G * CTXG_WORDS;
+  if (ns < 1 || ns > kCtxMaxStates || A < 1 || A > V + 1 || A > kCtxMaxStates) return false;
+  const long long off[4] = {h[CTXG_CLS], h[CTXG_NEXT], h[CTXG_DELTA], h[CTXG_POT]};
+  const long long len[4] = {V, ns * A, ns * A, ns};
+  for (int i = 0; i < 4; ++i)
+    if (off[i] < first || off[i] > words || len[i] > words - off[i]) return false;
+  out->cls = image + off[0];
+  out->next = image + off[1];
+  out->delta = (const float*)(image + off[2]);
+  out->pot = (const float*)(image + off[3]);
+  out->n_states = (int)ns;
+  out->A = (int)A;
+  out->V = (int)V;
+  return true;
+}
+int ctc_context_validate(const void* image, size_t bytes, int V);   // decode.hip, host only
+int ctc_prefix_beam_search_ctx_host(const float* top_logp, const int32_t* top_idx, int T, int k, int beam, int blank,
+                                    const void* image, size_t image_bytes, int graph, int32_t* hyp_tokens, int32_t* hyp_len,
+                                    float* hyp_score, float* hyp_bonus, int32_t* hyp_state, int32_t* n_hyps);
+size_t ctc_beam_ctx_state_size(const m3_ctc_beam_desc* d);
+int launch_ctc_beam_ctx_reset(const m3_ctc_beam_desc* d, void* state, size_t bytes, hipStream_t stream,
+                              const int32_t* slots = nullptr, int n = 0);
+int launch_ctc_beam_ctx_advance(const m3_ctc_beam_desc* d, void* state, size_t bytes, const void* image, size_t image_bytes,
+                                const int32_t* graph_of, const float* top_logp, const int32_t* top_idx, int T_chunk,
+                                const int32_t* n_frames, hipStream_t stream);
+int launch_ctc_beam_ctx_nbest(const m3_ctc_beam_desc* d, const void* state, size_t bytes, const void* image, size_t image_bytes,
+                              const int32_t* graph_of, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score,
+                              float* hyp_bonus, int32_t* n_hyps, hipStream_t stream);
 size_t ctc_greedy_stream_state_size(const m3_ctc_greedy_desc* d);
 int launch_ctc_greedy_stream_reset(const m3_ctc_greedy_desc* d, void* state, size_t bytes, hipStream_t stream,
                                    const int32_t* slots = nullptr, int n = 0);

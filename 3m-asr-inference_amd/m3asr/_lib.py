@@ -148,6 +148,13 @@ SIGNATURES = {
     "m3_ctc_beam_reset_slots": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp, _i, _vp]),
     "m3_ctc_beam_advance": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp, _vp, _i, _vp, _vp]),
     "m3_ctc_beam_nbest": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "m3_ctc_context_validate": (_i, [_vp, _sz, _i]),
+    "m3_ctc_prefix_beam_search_ctx": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "m3_ctc_beam_ctx_state_size": (_sz, [_P(CtcBeamDesc)]),
+    "m3_ctc_beam_ctx_reset": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp]),
+    "m3_ctc_beam_ctx_reset_slots": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp, _i, _vp]),
+    "m3_ctc_beam_ctx_advance": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp]),
+    "m3_ctc_beam_ctx_nbest": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "m3_ctc_greedy_stream_state_size": (_sz, [_P(CtcGreedyDesc)]),
     "m3_ctc_greedy_stream_reset": (_i, [_P(CtcGreedyDesc), _vp, _sz, _vp]),
     "m3_ctc_greedy_stream_reset_slots": (_i, [_P(CtcGreedyDesc), _vp, _sz, _vp, _i, _vp]),

@@ -24,6 +24,16 @@ from . import _lib, ops
 from .config import subsampled_len
 
 
+def _same_device(a, b):
+    """torch.device("cuda") names the current device and a tensor's device carries its index: compare what they resolve to"""
+    if a.type != b.type:
+        return False
+    if a.type != "cuda":
+        return a.index == b.index
+    cur = torch.cuda.current_device() if a.index is None or b.index is None else 0
+    return (cur if a.index is None else a.index) == (cur if b.index is None else b.index)
+
+
 class CtcBeamSearch:
     """B prefix beam searches on the device, resumable at any frame boundary (m3_ctc_beam_*).
 
@@ -32,14 +42,27 @@ class CtcBeamSearch:
         ...
         search.nbest()                              # [[(prefix tuple, score)], ...] per utterance, best first
 
+    With context=ContextSet(...) the search is biased towards the set's phrase lists (m3asr.context): see __init__.
+
     The result equals the host routine (ops.ctc_prefix_beam_search_host) on each utterance's frames, however the frames are
     cut into chunks.  max_frames bounds the frames one utterance may consume between resets; past it nbest() raises."""
 
-    def __init__(self, B, beam, max_frames, blank=0, device="cuda", k=None):
-        """k: candidate symbols per frame (default beam, as the reference's logp.topk(beam_size)); needs k <= V."""
+    def __init__(self, B, beam, max_frames, blank=0, device="cuda", k=None, context=None):
+        """k: candidate symbols per frame (default beam, as the reference's logp.topk(beam_size)); needs k <= V.
+        context: a m3asr.context.ContextSet uploaded to `device` -- the search then ranks by CTC score + bonus (hotword
+        biasing, m3_ctc_beam_ctx_*).  Every utterance starts unbiased (graph -1); reset(graph_ids=) / set_context choose."""
         self.desc = ops.ctc_beam_desc(B, beam, max_frames, blank, k)
         self.device = torch.device(device)
-        n = ops.ctc_beam_state_size(self.desc)
+        self.context = context
+        if context is not None:
+            if context.dev is None or not _same_device(context.dev.device, self.device):
+                raise _lib.M3Error("CtcBeamSearch: the ContextSet is not on %s" % self.device)
+            n = ops.ctc_beam_ctx_state_size(self.desc)
+            self.graph_ids = [-1] * self.desc.B               # what each utterance's next reset installs
+            self.graph_of = torch.full((max(self.desc.B, 1),), -1, dtype=torch.int32, device=self.device)[:self.desc.B]
+            self.used = [False] * self.desc.B                 # advanced since its last reset
+        else:
+            n = ops.ctc_beam_state_size(self.desc)
         self.state = torch.empty(max(n, 1), dtype=torch.uint8, device=self.device)
         self.reset()
 
@@ -51,13 +74,49 @@ class CtcBeamSearch:
     def beam(self):
         return self.desc.beam
 
-    def reset(self, stream=None, slots=None):
-        """slots: None = all B searches; else the utterances to restart (a list, or an int32 device tensor)."""
+    def set_context(self, slots, graph_ids):
+        """Graph (position in the ContextSet, -1 = unbiased) of each listed utterance.  It takes effect at the utterance's
+        next reset: a search keeps one graph from a reset to the next, because its nodes hold the context state and bonus
+        of their prefixes.  Raises for an utterance that has consumed frames since its last reset -- restart it with
+        reset(slots=, graph_ids=) instead."""
+        if self.context is None:
+            raise _lib.M3Error("CtcBeamSearch.set_context: the search was built without a context")
+        slots, graph_ids = [int(b) for b in slots], [int(g) for g in graph_ids]
+        if len(slots) != len(graph_ids):
+            raise ValueError("set_context: %d slots, %d graph ids" % (len(slots), len(graph_ids)))
+        for b, g in zip(slots, graph_ids):
+            if not 0 <= b < self.B:
+                raise ValueError("set_context: slot %d outside [0, %d)" % (b, self.B))
+            if not -1 <= g < len(self.context):
+                raise ValueError("set_context: graph %d outside [-1, %d)" % (g, len(self.context)))
+            if self.used[b]:
+                raise _lib.M3Error("set_context: utterance %d has consumed frames since its last reset" % b)
+        for b, g in zip(slots, graph_ids):
+            self.graph_ids[b] = g
+
+    def reset(self, stream=None, slots=None, graph_ids=None):
+        """slots: None = all B searches; else the utterances to restart (a list, or an int32 device tensor).
+        graph_ids (biased search): the graphs the restarted utterances take, one per slot (all B when slots is None)."""
+        which = None
+        if self.context is not None:
+            which = list(range(self.B)) if slots is None else [int(b) for b in (slots.tolist() if torch.is_tensor(slots) else slots)]
+            which = [b for b in which if 0 <= b < self.B]
+            for b in which:
+                self.used[b] = False
+            if graph_ids is not None:
+                self.set_context(which, graph_ids)
+        elif graph_ids is not None:
+            raise _lib.M3Error("CtcBeamSearch.reset: graph_ids without a context")
         with torch.cuda.stream(stream or torch.cuda.current_stream(self.device)):
             if slots is not None and not torch.is_tensor(slots):
                 slots = torch.tensor([int(b) for b in slots], dtype=torch.int32).to(self.device)
             if slots is None or slots.numel() > 0:
-                ops.ctc_beam_reset(self.desc, self.state, slots)
+                if self.context is None:
+                    ops.ctc_beam_reset(self.desc, self.state, slots)
+                else:
+                    ops.ctc_beam_ctx_reset(self.desc, self.state, slots)
+                    if self.B > 0:
+                        self.graph_of.copy_(torch.tensor(self.graph_ids, dtype=torch.int32))
 
     def advance(self, logits, n_frames, stream=None):
         """logits (B, Tc, V) on the device; n_frames (B,) how many of each row's Tc frames are real.  Enqueues m3_ctc_topk and
@@ -70,24 +129,44 @@ class CtcBeamSearch:
                 return
             nf = n_frames.reshape(-1).to(self.device, torch.int32, non_blocking=True)
             top_logp, top_idx = ops.ctc_topk(logits.contiguous(), self.desc.k)
-            ops.ctc_beam_advance(self.desc, self.state, top_logp, top_idx, nf)
+            if self.context is None:
+                ops.ctc_beam_advance(self.desc, self.state, top_logp, top_idx, nf)
+            else:
+                assert V == self.context.vocab_size, "the ContextSet was built for another vocabulary size"
+                self.used = [True] * self.B               # without a sync the host cannot tell which rows had frames
+                ops.ctc_beam_ctx_advance(self.desc, self.state, self.context.dev, self.graph_of, top_logp, top_idx, nf)
 
-    def nbest_tensors(self, stream=None):
-        """(hyp_tokens (B,beam,max_frames), hyp_len (B,beam), hyp_score (B,beam), n_hyps (B,)) on the device."""
+    def _nbest_tensors(self):
+        if self.context is None:
+            toks, hlen, score, n = ops.ctc_beam_nbest(self.desc, self.state)
+            return toks, hlen, score, None, n
+        return ops.ctc_beam_ctx_nbest(self.desc, self.state, self.context.dev, self.graph_of)
+
+    def nbest_tensors(self, stream=None, detail=False):
+        """(hyp_tokens (B,beam,max_frames), hyp_len (B,beam), hyp_score (B,beam), n_hyps (B,)) on the device; detail: with
+        hyp_bonus (B,beam) before n_hyps (zeros for a search without a context)."""
         with torch.cuda.stream(stream or torch.cuda.current_stream(self.device)):
-            return ops.ctc_beam_nbest(self.desc, self.state)
+            toks, hlen, score, bonus, n = self._nbest_tensors()
+            if not detail:
+                return toks, hlen, score, n
+            return toks, hlen, score, torch.zeros_like(score) if bonus is None else bonus, n
 
-    def nbest(self, stream=None, slots=None):
-        """slots: None = every utterance; else only the listed ones, in that order (the others may have failed or be idle)."""
+    def nbest(self, stream=None, slots=None, detail=False):
+        """slots: None = every utterance; else only the listed ones, in that order (the others may have failed or be idle).
+        [(prefix, CTC score)] per utterance, best first -- with a context, best by CTC score + bonus; detail: [(prefix, CTC
+        score, bonus)], bonus = the part of the context bonus that is final for that prefix."""
         with torch.cuda.stream(stream or torch.cuda.current_stream(self.device)):   # the copies wait for the search's stream
-            toks, hlen, score, n = (t.cpu() for t in ops.ctc_beam_nbest(self.desc, self.state))
+            toks, hlen, score, bonus, n = (None if t is None else t.cpu() for t in self._nbest_tensors())
         out = []
         for b in (range(self.B) if slots is None else [int(x) for x in slots]):
             nb = int(n[b])
             if nb < 0:
                 raise _lib.M3Error("ctc beam search: utterance %d consumed more than max_frames = %d frames"
                                    % (b, self.desc.max_frames))
-            out.append([(tuple(toks[b, i, :int(hlen[b, i])].tolist()), float(score[b, i])) for i in range(nb)])
+            hyps = [(tuple(toks[b, i, :int(hlen[b, i])].tolist()), float(score[b, i])) for i in range(nb)]
+            if detail:
+                hyps = [h + (0.0 if bonus is None else float(bonus[b, i]),) for i, h in enumerate(hyps)]
+            out.append(hyps)
         return out
 
 
@@ -183,20 +262,25 @@ class StreamingCtcDecoder:
     Over a slot-mode encoder (engine.streaming(..., independent=True)) the streams are independent here too: a slot that is
     idle in a step consumes no frame in either search, and reset / partial / finish take `slots=[...]`."""
 
-    def __init__(self, streaming_encoder, beam, blank=0):
+    def __init__(self, streaming_encoder, beam, blank=0, context=None):
+        """context: a m3asr.context.ContextSet on the engine's device (hotword biasing of the beam search; the greedy
+        search is not biased); reset(graph_ids=) chooses each stream's graph, -1 = unbiased."""
         self.st = streaming_encoder
+        self.context = context
         e = streaming_encoder.eng
         self.c = streaming_encoder.c
         B, max_frames = int(streaming_encoder.desc.B), int(streaming_encoder.desc.max_frames)
-        self.beam = CtcBeamSearch(B, beam, max_frames, blank, e.device)
+        self.beam = CtcBeamSearch(B, beam, max_frames, blank, e.device, context=context)
         self.gdesc = ops.ctc_greedy_stream_desc(B, max_frames, blank)
         self.gstate = torch.empty(max(ops.ctc_greedy_stream_state_size(self.gdesc), 1), dtype=torch.uint8, device=e.device)
         self.frame_ids = torch.empty(B, self.c, dtype=torch.int32, device=e.device)
         self.n_out = torch.zeros(B, dtype=torch.int32, device=e.device)
         self.reset()
 
-    def reset(self, slots=None):
-        """Restart all streams, or (slot-mode encoder) the listed slots: encoder state, beam search and greedy search."""
+    def reset(self, slots=None, graph_ids=None):
+        """Restart all streams, or (slot-mode encoder) the listed slots: encoder state, beam search and greedy search.
+        graph_ids (decoder with a context): the graph each restarted stream takes, one per slot; a stream restarted without
+        one keeps the graph it had."""
         e = self.st.eng
         if slots is None:
             self.st.reset()
@@ -204,11 +288,14 @@ class StreamingCtcDecoder:
             self.st.reset(slots=slots)
         with torch.cuda.stream(e.stream):
             if slots is None:
-                self.beam.reset(e.stream)
+                self.beam.reset(e.stream, graph_ids=graph_ids)
                 ops.ctc_greedy_stream_reset(self.gdesc, self.gstate)
             elif len(slots) > 0:
                 lst = torch.tensor([int(b) for b in slots], dtype=torch.int32).to(e.device)
-                self.beam.reset(e.stream, slots=lst)
+                if self.context is None:
+                    self.beam.reset(e.stream, slots=lst, graph_ids=graph_ids)
+                else:
+                    self.beam.reset(e.stream, slots=[int(b) for b in slots], graph_ids=graph_ids)
                 ops.ctc_greedy_stream_reset(self.gdesc, self.gstate, lst)
 
     def frames_of(self, valid):
@@ -247,9 +334,10 @@ class StreamingCtcDecoder:
         nb = self.beam.nbest(e.stream, slots=slots)
         return [h[0] for h in nb], self.greedy(slots)
 
-    def finish(self, slots=None):
-        """n-best [(prefix, score)] per stream, best first (slots: only the listed streams, in that order)."""
-        return self.beam.nbest(self.st.eng.stream, slots=slots)
+    def finish(self, slots=None, detail=False):
+        """n-best [(prefix, score)] per stream, best first (slots: only the listed streams, in that order); detail:
+        [(prefix, CTC score, bonus)] as CtcBeamSearch.nbest."""
+        return self.beam.nbest(self.st.eng.stream, slots=slots, detail=detail)
 
     def decode(self, feat, feat_len, use_graph=True):
         """Whole utterances chunk by chunk (the windows and frame counts of StreamingEncoder.decode) -> finish()."""

@@ -518,6 +518,89 @@ def ctc_beam_nbest(desc, state):
     return toks, hlen, score, n
 
 
+# ---- context biasing (m3asr.context builds the images)
+def ctc_context_validate(image, V):
+    """m3_ctc_context_validate on a HOST image (numpy int32 words); raises M3Error naming the first offence."""
+    import numpy as np
+    img = np.ascontiguousarray(image)
+    check(_lib.load().m3_ctc_context_validate(img.ctypes.data_as(C.c_void_p), img.nbytes, int(V)), "m3_ctc_context_validate")
+
+
+def ctc_prefix_beam_search_ctx_host(top_logp, top_idx, beam, blank=0, image=None, graph=0):
+    """ctc_prefix_beam_search_host with the biased ranking of graph `graph` of a HOST image (numpy int32 words; None =
+    unbiased): [(prefix tuple, ctc score, bonus = final, context state)], ordered by ctc score + bonus."""
+    import numpy as np
+    lib = _lib.load()
+    lp = np.ascontiguousarray(top_logp, dtype=np.float32)
+    ix = np.ascontiguousarray(top_idx, dtype=np.int32)
+    T, k = lp.shape
+    assert ix.shape == (T, k)
+    if T == 0:
+        return [(tuple(), 0.0, 0.0, 0)]
+    img = None if image is None else np.ascontiguousarray(image)
+    toks = np.empty((beam, T), dtype=np.int32)
+    hlen = np.empty(beam, dtype=np.int32)
+    score = np.empty(beam, dtype=np.float32)
+    bonus = np.empty(beam, dtype=np.float32)
+    state = np.empty(beam, dtype=np.int32)
+    n = C.c_int32(0)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    check(lib.m3_ctc_prefix_beam_search_ctx(vp(lp), vp(ix), T, k, int(beam), int(blank), None if img is None else vp(img),
+                                            0 if img is None else img.nbytes, int(graph), vp(toks), vp(hlen), vp(score),
+                                            vp(bonus), vp(state), C.cast(C.byref(n), C.c_void_p)),
+          "m3_ctc_prefix_beam_search_ctx")
+    return [(tuple(int(v) for v in toks[i, :hlen[i]]), float(score[i]), float(bonus[i]), int(state[i])) for i in range(n.value)]
+
+
+def ctc_beam_ctx_state_size(desc):
+    """bytes of device state of the biased search: the unbiased layout, then every node's context state and bonus."""
+    n = _lib.load().m3_ctc_beam_ctx_state_size(C.byref(desc))
+    if n == 0 and desc.B > 0:
+        raise _lib.M3Error("m3_ctc_beam_ctx_state_size failed: " + _lib.last_error())
+    return n
+
+
+def ctc_beam_ctx_reset(desc, state, slots=None):
+    if slots is not None:
+        check(_lib.load().m3_ctc_beam_ctx_reset_slots(C.byref(desc), _p(state), state.numel() * state.element_size(), _i32(slots),
+                                                      slots.numel(), _stream()), "m3_ctc_beam_ctx_reset_slots")
+        return
+    check(_lib.load().m3_ctc_beam_ctx_reset(C.byref(desc), _p(state), state.numel() * state.element_size(), _stream()),
+          "m3_ctc_beam_ctx_reset")
+
+
+def _image(image):
+    """(pointer, bytes) of a device context image (int32 words; None = no graphs)"""
+    return (None, 0) if image is None else (_i32(image), image.numel() * 4)
+
+
+def ctc_beam_ctx_advance(desc, state, image, graph_of, top_logp, top_idx, n_frames):
+    """ctc_beam_advance with the device image (int32 words, or None) and graph_of (B,) int32 on the device (-1 = unbiased)."""
+    B, Tc, k = top_logp.shape
+    assert B == desc.B and k == desc.k and tuple(top_idx.shape) == (B, Tc, k) and n_frames.numel() == B and graph_of.numel() == B
+    img, nbytes = _image(image)
+    check(_lib.load().m3_ctc_beam_ctx_advance(C.byref(desc), _p(state), state.numel() * state.element_size(), img, nbytes,
+                                              _i32(graph_of), _f32(top_logp), _i32(top_idx), Tc, _i32(n_frames), _stream()),
+          "m3_ctc_beam_ctx_advance")
+
+
+def ctc_beam_ctx_nbest(desc, state, image, graph_of):
+    """-> (hyp_tokens, hyp_len, hyp_score (the CTC score), hyp_bonus (B,beam), n_hyps), ordered by CTC score + bonus; device."""
+    dev = state.device
+    B, beam, F = desc.B, desc.beam, desc.max_frames
+    assert graph_of.numel() == B
+    toks = torch.empty(B, beam, F, dtype=torch.int32, device=dev)
+    hlen = torch.empty(B, beam, dtype=torch.int32, device=dev)
+    score = torch.empty(B, beam, dtype=torch.float32, device=dev)
+    bonus = torch.empty(B, beam, dtype=torch.float32, device=dev)
+    n = torch.empty(B, dtype=torch.int32, device=dev)
+    img, nbytes = _image(image)
+    check(_lib.load().m3_ctc_beam_ctx_nbest(C.byref(desc), _p(state), state.numel() * state.element_size(), img, nbytes,
+                                            _i32(graph_of), _p(toks), _p(hlen), _p(score), _p(bonus), _p(n), _stream()),
+          "m3_ctc_beam_ctx_nbest")
+    return toks, hlen, score, bonus, n
+
+
 def ctc_greedy_stream_desc(B, max_frames, blank=0):
     d = _lib.CtcGreedyDesc(int(B), int(max_frames), int(blank))
     if _lib.load().m3_ctc_greedy_stream_state_size(C.byref(_lib.CtcGreedyDesc(1, d.max_frames, d.blank))) == 0:

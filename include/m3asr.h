@@ -402,6 +402,44 @@ int m3_ctc_beam_advance(const m3_ctc_beam_desc* desc, void* state, size_t state_
                         const int32_t* top_idx, int T_chunk, const int32_t* n_frames, m3_stream stream);
 int m3_ctc_beam_nbest(const m3_ctc_beam_desc* desc, const void* state, size_t state_bytes, int32_t* hyp_tokens,
                       int32_t* hyp_len, float* hyp_score, int32_t* n_hyps, m3_stream stream);
+/* Context biasing of the prefix beam search (hotwords; csrc/ctc_beam.hip, csrc/decode.hip).  The searches know a weighted
+ * deterministic token automaton, nothing about phrases: cls [V] int32 maps a token to a column in [0, A) (0 = in no phrase),
+ * next [n_states][A] int32 is total (state 0 is the start), delta [n_states][A] float32 is added to the prefix's bonus on
+ * that arc, pot [n_states] float32 is the part of the bonus that is still provisional in that state.  For a prefix y,
+ * state(y) and bonus(y) come from walking y from state 0, the bonus summed in double left to right; final(y) = bonus(y) -
+ * pot[state(y)].  The second prune ranks by log(p_blank + p_non_blank) + bonus (first-touch tie-break as before); the
+ * hypotheses are reported ordered by log(p_blank + p_non_blank) + final, stable on the beam order.
+ * A CONTEXT SET is one image of 4-byte little-endian words holding G >= 0 graphs:
+ *   [0x5843334d, G, V, words]   G x [n_states, A, cls, next, delta, pot, 0, 0]   the tables
+ * (cls .. pot: word offsets of the graph's tables from the start of the image).  Limits: G <= 1024, n_states <= 65536,
+ * A <= min(V + 1, 65536), image <= 64 MiB.  m3asr.context (Python) compiles phrase lists into such images.
+ * m3_ctc_context_validate: host-only check of a HOST image for vocabulary size V: header, limits, every table inside the
+ *   image, every cls entry in [0, A), every next entry in [0, n_states), delta and pot finite.  Run it on the host copy
+ *   before the image is uploaded; the device search only sees images that passed.  Independently the kernels range-check
+ *   graph_of, the header and every index they form an address from (a failed check means "unbiased" / column 0 / state 0).
+ * m3_ctc_prefix_beam_search_ctx: m3_ctc_prefix_beam_search with the biased ranking, one utterance, graph `graph` of a host
+ *   image (validated inside the call).  Adds hyp_bonus [beam] (= final) and hyp_state [beam]; hyp_score stays the CTC score.
+ *   image NULL (or graph -1): exactly what m3_ctc_prefix_beam_search returns, bonus and state 0.
+ * m3_ctc_beam_ctx_*: the device search with the biased ranking.  The state is m3_ctc_beam_state_size bytes laid out as for
+ *   m3_ctc_beam_*, byte for byte, then per utterance ctx_state [1 + max_frames * beam] int32 and ctx_bonus [...] double
+ *   (every trie node's context state and bonus: a prefix that leaves the beam and returns finds them again).
+ *   _advance / _nbest take the DEVICE image (NULL, 0 = no graphs) and graph_of [B] (device int32; a value outside [0, G),
+ *   -1 by convention, = this utterance is unbiased, and its result is m3_ctc_beam_*'s bit for bit).  An utterance keeps one
+ *   graph from a reset to the next.  _nbest additionally writes hyp_bonus [B][beam] (= final). */
+int m3_ctc_context_validate(const void* image, size_t image_bytes, int V);
+int m3_ctc_prefix_beam_search_ctx(const float* top_logp, const int32_t* top_idx, int T, int k, int beam, int blank,
+                                  const void* image, size_t image_bytes, int graph, int32_t* hyp_tokens, int32_t* hyp_len,
+                                  float* hyp_score, float* hyp_bonus, int32_t* hyp_state, int32_t* n_hyps);
+size_t m3_ctc_beam_ctx_state_size(const m3_ctc_beam_desc* desc);
+int m3_ctc_beam_ctx_reset(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, m3_stream stream);
+int m3_ctc_beam_ctx_reset_slots(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const int32_t* slots, int n,
+                                m3_stream stream);
+int m3_ctc_beam_ctx_advance(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const void* image, size_t image_bytes,
+                            const int32_t* graph_of, const float* top_logp, const int32_t* top_idx, int T_chunk,
+                            const int32_t* n_frames, m3_stream stream);
+int m3_ctc_beam_ctx_nbest(const m3_ctc_beam_desc* desc, const void* state, size_t state_bytes, const void* image,
+                          size_t image_bytes, const int32_t* graph_of, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score,
+                          float* hyp_bonus, int32_t* n_hyps, m3_stream stream);
 /* Greedy search chunk by chunk: per stream the previous frame's argmax is carried across calls and the collapsed tokens are
  * appended to a buffer inside the state (m3_ctc_greedy_stream_state_size bytes, device).  After any sequence of advances the
  * tokens equal m3_ctc_greedy on the concatenation of the frames each stream was given.

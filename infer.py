@@ -7,7 +7,12 @@
 feat.npy is (B,T,idim) float32; feat_len = feat.shape[1] for every utterance, as in the reference (infer.py:111-113).
 speech.wav (-w, instead of -i) is a 16 kHz mono 16-bit RIFF file; its log-Mel frames are computed on the device by the
 library's Kaldi-style front end (m3asr.frontend.Fbank with the plan's input_dim mel bins) and run as a batch of one.
-Prints ``time=...ms`` for one forward after a warm-up and the output's shape / sum (reference :81-103)."""
+Prints ``time=...ms`` for one forward after a warm-up and the output's shape / sum (reference :81-103).
+
+    python3 infer.py -p encoder.plan -w speech.wav --hotwords words.txt [--hotword-score 3.0] [--beam 10]
+
+words.txt holds one phrase per line as space-separated token ids (the project has no tokenizer).  The output scores are then
+searched twice on the device, plain and biased towards the phrases (m3asr.context), and the best hypothesis of each is printed."""
 import argparse
 import os
 import sys
@@ -31,6 +36,26 @@ def read_wav(path):
         return np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").astype(np.int16).reshape(1, -1)
 
 
+def print_hotword_search(scores, device, args):
+    """Best prefix beam hypothesis of every utterance without and with the hotword list (blank = 0, all T' frames)."""
+    import torch
+    from m3asr.context import ContextGraph, ContextSet, read_phrases
+    from m3asr.decode import CtcBeamSearch
+    x = torch.from_numpy(np.ascontiguousarray(scores, dtype=np.float32)).to(device)
+    x = x.reshape(-1, x.shape[-2], x.shape[-1])
+    B, T, V = x.shape
+    ctx = ContextSet([ContextGraph(read_phrases(args.hotwords), V, score=args.hotword_score)], device=device)
+    lens = torch.full((B,), T, dtype=torch.int32)
+    plain = CtcBeamSearch(B, args.beam, T, device=device)
+    plain.advance(x, lens)
+    biased = CtcBeamSearch(B, args.beam, T, device=device, context=ctx)
+    biased.reset(graph_ids=[0] * B)
+    biased.advance(x, lens)
+    for b, (u, h) in enumerate(zip(plain.nbest(), biased.nbest(detail=True))):
+        print("utt %d plain:  score=%.4f tokens=%s" % (b, u[0][1], " ".join(str(t) for t in u[0][0])))
+        print("utt %d biased: score=%.4f bonus=%.4f tokens=%s" % (b, h[0][1], h[0][2], " ".join(str(t) for t in h[0][0])))
+
+
 def main(args):
     logger = trt_helper.init_trt_plugin(trt.Logger.INFO, "libm3asr_hip.so")
     helper = trt_helper.InferHelper(args.plan_name, logger)
@@ -46,6 +71,8 @@ def main(args):
         print("outputs.shape:" + str(o.shape))
         print("outputs.sum:" + str(o.sum()))
         print(o)
+    if args.hotwords:
+        print_hotword_search(outputs[0], helper.engine.device, args)
     if base is not None:
         print("compare_output=%s, dtype=%s, shape=%s" % (args.compare_output_file, base[0].dtype, base[0].shape))
         print("output.sum:" + str(base[0].sum()))
@@ -58,4 +85,7 @@ if __name__ == "__main__":
     src.add_argument("-i", "--input_file", help="The input feat.npy file path.")
     src.add_argument("-w", "--wav", dest="wav_file", help="A 16 kHz mono 16-bit wav file, instead of feat.npy.")
     p.add_argument("-o", "--compare_output_file", required=False, help="The compare output .npy file path.")
+    p.add_argument("--hotwords", help="Phrase list: one phrase of space-separated token ids per line.")
+    p.add_argument("--hotword-score", type=float, default=3.0, help="Bonus per matched token (log domain).")
+    p.add_argument("--beam", type=int, default=10, help="Beam size of the prefix beam searches run with --hotwords.")
     main(p.parse_args())

@@ -2,7 +2,10 @@
 """The device prefix beam search (m3_ctc_beam_advance) against the host routine (m3_ctc_prefix_beam_search) on a configs[2]-like
 batch: B = 16 utterances of T' = 125 output frames, V = 1434, beam = k = 10, synthetic logits.
 
-  python tools/bench_ctc_beam.py [--batch 16] [--frames 125] [--beam 10] [--chunk 16] [--reps 5]
+  python tools/bench_ctc_beam.py [--batch 16] [--frames 125] [--beam 10] [--chunk 16] [--reps 5] [--context N_PHRASES]
+
+--context N: the biased search (m3_ctc_beam_ctx_advance) with one graph of N random phrases of 2..6 tokens (N = 0: an empty
+graph, the cost of the biased kernel alone), next to the unbiased one; its host column is m3_ctc_prefix_beam_search_ctx.
 
 Device: one advance over all frames, and the same frames in chunks of --chunk (one advance per chunk), timed with hipEvents
 (top-k excluded: it is the same launch for both searches); run under `rocprofv3 --kernel-trace --stats` for kernel times.
@@ -31,6 +34,7 @@ def main():
     ap.add_argument("--beam", type=int, default=10)
     ap.add_argument("--chunk", type=int, default=16)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--context", type=int, default=None, metavar="N_PHRASES")
     args = ap.parse_args()
     B, T, V, beam = args.batch, args.frames, args.vocab, args.beam
     g = torch.Generator().manual_seed(0)
@@ -43,10 +47,10 @@ def main():
     nfc = [torch.full((B,), c, dtype=torch.int32, device="cuda") for _, c in chunks]
     lpc = [(lp[:, t0:t0 + c].contiguous(), ix[:, t0:t0 + c].contiguous()) for t0, c in chunks]
 
-    def timed(fn):
+    def timed(fn, reset=lambda: ops.ctc_beam_reset(desc, state)):
         ts = []
         for _ in range(args.reps + 1):
-            ops.ctc_beam_reset(desc, state)
+            reset()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             fn()
@@ -64,11 +68,34 @@ def main():
         for b in range(B):
             ops.ctc_prefix_beam_search_host(lph[b], ixh[b], beam, 0)
         hs.append((time.perf_counter() - t0) * 1e3)
-    print(json.dumps({"metric": "CTC prefix beam search, B %d x T' %d, V %d, beam = k = %d" % (B, T, V, beam),
-                      "device_one_advance_ms": round(one, 4),
-                      "device_chunked_ms": {"chunk": args.chunk, "advances": len(chunks), "total": round(per, 4),
-                                            "per_advance": round(per / len(chunks), 4)},
-                      "host_routine_ms": round(float(np.median(hs)), 4), "data": "synthetic"}))
+    out = {"metric": "CTC prefix beam search, B %d x T' %d, V %d, beam = k = %d" % (B, T, V, beam),
+           "device_one_advance_ms": round(one, 4),
+           "device_chunked_ms": {"chunk": args.chunk, "advances": len(chunks), "total": round(per, 4),
+                                 "per_advance": round(per / len(chunks), 4)},
+           "host_routine_ms": round(float(np.median(hs)), 4), "data": "synthetic"}
+    if args.context is not None:
+        from m3asr.context import ContextGraph, ContextSet
+        rng = np.random.default_rng(0)
+        phrases = set()
+        while len(phrases) < args.context:
+            phrases.add(tuple(int(t) for t in rng.integers(1, V, int(rng.integers(2, 7)))))
+        cs = ContextSet([ContextGraph([list(p) for p in sorted(phrases)], V)], device="cuda")
+        cstate = torch.empty(ops.ctc_beam_ctx_state_size(desc), dtype=torch.uint8, device="cuda")
+        go = torch.zeros(B, dtype=torch.int32, device="cuda")
+        creset = lambda: ops.ctc_beam_ctx_reset(desc, cstate)
+        c_one = timed(lambda: ops.ctc_beam_ctx_advance(desc, cstate, cs.dev, go, lp, ix, nf), creset)
+        c_per = timed(lambda: [ops.ctc_beam_ctx_advance(desc, cstate, cs.dev, go, a, b, n) for (a, b), n in zip(lpc, nfc)], creset)
+        hs = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            for b in range(B):
+                ops.ctc_prefix_beam_search_ctx_host(lph[b], ixh[b], beam, 0, cs.image, 0)
+            hs.append((time.perf_counter() - t0) * 1e3)
+        out["context"] = {"phrases": args.context, "states": cs.graphs[0].n_states, "image_bytes": int(cs.image.nbytes),
+                          "device_one_advance_ms": round(c_one, 4),
+                          "device_chunked_ms": {"total": round(c_per, 4), "per_advance": round(c_per / len(chunks), 4)},
+                          "host_routine_ms": round(float(np.median(hs)), 4)}
+    print(json.dumps(out))
 
 
 if __name__ == "__main__":

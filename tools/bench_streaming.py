@@ -10,6 +10,7 @@ lives on the device).  Prints one JSON line: ms per chunk (p50 / p99 over all st
 audio seconds per chunk, real-time factor = compute time / audio time, streams one GPU could serve in real time.
 --beam N (> 0): also time the CTC decode of every chunk (StreamingCtcDecoder: top-k + prefix beam advance + streaming greedy,
 on the engine stream behind the chunk forward) and add "decode_ms_per_chunk" to the line.
+--context N (with --beam): the beam search of every stream is biased by one graph of N random phrases (m3asr.context).
 --independent: slot mode (m3_engine_forward_chunk_slots), every stream with its own position; --stagger N: stream b starts N
 steps after stream b - 1 and ends as many steps later (idle slots before and after).  The line then also carries "mode" and
 the mean number of live slots per timed step.
@@ -44,6 +45,7 @@ def main():
     ap.add_argument("--layers", type=int, default=18)
     ap.add_argument("--seconds", type=float, default=20.0, help="audio per stream")
     ap.add_argument("--beam", type=int, default=0, help="> 0: decode every chunk with a prefix beam search of this width")
+    ap.add_argument("--context", type=int, default=None, metavar="N_PHRASES", help="with --beam: bias the beam search by N phrases")
     ap.add_argument("--independent", action="store_true", help="slot mode: every stream has its own chunk counter")
     ap.add_argument("--stagger", type=int, default=0, help="slot mode: stream b starts this many steps after stream b - 1")
     ap.add_argument("--audio", action="store_true", help="also time the chunks fed samples through the log-Mel front end")
@@ -64,12 +66,19 @@ def main():
     dec = None
     if args.beam > 0:
         from m3asr.decode import StreamingCtcDecoder
-        dec = StreamingCtcDecoder(st, args.beam)
+        ctx = None
+        if args.context is not None:
+            from m3asr.context import ContextGraph, ContextSet
+            prng, phrases = np.random.default_rng(0), set()
+            while len(phrases) < args.context:
+                phrases.add(tuple(int(t) for t in prng.integers(1, cfg.output_dim, int(prng.integers(2, 7)))))
+            ctx = ContextSet([ContextGraph([list(p) for p in sorted(phrases)], cfg.output_dim)], device=eng.device)
+        dec = StreamingCtcDecoder(st, args.beam, context=ctx)
         n_out = torch.full((args.batch,), args.chunk, dtype=torch.int32, device=eng.device)
     times, dtimes, live = [], [], []
     for rep in range(3):
         if dec is not None:
-            dec.reset()
+            dec.reset(graph_ids=None if dec.context is None else [0] * args.batch)
         else:
             st.reset()
         for n in range(n_steps):
@@ -140,6 +149,8 @@ def main():
                                         "samples_per_window": n_win}
     if dec is not None:
         d = np.sort(np.array(dtimes))
+        if dec.context is not None:
+            out["context_phrases"] = args.context
         out["decode_ms_per_chunk"] = {"beam": args.beam, "p50": round(float(np.median(d)), 4),
                                       "p99": round(float(d[int(0.99 * (len(d) - 1))]), 4), "min": round(float(d[0]), 4)}
     print(json.dumps(out))
