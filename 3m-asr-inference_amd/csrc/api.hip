@@ -464,6 +464,38 @@ int m3_ctc_beam_ctx_nbest(const m3_ctc_beam_desc* desc, const void* state, size_
   return launch_ctc_beam_ctx_nbest(desc, state, state_bytes, image, image_bytes, graph_of, hyp_tokens, hyp_len, hyp_score,
                                    hyp_bonus, n_hyps, (hipStream_t)stream);
 }
+int m3_ctc_lm_validate(const void* image, size_t image_bytes, int V) { return ctc_lm_validate(image, image_bytes, V); }
+int m3_ctc_prefix_beam_search_lm(const float* top_logp, const int32_t* top_idx, int T, int k, int beam, int blank,
+                                 const void* image, size_t image_bytes, int graph, const void* lm_image, size_t lm_bytes,
+                                 double alpha, double beta, int use_eos, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score,
+                                 float* hyp_bonus, int32_t* hyp_state, float* hyp_lm, int32_t* n_hyps) {
+  return ctc_prefix_beam_search_lm_host(top_logp, top_idx, T, k, beam, blank, image, image_bytes, graph, lm_image, lm_bytes, alpha,
+                                        beta, use_eos, hyp_tokens, hyp_len, hyp_score, hyp_bonus, hyp_state, hyp_lm, n_hyps);
+}
+size_t m3_ctc_beam_lm_state_size(const m3_ctc_beam_desc* desc) { return ctc_beam_lm_state_size(desc); }
+int m3_ctc_beam_lm_reset(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, m3_stream stream) {
+  return launch_ctc_beam_lm_reset(desc, state, state_bytes, (hipStream_t)stream);
+}
+int m3_ctc_beam_lm_reset_slots(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const int32_t* slots, int n,
+                               m3_stream stream) {
+  M3_REQUIRE(n == 0 || slots != nullptr, "ctc_beam_lm_reset_slots: null slot list");
+  if (n == 0) return 0;
+  return launch_ctc_beam_lm_reset(desc, state, state_bytes, (hipStream_t)stream, slots, n);
+}
+int m3_ctc_beam_lm_advance(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const void* image, size_t image_bytes,
+                           const int32_t* graph_of, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha,
+                           double beta, const float* top_logp, const int32_t* top_idx, int T_chunk, const int32_t* n_frames,
+                           m3_stream stream) {
+  return launch_ctc_beam_lm_advance(desc, state, state_bytes, image, image_bytes, graph_of, lm_image, lm_bytes, lm_on, alpha, beta,
+                                    top_logp, top_idx, T_chunk, n_frames, (hipStream_t)stream);
+}
+int m3_ctc_beam_lm_nbest(const m3_ctc_beam_desc* desc, const void* state, size_t state_bytes, const void* image, size_t image_bytes,
+                         const int32_t* graph_of, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha,
+                         double beta, int use_eos, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score, float* hyp_bonus,
+                         float* hyp_lm, int32_t* n_hyps, m3_stream stream) {
+  return launch_ctc_beam_lm_nbest(desc, state, state_bytes, image, image_bytes, graph_of, lm_image, lm_bytes, lm_on, alpha, beta,
+                                  use_eos, hyp_tokens, hyp_len, hyp_score, hyp_bonus, hyp_lm, n_hyps, (hipStream_t)stream);
+}
 size_t m3_ctc_greedy_stream_state_size(const m3_ctc_greedy_desc* desc) { return ctc_greedy_stream_state_size(desc); }
 int m3_ctc_greedy_stream_reset(const m3_ctc_greedy_desc* desc, void* state, size_t state_bytes, m3_stream stream) {
   return launch_ctc_greedy_stream_reset(desc, state, state_bytes, (hipStream_t)stream);

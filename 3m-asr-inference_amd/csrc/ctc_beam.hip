@@ -75,6 +75,14 @@ CtxLayout ctx_layout(const BeamLayout& L, int B) {
   return C;
 }
 
+// LM fusion appends, behind the context blocks (which stay as they are, byte for byte), per utterance the LM state and the LM
+// sum of every trie node: lm_state[pool] int32, lm_sum[pool] double -- the shape of a context block, so one layout type serves.
+CtxLayout lm_layout(const BeamLayout& L, int B) {
+  CtxLayout M = ctx_layout(L, B);
+  M.base += (size_t)B * M.stride;
+  return M;
+}
+
 int check_beam_desc(const m3_ctc_beam_desc* d) {
   M3_REQUIRE(d != nullptr, "ctc_beam: null descriptor");
   M3_REQUIRE(d->B >= 0, "ctc_beam: B = %d < 0", d->B);
@@ -158,11 +166,25 @@ struct CtxArgs {
   const int32_t* graph_of;
 };
 struct NoCtx {};
+// What the fused search (LM) adds to the biased one.  M: the layout of the LM blocks (`bonus` is the offset of lm_sum).
+struct LmArgs : CtxArgs {
+  CtxLayout M;
+  const int32_t* lm;
+  long long lm_words;
+  const int32_t* lm_on;
+  double alpha, beta;
+};
+// A beam entry's back-off chain, staged in LDS once per frame: per level the arcs [lo, hi) and the weight gathered above it.
+constexpr int kLmLevels = kLmMaxOrder, kLmW = kLmMaxOrder + 1;
 __device__ __forceinline__ int ctx_in_range(int v, int n) { return (unsigned)v < (unsigned)n ? v : 0; }
 
 // CTX: every trie node carries (context state, bonus), pure functions of its prefix; candidates are ranked by
 // log_add2(pb, pnb) + bonus.  An utterance whose graph_of is outside [0, G) runs with state 0 and bonus 0.0 throughout.
-template <bool CTX, class Ctx>
+// LM (on top of CTX): every trie node also carries (LM state, LM sum) of its prefix, and an utterance with lm_on != 0 and a
+// well-formed LM image ranks by (log_add2(pb, pnb) + bonus) + (alpha lm + beta depth).  Per frame each beam entry's back-off
+// chain is staged in LDS (wave 1, while wave 0 reads the frame), so an extension's walk (lm_step, kernels.h, term for term)
+// goes to memory only for its binary-search probes and the arc it finds.  With lm_on == 0 nothing is added to the key.
+template <bool CTX, class Ctx, bool LM = false>
 __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayout L, int beam, int k, int blank, int max_frames,
                                                                         char* state, const float* __restrict__ top_logp,
                                                                         const int32_t* __restrict__ top_idx, int T_chunk,
@@ -180,6 +202,23 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
     char* c = state + cx.C.base + (size_t)b * cx.C.stride;
     cs = (int32_t*)c;
     cb = (double*)(c + cx.C.bonus);
+  }
+  // LM only: the beam's and the survivors' (LM state, LM sum), the staged chains, what each extension's walk found
+  __shared__ int s_lst[LM ? kBeamMax : 1], n_lst[LM ? kBeamMax : 1], lv_n[LM ? kBeamMax : 1];
+  __shared__ double s_lsum[LM ? kBeamMax : 1], n_lsum[LM ? kBeamMax : 1];
+  __shared__ int lv_lo[LM ? kBeamMax * kLmLevels : 1], lv_hi[LM ? kBeamMax * kLmLevels : 1];
+  __shared__ double lv_w[LM ? kBeamMax * kLmW : 1];
+  __shared__ int c_lst[LM ? kBeamMax * kTopkMax : 1];
+  __shared__ double c_lsum[LM ? kBeamMax * kTopkMax : 1];
+  int32_t* ls = nullptr;
+  double* lsm = nullptr;
+  LmView lm{};
+  bool fused = false;
+  if constexpr (LM) {                             // uniform: the header goes through the scalar cache
+    char* c = state + cx.M.base + (size_t)b * cx.M.stride;
+    ls = (int32_t*)c;
+    lsm = (double*)(c + cx.M.bonus);
+    fused = cx.lm_on[b] != 0 && lm_view(cx.lm, cx.lm_words, &lm);
   }
   // current beam (best first) and its nodes
   __shared__ int s_node[kBeamMax], s_par[kBeamMax], s_tok[kBeamMax], s_dep[kBeamMax];
@@ -224,7 +263,12 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
       s_state[tid] = sh_biased ? ctx_in_range(cs[nd], sh_g.n_states) : 0;
       s_bonus[tid] = cb[nd];
     }
+    if constexpr (LM) {                           // the root is in the LM's start state, whichever LM that is
+      s_lst[tid] = fused ? (nd == 0 ? lm.start : lm_in_range(ls[nd], lm.n_states)) : 0;
+      s_lsum[tid] = lsm[nd];
+    }
   }
+  if constexpr (LM) __syncthreads();
   int t = 0;
   for (; t < nf; ++t) {
     const int n = sh_ncur;
@@ -235,6 +279,25 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
       if constexpr (CTX) {                        // the frame's symbols are classed once
         const int s = f_s[tid];
         f_cls[tid] = sh_biased && (unsigned)s < (unsigned)sh_g.V ? ctx_in_range(sh_g.cls[s], sh_g.A) : 0;
+      }
+    }
+    if constexpr (LM) {
+      if (fused && tid >= 64 && tid < 64 + n) {
+        const int h = tid - 64;
+        int st = s_lst[h], l = 0;
+        double w = 0.0;
+        for (; st != 0 && l < kLmLevels; ++l) {
+          int lo, hi;
+          lm_arcs(lm, st, &lo, &hi);
+          lv_lo[h * kLmLevels + l] = lo;
+          lv_hi[h * kLmLevels + l] = hi;
+          lv_w[h * kLmW + l] = w;
+          w += (double)lm.bo_weight[st];
+          const int nb = lm.bo_state[st];
+          st = nb >= 0 && nb < st ? nb : 0;
+        }
+        lv_n[h] = l;
+        lv_w[h * kLmW + l] = w;
       }
     }
     for (int i = tid; i < n * k; i += kBeamThreads) merged[i] = 0;
@@ -281,7 +344,11 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
       c_pnb[q] = pnb;
       c_first[q] = first;
       if (first != 0x7fffffff) {
-        if constexpr (CTX) c_score[q] = log_add2(pb, pnb) + s_bonus[q];     // a beam entry's node holds its bonus
+        if constexpr (LM) {                       // ... and its LM sum
+          double key = log_add2(pb, pnb) + s_bonus[q];
+          if (fused) key = key + (cx.alpha * s_lsum[q] + cx.beta * (double)s_dep[q]);
+          c_score[q] = key;
+        } else if constexpr (CTX) c_score[q] = log_add2(pb, pnb) + s_bonus[q];     // a beam entry's node holds its bonus
         else c_score[q] = log_add2(pb, pnb);
       }
     }
@@ -311,7 +378,31 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
       if constexpr (CTX) {
         double bonus = s_bonus[h];
         if (sh_biased) bonus += (double)sh_g.delta[s_state[h] * sh_g.A + f_cls[j]];
-        c_score[c] = log_add2(-INFINITY, pnb) + bonus;
+        if constexpr (LM) {
+          double key = log_add2(-INFINITY, pnb) + bonus;
+          if (fused) {                            // lm_step from the staged chain
+            const int nl = lv_n[h];
+            int nx = 0, a = -1, l = 0;
+            for (; l < nl; ++l) {
+              a = lm_find(lm, lv_lo[h * kLmLevels + l], lv_hi[h * kLmLevels + l], s);
+              if (a >= 0) break;
+            }
+            double lp;
+            if (a >= 0) {
+              nx = lm_in_range(lm.arc_next[a], lm.n_states);
+              lp = lv_w[h * kLmW + l] + (double)lm.arc_logp[a];
+            } else {
+              lp = lm_step_root(lm, lv_w[h * kLmW + nl], s, &nx);
+            }
+            const double lsum = s_lsum[h] + lp;
+            c_lst[i] = nx;
+            c_lsum[i] = lsum;
+            key = key + (cx.alpha * lsum + cx.beta * (double)(s_dep[h] + 1));
+          }
+          c_score[c] = key;
+        } else {
+          c_score[c] = log_add2(-INFINITY, pnb) + bonus;
+        }
       } else {
         c_score[c] = log_add2(-INFINITY, pnb);
       }
@@ -343,6 +434,8 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
       int node = -1, par = -1, tok = -1, dep = 0;
       int cst = 0, ch = 0, cj = 0;                // CTX: the survivor's state and bonus; its parent and rank if an extension
       double cbo = 0.0;
+      int lst = 0;                                // LM: the survivor's LM state and sum
+      double lsum = 0.0;
       unsigned long long key = 0;
       if (tid < n_next) {
         const int src = n_src[tid];
@@ -354,6 +447,10 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
           if constexpr (CTX) {
             cst = s_state[src];
             cbo = s_bonus[src];
+          }
+          if constexpr (LM) {
+            lst = s_lst[src];
+            lsum = s_lsum[src];
           }
         } else {
           const int h = (src - n) / k, j = (src - n) - h * k;
@@ -386,6 +483,15 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
               }
             }
           }
+          if constexpr (LM) {
+            if (node >= 0) {
+              lst = fused ? lm_in_range(ls[node], lm.n_states) : 0;
+              lsum = lsm[node];
+            } else if (fused) {
+              lst = c_lst[src - n];
+              lsum = c_lsum[src - n];
+            }
+          }
         }
       }
       const bool fresh = tid < n_next && node < 0;
@@ -401,6 +507,10 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
         if constexpr (CTX) {
           cs[node] = cst;
           cb[node] = cbo;
+        }
+        if constexpr (LM) {
+          ls[node] = lst;
+          lsm[node] = lsum;
         }
         int slot = hash_slot(key, L.hcap);
         for (int probe = 0; probe < L.hcap; ++probe) {
@@ -420,6 +530,10 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
           n_state[tid] = cst;
           n_bonus[tid] = cbo;
         }
+        if constexpr (LM) {
+          n_lst[tid] = lst;
+          n_lsum[tid] = lsum;
+        }
       }
       if (tid == 0) {
         sh_nnodes = base + (sh_status == 0 ? __popcll(m) : 0);
@@ -438,6 +552,10 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
       if constexpr (CTX) {
         s_state[tid] = n_state[tid];
         s_bonus[tid] = n_bonus[tid];
+      }
+      if constexpr (LM) {
+        s_lst[tid] = n_lst[tid];
+        s_lsum[tid] = n_lsum[tid];
       }
     }
     __syncthreads();
@@ -470,13 +588,26 @@ __global__ __launch_bounds__(256) void ctc_beam_ctx_reset_kernel(CtxLayout C, ch
 }
 
 // ctc_beam_nbest_kernel plus the bonus: hypothesis r's final = bonus - pot[state]; rows are written in the order of
-// (CTC score + final) desc, stable on the beam order; hyp_score stays the CTC score
+// (CTC score + final) desc, stable on the beam order; hyp_score stays the CTC score.
+// LM: a fused utterance's key is (CTC score + final) + (alpha (lm + fin[lm_state] use_eos) + beta depth), and hyp_lm gets
+// lm + fin[lm_state] use_eos (0 for an utterance that runs without the LM).
+struct LmNbest {
+  CtxLayout M;
+  const int32_t* lm;
+  long long lm_words;
+  const int32_t* lm_on;
+  double alpha, beta;
+  int use_eos;
+  float* hyp_lm;
+};
+struct NoLm {};
+template <bool LM, class Lm>
 __global__ __launch_bounds__(64) void ctc_beam_ctx_nbest_kernel(BeamLayout L, CtxLayout C, int beam, int max_frames,
                                                                 const char* state, const int32_t* __restrict__ image,
                                                                 long long words, const int32_t* __restrict__ graph_of,
                                                                 int32_t* __restrict__ hyp_tokens, int32_t* __restrict__ hyp_len,
                                                                 float* __restrict__ hyp_score, float* __restrict__ hyp_bonus,
-                                                                int32_t* __restrict__ n_hyps) {
+                                                                int32_t* __restrict__ n_hyps, Lm lx) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const BeamPtrs p = beam_ptrs(L, (char*)state, b);
   const char* c = state + C.base + (size_t)b * C.stride;
@@ -489,14 +620,25 @@ __global__ __launch_bounds__(64) void ctc_beam_ctx_nbest_kernel(BeamLayout L, Ct
   int32_t* toks = hyp_tokens + (size_t)b * beam * max_frames;
   CtxGraph g;
   const bool biased = ctx_graph_view(image, words, graph_of[b], &g);
-  double score = -INFINITY, fin = 0.0;
+  double score = -INFINITY, fin = 0.0, lmf = 0.0;
   int nd = 0;
+  LmView lm{};
+  bool fused = false;
+  if constexpr (LM) fused = lx.lm_on[b] != 0 && lm_view(lx.lm, lx.lm_words, &lm);
   if (lane < n) {
     nd = p.node[lane];
     score = log_add2(p.pb[lane], p.pnb[lane]);
     fin = cb[nd];
     if (biased) fin -= (double)g.pot[ctx_in_range(cs[nd], g.n_states)];
     key[lane] = score + fin;
+    if constexpr (LM) {
+      if (fused) {
+        const char* c2 = state + lx.M.base + (size_t)b * lx.M.stride;
+        const int st = nd == 0 ? lm.start : lm_in_range(((const int32_t*)c2)[nd], lm.n_states);
+        lmf = ((const double*)(c2 + lx.M.bonus))[nd] + (lx.use_eos ? (double)lm.fin[st] : 0.0);
+        key[lane] = key[lane] + (lx.alpha * lmf + lx.beta * (double)p.depth[nd]);
+      }
+    }
   }
   __syncthreads();
   if (lane < beam) {
@@ -514,6 +656,7 @@ __global__ __launch_bounds__(64) void ctc_beam_ctx_nbest_kernel(BeamLayout L, Ct
     hyp_len[(size_t)b * beam + r] = L_r;
     hyp_score[(size_t)b * beam + r] = (float)score;
     hyp_bonus[(size_t)b * beam + r] = (float)fin;
+    if constexpr (LM) lx.hyp_lm[(size_t)b * beam + r] = (float)lmf;
   }
   __syncthreads();
   for (int r = 0; r < beam; ++r)
@@ -732,9 +875,90 @@ int launch_ctc_beam_ctx_nbest(const m3_ctc_beam_desc* d, const void* state, size
   M3_REQUIRE(hyp_len && hyp_score && hyp_bonus && n_hyps && (hyp_tokens || d->max_frames == 0), "ctc_beam_ctx_nbest: null pointer");
   if (int rc = check_ctx_image("ctc_beam_ctx_nbest", image, image_bytes, graph_of)) return rc;
   const BeamLayout L = beam_layout(d->beam, d->max_frames);
-  hipLaunchKernelGGL(ctc_beam_ctx_nbest_kernel, dim3(d->B), dim3(64), 0, stream, L, ctx_layout(L, d->B), d->beam, d->max_frames,
-                     (const char*)state, (const int32_t*)image, (long long)(image_bytes / 4), graph_of, hyp_tokens, hyp_len,
-                     hyp_score, hyp_bonus, n_hyps);
+  hipLaunchKernelGGL((ctc_beam_ctx_nbest_kernel<false, NoLm>), dim3(d->B), dim3(64), 0, stream, L, ctx_layout(L, d->B), d->beam,
+                     d->max_frames, (const char*)state, (const int32_t*)image, (long long)(image_bytes / 4), graph_of, hyp_tokens,
+                     hyp_len, hyp_score, hyp_bonus, n_hyps, NoLm{});
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+size_t ctc_beam_lm_state_size(const m3_ctc_beam_desc* d) {
+  if (check_beam_desc(d)) return 0;
+  const CtxLayout M = lm_layout(beam_layout(d->beam, d->max_frames), d->B);
+  return M.base + (size_t)d->B * M.stride;
+}
+
+int launch_ctc_beam_lm_reset(const m3_ctc_beam_desc* d, void* state, size_t bytes, hipStream_t stream, const int32_t* slots,
+                             int n) {
+  if (int rc = check_beam_desc(d)) return rc;
+  const size_t need = ctc_beam_lm_state_size(d);
+  M3_REQUIRE(state != nullptr && bytes >= need, "ctc_beam_lm_reset: state %zu bytes < required %zu", bytes, need);
+  if (int rc = launch_ctc_beam_ctx_reset(d, state, bytes, stream, slots, n)) return rc;
+  if (d->B == 0 || (slots != nullptr && n == 0)) return 0;
+  const int cnt = slots ? n : d->B;              // the root's (LM state, LM sum): the context block's kernel on the LM blocks
+  hipLaunchKernelGGL(ctc_beam_ctx_reset_kernel, dim3((cnt + 255) / 256), dim3(256), 0, stream,
+                     lm_layout(beam_layout(d->beam, d->max_frames), d->B), (char*)state, slots, d->B, cnt);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+static int check_lm_image(const char* who, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha, double beta) {
+  M3_REQUIRE(lm_on != nullptr, "%s: null lm_on", who);
+  M3_REQUIRE(lm_image != nullptr || lm_bytes == 0, "%s: null LM image of %zu bytes", who, lm_bytes);
+  M3_REQUIRE(lm_bytes % 4 == 0 && lm_bytes <= kLmMaxBytes && (lm_image == nullptr || lm_bytes >= LM_HDR_WORDS * 4),
+             "%s: LM image of %zu bytes (a multiple of 4 in [%d, %zu])", who, lm_bytes, LM_HDR_WORDS * 4, kLmMaxBytes);
+  M3_REQUIRE(std::isfinite(alpha) && std::isfinite(beta), "%s: alpha or beta is not finite", who);
+  return 0;
+}
+
+int launch_ctc_beam_lm_advance(const m3_ctc_beam_desc* d, void* state, size_t bytes, const void* image, size_t image_bytes,
+                               const int32_t* graph_of, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha,
+                               double beta, const float* top_logp, const int32_t* top_idx, int T_chunk, const int32_t* n_frames,
+                               hipStream_t stream) {
+  if (int rc = check_beam_desc(d)) return rc;
+  const size_t need = ctc_beam_lm_state_size(d);
+  M3_REQUIRE(state != nullptr && bytes >= need, "ctc_beam_lm_advance: state %zu bytes < required %zu", bytes, need);
+  M3_REQUIRE(T_chunk >= 0, "ctc_beam_lm_advance: T_chunk = %d < 0", T_chunk);
+  if (d->B == 0 || T_chunk == 0) return 0;
+  M3_REQUIRE(top_logp && top_idx && n_frames, "ctc_beam_lm_advance: null pointer");
+  if (int rc = check_ctx_image("ctc_beam_lm_advance", image, image_bytes, graph_of)) return rc;
+  if (int rc = check_lm_image("ctc_beam_lm_advance", lm_image, lm_bytes, lm_on, alpha, beta)) return rc;
+  const BeamLayout L = beam_layout(d->beam, d->max_frames);
+  LmArgs cx;
+  cx.C = ctx_layout(L, d->B);
+  cx.image = (const int32_t*)image;
+  cx.words = (long long)(image_bytes / 4);
+  cx.graph_of = graph_of;
+  cx.M = lm_layout(L, d->B);
+  cx.lm = (const int32_t*)lm_image;
+  cx.lm_words = (long long)(lm_bytes / 4);
+  cx.lm_on = lm_on;
+  cx.alpha = alpha;
+  cx.beta = beta;
+  hipLaunchKernelGGL((ctc_beam_advance_kernel<true, LmArgs, true>), dim3(d->B), dim3(kBeamThreads), 0, stream, L, d->beam, d->k,
+                     d->blank, d->max_frames, (char*)state, top_logp, top_idx, T_chunk, n_frames, cx);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_ctc_beam_lm_nbest(const m3_ctc_beam_desc* d, const void* state, size_t bytes, const void* image, size_t image_bytes,
+                             const int32_t* graph_of, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha,
+                             double beta, int use_eos, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score, float* hyp_bonus,
+                             float* hyp_lm, int32_t* n_hyps, hipStream_t stream) {
+  if (int rc = check_beam_desc(d)) return rc;
+  const size_t need = ctc_beam_lm_state_size(d);
+  M3_REQUIRE(state != nullptr && bytes >= need, "ctc_beam_lm_nbest: state %zu bytes < required %zu", bytes, need);
+  if (d->B == 0) return 0;
+  M3_REQUIRE(hyp_len && hyp_score && hyp_bonus && hyp_lm && n_hyps && (hyp_tokens || d->max_frames == 0),
+             "ctc_beam_lm_nbest: null pointer");
+  if (int rc = check_ctx_image("ctc_beam_lm_nbest", image, image_bytes, graph_of)) return rc;
+  if (int rc = check_lm_image("ctc_beam_lm_nbest", lm_image, lm_bytes, lm_on, alpha, beta)) return rc;
+  const BeamLayout L = beam_layout(d->beam, d->max_frames);
+  const LmNbest lx{lm_layout(L, d->B), (const int32_t*)lm_image, (long long)(lm_bytes / 4), lm_on, alpha, beta, use_eos ? 1 : 0,
+                   hyp_lm};
+  hipLaunchKernelGGL((ctc_beam_ctx_nbest_kernel<true, LmNbest>), dim3(d->B), dim3(64), 0, stream, L, ctx_layout(L, d->B), d->beam,
+                     d->max_frames, (const char*)state, (const int32_t*)image, (long long)(image_bytes / 4), graph_of, hyp_tokens,
+                     hyp_len, hyp_score, hyp_bonus, n_hyps, lx);
   M3_LAUNCH_CHECK();
   return 0;
 }

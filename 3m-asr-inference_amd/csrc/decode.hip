@@ -284,44 +284,115 @@ int ctc_context_validate(const void* image, size_t bytes, int V) {
   return 0;
 }
 
-// ctc_prefix_beam_search_host with the biased ranking: every prefix carries (state, bonus) of its walk through graph
-// `graph` of the image, the second prune ranks by log_add2(pb, pnb) + bonus, the hypotheses come out ordered by
-// log_add2(pb, pnb) + final (final = bonus - pot[state]), stable on the beam order.  image == null or graph == -1: state 0
-// and bonus 0.0 throughout, and x + 0.0 == x: the unbiased routine's result.
-int ctc_prefix_beam_search_ctx_host(const float* top_logp, const int32_t* top_idx, int T, int k, int beam, int blank,
-                                    const void* image, size_t image_bytes, int graph, int32_t* hyp_tokens, int32_t* hyp_len,
-                                    float* hyp_score, float* hyp_bonus, int32_t* hyp_state, int32_t* n_hyps) {
-  M3_REQUIRE(T >= 0 && k > 0 && beam > 0, "ctc_prefix_beam_search_ctx: bad sizes T=%d k=%d beam=%d", T, k, beam);
-  M3_REQUIRE(top_logp && top_idx && hyp_tokens && hyp_len && hyp_score && hyp_bonus && hyp_state && n_hyps,
-             "ctc_prefix_beam_search_ctx: null pointer");
+// ---------------------------------------------------------------- n-gram LM shallow fusion, host side
+// Structure of an LM image (kernels.h): the header and limits, every table inside the image, and every table entry that the
+// searches use as an index or add to a score.  Limits: order <= 8, n_states <= 2^26, image <= 1 GiB.
+int ctc_lm_validate(const void* image, size_t bytes, int V) {
+  M3_REQUIRE(image != nullptr, "ctc_lm_validate: null image");
+  M3_REQUIRE(V >= 1, "ctc_lm_validate: V = %d < 1", V);
+  M3_REQUIRE(bytes % 4 == 0 && bytes >= LM_HDR_WORDS * 4 && bytes <= kLmMaxBytes,
+             "ctc_lm_validate: image of %zu bytes (a multiple of 4 in [%d, %zu])", bytes, LM_HDR_WORDS * 4, kLmMaxBytes);
+  const int32_t* w = (const int32_t*)image;
+  const long long words = (long long)(bytes / 4);
+  M3_REQUIRE(w[LM_MAGIC] == kLmMagic, "ctc_lm_validate: not an LM image");
+  M3_REQUIRE(w[LM_VERSION] == kLmVersion, "ctc_lm_validate: image version %d, this library reads version %d", w[LM_VERSION],
+             kLmVersion);
+  M3_REQUIRE(w[LM_V] == V, "ctc_lm_validate: image built for V = %d, asked for V = %d", w[LM_V], V);
+  M3_REQUIRE(w[LM_WORDS] == words, "ctc_lm_validate: image says %d words, has %lld", w[LM_WORDS], words);
+  LmView m;
+  M3_REQUIRE(lm_view(w, words, &m),
+             "ctc_lm_validate: order outside [1, %d], n_states outside [1, %d], n_arcs < 0, start outside [0, n_states) or a "
+             "table outside the image", kLmMaxOrder, kLmMaxStates);
+  M3_REQUIRE(std::isfinite(m.unk_logp), "ctc_lm_validate: unk_logp is not finite");
+  for (int v = 0; v < V; ++v) {
+    M3_REQUIRE(std::isfinite(m.uni_logp[v]), "ctc_lm_validate: uni_logp[%d] is not finite", v);
+    M3_REQUIRE(m.uni_next[v] >= 0 && m.uni_next[v] < m.n_states, "ctc_lm_validate: uni_next[%d] = %d outside [0, %d)", v,
+               m.uni_next[v], m.n_states);
+  }
+  M3_REQUIRE(m.arc_begin[0] == 0 && m.arc_begin[1] == 0, "ctc_lm_validate: arc_begin[0..1] = %d, %d (state 0 has no sparse arcs)",
+             m.arc_begin[0], m.arc_begin[1]);
+  M3_REQUIRE(m.arc_begin[m.n_states] == m.n_arcs, "ctc_lm_validate: arc_begin[n_states] = %d, n_arcs = %d", m.arc_begin[m.n_states],
+             m.n_arcs);
+  std::vector<unsigned char> depth((size_t)m.n_states, 0);     // levels of the back-off chain above state 0
+  for (int s = 0; s < m.n_states; ++s) {
+    const int lo = m.arc_begin[s], hi = m.arc_begin[s + 1];
+    M3_REQUIRE(lo >= 0 && lo <= hi && hi <= m.n_arcs, "ctc_lm_validate: arc_begin[%d..] = %d, %d is not monotone in [0, %d]", s, lo,
+               hi, m.n_arcs);
+    for (int i = lo; i < hi; ++i) {
+      M3_REQUIRE(m.arc_tok[i] >= 0 && m.arc_tok[i] < V, "ctc_lm_validate: arc_tok[%d] = %d outside [0, %d)", i, m.arc_tok[i], V);
+      M3_REQUIRE(i == lo || m.arc_tok[i - 1] < m.arc_tok[i], "ctc_lm_validate: arc_tok[%d] = %d is not above arc_tok[%d] = %d (state %d)",
+                 i, m.arc_tok[i], i - 1, m.arc_tok[i - 1], s);
+      M3_REQUIRE(m.arc_next[i] >= 0 && m.arc_next[i] < m.n_states, "ctc_lm_validate: arc_next[%d] = %d outside [0, %d)", i,
+                 m.arc_next[i], m.n_states);
+      M3_REQUIRE(std::isfinite(m.arc_logp[i]), "ctc_lm_validate: arc_logp[%d] is not finite", i);
+    }
+    M3_REQUIRE(s == 0 ? m.bo_state[0] == 0 : (m.bo_state[s] >= 0 && m.bo_state[s] < s),
+               "ctc_lm_validate: bo_state[%d] = %d (0 for state 0, else in [0, %d))", s, m.bo_state[s], s);
+    if (s > 0) {
+      depth[s] = (unsigned char)(depth[m.bo_state[s]] + 1);
+      M3_REQUIRE(depth[s] < m.order, "ctc_lm_validate: back-off chain of state %d has %d levels, order %d", s, (int)depth[s],
+                 m.order);
+    }
+    M3_REQUIRE(std::isfinite(m.bo_weight[s]), "ctc_lm_validate: bo_weight[%d] is not finite", s);
+    M3_REQUIRE(std::isfinite(m.fin[s]), "ctc_lm_validate: final[%d] is not finite", s);
+  }
+  return 0;
+}
+
+// ctc_prefix_beam_search_host with the fused ranking.  Every prefix carries (state, bonus) of its walk through graph `graph`
+// of the context image and (lm_state, lm) of its walk through the LM (lm = the left-to-right double sum of lm_step from the
+// LM's start state).  The second prune ranks by (log_add2(pb, pnb) + bonus) + (alpha lm + beta |prefix|); the hypotheses come
+// out ordered by (log_add2(pb, pnb) + final) + (alpha (lm + fin[lm_state] use_eos) + beta |prefix|), stable on the beam
+// order (final = bonus - pot[state]).  Without a graph: state 0 and bonus 0.0 throughout, and x + 0.0 == x.  Without an LM
+// the second bracket is not added at all: the biased routine's result, and without either the unbiased routine's.
+int ctc_prefix_beam_search_lm_host(const float* top_logp, const int32_t* top_idx, int T, int k, int beam, int blank,
+                                   const void* image, size_t image_bytes, int graph, const void* lm_image, size_t lm_bytes,
+                                   double alpha, double beta, int use_eos, int32_t* hyp_tokens, int32_t* hyp_len,
+                                   float* hyp_score, float* hyp_bonus, int32_t* hyp_state, float* hyp_lm, int32_t* n_hyps) {
+  const char* who = lm_image ? "ctc_prefix_beam_search_lm" : "ctc_prefix_beam_search_ctx";
+  M3_REQUIRE(T >= 0 && k > 0 && beam > 0, "%s: bad sizes T=%d k=%d beam=%d", who, T, k, beam);
+  M3_REQUIRE(top_logp && top_idx && hyp_tokens && hyp_len && hyp_score && hyp_bonus && hyp_state && n_hyps, "%s: null pointer", who);
   CtxGraph g{};
   const bool biased = image != nullptr && graph != -1;
   if (biased) {
-    M3_REQUIRE(image_bytes >= CTX_HDR_WORDS * 4, "ctc_prefix_beam_search_ctx: image of %zu bytes", image_bytes);
+    M3_REQUIRE(image_bytes >= CTX_HDR_WORDS * 4, "%s: image of %zu bytes", who, image_bytes);
     if (int rc = ctc_context_validate(image, image_bytes, ((const int32_t*)image)[CTX_V])) return rc;
-    M3_REQUIRE(ctx_graph_view((const int32_t*)image, (long long)(image_bytes / 4), graph, &g),
-               "ctc_prefix_beam_search_ctx: graph %d is not in the image", graph);
+    M3_REQUIRE(ctx_graph_view((const int32_t*)image, (long long)(image_bytes / 4), graph, &g), "%s: graph %d is not in the image",
+               who, graph);
+  }
+  LmView lm{};
+  const bool fused = lm_image != nullptr;
+  if (fused) {
+    M3_REQUIRE(hyp_lm != nullptr, "%s: null hyp_lm", who);
+    M3_REQUIRE(std::isfinite(alpha) && std::isfinite(beta), "%s: alpha or beta is not finite", who);
+    M3_REQUIRE(lm_bytes >= LM_HDR_WORDS * 4, "%s: LM image of %zu bytes", who, lm_bytes);
+    if (int rc = ctc_lm_validate(lm_image, lm_bytes, ((const int32_t*)lm_image)[LM_V])) return rc;
+    lm_view((const int32_t*)lm_image, (long long)(lm_bytes / 4), &lm);
   }
   struct CHyp {
     std::vector<int32_t> prefix;
     double pb, pnb;
     int state;
     double bonus;
+    int lm_state;
+    double lm;
   };
   std::vector<CHyp> cur(1);
   cur[0].pb = 0.0;
   cur[0].pnb = NEG_INF;
   cur[0].state = 0;
   cur[0].bonus = 0.0;
+  cur[0].lm_state = fused ? lm.start : 0;
+  cur[0].lm = 0.0;
   std::vector<CHyp> next;
   std::map<std::vector<int32_t>, int> where;
   std::vector<int> order;
   std::vector<double> key;
-  auto slot = [&](const std::vector<int32_t>& p, int state, double bonus) -> CHyp& {
+  auto slot = [&](const std::vector<int32_t>& p, int state, double bonus, int lm_state, double lm_sum) -> CHyp& {
     auto it = where.find(p);
     if (it == where.end()) {
       it = where.emplace(p, (int)next.size()).first;
-      next.push_back(CHyp{p, NEG_INF, NEG_INF, state, bonus});
+      next.push_back(CHyp{p, NEG_INF, NEG_INF, state, bonus, lm_state, lm_sum});
     }
     return next[it->second];
   };
@@ -334,32 +405,33 @@ int ctc_prefix_beam_search_ctx_host(const float* top_logp, const int32_t* top_id
       const double ps = (double)top_logp[(size_t)t * k + j];
       const int col = biased && s >= 0 && s < g.V ? g.cls[s] : 0;
       for (size_t h = 0; h < cur.size(); ++h) {
-        const double pb = cur[h].pb, pnb = cur[h].pnb, bonus = cur[h].bonus;
-        const int state = cur[h].state;
+        const double pb = cur[h].pb, pnb = cur[h].pnb, bonus = cur[h].bonus, lm_sum = cur[h].lm;
+        const int state = cur[h].state, lm_state = cur[h].lm_state;
         const std::vector<int32_t>& prefix = cur[h].prefix;
         const bool has_last = !prefix.empty();
-        int e_state = 0;
-        double e_bonus = bonus;
+        int e_state = 0, e_lm_state = 0;
+        double e_bonus = bonus, e_lm = 0.0;
         if (biased) {
           e_state = g.next[(size_t)state * g.A + col];
           e_bonus = bonus + (double)g.delta[(size_t)state * g.A + col];
         }
+        if (fused && s != blank) e_lm = lm_sum + lm_step(lm, lm_state, s, &e_lm_state);
         if (s == blank) {
-          CHyp& n = slot(prefix, state, bonus);
+          CHyp& n = slot(prefix, state, bonus, lm_state, lm_sum);
           n.pb = log_add3(n.pb, pb + ps, pnb + ps);
         } else if (has_last && s == prefix.back()) {
           {
-            CHyp& n = slot(prefix, state, bonus);
+            CHyp& n = slot(prefix, state, bonus, lm_state, lm_sum);
             n.pnb = log_add2(n.pnb, pnb + ps);
           }
           ext = prefix;
           ext.push_back(s);
-          CHyp& n = slot(ext, e_state, e_bonus);
+          CHyp& n = slot(ext, e_state, e_bonus, e_lm_state, e_lm);
           n.pnb = log_add2(n.pnb, pb + ps);
         } else {
           ext = prefix;
           ext.push_back(s);
-          CHyp& n = slot(ext, e_state, e_bonus);
+          CHyp& n = slot(ext, e_state, e_bonus, e_lm_state, e_lm);
           n.pnb = log_add3(n.pnb, pb + ps, pnb + ps);
         }
       }
@@ -369,6 +441,7 @@ int ctc_prefix_beam_search_ctx_host(const float* top_logp, const int32_t* top_id
     for (size_t i = 0; i < next.size(); ++i) {
       order[i] = (int)i;
       key[i] = log_add2(next[i].pb, next[i].pnb) + next[i].bonus;
+      if (fused) key[i] = key[i] + (alpha * next[i].lm + beta * (double)next[i].prefix.size());
     }
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key[a] > key[b]; });
     const size_t keep = std::min(order.size(), (size_t)beam);
@@ -380,11 +453,15 @@ int ctc_prefix_beam_search_ctx_host(const float* top_logp, const int32_t* top_id
   const int n = (int)std::min(cur.size(), (size_t)beam);
   order.resize(n);
   key.resize(n);
-  std::vector<double> fin(n);
+  std::vector<double> fin(n), lmf(n, 0.0);
   for (int i = 0; i < n; ++i) {
     order[i] = i;
     fin[i] = cur[i].bonus - (biased ? (double)g.pot[cur[i].state] : 0.0);
     key[i] = log_add2(cur[i].pb, cur[i].pnb) + fin[i];
+    if (fused) {
+      lmf[i] = cur[i].lm + (use_eos ? (double)lm.fin[cur[i].lm_state] : 0.0);
+      key[i] = key[i] + (alpha * lmf[i] + beta * (double)cur[i].prefix.size());
+    }
   }
   std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key[a] > key[b]; });
   for (int r = 0; r < n; ++r) {
@@ -396,9 +473,18 @@ int ctc_prefix_beam_search_ctx_host(const float* top_logp, const int32_t* top_id
     hyp_score[r] = (float)log_add2(hyp.pb, hyp.pnb);
     hyp_bonus[r] = (float)fin[order[r]];
     hyp_state[r] = hyp.state;
+    if (hyp_lm) hyp_lm[r] = (float)lmf[order[r]];
   }
   *n_hyps = n;
   return 0;
+}
+
+// the biased routine: the fused one without an LM
+int ctc_prefix_beam_search_ctx_host(const float* top_logp, const int32_t* top_idx, int T, int k, int beam, int blank,
+                                    const void* image, size_t image_bytes, int graph, int32_t* hyp_tokens, int32_t* hyp_len,
+                                    float* hyp_score, float* hyp_bonus, int32_t* hyp_state, int32_t* n_hyps) {
+  return ctc_prefix_beam_search_lm_host(top_logp, top_idx, T, k, beam, blank, image, image_bytes, graph, nullptr, 0, 0.0, 0.0, 0,
+                                        hyp_tokens, hyp_len, hyp_score, hyp_bonus, hyp_state, nullptr, n_hyps);
 }
 
 // ---------------------------------------------------------------- CatSplitCache

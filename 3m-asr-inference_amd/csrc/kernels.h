@@ -405,6 +405,123 @@ int launch_ctc_beam_ctx_advance(const m3_ctc_beam_desc* d, void* state, size_t b
 int launch_ctc_beam_ctx_nbest(const m3_ctc_beam_desc* d, const void* state, size_t bytes, const void* image, size_t image_bytes,
                               const int32_t* graph_of, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score,
                               float* hyp_bonus, int32_t* n_hyps, hipStream_t stream);
+// n-gram LM shallow fusion of the prefix beam search (include/m3asr.h, "LM image"): one image of 4-byte words,
+//   [magic, version, V, order, n_states, n_arcs, start, unk_logp bits, the tables' word offsets (LMT_* order), words, 0, 0]
+// then the tables of a deterministic back-off automaton over context states (m3asr/lm.py compiles ARPA files into it).
+constexpr int32_t kLmMagic = 0x4d4c334d;   // "M3LM"
+constexpr int32_t kLmVersion = 1;
+constexpr int kLmMaxOrder = 8, kLmMaxStates = 1 << 26;
+constexpr size_t kLmMaxBytes = (size_t)1 << 30;
+enum { LM_MAGIC = 0, LM_VERSION = 1, LM_V = 2, LM_ORDER = 3, LM_STATES = 4, LM_ARCS = 5, LM_START = 6, LM_UNK = 7, LM_TABLES = 8,
+       LM_WORDS = 17, LM_HDR_WORDS = 20 };
+enum { LMT_UNI_LOGP = 0, LMT_UNI_NEXT, LMT_ARC_BEGIN, LMT_ARC_TOK, LMT_ARC_NEXT, LMT_ARC_LOGP, LMT_BO_STATE, LMT_BO_WEIGHT,
+       LMT_FINAL, LMT_COUNT };
+struct LmView {
+  const float* uni_logp;      // [V]             state 0's arcs are dense
+  const int32_t* uni_next;    // [V]
+  const int32_t* arc_begin;   // [n_states + 1]  arcs of state s: [arc_begin[s], arc_begin[s + 1])
+  const int32_t* arc_tok;     // [n_arcs]        strictly ascending inside a state
+  const int32_t* arc_next;    // [n_arcs]
+  const float* arc_logp;      // [n_arcs]
+  const int32_t* bo_state;    // [n_states]      bo_state[s] < s for s >= 1
+  const float* bo_weight;     // [n_states]
+  const float* fin;           // [n_states]      log P(</s> | state), back-off resolved
+  int V, order, n_states, n_arcs, start;
+  float unk_logp;
+};
+// The tables of an image of `words` words, for the host and the device alike.  False unless the header and all nine tables
+// lie inside the image and the limits hold: no address is formed from a value that failed its check.  (Table ENTRIES are
+// checked by ctc_lm_validate on the host, and once more where a search uses one as an index.)
+__host__ __device__ inline bool lm_view(const int32_t* image, long long words, LmView* out) {
+  if (image == nullptr || words < LM_HDR_WORDS || image[LM_MAGIC] != kLmMagic || image[LM_VERSION] != kLmVersion) return false;
+  const long long V = image[LM_V], order = image[LM_ORDER], ns = image[LM_STATES], na = image[LM_ARCS], start = image[LM_START];
+  if (V < 1 || order < 1 || order > kLmMaxOrder || ns < 1 || ns > kLmMaxStates || na < 0 || start < 0 || start >= ns) return false;
+  const long long len[LMT_COUNT] = {V, V, ns + 1, na, na, na, ns, ns, ns};
+  for (int i = 0; i < LMT_COUNT; ++i) {
+    const long long off = image[LM_TABLES + i];
+    if (off < LM_HDR_WORDS || off > words || len[i] > words - off) return false;
+  }
+  out->uni_logp = (const float*)(image + image[LM_TABLES + LMT_UNI_LOGP]);
+  out->uni_next = image + image[LM_TABLES + LMT_UNI_NEXT];
+  out->arc_begin = image + image[LM_TABLES + LMT_ARC_BEGIN];
+  out->arc_tok = image + image[LM_TABLES + LMT_ARC_TOK];
+  out->arc_next = image + image[LM_TABLES + LMT_ARC_NEXT];
+  out->arc_logp = (const float*)(image + image[LM_TABLES + LMT_ARC_LOGP]);
+  out->bo_state = image + image[LM_TABLES + LMT_BO_STATE];
+  out->bo_weight = (const float*)(image + image[LM_TABLES + LMT_BO_WEIGHT]);
+  out->fin = (const float*)(image + image[LM_TABLES + LMT_FINAL]);
+  out->V = (int)V;
+  out->order = (int)order;
+  out->n_states = (int)ns;
+  out->n_arcs = (int)na;
+  out->start = (int)start;
+  out->unk_logp = ((const float*)image)[LM_UNK];
+  return true;
+}
+__host__ __device__ inline int lm_in_range(int v, int n) { return (unsigned)v < (unsigned)n ? v : 0; }
+// position of tok among the arcs [lo, hi) (0 <= lo <= hi <= n_arcs, checked by the caller), or -1
+__host__ __device__ inline int lm_find(const LmView& m, int lo, int hi, int tok) {
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1, t = m.arc_tok[mid];
+    if (t == tok) return mid;
+    if (t < tok) lo = mid + 1;
+    else hi = mid;
+  }
+  return -1;
+}
+// The arcs of state st as a checked range: an arc_begin pair that is not 0 <= lo <= hi <= n_arcs means "no arcs".
+__host__ __device__ inline void lm_arcs(const LmView& m, int st, int* lo, int* hi) {
+  *lo = m.arc_begin[st];
+  *hi = m.arc_begin[st + 1];
+  if (*lo < 0 || *hi > m.n_arcs || *lo > *hi) *lo = *hi = 0;
+}
+// The last level of every walk: state 0, whose arcs are dense.  A token outside [0, V) is one the LM does not know.
+__host__ __device__ inline double lm_step_root(const LmView& m, double w, int tok, int* next) {
+  if ((unsigned)tok < (unsigned)m.V) {
+    *next = lm_in_range(m.uni_next[tok], m.n_states);
+    return w + (double)m.uni_logp[tok];
+  }
+  *next = 0;
+  return w + (double)m.unk_logp;
+}
+// THE SCORE CONTRACT: log P(tok | state) and the state reached.  From `state` down its back-off chain (bo_state[s] < s, so
+// the walk ends; a validated image has at most order - 1 levels above state 0), the back-off weights summed in double in
+// walk order, then the arc's value added.  *backoffs (optional): levels left without a match.
+__host__ __device__ inline double lm_step(const LmView& m, int state, int tok, int* next, int* backoffs = nullptr) {
+  double w = 0.0;
+  int st = state, lvl = 0;
+  for (; st != 0 && lvl < kLmMaxOrder; ++lvl) {
+    int lo, hi;
+    lm_arcs(m, st, &lo, &hi);
+    const int i = lm_find(m, lo, hi, tok);
+    if (i >= 0) {
+      if (backoffs) *backoffs = lvl;
+      *next = lm_in_range(m.arc_next[i], m.n_states);
+      return w + (double)m.arc_logp[i];
+    }
+    w += (double)m.bo_weight[st];
+    const int nb = m.bo_state[st];
+    st = nb >= 0 && nb < st ? nb : 0;
+  }
+  if (backoffs) *backoffs = lvl;
+  return lm_step_root(m, w, tok, next);
+}
+int ctc_lm_validate(const void* image, size_t bytes, int V);   // decode.hip, host only
+int ctc_prefix_beam_search_lm_host(const float* top_logp, const int32_t* top_idx, int T, int k, int beam, int blank,
+                                   const void* image, size_t image_bytes, int graph, const void* lm_image, size_t lm_bytes,
+                                   double alpha, double beta, int use_eos, int32_t* hyp_tokens, int32_t* hyp_len,
+                                   float* hyp_score, float* hyp_bonus, int32_t* hyp_state, float* hyp_lm, int32_t* n_hyps);
+size_t ctc_beam_lm_state_size(const m3_ctc_beam_desc* d);
+int launch_ctc_beam_lm_reset(const m3_ctc_beam_desc* d, void* state, size_t bytes, hipStream_t stream,
+                             const int32_t* slots = nullptr, int n = 0);
+int launch_ctc_beam_lm_advance(const m3_ctc_beam_desc* d, void* state, size_t bytes, const void* image, size_t image_bytes,
+                               const int32_t* graph_of, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha,
+                               double beta, const float* top_logp, const int32_t* top_idx, int T_chunk, const int32_t* n_frames,
+                               hipStream_t stream);
+int launch_ctc_beam_lm_nbest(const m3_ctc_beam_desc* d, const void* state, size_t bytes, const void* image, size_t image_bytes,
+                             const int32_t* graph_of, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha,
+                             double beta, int use_eos, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score, float* hyp_bonus,
+                             float* hyp_lm, int32_t* n_hyps, hipStream_t stream);
 size_t ctc_greedy_stream_state_size(const m3_ctc_greedy_desc* d);
 int launch_ctc_greedy_stream_reset(const m3_ctc_greedy_desc* d, void* state, size_t bytes, hipStream_t stream,
                                    const int32_t* slots = nullptr, int n = 0);

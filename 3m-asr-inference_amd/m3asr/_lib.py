@@ -70,7 +70,7 @@ F32, F16, I8, I32, BF16, FP8 = 0, 1, 2, 3, 4, 5
 ACT_NONE, ACT_RELU, ACT_SILU, ACT_GLU, ACT_SIGMOID, ACT_LOG = 0, 1, 2, 3, 4, 5
 OP_SUM, OP_PROD = 0, 1
 
-_vp, _i, _f, _sz, _i64, _cp = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64, C.c_char_p
+_vp, _i, _f, _sz, _i64, _cp, _d = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64, C.c_char_p, C.c_double
 _P = C.POINTER
 
 # name -> (restype, argtypes).  Must list every symbol include/m3asr.h declares
@@ -155,6 +155,15 @@ SIGNATURES = {
     "m3_ctc_beam_ctx_reset_slots": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp, _i, _vp]),
     "m3_ctc_beam_ctx_advance": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp]),
     "m3_ctc_beam_ctx_nbest": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "m3_ctc_lm_validate": (_i, [_vp, _sz, _i]),
+    "m3_ctc_prefix_beam_search_lm": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _i, _vp, _sz, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp]),
+    "m3_ctc_beam_lm_state_size": (_sz, [_P(CtcBeamDesc)]),
+    "m3_ctc_beam_lm_reset": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp]),
+    "m3_ctc_beam_lm_reset_slots": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp, _i, _vp]),
+    "m3_ctc_beam_lm_advance": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _d, _d, _vp, _vp, _i, _vp, _vp]),
+    "m3_ctc_beam_lm_nbest": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _vp]),
     "m3_ctc_greedy_stream_state_size": (_sz, [_P(CtcGreedyDesc)]),
     "m3_ctc_greedy_stream_reset": (_i, [_P(CtcGreedyDesc), _vp, _sz, _vp]),
     "m3_ctc_greedy_stream_reset_slots": (_i, [_P(CtcGreedyDesc), _vp, _sz, _vp, _i, _vp]),

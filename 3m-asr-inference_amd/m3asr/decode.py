@@ -42,25 +42,36 @@ class CtcBeamSearch:
         ...
         search.nbest()                              # [[(prefix tuple, score)], ...] per utterance, best first
 
-    With context=ContextSet(...) the search is biased towards the set's phrase lists (m3asr.context): see __init__.
+    With context=ContextSet(...) the search is biased towards the set's phrase lists (m3asr.context), with lm=NgramLm(...)
+    an n-gram LM is fused into the ranking (m3asr.lm): see __init__.
 
     The result equals the host routine (ops.ctc_prefix_beam_search_host) on each utterance's frames, however the frames are
     cut into chunks.  max_frames bounds the frames one utterance may consume between resets; past it nbest() raises."""
 
-    def __init__(self, B, beam, max_frames, blank=0, device="cuda", k=None, context=None):
+    def __init__(self, B, beam, max_frames, blank=0, device="cuda", k=None, context=None, lm=None, lm_weight=0.5,
+                 length_bonus=0.0, lm_eos=True):
         """k: candidate symbols per frame (default beam, as the reference's logp.topk(beam_size)); needs k <= V.
         context: a m3asr.context.ContextSet uploaded to `device` -- the search then ranks by CTC score + bonus (hotword
-        biasing, m3_ctc_beam_ctx_*).  Every utterance starts unbiased (graph -1); reset(graph_ids=) / set_context choose."""
+        biasing, m3_ctc_beam_ctx_*).  Every utterance starts unbiased (graph -1); reset(graph_ids=) / set_context choose.
+        lm: a m3asr.lm.NgramLm uploaded to `device` (lm.to(device)) -- the search then ranks a prefix y by
+        (CTC score + bonus) + (lm_weight log P_LM(y) + length_bonus |y|) (shallow fusion, m3_ctc_beam_lm_*); lm_eos: the
+        n-best is ordered with log P(</s> | y) added to the LM score.  Every utterance starts with the LM on; reset(lm_on=)
+        switches it per utterance."""
         self.desc = ops.ctc_beam_desc(B, beam, max_frames, blank, k)
         self.device = torch.device(device)
         self.context = context
-        if context is not None:
-            if context.dev is None or not _same_device(context.dev.device, self.device):
-                raise _lib.M3Error("CtcBeamSearch: the ContextSet is not on %s" % self.device)
-            n = ops.ctc_beam_ctx_state_size(self.desc)
+        self.lm, self.lm_weight, self.length_bonus, self.lm_eos = lm, float(lm_weight), float(length_bonus), bool(lm_eos)
+        if context is not None and (context.dev is None or not _same_device(context.dev.device, self.device)):
+            raise _lib.M3Error("CtcBeamSearch: the ContextSet is not on %s" % self.device)
+        if lm is not None and (lm.dev is None or not _same_device(lm.dev.device, self.device)):
+            raise _lib.M3Error("CtcBeamSearch: the NgramLm is not on %s (lm.to(device))" % self.device)
+        if context is not None or lm is not None:
+            n = ops.ctc_beam_ctx_state_size(self.desc) if lm is None else ops.ctc_beam_lm_state_size(self.desc)
             self.graph_ids = [-1] * self.desc.B               # what each utterance's next reset installs
             self.graph_of = torch.full((max(self.desc.B, 1),), -1, dtype=torch.int32, device=self.device)[:self.desc.B]
             self.used = [False] * self.desc.B                 # advanced since its last reset
+            self.lm_flags = [1] * self.desc.B
+            self.lm_on = torch.ones(max(self.desc.B, 1), dtype=torch.int32, device=self.device)[:self.desc.B]
         else:
             n = ops.ctc_beam_state_size(self.desc)
         self.state = torch.empty(max(n, 1), dtype=torch.uint8, device=self.device)
@@ -94,29 +105,43 @@ class CtcBeamSearch:
         for b, g in zip(slots, graph_ids):
             self.graph_ids[b] = g
 
-    def reset(self, stream=None, slots=None, graph_ids=None):
+    def reset(self, stream=None, slots=None, graph_ids=None, lm_on=None):
         """slots: None = all B searches; else the utterances to restart (a list, or an int32 device tensor).
-        graph_ids (biased search): the graphs the restarted utterances take, one per slot (all B when slots is None)."""
+        graph_ids (biased search): the graphs the restarted utterances take, one per slot (all B when slots is None).
+        lm_on (fused search): whether each restarted utterance runs with the LM, one flag per slot; an utterance keeps its
+        setting from a reset to the next, because its nodes hold the LM state and sum of their prefixes."""
         which = None
-        if self.context is not None:
+        if graph_ids is not None and self.context is None:
+            raise _lib.M3Error("CtcBeamSearch.reset: graph_ids without a context")
+        if lm_on is not None and self.lm is None:
+            raise _lib.M3Error("CtcBeamSearch.reset: lm_on without an LM")
+        if self.context is not None or self.lm is not None:
             which = list(range(self.B)) if slots is None else [int(b) for b in (slots.tolist() if torch.is_tensor(slots) else slots)]
             which = [b for b in which if 0 <= b < self.B]
             for b in which:
                 self.used[b] = False
             if graph_ids is not None:
                 self.set_context(which, graph_ids)
-        elif graph_ids is not None:
-            raise _lib.M3Error("CtcBeamSearch.reset: graph_ids without a context")
+            if lm_on is not None:
+                if len(lm_on) != len(which):
+                    raise ValueError("reset: %d slots, %d lm_on flags" % (len(which), len(lm_on)))
+                for b, f in zip(which, lm_on):
+                    self.lm_flags[b] = 1 if f else 0
         with torch.cuda.stream(stream or torch.cuda.current_stream(self.device)):
             if slots is not None and not torch.is_tensor(slots):
                 slots = torch.tensor([int(b) for b in slots], dtype=torch.int32).to(self.device)
             if slots is None or slots.numel() > 0:
-                if self.context is None:
+                if self.context is None and self.lm is None:
                     ops.ctc_beam_reset(self.desc, self.state, slots)
-                else:
+                    return
+                if self.lm is None:
                     ops.ctc_beam_ctx_reset(self.desc, self.state, slots)
+                else:
+                    ops.ctc_beam_lm_reset(self.desc, self.state, slots)
                     if self.B > 0:
-                        self.graph_of.copy_(torch.tensor(self.graph_ids, dtype=torch.int32))
+                        self.lm_on.copy_(torch.tensor(self.lm_flags, dtype=torch.int32))
+                if self.B > 0:
+                    self.graph_of.copy_(torch.tensor(self.graph_ids, dtype=torch.int32))
 
     def advance(self, logits, n_frames, stream=None):
         """logits (B, Tc, V) on the device; n_frames (B,) how many of each row's Tc frames are real.  Enqueues m3_ctc_topk and
@@ -129,34 +154,49 @@ class CtcBeamSearch:
                 return
             nf = n_frames.reshape(-1).to(self.device, torch.int32, non_blocking=True)
             top_logp, top_idx = ops.ctc_topk(logits.contiguous(), self.desc.k)
-            if self.context is None:
+            if self.context is None and self.lm is None:
                 ops.ctc_beam_advance(self.desc, self.state, top_logp, top_idx, nf)
+                return
+            assert self.context is None or V == self.context.vocab_size, "the ContextSet was built for another vocabulary size"
+            assert self.lm is None or V == self.lm.vocab_size, "the NgramLm was built for another vocabulary size"
+            self.used = [True] * self.B                   # without a sync the host cannot tell which rows had frames
+            image = None if self.context is None else self.context.dev
+            if self.lm is None:
+                ops.ctc_beam_ctx_advance(self.desc, self.state, image, self.graph_of, top_logp, top_idx, nf)
             else:
-                assert V == self.context.vocab_size, "the ContextSet was built for another vocabulary size"
-                self.used = [True] * self.B               # without a sync the host cannot tell which rows had frames
-                ops.ctc_beam_ctx_advance(self.desc, self.state, self.context.dev, self.graph_of, top_logp, top_idx, nf)
+                ops.ctc_beam_lm_advance(self.desc, self.state, image, self.graph_of, self.lm.dev, self.lm_on, self.lm_weight,
+                                        self.length_bonus, top_logp, top_idx, nf)
 
     def _nbest_tensors(self):
-        if self.context is None:
+        """(hyp_tokens, hyp_len, hyp_score, hyp_bonus or None, hyp_lm or None, n_hyps)"""
+        if self.context is None and self.lm is None:
             toks, hlen, score, n = ops.ctc_beam_nbest(self.desc, self.state)
-            return toks, hlen, score, None, n
-        return ops.ctc_beam_ctx_nbest(self.desc, self.state, self.context.dev, self.graph_of)
+            return toks, hlen, score, None, None, n
+        image = None if self.context is None else self.context.dev
+        if self.lm is None:
+            toks, hlen, score, bonus, n = ops.ctc_beam_ctx_nbest(self.desc, self.state, image, self.graph_of)
+            return toks, hlen, score, bonus, None, n
+        return ops.ctc_beam_lm_nbest(self.desc, self.state, image, self.graph_of, self.lm.dev, self.lm_on, self.lm_weight,
+                                     self.length_bonus, self.lm_eos)
 
     def nbest_tensors(self, stream=None, detail=False):
         """(hyp_tokens (B,beam,max_frames), hyp_len (B,beam), hyp_score (B,beam), n_hyps (B,)) on the device; detail: with
-        hyp_bonus (B,beam) before n_hyps (zeros for a search without a context)."""
+        hyp_bonus (B,beam) before n_hyps (zeros for a search without a context) and, for a search with an LM, hyp_lm (B,beam)
+        after hyp_bonus."""
         with torch.cuda.stream(stream or torch.cuda.current_stream(self.device)):
-            toks, hlen, score, bonus, n = self._nbest_tensors()
+            toks, hlen, score, bonus, lm, n = self._nbest_tensors()
             if not detail:
                 return toks, hlen, score, n
-            return toks, hlen, score, torch.zeros_like(score) if bonus is None else bonus, n
+            bonus = torch.zeros_like(score) if bonus is None else bonus
+            return (toks, hlen, score, bonus, n) if self.lm is None else (toks, hlen, score, bonus, lm, n)
 
     def nbest(self, stream=None, slots=None, detail=False):
         """slots: None = every utterance; else only the listed ones, in that order (the others may have failed or be idle).
-        [(prefix, CTC score)] per utterance, best first -- with a context, best by CTC score + bonus; detail: [(prefix, CTC
-        score, bonus)], bonus = the part of the context bonus that is final for that prefix."""
+        [(prefix, CTC score)] per utterance, best first -- with a context, best by CTC score + bonus, with an LM by the fused
+        key; detail: [(prefix, CTC score, bonus)], bonus = the part of the context bonus that is final for that prefix, and
+        for a search with an LM [(prefix, CTC score, bonus, lm)], lm = log P_LM(prefix) (+ log P(</s> | prefix) with lm_eos)."""
         with torch.cuda.stream(stream or torch.cuda.current_stream(self.device)):   # the copies wait for the search's stream
-            toks, hlen, score, bonus, n = (None if t is None else t.cpu() for t in self._nbest_tensors())
+            toks, hlen, score, bonus, lm, n = (None if t is None else t.cpu() for t in self._nbest_tensors())
         out = []
         for b in (range(self.B) if slots is None else [int(x) for x in slots]):
             nb = int(n[b])
@@ -166,6 +206,8 @@ class CtcBeamSearch:
             hyps = [(tuple(toks[b, i, :int(hlen[b, i])].tolist()), float(score[b, i])) for i in range(nb)]
             if detail:
                 hyps = [h + (0.0 if bonus is None else float(bonus[b, i]),) for i, h in enumerate(hyps)]
+                if lm is not None:
+                    hyps = [h + (float(lm[b, i]),) for i, h in enumerate(hyps)]
             out.append(hyps)
         return out
 
@@ -236,10 +278,13 @@ class CtcDecoder:
         res = self.forward(xs, xs_lens)
         return self.batch_prefix_beam_from_logits(res["out_nosm"], res["out_lens"], beam_size), res["out_nosm"]
 
-    def batch_prefix_beam_from_logits(self, logits: torch.Tensor, lens: torch.Tensor, beam_size: int):
-        """logits (B,T',V) on the device, lens (B,) valid frames per utterance -> n-best per utterance (device search)."""
+    def batch_prefix_beam_from_logits(self, logits: torch.Tensor, lens: torch.Tensor, beam_size: int, lm=None, lm_weight=0.5,
+                                      length_bonus=0.0, lm_eos=True):
+        """logits (B,T',V) on the device, lens (B,) valid frames per utterance -> n-best per utterance (device search).
+        lm: a m3asr.lm.NgramLm on the logits' device -- shallow fusion, as CtcBeamSearch(lm=)."""
         B, T = int(logits.shape[0]), int(logits.shape[1])
-        search = CtcBeamSearch(B, beam_size, T, self.blank_idx, logits.device)
+        search = CtcBeamSearch(B, beam_size, T, self.blank_idx, logits.device, lm=lm, lm_weight=lm_weight,
+                               length_bonus=length_bonus, lm_eos=lm_eos)
         search.advance(logits, lens)
         return search.nbest()
 
@@ -262,25 +307,31 @@ class StreamingCtcDecoder:
     Over a slot-mode encoder (engine.streaming(..., independent=True)) the streams are independent here too: a slot that is
     idle in a step consumes no frame in either search, and reset / partial / finish take `slots=[...]`."""
 
-    def __init__(self, streaming_encoder, beam, blank=0, context=None):
+    def __init__(self, streaming_encoder, beam, blank=0, context=None, lm=None, lm_weight=0.5, length_bonus=0.0, lm_eos=True):
         """context: a m3asr.context.ContextSet on the engine's device (hotword biasing of the beam search; the greedy
-        search is not biased); reset(graph_ids=) chooses each stream's graph, -1 = unbiased."""
+        search is not biased); reset(graph_ids=) chooses each stream's graph, -1 = unbiased.
+        lm: a m3asr.lm.NgramLm on the engine's device (shallow fusion in the beam search, as CtcBeamSearch(lm=); the walk
+        runs inside the advance kernel, so a chunk is still one graph replay and no host round trip); reset(lm_on=) switches
+        it per stream."""
         self.st = streaming_encoder
         self.context = context
+        self.lm = lm
         e = streaming_encoder.eng
         self.c = streaming_encoder.c
         B, max_frames = int(streaming_encoder.desc.B), int(streaming_encoder.desc.max_frames)
-        self.beam = CtcBeamSearch(B, beam, max_frames, blank, e.device, context=context)
+        self.beam = CtcBeamSearch(B, beam, max_frames, blank, e.device, context=context, lm=lm, lm_weight=lm_weight,
+                                  length_bonus=length_bonus, lm_eos=lm_eos)
         self.gdesc = ops.ctc_greedy_stream_desc(B, max_frames, blank)
         self.gstate = torch.empty(max(ops.ctc_greedy_stream_state_size(self.gdesc), 1), dtype=torch.uint8, device=e.device)
         self.frame_ids = torch.empty(B, self.c, dtype=torch.int32, device=e.device)
         self.n_out = torch.zeros(B, dtype=torch.int32, device=e.device)
         self.reset()
 
-    def reset(self, slots=None, graph_ids=None):
+    def reset(self, slots=None, graph_ids=None, lm_on=None):
         """Restart all streams, or (slot-mode encoder) the listed slots: encoder state, beam search and greedy search.
         graph_ids (decoder with a context): the graph each restarted stream takes, one per slot; a stream restarted without
-        one keeps the graph it had."""
+        one keeps the graph it had.  lm_on (decoder with an LM): whether each restarted stream runs with the LM."""
+        kw = {} if lm_on is None else {"lm_on": lm_on}
         e = self.st.eng
         if slots is None:
             self.st.reset()
@@ -288,14 +339,14 @@ class StreamingCtcDecoder:
             self.st.reset(slots=slots)
         with torch.cuda.stream(e.stream):
             if slots is None:
-                self.beam.reset(e.stream, graph_ids=graph_ids)
+                self.beam.reset(e.stream, graph_ids=graph_ids, **kw)
                 ops.ctc_greedy_stream_reset(self.gdesc, self.gstate)
             elif len(slots) > 0:
                 lst = torch.tensor([int(b) for b in slots], dtype=torch.int32).to(e.device)
-                if self.context is None:
+                if self.context is None and self.lm is None:
                     self.beam.reset(e.stream, slots=lst, graph_ids=graph_ids)
                 else:
-                    self.beam.reset(e.stream, slots=[int(b) for b in slots], graph_ids=graph_ids)
+                    self.beam.reset(e.stream, slots=[int(b) for b in slots], graph_ids=graph_ids, **kw)
                 ops.ctc_greedy_stream_reset(self.gdesc, self.gstate, lst)
 
     def frames_of(self, valid):

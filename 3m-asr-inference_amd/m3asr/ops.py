@@ -601,6 +601,97 @@ def ctc_beam_ctx_nbest(desc, state, image, graph_of):
     return toks, hlen, score, bonus, n
 
 
+# ---- n-gram LM shallow fusion (m3asr.lm builds the images)
+def ctc_lm_validate(image, V):
+    """m3_ctc_lm_validate on a HOST image (numpy int32 words); raises M3Error naming the first offence."""
+    import numpy as np
+    img = np.ascontiguousarray(image)
+    check(_lib.load().m3_ctc_lm_validate(img.ctypes.data_as(C.c_void_p), img.nbytes, int(V)), "m3_ctc_lm_validate")
+
+
+def ctc_prefix_beam_search_lm_host(top_logp, top_idx, beam, blank=0, image=None, graph=0, lm_image=None, alpha=0.5, beta=0.0,
+                                   use_eos=True):
+    """ctc_prefix_beam_search_ctx_host with the fused ranking of a HOST LM image (numpy int32 words; None = no LM):
+    [(prefix tuple, ctc score, bonus = context final, lm = log P_LM (+ final with use_eos), context state)], ordered by
+    (ctc + bonus) + (alpha lm + beta len)."""
+    import numpy as np
+    lib = _lib.load()
+    lp = np.ascontiguousarray(top_logp, dtype=np.float32)
+    ix = np.ascontiguousarray(top_idx, dtype=np.int32)
+    T, k = lp.shape
+    assert ix.shape == (T, k)
+    if T == 0:
+        return [(tuple(), 0.0, 0.0, 0.0, 0)]
+    img = None if image is None else np.ascontiguousarray(image)
+    lmi = None if lm_image is None else np.ascontiguousarray(lm_image)
+    toks = np.empty((beam, T), dtype=np.int32)
+    hlen = np.empty(beam, dtype=np.int32)
+    score = np.empty(beam, dtype=np.float32)
+    bonus = np.empty(beam, dtype=np.float32)
+    lm = np.zeros(beam, dtype=np.float32)
+    state = np.empty(beam, dtype=np.int32)
+    n = C.c_int32(0)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    check(lib.m3_ctc_prefix_beam_search_lm(vp(lp), vp(ix), T, k, int(beam), int(blank), None if img is None else vp(img),
+                                           0 if img is None else img.nbytes, int(graph), None if lmi is None else vp(lmi),
+                                           0 if lmi is None else lmi.nbytes, float(alpha), float(beta), int(bool(use_eos)),
+                                           vp(toks), vp(hlen), vp(score), vp(bonus), vp(state), vp(lm),
+                                           C.cast(C.byref(n), C.c_void_p)), "m3_ctc_prefix_beam_search_lm")
+    return [(tuple(int(v) for v in toks[i, :hlen[i]]), float(score[i]), float(bonus[i]), float(lm[i]), int(state[i]))
+            for i in range(n.value)]
+
+
+def ctc_beam_lm_state_size(desc):
+    """bytes of device state of the fused search: the biased layout, then every node's LM state and LM sum."""
+    n = _lib.load().m3_ctc_beam_lm_state_size(C.byref(desc))
+    if n == 0 and desc.B > 0:
+        raise _lib.M3Error("m3_ctc_beam_lm_state_size failed: " + _lib.last_error())
+    return n
+
+
+def ctc_beam_lm_reset(desc, state, slots=None):
+    if slots is not None:
+        check(_lib.load().m3_ctc_beam_lm_reset_slots(C.byref(desc), _p(state), state.numel() * state.element_size(), _i32(slots),
+                                                     slots.numel(), _stream()), "m3_ctc_beam_lm_reset_slots")
+        return
+    check(_lib.load().m3_ctc_beam_lm_reset(C.byref(desc), _p(state), state.numel() * state.element_size(), _stream()),
+          "m3_ctc_beam_lm_reset")
+
+
+def ctc_beam_lm_advance(desc, state, image, graph_of, lm_image, lm_on, alpha, beta, top_logp, top_idx, n_frames):
+    """ctc_beam_ctx_advance with the device LM image (int32 words, or None), lm_on (B,) int32 on the device (0 = this
+    utterance runs without the LM) and the run-time weights alpha (LM) and beta (per token)."""
+    B, Tc, k = top_logp.shape
+    assert B == desc.B and k == desc.k and tuple(top_idx.shape) == (B, Tc, k) and n_frames.numel() == B
+    assert graph_of.numel() == B and lm_on.numel() == B
+    img, nbytes = _image(image)
+    lmi, lm_bytes = _image(lm_image)
+    check(_lib.load().m3_ctc_beam_lm_advance(C.byref(desc), _p(state), state.numel() * state.element_size(), img, nbytes,
+                                             _i32(graph_of), lmi, lm_bytes, _i32(lm_on), float(alpha), float(beta),
+                                             _f32(top_logp), _i32(top_idx), Tc, _i32(n_frames), _stream()),
+          "m3_ctc_beam_lm_advance")
+
+
+def ctc_beam_lm_nbest(desc, state, image, graph_of, lm_image, lm_on, alpha, beta, use_eos=True):
+    """-> (hyp_tokens, hyp_len, hyp_score (the CTC score), hyp_bonus, hyp_lm (B,beam), n_hyps), ordered by the fused key."""
+    dev = state.device
+    B, beam, F = desc.B, desc.beam, desc.max_frames
+    assert graph_of.numel() == B and lm_on.numel() == B
+    toks = torch.empty(B, beam, F, dtype=torch.int32, device=dev)
+    hlen = torch.empty(B, beam, dtype=torch.int32, device=dev)
+    score = torch.empty(B, beam, dtype=torch.float32, device=dev)
+    bonus = torch.empty(B, beam, dtype=torch.float32, device=dev)
+    lm = torch.empty(B, beam, dtype=torch.float32, device=dev)
+    n = torch.empty(B, dtype=torch.int32, device=dev)
+    img, nbytes = _image(image)
+    lmi, lm_bytes = _image(lm_image)
+    check(_lib.load().m3_ctc_beam_lm_nbest(C.byref(desc), _p(state), state.numel() * state.element_size(), img, nbytes,
+                                           _i32(graph_of), lmi, lm_bytes, _i32(lm_on), float(alpha), float(beta),
+                                           int(bool(use_eos)), _p(toks), _p(hlen), _p(score), _p(bonus), _p(lm), _p(n), _stream()),
+          "m3_ctc_beam_lm_nbest")
+    return toks, hlen, score, bonus, lm, n
+
+
 def ctc_greedy_stream_desc(B, max_frames, blank=0):
     d = _lib.CtcGreedyDesc(int(B), int(max_frames), int(blank))
     if _lib.load().m3_ctc_greedy_stream_state_size(C.byref(_lib.CtcGreedyDesc(1, d.max_frames, d.blank))) == 0:

@@ -5,7 +5,8 @@ arrives per session in pieces of any size; every `step()` is ONE engine call in 
 live and every other slot idle.
 
     pool = StreamPool(StreamingCtcDecoder(engine.streaming(B, max_frames, independent=True), beam=10))
-    sid = pool.open()                       # takes a free slot, restarts it (open(context=graph_id): with hotwords)
+    sid = pool.open()                       # takes a free slot, restarts it (open(context=graph_id): with hotwords;
+                                            # open(lm=False): without the decoder's LM)
     pool.push(sid, frames)                  # (n, idim) feature frames, any n
     pool.end(sid)                           # no more audio for this session
     live = pool.step()                      # sids that moved one chunk
@@ -143,18 +144,24 @@ class StreamPool:
     def slot_of(self, sid):
         return self._get(sid)[0]
 
-    def open(self, context=None):
+    def open(self, context=None, lm=None):
         """Take a free slot and restart it; -> stream id.  Raises M3Error when all B slots are taken.
-        context: graph id in the decoder's ContextSet for this session's beam search (None = unbiased)."""
+        context: graph id in the decoder's ContextSet for this session's beam search (None = unbiased).
+        lm: whether this session's beam search runs with the decoder's LM (None = yes if the decoder has one)."""
         biased = getattr(self.dec, "context", None) is not None
+        fused = getattr(self.dec, "lm", None) is not None
         if context is not None and not biased:
             raise _lib.M3Error("StreamPool.open: the decoder was built without a context")
+        if lm and not fused:
+            raise _lib.M3Error("StreamPool.open: the decoder was built without an LM")
         for b, holder in enumerate(self.slot_sid):
             if holder is None:
+                kw = {}
                 if biased:
-                    self.dec.reset(slots=[b], graph_ids=[-1 if context is None else int(context)])
-                else:
-                    self.dec.reset(slots=[b])
+                    kw["graph_ids"] = [-1 if context is None else int(context)]
+                if fused:
+                    kw["lm_on"] = [lm is None or bool(lm)]
+                self.dec.reset(slots=[b], **kw)
                 sid = self.next_sid
                 self.next_sid += 1
                 self.slot_sid[b] = sid

@@ -440,6 +440,53 @@ int m3_ctc_beam_ctx_advance(const m3_ctc_beam_desc* desc, void* state, size_t st
 int m3_ctc_beam_ctx_nbest(const m3_ctc_beam_desc* desc, const void* state, size_t state_bytes, const void* image,
                           size_t image_bytes, const int32_t* graph_of, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score,
                           float* hyp_bonus, int32_t* n_hyps, m3_stream stream);
+/* N-gram LM shallow fusion of the prefix beam search: a prefix y is ranked by
+ *   (ctc + bonus) + (alpha lm(y) + beta |y|),   lm(y) = log P_LM(y), natural log.
+ * An LM IMAGE is one image of 4-byte little-endian words: a 20-word header
+ *   [0x4d4c334d, version = 1, V, order, n_states, n_arcs, start, unk_logp (float bits),
+ *    word offsets of uni_logp, uni_next, arc_begin, arc_tok, arc_next, arc_logp, bo_state, bo_weight, final, words, 0, 0]
+ * and the tables of a deterministic back-off automaton over context states: state 0 (the empty context) has dense arcs
+ * uni_logp [V] float / uni_next [V] int32; state s >= 1 has the sparse arcs [arc_begin[s], arc_begin[s + 1]) of arc_tok
+ * (strictly ascending inside a state), arc_next, arc_logp, and backs off to bo_state[s] < s at the price bo_weight[s];
+ * final [n_states] = log P(</s> | state), back-off resolved.  Limits: order <= 8, n_states <= 2^26, image <= 1 GiB.
+ * m3asr.lm (Python) compiles ARPA files into such images.  THE SCORE CONTRACT, step(state, tok):
+ *   w = 0.0 (double); st = state; while st != 0: binary-search tok among st's arcs; found: return (w + (double)arc_logp,
+ *   arc_next); else w += (double)bo_weight[st], st = bo_state[st].  At st = 0: (w + (double)uni_logp[tok], uni_next[tok]);
+ *   a token outside [0, V): (w + (double)unk_logp, 0).
+ * lm(y) is the left-to-right double sum of the steps from `start`; lm_state(y) the state reached.
+ * m3_ctc_lm_validate: host-only check of a HOST image for vocabulary size V: header, limits, every table inside the image,
+ *   arc_begin monotone from 0 to n_arcs, arc_tok ascending inside a state and in [0, V), every uni_next / arc_next in
+ *   [0, n_states), bo_state[s] < s and at most order - 1 back-off levels above state 0, every float finite.  Run it on the
+ *   host copy before the image is uploaded.  Independently the kernels range-check the header and every index they form an
+ *   address from (a failed header check means "LM off", a bad index state 0).
+ * m3_ctc_prefix_beam_search_lm: m3_ctc_prefix_beam_search_ctx plus a host LM image (validated inside the call), alpha, beta
+ *   and use_eos.  Candidates are pruned by the key above, evaluated in double in exactly that association; the hypotheses come
+ *   out ordered by (ctc + final) + (alpha (lm + final_lm[lm_state] use_eos) + beta |y|), stable on the beam order.  hyp_score
+ *   stays the CTC score, hyp_bonus the context final; hyp_lm [beam] = lm + final_lm use_eos.  lm_image NULL: exactly what
+ *   m3_ctc_prefix_beam_search_ctx returns (hyp_lm, if given, zeros).
+ * m3_ctc_beam_lm_*: the device search with the fused ranking.  The state is m3_ctc_beam_ctx_state_size bytes laid out as for
+ *   m3_ctc_beam_ctx_*, byte for byte, then per utterance lm_state [1 + max_frames * beam] int32 and lm_sum [...] double.
+ *   _advance / _nbest take both DEVICE images (either may be NULL, 0), graph_of [B] as m3_ctc_beam_ctx_*, lm_on [B] (device
+ *   int32; 0 = this utterance runs without the LM, and its result is m3_ctc_beam_ctx_*'s bit for bit) and alpha, beta (and
+ *   _nbest use_eos): run-time arguments, not part of the image.  An utterance keeps its lm_on, alpha and beta from a reset to
+ *   the next.  _nbest additionally writes hyp_lm [B][beam]. */
+int m3_ctc_lm_validate(const void* image, size_t image_bytes, int V);
+int m3_ctc_prefix_beam_search_lm(const float* top_logp, const int32_t* top_idx, int T, int k, int beam, int blank,
+                                 const void* image, size_t image_bytes, int graph, const void* lm_image, size_t lm_bytes,
+                                 double alpha, double beta, int use_eos, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score,
+                                 float* hyp_bonus, int32_t* hyp_state, float* hyp_lm, int32_t* n_hyps);
+size_t m3_ctc_beam_lm_state_size(const m3_ctc_beam_desc* desc);
+int m3_ctc_beam_lm_reset(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, m3_stream stream);
+int m3_ctc_beam_lm_reset_slots(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const int32_t* slots, int n,
+                               m3_stream stream);
+int m3_ctc_beam_lm_advance(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const void* image, size_t image_bytes,
+                           const int32_t* graph_of, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha,
+                           double beta, const float* top_logp, const int32_t* top_idx, int T_chunk, const int32_t* n_frames,
+                           m3_stream stream);
+int m3_ctc_beam_lm_nbest(const m3_ctc_beam_desc* desc, const void* state, size_t state_bytes, const void* image, size_t image_bytes,
+                         const int32_t* graph_of, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha,
+                         double beta, int use_eos, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score, float* hyp_bonus,
+                         float* hyp_lm, int32_t* n_hyps, m3_stream stream);
 /* Greedy search chunk by chunk: per stream the previous frame's argmax is carried across calls and the collapsed tokens are
  * appended to a buffer inside the state (m3_ctc_greedy_stream_state_size bytes, device).  After any sequence of advances the
  * tokens equal m3_ctc_greedy on the concatenation of the frames each stream was given.

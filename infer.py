@@ -12,7 +12,13 @@ Prints ``time=...ms`` for one forward after a warm-up and the output's shape / s
     python3 infer.py -p encoder.plan -w speech.wav --hotwords words.txt [--hotword-score 3.0] [--beam 10]
 
 words.txt holds one phrase per line as space-separated token ids (the project has no tokenizer).  The output scores are then
-searched twice on the device, plain and biased towards the phrases (m3asr.context), and the best hypothesis of each is printed."""
+searched twice on the device, plain and biased towards the phrases (m3asr.context), and the best hypothesis of each is printed.
+
+    python3 infer.py -p encoder.plan -w speech.wav --lm lm.arpa [--units units.txt] [--lm-weight 0.5] [--length-bonus 0.0]
+
+lm.arpa is an n-gram LM in ARPA format (or an image saved by m3asr.lm.NgramLm.save, *.npy); units.txt maps its words to
+token ids (`token id` per line; without it the words are token ids).  The scores are searched plain and with the LM fused into
+the ranking (m3asr.lm), together with --hotwords if both are given."""
 import argparse
 import os
 import sys
@@ -56,6 +62,34 @@ def print_hotword_search(scores, device, args):
         print("utt %d biased: score=%.4f bonus=%.4f tokens=%s" % (b, h[0][1], h[0][2], " ".join(str(t) for t in h[0][0])))
 
 
+def print_lm_search(scores, device, args):
+    """Best prefix beam hypothesis of every utterance without and with the LM (and the hotwords, if given) fused in."""
+    import torch
+    from m3asr.decode import CtcBeamSearch
+    from m3asr.lm import NgramLm
+    x = torch.from_numpy(np.ascontiguousarray(scores, dtype=np.float32)).to(device)
+    x = x.reshape(-1, x.shape[-2], x.shape[-1])
+    B, T, V = x.shape
+    lm = NgramLm.load(args.lm) if args.lm.endswith(".npy") else NgramLm.from_arpa(args.lm, args.units, vocab_size=V)
+    lm.to(device)
+    ctx = None
+    if args.hotwords:
+        from m3asr.context import ContextGraph, ContextSet, read_phrases
+        ctx = ContextSet([ContextGraph(read_phrases(args.hotwords), V, score=args.hotword_score)], device=device)
+    lens = torch.full((B,), T, dtype=torch.int32)
+    plain = CtcBeamSearch(B, args.beam, T, device=device)
+    plain.advance(x, lens)
+    fused = CtcBeamSearch(B, args.beam, T, device=device, context=ctx, lm=lm, lm_weight=args.lm_weight,
+                          length_bonus=args.length_bonus)
+    if ctx is not None:
+        fused.reset(graph_ids=[0] * B)
+    fused.advance(x, lens)
+    for b, (u, h) in enumerate(zip(plain.nbest(), fused.nbest(detail=True))):
+        print("utt %d plain: score=%.4f tokens=%s" % (b, u[0][1], " ".join(str(t) for t in u[0][0])))
+        print("utt %d fused: score=%.4f bonus=%.4f lm=%.4f tokens=%s" % (b, h[0][1], h[0][2], h[0][3],
+                                                                         " ".join(str(t) for t in h[0][0])))
+
+
 def main(args):
     logger = trt_helper.init_trt_plugin(trt.Logger.INFO, "libm3asr_hip.so")
     helper = trt_helper.InferHelper(args.plan_name, logger)
@@ -71,7 +105,9 @@ def main(args):
         print("outputs.shape:" + str(o.shape))
         print("outputs.sum:" + str(o.sum()))
         print(o)
-    if args.hotwords:
+    if args.lm:
+        print_lm_search(outputs[0], helper.engine.device, args)
+    elif args.hotwords:
         print_hotword_search(outputs[0], helper.engine.device, args)
     if base is not None:
         print("compare_output=%s, dtype=%s, shape=%s" % (args.compare_output_file, base[0].dtype, base[0].shape))
@@ -87,5 +123,9 @@ if __name__ == "__main__":
     p.add_argument("-o", "--compare_output_file", required=False, help="The compare output .npy file path.")
     p.add_argument("--hotwords", help="Phrase list: one phrase of space-separated token ids per line.")
     p.add_argument("--hotword-score", type=float, default=3.0, help="Bonus per matched token (log domain).")
-    p.add_argument("--beam", type=int, default=10, help="Beam size of the prefix beam searches run with --hotwords.")
+    p.add_argument("--beam", type=int, default=10, help="Beam size of the prefix beam searches run with --hotwords / --lm.")
+    p.add_argument("--lm", help="n-gram LM: an ARPA file, or a compiled image (*.npy) saved by m3asr.lm.NgramLm.save.")
+    p.add_argument("--units", help="`token id` per line: the ARPA's words as token ids (default: the words are token ids).")
+    p.add_argument("--lm-weight", type=float, default=0.5, help="Weight of log P_LM in the ranking.")
+    p.add_argument("--length-bonus", type=float, default=0.0, help="Bonus per token of a prefix in the ranking.")
     main(p.parse_args())

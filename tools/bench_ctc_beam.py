@@ -3,9 +3,14 @@
 batch: B = 16 utterances of T' = 125 output frames, V = 1434, beam = k = 10, synthetic logits.
 
   python tools/bench_ctc_beam.py [--batch 16] [--frames 125] [--beam 10] [--chunk 16] [--reps 5] [--context N_PHRASES]
+                                 [--lm N_NGRAMS | --lm-image FILE.npy] [--lm-weight 0.5]
 
 --context N: the biased search (m3_ctc_beam_ctx_advance) with one graph of N random phrases of 2..6 tokens (N = 0: an empty
 graph, the cost of the biased kernel alone), next to the unbiased one; its host column is m3_ctc_prefix_beam_search_ctx.
+
+--lm N: the fused search (m3_ctc_beam_lm_advance) with a synthetic trigram LM of about N n-grams (tools/lm_synth.py; or
+--lm-image: an image saved by m3asr.lm.NgramLm.save), with the --context graph if one is given, next to the plain search: its
+figures, their ratio to the plain ones of the same run, the same kernel with lm_on = 0, and m3_ctc_prefix_beam_search_lm.
 
 Device: one advance over all frames, and the same frames in chunks of --chunk (one advance per chunk), timed with hipEvents
 (top-k excluded: it is the same launch for both searches); run under `rocprofv3 --kernel-trace --stats` for kernel times.
@@ -35,6 +40,9 @@ def main():
     ap.add_argument("--chunk", type=int, default=16)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--context", type=int, default=None, metavar="N_PHRASES")
+    ap.add_argument("--lm", type=int, default=None, metavar="N_NGRAMS")
+    ap.add_argument("--lm-image", default=None, metavar="FILE.npy")
+    ap.add_argument("--lm-weight", type=float, default=0.5)
     args = ap.parse_args()
     B, T, V, beam = args.batch, args.frames, args.vocab, args.beam
     g = torch.Generator().manual_seed(0)
@@ -73,6 +81,7 @@ def main():
            "device_chunked_ms": {"chunk": args.chunk, "advances": len(chunks), "total": round(per, 4),
                                  "per_advance": round(per / len(chunks), 4)},
            "host_routine_ms": round(float(np.median(hs)), 4), "data": "synthetic"}
+    cs = None
     if args.context is not None:
         from m3asr.context import ContextGraph, ContextSet
         rng = np.random.default_rng(0)
@@ -95,6 +104,37 @@ def main():
                           "device_one_advance_ms": round(c_one, 4),
                           "device_chunked_ms": {"total": round(c_per, 4), "per_advance": round(c_per / len(chunks), 4)},
                           "host_routine_ms": round(float(np.median(hs)), 4)}
+    if args.lm is not None or args.lm_image:
+        from m3asr.lm import NgramLm
+        if args.lm_image:
+            lm = NgramLm.load(args.lm_image)
+        else:
+            from lm_synth import synthetic_lm
+            lm = synthetic_lm(args.lm, V)
+        lm.to("cuda")
+        lstate = torch.empty(ops.ctc_beam_lm_state_size(desc), dtype=torch.uint8, device="cuda")
+        go = torch.full((B,), 0 if cs is not None else -1, dtype=torch.int32, device="cuda")
+        image = None if cs is None else cs.dev
+        lreset = lambda: ops.ctc_beam_lm_reset(desc, lstate)
+        a, w = args.lm_weight, 0.0
+        res = {}
+        for name, flag in (("fused", 1), ("lm_off", 0)):
+            on = torch.full((B,), flag, dtype=torch.int32, device="cuda")
+            l_one = timed(lambda: ops.ctc_beam_lm_advance(desc, lstate, image, go, lm.dev, on, a, w, lp, ix, nf), lreset)
+            l_per = timed(lambda: [ops.ctc_beam_lm_advance(desc, lstate, image, go, lm.dev, on, a, w, p, q, n)
+                                   for (p, q), n in zip(lpc, nfc)], lreset)
+            res[name] = {"device_one_advance_ms": round(l_one, 4),
+                         "device_chunked_ms": {"total": round(l_per, 4), "per_advance": round(l_per / len(chunks), 4)},
+                         "one_advance_over_plain": round(l_one / one, 3)}
+        hs = []
+        for _ in range(args.reps):
+            t0 = time.perf_counter()
+            for b in range(B):
+                ops.ctc_prefix_beam_search_lm_host(lph[b], ixh[b], beam, 0, None if cs is None else cs.image, 0, lm.image, a, w)
+            hs.append((time.perf_counter() - t0) * 1e3)
+        out["lm"] = {"n_grams": lm.n_grams, "order": lm.order, "states": lm.n_states, "arcs": lm.n_arcs,
+                     "image_bytes": int(lm.image.nbytes), "weight": a, "with_context": cs is not None, **res,
+                     "host_routine_ms": round(float(np.median(hs)), 4)}
     print(json.dumps(out))
 
 

@@ -2,7 +2,7 @@
 """Chunk-by-chunk decoding (m3_engine_forward_chunk) timed: latency of one chunk step and the real-time factor it implies.
 
   python tools/bench_streaming.py [--chunk 16] [--left-chunks 4] [--batch 1] [--weight-dtype f32] [--seconds 20] [--beam N]
-                                  [--independent [--stagger N]] [--audio]
+                                  [--independent [--stagger N]] [--audio] [--lm [N_NGRAMS]]
 
 18L x 32e encoder with causal conv modules in both encoders, static_chunk_size = chunk (output frames; one chunk = 4 x chunk
 input frames of 10 ms), synthetic weights and features.  Every step after the first is a hipGraph replay (the chunk counter
@@ -11,6 +11,9 @@ audio seconds per chunk, real-time factor = compute time / audio time, streams o
 --beam N (> 0): also time the CTC decode of every chunk (StreamingCtcDecoder: top-k + prefix beam advance + streaming greedy,
 on the engine stream behind the chunk forward) and add "decode_ms_per_chunk" to the line.
 --context N (with --beam): the beam search of every stream is biased by one graph of N random phrases (m3asr.context).
+--lm [N] (with --beam): after the plain pass the same chunks are decoded again with a synthetic trigram LM of about N n-grams
+(default 100000; tools/lm_synth.py) fused into the beam search (StreamingCtcDecoder(lm=), with the --context graph if given):
+"lm" carries its "decode_ms_per_chunk" next to the plain one and their ratio.
 --independent: slot mode (m3_engine_forward_chunk_slots), every stream with its own position; --stagger N: stream b starts N
 steps after stream b - 1 and ends as many steps later (idle slots before and after).  The line then also carries "mode" and
 the mean number of live slots per timed step.
@@ -46,6 +49,8 @@ def main():
     ap.add_argument("--seconds", type=float, default=20.0, help="audio per stream")
     ap.add_argument("--beam", type=int, default=0, help="> 0: decode every chunk with a prefix beam search of this width")
     ap.add_argument("--context", type=int, default=None, metavar="N_PHRASES", help="with --beam: bias the beam search by N phrases")
+    ap.add_argument("--lm", type=int, nargs="?", const=100000, default=None, metavar="N_NGRAMS",
+                    help="with --beam: decode the chunks again with an n-gram LM fused into the beam search")
     ap.add_argument("--independent", action="store_true", help="slot mode: every stream has its own chunk counter")
     ap.add_argument("--stagger", type=int, default=0, help="slot mode: stream b starts this many steps after stream b - 1")
     ap.add_argument("--audio", action="store_true", help="also time the chunks fed samples through the log-Mel front end")
@@ -153,6 +158,31 @@ def main():
             out["context_phrases"] = args.context
         out["decode_ms_per_chunk"] = {"beam": args.beam, "p50": round(float(np.median(d)), 4),
                                       "p99": round(float(d[int(0.99 * (len(d) - 1))]), 4), "min": round(float(d[0]), 4)}
+    if dec is not None and args.lm is not None:
+        from lm_synth import synthetic_lm
+        from m3asr.decode import StreamingCtcDecoder
+        lm = synthetic_lm(args.lm, cfg.output_dim).to(eng.device)
+        fdec = StreamingCtcDecoder(st, args.beam, context=dec.context, lm=lm)
+        full_out = torch.full((args.batch,), args.chunk, dtype=torch.int32, device=eng.device)
+        ftimes = []
+        for rep in range(3):
+            fdec.reset(graph_ids=None if fdec.context is None else [0] * args.batch)
+            for n in range(n_chunks):
+                e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+                st.step(win, torch.full((args.batch,), st.window, dtype=torch.int32, device=eng.device))
+                e1.record(eng.stream)
+                with torch.cuda.stream(eng.stream):
+                    fdec.beam.advance(st.logits, full_out, eng.stream)
+                    ops.ctc_greedy_stream_advance(fdec.gdesc, fdec.gstate, st.logits, full_out, fdec.frame_ids)
+                e2.record(eng.stream)
+                e2.synchronize()
+                if rep > 0:
+                    ftimes.append(e1.elapsed_time(e2))
+        f = np.sort(np.array(ftimes))
+        out["lm"] = {"n_grams": lm.n_grams, "states": lm.n_states, "arcs": lm.n_arcs,
+                     "decode_ms_per_chunk": {"p50": round(float(np.median(f)), 4), "p99": round(float(f[int(0.99 * (len(f) - 1))]), 4),
+                                             "min": round(float(f[0]), 4)},
+                     "p50_over_plain": round(float(np.median(f)) / out["decode_ms_per_chunk"]["p50"], 3)}
     print(json.dumps(out))
 
 
