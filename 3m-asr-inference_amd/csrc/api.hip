@@ -514,6 +514,23 @@ int m3_ctc_greedy_stream_tokens(const m3_ctc_greedy_desc* desc, const void* stat
                                 int32_t* n_tokens, m3_stream stream) {
   return launch_ctc_greedy_stream_tokens(desc, state, state_bytes, tokens, n_tokens, (hipStream_t)stream);
 }
+size_t m3_ctc_endpoint_state_size(const m3_ctc_endpoint_desc* desc) { return ctc_endpoint_state_size(desc); }
+int m3_ctc_endpoint_reset(const m3_ctc_endpoint_desc* desc, void* state, size_t state_bytes, m3_stream stream) {
+  return launch_ctc_endpoint_reset(desc, state, state_bytes, (hipStream_t)stream);
+}
+int m3_ctc_endpoint_reset_slots(const m3_ctc_endpoint_desc* desc, void* state, size_t state_bytes, const int32_t* slots, int n,
+                                m3_stream stream) {
+  M3_REQUIRE(n == 0 || slots != nullptr, "ctc_endpoint_reset_slots: null slot list");
+  if (n == 0) return 0;
+  return launch_ctc_endpoint_reset(desc, state, state_bytes, (hipStream_t)stream, slots, n);
+}
+int m3_ctc_endpoint_advance(const m3_ctc_endpoint_desc* desc, void* state, size_t state_bytes, const float* top_logp,
+                            const int32_t* top_idx, int T_chunk, int k, const int32_t* n_frames, m3_stream stream) {
+  return launch_ctc_endpoint_advance(desc, state, state_bytes, top_logp, top_idx, T_chunk, k, n_frames, (hipStream_t)stream);
+}
+int m3_ctc_endpoint_read(const m3_ctc_endpoint_desc* desc, const void* state, size_t state_bytes, int32_t* info, m3_stream stream) {
+  return launch_ctc_endpoint_read(desc, state, state_bytes, info, (hipStream_t)stream);
+}
 int m3_cat_split_cache(const void* in_cache, const void* input, int B, int cache_dim, int input_dim, void* output,
                        void* out_cache, m3_stream stream) {
   return launch_cat_split_cache(in_cache, input, B, cache_dim, input_dim, output, out_cache, (hipStream_t)stream);

@@ -1,5 +1,5 @@
 // Batched, resumable CTC prefix beam search on the device (trainer_3m_fix/model/encoder.py:182-275), and the streaming
-// form of the greedy search (:156-180).
+// form of the greedy search (:156-180); behind them the endpoint detector that runs next to the two searches.
 //
 // Prefix beam search.  The input is m3_ctc_topk's (top_logp, top_idx) [B][T_chunk][k]; the recursion is the host routine's
 // (decode.hip, ctc_prefix_beam_search_host) term for term, in double: the same log_add2 / log_add3 calls on the same operands in
@@ -768,6 +768,122 @@ __global__ __launch_bounds__(64) void ctc_greedy_stream_tokens_kernel(const int3
   if (lane == 0) n_tokens[b] = status ? -1 : count;
 }
 
+
+// ---------------------------------------------------------------- endpoint detection
+// state per stream (and a row of m3_ctc_endpoint_read's info): the seven values of the rule and one spare word
+enum { E_FRAMES = 0, E_TRAIL = 1, E_DECODED = 2, E_FIRST = 3, E_LAST = 4, E_RULE = 5, E_FIRED = 6, E_SPARE = 7, E_WORDS = 8 };
+
+int check_endpoint_desc(const m3_ctc_endpoint_desc* d) {
+  M3_REQUIRE(d != nullptr, "ctc_endpoint: null descriptor");
+  M3_REQUIRE(d->B >= 0 && d->B <= (1 << 24), "ctc_endpoint: B = %d outside [0, 2^24]", d->B);
+  M3_REQUIRE(d->blank >= 0, "ctc_endpoint: blank = %d < 0", d->blank);
+  M3_REQUIRE(d->n_rules >= 1 && d->n_rules <= 4, "ctc_endpoint: n_rules = %d outside [1, 4]", d->n_rules);
+  // a blank above p = 0.5 is the frame's argmax, so entry 0 of any top-k decides; NaN fails both comparisons
+  M3_REQUIRE(d->log_blank_threshold >= (float)std::log(0.5) && d->log_blank_threshold < 0.0f,
+             "ctc_endpoint: log_blank_threshold = %g outside [log 0.5, 0)", (double)d->log_blank_threshold);
+  for (int r = 0; r < d->n_rules; ++r)
+    M3_REQUIRE((d->rule[r].must_decoded == 0 || d->rule[r].must_decoded == 1) && d->rule[r].min_trailing >= 0 &&
+                   d->rule[r].min_length >= 0,
+               "ctc_endpoint: rule %d = (%d, %d, %d): must_decoded is 0 or 1, the frame counts are >= 0", r + 1,
+               d->rule[r].must_decoded, d->rule[r].min_trailing, d->rule[r].min_length);
+  return 0;
+}
+
+__global__ __launch_bounds__(256) void ctc_endpoint_reset_kernel(int32_t* state, int B, const int32_t* __restrict__ slots, int n) {
+  int b = blockIdx.x * 256 + threadIdx.x;
+  if (slots != nullptr) {                         // a device list of n streams (entries outside [0, B) are skipped)
+    if (b >= n) return;
+    b = slots[b];
+    if (b < 0) return;
+  }
+  if (b >= B) return;
+  int32_t* st = state + (size_t)b * E_WORDS;
+  st[E_FRAMES] = 0;
+  st[E_TRAIL] = 0;
+  st[E_DECODED] = 0;
+  st[E_FIRST] = -1;
+  st[E_LAST] = -1;
+  st[E_RULE] = 0;
+  st[E_FIRED] = -1;
+  st[E_SPARE] = 0;
+}
+
+// What a stream's state is after lane L of an iteration, from the state before the iteration's lane 0 and the two ballots.
+// Lanes 0 .. L hold real frames (the caller asks only for those), so a clear bit of `blank` at or below L is a frame that
+// ends the run of blanks.
+struct EpState {
+  int frames, trail, decoded, first, last;
+};
+__device__ __forceinline__ EpState ep_after_lane(const EpState& c, unsigned long long blank, unsigned long long speech, int L) {
+  const unsigned long long upto = L >= 63 ? ~0ull : (1ull << (L + 1)) - 1ull;      // lanes 0 .. L
+  const unsigned long long stop = ~blank & upto, sp = speech & upto;
+  EpState s;
+  s.frames = c.frames + L + 1;
+  s.trail = stop ? L - (63 - __clzll((long long)stop)) : c.trail + L + 1;
+  s.decoded = (c.decoded || sp) ? 1 : 0;
+  s.first = c.first >= 0 || !sp ? c.first : c.frames + (__ffsll((long long)sp) - 1);
+  s.last = sp ? c.frames + (63 - __clzll((long long)sp)) : c.last;
+  return s;
+}
+
+// one wave per stream, 64 frames per iteration: every lane works out the state after its own frame and evaluates the rules
+// there; the first lane on which a rule fires ends the call for this stream
+__global__ __launch_bounds__(64) void ctc_endpoint_advance_kernel(m3_ctc_endpoint_desc d, int32_t* state,
+                                                                  const float* __restrict__ top_logp,
+                                                                  const int32_t* __restrict__ top_idx, int T_chunk, int k,
+                                                                  const int32_t* __restrict__ n_frames) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  int32_t* st = state + (size_t)b * E_WORDS;
+  const int nf = min(max(n_frames[b], 0), T_chunk);
+  if (nf == 0 || st[E_RULE] != 0) return;         // idle, or latched: the state stays word for word
+  EpState c{st[E_FRAMES], st[E_TRAIL], st[E_DECODED], st[E_FIRST], st[E_LAST]};
+  int rule = 0;
+  for (int t0 = 0; t0 < nf; t0 += 64) {
+    const int t = t0 + lane, n_it = min(nf - t0, 64);
+    bool is_blank = false, is_speech = false;
+    if (t < nf) {                                 // rows past nf are padding and are not read
+      const size_t e0 = ((size_t)b * T_chunk + t) * k;
+      const int id = top_idx[e0];
+      is_speech = id != d.blank;
+      is_blank = !is_speech && top_logp[e0] > d.log_blank_threshold;
+    }
+    const unsigned long long mb = __ballot(is_blank), ms = __ballot(is_speech);
+    int fired = 0;
+    if (t < nf) {
+      const EpState s = ep_after_lane(c, mb, ms, lane);
+#pragma unroll
+      for (int r = 3; r >= 0; --r)
+        if (r < d.n_rules && (s.decoded || !d.rule[r].must_decoded) && s.trail >= d.rule[r].min_trailing &&
+            s.frames >= d.rule[r].min_length)
+          fired = r + 1;                          // descending r: the lowest rule that fires stays
+    }
+    const unsigned long long mf = __ballot(fired != 0);
+    if (mf) {                                     // frames behind the first firing lane are ignored
+      const int L = __ffsll((long long)mf) - 1;
+      rule = __shfl(fired, L, 64);
+      c = ep_after_lane(c, mb, ms, L);
+      break;
+    }
+    c = ep_after_lane(c, mb, ms, n_it - 1);
+  }
+  if (lane == 0) {
+    st[E_FRAMES] = c.frames;
+    st[E_TRAIL] = c.trail;
+    st[E_DECODED] = c.decoded;
+    st[E_FIRST] = c.first;
+    st[E_LAST] = c.last;
+    if (rule) {
+      st[E_RULE] = rule;
+      st[E_FIRED] = c.frames - 1;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void ctc_endpoint_read_kernel(const int32_t* __restrict__ state, int32_t* __restrict__ info, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) info[i] = state[i];
+}
+
 }  // namespace
 
 size_t ctc_beam_state_size(const m3_ctc_beam_desc* d) {
@@ -1009,6 +1125,52 @@ int launch_ctc_greedy_stream_tokens(const m3_ctc_greedy_desc* d, const void* sta
   M3_REQUIRE(n_tokens && (tokens || d->max_frames == 0), "ctc_greedy_stream_tokens: null pointer");
   hipLaunchKernelGGL(ctc_greedy_stream_tokens_kernel, dim3(d->B), dim3(64), 0, stream, (const int32_t*)state, stride,
                      d->max_frames, tokens, n_tokens);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+size_t ctc_endpoint_state_size(const m3_ctc_endpoint_desc* d) {
+  if (check_endpoint_desc(d)) return 0;
+  return (size_t)d->B * E_WORDS * 4;
+}
+
+int launch_ctc_endpoint_reset(const m3_ctc_endpoint_desc* d, void* state, size_t bytes, hipStream_t stream, const int32_t* slots,
+                              int n) {
+  if (int rc = check_endpoint_desc(d)) return rc;
+  M3_REQUIRE(n >= 0 && (slots != nullptr || n == 0), "ctc_endpoint_reset: bad slot list");
+  if (slots != nullptr && n == 0) return 0;
+  M3_REQUIRE(bytes >= (size_t)d->B * E_WORDS * 4, "ctc_endpoint_reset: state %zu bytes < required %zu", bytes,
+             (size_t)d->B * E_WORDS * 4);
+  if (d->B == 0) return 0;
+  M3_REQUIRE(state != nullptr, "ctc_endpoint_reset: null state");
+  hipLaunchKernelGGL(ctc_endpoint_reset_kernel, dim3(((slots ? n : d->B) + 255) / 256), dim3(256), 0, stream, (int32_t*)state,
+                     d->B, slots, n);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_ctc_endpoint_advance(const m3_ctc_endpoint_desc* d, void* state, size_t bytes, const float* top_logp,
+                                const int32_t* top_idx, int T_chunk, int k, const int32_t* n_frames, hipStream_t stream) {
+  if (int rc = check_endpoint_desc(d)) return rc;
+  M3_REQUIRE(bytes >= (size_t)d->B * E_WORDS * 4, "ctc_endpoint_advance: state %zu bytes < required %zu", bytes,
+             (size_t)d->B * E_WORDS * 4);
+  M3_REQUIRE(T_chunk >= 0 && k >= 1, "ctc_endpoint_advance: bad shape T_chunk=%d k=%d", T_chunk, k);
+  if (d->B == 0 || T_chunk == 0) return 0;
+  M3_REQUIRE(state && top_logp && top_idx && n_frames, "ctc_endpoint_advance: null pointer");
+  hipLaunchKernelGGL(ctc_endpoint_advance_kernel, dim3(d->B), dim3(64), 0, stream, *d, (int32_t*)state, top_logp, top_idx, T_chunk,
+                     k, n_frames);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_ctc_endpoint_read(const m3_ctc_endpoint_desc* d, const void* state, size_t bytes, int32_t* info, hipStream_t stream) {
+  if (int rc = check_endpoint_desc(d)) return rc;
+  M3_REQUIRE(bytes >= (size_t)d->B * E_WORDS * 4, "ctc_endpoint_read: state %zu bytes < required %zu", bytes,
+             (size_t)d->B * E_WORDS * 4);
+  if (d->B == 0) return 0;
+  M3_REQUIRE(state && info, "ctc_endpoint_read: null pointer");
+  const int n = d->B * E_WORDS;
+  hipLaunchKernelGGL(ctc_endpoint_read_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const int32_t*)state, info, n);
   M3_LAUNCH_CHECK();
   return 0;
 }

@@ -529,6 +529,13 @@ int launch_ctc_greedy_stream_advance(const m3_ctc_greedy_desc* d, void* state, s
                                      int V, const int32_t* n_frames, int32_t* frame_ids, hipStream_t stream);
 int launch_ctc_greedy_stream_tokens(const m3_ctc_greedy_desc* d, const void* state, size_t bytes, int32_t* tokens,
                                     int32_t* n_tokens, hipStream_t stream);
+// endpoint detection next to the two searches (ctc_beam.hip)
+size_t ctc_endpoint_state_size(const m3_ctc_endpoint_desc* d);
+int launch_ctc_endpoint_reset(const m3_ctc_endpoint_desc* d, void* state, size_t bytes, hipStream_t stream,
+                              const int32_t* slots = nullptr, int n = 0);
+int launch_ctc_endpoint_advance(const m3_ctc_endpoint_desc* d, void* state, size_t bytes, const float* top_logp,
+                                const int32_t* top_idx, int T_chunk, int k, const int32_t* n_frames, hipStream_t stream);
+int launch_ctc_endpoint_read(const m3_ctc_endpoint_desc* d, const void* state, size_t bytes, int32_t* info, hipStream_t stream);
 int launch_cat_split_cache(const void* in_cache, const void* input, int B, int cache_dim, int input_dim, void* output,
                            void* out_cache, hipStream_t stream);
 int launch_att_stream_softmax(const float* scores, const int32_t* decode_frame_num, const int32_t* mask_idx, int B, int N,

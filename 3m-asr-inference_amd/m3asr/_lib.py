@@ -61,6 +61,15 @@ class CtcGreedyDesc(C.Structure):  # m3_ctc_greedy_desc
     _fields_ = [("B", C.c_int32), ("max_frames", C.c_int32), ("blank", C.c_int32)]
 
 
+class CtcEndpointRule(C.Structure):  # m3_ctc_endpoint_rule
+    _fields_ = [("must_decoded", C.c_int32), ("min_trailing", C.c_int32), ("min_length", C.c_int32)]
+
+
+class CtcEndpointDesc(C.Structure):  # m3_ctc_endpoint_desc
+    _fields_ = [("B", C.c_int32), ("blank", C.c_int32), ("n_rules", C.c_int32), ("log_blank_threshold", C.c_float),
+                ("rule", CtcEndpointRule * 4)]
+
+
 class WeightEntry(C.Structure):  # m3_weight_entry
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64), ("dtype", C.c_int32)]
 
@@ -169,6 +178,11 @@ SIGNATURES = {
     "m3_ctc_greedy_stream_reset_slots": (_i, [_P(CtcGreedyDesc), _vp, _sz, _vp, _i, _vp]),
     "m3_ctc_greedy_stream_advance": (_i, [_P(CtcGreedyDesc), _vp, _sz, _vp, _i, _i, _vp, _vp, _vp]),
     "m3_ctc_greedy_stream_tokens": (_i, [_P(CtcGreedyDesc), _vp, _sz, _vp, _vp, _vp]),
+    "m3_ctc_endpoint_state_size": (_sz, [_P(CtcEndpointDesc)]),
+    "m3_ctc_endpoint_reset": (_i, [_P(CtcEndpointDesc), _vp, _sz, _vp]),
+    "m3_ctc_endpoint_reset_slots": (_i, [_P(CtcEndpointDesc), _vp, _sz, _vp, _i, _vp]),
+    "m3_ctc_endpoint_advance": (_i, [_P(CtcEndpointDesc), _vp, _sz, _vp, _vp, _i, _i, _vp, _vp]),
+    "m3_ctc_endpoint_read": (_i, [_P(CtcEndpointDesc), _vp, _sz, _vp, _vp]),
     "m3_cat_split_cache": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "m3_att_stream_softmax": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
     "m3_rel_positional_encoding": (_i, [_vp, _vp, _i, _vp, _i, _f, _i, _i, _i, _vp, _vp, _vp, _vp]),

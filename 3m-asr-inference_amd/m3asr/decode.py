@@ -9,6 +9,8 @@ and return types), running on the device through libm3asr_hip.so:
   batched beam  B utterances in one device search (m3_ctc_topk + m3_ctc_beam_advance + m3_ctc_beam_nbest): CtcBeamSearch,
                 CtcDecoder.batch_prefix_beam_search; resumable chunk by chunk, which StreamingCtcDecoder uses on top of the
                 chunk-by-chunk engine (with the streaming greedy search, m3_ctc_greedy_stream_*).
+  endpoints     when an utterance of a live stream is over (m3_ctc_endpoint_*): EndpointConfig, and
+                StreamingCtcDecoder(endpoint=...).endpoints(); m3asr.serve.StreamPool(segment=True) cuts sessions there.
 
 Chunked decoding (decoding_chunk_size > 0) is accepted when the engine was built for exactly that chunk mask
 (cfg.static_chunk_size == decoding_chunk_size, same num_decoding_left_chunks): its ordinary forward is then the reference's
@@ -16,8 +18,11 @@ chunk-masked forward (encoder.py:100-140).
 
 There is no CPU fallback: without the HIP library every call raises.
 """
+import collections
+import math
 from typing import List, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib, ops
@@ -32,6 +37,47 @@ def _same_device(a, b):
         return a.index == b.index
     cur = torch.cuda.current_device() if a.index is None or b.index is None else 0
     return (cur if a.index is None else a.index) == (cur if b.index is None else b.index)
+
+
+class EndpointConfig:
+    """The endpoint rule of a streaming decoder (include/m3asr.h, m3_ctc_endpoint_*).
+
+    A frame whose argmax is the blank with probability above `blank_threshold` is a blank frame; any other frame ends the
+    run of trailing blanks, and a frame whose argmax is a token means something has been decoded.  rules: up to four
+    (must_decoded, min trailing blank ms, min utterance ms); after every frame the first rule that holds ends the utterance.
+    The defaults: 5 s of silence before anything was said, 1 s of silence after something was said, or 20 s in all.
+    Milliseconds become frames of `frame_ms` by ceil(ms / frame_ms).  blank_threshold lies in [0.5, 1): a blank above 0.5
+    is the frame's argmax, so the detector needs nothing but the top-1 of the search's top-k."""
+
+    def __init__(self, blank_threshold=0.8, rules=((False, 5000, 0), (True, 1000, 0), (False, 0, 20000)), frame_ms=40):
+        self.blank_threshold, self.frame_ms = float(blank_threshold), int(frame_ms)
+        if not 0.5 <= self.blank_threshold < 1.0:
+            raise ValueError("EndpointConfig: blank_threshold = %r outside [0.5, 1)" % (blank_threshold,))
+        if self.frame_ms <= 0:
+            raise ValueError("EndpointConfig: frame_ms = %r" % (frame_ms,))
+        self.rules = tuple((bool(m), t, n) for m, t, n in rules)
+        if not 1 <= len(self.rules) <= 4:
+            raise ValueError("EndpointConfig: %d rules, need 1 to 4" % len(self.rules))
+        if any(t < 0 or n < 0 for _, t, n in self.rules):
+            raise ValueError("EndpointConfig: negative time in %r" % (self.rules,))
+        self.log_blank_threshold = float(np.float32(math.log(self.blank_threshold)))    # the float32 the kernel compares with
+        self.frame_rules = tuple((m, self.frames(t), self.frames(n)) for m, t, n in self.rules)
+
+    def frames(self, ms):
+        """ceil(ms / frame_ms)"""
+        return int(-(-ms // self.frame_ms)) if isinstance(ms, int) else int(math.ceil(ms / self.frame_ms))
+
+    def length_bound(self):
+        """Frames after which a rule fires whatever the audio holds (a rule without must_decoded and without trailing
+        blanks), or None when no rule bounds an utterance's length."""
+        return min((n for m, t, n in self.frame_rules if not m and t == 0), default=None)
+
+    def desc(self, B, blank=0):
+        return ops.ctc_endpoint_desc(B, blank, self.log_blank_threshold, self.frame_rules)
+
+
+# what StreamingCtcDecoder.endpoints() returns per stream; rule == 0: no endpoint yet (frame is then -1)
+EndpointInfo = collections.namedtuple("EndpointInfo", "rule frame frames trailing_blank decoded first_speech last_speech")
 
 
 class CtcBeamSearch:
@@ -75,6 +121,7 @@ class CtcBeamSearch:
         else:
             n = ops.ctc_beam_state_size(self.desc)
         self.state = torch.empty(max(n, 1), dtype=torch.uint8, device=self.device)
+        self.last_topk = None                                 # (top_logp, top_idx) of the last advance, for the endpointer
         self.reset()
 
     @property
@@ -153,7 +200,7 @@ class CtcBeamSearch:
             if Tc == 0:
                 return
             nf = n_frames.reshape(-1).to(self.device, torch.int32, non_blocking=True)
-            top_logp, top_idx = ops.ctc_topk(logits.contiguous(), self.desc.k)
+            top_logp, top_idx = self.last_topk = ops.ctc_topk(logits.contiguous(), self.desc.k)
             if self.context is None and self.lm is None:
                 ops.ctc_beam_advance(self.desc, self.state, top_logp, top_idx, nf)
                 return
@@ -305,14 +352,20 @@ class StreamingCtcDecoder:
     the utterance lengths passes them as n_out (decode() does).
 
     Over a slot-mode encoder (engine.streaming(..., independent=True)) the streams are independent here too: a slot that is
-    idle in a step consumes no frame in either search, and reset / partial / finish take `slots=[...]`."""
+    idle in a step consumes no frame in either search, and reset / partial / finish take `slots=[...]`.
 
-    def __init__(self, streaming_encoder, beam, blank=0, context=None, lm=None, lm_weight=0.5, length_bonus=0.0, lm_eos=True):
+    With endpoint=EndpointConfig(...) every step() also advances the endpoint detector on the top-k the beam search just
+    computed (one more small launch on the engine's stream, no second log-softmax, no sync); endpoints() tells which streams'
+    utterances are over."""
+
+    def __init__(self, streaming_encoder, beam, blank=0, context=None, lm=None, lm_weight=0.5, length_bonus=0.0, lm_eos=True,
+                 endpoint=None):
         """context: a m3asr.context.ContextSet on the engine's device (hotword biasing of the beam search; the greedy
         search is not biased); reset(graph_ids=) chooses each stream's graph, -1 = unbiased.
         lm: a m3asr.lm.NgramLm on the engine's device (shallow fusion in the beam search, as CtcBeamSearch(lm=); the walk
         runs inside the advance kernel, so a chunk is still one graph replay and no host round trip); reset(lm_on=) switches
-        it per stream."""
+        it per stream.
+        endpoint: an EndpointConfig; None = no endpoint detection (nothing is allocated for it, endpoints() raises)."""
         self.st = streaming_encoder
         self.context = context
         self.lm = lm
@@ -325,10 +378,17 @@ class StreamingCtcDecoder:
         self.gstate = torch.empty(max(ops.ctc_greedy_stream_state_size(self.gdesc), 1), dtype=torch.uint8, device=e.device)
         self.frame_ids = torch.empty(B, self.c, dtype=torch.int32, device=e.device)
         self.n_out = torch.zeros(B, dtype=torch.int32, device=e.device)
+        self.endpoint = endpoint
+        if endpoint is not None:
+            self.edesc = endpoint.desc(B, blank)
+            self.estate = torch.empty(max(ops.ctc_endpoint_state_size(self.edesc), 1), dtype=torch.uint8, device=e.device)
+            self.einfo = torch.empty(B, 8, dtype=torch.int32, device=e.device)
+            self.einfo_host = torch.empty(B, 8, dtype=torch.int32, pin_memory=True)
         self.reset()
 
     def reset(self, slots=None, graph_ids=None, lm_on=None):
-        """Restart all streams, or (slot-mode encoder) the listed slots: encoder state, beam search and greedy search.
+        """Restart all streams, or (slot-mode encoder) the listed slots: encoder state, beam search, greedy search and
+        endpoint state.
         graph_ids (decoder with a context): the graph each restarted stream takes, one per slot; a stream restarted without
         one keeps the graph it had.  lm_on (decoder with an LM): whether each restarted stream runs with the LM."""
         kw = {} if lm_on is None else {"lm_on": lm_on}
@@ -341,6 +401,8 @@ class StreamingCtcDecoder:
             if slots is None:
                 self.beam.reset(e.stream, graph_ids=graph_ids, **kw)
                 ops.ctc_greedy_stream_reset(self.gdesc, self.gstate)
+                if self.endpoint is not None:
+                    ops.ctc_endpoint_reset(self.edesc, self.estate)
             elif len(slots) > 0:
                 lst = torch.tensor([int(b) for b in slots], dtype=torch.int32).to(e.device)
                 if self.context is None and self.lm is None:
@@ -348,6 +410,8 @@ class StreamingCtcDecoder:
                 else:
                     self.beam.reset(e.stream, slots=[int(b) for b in slots], graph_ids=graph_ids, **kw)
                 ops.ctc_greedy_stream_reset(self.gdesc, self.gstate, lst)
+                if self.endpoint is not None:
+                    ops.ctc_endpoint_reset(self.edesc, self.estate, lst)
 
     def frames_of(self, valid):
         """Output frames of this chunk that count, from the real feature frames in its window."""
@@ -365,7 +429,25 @@ class StreamingCtcDecoder:
             self.n_out.copy_(torch.as_tensor(n_out).reshape(-1).to(torch.int32), non_blocking=True)
             self.beam.advance(logits, self.n_out, e.stream)
             ops.ctc_greedy_stream_advance(self.gdesc, self.gstate, logits, self.n_out, self.frame_ids)
+            if self.endpoint is not None:
+                top_logp, top_idx = self.beam.last_topk
+                ops.ctc_endpoint_advance(self.edesc, self.estate, top_logp, top_idx, self.n_out)
         return logits
+
+    def endpoints(self, slots=None):
+        """One EndpointInfo per stream (slots: only the listed streams, in that order) after the chunks so far; rule != 0:
+        that rule ended the stream's utterance at output frame `frame` (counted from the stream's last reset), and the
+        detector stands still until the stream is reset.  Waits for the engine's stream."""
+        if self.endpoint is None:
+            raise _lib.M3Error("StreamingCtcDecoder.endpoints: the decoder was built without an endpoint config")
+        e = self.st.eng
+        with torch.cuda.stream(e.stream):
+            ops.ctc_endpoint_read(self.edesc, self.estate, self.einfo)
+            self.einfo_host.copy_(self.einfo, non_blocking=True)
+        e.stream.synchronize()
+        rows = self.einfo_host.tolist()
+        return [EndpointInfo(r[5], r[6], r[0], r[1], bool(r[2]), r[3], r[4])
+                for r in (rows[int(b)] for b in (range(len(rows)) if slots is None else slots))]
 
     def greedy(self, slots=None):
         """Greedy hypotheses of the frames so far: [[token, ...]] per stream (slots: only the listed streams)."""

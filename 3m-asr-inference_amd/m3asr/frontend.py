@@ -159,6 +159,15 @@ class AudioWindowBuffer:
     def end(self):
         self.ended = True
 
+    def rebase(self):
+        """Start over at the next window: from here on the buffer behaves like a fresh one that was pushed every sample
+        from sample 160 * 4 c * chunks on (serve.WindowBuffer.rebase in samples).  `ended` stays."""
+        start = self.hop * self.chunks
+        self.buf = self.buf[min(max(start - self.base, 0), self.buf.shape[0]):]
+        self.total = max(self.total - start, 0)
+        self.base = 0
+        self.chunks = 0
+
     def ready(self):
         """Real FRAMES of the next window if it can run now, else 0 (the rule of serve.next_window_valid on frame counts)."""
         return next_window_valid(num_frames(self.total), self.chunks, self.c, self.ended)

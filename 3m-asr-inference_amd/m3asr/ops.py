@@ -733,6 +733,58 @@ def ctc_greedy_stream_tokens(desc, state):
     return tokens, n
 
 
+# ---- endpoint detection (m3asr.decode.EndpointConfig builds the descriptor)
+def ctc_endpoint_desc(B, blank, log_blank_threshold, rules):
+    """m3_ctc_endpoint_desc for B streams; rules: up to four (must_decoded, min_trailing frames, min_length frames);
+    log_blank_threshold: a float32 in [log 0.5, 0).  Raises M3Error on a descriptor the library rejects."""
+    if len(rules) > 4:
+        raise _lib.M3Error("ctc_endpoint_desc: %d rules, at most 4" % len(rules))
+    d = _lib.CtcEndpointDesc()
+    d.B, d.blank, d.n_rules, d.log_blank_threshold = int(B), int(blank), len(rules), float(log_blank_threshold)
+    for r, (must, trail, length) in enumerate(rules):
+        d.rule[r].must_decoded, d.rule[r].min_trailing, d.rule[r].min_length = int(bool(must)), int(trail), int(length)
+    one = _lib.CtcEndpointDesc.from_buffer_copy(d)                     # B = 0 is a valid (empty) size
+    one.B = 1
+    if _lib.load().m3_ctc_endpoint_state_size(C.byref(one)) == 0:
+        raise _lib.M3Error("m3_ctc_endpoint_state_size failed: " + _lib.last_error())
+    return d
+
+
+def ctc_endpoint_state_size(desc):
+    n = _lib.load().m3_ctc_endpoint_state_size(C.byref(desc))
+    if n == 0 and desc.B > 0:
+        raise _lib.M3Error("m3_ctc_endpoint_state_size failed: " + _lib.last_error())
+    return n
+
+
+def ctc_endpoint_reset(desc, state, slots=None):
+    """slots: None = every stream; else an int32 device tensor listing the streams to restart."""
+    if slots is not None:
+        check(_lib.load().m3_ctc_endpoint_reset_slots(C.byref(desc), _p(state), state.numel() * state.element_size(), _i32(slots),
+                                                      slots.numel(), _stream()), "m3_ctc_endpoint_reset_slots")
+        return
+    check(_lib.load().m3_ctc_endpoint_reset(C.byref(desc), _p(state), state.numel() * state.element_size(), _stream()),
+          "m3_ctc_endpoint_reset")
+
+
+def ctc_endpoint_advance(desc, state, top_logp, top_idx, n_frames):
+    """top_logp / top_idx (B, T_chunk, k) from ctc_topk (any k >= 1), n_frames (B,) int32 on the device: enqueue, no host sync."""
+    B, Tc, k = top_logp.shape
+    assert B == desc.B and tuple(top_idx.shape) == (B, Tc, k) and n_frames.numel() == B
+    check(_lib.load().m3_ctc_endpoint_advance(C.byref(desc), _p(state), state.numel() * state.element_size(), _f32(top_logp),
+                                              _i32(top_idx), Tc, k, _i32(n_frames), _stream()), "m3_ctc_endpoint_advance")
+
+
+def ctc_endpoint_read(desc, state, info=None):
+    """-> info (B, 8) int32 on the device: frames, trailing_blank, decoded, first_speech, last_speech, fired_rule, fired_frame, 0."""
+    if info is None:
+        info = torch.empty(desc.B, 8, dtype=torch.int32, device=state.device)
+    assert tuple(info.shape) == (desc.B, 8)
+    check(_lib.load().m3_ctc_endpoint_read(C.byref(desc), _p(state), state.numel() * state.element_size(), _i32(info), _stream()),
+          "m3_ctc_endpoint_read")
+    return info
+
+
 # ---------------------------------------------------------------------------------------- streaming operators
 def cat_split_cache(in_cache, inp):
     """CatSplitCache plugin: (output (B, cache+input), out_cache (B, cache)); f32 or i32 rows."""

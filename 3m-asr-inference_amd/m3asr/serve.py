@@ -18,13 +18,25 @@ float32 in the int16 range).  step() gathers the live slots' sample windows into
 runs the log-Mel front end (m3asr.frontend.Fbank, one launch on the engine stream) straight into the encoder's window
 buffer; the chunk itself is the same graph replay as in feature mode.
 
+Segmenting, `StreamPool(decoder, segment=True)` over a decoder with an endpoint config
+(StreamingCtcDecoder(..., endpoint=EndpointConfig())): after every step() the pool asks the device-side endpoint detector
+which live sessions' utterances are over, files each one's n-best as a `Segment` (`pool.segments(sid)`) and restarts the
+slot, so a session may stay open for any length of time inside a state sized for `max_frames`.
+
 The window rule is the one StreamingEncoder.decode applies to whole utterances (window n of a stream starts at its input
 frame 4 c n, holds 4 c + 3 frames, overlaps the next by 3; fewer than 7 real frames count as none).  It lives in
 `next_window_valid` / `WindowBuffer`, host-only code.
 """
+import collections
+
 import torch
 
 from . import _lib
+
+# One finished utterance of a segmenting pool's session.  rule: the endpoint rule that ended it (1-based); start_ms / end_ms:
+# where its first and behind its last non-blank frame lie in the SESSION (the whole segment when no frame's argmax was a
+# token); nbest: [(prefix, score)] best first, as close() returns; end_frame: the session's output frame at which the rule fired.
+Segment = collections.namedtuple("Segment", "rule start_ms end_ms nbest end_frame")
 
 
 def next_window_valid(buffered, chunks_done, chunk, ended):
@@ -64,6 +76,15 @@ class WindowBuffer:
     def end(self):
         self.ended = True
 
+    def rebase(self):
+        """Start over at the next window: from here on the buffer behaves like a fresh one that was pushed every frame from
+        input frame 4 c chunks on (the frames that window would read).  `ended` stays."""
+        start = 4 * self.c * self.chunks
+        self.buf = self.buf[min(max(start - self.base, 0), self.buf.shape[0]):]
+        self.total = max(self.total - start, 0)
+        self.base = 0
+        self.chunks = 0
+
     def ready(self):
         """Real frames of the next window if it can run now, else 0."""
         return next_window_valid(self.total, self.chunks, self.c, self.ended)
@@ -96,9 +117,21 @@ class StreamPool:
     (B,))`, `reset(slots=[...])`, `partial(slots=[...])`, `finish(slots=[...])`; B, chunk and input_dim are read from
     `decoder.st` unless given.  audio=True: the sessions are fed samples (push_audio) and step() featurises them on the device;
     fbank: the front end, `fbank(pcm (B, n) int16, n_samples (B,), out=, out_len=, stream=)` (default: an
-    m3asr.frontend.Fbank for input_dim on the engine's device)."""
+    m3asr.frontend.Fbank for input_dim on the engine's device).
 
-    def __init__(self, decoder, B=None, chunk=None, input_dim=None, audio=False, fbank=None):
+    segment=True: continuous decoding.  The decoder needs an endpoint config (`decoder.endpoint`, an
+    m3asr.decode.EndpointConfig, and `decoder.endpoints(slots=[...])`).  After the engine call of a step() the pool reads the
+    live slots' endpoint state -- the one host sync of a step.  For every slot whose rule fired it takes finish(slots=[b]),
+    appends a Segment to the session unless the best hypothesis is empty, moves the session's offset on by the chunks the
+    slot ran, restarts the slot (it keeps its hotword graph and LM setting) and rebases the session's buffer.  The session
+    keeps its sid and goes on.  BOUNDARY: a rule fires at a frame, a slot moves by chunks: the frames of the firing chunk
+    behind the endpoint stay with the finished segment (its n-best covers them), and the next segment starts at the next
+    window -- it sees the three frames of overlap again but no encoder history from before.  segments(sid) hands out the
+    finished segments, close(sid) the n-best of the open one, offset_ms(sid) where the open one starts.  With a rule that
+    bounds an utterance's length (the default third rule) no slot reaches max_frames; that needs min_length + c <= max_frames
+    (max_frames is read from `decoder.st` unless given)."""
+
+    def __init__(self, decoder, B=None, chunk=None, input_dim=None, audio=False, fbank=None, segment=False, max_frames=None):
         self.dec = decoder
         st = getattr(decoder, "st", None)
         if st is not None and not getattr(st, "independent", False):
@@ -112,6 +145,21 @@ class StreamPool:
         self.next_sid = 0
         self.win = torch.zeros(self.B, self.window, self.idim)
         self.steps = 0
+        self.segment = bool(segment)
+        if self.segment:
+            ep = getattr(decoder, "endpoint", None)
+            if ep is None or not hasattr(decoder, "endpoints"):
+                raise _lib.M3Error("StreamPool(segment=True) needs a decoder with an endpoint config: "
+                                   "StreamingCtcDecoder(..., endpoint=EndpointConfig())")
+            self.frame_ms = int(ep.frame_ms)
+            if max_frames is None and st is not None:
+                max_frames = st.desc.max_frames
+            bound = ep.length_bound()
+            if max_frames is not None and bound is not None and bound + self.c > int(max_frames):
+                raise _lib.M3Error("StreamPool(segment=True): the length rule fires at %d frames, a slot may then stand at up "
+                                   "to %d + c = %d > max_frames = %d" % (bound, bound, bound + self.c, int(max_frames)))
+            self.offset = {}                     # sid -> output frames of the session before its open segment
+            self.finished = {}                   # sid -> [Segment] not handed out yet
         self.audio = bool(audio)
         if self.audio:
             self._init_audio(st, fbank)
@@ -166,6 +214,8 @@ class StreamPool:
                 self.next_sid += 1
                 self.slot_sid[b] = sid
                 self.streams[sid] = (b, self._new_audio_buffer() if self.audio else WindowBuffer(self.c, self.idim))
+                if self.segment:
+                    self.offset[sid], self.finished[sid] = 0, []
                 return sid
         raise _lib.M3Error("StreamPool.open: all %d slots are taken" % self.B)
 
@@ -202,7 +252,41 @@ class StreamPool:
         if live:
             self.dec.step(self.win, valid)
             self.steps += 1
+            if self.segment:
+                self._cut(live)
         return live
+
+    def _cut(self, live):
+        """segment=True, after the engine call: end the utterance of every live session whose endpoint rule fired."""
+        slots = [self.streams[sid][0] for sid in live]
+        for sid, b, info in zip(live, slots, self.dec.endpoints(slots=slots)):
+            if not info.rule:
+                continue
+            nbest = self.dec.finish(slots=[b])[0]
+            buf, off = self.streams[sid][1], self.offset[sid]
+            if nbest and len(nbest[0][0]) > 0:
+                first = info.first_speech if info.first_speech >= 0 else 0
+                last = info.last_speech if info.last_speech >= 0 else info.frame
+                self.finished[sid].append(Segment(info.rule, (off + first) * self.frame_ms, (off + last + 1) * self.frame_ms,
+                                                  nbest, off + info.frame))
+            self.offset[sid] = off + buf.chunks * self.c
+            self.dec.reset(slots=[b])
+            buf.rebase()
+
+    def segments(self, sid):
+        """The session's finished segments since the last call, oldest first (segment=True); the list is cleared."""
+        if not self.segment:
+            raise ValueError("StreamPool.segments: this pool does not segment, build it with segment=True")
+        self._get(sid)
+        out, self.finished[sid] = self.finished[sid], []
+        return out
+
+    def offset_ms(self, sid):
+        """Where in the session its open segment starts, in ms (segment=True)."""
+        if not self.segment:
+            raise ValueError("StreamPool.offset_ms: this pool does not segment, build it with segment=True")
+        self._get(sid)
+        return self.offset[sid] * self.frame_ms
 
     def _step_audio(self):
         """step() of a pool fed samples: one small int16 upload, one front-end launch into the encoder's window buffer, then
@@ -232,6 +316,8 @@ class StreamPool:
         self.fbank(self.pcm_dev, self.n_real_dev, out=self.feat, out_len=self.feat_len_dev, stream=self.stream)
         self.dec.step(self.feat, valid)
         self.steps += 1
+        if self.segment:
+            self._cut(live)
         return live
 
     def partial(self, sid):
@@ -241,9 +327,12 @@ class StreamPool:
         return best[0], greedy[0]
 
     def close(self, sid):
-        """n-best [(prefix, score)] of what the stream has decoded; the slot is free again."""
+        """n-best [(prefix, score)] of what the stream has decoded (segment=True: of its open segment; read segments(sid)
+        first, the finished ones go with the session); the slot is free again."""
         b = self.slot_of(sid)
         nbest = self.dec.finish(slots=[b])[0]
         del self.streams[sid]
+        if self.segment:
+            del self.offset[sid], self.finished[sid]
         self.slot_sid[b] = None
         return nbest

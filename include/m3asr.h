@@ -506,6 +506,41 @@ int m3_ctc_greedy_stream_advance(const m3_ctc_greedy_desc* desc, void* state, si
                                  int T_chunk, int V, const int32_t* n_frames, int32_t* frame_ids, m3_stream stream);
 int m3_ctc_greedy_stream_tokens(const m3_ctc_greedy_desc* desc, const void* state, size_t state_bytes, int32_t* tokens,
                                 int32_t* n_tokens, m3_stream stream);
+/* Endpoint detection next to the two searches (csrc/ctc_beam.hip): when is an utterance over.  Frames are
+ * encoder output frames.  Per stream the state is (frames, trailing_blank, decoded, first_speech, last_speech, fired_rule,
+ * fired_frame), after a reset (0, 0, 0, -1, -1, 0, -1).  Each real frame, in order, is judged by entry 0 of m3_ctc_topk's
+ * output for it (the argmax, the greedy search's winner):  frames += 1;  the frame is BLANK iff top_idx0 == blank and
+ * top_logp0 > log_blank_threshold (strict): trailing_blank += 1, any other frame sets trailing_blank = 0;  top_idx0 != blank
+ * sets decoded = 1, last_speech = frames - 1 and first_speech if it was -1.  Then rule r = 1 .. n_rules fires iff
+ * (decoded || !must_decoded) && trailing_blank >= min_trailing && frames >= min_length; the first that fires latches
+ * fired_rule = r, fired_frame = frames - 1, and from then on no frame changes anything until the stream is reset.
+ * Limits: 1 <= n_rules <= 4, counts >= 0, must_decoded 0 or 1, log_blank_threshold in [log 0.5, 0) as a float32 (a blank above
+ * p = 0.5 is necessarily entry 0, for any k >= 1).  The state is eight words per stream (m3_ctc_endpoint_state_size bytes,
+ * device) and there is no max_frames: this is the one piece of a session that never overflows.
+ * m3_ctc_endpoint_advance: top_logp / top_idx [B][T_chunk][k], n_frames [B] (device) real rows per stream, clamped to
+ *   [0, T_chunk]; rows past it are padding and are not read, a stream with 0 frames keeps its state word for word.  One wave
+ *   per stream, no host sync.
+ * m3_ctc_endpoint_read: info [B][8] (device int32) = the seven values above in that order and one spare word (0). */
+typedef struct m3_ctc_endpoint_rule {
+  int32_t must_decoded;
+  int32_t min_trailing;
+  int32_t min_length;
+} m3_ctc_endpoint_rule;
+typedef struct m3_ctc_endpoint_desc {
+  int32_t B;
+  int32_t blank;
+  int32_t n_rules;
+  float log_blank_threshold;
+  m3_ctc_endpoint_rule rule[4];
+} m3_ctc_endpoint_desc;
+size_t m3_ctc_endpoint_state_size(const m3_ctc_endpoint_desc* desc);
+int m3_ctc_endpoint_reset(const m3_ctc_endpoint_desc* desc, void* state, size_t state_bytes, m3_stream stream);
+int m3_ctc_endpoint_reset_slots(const m3_ctc_endpoint_desc* desc, void* state, size_t state_bytes, const int32_t* slots, int n,
+                                m3_stream stream); /* only the n streams listed in `slots` (device int32[n]) */
+int m3_ctc_endpoint_advance(const m3_ctc_endpoint_desc* desc, void* state, size_t state_bytes, const float* top_logp,
+                            const int32_t* top_idx, int T_chunk, int k, const int32_t* n_frames, m3_stream stream);
+int m3_ctc_endpoint_read(const m3_ctc_endpoint_desc* desc, const void* state, size_t state_bytes, int32_t* info,
+                         m3_stream stream);
 
 /* Streaming operators of the reference's plugin library (built there but not registered, trt_plugin_plus.cpp:155-156).
  * CatSplitCachePluginDynamic (cat_split_cache_kernel.cu:30-107), 4-byte elements: output [B][cache_dim+input_dim] =

@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""Continuous decoding of a wav file as a live service would see it: the samples go into StreamPool(audio=True, segment=True)
+in 100 ms pieces, the device-side endpoint detector cuts the session into utterances, and every finished segment is printed
+as soon as the step that ended it returns:
+
+    python tools/transcribe_stream.py -p encoder.plan -w speech.wav [--hotwords words.txt] [--lm lm.arpa] [--beam 10]
+                                      [--blank-threshold 0.8] [--rule must_decoded,trailing_ms,length_ms ...]
+
+    <start ms>-<end ms> rule <r>: <token ids of the best hypothesis>
+
+The plan must be a streaming one (static_chunk_size > 0, causal conv modules).  speech.wav is 16 kHz mono 16-bit PCM.  The
+last line (rule 0) is what was still open when the file ended.  --synthetic N pushes N seconds of a generated signal instead
+of a file (no plan either: a small random streaming model), to see the mechanics on a machine without a model."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "3m-asr-inference_amd"))
+import numpy as np
+import torch
+
+from m3asr.decode import EndpointConfig, StreamingCtcDecoder
+from m3asr.serve import StreamPool
+
+PIECE = 1600          # 100 ms of samples
+
+
+def read_wav(path):
+    import wave
+    with wave.open(path, "rb") as w:
+        if (w.getframerate(), w.getnchannels(), w.getsampwidth()) != (16000, 1, 2):
+            raise SystemExit("%s: need 16 kHz mono 16-bit PCM, got %d Hz, %d channel(s), %d-bit" % (
+                path, w.getframerate(), w.getnchannels(), 8 * w.getsampwidth()))
+        return np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").astype(np.int16)
+
+
+def load_engine(a):
+    if a.synthetic:
+        from m3asr.config import EncoderConfig
+        from m3asr.engine import Engine
+        from m3asr.weights import make_weights
+        cfg = EncoderConfig(num_blocks=2, embed_blocks=2, causal=True, embed_causal=True, static_chunk_size=16,
+                            num_decoding_left_chunks=2)
+        return Engine.from_state_dict(cfg, make_weights(cfg, seed=0), packed_rows=False)
+    import trt_helper
+    from trt_helper import trt
+    return trt_helper.InferHelper(a.plan_name, trt_helper.init_trt_plugin(trt.Logger.INFO, "libm3asr_hip.so")).engine
+
+
+def main(a):
+    eng = load_engine(a)
+    V, kw = eng.cfg.output_dim, {}
+    if a.hotwords:
+        from m3asr.context import ContextGraph, ContextSet, read_phrases
+        kw["context"] = ContextSet([ContextGraph(read_phrases(a.hotwords), V, score=a.hotword_score)], device=eng.device)
+    if a.lm:
+        from m3asr.lm import NgramLm
+        lm = NgramLm.load(a.lm) if a.lm.endswith(".npy") else NgramLm.from_arpa(a.lm, a.units, vocab_size=V)
+        kw.update(lm=lm.to(eng.device), lm_weight=a.lm_weight, length_bonus=a.length_bonus)
+    rules = [tuple(int(v) for v in r.split(",")) for r in a.rule] if a.rule else EndpointConfig().rules
+    ep = EndpointConfig(a.blank_threshold, rules)
+    bound = ep.length_bound()
+    max_frames = a.max_frames or (bound if bound is not None else 2000) + eng.cfg.static_chunk_size
+    dec = StreamingCtcDecoder(eng.streaming(1, max_frames, independent=True), beam=a.beam, endpoint=ep, **kw)
+    pool = StreamPool(dec, audio=True, segment=True)
+    if a.synthetic:
+        rng = np.random.default_rng(1)
+        pcm = np.clip(np.cumsum(rng.normal(0, 1, int(16000 * a.synthetic))) * 50 % 20000 - 10000, -32768, 32767).astype(np.int16)
+    else:
+        pcm = read_wav(a.wav_file)
+    sid = pool.open(context=0 if a.hotwords else None)
+
+    def show():
+        for s in pool.segments(sid):
+            print("%d-%d ms rule %d: %s" % (s.start_ms, s.end_ms, s.rule, " ".join(str(t) for t in s.nbest[0][0])), flush=True)
+
+    for pos in range(0, len(pcm), PIECE):
+        pool.push_audio(sid, torch.from_numpy(pcm[pos:pos + PIECE].copy()))
+        while pool.step():
+            show()
+    pool.end(sid)
+    while pool.step():
+        show()
+    start = pool.offset_ms(sid)
+    rest = pool.close(sid)
+    print("%d- ms rule 0: %s" % (start, " ".join(str(t) for t in rest[0][0]) if rest else ""))
+    print("%d engine steps, %.1f s of audio" % (pool.steps, len(pcm) / 16000.0))
+
+
+if __name__ == "__main__":
+    p = argparse.ArgumentParser(description="Continuous streaming decoding of a wav file with endpoint detection (MI355X)")
+    src = p.add_mutually_exclusive_group(required=True)
+    src.add_argument("-w", "--wav", dest="wav_file", help="A 16 kHz mono 16-bit wav file.")
+    src.add_argument("--synthetic", type=float, default=0.0, help="Seconds of a generated signal through a small random model.")
+    p.add_argument("-p", "--plan_name", help="The plan file of a streaming encoder (with -w).")
+    p.add_argument("--beam", type=int, default=10)
+    p.add_argument("--max-frames", type=int, default=0, help="Output frames of the streaming state (default: the length rule + c).")
+    p.add_argument("--blank-threshold", type=float, default=0.8)
+    p.add_argument("--rule", action="append", help="must_decoded (0/1),min trailing blank ms,min length ms; up to four, in order.")
+    p.add_argument("--hotwords", help="Phrase list: one phrase of space-separated token ids per line.")
+    p.add_argument("--hotword-score", type=float, default=3.0)
+    p.add_argument("--lm", help="n-gram LM: an ARPA file, or a compiled image (*.npy).")
+    p.add_argument("--units", help="`token id` per line: the ARPA's words as token ids.")
+    p.add_argument("--lm-weight", type=float, default=0.5)
+    p.add_argument("--length-bonus", type=float, default=0.0)
+    args = p.parse_args()
+    if args.wav_file and not args.plan_name:
+        p.error("-w needs -p")
+    main(args)
