@@ -227,6 +227,9 @@ SIGNATURES = {
     "m3_fbank_tables_init": (_i, [_i, _f, _f, _f, _vp, _vp]),
     "m3_fbank_num_frames": (_i, [_i]),
     "m3_fbank": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "m3_aed_embed": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "m3_aed_attention": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp]),
+    "m3_aed_score": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

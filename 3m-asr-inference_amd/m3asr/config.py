@@ -114,6 +114,52 @@ class EncoderConfig:
         )
 
 
+@dataclass
+class DecoderConfig:
+    """The attention decoder of a joint CTC/attention checkpoint (layer/att_decoder.py:165-180,323-339: TransformerDecoder,
+    or BiTransformerDecoder when r_num_blocks > 0).  sos = eos = vocab - 1 (model/ctc_aed.py:33-34).  It travels in a plan's
+    header as extra["decoder"]; EncoderConfig and plans without a decoder are untouched."""
+    vocab: int = 1434
+    dim: int = 512                 # encoder_output_size = the encoder's attention_dim
+    heads: int = 4
+    linear_units: int = 2048
+    num_blocks: int = 6
+    r_num_blocks: int = 0          # right-to-left decoder (BiTransformerDecoder); 0 = none
+    # the decoder builds PositionwiseFeedForward with its default activation, ReLU; "silu" for a checkpoint trained otherwise
+    activation: str = "relu"
+    max_len: int = 5000            # positional_encoding.py:31
+
+    def __post_init__(self):
+        if self.activation not in ("relu", "silu"):
+            raise ValueError("DecoderConfig: activation %r, need 'relu' or 'silu'" % (self.activation,))
+        if self.dim % self.heads:
+            raise ValueError("DecoderConfig: dim %d is no multiple of heads %d" % (self.dim, self.heads))
+
+    @property
+    def d_k(self):
+        return self.dim // self.heads
+
+    @property
+    def sos(self):
+        return self.vocab - 1
+
+    eos = sos
+
+    def to_dict(self):
+        return asdict(self)
+
+    @staticmethod
+    def from_dict(d):
+        return DecoderConfig(**d)
+
+    @staticmethod
+    def tiny(**kw):
+        """The decoder that goes with EncoderConfig.tiny()."""
+        base = dict(vocab=16, dim=32, heads=2, linear_units=64, num_blocks=2)
+        base.update(kw)
+        return DecoderConfig(**base)
+
+
 def subsampled_len(t):
     """T -> T' of Conv2dSubsampling4: two (l-3)//2+1 steps
     (mask_conv2d_sample_kernel.cu:34-35 with left_padding=2, stride=2)."""

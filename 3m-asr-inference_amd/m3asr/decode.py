@@ -11,6 +11,8 @@ and return types), running on the device through libm3asr_hip.so:
                 chunk-by-chunk engine (with the streaming greedy search, m3_ctc_greedy_stream_*).
   endpoints     when an utterance of a live stream is over (m3_ctc_endpoint_*): EndpointConfig, and
                 StreamingCtcDecoder(endpoint=...).endpoints(); m3asr.serve.StreamPool(segment=True) cuts sessions there.
+  rescoring     the reference's second pass (model/ctc_aed.py:160-252): CtcDecoder(engine, rescorer=...).attention_rescoring
+                runs the batched beam search, then the attention decoder over its n-best (m3asr.rescore).
 
 Chunked decoding (decoding_chunk_size > 0) is accepted when the engine was built for exactly that chunk mask
 (cfg.static_chunk_size == decoding_chunk_size, same num_decoding_left_chunks): its ordinary forward is then the reference's
@@ -262,9 +264,11 @@ class CtcBeamSearch:
 class CtcDecoder:
     """decoder = CtcDecoder(engine, blank_idx=0); engine: m3asr.engine.Engine (feat (B,T,idim), feat_len -> logits (B,T',V))."""
 
-    def __init__(self, engine, blank_idx: int = 0):
+    def __init__(self, engine, blank_idx: int = 0, rescorer=None):
+        """rescorer: a m3asr.rescore.AttentionRescorer on the engine's device, for attention_rescoring()."""
         self.engine = engine
         self.blank_idx = int(blank_idx)
+        self.rescorer = rescorer
 
     def forward(self, xs: torch.Tensor, xs_lens: torch.Tensor):
         """-> {"out_nosm": logits (B,T',V) on the device, "out_lens": (B,) int32 on the device} (encoder.py:140-147)."""
@@ -301,15 +305,17 @@ class CtcDecoder:
         return [tokens[b, :n].tolist() for b, n in enumerate(n_tokens)]
 
     def ctc_prefix_beam_search(self, xs: torch.Tensor, xs_lens: torch.Tensor, beam_size: int,
-                               decoding_chunk_size: int = -1, num_decoding_left_chunks: int = -1
+                               decoding_chunk_size: int = -1, num_decoding_left_chunks: int = -1, return_hidden: bool = False
                                ) -> Tuple[List[Tuple[Tuple[int, ...], float]], torch.Tensor]:
         """-> (n-best [(prefix, ctc score)], logits (1,T',V)); batch size 1 as in the reference (encoder.py:213-214).
-        The reference returns the encoder's hidden states for attention rescoring as the second item; the AED decoder
-        is out of scope here, the scores the search ran on are returned instead."""
+        return_hidden: the second item is the encoder's hidden states (1,T',D) (Engine.hidden()), which is what the reference
+        returns there "for attention rescoring"; by default it stays the scores the search ran on, as callers of this
+        method have come to expect."""
         assert xs.shape[0] == xs_lens.reshape(-1).shape[0] == 1, "prefix beam search supports batch size 1"
         self._full_context(decoding_chunk_size, num_decoding_left_chunks)
         res = self.forward(xs, xs_lens)
-        return self.prefix_beam_from_logits(res["out_nosm"], beam_size), res["out_nosm"]
+        hyps = self.prefix_beam_from_logits(res["out_nosm"], beam_size)
+        return hyps, (self.engine.hidden() if return_hidden else res["out_nosm"])
 
     def prefix_beam_from_logits(self, logits: torch.Tensor, beam_size: int):
         """logits (1,T',V) or (T',V) on the device; all T' frames are searched (max_len, encoder.py:222)."""
@@ -334,6 +340,31 @@ class CtcDecoder:
                                length_bonus=length_bonus, lm_eos=lm_eos)
         search.advance(logits, lens)
         return search.nbest()
+
+
+    def attention_rescoring(self, xs: torch.Tensor, xs_lens: torch.Tensor, beam_size: int, decoding_chunk_size: int = -1,
+                            num_decoding_left_chunks: int = -1, ctc_weight: float = 0.0, reverse_weight: float = 0.0,
+                            context=None, graph_ids=None, lm=None, lm_weight=0.5, length_bonus=0.0, lm_eos=True, detail=False):
+        """The reference's two-pass decoding (model/ctc_aed.py:160-252) for any batch size, all on the device: encoder
+        forward, batched CTC prefix beam search, then the attention decoder rescoring each utterance's n-best on the
+        encoder's hidden states (m3asr.rescore).  The prior that ctc_weight multiplies is the search's own ranking key: the
+        CTC score, plus the context bonus and lm_weight log P_LM + length_bonus |y| when the search has them.
+        -> the best token list per utterance; detail: AttentionRescorer.rescore's result, (best tokens, [(tokens, prior, att,
+        final)]) per utterance."""
+        if self.rescorer is None:
+            raise _lib.M3Error("CtcDecoder.attention_rescoring: built without a rescorer (CtcDecoder(engine, rescorer=AttentionRescorer(...)))")
+        self._full_context(decoding_chunk_size, num_decoding_left_chunks)
+        res = self.forward(xs, xs_lens)
+        logits, lens = res["out_nosm"], res["out_lens"]
+        search = CtcBeamSearch(int(logits.shape[0]), beam_size, int(logits.shape[1]), self.blank_idx, logits.device, context=context,
+                               lm=lm, lm_weight=lm_weight, length_bonus=length_bonus, lm_eos=lm_eos)
+        if graph_ids is not None:
+            search.reset(graph_ids=graph_ids)
+        search.advance(logits, lens)
+        # the residual stream as it is: after_norm rides in the prologue of the rescorer's K / V GEMM
+        out = self.rescorer.rescore(self.engine.hidden(normalized=False), lens, search, ctc_weight=ctc_weight,
+                                    reverse_weight=reverse_weight, raw_memory=True)
+        return out if detail else [list(best) for best, _ in out]
 
 
 class StreamingCtcDecoder:

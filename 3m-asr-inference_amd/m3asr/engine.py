@@ -69,8 +69,11 @@ class Engine:
         self.cfg = cfg
         self.device = torch.device(device)
         torch.cuda.set_device(self.device)
-        self.weights = {k: (v if v.is_cuda else v.to(self.device, non_blocking=False)).contiguous() for k, v in packed.items()}
-        names = list(self.weights)
+        # the attention decoder's entries (plan.pack_decoder) belong to m3asr.rescore.AttentionRescorer: the engine neither
+        # uploads nor names them; after_norm.* (the encoder's final LayerNorm as vectors) stays here for hidden()
+        self.weights = {k: (v if v.is_cuda else v.to(self.device, non_blocking=False)).contiguous() for k, v in packed.items()
+                        if not k.startswith("decoder.")}
+        names = [n for n in self.weights if not n.startswith("after_norm.")]
         table = (_lib.WeightEntry * len(names))()
         self._keep = [n.encode() for n in names]
         for i, n in enumerate(names):
@@ -265,6 +268,27 @@ class Engine:
             n = row0[b + 1] - row0[b]
             out[b, :n] = rows[row0[b]:row0[b + 1]]
         return out
+
+    def hidden(self, normalized=True):
+        """Hidden states of the last forward, (B, T', D) on the device: what the reference's encoder returns as 'hidden' for
+        attention rescoring (model/encoder.py:140-147) -- after_norm(x), the input of out_linear, eps 1e-12.  Built from the
+        residual stream "x" (through row0 when the batch ran on packed rows; frames past an utterance's end are then
+        LayerNorm(0)).  normalized=False: the residual stream itself, for a consumer that applies after_norm in its own
+        GEMM's prologue (AttentionRescorer.rescore(raw_memory=True)).  A copy: it stays valid after the next forward.
+        Needs the plan's after_norm.weight / after_norm.bias (plan.pack_decoder writes them)."""
+        if self._bound is None:
+            raise _lib.M3Error("Engine.hidden: no forward has run")
+        if normalized and "after_norm.weight" not in self.weights:
+            raise _lib.M3Error("Engine.hidden: the plan has no after_norm.weight / after_norm.bias (it folds the encoder's final "
+                               "LayerNorm into out_linear); plans packed with a decoder carry them")
+        from . import ops
+        self.stream.synchronize()
+        x = self.rows_padded("x")
+        B, Tp, D = x.shape
+        if not normalized:
+            return x.clone()
+        return ops.layer_norm(x.contiguous().view(B * Tp, D), self.weights["after_norm.weight"], self.weights["after_norm.bias"],
+                              1e-12).view(B, Tp, D)
 
     def buffer(self, name, dtype=torch.float32, ws=None):
         """Zero-copy view of a named intermediate inside the bound workspace (ws: the workspace of the binding that ran last

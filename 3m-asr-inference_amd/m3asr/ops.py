@@ -785,6 +785,55 @@ def ctc_endpoint_read(desc, state, info=None):
     return info
 
 
+# ---- attention rescoring (m3asr.rescore drives these around the decoder's GEMMs)
+def aed_embed(hyp_tokens, hyp_len, n_hyps, hyp_row0, emb, pe, rows, reverse=False):
+    """Decoder input rows of the device n-best (m3_aed_embed): hyp_tokens (B,beam,max_frames), hyp_len (B,beam), n_hyps (B,),
+    hyp_row0 (B*beam+1,) int32; emb (V,D), pe (pe_rows,D) -> (x (rows,D) f32, target (rows,) int32)."""
+    B, beam, F = hyp_tokens.shape
+    V, D = emb.shape
+    assert hyp_row0.numel() == B * beam + 1 and hyp_len.numel() == B * beam and n_hyps.numel() == B and pe.shape[1] == D
+    x = torch.empty(rows, D, dtype=torch.float32, device=emb.device)
+    target = torch.empty(rows, dtype=torch.int32, device=emb.device)
+    check(_lib.load().m3_aed_embed(_i32(hyp_tokens), _i32(hyp_len), _i32(n_hyps), _i32(hyp_row0), B, beam, F, _f32(emb), _f32(pe),
+                                   pe.shape[0], V, D, int(bool(reverse)), int(rows), _p(x), D, _p(target), _stream()), "m3_aed_embed")
+    return x, target
+
+
+def aed_attention(q, k, v, desc, max_q, H, out=None):
+    """Multi-head attention core on packed query rows (m3_aed_attention): q (q_rows, H*dk), k / v (kv_rows, H*dk) row-strided
+    views, desc (n_slots, 5) int32 = (q_row0, n_q, kv_row0, kv_len, causal) per hypothesis slot -> ctx (q_rows, H*dk)."""
+    D = q.shape[1]
+    dk = D // H
+    assert D == H * dk and k.shape[1] == D and v.shape[1] == D and k.shape[0] == v.shape[0]
+    assert desc.dim() == 2 and desc.shape[1] == 5
+    if out is None:
+        out = torch.empty(q.shape[0], D, dtype=torch.float32, device=q.device)
+    (qp, ldq), (kp, ldk), (vp, ldv), (op, ldo) = _rows(q), _rows(k), _rows(v), _rows(out)
+    check(_lib.load().m3_aed_attention(qp, ldq, kp, ldk, vp, ldv, _i32(desc), desc.shape[0], int(max_q), q.shape[0], k.shape[0],
+                                       H, dk, 1.0 / math.sqrt(dk), op, ldo, _stream()), "m3_aed_attention")
+    return out
+
+
+def aed_score(logits, target, hyp_row0, n_hyps, B, beam, prior=None, ctc_weight=0.0, r_logits=None, r_target=None,
+              reverse_weight=0.0):
+    """Scores and choice (m3_aed_score): logits (rows, V) [+ r_logits of the right-to-left decoder] ->
+    (att, r_att, final (B,beam) f32, best (B,) int32); dead slots hold -inf, best = -1 without hypotheses."""
+    rows, V = logits.shape
+    dev = logits.device
+    att = torch.empty(B, beam, dtype=torch.float32, device=dev)
+    r_att, final = torch.empty_like(att), torch.empty_like(att)
+    best = torch.empty(B, dtype=torch.int32, device=dev)
+    scratch = torch.empty(max(2 * rows, 1), dtype=torch.float32, device=dev)
+    (lp, ldl) = _rows(logits) if rows else (None, V)
+    (rp, ldrl) = _rows(r_logits) if (r_logits is not None and rows) else (None, V)
+    assert r_logits is None or tuple(r_logits.shape) == (rows, V)
+    check(_lib.load().m3_aed_score(lp, ldl, rp, ldrl, _i32(target) if rows else None,
+                                   _i32(r_target) if (r_logits is not None and rows) else None, _i32(hyp_row0), _i32(n_hyps),
+                                   _f32(prior), B, beam, rows, V, float(ctc_weight), float(reverse_weight), _p(scratch), _p(att),
+                                   _p(r_att), _p(final), _p(best), _stream()), "m3_aed_score")
+    return att, r_att, final, best
+
+
 # ---------------------------------------------------------------------------------------- streaming operators
 def cat_split_cache(in_cache, inp):
     """CatSplitCache plugin: (output (B, cache+input), out_cache (B, cache)); f32 or i32 rows."""

@@ -14,6 +14,8 @@ into the layouts the HIP engine consumes (all build-time host work, done once):
   * router_weights [D+De, E] -> transposed [E, D+De]; expert w_2 [E,D,F] -> slice-major [E,F/64,D,64];
   * eval BatchNorm in the conv module (cnn_module_norm='batch_norm') folded into the depthwise conv;
   * the sinusoidal table ``pe`` (positional_encoding.py:40-48) for max_len positions;
+  * ``pack_decoder``: the attention decoder of a joint CTC/attention checkpoint (`decoder.*`, fp32 in every mode) for
+    m3asr.rescore; its DecoderConfig travels in the header's extra["decoder"], so encoder-only plans are unchanged;
   * in expert-parallel mode only this rank's expert slice [rank*E_loc, (rank+1)*E_loc) is kept
     (load_state_dict_comm, conformer_fmoe_localComm_catEmbed_domain_acc_hier.py:259-273).
 
@@ -29,7 +31,7 @@ from collections import OrderedDict
 import numpy as np
 import torch
 
-from .config import EncoderConfig
+from .config import DecoderConfig, EncoderConfig
 
 MAGIC = b"M3ASRPL1"
 EXPERT_SLICE = 64    # = m3_moe_expert_slice() of libm3asr_hip.so (checked when an Engine is created)
@@ -178,6 +180,89 @@ def pack_weights(state_dict, cfg: EncoderConfig):
         [sd["embed.blocks.%d.self_attn.linear_pos.weight" % i] for i in range(cfg.embed_blocks)] +
         [sd["blocks.%d.self_attn.linear_pos.weight" % i] for i in range(cfg.num_blocks)], 0)
     return cast_gemm_weights(OrderedDict((k, v.contiguous()) for k, v in out.items()), cfg)
+
+
+def memory_norm(state_dict):
+    """The encoder's final LayerNorm as vectors, `after_norm.weight` / `after_norm.bias` (pack_weights folds it into out_linear):
+    with them in its plan Engine.hidden() can turn the residual stream into the attention decoder's memory."""
+    enc = "encoder." if "encoder.after_norm.weight" in state_dict else ""
+    return OrderedDict((n, state_dict[enc + n].detach().float().contiguous()) for n in ("after_norm.weight", "after_norm.bias"))
+
+
+def has_decoder(state_dict, prefix="decoder."):
+    """whether a checkpoint carries an attention decoder under `prefix`"""
+    return any(k.startswith(prefix) and k.endswith("embed.0.weight") for k in state_dict)
+
+
+def decoder_config_from_state_dict(state_dict, prefix="decoder.", heads=4, activation="relu"):
+    """DecoderConfig of the decoder under `prefix`, from its tensors' shapes (heads and activation are not in the shapes)."""
+    bi = (prefix + "left_decoder.embed.0.weight") in state_dict
+    left = prefix + ("left_decoder." if bi else "")
+
+    def blocks(p):
+        n = 0
+        while (p + "decoders.%d.norm1.weight" % n) in state_dict:
+            n += 1
+        return n
+
+    V, D = state_dict[left + "embed.0.weight"].shape
+    F = state_dict[left + "decoders.0.feed_forward.w_1.weight"].shape[0]
+    return DecoderConfig(vocab=int(V), dim=int(D), heads=int(heads), linear_units=int(F), num_blocks=blocks(left),
+                         r_num_blocks=blocks(prefix + "right_decoder.") if bi else 0, activation=activation)
+
+
+def pack_decoder(state_dict, dcfg: DecoderConfig, prefix="decoder."):
+    """The attention decoder of a reference-layout state_dict (layer/att_decoder.py: `prefix`embed.0 / decoders.N.* /
+    after_norm / output_layer, or left_decoder.* / right_decoder.* under it) -> OrderedDict of packed fp32 tensors for
+    m3asr.rescore.AttentionRescorer, to be merged into the encoder's packed weights:
+      * `decoder.*` the left-to-right decoder, `decoder.right.*` the right-to-left one: embed.weight, per layer the
+        self-attention q/k/v fused into qkv [3D, D], the source attention's linear_q, both linear_out, the FFN, norm1-3
+        (kept as vectors: they are the GEMMs' LayerNorm prologue), after_norm, output_layer;
+      * decoder.src_kv_all: linear_k / linear_v of the source attention of EVERY layer of both decoders stacked to
+        [(L + Lr) 2D, D] -- the memory is projected by one GEMM per rescoring call (pos_all.weight is the precedent); layer l
+        owns rows [l 2D, l 2D + D) = K and the next D = V, the right decoder's layers follow the left one's;
+      * decoder.pe, the sinusoidal table; after_norm.weight / bias: the encoder's final LayerNorm as vectors (pack_weights
+        folds it into out_linear), which turns the engine's residual stream into the decoder's memory.
+    The decoder's weights stay fp32 whatever the plan's weight_dtype: cast_gemm_weights is not applied to them."""
+    sd = {k: v.detach().float() for k, v in state_dict.items()}
+    bi = dcfg.r_num_blocks > 0
+    out = OrderedDict()
+    kv_w, kv_b = [], []
+    for src, dst, blocks in ((prefix + ("left_decoder." if bi else ""), "decoder.", dcfg.num_blocks),
+                             (prefix + "right_decoder.", "decoder.right.", dcfg.r_num_blocks)):
+        if blocks == 0 and dst != "decoder.":
+            continue
+        emb = sd[src + "embed.0.weight"]
+        assert tuple(emb.shape) == (dcfg.vocab, dcfg.dim), "%sembed.0.weight %s, config says (%d, %d)" % (
+            src, tuple(emb.shape), dcfg.vocab, dcfg.dim)
+        out[dst + "embed.weight"] = emb
+        for n in ("after_norm.weight", "after_norm.bias", "output_layer.weight", "output_layer.bias"):
+            out[dst + n] = sd[src + n]
+        for i in range(blocks):
+            p, q = src + "decoders.%d." % i, dst + "layers.%d." % i
+            a = p + "self_attn."
+            out[q + "self_attn.qkv.weight"] = torch.cat([sd[a + "linear_%s.weight" % n] for n in "qkv"], 0)
+            out[q + "self_attn.qkv.bias"] = torch.cat([sd[a + "linear_%s.bias" % n] for n in "qkv"], 0)
+            c = p + "src_attn."
+            kv_w += [sd[c + "linear_k.weight"], sd[c + "linear_v.weight"]]
+            kv_b += [sd[c + "linear_k.bias"], sd[c + "linear_v.bias"]]
+            for n in ("self_attn.linear_out", "src_attn.linear_q", "src_attn.linear_out", "feed_forward.w_1", "feed_forward.w_2",
+                      "norm1", "norm2", "norm3"):
+                out[q + n + ".weight"] = sd[p + n + ".weight"]
+                out[q + n + ".bias"] = sd[p + n + ".bias"]
+            assert out[q + "feed_forward.w_1.weight"].shape[0] == dcfg.linear_units
+    if kv_w:
+        out["decoder.src_kv_all.weight"] = torch.cat(kv_w, 0)
+        out["decoder.src_kv_all.bias"] = torch.cat(kv_b, 0)
+    out["decoder.pe"] = positional_table(dcfg.max_len, dcfg.dim)
+    out.update(memory_norm(sd))
+    return OrderedDict((k, v.contiguous()) for k, v in out.items())
+
+
+def decoder_config_of(extra):
+    """DecoderConfig a plan's header carries (extra["decoder"]), or None for an encoder-only plan."""
+    d = (extra or {}).get("decoder")
+    return None if d is None else DecoderConfig.from_dict(d)
 
 
 def read_cmvn_stats(path):

@@ -165,6 +165,59 @@ def make_weights(cfg, seed=0, router_std=0.5, skip_unused=True):
     return sd
 
 
+def decoder_param_shapes(dcfg, prefix="decoder."):
+    """Ordered {name: shape} of the attention decoder's state_dict (layer/att_decoder.py:184-210; the concat_linear layers,
+    which concat_after=False never reads, are left out): a TransformerDecoder under `prefix`, or with r_num_blocks > 0 a
+    BiTransformerDecoder's left_decoder / right_decoder under it."""
+    D, F, V = dcfg.dim, dcfg.linear_units, dcfg.vocab
+    sh = OrderedDict()
+
+    def one(p, blocks):
+        sh[p + "embed.0.weight"] = (V, D)
+        for n in ("after_norm.weight", "after_norm.bias"):
+            sh[p + n] = (D,)
+        sh[p + "output_layer.weight"] = (V, D)
+        sh[p + "output_layer.bias"] = (V,)
+        for i in range(blocks):
+            q = p + "decoders.%d." % i
+            for a in ("self_attn.", "src_attn."):
+                for n in ("linear_q", "linear_k", "linear_v", "linear_out"):
+                    sh[q + a + n + ".weight"] = (D, D)
+                    sh[q + a + n + ".bias"] = (D,)
+            sh[q + "feed_forward.w_1.weight"] = (F, D)
+            sh[q + "feed_forward.w_1.bias"] = (F,)
+            sh[q + "feed_forward.w_2.weight"] = (D, F)
+            sh[q + "feed_forward.w_2.bias"] = (D,)
+            for n in ("norm1", "norm2", "norm3"):
+                sh[q + n + ".weight"] = (D,)
+                sh[q + n + ".bias"] = (D,)
+
+    if dcfg.r_num_blocks > 0:
+        one(prefix + "left_decoder.", dcfg.num_blocks)
+        one(prefix + "right_decoder.", dcfg.r_num_blocks)
+    else:
+        one(prefix, dcfg.num_blocks)
+    return sh
+
+
+def make_decoder_weights(dcfg, seed=0, prefix="decoder."):
+    """Deterministic synthetic decoder state_dict (CPU fp32), by make_weights' init law: Linear U(+-1/sqrt(fan_in)), LayerNorm
+    gamma U(0.5,1.5) / beta N(0,0.1), the embedding N(0,1) as nn.Embedding."""
+    shapes = decoder_param_shapes(dcfg, prefix)
+    sd = OrderedDict()
+    for name, shape in shapes.items():
+        leaf = name.rsplit(".", 1)[-1]
+        if name.endswith("embed.0.weight"):
+            t = _normal(shape, 1.0, seed, name)
+        elif "norm" in name:
+            t = _uniform(shape, 0.5, seed, name) + 1.0 if leaf == "weight" else _normal(shape, 0.1, seed, name)
+        else:
+            fan_in = shapes[name[: -len(leaf)] + "weight"][1]
+            t = _uniform(shape, 1.0 / math.sqrt(fan_in), seed, name)
+        sd[name] = t
+    return sd
+
+
 _shape_cache = {}
 
 

@@ -1,6 +1,7 @@
 """AED wrapper description (reference: trainer_3m_fix/model/conformer_aed_fmoe_localComm_catEmbed_domain_acc_hier.py:13-20):
-only ``.encoder`` is built into the engine (builder.py:75); the attention decoders are outside the inference path, their
-checkpoint entries are ignored."""
+only ``.encoder`` is built into the engine (builder.py:75).  The attention decoder's checkpoint entries (`decoder.*`) do not pass
+through this class: builder.py packs them into the plan for m3asr.rescore (plan.pack_decoder); `decoder_1` / `decoder_2`, the
+auxiliary decoders on the intermediate layers, are training-only and ignored."""
 from collections import OrderedDict
 
 from model.conformer_fmoe_localComm_catEmbed_domain_acc_hier import Net as ConformerEncoder

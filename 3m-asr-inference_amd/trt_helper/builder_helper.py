@@ -168,8 +168,12 @@ class BuilderHelper:
         if not err <= tol * max(scale, 1.0):
             raise RuntimeError("build_engine: fused engine disagrees with the emitted network (%.3e)" % err)
         if engine_name is not None:
-            save_plan(engine_name, self.model_cfg, packed,
-                      extra={"profiles": {k: [list(s) for s in v] for k, v in self.profiles.items()}})
+            extra = {"profiles": {k: [list(s) for s in v] for k, v in self.profiles.items()}}
+            decoder = getattr(self, "decoder", None)       # (plan.pack_decoder's tensors, DecoderConfig): builder.py sets it
+            if decoder is not None:                        # the engine ignores these entries; m3asr.rescore reads them
+                packed.update(decoder[0])
+                extra["decoder"] = decoder[1].to_dict()
+            save_plan(engine_name, self.model_cfg, packed, extra=extra)
             self.logger.log(trt.Logger.INFO, "[Builder] plan written to " + engine_name)
         names = list(nh.inputs) + ["output"]
         shapes = [tuple(-1 for _ in nh.inputs[n].shape) for n in nh.inputs] + [(-1, -1, self.model_cfg.output_dim)]

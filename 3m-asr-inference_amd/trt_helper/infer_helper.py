@@ -17,6 +17,8 @@ class InferHelper:
         cfg, packed, extra = load_plan(plan_name)
         self.cfg, self.extra = cfg, extra
         self.engine = Engine(cfg, packed, device=device)
+        # what m3asr.rescore.AttentionRescorer needs of the plan (empty for an encoder-only plan)
+        self.decoder_packed = {k: v for k, v in packed.items() if k.startswith("decoder.") or k.startswith("after_norm.")}
         self.output_bias = None      # a prior is inside the plan (folded into out_linear or applied after log-softmax)
 
     def _run(self, feat, feat_len, use_graph):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Build an encoder plan -- same command line as the reference's builder.py (:150-168):
+"""Build an encoder plan (with the attention decoder, when the checkpoint has one) -- same command line as the reference's builder.py (:150-168):
 
     python3 builder.py -c config.yaml -m checkpoint.pt -o encoder.plan [-prior prior.txt] [-cmvn cmvn] [-f] [-i]
 
@@ -36,7 +36,7 @@ class ConformerConfig(trt_helper.HelperConfig):
     pass
 
 
-def build_trt(model, args, input_dim, plan_name, prior=None, profile=None):
+def build_trt(model, args, input_dim, plan_name, prior=None, profile=None, decoder=None):
     logger = trt_helper.init_trt_plugin(trt.Logger.VERBOSE if args.verbose else trt.Logger.INFO, "libm3asr_hip.so")
     cfg = ConformerConfig()
     cfg.max_workspace_size = 8
@@ -51,6 +51,7 @@ def build_trt(model, args, input_dim, plan_name, prior=None, profile=None):
         cfg.use_int8 = True
         calibrator = trt_helper.AsrCalibrator(args.calib_feat_list, args.calib_feat_len_list, args.calib_cache, args.calib_batches)
     builder_helper = trt_helper.BuilderHelper(cfg, logger, calibrator)
+    builder_helper.decoder = decoder                # (packed attention decoder, DecoderConfig) or None: goes into the plan
     nh = builder_helper.get_network_helper()
     feat = nh.addInput(name="feat", dtype=trt.float32, shape=(-1, -1, input_dim))
     feat_len = nh.addInput(name="feat_len", dtype=trt.int32, shape=(1, -1))
@@ -101,7 +102,15 @@ def main(args):
     if args.opt_shape:
         b, t = (int(v) for v in args.opt_shape.split("x"))
         profile = ((1, b, max(b, 6)), (1, t, max(t, 6100)))
-    build_trt(model, args, input_dim, args.output, prior, profile)
+    decoder = None
+    from m3asr.plan import decoder_config_from_state_dict, has_decoder, pack_decoder
+    if has_decoder(param_dict):                     # a joint CTC/attention checkpoint: pack its decoder for infer.py --rescore
+        dconf = configs["model_conf"].get("decoder_conf") or {}
+        dcfg = decoder_config_from_state_dict(param_dict, heads=dconf.get("attention_heads", 4),
+                                              activation=dconf.get("activation", "relu"))
+        decoder = (pack_decoder(param_dict, dcfg), dcfg)
+        print("attention decoder: {}".format(dcfg))
+    build_trt(model, args, input_dim, args.output, prior, profile, decoder)
 
 
 if __name__ == "__main__":

@@ -782,6 +782,44 @@ int m3_fbank_num_frames(int n_samples);
 int m3_fbank(const void* tables, const void* pcm, int pcm_is_int16, int ld_pcm, const int32_t* n_samples, int B, int T,
              int num_mel_bins, float* feat, int ld_feat, int32_t* feat_len_out, m3_stream stream);
 
+/* Attention rescoring: the AED decoder's second pass over the CTC n-best (csrc/aed_rescore.hip).  The decoder
+ * runs teacher-forced on PACKED hypothesis rows: hypothesis slot h = b * beam + i owns rows [hyp_row0[h], hyp_row0[h + 1]) of
+ * every row buffer, len + 1 of them for a live slot (sos, then its tokens) and none for a slot i >= n_hyps[b] (n_hyps < 0, a
+ * failed search, counts as 0).  The dense layers between these kernels are m3_linear calls.  All kernels are fp32 and
+ * deterministic: no atomics, every reduction in a fixed order, a row's result independent of where the row lies.  All
+ * pointers are device memory.
+ * m3_aed_embed: decoder input x [rows][ldx] = emb[tok] * sqrt(D) + pe[pos] for the input tokens (sos, y_0 .. y_{n-1}), or
+ *   (sos, y_{n-1} .. y_0) with reverse != 0, and target [rows] = the token each row has to predict (the input shifted by one,
+ *   then eos = sos).  hyp_tokens [B][beam][max_frames] / hyp_len / n_hyps as m3_ctc_beam_*_nbest leave them; hyp_row0
+ *   [B * beam + 1].  emb [V][D], pe [pe_rows][D].  A slot whose row range disagrees with its length, leaves [0, rows) or
+ *   needs more than pe_rows positions is skipped; a token outside [0, V) gives a row of NaN.  D a multiple of 4, ldx >= D.
+ * m3_aed_attention: multi-head attention core on packed query rows, online softmax over key tiles staged in LDS, no score
+ *   matrix in memory.  att_desc [n_slots][5] int32 = (q_row0, n_q, kv_row0, kv_len, causal) per hypothesis slot: its n_q
+ *   query rows start at row q_row0 of q / out, its keys and values are rows [kv_row0, kv_row0 + kv_len) of k / v; causal:
+ *   query i sees keys j <= i.  Self-attention points a slot at its own rows (causal = 1), source attention at the memory
+ *   rows of its utterance, which the whole beam shares.  q [q_rows][ldq], k [kv_rows][ldk], v [kv_rows][ldv], out
+ *   [q_rows][ldo], head h in columns [h dk, (h + 1) dk).  max_q >= every n_q (sizes the grid).  dk a multiple of 16, <= 128;
+ *   ldq / ldk / ldv multiples of 4 and the pointers 16-byte aligned.  A slot with n_q <= 0 does nothing; a slot with
+ *   kv_len <= 0 or a range outside [0, q_rows) / [0, kv_rows) is skipped (its rows stay unwritten): the caller rejects
+ *   kv_len = 0 before it builds the descriptors.
+ * m3_aed_score: per packed row logsumexp over V and the target's logit (one wave per row), per hypothesis their sum in row
+ *   order, att [B][beam]; with r_logits the same for the right-to-left decoder, r_att; final = (1 - reverse_weight) att +
+ *   reverse_weight r_att + ctc_weight prior (the r_att term only with r_logits, the prior term only with ctc_weight != 0);
+ *   best [B] = the first slot with the strictly largest final, -1 for an utterance without hypotheses.  Dead slots report
+ *   -inf in att / r_att / final (r_att is 0 for live slots without r_logits).  logits [rows][ldl], r_logits NULL or
+ *   [rows][ldrl], target / r_target [rows], prior [B][beam] (may be NULL when ctc_weight = 0), row_logp [2 * rows] scratch.
+ *   1 <= beam <= 64. */
+int m3_aed_embed(const int32_t* hyp_tokens, const int32_t* hyp_len, const int32_t* n_hyps, const int32_t* hyp_row0, int B,
+                 int beam, int max_frames, const float* emb, const float* pe, int pe_rows, int V, int D, int reverse, int rows,
+                 float* x, int ldx, int32_t* target, m3_stream stream);
+int m3_aed_attention(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const int32_t* att_desc,
+                     int n_slots, int max_q, int q_rows, int kv_rows, int H, int dk, float scale, float* out, int ldo,
+                     m3_stream stream);
+int m3_aed_score(const float* logits, int ldl, const float* r_logits, int ldrl, const int32_t* target, const int32_t* r_target,
+                 const int32_t* hyp_row0, const int32_t* n_hyps, const float* prior, int B, int beam, int rows, int V,
+                 float ctc_weight, float reverse_weight, float* row_logp, float* att, float* r_att, float* final_score,
+                 int32_t* best, m3_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,13 @@ searched twice on the device, plain and biased towards the phrases (m3asr.contex
 
 lm.arpa is an n-gram LM in ARPA format (or an image saved by m3asr.lm.NgramLm.save, *.npy); units.txt maps its words to
 token ids (`token id` per line; without it the words are token ids).  The scores are searched plain and with the LM fused into
-the ranking (m3asr.lm), together with --hotwords if both are given."""
+the ranking (m3asr.lm), together with --hotwords if both are given.
+
+    python3 infer.py -p aed.plan -i feat.npy --rescore [--beam 10] [--ctc-weight 0.5] [--reverse-weight 0.3]
+
+Attention rescoring, for a plan built from a joint CTC/attention checkpoint: the batched prefix beam search, then the plan's
+attention decoder rescoring every utterance's n-best on the encoder's hidden states (m3asr.rescore).  Prints the first-pass
+best and the rescored best hypothesis of each utterance."""
 import argparse
 import os
 import sys
@@ -90,6 +96,25 @@ def print_lm_search(scores, device, args):
                                                                          " ".join(str(t) for t in h[0][0])))
 
 
+def print_rescore(helper, feat, feat_len, args):
+    """Best hypothesis of every utterance after the first pass and after attention rescoring."""
+    import torch
+    from m3asr.decode import CtcDecoder
+    from m3asr.plan import decoder_config_of
+    from m3asr.rescore import AttentionRescorer
+    rescorer = AttentionRescorer(helper.decoder_packed, decoder_config_of(helper.extra), helper.engine.device)
+    dec = CtcDecoder(helper.engine, rescorer=rescorer)
+    out = dec.attention_rescoring(torch.from_numpy(feat), torch.from_numpy(feat_len), args.beam, ctc_weight=args.ctc_weight,
+                                  reverse_weight=args.reverse_weight, detail=True)
+    for b, (best, hyps) in enumerate(out):
+        if not hyps:
+            print("utt %d: no hypothesis" % b)
+            continue
+        chosen = next(h for h in hyps if h[0] == best)
+        print("utt %d ctc:      prior=%.4f tokens=%s" % (b, hyps[0][1], " ".join(str(t) for t in hyps[0][0])))
+        print("utt %d rescored: att=%.4f final=%.4f tokens=%s" % (b, chosen[2], chosen[3], " ".join(str(t) for t in best)))
+
+
 def main(args):
     logger = trt_helper.init_trt_plugin(trt.Logger.INFO, "libm3asr_hip.so")
     helper = trt_helper.InferHelper(args.plan_name, logger)
@@ -105,6 +130,8 @@ def main(args):
         print("outputs.shape:" + str(o.shape))
         print("outputs.sum:" + str(o.sum()))
         print(o)
+    if args.rescore:
+        print_rescore(helper, feat, feat_len, args)
     if args.lm:
         print_lm_search(outputs[0], helper.engine.device, args)
     elif args.hotwords:
@@ -128,4 +155,7 @@ if __name__ == "__main__":
     p.add_argument("--units", help="`token id` per line: the ARPA's words as token ids (default: the words are token ids).")
     p.add_argument("--lm-weight", type=float, default=0.5, help="Weight of log P_LM in the ranking.")
     p.add_argument("--length-bonus", type=float, default=0.0, help="Bonus per token of a prefix in the ranking.")
+    p.add_argument("--rescore", action="store_true", help="Attention rescoring of the n-best with the plan's AED decoder.")
+    p.add_argument("--ctc-weight", type=float, default=0.0, help="--rescore: weight of the first-pass score in the final score.")
+    p.add_argument("--reverse-weight", type=float, default=0.0, help="--rescore: weight of the right-to-left decoder.")
     main(p.parse_args())
