@@ -109,7 +109,8 @@ __device__ __forceinline__ void stg4(float* p, f32x4 v) { *reinterpret_cast<f32x
 // -DM3_NT_WEIGHTS=1 makes these loads non-temporal (L2-served, bypass L1: MI355X_MICROARCH.md).  A/B at configs[1], same device,
 // same process order (profiles/r03_ab_headline.txt): one forward alone 2.377 vs 2.390 ms (-0.5 %), but 187 k vs 207 k frames/s
 // with four execution contexts (-10 %): the four row-tile work-groups that share a weight tile through their XCD's L2 no
-// longer find it there once their timing is skewed by the other contexts.  Off by default.
+// longer find it there once their timing is skewed by the other contexts.  Off by default.  Switched on for the B = 1 expert
+// launch ALONE (no weight byte has a second reader there) it loses as well: 33.6 vs 30.3 us per launch, -5.5 %.
 #ifndef M3_NT_WEIGHTS
 #define M3_NT_WEIGHTS 0
 #endif

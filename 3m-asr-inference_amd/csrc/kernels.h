@@ -163,6 +163,7 @@ size_t expert_ffn_slab_bytes(int S, int D, int F);   // the slab region: F / kEx
 //              form does not apply), not EXPERT_NORM_IN_KERNEL              2 launches, H | sorted rows (one slab)
 //   Slab*      everything else                                              1 launch,   F / 64 partial-result slabs at offset 0
 // A form is taken only if all its sections fit into expert_ffn_slab_bytes.  The thresholds are read once per process.
+// (SlabF32's weight stream keeps the default cache policy also where every byte has one reader: non-temporal loads there lost)
 enum class ExpertWeights { F32, BF16, FP8, FP8A8 };   // FP8A8: fp8 weights + fp8 activations where FusedFp8 applies, else the weight-only forms
 enum class ExpertKernel { SlabF32, TiledF32, SlabBf16, TiledBf16, G256Bf16, SlabW8, TiledW8, FusedFp8 };
 struct ExpertFfnPlan {

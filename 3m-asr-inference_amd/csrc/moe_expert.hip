@@ -19,6 +19,8 @@
 // pure weight streaming: 4.2 MB per touched expert, E*F/64 = 512 workgroups of 256 KB each.
 // Measured dead ends: a persistent work-queue form (atomic item counter) was 30 % slower,
 // 32-wide slices and 3-4 deep load rings did not move the time: the kernel sits at the ~24 GB/s a CU can pull.
+#include <stdlib.h>
+
 #include "common.h"
 #include "kernels.h"
 #include "moe_gate.h"
@@ -38,7 +40,24 @@ struct ExpertRoute {
   int32_t* gate_idx = nullptr; float* gate_value = nullptr;
   int32_t* mapping = nullptr; int32_t* acc_hist = nullptr; int32_t* pos = nullptr;
   const float* b2 = nullptr;                // [E][D], added by slice 0
+  int wave_route = 0;                       // S <= 64: every wave routes all rows itself (no LDS exchange, no barrier)
 };
+
+// The self-routing launch's run-time switch: an environment variable read once per process (it exists for the A/B).
+struct ExpertSwitches {
+  // M3_ROUTE_WAVE (1): the self-routing launch of S <= 64 rows routes per wave, in registers.  0: the per-work-group prologue
+  // (LDS count exchange + barrier) that 64 < S <= 256 runs
+  bool route_wave;
+};
+static const ExpertSwitches& expert_switches() {
+  static const ExpertSwitches sw = [] {
+    auto num = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
+    ExpertSwitches w;
+    w.route_wave = num("M3_ROUTE_WAVE", 1) != 0;
+    return w;
+  }();
+  return sw;
+}
 
 // LNS: apply the layer's LayerNorm while gathering rows (fused-route engines); a separate instantiation so the
 // default path does not carry its registers.
@@ -107,7 +126,9 @@ __global__ __launch_bounds__(64 * (kExpertSlice / 16)) void expert_ffn_f32_kerne
   // known, was measured and LOSES: expert launch 32.1 vs 30.6 us in situ, 214 k vs 220 k frames/s -- profiles/r04_ab_self_route.txt)
   constexpr int REW = RE > 0 ? RE : 8;
   f32x4 lrow[REW / 4];
-  const int rt_r = 64 * wave + lane;
+  // wave routing (S <= 64): lane l of EVERY wave takes row l, so each wave ends up with the whole routing in its own registers
+  const bool wroute = RE > 0 && MT == 1 && rt.wave_route != 0;
+  const int rt_r = wroute ? lane : 64 * wave + lane;
   bool rt_live = false;
   if (RE > 0) {
     rt_live = rt_r < S && (rt.row_len == nullptr || (rt_r % rt.rows_per_batch) < rt.row_len[rt_r / rt.rows_per_batch]);
@@ -116,9 +137,43 @@ __global__ __launch_bounds__(64 * (kExpertSlice / 16)) void expert_ffn_f32_kerne
     for (int j = 0; j < REW / 4; ++j) lrow[j] = ldg4(lp + 4 * j);
   }
   int row_lo, row_hi;
+  int wrow = 0;           // wave routing: lane q holds the row of rank q among my expert's rows
   __shared__ int32_t route_rows[RE > 0 ? 64 * (kExpertSlice / 16) : 1];   // self-routing: my expert's rows in stable order
   __shared__ int route_cnt[RE > 0 ? 2 * (kExpertSlice / 16) : 1];
-  if (RE > 0) {
+  if (wroute) {
+    const int r = rt_r;
+    const bool live = rt_live, taps = slice == 0 && wave == 0;    // (one wave of slice 0 leaves the taps)
+    int gi = -1;
+    float gv = 0.f;
+    gate_top1_regs<REW>(lrow, &gi, &gv, taps);
+    if (!live) { gi = -1; gv = 0.f; }
+    const unsigned long long mine = __ballot(gi == e), below = __ballot(live && gi < e);
+    const unsigned long long lower = (1ull << lane) - 1ull;
+    const int n_e = __popcll(mine), acc_e = __popcll(below);
+    const int rank = __popcll(mine & lower);
+    // a full permutation of the lanes (my rows first, in lane order = the stable order; the others behind them): one forward
+    // permute of the lane id, no two lanes aim at the same one
+    const int dest = gi == e ? rank : n_e + __popcll(~mine & lower);
+    wrow = __builtin_amdgcn_ds_permute(dest << 2, lane);
+    if (taps) {
+      if (gi == e) {
+        rt.gate_idx[r] = gi;
+        rt.gate_value[r] = gv;
+        if (rt.mapping) rt.mapping[r] = acc_e + rank;
+        if (rt.pos) rt.pos[acc_e + rank] = r;
+      } else if (e == 0 && r < S && !live) {
+        rt.gate_idx[r] = -1;
+        rt.gate_value[r] = 0.f;
+        if (rt.mapping) rt.mapping[r] = -1;
+      }
+      if (rt.acc_hist && lane == 0) {
+        rt.acc_hist[e] = acc_e;
+        if (e == RE - 1) rt.acc_hist[RE] = acc_e + n_e;
+      }
+    }
+    row_lo = 0;
+    row_hi = n_e;          // (the same in every wave: they leave or stay together)
+  } else if (RE > 0) {
     constexpr int NWR = kExpertSlice / 16;
     const int r = rt_r;
     const bool live = rt_live;
@@ -177,7 +232,9 @@ __global__ __launch_bounds__(64 * (kExpertSlice / 16)) void expert_ffn_f32_kerne
     for (int i = wave; i < 16 * MT; i += NWV) {
       float* dst = xs + i * xs_ld;
       if (i < nrows) {
-        const float* src = x + (size_t)(RE > 0 ? route_rows[r0 + i] : pos[r0 + i]) * ldx;
+        const int xrow = wroute ? __builtin_amdgcn_readlane(wrow, __builtin_amdgcn_readfirstlane(r0 + i))
+                                : (RE > 0 ? route_rows[r0 + i] : pos[r0 + i]);
+        const float* src = x + (size_t)xrow * ldx;
         if (LNS) {
           // the layer's LayerNorm (norm_ff) applied on the fly: x is the raw residual stream and the normalised
           // MoE input never exists in memory (two-pass statistics; the row is L1/L2-resident)
@@ -232,7 +289,10 @@ __global__ __launch_bounds__(64 * (kExpertSlice / 16)) void expert_ffn_f32_kerne
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) orow[mt][r] = route_rows[min(r0 + 16 * mt + 4 * kq + r, row_hi - 1)];
+        for (int r = 0; r < 4; ++r) {
+          const int q = min(r0 + 16 * mt + 4 * kq + r, row_hi - 1);
+          orow[mt][r] = wroute ? __shfl(wrow, q, 64) : route_rows[q];
+        }
     }
 
     // phase change: H = SiLU(acc1 + b1) -> LDS -> A fragments of phase 2
@@ -383,6 +443,7 @@ int launch_expert_route_ffn_f32(const float* x, int ldx, const float* logits, co
   ExpertRoute rt;
   rt.logits = logits; rt.row_len = row_len; rt.rows_per_batch = rows_per_batch; rt.gate_idx = gate_idx; rt.gate_value = gate_value;
   rt.mapping = mapping; rt.acc_hist = acc_hist; rt.pos = pos; rt.b2 = b2;
+  rt.wave_route = S <= 64 && expert_switches().route_wave;
   dim3 grid(F / kExpertSlice, E, 1);
   const int w2_row_stride = w2_sliced ? kExpertSlice : F;
   const int w2_slice_stride = w2_sliced ? D * kExpertSlice : kExpertSlice;
@@ -426,11 +487,46 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(const float* __restric
   const int s = blockIdx.x * 4 + wave;
   if (s >= S) return;
   if (n_slices_dev != nullptr) n_slices = min(n_slices, *n_slices_dev);   // (the fused fp8 kernel chose its F split on the device)
+  // ORIGINAL-row slabs, D <= 512, at most 16 of them (the B = 1 layer): no address depends on a loaded value, so EVERY load the
+  // row needs -- gate index and value, n_slices x NV slab float4, residual, gamma, beta -- is requested before the first use of
+  // one: one memory round trip.  Same sums in the same order as the loop below (slices 0, 1, ... and the zeros behind n_slices).
+  constexpr int NG = NV <= 2 ? NV : 1;           // (the register arrays of the one-trip form; unused beyond NV = 2)
+  const bool one_trip = NV <= 2 && mapping == nullptr && n_slices_dev == nullptr && n_slices >= 1 && n_slices <= 16;
   const int g = gate_idx ? gate_idx[s] : 0;
+  const float gv_early = (one_trip && gate_value) ? gate_value[s] : 1.f;    // (not behind the gate index's round trip)
   const int m = mapping ? mapping[s] : (g >= 0 ? s : -1);
-  const float gate = (m >= 0) ? (gate_value ? gate_value[s] : 1.f) : 0.f;
+  const float gate = (m >= 0) ? (one_trip ? gv_early : (gate_value ? gate_value[s] : 1.f)) : 0.f;
   f32x4 v[NV];
   float sum = 0.f;
+  f32x4 ga[NG], be[NG];
+  if (NV <= 2 && one_trip) {
+    f32x4 t[NG][16], rs[NG];
+#pragma unroll
+    for (int i = 0; i < NG; ++i) {
+      const int c = min((lane + 64 * i) * 4, D - 4);       // clamped, not branched: the loads stay back to back
+#pragma unroll
+      for (int j = 0; j < 16; ++j) t[i][j] = ldg4(slab + ((size_t)min(j, n_slices - 1) * S + s) * D + c);
+      rs[i] = resid ? ldg4(resid + (size_t)s * D + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+      ga[i] = ln_gamma ? ldg4(ln_gamma + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+      be[i] = ln_gamma ? ldg4(ln_beta + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int i = 0; i < NG; ++i) {
+      const int c = (lane + 64 * i) * 4;
+      v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (c < D) {
+        f32x4 y = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int j = 0; j < 16; ++j) y += (j < n_slices) ? t[i][j] : f32x4{0.f, 0.f, 0.f, 0.f};
+        if (b2) y += ldg4(b2 + (size_t)max(g, 0) * D + c);
+        if (m < 0) y = f32x4{0.f, 0.f, 0.f, 0.f};
+        y *= (alpha * gate);
+        if (resid) y += rs[i];
+        v[i] = y;
+        sum += (y[0] + y[1]) + (y[2] + y[3]);
+      }
+    }
+  } else {
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = (lane + 64 * i) * 4;
@@ -468,6 +564,7 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(const float* __restric
       sum += (y[0] + y[1]) + (y[2] + y[3]);
     }
   }
+  }
   if (ln_gamma) {
     const float mean = wave_sum(sum) / (float)D;
     float q = 0.f;
@@ -487,9 +584,9 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(const float* __restric
     for (int i = 0; i < NV; ++i) {
       const int c = (lane + 64 * i) * 4;
       if (c < D) {
-        const f32x4 ga = ldg4(ln_gamma + c), be = ldg4(ln_beta + c);
+        const f32x4 gm = one_trip ? ga[NV <= 2 ? i : 0] : ldg4(ln_gamma + c), bt = one_trip ? be[NV <= 2 ? i : 0] : ldg4(ln_beta + c);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[i][j] = (v[i][j] - mean) * rstd * ga[j] + be[j];
+        for (int j = 0; j < 4; ++j) v[i][j] = (v[i][j] - mean) * rstd * gm[j] + bt[j];
       }
     }
   }
