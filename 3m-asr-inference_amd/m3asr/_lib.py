@@ -70,6 +70,10 @@ class CtcEndpointDesc(C.Structure):  # m3_ctc_endpoint_desc
                 ("rule", CtcEndpointRule * 4)]
 
 
+class AedMemoryDesc(C.Structure):  # m3_aed_memory_desc
+    _fields_ = [("B", C.c_int32), ("max_frames", C.c_int32), ("D", C.c_int32)]
+
+
 class WeightEntry(C.Structure):  # m3_weight_entry
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64), ("dtype", C.c_int32)]
 
@@ -230,6 +234,12 @@ SIGNATURES = {
     "m3_aed_embed": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "m3_aed_attention": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp]),
     "m3_aed_score": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "m3_aed_memory_state_size": (_sz, [_P(AedMemoryDesc)]),
+    "m3_aed_memory_reset": (_i, [_P(AedMemoryDesc), _vp, _sz, _vp]),
+    "m3_aed_memory_reset_slots": (_i, [_P(AedMemoryDesc), _vp, _sz, _vp, _i, _vp]),
+    "m3_aed_memory_append": (_i, [_P(AedMemoryDesc), _vp, _sz, _vp, _i, _i, _vp, _vp]),
+    "m3_aed_memory_lengths": (_i, [_P(AedMemoryDesc), _vp, _sz, _vp, _vp]),
+    "m3_aed_memory_gather": (_i, [_P(AedMemoryDesc), _vp, _sz, _vp, _i, _vp, _i, _i, _vp, _vp]),
 }
 
 _lib = None

@@ -13,6 +13,8 @@ and return types), running on the device through libm3asr_hip.so:
                 StreamingCtcDecoder(endpoint=...).endpoints(); m3asr.serve.StreamPool(segment=True) cuts sessions there.
   rescoring     the reference's second pass (model/ctc_aed.py:160-252): CtcDecoder(engine, rescorer=...).attention_rescoring
                 runs the batched beam search, then the attention decoder over its n-best (m3asr.rescore).
+  two passes,   StreamingCtcDecoder(..., rescorer=...) keeps every stream's encoder memory on the device (m3_aed_memory_*) and
+  streaming     rescore() runs the second pass over a stream's n-best when its utterance ends; StreamPool(rescore=True).
 
 Chunked decoding (decoding_chunk_size > 0) is accepted when the engine was built for exactly that chunk mask
 (cfg.static_chunk_size == decoding_chunk_size, same num_decoding_left_chunks): its ordinary forward is then the reference's
@@ -387,17 +389,36 @@ class StreamingCtcDecoder:
 
     With endpoint=EndpointConfig(...) every step() also advances the endpoint detector on the top-k the beam search just
     computed (one more small launch on the engine's stream, no second log-softmax, no sync); endpoints() tells which streams'
-    utterances are over."""
+    utterances are over.
+
+    With rescorer=AttentionRescorer(...) the decoder also keeps every stream's encoder memory: each step() appends the chunk's
+    residual stream (the binding's buffer "x", before after_norm) to the stream's rows of a device store, with the same frame
+    counts the beam search consumes (one more launch on the engine's stream, no sync, the chunk's graph is unchanged), and
+    rescore() runs the attention decoder over the listed streams' current n-best.  The memory of a stream is exactly the
+    frames its n-best was searched over."""
 
     def __init__(self, streaming_encoder, beam, blank=0, context=None, lm=None, lm_weight=0.5, length_bonus=0.0, lm_eos=True,
-                 endpoint=None):
+                 endpoint=None, rescorer=None, ctc_weight=0.5, reverse_weight=0.0):
         """context: a m3asr.context.ContextSet on the engine's device (hotword biasing of the beam search; the greedy
         search is not biased); reset(graph_ids=) chooses each stream's graph, -1 = unbiased.
         lm: a m3asr.lm.NgramLm on the engine's device (shallow fusion in the beam search, as CtcBeamSearch(lm=); the walk
         runs inside the advance kernel, so a chunk is still one graph replay and no host round trip); reset(lm_on=) switches
         it per stream.
-        endpoint: an EndpointConfig; None = no endpoint detection (nothing is allocated for it, endpoints() raises)."""
+        endpoint: an EndpointConfig; None = no endpoint detection (nothing is allocated for it, endpoints() raises).
+        rescorer: a m3asr.rescore.AttentionRescorer on the engine's device for rescore(); ctc_weight / reverse_weight: the
+        weights of the first pass and of the right-to-left decoder in its final score.  None = no second pass (nothing is
+        allocated for it, step() launches nothing for it, rescore() raises)."""
         self.st = streaming_encoder
+        self.rescorer, self.ctc_weight, self.reverse_weight = rescorer, float(ctc_weight), float(reverse_weight)
+        if rescorer is not None:          # refuse before anything is allocated or launched
+            ecfg = streaming_encoder.eng.cfg
+            if rescorer.cfg.dim != ecfg.attention_dim or rescorer.cfg.vocab != ecfg.output_dim:
+                raise _lib.M3Error("StreamingCtcDecoder: the rescorer's decoder has dim %d / vocab %d, the encoder attention_dim %d / "
+                                   "output_dim %d" % (rescorer.cfg.dim, rescorer.cfg.vocab, ecfg.attention_dim, ecfg.output_dim))
+            if not _same_device(rescorer.device, streaming_encoder.eng.device):
+                raise _lib.M3Error("StreamingCtcDecoder: the rescorer is on %s, the engine on %s" % (rescorer.device, streaming_encoder.eng.device))
+            if self.reverse_weight > 0 and rescorer.cfg.r_num_blocks == 0:
+                raise _lib.M3Error("StreamingCtcDecoder: reverse_weight = %g needs a right-to-left decoder" % self.reverse_weight)
         self.context = context
         self.lm = lm
         e = streaming_encoder.eng
@@ -415,11 +436,15 @@ class StreamingCtcDecoder:
             self.estate = torch.empty(max(ops.ctc_endpoint_state_size(self.edesc), 1), dtype=torch.uint8, device=e.device)
             self.einfo = torch.empty(B, 8, dtype=torch.int32, device=e.device)
             self.einfo_host = torch.empty(B, 8, dtype=torch.int32, pin_memory=True)
+        if rescorer is not None:
+            self.mdesc = ops.aed_memory_desc(B, max_frames, e.cfg.attention_dim)
+            self.mstate = torch.empty(max(ops.aed_memory_state_size(self.mdesc), 1), dtype=torch.uint8, device=e.device)
+            self.mx = None                # the chunk binding's "x" as (B * c, D) rows, looked up after the first chunk
         self.reset()
 
     def reset(self, slots=None, graph_ids=None, lm_on=None):
-        """Restart all streams, or (slot-mode encoder) the listed slots: encoder state, beam search, greedy search and
-        endpoint state.
+        """Restart all streams, or (slot-mode encoder) the listed slots: encoder state, beam search, greedy search,
+        endpoint state and (decoder with a rescorer) the encoder memory.
         graph_ids (decoder with a context): the graph each restarted stream takes, one per slot; a stream restarted without
         one keeps the graph it had.  lm_on (decoder with an LM): whether each restarted stream runs with the LM."""
         kw = {} if lm_on is None else {"lm_on": lm_on}
@@ -434,6 +459,8 @@ class StreamingCtcDecoder:
                 ops.ctc_greedy_stream_reset(self.gdesc, self.gstate)
                 if self.endpoint is not None:
                     ops.ctc_endpoint_reset(self.edesc, self.estate)
+                if self.rescorer is not None:
+                    ops.aed_memory_reset(self.mdesc, self.mstate)
             elif len(slots) > 0:
                 lst = torch.tensor([int(b) for b in slots], dtype=torch.int32).to(e.device)
                 if self.context is None and self.lm is None:
@@ -443,6 +470,8 @@ class StreamingCtcDecoder:
                 ops.ctc_greedy_stream_reset(self.gdesc, self.gstate, lst)
                 if self.endpoint is not None:
                     ops.ctc_endpoint_reset(self.edesc, self.estate, lst)
+                if self.rescorer is not None:
+                    ops.aed_memory_reset(self.mdesc, self.mstate, lst)
 
     def frames_of(self, valid):
         """Output frames of this chunk that count, from the real feature frames in its window."""
@@ -463,7 +492,56 @@ class StreamingCtcDecoder:
             if self.endpoint is not None:
                 top_logp, top_idx = self.beam.last_topk
                 ops.ctc_endpoint_advance(self.edesc, self.estate, top_logp, top_idx, self.n_out)
+            if self.rescorer is not None:
+                if self.mx is None:
+                    self.mx = self.st.buffer("x").view(-1, self.mdesc.D)
+                ops.aed_memory_append(self.mdesc, self.mstate, self.mx, self.n_out)
         return logits
+
+    def memory_lengths(self):
+        """Decoder with a rescorer: encoder-memory frames every stream holds, (B,) int32 on the host; -1 for a stream that
+        ran past max_frames.  Waits for the engine's stream."""
+        if self.rescorer is None:
+            raise _lib.M3Error("StreamingCtcDecoder.memory_lengths: the decoder was built without a rescorer")
+        e = self.st.eng
+        with torch.cuda.stream(e.stream):
+            n = ops.aed_memory_lengths(self.mdesc, self.mstate)
+        e.stream.synchronize()
+        return n.cpu()
+
+    def memory(self, slots=None):
+        """Decoder with a rescorer: (rows (R, D), row0 (n + 1,) int32) on the device -- the listed streams' encoder memory
+        packed in list order (the residual stream before after_norm), as m3_aed_memory_gather leaves it; stream j of the
+        list owns rows [row0[j], row0[j + 1]).  Enqueued on the engine's stream."""
+        if self.rescorer is None:
+            raise _lib.M3Error("StreamingCtcDecoder.memory: the decoder was built without a rescorer")
+        e = self.st.eng
+        which = list(range(self.mdesc.B)) if slots is None else [int(b) for b in slots]
+        with torch.cuda.stream(e.stream):
+            lst = torch.tensor(which, dtype=torch.int32).to(e.device)
+            return ops.aed_memory_gather(self.mdesc, self.mstate, lst)
+
+    def rescore(self, slots=None, detail=False):
+        """The second pass over the streams' current n-best (slots: only the listed streams, in that order): their encoder
+        memory is gathered (one launch), the attention decoder scores every hypothesis teacher-forced and picks per stream
+        (m3asr.rescore; final = (1 - reverse_weight) att + reverse_weight r_att + ctc_weight prior, the prior being the
+        search's own ranking key).  -> the best token list per stream; detail: AttentionRescorer.rescore's pair per stream,
+        (best tokens, [(tokens, prior, att, final)] in n-best order).  A stream that has consumed no frame gives ((), []).
+        The streams go on as they were: call it before reset() when an utterance ends.  Waits for the engine's stream."""
+        if self.rescorer is None:
+            raise _lib.M3Error("StreamingCtcDecoder.rescore: the decoder was built without a rescorer "
+                               "(StreamingCtcDecoder(..., rescorer=AttentionRescorer(...)))")
+        e = self.st.eng
+        which = list(range(self.mdesc.B)) if slots is None else [int(b) for b in slots]
+        if any(not 0 <= b < self.mdesc.B for b in which):
+            raise ValueError("StreamingCtcDecoder.rescore: slots %s outside [0, %d)" % (which, self.mdesc.B))
+        if not which:
+            return []
+        rows, row0 = self.memory(which)
+        with torch.cuda.stream(e.stream):
+            out = self.rescorer.rescore_rows(rows, row0, self.beam, streams=which, ctc_weight=self.ctc_weight,
+                                             reverse_weight=self.reverse_weight, raw_memory=True)
+        return out if detail else [list(best) for best, _ in out]
 
     def endpoints(self, slots=None):
         """One EndpointInfo per stream (slots: only the listed streams, in that order) after the chunks so far; rule != 0:

@@ -834,6 +834,62 @@ def aed_score(logits, target, hyp_row0, n_hyps, B, beam, prior=None, ctc_weight=
     return att, r_att, final, best
 
 
+# ---- per-slot encoder memory of streaming two-pass decoding (m3_aed_memory_*; StreamingCtcDecoder(rescorer=) drives these)
+def aed_memory_desc(B, max_frames, D):
+    """m3_aed_memory_desc for B streams of at most max_frames rows of D floats.  Raises M3Error on a descriptor the library
+    rejects (D no multiple of 4, a negative size)."""
+    d = _lib.AedMemoryDesc(int(B), int(max_frames), int(D))
+    if _lib.load().m3_aed_memory_state_size(C.byref(_lib.AedMemoryDesc(1, d.max_frames, d.D))) == 0 or d.B < 0:
+        raise _lib.M3Error("m3_aed_memory_state_size failed: " + (_lib.last_error() if d.B >= 0 else "B = %d" % d.B))
+    return d
+
+
+def aed_memory_state_size(desc):
+    return _lib.load().m3_aed_memory_state_size(C.byref(desc))
+
+
+def aed_memory_reset(desc, state, slots=None):
+    """slots: None = every stream; else an int32 device tensor listing the streams to restart."""
+    if slots is not None:
+        check(_lib.load().m3_aed_memory_reset_slots(C.byref(desc), _p(state), state.numel() * state.element_size(), _i32(slots),
+                                                    slots.numel(), _stream()), "m3_aed_memory_reset_slots")
+        return
+    check(_lib.load().m3_aed_memory_reset(C.byref(desc), _p(state), state.numel() * state.element_size(), _stream()),
+          "m3_aed_memory_reset")
+
+
+def aed_memory_append(desc, state, x, n_frames):
+    """x (B * T_chunk, D) f32 rows of the chunk (a row-strided view is fine), n_frames (B,) int32 on the device: enqueue, no
+    host sync."""
+    xp, ldx = _rows(x)
+    assert x.shape[1] == desc.D and x.shape[0] % max(desc.B, 1) == 0 and n_frames.numel() == desc.B
+    check(_lib.load().m3_aed_memory_append(C.byref(desc), _p(state), state.numel() * state.element_size(), xp, ldx,
+                                           x.shape[0] // max(desc.B, 1), _i32(n_frames), _stream()), "m3_aed_memory_append")
+
+
+def aed_memory_lengths(desc, state):
+    """-> (B,) int32 on the device: rows every stream holds, -1 for a stream that ran past max_frames."""
+    n = torch.empty(desc.B, dtype=torch.int32, device=state.device)
+    check(_lib.load().m3_aed_memory_lengths(C.byref(desc), _p(state), state.numel() * state.element_size(), _p(n), _stream()),
+          "m3_aed_memory_lengths")
+    return n
+
+
+def aed_memory_gather(desc, state, slots, out=None):
+    """The listed streams' rows packed in list order: slots (n,) int32 on the device -> (out (rows, D), row0 (n + 1,) int32 on
+    the device); the first row0[n] rows of `out` are written.  out: a row-strided (rows, D) view to fill (default: a fresh
+    (n * max_frames, D) buffer, which holds whatever the streams have)."""
+    n = slots.numel()
+    if out is None:
+        out = torch.empty(n * desc.max_frames, desc.D, dtype=torch.float32, device=state.device)
+    assert out.dim() == 2 and out.shape[1] == desc.D
+    row0 = torch.empty(n + 1, dtype=torch.int32, device=state.device)
+    (op, ldo) = _rows(out) if out.shape[0] else (None, desc.D)
+    check(_lib.load().m3_aed_memory_gather(C.byref(desc), _p(state), state.numel() * state.element_size(), _i32(slots), n, op, ldo,
+                                           out.shape[0], _p(row0), _stream()), "m3_aed_memory_gather")
+    return out, row0
+
+
 # ---------------------------------------------------------------------------------------- streaming operators
 def cat_split_cache(in_cache, inp):
     """CatSplitCache plugin: (output (B, cache+input), out_cache (B, cache)); f32 or i32 rows."""

@@ -56,30 +56,32 @@ class AttentionRescorer:
         toks, hlen, score, n = source
         return toks, hlen, score, n
 
-    def _layout(self, hlen, n_hyps, mem_len, Tm):
-        """Host side of the packed rows, from ONE device-to-host read of hyp_len / n_hyps / mem_len."""
-        B, beam = hlen.shape
-        hl, nh, ml = hlen.cpu().tolist(), n_hyps.reshape(-1).cpu().tolist(), torch.as_tensor(mem_len).reshape(-1).cpu().tolist()
-        if len(ml) != B:
-            raise ValueError("rescore: %d memory lengths for %d utterances" % (len(ml), B))
+    def _layout(self, hl, nh, kv):
+        """Host side of the packed rows: hl hyp_len (B x beam lists), nh n_hyps (B), kv (first memory row, memory frames) of
+        every utterance -- all read from the device by the caller in ONE device-to-host copy."""
+        B, beam = len(hl), (len(hl[0]) if hl else 0)
         row0, self_d, src_d = [0], [], []
         for b in range(B):
             live = max(min(nh[b], beam), 0)
-            if live > 0 and not 1 <= ml[b] <= Tm:
-                # a query row with no visible key has no softmax: refuse before anything is launched
-                raise _lib.M3Error("rescore: utterance %d has %d memory frames (kv_len = 0 is rejected; the memory holds %d)"
-                                   % (b, ml[b], Tm))
             for i in range(beam):
                 nq = hl[b][i] + 1 if i < live else 0
                 if nq > self.cfg.max_len:
                     raise _lib.M3Error("rescore: a hypothesis of %d tokens exceeds the positional table (%d)" % (nq - 1, self.cfg.max_len))
                 r = row0[-1]
                 self_d.append((r, nq, r, nq, 1))
-                src_d.append((r, nq, b * Tm, ml[b] if nq else 0, 0))
+                src_d.append((r, nq, kv[b][0], kv[b][1] if nq else 0, 0))
                 row0.append(r + nq)
         i32 = lambda v: torch.tensor(v, dtype=torch.int32).to(self.device)   # noqa: E731
         max_q = max((d[1] for d in self_d), default=0)
-        return row0[-1], max_q, i32(row0), i32(self_d).view(-1, 5), i32(src_d).view(-1, 5), hl, nh
+        return row0[-1], max_q, i32(row0), i32(self_d).view(-1, 5), i32(src_d).view(-1, 5)
+
+    def _read(self, hlen, n_hyps, extra):
+        """(hyp_len lists, n_hyps list, extra list) from one device-to-host copy of the three int32 tensors"""
+        B, beam = hlen.shape
+        parts = [hlen.reshape(-1), n_hyps.reshape(-1)] + ([extra.reshape(-1).to(torch.int32)] if extra.is_cuda else [])
+        flat = torch.cat(parts).cpu().tolist()
+        hl = [flat[b * beam:(b + 1) * beam] for b in range(B)]
+        return hl, flat[B * beam:B * beam + B], (flat[B * beam + B:] if extra.is_cuda else extra.reshape(-1).tolist())
 
     # ---- one decoder over the packed rows
     def _decode(self, p, blocks, kv, kv_layer0, toks, hlen, n_hyps, row0, rows, max_q, self_d, src_d, reverse):
@@ -101,32 +103,19 @@ class AttentionRescorer:
                             ln=(w[p + "after_norm.weight"], w[p + "after_norm.bias"], LN_EPS))
         return logits, target
 
-    def rescore(self, memory, mem_len, nbest, ctc_weight=0.0, reverse_weight=0.0, raw_memory=False):
-        """memory (B, T', D) on the device: the encoder's normalised hidden states (Engine.hidden()), or with raw_memory the
-        residual stream before after_norm (Engine.hidden(normalized=False)) -- the LayerNorm then rides in the K / V GEMM's
-        prologue; mem_len (B,) valid frames; nbest: a CtcBeamSearch, or its tensors (hyp_tokens, hyp_len, hyp_score, n_hyps).
-        final = (1 - reverse_weight) att + reverse_weight r_att + ctc_weight prior.
-        -> per utterance (best tokens, [(tokens, prior, att, final)] in n-best order); an utterance without hypotheses gives
-        ((), []).  The device tensors of the call stay in self.last."""
+    def _score(self, rows_kv, raw_memory, toks, hlen, prior, n_hyps, hl, nh, kv, ctc_weight, reverse_weight):
+        """The decoder pass and the choice over memory rows (R, D): the K / V GEMM runs over exactly these rows."""
         cfg, w = self.cfg, self.w
-        if reverse_weight > 0 and cfg.r_num_blocks == 0:
-            raise _lib.M3Error("rescore: reverse_weight = %g needs a right-to-left decoder (r_num_blocks = 0)" % reverse_weight)
-        toks, hlen, prior, n_hyps = self._nbest(nbest)
-        B, beam, _ = toks.shape
-        memory = memory.to(self.device, torch.float32)
-        if memory.dim() != 3 or memory.shape[0] != B or memory.shape[2] != cfg.dim:
-            raise ValueError("rescore: memory %s for %d utterances of dim %d" % (tuple(memory.shape), B, cfg.dim))
-        Tm = int(memory.shape[1])
-        rows, max_q, row0, self_d, src_d, hl, nh = self._layout(hlen, n_hyps, mem_len, Tm)
+        B, beam = hlen.shape
+        rows, max_q, row0, self_d, src_d = self._layout(hl, nh, kv)
         logits = target = r_logits = r_target = None
         if rows > 0:
             norm = (w["after_norm.weight"], w["after_norm.bias"], LN_EPS) if raw_memory else None
-            kv = ops.linear(memory.contiguous().view(B * Tm, cfg.dim), w["decoder.src_kv_all.weight"], w["decoder.src_kv_all.bias"],
-                            ln=norm)
+            kvp = ops.linear(rows_kv, w["decoder.src_kv_all.weight"], w["decoder.src_kv_all.bias"], ln=norm)
             args = (toks, hlen, n_hyps, row0, rows, max_q, self_d, src_d)
-            logits, target = self._decode("decoder.", cfg.num_blocks, kv, 0, *args, reverse=False)
+            logits, target = self._decode("decoder.", cfg.num_blocks, kvp, 0, *args, reverse=False)
             if reverse_weight > 0:
-                r_logits, r_target = self._decode("decoder.right.", cfg.r_num_blocks, kv, cfg.num_blocks, *args, reverse=True)
+                r_logits, r_target = self._decode("decoder.right.", cfg.r_num_blocks, kvp, cfg.num_blocks, *args, reverse=True)
         else:
             logits = torch.empty(0, cfg.vocab, dtype=torch.float32, device=self.device)
         att, r_att, final, best = ops.aed_score(logits, target, row0, n_hyps, B, beam, prior=prior, ctc_weight=ctc_weight,
@@ -139,3 +128,65 @@ class AttentionRescorer:
                     for i in range(max(min(nh[b], beam), 0))]
             out.append((hyps[best_h[b]][0] if best_h[b] >= 0 else (), hyps))
         return out
+
+    def _check_weights(self, reverse_weight):
+        if reverse_weight > 0 and self.cfg.r_num_blocks == 0:
+            raise _lib.M3Error("rescore: reverse_weight = %g needs a right-to-left decoder (r_num_blocks = 0)" % reverse_weight)
+
+    def rescore(self, memory, mem_len, nbest, ctc_weight=0.0, reverse_weight=0.0, raw_memory=False):
+        """memory (B, T', D) on the device: the encoder's normalised hidden states (Engine.hidden()), or with raw_memory the
+        residual stream before after_norm (Engine.hidden(normalized=False)) -- the LayerNorm then rides in the K / V GEMM's
+        prologue; mem_len (B,) valid frames; nbest: a CtcBeamSearch, or its tensors (hyp_tokens, hyp_len, hyp_score, n_hyps).
+        final = (1 - reverse_weight) att + reverse_weight r_att + ctc_weight prior.
+        -> per utterance (best tokens, [(tokens, prior, att, final)] in n-best order); an utterance without hypotheses gives
+        ((), []).  The device tensors of the call stay in self.last."""
+        cfg = self.cfg
+        self._check_weights(reverse_weight)
+        toks, hlen, prior, n_hyps = self._nbest(nbest)
+        B, beam, _ = toks.shape
+        memory = memory.to(self.device, torch.float32)
+        if memory.dim() != 3 or memory.shape[0] != B or memory.shape[2] != cfg.dim:
+            raise ValueError("rescore: memory %s for %d utterances of dim %d" % (tuple(memory.shape), B, cfg.dim))
+        Tm = int(memory.shape[1])
+        mem_len = torch.as_tensor(mem_len).reshape(-1)
+        if mem_len.numel() != B:
+            raise ValueError("rescore: %d memory lengths for %d utterances" % (mem_len.numel(), B))
+        hl, nh, ml = self._read(hlen, n_hyps, mem_len)
+        for b in range(B):
+            if min(nh[b], beam) > 0 and not 1 <= ml[b] <= Tm:
+                # a query row with no visible key has no softmax: refuse before anything is launched
+                raise _lib.M3Error("rescore: utterance %d has %d memory frames (kv_len = 0 is rejected; the memory holds %d)"
+                                   % (b, ml[b], Tm))
+        return self._score(memory.contiguous().view(B * Tm, cfg.dim), raw_memory, toks, hlen, prior, n_hyps, hl, nh,
+                           [(b * Tm, ml[b]) for b in range(B)], ctc_weight, reverse_weight)
+
+    def rescore_rows(self, rows, row0, nbest, streams=None, ctc_weight=0.0, reverse_weight=0.0, raw_memory=True):
+        """Rescore the listed streams of a search over PACKED memory rows (streaming two-pass decoding).
+        rows (>= R, D) on the device, row0 (n + 1,) int32 on the device as m3_aed_memory_gather leaves them: listed stream j
+        owns rows [row0[j], row0[j + 1]), R = row0[n]; raw_memory: the rows are the residual stream before after_norm (what
+        the store keeps).  streams: the n streams of `nbest` the rows belong to, in that order (default: all of them).  The
+        K / V GEMM runs over the R rows only.  A listed stream with hypotheses but no memory row (it was closed before its
+        first chunk, or its store overflowed) is not an error: its result is ((), []), as for a stream without hypotheses.
+        -> per LISTED stream what rescore() returns per utterance; self.last holds the listed streams' tensors."""
+        cfg = self.cfg
+        self._check_weights(reverse_weight)
+        toks, hlen, prior, n_hyps = self._nbest(nbest)
+        if streams is not None:
+            streams = [int(b) for b in streams]
+            if any(not 0 <= b < toks.shape[0] for b in streams):
+                raise ValueError("rescore_rows: streams %s outside [0, %d)" % (streams, toks.shape[0]))
+            sel = torch.tensor(streams, dtype=torch.int64).to(self.device)
+            toks, hlen, prior, n_hyps = (t.index_select(0, sel).contiguous() for t in (toks, hlen, prior, n_hyps))
+        n, beam, _ = toks.shape
+        if rows.dim() != 2 or rows.shape[1] != cfg.dim or not rows.is_contiguous() or row0.numel() != n + 1:
+            raise ValueError("rescore_rows: rows %s / row0 (%d,) for %d streams of dim %d" % (tuple(rows.shape), row0.numel(), n, cfg.dim))
+        hl, nh, r0 = self._read(hlen, n_hyps, row0)
+        if r0[0] != 0 or any(a > b for a, b in zip(r0, r0[1:])) or r0[-1] > rows.shape[0]:
+            raise _lib.M3Error("rescore_rows: row0 = %s does not describe %d packed rows" % (r0, rows.shape[0]))
+        kv = [(r0[j], r0[j + 1] - r0[j]) for j in range(n)]
+        dead = [j for j in range(n) if nh[j] > 0 and kv[j][1] == 0]
+        if dead:                      # hypotheses without memory: the stream counts as one without hypotheses
+            for j in dead:
+                nh[j] = 0
+            n_hyps = torch.tensor(nh, dtype=torch.int32).to(self.device)
+        return self._score(rows[:r0[-1]], raw_memory, toks, hlen, prior, n_hyps, hl, nh, kv, ctc_weight, reverse_weight)

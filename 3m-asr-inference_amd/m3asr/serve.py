@@ -23,6 +23,11 @@ Segmenting, `StreamPool(decoder, segment=True)` over a decoder with an endpoint 
 which live sessions' utterances are over, files each one's n-best as a `Segment` (`pool.segments(sid)`) and restarts the
 slot, so a session may stay open for any length of time inside a state sized for `max_frames`.
 
+Two passes, `StreamPool(decoder, segment=True, rescore=True)` over a decoder with a rescorer
+(StreamingCtcDecoder(..., endpoint=..., rescorer=AttentionRescorer(...))): when utterances end, ONE attention-decoder pass
+rescores the n-best of all of them over the encoder memory the decoder kept per slot, and each is filed as a
+`RescoredSegment`; `pool.close(sid, rescored=True)` does the same for the open segment.
+
 The window rule is the one StreamingEncoder.decode applies to whole utterances (window n of a stream starts at its input
 frame 4 c n, holds 4 c + 3 frames, overlaps the next by 3; fewer than 7 real frames count as none).  It lives in
 `next_window_valid` / `WindowBuffer`, host-only code.
@@ -37,6 +42,10 @@ from . import _lib
 # where its first and behind its last non-blank frame lie in the SESSION (the whole segment when no frame's argmax was a
 # token); nbest: [(prefix, score)] best first, as close() returns; end_frame: the session's output frame at which the rule fired.
 Segment = collections.namedtuple("Segment", "rule start_ms end_ms nbest end_frame")
+# The same of a pool with rescore=True: the five fields of Segment, then best: the token tuple the attention decoder chose;
+# scores: [(tokens, prior, att, final)] in n-best order (AttentionRescorer.rescore's pair).  Its memory is exactly the frames
+# the n-best was searched over: the frames of the firing chunk behind the endpoint included.
+RescoredSegment = collections.namedtuple("RescoredSegment", "rule start_ms end_ms nbest end_frame best scores")
 
 
 def next_window_valid(buffered, chunks_done, chunk, ended):
@@ -129,10 +138,19 @@ class StreamPool:
     window -- it sees the three frames of overlap again but no encoder history from before.  segments(sid) hands out the
     finished segments, close(sid) the n-best of the open one, offset_ms(sid) where the open one starts.  With a rule that
     bounds an utterance's length (the default third rule) no slot reaches max_frames; that needs min_length + c <= max_frames
-    (max_frames is read from `decoder.st` unless given)."""
+    (max_frames is read from `decoder.st` unless given).
 
-    def __init__(self, decoder, B=None, chunk=None, input_dim=None, audio=False, fbank=None, segment=False, max_frames=None):
+    rescore=True: two-pass decoding.  The decoder needs a rescorer (`decoder.rescorer`, `decoder.rescore(slots=[...],
+    detail=True)`).  With segment=True all slots whose rule fired in a step are rescored by ONE decoder.rescore call before
+    they are restarted, and segments(sid) hands out RescoredSegments; close(sid, rescored=True) rescores the open segment."""
+
+    def __init__(self, decoder, B=None, chunk=None, input_dim=None, audio=False, fbank=None, segment=False, max_frames=None,
+                 rescore=False):
         self.dec = decoder
+        self.rescore = bool(rescore)
+        if self.rescore and (getattr(decoder, "rescorer", None) is None or not hasattr(decoder, "rescore")):
+            raise _lib.M3Error("StreamPool(rescore=True) needs a decoder with a rescorer: "
+                               "StreamingCtcDecoder(..., rescorer=AttentionRescorer(...))")
         st = getattr(decoder, "st", None)
         if st is not None and not getattr(st, "independent", False):
             raise _lib.M3Error("StreamPool needs a slot-mode encoder: engine.streaming(B, max_frames, independent=True)")
@@ -259,16 +277,21 @@ class StreamPool:
     def _cut(self, live):
         """segment=True, after the engine call: end the utterance of every live session whose endpoint rule fired."""
         slots = [self.streams[sid][0] for sid in live]
-        for sid, b, info in zip(live, slots, self.dec.endpoints(slots=slots)):
-            if not info.rule:
-                continue
+        fired = [(sid, b, info) for sid, b, info in zip(live, slots, self.dec.endpoints(slots=slots)) if info.rule]
+        if not fired:
+            return
+        # two passes: one decoder pass over everything that ended in this step, before any of the slots is restarted
+        second = self.dec.rescore(slots=[b for _, b, _ in fired], detail=True) if self.rescore else None
+        for j, (sid, b, info) in enumerate(fired):
             nbest = self.dec.finish(slots=[b])[0]
             buf, off = self.streams[sid][1], self.offset[sid]
             if nbest and len(nbest[0][0]) > 0:
                 first = info.first_speech if info.first_speech >= 0 else 0
                 last = info.last_speech if info.last_speech >= 0 else info.frame
-                self.finished[sid].append(Segment(info.rule, (off + first) * self.frame_ms, (off + last + 1) * self.frame_ms,
-                                                  nbest, off + info.frame))
+                seg = Segment(info.rule, (off + first) * self.frame_ms, (off + last + 1) * self.frame_ms, nbest, off + info.frame)
+                if second is not None:
+                    seg = RescoredSegment(*seg, tuple(second[j][0]), second[j][1])
+                self.finished[sid].append(seg)
             self.offset[sid] = off + buf.chunks * self.c
             self.dec.reset(slots=[b])
             buf.rebase()
@@ -326,11 +349,19 @@ class StreamPool:
         best, greedy = self.dec.partial(slots=[b])
         return best[0], greedy[0]
 
-    def close(self, sid):
+    def close(self, sid, rescored=False):
         """n-best [(prefix, score)] of what the stream has decoded (segment=True: of its open segment; read segments(sid)
-        first, the finished ones go with the session); the slot is free again."""
+        first, the finished ones go with the session); the slot is free again.
+        rescored=True (rescore=True): instead the second pass's pair for it, (best tokens, [(tokens, prior, att, final)]);
+        ((), []) when nothing was decoded."""
         b = self.slot_of(sid)
-        nbest = self.dec.finish(slots=[b])[0]
+        if rescored:
+            if not self.rescore:
+                raise _lib.M3Error("StreamPool.close(rescored=True): this pool does not rescore, build it with rescore=True")
+            best, scores = self.dec.rescore(slots=[b], detail=True)[0]
+            nbest = (tuple(best), scores)
+        else:
+            nbest = self.dec.finish(slots=[b])[0]
         del self.streams[sid]
         if self.segment:
             del self.offset[sid], self.finished[sid]

@@ -820,6 +820,44 @@ int m3_aed_score(const float* logits, int ldl, const float* r_logits, int ldrl, 
                  float ctc_weight, float reverse_weight, float* row_logp, float* att, float* r_att, float* final_score,
                  int32_t* best, m3_stream stream);
 
+/* Streaming two-pass decoding: the encoder memory of B live streams, kept per slot on the device so that a stream's n-best can
+ * be rescored when its utterance ends (csrc/aed_memory.hip).  One state blob per streaming decoder, caller-owned
+ * device memory of m3_aed_memory_state_size bytes (16-byte aligned; 0 and m3_last_error for a descriptor the library
+ * rejects: D a multiple of 4, B and max_frames >= 0).  Per slot it holds max_frames rows of D fp32 and two words, the rows
+ * held (len) and a status.  The rows are COPIES of the residual stream before after_norm (the chunk binding's buffer "x"):
+ * the rescorer applies after_norm in the prologue of its K / V GEMM, so nothing is normalised here.  All calls of one state
+ * are enqueued on one stream; none synchronises with the host.  Row loads and stores are 16 bytes wide, there are no atomics.
+ * BOUNDARY RULE: the memory of an utterance is exactly the frames its n-best was searched over -- the caller appends with
+ * the same n_frames the beam search advances by, the frames of an endpoint's firing chunk behind the endpoint included.
+ * m3_aed_memory_reset / _reset_slots: len = 0, status cleared, for all B slots or for the n slots listed in `slots` (device
+ *   int32[n], entries outside [0, B) skipped).  Only the words are cleared: no kernel reads a row the slot's current stream
+ *   has not written.
+ * m3_aed_memory_append: x [B * T_chunk][ldx], rows b * T_chunk + t with t < clamp(n_frames[b], 0, T_chunk) go to positions
+ *   len[b] + t of slot b, then len[b] moves (n_frames [B] int32 on the device).  A slot with 0 frames keeps its words and rows
+ *   exactly as they are.  A slot that would pass max_frames consumes nothing and its status is set until the slot is reset
+ *   (the convention of m3_ctc_greedy_stream_advance).  One work-group per slot reads the words once, copies, passes a barrier
+ *   and then moves the length.  ldx >= D and a multiple of 4, x 16-byte aligned, T_chunk <= 2^14.
+ * m3_aed_memory_lengths: len [B] = rows slot b holds, -1 for a slot whose status is set.
+ * m3_aed_memory_gather: the valid rows of the n slots listed in `slots` (device int32[n], n <= 65535) packed one after the
+ *   other in list order into out [out_rows][ldo]; out_row0 [n + 1] = the prefix sums of their lengths.  A failed slot and an
+ *   entry outside [0, B) contribute 0 rows.  Rows at or past out_rows are not written (out_row0 still tells the full sums, so
+ *   n * max_frames rows always suffice); rows past out_row0[n] are not touched.  ldo >= D and a multiple of 4, out 16-byte
+ *   aligned. */
+typedef struct m3_aed_memory_desc {
+  int32_t B;
+  int32_t max_frames;
+  int32_t D;
+} m3_aed_memory_desc;
+size_t m3_aed_memory_state_size(const m3_aed_memory_desc* desc);
+int m3_aed_memory_reset(const m3_aed_memory_desc* desc, void* state, size_t state_bytes, m3_stream stream);
+int m3_aed_memory_reset_slots(const m3_aed_memory_desc* desc, void* state, size_t state_bytes, const int32_t* slots, int n,
+                              m3_stream stream);
+int m3_aed_memory_append(const m3_aed_memory_desc* desc, void* state, size_t state_bytes, const float* x, int ldx, int T_chunk,
+                         const int32_t* n_frames, m3_stream stream);
+int m3_aed_memory_lengths(const m3_aed_memory_desc* desc, const void* state, size_t state_bytes, int32_t* len, m3_stream stream);
+int m3_aed_memory_gather(const m3_aed_memory_desc* desc, const void* state, size_t state_bytes, const int32_t* slots, int n,
+                         float* out, int ldo, int out_rows, int32_t* out_row0, m3_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

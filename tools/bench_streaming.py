@@ -2,7 +2,7 @@
 """Chunk-by-chunk decoding (m3_engine_forward_chunk) timed: latency of one chunk step and the real-time factor it implies.
 
   python tools/bench_streaming.py [--chunk 16] [--left-chunks 4] [--batch 1] [--weight-dtype f32] [--seconds 20] [--beam N]
-                                  [--independent [--stagger N]] [--audio] [--lm [N_NGRAMS]]
+                                  [--independent [--stagger N]] [--audio] [--lm [N_NGRAMS]] [--rescore]
 
 18L x 32e encoder with causal conv modules in both encoders, static_chunk_size = chunk (output frames; one chunk = 4 x chunk
 input frames of 10 ms), synthetic weights and features.  Every step after the first is a hipGraph replay (the chunk counter
@@ -14,6 +14,11 @@ on the engine stream behind the chunk forward) and add "decode_ms_per_chunk" to 
 --lm [N] (with --beam): after the plain pass the same chunks are decoded again with a synthetic trigram LM of about N n-grams
 (default 100000; tools/lm_synth.py) fused into the beam search (StreamingCtcDecoder(lm=), with the --context graph if given):
 "lm" carries its "decode_ms_per_chunk" next to the plain one and their ratio.
+--rescore (with --beam): two-pass decoding (StreamingCtcDecoder(rescorer=)) with a random attention decoder
+of 6 blocks (D = the encoder's, F = 2048, 8 heads).  Every timed step also appends the chunk's residual stream to the per-slot
+encoder memory: "append_ms_per_chunk" is that launch alone, "ms_per_chunk_with_append" the chunk forward plus it.  Afterwards
+stream 0 is decoded for 125 output frames and ONE dec.rescore(slots=[0]) call is timed with a host clock around it (gather,
+the device-to-host reads, the decoder pass, the result lists): "rescore" carries its ms next to the chunk's.
 --independent: slot mode (m3_engine_forward_chunk_slots), every stream with its own position; --stagger N: stream b starts N
 steps after stream b - 1 and ends as many steps later (idle slots before and after).  The line then also carries "mode" and
 the mean number of live slots per timed step.
@@ -54,9 +59,12 @@ def main():
     ap.add_argument("--independent", action="store_true", help="slot mode: every stream has its own chunk counter")
     ap.add_argument("--stagger", type=int, default=0, help="slot mode: stream b starts this many steps after stream b - 1")
     ap.add_argument("--audio", action="store_true", help="also time the chunks fed samples through the log-Mel front end")
+    ap.add_argument("--rescore", action="store_true", help="with --beam: keep the encoder memory per slot and time one rescoring call")
     args = ap.parse_args()
     if args.stagger and not args.independent:
         ap.error("--stagger needs --independent")
+    if args.rescore and args.beam <= 0:
+        ap.error("--rescore needs --beam")
     cfg = EncoderConfig(num_blocks=args.layers, causal=True, embed_causal=True, static_chunk_size=args.chunk,
                         num_decoding_left_chunks=args.left_chunks, weight_dtype=args.weight_dtype)
     w = make_weights(cfg, seed=0)
@@ -78,9 +86,20 @@ def main():
             while len(phrases) < args.context:
                 phrases.add(tuple(int(t) for t in prng.integers(1, cfg.output_dim, int(prng.integers(2, 7)))))
             ctx = ContextSet([ContextGraph([list(p) for p in sorted(phrases)], cfg.output_dim)], device=eng.device)
-        dec = StreamingCtcDecoder(st, args.beam, context=ctx)
+        rescorer = None
+        if args.rescore:
+            from m3asr.config import DecoderConfig
+            from m3asr.plan import pack_decoder
+            from m3asr.rescore import AttentionRescorer
+            from m3asr.weights import make_decoder_weights
+            dcfg = DecoderConfig(vocab=cfg.output_dim, dim=cfg.attention_dim, heads=8, linear_units=2048, num_blocks=6)
+            sd = dict(make_decoder_weights(dcfg, seed=0))
+            sd.update({n: w[n] for n in ("after_norm.weight", "after_norm.bias")})
+            rescorer = AttentionRescorer(pack_decoder(sd, dcfg), dcfg, eng.device)
+        dec = StreamingCtcDecoder(st, args.beam, context=ctx, rescorer=rescorer)
         n_out = torch.full((args.batch,), args.chunk, dtype=torch.int32, device=eng.device)
-    times, dtimes, live = [], [], []
+    times, dtimes, mtimes, live = [], [], [], []
+    mem_x = None
     for rep in range(3):
         if dec is not None:
             dec.reset(graph_ids=None if dec.context is None else [0] * args.batch)
@@ -96,7 +115,7 @@ def main():
                     live.append(int(on.sum()))
             elif rep > 0:
                 live.append(args.batch)
-            e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            e0, e1, e2, e3 = (torch.cuda.Event(enable_timing=True) for _ in range(4))
             e0.record(eng.stream)
             st.step(win, valid)
             e1.record(eng.stream)
@@ -105,10 +124,17 @@ def main():
                     dec.beam.advance(st.logits, n_out, eng.stream)
                     ops.ctc_greedy_stream_advance(dec.gdesc, dec.gstate, st.logits, n_out, dec.frame_ids)
             e2.record(eng.stream)
-            e2.synchronize()
+            if args.rescore:
+                if mem_x is None:
+                    mem_x = st.buffer("x").view(-1, cfg.attention_dim)
+                with torch.cuda.stream(eng.stream):
+                    ops.aed_memory_append(dec.mdesc, dec.mstate, mem_x, n_out)
+            e3.record(eng.stream)
+            e3.synchronize()
             if rep > 0:
                 times.append(e0.elapsed_time(e1))
                 dtimes.append(e1.elapsed_time(e2))
+                mtimes.append(e2.elapsed_time(e3))
     t = np.sort(np.array(times))
     audio_s = 4 * args.chunk * 0.01
     p50 = float(np.median(t))
@@ -158,6 +184,35 @@ def main():
             out["context_phrases"] = args.context
         out["decode_ms_per_chunk"] = {"beam": args.beam, "p50": round(float(np.median(d)), 4),
                                       "p99": round(float(d[int(0.99 * (len(d) - 1))]), 4), "min": round(float(d[0]), 4)}
+    if args.rescore:
+        import time
+        m = np.array(mtimes)
+        both = np.array(times) + m
+        out["append_ms_per_chunk"] = {"p50": round(float(np.median(m)), 4), "p99": round(float(np.sort(m)[int(0.99 * (len(m) - 1))]), 4),
+                                      "min": round(float(m.min()), 4)}
+        out["ms_per_chunk_with_append"] = {"p50": round(float(np.median(both)), 4), "min": round(float(both.min()), 4)}
+        out["memory_state_MB"] = round(dec.mstate.numel() / 2 ** 20, 1)
+        # endpoint latency: stream 0 after 125 output frames, one rescoring call end to end
+        frames, per = 125, []
+        dec.reset(graph_ids=None if dec.context is None else [0] * args.batch)
+        full = torch.full((args.batch,), st.window, dtype=torch.int32, device=eng.device)
+        for n in range(-(-frames // args.chunk)):
+            cnt = torch.full((args.batch,), min(args.chunk, frames - n * args.chunk), dtype=torch.int32)
+            dec.step(win, full, cnt)
+        eng.stream.synchronize()
+        for rep in range(12):
+            t0 = time.perf_counter()
+            res = dec.rescore(slots=[0], detail=True)
+            eng.stream.synchronize()
+            if rep >= 2:
+                per.append((time.perf_counter() - t0) * 1e3)
+        hyps = res[0][1]
+        out["rescore"] = {"ms_per_call": {"p50": round(float(np.median(per)), 3), "min": round(min(per), 3), "max": round(max(per), 3),
+                                          "n": len(per)},
+                          "memory_frames": int(dec.memory_lengths()[0]), "hypotheses": len(hyps),
+                          "decoder_rows": sum(len(h[0]) + 1 for h in hyps), "decoder_blocks": rescorer.cfg.num_blocks,
+                          "dim": rescorer.cfg.dim, "vocab": rescorer.cfg.vocab, "beam": args.beam,
+                          "chunk_ms_p50": out["ms_per_chunk"]["p50"]}
     if dec is not None and args.lm is not None:
         from lm_synth import synthetic_lm
         from m3asr.decode import StreamingCtcDecoder

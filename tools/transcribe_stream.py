@@ -5,12 +5,19 @@ as soon as the step that ended it returns:
 
     python tools/transcribe_stream.py -p encoder.plan -w speech.wav [--hotwords words.txt] [--lm lm.arpa] [--beam 10]
                                       [--blank-threshold 0.8] [--rule must_decoded,trailing_ms,length_ms ...]
+                                      [--rescore [--ctc-weight 0.5] [--reverse-weight 0.0]]
 
     <start ms>-<end ms> rule <r>: <token ids of the best hypothesis>
+    <start ms>-<end ms> rule <r> rescored: att=<a> final=<f> tokens=<token ids the attention decoder chose>      (--rescore)
+
+--rescore: two-pass decoding.  The plan must come from a joint CTC/attention checkpoint (builder.py packs the decoder when the
+checkpoint has one); the decoder keeps every session's encoder memory on the device and the plan's attention decoder rescores
+a segment's n-best when its utterance ends (StreamPool(rescore=True)).
 
 The plan must be a streaming one (static_chunk_size > 0, causal conv modules).  speech.wav is 16 kHz mono 16-bit PCM.  The
 last line (rule 0) is what was still open when the file ended.  --synthetic N pushes N seconds of a generated signal instead
-of a file (no plan either: a small random streaming model), to see the mechanics on a machine without a model."""
+of a file (no plan either: a small random streaming model, with --rescore plus a small random attention decoder), to see
+the mechanics on a machine without a model."""
 import argparse
 import os
 import sys
@@ -27,6 +34,14 @@ from m3asr.serve import StreamPool
 PIECE = 1600          # 100 ms of samples
 
 
+def rescored(best, scores):
+    """att=<a> final=<f> tokens=<ids> of the hypothesis the second pass chose (nothing decoded: the scores are missing)"""
+    chosen = next((h for h in scores if tuple(h[0]) == tuple(best)), None)
+    if chosen is None:
+        return "att=nan final=nan tokens="
+    return "att=%.4f final=%.4f tokens=%s" % (chosen[2], chosen[3], " ".join(str(t) for t in best))
+
+
 def read_wav(path):
     import wave
     with wave.open(path, "rb") as w:
@@ -37,21 +52,43 @@ def read_wav(path):
 
 
 def load_engine(a):
+    """-> (engine, AttentionRescorer or None)"""
     if a.synthetic:
-        from m3asr.config import EncoderConfig
+        from m3asr.config import DecoderConfig, EncoderConfig
         from m3asr.engine import Engine
-        from m3asr.weights import make_weights
+        from m3asr.weights import make_decoder_weights, make_weights
         cfg = EncoderConfig(num_blocks=2, embed_blocks=2, causal=True, embed_causal=True, static_chunk_size=16,
                             num_decoding_left_chunks=2)
-        return Engine.from_state_dict(cfg, make_weights(cfg, seed=0), packed_rows=False)
+        w = make_weights(cfg, seed=0)
+        eng, rescorer = Engine.from_state_dict(cfg, w, packed_rows=False), None
+        if a.rescore:
+            from m3asr.plan import pack_decoder
+            from m3asr.rescore import AttentionRescorer
+            dcfg = DecoderConfig(vocab=cfg.output_dim, dim=cfg.attention_dim, heads=cfg.attention_heads, linear_units=256,
+                                 num_blocks=2, r_num_blocks=1 if a.reverse_weight > 0 else 0)
+            sd = dict(make_decoder_weights(dcfg, seed=0))
+            sd.update({n: w[n] for n in ("after_norm.weight", "after_norm.bias")})      # the encoder's own final LayerNorm
+            rescorer = AttentionRescorer(pack_decoder(sd, dcfg), dcfg, eng.device)
+        return eng, rescorer
     import trt_helper
     from trt_helper import trt
-    return trt_helper.InferHelper(a.plan_name, trt_helper.init_trt_plugin(trt.Logger.INFO, "libm3asr_hip.so")).engine
+    helper = trt_helper.InferHelper(a.plan_name, trt_helper.init_trt_plugin(trt.Logger.INFO, "libm3asr_hip.so"))
+    rescorer = None
+    if a.rescore:
+        from m3asr.plan import decoder_config_of
+        from m3asr.rescore import AttentionRescorer
+        dcfg = decoder_config_of(helper.extra)
+        if dcfg is None:
+            raise SystemExit("%s: --rescore needs a plan with an attention decoder (build it from a CTC/attention checkpoint)" % a.plan_name)
+        rescorer = AttentionRescorer(helper.decoder_packed, dcfg, helper.engine.device)
+    return helper.engine, rescorer
 
 
 def main(a):
-    eng = load_engine(a)
+    eng, rescorer = load_engine(a)
     V, kw = eng.cfg.output_dim, {}
+    if rescorer is not None:
+        kw.update(rescorer=rescorer, ctc_weight=a.ctc_weight, reverse_weight=a.reverse_weight)
     if a.hotwords:
         from m3asr.context import ContextGraph, ContextSet, read_phrases
         kw["context"] = ContextSet([ContextGraph(read_phrases(a.hotwords), V, score=a.hotword_score)], device=eng.device)
@@ -64,7 +101,7 @@ def main(a):
     bound = ep.length_bound()
     max_frames = a.max_frames or (bound if bound is not None else 2000) + eng.cfg.static_chunk_size
     dec = StreamingCtcDecoder(eng.streaming(1, max_frames, independent=True), beam=a.beam, endpoint=ep, **kw)
-    pool = StreamPool(dec, audio=True, segment=True)
+    pool = StreamPool(dec, audio=True, segment=True, rescore=rescorer is not None)
     if a.synthetic:
         rng = np.random.default_rng(1)
         pcm = np.clip(np.cumsum(rng.normal(0, 1, int(16000 * a.synthetic))) * 50 % 20000 - 10000, -32768, 32767).astype(np.int16)
@@ -75,6 +112,8 @@ def main(a):
     def show():
         for s in pool.segments(sid):
             print("%d-%d ms rule %d: %s" % (s.start_ms, s.end_ms, s.rule, " ".join(str(t) for t in s.nbest[0][0])), flush=True)
+            if rescorer is not None:
+                print("%d-%d ms rule %d rescored: %s" % (s.start_ms, s.end_ms, s.rule, rescored(s.best, s.scores)), flush=True)
 
     for pos in range(0, len(pcm), PIECE):
         pool.push_audio(sid, torch.from_numpy(pcm[pos:pos + PIECE].copy()))
@@ -84,8 +123,13 @@ def main(a):
     while pool.step():
         show()
     start = pool.offset_ms(sid)
-    rest = pool.close(sid)
-    print("%d- ms rule 0: %s" % (start, " ".join(str(t) for t in rest[0][0]) if rest else ""))
+    if rescorer is None:
+        rest = pool.close(sid)
+        print("%d- ms rule 0: %s" % (start, " ".join(str(t) for t in rest[0][0]) if rest else ""))
+    else:
+        best, scores = pool.close(sid, rescored=True)
+        print("%d- ms rule 0: %s" % (start, " ".join(str(t) for t in scores[0][0]) if scores else ""))
+        print("%d- ms rule 0 rescored: %s" % (start, rescored(best, scores)))
     print("%d engine steps, %.1f s of audio" % (pool.steps, len(pcm) / 16000.0))
 
 
@@ -105,6 +149,9 @@ if __name__ == "__main__":
     p.add_argument("--units", help="`token id` per line: the ARPA's words as token ids.")
     p.add_argument("--lm-weight", type=float, default=0.5)
     p.add_argument("--length-bonus", type=float, default=0.0)
+    p.add_argument("--rescore", action="store_true", help="Two passes: the attention decoder rescores every segment's n-best.")
+    p.add_argument("--ctc-weight", type=float, default=0.5, help="--rescore: weight of the first-pass score in the final score.")
+    p.add_argument("--reverse-weight", type=float, default=0.0, help="--rescore: weight of the right-to-left decoder.")
     args = p.parse_args()
     if args.wav_file and not args.plan_name:
         p.error("-w needs -p")
