@@ -74,6 +74,10 @@ class AedMemoryDesc(C.Structure):  # m3_aed_memory_desc
     _fields_ = [("B", C.c_int32), ("max_frames", C.c_int32), ("D", C.c_int32)]
 
 
+class AedSearchDesc(C.Structure):  # m3_aed_search_desc
+    _fields_ = [(n, C.c_int32) for n in ("B", "beam", "max_steps", "V", "D", "H", "layers", "pe_rows")]
+
+
 class WeightEntry(C.Structure):  # m3_weight_entry
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64), ("dtype", C.c_int32)]
 
@@ -240,6 +244,13 @@ SIGNATURES = {
     "m3_aed_memory_append": (_i, [_P(AedMemoryDesc), _vp, _sz, _vp, _i, _i, _vp, _vp]),
     "m3_aed_memory_lengths": (_i, [_P(AedMemoryDesc), _vp, _sz, _vp, _vp]),
     "m3_aed_memory_gather": (_i, [_P(AedMemoryDesc), _vp, _sz, _vp, _i, _vp, _i, _i, _vp, _vp]),
+    "m3_aed_search_state_size": (_sz, [_P(AedSearchDesc)]),
+    "m3_aed_search_cache_size": (_sz, [_P(AedSearchDesc)]),
+    "m3_aed_search_reset": (_i, [_P(AedSearchDesc), _vp, _sz, _vp, _vp, _i, _vp]),
+    "m3_aed_search_embed": (_i, [_P(AedSearchDesc), _vp, _sz, _vp, _vp, _vp, _i, _vp]),
+    "m3_aed_search_attention": (_i, [_P(AedSearchDesc), _vp, _sz, _vp, _i, _vp, _i, _i, _vp, _sz, _i, _vp, _i, _vp]),
+    "m3_aed_search_prune": (_i, [_P(AedSearchDesc), _vp, _sz, _vp, _i, _vp, _vp]),
+    "m3_aed_search_result": (_i, [_P(AedSearchDesc), _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

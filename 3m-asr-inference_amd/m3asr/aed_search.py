@@ -1,0 +1,187 @@
+"""Attention decoding on the device: the AED decoder searching on its own, autoregressively, with a beam (the reference's
+decoding mode `attention`; the per-step decoder is layer/att_decoder.py:258-299 forward_one_step, a bidirectional decoder
+searches with its left decoder only, att_decoder.py:389-411; the step's two helpers are utils/mask.py:205-251).  The contract
+is restated in tests/aed_search_ref.py; DESIGN.md 21 has the design.
+
+    rescorer = AttentionRescorer(packed, decoder_config_of(extra), device)        # the uploaded decoder weights
+    search = AttentionBeamSearch(rescorer, B, beam, max_steps)
+    best = search.search(engine.hidden(), out_lens)                               # a token list per utterance
+
+R = B * beam hypothesis rows take one new token per step.  A step is ALWAYS the same launches with the same arguments --
+m3_aed_search_embed, per block eight launches (fused QKV GEMM with the norm1 prologue, self-attention over the K / V cache,
+linear_out with the residual, the source attention's Q GEMM with norm2, source attention over the memory's K / V projection,
+linear_out with the residual, the two FFN GEMMs), the output layer with after_norm, m3_aed_search_prune: 8 L + 3 -- because the
+position, who is finished and which utterance is done live in the device state.  The host enqueues steps without
+synchronising and reads the B done flags in one small copy every `poll` steps; steps issued past an utterance's end are
+no-ops for it.  The (R, V) log-probabilities never leave the device.  There is no torch fallback.
+
+Memory: the self-attention K / V cache holds num_blocks * max_steps * B * beam * 2 * dim floats (6 blocks, 125 steps, 16 x 10
+rows, dim 512: 0.49 GB) -- it is sized from max_steps, so give the constructor the bound you need, not the table's length."""
+import torch
+
+from . import _lib, ops
+from .rescore import LN_EPS
+
+
+class AttentionBeamSearch:
+    def __init__(self, rescorer, B, beam, max_steps, poll=8, use_graph=False):
+        """rescorer: the AttentionRescorer whose uploaded weights and config the search shares; B utterances per call, `beam`
+        hypotheses each (1 <= beam <= min(64, vocab)); max_steps: the most tokens a hypothesis can get (it sizes the state and
+        the K / V cache, see the module docstring; more than max_len - 1 steps are never taken).  poll: steps between two reads of
+        the done flags.  use_graph: capture the step once with torch.cuda.graph and replay it (the step is a straight line of
+        launches whose arguments never change); off by default: the A/B in DESIGN.md 21 shows no gain.  The first graph call
+        of an object pays one extra eager step, a synchronisation and the capture.
+        Raises M3Error before anything is allocated for a beam or a head size the kernels do not take."""
+        cfg = rescorer.cfg
+        self.rescorer, self.cfg, self.device = rescorer, cfg, rescorer.device
+        self.B, self.beam, self.poll, self.use_graph = int(B), int(beam), max(int(poll), 1), bool(use_graph)
+        if self.beam < 1 or self.beam > cfg.vocab or self.beam > 64:
+            raise _lib.M3Error("AttentionBeamSearch: beam = %d, need 1 <= beam <= min(64, vocab = %d)" % (self.beam, cfg.vocab))
+        if int(max_steps) < 1:
+            raise _lib.M3Error("AttentionBeamSearch: max_steps = %d, need at least 1" % int(max_steps))
+        self.max_steps = min(int(max_steps), cfg.max_len - 1)
+        self.desc = ops.aed_search_desc(self.B, self.beam, self.max_steps, cfg.vocab, cfg.dim, cfg.heads, cfg.num_blocks, cfg.max_len)
+        R, D, dev = self.B * self.beam, cfg.dim, self.device
+        f32 = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=dev)   # noqa: E731
+        self.state = torch.zeros(ops.aed_search_state_size(self.desc), dtype=torch.uint8, device=dev)
+        self.cache = torch.zeros(ops.aed_search_cache_size(self.desc) // 4, dtype=torch.float32, device=dev)
+        # zeros, not empty: the rows of a done utterance are skipped by the kernels and the GEMMs still read them
+        self.x, self.qkv, self.ctx, self.q = f32(R, D), f32(R, 3 * D), f32(R, D), f32(R, D)
+        self.h, self.logits = f32(R, cfg.linear_units), f32(R, cfg.vocab)
+        self.done = torch.zeros(self.B, dtype=torch.int32, device=dev)
+        self._done_host = torch.zeros(self.B, dtype=torch.int32).pin_memory()     # the poll's target: one small asynchronous copy
+        self.kvp = None           # the memory's K / V projection of the current call, (rows, num_blocks * 2 D)
+        self._graph = None
+        self.steps_issued = 0     # of the last call
+        self.last = None          # device tensors of the last call: m3_aed_search_result's, plus state and done
+
+    def launches_per_step(self):
+        return 8 * self.cfg.num_blocks + 3
+
+    # ---- one step: the same launches with the same arguments, whatever the step
+    def _step(self):
+        w, cfg, d, st = self.rescorer.w, self.cfg, self.desc, self.state
+        D, x = cfg.dim, self.x
+        ops.aed_search_embed(d, st, w["decoder.embed.weight"], w["decoder.pe"], x)
+        for i in range(cfg.num_blocks):
+            q = "decoder.layers.%d." % i
+            ln = lambda n: (w[q + n + ".weight"], w[q + n + ".bias"], LN_EPS)   # noqa: E731
+            ops.linear(x, w[q + "self_attn.qkv.weight"], w[q + "self_attn.qkv.bias"], ln=ln("norm1"), out=self.qkv)
+            ops.aed_search_attention(d, st, self.qkv[:, :D], self.qkv[:, D:], self.ctx, i, cache=self.cache)
+            ops.linear(self.ctx, w[q + "self_attn.linear_out.weight"], w[q + "self_attn.linear_out.bias"], resid=x, out=x)
+            ops.linear(x, w[q + "src_attn.linear_q.weight"], w[q + "src_attn.linear_q.bias"], ln=ln("norm2"), out=self.q)
+            ops.aed_search_attention(d, st, self.q, self.kvp[:, i * 2 * D:(i + 1) * 2 * D], self.ctx, i)
+            ops.linear(self.ctx, w[q + "src_attn.linear_out.weight"], w[q + "src_attn.linear_out.bias"], resid=x, out=x)
+            ops.linear(x, w[q + "feed_forward.w_1.weight"], w[q + "feed_forward.w_1.bias"], ln=ln("norm3"), act=self.rescorer.act,
+                       out=self.h)
+            ops.linear(self.h, w[q + "feed_forward.w_2.weight"], w[q + "feed_forward.w_2.bias"], resid=x, out=x)
+        ops.linear(x, w["decoder.output_layer.weight"], w["decoder.output_layer.bias"],
+                   ln=(w["decoder.after_norm.weight"], w["decoder.after_norm.bias"], LN_EPS), out=self.logits)
+        ops.aed_search_prune(d, st, self.logits, self.done)
+
+    def _project(self, rows, raw_memory):
+        """The memory's K / V projection for all layers: one GEMM per search, shared by every beam and every step.  The buffer
+        is kept (and grown) across calls so that a captured step keeps reading the same addresses."""
+        w, L, D = self.rescorer.w, self.cfg.num_blocks, self.cfg.dim
+        if self.kvp is None or self.kvp.shape[0] < rows.shape[0]:
+            self.kvp = torch.zeros(rows.shape[0], L * 2 * D, dtype=torch.float32, device=self.device)
+            self._graph = None
+        norm = (w["after_norm.weight"], w["after_norm.bias"], LN_EPS) if raw_memory else None
+        # src_kv_all stacks the right-to-left decoder's layers behind the left one's: the search takes the first L only
+        ops.linear(rows, w["decoder.src_kv_all.weight"][:L * 2 * D], w["decoder.src_kv_all.bias"][:L * 2 * D], ln=norm,
+                   out=self.kvp[:rows.shape[0]])
+
+    def _run(self, rows, row0, lens, raw_memory, detail, max_steps, poll):
+        """rows (n, D) memory rows on the device; row0 / lens: B Python ints each, validated by the caller"""
+        cfg, d = self.cfg, self.desc
+        cap = self.max_steps if max_steps is None else int(max_steps)
+        if not 1 <= cap <= self.max_steps:
+            raise _lib.M3Error("search: max_steps = %d outside [1, %d] (the constructor's bound sizes the cache)" % (cap, self.max_steps))
+        poll = self.poll if poll is None else max(int(poll), 1)
+        meta = torch.tensor([row0, lens], dtype=torch.int32).to(self.device)
+        self._project(rows, raw_memory)
+        ops.aed_search_reset(d, self.state, meta[0], meta[1], cap)
+        self.done.zero_()
+        most = min(max(lens), cfg.max_len - 1, cap)
+        issued = 0
+        while issued < most:
+            if self.use_graph:
+                self._replay(meta, cap)
+            else:
+                self._step()
+            issued += 1
+            if issued % poll == 0 and issued < most and self._all_done():
+                break
+        self.steps_issued = issued
+        res = ops.aed_search_result(d, self.state)
+        self.last = dict(res, state=self.state, done=self.done)
+        host = torch.cat([res["hyp_tokens"].reshape(-1), res["hyp_len"].reshape(-1), res["finished"].reshape(-1), res["best"],
+                          res["score"].reshape(-1).view(torch.int32)]).cpu()
+        B, N, S = self.B, self.beam, self.max_steps
+        toks = host[:B * N * S].view(B, N, S)
+        o = B * N * S
+        hlen, fin, best = host[o:o + B * N].tolist(), host[o + B * N:o + 2 * B * N].tolist(), host[o + 2 * B * N:o + 2 * B * N + B].tolist()
+        score = host[o + 2 * B * N + B:].view(torch.float32).tolist()
+        out = []
+        for b in range(B):
+            hyps = [(tuple(toks[b, i, :hlen[b * N + i]].tolist()), score[b * N + i], bool(fin[b * N + i])) for i in range(N)]
+            out.append((list(hyps[best[b]][0]), hyps) if detail else list(hyps[best[b]][0]))
+        return out
+
+    def _all_done(self):
+        self._done_host.copy_(self.done, non_blocking=True)
+        torch.cuda.current_stream(self.device).synchronize()
+        return bool(self._done_host.all())
+
+    def _replay(self, meta, cap):
+        """use_graph: the step as one captured graph.  The first graph call of an object warms the launchers up with one eager
+        step (kernel attributes are set once per device, outside any capture), restores the start and captures."""
+        if self._graph is None:
+            self._step()
+            ops.aed_search_reset(self.desc, self.state, meta[0], meta[1], cap)
+            self.done.zero_()
+            torch.cuda.synchronize(self.device)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._step()
+            self._graph = g
+        self._graph.replay()
+
+    # ---- the public calls
+    def search(self, memory, mem_len, raw_memory=False, detail=False, max_steps=None, poll=None):
+        """memory (B, T', D) on the device: the encoder's normalised hidden states (Engine.hidden()), or with raw_memory the
+        residual stream before after_norm (Engine.hidden(normalized=False)), the LayerNorm then riding in the K / V GEMM's
+        prologue; mem_len (B,) valid frames.  Utterance b stops once its `beam` hypotheses have all ended in eos, or after
+        min(mem_len[b], max_len - 1, max_steps) steps with whatever it has; max_steps: a bound for this call, at most the
+        constructor's.
+        -> the best token list per utterance; detail: (best tokens, [(tokens, score, finished)] in slot order) per utterance.
+        mem_len < 1 is refused before anything is launched.  The device tensors of the call stay in self.last."""
+        cfg, B = self.cfg, self.B
+        memory = memory.to(self.device, torch.float32)
+        if memory.dim() != 3 or memory.shape[0] != B or memory.shape[2] != cfg.dim:
+            raise ValueError("search: memory %s for %d utterances of dim %d" % (tuple(memory.shape), B, cfg.dim))
+        Tm = int(memory.shape[1])
+        lens = [int(v) for v in torch.as_tensor(mem_len).reshape(-1).tolist()]
+        if len(lens) != B:
+            raise ValueError("search: %d memory lengths for %d utterances" % (len(lens), B))
+        for b, m in enumerate(lens):
+            if not 1 <= m <= Tm:
+                raise _lib.M3Error("search: utterance %d has %d memory frames (mem_len = 0 is rejected; the memory holds %d)" % (b, m, Tm))
+        return self._run(memory.contiguous().view(B * Tm, cfg.dim), [b * Tm for b in range(B)], lens, raw_memory, detail, max_steps, poll)
+
+    def search_rows(self, rows, row0, raw_memory=True, detail=False, max_steps=None, poll=None):
+        """The search over PACKED memory rows, as AttentionRescorer.rescore_rows takes them: rows (>= R, D) on the device,
+        row0 (B + 1,) int32 (m3_aed_memory_gather leaves them so): utterance b owns rows [row0[b], row0[b + 1]).  raw_memory:
+        the rows are the residual stream before after_norm (what the streaming store keeps).  An utterance without a row is
+        refused before anything is launched."""
+        cfg, B = self.cfg, self.B
+        if rows.dim() != 2 or rows.shape[1] != cfg.dim or not rows.is_contiguous() or row0.numel() != B + 1:
+            raise ValueError("search_rows: rows %s / row0 (%d,) for %d utterances of dim %d" % (tuple(rows.shape), row0.numel(), B, cfg.dim))
+        r0 = [int(v) for v in row0.reshape(-1).tolist()]
+        if r0[0] != 0 or any(a > b for a, b in zip(r0, r0[1:])) or r0[-1] > rows.shape[0]:
+            raise _lib.M3Error("search_rows: row0 = %s does not describe %d packed rows" % (r0, rows.shape[0]))
+        lens = [b - a for a, b in zip(r0, r0[1:])]
+        for b, m in enumerate(lens):
+            if m < 1:
+                raise _lib.M3Error("search_rows: utterance %d has no memory row (mem_len = 0 is rejected)" % b)
+        return self._run(rows[:r0[-1]].to(self.device, torch.float32), r0[:-1], lens, raw_memory, detail, max_steps, poll)

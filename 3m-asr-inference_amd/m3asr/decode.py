@@ -13,6 +13,7 @@ and return types), running on the device through libm3asr_hip.so:
                 StreamingCtcDecoder(endpoint=...).endpoints(); m3asr.serve.StreamPool(segment=True) cuts sessions there.
   rescoring     the reference's second pass (model/ctc_aed.py:160-252): CtcDecoder(engine, rescorer=...).attention_rescoring
                 runs the batched beam search, then the attention decoder over its n-best (m3asr.rescore).
+  attention     CtcDecoder(engine, rescorer=...).attention: the attention decoder's own beam search (m3asr.aed_search).
   two passes,   StreamingCtcDecoder(..., rescorer=...) keeps every stream's encoder memory on the device (m3_aed_memory_*) and
   streaming     rescore() runs the second pass over a stream's n-best when its utterance ends; StreamPool(rescore=True).
 
@@ -368,6 +369,30 @@ class CtcDecoder:
                                     reverse_weight=reverse_weight, raw_memory=True)
         return out if detail else [list(best) for best, _ in out]
 
+    def attention(self, xs: torch.Tensor, xs_lens: torch.Tensor, beam_size: int, decoding_chunk_size: int = -1,
+                  num_decoding_left_chunks: int = -1, max_steps=None, detail=False):
+        """The reference's decoding mode `attention` for any batch size, all on the device: encoder forward, then the attention
+        decoder's own autoregressive beam search over the encoder's hidden states (m3asr.aed_search).  There is
+        no first pass: CTC scores and the right-to-left decoder take no part.  max_steps: the most tokens per hypothesis
+        (default: the encoder's output frames, the reference's maxlen); it sizes the search's K / V cache.
+        -> the best token list per utterance; detail: (best tokens, [(tokens, score, finished)]) per utterance."""
+        if self.rescorer is None:
+            raise _lib.M3Error("CtcDecoder.attention: built without a rescorer (CtcDecoder(engine, rescorer=AttentionRescorer(...)))")
+        from .aed_search import AttentionBeamSearch
+        self._full_context(decoding_chunk_size, num_decoding_left_chunks)
+        res = self.forward(xs, xs_lens)
+        memory = self.engine.hidden(normalized=False)     # after_norm rides in the prologue of the search's K / V GEMM
+        B, frames = int(memory.shape[0]), int(memory.shape[1])
+        steps = min(frames, self.rescorer.cfg.max_len - 1) if max_steps is None else int(max_steps)
+        if steps < 1:
+            raise _lib.M3Error("CtcDecoder.attention: max_steps = %d, need at least 1" % steps)
+        # the searcher (state, K / V cache, work buffers) is kept across calls: sized by the step bound rounded up to a multiple
+        # of 64 and re-allocated only when a call needs more; the call's own bound goes to search()
+        key, kept = (B, int(beam_size)), getattr(self, "_attention_search", None)
+        if kept is None or kept[0] != key or kept[1].max_steps < steps:
+            bound = min(-(-steps // 64) * 64, self.rescorer.cfg.max_len - 1)
+            kept = self._attention_search = (key, AttentionBeamSearch(self.rescorer, B, beam_size, bound))
+        return kept[1].search(memory, res["out_lens"].cpu(), raw_memory=True, detail=detail, max_steps=steps)
 
 class StreamingCtcDecoder:
     """CTC decoding chunk by chunk on top of a StreamingEncoder: every step() runs the chunk forward, then log-softmax +

@@ -890,6 +890,81 @@ def aed_memory_gather(desc, state, slots, out=None):
     return out, row0
 
 
+# ---- attention decoding: the AED decoder's own beam search (m3_aed_search_*; m3asr.aed_search drives these around the GEMMs)
+def aed_search_desc(B, beam, max_steps, V, D, H, layers, pe_rows):
+    """m3_aed_search_desc.  Raises M3Error on a descriptor the library rejects (beam outside [1, min(64, V)], a head size that
+    is no multiple of 16 up to 128, sizes that overflow the int32 row arithmetic of the state or of the K / V cache)."""
+    d = _lib.AedSearchDesc(int(B), int(beam), int(max_steps), int(V), int(D), int(H), int(layers), int(pe_rows))
+    if d.B < 1:
+        raise _lib.M3Error("aed_search_desc: B = %d, need at least one utterance" % d.B)
+    if _lib.load().m3_aed_search_state_size(C.byref(d)) == 0:
+        raise _lib.M3Error("m3_aed_search_state_size failed: " + _lib.last_error())
+    return d
+
+
+def aed_search_state_size(desc):
+    return _lib.load().m3_aed_search_state_size(C.byref(desc))
+
+
+def aed_search_cache_size(desc):
+    """bytes of the self-attention K / V cache: layers * max_steps * B * beam * 2 D fp32"""
+    return _lib.load().m3_aed_search_cache_size(C.byref(desc))
+
+
+def _nbytes(t):
+    return t.numel() * t.element_size()
+
+
+def aed_search_reset(desc, state, mem_row0, mem_len, max_steps=None):
+    """mem_row0 / mem_len (B,) int32 on the device: the memory rows of every utterance; max_steps <= desc.max_steps"""
+    assert mem_row0.numel() == desc.B and mem_len.numel() == desc.B
+    check(_lib.load().m3_aed_search_reset(C.byref(desc), _p(state), _nbytes(state), _i32(mem_row0), _i32(mem_len),
+                                          int(desc.max_steps if max_steps is None else max_steps), _stream()), "m3_aed_search_reset")
+
+
+def aed_search_embed(desc, state, emb, pe, x):
+    """x (R, D) <- emb[last token] * sqrt(D) + pe[step], from the state"""
+    assert tuple(emb.shape) == (desc.V, desc.D) and tuple(pe.shape) == (desc.pe_rows, desc.D)
+    xp, ldx = _rows(x)
+    assert tuple(x.shape) == (desc.B * desc.beam, desc.D)
+    check(_lib.load().m3_aed_search_embed(C.byref(desc), _p(state), _nbytes(state), _f32(emb), _f32(pe), xp, ldx, _stream()),
+          "m3_aed_search_embed")
+    return x
+
+
+def aed_search_attention(desc, state, q, kv, out, layer, cache=None):
+    """Single-query attention of the R hypothesis rows (m3_aed_search_attention).  q (R, D) and kv (rows, 2 D) = K | V are
+    row-strided views.  cache given: self use, kv = the rows' new K | V (qkv[:, D:]), stored at the step's cache position;
+    cache None: source use, kv = the memory's projection for `layer`."""
+    R = desc.B * desc.beam
+    (qp, ldq), (kp, ldkv), (op, ldo) = _rows(q), _rows(kv), _rows(out)
+    assert tuple(q.shape) == (R, desc.D) and tuple(out.shape) == (R, desc.D) and kv.shape[1] == 2 * desc.D
+    check(_lib.load().m3_aed_search_attention(C.byref(desc), _p(state), _nbytes(state), qp, ldq, kp, ldkv, kv.shape[0],
+                                              _f32(cache), _nbytes(cache) if cache is not None else 0, int(layer), op, ldo,
+                                              _stream()), "m3_aed_search_attention")
+    return out
+
+
+def aed_search_prune(desc, state, logits, done=None):
+    """One search step's log-softmax, top-k, prune and bookkeeping over logits (R, V); done (B,) int32 receives the flags"""
+    lp, ldl = _rows(logits)
+    assert tuple(logits.shape) == (desc.B * desc.beam, desc.V) and (done is None or done.numel() == desc.B)
+    check(_lib.load().m3_aed_search_prune(C.byref(desc), _p(state), _nbytes(state), lp, ldl, _i32(done), _stream()),
+          "m3_aed_search_prune")
+
+
+def aed_search_result(desc, state):
+    """-> dict(hyp_tokens (B,beam,max_steps), hyp_len, score, finished (B,beam), best, steps (B,)) on the device"""
+    B, N, dev = desc.B, desc.beam, state.device
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)   # noqa: E731
+    out = dict(hyp_tokens=i32(B, N, desc.max_steps), hyp_len=i32(B, N), score=torch.empty(B, N, dtype=torch.float32, device=dev),
+               finished=i32(B, N), best=i32(B), steps=i32(B))
+    check(_lib.load().m3_aed_search_result(C.byref(desc), _p(state), _nbytes(state), _p(out["hyp_tokens"]), _p(out["hyp_len"]),
+                                           _p(out["score"]), _p(out["finished"]), _p(out["best"]), _p(out["steps"]), _stream()),
+          "m3_aed_search_result")
+    return out
+
+
 # ---------------------------------------------------------------------------------------- streaming operators
 def cat_split_cache(in_cache, inp):
     """CatSplitCache plugin: (output (B, cache+input), out_cache (B, cache)); f32 or i32 rows."""

@@ -858,6 +858,63 @@ int m3_aed_memory_lengths(const m3_aed_memory_desc* desc, const void* state, siz
 int m3_aed_memory_gather(const m3_aed_memory_desc* desc, const void* state, size_t state_bytes, const int32_t* slots, int n,
                          float* out, int ldo, int out_rows, int32_t* out_row0, m3_stream stream);
 
+/* Attention decoding: the AED decoder's own autoregressive beam search (csrc/aed_search.hip).  R = B * beam
+ * hypothesis rows, row r = u * beam + slot; one new token per row per step; sos = eos = V - 1.  Everything that changes from
+ * step to step lives in the state blob, so a step is the same launches with the same arguments every time and the host reads
+ * nothing to issue the next one:  m3_aed_search_embed, then per decoder layer [m3_linear qkv (norm1 prologue),
+ * m3_aed_search_attention (self), m3_linear out (+ residual), m3_linear q (norm2), m3_aed_search_attention (source), m3_linear
+ * out (+ residual), m3_linear w_1 (norm3, activation), m3_linear w_2 (+ residual)], m3_linear output layer (after_norm),
+ * m3_aed_search_prune.  fp32, no atomics, fixed reduction orders, a row's result independent of its place in the batch.
+ * State blob: caller-owned device memory of m3_aed_search_state_size bytes, 16-byte aligned (0 and m3_last_error for a
+ *   descriptor the library rejects: 1 <= beam <= min(64, V), max_steps >= 1, D / H a multiple of 16 up to 128, sizes that
+ *   overflow the int32 row arithmetic).  Per utterance: its own step counter, its limit, a done flag and its memory rows.
+ *   Per row, double-buffered by the parity of the utterance's step: score, finished flag, the token path [max_steps + 1]
+ *   (position 0 = sos) and the ancestry path[t] = the slot that wrote position t of the hypothesis's self-attention keys.
+ * K / V cache: caller-owned, m3_aed_search_cache_size bytes = layers * max_steps * R * 2 D fp32, laid out
+ *   [layer][position][R][K (D) | V (D)]; written once per (position, slot), never moved: pruning copies the integer paths.
+ * m3_aed_search_reset: every row holds [sos]; slot 0 scores 0, the others -inf; utterance u owns memory rows
+ *   [mem_row0[u], mem_row0[u] + mem_len[u]) (device int32 [B]) and stops after limit = min(mem_len, pe_rows - 1, max_steps)
+ *   steps (max_steps <= desc->max_steps); mem_len < 1 marks it done at once (the caller refuses that before it launches).
+ * m3_aed_search_embed: x [R][ldx] = emb[last token of r] * sqrt(D) + pe[step of r's utterance].  emb [V][D], pe [pe_rows][D].
+ * m3_aed_search_attention: single-query attention, one wave per (row, head), online softmax over tiles of 64 keys.
+ *   cache != NULL, self use: kv [R][ldkv] holds the rows' new K | V (columns [0, D) and [D, 2 D): the fused QKV GEMM's output
+ *   from column D on); the wave stores its head's slice at cache position `step` under the row's own slot, then attends over
+ *   positions 0 .. step, position t < step fetched from slot path[t], the last one from kv itself.  cache == NULL, source use:
+ *   kv [kv_rows][ldkv] = the memory's K | V projection of `layer` (columns as above), keys = the utterance's memory rows, shared
+ *   by its beam.  q [R][ldq], out [R][ldo], head h in columns [h dk, (h + 1) dk); ldkv a multiple of 4, kv / cache 16-byte
+ *   aligned.  Rows of a done utterance are skipped (nothing stored, out untouched).
+ * m3_aed_search_prune: one work-group per utterance: per row logsumexp over V and the beam largest logits (lower token id on
+ *   ties), a finished row offering the single candidate (increment 0, eos) instead; the beam largest of the beam^2 candidate
+ *   scores (lower flat index slot * beam + rank on ties; a candidate of a -inf slot stays -inf); new tokens, scores, flags
+ *   and ancestry go to the other record; the utterance's step moves and its done flag is set once every slot is finished or
+ *   the limit is reached.  A done utterance is left bit for bit alone.  logits [R][ldl]; done: NULL or device int32 [B] that
+ *   receives every utterance's done flag (the one word the host polls).
+ * m3_aed_search_result: hyp_tokens [B][beam][max_steps] (sos and trailing eos stripped, -1 behind), hyp_len, score, finished
+ *   [B][beam], best [B] = the first slot with the strictly largest score, steps [B] = steps taken. */
+typedef struct m3_aed_search_desc {
+  int32_t B;
+  int32_t beam;
+  int32_t max_steps;
+  int32_t V;
+  int32_t D;
+  int32_t H;
+  int32_t layers;
+  int32_t pe_rows;
+} m3_aed_search_desc;
+size_t m3_aed_search_state_size(const m3_aed_search_desc* desc);
+size_t m3_aed_search_cache_size(const m3_aed_search_desc* desc);
+int m3_aed_search_reset(const m3_aed_search_desc* desc, void* state, size_t state_bytes, const int32_t* mem_row0,
+                        const int32_t* mem_len, int max_steps, m3_stream stream);
+int m3_aed_search_embed(const m3_aed_search_desc* desc, const void* state, size_t state_bytes, const float* emb, const float* pe,
+                        float* x, int ldx, m3_stream stream);
+int m3_aed_search_attention(const m3_aed_search_desc* desc, const void* state, size_t state_bytes, const float* q, int ldq,
+                            const float* kv, int ldkv, int kv_rows, float* cache, size_t cache_bytes, int layer, float* out, int ldo,
+                            m3_stream stream);
+int m3_aed_search_prune(const m3_aed_search_desc* desc, void* state, size_t state_bytes, const float* logits, int ldl,
+                        int32_t* done, m3_stream stream);
+int m3_aed_search_result(const m3_aed_search_desc* desc, const void* state, size_t state_bytes, int32_t* hyp_tokens, int32_t* hyp_len,
+                         float* score, int32_t* finished, int32_t* best, int32_t* steps, m3_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

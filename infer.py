@@ -24,7 +24,13 @@ the ranking (m3asr.lm), together with --hotwords if both are given.
 
 Attention rescoring, for a plan built from a joint CTC/attention checkpoint: the batched prefix beam search, then the plan's
 attention decoder rescoring every utterance's n-best on the encoder's hidden states (m3asr.rescore).  Prints the first-pass
-best and the rescored best hypothesis of each utterance."""
+best and the rescored best hypothesis of each utterance.
+
+    python3 infer.py -p aed.plan -i feat.npy --attention [--beam 10] [--max-steps K]
+
+Attention decoding, for such a plan: the attention decoder searches on its own, autoregressively, over the encoder's hidden
+states (m3asr.aed_search); --max-steps bounds the tokens per hypothesis (default: the encoder's output frames).  Prints the
+best hypothesis of each utterance."""
 import argparse
 import os
 import sys
@@ -115,6 +121,20 @@ def print_rescore(helper, feat, feat_len, args):
         print("utt %d rescored: att=%.4f final=%.4f tokens=%s" % (b, chosen[2], chosen[3], " ".join(str(t) for t in best)))
 
 
+def print_attention(helper, feat, feat_len, args):
+    """Best hypothesis of every utterance of the attention decoder's own beam search."""
+    import torch
+    from m3asr.decode import CtcDecoder
+    from m3asr.plan import decoder_config_of
+    from m3asr.rescore import AttentionRescorer
+    rescorer = AttentionRescorer(helper.decoder_packed, decoder_config_of(helper.extra), helper.engine.device)
+    dec = CtcDecoder(helper.engine, rescorer=rescorer)
+    out = dec.attention(torch.from_numpy(feat), torch.from_numpy(feat_len), args.beam, max_steps=args.max_steps, detail=True)
+    for b, (best, hyps) in enumerate(out):
+        chosen = next(h for h in hyps if list(h[0]) == best)
+        print("utt %d attention: score=%.4f finished=%d tokens=%s" % (b, chosen[1], chosen[2], " ".join(str(t) for t in best)))
+
+
 def main(args):
     logger = trt_helper.init_trt_plugin(trt.Logger.INFO, "libm3asr_hip.so")
     helper = trt_helper.InferHelper(args.plan_name, logger)
@@ -132,6 +152,8 @@ def main(args):
         print(o)
     if args.rescore:
         print_rescore(helper, feat, feat_len, args)
+    if args.attention:
+        print_attention(helper, feat, feat_len, args)
     if args.lm:
         print_lm_search(outputs[0], helper.engine.device, args)
     elif args.hotwords:
@@ -158,4 +180,6 @@ if __name__ == "__main__":
     p.add_argument("--rescore", action="store_true", help="Attention rescoring of the n-best with the plan's AED decoder.")
     p.add_argument("--ctc-weight", type=float, default=0.0, help="--rescore: weight of the first-pass score in the final score.")
     p.add_argument("--reverse-weight", type=float, default=0.0, help="--rescore: weight of the right-to-left decoder.")
+    p.add_argument("--attention", action="store_true", help="Attention decoding: the plan's AED decoder searching on its own.")
+    p.add_argument("--max-steps", type=int, default=None, help="--attention: the most tokens per hypothesis.")
     main(p.parse_args())

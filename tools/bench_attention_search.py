@@ -1,0 +1,124 @@
+#!/usr/bin/env python3
+"""Attention decoding timed: 16 utterances x beam 10 at real dimensions (D 512, 4 heads, F 2048, V 1434,
+6 blocks; 125 memory frames = 5 s of audio), synthetic weights.  With random weights eos has probability about 1 / V and every
+search would run to its limit, so output_layer.bias[eos] is raised by --eos-bias.  The JSON line reports what the searches did
+(steps taken, hypothesis lengths); see DESIGN.md 21 for what the default gives and why no bias gives a uniform beam.  The
+memory lengths are drawn from [frames / 2, frames] as tools/bench_rescore.py draws them (the JSON line says which);
+--full-length gives every utterance all --frames frames.
+
+  python tools/bench_attention_search.py [--batch 16] [--beam 10] [--frames 125] [--blocks 6] [--rounds 10] [--graph]
+
+"device": wall time of AttentionBeamSearch.search() per call -- the K / V GEMM, every step's launches, the polls of the done
+flags and the read of the results -- median over the rounds after a warm-up; us per step = that over the steps issued.
+"eager": the same search as tests/aed_search_ref.py states it -- every hypothesis on its own, the prefix recomputed at every
+step, plain torch float32 -- on the same GPU, timed --eager-rounds times (default 1; 0 skips it) after a warm-up search
+of the first utterance for two steps, which loads every kernel the eager path uses.  --graph also times the captured step
+and checks that it leaves the same bits.  Prints one JSON line; the results are compared before anything is timed."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "3m-asr-inference_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import torch
+
+from m3asr.config import DecoderConfig
+from m3asr.weights import make_decoder_weights
+
+
+def make_case(batch, frames, blocks, eos_bias, seed=0, full_length=False):
+    dcfg = DecoderConfig(vocab=1434, dim=512, heads=4, linear_units=2048, num_blocks=blocks)
+    sd = make_decoder_weights(dcfg, seed=seed)
+    g = torch.Generator().manual_seed(seed)
+    sd["after_norm.weight"], sd["after_norm.bias"] = torch.ones(dcfg.dim), torch.zeros(dcfg.dim)
+    sd["decoder.output_layer.bias"] = sd["decoder.output_layer.bias"].clone()
+    sd["decoder.output_layer.bias"][-1] += eos_bias
+    memory = torch.randn(batch, frames, dcfg.dim, generator=g)
+    mem_len = torch.randint(frames // 2, frames + 1, (batch,), generator=g).to(torch.int32)
+    if full_length:
+        mem_len = torch.full((batch,), frames, dtype=torch.int32)
+    return dcfg, sd, memory, mem_len
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--beam", type=int, default=10)
+    ap.add_argument("--frames", type=int, default=125)
+    ap.add_argument("--blocks", type=int, default=6)
+    ap.add_argument("--eos-bias", type=float, default=1.2)
+    ap.add_argument("--max-steps", type=int, default=None, help="default: --frames")
+    ap.add_argument("--poll", type=int, default=8)
+    ap.add_argument("--rounds", type=int, default=10)
+    ap.add_argument("--eager-rounds", type=int, default=1)
+    ap.add_argument("--graph", action="store_true")
+    ap.add_argument("--full-length", action="store_true")
+    a = ap.parse_args()
+    import aed_search_ref
+    from m3asr.aed_search import AttentionBeamSearch
+    from m3asr.plan import pack_decoder
+    from m3asr.rescore import AttentionRescorer
+    dcfg, sd, memory, mem_len = make_case(a.batch, a.frames, a.blocks, a.eos_bias, full_length=a.full_length)
+    B, beam, steps = a.batch, a.beam, a.max_steps or a.frames
+    res = AttentionRescorer(pack_decoder(sd, dcfg), dcfg, "cuda:0")
+    search = AttentionBeamSearch(res, B, beam, steps, poll=a.poll)
+    mem_d = memory.cuda()
+    out = search.search(mem_d, mem_len, detail=True)
+    taken = search.last["steps"].cpu().tolist()
+    lengths = [len(h[0]) for u in out for h in u[1]]
+    record = {"metric": "attention decoding, %d utterances x beam %d, %d blocks, D 512 / F 2048 / V 1434, %d frames" % (
+        B, beam, a.blocks, a.frames), "mem_len_min_max": [int(mem_len.min()), int(mem_len.max())], "eos_bias": a.eos_bias, "steps_taken_min_max": [min(taken), max(taken)],
+        "hyp_tokens_min_median_max": [min(lengths), statistics.median(lengths), max(lengths)],
+        "finished": "%d/%d" % (sum(int(h[2]) for u in out for h in u[1]), B * beam),
+        "launches_per_step": search.launches_per_step(), "poll": a.poll, "data": "synthetic"}
+
+    def timed(f, n):
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return ts
+
+    def add(tag, s, ts):
+        record[tag + "_ms_median"] = round(statistics.median(ts), 3)
+        record[tag + "_ms_min"] = round(min(ts), 3)
+        record[tag + "_steps_issued"] = s.steps_issued
+        record[tag + "_us_per_step"] = round(statistics.median(ts) * 1e3 / max(s.steps_issued, 1), 1)
+
+    timed(lambda: search.search(mem_d, mem_len), 3)
+    add("device", search, timed(lambda: search.search(mem_d, mem_len), a.rounds))
+    if a.graph:
+        graphed = AttentionBeamSearch(res, B, beam, steps, poll=a.poll, use_graph=True)
+        same = graphed.search(mem_d, mem_len, detail=True) == out
+        same = same and torch.equal(graphed.last["score"].view(torch.int32), search.last["score"].view(torch.int32))
+        record["graph_same_bits"] = bool(same)
+        timed(lambda: graphed.search(mem_d, mem_len), 3)
+        add("graph", graphed, timed(lambda: graphed.search(mem_d, mem_len), a.rounds))
+    if a.eager_rounds > 0:
+        sd_d = {k: v.cuda() for k, v in sd.items()}
+
+        def eager():
+            r = aed_search_ref.search(sd_d, dcfg, mem_d, mem_len.tolist(), beam, steps, dtype=torch.float32)
+            torch.cuda.synchronize()
+            return r
+
+        aed_search_ref.search(sd_d, dcfg, mem_d[:1], mem_len[:1].tolist(), beam, 2, dtype=torch.float32)     # warm-up
+        ref = eager()
+        eag = timed(eager, a.eager_rounds)
+        record["eager_aed_search_ref_ms_median"] = round(statistics.median(eag), 1)
+        record["same_best_as_eager"] = "%d/%d" % (sum(int(tuple(u[0]) == r["nbest"][r["best"]][0]) for u, r in zip(out, ref)), B)
+        record["max_abs_score_diff_vs_eager"] = max(abs(h[1] - w[1]) for u, r in zip(out, ref) for h, w in zip(u[1], r["nbest"])
+                                                    if h[0] == w[0])
+    print(json.dumps(record))
+
+
+if __name__ == "__main__":
+    main()
