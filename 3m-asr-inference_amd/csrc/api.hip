@@ -360,6 +360,41 @@ int m3_dwconv_ln_silu(const float* z, const float* w_kc, const float* bias, cons
                       float eps, int B, int T, int D, int K, float* out, m3_stream stream) {
   return launch_dwconv_ln_silu(z, w_kc, bias, gamma, beta, eps, B, T, D, K, out, (hipStream_t)stream);
 }
+// The stateful launches of the chunk-by-chunk engine (engine.hip "att_stream" / "conv.dw_ln_silu" stages) at the boundary: argument
+// checks and one launcher call each.  What lives on the device (the counters, chunk_len) cannot be checked here.
+int m3_relpos_attention_stream(const float* qkv, int ldq, float* hist, int cap, const float* p, int ldp, int p_rows, const float* pos_u,
+                               const float* pos_v, const int32_t* chunk_len, const int32_t* step, int B, int C, int H, int dk,
+                               float scale, int left_chunks, int slot_max_chunks, float* out, int ldo, m3_stream stream) {
+  M3_REQUIRE(B > 0 && C > 0 && H > 0 && dk > 0, "attention (stream): empty problem");
+  M3_REQUIRE(qkv && p && pos_u && pos_v && out, "attention (stream): null qkv / p / pos_u / pos_v / out");
+  M3_REQUIRE(ldq >= 3 * H * dk && ldp >= H * dk && ldo >= H * dk, "attention (stream): ldq=%d / ldp=%d / ldo=%d shorter than the rows (%d / %d / %d)",
+             ldq, ldp, ldo, 3 * H * dk, H * dk, H * dk);
+  M3_REQUIRE(aligned16(qkv) && aligned16(hist) && aligned16(p) && aligned16(pos_u) && aligned16(pos_v) && aligned16(out),
+             "attention (stream): qkv / hist / p / pos_u / pos_v / out must be 16-byte aligned");
+  M3_REQUIRE(p_rows >= C, "attention (stream): a position table of %d rows is shorter than one chunk of %d", p_rows, C);
+  M3_REQUIRE(slot_max_chunks < 0 || (long)slot_max_chunks * C <= (long)p_rows,
+             "attention (stream, slot mode): %d chunks of %d frames pass the position table's %d rows", slot_max_chunks, C, p_rows);
+  return launch_relpos_attention_stream(qkv, ldq, hist, cap, p, ldp, pos_u, pos_v, chunk_len, step, B, C, H, dk, scale, out, ldo, left_chunks,
+                                        (hipStream_t)stream, slot_max_chunks);
+}
+int m3_dwconv_ln_silu_stream(const float* z, const float* w_kc, const float* bias, const float* gamma, const float* beta, float eps, int B,
+                             int T, int D, int K, float* cache_pair, const int32_t* step, const int32_t* chunk_len, int slot_max_chunks,
+                             float* out, m3_stream stream) {
+  M3_REQUIRE(B > 0 && T > 0 && D > 0, "dwconv (stream): empty problem");
+  M3_REQUIRE(z && w_kc && bias && out && (gamma == nullptr) == (beta == nullptr), "dwconv (stream): null z / w_kc / bias / out, or gamma without beta");
+  M3_REQUIRE(aligned16(z) && aligned16(w_kc) && aligned16(bias) && aligned16(gamma) && aligned16(beta) && aligned16(cache_pair) && aligned16(out),
+             "dwconv (stream): every operand must be 16-byte aligned");
+  return launch_dwconv_ln_silu_stream(z, w_kc, bias, gamma, beta, eps, B, T, D, K, out, cache_pair, step, chunk_len, (hipStream_t)stream, 0,
+                                      slot_max_chunks);
+}
+int m3_dwconv_ln_silu_causal(const float* z, const float* w_kc, const float* bias, const float* gamma, const float* beta, float eps,
+                             const float* left_fill, int B, int T, int D, int K, float* out, m3_stream stream) {
+  M3_REQUIRE(z && w_kc && bias && out && (gamma == nullptr) == (beta == nullptr), "dwconv (causal): null z / w_kc / bias / out, or gamma without beta");
+  M3_REQUIRE(left_fill != nullptr, "dwconv (causal): left_fill [D], the frame left of frame 0, must be supplied");
+  M3_REQUIRE(aligned16(z) && aligned16(w_kc) && aligned16(bias) && aligned16(gamma) && aligned16(beta) && aligned16(left_fill) && aligned16(out),
+             "dwconv (causal): every operand must be 16-byte aligned");
+  return launch_dwconv_ln_silu(z, w_kc, bias, gamma, beta, eps, B, T, D, K, out, (hipStream_t)stream, 0, nullptr, nullptr, nullptr, left_fill);
+}
 int m3_subsample_conv1(const float* feat, const float* w9c, const float* bias, int B, int T, int idim, int C,
                        float* out, m3_stream stream) {
   return launch_conv1_relu(feat, w9c, bias, nullptr, nullptr, B, T, idim, C, out, (hipStream_t)stream);

@@ -395,6 +395,51 @@ def dwconv_ln_silu(z, w_kc, bias, gamma, beta, eps, B, T):
     return out
 
 
+def relpos_attention_stream(qkv, hist, p, pos_u, pos_v, chunk_len, step, B, C, H, dk, left_chunks=-1, slot_max_chunks=-1, out=None):
+    """One chunk of the streaming attention (m3_relpos_attention_stream): qkv (B*C, 3*H*dk) and out (B*C, H*dk) may be
+    row-strided views, p (p_rows, H*dk) too; hist (B, cap, 2*H*dk) is appended to in place.  step: one int32 on the device
+    (lockstep) or int32 [B] with slot_max_chunks >= 0 (slot mode).  The caller advances the counter(s)."""
+    lib = _lib.load()
+    D = H * dk
+    if out is None:
+        out = torch.empty(B * C, D, dtype=torch.float32, device=qkv.device)
+    assert tuple(qkv.shape) == (B * C, 3 * D) and p.shape[1] == D and tuple(out.shape) == (B * C, D)
+    assert hist.dim() == 3 and hist.shape[0] == B and hist.shape[2] == 2 * D
+    assert chunk_len.numel() == B and step.numel() == (B if slot_max_chunks >= 0 else 1)
+    (qp, ldq), (pp, ldp), (op, ldo) = _rows(qkv), _rows(p), _rows(out)
+    check(lib.m3_relpos_attention_stream(qp, ldq, _f32(hist), hist.shape[1], pp, ldp, p.shape[0], _f32(pos_u), _f32(pos_v),
+                                         _i32(chunk_len), _i32(step), B, C, H, dk, 1.0 / math.sqrt(dk), int(left_chunks),
+                                         int(slot_max_chunks), op, ldo, _stream()), "m3_relpos_attention_stream")
+    return out
+
+
+def dwconv_ln_silu_stream(z, w_kc, bias, gamma, beta, eps, B, T, cache_pair, step, chunk_len, slot_max_chunks=-1, out=None):
+    """One chunk of the streaming causal conv + LayerNorm (gamma / beta None: none) + SiLU (m3_dwconv_ln_silu_stream);
+    cache_pair (2, B, K-1, D) is the ping-pong state: half (counter & 1) is read, the other half written."""
+    lib = _lib.load()
+    K, D = w_kc.shape
+    assert tuple(cache_pair.shape) == (2, B, K - 1, D) and z.numel() == B * T * D
+    assert chunk_len.numel() == B and step.numel() == (B if slot_max_chunks >= 0 else 1)
+    if out is None:
+        out = torch.empty_like(z)
+    check(lib.m3_dwconv_ln_silu_stream(_f32(z), _f32(w_kc), _f32(bias), _f32(gamma), _f32(beta), float(eps), B, T, D, K,
+                                       _f32(cache_pair), _i32(step), _i32(chunk_len), int(slot_max_chunks), _f32(out), _stream()),
+          "m3_dwconv_ln_silu_stream")
+    return out
+
+
+def dwconv_ln_silu_causal(z, w_kc, bias, gamma, beta, eps, left_fill, B, T, out=None):
+    """The causal conv on whole padded utterances (m3_dwconv_ln_silu_causal); left_fill (D,) stands for every frame left of frame 0."""
+    lib = _lib.load()
+    K, D = w_kc.shape
+    assert z.numel() == B * T * D and left_fill.numel() == D
+    if out is None:
+        out = torch.empty_like(z)
+    check(lib.m3_dwconv_ln_silu_causal(_f32(z), _f32(w_kc), _f32(bias), _f32(gamma), _f32(beta), float(eps), _f32(left_fill), B, T, D, K,
+                                       _f32(out), _stream()), "m3_dwconv_ln_silu_causal")
+    return out
+
+
 def subsample_conv1(feat, w9c, bias, act=_lib.ACT_RELU):
     """Conv2d(1, C, 3, stride 2) on (B,T,idim) -> channel-last (B,T1,F1,C); act = ACT_RELU (fused, default) or ACT_NONE."""
     lib = _lib.load()

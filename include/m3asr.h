@@ -335,6 +335,38 @@ int m3_relpos_attention_chunk(const float* qkv, int ldq, const float* p, int ldp
  * replaces convolution.py:134-152.  w_kc [K][D] = depthwise weight (D,1,K) transposed. */
 int m3_dwconv_ln_silu(const float* z, const float* w_kc, const float* bias, const float* gamma,
                       const float* beta, float eps, int B, int T, int D, int K, float* out, m3_stream stream);
+/* The two stateful launches of chunk-by-chunk decoding (m3_engine_forward_chunk[_slots] is built from them) and the dense causal
+ * conv, exposed so that they can be tested at the boundary (additions only; tests/test_stream_kernels_gpu.py).
+ *
+ * m3_relpos_attention_stream: the attention core on the C frames of the current chunk under the static chunk mask.  qkv
+ * [B*C][ldq] = (q|k|v) of the chunk, rows at and past chunk_len[b] hold finite values; hist [B][cap][2 D] = K | V rows of the
+ * frames so far, a ring indexed by (absolute frame) % cap, which this launch also appends the chunk's C rows to (read only by
+ * later chunks); p [p_rows][ldp] indexed by the key's absolute frame; chunk_len [B] valid frames of the chunk per utterance
+ * (device int32); out [B*C][ldo].  Chunk number n = the device-side counter: keys [max((n - left_chunks) C, 0), n C + chunk_len[b])
+ * (all frames so far when left_chunks < 0), so the rows equal those m3_relpos_attention_chunk(chunk = C) gives on the whole
+ * utterance, bit for bit.
+ *   slot_max_chunks < 0: lockstep, `step` is ONE device int32 shared by the batch.  The caller guarantees
+ *                        (*step + 1) * C <= p_rows: the counter lives on the device, the entry cannot check it.
+ *   slot_max_chunks >= 0: slot mode, `step` is int32 [B], one counter per utterance slot.  A slot with chunk_len[b] <= 0,
+ *                        step[b] < 0 or step[b] >= slot_max_chunks is not live: zero context rows, its history untouched.
+ *                        slot_max_chunks * C <= p_rows is checked.
+ * Strides: ldq >= 3 D and ldp >= D, multiples of 4; ldo >= D, any value.  cap >= C and cap >= (left_chunks + 1) * C.
+ * dk 16 / 32 / 64 / 128.  The caller advances the counter(s) between launches. */
+int m3_relpos_attention_stream(const float* qkv, int ldq, float* hist, int cap, const float* p, int ldp, int p_rows, const float* pos_u,
+                               const float* pos_v, const int32_t* chunk_len, const int32_t* step, int B, int C, int H, int dk,
+                               float scale, int left_chunks, int slot_max_chunks, float* out, int ldo, m3_stream stream);
+/* m3_dwconv_ln_silu_stream: causal depthwise conv (lorder K - 1, K >= 2, no taps to the right) + LayerNorm (gamma / beta NULL =
+ * none) + SiLU on the T frames of the current chunk, z / out [B*T][D] fp32.  cache_pair [2][B][K-1][D]: half (counter & 1) holds
+ * the K - 1 frames left of the chunk and is only read; the other half receives the last K - 1 frames of
+ * [that half | z[b][0 : chunk_len[b])] (chunk_len = 0: a copy).  step / chunk_len / slot_max_chunks as above (slot mode needs
+ * slot_max_chunks > 0; a slot that is not live leaves both halves of its pair alone).  D a multiple of 4, <= 4096. */
+int m3_dwconv_ln_silu_stream(const float* z, const float* w_kc, const float* bias, const float* gamma, const float* beta, float eps, int B,
+                             int T, int D, int K, float* cache_pair, const int32_t* step, const int32_t* chunk_len, int slot_max_chunks,
+                             float* out, m3_stream stream);
+/* m3_dwconv_ln_silu_causal: the same conv on whole utterances, dense padded rows z / out [B*T][D]; every frame left of frame 0
+ * is the row left_fill [D] (convolution.py:43-49,118-123: what pointwise_conv1 + GLU make of the module's zero padding). */
+int m3_dwconv_ln_silu_causal(const float* z, const float* w_kc, const float* bias, const float* gamma, const float* beta, float eps,
+                             const float* left_fill, int B, int T, int D, int K, float* out, m3_stream stream);
 /* Conv2dSubsampling4 (subsampling.py:103-145) on channel-last data: conv1 (1->C, 3x3, s2) + ReLU. */
 int m3_subsample_conv1(const float* feat, const float* w9c, const float* bias, int B, int T, int idim, int C,
                        float* out, m3_stream stream);

@@ -19,6 +19,7 @@ from m3asr import ops, _lib
 from m3asr._lib import M3Error
 from m3asr.plan import fold_layernorm
 from oracle import encoder_ref as ref
+from stream_kernels_ref import attention_ref as _attention_ref
 
 
 def rnd(*shape, seed=0, scale=1.0):
@@ -319,26 +320,6 @@ def test_linear_rejects_bad_strides(kw):
 
 
 # ================================================================================================ attention
-def _attention_ref(qkv, p, u, v, L, B, T, H, dk, chunk=0, left=-1, round_q16=False, dtype=torch.float64):
-    D = H * dk
-    q, k, vv = [t.to(dtype).view(B, T, H, dk) for t in qkv.view(B, T, 3 * D).split(D, -1)]
-    pp = p.to(dtype).view(1, T, H, dk)
-    qu, qv = q + u.to(dtype), q + v.to(dtype)
-    if round_q16:
-        qu, qv = r16(qu), r16(qv)
-    ac = torch.matmul(qu.transpose(1, 2), k.permute(0, 2, 3, 1))
-    bd = torch.matmul(qv.transpose(1, 2), pp.permute(0, 2, 3, 1))
-    hide = (torch.arange(T).view(1, 1, 1, T) >= L.view(B, 1, 1, 1)).expand(B, 1, T, T).clone()
-    if chunk > 0:
-        i, j = torch.arange(T).view(T, 1), torch.arange(T).view(1, T)
-        c = i // chunk
-        lo = torch.zeros_like(c) if left < 0 else ((c - left) * chunk).clamp(min=0)
-        hide |= ((j < lo) | (j >= (c + 1) * chunk)).view(1, 1, T, T)
-    att = torch.softmax(((ac + bd) / math.sqrt(dk)).masked_fill(hide, -float("inf")), -1)
-    att = torch.nan_to_num(att, nan=0.0).masked_fill(hide, 0.0)          # a row with no visible key: zeros
-    return torch.matmul(att, vv.transpose(1, 2)).transpose(1, 2).reshape(B * T, D)
-
-
 ATT_SHAPES = [(1, 50, 8, 64, [50]), (2, 50, 8, 64, [50, 36]), (2, 37, 4, 128, [37, 5]), (3, 9, 2, 16, [9, 6, 1]), (1, 124, 8, 64, [124]),
               (16, 124, 8, 64, [124, 12, 99, 124, 77, 64, 65, 1, 124, 33, 120, 124, 50, 63, 17, 101]),
               (12, 70, 4, 128, [70, 66, 3, 64, 65, 70, 1, 20, 70, 70, 48, 49]),
