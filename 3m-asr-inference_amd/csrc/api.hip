@@ -360,6 +360,17 @@ int m3_dwconv_ln_silu(const float* z, const float* w_kc, const float* bias, cons
                       float eps, int B, int T, int D, int K, float* out, m3_stream stream) {
   return launch_dwconv_ln_silu(z, w_kc, bias, gamma, beta, eps, B, T, D, K, out, (hipStream_t)stream);
 }
+int m3_dwconv_glu_ln_silu(const float* vg, int ldz, const float* w_kc, const float* bias, const float* gamma, const float* beta,
+                          float eps, int B, int T, int D, int K, float* out, m3_stream stream) {
+  M3_REQUIRE(B > 0 && T > 0, "dwconv (GLU on load): empty problem");
+  M3_REQUIRE(vg && w_kc && bias && out && (gamma == nullptr) == (beta == nullptr), "dwconv (GLU on load): null vg / w_kc / bias / out, or gamma without beta");
+  M3_REQUIRE(aligned16(vg) && aligned16(w_kc) && aligned16(bias) && aligned16(gamma) && aligned16(beta) && aligned16(out),
+             "dwconv (GLU on load): every operand must be 16-byte aligned");
+  DwArgs a;
+  a.z = vg; a.glu_ldz = ldz; a.w_kc = w_kc; a.bias = bias; a.gamma = gamma; a.beta = beta; a.eps = eps; a.B = B; a.T = T; a.D = D; a.K = K; a.out = out;
+  M3_REQUIRE(ldz > 0, "dwconv (GLU on load): ldz=%d", ldz);
+  return launch_dwconv_ln_silu_args(a, (hipStream_t)stream);
+}
 // The stateful launches of the chunk-by-chunk engine (engine.hip "att_stream" / "conv.dw_ln_silu" stages) at the boundary: argument
 // checks and one launcher call each.  What lives on the device (the counters, chunk_len) cannot be checked here.
 int m3_relpos_attention_stream(const float* qkv, int ldq, float* hist, int cap, const float* p, int ldp, int p_rows, const float* pos_u,

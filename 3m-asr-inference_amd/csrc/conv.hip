@@ -41,19 +41,25 @@ struct DwCausal {
 //  see gemm.hip / engine.hip "horizontal fusion")
 // SLOTS is a template parameter for the same reason: the lockstep streaming form reads ONE counter, slot mode utterance b's own
 // (cs.step[b]); a slot that is not live in this chunk (stream_slot_live) leaves its cache pair alone.
-template <int KT, bool CAUSAL, bool SLOTS = false>
+// GLU_IN (symmetric form only): z is the pointwise_conv1 GEMM's raw [rows][ldz] output, value columns [0, D) | gate columns
+// [D, 2 D) (bias added, no GLU): every tap is value * sigmoid(gate) as it is loaded -- the operation, and the operands, the GEMM's
+// GLU epilogue has (gemm_epilogue.h), so the taps hold the same bits.  The GEMM in front then is the plain one-column-tile form:
+// twice the work-groups, 64 instead of 96 KB of operands through each CU.  All 2 K row loads still precede the first use.
+template <int KT, bool CAUSAL, bool SLOTS = false, bool GLU_IN = false>
 __device__ __forceinline__ void dwconv_ln_silu_body(const float* __restrict__ z, const float* __restrict__ w_kc,
                                                     const float* __restrict__ bias, const float* __restrict__ gamma,
                                                     const float* __restrict__ beta, float eps, int T, int D, int K,
                                                     float* __restrict__ out, int out_bf16, const int32_t* __restrict__ pad_of,
                                                     const int32_t* __restrict__ row0, const int32_t* __restrict__ row_len,
-                                                    int n_rows, const DwCausal& cs, const int row) {
+                                                    int n_rows, const DwCausal& cs, const int row, const int ldz = 0) {
+  static_assert(!GLU_IN || (!CAUSAL && !SLOTS), "GLU on load: the symmetric conv only");
   __shared__ float red[2][16];
   // one batch of kernel-argument loads instead of one per first use (see gemm.hip: ~6 dependent s_load rounds otherwise)
   asm volatile("" ::"s"(z), "s"(w_kc), "s"(bias), "s"(gamma), "s"(beta), "s"(eps), "s"(T), "s"(D), "s"(K), "s"(out), "s"(out_bf16),
                "s"(pad_of), "s"(row0), "s"(row_len), "s"(n_rows));
   const int c = threadIdx.x * 4;
   const bool live = c < D;
+  const size_t zs = GLU_IN ? (size_t)ldz : (size_t)D;   // row stride of z
   const float* leftp = cs.left;
   if (CAUSAL && cs.step != nullptr) {                         // streaming: read half (step & 1), write the other one
     int par;
@@ -99,14 +105,14 @@ __device__ __forceinline__ void dwconv_ln_silu_body(const float* __restrict__ z,
   if (live) {
     v = ldg4(bias + c);
     for (int k0 = 0; k0 < K; k0 += KT) {
-      f32x4 zz[KT], ww[KT];
+      f32x4 zz[KT], ww[KT], gg[GLU_IN ? KT : 1];
       float on[KT];
 #pragma unroll
       for (int kk = 0; kk < KT; ++kk) {
         const int k = min(k0 + kk, K - 1);
         const int tt = t + k - pad;
         const int tc = min(max(tt, 0), T - 1);
-        const float* src = z + (tc < len ? r0 + tc : rpad) * D;
+        const float* src = z + (tc < len ? r0 + tc : rpad) * zs;
         if (CAUSAL) {                                 // no taps to the right; frames left of the utterance come from `left`
           on[kk] = (k0 + kk < K) ? 1.f : 0.f;
           if (tt < 0) src = leftp + (long)tt * cs.left_t_stride;
@@ -114,7 +120,17 @@ __device__ __forceinline__ void dwconv_ln_silu_body(const float* __restrict__ z,
           on[kk] = (k0 + kk < K && tt >= 0 && tt < T) ? 1.f : 0.f;
         }
         zz[kk] = ldg4(src + c);
+        if (GLU_IN) gg[kk] = ldg4(src + D + c);
         ww[kk] = ldg4(w_kc + (size_t)k * D + c);
+      }
+      if (GLU_IN) {
+        // all 3 K loads are issued before the first sigmoid: the 60 exp + divide of a thread would otherwise be scheduled between
+        // them and the taps would arrive in six or seven dependent round trips instead of one
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int kk = 0; kk < KT; ++kk)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) zz[kk][j] = zz[kk][j] * sigmoidf(gg[kk][j]);
       }
 #pragma unroll
       for (int kk = 0; kk < KT; ++kk)
@@ -164,34 +180,38 @@ __device__ __forceinline__ void dwconv_ln_silu_body(const float* __restrict__ z,
   }
 }
 
-template <int KT, bool CAUSAL, bool SLOTS = false>
-__global__ __launch_bounds__(1024) void dwconv_ln_silu_kernel(const float* __restrict__ z, const float* __restrict__ w_kc,
+// (GLU_IN holds 2 K row fragments + K weight fragments per thread: 256 threads (D <= 1024) leave a wave the registers for them)
+template <int KT, bool CAUSAL, bool SLOTS = false, bool GLU_IN = false>
+__global__ __launch_bounds__(GLU_IN ? 256 : 1024) void dwconv_ln_silu_kernel(const float* __restrict__ z, const float* __restrict__ w_kc,
                                                               const float* __restrict__ bias,
                                                               const float* __restrict__ gamma,
                                                               const float* __restrict__ beta, float eps, int T,
                                                               int D, int K, float* __restrict__ out, int out_bf16,
                                                               const int32_t* __restrict__ pad_of,
                                                               const int32_t* __restrict__ row0,
-                                                              const int32_t* __restrict__ row_len, int n_rows, DwCausal cs) {
-  dwconv_ln_silu_body<KT, CAUSAL, SLOTS>(z, w_kc, bias, gamma, beta, eps, T, D, K, out, out_bf16, pad_of, row0, row_len, n_rows, cs, (int)blockIdx.x);
+                                                              const int32_t* __restrict__ row_len, int n_rows, DwCausal cs, int ldz) {
+  dwconv_ln_silu_body<KT, CAUSAL, SLOTS, GLU_IN>(z, w_kc, bias, gamma, beta, eps, T, D, K, out, out_bf16, pad_of, row0, row_len, n_rows, cs,
+                                                 (int)blockIdx.x, ldz);
 }
 struct DwKernArgs {
   const float *z, *w_kc, *bias, *gamma, *beta; float eps; int T, D, K; float* out; int out_bf16;
-  const int32_t *pad_of, *row0, *row_len; int n_rows; DwCausal cs;
+  const int32_t *pad_of, *row0, *row_len; int n_rows; DwCausal cs; int ldz;
 };
-template <int KT, bool CAUSAL>
-__global__ __launch_bounds__(1024) void dwconv_ln_silu_dual_kernel(const DwKernArgs a, const DwKernArgs b) {
+template <int KT, bool CAUSAL, bool GLU_IN = false>
+__global__ __launch_bounds__(GLU_IN ? 256 : 1024) void dwconv_ln_silu_dual_kernel(const DwKernArgs a, const DwKernArgs b) {
   if ((int)blockIdx.x < a.n_rows)
-    dwconv_ln_silu_body<KT, CAUSAL>(a.z, a.w_kc, a.bias, a.gamma, a.beta, a.eps, a.T, a.D, a.K, a.out, a.out_bf16, a.pad_of, a.row0, a.row_len,
-                                    a.n_rows, a.cs, (int)blockIdx.x);
+    dwconv_ln_silu_body<KT, CAUSAL, false, GLU_IN>(a.z, a.w_kc, a.bias, a.gamma, a.beta, a.eps, a.T, a.D, a.K, a.out, a.out_bf16, a.pad_of, a.row0,
+                                                   a.row_len, a.n_rows, a.cs, (int)blockIdx.x, a.ldz);
   else
-    dwconv_ln_silu_body<KT, CAUSAL>(b.z, b.w_kc, b.bias, b.gamma, b.beta, b.eps, b.T, b.D, b.K, b.out, b.out_bf16, b.pad_of, b.row0, b.row_len,
-                                    b.n_rows, b.cs, (int)blockIdx.x - a.n_rows);
+    dwconv_ln_silu_body<KT, CAUSAL, false, GLU_IN>(b.z, b.w_kc, b.bias, b.gamma, b.beta, b.eps, b.T, b.D, b.K, b.out, b.out_bf16, b.pad_of, b.row0,
+                                                   b.row_len, b.n_rows, b.cs, (int)blockIdx.x - a.n_rows, b.ldz);
 }
 
 static int launch_dwconv_impl(const float* z, const float* w_kc, const float* bias, const float* gamma, const float* beta, float eps,
                               int B, int T, int D, int K, float* out, hipStream_t stream, int out_bf16, const int32_t* pad_of,
-                              const int32_t* row0, const int32_t* row_len, const DwCausal& cs, bool slots = false) {
+                              const int32_t* row0, const int32_t* row_len, const DwCausal& cs, bool slots = false, int glu_ldz = 0) {
+  M3_REQUIRE(glu_ldz == 0 || dwconv_glu_in_supports(D, K, cs.causal != 0 || slots, out_bf16, glu_ldz),
+             "dwconv (GLU on load): needs the symmetric fp32 conv, K <= 15, 256 <= channels <= 1024, ldz=%d a multiple of 4 and >= %d", glu_ldz, 2 * D);
   M3_REQUIRE(!slots || (cs.causal && cs.step != nullptr && cs.max_chunks > 0), "dwconv (slot mode): needs the streaming causal form");
   M3_REQUIRE((D & 3) == 0 && D <= 4096, "dwconv: channels=%d must be a multiple of 4 (<=4096)", D);
   M3_REQUIRE(cs.causal || (K & 1) == 1, "dwconv: kernel size %d must be odd (non-causal)", K);
@@ -202,11 +222,14 @@ static int launch_dwconv_impl(const float* z, const float* w_kc, const float* bi
   const int grid = rows + (cs.step != nullptr ? B * (K - 1) : 0);     // streaming: + the work-groups that write the new cache
 #define M3_DW_CASE(KT_, C_)                                                                                                  \
   hipLaunchKernelGGL((dwconv_ln_silu_kernel<KT_, C_>), dim3(grid), dim3(threads), 0, stream, z, w_kc, bias, gamma, beta, eps, T, \
-                     D, K, out, out_bf16, pad_of, row0, row_len, rows, cs)
+                     D, K, out, out_bf16, pad_of, row0, row_len, rows, cs, 0)
 #define M3_DW_SLOTS(KT_)                                                                                                        \
   hipLaunchKernelGGL((dwconv_ln_silu_kernel<KT_, true, true>), dim3(grid), dim3(threads), 0, stream, z, w_kc, bias, gamma, beta, eps, \
-                     T, D, K, out, out_bf16, pad_of, row0, row_len, rows, cs)
-  if (slots) { if (K <= 15) M3_DW_SLOTS(15); else M3_DW_SLOTS(8); }
+                     T, D, K, out, out_bf16, pad_of, row0, row_len, rows, cs, 0)
+  if (glu_ldz)
+    hipLaunchKernelGGL((dwconv_ln_silu_kernel<15, false, false, true>), dim3(grid), dim3(threads), 0, stream, z, w_kc, bias, gamma, beta, eps, T,
+                       D, K, out, out_bf16, pad_of, row0, row_len, rows, cs, glu_ldz);
+  else if (slots) { if (K <= 15) M3_DW_SLOTS(15); else M3_DW_SLOTS(8); }
   else if (K <= 15) { if (cs.causal) M3_DW_CASE(15, true); else M3_DW_CASE(15, false); }
   else { if (cs.causal) M3_DW_CASE(8, true); else M3_DW_CASE(8, false); }
 #undef M3_DW_SLOTS
@@ -223,12 +246,25 @@ int launch_dwconv_ln_silu(const float* z, const float* w_kc, const float* bias, 
   return launch_dwconv_impl(z, w_kc, bias, gamma, beta, eps, B, T, D, K, out, stream, out_bf16, pad_of, row0, row_len, cs);
 }
 
+bool dwconv_glu_in_supports(int D, int K, bool causal_or_stream, int out_bf16, int ldz) {
+  return !causal_or_stream && !out_bf16 && (K & 1) == 1 && K <= 15 && D >= 256 && D <= 1024 && (D & 3) == 0 && ldz >= 2 * D && (ldz & 3) == 0;
+}
+
 int launch_dwconv_ln_silu_args(const DwArgs& a, hipStream_t stream) {
+  if (a.glu_ldz) {
+    M3_REQUIRE(a.causal_left_fill == nullptr, "dwconv (GLU on load): the symmetric conv only");
+    return launch_dwconv_impl(a.z, a.w_kc, a.bias, a.gamma, a.beta, a.eps, a.B, a.T, a.D, a.K, a.out, stream, a.out_bf16, a.pad_of, a.row0, a.row_len,
+                              DwCausal{}, false, a.glu_ldz);
+  }
   return launch_dwconv_ln_silu(a.z, a.w_kc, a.bias, a.gamma, a.beta, a.eps, a.B, a.T, a.D, a.K, a.out, stream, a.out_bf16, a.pad_of, a.row0,
                                a.row_len, a.causal_left_fill);
 }
 // two independent conv modules of the same shape class (channels, taps, causal or not) in ONE launch
 bool dwconv_dual_fusable(const DwArgs& a, const DwArgs& b) {
+  if ((a.glu_ldz != 0) != (b.glu_ldz != 0)) return false;
+  if (a.glu_ldz && !(dwconv_glu_in_supports(a.D, a.K, a.causal_left_fill != nullptr, a.out_bf16, a.glu_ldz) &&
+                     dwconv_glu_in_supports(b.D, b.K, b.causal_left_fill != nullptr, b.out_bf16, b.glu_ldz)))
+    return false;
   return a.D == b.D && a.K == b.K && (a.causal_left_fill != nullptr) == (b.causal_left_fill != nullptr) && a.B * a.T > 0 && b.B * b.T > 0 &&
          (a.D & 3) == 0 && a.D <= 4096 && (a.causal_left_fill != nullptr || (a.K & 1) == 1);
 }
@@ -239,13 +275,15 @@ int launch_dwconv_ln_silu_dual(const DwArgs& a, const DwArgs& b, hipStream_t str
     k.z = q.z; k.w_kc = q.w_kc; k.bias = q.bias; k.gamma = q.gamma; k.beta = q.beta; k.eps = q.eps; k.T = q.T; k.D = q.D; k.K = q.K;
     k.out = q.out; k.out_bf16 = q.out_bf16; k.pad_of = q.pad_of; k.row0 = q.row0; k.row_len = q.row_len; k.n_rows = q.B * q.T;
     if (q.causal_left_fill != nullptr) { k.cs.causal = 1; k.cs.left = q.causal_left_fill; }
+    k.ldz = q.glu_ldz;
     return k;
   };
   const DwKernArgs ka = pack(a), kb = pack(b);
   const int threads = (int)align_up(a.D / 4, 64), grid = ka.n_rows + kb.n_rows;
   const bool causal = a.causal_left_fill != nullptr;
 #define M3_DWD_CASE(KT_, C_) hipLaunchKernelGGL((dwconv_ln_silu_dual_kernel<KT_, C_>), dim3(grid), dim3(threads), 0, stream, ka, kb)
-  if (a.K <= 15) { if (causal) M3_DWD_CASE(15, true); else M3_DWD_CASE(15, false); }
+  if (a.glu_ldz) hipLaunchKernelGGL((dwconv_ln_silu_dual_kernel<15, false, true>), dim3(grid), dim3(threads), 0, stream, ka, kb);
+  else if (a.K <= 15) { if (causal) M3_DWD_CASE(15, true); else M3_DWD_CASE(15, false); }
   else { if (causal) M3_DWD_CASE(8, true); else M3_DWD_CASE(8, false); }
 #undef M3_DWD_CASE
   M3_LAUNCH_CHECK();
@@ -271,17 +309,17 @@ int launch_dwconv_ln_silu_stream(const float* z, const float* w_kc, const float*
 // One work-group per output row (b, t1): thread = 4 channels.  The thread's 9 x 4 weights and bias stay in registers,
 // the three input rows (CMVN applied on the way) sit in LDS and are read as broadcasts, and the work-group walks the F1
 // output columns writing C contiguous channels each -- no per-element index arithmetic, no weight reloads, 1-2 KB stores.
-__global__ __launch_bounds__(256) void conv1_relu_kernel(const float* __restrict__ feat, const float* __restrict__ w9c,
-                                                         const float* __restrict__ bias,
-                                                         const float* __restrict__ cmvn_mean,
-                                                         const float* __restrict__ cmvn_istd, int T, int idim, int T1,
-                                                         int F1, int C, float* __restrict__ out, int relu, int out_bf16,
-                                                         const int32_t* __restrict__ feat_len, int32_t* __restrict__ lens_out, int B) {
+// (the body as a device function of the work-group's output row and column chunk: conv1_relu_dual_kernel runs the embed and the
+//  main subsampler's first conv, which read the same features, in one launch)
+__device__ __forceinline__ void conv1_relu_body(const float* __restrict__ feat, const float* __restrict__ w9c,
+                                                const float* __restrict__ bias, const float* __restrict__ cmvn_mean,
+                                                const float* __restrict__ cmvn_istd, int T, int idim, int T1, int F1, int C,
+                                                float* __restrict__ out, int relu, int out_bf16, const int32_t* __restrict__ feat_len,
+                                                int32_t* __restrict__ lens_out, int B, const int row) {   // row = b * T1 + t1
   extern __shared__ float xs[];                       // [3][idim]
-  const int row = blockIdx.x;                         // b * T1 + t1
   // the engine's first launch also forms the valid lengths after the two stride-2 convs (both MaskConv2dSample applications,
   // subsampling.py:119-137) -- one launch less at the head of every forward
-  if (feat_len != nullptr && blockIdx.x == 0 && blockIdx.y == 0)
+  if (feat_len != nullptr && row == 0 && blockIdx.y == 0)
     for (int i = threadIdx.x; i < B; i += blockDim.x) lens_out[i] = ((feat_len[i] - 3) / 2 + 1 - 3) / 2 + 1;
   const int b = row / T1, t1 = row - b * T1;
   const float* src = feat + ((size_t)b * T + 2 * t1) * idim;
@@ -330,6 +368,32 @@ __global__ __launch_bounds__(256) void conv1_relu_kernel(const float* __restrict
   }
 }
 
+__global__ __launch_bounds__(256) void conv1_relu_kernel(const float* __restrict__ feat, const float* __restrict__ w9c,
+                                                         const float* __restrict__ bias,
+                                                         const float* __restrict__ cmvn_mean,
+                                                         const float* __restrict__ cmvn_istd, int T, int idim, int T1,
+                                                         int F1, int C, float* __restrict__ out, int relu, int out_bf16,
+                                                         const int32_t* __restrict__ feat_len, int32_t* __restrict__ lens_out, int B) {
+  conv1_relu_body(feat, w9c, bias, cmvn_mean, cmvn_istd, T, idim, T1, F1, C, out, relu, out_bf16, feat_len, lens_out, B, (int)blockIdx.x);
+}
+// both problems: the same input shape (B, T, idim), so the same T1, F1 and column split; the second problem's rows start at n0,
+// a multiple of 8
+struct Conv1KernArgs {
+  const float *feat, *w9c, *bias, *cmvn_mean, *cmvn_istd; int C; float* out; int relu, out_bf16; const int32_t* feat_len; int32_t* lens_out;
+};
+__global__ __launch_bounds__(256) void conv1_relu_dual_kernel(const Conv1KernArgs a, const Conv1KernArgs b, int T, int idim, int T1, int F1,
+                                                              int B, int rows, int n0) {
+  const int id = (int)blockIdx.x;
+  if (id < n0) {
+    if (id < rows)
+      conv1_relu_body(a.feat, a.w9c, a.bias, a.cmvn_mean, a.cmvn_istd, T, idim, T1, F1, a.C, a.out, a.relu, a.out_bf16, a.feat_len, a.lens_out, B, id);
+  } else {
+    conv1_relu_body(b.feat, b.w9c, b.bias, b.cmvn_mean, b.cmvn_istd, T, idim, T1, F1, b.C, b.out, b.relu, b.out_bf16, b.feat_len, b.lens_out, B, id - n0);
+  }
+}
+
+static int conv1_fsplit(int rows) { return rows >= 2048 ? 1 : (rows >= 512 ? 2 : 5); }
+
 int launch_conv1_relu(const float* feat, const float* w9c, const float* bias, const float* cmvn_mean,
                       const float* cmvn_istd, int B, int T, int idim, int C, float* out, hipStream_t stream, int relu, int out_bf16,
                       const int32_t* feat_len, int32_t* lens_out) {
@@ -338,9 +402,31 @@ int launch_conv1_relu(const float* feat, const float* w9c, const float* bias, co
   const int T1 = (T - 3) / 2 + 1, F1 = (idim - 3) / 2 + 1;
   if (B * T1 == 0) return 0;
   const int threads = (int)align_up(C / 4, 64);
-  const int fsplit = B * T1 >= 2048 ? 1 : (B * T1 >= 512 ? 2 : 5);
+  const int fsplit = conv1_fsplit(B * T1);
   hipLaunchKernelGGL(conv1_relu_kernel, dim3(B * T1, fsplit), dim3(threads), 3 * idim * sizeof(float), stream,
                      feat, w9c, bias, cmvn_mean, cmvn_istd, T, idim, T1, F1, C, out, relu, out_bf16, feat_len, lens_out, B);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+int launch_conv1_relu_args(const Conv1Args& a, hipStream_t stream) {
+  return launch_conv1_relu(a.feat, a.w9c, a.bias, a.cmvn_mean, a.cmvn_istd, a.B, a.T, a.idim, a.C, a.out, stream, a.relu, a.out_bf16, a.feat_len,
+                           a.lens_out);
+}
+bool conv1_dual_fusable(const Conv1Args& a, const Conv1Args& b) {
+  auto ok = [](const Conv1Args& q) { return q.T >= 3 && q.idim >= 3 && (q.C & 3) == 0 && q.C > 0 && q.C <= 1024; };
+  return ok(a) && ok(b) && a.B == b.B && a.T == b.T && a.idim == b.idim && a.B * ((a.T - 3) / 2 + 1) > 0 && a.out != b.out;
+}
+int launch_conv1_relu_dual(const Conv1Args& a, const Conv1Args& b, hipStream_t stream) {
+  M3_REQUIRE(conv1_dual_fusable(a, b), "subsampling conv1 dual: the two problems do not share an input shape");
+  const int T1 = (a.T - 3) / 2 + 1, F1 = (a.idim - 3) / 2 + 1, rows = a.B * T1;
+  auto pack = [](const Conv1Args& q) {
+    return Conv1KernArgs{q.feat, q.w9c, q.bias, q.cmvn_mean, q.cmvn_istd, q.C, q.out, q.relu, q.out_bf16, q.feat_len, q.lens_out};
+  };
+  const int threads = (int)align_up((a.C > b.C ? a.C : b.C) / 4, 64);
+  const int n0 = (int)align_up((size_t)rows, 8);
+  hipLaunchKernelGGL(conv1_relu_dual_kernel, dim3(n0 + rows, conv1_fsplit(rows)), dim3(threads), 3 * a.idim * sizeof(float), stream, pack(a), pack(b),
+                     a.T, a.idim, T1, F1, a.B, rows, n0);
   M3_LAUNCH_CHECK();
   return 0;
 }

@@ -55,8 +55,9 @@ struct BlockW {
 struct SubW { const float* c1w; const float* c1b; const float* c2w; const float* c2b; Lin out; };
 
 // what horizontal fusion pairs up (fuse_independent_pairs): a one-launch dense GEMM stage (Stage::gemm + its plan), the conv module's
-// depthwise conv + LayerNorm + SiLU (Stage::dw), the fp32 rel-pos attention core (Stage::att)
-enum class FuseKind { None, Gemm, Dwconv, Attention };
+// depthwise conv + LayerNorm + SiLU (Stage::dw), the fp32 rel-pos attention core (Stage::att), and of the two subsamplers the first
+// conv (Stage::c1) and the split-K GEMM + reduce stages (Stage::gemm + its plan + Stage::gemm_ws; two launches before and after)
+enum class FuseKind { None, Gemm, Dwconv, Attention, Conv1, SplitK };
 
 struct Stage {
   std::string name;
@@ -64,7 +65,8 @@ struct Stage {
   m3_stage_info info;   // kernel label + algorithmic bytes / FLOPs of the stage (m3_engine_stage_info)
   bool reads_embed = false;   // reads the embed encoder's output (pl.emb, or pl.eall computed from it): where the chains join
   FuseKind fuse_kind = FuseKind::None;
-  GemmParams gemm; GemmPlan gemm_plan;
+  GemmParams gemm; GemmPlan gemm_plan; float* gemm_ws = nullptr;
+  Conv1Args c1;
   DwArgs dw;
   AttArgs att;
 };
@@ -176,6 +178,14 @@ struct Switches {
   // but 4.58 -> 4.45 M frames/s at four contexts (twice the partial-output slabs; the idle CUs were being used by the other
   // contexts' kernels)
   bool fused8_adapt;
+  // M3_GLU_DEFER (1): 0 = the conv module's pointwise_conv1 keeps its GLU epilogue at every shape.  1: fp32 plans, symmetric
+  // conv module, 16-row-tile skinny GEMM, 256 <= D <= 1024: pointwise_conv1 runs as the plain folded-LayerNorm form and the
+  // depthwise kernel applies the GLU to the taps it loads (glu_deferred)
+  bool glu_defer;
+  // M3_FRONT_PAIR (1): 0 = the two subsamplers keep their five launches each.  1: where both second convs plan as split-K
+  // (C >= 512) and the embed chain is interleaved with the main prefix (M3_HFUSE), conv1, conv2 + reduce and Linear + reduce of
+  // the two run as one launch each
+  bool front_pair;
 };
 const Switches& switches() {
   static const Switches sw = [] {
@@ -188,6 +198,8 @@ const Switches& switches() {
     w.router_xq = num("M3_ROUTER_XQ", 1) != 0;
     w.router_skip_xn = num("M3_ROUTER_SKIP_XN", 0) != 0;
     w.fused8_adapt = num("M3_FUSED8_ADAPT", 0) != 0;
+    w.glu_defer = num("M3_GLU_DEFER", 1) != 0;
+    w.front_pair = num("M3_FRONT_PAIR", 1) != 0;
     return w;
   }();
   return sw;
@@ -382,7 +394,9 @@ Plan make_plan(const m3_engine_config& c, void* base, int B, int T, int ep_capac
   p.qkv = cv.take<float>((size_t)S * 3 * D);
   p.pbuf = cv.take<float>((size_t)Tp * D * (c.num_blocks + c.embed_blocks));
   p.ctx = cv.take<float>((size_t)S * D);
-  p.glu = cv.take<float>((size_t)S * D);
+  // (pointwise_conv1's raw value | gate columns where the GLU is deferred to the depthwise kernel: glu_deferred)
+  const size_t glu_floats = (size_t)S * D * (switches().glu_defer && c.weight_dtype == M3_F32 && D >= 256 ? 2 : 1);
+  p.glu = cv.take<float>(glu_floats);
   p.dw = cv.take<float>((size_t)S * D);
   p.xn = cv.take<float>((size_t)S * D);
   p.xq = nullptr; p.xq_scale = nullptr; p.moe_fs = nullptr;
@@ -450,7 +464,7 @@ Plan make_plan(const m3_engine_config& c, void* base, int B, int T, int ep_capac
     p.e_h1 = cv.take<float>((size_t)S * F);
     p.e_qkv = cv.take<float>((size_t)S * 3 * D);
     p.e_ctx = cv.take<float>((size_t)S * D);
-    p.e_glu = cv.take<float>((size_t)S * D);
+    p.e_glu = cv.take<float>(glu_floats);
     p.e_dw = cv.take<float>((size_t)S * D);
     if (p.splitk_bytes) p.e_splitk = cv.take<float>(p.splitk_bytes / sizeof(float));
     if (use_packed_rows(c, B)) {      // (not `if (p.xpad)`: the sizing pass carves from a null base)
@@ -612,6 +626,10 @@ static void add_gemm(StageBuilder& sb, const std::string& name, GemmParams p, bo
     sb.bd.stages.back().fuse_kind = FuseKind::Gemm;
     sb.bd.stages.back().gemm = p;
     sb.bd.stages.back().gemm_plan = plan;
+  } else if (plan.kernel == GemmKernel::SplitKF32 && plan.launches == 2) {   // (build_subsample decides whether it may pair)
+    sb.bd.stages.back().gemm = p;
+    sb.bd.stages.back().gemm_plan = plan;
+    sb.bd.stages.back().gemm_ws = ws;
   }
 }
 
@@ -626,13 +644,28 @@ static bool stages_fusable(const Stage& a, const Stage& b) {
   if (a.fuse_kind == FuseKind::Gemm) return gemm_dual_fusable(a.gemm_plan, b.gemm_plan);
   if (a.fuse_kind == FuseKind::Dwconv) return dwconv_dual_fusable(a.dw, b.dw);
   if (a.fuse_kind == FuseKind::Attention) return relpos_attention_dual_fusable(a.att, b.att);
+  if (a.fuse_kind == FuseKind::Conv1) return conv1_dual_fusable(a.c1, b.c1);
+  if (a.fuse_kind == FuseKind::SplitK) return gemm_splitk_dual_fusable(a.gemm_plan, b.gemm_plan) && a.gemm_ws != b.gemm_ws;
   return false;
 }
-static Stage fused_stage(const Stage& a, const Stage& b) {
+// (a split-K pair is two stages, the GEMM launch and the reduce launch -- `reduce_half`, named a.reduce+b.reduce: every stage
+//  named a+b is one launch that replaces two)
+static Stage fused_stage(const Stage& a, const Stage& b, bool reduce_half = false) {
   Stage d;
-  d.name = a.name + "+" + b.name;
+  d.name = reduce_half ? a.name + ".reduce+" + b.name + ".reduce" : a.name + "+" + b.name;
   const char* label = "";
-  if (a.fuse_kind == FuseKind::Gemm) {
+  if (a.fuse_kind == FuseKind::Conv1) {
+    const Conv1Args pa = a.c1, pb = b.c1;
+    d.run = [pa, pb](hipStream_t s) { return launch_conv1_relu_dual(pa, pb, s); };
+    label = "conv1_relu_dual_kernel";
+  } else if (a.fuse_kind == FuseKind::SplitK) {
+    const GemmParams pa = a.gemm, pb = b.gemm;
+    const GemmPlan qa = a.gemm_plan, qb = b.gemm_plan;
+    float* const wa = a.gemm_ws; float* const wb = b.gemm_ws;
+    const int which = reduce_half ? 2 : 1;
+    d.run = [qa, pa, wa, qb, pb, wb, which](hipStream_t s) { return launch_gemm_f32_splitk_dual(qa, pa, wa, qb, pb, wb, s, which); };
+    label = "gemm_f32_splitk_dual_kernel";   // (both halves: the unpaired stage carries its reduce under the GEMM's label too)
+  } else if (a.fuse_kind == FuseKind::Gemm) {
     const GemmParams pa = a.gemm, pb = b.gemm;
     const GemmPlan qa = a.gemm_plan, qb = b.gemm_plan;
     d.run = [qa, pa, qb, pb](hipStream_t s) { return launch_gemm_f32_dual(qa, pa, qb, pb, s); };
@@ -646,7 +679,9 @@ static Stage fused_stage(const Stage& a, const Stage& b) {
     d.run = [pa, pb](hipStream_t s) { return launch_relpos_attention_dual(pa, pb, s); };
     label = "relpos_attention_dual_kernel";
   }
-  d.info = stage_info(label, 1, a.info.alg_bytes + b.info.alg_bytes, a.info.flops + b.info.flops);
+  // (the algorithmic bytes and FLOPs of a split-K pair stand with its GEMM stage; the partial tiles are not algorithmic traffic)
+  d.info = reduce_half ? stage_info(label, 1, 0.0, 0.0, a.info.per_row != 0)
+                       : stage_info(label, 1, a.info.alg_bytes + b.info.alg_bytes, a.info.flops + b.info.flops, a.info.per_row != 0);
   return d;
 }
 static void fuse_independent_pairs(StageBuilder& sb, int first, int mid, int join) {
@@ -659,15 +694,20 @@ static void fuse_independent_pairs(StageBuilder& sb, int first, int mid, int joi
     assert(!st[m].reads_embed);                       // (moved ahead of embed stages: must not need the embedding)
     int partner = -1;
     if (st[m].fuse_kind != FuseKind::None)
-      for (int k = std::max(i, first + 1); k < mid; ++k)
+      // (the first embed stage pairs only as the subsamplers' conv1: no main-prefix stage is then in front of it either)
+      for (int k = st[m].fuse_kind == FuseKind::Conv1 ? i : std::max(i, first + 1); k < mid; ++k)
         if (stages_fusable(st[k], st[m])) { partner = k; break; }
     if (partner < 0) { pending.push_back(st[m]); continue; }
     for (; i < partner; ++i) out.push_back(st[i]);
     for (Stage& q : pending) out.push_back(q);
     pending.clear();
     out.push_back(fused_stage(st[partner], st[m]));
+    saved += st[partner].info.launches + st[m].info.launches - 1;
+    if (st[m].fuse_kind == FuseKind::SplitK) {
+      out.push_back(fused_stage(st[partner], st[m], true));
+      saved -= 1;
+    }
     i = partner + 1;
-    ++saved;
   }
   for (; i < mid; ++i) out.push_back(st[i]);
   for (Stage& q : pending) out.push_back(q);
@@ -697,8 +737,12 @@ static void build_subsample(StageBuilder& sb, const std::string& pfx, const SubW
   const int32_t* flen = sb.lens_in_conv1 ? sb.bd.key.feat_len : nullptr;
   int32_t* lens_out = pl.lens;
   sb.lens_in_conv1 = false;
-  add_stage(sb, pfx + "conv1", 1, [=](hipStream_t s) { return launch_conv1_relu(feat, w.c1w, w.c1b, cm, ci, B, T, idim, D, c1, s, 1, a16, flen, lens_out); },
+  Conv1Args ca;
+  ca.feat = feat; ca.w9c = w.c1w; ca.bias = w.c1b; ca.cmvn_mean = cm; ca.cmvn_istd = ci; ca.B = B; ca.T = T; ca.idim = idim; ca.C = D; ca.out = c1;
+  ca.relu = 1; ca.out_bf16 = a16; ca.feat_len = flen; ca.lens_out = lens_out;
+  add_stage(sb, pfx + "conv1", 1, [ca](hipStream_t s) { return launch_conv1_relu_args(ca, s); },
             stage_info("conv1_relu_kernel", 1, (double)B * T * idim * 4 + (double)B * T1 * F1 * D * (a16 ? 2 : 4), 18.0 * B * T1 * F1 * D, false));
+  const size_t conv1_at = sb.bd.stages.size() - 1;
   GemmParams g;
   g.a_bf16 = a16; g.y_bf16 = a16;
   g.mode = GEMM_A_CONV3X3S2; g.A = c1; g.lda = 4;
@@ -706,6 +750,15 @@ static void build_subsample(StageBuilder& sb, const std::string& pfx, const SubW
   g.W = w.c2w; g.bias = w.c2b; g.Y = c2; g.ldy = D; g.M = B * T2 * F2; g.N = D; g.K = 9 * D; g.act = ACT_RELU;
   if (sb.bd.packed) g.conv_len = pl.lens;   // tiles of padded frames only: skipped (never gathered into the packed rows)
   add_gemm(sb, pfx + "conv2", g);
+  // The front-end stages may share launches with the other subsampler's (fuse_independent_pairs) where this conv2 is a split-K
+  // problem (C >= 512): below that the launches are short, and the stage lists of the small models stay what they were.
+  const bool pairable = switches().front_pair && !a16 && !sb.bd.packed && sb.bd.stages.back().gemm_plan.kernel == GemmKernel::SplitKF32 &&
+                        sb.bd.stages.back().gemm_ws != nullptr;
+  if (pairable) {
+    sb.bd.stages[conv1_at].fuse_kind = FuseKind::Conv1;
+    sb.bd.stages[conv1_at].c1 = ca;
+    sb.bd.stages.back().fuse_kind = FuseKind::SplitK;
+  }
   // Linear(C*F2 -> D) on the (f, c)-ordered flatten, with the positional-encoding scale sqrt(D)
   // (rel_positional_encoding_kernel.cu:62-69) folded into the epilogue.
   // packed ragged batch: the subsampler works on the padded (B, T) input; its rows are packed right after it
@@ -716,6 +769,7 @@ static void build_subsample(StageBuilder& sb, const std::string& pfx, const SubW
   l.a_bf16 = a16;
   if (a16) { l.Yb = packed ? pl.xbpad : pl.xb; l.ldyb = D; }
   add_gemm(sb, pfx + "linear", l);
+  if (pairable && sb.bd.stages.back().gemm_ws != nullptr) sb.bd.stages.back().fuse_kind = FuseKind::SplitK;
   if (packed) {
     const float* xpad = pl.xpad; const void* xbpad = pl.xbpad; void* xb = pl.xb; const int32_t* pad_of = pl.pad_of;
     const int S = B * T2;
@@ -1012,6 +1066,18 @@ static void build_block(StageBuilder& sb, const std::string& pfx, const BlockW& 
     // row P thereby receives the constant a zeroed frame produces -- the depthwise conv reads it for taps len <= t < T'
     g.row_len = live_len; g.rows_per_batch = live_rpb; g.mask_in = 1;
     from_xb(g);
+    // GLU deferred to the depthwise kernel: pw1 as the plain one-column-tile form writing value | gate columns [S][2 D] (each
+    // element what the GLU epilogue holds just before its GLU line), the depthwise kernel forms value * sigmoid(gate) per tap.
+    // Same operations on the same operands: bit-identical.  Taken where a work-group's operand pull is what the launch costs
+    // (16-row tiles, D >= 256); everywhere else the stage list is what it was.
+    bool glu_deferred = false;
+    if (switches().glu_defer && c.weight_dtype == M3_F32 && !a16 && !causal && !streaming &&
+        dwconv_glu_in_supports(D, K, false, 0, 2 * D)) {
+      GemmParams r = g;
+      r.act = ACT_NONE; r.ldy = 2 * D;
+      const GemmPlan rp = plan_gemm(r, 0);
+      if (rp.launches == 1 && rp.kernel == GemmKernel::SkinnyF32 && rp.mt == 1) { g = r; glu_deferred = true; }
+    }
     add_gemm(sb, pfx + "conv.pw1_glu", g);
     const float* glu = pl.glu; float* dw = pl.dw;
     const float* dww = w.dw_w; const float* dwb = w.dw_b;
@@ -1027,8 +1093,9 @@ static void build_block(StageBuilder& sb, const std::string& pfx, const BlockW& 
       DwArgs da;
       da.z = glu; da.w_kc = dww; da.bias = dwb; da.gamma = ng; da.beta = nb; da.eps = 1e-5f; da.B = B; da.T = Tp; da.D = D; da.K = K;
       da.out = dw; da.out_bf16 = a16; da.pad_of = pad_of; da.row0 = row0; da.row_len = lens; da.causal_left_fill = lfill;
+      da.glu_ldz = glu_deferred ? 2 * D : 0;
       add_stage(sb, pfx + "conv.dw_ln_silu", 1, [da](hipStream_t s) { return launch_dwconv_ln_silu_args(da, s); },
-                stage_info("dwconv_ln_silu_kernel", 1, (double)S * D * (4 + (a16 ? 2 : 4)) + (double)K * D * 4, 2.0 * K * D * S));
+                stage_info("dwconv_ln_silu_kernel", 1, (double)S * D * ((glu_deferred ? 8 : 4) + (a16 ? 2 : 4)) + (double)K * D * 4, 2.0 * K * D * S));
       sb.bd.stages.back().fuse_kind = FuseKind::Dwconv;
       sb.bd.stages.back().dw = da;
     }
@@ -1383,6 +1450,7 @@ static int build_binding(m3_engine* e, const BindKey& k, m3_engine::Bound& bd) {
               stage_info("advance_counter_kernel", 1, 8.0, 0.0, false));
   }
   bd.buffers["x"] = Buf{pl.x, (size_t)S * D * 4};
+  bd.buffers["dw"] = Buf{pl.dw, (size_t)S * D * 4};   // the main encoder's depthwise conv + LayerNorm + SiLU output (last block run)
   if (!bd.xn_skipped) bd.buffers["xn"] = Buf{pl.xn, (size_t)S * D * 4};
   if (pl.xq != nullptr) {
     bd.buffers["xq"] = Buf{pl.xq, (size_t)S * D};

@@ -21,9 +21,12 @@ constexpr int SC_LD = SBN + 4;
 constexpr int kSplitLdsBytes = 2 * (SBM + SBN) * S_LD * 4;   // 69,632 B (the 17 KB epilogue image reuses it)
 }  // namespace
 
+// The kernel body as a device function of (parameter block, output tile, K range): gemm_f32_splitk_kernel runs one problem,
+// gemm_f32_splitk_dual_kernel two INDEPENDENT problems in one launch -- the embed and the main subsampler read the same features
+// through different weights (engine.hip "horizontal fusion").  Each problem keeps its own split count and partial tiles.
 template <bool CONV>
-__global__ __launch_bounds__(256, 2) void gemm_f32_splitk_kernel(const GemmParams p, float* __restrict__ part,
-                                                                 int ksteps_per_split) {
+__device__ __forceinline__ void gemm_f32_splitk_body(const GemmParams& p, float* __restrict__ part, const int ksteps_per_split,
+                                                     const int tile_id, const int split) {
   constexpr int MT = SBM / 32, NT = SBN / 32;
   constexpr int CA = SBK / 4, RA = 256 / CA, JA = SBM / RA, JB = SBN / RA;
   extern __shared__ __attribute__((aligned(16))) unsigned char splitk_lds[];
@@ -34,7 +37,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_splitk_kernel(const GemmParam
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int col = lane & 15, kq = lane >> 4;
   const int wm = wave >> 1, wn = wave & 1;
-  const int n_tile = blockIdx.x % p.n_tiles, m_tile = blockIdx.x / p.n_tiles, split = blockIdx.y;
+  const int n_tile = tile_id % p.n_tiles, m_tile = tile_id / p.n_tiles;
   const int m0 = m_tile * SBM, n0 = n_tile * SBN;
   const int nsteps_total = p.K / SBK;
   const int s_lo = split * ksteps_per_split, s_hi = min(s_lo + ksteps_per_split, nsteps_total);
@@ -133,12 +136,33 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_splitk_kernel(const GemmParam
   }
 }
 
+template <bool CONV>
+__global__ __launch_bounds__(256, 2) void gemm_f32_splitk_kernel(const GemmParams p, float* __restrict__ part,
+                                                                 int ksteps_per_split) {
+  gemm_f32_splitk_body<CONV>(p, part, ksteps_per_split, (int)blockIdx.x, (int)blockIdx.y);
+}
+// work-groups [0, live0) are problem 0's (tile fastest, then K range, the order of the two-dimensional grid), [n0, ...) problem
+// 1's; n0 = live0 rounded up to a multiple of 8, the ids between do nothing
+template <bool CONV>
+__global__ __launch_bounds__(256, 2) void gemm_f32_splitk_dual_kernel(const GemmParams p0, float* __restrict__ part0, int per0, int live0,
+                                                                      const GemmParams p1, float* __restrict__ part1, int per1, int n0) {
+  const int id = (int)blockIdx.x;
+  if (id < n0) {
+    const int tiles = p0.m_tiles * p0.n_tiles;
+    if (id < live0) gemm_f32_splitk_body<CONV>(p0, part0, per0, id % tiles, id / tiles);
+  } else {
+    const int tiles = p1.m_tiles * p1.n_tiles;
+    gemm_f32_splitk_body<CONV>(p1, part1, per1, (id - n0) % tiles, (id - n0) / tiles);
+  }
+}
+
 // y[m][n] = alpha * act(bias[n] + sum_s part[s][m][n]), fixed summation order
-__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ part, int splits, int M, int N,
-                                                            const float* __restrict__ bias, int act, float alpha,
-                                                            float* __restrict__ y, int ldy) {
+// (as a device function of the work-group's place among the `nblocks` of its problem: splitk_reduce_dual_kernel)
+__device__ __forceinline__ void splitk_reduce_body(const float* __restrict__ part, int splits, int M, int N,
+                                                   const float* __restrict__ bias, int act, float alpha,
+                                                   float* __restrict__ y, int ldy, const int bid, const int nblocks) {
   const size_t quads = (size_t)M * (N / 4);
-  for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < quads; q += (size_t)gridDim.x * 256) {
+  for (size_t q = (size_t)bid * 256 + threadIdx.x; q < quads; q += (size_t)nblocks * 256) {
     const int m = (int)(q / (N / 4)), n = 4 * (int)(q % (N / 4));
     f32x4 v = bias ? ldg4(bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
     for (int s0 = 0; s0 < splits; s0 += 4) {          // 4 partials in flight
@@ -160,11 +184,26 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
   }
 }
 
+__global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ part, int splits, int M, int N,
+                                                            const float* __restrict__ bias, int act, float alpha,
+                                                            float* __restrict__ y, int ldy) {
+  splitk_reduce_body(part, splits, M, N, bias, act, alpha, y, ldy, (int)blockIdx.x, (int)gridDim.x);
+}
+struct SplitkReduceArgs { const float* part; int splits, M, N; const float* bias; int act; float alpha; float* y; int ldy; int nblocks; };
+__global__ __launch_bounds__(256) void splitk_reduce_dual_kernel(const SplitkReduceArgs a, const SplitkReduceArgs b) {
+  if ((int)blockIdx.x < a.nblocks)
+    splitk_reduce_body(a.part, a.splits, a.M, a.N, a.bias, a.act, a.alpha, a.y, a.ldy, (int)blockIdx.x, a.nblocks);
+  else
+    splitk_reduce_body(b.part, b.splits, b.M, b.N, b.bias, b.act, b.alpha, b.y, b.ldy, (int)blockIdx.x - a.nblocks, b.nblocks);
+}
+
 int init_gemm_f32_splitk_kernels() {
   static PerDeviceOnce once;
   if (once.done()) return 0;
   M3_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_f32_splitk_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kSplitLdsBytes));
   M3_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_f32_splitk_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kSplitLdsBytes));
+  M3_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_f32_splitk_dual_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kSplitLdsBytes));
+  M3_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_f32_splitk_dual_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kSplitLdsBytes));
   once.mark();
   return 0;
 }
@@ -183,6 +222,40 @@ int launch_gemm_f32_splitk(const GemmPlan& plan, const GemmParams& pin, float* w
   const size_t quads = (size_t)p.M * (p.N / 4);
   hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid1d(quads, 1024)), dim3(256), 0, stream, ws, splits, p.M, p.N, p.bias, p.act,
                      p.alpha, p.Y, p.ldy);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+// two independent split-K problems (both implicit convs or both plain) in ONE GEMM launch and ONE reduce launch: each keeps its
+// split count, its partial tiles and its reduce order, so each result is what launch_gemm_f32_splitk gives, bit for bit.
+// `which`: 1 = the GEMM launch, 2 = the reduce launch, 3 = both (the engine lists them as two stages)
+bool gemm_splitk_dual_fusable(const GemmPlan& a, const GemmPlan& b) {
+  return a.launches == 2 && b.launches == 2 && a.kernel == GemmKernel::SplitKF32 && b.kernel == GemmKernel::SplitKF32 && a.conv == b.conv;
+}
+int launch_gemm_f32_splitk_dual(const GemmPlan& pa, const GemmParams& a_in, float* ws_a, const GemmPlan& pb, const GemmParams& b_in,
+                                float* ws_b, hipStream_t stream, int which) {
+  M3_REQUIRE(gemm_splitk_dual_fusable(pa, pb), "gemm split-K dual: the two problems do not share an instantiation");
+  M3_REQUIRE(ws_a != nullptr && ws_b != nullptr && ws_a != ws_b, "gemm split-K dual: each problem needs its own workspace");
+  if (int rc = init_gemm_f32_splitk_kernels()) return rc;
+  GemmParams q[2] = {a_in, b_in};
+  const GemmPlan* const plans[2] = {&pa, &pb};
+  int per[2], live[2];
+  SplitkReduceArgs r[2];
+  float* const ws[2] = {ws_a, ws_b};
+  for (int i = 0; i < 2; ++i) {
+    q[i].m_tiles = plans[i]->m_tiles; q[i].n_tiles = plans[i]->n_tiles;
+    per[i] = cdiv(q[i].K / SBK, plans[i]->splits);
+    live[i] = q[i].m_tiles * q[i].n_tiles * plans[i]->splits;
+    r[i] = SplitkReduceArgs{ws[i], plans[i]->splits, q[i].M, q[i].N, q[i].bias, q[i].act, q[i].alpha, q[i].Y, q[i].ldy,
+                            (int)grid1d((size_t)q[i].M * (q[i].N / 4), 1024)};
+  }
+  const int n0 = (int)align_up((size_t)live[0], 8);
+  const dim3 grid(n0 + live[1]);
+  if ((which & 1) && pa.conv)
+    hipLaunchKernelGGL((gemm_f32_splitk_dual_kernel<true>), grid, dim3(256), kSplitLdsBytes, stream, q[0], ws[0], per[0], live[0], q[1], ws[1], per[1], n0);
+  else if (which & 1)
+    hipLaunchKernelGGL((gemm_f32_splitk_dual_kernel<false>), grid, dim3(256), kSplitLdsBytes, stream, q[0], ws[0], per[0], live[0], q[1], ws[1], per[1], n0);
+  if (which & 2) hipLaunchKernelGGL(splitk_reduce_dual_kernel, dim3(r[0].nblocks + r[1].nblocks), dim3(256), 0, stream, r[0], r[1]);
   M3_LAUNCH_CHECK();
   return 0;
 }

@@ -104,6 +104,10 @@ int launch_gemm_bf16w_tiled(const GemmPlan& plan, const GemmParams& p, hipStream
 int launch_gemm_bf16_dma(const GemmPlan& plan, const GemmParams& p, hipStream_t stream);        // gemm_bf16_dma.hip
 // deep-K, few-tile fp32 problems (conv2 / subsampling Linear at short inputs): split-K tiled kernel + reduce
 int launch_gemm_f32_splitk(const GemmPlan& plan, const GemmParams& p, float* ws, hipStream_t stream);   // gemm_f32_splitk.hip
+// two independent split-K problems (both implicit convs or both plain), each with its own workspace, in one GEMM + one reduce launch
+bool gemm_splitk_dual_fusable(const GemmPlan& a, const GemmPlan& b);
+int launch_gemm_f32_splitk_dual(const GemmPlan& pa, const GemmParams& a, float* ws_a, const GemmPlan& pb, const GemmParams& b, float* ws_b,
+                                hipStream_t stream, int which = 3);   // which: 1 the GEMM launch, 2 the reduce launch, 3 both
 // once, outside graph capture (dynamic-LDS opt-in of the tiled kernels)
 int init_gemm_f32_splitk_kernels();
 int init_gemm_bf16_tiled_kernels();
@@ -323,8 +327,10 @@ struct DwArgs {
   const float *z = nullptr, *w_kc = nullptr, *bias = nullptr, *gamma = nullptr, *beta = nullptr; float eps = 1e-5f;
   int B = 0, T = 0, D = 0, K = 0; float* out = nullptr; int out_bf16 = 0;
   const int32_t *pad_of = nullptr, *row0 = nullptr, *row_len = nullptr; const float* causal_left_fill = nullptr;
+  int glu_ldz = 0;   // > 0: z is pointwise_conv1's raw [B*T][glu_ldz] output (value | gate columns), GLU applied as the taps are loaded
 };
 int launch_dwconv_ln_silu_args(const DwArgs& a, hipStream_t stream);
+bool dwconv_glu_in_supports(int D, int K, bool causal_or_stream, int out_bf16, int ldz);   // what the GLU-on-load form takes
 bool dwconv_dual_fusable(const DwArgs& a, const DwArgs& b);
 int launch_dwconv_ln_silu_dual(const DwArgs& a, const DwArgs& b, hipStream_t stream);
 int launch_dwconv_ln_silu_stream(const float* z, const float* w_kc, const float* bias, const float* gamma, const float* beta,
@@ -338,6 +344,15 @@ int launch_unpack_rows(const float* in, const int32_t* row0, int B, int T, int n
 int launch_conv1_relu(const float* feat, const float* w9c, const float* bias, const float* cmvn_mean,
                       const float* cmvn_istd, int B, int T, int idim, int C, float* out, hipStream_t stream, int relu = 1,
                       int out_bf16 = 0, const int32_t* feat_len = nullptr, int32_t* lens_out = nullptr);   // feat_len: also the subsampled lengths
+// the same as a value (what the engine keeps per stage so that the two subsamplers' first convs can share a launch)
+struct Conv1Args {
+  const float *feat = nullptr, *w9c = nullptr, *bias = nullptr, *cmvn_mean = nullptr, *cmvn_istd = nullptr;
+  int B = 0, T = 0, idim = 0, C = 0; float* out = nullptr; int relu = 1, out_bf16 = 0;
+  const int32_t* feat_len = nullptr; int32_t* lens_out = nullptr;
+};
+int launch_conv1_relu_args(const Conv1Args& a, hipStream_t stream);
+bool conv1_dual_fusable(const Conv1Args& a, const Conv1Args& b);
+int launch_conv1_relu_dual(const Conv1Args& a, const Conv1Args& b, hipStream_t stream);
 int launch_cmvn(const float* x, const int32_t* len, const float* mean, const float* istd, int B, int T, int D,
                 float* y, hipStream_t stream);
 int launch_log_softmax_bias(const float* x, const float* bias, float* y, size_t rows, int n, hipStream_t stream);

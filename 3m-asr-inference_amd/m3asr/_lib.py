@@ -152,6 +152,7 @@ SIGNATURES = {
     "m3_relpos_attention_bf16": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _i, _vp]),
     "m3_relpos_attention_chunk": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _i, _vp]),
     "m3_dwconv_ln_silu": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp, _vp]),
+    "m3_dwconv_glu_ln_silu": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp, _vp]),
     "m3_relpos_attention_stream": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _i, _vp, _i, _vp]),
     "m3_dwconv_ln_silu_stream": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "m3_dwconv_ln_silu_causal": (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _vp, _vp]),

@@ -395,6 +395,20 @@ def dwconv_ln_silu(z, w_kc, bias, gamma, beta, eps, B, T):
     return out
 
 
+def dwconv_glu_ln_silu(vg, w_kc, bias, gamma, beta, eps, B, T, out=None):
+    """Depthwise conv + LayerNorm + SiLU on GLU(vg) formed as the taps are loaded (m3_dwconv_glu_ln_silu): vg (B*T, 2*D) holds
+    pointwise_conv1's value | gate columns and may be a row-strided view."""
+    lib = _lib.load()
+    K, D = w_kc.shape
+    assert tuple(vg.shape) == (B * T, 2 * D)
+    if out is None:
+        out = torch.empty(B * T, D, dtype=torch.float32, device=vg.device)
+    vp, ldz = _rows(vg)
+    check(lib.m3_dwconv_glu_ln_silu(vp, ldz, _f32(w_kc), _f32(bias), _f32(gamma), _f32(beta), float(eps), B, T, D, K,
+                                    _f32(out), _stream()), "m3_dwconv_glu_ln_silu")
+    return out
+
+
 def relpos_attention_stream(qkv, hist, p, pos_u, pos_v, chunk_len, step, B, C, H, dk, left_chunks=-1, slot_max_chunks=-1, out=None):
     """One chunk of the streaming attention (m3_relpos_attention_stream): qkv (B*C, 3*H*dk) and out (B*C, H*dk) may be
     row-strided views, p (p_rows, H*dk) too; hist (B, cap, 2*H*dk) is appended to in place.  step: one int32 on the device

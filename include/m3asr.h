@@ -335,6 +335,13 @@ int m3_relpos_attention_chunk(const float* qkv, int ldq, const float* p, int ldp
  * replaces convolution.py:134-152.  w_kc [K][D] = depthwise weight (D,1,K) transposed. */
 int m3_dwconv_ln_silu(const float* z, const float* w_kc, const float* bias, const float* gamma,
                       const float* beta, float eps, int B, int T, int D, int K, float* out, m3_stream stream);
+/* The same with the GLU (glu_kernel.cu:26-44) of the convolution module applied where the conv loads its input: vg [B*T][ldz]
+ * holds pointwise_conv1's raw output, value columns [0, D) | gate columns [D, 2 D) (bias added), and every tap is
+ * value * sigmoid(gate) -- bit for bit what m3_linear (act = M3_ACT_GLU) followed by m3_dwconv_ln_silu gives (the engine's
+ * short fp32 inputs: the GEMM in front then is the plain form, M3_GLU_DEFER).  K odd, <= 15; 256 <= D <= 1024, D % 4 == 0;
+ * ldz >= 2 D, a multiple of 4; vg 16-byte aligned.  out [B*T][D] dense. */
+int m3_dwconv_glu_ln_silu(const float* vg, int ldz, const float* w_kc, const float* bias, const float* gamma,
+                          const float* beta, float eps, int B, int T, int D, int K, float* out, m3_stream stream);
 /* The two stateful launches of chunk-by-chunk decoding (m3_engine_forward_chunk[_slots] is built from them) and the dense causal
  * conv, exposed so that they can be tested at the boundary (additions only; tests/test_stream_kernels_gpu.py).
  *
