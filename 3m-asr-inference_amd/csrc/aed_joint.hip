@@ -1,0 +1,413 @@
+// Joint CTC/attention decoding: the attention beam search of DESIGN.md 21 with every candidate also scored by its
+// CTC PREFIX probability (Watanabe et al. 2017) and ranked by  key = (1 - w) att + w ctc.  The step keeps the launches of
+// aed_search.hip up to the output layer; m3_aed_joint_score and m3_aed_joint_prune then take the place of m3_aed_search_prune.
+// They work on the SAME search state (aed_search_state.h: headers, double-buffered records, token and ancestry paths; the
+// record's score word holds the joint key) plus two blobs of their own:
+//
+//   scorer state (fp32 words), per row r, double-buffered by the parity of its utterance's step like the records:
+//       [ att, ctc (= psi of the hypothesis), 0, 0, rn[F], rb[F] ]      F = max_frames
+//     rn[t] / rb[t]: log-probability of the alignments of frames 0 .. t that collapse to the hypothesis and end in its last
+//     token / in blank.  Only t < m (the utterance's frames) is ever read.
+//   scratch, rewritten by every step:
+//       candidate records [R][K][4]: token, att', ctc', key       K = pre_beam; key = NaN: no such candidate
+//       candidate states  [R][F][2][K]: rn' | rb' of candidate j of row r at frame t (lane j writes K contiguous floats)
+//
+// m3_aed_joint_prune COPIES the survivors' states from the scratch; it does not recompute them.  The copy is N * 2 m words per
+// utterance spread over 256 threads, against a second serial chain of m dependent log-add-exps on B work-groups, and a copy
+// cannot differ from what was scored.
+//
+// fp32, no atomics, every reduction in a fixed order, a row's result independent of its place in the batch.  No work-group
+// reads a word that another one writes in the same launch: score reads buffer `step & 1` and writes only its row's scratch;
+// prune reads the scratch and writes the other buffer.  A done utterance is left bit for bit alone in all blobs.
+#include "aed_search_state.h"
+
+namespace m3 {
+namespace {
+
+enum { JS_ATT = 0, JS_CTC = 1, JS_HDR = 4 };
+enum { JC_TOK = 0, JC_ATT = 1, JC_CTC = 2, JC_KEY = 3, JC_WORDS = 4 };
+constexpr int JT = 16;   // frames whose gathered CTC log-probabilities are in flight ahead of the serial chain
+
+int check_joint_desc(const m3_aed_joint_desc* d) {
+  M3_REQUIRE(d != nullptr, "aed_joint: null descriptor");
+  if (int rc = check_search_desc(&d->search)) return rc;
+  const m3_aed_search_desc* s = &d->search;
+  M3_REQUIRE(s->V >= 2, "aed_joint: V = %d, blank and eos need two different ids", s->V);
+  M3_REQUIRE(d->pre_beam >= s->beam && d->pre_beam <= AS_MAX_BEAM && d->pre_beam <= s->V,
+             "aed_joint: pre_beam = %d, need beam = %d <= pre_beam <= min(%d, V = %d)", d->pre_beam, s->beam, AS_MAX_BEAM, s->V);
+  M3_REQUIRE(d->max_frames >= 1 && d->max_frames <= (1 << 20), "aed_joint: max_frames = %d outside [1, 2^20]", d->max_frames);
+  const size_t R = (size_t)s->B * s->beam, F = (size_t)d->max_frames, K = (size_t)d->pre_beam;
+  M3_REQUIRE(R * 2 * (JS_HDR + 2 * F) <= (size_t)INT_MAX, "aed_joint: %zu rows of %zu frames overflow the int32 offsets of the scorer state", R, F);
+  M3_REQUIRE(R * K * (JC_WORDS + 2 * F) <= (size_t)INT_MAX,
+             "aed_joint: %zu rows x %zu candidates x %zu frames overflow the int32 offsets of the candidate scratch", R, K, F);
+  return 0;
+}
+
+size_t joint_row_words(const m3_aed_joint_desc* d) { return 2 * (JS_HDR + 2 * (size_t)d->max_frames); }
+size_t joint_state_bytes(const m3_aed_joint_desc* d) {
+  return align_up(4 * (size_t)d->search.B * d->search.beam * joint_row_words(d), 256);
+}
+size_t joint_scratch_bytes(const m3_aed_joint_desc* d) {
+  const size_t R = (size_t)d->search.B * d->search.beam;
+  return align_up(4 * R * d->pre_beam * (JC_WORDS + 2 * (size_t)d->max_frames), 256);
+}
+
+// everything a joint entry point checks before it launches: descriptor, the three blobs
+int check_joint(const m3_aed_joint_desc* d, const void* st, size_t st_bytes, const void* js, size_t js_bytes, const void* scr,
+                size_t scr_bytes, bool with_scratch, const char* what) {
+  if (int rc = check_joint_desc(d)) return rc;
+  if (int rc = check_search_state(&d->search, st, st_bytes, what)) return rc;
+  M3_REQUIRE(js_bytes >= joint_state_bytes(d), "%s: scorer state %zu bytes < required %zu", what, js_bytes, joint_state_bytes(d));
+  M3_REQUIRE(d->search.B == 0 || (js != nullptr && ((uintptr_t)js & 15) == 0), "%s: the scorer state must be 16-byte aligned device memory", what);
+  if (with_scratch) {
+    M3_REQUIRE(scr_bytes >= joint_scratch_bytes(d), "%s: scratch %zu bytes < required %zu", what, scr_bytes, joint_scratch_bytes(d));
+    M3_REQUIRE(d->search.B == 0 || (scr != nullptr && ((uintptr_t)scr & 15) == 0), "%s: the scratch must be 16-byte aligned device memory", what);
+  }
+  return 0;
+}
+
+int check_ctc(const m3_aed_joint_desc* d, const float* ctc, int ldc, int ctc_rows, const char* what) {
+  M3_REQUIRE(ldc >= d->search.V, "%s: ldc = %d < V = %d", what, ldc, d->search.V);
+  M3_REQUIRE(ctc_rows >= 0, "%s: ctc_rows = %d", what, ctc_rows);
+  M3_REQUIRE(d->search.B == 0 || ctc != nullptr, "%s: null CTC log-probabilities", what);
+  return 0;
+}
+
+// max + log(exp(a - max) + exp(b - max)); -inf when both are: no -inf - -inf is ever formed.  exp(max - max) is exactly 1, so the
+// sum is 1 + exp(min - max): one exponential, no branch (the chain of m3_aed_joint_score is one wave alone on its SIMD, its time is
+// its instruction count).  The hardware exp2 / log2 behind __expf / __logf are good to about 1e-7 ABSOLUTE here (the argument of the
+// exponential is <= 0, the logarithm's lies in [1, 2]); the result is added to a max of magnitude up to hundreds, whose last place
+// is 100 times that.  A/B in DESIGN.md 23.
+__device__ __forceinline__ float lae(float a, float b) {
+  const float mx = fmaxf(a, b), mn = fminf(a, b);
+  const float d = mx == -INFINITY ? 0.f : mn - mx;
+  return mx + __logf(1.f + __expf(d));                            // mx = -inf: -inf + log 2
+}
+
+__device__ __forceinline__ float* js_row(float* js, int F, int row, int buf) {
+  return js + ((size_t)row * 2 + buf) * (JS_HDR + 2 * (size_t)F);
+}
+// the utterance's CTC rows as the kernels may read them: m frames from row0, or none when the header does not fit the buffers
+__device__ __forceinline__ int usable_frames(const int32_t* hdr, int F, int x_rows) {
+  const int row0 = hdr[AS_MEM_ROW0], m = hdr[AS_MEM_LEN];
+  return (row0 >= 0 && m >= 1 && m <= F && m <= x_rows - row0) ? m : 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- reset
+// one wave per utterance, after m3_aed_search_reset (whose headers it reads).  The state of the empty hypothesis: rn = -inf,
+// rb[t] = x[0][blank] + .. + x[t][blank] summed left to right (a tile of 64 frames is loaded by the lanes and added up in frame
+// order through the wave), psi = 0; att = 0 for slot 0 and -inf for the dead start slots.  Buffer 1 and the frames past m are 0.
+__global__ __launch_bounds__(64) void aed_joint_reset_kernel(const int32_t* __restrict__ st, int N, int F, float* js,
+                                                             const float* __restrict__ x, int ldx, int x_rows) {
+  const int u = blockIdx.x, lane = threadIdx.x;
+  const int32_t* hdr = as_header(st, u);
+  const int m = usable_frames(hdr, F, x_rows), row0 = hdr[AS_MEM_ROW0];
+  const int half = JS_HDR + 2 * F;
+  for (int i = 0; i < N; ++i) {
+    float* row = js_row(js, F, u * N + i, 0);
+    for (int w = lane; w < 2 * half; w += 64) {
+      const int off = w < half ? w : w - half;
+      float v = 0.f;
+      if (w < half) {
+        if (off == JS_ATT) v = i == 0 ? 0.f : -INFINITY;
+        if (off >= JS_HDR && off < JS_HDR + F && off - JS_HDR < m) v = -INFINITY;
+        if (off >= JS_HDR + F && off - JS_HDR - F < m) continue;            // rb[t < m]: the scan below is its one writer
+      }
+      row[w] = v;
+    }
+  }
+  float run = 0.f;
+  for (int t0 = 0; t0 < m; t0 += 64) {
+    const int t = t0 + lane;
+    const float v = t < m ? x[(size_t)(row0 + t) * ldx] : 0.f;
+    float mine = 0.f;
+    const int cnt = min(64, m - t0);
+    for (int j = 0; j < cnt; ++j) {
+      run = run + lane_bcast_f(v, j);
+      if (lane == j) mine = run;
+    }
+    if (t < m)
+      for (int i = 0; i < N; ++i) js_row(js, F, u * N + i, 0)[JS_HDR + F + t] = mine;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- score
+// one wave per hypothesis row.  The row's logsumexp and its K picks in the order of aed_search_prune_kernel (value descending,
+// token id ascending); then lane j runs candidate j's prefix recursion over the utterance's m frames:
+//     rn'[t] = lae(rn'[t-1], phi[t-1]) + x[t][c],  rb'[t] = lae(rn'[t-1], rb'[t-1]) + x[t][0],  psi' = lae(psi', phi[t-1] + x[t][c])
+// with phi[t] = rb[t] when c repeats the parent's last token and lae(rn[t], rb[t]) otherwise.  The recursion is written from t = 1
+// for every hypothesis length: below max(|g|, 1) the parent's entries are -inf, so those steps leave -inf, exactly as the
+// contract's start at s = max(|g|, 1) does.  The parent's rn / rb are the same for all lanes: lane l of a 64-frame tile loads
+// frame t0 + l - 1 and forms both phi variants once, the chain reads them as broadcasts.  The per-lane operand x[t][c_j] is a
+// gather whose addresses do not depend on the chain: the loads of the NEXT JT frames are issued before the chain of the current JT.
+__global__ __launch_bounds__(64) void aed_joint_score_kernel(const int32_t* __restrict__ st, int B, int N, int P, int rec_words, int V,
+                                                             int K, int F, const float* __restrict__ js, int32_t* __restrict__ cand,
+                                                             float* __restrict__ scr, const float* __restrict__ logits, int ldl,
+                                                             const float* __restrict__ x, int ldx, int x_rows, float lam) {
+  const int r = blockIdx.x, u = r / N, lane = threadIdx.x;
+  const int32_t* hdr = as_header(st, u);
+  const int s = hdr[AS_STEP];
+  if (hdr[AS_DONE] != 0 || s < 0 || s >= P - 1) return;           // frozen: the scratch keeps what the last live step left
+  const int eos = V - 1;
+  const int32_t* rec = as_record(st, B, rec_words, r, s & 1);
+  const float* jr = js_row(const_cast<float*>(js), F, r, s & 1);
+  const float att = jr[JS_ATT], psi = jr[JS_CTC];
+  int32_t* crow = cand + ((size_t)r * K + lane) * JC_WORDS;       // lane j's candidate record (lanes below K)
+  if (rec[AS_FINISHED] != 0) {                                    // one candidate: increment 0, eos, the parts as they are
+    if (lane < K) {
+      crow[JC_TOK] = eos;
+      crow[JC_ATT] = __builtin_bit_cast(int32_t, lane == 0 ? att : -INFINITY);
+      crow[JC_CTC] = __builtin_bit_cast(int32_t, lane == 0 ? psi : -INFINITY);
+      crow[JC_KEY] = lane == 0 ? rec[AS_SCORE] : __builtin_bit_cast(int32_t, NAN);
+    }
+    return;
+  }
+  const float* lg = logits + (size_t)r * ldl;
+  float mx = -INFINITY;
+  for (int c = lane; c < V; c += 64) mx = fmaxf(mx, lg[c]);
+  mx = wave_max(mx);
+  float sum = 0.f;
+  for (int c = lane; c < V; c += 64) sum += expf(lg[c] - mx);
+  const float lse = logf(wave_sum(sum));
+  float pv = 0.f, my_lp = -INFINITY;
+  int pi = -1, my_tok = -1;
+  for (int k = 0; k < K; ++k) {
+    float bv;
+    int bi;
+    wave_next_best(lg, V, k == 0, pv, pi, lane, bv, bi);
+    if (lane == k) {
+      my_tok = bi;
+      my_lp = (bv - mx) - lse;
+    }
+    pv = bv;
+    pi = bi;
+    if (bi < 0) pv = -INFINITY, pi = INT_MAX;                     // nothing left (NaN logits): no further candidate
+  }
+  const bool is_cand = lane < K && my_tok >= 0;
+  const int m = usable_frames(hdr, F, x_rows), row0 = hdr[AS_MEM_ROW0];
+  const int last = s > 0 ? rec[AS_TOKENS + s] : -1;
+  const int c = is_cand ? my_tok : 0;                             // idle lanes walk column 0: in bounds, their results unused
+  const bool dead = c == 0;                                       // blank: psi' = -inf and an all -inf state
+  const bool rep = c == last;
+  const float* xc = x + (size_t)row0 * ldx + c;                   // formed from row0 only when m > 0 says it is in range
+  const float* jrn = jr + JS_HDR;
+  const float* jrb = jr + JS_HDR + F;
+  float* srow = scr + (size_t)B * N * K * JC_WORDS + (size_t)r * F * 2 * K + lane;   // + (t * 2 + {0, 1}) * K
+
+  float rn = -INFINITY, rb = -INFINITY, ps = -INFINITY;
+  if (m > 0) {
+    if (s == 0) rn = xc[0];
+    ps = rn;
+    if (lane < K) {
+      srow[0] = dead ? -INFINITY : rn;
+      srow[K] = -INFINITY;
+    }
+    float xg[JT], phi_a = -INFINITY, phi_b = -INFINITY, xb = 0.f;
+#pragma unroll
+    for (int i = 0; i < JT; ++i) xg[i] = i < m ? xc[(size_t)i * ldx] : 0.f;
+    for (int t0 = 0; t0 < m; t0 += JT) {
+      if ((t0 & 63) == 0) {                                       // a new 64-frame tile of the parent's state and of the blank column
+        const int tp = t0 + lane - 1, tb = t0 + lane;
+        const bool have = tp >= 0 && tp < m;
+        const float prn = have ? jrn[tp] : -INFINITY, prb = have ? jrb[tp] : -INFINITY;
+        phi_a = lae(prn, prb);
+        phi_b = prb;
+        xb = tb < m ? x[(size_t)(row0 + tb) * ldx] : 0.f;
+      }
+      float xn[JT];
+#pragma unroll
+      for (int i = 0; i < JT; ++i) xn[i] = t0 + JT + i < m ? xc[(size_t)(t0 + JT + i) * ldx] : 0.f;
+#pragma unroll
+      for (int i = 0; i < JT; ++i) {
+        const int t = t0 + i;
+        if (t >= 1 && t < m) {                                    // wave-uniform
+          const int j = t & 63;
+          const float pa = lane_bcast_f(phi_a, j), pb = lane_bcast_f(phi_b, j), xbt = lane_bcast_f(xb, j);
+          const float phi = rep ? pb : pa;
+          const float rn_new = lae(rn, phi) + xg[i];
+          rb = lae(rn, rb) + xbt;
+          ps = lae(ps, phi + xg[i]);
+          rn = rn_new;
+          if (lane < K) {
+            srow[(size_t)t * 2 * K] = dead ? -INFINITY : rn;
+            srow[(size_t)t * 2 * K + K] = dead ? -INFINITY : rb;
+          }
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < JT; ++i) xg[i] = xn[i];
+    }
+    if (c == eos) ps = lae(jrn[m - 1], jrb[m - 1]);
+  }
+  if (dead) ps = -INFINITY;
+  if (lane < K) {
+    const float att2 = att + my_lp;                               // -inf + increment stays -inf
+    float key = NAN;
+    if (is_cand) key = (att2 == -INFINITY || ps == -INFINITY) ? -INFINITY : (1.f - lam) * att2 + lam * ps;
+    crow[JC_TOK] = is_cand ? my_tok : eos;
+    crow[JC_ATT] = __builtin_bit_cast(int32_t, is_cand ? att2 : -INFINITY);
+    crow[JC_CTC] = __builtin_bit_cast(int32_t, is_cand ? ps : -INFINITY);
+    crow[JC_KEY] = __builtin_bit_cast(int32_t, key);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- prune
+// one work-group per utterance: wave 0 picks the N largest of the N * K keys (ties to the lower flat index row * K + rank; a
+// NaN key is no candidate), all threads copy the parents' token and ancestry paths into the other record exactly as
+// aed_search_prune_kernel does and the survivors' scorer states from the scratch into the other buffer, thread 0 moves the step.
+__global__ __launch_bounds__(256) void aed_joint_prune_kernel(int32_t* st, int B, int N, int P, int rec_words, int V, int K, int F,
+                                                              float* js, const int32_t* __restrict__ cand,
+                                                              const float* __restrict__ scr, int32_t* __restrict__ done_out) {
+  __shared__ float c_key[AS_MAX_BEAM * AS_MAX_BEAM];
+  __shared__ int32_t pick[AS_MAX_BEAM];
+  const int u = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  const int32_t* hdr = as_header(st, u);
+  const int s = hdr[AS_STEP], limit = hdr[AS_LIMIT];
+  if (hdr[AS_DONE] != 0 || s < 0 || s >= P - 1) {                  // frozen: not one word of the utterance changes
+    if (tid == 0 && done_out) done_out[u] = 1;
+    return;
+  }
+  const int m = (hdr[AS_MEM_LEN] >= 1 && hdr[AS_MEM_LEN] <= F) ? hdr[AS_MEM_LEN] : 0;   // only t < F is ever addressed
+  const int cur = s & 1, nxt = cur ^ 1, eos = V - 1;
+  const int32_t* ucand = cand + (size_t)u * N * K * JC_WORDS;
+  for (int idx = tid; idx < N * K; idx += 256) c_key[idx] = __builtin_bit_cast(float, ucand[(size_t)idx * JC_WORDS + JC_KEY]);
+  __syncthreads();
+  if (w == 0) {
+    float pv = 0.f;
+    int pi = -1;
+    for (int j = 0; j < N; ++j) {
+      float bv;
+      int bi;
+      wave_next_best(c_key, N * K, j == 0, pv, pi, lane, bv, bi);
+      if (lane == 0) pick[j] = bi;
+      pv = bv;
+      pi = bi;
+      if (bi < 0) pv = -INFINITY, pi = INT_MAX;
+    }
+  }
+  __syncthreads();
+  const int span = s + 1;
+  for (int idx = tid; idx < N * span; idx += 256) {
+    const int j = idx / span, t = idx - j * span;
+    const int parent = pick[j] >= 0 ? pick[j] / K : 0;
+    const int32_t* src = as_record(st, B, rec_words, u * N + parent, cur);
+    int32_t* dst = const_cast<int32_t*>(as_record(st, B, rec_words, u * N + j, nxt));
+    dst[AS_TOKENS + t] = src[AS_TOKENS + t];
+    dst[AS_TOKENS + P + t] = t < s ? src[AS_TOKENS + P + t] : parent;
+  }
+  for (int idx = tid; idx < N * m; idx += 256) {                  // the states of the survivors that can be extended again
+    const int j = idx / m, t = idx - j * m, c = pick[j];
+    if (c < 0 || ucand[(size_t)c * JC_WORDS + JC_TOK] == eos) continue;
+    const int parent = c / K, rank = c - parent * K;
+    const float* src = scr + (size_t)B * N * K * JC_WORDS + ((size_t)(u * N + parent) * F + t) * 2 * K + rank;
+    float* dst = js_row(js, F, u * N + j, nxt) + JS_HDR;
+    dst[t] = src[0];
+    dst[F + t] = src[K];
+  }
+  if (tid < N) {
+    const int j = tid, c = pick[j];
+    const int32_t* cr = ucand + (size_t)(c >= 0 ? c : 0) * JC_WORDS;
+    const int tok = c >= 0 ? cr[JC_TOK] : eos;
+    int32_t* dst = const_cast<int32_t*>(as_record(st, B, rec_words, u * N + j, nxt));
+    dst[AS_SCORE] = c >= 0 ? cr[JC_KEY] : __builtin_bit_cast(int32_t, -INFINITY);
+    dst[AS_FINISHED] = tok == eos;
+    dst[AS_TOKENS + s + 1] = tok;
+    int32_t* jd = reinterpret_cast<int32_t*>(js_row(js, F, u * N + j, nxt));
+    jd[JS_ATT] = c >= 0 ? cr[JC_ATT] : __builtin_bit_cast(int32_t, -INFINITY);
+    jd[JS_CTC] = c >= 0 ? cr[JC_CTC] : __builtin_bit_cast(int32_t, -INFINITY);
+  }
+  if (tid == 0) {
+    bool all = true;
+    for (int j = 0; j < N; ++j) all = all && (pick[j] < 0 || ucand[(size_t)pick[j] * JC_WORDS + JC_TOK] == eos);
+    const int done = all || s + 1 >= limit;
+    int32_t* h = const_cast<int32_t*>(hdr);
+    h[AS_STEP] = s + 1;                                           // every thread read the header before the first barrier
+    h[AS_DONE] = done;
+    if (done_out) done_out[u] = done;
+  }
+}
+
+// --------------------------------------------------------------------------------------------------------------- result
+__global__ __launch_bounds__(64) void aed_joint_result_kernel(const int32_t* __restrict__ st, int N, int P, int F,
+                                                              const float* __restrict__ js, float* __restrict__ att,
+                                                              float* __restrict__ ctc) {
+  const int u = blockIdx.x, j = threadIdx.x;
+  const int s = min(max(as_header(st, u)[AS_STEP], 0), P - 1);
+  if (j < N) {
+    const float* jr = js_row(const_cast<float*>(js), F, u * N + j, s & 1);
+    att[u * N + j] = jr[JS_ATT];
+    ctc[u * N + j] = jr[JS_CTC];
+  }
+}
+
+}  // namespace
+}  // namespace m3
+
+using namespace m3;
+
+extern "C" {
+
+size_t m3_aed_joint_state_size(const m3_aed_joint_desc* desc) {
+  if (check_joint_desc(desc)) return 0;
+  return joint_state_bytes(desc);
+}
+
+size_t m3_aed_joint_scratch_size(const m3_aed_joint_desc* desc) {
+  if (check_joint_desc(desc)) return 0;
+  return joint_scratch_bytes(desc);
+}
+
+int m3_aed_joint_reset(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, void* joint_state,
+                       size_t joint_state_bytes, const float* ctc, int ldc, int ctc_rows, m3_stream stream) {
+  if (int rc = check_joint(desc, search_state, search_state_bytes, joint_state, joint_state_bytes, nullptr, 0, false, "aed_joint_reset")) return rc;
+  if (int rc = check_ctc(desc, ctc, ldc, ctc_rows, "aed_joint_reset")) return rc;
+  if (desc->search.B == 0) return 0;
+  hipLaunchKernelGGL(aed_joint_reset_kernel, dim3((unsigned)desc->search.B), dim3(64), 0, (hipStream_t)stream, (const int32_t*)search_state,
+                     desc->search.beam, desc->max_frames, (float*)joint_state, ctc, ldc, ctc_rows);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+int m3_aed_joint_score(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, const void* joint_state,
+                       size_t joint_state_bytes, void* scratch, size_t scratch_bytes, const float* logits, int ldl, const float* ctc,
+                       int ldc, int ctc_rows, float ctc_weight, m3_stream stream) {
+  if (int rc = check_joint(desc, search_state, search_state_bytes, joint_state, joint_state_bytes, scratch, scratch_bytes, true, "aed_joint_score")) return rc;
+  if (int rc = check_ctc(desc, ctc, ldc, ctc_rows, "aed_joint_score")) return rc;
+  const m3_aed_search_desc* s = &desc->search;
+  M3_REQUIRE(ldl >= s->V, "aed_joint_score: ldl = %d < V = %d", ldl, s->V);
+  M3_REQUIRE(ctc_weight > 0.f && ctc_weight <= 1.f, "aed_joint_score: ctc_weight = %g outside (0, 1] (0 is m3_aed_search_prune)", (double)ctc_weight);
+  if (s->B == 0) return 0;
+  M3_REQUIRE(logits != nullptr, "aed_joint_score: null pointer");
+  const SearchLayout l = search_layout(s);
+  hipLaunchKernelGGL(aed_joint_score_kernel, dim3((unsigned)(s->B * s->beam)), dim3(64), 0, (hipStream_t)stream, (const int32_t*)search_state,
+                     s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames, (const float*)joint_state, (int32_t*)scratch,
+                     (float*)scratch, logits, ldl, ctc, ldc, ctc_rows, ctc_weight);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+int m3_aed_joint_prune(const m3_aed_joint_desc* desc, void* search_state, size_t search_state_bytes, void* joint_state,
+                       size_t joint_state_bytes, const void* scratch, size_t scratch_bytes, int32_t* done, m3_stream stream) {
+  if (int rc = check_joint(desc, search_state, search_state_bytes, joint_state, joint_state_bytes, scratch, scratch_bytes, true, "aed_joint_prune")) return rc;
+  const m3_aed_search_desc* s = &desc->search;
+  if (s->B == 0) return 0;
+  const SearchLayout l = search_layout(s);
+  hipLaunchKernelGGL(aed_joint_prune_kernel, dim3((unsigned)s->B), dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state, s->B, s->beam,
+                     l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames, (float*)joint_state, (const int32_t*)scratch,
+                     (const float*)scratch, done);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+int m3_aed_joint_result(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, const void* joint_state,
+                        size_t joint_state_bytes, float* att, float* ctc, m3_stream stream) {
+  if (int rc = check_joint(desc, search_state, search_state_bytes, joint_state, joint_state_bytes, nullptr, 0, false, "aed_joint_result")) return rc;
+  if (desc->search.B == 0) return 0;
+  M3_REQUIRE(att && ctc, "aed_joint_result: null pointer");
+  hipLaunchKernelGGL(aed_joint_result_kernel, dim3((unsigned)desc->search.B), dim3(64), 0, (hipStream_t)stream, (const int32_t*)search_state,
+                     desc->search.beam, search_layout(&desc->search).P, desc->max_frames, (const float*)joint_state, att, ctc);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // extern "C"

@@ -78,6 +78,10 @@ class AedSearchDesc(C.Structure):  # m3_aed_search_desc
     _fields_ = [(n, C.c_int32) for n in ("B", "beam", "max_steps", "V", "D", "H", "layers", "pe_rows")]
 
 
+class AedJointDesc(C.Structure):  # m3_aed_joint_desc
+    _fields_ = [("search", AedSearchDesc), ("pre_beam", C.c_int32), ("max_frames", C.c_int32)]
+
+
 class WeightEntry(C.Structure):  # m3_weight_entry
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64), ("dtype", C.c_int32)]
 
@@ -255,6 +259,12 @@ SIGNATURES = {
     "m3_aed_search_attention": (_i, [_P(AedSearchDesc), _vp, _sz, _vp, _i, _vp, _i, _i, _vp, _sz, _i, _vp, _i, _vp]),
     "m3_aed_search_prune": (_i, [_P(AedSearchDesc), _vp, _sz, _vp, _i, _vp, _vp]),
     "m3_aed_search_result": (_i, [_P(AedSearchDesc), _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "m3_aed_joint_state_size": (_sz, [_P(AedJointDesc)]),
+    "m3_aed_joint_scratch_size": (_sz, [_P(AedJointDesc)]),
+    "m3_aed_joint_reset": (_i, [_P(AedJointDesc), _vp, _sz, _vp, _sz, _vp, _i, _i, _vp]),
+    "m3_aed_joint_score": (_i, [_P(AedJointDesc), _vp, _sz, _vp, _sz, _vp, _sz, _vp, _i, _vp, _i, _i, _f, _vp]),
+    "m3_aed_joint_prune": (_i, [_P(AedJointDesc), _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "m3_aed_joint_result": (_i, [_P(AedJointDesc), _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
 }
 
 _lib = None

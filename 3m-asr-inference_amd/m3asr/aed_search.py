@@ -16,7 +16,17 @@ synchronising and reads the B done flags in one small copy every `poll` steps; s
 no-ops for it.  The (R, V) log-probabilities never leave the device.  There is no torch fallback.
 
 Memory: the self-attention K / V cache holds num_blocks * max_steps * B * beam * 2 * dim floats (6 blocks, 125 steps, 16 x 10
-rows, dim 512: 0.49 GB) -- it is sized from max_steps, so give the constructor the bound you need, not the table's length."""
+rows, dim 512: 0.49 GB) -- it is sized from max_steps, so give the constructor the bound you need, not the table's length.
+
+JOINT CTC/ATTENTION DECODING (ctc_weight > 0; the contract is restated in tests/aed_joint_ref.py).  Every step
+also scores its candidates with the CTC prefix probability and ranks them by (1 - ctc_weight) att + ctc_weight ctc: a row
+offers its `pre_beam` largest attention log-probabilities, m3_aed_joint_score runs every candidate's prefix recursion over the
+utterance's CTC log-probabilities, m3_aed_joint_prune keeps the `beam` best keys and moves the scorer states with the
+hypotheses.  Those two launches stand where m3_aed_search_prune stood: 8 L + 4.  The CTC output comes with the call
+(ctc_logits / ctc_rows, one row per memory row); its log-softmax runs on the device once per call.  With ctc_weight = 0 nothing
+of this exists: no scorer state, the same launches, the same bits as before."""
+import math
+
 import torch
 
 from . import _lib, ops
@@ -24,13 +34,16 @@ from .rescore import LN_EPS
 
 
 class AttentionBeamSearch:
-    def __init__(self, rescorer, B, beam, max_steps, poll=8, use_graph=False):
+    def __init__(self, rescorer, B, beam, max_steps, poll=8, use_graph=False, ctc_weight=0.0, pre_beam=None):
         """rescorer: the AttentionRescorer whose uploaded weights and config the search shares; B utterances per call, `beam`
         hypotheses each (1 <= beam <= min(64, vocab)); max_steps: the most tokens a hypothesis can get (it sizes the state and
         the K / V cache, see the module docstring; more than max_len - 1 steps are never taken).  poll: steps between two reads of
         the done flags.  use_graph: capture the step once with torch.cuda.graph and replay it (the step is a straight line of
         launches whose arguments never change); off by default: the A/B in DESIGN.md 21 shows no gain.  The first graph call
         of an object pays one extra eager step, a synchronisation and the capture.
+        ctc_weight in [0, 1]: above 0 the search is the joint CTC/attention search (module docstring) and every call must bring
+        the CTC output; pre_beam: the candidates a row offers to the CTC scorer, beam <= pre_beam <= min(64, vocab), default
+        min(max(beam, ceil(1.5 beam)), 64, vocab).  The scorer state is allocated by the first call, from its longest memory.
         Raises M3Error before anything is allocated for a beam or a head size the kernels do not take."""
         cfg = rescorer.cfg
         self.rescorer, self.cfg, self.device = rescorer, cfg, rescorer.device
@@ -39,6 +52,17 @@ class AttentionBeamSearch:
             raise _lib.M3Error("AttentionBeamSearch: beam = %d, need 1 <= beam <= min(64, vocab = %d)" % (self.beam, cfg.vocab))
         if int(max_steps) < 1:
             raise _lib.M3Error("AttentionBeamSearch: max_steps = %d, need at least 1" % int(max_steps))
+        self.ctc_weight = float(ctc_weight)
+        if not 0.0 <= self.ctc_weight <= 1.0:                      # also refuses NaN
+            raise _lib.M3Error("AttentionBeamSearch: ctc_weight = %r outside [0, 1]" % (ctc_weight,))
+        self.pre_beam = 0
+        if self.ctc_weight > 0:
+            self.pre_beam = min(max(self.beam, math.ceil(1.5 * self.beam)), 64, cfg.vocab) if pre_beam is None else int(pre_beam)
+            if not self.beam <= self.pre_beam <= min(64, cfg.vocab):
+                raise _lib.M3Error("AttentionBeamSearch: pre_beam = %d, need beam = %d <= pre_beam <= min(64, vocab = %d)" % (
+                    self.pre_beam, self.beam, cfg.vocab))
+            if cfg.vocab < 2:
+                raise _lib.M3Error("AttentionBeamSearch: joint decoding needs blank and eos to be two ids, vocab = %d" % cfg.vocab)
         self.max_steps = min(int(max_steps), cfg.max_len - 1)
         self.desc = ops.aed_search_desc(self.B, self.beam, self.max_steps, cfg.vocab, cfg.dim, cfg.heads, cfg.num_blocks, cfg.max_len)
         R, D, dev = self.B * self.beam, cfg.dim, self.device
@@ -50,13 +74,15 @@ class AttentionBeamSearch:
         self.h, self.logits = f32(R, cfg.linear_units), f32(R, cfg.vocab)
         self.done = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self._done_host = torch.zeros(self.B, dtype=torch.int32).pin_memory()     # the poll's target: one small asynchronous copy
+        # joint decoding only: descriptor, scorer state and candidate scratch, sized by the first call that needs them
+        self.jdesc = self.jstate = self.jscratch = self.ctc = None
         self.kvp = None           # the memory's K / V projection of the current call, (rows, num_blocks * 2 D)
         self._graph = None
         self.steps_issued = 0     # of the last call
         self.last = None          # device tensors of the last call: m3_aed_search_result's, plus state and done
 
     def launches_per_step(self):
-        return 8 * self.cfg.num_blocks + 3
+        return 8 * self.cfg.num_blocks + (4 if self.ctc_weight > 0 else 3)
 
     # ---- one step: the same launches with the same arguments, whatever the step
     def _step(self):
@@ -77,7 +103,44 @@ class AttentionBeamSearch:
             ops.linear(self.h, w[q + "feed_forward.w_2.weight"], w[q + "feed_forward.w_2.bias"], resid=x, out=x)
         ops.linear(x, w["decoder.output_layer.weight"], w["decoder.output_layer.bias"],
                    ln=(w["decoder.after_norm.weight"], w["decoder.after_norm.bias"], LN_EPS), out=self.logits)
-        ops.aed_search_prune(d, st, self.logits, self.done)
+        if self.ctc_weight > 0:
+            ops.aed_joint_score(self.jdesc, st, self.jstate, self.jscratch, self.logits, self.ctc, self.ctc_weight)
+            ops.aed_joint_prune(self.jdesc, st, self.jstate, self.jscratch, self.done)
+        else:
+            ops.aed_search_prune(d, st, self.logits, self.done)
+
+    def _reset(self, meta, cap):
+        ops.aed_search_reset(self.desc, self.state, meta[0], meta[1], cap)
+        if self.ctc_weight > 0:
+            ops.aed_joint_reset(self.jdesc, self.state, self.jstate, self.ctc)
+        self.done.zero_()
+
+    def _take_ctc(self, ctc, n_rows, frames, log_probs):
+        """Joint decoding: the call's CTC output, (n_rows, V) after flattening, one row per memory row -> self.ctc, its
+        log-softmax (m3_log_softmax_bias, once per call; log_probs: the input already holds log-probabilities and is used as it
+        is).  The buffers are kept and grown across calls, so that a captured step keeps reading the same addresses.  Refuses a
+        missing or unexpected input and a shape that does not fit, before anything is launched."""
+        if self.ctc_weight == 0:
+            if ctc is not None:
+                raise _lib.M3Error("search: CTC output given, but the search was built with ctc_weight = 0")
+            return
+        if ctc is None:
+            raise _lib.M3Error("search: ctc_weight = %g needs the CTC output (ctc_logits / ctc_rows)" % self.ctc_weight)
+        V = self.cfg.vocab
+        if ctc.shape[-1] != V:
+            raise _lib.M3Error("search: the CTC output has %d classes, the attention decoder %d" % (ctc.shape[-1], V))
+        if ctc.numel() // V < n_rows:
+            raise _lib.M3Error("search: the CTC output has %d frames, the memory %d" % (ctc.numel() // V, n_rows))
+        ctc = ctc.to(self.device, torch.float32).reshape(-1, V)[:n_rows]
+        if self.jdesc is None or self.jdesc.max_frames < frames:
+            self.jdesc = ops.aed_joint_desc(self.desc, self.pre_beam, -(-frames // 64) * 64)
+            self.jstate = torch.zeros(ops.aed_joint_state_size(self.jdesc), dtype=torch.uint8, device=self.device)
+            self.jscratch = torch.zeros(ops.aed_joint_scratch_size(self.jdesc), dtype=torch.uint8, device=self.device)
+            self._graph = None
+        if self.ctc is None or self.ctc.shape[0] < n_rows:
+            self.ctc = torch.zeros(n_rows, V, dtype=torch.float32, device=self.device)
+            self._graph = None
+        self.ctc[:n_rows].copy_(ctc.contiguous() if log_probs else ops.log_softmax_bias(ctc.contiguous()))
 
     def _project(self, rows, raw_memory):
         """The memory's K / V projection for all layers: one GEMM per search, shared by every beam and every step.  The buffer
@@ -91,17 +154,18 @@ class AttentionBeamSearch:
         ops.linear(rows, w["decoder.src_kv_all.weight"][:L * 2 * D], w["decoder.src_kv_all.bias"][:L * 2 * D], ln=norm,
                    out=self.kvp[:rows.shape[0]])
 
-    def _run(self, rows, row0, lens, raw_memory, detail, max_steps, poll):
-        """rows (n, D) memory rows on the device; row0 / lens: B Python ints each, validated by the caller"""
+    def _run(self, rows, row0, lens, raw_memory, detail, max_steps, poll, ctc=None, ctc_log_probs=False):
+        """rows (n, D) memory rows on the device; row0 / lens: B Python ints each, validated by the caller; ctc: None or the
+        CTC output of the same n rows"""
         cfg, d = self.cfg, self.desc
         cap = self.max_steps if max_steps is None else int(max_steps)
         if not 1 <= cap <= self.max_steps:
             raise _lib.M3Error("search: max_steps = %d outside [1, %d] (the constructor's bound sizes the cache)" % (cap, self.max_steps))
         poll = self.poll if poll is None else max(int(poll), 1)
+        self._take_ctc(ctc, rows.shape[0], max(lens), ctc_log_probs)
         meta = torch.tensor([row0, lens], dtype=torch.int32).to(self.device)
         self._project(rows, raw_memory)
-        ops.aed_search_reset(d, self.state, meta[0], meta[1], cap)
-        self.done.zero_()
+        self._reset(meta, cap)
         most = min(max(lens), cfg.max_len - 1, cap)
         issued = 0
         while issued < most:
@@ -115,16 +179,23 @@ class AttentionBeamSearch:
         self.steps_issued = issued
         res = ops.aed_search_result(d, self.state)
         self.last = dict(res, state=self.state, done=self.done)
+        parts = []
+        if self.ctc_weight > 0:
+            jres = ops.aed_joint_result(self.jdesc, self.state, self.jstate)
+            self.last.update(jres, joint_state=self.jstate)
+            parts = [jres["att"].reshape(-1).view(torch.int32), jres["ctc"].reshape(-1).view(torch.int32)]
         host = torch.cat([res["hyp_tokens"].reshape(-1), res["hyp_len"].reshape(-1), res["finished"].reshape(-1), res["best"],
-                          res["score"].reshape(-1).view(torch.int32)]).cpu()
+                          res["score"].reshape(-1).view(torch.int32)] + parts).cpu()
         B, N, S = self.B, self.beam, self.max_steps
         toks = host[:B * N * S].view(B, N, S)
         o = B * N * S
         hlen, fin, best = host[o:o + B * N].tolist(), host[o + B * N:o + 2 * B * N].tolist(), host[o + 2 * B * N:o + 2 * B * N + B].tolist()
-        score = host[o + 2 * B * N + B:].view(torch.float32).tolist()
+        score = host[o + 2 * B * N + B:].view(torch.float32).tolist()             # score, then (joint) att and ctc: B * N each
         out = []
         for b in range(B):
             hyps = [(tuple(toks[b, i, :hlen[b * N + i]].tolist()), score[b * N + i], bool(fin[b * N + i])) for i in range(N)]
+            if parts:
+                hyps = [h + (score[B * N + b * N + i], score[2 * B * N + b * N + i]) for i, h in enumerate(hyps)]
             out.append((list(hyps[best[b]][0]), hyps) if detail else list(hyps[best[b]][0]))
         return out
 
@@ -138,8 +209,7 @@ class AttentionBeamSearch:
         step (kernel attributes are set once per device, outside any capture), restores the start and captures."""
         if self._graph is None:
             self._step()
-            ops.aed_search_reset(self.desc, self.state, meta[0], meta[1], cap)
-            self.done.zero_()
+            self._reset(meta, cap)
             torch.cuda.synchronize(self.device)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
@@ -148,13 +218,17 @@ class AttentionBeamSearch:
         self._graph.replay()
 
     # ---- the public calls
-    def search(self, memory, mem_len, raw_memory=False, detail=False, max_steps=None, poll=None):
+    def search(self, memory, mem_len, raw_memory=False, detail=False, max_steps=None, poll=None, ctc_logits=None,
+               ctc_log_probs=False):
         """memory (B, T', D) on the device: the encoder's normalised hidden states (Engine.hidden()), or with raw_memory the
         residual stream before after_norm (Engine.hidden(normalized=False)), the LayerNorm then riding in the K / V GEMM's
         prologue; mem_len (B,) valid frames.  Utterance b stops once its `beam` hypotheses have all ended in eos, or after
         min(mem_len[b], max_len - 1, max_steps) steps with whatever it has; max_steps: a bound for this call, at most the
         constructor's.
         -> the best token list per utterance; detail: (best tokens, [(tokens, score, finished)] in slot order) per utterance.
+        Joint decoding (ctc_weight > 0): ctc_logits (B, T', V), the CTC output over the memory's frames (another frame count or
+        vocabulary is refused); ctc_log_probs: it already holds log-probabilities and is used as it is.  The score is then the
+        joint key and detail gives (tokens, key, finished, att, ctc).
         mem_len < 1 is refused before anything is launched.  The device tensors of the call stay in self.last."""
         cfg, B = self.cfg, self.B
         memory = memory.to(self.device, torch.float32)
@@ -167,13 +241,16 @@ class AttentionBeamSearch:
         for b, m in enumerate(lens):
             if not 1 <= m <= Tm:
                 raise _lib.M3Error("search: utterance %d has %d memory frames (mem_len = 0 is rejected; the memory holds %d)" % (b, m, Tm))
-        return self._run(memory.contiguous().view(B * Tm, cfg.dim), [b * Tm for b in range(B)], lens, raw_memory, detail, max_steps, poll)
+        if ctc_logits is not None and self.ctc_weight > 0 and (ctc_logits.dim() != 3 or ctc_logits.shape[0] != B or ctc_logits.shape[1] != Tm):
+            raise _lib.M3Error("search: the CTC output %s does not cover the memory's %d x %d frames" % (tuple(ctc_logits.shape), B, Tm))
+        return self._run(memory.contiguous().view(B * Tm, cfg.dim), [b * Tm for b in range(B)], lens, raw_memory, detail, max_steps, poll,
+                         ctc_logits, ctc_log_probs)
 
-    def search_rows(self, rows, row0, raw_memory=True, detail=False, max_steps=None, poll=None):
+    def search_rows(self, rows, row0, raw_memory=True, detail=False, max_steps=None, poll=None, ctc_rows=None, ctc_log_probs=False):
         """The search over PACKED memory rows, as AttentionRescorer.rescore_rows takes them: rows (>= R, D) on the device,
         row0 (B + 1,) int32 (m3_aed_memory_gather leaves them so): utterance b owns rows [row0[b], row0[b + 1]).  raw_memory:
         the rows are the residual stream before after_norm (what the streaming store keeps).  An utterance without a row is
-        refused before anything is launched."""
+        refused before anything is launched.  Joint decoding: ctc_rows (>= row0[B], V), the CTC output of the same packed rows."""
         cfg, B = self.cfg, self.B
         if rows.dim() != 2 or rows.shape[1] != cfg.dim or not rows.is_contiguous() or row0.numel() != B + 1:
             raise ValueError("search_rows: rows %s / row0 (%d,) for %d utterances of dim %d" % (tuple(rows.shape), row0.numel(), B, cfg.dim))
@@ -184,4 +261,7 @@ class AttentionBeamSearch:
         for b, m in enumerate(lens):
             if m < 1:
                 raise _lib.M3Error("search_rows: utterance %d has no memory row (mem_len = 0 is rejected)" % b)
-        return self._run(rows[:r0[-1]].to(self.device, torch.float32), r0[:-1], lens, raw_memory, detail, max_steps, poll)
+        if ctc_rows is not None and self.ctc_weight > 0 and ctc_rows.dim() != 2:
+            raise _lib.M3Error("search_rows: the CTC output %s is not (rows, vocab)" % (tuple(ctc_rows.shape),))
+        return self._run(rows[:r0[-1]].to(self.device, torch.float32), r0[:-1], lens, raw_memory, detail, max_steps, poll,
+                         ctc_rows, ctc_log_probs)

@@ -1024,6 +1024,56 @@ def aed_search_result(desc, state):
     return out
 
 
+# ---- joint CTC/attention decoding: CTC prefix scores inside that search (m3_aed_joint_*)
+def aed_joint_desc(search_desc, pre_beam, max_frames):
+    """m3_aed_joint_desc around a search descriptor.  Raises M3Error on what the library rejects (pre_beam outside
+    [beam, min(64, V)], max_frames < 1, V < 2, sizes that overflow the int32 offsets of the scorer state or the scratch)."""
+    d = _lib.AedJointDesc(search_desc, int(pre_beam), int(max_frames))
+    if _lib.load().m3_aed_joint_state_size(C.byref(d)) == 0:
+        raise _lib.M3Error("m3_aed_joint_state_size failed: " + _lib.last_error())
+    return d
+
+
+def aed_joint_state_size(desc):
+    return _lib.load().m3_aed_joint_state_size(C.byref(desc))
+
+
+def aed_joint_scratch_size(desc):
+    return _lib.load().m3_aed_joint_scratch_size(C.byref(desc))
+
+
+def aed_joint_reset(desc, state, jstate, ctc):
+    """after aed_search_reset: the scorer state of the empty hypothesis from ctc (rows, V) log-probabilities"""
+    cp, ldc = _rows(ctc)
+    check(_lib.load().m3_aed_joint_reset(C.byref(desc), _p(state), _nbytes(state), _p(jstate), _nbytes(jstate), cp, ldc, ctc.shape[0],
+                                         _stream()), "m3_aed_joint_reset")
+
+
+def aed_joint_score(desc, state, jstate, scratch, logits, ctc, ctc_weight):
+    """per row: log-softmax of logits (R, V), the pre_beam picks and every pick's CTC prefix score -> the candidate scratch"""
+    (lp, ldl), (cp, ldc) = _rows(logits), _rows(ctc)
+    assert tuple(logits.shape) == (desc.search.B * desc.search.beam, desc.search.V) and ctc.shape[1] == desc.search.V
+    check(_lib.load().m3_aed_joint_score(C.byref(desc), _p(state), _nbytes(state), _p(jstate), _nbytes(jstate), _p(scratch),
+                                         _nbytes(scratch), lp, ldl, cp, ldc, ctc.shape[0], float(ctc_weight), _stream()),
+          "m3_aed_joint_score")
+
+
+def aed_joint_prune(desc, state, jstate, scratch, done=None):
+    """the beam best keys of the scratch's candidates; records, paths, parts and scorer states move to the other buffer"""
+    assert done is None or done.numel() == desc.search.B
+    check(_lib.load().m3_aed_joint_prune(C.byref(desc), _p(state), _nbytes(state), _p(jstate), _nbytes(jstate), _p(scratch),
+                                         _nbytes(scratch), _i32(done), _stream()), "m3_aed_joint_prune")
+
+
+def aed_joint_result(desc, state, jstate):
+    """-> dict(att, ctc (B, beam)) on the device: the two parts of the keys aed_search_result returns as scores"""
+    B, N = desc.search.B, desc.search.beam
+    out = dict(att=torch.empty(B, N, dtype=torch.float32, device=state.device), ctc=torch.empty(B, N, dtype=torch.float32, device=state.device))
+    check(_lib.load().m3_aed_joint_result(C.byref(desc), _p(state), _nbytes(state), _p(jstate), _nbytes(jstate), _p(out["att"]),
+                                          _p(out["ctc"]), _stream()), "m3_aed_joint_result")
+    return out
+
+
 # ---------------------------------------------------------------------------------------- streaming operators
 def cat_split_cache(in_cache, inp):
     """CatSplitCache plugin: (output (B, cache+input), out_cache (B, cache)); f32 or i32 rows."""

@@ -954,6 +954,43 @@ int m3_aed_search_prune(const m3_aed_search_desc* desc, void* state, size_t stat
 int m3_aed_search_result(const m3_aed_search_desc* desc, const void* state, size_t state_bytes, int32_t* hyp_tokens, int32_t* hyp_len,
                          float* score, int32_t* finished, int32_t* best, int32_t* steps, m3_stream stream);
 
+/* Joint CTC/attention decoding (csrc/aed_joint.hip): the search above with every candidate also scored by its CTC
+ * prefix probability (Watanabe et al. 2017) and ranked by key = (1 - ctc_weight) att + ctc_weight ctc.  The step is the one
+ * above up to the output layer; m3_aed_joint_score and m3_aed_joint_prune then stand where m3_aed_search_prune stood (8 L + 4
+ * launches).  The search state, its descriptor and the other m3_aed_search_* calls are used unchanged; a record's score word
+ * holds the key, so m3_aed_search_result keeps working.  blank = 0, sos = eos = V - 1 (V >= 2).
+ * ctc [ctc_rows][ldc]: natural-log CTC probabilities over the same V, one row per memory row: utterance u reads rows
+ *   [mem_row0[u], mem_row0[u] + mem_len[u]) as the search state's headers name them.  An utterance whose rows do not lie
+ *   inside [0, ctc_rows) or exceed max_frames is read nowhere: all its CTC parts are -inf (the caller refuses it before).
+ * Scorer state: caller-owned, m3_aed_joint_state_size bytes, 16-byte aligned; per row, double-buffered by the parity of the
+ *   utterance's step: att, ctc (the two parts of the key), and the prefix scorer's rn / rb over max_frames frames.
+ * Scratch: caller-owned, m3_aed_joint_scratch_size bytes, 16-byte aligned; rewritten by every step: beam * pre_beam candidate
+ *   records per utterance and every candidate's extended rn / rb, from which prune copies the survivors' (it recomputes nothing).
+ * m3_aed_joint_reset: after m3_aed_search_reset on the same stream.  The empty hypothesis's state in every slot: rn = -inf,
+ *   rb[t] = the running sum of ctc[.][0], ctc part 0; att part 0 in slot 0, -inf in the others.
+ * m3_aed_joint_score: one wave per row: logsumexp of logits [R][ldl] and the pre_beam largest (m3_aed_search_prune's pick order),
+ *   candidate j's recursion over the frames in lane j; a finished row offers (eos, its parts unchanged) alone.
+ *   0 < ctc_weight <= 1.  A part at -inf makes the key -inf.
+ * m3_aed_joint_prune: one work-group per utterance: the beam largest keys (lower flat index slot * pre_beam + rank on ties),
+ *   paths, flags, step and done exactly as m3_aed_search_prune; parts and scorer states go to the other buffer.
+ * m3_aed_joint_result: att, ctc [B][beam], the parts of the hypotheses m3_aed_search_result returns. */
+typedef struct m3_aed_joint_desc {
+  m3_aed_search_desc search;
+  int32_t pre_beam;    /* beam <= pre_beam <= min(64, V) */
+  int32_t max_frames;  /* the most memory frames of an utterance */
+} m3_aed_joint_desc;
+size_t m3_aed_joint_state_size(const m3_aed_joint_desc* desc);
+size_t m3_aed_joint_scratch_size(const m3_aed_joint_desc* desc);
+int m3_aed_joint_reset(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, void* joint_state,
+                       size_t joint_state_bytes, const float* ctc, int ldc, int ctc_rows, m3_stream stream);
+int m3_aed_joint_score(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, const void* joint_state,
+                       size_t joint_state_bytes, void* scratch, size_t scratch_bytes, const float* logits, int ldl, const float* ctc,
+                       int ldc, int ctc_rows, float ctc_weight, m3_stream stream);
+int m3_aed_joint_prune(const m3_aed_joint_desc* desc, void* search_state, size_t search_state_bytes, void* joint_state,
+                       size_t joint_state_bytes, const void* scratch, size_t scratch_bytes, int32_t* done, m3_stream stream);
+int m3_aed_joint_result(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, const void* joint_state,
+                        size_t joint_state_bytes, float* att, float* ctc, m3_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

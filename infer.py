@@ -26,11 +26,13 @@ Attention rescoring, for a plan built from a joint CTC/attention checkpoint: the
 attention decoder rescoring every utterance's n-best on the encoder's hidden states (m3asr.rescore).  Prints the first-pass
 best and the rescored best hypothesis of each utterance.
 
-    python3 infer.py -p aed.plan -i feat.npy --attention [--beam 10] [--max-steps K]
+    python3 infer.py -p aed.plan -i feat.npy --attention [--beam 10] [--max-steps K] [--ctc-weight W [--pre-beam P]]
 
 Attention decoding, for such a plan: the attention decoder searches on its own, autoregressively, over the encoder's hidden
 states (m3asr.aed_search); --max-steps bounds the tokens per hypothesis (default: the encoder's output frames).  Prints the
-best hypothesis of each utterance."""
+best hypothesis of each utterance.  With --ctc-weight W > 0 the search is the one-pass joint CTC/attention search: every candidate
+is also scored by its CTC prefix probability on the forward's own CTC output and ranked by (1 - W) att + W ctc; --pre-beam P
+candidates per hypothesis go to the CTC scorer.  Both parts are printed."""
 import argparse
 import os
 import sys
@@ -129,10 +131,12 @@ def print_attention(helper, feat, feat_len, args):
     from m3asr.rescore import AttentionRescorer
     rescorer = AttentionRescorer(helper.decoder_packed, decoder_config_of(helper.extra), helper.engine.device)
     dec = CtcDecoder(helper.engine, rescorer=rescorer)
-    out = dec.attention(torch.from_numpy(feat), torch.from_numpy(feat_len), args.beam, max_steps=args.max_steps, detail=True)
+    out = dec.attention(torch.from_numpy(feat), torch.from_numpy(feat_len), args.beam, max_steps=args.max_steps, detail=True,
+                        ctc_weight=args.ctc_weight, pre_beam=args.pre_beam)
     for b, (best, hyps) in enumerate(out):
         chosen = next(h for h in hyps if list(h[0]) == best)
-        print("utt %d attention: score=%.4f finished=%d tokens=%s" % (b, chosen[1], chosen[2], " ".join(str(t) for t in best)))
+        parts = " att=%.4f ctc=%.4f" % (chosen[3], chosen[4]) if args.ctc_weight > 0 else ""
+        print("utt %d attention: score=%.4f%s finished=%d tokens=%s" % (b, chosen[1], parts, chosen[2], " ".join(str(t) for t in best)))
 
 
 def main(args):
@@ -178,8 +182,10 @@ if __name__ == "__main__":
     p.add_argument("--lm-weight", type=float, default=0.5, help="Weight of log P_LM in the ranking.")
     p.add_argument("--length-bonus", type=float, default=0.0, help="Bonus per token of a prefix in the ranking.")
     p.add_argument("--rescore", action="store_true", help="Attention rescoring of the n-best with the plan's AED decoder.")
-    p.add_argument("--ctc-weight", type=float, default=0.0, help="--rescore: weight of the first-pass score in the final score.")
+    p.add_argument("--ctc-weight", type=float, default=0.0, help="--rescore: weight of the first-pass score in the final score.  --attention: above 0, "
+                   "joint CTC/attention decoding with this weight on the CTC prefix score.")
     p.add_argument("--reverse-weight", type=float, default=0.0, help="--rescore: weight of the right-to-left decoder.")
     p.add_argument("--attention", action="store_true", help="Attention decoding: the plan's AED decoder searching on its own.")
     p.add_argument("--max-steps", type=int, default=None, help="--attention: the most tokens per hypothesis.")
+    p.add_argument("--pre-beam", type=int, default=None, help="--attention --ctc-weight W: candidates per hypothesis that the CTC scorer sees.")
     main(p.parse_args())

@@ -7,6 +7,13 @@ memory lengths are drawn from [frames / 2, frames] as tools/bench_rescore.py dra
 --full-length gives every utterance all --frames frames.
 
   python tools/bench_attention_search.py [--batch 16] [--beam 10] [--frames 125] [--blocks 6] [--rounds 10] [--graph]
+                                         [--ctc-weight W [--pre-beam K]]
+
+--ctc-weight W > 0 times the joint CTC/attention search on the same model and memories.  Its CTC output is
+synthetic too, but shaped like a trained model's: every utterance has a hidden token sequence of mem_len // 6 tokens, one spike
+every sixth frame and blank in between (logit +10 on the frame's target over unit noise), so the CTC part has an opinion on
+how long a hypothesis should be; the JSON line reports those lengths next to the hypotheses'.  The eager restatement is the
+attention-only search and is skipped in this mode.
 
 "device": wall time of AttentionBeamSearch.search() per call -- the K / V GEMM, every step's launches, the polls of the done
 flags and the read of the results -- median over the rounds after a warm-up; us per step = that over the steps issued.
@@ -45,6 +52,22 @@ def make_case(batch, frames, blocks, eos_bias, seed=0, full_length=False):
     return dcfg, sd, memory, mem_len
 
 
+def make_ctc(mem_len, frames, vocab, seed=1):
+    """(B, frames, V) CTC logits with a hidden target per utterance, and the targets' lengths"""
+    g = torch.Generator().manual_seed(seed)
+    B = mem_len.numel()
+    logits = torch.randn(B, frames, vocab, generator=g)
+    n_tok = []
+    for b in range(B):
+        m = int(mem_len[b])
+        target = torch.zeros(frames, dtype=torch.long)                      # blank
+        pos = torch.arange(3, m, 6)
+        target[pos] = torch.randint(1, vocab - 1, (pos.numel(),), generator=g)
+        logits[b, torch.arange(frames), target] += 10.0
+        n_tok.append(int(pos.numel()))
+    return logits, n_tok
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=16)
@@ -58,6 +81,8 @@ def main():
     ap.add_argument("--eager-rounds", type=int, default=1)
     ap.add_argument("--graph", action="store_true")
     ap.add_argument("--full-length", action="store_true")
+    ap.add_argument("--ctc-weight", type=float, default=0.0, help="above 0: the joint CTC/attention search with this weight")
+    ap.add_argument("--pre-beam", type=int, default=None, help="--ctc-weight: candidates per hypothesis for the CTC scorer")
     a = ap.parse_args()
     import aed_search_ref
     from m3asr.aed_search import AttentionBeamSearch
@@ -66,9 +91,14 @@ def main():
     dcfg, sd, memory, mem_len = make_case(a.batch, a.frames, a.blocks, a.eos_bias, full_length=a.full_length)
     B, beam, steps = a.batch, a.beam, a.max_steps or a.frames
     res = AttentionRescorer(pack_decoder(sd, dcfg), dcfg, "cuda:0")
-    search = AttentionBeamSearch(res, B, beam, steps, poll=a.poll)
+    joint = dict(ctc_weight=a.ctc_weight, pre_beam=a.pre_beam) if a.ctc_weight > 0 else {}
+    search = AttentionBeamSearch(res, B, beam, steps, poll=a.poll, **joint)
     mem_d = memory.cuda()
-    out = search.search(mem_d, mem_len, detail=True)
+    call = {}
+    if joint:
+        ctc, n_tok = make_ctc(mem_len, a.frames, dcfg.vocab)
+        call = dict(ctc_logits=ctc.cuda())
+    out = search.search(mem_d, mem_len, detail=True, **call)
     taken = search.last["steps"].cpu().tolist()
     lengths = [len(h[0]) for u in out for h in u[1]]
     record = {"metric": "attention decoding, %d utterances x beam %d, %d blocks, D 512 / F 2048 / V 1434, %d frames" % (
@@ -76,6 +106,11 @@ def main():
         "hyp_tokens_min_median_max": [min(lengths), statistics.median(lengths), max(lengths)],
         "finished": "%d/%d" % (sum(int(h[2]) for u in out for h in u[1]), B * beam),
         "launches_per_step": search.launches_per_step(), "poll": a.poll, "data": "synthetic"}
+    if joint:
+        best = [len(u[0]) for u in out]
+        record.update(ctc_weight=a.ctc_weight, pre_beam=search.pre_beam, ctc_target_tokens_min_median_max=[min(n_tok), statistics.median(n_tok), max(n_tok)],
+                      best_hyp_tokens_min_median_max=[min(best), statistics.median(best), max(best)],
+                      best_minus_target_min_max=[min(x - y for x, y in zip(best, n_tok)), max(x - y for x, y in zip(best, n_tok))])
 
     def timed(f, n):
         ts = []
@@ -93,16 +128,16 @@ def main():
         record[tag + "_steps_issued"] = s.steps_issued
         record[tag + "_us_per_step"] = round(statistics.median(ts) * 1e3 / max(s.steps_issued, 1), 1)
 
-    timed(lambda: search.search(mem_d, mem_len), 3)
-    add("device", search, timed(lambda: search.search(mem_d, mem_len), a.rounds))
+    timed(lambda: search.search(mem_d, mem_len, **call), 3)
+    add("device", search, timed(lambda: search.search(mem_d, mem_len, **call), a.rounds))
     if a.graph:
-        graphed = AttentionBeamSearch(res, B, beam, steps, poll=a.poll, use_graph=True)
-        same = graphed.search(mem_d, mem_len, detail=True) == out
+        graphed = AttentionBeamSearch(res, B, beam, steps, poll=a.poll, use_graph=True, **joint)
+        same = graphed.search(mem_d, mem_len, detail=True, **call) == out
         same = same and torch.equal(graphed.last["score"].view(torch.int32), search.last["score"].view(torch.int32))
         record["graph_same_bits"] = bool(same)
-        timed(lambda: graphed.search(mem_d, mem_len), 3)
-        add("graph", graphed, timed(lambda: graphed.search(mem_d, mem_len), a.rounds))
-    if a.eager_rounds > 0:
+        timed(lambda: graphed.search(mem_d, mem_len, **call), 3)
+        add("graph", graphed, timed(lambda: graphed.search(mem_d, mem_len, **call), a.rounds))
+    if a.eager_rounds > 0 and not joint:
         sd_d = {k: v.cuda() for k, v in sd.items()}
 
         def eager():
