@@ -19,7 +19,21 @@
 // fp32, no atomics, every reduction in a fixed order, a row's result independent of its place in the batch.  No work-group
 // reads a word that another one writes in the same launch: score reads buffer `step & 1` and writes only its row's scratch;
 // prune reads the scratch and writes the other buffer.  A done utterance is left bit for bit alone in all blobs.
+//
+// N-GRAM LM FUSION AND THE LENGTH BONUS (m3_aed_ngram_*).  The score and prune kernels are templates on <CTC, LM>:
+// <true, false> is the joint step above, unchanged; with LM every candidate also takes one step through the LM image of
+// kernels.h (lm_step's terms in lm_step's order) and  key = jkey + (float)(alpha lm' + beta n'),  jkey the joint key above;
+// with CTC = false (ctc_weight = 0) there is no scorer state, no frame chain, the ctc part is 0 and jkey = att'.  Two more blobs:
+//
+//   LM state (int32 words), per row, double-buffered like the records:  [ lm_state, n, lm (double, 2 words), att, 0, 0, 0 ]
+//     att is the attention part, kept here only by the CTC = false form (it has no scorer state to keep it in).
+//   LM scratch: [R][K] of [ lm_state', 0, lm' (double) ], then [R][K][4] candidate records of the CTC = false form (the CTC
+//     form's records stay in the joint scratch).
+//
+// Prune copies the survivors' (lm_state', lm') from the scratch: nothing is walked twice.  An utterance whose lm_on is 0 (or
+// whose image fails lm_view) adds nothing: its keys, parts, records and scorer states are the joint step's bits.
 #include "aed_search_state.h"
+#include "kernels.h"
 
 namespace m3 {
 namespace {
@@ -27,6 +41,23 @@ namespace {
 enum { JS_ATT = 0, JS_CTC = 1, JS_HDR = 4 };
 enum { JC_TOK = 0, JC_ATT = 1, JC_CTC = 2, JC_KEY = 3, JC_WORDS = 4 };
 constexpr int JT = 16;   // frames whose gathered CTC log-probabilities are in flight ahead of the serial chain
+enum { LS_STATE = 0, LS_N = 1, LS_LM = 2, LS_ATT = 4, LS_WORDS = 8 };   // LM state of a row's buffer; LS_LM: a double
+enum { LC_STATE = 0, LC_LM = 2, LC_WORDS = 4 };                         // LM scratch of a candidate; LC_LM: a double
+// A/B switch of DESIGN.md 24: 1 = the LM walk is issued before the CTC frame chain, 0 = after it
+#ifndef M3_AED_LM_WALK_FIRST
+#define M3_AED_LM_WALK_FIRST 1
+#endif
+
+struct NoLm {};
+struct LmFuse {
+  const int32_t* image;    // the device LM image and its words
+  long long words;
+  const int32_t* lm_on;    // [B]
+  int32_t* lstate;         // LM state: score reads buffer step & 1, prune writes the other
+  int32_t* lscr;           // LM scratch: score writes, prune reads
+  double alpha, beta;
+  int use_eos;
+};
 
 int check_joint_desc(const m3_aed_joint_desc* d) {
   M3_REQUIRE(d != nullptr, "aed_joint: null descriptor");
@@ -140,25 +171,106 @@ __global__ __launch_bounds__(64) void aed_joint_reset_kernel(const int32_t* __re
 // contract's start at s = max(|g|, 1) does.  The parent's rn / rb are the same for all lanes: lane l of a 64-frame tile loads
 // frame t0 + l - 1 and forms both phi variants once, the chain reads them as broadcasts.  The per-lane operand x[t][c_j] is a
 // gather whose addresses do not depend on the chain: the loads of the NEXT JT frames are issued before the chain of the current JT.
+//
+// LM: the parent's LM state is the same for all lanes, so its back-off chain -- per level the checked arc_begin pair
+// and the back-off weight summed above it, at most kLmMaxOrder levels -- is formed ONCE per wave from uniform loads into registers
+// (lm_chain).  Lane j then walks token j down the levels (lm_walk): only the binary search's probes and the arc it finds go to
+// memory, state 0 needs no search.  The terms and their order are lm_step's.  CTC = false: no scorer state, no chain, jkey = att'.
+struct LmChain {
+  int lo[kLmMaxOrder], hi[kLmMaxOrder], levels;
+  double w[kLmMaxOrder + 1];                                      // w[l]: the back-off weights above level l; the last: above the root
+};
+__device__ __forceinline__ void lm_chain(const LmView& lm, int state, LmChain* c) {
+  int st = state;
+  double w = 0.0;
+  c->levels = 0;
+#pragma unroll
+  for (int l = 0; l < kLmMaxOrder; ++l) {
+    c->lo[l] = c->hi[l] = 0;
+    c->w[l] = w;
+    if (st != 0) {                                                // wave-uniform
+      lm_arcs(lm, st, &c->lo[l], &c->hi[l]);
+      w += (double)lm.bo_weight[st];
+      const int nb = lm.bo_state[st];
+      st = nb >= 0 && nb < st ? nb : 0;
+      c->levels = l + 1;
+    }
+  }
+  c->w[kLmMaxOrder] = w;                                          // past the last level w no longer moves: the root's weight
+}
+__device__ __forceinline__ double lm_walk(const LmView& lm, const LmChain& c, int tok, int* next) {
+  int a = -1;
+  double wa = 0.0;
+#pragma unroll
+  for (int l = 0; l < kLmMaxOrder; ++l)
+    if (l < c.levels && a < 0) {
+      a = lm_find(lm, c.lo[l], c.hi[l], tok);
+      wa = c.w[l];
+    }
+  if (a >= 0) {
+    *next = lm_in_range(lm.arc_next[a], lm.n_states);
+    return wa + (double)lm.arc_logp[a];
+  }
+  return lm_step_root(lm, c.w[kLmMaxOrder], tok, next);
+}
+// the attention part of a row where the LM state keeps it (CTC = false)
+__device__ __forceinline__ float lm_att(const NoLm&, int, int) { return 0.f; }
+__device__ __forceinline__ float lm_att(const LmFuse& lx, int row, int buf) {
+  return __builtin_bit_cast(float, lx.lstate[((size_t)row * 2 + buf) * LS_WORDS + LS_ATT]);
+}
+// (lm_state', lm') of a hypothesis in `state` with the sum `sum`, extended by tok: eos takes the state's final value and stays
+__device__ __forceinline__ void lm_extend(const LmView& lm, int state, double sum, int tok, int eos, int use_eos, int* next,
+                                          double* out) {
+  const int st0 = __builtin_amdgcn_readfirstlane(lm_in_range(state, lm.n_states));
+  if (tok == eos) {
+    *next = st0;
+    *out = sum + (double)lm.fin[st0] * (double)use_eos;
+    return;
+  }
+  LmChain ch;
+  lm_chain(lm, st0, &ch);
+  *out = sum + lm_walk(lm, ch, tok, next);
+}
+
+template <bool CTC, bool LM, class Lx>
 __global__ __launch_bounds__(64) void aed_joint_score_kernel(const int32_t* __restrict__ st, int B, int N, int P, int rec_words, int V,
                                                              int K, int F, const float* __restrict__ js, int32_t* __restrict__ cand,
                                                              float* __restrict__ scr, const float* __restrict__ logits, int ldl,
-                                                             const float* __restrict__ x, int ldx, int x_rows, float lam) {
+                                                             const float* __restrict__ x, int ldx, int x_rows, float lam, Lx lx) {
   const int r = blockIdx.x, u = r / N, lane = threadIdx.x;
   const int32_t* hdr = as_header(st, u);
   const int s = hdr[AS_STEP];
   if (hdr[AS_DONE] != 0 || s < 0 || s >= P - 1) return;           // frozen: the scratch keeps what the last live step left
   const int eos = V - 1;
   const int32_t* rec = as_record(st, B, rec_words, r, s & 1);
-  const float* jr = js_row(const_cast<float*>(js), F, r, s & 1);
-  const float att = jr[JS_ATT], psi = jr[JS_CTC];
+  const float* jr = CTC ? js_row(const_cast<float*>(js), F, r, s & 1) : nullptr;
+  const float att = CTC ? jr[JS_ATT] : lm_att(lx, r, s & 1), psi = CTC ? jr[JS_CTC] : 0.f;
   int32_t* crow = cand + ((size_t)r * K + lane) * JC_WORDS;       // lane j's candidate record (lanes below K)
+  // LM only: the parent's (state, n, sum) as stored, lane j's scratch entry, and whether this utterance is fused at all
+  [[maybe_unused]] int l_state = 0, l_n = 0;
+  [[maybe_unused]] double l_sum = 0.0;
+  [[maybe_unused]] int32_t* lc = nullptr;
+  [[maybe_unused]] bool fused = false;
+  [[maybe_unused]] LmView lm{};
+  if constexpr (LM) {
+    const int32_t* lrow = lx.lstate + ((size_t)r * 2 + (s & 1)) * LS_WORDS;
+    l_state = lrow[LS_STATE];
+    l_n = lrow[LS_N];
+    l_sum = *reinterpret_cast<const double*>(lrow + LS_LM);
+    lc = lx.lscr + ((size_t)r * K + lane) * LC_WORDS;
+    fused = lx.lm_on[u] != 0 && lm_view(lx.image, lx.words, &lm) && lm.V == V;   // uniform
+  }
   if (rec[AS_FINISHED] != 0) {                                    // one candidate: increment 0, eos, the parts as they are
     if (lane < K) {
       crow[JC_TOK] = eos;
       crow[JC_ATT] = __builtin_bit_cast(int32_t, lane == 0 ? att : -INFINITY);
       crow[JC_CTC] = __builtin_bit_cast(int32_t, lane == 0 ? psi : -INFINITY);
       crow[JC_KEY] = lane == 0 ? rec[AS_SCORE] : __builtin_bit_cast(int32_t, NAN);
+      if constexpr (LM) {                                         // ... and (lm_state, lm) as they are
+        lc[LC_STATE] = lane == 0 ? l_state : 0;
+        lc[LC_STATE + 1] = 0;
+        *reinterpret_cast<double*>(lc + LC_LM) = lane == 0 ? l_sum : 0.0;
+      }
     }
     return;
   }
@@ -184,7 +296,13 @@ __global__ __launch_bounds__(64) void aed_joint_score_kernel(const int32_t* __re
     if (bi < 0) pv = -INFINITY, pi = INT_MAX;                     // nothing left (NaN logits): no further candidate
   }
   const bool is_cand = lane < K && my_tok >= 0;
-  const int m = usable_frames(hdr, F, x_rows), row0 = hdr[AS_MEM_ROW0];
+  // LM: candidate j's step from the parent's state.  eos takes the state's final value and stays; an utterance that is not fused
+  // carries (state, sum) along as they are
+  [[maybe_unused]] int l_next = l_state;
+  [[maybe_unused]] double l_new = l_sum;
+  if constexpr (LM && (M3_AED_LM_WALK_FIRST || !CTC))
+    if (fused) lm_extend(lm, l_state, l_sum, is_cand ? my_tok : eos, eos, lx.use_eos, &l_next, &l_new);   // idle lanes: no walk
+  const int m = CTC ? usable_frames(hdr, F, x_rows) : 0, row0 = hdr[AS_MEM_ROW0];   // CTC = false: no frame, no chain
   const int last = s > 0 ? rec[AS_TOKENS + s] : -1;
   const int c = is_cand ? my_tok : 0;                             // idle lanes walk column 0: in bounds, their results unused
   const bool dead = c == 0;                                       // blank: psi' = -inf and an all -inf state
@@ -194,7 +312,7 @@ __global__ __launch_bounds__(64) void aed_joint_score_kernel(const int32_t* __re
   const float* jrb = jr + JS_HDR + F;
   float* srow = scr + (size_t)B * N * K * JC_WORDS + (size_t)r * F * 2 * K + lane;   // + (t * 2 + {0, 1}) * K
 
-  float rn = -INFINITY, rb = -INFINITY, ps = -INFINITY;
+  float rn = -INFINITY, rb = -INFINITY, ps = CTC ? -INFINITY : 0.f;
   if (m > 0) {
     if (s == 0) rn = xc[0];
     ps = rn;
@@ -239,11 +357,23 @@ __global__ __launch_bounds__(64) void aed_joint_score_kernel(const int32_t* __re
     }
     if (c == eos) ps = lae(jrn[m - 1], jrb[m - 1]);
   }
-  if (dead) ps = -INFINITY;
+  if (CTC && dead) ps = -INFINITY;
+  if constexpr (LM && CTC && !M3_AED_LM_WALK_FIRST)
+    if (fused) lm_extend(lm, l_state, l_sum, is_cand ? my_tok : eos, eos, lx.use_eos, &l_next, &l_new);
   if (lane < K) {
     const float att2 = att + my_lp;                               // -inf + increment stays -inf
     float key = NAN;
-    if (is_cand) key = (att2 == -INFINITY || ps == -INFINITY) ? -INFINITY : (1.f - lam) * att2 + lam * ps;
+    if constexpr (CTC) {
+      if (is_cand) key = (att2 == -INFINITY || ps == -INFINITY) ? -INFINITY : (1.f - lam) * att2 + lam * ps;
+    } else {
+      if (is_cand) key = att2;
+    }
+    if constexpr (LM) {                                           // two products and one sum in double, rounded once
+      if (fused && is_cand && key != -INFINITY) key = key + (float)(lx.alpha * l_new + lx.beta * (double)(l_n + 1));
+      lc[LC_STATE] = is_cand ? l_next : 0;
+      lc[LC_STATE + 1] = 0;
+      *reinterpret_cast<double*>(lc + LC_LM) = is_cand ? l_new : 0.0;
+    }
     crow[JC_TOK] = is_cand ? my_tok : eos;
     crow[JC_ATT] = __builtin_bit_cast(int32_t, is_cand ? att2 : -INFINITY);
     crow[JC_CTC] = __builtin_bit_cast(int32_t, is_cand ? ps : -INFINITY);
@@ -255,9 +385,11 @@ __global__ __launch_bounds__(64) void aed_joint_score_kernel(const int32_t* __re
 // one work-group per utterance: wave 0 picks the N largest of the N * K keys (ties to the lower flat index row * K + rank; a
 // NaN key is no candidate), all threads copy the parents' token and ancestry paths into the other record exactly as
 // aed_search_prune_kernel does and the survivors' scorer states from the scratch into the other buffer, thread 0 moves the step.
+// LM: a survivor's (lm_state, lm) is copied from the LM scratch, its n is the parent's plus one unless the parent was finished.
+template <bool CTC, bool LM, class Lx>
 __global__ __launch_bounds__(256) void aed_joint_prune_kernel(int32_t* st, int B, int N, int P, int rec_words, int V, int K, int F,
                                                               float* js, const int32_t* __restrict__ cand,
-                                                              const float* __restrict__ scr, int32_t* __restrict__ done_out) {
+                                                              const float* __restrict__ scr, int32_t* __restrict__ done_out, Lx lx) {
   __shared__ float c_key[AS_MAX_BEAM * AS_MAX_BEAM];
   __shared__ int32_t pick[AS_MAX_BEAM];
   const int u = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
@@ -267,7 +399,7 @@ __global__ __launch_bounds__(256) void aed_joint_prune_kernel(int32_t* st, int B
     if (tid == 0 && done_out) done_out[u] = 1;
     return;
   }
-  const int m = (hdr[AS_MEM_LEN] >= 1 && hdr[AS_MEM_LEN] <= F) ? hdr[AS_MEM_LEN] : 0;   // only t < F is ever addressed
+  [[maybe_unused]] const int m = (hdr[AS_MEM_LEN] >= 1 && hdr[AS_MEM_LEN] <= F) ? hdr[AS_MEM_LEN] : 0;   // only t < F is ever addressed
   const int cur = s & 1, nxt = cur ^ 1, eos = V - 1;
   const int32_t* ucand = cand + (size_t)u * N * K * JC_WORDS;
   for (int idx = tid; idx < N * K; idx += 256) c_key[idx] = __builtin_bit_cast(float, ucand[(size_t)idx * JC_WORDS + JC_KEY]);
@@ -295,15 +427,16 @@ __global__ __launch_bounds__(256) void aed_joint_prune_kernel(int32_t* st, int B
     dst[AS_TOKENS + t] = src[AS_TOKENS + t];
     dst[AS_TOKENS + P + t] = t < s ? src[AS_TOKENS + P + t] : parent;
   }
-  for (int idx = tid; idx < N * m; idx += 256) {                  // the states of the survivors that can be extended again
-    const int j = idx / m, t = idx - j * m, c = pick[j];
-    if (c < 0 || ucand[(size_t)c * JC_WORDS + JC_TOK] == eos) continue;
-    const int parent = c / K, rank = c - parent * K;
-    const float* src = scr + (size_t)B * N * K * JC_WORDS + ((size_t)(u * N + parent) * F + t) * 2 * K + rank;
-    float* dst = js_row(js, F, u * N + j, nxt) + JS_HDR;
-    dst[t] = src[0];
-    dst[F + t] = src[K];
-  }
+  if constexpr (CTC)
+    for (int idx = tid; idx < N * m; idx += 256) {                // the states of the survivors that can be extended again
+      const int j = idx / m, t = idx - j * m, c = pick[j];
+      if (c < 0 || ucand[(size_t)c * JC_WORDS + JC_TOK] == eos) continue;
+      const int parent = c / K, rank = c - parent * K;
+      const float* src = scr + (size_t)B * N * K * JC_WORDS + ((size_t)(u * N + parent) * F + t) * 2 * K + rank;
+      float* dst = js_row(js, F, u * N + j, nxt) + JS_HDR;
+      dst[t] = src[0];
+      dst[F + t] = src[K];
+    }
   if (tid < N) {
     const int j = tid, c = pick[j];
     const int32_t* cr = ucand + (size_t)(c >= 0 ? c : 0) * JC_WORDS;
@@ -312,9 +445,22 @@ __global__ __launch_bounds__(256) void aed_joint_prune_kernel(int32_t* st, int B
     dst[AS_SCORE] = c >= 0 ? cr[JC_KEY] : __builtin_bit_cast(int32_t, -INFINITY);
     dst[AS_FINISHED] = tok == eos;
     dst[AS_TOKENS + s + 1] = tok;
-    int32_t* jd = reinterpret_cast<int32_t*>(js_row(js, F, u * N + j, nxt));
-    jd[JS_ATT] = c >= 0 ? cr[JC_ATT] : __builtin_bit_cast(int32_t, -INFINITY);
-    jd[JS_CTC] = c >= 0 ? cr[JC_CTC] : __builtin_bit_cast(int32_t, -INFINITY);
+    if constexpr (CTC) {
+      int32_t* jd = reinterpret_cast<int32_t*>(js_row(js, F, u * N + j, nxt));
+      jd[JS_ATT] = c >= 0 ? cr[JC_ATT] : __builtin_bit_cast(int32_t, -INFINITY);
+      jd[JS_CTC] = c >= 0 ? cr[JC_CTC] : __builtin_bit_cast(int32_t, -INFINITY);
+    }
+    if constexpr (LM) {
+      const int parent = c >= 0 ? c / K : 0;
+      const int32_t* lp = lx.lstate + ((size_t)(u * N + parent) * 2 + cur) * LS_WORDS;
+      const int32_t* lcs = lx.lscr + ((size_t)u * N * K + (c >= 0 ? c : 0)) * LC_WORDS;
+      const bool grew = as_record(st, B, rec_words, u * N + parent, cur)[AS_FINISHED] == 0;
+      int32_t* ld = lx.lstate + ((size_t)(u * N + j) * 2 + nxt) * LS_WORDS;
+      ld[LS_STATE] = c >= 0 ? lcs[LC_STATE] : 0;
+      ld[LS_N] = c >= 0 ? lp[LS_N] + (grew ? 1 : 0) : 0;
+      *reinterpret_cast<double*>(ld + LS_LM) = c >= 0 ? *reinterpret_cast<const double*>(lcs + LC_LM) : 0.0;
+      ld[LS_ATT] = CTC ? 0 : (c >= 0 ? cr[JC_ATT] : __builtin_bit_cast(int32_t, -INFINITY));
+    }
   }
   if (tid == 0) {
     bool all = true;
@@ -337,6 +483,86 @@ __global__ __launch_bounds__(64) void aed_joint_result_kernel(const int32_t* __r
     const float* jr = js_row(const_cast<float*>(js), F, u * N + j, s & 1);
     att[u * N + j] = jr[JS_ATT];
     ctc[u * N + j] = jr[JS_CTC];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------- LM
+// What a descriptor must hold for the LM entry points: with CTC everything check_joint_desc asks; without, the search's own
+// checks and the pre-beam's (no scorer state, so max_frames is not looked at).  Then the int32 offsets of the two LM blobs.
+int check_lm_desc(const m3_aed_joint_desc* d, bool ctc) {
+  M3_REQUIRE(d != nullptr, "aed_ngram: null descriptor");
+  if (ctc) {
+    if (int rc = check_joint_desc(d)) return rc;
+  } else {
+    if (int rc = check_search_desc(&d->search)) return rc;
+    const m3_aed_search_desc* s = &d->search;
+    M3_REQUIRE(s->V >= 2, "aed_ngram: V = %d, a token and eos need two different ids", s->V);
+    M3_REQUIRE(d->pre_beam >= s->beam && d->pre_beam <= AS_MAX_BEAM && d->pre_beam <= s->V,
+               "aed_ngram: pre_beam = %d, need beam = %d <= pre_beam <= min(%d, V = %d)", d->pre_beam, s->beam, AS_MAX_BEAM, s->V);
+  }
+  const size_t R = (size_t)d->search.B * d->search.beam, K = (size_t)d->pre_beam;
+  M3_REQUIRE(R * 2 * LS_WORDS <= (size_t)INT_MAX, "aed_ngram: %zu rows overflow the int32 offsets of the LM state", R);
+  M3_REQUIRE(R * K * (LC_WORDS + JC_WORDS) <= (size_t)INT_MAX, "aed_ngram: %zu rows x %zu candidates overflow the int32 offsets of the LM scratch", R, K);
+  return 0;
+}
+size_t lm_state_bytes(const m3_aed_joint_desc* d) { return align_up(4 * (size_t)d->search.B * d->search.beam * 2 * LS_WORDS, 256); }
+size_t lm_scratch_bytes(const m3_aed_joint_desc* d) {
+  return align_up(4 * (size_t)d->search.B * d->search.beam * d->pre_beam * (LC_WORDS + JC_WORDS), 256);
+}
+
+// everything an LM entry point checks before it launches: descriptor, search state, (CTC) scorer state and joint scratch, LM blobs
+int check_lm(const m3_aed_joint_desc* d, bool ctc, const void* st, size_t st_bytes, const void* js, size_t js_bytes, const void* scr,
+             size_t scr_bytes, const void* ls, size_t ls_bytes, const void* lscr, size_t lscr_bytes, bool with_scratch, const char* what) {
+  if (int rc = check_lm_desc(d, ctc)) return rc;
+  if (ctc) {
+    if (int rc = check_joint(d, st, st_bytes, js, js_bytes, scr, scr_bytes, with_scratch, what)) return rc;
+  } else {
+    if (int rc = check_search_state(&d->search, st, st_bytes, what)) return rc;
+  }
+  M3_REQUIRE(ls_bytes >= lm_state_bytes(d), "%s: LM state %zu bytes < required %zu", what, ls_bytes, lm_state_bytes(d));
+  M3_REQUIRE(d->search.B == 0 || (ls != nullptr && ((uintptr_t)ls & 15) == 0), "%s: the LM state must be 16-byte aligned device memory", what);
+  if (with_scratch) {
+    M3_REQUIRE(lscr_bytes >= lm_scratch_bytes(d), "%s: LM scratch %zu bytes < required %zu", what, lscr_bytes, lm_scratch_bytes(d));
+    M3_REQUIRE(d->search.B == 0 || (lscr != nullptr && ((uintptr_t)lscr & 15) == 0), "%s: the LM scratch must be 16-byte aligned device memory", what);
+  }
+  return 0;
+}
+
+int check_lm_args(const char* what, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha, double beta, int B) {
+  M3_REQUIRE(B == 0 || lm_on != nullptr, "%s: null lm_on", what);
+  M3_REQUIRE(B == 0 || lm_image != nullptr, "%s: null LM image", what);
+  M3_REQUIRE(lm_bytes % 4 == 0 && lm_bytes >= LM_HDR_WORDS * 4 && lm_bytes <= kLmMaxBytes, "%s: LM image of %zu bytes (a multiple of 4 in [%d, %zu])",
+             what, lm_bytes, LM_HDR_WORDS * 4, kLmMaxBytes);
+  M3_REQUIRE(std::isfinite(alpha) && std::isfinite(beta), "%s: alpha or beta is not finite", what);
+  return 0;
+}
+
+// the candidate records of the CTC = false form live behind the LM scratch's (state, sum) pairs
+int32_t* lm_cand(const m3_aed_joint_desc* d, void* lscr) {
+  return (int32_t*)lscr + (size_t)d->search.B * d->search.beam * d->pre_beam * LC_WORDS;
+}
+
+// one thread per row, after m3_aed_search_reset: [sos] is in the image's start state with sum 0.0 and n = 0; buffer 1 is 0
+__global__ __launch_bounds__(256) void aed_lm_reset_kernel(int R, int N, int32_t* ls, int start) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= R) return;
+  int32_t* row = ls + (size_t)r * 2 * LS_WORDS;
+  for (int w = 0; w < 2 * LS_WORDS; ++w) row[w] = 0;
+  row[LS_STATE] = start;
+  row[LS_ATT] = __builtin_bit_cast(int32_t, r % N == 0 ? 0.f : -INFINITY);
+}
+
+__global__ __launch_bounds__(64) void aed_lm_result_kernel(const int32_t* __restrict__ st, int N, int P, const int32_t* __restrict__ ls,
+                                                           float* __restrict__ lm, int32_t* __restrict__ lm_state, int32_t* __restrict__ n,
+                                                           float* __restrict__ att) {
+  const int u = blockIdx.x, j = threadIdx.x;
+  const int s = min(max(as_header(st, u)[AS_STEP], 0), P - 1);
+  if (j < N) {
+    const int32_t* row = ls + ((size_t)(u * N + j) * 2 + (s & 1)) * LS_WORDS;
+    lm[u * N + j] = (float)*reinterpret_cast<const double*>(row + LS_LM);
+    lm_state[u * N + j] = row[LS_STATE];
+    if (n) n[u * N + j] = row[LS_N];
+    if (att) att[u * N + j] = __builtin_bit_cast(float, row[LS_ATT]);
   }
 }
 
@@ -379,9 +605,9 @@ int m3_aed_joint_score(const m3_aed_joint_desc* desc, const void* search_state, 
   if (s->B == 0) return 0;
   M3_REQUIRE(logits != nullptr, "aed_joint_score: null pointer");
   const SearchLayout l = search_layout(s);
-  hipLaunchKernelGGL(aed_joint_score_kernel, dim3((unsigned)(s->B * s->beam)), dim3(64), 0, (hipStream_t)stream, (const int32_t*)search_state,
+  hipLaunchKernelGGL((aed_joint_score_kernel<true, false, NoLm>), dim3((unsigned)(s->B * s->beam)), dim3(64), 0, (hipStream_t)stream, (const int32_t*)search_state,
                      s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames, (const float*)joint_state, (int32_t*)scratch,
-                     (float*)scratch, logits, ldl, ctc, ldc, ctc_rows, ctc_weight);
+                     (float*)scratch, logits, ldl, ctc, ldc, ctc_rows, ctc_weight, NoLm{});
   M3_LAUNCH_CHECK();
   return 0;
 }
@@ -392,9 +618,9 @@ int m3_aed_joint_prune(const m3_aed_joint_desc* desc, void* search_state, size_t
   const m3_aed_search_desc* s = &desc->search;
   if (s->B == 0) return 0;
   const SearchLayout l = search_layout(s);
-  hipLaunchKernelGGL(aed_joint_prune_kernel, dim3((unsigned)s->B), dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state, s->B, s->beam,
+  hipLaunchKernelGGL((aed_joint_prune_kernel<true, false, NoLm>), dim3((unsigned)s->B), dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state, s->B, s->beam,
                      l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames, (float*)joint_state, (const int32_t*)scratch,
-                     (const float*)scratch, done);
+                     (const float*)scratch, done, NoLm{});
   M3_LAUNCH_CHECK();
   return 0;
 }
@@ -406,6 +632,104 @@ int m3_aed_joint_result(const m3_aed_joint_desc* desc, const void* search_state,
   M3_REQUIRE(att && ctc, "aed_joint_result: null pointer");
   hipLaunchKernelGGL(aed_joint_result_kernel, dim3((unsigned)desc->search.B), dim3(64), 0, (hipStream_t)stream, (const int32_t*)search_state,
                      desc->search.beam, search_layout(&desc->search).P, desc->max_frames, (const float*)joint_state, att, ctc);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+size_t m3_aed_ngram_state_size(const m3_aed_joint_desc* desc) {
+  if (check_lm_desc(desc, false)) return 0;
+  return lm_state_bytes(desc);
+}
+
+size_t m3_aed_ngram_scratch_size(const m3_aed_joint_desc* desc) {
+  if (check_lm_desc(desc, false)) return 0;
+  return lm_scratch_bytes(desc);
+}
+
+int m3_aed_ngram_reset(const m3_aed_joint_desc* desc, void* lm_state, size_t lm_state_bytes, const void* lm_image, size_t lm_bytes,
+                    m3_stream stream) {
+  if (int rc = check_lm_desc(desc, false)) return rc;
+  M3_REQUIRE(lm_state_bytes >= m3::lm_state_bytes(desc), "aed_ngram_reset: LM state %zu bytes < required %zu", lm_state_bytes, m3::lm_state_bytes(desc));
+  M3_REQUIRE(desc->search.B == 0 || (lm_state != nullptr && ((uintptr_t)lm_state & 15) == 0), "aed_ngram_reset: the LM state must be 16-byte aligned device memory");
+  M3_REQUIRE(lm_bytes % 4 == 0 && lm_bytes >= LM_HDR_WORDS * 4 && lm_bytes <= kLmMaxBytes && lm_image != nullptr,
+             "aed_ngram_reset: LM image of %zu bytes (a multiple of 4 in [%d, %zu])", lm_bytes, LM_HDR_WORDS * 4, kLmMaxBytes);
+  // the image's header, read back once per search: what lm_view refuses here the kernels would run as "LM off"
+  int32_t head[LM_HDR_WORDS];
+  M3_CHECK_HIP(hipMemcpy(head, lm_image, sizeof(head), hipMemcpyDeviceToHost));
+  LmView view;
+  M3_REQUIRE(lm_view(head, (long long)(lm_bytes / 4), &view), "aed_ngram_reset: the LM image's header does not describe an image of %zu bytes", lm_bytes);
+  M3_REQUIRE(view.V == desc->search.V, "aed_ngram_reset: the LM image was built for V = %d, the search has V = %d", view.V, desc->search.V);
+  if (desc->search.B == 0) return 0;
+  const int R = desc->search.B * desc->search.beam;
+  hipLaunchKernelGGL(aed_lm_reset_kernel, dim3((unsigned)cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream, R, desc->search.beam, (int32_t*)lm_state,
+                     view.start);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+int m3_aed_ngram_score(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, const void* joint_state,
+                    size_t joint_state_bytes, void* scratch, size_t scratch_bytes, const void* lm_state, size_t lm_state_bytes,
+                    void* lm_scratch, size_t lm_scratch_bytes, const float* logits, int ldl, const float* ctc, int ldc, int ctc_rows,
+                    float ctc_weight, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha, double beta, int use_eos,
+                    m3_stream stream) {
+  M3_REQUIRE(ctc_weight >= 0.f && ctc_weight <= 1.f, "aed_ngram_score: ctc_weight = %g outside [0, 1]", (double)ctc_weight);
+  const bool with_ctc = ctc_weight > 0.f;
+  M3_REQUIRE((ctc != nullptr) == with_ctc || (desc && desc->search.B == 0), "aed_ngram_score: the CTC log-probabilities are given exactly when ctc_weight > 0 (ctc_weight = %g)",
+             (double)ctc_weight);
+  if (int rc = check_lm(desc, with_ctc, search_state, search_state_bytes, joint_state, joint_state_bytes, scratch, scratch_bytes, lm_state,
+                        lm_state_bytes, lm_scratch, lm_scratch_bytes, true, "aed_ngram_score")) return rc;
+  if (with_ctc)
+    if (int rc = check_ctc(desc, ctc, ldc, ctc_rows, "aed_ngram_score")) return rc;
+  const m3_aed_search_desc* s = &desc->search;
+  M3_REQUIRE(ldl >= s->V, "aed_ngram_score: ldl = %d < V = %d", ldl, s->V);
+  if (int rc = check_lm_args("aed_ngram_score", lm_image, lm_bytes, lm_on, alpha, beta, s->B)) return rc;
+  M3_REQUIRE(use_eos == 0 || use_eos == 1, "aed_ngram_score: use_eos = %d", use_eos);
+  if (s->B == 0) return 0;
+  M3_REQUIRE(logits != nullptr, "aed_ngram_score: null pointer");
+  const SearchLayout l = search_layout(s);
+  const LmFuse lx{(const int32_t*)lm_image, (long long)(lm_bytes / 4), lm_on, (int32_t*)const_cast<void*>(lm_state), (int32_t*)lm_scratch, alpha, beta, use_eos};
+  if (with_ctc)
+    hipLaunchKernelGGL((aed_joint_score_kernel<true, true, LmFuse>), dim3((unsigned)(s->B * s->beam)), dim3(64), 0, (hipStream_t)stream,
+                       (const int32_t*)search_state, s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames,
+                       (const float*)joint_state, (int32_t*)scratch, (float*)scratch, logits, ldl, ctc, ldc, ctc_rows, ctc_weight, lx);
+  else
+    hipLaunchKernelGGL((aed_joint_score_kernel<false, true, LmFuse>), dim3((unsigned)(s->B * s->beam)), dim3(64), 0, (hipStream_t)stream,
+                       (const int32_t*)search_state, s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, 0, (const float*)nullptr,
+                       lm_cand(desc, lm_scratch), (float*)nullptr, logits, ldl, (const float*)nullptr, 0, 0, 0.f, lx);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+int m3_aed_ngram_prune(const m3_aed_joint_desc* desc, void* search_state, size_t search_state_bytes, void* joint_state, size_t joint_state_bytes,
+                    const void* scratch, size_t scratch_bytes, void* lm_state, size_t lm_state_bytes, const void* lm_scratch,
+                    size_t lm_scratch_bytes, int32_t* done, m3_stream stream) {
+  const bool with_ctc = joint_state != nullptr;                  // the CTC = false form has no scorer state
+  if (int rc = check_lm(desc, with_ctc, search_state, search_state_bytes, joint_state, joint_state_bytes, scratch, scratch_bytes, lm_state,
+                        lm_state_bytes, lm_scratch, lm_scratch_bytes, true, "aed_ngram_prune")) return rc;
+  const m3_aed_search_desc* s = &desc->search;
+  if (s->B == 0) return 0;
+  const SearchLayout l = search_layout(s);
+  const LmFuse lx{nullptr, 0, nullptr, (int32_t*)lm_state, (int32_t*)const_cast<void*>(lm_scratch), 0.0, 0.0, 0};
+  if (with_ctc)
+    hipLaunchKernelGGL((aed_joint_prune_kernel<true, true, LmFuse>), dim3((unsigned)s->B), dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state,
+                       s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames, (float*)joint_state, (const int32_t*)scratch,
+                       (const float*)scratch, done, lx);
+  else
+    hipLaunchKernelGGL((aed_joint_prune_kernel<false, true, LmFuse>), dim3((unsigned)s->B), dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state,
+                       s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, 0, (float*)nullptr,
+                       (const int32_t*)lm_cand(desc, const_cast<void*>(lm_scratch)), (const float*)nullptr, done, lx);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+int m3_aed_ngram_result(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, const void* lm_state,
+                     size_t lm_state_bytes, float* lm, int32_t* lm_state_out, int32_t* n, float* att, m3_stream stream) {
+  if (int rc = check_lm(desc, false, search_state, search_state_bytes, nullptr, 0, nullptr, 0, lm_state, lm_state_bytes, nullptr, 0, false,
+                        "aed_ngram_result")) return rc;
+  if (desc->search.B == 0) return 0;
+  M3_REQUIRE(lm && lm_state_out, "aed_ngram_result: null pointer");
+  hipLaunchKernelGGL(aed_lm_result_kernel, dim3((unsigned)desc->search.B), dim3(64), 0, (hipStream_t)stream, (const int32_t*)search_state,
+                     desc->search.beam, search_layout(&desc->search).P, (const int32_t*)lm_state, lm, lm_state_out, n, att);
   M3_LAUNCH_CHECK();
   return 0;
 }

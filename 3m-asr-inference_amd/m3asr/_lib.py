@@ -265,6 +265,13 @@ SIGNATURES = {
     "m3_aed_joint_score": (_i, [_P(AedJointDesc), _vp, _sz, _vp, _sz, _vp, _sz, _vp, _i, _vp, _i, _i, _f, _vp]),
     "m3_aed_joint_prune": (_i, [_P(AedJointDesc), _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     "m3_aed_joint_result": (_i, [_P(AedJointDesc), _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "m3_aed_ngram_state_size": (_sz, [_P(AedJointDesc)]),
+    "m3_aed_ngram_scratch_size": (_sz, [_P(AedJointDesc)]),
+    "m3_aed_ngram_reset": (_i, [_P(AedJointDesc), _vp, _sz, _vp, _sz, _vp]),
+    "m3_aed_ngram_score": (_i, [_P(AedJointDesc), _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _i, _vp, _i, _i, _f, _vp, _sz, _vp,
+                             _d, _d, _i, _vp]),
+    "m3_aed_ngram_prune": (_i, [_P(AedJointDesc), _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "m3_aed_ngram_result": (_i, [_P(AedJointDesc), _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

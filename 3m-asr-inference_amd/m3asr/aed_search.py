@@ -24,7 +24,15 @@ offers its `pre_beam` largest attention log-probabilities, m3_aed_joint_score ru
 utterance's CTC log-probabilities, m3_aed_joint_prune keeps the `beam` best keys and moves the scorer states with the
 hypotheses.  Those two launches stand where m3_aed_search_prune stood: 8 L + 4.  The CTC output comes with the call
 (ctc_logits / ctc_rows, one row per memory row); its log-softmax runs on the device once per call.  With ctc_weight = 0 nothing
-of this exists: no scorer state, the same launches, the same bits as before."""
+of this exists: no scorer state, the same launches, the same bits as before.
+
+N-GRAM LM FUSION AND A LENGTH BONUS (lm=; the contract is restated in tests/aed_lm_ref.py).  With an NgramLm
+(m3asr.lm, already moved with .to(device)) every candidate also takes one step through the LM and the rank is
+(1 - ctc_weight) att + ctc_weight ctc + lm_weight lm + length_bonus n, n the hypothesis's tokens, eos included.
+m3_aed_ngram_score and m3_aed_ngram_prune stand where the joint calls stood: still 8 L + 4.  ctc_weight = 0 with an LM is attention
+plus LM: no CTC input, no scorer state; the rows still offer `pre_beam` candidates, because the LM scores the pre-beam only.
+lm_on (per call, per utterance) switches the LM off for single utterances, which then get the bits of the search without it.
+Without lm nothing of this exists."""
 import math
 
 import torch
@@ -34,7 +42,8 @@ from .rescore import LN_EPS
 
 
 class AttentionBeamSearch:
-    def __init__(self, rescorer, B, beam, max_steps, poll=8, use_graph=False, ctc_weight=0.0, pre_beam=None):
+    def __init__(self, rescorer, B, beam, max_steps, poll=8, use_graph=False, ctc_weight=0.0, pre_beam=None, lm=None, lm_weight=0.0,
+                 length_bonus=0.0, lm_eos=True):
         """rescorer: the AttentionRescorer whose uploaded weights and config the search shares; B utterances per call, `beam`
         hypotheses each (1 <= beam <= min(64, vocab)); max_steps: the most tokens a hypothesis can get (it sizes the state and
         the K / V cache, see the module docstring; more than max_len - 1 steps are never taken).  poll: steps between two reads of
@@ -44,6 +53,9 @@ class AttentionBeamSearch:
         ctc_weight in [0, 1]: above 0 the search is the joint CTC/attention search (module docstring) and every call must bring
         the CTC output; pre_beam: the candidates a row offers to the CTC scorer, beam <= pre_beam <= min(64, vocab), default
         min(max(beam, ceil(1.5 beam)), 64, vocab).  The scorer state is allocated by the first call, from its longest memory.
+        lm: an NgramLm over the decoder's vocabulary, already moved with .to(device) (which validates it); lm_weight and
+        length_bonus: the weights of its log-probability and of the token count in the key; lm_eos: a hypothesis that ends also
+        takes log P(</s> | its LM state).  pre_beam applies whenever lm is given, whatever ctc_weight.
         Raises M3Error before anything is allocated for a beam or a head size the kernels do not take."""
         cfg = rescorer.cfg
         self.rescorer, self.cfg, self.device = rescorer, cfg, rescorer.device
@@ -55,8 +67,17 @@ class AttentionBeamSearch:
         self.ctc_weight = float(ctc_weight)
         if not 0.0 <= self.ctc_weight <= 1.0:                      # also refuses NaN
             raise _lib.M3Error("AttentionBeamSearch: ctc_weight = %r outside [0, 1]" % (ctc_weight,))
+        self.lm, self.lm_weight, self.length_bonus, self.lm_eos = lm, float(lm_weight), float(length_bonus), bool(lm_eos)
+        if lm is not None:
+            if not (math.isfinite(self.lm_weight) and math.isfinite(self.length_bonus)):
+                raise _lib.M3Error("AttentionBeamSearch: lm_weight = %r / length_bonus = %r is not finite" % (lm_weight, length_bonus))
+            if lm.dev is None or not lm.dev.is_cuda:
+                raise _lib.M3Error("AttentionBeamSearch: the LM is not on %s; move it with NgramLm.to(device), which validates it" % (self.device,))
+            if lm.vocab_size != cfg.vocab:
+                raise _lib.M3Error("AttentionBeamSearch: the LM was built for a vocabulary of %d, the attention decoder has %d" % (
+                    lm.vocab_size, cfg.vocab))
         self.pre_beam = 0
-        if self.ctc_weight > 0:
+        if self.ctc_weight > 0 or lm is not None:
             self.pre_beam = min(max(self.beam, math.ceil(1.5 * self.beam)), 64, cfg.vocab) if pre_beam is None else int(pre_beam)
             if not self.beam <= self.pre_beam <= min(64, cfg.vocab):
                 raise _lib.M3Error("AttentionBeamSearch: pre_beam = %d, need beam = %d <= pre_beam <= min(64, vocab = %d)" % (
@@ -76,13 +97,20 @@ class AttentionBeamSearch:
         self._done_host = torch.zeros(self.B, dtype=torch.int32).pin_memory()     # the poll's target: one small asynchronous copy
         # joint decoding only: descriptor, scorer state and candidate scratch, sized by the first call that needs them
         self.jdesc = self.jstate = self.jscratch = self.ctc = None
+        # LM fusion only: its descriptor without a CTC part, the LM state and scratch (sized by B, beam and pre_beam alone), lm_on
+        self.ldesc = self.lstate = self.lscratch = self.lm_on = None
+        if lm is not None:
+            self.ldesc = ops.aed_lm_desc(self.desc, self.pre_beam)
+            self.lstate = torch.zeros(ops.aed_lm_state_size(self.ldesc), dtype=torch.uint8, device=dev)
+            self.lscratch = torch.zeros(ops.aed_lm_scratch_size(self.ldesc), dtype=torch.uint8, device=dev)
+            self.lm_on = torch.ones(self.B, dtype=torch.int32, device=dev)
         self.kvp = None           # the memory's K / V projection of the current call, (rows, num_blocks * 2 D)
         self._graph = None
         self.steps_issued = 0     # of the last call
         self.last = None          # device tensors of the last call: m3_aed_search_result's, plus state and done
 
     def launches_per_step(self):
-        return 8 * self.cfg.num_blocks + (4 if self.ctc_weight > 0 else 3)
+        return 8 * self.cfg.num_blocks + (4 if self.ctc_weight > 0 or self.lm is not None else 3)
 
     # ---- one step: the same launches with the same arguments, whatever the step
     def _step(self):
@@ -103,7 +131,12 @@ class AttentionBeamSearch:
             ops.linear(self.h, w[q + "feed_forward.w_2.weight"], w[q + "feed_forward.w_2.bias"], resid=x, out=x)
         ops.linear(x, w["decoder.output_layer.weight"], w["decoder.output_layer.bias"],
                    ln=(w["decoder.after_norm.weight"], w["decoder.after_norm.bias"], LN_EPS), out=self.logits)
-        if self.ctc_weight > 0:
+        if self.lm is not None:
+            jd = self.jdesc if self.ctc_weight > 0 else self.ldesc
+            ops.aed_lm_score(jd, st, self.jstate, self.jscratch, self.lstate, self.lscratch, self.logits, self.ctc, self.ctc_weight,
+                             self.lm.dev, self.lm_on, self.lm_weight, self.length_bonus, self.lm_eos)
+            ops.aed_lm_prune(jd, st, self.jstate, self.jscratch, self.lstate, self.lscratch, self.done)
+        elif self.ctc_weight > 0:
             ops.aed_joint_score(self.jdesc, st, self.jstate, self.jscratch, self.logits, self.ctc, self.ctc_weight)
             ops.aed_joint_prune(self.jdesc, st, self.jstate, self.jscratch, self.done)
         else:
@@ -113,6 +146,8 @@ class AttentionBeamSearch:
         ops.aed_search_reset(self.desc, self.state, meta[0], meta[1], cap)
         if self.ctc_weight > 0:
             ops.aed_joint_reset(self.jdesc, self.state, self.jstate, self.ctc)
+        if self.lm is not None:
+            ops.aed_lm_reset(self.ldesc, self.lstate, self.lm.dev)
         self.done.zero_()
 
     def _take_ctc(self, ctc, n_rows, frames, log_probs):
@@ -154,15 +189,27 @@ class AttentionBeamSearch:
         ops.linear(rows, w["decoder.src_kv_all.weight"][:L * 2 * D], w["decoder.src_kv_all.bias"][:L * 2 * D], ln=norm,
                    out=self.kvp[:rows.shape[0]])
 
-    def _run(self, rows, row0, lens, raw_memory, detail, max_steps, poll, ctc=None, ctc_log_probs=False):
+    def _take_lm_on(self, lm_on):
+        """the per-utterance switch of the call -> self.lm_on (kept across calls: a captured step reads the same address)"""
+        if self.lm is None:
+            if lm_on is not None:
+                raise _lib.M3Error("search: lm_on given, but the search was built without an LM")
+            return
+        on = [1] * self.B if lm_on is None else [int(bool(v)) for v in torch.as_tensor(lm_on).reshape(-1).tolist()]
+        if len(on) != self.B:
+            raise _lib.M3Error("search: lm_on has %d entries for %d utterances" % (len(on), self.B))
+        self.lm_on.copy_(torch.tensor(on, dtype=torch.int32))
+
+    def _run(self, rows, row0, lens, raw_memory, detail, max_steps, poll, ctc=None, ctc_log_probs=False, lm_on=None):
         """rows (n, D) memory rows on the device; row0 / lens: B Python ints each, validated by the caller; ctc: None or the
-        CTC output of the same n rows"""
+        CTC output of the same n rows; lm_on: None or B switches"""
         cfg, d = self.cfg, self.desc
         cap = self.max_steps if max_steps is None else int(max_steps)
         if not 1 <= cap <= self.max_steps:
             raise _lib.M3Error("search: max_steps = %d outside [1, %d] (the constructor's bound sizes the cache)" % (cap, self.max_steps))
         poll = self.poll if poll is None else max(int(poll), 1)
         self._take_ctc(ctc, rows.shape[0], max(lens), ctc_log_probs)
+        self._take_lm_on(lm_on)
         meta = torch.tensor([row0, lens], dtype=torch.int32).to(self.device)
         self._project(rows, raw_memory)
         self._reset(meta, cap)
@@ -184,18 +231,25 @@ class AttentionBeamSearch:
             jres = ops.aed_joint_result(self.jdesc, self.state, self.jstate)
             self.last.update(jres, joint_state=self.jstate)
             parts = [jres["att"].reshape(-1).view(torch.int32), jres["ctc"].reshape(-1).view(torch.int32)]
+        if self.lm is not None:
+            lres = ops.aed_lm_result(self.ldesc, self.state, self.lstate)
+            self.last.update(lm=lres["lm"], lm_state=lres["lm_state"], lm_n=lres["lm_n"], lm_blob=self.lstate)
+            if not parts:                                           # attention + LM: the att part rides in the LM state, ctc is 0
+                self.last.update(att=lres["lm_att"], ctc=torch.zeros_like(lres["lm_att"]))
+                parts = [self.last["att"].reshape(-1).view(torch.int32), self.last["ctc"].reshape(-1).view(torch.int32)]
+            parts.append(lres["lm"].reshape(-1).view(torch.int32))
         host = torch.cat([res["hyp_tokens"].reshape(-1), res["hyp_len"].reshape(-1), res["finished"].reshape(-1), res["best"],
                           res["score"].reshape(-1).view(torch.int32)] + parts).cpu()
         B, N, S = self.B, self.beam, self.max_steps
         toks = host[:B * N * S].view(B, N, S)
         o = B * N * S
         hlen, fin, best = host[o:o + B * N].tolist(), host[o + B * N:o + 2 * B * N].tolist(), host[o + 2 * B * N:o + 2 * B * N + B].tolist()
-        score = host[o + 2 * B * N + B:].view(torch.float32).tolist()             # score, then (joint) att and ctc: B * N each
+        score = host[o + 2 * B * N + B:].view(torch.float32).tolist()             # score, then (joint) att, ctc, (LM) lm: B * N each
         out = []
         for b in range(B):
             hyps = [(tuple(toks[b, i, :hlen[b * N + i]].tolist()), score[b * N + i], bool(fin[b * N + i])) for i in range(N)]
             if parts:
-                hyps = [h + (score[B * N + b * N + i], score[2 * B * N + b * N + i]) for i, h in enumerate(hyps)]
+                hyps = [h + tuple(score[(k + 1) * B * N + b * N + i] for k in range(len(parts))) for i, h in enumerate(hyps)]
             out.append((list(hyps[best[b]][0]), hyps) if detail else list(hyps[best[b]][0]))
         return out
 
@@ -219,7 +273,7 @@ class AttentionBeamSearch:
 
     # ---- the public calls
     def search(self, memory, mem_len, raw_memory=False, detail=False, max_steps=None, poll=None, ctc_logits=None,
-               ctc_log_probs=False):
+               ctc_log_probs=False, lm_on=None):
         """memory (B, T', D) on the device: the encoder's normalised hidden states (Engine.hidden()), or with raw_memory the
         residual stream before after_norm (Engine.hidden(normalized=False)), the LayerNorm then riding in the K / V GEMM's
         prologue; mem_len (B,) valid frames.  Utterance b stops once its `beam` hypotheses have all ended in eos, or after
@@ -229,6 +283,8 @@ class AttentionBeamSearch:
         Joint decoding (ctc_weight > 0): ctc_logits (B, T', V), the CTC output over the memory's frames (another frame count or
         vocabulary is refused); ctc_log_probs: it already holds log-probabilities and is used as it is.  The score is then the
         joint key and detail gives (tokens, key, finished, att, ctc).
+        LM fusion (lm given): lm_on, None or B flags, 0 = this utterance is searched without the LM; detail appends lm, the LM's
+        log-probability of the hypothesis: (tokens, key, finished, att, ctc, lm), ctc = 0.0 when ctc_weight = 0.
         mem_len < 1 is refused before anything is launched.  The device tensors of the call stay in self.last."""
         cfg, B = self.cfg, self.B
         memory = memory.to(self.device, torch.float32)
@@ -244,9 +300,10 @@ class AttentionBeamSearch:
         if ctc_logits is not None and self.ctc_weight > 0 and (ctc_logits.dim() != 3 or ctc_logits.shape[0] != B or ctc_logits.shape[1] != Tm):
             raise _lib.M3Error("search: the CTC output %s does not cover the memory's %d x %d frames" % (tuple(ctc_logits.shape), B, Tm))
         return self._run(memory.contiguous().view(B * Tm, cfg.dim), [b * Tm for b in range(B)], lens, raw_memory, detail, max_steps, poll,
-                         ctc_logits, ctc_log_probs)
+                         ctc_logits, ctc_log_probs, lm_on)
 
-    def search_rows(self, rows, row0, raw_memory=True, detail=False, max_steps=None, poll=None, ctc_rows=None, ctc_log_probs=False):
+    def search_rows(self, rows, row0, raw_memory=True, detail=False, max_steps=None, poll=None, ctc_rows=None, ctc_log_probs=False,
+                    lm_on=None):
         """The search over PACKED memory rows, as AttentionRescorer.rescore_rows takes them: rows (>= R, D) on the device,
         row0 (B + 1,) int32 (m3_aed_memory_gather leaves them so): utterance b owns rows [row0[b], row0[b + 1]).  raw_memory:
         the rows are the residual stream before after_norm (what the streaming store keeps).  An utterance without a row is
@@ -264,4 +321,4 @@ class AttentionBeamSearch:
         if ctc_rows is not None and self.ctc_weight > 0 and ctc_rows.dim() != 2:
             raise _lib.M3Error("search_rows: the CTC output %s is not (rows, vocab)" % (tuple(ctc_rows.shape),))
         return self._run(rows[:r0[-1]].to(self.device, torch.float32), r0[:-1], lens, raw_memory, detail, max_steps, poll,
-                         ctc_rows, ctc_log_probs)
+                         ctc_rows, ctc_log_probs, lm_on)

@@ -370,7 +370,8 @@ class CtcDecoder:
         return out if detail else [list(best) for best, _ in out]
 
     def attention(self, xs: torch.Tensor, xs_lens: torch.Tensor, beam_size: int, decoding_chunk_size: int = -1,
-                  num_decoding_left_chunks: int = -1, max_steps=None, detail=False, ctc_weight: float = 0.0, pre_beam=None):
+                  num_decoding_left_chunks: int = -1, max_steps=None, detail=False, ctc_weight: float = 0.0, pre_beam=None,
+                  lm=None, lm_weight: float = 0.0, length_bonus: float = 0.0):
         """The reference's decoding mode `attention` for any batch size, all on the device: encoder forward, then the attention
         decoder's own autoregressive beam search over the encoder's hidden states (m3asr.aed_search).  There is
         no first pass, and the right-to-left decoder takes no part.  ctc_weight = 0: CTC scores take no part either.
@@ -379,7 +380,9 @@ class CtcDecoder:
         hypothesis that reach the CTC scorer (default min(max(beam, ceil(1.5 beam)), 64, vocab)).  max_steps: the most tokens per hypothesis
         (default: the encoder's output frames, the reference's maxlen); it sizes the search's K / V cache.
         -> the best token list per utterance; detail: (best tokens, [(tokens, score, finished)]) per utterance, and
-        (tokens, key, finished, att, ctc) per hypothesis in joint mode."""
+        (tokens, key, finished, att, ctc) per hypothesis in joint mode.
+        lm: an NgramLm on the engine's device (NgramLm.to): n-gram LM fusion and a length bonus inside the search,
+        the rank (1 - ctc_weight) att + ctc_weight ctc + lm_weight lm + length_bonus |y|; detail then appends lm to each hypothesis."""
         if self.rescorer is None:
             raise _lib.M3Error("CtcDecoder.attention: built without a rescorer (CtcDecoder(engine, rescorer=AttentionRescorer(...)))")
         from .aed_search import AttentionBeamSearch
@@ -392,11 +395,13 @@ class CtcDecoder:
             raise _lib.M3Error("CtcDecoder.attention: max_steps = %d, need at least 1" % steps)
         # the searcher (state, K / V cache, work buffers) is kept across calls: sized by the step bound rounded up to a multiple
         # of 64 and re-allocated only when a call needs more; the call's own bound goes to search()
-        key, kept = (B, int(beam_size), float(ctc_weight), pre_beam), getattr(self, "_attention_search", None)
+        key = (B, int(beam_size), float(ctc_weight), pre_beam, id(lm), float(lm_weight), float(length_bonus))
+        kept = getattr(self, "_attention_search", None)
         if kept is None or kept[0] != key or kept[1].max_steps < steps:
             bound = min(-(-steps // 64) * 64, self.rescorer.cfg.max_len - 1)
             kept = self._attention_search = (key, AttentionBeamSearch(self.rescorer, B, beam_size, bound, ctc_weight=ctc_weight,
-                                                                             pre_beam=pre_beam))
+                                                                             pre_beam=pre_beam, lm=lm, lm_weight=lm_weight,
+                                                                             length_bonus=length_bonus))
         ctc = res["out_nosm"][:, :frames] if float(ctc_weight) > 0 else None
         return kept[1].search(memory, res["out_lens"].cpu(), raw_memory=True, detail=detail, max_steps=steps, ctc_logits=ctc)
 

@@ -1074,6 +1074,61 @@ def aed_joint_result(desc, state, jstate):
     return out
 
 
+# ---- n-gram LM fusion and a length bonus in that search (m3_aed_ngram_*)
+def aed_lm_desc(search_desc, pre_beam, max_frames=0):
+    """The descriptor of the fused search: m3_aed_joint_desc; max_frames = 0 where there is no CTC part (ctc_weight = 0).
+    Raises M3Error on what the library rejects."""
+    d = _lib.AedJointDesc(search_desc, int(pre_beam), int(max_frames))
+    if _lib.load().m3_aed_ngram_state_size(C.byref(d)) == 0:
+        raise _lib.M3Error("m3_aed_ngram_state_size failed: " + _lib.last_error())
+    return d
+
+
+def aed_lm_state_size(desc):
+    return _lib.load().m3_aed_ngram_state_size(C.byref(desc))
+
+
+def aed_lm_scratch_size(desc):
+    return _lib.load().m3_aed_ngram_scratch_size(C.byref(desc))
+
+
+def aed_lm_reset(desc, lstate, lm_image):
+    """after aed_search_reset (and aed_joint_reset): every slot in the image's start state; refuses an image of another V"""
+    lmi, lm_bytes = _image(lm_image)
+    check(_lib.load().m3_aed_ngram_reset(C.byref(desc), _p(lstate), _nbytes(lstate), lmi, lm_bytes, _stream()), "m3_aed_ngram_reset")
+
+
+def aed_lm_score(desc, state, jstate, scratch, lstate, lscratch, logits, ctc, ctc_weight, lm_image, lm_on, alpha, beta, use_eos=True):
+    """aed_joint_score with every candidate's LM step and the fused key; ctc / jstate / scratch None exactly when ctc_weight = 0"""
+    lp, ldl = _rows(logits)
+    cp, ldc = _rows(ctc) if ctc is not None else (None, 0)
+    assert tuple(logits.shape) == (desc.search.B * desc.search.beam, desc.search.V) and lm_on.numel() == desc.search.B
+    lmi, lm_bytes = _image(lm_image)
+    check(_lib.load().m3_aed_ngram_score(C.byref(desc), _p(state), _nbytes(state), _p(jstate), _nbytes(jstate) if jstate is not None else 0,
+                                      _p(scratch), _nbytes(scratch) if scratch is not None else 0, _p(lstate), _nbytes(lstate),
+                                      _p(lscratch), _nbytes(lscratch), lp, ldl, cp, ldc, ctc.shape[0] if ctc is not None else 0,
+                                      float(ctc_weight), lmi, lm_bytes, _i32(lm_on), float(alpha), float(beta), int(bool(use_eos)),
+                                      _stream()), "m3_aed_ngram_score")
+
+
+def aed_lm_prune(desc, state, jstate, scratch, lstate, lscratch, done=None):
+    """aed_joint_prune, the survivors' LM state copied from the LM scratch; jstate / scratch None: the search without CTC"""
+    assert done is None or done.numel() == desc.search.B
+    check(_lib.load().m3_aed_ngram_prune(C.byref(desc), _p(state), _nbytes(state), _p(jstate), _nbytes(jstate) if jstate is not None else 0,
+                                      _p(scratch), _nbytes(scratch) if scratch is not None else 0, _p(lstate), _nbytes(lstate),
+                                      _p(lscratch), _nbytes(lscratch), _i32(done), _stream()), "m3_aed_ngram_prune")
+
+
+def aed_lm_result(desc, state, lstate):
+    """-> dict(lm (B, beam) float32, lm_state, lm_n (B, beam) int32, lm_att (B, beam) float32) on the device"""
+    B, N, dev = desc.search.B, desc.search.beam, state.device
+    out = dict(lm=torch.empty(B, N, dtype=torch.float32, device=dev), lm_state=torch.empty(B, N, dtype=torch.int32, device=dev),
+               lm_n=torch.empty(B, N, dtype=torch.int32, device=dev), lm_att=torch.empty(B, N, dtype=torch.float32, device=dev))
+    check(_lib.load().m3_aed_ngram_result(C.byref(desc), _p(state), _nbytes(state), _p(lstate), _nbytes(lstate), _p(out["lm"]),
+                                       _p(out["lm_state"]), _p(out["lm_n"]), _p(out["lm_att"]), _stream()), "m3_aed_ngram_result")
+    return out
+
+
 # ---------------------------------------------------------------------------------------- streaming operators
 def cat_split_cache(in_cache, inp):
     """CatSplitCache plugin: (output (B, cache+input), out_cache (B, cache)); f32 or i32 rows."""

@@ -991,6 +991,44 @@ int m3_aed_joint_prune(const m3_aed_joint_desc* desc, void* search_state, size_t
 int m3_aed_joint_result(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, const void* joint_state,
                         size_t joint_state_bytes, float* att, float* ctc, m3_stream stream);
 
+/* N-gram LM fusion and a length bonus in that search (csrc/aed_joint.hip): every candidate also takes one step
+ * through the LM image above ("LM image"; the score contract of the CTC search's fusion, unchanged) and is ranked by
+ *   key = jkey + (float)(alpha * lm + beta * n),   jkey = (1 - ctc_weight) att + ctc_weight ctc,
+ * lm the double sum of the LM's log-probabilities over the hypothesis's tokens (eos adds final[state] when use_eos), n its
+ * tokens after sos, eos included; the two products and the sum in double, rounded once.  A -inf jkey stays -inf.  The score
+ * and prune calls below stand where the joint ones stood, so the step keeps its 8 L + 4 launches.  ctc_weight = 0 is legal
+ * here: the search is then attention plus LM, jkey = att, the ctc part is 0, no CTC input is taken and neither the scorer state
+ * nor the joint scratch nor max_frames is looked at (pass NULL / 0); a row still offers pre_beam candidates.
+ * An utterance whose lm_on is 0 adds nothing: its records, keys, parts and scorer state are the joint search's, bit for bit.
+ * LM state: caller-owned, the first size query's bytes, 16-byte aligned; per row, double-buffered by the parity of the
+ *   utterance's step: lm_state, n, lm (double), and the att part where there is no scorer state to hold it.
+ * LM scratch: caller-owned, the second size query's bytes, 16-byte aligned; rewritten by every step: every candidate's
+ *   (lm_state, lm), from which prune copies the survivors' (nothing is walked twice), and the candidate records when
+ *   ctc_weight = 0.  Both sizes depend on B, beam and pre_beam only.
+ * reset: after the search's (and the joint search's) reset, once per search.  Reads the image's header back (a synchronous
+ *   20-word copy: call it outside a stream capture) and refuses an image that is not one or was built for another V; every
+ *   slot then holds the image's start state, lm = 0.0, n = 0.
+ * score: the joint score call plus the walk.  ctc is NULL exactly when ctc_weight == 0.  lm_image / lm_bytes: the DEVICE
+ *   image; lm_on: device int32 [B]; alpha, beta finite; use_eos 0 or 1.  The kernel range-checks every word of the image it
+ *   forms an address from (a bad state or next state means state 0, a bad arc range "no arcs", a token outside [0, V) unk_logp).
+ * prune: the joint prune call plus the survivors' LM state; joint_state is NULL exactly when the search runs without CTC.
+ * result: lm [B][beam] (the float32 rounding of the double) and lm_state of the hypotheses the search's result call returns;
+ *   n and att (NULL or [B][beam]): the token counts, and the attention parts as the LM state holds them for ctc_weight = 0. */
+size_t m3_aed_ngram_state_size(const m3_aed_joint_desc* desc);
+size_t m3_aed_ngram_scratch_size(const m3_aed_joint_desc* desc);
+int m3_aed_ngram_reset(const m3_aed_joint_desc* desc, void* lm_state, size_t lm_state_bytes, const void* lm_image, size_t lm_bytes,
+                    m3_stream stream);
+int m3_aed_ngram_score(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, const void* joint_state,
+                    size_t joint_state_bytes, void* scratch, size_t scratch_bytes, const void* lm_state, size_t lm_state_bytes,
+                    void* lm_scratch, size_t lm_scratch_bytes, const float* logits, int ldl, const float* ctc, int ldc, int ctc_rows,
+                    float ctc_weight, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha, double beta, int use_eos,
+                    m3_stream stream);
+int m3_aed_ngram_prune(const m3_aed_joint_desc* desc, void* search_state, size_t search_state_bytes, void* joint_state, size_t joint_state_bytes,
+                    const void* scratch, size_t scratch_bytes, void* lm_state, size_t lm_state_bytes, const void* lm_scratch,
+                    size_t lm_scratch_bytes, int32_t* done, m3_stream stream);
+int m3_aed_ngram_result(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, const void* lm_state,
+                     size_t lm_state_bytes, float* lm, int32_t* lm_state_out, int32_t* n, float* att, m3_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

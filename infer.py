@@ -26,13 +26,15 @@ Attention rescoring, for a plan built from a joint CTC/attention checkpoint: the
 attention decoder rescoring every utterance's n-best on the encoder's hidden states (m3asr.rescore).  Prints the first-pass
 best and the rescored best hypothesis of each utterance.
 
-    python3 infer.py -p aed.plan -i feat.npy --attention [--beam 10] [--max-steps K] [--ctc-weight W [--pre-beam P]]
+    python3 infer.py -p aed.plan -i feat.npy --attention [--beam 10] [--max-steps K] [--ctc-weight W] [--pre-beam P]
+                     [--lm lm.arpa [--units units.txt] [--lm-weight A] [--length-bonus B]]
 
 Attention decoding, for such a plan: the attention decoder searches on its own, autoregressively, over the encoder's hidden
 states (m3asr.aed_search); --max-steps bounds the tokens per hypothesis (default: the encoder's output frames).  Prints the
 best hypothesis of each utterance.  With --ctc-weight W > 0 the search is the one-pass joint CTC/attention search: every candidate
 is also scored by its CTC prefix probability on the forward's own CTC output and ranked by (1 - W) att + W ctc; --pre-beam P
-candidates per hypothesis go to the CTC scorer.  Both parts are printed."""
+candidates per hypothesis go to the CTC scorer.  Both parts are printed.  With --lm the n-gram LM is fused into this search
+(not into a prefix beam search): the rank gains lm_weight log P_LM + length_bonus per token, and the LM part is printed too."""
 import argparse
 import os
 import sys
@@ -76,16 +78,21 @@ def print_hotword_search(scores, device, args):
         print("utt %d biased: score=%.4f bonus=%.4f tokens=%s" % (b, h[0][1], h[0][2], " ".join(str(t) for t in h[0][0])))
 
 
+def load_lm(args, V, device):
+    """--lm [--units]: an ARPA file compiled for V tokens, or a saved image; validated and uploaded"""
+    from m3asr.lm import NgramLm
+    lm = NgramLm.load(args.lm) if args.lm.endswith(".npy") else NgramLm.from_arpa(args.lm, args.units, vocab_size=V)
+    return lm.to(device)
+
+
 def print_lm_search(scores, device, args):
     """Best prefix beam hypothesis of every utterance without and with the LM (and the hotwords, if given) fused in."""
     import torch
     from m3asr.decode import CtcBeamSearch
-    from m3asr.lm import NgramLm
     x = torch.from_numpy(np.ascontiguousarray(scores, dtype=np.float32)).to(device)
     x = x.reshape(-1, x.shape[-2], x.shape[-1])
     B, T, V = x.shape
-    lm = NgramLm.load(args.lm) if args.lm.endswith(".npy") else NgramLm.from_arpa(args.lm, args.units, vocab_size=V)
-    lm.to(device)
+    lm = load_lm(args, V, device)
     ctx = None
     if args.hotwords:
         from m3asr.context import ContextGraph, ContextSet, read_phrases
@@ -131,11 +138,15 @@ def print_attention(helper, feat, feat_len, args):
     from m3asr.rescore import AttentionRescorer
     rescorer = AttentionRescorer(helper.decoder_packed, decoder_config_of(helper.extra), helper.engine.device)
     dec = CtcDecoder(helper.engine, rescorer=rescorer)
+    lm = load_lm(args, rescorer.cfg.vocab, helper.engine.device) if args.lm else None
     out = dec.attention(torch.from_numpy(feat), torch.from_numpy(feat_len), args.beam, max_steps=args.max_steps, detail=True,
-                        ctc_weight=args.ctc_weight, pre_beam=args.pre_beam)
+                        ctc_weight=args.ctc_weight, pre_beam=args.pre_beam, lm=lm, lm_weight=args.lm_weight,
+                        length_bonus=args.length_bonus)
     for b, (best, hyps) in enumerate(out):
         chosen = next(h for h in hyps if list(h[0]) == best)
-        parts = " att=%.4f ctc=%.4f" % (chosen[3], chosen[4]) if args.ctc_weight > 0 else ""
+        parts = " att=%.4f ctc=%.4f" % (chosen[3], chosen[4]) if args.ctc_weight > 0 or lm is not None else ""
+        if lm is not None:
+            parts += " lm=%.4f" % chosen[5]
         print("utt %d attention: score=%.4f%s finished=%d tokens=%s" % (b, chosen[1], parts, chosen[2], " ".join(str(t) for t in best)))
 
 
@@ -158,7 +169,7 @@ def main(args):
         print_rescore(helper, feat, feat_len, args)
     if args.attention:
         print_attention(helper, feat, feat_len, args)
-    if args.lm:
+    if args.lm and not args.attention:                            # with --attention the LM goes into the attention search
         print_lm_search(outputs[0], helper.engine.device, args)
     elif args.hotwords:
         print_hotword_search(outputs[0], helper.engine.device, args)

@@ -7,13 +7,19 @@ memory lengths are drawn from [frames / 2, frames] as tools/bench_rescore.py dra
 --full-length gives every utterance all --frames frames.
 
   python tools/bench_attention_search.py [--batch 16] [--beam 10] [--frames 125] [--blocks 6] [--rounds 10] [--graph]
-                                         [--ctc-weight W [--pre-beam K]]
+                                         [--ctc-weight W [--pre-beam K]] [--lm N_NGRAMS | --lm-image FILE.npy] [--lm-weight A] [--length-bonus B] [--table]
 
 --ctc-weight W > 0 times the joint CTC/attention search on the same model and memories.  Its CTC output is
 synthetic too, but shaped like a trained model's: every utterance has a hidden token sequence of mem_len // 6 tokens, one spike
 every sixth frame and blank in between (logit +10 on the frame's target over unit noise), so the CTC part has an opinion on
 how long a hypothesis should be; the JSON line reports those lengths next to the hypotheses'.  The eager restatement is the
 attention-only search and is skipped in this mode.
+
+--lm N times the search with a synthetic trigram LM of about N n-grams (tools/lm_synth.py, as tools/bench_ctc_beam.py --lm
+draws it; or --lm-image: an image saved by m3asr.lm.NgramLm.save, the compile of a large LM takes minutes) fused in NEXT TO the unfused search of the same build, model, memories and --ctc-weight ("fused_*"
+beside "device_*"), and reports the fused hypotheses' lengths.  --table also prints one JSON line per (lm_weight, length_bonus)
+in {0, --lm-weight} x {0, 1, 2, 4, 6} with the lengths (all hypotheses and the best of each beam) and the finished count: one search
+each, nothing timed.  The weights are synthetic: the table shows lengths, not accuracy.
 
 "device": wall time of AttentionBeamSearch.search() per call -- the K / V GEMM, every step's launches, the polls of the done
 flags and the read of the results -- median over the rounds after a warm-up; us per step = that over the steps issued.
@@ -83,6 +89,11 @@ def main():
     ap.add_argument("--full-length", action="store_true")
     ap.add_argument("--ctc-weight", type=float, default=0.0, help="above 0: the joint CTC/attention search with this weight")
     ap.add_argument("--pre-beam", type=int, default=None, help="--ctc-weight: candidates per hypothesis for the CTC scorer")
+    ap.add_argument("--lm", type=int, default=None, metavar="N_NGRAMS", help="also time the search with a synthetic LM of N n-grams fused in")
+    ap.add_argument("--lm-image", default=None, metavar="FILE.npy", help="a compiled LM image instead of --lm")
+    ap.add_argument("--lm-weight", type=float, default=0.5)
+    ap.add_argument("--length-bonus", type=float, default=0.0)
+    ap.add_argument("--table", action="store_true", help="--lm: the hypothesis-length table over lm_weight x length_bonus")
     a = ap.parse_args()
     import aed_search_ref
     from m3asr.aed_search import AttentionBeamSearch
@@ -92,6 +103,14 @@ def main():
     B, beam, steps = a.batch, a.beam, a.max_steps or a.frames
     res = AttentionRescorer(pack_decoder(sd, dcfg), dcfg, "cuda:0")
     joint = dict(ctc_weight=a.ctc_weight, pre_beam=a.pre_beam) if a.ctc_weight > 0 else {}
+    lm = None
+    if a.lm_image:
+        from m3asr.lm import NgramLm
+        lm = NgramLm.load(a.lm_image).to("cuda:0")
+    elif a.lm is not None:
+        sys.path.insert(0, os.path.join(ROOT, "tools"))
+        from lm_synth import synthetic_lm
+        lm = synthetic_lm(a.lm, dcfg.vocab).to("cuda:0")
     search = AttentionBeamSearch(res, B, beam, steps, poll=a.poll, **joint)
     mem_d = memory.cuda()
     call = {}
@@ -130,6 +149,29 @@ def main():
 
     timed(lambda: search.search(mem_d, mem_len, **call), 3)
     add("device", search, timed(lambda: search.search(mem_d, mem_len, **call), a.rounds))
+    if lm is not None:
+        def lengths_of(o):
+            every, best = [len(h[0]) for u in o for h in u[1]], [len(u[0]) for u in o]
+            return dict(hyp_tokens_min_median_max=[min(every), statistics.median(every), max(every)],
+                        best_hyp_tokens_min_median_max=[min(best), statistics.median(best), max(best)],
+                        finished="%d/%d" % (sum(int(h[2]) for u in o for h in u[1]), B * beam))
+
+        fused = AttentionBeamSearch(res, B, beam, steps, poll=a.poll, ctc_weight=a.ctc_weight, pre_beam=a.pre_beam, lm=lm,
+                                    lm_weight=a.lm_weight, length_bonus=a.length_bonus)
+        fout = fused.search(mem_d, mem_len, detail=True, **call)
+        record["lm"] = dict(n_grams=lm.n_grams, order=lm.order, states=lm.n_states, arcs=lm.n_arcs, image_bytes=int(lm.image.nbytes),
+                            lm_weight=a.lm_weight, length_bonus=a.length_bonus, pre_beam=fused.pre_beam,
+                            launches_per_step=fused.launches_per_step(), **lengths_of(fout))
+        timed(lambda: fused.search(mem_d, mem_len, **call), 3)
+        add("fused", fused, timed(lambda: fused.search(mem_d, mem_len, **call), a.rounds))
+        record["fused_over_device"] = round(record["fused_ms_median"] / record["device_ms_median"], 3)
+        if a.table:
+            for lw in sorted({0.0, a.lm_weight}):
+                for lb in (0.0, 1.0, 2.0, 4.0, 6.0):
+                    fused.lm_weight, fused.length_bonus = lw, lb            # run-time arguments of the score launch
+                    row = lengths_of(fused.search(mem_d, mem_len, detail=True, **call))
+                    print(json.dumps(dict(table="hypothesis lengths", eos_bias=a.eos_bias, ctc_weight=a.ctc_weight, max_steps=steps,
+                                          lm_weight=lw, length_bonus=lb, steps_issued=fused.steps_issued, **row)))
     if a.graph:
         graphed = AttentionBeamSearch(res, B, beam, steps, poll=a.poll, use_graph=True, **joint)
         same = graphed.search(mem_d, mem_len, detail=True, **call) == out
