@@ -481,6 +481,17 @@ int m3_ctc_beam_nbest(const m3_ctc_beam_desc* desc, const void* state, size_t st
                       int32_t* hyp_len, float* hyp_score, int32_t* n_hyps, m3_stream stream) {
   return launch_ctc_beam_nbest(desc, state, state_bytes, hyp_tokens, hyp_len, hyp_score, n_hyps, (hipStream_t)stream);
 }
+size_t m3_ctc_align_workspace_size(const m3_ctc_align_desc* desc) { return ctc_align_workspace_size(desc); }
+int m3_ctc_align_emit(const m3_ctc_align_desc* desc, const float* logits, int ldl, const int32_t* row0, const int32_t* n_frames,
+                      const int32_t* tokens, const int32_t* tok0, float* emit, m3_stream stream) {
+  return launch_ctc_align_emit(desc, logits, ldl, row0, n_frames, tokens, tok0, emit, (hipStream_t)stream);
+}
+int m3_ctc_align_path(const m3_ctc_align_desc* desc, const float* emit, const int32_t* n_frames, const int32_t* tokens,
+                      const int32_t* tok0, void* workspace, size_t ws_bytes, float* score, int32_t* status, int32_t* state,
+                      int32_t* tok_start, int32_t* tok_end, int32_t* tok_peak, float* tok_logp, m3_stream stream) {
+  return launch_ctc_align_path(desc, emit, n_frames, tokens, tok0, workspace, ws_bytes, score, status, state, tok_start, tok_end,
+                               tok_peak, tok_logp, (hipStream_t)stream);
+}
 int m3_ctc_context_validate(const void* image, size_t image_bytes, int V) { return ctc_context_validate(image, image_bytes, V); }
 int m3_ctc_prefix_beam_search_ctx(const float* top_logp, const int32_t* top_idx, int T, int k, int beam, int blank,
                                   const void* image, size_t image_bytes, int graph, int32_t* hyp_tokens, int32_t* hyp_len,

@@ -371,6 +371,13 @@ int launch_ctc_beam_advance(const m3_ctc_beam_desc* d, void* state, size_t bytes
                             int T_chunk, const int32_t* n_frames, hipStream_t stream);
 int launch_ctc_beam_nbest(const m3_ctc_beam_desc* d, const void* state, size_t bytes, int32_t* hyp_tokens, int32_t* hyp_len,
                           float* hyp_score, int32_t* n_hyps, hipStream_t stream);
+// ctc_align.hip: CTC forced alignment: emissions of the asked-for tokens, then trellis + backtrace + spans
+size_t ctc_align_workspace_size(const m3_ctc_align_desc* d);
+int launch_ctc_align_emit(const m3_ctc_align_desc* d, const float* logits, int ldl, const int32_t* row0, const int32_t* n_frames,
+                          const int32_t* tokens, const int32_t* tok0, float* emit, hipStream_t stream);
+int launch_ctc_align_path(const m3_ctc_align_desc* d, const float* emit, const int32_t* n_frames, const int32_t* tokens,
+                          const int32_t* tok0, void* workspace, size_t ws_bytes, float* score, int32_t* status, int32_t* state,
+                          int32_t* tok_start, int32_t* tok_end, int32_t* tok_peak, float* tok_logp, hipStream_t stream);
 // Context biasing of the prefix beam search (include/m3asr.h, "context set"): one image of 4-byte words,
 //   [magic, G, V, words] then G x [n_states, A, cls, next, delta, pot (word offsets of the tables), 0, 0] then the tables.
 constexpr int32_t kCtxMagic = 0x5843334d;   // "M3CX"

@@ -61,6 +61,10 @@ class CtcGreedyDesc(C.Structure):  # m3_ctc_greedy_desc
     _fields_ = [("B", C.c_int32), ("max_frames", C.c_int32), ("blank", C.c_int32)]
 
 
+class CtcAlignDesc(C.Structure):  # m3_ctc_align_desc
+    _fields_ = [("n", C.c_int32), ("V", C.c_int32), ("blank", C.c_int32), ("max_frames", C.c_int32), ("max_tokens", C.c_int32)]
+
+
 class CtcEndpointRule(C.Structure):  # m3_ctc_endpoint_rule
     _fields_ = [("must_decoded", C.c_int32), ("min_trailing", C.c_int32), ("min_length", C.c_int32)]
 
@@ -199,6 +203,9 @@ SIGNATURES = {
     "m3_ctc_endpoint_reset_slots": (_i, [_P(CtcEndpointDesc), _vp, _sz, _vp, _i, _vp]),
     "m3_ctc_endpoint_advance": (_i, [_P(CtcEndpointDesc), _vp, _sz, _vp, _vp, _i, _i, _vp, _vp]),
     "m3_ctc_endpoint_read": (_i, [_P(CtcEndpointDesc), _vp, _sz, _vp, _vp]),
+    "m3_ctc_align_workspace_size": (_sz, [_P(CtcAlignDesc)]),
+    "m3_ctc_align_emit": (_i, [_P(CtcAlignDesc), _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "m3_ctc_align_path": (_i, [_P(CtcAlignDesc), _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "m3_cat_split_cache": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "m3_att_stream_softmax": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp]),
     "m3_rel_positional_encoding": (_i, [_vp, _vp, _i, _vp, _i, _f, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -17,6 +17,10 @@ and return types), running on the device through libm3asr_hip.so:
   two passes,   StreamingCtcDecoder(..., rescorer=...) keeps every stream's encoder memory on the device (m3_aed_memory_*) and
   streaming     rescore() runs the second pass over a stream's n-best when its utterance ends; StreamPool(rescore=True).
 
+  token times   when each token of a hypothesis was spoken (m3_ctc_align_*, m3asr.align): CtcDecoder.align for the hypotheses of
+                any mode above, StreamingCtcDecoder(..., aligner=CtcAligner(...)).align() on the logits the decoder kept per
+                stream; StreamPool(timestamps=True).
+
 Chunked decoding (decoding_chunk_size > 0) is accepted when the engine was built for exactly that chunk mask
 (cfg.static_chunk_size == decoding_chunk_size, same num_decoding_left_chunks): its ordinary forward is then the reference's
 chunk-masked forward (encoder.py:100-140).
@@ -405,6 +409,24 @@ class CtcDecoder:
         ctc = res["out_nosm"][:, :frames] if float(ctc_weight) > 0 else None
         return kept[1].search(memory, res["out_lens"].cpu(), raw_memory=True, detail=detail, max_steps=steps, ctc_logits=ctc)
 
+    def align(self, xs: torch.Tensor, xs_lens: torch.Tensor, tokens, frame_ms=40):
+        """Encoder forward, then the best CTC alignment of tokens[b] to utterance b's frames (m3asr.align): one
+        Alignment per utterance -- each token's start / end / peak frame and ms, its peak posterior, the alignment's score.  The
+        token lists may come from any decoding mode of this class."""
+        res = self.forward(xs, xs_lens)
+        return self.align_from_logits(res["out_nosm"], res["out_lens"], tokens, frame_ms)
+
+    def align_from_logits(self, logits: torch.Tensor, out_lens: torch.Tensor, tokens, frame_ms=40):
+        """logits (B,T',V) on the device (scores or raw: the aligner normalises each frame itself), out_lens (B,) frames per
+        utterance that count, tokens: one token list per utterance -> [Alignment] * B."""
+        from .align import CtcAligner
+        V = int(logits.shape[-1])
+        kept = getattr(self, "_aligner", None)        # the aligner's workspace is reused while it suffices
+        if kept is None or kept.V != V or kept.frame_ms != frame_ms or not _same_device(kept.device, logits.device):
+            kept = self._aligner = CtcAligner(V, self.blank_idx, logits.device, frame_ms)
+        return kept.align(logits, out_lens.cpu(), tokens)
+
+
 class StreamingCtcDecoder:
     """CTC decoding chunk by chunk on top of a StreamingEncoder: every step() runs the chunk forward, then log-softmax +
     top-k, the prefix beam search advance and the streaming greedy search, all on the engine's stream; partial() reads the
@@ -431,10 +453,15 @@ class StreamingCtcDecoder:
     residual stream (the binding's buffer "x", before after_norm) to the stream's rows of a device store, with the same frame
     counts the beam search consumes (one more launch on the engine's stream, no sync, the chunk's graph is unchanged), and
     rescore() runs the attention decoder over the listed streams' current n-best.  The memory of a stream is exactly the
-    frames its n-best was searched over."""
+    frames its n-best was searched over.
+
+    With aligner=CtcAligner(...) the decoder also keeps every stream's logits, in a second store of the same kind: each step()
+    copies the chunk's (B c, V) logits into a (B c, Vp) buffer (Vp = V rounded up to a multiple of 4, what the store's 16-byte
+    row copies need; the pad columns are never read) and appends it with the same frame counts, and align() gives the token
+    times of a stream's hypothesis on exactly the frames it was searched over."""
 
     def __init__(self, streaming_encoder, beam, blank=0, context=None, lm=None, lm_weight=0.5, length_bonus=0.0, lm_eos=True,
-                 endpoint=None, rescorer=None, ctc_weight=0.5, reverse_weight=0.0):
+                 endpoint=None, rescorer=None, ctc_weight=0.5, reverse_weight=0.0, aligner=None):
         """context: a m3asr.context.ContextSet on the engine's device (hotword biasing of the beam search; the greedy
         search is not biased); reset(graph_ids=) chooses each stream's graph, -1 = unbiased.
         lm: a m3asr.lm.NgramLm on the engine's device (shallow fusion in the beam search, as CtcBeamSearch(lm=); the walk
@@ -443,8 +470,18 @@ class StreamingCtcDecoder:
         endpoint: an EndpointConfig; None = no endpoint detection (nothing is allocated for it, endpoints() raises).
         rescorer: a m3asr.rescore.AttentionRescorer on the engine's device for rescore(); ctc_weight / reverse_weight: the
         weights of the first pass and of the right-to-left decoder in its final score.  None = no second pass (nothing is
-        allocated for it, step() launches nothing for it, rescore() raises)."""
+        allocated for it, step() launches nothing for it, rescore() raises).
+        aligner: a m3asr.align.CtcAligner for the engine's vocabulary, blank and device, for align().  None = no token times
+        (nothing is allocated for them, step() launches nothing for them, align() raises)."""
         self.st = streaming_encoder
+        self.aligner = aligner
+        if aligner is not None:           # refuse before anything is allocated or launched
+            ecfg = streaming_encoder.eng.cfg
+            if aligner.V != ecfg.output_dim or aligner.blank != int(blank):
+                raise _lib.M3Error("StreamingCtcDecoder: the aligner was built for V = %d / blank %d, the decoder has V = %d / blank %d"
+                                   % (aligner.V, aligner.blank, ecfg.output_dim, int(blank)))
+            if not _same_device(aligner.device, streaming_encoder.eng.device):
+                raise _lib.M3Error("StreamingCtcDecoder: the aligner is on %s, the engine on %s" % (aligner.device, streaming_encoder.eng.device))
         self.rescorer, self.ctc_weight, self.reverse_weight = rescorer, float(ctc_weight), float(reverse_weight)
         if rescorer is not None:          # refuse before anything is allocated or launched
             ecfg = streaming_encoder.eng.cfg
@@ -476,11 +513,16 @@ class StreamingCtcDecoder:
             self.mdesc = ops.aed_memory_desc(B, max_frames, e.cfg.attention_dim)
             self.mstate = torch.empty(max(ops.aed_memory_state_size(self.mdesc), 1), dtype=torch.uint8, device=e.device)
             self.mx = None                # the chunk binding's "x" as (B * c, D) rows, looked up after the first chunk
+        if aligner is not None:
+            vp = -(-aligner.V // 4) * 4
+            self.ldesc = ops.aed_memory_desc(B, max_frames, vp)
+            self.lstate = torch.empty(max(ops.aed_memory_state_size(self.ldesc), 1), dtype=torch.uint8, device=e.device)
+            self.lrows = torch.zeros(B * self.c, vp, dtype=torch.float32, device=e.device)      # the chunk's logits, padded to Vp
         self.reset()
 
     def reset(self, slots=None, graph_ids=None, lm_on=None):
         """Restart all streams, or (slot-mode encoder) the listed slots: encoder state, beam search, greedy search,
-        endpoint state and (decoder with a rescorer) the encoder memory.
+        endpoint state, (decoder with a rescorer) the encoder memory and (decoder with an aligner) the kept logits.
         graph_ids (decoder with a context): the graph each restarted stream takes, one per slot; a stream restarted without
         one keeps the graph it had.  lm_on (decoder with an LM): whether each restarted stream runs with the LM."""
         kw = {} if lm_on is None else {"lm_on": lm_on}
@@ -497,6 +539,8 @@ class StreamingCtcDecoder:
                     ops.ctc_endpoint_reset(self.edesc, self.estate)
                 if self.rescorer is not None:
                     ops.aed_memory_reset(self.mdesc, self.mstate)
+                if self.aligner is not None:
+                    ops.aed_memory_reset(self.ldesc, self.lstate)
             elif len(slots) > 0:
                 lst = torch.tensor([int(b) for b in slots], dtype=torch.int32).to(e.device)
                 if self.context is None and self.lm is None:
@@ -508,6 +552,8 @@ class StreamingCtcDecoder:
                     ops.ctc_endpoint_reset(self.edesc, self.estate, lst)
                 if self.rescorer is not None:
                     ops.aed_memory_reset(self.mdesc, self.mstate, lst)
+                if self.aligner is not None:
+                    ops.aed_memory_reset(self.ldesc, self.lstate, lst)
 
     def frames_of(self, valid):
         """Output frames of this chunk that count, from the real feature frames in its window."""
@@ -532,7 +578,45 @@ class StreamingCtcDecoder:
                 if self.mx is None:
                     self.mx = self.st.buffer("x").view(-1, self.mdesc.D)
                 ops.aed_memory_append(self.mdesc, self.mstate, self.mx, self.n_out)
+            if self.aligner is not None:
+                self.lrows[:, :self.aligner.V].copy_(logits.reshape(-1, self.aligner.V))
+                ops.aed_memory_append(self.ldesc, self.lstate, self.lrows, self.n_out)
         return logits
+
+    def align(self, slots=None, tokens=None):
+        """Token times of the streams' hypotheses on the frames they were searched over (slots: only the listed streams, in
+        that order; tokens: one token list per listed stream, default each stream's current best beam hypothesis): one
+        m3asr.align.Alignment per stream, None for a stream that ran past max_frames.  The kept logits are gathered (one
+        launch) and aligned (two).  The streams go on as they were.  Waits for the engine's stream."""
+        if self.aligner is None:
+            raise _lib.M3Error("StreamingCtcDecoder.align: the decoder was built without an aligner "
+                               "(StreamingCtcDecoder(..., aligner=CtcAligner(...)))")
+        e = self.st.eng
+        which = list(range(self.ldesc.B)) if slots is None else [int(b) for b in slots]
+        if any(not 0 <= b < self.ldesc.B for b in which):
+            raise ValueError("StreamingCtcDecoder.align: slots %s outside [0, %d)" % (which, self.ldesc.B))
+        if tokens is not None and len(tokens) != len(which):
+            raise ValueError("StreamingCtcDecoder.align: %d streams, %d token lists" % (len(which), len(tokens)))
+        if not which:
+            return []
+        with torch.cuda.stream(e.stream):
+            held = ops.aed_memory_lengths(self.ldesc, self.lstate).cpu().tolist()
+            lst = torch.tensor(which, dtype=torch.int32).to(e.device)
+            rows, row0 = ops.aed_memory_gather(self.ldesc, self.lstate, lst)
+            row0 = row0.cpu().tolist()
+            good = [j for j, b in enumerate(which) if held[b] >= 0]
+            if tokens is None:
+                best = self.beam.nbest(e.stream, slots=[which[j] for j in good])
+                tokens = [None] * len(which)
+                for j, hyps in zip(good, best):
+                    tokens[j] = list(hyps[0][0]) if hyps else []
+            out = [None] * len(which)
+            if good:
+                res = self.aligner.align_rows(rows[:, :self.aligner.V], [row0[j] for j in good], [row0[j + 1] - row0[j] for j in good],
+                                              [tokens[j] for j in good])
+                for j, a in zip(good, res):
+                    out[j] = a
+        return out
 
     def memory_lengths(self):
         """Decoder with a rescorer: encoder-memory frames every stream holds, (B,) int32 on the host; -1 for a stream that

@@ -949,6 +949,50 @@ def aed_memory_gather(desc, state, slots, out=None):
     return out, row0
 
 
+# ---- CTC forced alignment (m3_ctc_align_*; m3asr.align.CtcAligner drives these)
+def ctc_align_desc(n, V, blank, max_frames, max_tokens):
+    """m3_ctc_align_desc for n packed utterances of at most max_frames frames and max_tokens tokens.  Raises M3Error on a
+    descriptor the library refuses (blank outside [0, V), more than 4000 tokens, sizes that overflow the int32 arithmetic)."""
+    d = _lib.CtcAlignDesc(int(n), int(V), int(blank), int(max_frames), int(max_tokens))
+    if _lib.load().m3_ctc_align_workspace_size(C.byref(d)) == 0:
+        raise _lib.M3Error("m3_ctc_align_workspace_size failed: " + _lib.last_error())
+    return d
+
+
+def ctc_align_workspace_size(desc):
+    """bytes of the move table for desc (host-only call); 0 for a descriptor the library refuses."""
+    return _lib.load().m3_ctc_align_workspace_size(C.byref(desc))
+
+
+def ctc_align_emit(desc, rows, row0, n_frames, tokens, tok0, emit=None):
+    """rows (R, V) f32 logits (a row-strided view is fine), row0 / n_frames (n,), tokens (sum L,), tok0 (n + 1,) int32 on the
+    device -> emit (n, max_frames, max_tokens + 1) f32: the log-probabilities of the blank and of each utterance's tokens
+    (rows t < n_frames and columns <= L are written)."""
+    xp, ldl = _rows(rows)
+    assert rows.shape[1] == desc.V and row0.numel() == n_frames.numel() == desc.n and tok0.numel() == desc.n + 1
+    if emit is None:
+        emit = torch.empty(desc.n, desc.max_frames, desc.max_tokens + 1, dtype=torch.float32, device=rows.device)
+    check(_lib.load().m3_ctc_align_emit(C.byref(desc), xp, ldl, _i32(row0), _i32(n_frames), _i32(tokens), _i32(tok0), _f32(emit),
+                                        _stream()), "m3_ctc_align_emit")
+    return emit
+
+
+def ctc_align_path(desc, emit, n_frames, tokens, tok0, workspace, out=None):
+    """The trellis, the backtrace and the spans on `emit` -> (score (n,) f32, status (n,), state (n, max_frames), tok_start,
+    tok_end, tok_peak (sum L,) int32, tok_logp (sum L,) f32) on the device.  out: that tuple, to be filled."""
+    dev = emit.device
+    if out is None:
+        nt = tokens.numel()
+        out = (torch.empty(desc.n, dtype=torch.float32, device=dev), torch.empty(desc.n, dtype=torch.int32, device=dev),
+               torch.empty(desc.n, desc.max_frames, dtype=torch.int32, device=dev)) + \
+            tuple(torch.empty(nt, dtype=torch.int32, device=dev) for _ in range(3)) + (torch.empty(nt, dtype=torch.float32, device=dev),)
+    score, status, state, ts, te, tp, tl = out
+    check(_lib.load().m3_ctc_align_path(C.byref(desc), _f32(emit), _i32(n_frames), _i32(tokens), _i32(tok0), _p(workspace),
+                                        workspace.numel() * workspace.element_size(), _f32(score), _i32(status), _i32(state),
+                                        _i32(ts), _i32(te), _i32(tp), _f32(tl), _stream()), "m3_ctc_align_path")
+    return out
+
+
 # ---- attention decoding: the AED decoder's own beam search (m3_aed_search_*; m3asr.aed_search drives these around the GEMMs)
 def aed_search_desc(B, beam, max_steps, V, D, H, layers, pe_rows):
     """m3_aed_search_desc.  Raises M3Error on a descriptor the library rejects (beam outside [1, min(64, V)], a head size that

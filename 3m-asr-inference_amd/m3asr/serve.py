@@ -28,6 +28,11 @@ Two passes, `StreamPool(decoder, segment=True, rescore=True)` over a decoder wit
 rescores the n-best of all of them over the encoder memory the decoder kept per slot, and each is filed as a
 `RescoredSegment`; `pool.close(sid, rescored=True)` does the same for the open segment.
 
+Token times, `StreamPool(decoder, segment=True, timestamps=True)` over a decoder with an aligner
+(StreamingCtcDecoder(..., endpoint=..., aligner=CtcAligner(...))): before a finished utterance's slot is restarted its final
+best hypothesis is aligned to the logits the decoder kept for it, and the segment is filed as a `TimedSegment` whose `times`
+are in session time; `pool.close(sid, timed=True)` does the same for the open segment.
+
 The window rule is the one StreamingEncoder.decode applies to whole utterances (window n of a stream starts at its input
 frame 4 c n, holds 4 c + 3 frames, overlaps the next by 3; fewer than 7 real frames count as none).  It lives in
 `next_window_valid` / `WindowBuffer`, host-only code.
@@ -46,6 +51,12 @@ Segment = collections.namedtuple("Segment", "rule start_ms end_ms nbest end_fram
 # scores: [(tokens, prior, att, final)] in n-best order (AttentionRescorer.rescore's pair).  Its memory is exactly the frames
 # the n-best was searched over: the frames of the firing chunk behind the endpoint included.
 RescoredSegment = collections.namedtuple("RescoredSegment", "rule start_ms end_ms nbest end_frame best scores")
+
+# The same of a pool with timestamps=True: the seven fields of RescoredSegment (best / scores are None in a pool that does not
+# rescore), then times: [(token, start_ms, end_ms, conf)] of the segment's final best hypothesis -- `best` with rescore=True,
+# else the first n-best entry -- in SESSION time, (the segment's offset in frames + frame) * frame_ms; conf: the token's largest
+# posterior inside its span; None when CTC cannot align the hypothesis (m3asr.align).
+TimedSegment = collections.namedtuple("TimedSegment", "rule start_ms end_ms nbest end_frame best scores times")
 
 
 def next_window_valid(buffered, chunks_done, chunk, ended):
@@ -142,12 +153,23 @@ class StreamPool:
 
     rescore=True: two-pass decoding.  The decoder needs a rescorer (`decoder.rescorer`, `decoder.rescore(slots=[...],
     detail=True)`).  With segment=True all slots whose rule fired in a step are rescored by ONE decoder.rescore call before
-    they are restarted, and segments(sid) hands out RescoredSegments; close(sid, rescored=True) rescores the open segment."""
+    they are restarted, and segments(sid) hands out RescoredSegments; close(sid, rescored=True) rescores the open segment.
+
+    timestamps=True: token times.  The decoder needs an aligner (`decoder.aligner`, `decoder.align(slots=[...],
+    tokens=[...])`) and the pool must segment (the times are session times, frame_ms is the endpoint config's).  All slots whose
+    rule fired in a step are aligned by ONE decoder.align call before they are restarted, and segments(sid) hands out
+    TimedSegments; close(sid, timed=True) aligns the open segment."""
 
     def __init__(self, decoder, B=None, chunk=None, input_dim=None, audio=False, fbank=None, segment=False, max_frames=None,
-                 rescore=False):
+                 rescore=False, timestamps=False):
         self.dec = decoder
         self.rescore = bool(rescore)
+        self.timestamps = bool(timestamps)
+        if self.timestamps and (getattr(decoder, "aligner", None) is None or not hasattr(decoder, "align")):
+            raise _lib.M3Error("StreamPool(timestamps=True) needs a decoder with an aligner: "
+                               "StreamingCtcDecoder(..., aligner=CtcAligner(...))")
+        if self.timestamps and not segment:
+            raise _lib.M3Error("StreamPool(timestamps=True) needs segment=True: token times are session times")
         if self.rescore and (getattr(decoder, "rescorer", None) is None or not hasattr(decoder, "rescore")):
             raise _lib.M3Error("StreamPool(rescore=True) needs a decoder with a rescorer: "
                                "StreamingCtcDecoder(..., rescorer=AttentionRescorer(...))")
@@ -282,8 +304,12 @@ class StreamPool:
             return
         # two passes: one decoder pass over everything that ended in this step, before any of the slots is restarted
         second = self.dec.rescore(slots=[b for _, b, _ in fired], detail=True) if self.rescore else None
+        times = None
+        if self.timestamps:               # one alignment pass over everything that ended in this step, likewise
+            nbests = [self.dec.finish(slots=[b])[0] for _, b, _ in fired]
+            times = self._times(fired, nbests, second)
         for j, (sid, b, info) in enumerate(fired):
-            nbest = self.dec.finish(slots=[b])[0]
+            nbest = nbests[j] if times is not None else self.dec.finish(slots=[b])[0]
             buf, off = self.streams[sid][1], self.offset[sid]
             if nbest and len(nbest[0][0]) > 0:
                 first = info.first_speech if info.first_speech >= 0 else 0
@@ -291,10 +317,22 @@ class StreamPool:
                 seg = Segment(info.rule, (off + first) * self.frame_ms, (off + last + 1) * self.frame_ms, nbest, off + info.frame)
                 if second is not None:
                     seg = RescoredSegment(*seg, tuple(second[j][0]), second[j][1])
+                if times is not None:
+                    seg = TimedSegment(*(tuple(seg) + (None, None))[:7], times[j])
                 self.finished[sid].append(seg)
             self.offset[sid] = off + buf.chunks * self.c
             self.dec.reset(slots=[b])
             buf.rebase()
+
+    def _times(self, fired, nbests, second):
+        """timestamps=True: ONE decoder.align call over the slots of `fired` [(sid, slot, ...)], each on its final best
+        hypothesis (the second pass's choice when there was one, else the first n-best entry) -> per entry
+        [(token, start_ms, end_ms, conf)] in session time, or None where there is no alignment."""
+        from .align import token_times
+        tokens = [list(second[j][0]) if second is not None else (list(nbest[0][0]) if nbest else [])
+                  for j, nbest in enumerate(nbests)]
+        got = self.dec.align(slots=[f[1] for f in fired], tokens=tokens)
+        return [token_times(a, self.frame_ms, self.offset[f[0]]) for f, a in zip(fired, got)]
 
     def segments(self, sid):
         """The session's finished segments since the last call, oldest first (segment=True); the list is cleared."""
@@ -349,12 +387,16 @@ class StreamPool:
         best, greedy = self.dec.partial(slots=[b])
         return best[0], greedy[0]
 
-    def close(self, sid, rescored=False):
+    def close(self, sid, rescored=False, timed=False):
         """n-best [(prefix, score)] of what the stream has decoded (segment=True: of its open segment; read segments(sid)
         first, the finished ones go with the session); the slot is free again.
         rescored=True (rescore=True): instead the second pass's pair for it, (best tokens, [(tokens, prior, att, final)]);
-        ((), []) when nothing was decoded."""
+        ((), []) when nothing was decoded.
+        timed=True (timestamps=True): (that result, times) -- times as in TimedSegment, of the second pass's choice with
+        rescored=True and of the first n-best entry otherwise."""
         b = self.slot_of(sid)
+        if timed and not self.timestamps:
+            raise _lib.M3Error("StreamPool.close(timed=True): this pool keeps no token times, build it with timestamps=True")
         if rescored:
             if not self.rescore:
                 raise _lib.M3Error("StreamPool.close(rescored=True): this pool does not rescore, build it with rescore=True")
@@ -362,6 +404,9 @@ class StreamPool:
             nbest = (tuple(best), scores)
         else:
             nbest = self.dec.finish(slots=[b])[0]
+        if timed:
+            fired = [(sid, b)]
+            nbest = (nbest, self._times(fired, [[] if rescored else nbest], [nbest] if rescored else None)[0])
         del self.streams[sid]
         if self.segment:
             del self.offset[sid], self.finished[sid]

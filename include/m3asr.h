@@ -580,6 +580,53 @@ int m3_ctc_endpoint_advance(const m3_ctc_endpoint_desc* desc, void* state, size_
                             const int32_t* top_idx, int T_chunk, int k, const int32_t* n_frames, m3_stream stream);
 int m3_ctc_endpoint_read(const m3_ctc_endpoint_desc* desc, const void* state, size_t state_bytes, int32_t* info,
                          m3_stream stream);
+/* CTC forced alignment (csrc/ctc_align.hip): WHEN each token of a given hypothesis was spoken.  For every one of n
+ * utterances, given its frames' logits and ANY token sequence (however it was found: CTC search, rescoring, attention
+ * decoding), the best CTC alignment -- Viterbi over the blank-interleaved trellis -- and from it each token's first frame, end
+ * frame, peak frame and peak log-posterior.  Additions only (the ABI version stays 10); replaces nothing in the reference,
+ * which has no aligner.
+ * Utterances are packed and ragged: utterance u has T = n_frames[u] frames, its logits are the rows row0[u] .. row0[u] + T of
+ * `logits` (a padded (B, T, V) batch is row0[u] = u * T), its tokens y[0 .. L) = tokens[tok0[u] .. tok0[u + 1]) (tok0 [n + 1] =
+ * prefix sums of the token counts).  row0, n_frames, tokens, tok0 are device int32.
+ * THE CONTRACT (restated in tests/ctc_align_ref.py), e[t][v] = log_softmax(logits row t)[v], S = 2 L + 1 states, lab(s) = blank
+ * for even s and y[s >> 1] for odd s:
+ *   a[0][0] = e[0][blank], a[0][1] = e[0][y[0]], every other state -inf;  a[t][s] = best + e[t][lab(s)], best over
+ *   stay a[t-1][s] | step a[t-1][s-1] (s >= 1) | skip a[t-1][s-2] (s odd, s >= 3, lab(s) != lab(s-2)); a later move replaces an
+ *   earlier one only when STRICTLY greater (ties: stay over step over skip, -inf against -inf included); one float32 add on a
+ *   float32 maximum per (t, s).  The path ends in state S - 1, or in S - 2 when S > 1 and a[T-1][S-2] > a[T-1][S-1] (strictly),
+ *   and state[t] follows the recorded moves back.  Token i: start = first frame with state 2 i + 1, end = last such frame + 1,
+ *   peak = the frame of [start, end) with the largest e[t][y[i]] (the earliest on ties), peak_logp = that value.
+ *   score = a[T-1][final state].  T = 0 with L = 0 is an alignment of score 0.
+ * status [n]: 0 ok;  1 no alignment exists (T < L + the number of i with y[i] == y[i-1], T = 0 < L, or a best score of -inf);
+ *   2 bad input (a token that is `blank` or outside [0, V), n_frames[u] outside [0, max_frames], more than max_tokens tokens).
+ *   For status 1 and 2 the utterance's score is -inf, its state row and its tok_start / tok_end / tok_peak are -1 and its tok_logp
+ *   is -inf; nothing outside the utterance's own outputs is written.  Every loop is bounded by T and S, never by a value read
+ *   from the logits: a NaN gives an unspecified path, no access out of bounds and no hang.
+ * m3_ctc_align_workspace_size: host-only; bytes of the move table (one byte per frame and state).  0 (and m3_last_error) for a
+ *   descriptor the library refuses: a negative field, blank outside [0, V), n or max_frames above 2^20, max_tokens above 4000
+ *   (two score vectors of S floats live in 64 KB of LDS), sizes that overflow the int32 index arithmetic.  Never 0 otherwise.
+ * m3_ctc_align_emit: the only stage that rounds.  One wave per (utterance, frame): fp32 logsumexp over V (maximum subtracted),
+ *   then emit[u][t][0] = x[blank] - lse and emit[u][t][1 + i] = x[y[i]] - lse; emit is [n][max_frames][max_tokens + 1] fp32,
+ *   dense, and only rows t < T and columns <= L are written (nothing for an utterance whose sizes are bad; -inf for a token
+ *   outside [0, V)).  ldl >= V, any value, logits 4-byte aligned (16-byte loads are used where a row's address allows);
+ *   logits may hold -inf, a row must hold one finite value.
+ * m3_ctc_align_path: exact arithmetic on `emit`.  One work-group per utterance, serial in t, parallel in s.  workspace: at
+ *   least m3_ctc_align_workspace_size bytes.  score [n] f32, status [n], state [n][max_frames] (entries at and past T are -1),
+ *   tok_start / tok_end / tok_peak (int32) and tok_logp (f32) [tok0[n]], indexed like `tokens`.
+ * Both calls are enqueued on `stream` and neither synchronises; emit then path on one stream is the whole operation. */
+typedef struct m3_ctc_align_desc {
+  int32_t n;
+  int32_t V;
+  int32_t blank;
+  int32_t max_frames;
+  int32_t max_tokens;
+} m3_ctc_align_desc;
+size_t m3_ctc_align_workspace_size(const m3_ctc_align_desc* desc);
+int m3_ctc_align_emit(const m3_ctc_align_desc* desc, const float* logits, int ldl, const int32_t* row0, const int32_t* n_frames,
+                      const int32_t* tokens, const int32_t* tok0, float* emit, m3_stream stream);
+int m3_ctc_align_path(const m3_ctc_align_desc* desc, const float* emit, const int32_t* n_frames, const int32_t* tokens,
+                      const int32_t* tok0, void* workspace, size_t ws_bytes, float* score, int32_t* status, int32_t* state,
+                      int32_t* tok_start, int32_t* tok_end, int32_t* tok_peak, float* tok_logp, m3_stream stream);
 
 /* Streaming operators of the reference's plugin library (built there but not registered, trt_plugin_plus.cpp:155-156).
  * CatSplitCachePluginDynamic (cat_split_cache_kernel.cu:30-107), 4-byte elements: output [B][cache_dim+input_dim] =

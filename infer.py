@@ -34,7 +34,14 @@ states (m3asr.aed_search); --max-steps bounds the tokens per hypothesis (default
 best hypothesis of each utterance.  With --ctc-weight W > 0 the search is the one-pass joint CTC/attention search: every candidate
 is also scored by its CTC prefix probability on the forward's own CTC output and ranked by (1 - W) att + W ctc; --pre-beam P
 candidates per hypothesis go to the CTC scorer.  Both parts are printed.  With --lm the n-gram LM is fused into this search
-(not into a prefix beam search): the rank gains lm_weight log P_LM + length_bonus per token, and the LM part is printed too."""
+(not into a prefix beam search): the rank gains lm_weight log P_LM + length_bonus per token, and the LM part is printed too.
+
+    python3 infer.py -p encoder.plan -i feat.npy --timestamps [any of the modes above]
+
+Token times (m3asr.align): after a mode has chosen its best hypothesis -- without a mode, the CTC greedy search's -- the
+hypothesis is aligned to the forward's CTC output and one line per token follows an `utt <b> <mode> times:` line,
+`<token> <start ms> <end ms> <conf>`, conf being the token's largest posterior inside its span; `no alignment` for a
+hypothesis that CTC cannot align.  Without the flag nothing is added to the output."""
 import argparse
 import os
 import sys
@@ -58,6 +65,33 @@ def read_wav(path):
         return np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").astype(np.int16).reshape(1, -1)
 
 
+def print_times(scores, device, mode, hyps):
+    """--timestamps: `utt <b> <mode> times:` and one `token start_ms end_ms conf` line per token of hyps[b], aligned to the
+    forward's CTC output (all T' frames, blank = 0)."""
+    import torch
+    from m3asr.align import CtcAligner
+    x = torch.from_numpy(np.ascontiguousarray(scores, dtype=np.float32)).to(device)
+    x = x.reshape(-1, x.shape[-2], x.shape[-1])
+    B, T, V = x.shape
+    for b, a in enumerate(CtcAligner(V, device=device).align(x, [T] * B, hyps)):
+        print("utt %d %s times:" % (b, mode))
+        if not a.ok:
+            print("no alignment")
+        for tok, s, e, c in zip(a.tokens, a.start_ms, a.end_ms, a.conf):
+            print("%d %d %d %.4f" % (tok, s, e, c))
+
+
+def greedy_hyps(scores, device):
+    """the CTC greedy hypothesis of every utterance (blank = 0, all T' frames)"""
+    import torch
+    from m3asr import ops
+    x = torch.from_numpy(np.ascontiguousarray(scores, dtype=np.float32)).to(device)
+    x = x.reshape(-1, x.shape[-2], x.shape[-1])
+    _, tokens, n_tokens = ops.ctc_greedy(x, None, 0)
+    tokens = tokens.cpu()
+    return [tokens[b, :n].tolist() for b, n in enumerate(n_tokens.cpu().tolist())]
+
+
 def print_hotword_search(scores, device, args):
     """Best prefix beam hypothesis of every utterance without and with the hotword list (blank = 0, all T' frames)."""
     import torch
@@ -73,9 +107,11 @@ def print_hotword_search(scores, device, args):
     biased = CtcBeamSearch(B, args.beam, T, device=device, context=ctx)
     biased.reset(graph_ids=[0] * B)
     biased.advance(x, lens)
-    for b, (u, h) in enumerate(zip(plain.nbest(), biased.nbest(detail=True))):
+    chosen = biased.nbest(detail=True)
+    for b, (u, h) in enumerate(zip(plain.nbest(), chosen)):
         print("utt %d plain:  score=%.4f tokens=%s" % (b, u[0][1], " ".join(str(t) for t in u[0][0])))
         print("utt %d biased: score=%.4f bonus=%.4f tokens=%s" % (b, h[0][1], h[0][2], " ".join(str(t) for t in h[0][0])))
+    return [list(h[0][0]) for h in chosen]
 
 
 def load_lm(args, V, device):
@@ -105,10 +141,12 @@ def print_lm_search(scores, device, args):
     if ctx is not None:
         fused.reset(graph_ids=[0] * B)
     fused.advance(x, lens)
-    for b, (u, h) in enumerate(zip(plain.nbest(), fused.nbest(detail=True))):
+    chosen = fused.nbest(detail=True)
+    for b, (u, h) in enumerate(zip(plain.nbest(), chosen)):
         print("utt %d plain: score=%.4f tokens=%s" % (b, u[0][1], " ".join(str(t) for t in u[0][0])))
         print("utt %d fused: score=%.4f bonus=%.4f lm=%.4f tokens=%s" % (b, h[0][1], h[0][2], h[0][3],
                                                                          " ".join(str(t) for t in h[0][0])))
+    return [list(h[0][0]) for h in chosen]
 
 
 def print_rescore(helper, feat, feat_len, args):
@@ -128,6 +166,7 @@ def print_rescore(helper, feat, feat_len, args):
         chosen = next(h for h in hyps if h[0] == best)
         print("utt %d ctc:      prior=%.4f tokens=%s" % (b, hyps[0][1], " ".join(str(t) for t in hyps[0][0])))
         print("utt %d rescored: att=%.4f final=%.4f tokens=%s" % (b, chosen[2], chosen[3], " ".join(str(t) for t in best)))
+    return [list(best) for best, _ in out]
 
 
 def print_attention(helper, feat, feat_len, args):
@@ -148,6 +187,7 @@ def print_attention(helper, feat, feat_len, args):
         if lm is not None:
             parts += " lm=%.4f" % chosen[5]
         print("utt %d attention: score=%.4f%s finished=%d tokens=%s" % (b, chosen[1], parts, chosen[2], " ".join(str(t) for t in best)))
+    return [list(best) for best, _ in out]
 
 
 def main(args):
@@ -165,14 +205,18 @@ def main(args):
         print("outputs.shape:" + str(o.shape))
         print("outputs.sum:" + str(o.sum()))
         print(o)
+    chosen = []                                                   # (mode, best hypothesis per utterance) of every mode that ran
     if args.rescore:
-        print_rescore(helper, feat, feat_len, args)
+        chosen.append(("rescored", print_rescore(helper, feat, feat_len, args)))
     if args.attention:
-        print_attention(helper, feat, feat_len, args)
+        chosen.append(("attention", print_attention(helper, feat, feat_len, args)))
     if args.lm and not args.attention:                            # with --attention the LM goes into the attention search
-        print_lm_search(outputs[0], helper.engine.device, args)
+        chosen.append(("fused", print_lm_search(outputs[0], helper.engine.device, args)))
     elif args.hotwords:
-        print_hotword_search(outputs[0], helper.engine.device, args)
+        chosen.append(("biased", print_hotword_search(outputs[0], helper.engine.device, args)))
+    if args.timestamps:
+        for mode, hyps in chosen or [("greedy", greedy_hyps(outputs[0], helper.engine.device))]:
+            print_times(outputs[0], helper.engine.device, mode, hyps)
     if base is not None:
         print("compare_output=%s, dtype=%s, shape=%s" % (args.compare_output_file, base[0].dtype, base[0].shape))
         print("output.sum:" + str(base[0].sum()))
@@ -199,4 +243,5 @@ if __name__ == "__main__":
     p.add_argument("--attention", action="store_true", help="Attention decoding: the plan's AED decoder searching on its own.")
     p.add_argument("--max-steps", type=int, default=None, help="--attention: the most tokens per hypothesis.")
     p.add_argument("--pre-beam", type=int, default=None, help="--attention --ctc-weight W: candidates per hypothesis that the CTC scorer sees.")
+    p.add_argument("--timestamps", action="store_true", help="Token times: align the chosen hypothesis to the CTC output (start / end ms, confidence).")
     main(p.parse_args())

@@ -6,9 +6,16 @@ as soon as the step that ended it returns:
     python tools/transcribe_stream.py -p encoder.plan -w speech.wav [--hotwords words.txt] [--lm lm.arpa] [--beam 10]
                                       [--blank-threshold 0.8] [--rule must_decoded,trailing_ms,length_ms ...]
                                       [--rescore [--ctc-weight 0.5] [--reverse-weight 0.0]]
+                                      [--timestamps]
 
     <start ms>-<end ms> rule <r>: <token ids of the best hypothesis>
     <start ms>-<end ms> rule <r> rescored: att=<a> final=<f> tokens=<token ids the attention decoder chose>      (--rescore)
+
+    <token> <start ms> <end ms> <conf>      one line per token of the segment's final best hypothesis                    (--timestamps)
+
+--timestamps: token times in session time (StreamPool(timestamps=True)): the decoder keeps every session's logits
+on the device and aligns a segment's final best hypothesis -- the rescored one with --rescore -- when its utterance ends.
+`no alignment` where CTC cannot align it.
 
 --rescore: two-pass decoding.  The plan must come from a joint CTC/attention checkpoint (builder.py packs the decoder when the
 checkpoint has one); the decoder keeps every session's encoder memory on the device and the plan's attention decoder rescores
@@ -96,12 +103,15 @@ def main(a):
         from m3asr.lm import NgramLm
         lm = NgramLm.load(a.lm) if a.lm.endswith(".npy") else NgramLm.from_arpa(a.lm, a.units, vocab_size=V)
         kw.update(lm=lm.to(eng.device), lm_weight=a.lm_weight, length_bonus=a.length_bonus)
+    if a.timestamps:
+        from m3asr.align import CtcAligner
+        kw["aligner"] = CtcAligner(V, device=eng.device)
     rules = [tuple(int(v) for v in r.split(",")) for r in a.rule] if a.rule else EndpointConfig().rules
     ep = EndpointConfig(a.blank_threshold, rules)
     bound = ep.length_bound()
     max_frames = a.max_frames or (bound if bound is not None else 2000) + eng.cfg.static_chunk_size
     dec = StreamingCtcDecoder(eng.streaming(1, max_frames, independent=True), beam=a.beam, endpoint=ep, **kw)
-    pool = StreamPool(dec, audio=True, segment=True, rescore=rescorer is not None)
+    pool = StreamPool(dec, audio=True, segment=True, rescore=rescorer is not None, timestamps=a.timestamps)
     if a.synthetic:
         rng = np.random.default_rng(1)
         pcm = np.clip(np.cumsum(rng.normal(0, 1, int(16000 * a.synthetic))) * 50 % 20000 - 10000, -32768, 32767).astype(np.int16)
@@ -109,11 +119,19 @@ def main(a):
         pcm = read_wav(a.wav_file)
     sid = pool.open(context=0 if a.hotwords else None)
 
+    def show_times(times):
+        if times is None:
+            print("no alignment", flush=True)
+        for tok, t0, t1, conf in times or []:
+            print("%d %d %d %.4f" % (tok, t0, t1, conf), flush=True)
+
     def show():
         for s in pool.segments(sid):
             print("%d-%d ms rule %d: %s" % (s.start_ms, s.end_ms, s.rule, " ".join(str(t) for t in s.nbest[0][0])), flush=True)
             if rescorer is not None:
                 print("%d-%d ms rule %d rescored: %s" % (s.start_ms, s.end_ms, s.rule, rescored(s.best, s.scores)), flush=True)
+            if a.timestamps:
+                show_times(s.times)
 
     for pos in range(0, len(pcm), PIECE):
         pool.push_audio(sid, torch.from_numpy(pcm[pos:pos + PIECE].copy()))
@@ -123,13 +141,16 @@ def main(a):
     while pool.step():
         show()
     start = pool.offset_ms(sid)
+    rest = pool.close(sid, rescored=rescorer is not None, timed=a.timestamps)
+    rest, times = rest if a.timestamps else (rest, None)
     if rescorer is None:
-        rest = pool.close(sid)
         print("%d- ms rule 0: %s" % (start, " ".join(str(t) for t in rest[0][0]) if rest else ""))
     else:
-        best, scores = pool.close(sid, rescored=True)
+        best, scores = rest
         print("%d- ms rule 0: %s" % (start, " ".join(str(t) for t in scores[0][0]) if scores else ""))
         print("%d- ms rule 0 rescored: %s" % (start, rescored(best, scores)))
+    if a.timestamps:
+        show_times(times)
     print("%d engine steps, %.1f s of audio" % (pool.steps, len(pcm) / 16000.0))
 
 
@@ -152,6 +173,7 @@ if __name__ == "__main__":
     p.add_argument("--rescore", action="store_true", help="Two passes: the attention decoder rescores every segment's n-best.")
     p.add_argument("--ctc-weight", type=float, default=0.5, help="--rescore: weight of the first-pass score in the final score.")
     p.add_argument("--reverse-weight", type=float, default=0.0, help="--rescore: weight of the right-to-left decoder.")
+    p.add_argument("--timestamps", action="store_true", help="Token times of every segment's final best hypothesis, in session time.")
     args = p.parse_args()
     if args.wav_file and not args.plan_name:
         p.error("-w needs -p")
