@@ -972,7 +972,9 @@ int m3_aed_memory_gather(const m3_aed_memory_desc* desc, const void* state, size
  * m3_aed_search_prune: one work-group per utterance: per row logsumexp over V and the beam largest logits (lower token id on
  *   ties), a finished row offering the single candidate (increment 0, eos) instead; the beam largest of the beam^2 candidate
  *   scores (lower flat index slot * beam + rank on ties; a candidate of a -inf slot stays -inf); new tokens, scores, flags
- *   and ancestry go to the other record; the utterance's step moves and its done flag is set once every slot is finished or
+ *   and ancestry go to the other record;  a NaN is never picked, neither as a logit nor as a candidate score: a row holding a
+ *   NaN logit has a NaN logsumexp and so offers no candidate, a rank of a row without a logit left is (-inf, eos), and a new
+ *   slot without a candidate left is (-inf, eos) under parent 0; the utterance's step moves and its done flag is set once every slot is finished or
  *   the limit is reached.  A done utterance is left bit for bit alone.  logits [R][ldl]; done: NULL or device int32 [B] that
  *   receives every utterance's done flag (the one word the host polls).
  * m3_aed_search_result: hyp_tokens [B][beam][max_steps] (sos and trailing eos stripped, -1 behind), hyp_len, score, finished
