@@ -45,7 +45,10 @@ struct DwCausal {
 // [D, 2 D) (bias added, no GLU): every tap is value * sigmoid(gate) as it is loaded -- the operation, and the operands, the GEMM's
 // GLU epilogue has (gemm_epilogue.h), so the taps hold the same bits.  The GEMM in front then is the plain one-column-tile form:
 // twice the work-groups, 64 instead of 96 KB of operands through each CU.  All 2 K row loads still precede the first use.
-template <int KT, bool CAUSAL, bool SLOTS = false, bool GLU_IN = false>
+// GLU_IN = 2: the gate columns hold sigmoid(gate) already -- the GEMM's epilogue formed it once per element (GemmParams::sig_col0)
+// where this kernel would form it in each of the K work-groups whose taps touch the row.  Every tap is value * gate', the
+// multiply GLU_IN = 1 ends with, on the same operands: the same bits, and no exp / divide chain behind the last load.
+template <int KT, bool CAUSAL, bool SLOTS = false, int GLU_IN = 0>
 __device__ __forceinline__ void dwconv_ln_silu_body(const float* __restrict__ z, const float* __restrict__ w_kc,
                                                     const float* __restrict__ bias, const float* __restrict__ gamma,
                                                     const float* __restrict__ beta, float eps, int T, int D, int K,
@@ -123,7 +126,15 @@ __device__ __forceinline__ void dwconv_ln_silu_body(const float* __restrict__ z,
         if (GLU_IN) gg[kk] = ldg4(src + D + c);
         ww[kk] = ldg4(w_kc + (size_t)k * D + c);
       }
-      if (GLU_IN) {
+      if (GLU_IN == 2) {
+        // (as below: every tap is requested before the first is used -- one round trip for the 3 K loads, not one per few taps)
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int kk = 0; kk < KT; ++kk)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) zz[kk][j] = zz[kk][j] * gg[kk][j];
+      }
+      if (GLU_IN == 1) {
         // all 3 K loads are issued before the first sigmoid: the 60 exp + divide of a thread would otherwise be scheduled between
         // them and the taps would arrive in six or seven dependent round trips instead of one
         __builtin_amdgcn_sched_barrier(0);
@@ -181,7 +192,7 @@ __device__ __forceinline__ void dwconv_ln_silu_body(const float* __restrict__ z,
 }
 
 // (GLU_IN holds 2 K row fragments + K weight fragments per thread: 256 threads (D <= 1024) leave a wave the registers for them)
-template <int KT, bool CAUSAL, bool SLOTS = false, bool GLU_IN = false>
+template <int KT, bool CAUSAL, bool SLOTS = false, int GLU_IN = 0>
 __global__ __launch_bounds__(GLU_IN ? 256 : 1024) void dwconv_ln_silu_kernel(const float* __restrict__ z, const float* __restrict__ w_kc,
                                                               const float* __restrict__ bias,
                                                               const float* __restrict__ gamma,
@@ -197,7 +208,7 @@ struct DwKernArgs {
   const float *z, *w_kc, *bias, *gamma, *beta; float eps; int T, D, K; float* out; int out_bf16;
   const int32_t *pad_of, *row0, *row_len; int n_rows; DwCausal cs; int ldz;
 };
-template <int KT, bool CAUSAL, bool GLU_IN = false>
+template <int KT, bool CAUSAL, int GLU_IN = 0>
 __global__ __launch_bounds__(GLU_IN ? 256 : 1024) void dwconv_ln_silu_dual_kernel(const DwKernArgs a, const DwKernArgs b) {
   if ((int)blockIdx.x < a.n_rows)
     dwconv_ln_silu_body<KT, CAUSAL, false, GLU_IN>(a.z, a.w_kc, a.bias, a.gamma, a.beta, a.eps, a.T, a.D, a.K, a.out, a.out_bf16, a.pad_of, a.row0,
@@ -209,7 +220,8 @@ __global__ __launch_bounds__(GLU_IN ? 256 : 1024) void dwconv_ln_silu_dual_kerne
 
 static int launch_dwconv_impl(const float* z, const float* w_kc, const float* bias, const float* gamma, const float* beta, float eps,
                               int B, int T, int D, int K, float* out, hipStream_t stream, int out_bf16, const int32_t* pad_of,
-                              const int32_t* row0, const int32_t* row_len, const DwCausal& cs, bool slots = false, int glu_ldz = 0) {
+                              const int32_t* row0, const int32_t* row_len, const DwCausal& cs, bool slots = false, int glu_ldz = 0,
+                              int glu_sig = 0) {
   M3_REQUIRE(glu_ldz == 0 || dwconv_glu_in_supports(D, K, cs.causal != 0 || slots, out_bf16, glu_ldz),
              "dwconv (GLU on load): needs the symmetric fp32 conv, K <= 15, 256 <= channels <= 1024, ldz=%d a multiple of 4 and >= %d", glu_ldz, 2 * D);
   M3_REQUIRE(!slots || (cs.causal && cs.step != nullptr && cs.max_chunks > 0), "dwconv (slot mode): needs the streaming causal form");
@@ -226,8 +238,12 @@ static int launch_dwconv_impl(const float* z, const float* w_kc, const float* bi
 #define M3_DW_SLOTS(KT_)                                                                                                        \
   hipLaunchKernelGGL((dwconv_ln_silu_kernel<KT_, true, true>), dim3(grid), dim3(threads), 0, stream, z, w_kc, bias, gamma, beta, eps, \
                      T, D, K, out, out_bf16, pad_of, row0, row_len, rows, cs, 0)
-  if (glu_ldz)
-    hipLaunchKernelGGL((dwconv_ln_silu_kernel<15, false, false, true>), dim3(grid), dim3(threads), 0, stream, z, w_kc, bias, gamma, beta, eps, T,
+  M3_REQUIRE(!glu_sig || glu_ldz, "dwconv: sigmoided gate columns belong to the GLU-on-load form");
+  if (glu_ldz && glu_sig)
+    hipLaunchKernelGGL((dwconv_ln_silu_kernel<15, false, false, 2>), dim3(grid), dim3(threads), 0, stream, z, w_kc, bias, gamma, beta, eps, T,
+                       D, K, out, out_bf16, pad_of, row0, row_len, rows, cs, glu_ldz);
+  else if (glu_ldz)
+    hipLaunchKernelGGL((dwconv_ln_silu_kernel<15, false, false, 1>), dim3(grid), dim3(threads), 0, stream, z, w_kc, bias, gamma, beta, eps, T,
                        D, K, out, out_bf16, pad_of, row0, row_len, rows, cs, glu_ldz);
   else if (slots) { if (K <= 15) M3_DW_SLOTS(15); else M3_DW_SLOTS(8); }
   else if (K <= 15) { if (cs.causal) M3_DW_CASE(15, true); else M3_DW_CASE(15, false); }
@@ -254,14 +270,14 @@ int launch_dwconv_ln_silu_args(const DwArgs& a, hipStream_t stream) {
   if (a.glu_ldz) {
     M3_REQUIRE(a.causal_left_fill == nullptr, "dwconv (GLU on load): the symmetric conv only");
     return launch_dwconv_impl(a.z, a.w_kc, a.bias, a.gamma, a.beta, a.eps, a.B, a.T, a.D, a.K, a.out, stream, a.out_bf16, a.pad_of, a.row0, a.row_len,
-                              DwCausal{}, false, a.glu_ldz);
+                              DwCausal{}, false, a.glu_ldz, a.glu_sig);
   }
   return launch_dwconv_ln_silu(a.z, a.w_kc, a.bias, a.gamma, a.beta, a.eps, a.B, a.T, a.D, a.K, a.out, stream, a.out_bf16, a.pad_of, a.row0,
                                a.row_len, a.causal_left_fill);
 }
 // two independent conv modules of the same shape class (channels, taps, causal or not) in ONE launch
 bool dwconv_dual_fusable(const DwArgs& a, const DwArgs& b) {
-  if ((a.glu_ldz != 0) != (b.glu_ldz != 0)) return false;
+  if ((a.glu_ldz != 0) != (b.glu_ldz != 0) || (a.glu_sig != 0) != (b.glu_sig != 0)) return false;
   if (a.glu_ldz && !(dwconv_glu_in_supports(a.D, a.K, a.causal_left_fill != nullptr, a.out_bf16, a.glu_ldz) &&
                      dwconv_glu_in_supports(b.D, b.K, b.causal_left_fill != nullptr, b.out_bf16, b.glu_ldz)))
     return false;
@@ -282,7 +298,8 @@ int launch_dwconv_ln_silu_dual(const DwArgs& a, const DwArgs& b, hipStream_t str
   const int threads = (int)align_up(a.D / 4, 64), grid = ka.n_rows + kb.n_rows;
   const bool causal = a.causal_left_fill != nullptr;
 #define M3_DWD_CASE(KT_, C_) hipLaunchKernelGGL((dwconv_ln_silu_dual_kernel<KT_, C_>), dim3(grid), dim3(threads), 0, stream, ka, kb)
-  if (a.glu_ldz) hipLaunchKernelGGL((dwconv_ln_silu_dual_kernel<15, false, true>), dim3(grid), dim3(threads), 0, stream, ka, kb);
+  if (a.glu_ldz && a.glu_sig) hipLaunchKernelGGL((dwconv_ln_silu_dual_kernel<15, false, 2>), dim3(grid), dim3(threads), 0, stream, ka, kb);
+  else if (a.glu_ldz) hipLaunchKernelGGL((dwconv_ln_silu_dual_kernel<15, false, 1>), dim3(grid), dim3(threads), 0, stream, ka, kb);
   else if (a.K <= 15) { if (causal) M3_DWD_CASE(15, true); else M3_DWD_CASE(15, false); }
   else { if (causal) M3_DWD_CASE(8, true); else M3_DWD_CASE(8, false); }
 #undef M3_DWD_CASE

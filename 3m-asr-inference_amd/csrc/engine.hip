@@ -69,6 +69,8 @@ struct Stage {
   Conv1Args c1;
   DwArgs dw;
   AttArgs att;
+  // a router stage that starts from the accumulator prefix of "router_e_prefix": recomputes its layer's slice (m3_engine_run)
+  std::function<int(hipStream_t)> refresh_prefix;
 };
 
 m3_stage_info stage_info(const char* kernel, int launches, double bytes, double flops, bool per_row = true) {
@@ -126,6 +128,7 @@ struct m3_engine {
     // fork_embed: stages [fork_first, fork_mid) = the embed encoder (side branch of the captured graph), [fork_mid, join_at) =
     // what the main encoder does before it needs the embedding (embed_join); -1 = one linear chain
     int fork_first = -1, fork_mid = -1, join_at = -1;
+    int prefix_stage = -1;   // index of "router_e_prefix" (-1: the routers run their whole K)
     // fold_pos_proj: linear_pos(pe[:T']) of every block, computed once per T'.  ENGINE-owned device memory (shared by all
     // bindings of the same T', freed with the last of them): a caller that reuses one workspace for several shapes, as a
     // TensorRT execution context does, must not be able to overwrite it between two forwards of a revived binding
@@ -186,6 +189,13 @@ struct Switches {
   // (C >= 512) and the embed chain is interleaved with the main prefix (M3_HFUSE), conv1, conv2 + reduce and Linear + reduce of
   // the two run as one launch each
   bool front_pair;
+  // M3_ROUTER_PREFIX (1): 0 = every staged fp32 router GEMM walks its whole K.  1 (fp32, S <= 128 rows, De = D >= 256, the router
+  // planning as the one-group 16-row form): the embed half of all layers' router products is run once per forward by
+  // "router_e_prefix", as the accumulator registers the router GEMMs then start from (GemmParams::acc_init)
+  bool router_prefix;
+  // M3_GLU_SIG_EPI (1): 0 = a deferred GLU's gate columns leave pointwise_conv1 raw and the depthwise kernel sigmoids them per
+  // tap.  1: pointwise_conv1's epilogue stores sigmoid(gate) (GemmParams::sig_col0), the depthwise kernel multiplies
+  bool glu_sig_epi;
 };
 const Switches& switches() {
   static const Switches sw = [] {
@@ -200,6 +210,8 @@ const Switches& switches() {
     w.fused8_adapt = num("M3_FUSED8_ADAPT", 0) != 0;
     w.glu_defer = num("M3_GLU_DEFER", 1) != 0;
     w.front_pair = num("M3_FRONT_PAIR", 1) != 0;
+    w.router_prefix = num("M3_ROUTER_PREFIX", 1) != 0;
+    w.glu_sig_epi = num("M3_GLU_SIG_EPI", 1) != 0;
     return w;
   }();
   return sw;
@@ -335,6 +347,8 @@ struct Carver {
 struct Plan {
   int32_t* lens;
   float *c1, *c2, *x, *emb, *h1, *qkv, *pbuf, *ctx, *glu, *dw, *xn, *rl, *eall;
+  // the routers' accumulator prefix [num_blocks][rprefix_layer floats] (null: not taken), router_prefix_layer_floats
+  float* rprefix; size_t rprefix_layer;
   void* xb;                             // bf16 copy of the residual stream (16-bit modes, long batches)
   int32_t* moe_fs;                      // fp8 plans: the F split the fused expert kernel chose on the device (slab count for the combine)
   unsigned char* xq; float* xq_scale;   // fp8 plans: the MoE input rows as e4m3 [S][D] + per-row scales (router kernel -> fused fp8 expert kernel)
@@ -373,6 +387,8 @@ bool use_hfuse(const m3_engine_config& c, int B, int S) {
   return switches().hfuse && !c.debug_taps && c.weight_dtype == M3_F32 && c.embed_blocks > 0 && c.num_blocks > 0 && S <= 128 && c.fork_embed <= 0 &&
          !use_packed_rows(c, B);
 }
+
+size_t router_prefix_layer_floats(const m3_engine_config& c, int S, const Plan& pl);
 
 Plan make_plan(const m3_engine_config& c, void* base, int B, int T, int ep_capacity = 0) {
   Plan p;
@@ -472,6 +488,8 @@ Plan make_plan(const m3_engine_config& c, void* base, int B, int T, int ep_capac
       p.e_xbpad = cv.take<uint16_t>((size_t)S * D);
     }
   }
+  p.rprefix_layer = router_prefix_layer_floats(c, S, p);
+  p.rprefix = p.rprefix_layer ? cv.take<float>(p.rprefix_layer * (size_t)c.num_blocks) : nullptr;
   p.bytes = cv.off;
   return p;
 }
@@ -575,6 +593,32 @@ MoeRoute choose_moe_route(const m3_engine_config& c, int S, const BlockW& w, con
   r.fs_dev = sw.fused8_adapt && fused8 && pl.moe_fs != nullptr && !c.debug_taps;
   r.needs_e_all = r.norm_in_expert();
   return r;
+}
+
+// The staged router GEMM of a main block on cat([embed, x]): the operands every layer shares (add_moe_router adds the layer's)
+GemmParams router_concat_gemm(const m3_engine_config& c, int S, const float* emb, const float* x) {
+  const int world = c.ep_world_size > 0 ? c.ep_world_size : 1;
+  const int D = c.attention_dim, De = c.embed_dim, Etot = c.num_experts * world;
+  GemmParams g;
+  g.ldy = Etot; g.M = S; g.N = Etot;
+  g.mode = GEMM_A_CONCAT2; g.A = emb; g.lda = De; g.K1 = De; g.A2 = x; g.lda2 = D; g.K = De + D;
+  g.ln_on_a2 = 1; g.ld_ln_out = D;
+  return g;
+}
+// Floats per layer of the routers' accumulator prefix, 0 where it is not taken.  Taken (M3_ROUTER_PREFIX) by the staged fp32
+// router of short inputs: S <= 128 rows -- the 16-row-tile regime, where the router's few work-groups each pull both halves
+// through one CU; on long batches the prefix is as many bytes as the embed rows it saves -- and the GEMM planning as the form
+// that takes acc_init (De = D = 256 or 512 today).
+size_t router_prefix_layer_floats(const m3_engine_config& c, int S, const Plan& pl) {
+  if (!switches().router_prefix || c.weight_dtype != M3_F32 || c.embed_dim < 256 || S > 128 || c.num_blocks < 1 ||
+      c.num_blocks > kRouterPrefixMaxLayers)
+    return 0;
+  if (choose_moe_route(c, S, BlockW(), pl).router != RouterForm::Gemm) return 0;
+  static const float some = 0.f;   // (plan_gemm asks which operands exist, not where)
+  GemmParams g = router_concat_gemm(c, S, &some, &some);
+  g.W = &some; g.Y = const_cast<float*>(&some); g.ln_gamma = g.ln_beta = &some; g.acc_init = &some;
+  const GemmPlan plan = plan_gemm(g, 0);
+  return plan.launches == 1 ? router_prefix_floats(plan) : 0;
 }
 
 // What the stage list of one binding is built with.  The binding under construction is a local of build_binding: the engine
@@ -799,6 +843,7 @@ struct MoeLayer {
   const int32_t *lens, *live_len; int live_rpb;   // which rows are padding (padded or packed layout)
   const int32_t* pdev;                   // packed rows: the live-row count on the device (else null)
   const float* eall; int ld_eall;        // this layer's columns of router_e_all's output
+  int layer;                             // index among the main blocks
   void* xb_out; float* xstats_out;       // 16-bit modes: the combine also writes the bf16 copy of x / its row statistics
   void* ws; MoeWorkspace mw;             // the layer's MoE workspace, carved for the S local rows
 };
@@ -830,11 +875,27 @@ static void add_moe_router(StageBuilder& sb, const MoeLayer& m, const MoeRoute& 
       g.A = m.x; g.lda = D; g.W = w.router_x.w; g.bias = w.router_x.b; g.ln_wsum = w.router_x.wsum; g.ln_eps = m.eps; g.K = D;
       g.resid = m.eall; g.ldr = m.ld_eall;
     } else {   // LayerNorm(norm_ff) on the x half of cat([embed, x]) as the prologue, written out once as xn (the expert FFN's input)
-      g.mode = GEMM_A_CONCAT2; g.A = pl.emb; g.lda = De; g.K1 = De; g.A2 = m.x; g.lda2 = D; g.K = De + D;
+      g = router_concat_gemm(sb.eng.cfg, S, pl.emb, m.x);
+      g.Y = m.rl; g.m_dev = m.pdev;
       g.W = w.router.w; g.bias = w.router.b;
-      g.ln_gamma = w.n_ff.g; g.ln_beta = w.n_ff.b; g.ln_eps = m.eps; g.ln_on_a2 = 1; g.ln_out = m.xn; g.ld_ln_out = D;
+      g.ln_gamma = w.n_ff.g; g.ln_beta = w.n_ff.b; g.ln_eps = m.eps; g.ln_out = m.xn;
+      // the embed half was run by "router_e_prefix": the waves start from its accumulators and walk the x half only
+      if (pl.rprefix != nullptr) g.acc_init = pl.rprefix + (size_t)m.layer * pl.rprefix_layer;
     }
     add_gemm(sb, m.pfx + "moe_router", g, true);
+    if (g.acc_init != nullptr) {
+      Stage& st = sb.bd.stages.back();
+      // (what moved to the prefix stage: the embed rows, the embed columns of the weight, their FLOPs; what came: the prefix read)
+      st.info.alg_bytes += 4.0 * pl.rprefix_layer - 4.0 * De * (Etot + S);
+      st.info.flops -= 2.0 * S * Etot * De;
+      const GemmPlan plan = st.gemm_plan;
+      float* prefix = pl.rprefix; const int layer = m.layer;
+      st.refresh_prefix = [plan, g, prefix, layer](hipStream_t s) {
+        const float* wt[kRouterPrefixMaxLayers] = {};
+        wt[layer] = g.W;
+        return launch_router_embed_prefix(plan, g, wt, layer, 1, prefix, s);
+      };
+    }
   }
   sb.bd.stages.back().reads_embed = true;
 }
@@ -1078,6 +1139,10 @@ static void build_block(StageBuilder& sb, const std::string& pfx, const BlockW& 
       const GemmPlan rp = plan_gemm(r, 0);
       if (rp.launches == 1 && rp.kernel == GemmKernel::SkinnyF32 && rp.mt == 1) { g = r; glu_deferred = true; }
     }
+    // ... and the gate's sigmoid taken where each gate element exists once, in pw1's epilogue (M3_GLU_SIG_EPI): the depthwise
+    // kernel's taps are then one multiply each
+    const bool glu_sig = glu_deferred && switches().glu_sig_epi && (D & 15) == 0;
+    if (glu_sig) g.sig_col0 = D;
     add_gemm(sb, pfx + "conv.pw1_glu", g);
     const float* glu = pl.glu; float* dw = pl.dw;
     const float* dww = w.dw_w; const float* dwb = w.dw_b;
@@ -1093,7 +1158,7 @@ static void build_block(StageBuilder& sb, const std::string& pfx, const BlockW& 
       DwArgs da;
       da.z = glu; da.w_kc = dww; da.bias = dwb; da.gamma = ng; da.beta = nb; da.eps = 1e-5f; da.B = B; da.T = Tp; da.D = D; da.K = K;
       da.out = dw; da.out_bf16 = a16; da.pad_of = pad_of; da.row0 = row0; da.row_len = lens; da.causal_left_fill = lfill;
-      da.glu_ldz = glu_deferred ? 2 * D : 0;
+      da.glu_ldz = glu_deferred ? 2 * D : 0; da.glu_sig = glu_sig;
       add_stage(sb, pfx + "conv.dw_ln_silu", 1, [da](hipStream_t s) { return launch_dwconv_ln_silu_args(da, s); },
                 stage_info("dwconv_ln_silu_kernel", 1, (double)S * D * ((glu_deferred ? 8 : 4) + (a16 ? 2 : 4)) + (double)K * D * 4, 2.0 * K * D * S));
       sb.bd.stages.back().fuse_kind = FuseKind::Dwconv;
@@ -1133,7 +1198,7 @@ static void build_block(StageBuilder& sb, const std::string& pfx, const BlockW& 
     m.gidx = pl.gate_idx + (size_t)layer * S; m.gval = pl.gate_val + (size_t)layer * S;
     m.gv = c.keep_expert_output ? nullptr : m.gval;
     m.lens = lens; m.live_len = live_len; m.live_rpb = live_rpb; m.pdev = pdev;
-    m.eall = pl.eall + (size_t)layer * m.E; m.ld_eall = c.num_blocks * m.E;
+    m.eall = pl.eall + (size_t)layer * m.E; m.ld_eall = c.num_blocks * m.E; m.layer = layer;
     m.xb_out = a16 ? xb : nullptr; m.xstats_out = dma ? xstats : nullptr;
     m.ws = (char*)pl.moe_ws + (c.debug_taps ? (size_t)layer * pl.moe_ws_bytes : 0);
     m.mw = carve_moe_workspace(m.ws, S, m.E, D, F);
@@ -1398,6 +1463,22 @@ static int build_binding(m3_engine* e, const BindKey& k, m3_engine::Bound& bd) {
     add_gemm(sb, "router_e_all", g, true);
     bd.stages.back().reads_embed = true;
   }
+  // ... or, staged fp32 router of short inputs, as the accumulators every layer's router GEMM starts from: the same bits as the
+  // whole-K GEMM, half the operand pull on each layer's critical path (router_prefix_layer_floats)
+  if (pl.rprefix != nullptr) {
+    GemmParams g = router_concat_gemm(c, S, pl.emb, pl.x);
+    g.W = e->mblocks[0].router.w; g.Y = pl.rl; g.ln_gamma = e->mblocks[0].n_ff.g; g.ln_beta = e->mblocks[0].n_ff.b; g.acc_init = pl.rprefix;
+    if (bd.packed) g.m_dev = pl.row0 + B;
+    const GemmPlan plan = plan_gemm(g, 0);
+    M3_REQUIRE(plan.launches == 1 && router_prefix_floats(plan) == pl.rprefix_layer, "engine_prepare: router prefix: %s", plan.reason);
+    std::vector<const float*> wt(kRouterPrefixMaxLayers, nullptr);
+    for (int i = 0; i < c.num_blocks; ++i) wt[i] = e->mblocks[i].router.w;
+    float* prefix = pl.rprefix; const int L = c.num_blocks;
+    const double Etot = g.N;
+    add_stage(sb, "router_e_prefix", 1, [plan, g, wt, prefix, L](hipStream_t s) { return launch_router_embed_prefix(plan, g, wt.data(), 0, L, prefix, s); },
+              stage_info("router_embed_prefix_kernel", 1, 4.0 * De * (L * Etot + S) + 4.0 * L * pl.rprefix_layer, 2.0 * S * Etot * De * L));
+    bd.stages.back().reads_embed = true;
+  }
   // ---- main MoE encoder (conformer_fmoe_localComm_catEmbed_domain_acc_hier.py:198-234) ----
   const int main_start = (int)bd.stages.size();     // ... and the main encoder here
   build_subsample(sb, "subsample.", e->sub_m, D, pl, pl.x);
@@ -1449,6 +1530,8 @@ static int build_binding(m3_engine* e, const BindKey& k, m3_engine::Bound& bd) {
     add_stage(sb, "stream.advance", 1, [=](hipStream_t s) { return launch_advance_counter(step, 1, s); },
               stage_info("advance_counter_kernel", 1, 8.0, 0.0, false));
   }
+  for (int i = 0; i < (int)bd.stages.size(); ++i)
+    if (bd.stages[i].name == "router_e_prefix") bd.prefix_stage = i;
   bd.buffers["x"] = Buf{pl.x, (size_t)S * D * 4};
   bd.buffers["dw"] = Buf{pl.dw, (size_t)S * D * 4};   // the main encoder's depthwise conv + LayerNorm + SiLU output (last block run)
   if (!bd.xn_skipped) bd.buffers["xn"] = Buf{pl.xn, (size_t)S * D * 4};
@@ -1558,13 +1641,28 @@ int m3_engine_stage_info(const m3_engine* engine, int index, m3_stage_info* info
 }
 int m3_engine_num_kernels(const m3_engine* engine) { return engine ? engine->cur.n_kernels : 0; }
 
+// Stages [first, last) of the current binding.  A caller that runs stages piecewise may change a router's weights between two
+// calls (the calibration does: it runs up to a layer's router, edits that router, runs the router stage again), and the routers'
+// accumulator prefix was formed from the weights as they stood when "router_e_prefix" ran.  So a router stage that is reached
+// without the prefix stage in front of it IN THIS CALL first recomputes its own layer's slice, on the same stream: the stage
+// then computes what the whole-K GEMM would, whatever happened between the calls.  `whole`: the ranges are the pieces of one
+// forward (forked capture), the prefix stage has run in an earlier piece.
+static int run_stage_range(m3_engine* engine, int first_stage, int last_stage, hipStream_t stream, bool whole) {
+  const int ps = engine->cur.prefix_stage;
+  for (int i = first_stage; i < last_stage; ++i) {
+    const Stage& st = engine->cur.stages[i];
+    if (st.refresh_prefix && !whole && !(ps >= first_stage && ps < i))
+      if (int rc = st.refresh_prefix(stream)) return rc;
+    if (int rc = st.run(stream)) return rc;
+  }
+  return 0;
+}
+
 int m3_engine_run(m3_engine* engine, int first_stage, int last_stage, m3_stream stream) {
   M3_REQUIRE(engine && !engine->cur.stages.empty(), "engine_run: engine not prepared");
   M3_REQUIRE(first_stage >= 0 && last_stage <= (int)engine->cur.stages.size() && first_stage <= last_stage,
              "engine_run: bad stage range [%d,%d)", first_stage, last_stage);
-  for (int i = first_stage; i < last_stage; ++i)
-    if (int rc = engine->cur.stages[i].run((hipStream_t)stream)) return rc;
-  return 0;
+  return run_stage_range(engine, first_stage, last_stage, (hipStream_t)stream, false);
 }
 
 int m3_engine_buffer(const m3_engine* engine, const char* name, void** ptr, size_t* bytes) {
@@ -1586,7 +1684,6 @@ static int capture_graph(m3_engine* e, hipStream_t stream, const char* who) {
     b.graph_exec = nullptr;
   }
   hipGraph_t graph = nullptr;
-  const m3_stream stream_ = (m3_stream)stream;
   const int n_st = (int)b.stages.size();
   const bool fork = b.fork_first >= 0 && b.fork_mid > b.fork_first && b.join_at > b.fork_mid;
   if (fork && e->side == nullptr) {
@@ -1597,19 +1694,19 @@ static int capture_graph(m3_engine* e, hipStream_t stream, const char* who) {
   M3_CHECK_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
   int rc = 0;
   if (!fork) {
-    rc = m3_engine_run(e, 0, n_st, stream_);
+    rc = run_stage_range(e, 0, n_st, stream, true);
   } else {
     // two branches between "lens" and blocks.0's router: the embed encoder on the side stream (it joins the capture through
     // the fork event), the main subsampler + block 0 up to its router on the capture stream
     hipError_t he = hipSuccess;
-    rc = m3_engine_run(e, 0, b.fork_first, stream_);
+    rc = run_stage_range(e, 0, b.fork_first, stream, true);
     if (!rc && (he = hipEventRecord(e->ev_fork, stream)) != hipSuccess) rc = -1;
     if (!rc && (he = hipStreamWaitEvent(e->side, e->ev_fork, 0)) != hipSuccess) rc = -1;
-    if (!rc) rc = m3_engine_run(e, b.fork_first, b.fork_mid, (m3_stream)e->side);
-    if (!rc) rc = m3_engine_run(e, b.fork_mid, b.join_at, stream_);
+    if (!rc) rc = run_stage_range(e, b.fork_first, b.fork_mid, e->side, true);
+    if (!rc) rc = run_stage_range(e, b.fork_mid, b.join_at, stream, true);
     if (!rc && (he = hipEventRecord(e->ev_join, e->side)) != hipSuccess) rc = -1;
     if (!rc && (he = hipStreamWaitEvent(stream, e->ev_join, 0)) != hipSuccess) rc = -1;
-    if (!rc) rc = m3_engine_run(e, b.join_at, n_st, stream_);
+    if (!rc) rc = run_stage_range(e, b.join_at, n_st, stream, true);
     if (he != hipSuccess) set_error("%s: forked capture failed: %s", who, hipGetErrorString(he));
   }
   hipError_t ce = hipStreamEndCapture(stream, &graph);

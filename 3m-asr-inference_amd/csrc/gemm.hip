@@ -53,10 +53,16 @@ enum { LN_NONE = GEMM_LN_NONE, LN_EPI = GEMM_LN_EPI, LN_PRO = GEMM_LN_PRO };
 // gemm_f32_dual_kernel two INDEPENDENT problems of the same instantiation in one launch (work-groups [0, n0) the first,
 // the rest the second) -- the embed encoder and the main encoder's first block do not depend on each other until that block's
 // router, so their GEMMs can share launches (engine.hip: "horizontal fusion"; a launch saved is ~6 us of a B = 1 forward).
-template <int MT, bool GLU, int NW, bool CONV, int LN, int NBUF>
+// ACCI (GemmParams::acc_init; the router on cat([embed, LN(x)])): the wave's A-half K-steps -- the first half of its one load
+// group, K1 == K / 2 == 8 * NW * G by the plan's check -- were run by router_embed_prefix_kernel, which left (acc, acc2) as they
+// stand after them.  The wave loads the pair with its operand group and starts at step G / 2: the skipped steps are not in the
+// instantiation at all.  wave w walks steps w, w + NW, ... in increasing order, so an MFMA chain cut there yields the same bits.
+template <int MT, bool GLU, int NW, bool CONV, int LN, int NBUF, bool ACCI = false>
 __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid) {
   constexpr int NT = GLU ? 2 : 1;
   constexpr int G = gemm_group_steps(MT, NT, NW);
+  constexpr int I0 = ACCI ? G / 2 : 0;   // first K-step of the load group this instantiation runs
+  static_assert(!ACCI || (MT == 1 && !GLU && !CONV && NBUF == 1 && G % 2 == 0), "acc_init: the one-group 16-row concat form only");
   constexpr int RW = (16 * MT) / NW;   // rows per wave in the LN_PRO prologue (>= 1)
   static_assert(RW >= 1, "more waves than rows");
   __shared__ float red[NW][MT * NT][256];
@@ -71,7 +77,8 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
   // them together, one wait.
   asm volatile("" ::"s"(p.A), "s"(p.lda), "s"(p.W), "s"(p.bias), "s"(p.Y), "s"(p.ldy), "s"(p.M), "s"(p.N), "s"(p.K), "s"(p.mode),
                "s"(p.n_tiles), "s"(p.m_tiles), "s"(p.xcd_swizzle), "s"(p.m_dev), "s"(p.resid), "s"(p.ldr), "s"(p.act), "s"(p.alpha),
-               "s"(p.mask_in), "s"(p.mask_out), "s"(p.row_len), "s"(p.rows_per_batch));
+               "s"(p.mask_in), "s"(p.mask_out), "s"(p.row_len), "s"(p.rows_per_batch), "s"(p.sig_col0));
+  if (ACCI) asm volatile("" ::"s"(p.acc_init));
   if (LN == LN_EPI) asm volatile("" ::"s"(p.ln_wsum), "s"(p.ln_wbeta), "s"(p.ln_eps));
   if (LN == LN_PRO) asm volatile("" ::"s"(p.ln_gamma), "s"(p.ln_beta), "s"(p.ln_eps), "s"(p.ln_out), "s"(p.ld_ln_out), "s"(p.ln_on_a2));
   if (!CONV) asm volatile("" ::"s"(p.A2), "s"(p.lda2), "s"(p.K1));
@@ -150,13 +157,13 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
   f32x4 wbuf[NBUF][G][NT], abuf[NBUF][G][MT];
   auto load_group = [&](int g, int buf) {
 #pragma unroll
-    for (int i = 0; i < G; ++i) {
+    for (int i = I0; i < G; ++i) {
       // steps past the end re-load the last step (results unused): no branch around the loads
       const int s = min(wave + NW * (G * g + i), nsteps - 1);
       const int k = s << 4;
 #pragma unroll
       for (int t = 0; t < NT; ++t) wbuf[buf][i][t] = ldg4_w(wrow[t] + k);
-      const bool second = !CONV && p.mode == GEMM_A_CONCAT2 && k >= p.K1;
+      const bool second = ACCI || (!CONV && p.mode == GEMM_A_CONCAT2 && k >= p.K1);
       const int off = second ? (k - p.K1) : a_offset(k);
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) abuf[buf][i][mt] = ldg4((second ? arow2[mt] : arow[mt]) + off);
@@ -168,7 +175,32 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
   // (Compile-time load offsets for the common exact shape -- one base address per row, no per-load address arithmetic -- were
   //  tried: issue-to-data time unchanged (4 830 vs 4 650 cycles).  The loads are not issue-bound: a CU keeps ~16 KB of misses in
   //  flight whatever the instruction stream, so 64 KB per work-group take ~4 latencies.)
+  // ACCI: the LayerNorm statistics pass's row loads go out AHEAD of the operand group.  Loads return in issue order, and the
+  // pass (two reductions, LDS, a barrier) stands between the last load and the first MFMA: behind the operand group it waited
+  // for all of it.  Load order only; the arithmetic below is the same.
+  f32x4 ln_v[16];
+  auto load_stat_rows = [&](int c) {
+    const int l16 = lane & 15;
+    const int rloc = wave * RW + 4 * c + (lane >> 4);
+    const int m = min(m0 + min(rloc, 16 * MT - 1), p.M - 1);
+    const float* row = (p.ln_on_a2 ? p.A2 : p.A) + (size_t)m * (p.ln_on_a2 ? p.lda2 : p.lda);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) ln_v[j] = ldg4(row + min(4 * (l16 + 16 * j), Kl - 4));
+    if (Kl > 512) {   // (one wave-uniform branch: rows up to 512 wide have no element in the second eight fragments)
+#pragma unroll
+      for (int j = 8; j < 16; ++j) ln_v[j] = ldg4(row + min(4 * (l16 + 16 * j), Kl - 4));
+    } else {
+#pragma unroll
+      for (int j = 8; j < 16; ++j) ln_v[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  };
+  if (LN == LN_PRO && ACCI) load_stat_rows(0);
   load_group(0, 0);
+  if (ACCI) {   // the accumulator pair as the A-half steps left it: requested with the operand group, needed at the first MFMA
+    const float* pre = p.acc_init + ((size_t)((m_tile * p.n_tiles + n_tile) * NW + wave) * 2) * 256 + 4 * lane;
+    acc[0][0] = ldg4(pre);
+    acc2[0][0] = ldg4(pre + 256);
+  }
   M3_GDIAG(dg[2] = __builtin_amdgcn_s_memtime();)
   // (everything below is issued behind the first group of operand loads: it is needed at epilogue time only)
   // the epilogue wave's bias / residual are requested up front (they would otherwise be a dependent
@@ -221,8 +253,6 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
     ln_out_row[mt] = nullptr;
   }
   if (LN == LN_PRO) {
-    const float* lnA = p.ln_on_a2 ? p.A2 : p.A;
-    const int ldl = p.ln_on_a2 ? p.lda2 : p.lda;
     for (int k = threadIdx.x * 4; k < Kl; k += 256 * NW) {
       *reinterpret_cast<f32x4*>(&ln_g[k]) = ldg4(p.ln_gamma + k);
       *reinterpret_cast<f32x4*>(&ln_b[k]) = ldg4(p.ln_beta + k);
@@ -233,13 +263,12 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
     for (int c = 0; c < (RW + 3) / 4; ++c) {
       const int rloc = wave * RW + 4 * c + q;
       const bool row_on = (4 * c + q) < RW;
-      const int m = min(m0 + min(rloc, 16 * MT - 1), p.M - 1);
-      const float* row = lnA + (size_t)m * ldl;
       f32x4 v[16];
+      if (!(ACCI && c == 0)) load_stat_rows(c);
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
         const int k = 4 * (l16 + 16 * j);
-        const f32x4 t = ldg4(row + min(k, Kl - 4));
+        const f32x4 t = ln_v[j];
         const bool in = j < nj && k < Kl;
         v[j] = f32x4{in ? t[0] : 0.f, in ? t[1] : 0.f, in ? t[2] : 0.f, in ? t[3] : 0.f};
       }
@@ -276,7 +305,7 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
 
   auto compute_group = [&](int g, int buf) {
 #pragma unroll
-    for (int i = 0; i < G; ++i) {
+    for (int i = I0; i < G; ++i) {
       const int s = wave + NW * (G * g + i);
       if (s < nsteps) {
         const int k = s << 4;
@@ -395,8 +424,11 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
           }
           ln_mean_rstd(t1, t2, Kl, p.ln_eps, mean, rstd);
         }
-        p.Y[(size_t)m * p.ldy + ep_n] =
-            gemm_epilogue<GLU, LN == LN_EPI>(y0, y1, bias0, bias1, wsum0, wsum1, wbeta0, wbeta1, mean, rstd, pad, res[r], p);
+        float y = gemm_epilogue<GLU, LN == LN_EPI>(y0, y1, bias0, bias1, wsum0, wsum1, wbeta0, wbeta1, mean, rstd, pad, res[r], p);
+        // a deferred GLU's gate columns (uniform per work-group: sig_col0 is a multiple of 16): the value the GLU epilogue hands to
+        // its sigmoid, through the same sigmoid
+        if (!GLU && p.sig_col0 >= 0 && n0 >= p.sig_col0) y = sigmoidf(y);
+        p.Y[(size_t)m * p.ldy + ep_n] = y;
       }
     }
   }
@@ -412,9 +444,83 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
            })
 }
 
-template <int MT, bool GLU, int NW, bool CONV, int LN, int NBUF>
+template <int MT, bool GLU, int NW, bool CONV, int LN, int NBUF, bool ACCI = false>
 __global__ __launch_bounds__(64 * NW) void gemm_f32_kernel(const GemmParams p) {
-  gemm_f32_body<MT, GLU, NW, CONV, LN, NBUF>(p, (int)blockIdx.x);
+  gemm_f32_body<MT, GLU, NW, CONV, LN, NBUF, ACCI>(p, (int)blockIdx.x);
+}
+
+// The A half of the concat GEMMs gemm_f32_kernel<1, false, NW, false, LN_PRO, 1, true> finishes, for several weight matrices over
+// the same A rows (the routers of all main blocks: the embedding is final before block 0's and none of them changes it).
+// Work-group (tile, layer), wave w: exactly the K-steps w, w + NW, ... < K1 / 16 of gemm_f32_body, the same operand fragments, the
+// same two MFMA chains in the same order; the pair goes to memory as it stands, no reduction.
+struct RouterPrefixArgs {
+  const float* A; int lda; int M, N, K;            // K: row stride of the weights (both halves); the A half is columns [0, K / 2)
+  int n_tiles, m_tiles, xcd_swizzle;
+  const int32_t* m_dev;
+  float* prefix; long layer_floats; int layer0;
+  const float* w[kRouterPrefixMaxLayers];
+};
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void router_embed_prefix_kernel(const RouterPrefixArgs a) {
+  constexpr int H = gemm_group_steps(1, 1, NW) / 2;   // K-steps per wave
+  asm volatile("" ::"s"(a.A), "s"(a.lda), "s"(a.M), "s"(a.N), "s"(a.K), "s"(a.n_tiles), "s"(a.m_tiles), "s"(a.xcd_swizzle), "s"(a.m_dev),
+               "s"(a.prefix), "s"(a.layer_floats), "s"(a.layer0));
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int col = lane & 15, kq = lane >> 4;
+  const int layer = a.layer0 + (int)blockIdx.y;
+  int n_tile, m_tile;
+  {
+    const int id = (int)blockIdx.x;
+    if (a.xcd_swizzle) {
+      const int j = id >> 3;
+      m_tile = j % a.m_tiles;
+      n_tile = (j / a.m_tiles) * 8 + (id & 7);
+    } else {
+      n_tile = id % a.n_tiles;
+      m_tile = id / a.n_tiles;
+    }
+  }
+  const int n0 = n_tile * 16, m0 = m_tile * 16;
+  if (a.m_dev != nullptr && m0 > *a.m_dev) return;   // (the consumer's tile exits the same way)
+  const float* arow = a.A + (size_t)min(m0 + col, a.M - 1) * a.lda + 4 * kq;
+  const float* wrow = a.w[layer] + (size_t)min(n0 + col, a.N - 1) * a.K + 4 * kq;
+  f32x4 wb[H], ab[H];
+#pragma unroll
+  for (int i = 0; i < H; ++i) {
+    const int k = (wave + NW * i) << 4;
+    wb[i] = ldg4_w(wrow + k);
+    ab[i] = ldg4(arow + k);
+  }
+  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f}, acc2 = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < H; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; j += 2) {
+      acc = mfma16(ab[i][j], wb[i][j], acc);
+      acc2 = mfma16(ab[i][j + 1], wb[i][j + 1], acc2);
+    }
+  float* o = a.prefix + (size_t)layer * a.layer_floats + ((size_t)((m_tile * a.n_tiles + n_tile) * NW + wave) * 2) * 256 + 4 * lane;
+  stg4(o, acc);
+  stg4(o + 256, acc2);
+}
+
+size_t router_prefix_floats(const GemmPlan& plan) { return (size_t)plan.m_tiles * plan.n_tiles * plan.nw * 2 * 256; }
+
+int launch_router_embed_prefix(const GemmPlan& plan, const GemmParams& p, const float* const* w, int layer0, int n_layers, float* prefix,
+                               hipStream_t stream) {
+  M3_REQUIRE(plan.launches == 1 && plan.kernel == GemmKernel::SkinnyF32 && p.acc_init != nullptr && (plan.nw == 4 || plan.nw == 8),
+             "router prefix: the consumer's plan does not take an accumulator prefix");
+  M3_REQUIRE(layer0 >= 0 && n_layers > 0 && layer0 + n_layers <= kRouterPrefixMaxLayers && prefix != nullptr, "router prefix: bad layer range");
+  RouterPrefixArgs a;
+  a.A = p.A; a.lda = p.lda; a.M = p.M; a.N = p.N; a.K = p.K;
+  a.n_tiles = plan.n_tiles; a.m_tiles = plan.m_tiles; a.xcd_swizzle = plan.xcd_swizzle;
+  a.m_dev = p.m_dev; a.prefix = prefix; a.layer_floats = (long)router_prefix_floats(plan); a.layer0 = layer0;
+  for (int l = 0; l < kRouterPrefixMaxLayers; ++l) a.w[l] = (l >= layer0 && l < layer0 + n_layers) ? w[l] : nullptr;
+  const dim3 grid(plan.n_tiles * plan.m_tiles, n_layers);
+  if (plan.nw == 8) hipLaunchKernelGGL((router_embed_prefix_kernel<8>), grid, dim3(512), 0, stream, a);
+  else hipLaunchKernelGGL((router_embed_prefix_kernel<4>), grid, dim3(256), 0, stream, a);
+  M3_LAUNCH_CHECK();
+  return 0;
 }
 // (the second problem's work-group ids start at a multiple of 8, so that "id % 8 = XCD" holds for its XCD-aware tile order too)
 template <int MT, bool GLU, int NW, int LN>
@@ -455,6 +561,12 @@ int launch_gemm_f32_skinny(const GemmPlan& plan, const GemmParams& pin, hipStrea
   p.n_tiles = plan.n_tiles; p.m_tiles = plan.m_tiles; p.xcd_swizzle = plan.xcd_swizzle;
   dim3 grid(p.n_tiles * p.m_tiles);
   const int mt = plan.mt, nw = plan.nw, ln = plan.ln;
+  if (p.acc_init != nullptr) {        // (plan_gemm: 16-row tiles, 4 / 8 waves, one load group, affine LayerNorm on the A2 half)
+    if (nw == 8) hipLaunchKernelGGL((gemm_f32_kernel<1, false, 8, false, LN_PRO, 1, true>), grid, dim3(512), 0, stream, p);
+    else hipLaunchKernelGGL((gemm_f32_kernel<1, false, 4, false, LN_PRO, 1, true>), grid, dim3(256), 0, stream, p);
+    M3_LAUNCH_CHECK();
+    return 0;
+  }
 
 #define M3_GEMM_LAUNCH(MT_, GLU_, NW_, CONV_, LN_)                                                              \
   do {                                                                                                          \

@@ -162,7 +162,25 @@ static bool choose_form(const GemmParams& p, size_t ws_avail, GemmPlan& plan) {
   skinny_grid(p, plan, Nout);
   // the dual instantiations: 16-row tiles, 4 / 8 waves, one load group per wave (every block GEMM of the model at B = 1)
   plan.dual_ok = plan.mt == 1 && (plan.nw == 4 || plan.nw == 8) && plan.nbuf == 1 && p.mode == GEMM_A_PLAIN &&
-                 plan.ln != GEMM_LN_PRO && p.m_dev == nullptr;
+                 plan.ln != GEMM_LN_PRO && p.m_dev == nullptr && p.acc_init == nullptr;
+  return true;
+}
+
+// sig_col0 and acc_init are features of the skinny fp32 kernel alone (kernels.h says of which of its forms)
+static bool extras_ok(const GemmParams& p, GemmPlan& plan) {
+  if (p.sig_col0 >= 0) {
+    M3_PLAN_REQUIRE(plan.kernel == GemmKernel::SkinnyF32 && !plan.glu, "gemm: sig_col0 needs the skinny fp32 kernel with a plain epilogue (M=%d N=%d K=%d)",
+                    p.M, p.N, p.K);
+    M3_PLAN_REQUIRE((p.sig_col0 & 15) == 0, "gemm: sig_col0=%d must be a multiple of 16", p.sig_col0);
+  }
+  if (p.acc_init != nullptr) {
+    M3_PLAN_REQUIRE(plan.kernel == GemmKernel::SkinnyF32 && plan.mt == 1 && !plan.glu && p.mode == GEMM_A_CONCAT2 && (p.K1 & 15) == 0,
+                    "gemm: acc_init needs the skinny fp32 kernel, 16-row tiles, concat operands with K1 %% 16 == 0");
+    M3_PLAN_REQUIRE(plan.ln == GEMM_LN_PRO && p.ln_on_a2 && (plan.nw == 4 || plan.nw == 8) && plan.nbuf == 1 && 2 * p.K1 == p.K &&
+                    p.K == 16 * plan.nw * gemm_group_steps(1, 1, plan.nw),
+                    "gemm: acc_init is built for K1 = K / 2 = %d with the LayerNorm prologue on the A2 half (K1=%d K=%d)",
+                    8 * plan.nw * gemm_group_steps(1, 1, plan.nw), p.K1, p.K);
+  }
   return true;
 }
 
@@ -172,7 +190,7 @@ GemmPlan plan_gemm(const GemmParams& p, size_t workspace_bytes_available) {
   plan.label = "";
   plan.glu = p.act == ACT_GLU; plan.conv = p.mode == GEMM_A_CONV3X3S2;
   plan.ln = p.ln_wsum ? GEMM_LN_EPI : (p.ln_gamma ? GEMM_LN_PRO : GEMM_LN_NONE);
-  if (operands_ok(p, p.w_bf16 ? "gemm_bf16w" : "gemm", plan) && choose_form(p, workspace_bytes_available, plan))
+  if (operands_ok(p, p.w_bf16 ? "gemm_bf16w" : "gemm", plan) && choose_form(p, workspace_bytes_available, plan) && extras_ok(p, plan))
     plan.launches = plan.kernel == GemmKernel::SplitKF32 ? 2 : 1;
   return plan;
 }

@@ -51,6 +51,13 @@ struct GemmParams {
   // implicit conv on a packed ragged batch: valid output frames per utterance; a tile whose rows (b, t2, f2) all lie past
   // the utterance's last frame is skipped (its output rows are never gathered into the packed layout)
   const int32_t* conv_len = nullptr;
+  // skinny fp32 kernel, plain epilogue: output columns >= sig_col0 (a multiple of 16; -1: none) are stored as sigmoid(y) -- the
+  // GLU gate of a deferred-GLU pointwise_conv1, sigmoided once where the epilogue holds it instead of once per depthwise tap
+  int sig_col0 = -1;
+  // skinny fp32 kernel, 16-row tiles, concat mode with K1 == K / 2 and one load group per wave: the accumulator pair every wave
+  // holds after its A-half K-steps, [m_tile][n_tile][wave][2][64 lanes] float4, as router_embed_prefix_kernel leaves it.  The wave
+  // starts from it and runs its A2-half steps only (an MFMA chain cut and resumed from the stored registers: the same bits)
+  const float* acc_init = nullptr;
   // filled by the launchers from the GemmPlan
   int n_tiles = 0, m_tiles = 0, xcd_swizzle = 0;
 };
@@ -87,6 +94,13 @@ GemmPlan plan_gemm(const GemmParams& p, size_t workspace_bytes_available);
 int launch_gemm(const GemmPlan& plan, const GemmParams& p, float* ws, hipStream_t stream);
 bool gemm_dual_fusable(const GemmPlan& a, const GemmPlan& b);   // two independent skinny fp32 GEMMs of one instantiation
 int launch_gemm_f32_dual(const GemmPlan& pa, const GemmParams& a, const GemmPlan& pb, const GemmParams& b, hipStream_t stream);   // ... in ONE launch
+// The A (embed) half of up to kRouterPrefixMaxLayers concat GEMMs that share A, M, N, K, K1 and differ in W: the accumulator
+// pairs GemmParams::acc_init takes, layer l's at prefix + l * router_prefix_floats(plan).  `plan`: the consumers' plan (a form
+// that takes acc_init); layers [layer0, layer0 + n_layers) of w[] are computed, one launch.
+constexpr int kRouterPrefixMaxLayers = 64;
+size_t router_prefix_floats(const GemmPlan& plan);   // per layer
+int launch_router_embed_prefix(const GemmPlan& plan, const GemmParams& p, const float* const* w, int layer0, int n_layers, float* prefix,
+                               hipStream_t stream);
 // K-steps per in-flight load group of the skinny kernels (the planner needs them for nbuf).  fp32: 2 buffers x G x (NT + MT)
 // float4 must fit the per-lane register budget (512 VGPR+AGPR for 4 waves, 256 for 8, 128 for 16 waves per workgroup)
 constexpr int gemm_group_steps(int MT, int NT, int NW) {
@@ -328,6 +342,7 @@ struct DwArgs {
   int B = 0, T = 0, D = 0, K = 0; float* out = nullptr; int out_bf16 = 0;
   const int32_t *pad_of = nullptr, *row0 = nullptr, *row_len = nullptr; const float* causal_left_fill = nullptr;
   int glu_ldz = 0;   // > 0: z is pointwise_conv1's raw [B*T][glu_ldz] output (value | gate columns), GLU applied as the taps are loaded
+  int glu_sig = 0;   // (with glu_ldz) the gate columns hold sigmoid(gate) already (GemmParams::sig_col0): every tap is one multiply
 };
 int launch_dwconv_ln_silu_args(const DwArgs& a, hipStream_t stream);
 bool dwconv_glu_in_supports(int D, int K, bool causal_or_stream, int out_bf16, int ldz);   // what the GLU-on-load form takes
