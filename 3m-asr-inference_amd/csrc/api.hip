@@ -429,14 +429,11 @@ int m3_log_softmax_bias(const float* x, const float* bias, float* y, size_t rows
   M3_REQUIRE(x && y && n > 0, "log_softmax_bias: bad arguments");
   return launch_log_softmax_bias(x, bias, y, rows, n, (hipStream_t)stream);
 }
-int m3_conv2d_3x3s2(const float* in, const float* w, const float* bias, int B, int T1, int F1, int C, int act, float* out,
-                    m3_stream stream);
 int m3_subsample_conv2(const float* in, const float* w, const float* bias, int B, int T1, int F1, int C, float* out,
                        m3_stream stream) {
   return m3_conv2d_3x3s2(in, w, bias, B, T1, F1, C, M3_ACT_RELU, out, stream);
 }
-int m3_conv2d_3x3s2(const float* in, const float* w, const float* bias, int B, int T1, int F1, int C, int act, float* out,
-                    m3_stream stream) {
+static int conv2d_params(const float* in, const float* w, const float* bias, int B, int T1, int F1, int C, int act, float* out, GemmParams* q) {
   M3_REQUIRE(T1 >= 3 && F1 >= 3, "subsample_conv2: input (%d,%d) smaller than the kernel", T1, F1);
   M3_REQUIRE(act == M3_ACT_NONE || act == M3_ACT_RELU || act == M3_ACT_SILU, "conv2d: act %d", act);
   GemmParams p;
@@ -446,7 +443,172 @@ int m3_conv2d_3x3s2(const float* in, const float* w, const float* bias, int B, i
   p.W = w; p.bias = bias; p.Y = out; p.ldy = C;
   p.M = B * p.conv_T2 * p.conv_F2; p.N = C; p.K = 9 * C;
   p.act = act;
-  return launch_gemm(plan_gemm(p, 0), p, nullptr, (hipStream_t)stream);
+  *q = p;
+  return 0;
+}
+int m3_conv2d_3x3s2(const float* in, const float* w, const float* bias, int B, int T1, int F1, int C, int act, float* out,
+                    m3_stream stream) {
+  return m3_conv2d_3x3s2_ws(in, w, bias, B, T1, F1, C, act, out, nullptr, 0, stream);
+}
+size_t m3_conv2d_3x3s2_workspace_size(int B, int T1, int F1, int C, int act) {
+  GemmParams p;
+  return conv2d_params(nullptr, nullptr, nullptr, B, T1, F1, C, act, nullptr, &p) == 0 ? plan_gemm(p, SIZE_MAX).ws_bytes : 0;
+}
+// (a missing or too-small workspace: the plan is the one-launch form)
+int m3_conv2d_3x3s2_ws(const float* in, const float* w, const float* bias, int B, int T1, int F1, int C, int act, float* out,
+                       void* workspace, size_t workspace_bytes, m3_stream stream) {
+  GemmParams p;
+  if (int rc = conv2d_params(in, w, bias, B, T1, F1, C, act, out, &p)) return rc;
+  return launch_gemm(plan_gemm(p, workspace != nullptr ? workspace_bytes : 0), p, (float*)workspace, (hipStream_t)stream);
+}
+
+// ---- the paired launches at the boundary (include/m3asr.h): both problems checked as their single entries check them, outputs
+// apart, one launcher call
+static bool ranges_overlap(const void* a, size_t bytes_a, const void* b, size_t bytes_b) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 < b0 + bytes_b && b0 < a0 + bytes_a;
+}
+static size_t rows_bytes(long rows, long ld, long width) { return rows > 0 ? (size_t)((rows - 1) * ld + width) * sizeof(float) : 0; }
+static size_t linear_out_bytes(const m3_linear_desc* d) { return rows_bytes(d->M, d->ldy, d->act == M3_ACT_GLU ? d->N / 2 : d->N); }
+// why two plans have no common instantiation of gemm_f32_dual_kernel, as text (gemm_dual_fusable says only that)
+static int linear_pair_plans(const GemmPlan& pa, const GemmPlan& pb) {
+  const GemmPlan* const plans[2] = {&pa, &pb};
+  for (int i = 0; i < 2; ++i) {
+    const GemmPlan& q = *plans[i];
+    M3_REQUIRE(q.launches > 0, "%s", q.reason);
+    M3_REQUIRE(q.kernel == GemmKernel::SkinnyF32 && q.launches == 1, "linear pair: problem %d runs %s: only the skinny fp32 kernel (gemm_f32_kernel) pairs", i, q.label);
+    M3_REQUIRE(q.dual_ok,
+               "linear pair: problem %d has %d-row tiles, %d waves, %d load group%s: the paired kernel takes 16-row tiles, 4 or 8 waves, one load "
+               "group, plain a, no affine LayerNorm", i, 16 * q.mt, q.nw, q.nbuf, q.nbuf == 1 ? "" : "s");
+  }
+  M3_REQUIRE(gemm_dual_fusable(pa, pb), "linear pair: the problems differ in waves (%d / %d), folded LayerNorm (%d / %d) or GLU (%d / %d)",
+             pa.nw, pb.nw, pa.ln != GEMM_LN_NONE, pb.ln != GEMM_LN_NONE, (int)pa.glu, (int)pb.glu);
+  return 0;
+}
+static int splitk_pair_plans(const char* who, const GemmPlan& pa, const GemmPlan& pb) {
+  const GemmPlan* const plans[2] = {&pa, &pb};
+  for (int i = 0; i < 2; ++i) {
+    M3_REQUIRE(plans[i]->launches > 0, "%s", plans[i]->reason);
+    M3_REQUIRE(plans[i]->kernel == GemmKernel::SplitKF32, "%s: problem %d is no split-K problem with its workspace (it runs %s)", who, i, plans[i]->label);
+  }
+  M3_REQUIRE(gemm_splitk_dual_fusable(pa, pb), "%s: an implicit conv pairs with an implicit conv, a plain problem with a plain one", who);
+  return 0;
+}
+static int splitk_pair_launch(const char* who, const GemmParams& pa, void* ws_a, size_t bytes_a, const void* out_a, size_t out_bytes_a,
+                              const GemmParams& pb, void* ws_b, size_t bytes_b, const void* out_b, size_t out_bytes_b, int which, m3_stream stream) {
+  M3_REQUIRE(which >= 1 && which <= 3, "%s: which=%d (1 the GEMM launch, 2 the reduce launch, 3 both)", who, which);
+  const GemmPlan qa = plan_gemm(pa, ws_a != nullptr ? bytes_a : 0), qb = plan_gemm(pb, ws_b != nullptr ? bytes_b : 0);
+  if (int rc = splitk_pair_plans(who, qa, qb)) return rc;
+  M3_REQUIRE(!ranges_overlap(ws_a, qa.ws_bytes, ws_b, qb.ws_bytes), "%s: each problem needs its own workspace", who);
+  M3_REQUIRE(!ranges_overlap(out_a, out_bytes_a, out_b, out_bytes_b), "%s: the two outputs overlap", who);
+  return launch_gemm_f32_splitk_dual(qa, pa, (float*)ws_a, qb, pb, (float*)ws_b, (hipStream_t)stream, which);
+}
+const char* m3_linear_pair_kernel(const m3_linear_desc* a, const m3_linear_desc* b, int with_workspace) {
+  GemmParams pa, pb;
+  if (linear_params(a, &pa) || linear_params(b, &pb)) return nullptr;
+  const size_t ws = with_workspace ? SIZE_MAX : 0;
+  const GemmPlan qa = plan_gemm(pa, ws), qb = plan_gemm(pb, ws);
+  if (with_workspace) return splitk_pair_plans("linear pair (workspaces)", qa, qb) ? nullptr : "gemm_f32_splitk_dual_kernel";
+  return linear_pair_plans(qa, qb) ? nullptr : "gemm_f32_dual_kernel";
+}
+int m3_linear_pair(const m3_linear_desc* a, const m3_linear_desc* b, m3_stream stream) {
+  GemmParams pa, pb;
+  if (int rc = linear_params(a, &pa)) return rc;
+  if (int rc = linear_params(b, &pb)) return rc;
+  if (int rc = linear_pointers(a)) return rc;
+  if (int rc = linear_pointers(b)) return rc;
+  const GemmPlan qa = plan_gemm(pa, 0), qb = plan_gemm(pb, 0);
+  if (int rc = linear_pair_plans(qa, qb)) return rc;
+  M3_REQUIRE(!ranges_overlap(a->y, linear_out_bytes(a), b->y, linear_out_bytes(b)), "linear pair: the two outputs overlap");
+  return launch_gemm_f32_dual(qa, pa, qb, pb, (hipStream_t)stream);
+}
+int m3_linear_ws_pair(const m3_linear_desc* a, void* workspace_a, size_t bytes_a, const m3_linear_desc* b, void* workspace_b,
+                      size_t bytes_b, int which, m3_stream stream) {
+  GemmParams pa, pb;
+  if (int rc = linear_params(a, &pa)) return rc;
+  if (int rc = linear_params(b, &pb)) return rc;
+  if (int rc = linear_pointers(a)) return rc;
+  if (int rc = linear_pointers(b)) return rc;
+  return splitk_pair_launch("linear pair (workspaces)", pa, workspace_a, bytes_a, a->y, linear_out_bytes(a), pb, workspace_b, bytes_b, b->y,
+                            linear_out_bytes(b), which, stream);
+}
+int m3_conv2d_3x3s2_ws_pair(const m3_conv2d_desc* a, void* workspace_a, size_t bytes_a, const m3_conv2d_desc* b, void* workspace_b,
+                            size_t bytes_b, int which, m3_stream stream) {
+  M3_REQUIRE(a != nullptr && b != nullptr, "conv2d pair: null descriptor");
+  GemmParams pa, pb;
+  if (int rc = conv2d_params(a->in, a->w, a->bias, a->B, a->T1, a->F1, a->C, a->act, a->out, &pa)) return rc;
+  if (int rc = conv2d_params(b->in, b->w, b->bias, b->B, b->T1, b->F1, b->C, b->act, b->out, &pb)) return rc;
+  M3_REQUIRE(a->in && a->w && a->out && b->in && b->w && b->out, "conv2d pair: null in / w / out");
+  return splitk_pair_launch("conv2d pair", pa, workspace_a, bytes_a, a->out, rows_bytes(pa.M, pa.ldy, pa.N), pb, workspace_b, bytes_b, b->out,
+                            rows_bytes(pb.M, pb.ldy, pb.N), which, stream);
+}
+int m3_relpos_attention_pair(const m3_attention_desc* a, const m3_attention_desc* b, m3_stream stream) {
+  M3_REQUIRE(a != nullptr && b != nullptr, "attention pair: null descriptor");
+  const m3_attention_desc* const ds[2] = {a, b};
+  AttArgs q[2];
+  for (int i = 0; i < 2; ++i) {
+    const m3_attention_desc* d = ds[i];
+    M3_REQUIRE(d->B > 0 && d->T > 0 && d->H > 0 && d->dk > 0, "attention pair: empty problem %d", i);
+    M3_REQUIRE(d->qkv && d->p && d->pos_u && d->pos_v && d->out, "attention pair: null qkv / p / pos_u / pos_v / out");
+    if (int rc = attention_operands(d->qkv, d->ldq, d->p, d->ldp, d->out, d->ldo, d->B, d->T, d->H, d->dk)) return rc;
+    q[i].qkv = d->qkv; q[i].ldq = d->ldq; q[i].pmat = d->p; q[i].ldp = d->ldp; q[i].pos_u = d->pos_u; q[i].pos_v = d->pos_v;
+    q[i].row_len = d->len; q[i].B = d->B; q[i].T = d->T; q[i].H = d->H; q[i].dk = d->dk; q[i].scale = d->scale; q[i].out = d->out;
+    q[i].ldo = d->ldo; q[i].chunk = d->chunk; q[i].left_chunks = d->left_chunks;
+  }
+  M3_REQUIRE(relpos_attention_dual_fusable(q[0], q[1]),
+             "attention pair: head widths %d / %d (64 or 128 each) or row strides ldq %d / %d, ldp %d / %d (multiples of 4) are not a paired instantiation",
+             a->dk, b->dk, a->ldq, b->ldq, a->ldp, b->ldp);
+  M3_REQUIRE(!ranges_overlap(a->out, rows_bytes((long)a->B * a->T, a->ldo, a->H * a->dk), b->out, rows_bytes((long)b->B * b->T, b->ldo, b->H * b->dk)),
+             "attention pair: the two outputs overlap");
+  return launch_relpos_attention_dual(q[0], q[1], (hipStream_t)stream);
+}
+int m3_dwconv_ln_silu_pair(const m3_dwconv_desc* a, const m3_dwconv_desc* b, m3_stream stream) {
+  M3_REQUIRE(a != nullptr && b != nullptr, "dwconv pair: null descriptor");
+  const m3_dwconv_desc* const ds[2] = {a, b};
+  DwArgs q[2];
+  for (int i = 0; i < 2; ++i) {
+    const m3_dwconv_desc* d = ds[i];
+    M3_REQUIRE(d->B > 0 && d->T > 0 && d->D > 0 && d->K > 0, "dwconv pair: empty problem %d", i);
+    M3_REQUIRE(d->z && d->w_kc && d->bias && d->out && (d->gamma == nullptr) == (d->beta == nullptr),
+               "dwconv pair: null z / w_kc / bias / out, or gamma without beta");
+    M3_REQUIRE(aligned16(d->z) && aligned16(d->w_kc) && aligned16(d->bias) && aligned16(d->gamma) && aligned16(d->beta) &&
+               aligned16(d->left_fill) && aligned16(d->out), "dwconv pair: every operand must be 16-byte aligned");
+    M3_REQUIRE(d->ldz >= 0 && (d->ldz > 0 || !d->gate_sigmoided), "dwconv pair: ldz=%d (sigmoided gate columns belong to the GLU-on-load form)", d->ldz);
+    M3_REQUIRE(d->left_fill == nullptr || d->K >= 2, "dwconv pair: the causal conv needs K >= 2");
+    q[i].z = d->z; q[i].glu_ldz = d->ldz; q[i].glu_sig = d->gate_sigmoided != 0; q[i].w_kc = d->w_kc; q[i].bias = d->bias; q[i].gamma = d->gamma;
+    q[i].beta = d->beta; q[i].eps = d->eps; q[i].causal_left_fill = d->left_fill; q[i].B = d->B; q[i].T = d->T; q[i].D = d->D; q[i].K = d->K;
+    q[i].out = d->out;
+  }
+  M3_REQUIRE(dwconv_dual_fusable(q[0], q[1]),
+             "dwconv pair: channels %d / %d, taps %d / %d, causal %d / %d, GLU on load (ldz) %d / %d: the problems must agree in each (D %% 4 == 0, "
+             "<= 4096; symmetric: K odd; GLU on load: symmetric, K <= 15, 256 <= D <= 1024, ldz >= 2 D a multiple of 4)",
+             a->D, b->D, a->K, b->K, a->left_fill != nullptr, b->left_fill != nullptr, a->ldz, b->ldz);
+  M3_REQUIRE(!ranges_overlap(a->out, (size_t)a->B * a->T * a->D * 4, b->out, (size_t)b->B * b->T * b->D * 4), "dwconv pair: the two outputs overlap");
+  return launch_dwconv_ln_silu_dual(q[0], q[1], (hipStream_t)stream);
+}
+int m3_subsample_conv1_pair(const m3_conv1_desc* a, const m3_conv1_desc* b, m3_stream stream) {
+  M3_REQUIRE(a != nullptr && b != nullptr, "conv1 pair: null descriptor");
+  const m3_conv1_desc* const ds[2] = {a, b};
+  Conv1Args q[2];
+  size_t bytes[2];
+  for (int i = 0; i < 2; ++i) {
+    const m3_conv1_desc* d = ds[i];
+    M3_REQUIRE(d->feat && d->w9c && d->bias && d->out, "conv1 pair: null feat / w9c / bias / out");
+    M3_REQUIRE(d->act == M3_ACT_NONE || d->act == M3_ACT_RELU, "conv1 pair: act %d (none / relu)", d->act);
+    M3_REQUIRE((d->cmvn_mean == nullptr) == (d->cmvn_istd == nullptr), "conv1 pair: cmvn mean and istd go together");
+    M3_REQUIRE((d->feat_len == nullptr) == (d->lens_out == nullptr) && (i == 0 || d->feat_len == nullptr),
+               "conv1 pair: feat_len and lens_out go together, on the first problem only");
+    M3_REQUIRE(d->B > 0 && d->T >= 3 && d->idim >= 3, "conv1 pair: input (B=%d, T=%d, idim=%d) shorter than the 3x3 kernel", d->B, d->T, d->idim);
+    M3_REQUIRE(d->C > 0 && (d->C & 3) == 0 && d->C <= 1024, "conv1 pair: channels=%d must be a multiple of 4 (<= 1024)", d->C);
+    q[i].feat = d->feat; q[i].w9c = d->w9c; q[i].bias = d->bias; q[i].cmvn_mean = d->cmvn_mean; q[i].cmvn_istd = d->cmvn_istd;
+    q[i].B = d->B; q[i].T = d->T; q[i].idim = d->idim; q[i].C = d->C; q[i].out = d->out; q[i].relu = d->act == M3_ACT_RELU;
+    q[i].feat_len = d->feat_len; q[i].lens_out = d->lens_out;
+    bytes[i] = (size_t)d->B * ((d->T - 3) / 2 + 1) * ((d->idim - 3) / 2 + 1) * d->C * sizeof(float);
+  }
+  M3_REQUIRE(a->B == b->B && a->T == b->T && a->idim == b->idim, "conv1 pair: the two problems do not share an input shape (B %d / %d, T %d / %d, idim %d / %d)",
+             a->B, b->B, a->T, b->T, a->idim, b->idim);
+  M3_REQUIRE(!ranges_overlap(a->out, bytes[0], b->out, bytes[1]), "conv1 pair: the two outputs overlap");
+  return launch_conv1_relu_dual(q[0], q[1], (hipStream_t)stream);
 }
 
 int m3_att_masked_softmax(const float* scores, const int32_t* len, int B, int H, int T1, int T2, float scale,

@@ -40,6 +40,30 @@ class LinearDesc(C.Structure):  # m3_linear_desc
                 ("y_copy_stats", C.c_void_p), ("ln_stats", C.c_void_p), ("ln_stat_parts", C.c_int32)]
 
 
+class Conv2dDesc(C.Structure):  # m3_conv2d_desc
+    _fields_ = [("inp", C.c_void_p), ("w", C.c_void_p), ("bias", C.c_void_p),
+                ("B", C.c_int32), ("T1", C.c_int32), ("F1", C.c_int32), ("C", C.c_int32), ("act", C.c_int32), ("out", C.c_void_p)]
+
+
+class AttentionDesc(C.Structure):  # m3_attention_desc
+    _fields_ = [("qkv", C.c_void_p), ("ldq", C.c_int32), ("p", C.c_void_p), ("ldp", C.c_int32),
+                ("pos_u", C.c_void_p), ("pos_v", C.c_void_p), ("len", C.c_void_p),
+                ("B", C.c_int32), ("T", C.c_int32), ("H", C.c_int32), ("dk", C.c_int32), ("scale", C.c_float),
+                ("chunk", C.c_int32), ("left_chunks", C.c_int32), ("out", C.c_void_p), ("ldo", C.c_int32)]
+
+
+class DwconvDesc(C.Structure):  # m3_dwconv_desc
+    _fields_ = [("z", C.c_void_p), ("ldz", C.c_int32), ("gate_sigmoided", C.c_int32),
+                ("w_kc", C.c_void_p), ("bias", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("eps", C.c_float),
+                ("left_fill", C.c_void_p), ("B", C.c_int32), ("T", C.c_int32), ("D", C.c_int32), ("K", C.c_int32), ("out", C.c_void_p)]
+
+
+class Conv1Desc(C.Structure):  # m3_conv1_desc
+    _fields_ = [("feat", C.c_void_p), ("w9c", C.c_void_p), ("bias", C.c_void_p), ("cmvn_mean", C.c_void_p), ("cmvn_istd", C.c_void_p),
+                ("B", C.c_int32), ("T", C.c_int32), ("idim", C.c_int32), ("C", C.c_int32), ("act", C.c_int32), ("out", C.c_void_p),
+                ("feat_len", C.c_void_p), ("lens_out", C.c_void_p)]
+
+
 class EngineConfig(C.Structure):  # m3_engine_config
     _fields_ = [(n, C.c_int32) for n in (
         "input_dim", "output_dim", "attention_dim", "attention_heads", "num_blocks",
@@ -153,6 +177,15 @@ SIGNATURES = {
     "m3_linear_workspace_size": (_sz, [_P(LinearDesc)]),
     "m3_linear_kernel": (C.c_char_p, [_P(LinearDesc), _i]),
     "m3_linear_ws": (_i, [_P(LinearDesc), _vp, _sz, _vp]),
+    "m3_linear_pair": (_i, [_P(LinearDesc), _P(LinearDesc), _vp]),
+    "m3_linear_ws_pair": (_i, [_P(LinearDesc), _vp, _sz, _P(LinearDesc), _vp, _sz, _i, _vp]),
+    "m3_linear_pair_kernel": (C.c_char_p, [_P(LinearDesc), _P(LinearDesc), _i]),
+    "m3_conv2d_3x3s2_workspace_size": (_sz, [_i, _i, _i, _i, _i]),
+    "m3_conv2d_3x3s2_ws": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "m3_conv2d_3x3s2_ws_pair": (_i, [_P(Conv2dDesc), _vp, _sz, _P(Conv2dDesc), _vp, _sz, _i, _vp]),
+    "m3_relpos_attention_pair": (_i, [_P(AttentionDesc), _P(AttentionDesc), _vp]),
+    "m3_dwconv_ln_silu_pair": (_i, [_P(DwconvDesc), _P(DwconvDesc), _vp]),
+    "m3_subsample_conv1_pair": (_i, [_P(Conv1Desc), _P(Conv1Desc), _vp]),
     "m3_conv2d_3x3s2_first": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "m3_conv2d_3x3s2": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "m3_layer_norm": (_i, [_vp, _vp, _vp, _f, _vp, _i, _i, _vp]),

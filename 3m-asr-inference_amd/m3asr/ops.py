@@ -273,7 +273,7 @@ def moe_route_expert_ffn(x, logits, w1, b1, w2, b2, row_len=None, rows_per_batch
 # ---------------------------------------------------------------------------------------- dense
 def linear(a, w, bias=None, act=_lib.ACT_NONE, a2=None, ln=None, lens=None, rows_per_batch=0, mask_in=False,
            mask_out=False, alpha=1.0, resid=None, out=None, ln_folded=None, split_k=False, out_dtype=torch.float32,
-           copy_bf16=None, copy_stats=None, ln_stats=None, workspace=None, _kernel_only=False):
+           copy_bf16=None, copy_stats=None, ln_stats=None, workspace=None, _kernel_only=False, _desc_only=False):
     """y = resid + alpha * mask_out(act(LN(mask_in(cat[a,a2])) @ w^T + bias)); a (M,K1), w (N,K).
     ln = (gamma, beta, eps): affine LayerNorm prologue.  ln_folded = (wsum, wbeta or None, eps): w / bias already
     contain the LayerNorm affine (plan.fold_layernorm) and the kernel normalises its output.
@@ -326,6 +326,8 @@ def linear(a, w, bias=None, act=_lib.ACT_NONE, a2=None, ln=None, lens=None, rows
     d.act, d.alpha = act, float(alpha)
     if resid is not None:
         d.resid, d.ldr = resid.data_ptr(), resid.stride(0)
+    if _desc_only:
+        return d, y
     if _kernel_only:
         name = lib.m3_linear_kernel(C.byref(d), int(bool(split_k)))
         return name.decode() if name else None
@@ -342,6 +344,117 @@ def linear(a, w, bias=None, act=_lib.ACT_NONE, a2=None, ln=None, lens=None, rows
 def linear_kernel(*args, **kw):
     """name of the device kernel linear(*args, **kw) would run (host-only query, m3_linear_kernel); None if it is rejected"""
     return linear(*args, _kernel_only=True, **kw)
+
+
+# ---- the paired launches (include/m3asr.h "paired launches"): each problem is given as the keyword dict of its single wrapper
+def _linear_desc(kw):
+    kw = dict(kw)
+    return linear(kw.pop("a"), kw.pop("w"), _desc_only=True, **kw)
+
+
+def linear_workspace_size(**kw):
+    """m3_linear_workspace_size of linear(**kw): bytes of split-K scratch, 0 where the problem is no split-K problem"""
+    return _lib.load().m3_linear_workspace_size(C.byref(_linear_desc(kw)[0]))
+
+
+def linear_pair(a, b):
+    """linear(**a) and linear(**b) in one launch (m3_linear_pair); returns (y_a, y_b)"""
+    (da, ya), (db, yb) = _linear_desc(a), _linear_desc(b)
+    check(_lib.load().m3_linear_pair(C.byref(da), C.byref(db), _stream()), "m3_linear_pair")
+    return ya, yb
+
+
+def linear_pair_kernel(a, b, with_workspace=False):
+    """label of the paired kernel (host-only query, m3_linear_pair_kernel); None if the pair is refused"""
+    name = _lib.load().m3_linear_pair_kernel(C.byref(_linear_desc(a)[0]), C.byref(_linear_desc(b)[0]), int(bool(with_workspace)))
+    return name.decode() if name else None
+
+
+def linear_ws_pair(a, ws_a, b, ws_b, which=3):
+    """two split-K problems in one GEMM launch (which & 1) and one reduce launch (which & 2): m3_linear_ws_pair.  ws_a / ws_b:
+    uint8 scratch of at least linear_workspace_size bytes each."""
+    (da, ya), (db, yb) = _linear_desc(a), _linear_desc(b)
+    check(_lib.load().m3_linear_ws_pair(C.byref(da), _p(ws_a), ws_a.numel(), C.byref(db), _p(ws_b), ws_b.numel(), int(which), _stream()),
+          "m3_linear_ws_pair")
+    return ya, yb
+
+
+def _attention_desc(qkv, p, pos_u, pos_v, lens, B, T, H, dk, chunk=0, left_chunks=-1, out=None):
+    D = H * dk
+    if out is None:
+        out = torch.empty(B * T, D, dtype=torch.float32, device=qkv.device)
+    assert tuple(qkv.shape) == (B * T, 3 * D) and tuple(p.shape)[1] == D and p.shape[0] >= T and tuple(out.shape) == (B * T, D)
+    d = _lib.AttentionDesc()
+    (d.qkv, d.ldq), (d.p, d.ldp), (d.out, d.ldo) = [(q.value, ld) for q, ld in (_rows(qkv), _rows(p), _rows(out))]
+    d.pos_u, d.pos_v, d.len = _f32(pos_u).value, _f32(pos_v).value, (_i32(lens).value if lens is not None else None)
+    d.B, d.T, d.H, d.dk, d.scale, d.chunk, d.left_chunks = B, T, H, dk, 1.0 / math.sqrt(dk), int(chunk), int(left_chunks)
+    return d, out
+
+
+def relpos_attention_pair(a, b):
+    """relpos_attention(**a) and relpos_attention(**b) in one launch (m3_relpos_attention_pair); returns (out_a, out_b)"""
+    (da, oa), (db, ob) = _attention_desc(**a), _attention_desc(**b)
+    check(_lib.load().m3_relpos_attention_pair(C.byref(da), C.byref(db), _stream()), "m3_relpos_attention_pair")
+    return oa, ob
+
+
+def _dwconv_desc(z, w_kc, bias, gamma, beta, eps, B, T, out=None, left_fill=None, glu=False, gate_sigmoided=False):
+    K, D = w_kc.shape
+    d = _lib.DwconvDesc()
+    if glu:                      # z: value | gate rows, may be a row-strided view
+        assert tuple(z.shape) == (B * T, 2 * D)
+        zp, d.ldz = _rows(z)
+        d.z = zp.value
+    else:
+        assert z.numel() == B * T * D
+        d.z = _f32(z).value
+    d.gate_sigmoided = int(bool(gate_sigmoided))
+    if out is None:
+        out = torch.empty(B * T, D, dtype=torch.float32, device=z.device)
+    d.w_kc, d.bias, d.out = _f32(w_kc).value, _f32(bias).value, _f32(out).value
+    d.gamma, d.beta = (_f32(gamma).value if gamma is not None else None), (_f32(beta).value if beta is not None else None)
+    d.left_fill = _f32(left_fill).value if left_fill is not None else None
+    d.eps, d.B, d.T, d.D, d.K = float(eps), B, T, D, K
+    return d, out
+
+
+def dwconv_ln_silu_pair(a, b):
+    """two depthwise conv + LayerNorm + SiLU problems in one launch (m3_dwconv_ln_silu_pair).  Keys of a / b: z, w_kc, bias, gamma,
+    beta, eps, B, T and optionally out, left_fill (causal), glu (z holds value | gate rows), gate_sigmoided."""
+    (da, oa), (db, ob) = _dwconv_desc(**a), _dwconv_desc(**b)
+    check(_lib.load().m3_dwconv_ln_silu_pair(C.byref(da), C.byref(db), _stream()), "m3_dwconv_ln_silu_pair")
+    return oa, ob
+
+
+def _conv1_desc(feat, w9c, bias, act=_lib.ACT_RELU, cmvn=None, out=None, feat_len=None, lens_out=None):
+    B, T, idim = feat.shape
+    Cc = w9c.shape[1]
+    if out is None:
+        out = torch.empty(B, (T - 3) // 2 + 1, (idim - 3) // 2 + 1, Cc, dtype=torch.float32, device=feat.device)
+    d = _lib.Conv1Desc()
+    d.feat, d.w9c, d.bias, d.out = _f32(feat).value, _f32(w9c).value, _f32(bias).value, _f32(out).value
+    if cmvn is not None:
+        d.cmvn_mean, d.cmvn_istd = _f32(cmvn[0]).value, _f32(cmvn[1]).value
+    d.B, d.T, d.idim, d.C, d.act = B, T, idim, Cc, int(act)
+    if feat_len is not None:
+        d.feat_len, d.lens_out = _i32(feat_len).value, _i32(lens_out).value
+    return d, out
+
+
+def subsample_conv1_pair(a, b):
+    """two first convs on inputs of one shape in one launch (m3_subsample_conv1_pair).  Keys of a / b: feat, w9c, bias and
+    optionally act, cmvn = (mean, istd), out, feat_len + lens_out (a only)."""
+    (da, oa), (db, ob) = _conv1_desc(**a), _conv1_desc(**b)
+    check(_lib.load().m3_subsample_conv1_pair(C.byref(da), C.byref(db), _stream()), "m3_subsample_conv1_pair")
+    return oa, ob
+
+
+def subsample_conv1_cmvn(feat, w9c, bias, cmvn, out=None):
+    """conv1 + ReLU with global CMVN folded into the read (m3_subsample_conv1_cmvn); cmvn = (mean, istd)"""
+    d, out = _conv1_desc(feat, w9c, bias, cmvn=cmvn, out=out)
+    check(_lib.load().m3_subsample_conv1_cmvn(d.feat, d.w9c, d.bias, d.cmvn_mean, d.cmvn_istd, d.B, d.T, d.idim, d.C, d.out, _stream()),
+          "m3_subsample_conv1_cmvn")
+    return out
 
 
 def layer_norm(x, gamma, beta, eps):
@@ -386,10 +499,11 @@ def relpos_attention_bf16(qkv, p, pos_u, pos_v, lens, B, T, H, dk, chunk=0, left
     return out
 
 
-def dwconv_ln_silu(z, w_kc, bias, gamma, beta, eps, B, T):
+def dwconv_ln_silu(z, w_kc, bias, gamma, beta, eps, B, T, out=None):
     lib = _lib.load()
     K, D = w_kc.shape
-    out = torch.empty_like(z)
+    if out is None:
+        out = torch.empty_like(z)
     check(lib.m3_dwconv_ln_silu(_f32(z), _f32(w_kc), _f32(bias), _f32(gamma), _f32(beta), float(eps), B, T, D, K,
                                 _p(out), _stream()), "m3_dwconv_ln_silu")
     return out
@@ -454,13 +568,15 @@ def dwconv_ln_silu_causal(z, w_kc, bias, gamma, beta, eps, left_fill, B, T, out=
     return out
 
 
-def subsample_conv1(feat, w9c, bias, act=_lib.ACT_RELU):
+def subsample_conv1(feat, w9c, bias, act=_lib.ACT_RELU, out=None):
     """Conv2d(1, C, 3, stride 2) on (B,T,idim) -> channel-last (B,T1,F1,C); act = ACT_RELU (fused, default) or ACT_NONE."""
     lib = _lib.load()
     B, T, idim = feat.shape
     Cc = w9c.shape[1]
     T1, F1 = (T - 3) // 2 + 1, (idim - 3) // 2 + 1
-    out = torch.empty(B, T1, F1, Cc, dtype=torch.float32, device=feat.device)
+    if out is None:
+        out = torch.empty(B, T1, F1, Cc, dtype=torch.float32, device=feat.device)
+    assert tuple(out.shape) == (B, T1, F1, Cc)
     check(lib.m3_conv2d_3x3s2_first(_f32(feat), _f32(w9c), _f32(bias), B, T, idim, Cc, int(act), _p(out), _stream()),
           "m3_conv2d_3x3s2_first")
     return out
@@ -1209,6 +1325,38 @@ def rel_positional_encoding(x, pe, scale, frame_num=None, max_offset=0):
     check(lib.m3_rel_positional_encoding(_f32(x), _f32(pe2), pe2.shape[0], _i32(frame_num), int(max_offset), float(scale),
                                          B, T, D, _p(y), _p(pos), _p(fn_out), _stream()), "m3_rel_positional_encoding")
     return (y, pos) if frame_num is None else (y, pos, fn_out)
+
+
+def _conv2d_desc(x, w, bias, act=_lib.ACT_RELU, out=None):
+    B, T1, F1, Cc = x.shape
+    if out is None:
+        out = torch.empty(B, (T1 - 3) // 2 + 1, (F1 - 3) // 2 + 1, Cc, dtype=torch.float32, device=x.device)
+    d = _lib.Conv2dDesc()
+    d.inp, d.w, d.bias, d.out = _f32(x).value, _f32(w).value, (_f32(bias).value if bias is not None else None), _f32(out).value
+    d.B, d.T1, d.F1, d.C, d.act = B, T1, F1, Cc, int(act)
+    return d, out
+
+
+def conv2d_workspace_size(B, T1, F1, Cc, act=_lib.ACT_RELU):
+    """bytes of split-K scratch subsample_conv2_ws takes for this shape (m3_conv2d_3x3s2_workspace_size); 0: no split-K problem"""
+    return _lib.load().m3_conv2d_3x3s2_workspace_size(B, T1, F1, Cc, int(act))
+
+
+def subsample_conv2_ws(x, w, bias, workspace, act=_lib.ACT_RELU, out=None):
+    """subsample_conv2 with a caller-owned uint8 workspace (m3_conv2d_3x3s2_ws): split-K where the shape takes it"""
+    d, out = _conv2d_desc(x, w, bias, act, out)
+    check(_lib.load().m3_conv2d_3x3s2_ws(d.inp, d.w, d.bias, d.B, d.T1, d.F1, d.C, d.act, d.out, _p(workspace),
+                                         workspace.numel() if workspace is not None else 0, _stream()), "m3_conv2d_3x3s2_ws")
+    return out
+
+
+def subsample_conv2_ws_pair(a, ws_a, b, ws_b, which=3):
+    """two split-K implicit convs in one GEMM launch and one reduce launch (m3_conv2d_3x3s2_ws_pair).  Keys of a / b: x, w, bias
+    and optionally act, out."""
+    (da, oa), (db, ob) = _conv2d_desc(**a), _conv2d_desc(**b)
+    check(_lib.load().m3_conv2d_3x3s2_ws_pair(C.byref(da), _p(ws_a), ws_a.numel(), C.byref(db), _p(ws_b), ws_b.numel(), int(which),
+                                              _stream()), "m3_conv2d_3x3s2_ws_pair")
+    return oa, ob
 
 
 def subsample_conv2(x, w, bias, act=_lib.ACT_RELU):

@@ -389,6 +389,75 @@ int m3_conv2d_3x3s2(const float* in, const float* w, const float* bias, int B, i
 /* second conv (C->C, 3x3, s2) + ReLU as implicit GEMM: in (B,T1,F1,C) -> out (B,T2,F2,C); w [C][3][3][C]. */
 int m3_subsample_conv2(const float* in, const float* w, const float* bias, int B, int T1, int F1, int C,
                        float* out, m3_stream stream);
+/* m3_conv2d_3x3s2 with a caller-owned workspace: deep, few-tile problems (C a multiple of 64, 9 C >= 4096, at most 160 output
+ * tiles of 64 x 64) run as the implicit-conv split-K kernel + fixed-order reduce when m3_conv2d_3x3s2_workspace_size(...) > 0
+ * bytes are provided; otherwise identical to m3_conv2d_3x3s2 (the size query answers 0 for such a problem). */
+size_t m3_conv2d_3x3s2_workspace_size(int B, int T1, int F1, int C, int act);
+int m3_conv2d_3x3s2_ws(const float* in, const float* w, const float* bias, int B, int T1, int F1, int C, int act, float* out,
+                       void* workspace, size_t workspace_bytes, m3_stream stream);
+
+/* The paired launches of the B = 1 fp32 engine (two INDEPENDENT problems of one operator in one launch: a stage of the embed
+ * encoder next to a stage of the main encoder's prefix), exposed so that they can be tested at the boundary (additions only;
+ * tests/test_pair_kernels_gpu.py).  Each entry checks both problems as the single entry of the operator does, requires that the
+ * two outputs do not overlap, and makes ONE launcher call; each half of the result is what the single entry gives on the same
+ * operands, bit for bit.  A pair the kernels have no common instantiation for returns a non-zero status with the reason in
+ * m3_last_error() and launches nothing.
+ *
+ * m3_linear_pair: two m3_linear problems that both plan as the skinny fp32 kernel with 16-row tiles (M <= 128, or few enough
+ * tiles), 4 or 8 waves (K < 2048) and one load group per wave (K <= 512, or K = 1024), plain `a`, no affine LayerNorm, and that
+ * agree in the wave count (K < 1024 / K >= 1024), in GLU or not and in folded LayerNorm or not.  M, N, K, strides and every
+ * other epilogue field may differ.
+ * m3_linear_ws_pair: two m3_linear_ws problems that both plan as split-K with their workspaces (bytes_x >=
+ * m3_linear_workspace_size(x) > 0; the workspaces must not overlap).  which: 1 = the GEMM launch, 2 = the reduce launch,
+ * 3 = both.
+ * m3_linear_pair_kernel: host only; the label of the kernel m3_linear_pair (with_workspace = 0) or m3_linear_ws_pair given both
+ * workspaces (1) runs, NULL with the reason in m3_last_error() for a pair they refuse. */
+int m3_linear_pair(const m3_linear_desc* a, const m3_linear_desc* b, m3_stream stream);
+int m3_linear_ws_pair(const m3_linear_desc* a, void* workspace_a, size_t bytes_a, const m3_linear_desc* b, void* workspace_b,
+                      size_t bytes_b, int which, m3_stream stream);
+const char* m3_linear_pair_kernel(const m3_linear_desc* a, const m3_linear_desc* b, int with_workspace);
+/* m3_conv2d_3x3s2_ws_pair: two m3_conv2d_3x3s2_ws problems that both run as split-K (which: as above). */
+typedef struct m3_conv2d_desc {
+  const float* in; const float* w; const float* bias;
+  int32_t B, T1, F1, C, act;
+  float* out;
+} m3_conv2d_desc;
+int m3_conv2d_3x3s2_ws_pair(const m3_conv2d_desc* a, void* workspace_a, size_t bytes_a, const m3_conv2d_desc* b, void* workspace_b,
+                            size_t bytes_b, int which, m3_stream stream);
+/* m3_relpos_attention_pair: two m3_relpos_attention_chunk problems, each with dk 64 or 128 (the four combinations). */
+typedef struct m3_attention_desc {
+  const float* qkv; int32_t ldq;
+  const float* p; int32_t ldp;
+  const float* pos_u; const float* pos_v;
+  const int32_t* len;
+  int32_t B, T, H, dk;
+  float scale;
+  int32_t chunk, left_chunks;
+  float* out; int32_t ldo;
+} m3_attention_desc;
+int m3_relpos_attention_pair(const m3_attention_desc* a, const m3_attention_desc* b, m3_stream stream);
+/* m3_dwconv_ln_silu_pair: two depthwise conv + LayerNorm + SiLU problems with the same D, K and causality.  ldz = 0: z is the
+ * dense [B*T][D] input of m3_dwconv_ln_silu (left_fill NULL) or m3_dwconv_ln_silu_causal (left_fill [D]); ldz > 0: z is the
+ * value | gate rows of m3_dwconv_glu_ln_silu (both problems then), and with gate_sigmoided != 0 its gate columns hold
+ * sigmoid(gate) already (every tap is value * gate'; no single entry has this form).  gamma / beta NULL: no LayerNorm. */
+typedef struct m3_dwconv_desc {
+  const float* z; int32_t ldz; int32_t gate_sigmoided;
+  const float* w_kc; const float* bias; const float* gamma; const float* beta; float eps;
+  const float* left_fill;
+  int32_t B, T, D, K;
+  float* out;
+} m3_dwconv_desc;
+int m3_dwconv_ln_silu_pair(const m3_dwconv_desc* a, const m3_dwconv_desc* b, m3_stream stream);
+/* m3_subsample_conv1_pair: two first convs (m3_conv2d_3x3s2_first / m3_subsample_conv1_cmvn) on inputs of the same B, T and
+ * idim; act = M3_ACT_NONE or M3_ACT_RELU, cmvn_mean / cmvn_istd NULL or both given.  feat_len / lens_out (first problem only,
+ * NULL or both given): the launch also writes lens_out[b] = ((feat_len[b] - 3) / 2 + 1 - 3) / 2 + 1, b < B. */
+typedef struct m3_conv1_desc {
+  const float* feat; const float* w9c; const float* bias; const float* cmvn_mean; const float* cmvn_istd;
+  int32_t B, T, idim, C, act;
+  float* out;
+  const int32_t* feat_len; int32_t* lens_out;
+} m3_conv1_desc;
+int m3_subsample_conv1_pair(const m3_conv1_desc* a, const m3_conv1_desc* b, m3_stream stream);
 
 /* Front / back end of the acoustic score.  Global CMVN: y = (x - mean[d]) * istd[d] on frames
  * t < len[b] (the reference's unfinished CmvnPlugin, incomplete_plugin/cmvn_plugin/cmvn_plugin.cu:17-43).
