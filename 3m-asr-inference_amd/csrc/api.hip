@@ -257,12 +257,28 @@ int m3_moe_route_expert_ffn(const float* x, int ldx, const float* logits, const 
                             alpha, ln_gamma, ln_beta, ln_eps, y, S, idim, (hipStream_t)stream);
 }
 
-// what the three attention entry points ask of their row operands besides the multiples the launchers check (include/m3asr.h)
-static int attention_operands(const void* qkv, int ldq, const void* p, int ldp, const void* out, int ldo, int B, int T, int H, int dk) {
-  M3_REQUIRE(B * T <= 1 || (ldq >= 3 * H * dk && ldo >= H * dk), "attention: ldq=%d / ldo=%d shorter than the rows (%d / %d)", ldq, ldo, 3 * H * dk, H * dk);
-  M3_REQUIRE(T <= 1 || ldp >= H * dk, "attention: ldp=%d is shorter than a row of %d", ldp, H * dk);
-  M3_REQUIRE(aligned16(qkv) && aligned16(p) && aligned16(out), "attention: qkv / p / out must be 16-byte aligned");
+// The attention core at the boundary: the record from the ABI descriptor plus what only the boundary asks of the row operands
+// besides the multiples the launcher checks (include/m3asr.h).  pair < 0: a single entry; 0 / 1: a problem of m3_relpos_attention_pair.
+static int attention_args_from_desc(const m3_attention_desc* d, const char* who, int pair, AttArgs* q) {
+  if (pair >= 0) M3_REQUIRE(d->B > 0 && d->T > 0 && d->H > 0 && d->dk > 0, "%s: empty problem %d", who, pair);
+  M3_REQUIRE((pair < 0 && (d->B <= 0 || d->T <= 0 || d->H <= 0)) || (d->qkv && d->p && d->pos_u && d->pos_v && d->out),
+             "%s: null qkv / p / pos_u / pos_v / out", who);
+  M3_REQUIRE(d->B * d->T <= 1 || (d->ldq >= 3 * d->H * d->dk && d->ldo >= d->H * d->dk), "attention: ldq=%d / ldo=%d shorter than the rows (%d / %d)",
+             d->ldq, d->ldo, 3 * d->H * d->dk, d->H * d->dk);
+  M3_REQUIRE(d->T <= 1 || d->ldp >= d->H * d->dk, "attention: ldp=%d is shorter than a row of %d", d->ldp, d->H * d->dk);
+  M3_REQUIRE(aligned16(d->qkv) && aligned16(d->p) && aligned16(d->out), "attention: qkv / p / out must be 16-byte aligned");
+  q->qkv = d->qkv; q->ldq = d->ldq; q->pmat = d->p; q->ldp = d->ldp; q->pos_u = d->pos_u; q->pos_v = d->pos_v; q->row_len = d->len;
+  q->B = d->B; q->T = d->T; q->H = d->H; q->dk = d->dk; q->scale = d->scale; q->out = d->out; q->ldo = d->ldo; q->chunk = d->chunk;
+  q->left_chunks = d->left_chunks;
   return 0;
+}
+static int attention_single(const void* qkv, int ldq, const float* p, int ldp, const float* pos_u, const float* pos_v, const int32_t* len, int B, int T,
+                            int H, int dk, float scale, int chunk, int left_chunks, void* out, int ldo, int rows_bf16, m3_stream stream) {
+  const m3_attention_desc d = {(const float*)qkv, ldq, p, ldp, pos_u, pos_v, len, B, T, H, dk, scale, chunk, left_chunks, (float*)out, ldo};
+  AttArgs a;
+  if (int rc = attention_args_from_desc(&d, "attention", -1, &a)) return rc;
+  a.rows_bf16 = rows_bf16;
+  return launch_relpos_attention(a, (hipStream_t)stream);
 }
 
 static int linear_params(const m3_linear_desc* d, GemmParams* out) {
@@ -338,38 +354,56 @@ int m3_layer_norm(const float* x, const float* gamma, const float* beta, float e
 int m3_relpos_attention(const float* qkv, int ldq, const float* p, int ldp, const float* pos_u, const float* pos_v,
                         const int32_t* len, int B, int T, int H, int dk, float scale, float* out, int ldo,
                         m3_stream stream) {
-  if (int rc = attention_operands(qkv, ldq, p, ldp, out, ldo, B, T, H, dk)) return rc;
-  return launch_relpos_attention(qkv, ldq, p, ldp, pos_u, pos_v, len, B, T, H, dk, scale, out, ldo,
-                                 (hipStream_t)stream);
+  return attention_single(qkv, ldq, p, ldp, pos_u, pos_v, len, B, T, H, dk, scale, 0, -1, out, ldo, 0, stream);
 }
 int m3_relpos_attention_bf16(const void* qkv, int ldq, const float* p, int ldp, const float* pos_u, const float* pos_v,
                              const int32_t* len, int B, int T, int H, int dk, float scale, int chunk, int left_chunks,
                              void* out, int ldo, m3_stream stream) {
-  if (int rc = attention_operands(qkv, ldq, p, ldp, out, ldo, B, T, H, dk)) return rc;
-  return launch_relpos_attention_bf16(qkv, ldq, p, ldp, pos_u, pos_v, len, B, T, H, dk, scale, out, ldo, (hipStream_t)stream,
-                                      nullptr, chunk, left_chunks);
+  return attention_single(qkv, ldq, p, ldp, pos_u, pos_v, len, B, T, H, dk, scale, chunk, left_chunks, out, ldo, 1, stream);
 }
 int m3_relpos_attention_chunk(const float* qkv, int ldq, const float* p, int ldp, const float* pos_u, const float* pos_v,
                               const int32_t* len, int B, int T, int H, int dk, float scale, int chunk, int left_chunks,
                               float* out, int ldo, m3_stream stream) {
-  if (int rc = attention_operands(qkv, ldq, p, ldp, out, ldo, B, T, H, dk)) return rc;
-  return launch_relpos_attention(qkv, ldq, p, ldp, pos_u, pos_v, len, B, T, H, dk, scale, out, ldo, (hipStream_t)stream, 0,
-                                 nullptr, chunk, left_chunks);
+  return attention_single(qkv, ldq, p, ldp, pos_u, pos_v, len, B, T, H, dk, scale, chunk, left_chunks, out, ldo, 0, stream);
+}
+// The depthwise conv at the boundary: the record from the ABI descriptor plus what only the boundary asks.  pair < 0: a single entry
+// (`who` in its messages), which takes an empty batch as a launch of nothing; pair = 0 / 1: a problem of m3_dwconv_ln_silu_pair.
+// zname: what the entry calls z.  strict: the entry asks for 16-byte aligned operands and for gamma and beta together
+// (m3_dwconv_ln_silu, the oldest entry, never did: it refuses only what the kernel would dereference as a null pointer).
+static int dwconv_args_from_desc(const m3_dwconv_desc* d, const char* who, const char* zname, int pair, bool strict, DwArgs* q) {
+  if (pair >= 0) M3_REQUIRE(d->B > 0 && d->T > 0 && d->D > 0 && d->K > 0, "%s: empty problem %d", who, pair);
+  const bool ln_ok = strict ? (d->gamma == nullptr) == (d->beta == nullptr) : (d->gamma == nullptr || d->beta != nullptr);
+  M3_REQUIRE((pair < 0 && (d->B <= 0 || d->T <= 0)) || (d->z && d->w_kc && d->bias && d->out && ln_ok),
+             "%s: null %s / w_kc / bias / out, or gamma without beta", who, zname);
+  M3_REQUIRE(!strict || (aligned16(d->z) && aligned16(d->w_kc) && aligned16(d->bias) && aligned16(d->gamma) && aligned16(d->beta) &&
+                          aligned16(d->left_fill) && aligned16(d->out)), "%s: every operand must be 16-byte aligned", who);
+  if (pair >= 0) {   // (a single entry has no gate_sigmoided, and hears the launcher's words about K)
+    M3_REQUIRE(d->ldz >= 0 && (d->ldz > 0 || !d->gate_sigmoided), "%s: ldz=%d (sigmoided gate columns belong to the GLU-on-load form)", who, d->ldz);
+    M3_REQUIRE(d->left_fill == nullptr || d->K >= 2, "%s: the causal conv needs K >= 2", who);
+  }
+  q->z = d->z; q->glu_ldz = d->ldz; q->glu_sig = d->gate_sigmoided != 0; q->w_kc = d->w_kc; q->bias = d->bias; q->gamma = d->gamma;
+  q->beta = d->beta; q->eps = d->eps; q->causal_left_fill = d->left_fill; q->B = d->B; q->T = d->T; q->D = d->D; q->K = d->K; q->out = d->out;
+  return 0;
+}
+static m3_dwconv_desc dwconv_desc(const float* z, int ldz, const float* w_kc, const float* bias, const float* gamma, const float* beta, float eps,
+                                  const float* left_fill, int B, int T, int D, int K, float* out) {
+  return m3_dwconv_desc{z, ldz, 0, w_kc, bias, gamma, beta, eps, left_fill, B, T, D, K, out};
 }
 int m3_dwconv_ln_silu(const float* z, const float* w_kc, const float* bias, const float* gamma, const float* beta,
                       float eps, int B, int T, int D, int K, float* out, m3_stream stream) {
-  return launch_dwconv_ln_silu(z, w_kc, bias, gamma, beta, eps, B, T, D, K, out, (hipStream_t)stream);
+  const m3_dwconv_desc d = dwconv_desc(z, 0, w_kc, bias, gamma, beta, eps, nullptr, B, T, D, K, out);
+  DwArgs a;
+  if (int rc = dwconv_args_from_desc(&d, "dwconv", "z", -1, false, &a)) return rc;
+  return launch_dwconv_ln_silu(a, (hipStream_t)stream);
 }
 int m3_dwconv_glu_ln_silu(const float* vg, int ldz, const float* w_kc, const float* bias, const float* gamma, const float* beta,
                           float eps, int B, int T, int D, int K, float* out, m3_stream stream) {
   M3_REQUIRE(B > 0 && T > 0, "dwconv (GLU on load): empty problem");
-  M3_REQUIRE(vg && w_kc && bias && out && (gamma == nullptr) == (beta == nullptr), "dwconv (GLU on load): null vg / w_kc / bias / out, or gamma without beta");
-  M3_REQUIRE(aligned16(vg) && aligned16(w_kc) && aligned16(bias) && aligned16(gamma) && aligned16(beta) && aligned16(out),
-             "dwconv (GLU on load): every operand must be 16-byte aligned");
+  const m3_dwconv_desc d = dwconv_desc(vg, ldz, w_kc, bias, gamma, beta, eps, nullptr, B, T, D, K, out);
   DwArgs a;
-  a.z = vg; a.glu_ldz = ldz; a.w_kc = w_kc; a.bias = bias; a.gamma = gamma; a.beta = beta; a.eps = eps; a.B = B; a.T = T; a.D = D; a.K = K; a.out = out;
+  if (int rc = dwconv_args_from_desc(&d, "dwconv (GLU on load)", "vg", -1, true, &a)) return rc;
   M3_REQUIRE(ldz > 0, "dwconv (GLU on load): ldz=%d", ldz);
-  return launch_dwconv_ln_silu_args(a, (hipStream_t)stream);
+  return launch_dwconv_ln_silu(a, (hipStream_t)stream);
 }
 // The stateful launches of the chunk-by-chunk engine (engine.hip "att_stream" / "conv.dw_ln_silu" stages) at the boundary: argument
 // checks and one launcher call each.  What lives on the device (the counters, chunk_len) cannot be checked here.
@@ -385,40 +419,66 @@ int m3_relpos_attention_stream(const float* qkv, int ldq, float* hist, int cap, 
   M3_REQUIRE(p_rows >= C, "attention (stream): a position table of %d rows is shorter than one chunk of %d", p_rows, C);
   M3_REQUIRE(slot_max_chunks < 0 || (long)slot_max_chunks * C <= (long)p_rows,
              "attention (stream, slot mode): %d chunks of %d frames pass the position table's %d rows", slot_max_chunks, C, p_rows);
-  return launch_relpos_attention_stream(qkv, ldq, hist, cap, p, ldp, pos_u, pos_v, chunk_len, step, B, C, H, dk, scale, out, ldo, left_chunks,
-                                        (hipStream_t)stream, slot_max_chunks);
+  AttArgs a;
+  a.qkv = qkv; a.ldq = ldq; a.pmat = p; a.ldp = ldp; a.pos_u = pos_u; a.pos_v = pos_v; a.row_len = chunk_len; a.B = B; a.T = C; a.H = H; a.dk = dk;
+  a.scale = scale; a.out = out; a.ldo = ldo; a.left_chunks = left_chunks;
+  a.streaming = 1; a.hist = hist; a.cap = cap; a.step = step; a.slot_max_chunks = slot_max_chunks;
+  return launch_relpos_attention(a, (hipStream_t)stream);
 }
 int m3_dwconv_ln_silu_stream(const float* z, const float* w_kc, const float* bias, const float* gamma, const float* beta, float eps, int B,
                              int T, int D, int K, float* cache_pair, const int32_t* step, const int32_t* chunk_len, int slot_max_chunks,
                              float* out, m3_stream stream) {
   M3_REQUIRE(B > 0 && T > 0 && D > 0, "dwconv (stream): empty problem");
-  M3_REQUIRE(z && w_kc && bias && out && (gamma == nullptr) == (beta == nullptr), "dwconv (stream): null z / w_kc / bias / out, or gamma without beta");
-  M3_REQUIRE(aligned16(z) && aligned16(w_kc) && aligned16(bias) && aligned16(gamma) && aligned16(beta) && aligned16(cache_pair) && aligned16(out),
-             "dwconv (stream): every operand must be 16-byte aligned");
-  return launch_dwconv_ln_silu_stream(z, w_kc, bias, gamma, beta, eps, B, T, D, K, out, cache_pair, step, chunk_len, (hipStream_t)stream, 0,
-                                      slot_max_chunks);
+  const m3_dwconv_desc d = dwconv_desc(z, 0, w_kc, bias, gamma, beta, eps, nullptr, B, T, D, K, out);
+  DwArgs a;
+  if (int rc = dwconv_args_from_desc(&d, "dwconv (stream)", "z", -1, true, &a)) return rc;
+  M3_REQUIRE(aligned16(cache_pair), "dwconv (stream): every operand must be 16-byte aligned");
+  a.streaming = 1; a.cache_pair = cache_pair; a.step = step; a.chunk_len = chunk_len; a.slot_max_chunks = slot_max_chunks;
+  return launch_dwconv_ln_silu(a, (hipStream_t)stream);
 }
 int m3_dwconv_ln_silu_causal(const float* z, const float* w_kc, const float* bias, const float* gamma, const float* beta, float eps,
                              const float* left_fill, int B, int T, int D, int K, float* out, m3_stream stream) {
-  M3_REQUIRE(z && w_kc && bias && out && (gamma == nullptr) == (beta == nullptr), "dwconv (causal): null z / w_kc / bias / out, or gamma without beta");
+  const m3_dwconv_desc d = dwconv_desc(z, 0, w_kc, bias, gamma, beta, eps, left_fill, B, T, D, K, out);
+  DwArgs a;
   M3_REQUIRE(left_fill != nullptr, "dwconv (causal): left_fill [D], the frame left of frame 0, must be supplied");
-  M3_REQUIRE(aligned16(z) && aligned16(w_kc) && aligned16(bias) && aligned16(gamma) && aligned16(beta) && aligned16(left_fill) && aligned16(out),
-             "dwconv (causal): every operand must be 16-byte aligned");
-  return launch_dwconv_ln_silu(z, w_kc, bias, gamma, beta, eps, B, T, D, K, out, (hipStream_t)stream, 0, nullptr, nullptr, nullptr, left_fill);
+  if (int rc = dwconv_args_from_desc(&d, "dwconv (causal)", "z", -1, true, &a)) return rc;
+  return launch_dwconv_ln_silu(a, (hipStream_t)stream);
+}
+// The first conv at the boundary: the record from the ABI descriptor plus what only the boundary asks.  pair < 0: a single entry
+// (`who` in its messages), which takes an empty batch as a launch of nothing; pair = 0 / 1: a problem of m3_subsample_conv1_pair.
+static int conv1_args_from_desc(const m3_conv1_desc* d, const char* who, int pair, Conv1Args* q) {
+  M3_REQUIRE((pair < 0 && d->B <= 0) || (d->feat && d->w9c && d->bias && d->out), "%s: null feat / w9c / bias / out", who);
+  M3_REQUIRE(d->act == M3_ACT_NONE || d->act == M3_ACT_RELU, "%s: act %d (none / relu)", who, d->act);
+  M3_REQUIRE((d->cmvn_mean == nullptr) == (d->cmvn_istd == nullptr), "%s: cmvn mean and istd go together", who);
+  M3_REQUIRE((d->feat_len == nullptr) == (d->lens_out == nullptr) && (pair <= 0 || d->feat_len == nullptr),
+             "%s: feat_len and lens_out go together, on the first problem only", who);
+  if (pair >= 0) {   // (the words of the pair entry; a single entry hears the launcher's)
+    M3_REQUIRE(d->B > 0 && d->T >= 3 && d->idim >= 3, "%s: input (B=%d, T=%d, idim=%d) shorter than the 3x3 kernel", who, d->B, d->T, d->idim);
+    M3_REQUIRE(d->C > 0 && (d->C & 3) == 0 && d->C <= 1024, "%s: channels=%d must be a multiple of 4 (<= 1024)", who, d->C);
+  }
+  q->feat = d->feat; q->w9c = d->w9c; q->bias = d->bias; q->cmvn_mean = d->cmvn_mean; q->cmvn_istd = d->cmvn_istd;
+  q->B = d->B; q->T = d->T; q->idim = d->idim; q->C = d->C; q->out = d->out; q->relu = d->act == M3_ACT_RELU;
+  q->feat_len = d->feat_len; q->lens_out = d->lens_out;
+  return 0;
+}
+static int conv1_single(const char* who, const float* feat, const float* w9c, const float* bias, const float* cmvn_mean, const float* cmvn_istd,
+                        int B, int T, int idim, int C, int act, float* out, m3_stream stream) {
+  const m3_conv1_desc d = {feat, w9c, bias, cmvn_mean, cmvn_istd, B, T, idim, C, act, out, nullptr, nullptr};
+  Conv1Args q;
+  if (int rc = conv1_args_from_desc(&d, who, -1, &q)) return rc;
+  return launch_conv1_relu(q, (hipStream_t)stream);
 }
 int m3_subsample_conv1(const float* feat, const float* w9c, const float* bias, int B, int T, int idim, int C,
                        float* out, m3_stream stream) {
-  return launch_conv1_relu(feat, w9c, bias, nullptr, nullptr, B, T, idim, C, out, (hipStream_t)stream);
+  return conv1_single("subsample_conv1", feat, w9c, bias, nullptr, nullptr, B, T, idim, C, M3_ACT_RELU, out, stream);
 }
 int m3_subsample_conv1_cmvn(const float* feat, const float* w9c, const float* bias, const float* cmvn_mean,
                             const float* cmvn_istd, int B, int T, int idim, int C, float* out, m3_stream stream) {
-  M3_REQUIRE((cmvn_mean == nullptr) == (cmvn_istd == nullptr), "subsample_conv1: cmvn mean and istd go together");
-  return launch_conv1_relu(feat, w9c, bias, cmvn_mean, cmvn_istd, B, T, idim, C, out, (hipStream_t)stream);
+  return conv1_single("subsample_conv1", feat, w9c, bias, cmvn_mean, cmvn_istd, B, T, idim, C, M3_ACT_RELU, out, stream);
 }
 int m3_conv2d_3x3s2_first(const float* feat, const float* w9c, const float* bias, int B, int T, int idim, int C, int act,
                           float* out, m3_stream stream) {
-  M3_REQUIRE(act == M3_ACT_NONE || act == M3_ACT_RELU, "conv2d: act %d (none / relu)", act);
-  return launch_conv1_relu(feat, w9c, bias, nullptr, nullptr, B, T, idim, C, out, (hipStream_t)stream, act == M3_ACT_RELU);
+  return conv1_single("conv2d", feat, w9c, bias, nullptr, nullptr, B, T, idim, C, act, out, stream);
 }
 int m3_cmvn(const float* x, const int32_t* len, const float* mean, const float* istd, int B, int T, int D, float* y,
             m3_stream stream) {
@@ -544,71 +604,38 @@ int m3_conv2d_3x3s2_ws_pair(const m3_conv2d_desc* a, void* workspace_a, size_t b
 }
 int m3_relpos_attention_pair(const m3_attention_desc* a, const m3_attention_desc* b, m3_stream stream) {
   M3_REQUIRE(a != nullptr && b != nullptr, "attention pair: null descriptor");
-  const m3_attention_desc* const ds[2] = {a, b};
-  AttArgs q[2];
-  for (int i = 0; i < 2; ++i) {
-    const m3_attention_desc* d = ds[i];
-    M3_REQUIRE(d->B > 0 && d->T > 0 && d->H > 0 && d->dk > 0, "attention pair: empty problem %d", i);
-    M3_REQUIRE(d->qkv && d->p && d->pos_u && d->pos_v && d->out, "attention pair: null qkv / p / pos_u / pos_v / out");
-    if (int rc = attention_operands(d->qkv, d->ldq, d->p, d->ldp, d->out, d->ldo, d->B, d->T, d->H, d->dk)) return rc;
-    q[i].qkv = d->qkv; q[i].ldq = d->ldq; q[i].pmat = d->p; q[i].ldp = d->ldp; q[i].pos_u = d->pos_u; q[i].pos_v = d->pos_v;
-    q[i].row_len = d->len; q[i].B = d->B; q[i].T = d->T; q[i].H = d->H; q[i].dk = d->dk; q[i].scale = d->scale; q[i].out = d->out;
-    q[i].ldo = d->ldo; q[i].chunk = d->chunk; q[i].left_chunks = d->left_chunks;
-  }
-  M3_REQUIRE(relpos_attention_dual_fusable(q[0], q[1]),
+  AttArgs qa, qb;
+  if (int rc = attention_args_from_desc(a, "attention pair", 0, &qa)) return rc;
+  if (int rc = attention_args_from_desc(b, "attention pair", 1, &qb)) return rc;
+  M3_REQUIRE(relpos_attention_dual_fusable(qa, qb),
              "attention pair: head widths %d / %d (64 or 128 each) or row strides ldq %d / %d, ldp %d / %d (multiples of 4) are not a paired instantiation",
              a->dk, b->dk, a->ldq, b->ldq, a->ldp, b->ldp);
   M3_REQUIRE(!ranges_overlap(a->out, rows_bytes((long)a->B * a->T, a->ldo, a->H * a->dk), b->out, rows_bytes((long)b->B * b->T, b->ldo, b->H * b->dk)),
              "attention pair: the two outputs overlap");
-  return launch_relpos_attention_dual(q[0], q[1], (hipStream_t)stream);
+  return launch_relpos_attention_dual(qa, qb, (hipStream_t)stream);
 }
 int m3_dwconv_ln_silu_pair(const m3_dwconv_desc* a, const m3_dwconv_desc* b, m3_stream stream) {
   M3_REQUIRE(a != nullptr && b != nullptr, "dwconv pair: null descriptor");
-  const m3_dwconv_desc* const ds[2] = {a, b};
-  DwArgs q[2];
-  for (int i = 0; i < 2; ++i) {
-    const m3_dwconv_desc* d = ds[i];
-    M3_REQUIRE(d->B > 0 && d->T > 0 && d->D > 0 && d->K > 0, "dwconv pair: empty problem %d", i);
-    M3_REQUIRE(d->z && d->w_kc && d->bias && d->out && (d->gamma == nullptr) == (d->beta == nullptr),
-               "dwconv pair: null z / w_kc / bias / out, or gamma without beta");
-    M3_REQUIRE(aligned16(d->z) && aligned16(d->w_kc) && aligned16(d->bias) && aligned16(d->gamma) && aligned16(d->beta) &&
-               aligned16(d->left_fill) && aligned16(d->out), "dwconv pair: every operand must be 16-byte aligned");
-    M3_REQUIRE(d->ldz >= 0 && (d->ldz > 0 || !d->gate_sigmoided), "dwconv pair: ldz=%d (sigmoided gate columns belong to the GLU-on-load form)", d->ldz);
-    M3_REQUIRE(d->left_fill == nullptr || d->K >= 2, "dwconv pair: the causal conv needs K >= 2");
-    q[i].z = d->z; q[i].glu_ldz = d->ldz; q[i].glu_sig = d->gate_sigmoided != 0; q[i].w_kc = d->w_kc; q[i].bias = d->bias; q[i].gamma = d->gamma;
-    q[i].beta = d->beta; q[i].eps = d->eps; q[i].causal_left_fill = d->left_fill; q[i].B = d->B; q[i].T = d->T; q[i].D = d->D; q[i].K = d->K;
-    q[i].out = d->out;
-  }
-  M3_REQUIRE(dwconv_dual_fusable(q[0], q[1]),
+  DwArgs qa, qb;
+  if (int rc = dwconv_args_from_desc(a, "dwconv pair", "z", 0, true, &qa)) return rc;
+  if (int rc = dwconv_args_from_desc(b, "dwconv pair", "z", 1, true, &qb)) return rc;
+  M3_REQUIRE(dwconv_dual_fusable(qa, qb),
              "dwconv pair: channels %d / %d, taps %d / %d, causal %d / %d, GLU on load (ldz) %d / %d: the problems must agree in each (D %% 4 == 0, "
              "<= 4096; symmetric: K odd; GLU on load: symmetric, K <= 15, 256 <= D <= 1024, ldz >= 2 D a multiple of 4)",
              a->D, b->D, a->K, b->K, a->left_fill != nullptr, b->left_fill != nullptr, a->ldz, b->ldz);
   M3_REQUIRE(!ranges_overlap(a->out, (size_t)a->B * a->T * a->D * 4, b->out, (size_t)b->B * b->T * b->D * 4), "dwconv pair: the two outputs overlap");
-  return launch_dwconv_ln_silu_dual(q[0], q[1], (hipStream_t)stream);
+  return launch_dwconv_ln_silu_dual(qa, qb, (hipStream_t)stream);
 }
 int m3_subsample_conv1_pair(const m3_conv1_desc* a, const m3_conv1_desc* b, m3_stream stream) {
   M3_REQUIRE(a != nullptr && b != nullptr, "conv1 pair: null descriptor");
-  const m3_conv1_desc* const ds[2] = {a, b};
-  Conv1Args q[2];
-  size_t bytes[2];
-  for (int i = 0; i < 2; ++i) {
-    const m3_conv1_desc* d = ds[i];
-    M3_REQUIRE(d->feat && d->w9c && d->bias && d->out, "conv1 pair: null feat / w9c / bias / out");
-    M3_REQUIRE(d->act == M3_ACT_NONE || d->act == M3_ACT_RELU, "conv1 pair: act %d (none / relu)", d->act);
-    M3_REQUIRE((d->cmvn_mean == nullptr) == (d->cmvn_istd == nullptr), "conv1 pair: cmvn mean and istd go together");
-    M3_REQUIRE((d->feat_len == nullptr) == (d->lens_out == nullptr) && (i == 0 || d->feat_len == nullptr),
-               "conv1 pair: feat_len and lens_out go together, on the first problem only");
-    M3_REQUIRE(d->B > 0 && d->T >= 3 && d->idim >= 3, "conv1 pair: input (B=%d, T=%d, idim=%d) shorter than the 3x3 kernel", d->B, d->T, d->idim);
-    M3_REQUIRE(d->C > 0 && (d->C & 3) == 0 && d->C <= 1024, "conv1 pair: channels=%d must be a multiple of 4 (<= 1024)", d->C);
-    q[i].feat = d->feat; q[i].w9c = d->w9c; q[i].bias = d->bias; q[i].cmvn_mean = d->cmvn_mean; q[i].cmvn_istd = d->cmvn_istd;
-    q[i].B = d->B; q[i].T = d->T; q[i].idim = d->idim; q[i].C = d->C; q[i].out = d->out; q[i].relu = d->act == M3_ACT_RELU;
-    q[i].feat_len = d->feat_len; q[i].lens_out = d->lens_out;
-    bytes[i] = (size_t)d->B * ((d->T - 3) / 2 + 1) * ((d->idim - 3) / 2 + 1) * d->C * sizeof(float);
-  }
+  Conv1Args qa, qb;
+  if (int rc = conv1_args_from_desc(a, "conv1 pair", 0, &qa)) return rc;
+  if (int rc = conv1_args_from_desc(b, "conv1 pair", 1, &qb)) return rc;
+  auto bytes = [](const m3_conv1_desc* d) { return (size_t)d->B * ((d->T - 3) / 2 + 1) * ((d->idim - 3) / 2 + 1) * d->C * sizeof(float); };
   M3_REQUIRE(a->B == b->B && a->T == b->T && a->idim == b->idim, "conv1 pair: the two problems do not share an input shape (B %d / %d, T %d / %d, idim %d / %d)",
              a->B, b->B, a->T, b->T, a->idim, b->idim);
-  M3_REQUIRE(!ranges_overlap(a->out, bytes[0], b->out, bytes[1]), "conv1 pair: the two outputs overlap");
-  return launch_conv1_relu_dual(q[0], q[1], (hipStream_t)stream);
+  M3_REQUIRE(!ranges_overlap(a->out, bytes(a), b->out, bytes(b)), "conv1 pair: the two outputs overlap");
+  return launch_conv1_relu_dual(qa, qb, (hipStream_t)stream);
 }
 
 int m3_att_masked_softmax(const float* scores, const int32_t* len, int B, int H, int T1, int T2, float scale,

@@ -180,89 +180,27 @@ __device__ __forceinline__ void relpos_attention_body(const float* __restrict__ 
   }
 }
 
-template <int DK>
-__global__ __launch_bounds__(256) void relpos_attention_kernel(const float* __restrict__ qkv, int ldq,
-                                                              const float* __restrict__ pmat, int ldp,
-                                                              const float* __restrict__ pos_u,
-                                                              const float* __restrict__ pos_v,
-                                                              const int32_t* __restrict__ row_len, int T, int D,
-                                                              float scale, float* __restrict__ out, int ldo, int out_bf16,
-                                                              const int32_t* __restrict__ row0, int QT, int H, int xcd_map,
-                                                              int chunk, int left_chunks) {
-  relpos_attention_body<DK>(qkv, ldq, pmat, ldp, pos_u, pos_v, row_len, T, D, scale, out, ldo, out_bf16, row0, QT, H, xcd_map, chunk,
-                            left_chunks, (int)blockIdx.x);
-}
+// One record per problem, filled by att_pack: the single kernel takes one, the dual kernel two.  QT, the XCD mapping and the
+// work-group count are derived there, once.
 struct AttKernArgs {
   const float *qkv; int ldq; const float* pmat; int ldp; const float *pos_u, *pos_v; const int32_t* row_len; int T, D; float scale;
   float* out; int ldo, out_bf16; const int32_t* row0; int QT, H, xcd_map, chunk, left_chunks, n_wg;
 };
+#define M3_ATT_SPREAD(a) a.qkv, a.ldq, a.pmat, a.ldp, a.pos_u, a.pos_v, a.row_len, a.T, a.D, a.scale, a.out, a.ldo, a.out_bf16, a.row0, a.QT, a.H, a.xcd_map, a.chunk, a.left_chunks
+template <int DK>
+__global__ __launch_bounds__(256) void relpos_attention_kernel(const AttKernArgs a) {
+  relpos_attention_body<DK>(M3_ATT_SPREAD(a), (int)blockIdx.x);
+}
 // work-groups [0, n0) the first problem (n0 = its count rounded up to a multiple of 8: "id % 8 = XCD" holds for both), the rest the second
 template <int DK0, int DK1>
 __global__ __launch_bounds__(256) void relpos_attention_dual_kernel(const AttKernArgs a, const AttKernArgs b, const int n0) {
   if ((int)blockIdx.x < n0) {
-    if ((int)blockIdx.x < a.n_wg)
-      relpos_attention_body<DK0>(a.qkv, a.ldq, a.pmat, a.ldp, a.pos_u, a.pos_v, a.row_len, a.T, a.D, a.scale, a.out, a.ldo, a.out_bf16, a.row0,
-                                 a.QT, a.H, a.xcd_map, a.chunk, a.left_chunks, (int)blockIdx.x);
+    if ((int)blockIdx.x < a.n_wg) relpos_attention_body<DK0>(M3_ATT_SPREAD(a), (int)blockIdx.x);
   } else {
-    relpos_attention_body<DK1>(b.qkv, b.ldq, b.pmat, b.ldp, b.pos_u, b.pos_v, b.row_len, b.T, b.D, b.scale, b.out, b.ldo, b.out_bf16, b.row0,
-                               b.QT, b.H, b.xcd_map, b.chunk, b.left_chunks, (int)blockIdx.x - n0);
+    relpos_attention_body<DK1>(M3_ATT_SPREAD(b), (int)blockIdx.x - n0);
   }
 }
-
-int launch_relpos_attention_args(const AttArgs& a, hipStream_t stream) {
-  return launch_relpos_attention(a.qkv, a.ldq, a.pmat, a.ldp, a.pos_u, a.pos_v, a.row_len, a.B, a.T, a.H, a.dk, a.scale, a.out, a.ldo, stream,
-                                 a.out_bf16, a.row0, a.chunk, a.left_chunks);
-}
-static bool att_dual_dk(int dk) { return dk == 64 || dk == 128; }
-bool relpos_attention_dual_fusable(const AttArgs& a, const AttArgs& b) {
-  return att_dual_dk(a.dk) && att_dual_dk(b.dk) && a.B > 0 && a.T > 0 && b.B > 0 && b.T > 0 && (a.ldq & 3) == 0 && (a.ldp & 3) == 0 &&
-         (b.ldq & 3) == 0 && (b.ldp & 3) == 0;
-}
-int launch_relpos_attention_dual(const AttArgs& a, const AttArgs& b, hipStream_t stream) {
-  M3_REQUIRE(relpos_attention_dual_fusable(a, b), "attention dual: head widths %d / %d are not a dual instantiation", a.dk, b.dk);
-  auto pack = [](const AttArgs& q) {
-    AttKernArgs k;
-    k.qkv = q.qkv; k.ldq = q.ldq; k.pmat = q.pmat; k.ldp = q.ldp; k.pos_u = q.pos_u; k.pos_v = q.pos_v; k.row_len = q.row_len; k.T = q.T;
-    k.D = q.H * q.dk; k.scale = q.scale; k.out = q.out; k.ldo = q.ldo; k.out_bf16 = q.out_bf16; k.row0 = q.row0; k.QT = cdiv(q.T, 16); k.H = q.H;
-    k.xcd_map = ((q.H * q.B) % 8 == 0) ? 1 : 0; k.chunk = q.chunk; k.left_chunks = q.left_chunks; k.n_wg = k.QT * q.H * q.B;
-    return k;
-  };
-  const AttKernArgs ka = pack(a), kb = pack(b);
-  const int n0 = (int)align_up((size_t)ka.n_wg, 8);
-  dim3 grid(n0 + kb.n_wg);
-#define M3_ATTD(D0_, D1_) hipLaunchKernelGGL((relpos_attention_dual_kernel<D0_, D1_>), grid, dim3(256), 0, stream, ka, kb, n0)
-  if (a.dk == 128 && b.dk == 64) M3_ATTD(128, 64);
-  else if (a.dk == 64 && b.dk == 128) M3_ATTD(64, 128);
-  else if (a.dk == 64) M3_ATTD(64, 64);
-  else M3_ATTD(128, 128);
-#undef M3_ATTD
-  M3_LAUNCH_CHECK();
-  return 0;
-}
-
-int launch_relpos_attention(const float* qkv, int ldq, const float* pmat, int ldp, const float* pos_u,
-                            const float* pos_v, const int32_t* row_len, int B, int T, int H, int dk, float scale,
-                            float* out, int ldo, hipStream_t stream, int out_bf16, const int32_t* row0, int chunk, int left_chunks) {
-  M3_REQUIRE(B > 0 && T > 0 && H > 0, "attention: empty problem");
-  M3_REQUIRE((ldq & 3) == 0 && (ldp & 3) == 0, "attention: row strides must be multiples of 4");
-  const int QT = cdiv(T, 16);
-  dim3 grid(QT * H * B);
-  const int D = H * dk;
-  const int xcd_map = ((H * B) % 8 == 0) ? 1 : 0;
-#define M3_ATT_CASE(DK_)                                                                                   \
-  hipLaunchKernelGGL((relpos_attention_kernel<DK_>), grid, dim3(256), 0, stream, qkv, ldq, pmat, ldp, pos_u, \
-                     pos_v, row_len, T, D, scale, out, ldo, out_bf16, row0, QT, H, xcd_map, chunk, left_chunks)
-  switch (dk) {
-    case 16: M3_ATT_CASE(16); break;
-    case 32: M3_ATT_CASE(32); break;
-    case 64: M3_ATT_CASE(64); break;
-    case 128: M3_ATT_CASE(128); break;
-    default: M3_REQUIRE(false, "attention: d_k=%d unsupported (16/32/64/128)", dk);
-  }
-#undef M3_ATT_CASE
-  M3_LAUNCH_CHECK();
-  return 0;
-}
+#undef M3_ATT_SPREAD
 
 
 // ------------------------------------------------------------------------------------------------------------------------
@@ -424,30 +362,24 @@ __global__ __launch_bounds__(256) void relpos_attention_stream_kernel(const floa
   }
 }
 
-int launch_relpos_attention_stream(const float* qkv, int ldq, float* hist, int cap, const float* pmat, int ldp, const float* pos_u,
-                                   const float* pos_v, const int32_t* chunk_len, const int32_t* step, int B, int C, int H, int dk,
-                                   float scale, float* out, int ldo, int left_chunks, hipStream_t stream, int slot_max_chunks) {
-  M3_REQUIRE(B > 0 && C > 0 && H > 0 && cap >= C, "attention (stream): empty problem or history shorter than a chunk");
-  M3_REQUIRE(left_chunks < 0 || cap >= (left_chunks + 1) * C, "attention (stream): a history of %d frames cannot hold %d left chunks of %d", cap, left_chunks, C);
-  M3_REQUIRE((ldq & 3) == 0 && (ldp & 3) == 0 && (dk & 3) == 0, "attention (stream): row strides must be multiples of 4");
-  M3_REQUIRE(hist && chunk_len && step, "attention (stream): null state");
-  const int QT = cdiv(C, 16);
-  dim3 grid(QT * H * B);
-  const int D = H * dk;
+// (a.T: the C frames of a chunk, a.row_len: their valid count per utterance; checked by check_relpos_attention)
+static int launch_relpos_attention_stream(const AttArgs& a, hipStream_t stream) {
+  const int QT = cdiv(a.T, 16), D = a.H * a.dk;
+  dim3 grid(QT * a.H * a.B);
   // slot_max_chunks >= 0: slot mode, `step` holds B counters (one per utterance slot)
-#define M3_ATT_CASE(DK_)                                                                                                           \
-  if (slot_max_chunks >= 0)                                                                                                        \
-    hipLaunchKernelGGL((relpos_attention_stream_kernel<DK_, true>), grid, dim3(256), 0, stream, qkv, ldq, hist, cap, pmat, ldp,    \
-                       pos_u, pos_v, chunk_len, step, C, D, scale, out, ldo, QT, H, left_chunks, slot_max_chunks);                 \
-  else                                                                                                                             \
-    hipLaunchKernelGGL((relpos_attention_stream_kernel<DK_, false>), grid, dim3(256), 0, stream, qkv, ldq, hist, cap, pmat, ldp,   \
-                       pos_u, pos_v, chunk_len, step, C, D, scale, out, ldo, QT, H, left_chunks, 0)
-  switch (dk) {
+#define M3_ATT_CASE(DK_)                                                                                                                   \
+  if (a.slot_max_chunks >= 0)                                                                                                              \
+    hipLaunchKernelGGL((relpos_attention_stream_kernel<DK_, true>), grid, dim3(256), 0, stream, (const float*)a.qkv, a.ldq, a.hist, a.cap, \
+                       a.pmat, a.ldp, a.pos_u, a.pos_v, a.row_len, a.step, a.T, D, a.scale, (float*)a.out, a.ldo, QT, a.H, a.left_chunks,  \
+                       a.slot_max_chunks);                                                                                                 \
+  else                                                                                                                                     \
+    hipLaunchKernelGGL((relpos_attention_stream_kernel<DK_, false>), grid, dim3(256), 0, stream, (const float*)a.qkv, a.ldq, a.hist, a.cap, \
+                       a.pmat, a.ldp, a.pos_u, a.pos_v, a.row_len, a.step, a.T, D, a.scale, (float*)a.out, a.ldo, QT, a.H, a.left_chunks, 0)
+  switch (a.dk) {
     case 16: M3_ATT_CASE(16); break;
     case 32: M3_ATT_CASE(32); break;
     case 64: M3_ATT_CASE(64); break;
-    case 128: M3_ATT_CASE(128); break;
-    default: M3_REQUIRE(false, "attention (stream): d_k=%d unsupported (16/32/64/128)", dk);
+    default: M3_ATT_CASE(128);
   }
 #undef M3_ATT_CASE
   M3_LAUNCH_CHECK();
@@ -661,20 +593,85 @@ int init_relpos_attention_bf16_kernels() {
   return 0;
 }
 
-int launch_relpos_attention_bf16(const void* qkv, int ldq, const float* pmat, int ldp, const float* pos_u, const float* pos_v,
-                                 const int32_t* row_len, int B, int T, int H, int dk, float scale, void* out, int ldo,
-                                 hipStream_t stream, const int32_t* row0, int chunk, int left_chunks) {
-  M3_REQUIRE(B > 0 && T > 0 && H > 0, "attention: empty problem");
-  M3_REQUIRE(relpos_attention_bf16_supports(T, dk), "attention (bf16 rows): T'=%d > %d keys or d_k=%d not 64 / 128", T, kAttTP, dk);
-  M3_REQUIRE((ldq & 7) == 0 && (ldp & 3) == 0 && (ldo & 3) == 0, "attention (bf16 rows): row strides must be multiples of 8 / 4 / 4");
+static int launch_relpos_attention_bf16(const AttArgs& a, hipStream_t stream) {
   if (int rc = init_relpos_attention_bf16_kernels()) return rc;
-  const int D = H * dk;
-  if (dk == 64)
-    hipLaunchKernelGGL((relpos_attention_bf16_kernel<64>), dim3(B * H), dim3(256), att16_lds_bytes<64>(), stream, (const bf16_t*)qkv,
-                       ldq, pmat, ldp, pos_u, pos_v, row_len, T, D, H, scale, (bf16_t*)out, ldo, row0, chunk, left_chunks);
-  else
-    hipLaunchKernelGGL((relpos_attention_bf16_kernel<128>), dim3(B * H), dim3(256), att16_lds_bytes<128>(), stream, (const bf16_t*)qkv,
-                       ldq, pmat, ldp, pos_u, pos_v, row_len, T, D, H, scale, (bf16_t*)out, ldo, row0, chunk, left_chunks);
+  const int D = a.H * a.dk;
+#define M3_ATT_CASE(DK_)                                                                                                                       \
+  hipLaunchKernelGGL((relpos_attention_bf16_kernel<DK_>), dim3(a.B * a.H), dim3(256), att16_lds_bytes<DK_>(), stream, (const bf16_t*)a.qkv, a.ldq, \
+                     a.pmat, a.ldp, a.pos_u, a.pos_v, a.row_len, a.T, D, a.H, a.scale, (bf16_t*)a.out, a.ldo, a.row0, a.chunk, a.left_chunks)
+  if (a.dk == 64) M3_ATT_CASE(64);
+  else M3_ATT_CASE(128);
+#undef M3_ATT_CASE
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// The host side of the three cores: one record (AttArgs), one check, one launcher; att_pack serves the fp32 single and dual kernels.
+static AttKernArgs att_pack(const AttArgs& q) {
+  AttKernArgs k;
+  k.qkv = (const float*)q.qkv; k.ldq = q.ldq; k.pmat = q.pmat; k.ldp = q.ldp; k.pos_u = q.pos_u; k.pos_v = q.pos_v; k.row_len = q.row_len; k.T = q.T;
+  k.D = q.H * q.dk; k.scale = q.scale; k.out = (float*)q.out; k.ldo = q.ldo; k.out_bf16 = q.out_bf16; k.row0 = q.row0; k.QT = cdiv(q.T, 16); k.H = q.H;
+  k.xcd_map = ((q.H * q.B) % 8 == 0) ? 1 : 0; k.chunk = q.chunk; k.left_chunks = q.left_chunks; k.n_wg = k.QT * q.H * q.B;
+  return k;
+}
+static bool att_dk(int dk) { return dk == 16 || dk == 32 || dk == 64 || dk == 128; }
+static bool att_dual_dk(int dk) { return dk == 64 || dk == 128; }
+
+// the three cores' argument checks (fp32 rows, bf16 rows, chunk-by-chunk), for the single and the dual launcher
+static int check_relpos_attention(const AttArgs& a, bool say = true) {
+  if (a.streaming) {
+    M3_REQUIRE_SAY(say, a.B > 0 && a.T > 0 && a.H > 0 && a.cap >= a.T, "attention (stream): empty problem or history shorter than a chunk");
+    M3_REQUIRE_SAY(say, a.left_chunks < 0 || a.cap >= (a.left_chunks + 1) * a.T, "attention (stream): a history of %d frames cannot hold %d left chunks of %d",
+                   a.cap, a.left_chunks, a.T);
+    M3_REQUIRE_SAY(say, (a.ldq & 3) == 0 && (a.ldp & 3) == 0 && (a.dk & 3) == 0, "attention (stream): row strides must be multiples of 4");
+    M3_REQUIRE_SAY(say, a.hist && a.row_len && a.step, "attention (stream): null state");
+    M3_REQUIRE_SAY(say, att_dk(a.dk), "attention (stream): d_k=%d unsupported (16/32/64/128)", a.dk);
+    return 0;
+  }
+  M3_REQUIRE_SAY(say, a.B > 0 && a.T > 0 && a.H > 0, "attention: empty problem");
+  if (a.rows_bf16) {
+    M3_REQUIRE_SAY(say, relpos_attention_bf16_supports(a.T, a.dk), "attention (bf16 rows): T'=%d > %d keys or d_k=%d not 64 / 128", a.T, kAttTP, a.dk);
+    M3_REQUIRE_SAY(say, (a.ldq & 7) == 0 && (a.ldp & 3) == 0 && (a.ldo & 3) == 0, "attention (bf16 rows): row strides must be multiples of 8 / 4 / 4");
+    return 0;
+  }
+  M3_REQUIRE_SAY(say, (a.ldq & 3) == 0 && (a.ldp & 3) == 0, "attention: row strides must be multiples of 4");
+  M3_REQUIRE_SAY(say, att_dk(a.dk), "attention: d_k=%d unsupported (16/32/64/128)", a.dk);
+  return 0;
+}
+
+int launch_relpos_attention(const AttArgs& a, hipStream_t stream) {
+  if (int rc = check_relpos_attention(a)) return rc;
+  if (a.streaming) return launch_relpos_attention_stream(a, stream);
+  if (a.rows_bf16) return launch_relpos_attention_bf16(a, stream);
+  const AttKernArgs k = att_pack(a);
+#define M3_ATT_CASE(DK_) hipLaunchKernelGGL((relpos_attention_kernel<DK_>), dim3(k.n_wg), dim3(256), 0, stream, k)
+  switch (a.dk) {
+    case 16: M3_ATT_CASE(16); break;
+    case 32: M3_ATT_CASE(32); break;
+    case 64: M3_ATT_CASE(64); break;
+    default: M3_ATT_CASE(128);
+  }
+#undef M3_ATT_CASE
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+// two independent fp32 attention problems, head widths 64 or 128 each, in ONE launch
+bool relpos_attention_dual_fusable(const AttArgs& a, const AttArgs& b) {
+  return check_relpos_attention(a, false) == 0 && check_relpos_attention(b, false) == 0 && !a.streaming && !b.streaming && !a.rows_bf16 &&
+         !b.rows_bf16 && att_dual_dk(a.dk) && att_dual_dk(b.dk);
+}
+int launch_relpos_attention_dual(const AttArgs& a, const AttArgs& b, hipStream_t stream) {
+  M3_REQUIRE(relpos_attention_dual_fusable(a, b), "attention dual: head widths %d / %d are not a dual instantiation", a.dk, b.dk);
+  const AttKernArgs ka = att_pack(a), kb = att_pack(b);
+  const int n0 = (int)align_up((size_t)ka.n_wg, 8);
+  dim3 grid(n0 + kb.n_wg);
+#define M3_ATTD(D0_, D1_) hipLaunchKernelGGL((relpos_attention_dual_kernel<D0_, D1_>), grid, dim3(256), 0, stream, ka, kb, n0)
+  if (a.dk == 128 && b.dk == 64) M3_ATTD(128, 64);
+  else if (a.dk == 64 && b.dk == 128) M3_ATTD(64, 128);
+  else if (a.dk == 64) M3_ATTD(64, 64);
+  else M3_ATTD(128, 128);
+#undef M3_ATTD
   M3_LAUNCH_CHECK();
   return 0;
 }

@@ -28,6 +28,14 @@ const char* last_error();
       return -2;                               \
     }                                          \
   } while (0)
+// inside a check that is also asked as a question (say = false: the *_dual_fusable predicates leave the error string alone)
+#define M3_REQUIRE_SAY(say, cond, ...)         \
+  do {                                         \
+    if (!(cond)) {                             \
+      if (say) m3::set_error(__VA_ARGS__);     \
+      return -2;                               \
+    }                                          \
+  } while (0)
 
 #define M3_LAUNCH_CHECK() M3_CHECK_HIP(hipGetLastError())
 

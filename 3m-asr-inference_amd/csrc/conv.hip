@@ -191,133 +191,98 @@ __device__ __forceinline__ void dwconv_ln_silu_body(const float* __restrict__ z,
   }
 }
 
-// (GLU_IN holds 2 K row fragments + K weight fragments per thread: 256 threads (D <= 1024) leave a wave the registers for them)
-template <int KT, bool CAUSAL, bool SLOTS = false, int GLU_IN = 0>
-__global__ __launch_bounds__(GLU_IN ? 256 : 1024) void dwconv_ln_silu_kernel(const float* __restrict__ z, const float* __restrict__ w_kc,
-                                                              const float* __restrict__ bias,
-                                                              const float* __restrict__ gamma,
-                                                              const float* __restrict__ beta, float eps, int T,
-                                                              int D, int K, float* __restrict__ out, int out_bf16,
-                                                              const int32_t* __restrict__ pad_of,
-                                                              const int32_t* __restrict__ row0,
-                                                              const int32_t* __restrict__ row_len, int n_rows, DwCausal cs, int ldz) {
-  dwconv_ln_silu_body<KT, CAUSAL, SLOTS, GLU_IN>(z, w_kc, bias, gamma, beta, eps, T, D, K, out, out_bf16, pad_of, row0, row_len, n_rows, cs,
-                                                 (int)blockIdx.x, ldz);
-}
+// One record per problem, filled by dwconv_pack: the single kernel takes one, the dual kernel two.
 struct DwKernArgs {
   const float *z, *w_kc, *bias, *gamma, *beta; float eps; int T, D, K; float* out; int out_bf16;
   const int32_t *pad_of, *row0, *row_len; int n_rows; DwCausal cs; int ldz;
+  int slots, glu_in, threads, grid;   // the launch: instantiation (with cs.causal and K), block, work-groups
 };
+#define M3_DW_SPREAD(a) a.z, a.w_kc, a.bias, a.gamma, a.beta, a.eps, a.T, a.D, a.K, a.out, a.out_bf16, a.pad_of, a.row0, a.row_len, a.n_rows, a.cs
+// (GLU_IN holds 2 K row fragments + K weight fragments per thread: 256 threads (D <= 1024) leave a wave the registers for them)
+template <int KT, bool CAUSAL, bool SLOTS = false, int GLU_IN = 0>
+__global__ __launch_bounds__(GLU_IN ? 256 : 1024) void dwconv_ln_silu_kernel(const DwKernArgs a) {
+  dwconv_ln_silu_body<KT, CAUSAL, SLOTS, GLU_IN>(M3_DW_SPREAD(a), (int)blockIdx.x, a.ldz);
+}
 template <int KT, bool CAUSAL, int GLU_IN = 0>
 __global__ __launch_bounds__(GLU_IN ? 256 : 1024) void dwconv_ln_silu_dual_kernel(const DwKernArgs a, const DwKernArgs b) {
-  if ((int)blockIdx.x < a.n_rows)
-    dwconv_ln_silu_body<KT, CAUSAL, false, GLU_IN>(a.z, a.w_kc, a.bias, a.gamma, a.beta, a.eps, a.T, a.D, a.K, a.out, a.out_bf16, a.pad_of, a.row0,
-                                                   a.row_len, a.n_rows, a.cs, (int)blockIdx.x, a.ldz);
-  else
-    dwconv_ln_silu_body<KT, CAUSAL, false, GLU_IN>(b.z, b.w_kc, b.bias, b.gamma, b.beta, b.eps, b.T, b.D, b.K, b.out, b.out_bf16, b.pad_of, b.row0,
-                                                   b.row_len, b.n_rows, b.cs, (int)blockIdx.x - a.n_rows, b.ldz);
+  if ((int)blockIdx.x < a.n_rows) dwconv_ln_silu_body<KT, CAUSAL, false, GLU_IN>(M3_DW_SPREAD(a), (int)blockIdx.x, a.ldz);
+  else dwconv_ln_silu_body<KT, CAUSAL, false, GLU_IN>(M3_DW_SPREAD(b), (int)blockIdx.x - a.n_rows, b.ldz);
 }
-
-static int launch_dwconv_impl(const float* z, const float* w_kc, const float* bias, const float* gamma, const float* beta, float eps,
-                              int B, int T, int D, int K, float* out, hipStream_t stream, int out_bf16, const int32_t* pad_of,
-                              const int32_t* row0, const int32_t* row_len, const DwCausal& cs, bool slots = false, int glu_ldz = 0,
-                              int glu_sig = 0) {
-  M3_REQUIRE(glu_ldz == 0 || dwconv_glu_in_supports(D, K, cs.causal != 0 || slots, out_bf16, glu_ldz),
-             "dwconv (GLU on load): needs the symmetric fp32 conv, K <= 15, 256 <= channels <= 1024, ldz=%d a multiple of 4 and >= %d", glu_ldz, 2 * D);
-  M3_REQUIRE(!slots || (cs.causal && cs.step != nullptr && cs.max_chunks > 0), "dwconv (slot mode): needs the streaming causal form");
-  M3_REQUIRE((D & 3) == 0 && D <= 4096, "dwconv: channels=%d must be a multiple of 4 (<=4096)", D);
-  M3_REQUIRE(cs.causal || (K & 1) == 1, "dwconv: kernel size %d must be odd (non-causal)", K);
-  M3_REQUIRE(!cs.causal || (cs.left != nullptr && K >= 2), "dwconv (causal): the frames left of frame 0 must be supplied (left_fill / cache)");
-  const int rows = B * T;
-  if (rows == 0) return 0;
-  const int threads = (int)align_up(D / 4, 64);
-  const int grid = rows + (cs.step != nullptr ? B * (K - 1) : 0);     // streaming: + the work-groups that write the new cache
-#define M3_DW_CASE(KT_, C_)                                                                                                  \
-  hipLaunchKernelGGL((dwconv_ln_silu_kernel<KT_, C_>), dim3(grid), dim3(threads), 0, stream, z, w_kc, bias, gamma, beta, eps, T, \
-                     D, K, out, out_bf16, pad_of, row0, row_len, rows, cs, 0)
-#define M3_DW_SLOTS(KT_)                                                                                                        \
-  hipLaunchKernelGGL((dwconv_ln_silu_kernel<KT_, true, true>), dim3(grid), dim3(threads), 0, stream, z, w_kc, bias, gamma, beta, eps, \
-                     T, D, K, out, out_bf16, pad_of, row0, row_len, rows, cs, 0)
-  M3_REQUIRE(!glu_sig || glu_ldz, "dwconv: sigmoided gate columns belong to the GLU-on-load form");
-  if (glu_ldz && glu_sig)
-    hipLaunchKernelGGL((dwconv_ln_silu_kernel<15, false, false, 2>), dim3(grid), dim3(threads), 0, stream, z, w_kc, bias, gamma, beta, eps, T,
-                       D, K, out, out_bf16, pad_of, row0, row_len, rows, cs, glu_ldz);
-  else if (glu_ldz)
-    hipLaunchKernelGGL((dwconv_ln_silu_kernel<15, false, false, 1>), dim3(grid), dim3(threads), 0, stream, z, w_kc, bias, gamma, beta, eps, T,
-                       D, K, out, out_bf16, pad_of, row0, row_len, rows, cs, glu_ldz);
-  else if (slots) { if (K <= 15) M3_DW_SLOTS(15); else M3_DW_SLOTS(8); }
-  else if (K <= 15) { if (cs.causal) M3_DW_CASE(15, true); else M3_DW_CASE(15, false); }
-  else { if (cs.causal) M3_DW_CASE(8, true); else M3_DW_CASE(8, false); }
-#undef M3_DW_SLOTS
-#undef M3_DW_CASE
-  M3_LAUNCH_CHECK();
-  return 0;
-}
-
-int launch_dwconv_ln_silu(const float* z, const float* w_kc, const float* bias, const float* gamma,
-                          const float* beta, float eps, int B, int T, int D, int K, float* out, hipStream_t stream, int out_bf16,
-                          const int32_t* pad_of, const int32_t* row0, const int32_t* row_len, const float* causal_left_fill) {
-  DwCausal cs;
-  if (causal_left_fill != nullptr) { cs.causal = 1; cs.left = causal_left_fill; }
-  return launch_dwconv_impl(z, w_kc, bias, gamma, beta, eps, B, T, D, K, out, stream, out_bf16, pad_of, row0, row_len, cs);
-}
+#undef M3_DW_SPREAD
 
 bool dwconv_glu_in_supports(int D, int K, bool causal_or_stream, int out_bf16, int ldz) {
   return !causal_or_stream && !out_bf16 && (K & 1) == 1 && K <= 15 && D >= 256 && D <= 1024 && (D & 3) == 0 && ldz >= 2 * D && (ldz & 3) == 0;
 }
-
-int launch_dwconv_ln_silu_args(const DwArgs& a, hipStream_t stream) {
-  if (a.glu_ldz) {
-    M3_REQUIRE(a.causal_left_fill == nullptr, "dwconv (GLU on load): the symmetric conv only");
-    return launch_dwconv_impl(a.z, a.w_kc, a.bias, a.gamma, a.beta, a.eps, a.B, a.T, a.D, a.K, a.out, stream, a.out_bf16, a.pad_of, a.row0, a.row_len,
-                              DwCausal{}, false, a.glu_ldz, a.glu_sig);
+static bool dwconv_causal(const DwArgs& a) { return a.streaming || a.causal_left_fill != nullptr; }
+static int check_dwconv(const DwArgs& a, bool say = true) {
+  const bool causal = dwconv_causal(a);
+  M3_REQUIRE_SAY(say, !a.streaming || (a.cache_pair && a.step && a.chunk_len), "dwconv (stream): null state");
+  M3_REQUIRE_SAY(say, !a.glu_ldz || a.causal_left_fill == nullptr, "dwconv (GLU on load): the symmetric conv only");
+  M3_REQUIRE_SAY(say, a.glu_ldz == 0 || dwconv_glu_in_supports(a.D, a.K, causal, a.out_bf16, a.glu_ldz),
+                 "dwconv (GLU on load): needs the symmetric fp32 conv, K <= 15, 256 <= channels <= 1024, ldz=%d a multiple of 4 and >= %d", a.glu_ldz, 2 * a.D);
+  M3_REQUIRE_SAY(say, !a.streaming || a.slot_max_chunks != 0, "dwconv (slot mode): needs the streaming causal form");
+  M3_REQUIRE_SAY(say, (a.D & 3) == 0 && a.D <= 4096, "dwconv: channels=%d must be a multiple of 4 (<=4096)", a.D);
+  M3_REQUIRE_SAY(say, causal || (a.K & 1) == 1, "dwconv: kernel size %d must be odd (non-causal)", a.K);
+  M3_REQUIRE_SAY(say, !causal || a.K >= 2, "dwconv (causal): the frames left of frame 0 must be supplied (left_fill / cache)");
+  M3_REQUIRE_SAY(say, !a.glu_sig || a.glu_ldz, "dwconv: sigmoided gate columns belong to the GLU-on-load form");
+  return 0;
+}
+static DwKernArgs dwconv_pack(const DwArgs& q) {
+  DwKernArgs k;
+  k.z = q.z; k.w_kc = q.w_kc; k.bias = q.bias; k.gamma = q.gamma; k.beta = q.beta; k.eps = q.eps; k.T = q.T; k.D = q.D; k.K = q.K;
+  k.out = q.out; k.out_bf16 = q.out_bf16; k.pad_of = q.pad_of; k.row0 = q.row0; k.row_len = q.row_len; k.n_rows = q.B * q.T;
+  k.ldz = q.glu_ldz;
+  k.cs.causal = dwconv_causal(q);
+  k.cs.left = q.causal_left_fill;
+  if (q.streaming) {   // the ping-pong cache [2][B][K-1][D], chunk counter(s) and valid frames on the device
+    k.cs.left = q.cache_pair; k.cs.left_b_stride = (long)(q.K - 1) * q.D; k.cs.left_t_stride = q.D;
+    k.cs.step = q.step; k.cs.half = (long)q.B * (q.K - 1) * q.D; k.cs.chunk_len = q.chunk_len;
+    k.cs.max_chunks = q.slot_max_chunks > 0 ? q.slot_max_chunks : 0;
   }
-  return launch_dwconv_ln_silu(a.z, a.w_kc, a.bias, a.gamma, a.beta, a.eps, a.B, a.T, a.D, a.K, a.out, stream, a.out_bf16, a.pad_of, a.row0,
-                               a.row_len, a.causal_left_fill);
+  k.slots = q.streaming && q.slot_max_chunks >= 0;
+  k.glu_in = q.glu_ldz ? (q.glu_sig ? 2 : 1) : 0;
+  k.threads = (int)align_up(q.D / 4, 64);
+  k.grid = k.n_rows + (q.streaming ? q.B * (q.K - 1) : 0);     // streaming: + the work-groups that write the new cache
+  return k;
 }
-// two independent conv modules of the same shape class (channels, taps, causal or not) in ONE launch
-bool dwconv_dual_fusable(const DwArgs& a, const DwArgs& b) {
-  if ((a.glu_ldz != 0) != (b.glu_ldz != 0) || (a.glu_sig != 0) != (b.glu_sig != 0)) return false;
-  if (a.glu_ldz && !(dwconv_glu_in_supports(a.D, a.K, a.causal_left_fill != nullptr, a.out_bf16, a.glu_ldz) &&
-                     dwconv_glu_in_supports(b.D, b.K, b.causal_left_fill != nullptr, b.out_bf16, b.glu_ldz)))
-    return false;
-  return a.D == b.D && a.K == b.K && (a.causal_left_fill != nullptr) == (b.causal_left_fill != nullptr) && a.B * a.T > 0 && b.B * b.T > 0 &&
-         (a.D & 3) == 0 && a.D <= 4096 && (a.causal_left_fill != nullptr || (a.K & 1) == 1);
+// The instantiation of a packed problem, named once for the single and the dual kernel: f(KT, CAUSAL, SLOTS, GLU_IN as constants)
+template <int KT_, bool CAUSAL_, bool SLOTS_, int GLU_IN_>
+struct DwForm { static constexpr int KT = KT_, GLU_IN = GLU_IN_; static constexpr bool CAUSAL = CAUSAL_, SLOTS = SLOTS_; };
+template <class F>
+static void dwconv_with_form(const DwKernArgs& k, F f) {
+  if (k.glu_in == 2) f(DwForm<15, false, false, 2>{});
+  else if (k.glu_in) f(DwForm<15, false, false, 1>{});
+  else if (k.slots) { if (k.K <= 15) f(DwForm<15, true, true, 0>{}); else f(DwForm<8, true, true, 0>{}); }
+  else if (k.K <= 15) { if (k.cs.causal) f(DwForm<15, true, false, 0>{}); else f(DwForm<15, false, false, 0>{}); }
+  else { if (k.cs.causal) f(DwForm<8, true, false, 0>{}); else f(DwForm<8, false, false, 0>{}); }
 }
-int launch_dwconv_ln_silu_dual(const DwArgs& a, const DwArgs& b, hipStream_t stream) {
-  M3_REQUIRE(dwconv_dual_fusable(a, b), "dwconv dual: the two problems do not share an instantiation");
-  auto pack = [](const DwArgs& q) {
-    DwKernArgs k;
-    k.z = q.z; k.w_kc = q.w_kc; k.bias = q.bias; k.gamma = q.gamma; k.beta = q.beta; k.eps = q.eps; k.T = q.T; k.D = q.D; k.K = q.K;
-    k.out = q.out; k.out_bf16 = q.out_bf16; k.pad_of = q.pad_of; k.row0 = q.row0; k.row_len = q.row_len; k.n_rows = q.B * q.T;
-    if (q.causal_left_fill != nullptr) { k.cs.causal = 1; k.cs.left = q.causal_left_fill; }
-    k.ldz = q.glu_ldz;
-    return k;
-  };
-  const DwKernArgs ka = pack(a), kb = pack(b);
-  const int threads = (int)align_up(a.D / 4, 64), grid = ka.n_rows + kb.n_rows;
-  const bool causal = a.causal_left_fill != nullptr;
-#define M3_DWD_CASE(KT_, C_) hipLaunchKernelGGL((dwconv_ln_silu_dual_kernel<KT_, C_>), dim3(grid), dim3(threads), 0, stream, ka, kb)
-  if (a.glu_ldz && a.glu_sig) hipLaunchKernelGGL((dwconv_ln_silu_dual_kernel<15, false, 2>), dim3(grid), dim3(threads), 0, stream, ka, kb);
-  else if (a.glu_ldz) hipLaunchKernelGGL((dwconv_ln_silu_dual_kernel<15, false, 1>), dim3(grid), dim3(threads), 0, stream, ka, kb);
-  else if (a.K <= 15) { if (causal) M3_DWD_CASE(15, true); else M3_DWD_CASE(15, false); }
-  else { if (causal) M3_DWD_CASE(8, true); else M3_DWD_CASE(8, false); }
-#undef M3_DWD_CASE
+
+int launch_dwconv_ln_silu(const DwArgs& a, hipStream_t stream) {
+  if (int rc = check_dwconv(a)) return rc;
+  const DwKernArgs k = dwconv_pack(a);
+  if (k.n_rows == 0) return 0;
+  dwconv_with_form(k, [&](auto f) {
+    using F = decltype(f);
+    hipLaunchKernelGGL((dwconv_ln_silu_kernel<F::KT, F::CAUSAL, F::SLOTS, F::GLU_IN>), dim3(k.grid), dim3(k.threads), 0, stream, k);
+  });
   M3_LAUNCH_CHECK();
   return 0;
 }
-
-// chunk-by-chunk (streaming) form of the causal conv: cache_pair [2][B][K-1][D], chunk counter and valid frames on the device
-int launch_dwconv_ln_silu_stream(const float* z, const float* w_kc, const float* bias, const float* gamma, const float* beta,
-                                 float eps, int B, int T, int D, int K, float* out, float* cache_pair, const int32_t* step,
-                                 const int32_t* chunk_len, hipStream_t stream, int out_bf16, int slot_max_chunks) {
-  M3_REQUIRE(cache_pair && step && chunk_len, "dwconv (stream): null state");
-  DwCausal cs;
-  cs.causal = 1; cs.left = cache_pair; cs.left_b_stride = (long)(K - 1) * D; cs.left_t_stride = D;
-  cs.step = step; cs.half = (long)B * (K - 1) * D; cs.chunk_len = chunk_len;
-  cs.max_chunks = slot_max_chunks > 0 ? slot_max_chunks : 0;
-  return launch_dwconv_impl(z, w_kc, bias, gamma, beta, eps, B, T, D, K, out, stream, out_bf16, nullptr, nullptr, nullptr, cs,
-                            slot_max_chunks >= 0);
+// two independent conv modules of the same shape class (channels, taps, causal or not, GLU on load or not) in ONE launch
+bool dwconv_dual_fusable(const DwArgs& a, const DwArgs& b) {
+  return check_dwconv(a, false) == 0 && check_dwconv(b, false) == 0 && !a.streaming && !b.streaming && a.D == b.D && a.K == b.K &&
+         dwconv_causal(a) == dwconv_causal(b) && (a.glu_ldz != 0) == (b.glu_ldz != 0) && (a.glu_sig != 0) == (b.glu_sig != 0) &&
+         a.B * a.T > 0 && b.B * b.T > 0;
+}
+int launch_dwconv_ln_silu_dual(const DwArgs& a, const DwArgs& b, hipStream_t stream) {
+  M3_REQUIRE(dwconv_dual_fusable(a, b), "dwconv dual: the two problems do not share an instantiation");
+  const DwKernArgs ka = dwconv_pack(a), kb = dwconv_pack(b);
+  dwconv_with_form(ka, [&](auto f) {
+    using F = decltype(f);
+    hipLaunchKernelGGL((dwconv_ln_silu_dual_kernel<F::KT, F::CAUSAL, F::GLU_IN>), dim3(ka.grid + kb.grid), dim3(ka.threads), 0, stream, ka, kb);
+  });
+  M3_LAUNCH_CHECK();
+  return 0;
 }
 
 // feat [B][T][idim] -> out [B][T1][F1][C] (channel-last), w9c [9][C] (repacked from (C,1,3,3)), ReLU.
@@ -385,65 +350,61 @@ __device__ __forceinline__ void conv1_relu_body(const float* __restrict__ feat, 
   }
 }
 
-__global__ __launch_bounds__(256) void conv1_relu_kernel(const float* __restrict__ feat, const float* __restrict__ w9c,
-                                                         const float* __restrict__ bias,
-                                                         const float* __restrict__ cmvn_mean,
-                                                         const float* __restrict__ cmvn_istd, int T, int idim, int T1,
-                                                         int F1, int C, float* __restrict__ out, int relu, int out_bf16,
-                                                         const int32_t* __restrict__ feat_len, int32_t* __restrict__ lens_out, int B) {
-  conv1_relu_body(feat, w9c, bias, cmvn_mean, cmvn_istd, T, idim, T1, F1, C, out, relu, out_bf16, feat_len, lens_out, B, (int)blockIdx.x);
-}
+// One record per problem, filled by conv1_pack: the single kernel takes one, the dual kernel two.  T1, F1, the row count, the
+// column split (short inputs: see conv1_relu_body) and the work-group size are derived there, once.
+struct Conv1KernArgs {
+  const float *feat, *w9c, *bias, *cmvn_mean, *cmvn_istd; int T, idim, T1, F1, C; float* out; int relu, out_bf16;
+  const int32_t* feat_len; int32_t* lens_out; int B;
+  int rows, fsplit, threads;   // the launch: B * T1 output rows, grid.y, block
+};
+#define M3_CONV1_SPREAD(a) a.feat, a.w9c, a.bias, a.cmvn_mean, a.cmvn_istd, a.T, a.idim, a.T1, a.F1, a.C, a.out, a.relu, a.out_bf16, a.feat_len, a.lens_out, a.B
+__global__ __launch_bounds__(256) void conv1_relu_kernel(const Conv1KernArgs a) { conv1_relu_body(M3_CONV1_SPREAD(a), (int)blockIdx.x); }
 // both problems: the same input shape (B, T, idim), so the same T1, F1 and column split; the second problem's rows start at n0,
 // a multiple of 8
-struct Conv1KernArgs {
-  const float *feat, *w9c, *bias, *cmvn_mean, *cmvn_istd; int C; float* out; int relu, out_bf16; const int32_t* feat_len; int32_t* lens_out;
-};
-__global__ __launch_bounds__(256) void conv1_relu_dual_kernel(const Conv1KernArgs a, const Conv1KernArgs b, int T, int idim, int T1, int F1,
-                                                              int B, int rows, int n0) {
+__global__ __launch_bounds__(256) void conv1_relu_dual_kernel(const Conv1KernArgs a, const Conv1KernArgs b, int n0) {
   const int id = (int)blockIdx.x;
   if (id < n0) {
-    if (id < rows)
-      conv1_relu_body(a.feat, a.w9c, a.bias, a.cmvn_mean, a.cmvn_istd, T, idim, T1, F1, a.C, a.out, a.relu, a.out_bf16, a.feat_len, a.lens_out, B, id);
+    if (id < a.rows) conv1_relu_body(M3_CONV1_SPREAD(a), id);
   } else {
-    conv1_relu_body(b.feat, b.w9c, b.bias, b.cmvn_mean, b.cmvn_istd, T, idim, T1, F1, b.C, b.out, b.relu, b.out_bf16, b.feat_len, b.lens_out, B, id - n0);
+    conv1_relu_body(M3_CONV1_SPREAD(b), id - n0);
   }
 }
+#undef M3_CONV1_SPREAD
 
-static int conv1_fsplit(int rows) { return rows >= 2048 ? 1 : (rows >= 512 ? 2 : 5); }
+static int check_conv1(const Conv1Args& a, bool say = true) {
+  M3_REQUIRE_SAY(say, a.T >= 3 && a.idim >= 3, "subsampling: input (T=%d, idim=%d) shorter than the 3x3 kernel", a.T, a.idim);
+  M3_REQUIRE_SAY(say, (a.C & 3) == 0 && a.C > 0 && a.C <= 1024, "subsampling: channels=%d must be a multiple of 4 (<= 1024)", a.C);
+  return 0;
+}
+static Conv1KernArgs conv1_pack(const Conv1Args& q) {
+  Conv1KernArgs k;
+  k.feat = q.feat; k.w9c = q.w9c; k.bias = q.bias; k.cmvn_mean = q.cmvn_mean; k.cmvn_istd = q.cmvn_istd; k.T = q.T; k.idim = q.idim;
+  k.T1 = (q.T - 3) / 2 + 1; k.F1 = (q.idim - 3) / 2 + 1; k.C = q.C; k.out = q.out; k.relu = q.relu; k.out_bf16 = q.out_bf16;
+  k.feat_len = q.feat_len; k.lens_out = q.lens_out; k.B = q.B;
+  k.rows = q.B * k.T1;
+  k.fsplit = k.rows >= 2048 ? 1 : (k.rows >= 512 ? 2 : 5);
+  k.threads = (int)align_up(q.C / 4, 64);
+  return k;
+}
 
-int launch_conv1_relu(const float* feat, const float* w9c, const float* bias, const float* cmvn_mean,
-                      const float* cmvn_istd, int B, int T, int idim, int C, float* out, hipStream_t stream, int relu, int out_bf16,
-                      const int32_t* feat_len, int32_t* lens_out) {
-  M3_REQUIRE(T >= 3 && idim >= 3, "subsampling: input (T=%d, idim=%d) shorter than the 3x3 kernel", T, idim);
-  M3_REQUIRE((C & 3) == 0 && C <= 1024, "subsampling: channels=%d must be a multiple of 4 (<= 1024)", C);
-  const int T1 = (T - 3) / 2 + 1, F1 = (idim - 3) / 2 + 1;
-  if (B * T1 == 0) return 0;
-  const int threads = (int)align_up(C / 4, 64);
-  const int fsplit = conv1_fsplit(B * T1);
-  hipLaunchKernelGGL(conv1_relu_kernel, dim3(B * T1, fsplit), dim3(threads), 3 * idim * sizeof(float), stream,
-                     feat, w9c, bias, cmvn_mean, cmvn_istd, T, idim, T1, F1, C, out, relu, out_bf16, feat_len, lens_out, B);
+int launch_conv1_relu(const Conv1Args& a, hipStream_t stream) {
+  if (int rc = check_conv1(a)) return rc;
+  const Conv1KernArgs k = conv1_pack(a);
+  if (k.rows == 0) return 0;
+  hipLaunchKernelGGL(conv1_relu_kernel, dim3(k.rows, k.fsplit), dim3(k.threads), 3 * a.idim * sizeof(float), stream, k);
   M3_LAUNCH_CHECK();
   return 0;
 }
-
-int launch_conv1_relu_args(const Conv1Args& a, hipStream_t stream) {
-  return launch_conv1_relu(a.feat, a.w9c, a.bias, a.cmvn_mean, a.cmvn_istd, a.B, a.T, a.idim, a.C, a.out, stream, a.relu, a.out_bf16, a.feat_len,
-                           a.lens_out);
-}
 bool conv1_dual_fusable(const Conv1Args& a, const Conv1Args& b) {
-  auto ok = [](const Conv1Args& q) { return q.T >= 3 && q.idim >= 3 && (q.C & 3) == 0 && q.C > 0 && q.C <= 1024; };
-  return ok(a) && ok(b) && a.B == b.B && a.T == b.T && a.idim == b.idim && a.B * ((a.T - 3) / 2 + 1) > 0 && a.out != b.out;
+  return check_conv1(a, false) == 0 && check_conv1(b, false) == 0 && a.B == b.B && a.T == b.T && a.idim == b.idim &&
+         a.B * ((a.T - 3) / 2 + 1) > 0 && a.out != b.out;
 }
 int launch_conv1_relu_dual(const Conv1Args& a, const Conv1Args& b, hipStream_t stream) {
   M3_REQUIRE(conv1_dual_fusable(a, b), "subsampling conv1 dual: the two problems do not share an input shape");
-  const int T1 = (a.T - 3) / 2 + 1, F1 = (a.idim - 3) / 2 + 1, rows = a.B * T1;
-  auto pack = [](const Conv1Args& q) {
-    return Conv1KernArgs{q.feat, q.w9c, q.bias, q.cmvn_mean, q.cmvn_istd, q.C, q.out, q.relu, q.out_bf16, q.feat_len, q.lens_out};
-  };
-  const int threads = (int)align_up((a.C > b.C ? a.C : b.C) / 4, 64);
-  const int n0 = (int)align_up((size_t)rows, 8);
-  hipLaunchKernelGGL(conv1_relu_dual_kernel, dim3(n0 + rows, conv1_fsplit(rows)), dim3(threads), 3 * a.idim * sizeof(float), stream, pack(a), pack(b),
-                     a.T, a.idim, T1, F1, a.B, rows, n0);
+  const Conv1KernArgs ka = conv1_pack(a), kb = conv1_pack(b);
+  const int n0 = (int)align_up((size_t)ka.rows, 8);
+  hipLaunchKernelGGL(conv1_relu_dual_kernel, dim3(n0 + kb.rows, ka.fsplit), dim3(ka.threads > kb.threads ? ka.threads : kb.threads),
+                     3 * a.idim * sizeof(float), stream, ka, kb, n0);
   M3_LAUNCH_CHECK();
   return 0;
 }

@@ -784,7 +784,7 @@ static void build_subsample(StageBuilder& sb, const std::string& pfx, const SubW
   Conv1Args ca;
   ca.feat = feat; ca.w9c = w.c1w; ca.bias = w.c1b; ca.cmvn_mean = cm; ca.cmvn_istd = ci; ca.B = B; ca.T = T; ca.idim = idim; ca.C = D; ca.out = c1;
   ca.relu = 1; ca.out_bf16 = a16; ca.feat_len = flen; ca.lens_out = lens_out;
-  add_stage(sb, pfx + "conv1", 1, [ca](hipStream_t s) { return launch_conv1_relu_args(ca, s); },
+  add_stage(sb, pfx + "conv1", 1, [ca](hipStream_t s) { return launch_conv1_relu(ca, s); },
             stage_info("conv1_relu_kernel", 1, (double)B * T * idim * 4 + (double)B * T1 * F1 * D * (a16 ? 2 : 4), 18.0 * B * T1 * F1 * D, false));
   const size_t conv1_at = sb.bd.stages.size() - 1;
   GemmParams g;
@@ -1092,26 +1092,22 @@ static void build_block(StageBuilder& sb, const std::string& pfx, const BlockW& 
     const int dk = D / H;
     const float scale = 1.f / sqrtf((float)dk);
     const int chunk = c.static_chunk_size, left_chunks = c.num_left_chunks;   // static chunk mask (0 = full context)
+    AttArgs aa;
+    aa.qkv = qkv; aa.ldq = 3 * D; aa.pmat = pmat; aa.ldp = ldp; aa.pos_u = pu; aa.pos_v = pv; aa.row_len = lens; aa.B = B; aa.T = Tp; aa.H = H;
+    aa.dk = dk; aa.scale = scale; aa.out = ctx; aa.ldo = D; aa.left_chunks = left_chunks;
+    const char* label = att16 ? "relpos_attention_bf16_kernel" : "relpos_attention_kernel";
+    double row_bytes = att16 ? 8 : (12 + (a16 ? 2 : 4));
     if (streaming) {   // chunk-by-chunk: keys = K / V history + this chunk, positions absolute, history appended in place
-      float* hist = sb.st.kv[tap_index]; const int cap = key.s_hist;
-      add_stage(sb, pfx + "att.core", 1, [=](hipStream_t s) {
-        return launch_relpos_attention_stream(qkv, 3 * D, hist, cap, pmat, ldp, pu, pv, lens, step, B, Tp, H, dk, scale, ctx, D, left_chunks, s,
-                                              slot_chunks);
-      }, stage_info("relpos_attention_stream_kernel", 1, (double)S * D * 24 + (double)Tp * D * 4, 6.0 * Tp * D * S));
-    } else
-    {
-    add_stage(sb, pfx + "att.core", 1, [=](hipStream_t s) {
-      if (att16) return launch_relpos_attention_bf16(qkv, 3 * D, pmat, ldp, pu, pv, lens, B, Tp, H, dk, scale, ctx, D, s, row0, chunk, left_chunks);
-      return launch_relpos_attention(qkv, 3 * D, pmat, ldp, pu, pv, lens, B, Tp, H, dk, scale, ctx, D, s, a16, row0, chunk, left_chunks);
-    }, stage_info(att16 ? "relpos_attention_bf16_kernel" : "relpos_attention_kernel", 1,
-                  (double)S * D * (att16 ? 8 : (12 + (a16 ? 2 : 4))) + (double)Tp * D * 4, 6.0 * Tp * D * S));
-    if (!att16) {      // (the fp32 core: a candidate for sharing a launch with the other encoder's, fuse_independent_pairs)
-      AttArgs aa;
-      aa.qkv = qkv; aa.ldq = 3 * D; aa.pmat = pmat; aa.ldp = ldp; aa.pos_u = pu; aa.pos_v = pv; aa.row_len = lens; aa.B = B; aa.T = Tp; aa.H = H;
-      aa.dk = dk; aa.scale = scale; aa.out = ctx; aa.ldo = D; aa.out_bf16 = a16; aa.row0 = row0; aa.chunk = chunk; aa.left_chunks = left_chunks;
+      aa.streaming = 1; aa.hist = sb.st.kv[tap_index]; aa.cap = key.s_hist; aa.step = step; aa.slot_max_chunks = slot_chunks;
+      label = "relpos_attention_stream_kernel"; row_bytes = 24;
+    } else {
+      aa.rows_bf16 = att16; aa.out_bf16 = a16; aa.row0 = row0; aa.chunk = chunk;
+    }
+    add_stage(sb, pfx + "att.core", 1, [aa](hipStream_t s) { return launch_relpos_attention(aa, s); },
+              stage_info(label, 1, (double)S * D * row_bytes + (double)Tp * D * 4, 6.0 * Tp * D * S));
+    if (!streaming && !att16) {   // (the fp32 core: a candidate for sharing a launch with the other encoder's, fuse_independent_pairs)
       sb.bd.stages.back().fuse_kind = FuseKind::Attention;
       sb.bd.stages.back().att = aa;
-    }
     }
     GemmParams o;
     o.A = pl.ctx; o.lda = D; o.W = w.out.w; o.bias = w.out.b; o.Y = x; o.ldy = D; o.M = S; o.N = D; o.K = D;
@@ -1148,19 +1144,21 @@ static void build_block(StageBuilder& sb, const std::string& pfx, const BlockW& 
     const float* dww = w.dw_w; const float* dwb = w.dw_b;
     const float* ng = cnn_ln ? w.n_cnn.g : nullptr; const float* nb = cnn_ln ? w.n_cnn.b : nullptr;
     const float* lfill = causal ? w.left_fill : nullptr;   // causal conv module (convolution.py:43-49,118-123)
+    DwArgs da;
+    da.z = glu; da.w_kc = dww; da.bias = dwb; da.gamma = ng; da.beta = nb; da.eps = 1e-5f; da.B = B; da.T = Tp; da.D = D; da.K = K;
+    da.out = dw; da.out_bf16 = a16;
+    double row_bytes = (glu_deferred ? 8 : 4) + (a16 ? 2 : 4), cache_bytes = 0.0;
     if (streaming) {
-      float* cpair = sb.st.conv[tap_index];
-      add_stage(sb, pfx + "conv.dw_ln_silu", 1, [=](hipStream_t s) {
-        return launch_dwconv_ln_silu_stream(glu, dww, dwb, ng, nb, 1e-5f, B, Tp, D, K, dw, cpair, step, lens, s, a16, slot_chunks);
-      }, stage_info("dwconv_ln_silu_kernel", 1, (double)S * D * 8 + (double)K * D * 4 + 8.0 * B * (K - 1) * D, 2.0 * K * D * S));
-    } else
-    {
-      DwArgs da;
-      da.z = glu; da.w_kc = dww; da.bias = dwb; da.gamma = ng; da.beta = nb; da.eps = 1e-5f; da.B = B; da.T = Tp; da.D = D; da.K = K;
-      da.out = dw; da.out_bf16 = a16; da.pad_of = pad_of; da.row0 = row0; da.row_len = lens; da.causal_left_fill = lfill;
+      da.streaming = 1; da.cache_pair = sb.st.conv[tap_index]; da.step = step; da.chunk_len = lens; da.slot_max_chunks = slot_chunks;
+      row_bytes = 8; cache_bytes = 8.0 * B * (K - 1) * D;
+    } else {
+      da.pad_of = pad_of; da.row0 = row0; da.row_len = lens; da.causal_left_fill = lfill;
       da.glu_ldz = glu_deferred ? 2 * D : 0; da.glu_sig = glu_sig;
-      add_stage(sb, pfx + "conv.dw_ln_silu", 1, [da](hipStream_t s) { return launch_dwconv_ln_silu_args(da, s); },
-                stage_info("dwconv_ln_silu_kernel", 1, (double)S * D * ((glu_deferred ? 8 : 4) + (a16 ? 2 : 4)) + (double)K * D * 4, 2.0 * K * D * S));
+    }
+    add_stage(sb, pfx + "conv.dw_ln_silu", 1, [da](hipStream_t s) { return launch_dwconv_ln_silu(da, s); },
+              stage_info("dwconv_ln_silu_kernel", 1, (double)S * D * row_bytes + (double)K * D * 4 + cache_bytes,
+                         2.0 * K * D * S));
+    if (!streaming) {
       sb.bd.stages.back().fuse_kind = FuseKind::Dwconv;
       sb.bd.stages.back().dw = da;
     }

@@ -289,37 +289,27 @@ int launch_bmm(const float* a, const float* b, float* c, int batch, int M, int N
                int trans_b, hipStream_t stream);
 
 // ---- fused rel-pos attention (attention.hip) ----
-int launch_relpos_attention(const float* qkv, int ldq, const float* pmat, int ldp, const float* pos_u,
-                            const float* pos_v, const int32_t* row_len, int B, int T, int H, int dk, float scale,
-                            float* out, int ldo, hipStream_t stream, int out_bf16 = 0, const int32_t* row0 = nullptr,
-                            int chunk = 0, int left_chunks = -1);
-// the same as a value (what the engine keeps per stage so that two independent attention stages can share a launch)
+// One record per problem (what the engine keeps per stage and the C ABI fills from its descriptor), one check, one launcher for the
+// three cores; two fp32 problems with head widths 64 or 128 each can share a launch.
+//   fp32 rows (default): qkv fp32 [B*T][ldq], out fp32 (or bf16 with out_bf16) [B*T][ldo]
+//   rows_bf16 (16-bit modes, T' <= 128): qkv bf16 [B*T][ldq], out bf16; one work-group per (utterance, head)
+//   streaming (chunk by chunk): T query frames per utterance (row_len: the valid ones), K / V history hist [B][cap][2 D] appended
+//   to in place, device-side chunk counter `step`
 struct AttArgs {
-  const float* qkv = nullptr; int ldq = 0; const float* pmat = nullptr; int ldp = 0; const float *pos_u = nullptr, *pos_v = nullptr;
-  const int32_t* row_len = nullptr; int B = 0, T = 0, H = 0, dk = 0; float scale = 1.f; float* out = nullptr; int ldo = 0, out_bf16 = 0;
-  const int32_t* row0 = nullptr; int chunk = 0, left_chunks = 0;
+  const void* qkv = nullptr; int ldq = 0; const float* pmat = nullptr; int ldp = 0; const float *pos_u = nullptr, *pos_v = nullptr;
+  const int32_t* row_len = nullptr; int B = 0, T = 0, H = 0, dk = 0; float scale = 1.f; void* out = nullptr; int ldo = 0, out_bf16 = 0;
+  const int32_t* row0 = nullptr; int chunk = 0, left_chunks = 0;   // chunk > 0: static chunk mask (utils/mask.py:42-75)
+  int rows_bf16 = 0;
+  int streaming = 0; float* hist = nullptr; int cap = 0; const int32_t* step = nullptr;
+  int slot_max_chunks = -1;   // >= 0: slot mode, step [B] = one counter per slot, max_frames / T
 };
-int launch_relpos_attention_args(const AttArgs& a, hipStream_t stream);
+int launch_relpos_attention(const AttArgs& a, hipStream_t stream);
 bool relpos_attention_dual_fusable(const AttArgs& a, const AttArgs& b);
-int launch_relpos_attention_dual(const AttArgs& a, const AttArgs& b, hipStream_t stream);   // chunk > 0: static chunk mask (utils/mask.py:42-75)
-// chunk-by-chunk form: C query frames per utterance, K / V history [B][cap][2D] appended to in place, device-side chunk counter
-int launch_relpos_attention_stream(const float* qkv, int ldq, float* hist, int cap, const float* pmat, int ldp, const float* pos_u,
-                                   const float* pos_v, const int32_t* chunk_len, const int32_t* step, int B, int C, int H, int dk,
-                                   float scale, float* out, int ldo, int left_chunks, hipStream_t stream,
-                                   int slot_max_chunks = -1);   // >= 0: slot mode, step [B] = one counter per slot, max_frames / C
-
-// the same on bf16 rows (16-bit modes, T' <= 128): qkv bf16 [B*T][ldq], out bf16; one work-group per (utterance, head)
+int launch_relpos_attention_dual(const AttArgs& a, const AttArgs& b, hipStream_t stream);
 bool relpos_attention_bf16_supports(int T, int dk);
 int init_relpos_attention_bf16_kernels();
-int launch_relpos_attention_bf16(const void* qkv, int ldq, const float* pmat, int ldp, const float* pos_u, const float* pos_v,
-                                 const int32_t* row_len, int B, int T, int H, int dk, float scale, void* out, int ldo,
-                                 hipStream_t stream, const int32_t* row0 = nullptr, int chunk = 0, int left_chunks = -1);
 
 // ---- conv module / subsampling (conv.hip) ----
-int launch_dwconv_ln_silu(const float* z, const float* w_kc, const float* bias, const float* gamma,
-                          const float* beta, float eps, int B, int T, int D, int K, float* out, hipStream_t stream,
-                          int out_bf16 = 0, const int32_t* pad_of = nullptr, const int32_t* row0 = nullptr,
-                          const int32_t* row_len = nullptr, const float* causal_left_fill = nullptr);   // non-null: causal conv (lorder K-1)
 int launch_pad2d(const float* x, size_t outer, int H, int W, int pre_h, int post_h, int pre_w, int post_w, float* y, hipStream_t stream);
 int launch_advance_counter(int32_t* counter, int by, hipStream_t stream);
 int launch_fill_rows(const float* row, int D, float* out, size_t rows, hipStream_t stream);
@@ -336,36 +326,35 @@ struct SlotResetArgs {
 };
 int launch_reset_slots(const SlotResetArgs& a, hipStream_t stream);
 int launch_slot_positions(const int32_t* status, const int32_t* frames, int B, int32_t* out, hipStream_t stream);
-// the same as a value (what the engine keeps per stage so that two independent conv modules can share a launch)
+// The conv module's depthwise conv + LayerNorm + SiLU: one record per problem (what the engine keeps per stage and the C ABI fills
+// from its descriptor), one check, one launcher; two problems of one instantiation can share a launch
 struct DwArgs {
   const float *z = nullptr, *w_kc = nullptr, *bias = nullptr, *gamma = nullptr, *beta = nullptr; float eps = 1e-5f;
   int B = 0, T = 0, D = 0, K = 0; float* out = nullptr; int out_bf16 = 0;
-  const int32_t *pad_of = nullptr, *row0 = nullptr, *row_len = nullptr; const float* causal_left_fill = nullptr;
+  const int32_t *pad_of = nullptr, *row0 = nullptr, *row_len = nullptr;
+  const float* causal_left_fill = nullptr;   // non-null: causal conv (lorder K-1), the row [D] every frame left of frame 0 holds
   int glu_ldz = 0;   // > 0: z is pointwise_conv1's raw [B*T][glu_ldz] output (value | gate columns), GLU applied as the taps are loaded
   int glu_sig = 0;   // (with glu_ldz) the gate columns hold sigmoid(gate) already (GemmParams::sig_col0): every tap is one multiply
+  // chunk-by-chunk (streaming) form of the causal conv: cache_pair [2][B][K-1][D], chunk counter and valid frames on the device
+  int streaming = 0; float* cache_pair = nullptr; const int32_t *step = nullptr, *chunk_len = nullptr;
+  int slot_max_chunks = -1;   // >= 0: slot mode, step [B]
 };
-int launch_dwconv_ln_silu_args(const DwArgs& a, hipStream_t stream);
+int launch_dwconv_ln_silu(const DwArgs& a, hipStream_t stream);
 bool dwconv_glu_in_supports(int D, int K, bool causal_or_stream, int out_bf16, int ldz);   // what the GLU-on-load form takes
 bool dwconv_dual_fusable(const DwArgs& a, const DwArgs& b);
 int launch_dwconv_ln_silu_dual(const DwArgs& a, const DwArgs& b, hipStream_t stream);
-int launch_dwconv_ln_silu_stream(const float* z, const float* w_kc, const float* bias, const float* gamma, const float* beta,
-                                 float eps, int B, int T, int D, int K, float* out, float* cache_pair, const int32_t* step,
-                                 const int32_t* chunk_len, hipStream_t stream, int out_bf16 = 0,
-                                 int slot_max_chunks = -1);     // >= 0: slot mode, step [B]
 // packed (padding-free) rows of a ragged batch (rowops.hip): plan from the valid lengths; padded output from packed rows
 int launch_pack_plan(int32_t* len, int B, int T, int32_t* row0, int32_t* pad_of, hipStream_t stream,
                      const int32_t* feat_len = nullptr);   // feat_len: form the subsampled lengths here too (len becomes an output)
 int launch_unpack_rows(const float* in, const int32_t* row0, int B, int T, int n, float* out, hipStream_t stream);
-int launch_conv1_relu(const float* feat, const float* w9c, const float* bias, const float* cmvn_mean,
-                      const float* cmvn_istd, int B, int T, int idim, int C, float* out, hipStream_t stream, int relu = 1,
-                      int out_bf16 = 0, const int32_t* feat_len = nullptr, int32_t* lens_out = nullptr);   // feat_len: also the subsampled lengths
-// the same as a value (what the engine keeps per stage so that the two subsamplers' first convs can share a launch)
+// The subsamplers' first conv: one record per problem (what the engine keeps per stage and the C ABI fills from its descriptor),
+// one check, one launcher; two problems on the same input shape can share a launch
 struct Conv1Args {
   const float *feat = nullptr, *w9c = nullptr, *bias = nullptr, *cmvn_mean = nullptr, *cmvn_istd = nullptr;
   int B = 0, T = 0, idim = 0, C = 0; float* out = nullptr; int relu = 1, out_bf16 = 0;
-  const int32_t* feat_len = nullptr; int32_t* lens_out = nullptr;
+  const int32_t* feat_len = nullptr; int32_t* lens_out = nullptr;   // feat_len: the launch also forms the subsampled lengths
 };
-int launch_conv1_relu_args(const Conv1Args& a, hipStream_t stream);
+int launch_conv1_relu(const Conv1Args& a, hipStream_t stream);
 bool conv1_dual_fusable(const Conv1Args& a, const Conv1Args& b);
 int launch_conv1_relu_dual(const Conv1Args& a, const Conv1Args& b, hipStream_t stream);
 int launch_cmvn(const float* x, const int32_t* len, const float* mean, const float* istd, int B, int T, int D,

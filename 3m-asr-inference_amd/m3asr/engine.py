@@ -342,6 +342,7 @@ class StreamingEncoder:
         self.ws = torch.empty(engine.workspace_size(B, self.window), dtype=torch.uint8, device=dev)
         self.chunks = 0
         self.slot_chunks = None           # slot mode: host mirror of the per-slot chunk counters (None: not known)
+        engine.stream.wait_stream(torch.cuda.current_stream())    # the fills above are queued on the caller's stream, steps run on the engine's
         self.reset()
 
     def reset(self, slots=None):

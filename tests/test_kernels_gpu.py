@@ -315,7 +315,8 @@ def test_fmoe_expert_position_independence_long_batch():
                                            (3, 9, 2, 16, [9, 6, 1]), (1, 124, 8, 64, [124]),
                                            # >= 128 workgroups of 64 queries: one 16-query tile per wave, no merge
                                            (16, 124, 8, 64, [124, 12, 99, 124, 77, 64, 65, 1, 124, 33, 120, 124, 50, 63, 17, 101]),
-                                           (12, 70, 4, 128, [70, 66, 3, 64, 65, 70, 1, 20, 70, 70, 48, 49])])
+                                           (12, 70, 4, 128, [70, 66, 3, 64, 65, 70, 1, 20, 70, 70, 48, 49]),
+                                           (2, 33, 4, 32, [33, 16])])   # d_k = 32 (last: the rows above keep their ids)
 def test_relpos_attention(B, T, H, dk, lens):
     D = H * dk
     qkv, p = rnd(B * T, 3 * D, seed=1), rnd(T, D, seed=2)
@@ -361,7 +362,8 @@ def test_relpos_attention_bf16(B, T, H, dk, lens):
 
 # ------------------------------------------------------------------------------------------ conv pieces
 @pytest.mark.parametrize("B,T,D,K", [(1, 50, 512, 15), (2, 36, 512, 15), (2, 9, 32, 15), (1, 5, 64, 7),
-                                     (16, 124, 512, 15), (7, 99, 512, 7), (130, 5, 64, 15)])   # >= 512 rows: 8 frames per workgroup
+                                     (16, 124, 512, 15), (7, 99, 512, 7), (130, 5, 64, 15),    # >= 512 rows: 8 frames per workgroup
+                                     (2, 9, 32, 17), (1, 40, 64, 31)])   # K > 15: the taps in batches of 8 (T > K: every tap position)
 def test_dwconv_ln_silu(B, T, D, K):
     z, w, b = rnd(B, T, D, seed=1), rnd(D, 1, K, seed=2, scale=0.3), rnd(D, seed=3, scale=0.1)
     g, be = rnd(D, seed=4) * 0.2 + 1.0, rnd(D, seed=5, scale=0.1)
@@ -371,7 +373,9 @@ def test_dwconv_ln_silu(B, T, D, K):
     close(out, (y * torch.sigmoid(y)).reshape(B * T, D), 2e-5, 2e-5)
 
 
-@pytest.mark.parametrize("B,T,idim,C", [(1, 206, 40, 512), (2, 40, 40, 32), (2, 61, 40, 64)])
+@pytest.mark.parametrize("B,T,idim,C", [(1, 206, 40, 512), (2, 40, 40, 32), (2, 61, 40, 64),
+                                        # conv1's column split changes at B * T1 = 512 and 2048 rows: 511, 512, 2047, 2048
+                                        (7, 147, 16, 32), (8, 129, 16, 32), (23, 179, 16, 32), (32, 129, 16, 32)])
 def test_subsampling_convs(B, T, idim, C):
     feat = torch.rand(B, T, idim, generator=torch.Generator().manual_seed(1))
     w0, b0 = rnd(C, 1, 3, 3, seed=2, scale=1 / 3), rnd(C, seed=3, scale=0.1)
