@@ -344,7 +344,7 @@ int m3_linear_ws(const m3_linear_desc* d, void* workspace, size_t workspace_byte
   GemmParams p;
   if (int rc = linear_params(d, &p)) return rc;
   if (int rc = linear_pointers(d)) return rc;
-  return launch_gemm(plan_gemm(p, workspace != nullptr ? workspace_bytes : 0), p, (float*)workspace, (hipStream_t)stream);
+  return launch_gemm(gemm_launch(p, (float*)workspace, workspace_bytes), (hipStream_t)stream);
 }
 
 int m3_layer_norm(const float* x, const float* gamma, const float* beta, float eps, float* y, int rows, int dim,
@@ -519,7 +519,7 @@ int m3_conv2d_3x3s2_ws(const float* in, const float* w, const float* bias, int B
                        void* workspace, size_t workspace_bytes, m3_stream stream) {
   GemmParams p;
   if (int rc = conv2d_params(in, w, bias, B, T1, F1, C, act, out, &p)) return rc;
-  return launch_gemm(plan_gemm(p, workspace != nullptr ? workspace_bytes : 0), p, (float*)workspace, (hipStream_t)stream);
+  return launch_gemm(gemm_launch(p, (float*)workspace, workspace_bytes), (hipStream_t)stream);
 }
 
 // ---- the paired launches at the boundary (include/m3asr.h): both problems checked as their single entries check them, outputs
@@ -531,7 +531,8 @@ static bool ranges_overlap(const void* a, size_t bytes_a, const void* b, size_t 
 static size_t rows_bytes(long rows, long ld, long width) { return rows > 0 ? (size_t)((rows - 1) * ld + width) * sizeof(float) : 0; }
 static size_t linear_out_bytes(const m3_linear_desc* d) { return rows_bytes(d->M, d->ldy, d->act == M3_ACT_GLU ? d->N / 2 : d->N); }
 // why two plans have no common instantiation of gemm_f32_dual_kernel, as text (gemm_dual_fusable says only that)
-static int linear_pair_plans(const GemmPlan& pa, const GemmPlan& pb) {
+static int linear_pair_plans(const GemmLaunch& a, const GemmLaunch& b) {
+  const GemmPlan &pa = a.plan, &pb = b.plan;
   const GemmPlan* const plans[2] = {&pa, &pb};
   for (int i = 0; i < 2; ++i) {
     const GemmPlan& q = *plans[i];
@@ -541,34 +542,34 @@ static int linear_pair_plans(const GemmPlan& pa, const GemmPlan& pb) {
                "linear pair: problem %d has %d-row tiles, %d waves, %d load group%s: the paired kernel takes 16-row tiles, 4 or 8 waves, one load "
                "group, plain a, no affine LayerNorm", i, 16 * q.mt, q.nw, q.nbuf, q.nbuf == 1 ? "" : "s");
   }
-  M3_REQUIRE(gemm_dual_fusable(pa, pb), "linear pair: the problems differ in waves (%d / %d), folded LayerNorm (%d / %d) or GLU (%d / %d)",
+  M3_REQUIRE(gemm_dual_fusable(a, b), "linear pair: the problems differ in waves (%d / %d), folded LayerNorm (%d / %d) or GLU (%d / %d)",
              pa.nw, pb.nw, pa.ln != GEMM_LN_NONE, pb.ln != GEMM_LN_NONE, (int)pa.glu, (int)pb.glu);
   return 0;
 }
+// (m3_linear_pair_kernel asks about plans made against any workspace: the workspaces themselves are the launch's to check)
 static int splitk_pair_plans(const char* who, const GemmPlan& pa, const GemmPlan& pb) {
   const GemmPlan* const plans[2] = {&pa, &pb};
   for (int i = 0; i < 2; ++i) {
     M3_REQUIRE(plans[i]->launches > 0, "%s", plans[i]->reason);
     M3_REQUIRE(plans[i]->kernel == GemmKernel::SplitKF32, "%s: problem %d is no split-K problem with its workspace (it runs %s)", who, i, plans[i]->label);
   }
-  M3_REQUIRE(gemm_splitk_dual_fusable(pa, pb), "%s: an implicit conv pairs with an implicit conv, a plain problem with a plain one", who);
+  M3_REQUIRE(pa.conv == pb.conv, "%s: an implicit conv pairs with an implicit conv, a plain problem with a plain one", who);
   return 0;
 }
-static int splitk_pair_launch(const char* who, const GemmParams& pa, void* ws_a, size_t bytes_a, const void* out_a, size_t out_bytes_a,
-                              const GemmParams& pb, void* ws_b, size_t bytes_b, const void* out_b, size_t out_bytes_b, int which, m3_stream stream) {
+static int splitk_pair_launch(const char* who, const GemmLaunch& a, const void* out_a, size_t out_bytes_a, const GemmLaunch& b, const void* out_b,
+                              size_t out_bytes_b, int which, m3_stream stream) {
   M3_REQUIRE(which >= 1 && which <= 3, "%s: which=%d (1 the GEMM launch, 2 the reduce launch, 3 both)", who, which);
-  const GemmPlan qa = plan_gemm(pa, ws_a != nullptr ? bytes_a : 0), qb = plan_gemm(pb, ws_b != nullptr ? bytes_b : 0);
-  if (int rc = splitk_pair_plans(who, qa, qb)) return rc;
-  M3_REQUIRE(!ranges_overlap(ws_a, qa.ws_bytes, ws_b, qb.ws_bytes), "%s: each problem needs its own workspace", who);
+  if (int rc = splitk_pair_plans(who, a.plan, b.plan)) return rc;
+  M3_REQUIRE(!ranges_overlap(a.ws, a.plan.ws_bytes, b.ws, b.plan.ws_bytes), "%s: each problem needs its own workspace", who);
   M3_REQUIRE(!ranges_overlap(out_a, out_bytes_a, out_b, out_bytes_b), "%s: the two outputs overlap", who);
-  return launch_gemm_f32_splitk_dual(qa, pa, (float*)ws_a, qb, pb, (float*)ws_b, (hipStream_t)stream, which);
+  return launch_gemm_f32_splitk_dual(a, b, (hipStream_t)stream, which);
 }
 const char* m3_linear_pair_kernel(const m3_linear_desc* a, const m3_linear_desc* b, int with_workspace) {
   GemmParams pa, pb;
   if (linear_params(a, &pa) || linear_params(b, &pb)) return nullptr;
   const size_t ws = with_workspace ? SIZE_MAX : 0;
-  const GemmPlan qa = plan_gemm(pa, ws), qb = plan_gemm(pb, ws);
-  if (with_workspace) return splitk_pair_plans("linear pair (workspaces)", qa, qb) ? nullptr : "gemm_f32_splitk_dual_kernel";
+  const GemmLaunch qa{pa, plan_gemm(pa, ws)}, qb{pb, plan_gemm(pb, ws)};
+  if (with_workspace) return splitk_pair_plans("linear pair (workspaces)", qa.plan, qb.plan) ? nullptr : "gemm_f32_splitk_dual_kernel";
   return linear_pair_plans(qa, qb) ? nullptr : "gemm_f32_dual_kernel";
 }
 int m3_linear_pair(const m3_linear_desc* a, const m3_linear_desc* b, m3_stream stream) {
@@ -577,10 +578,10 @@ int m3_linear_pair(const m3_linear_desc* a, const m3_linear_desc* b, m3_stream s
   if (int rc = linear_params(b, &pb)) return rc;
   if (int rc = linear_pointers(a)) return rc;
   if (int rc = linear_pointers(b)) return rc;
-  const GemmPlan qa = plan_gemm(pa, 0), qb = plan_gemm(pb, 0);
+  const GemmLaunch qa = gemm_launch(pa, nullptr, 0), qb = gemm_launch(pb, nullptr, 0);
   if (int rc = linear_pair_plans(qa, qb)) return rc;
   M3_REQUIRE(!ranges_overlap(a->y, linear_out_bytes(a), b->y, linear_out_bytes(b)), "linear pair: the two outputs overlap");
-  return launch_gemm_f32_dual(qa, pa, qb, pb, (hipStream_t)stream);
+  return launch_gemm_f32_dual(qa, qb, (hipStream_t)stream);
 }
 int m3_linear_ws_pair(const m3_linear_desc* a, void* workspace_a, size_t bytes_a, const m3_linear_desc* b, void* workspace_b,
                       size_t bytes_b, int which, m3_stream stream) {
@@ -589,8 +590,8 @@ int m3_linear_ws_pair(const m3_linear_desc* a, void* workspace_a, size_t bytes_a
   if (int rc = linear_params(b, &pb)) return rc;
   if (int rc = linear_pointers(a)) return rc;
   if (int rc = linear_pointers(b)) return rc;
-  return splitk_pair_launch("linear pair (workspaces)", pa, workspace_a, bytes_a, a->y, linear_out_bytes(a), pb, workspace_b, bytes_b, b->y,
-                            linear_out_bytes(b), which, stream);
+  return splitk_pair_launch("linear pair (workspaces)", gemm_launch(pa, (float*)workspace_a, bytes_a), a->y, linear_out_bytes(a),
+                            gemm_launch(pb, (float*)workspace_b, bytes_b), b->y, linear_out_bytes(b), which, stream);
 }
 int m3_conv2d_3x3s2_ws_pair(const m3_conv2d_desc* a, void* workspace_a, size_t bytes_a, const m3_conv2d_desc* b, void* workspace_b,
                             size_t bytes_b, int which, m3_stream stream) {
@@ -599,8 +600,8 @@ int m3_conv2d_3x3s2_ws_pair(const m3_conv2d_desc* a, void* workspace_a, size_t b
   if (int rc = conv2d_params(a->in, a->w, a->bias, a->B, a->T1, a->F1, a->C, a->act, a->out, &pa)) return rc;
   if (int rc = conv2d_params(b->in, b->w, b->bias, b->B, b->T1, b->F1, b->C, b->act, b->out, &pb)) return rc;
   M3_REQUIRE(a->in && a->w && a->out && b->in && b->w && b->out, "conv2d pair: null in / w / out");
-  return splitk_pair_launch("conv2d pair", pa, workspace_a, bytes_a, a->out, rows_bytes(pa.M, pa.ldy, pa.N), pb, workspace_b, bytes_b, b->out,
-                            rows_bytes(pb.M, pb.ldy, pb.N), which, stream);
+  return splitk_pair_launch("conv2d pair", gemm_launch(pa, (float*)workspace_a, bytes_a), a->out, rows_bytes(pa.M, pa.ldy, pa.N),
+                            gemm_launch(pb, (float*)workspace_b, bytes_b), b->out, rows_bytes(pb.M, pb.ldy, pb.N), which, stream);
 }
 int m3_relpos_attention_pair(const m3_attention_desc* a, const m3_attention_desc* b, m3_stream stream) {
   M3_REQUIRE(a != nullptr && b != nullptr, "attention pair: null descriptor");

@@ -19,6 +19,7 @@
 #include <memory>
 #include <string>
 #include <unordered_map>
+#include <variant>
 #include <vector>
 
 #include "../../include/m3asr.h"
@@ -54,24 +55,25 @@ struct BlockW {
 
 struct SubW { const float* c1w; const float* c1b; const float* c2w; const float* c2b; Lin out; };
 
-// what horizontal fusion pairs up (fuse_independent_pairs): a one-launch dense GEMM stage (Stage::gemm + its plan), the conv module's
-// depthwise conv + LayerNorm + SiLU (Stage::dw), the fp32 rel-pos attention core (Stage::att), and of the two subsamplers the first
-// conv (Stage::c1) and the split-K GEMM + reduce stages (Stage::gemm + its plan + Stage::gemm_ws; two launches before and after)
-enum class FuseKind { None, Gemm, Dwconv, Attention, Conv1, SplitK };
+// One launch of a kernel family, as the family's host record (kernels.h).  A stage that is one such launch holds the record and
+// nothing else: run_stage runs it from the record, and horizontal fusion (fuse_independent_pairs) pairs two stages by reading
+// the same records -- a one-launch dense GEMM, the conv module's depthwise conv + LayerNorm + SiLU, the fp32 rel-pos attention
+// core, and of the two subsamplers the first conv and the split-K GEMM + reduce stages (two launches before and after).
+using Launch = std::variant<std::monostate, GemmLaunch, Conv1Args, DwArgs, AttArgs>;
 
 struct Stage {
   std::string name;
-  std::function<int(hipStream_t)> run;
+  std::function<int(hipStream_t)> run;   // a stage that is NOT one family launch (MoE stages, layernorm, pack, taps, a fused pair)
   m3_stage_info info;   // kernel label + algorithmic bytes / FLOPs of the stage (m3_engine_stage_info)
   bool reads_embed = false;   // reads the embed encoder's output (pl.emb, or pl.eall computed from it): where the chains join
-  FuseKind fuse_kind = FuseKind::None;
-  GemmParams gemm; GemmPlan gemm_plan; float* gemm_ws = nullptr;
-  Conv1Args c1;
-  DwArgs dw;
-  AttArgs att;
+  Launch launch;              // the record of the one launch the stage is (empty: the stage is what `run` does)
+  bool pairable = false;      // a record stage that may share its launch with a stage of the other encoder
+  bool router_prefix = false;   // the "router_e_prefix" stage (Bound::prefix_stage)
   // a router stage that starts from the accumulator prefix of "router_e_prefix": recomputes its layer's slice (m3_engine_run)
   std::function<int(hipStream_t)> refresh_prefix;
 };
+const GemmLaunch& gemm_of(const Stage& st) { return std::get<GemmLaunch>(st.launch); }
+bool is_splitk(const Stage& st) { return std::holds_alternative<GemmLaunch>(st.launch) && gemm_of(st).plan.kernel == GemmKernel::SplitKF32; }
 
 m3_stage_info stage_info(const char* kernel, int launches, double bytes, double flops, bool per_row = true) {
   m3_stage_info i;
@@ -659,22 +661,20 @@ static m3_stage_info gemm_info(const GemmParams& p, const GemmPlan& plan) {
   return stage_info(plan.label, 1, bytes, 2.0 * M * N * K, p.mode != GEMM_A_CONV3X3S2);
 }
 
+static void add_launch(StageBuilder& sb, const std::string& name, Launch record, const m3_stage_info& info, bool pairable = false) {
+  add_stage(sb, name, info.launches, nullptr, info);
+  sb.bd.stages.back().launch = std::move(record);
+  sb.bd.stages.back().pairable = pairable;
+}
+
 // fp32_weights: the router GEMMs keep fp32 weights in every mode (a flipped top-1 is a discrete error)
 static void add_gemm(StageBuilder& sb, const std::string& name, GemmParams p, bool fp32_weights = false) {
   p.w_bf16 = (!fp32_weights && sb.eng.cfg.weight_dtype != M3_F32) ? 1 : 0;
-  // planned once, when the shape is bound: the stage runs the plan it captures (a plan no kernel takes fails there, with its reason)
-  float* ws = sb.splitk_ws;
-  const GemmPlan plan = plan_gemm(p, ws != nullptr ? sb.splitk_bytes : 0);
-  add_stage(sb, name, plan.launches ? plan.launches : 1, [plan, p, ws](hipStream_t s) { return launch_gemm(plan, p, ws, s); }, gemm_info(p, plan));
-  if (plan.launches == 1) {
-    sb.bd.stages.back().fuse_kind = FuseKind::Gemm;
-    sb.bd.stages.back().gemm = p;
-    sb.bd.stages.back().gemm_plan = plan;
-  } else if (plan.kernel == GemmKernel::SplitKF32 && plan.launches == 2) {   // (build_subsample decides whether it may pair)
-    sb.bd.stages.back().gemm = p;
-    sb.bd.stages.back().gemm_plan = plan;
-    sb.bd.stages.back().gemm_ws = ws;
-  }
+  // planned once, when the shape is bound: the stage runs the record made here (a plan no kernel takes fails there, with its reason)
+  const GemmLaunch g = gemm_launch(p, sb.splitk_ws, sb.splitk_bytes);
+  m3_stage_info info = gemm_info(p, g.plan);
+  info.launches = g.plan.launches ? g.plan.launches : 1;
+  add_launch(sb, name, g, info, g.plan.launches == 1);   // (a split-K stage: build_subsample decides whether it may pair)
 }
 
 // Horizontal fusion (B = 1-sized fp32 plans): the embed encoder and the main encoder's prefix -- its subsampling and block 0 up to
@@ -684,45 +684,42 @@ static void add_gemm(StageBuilder& sb, const std::string& name, GemmParams p, bo
 // later kernel reads) is guaranteed to stay in front of every main-prefix stage.  Arithmetic per problem is unchanged: results
 // are bit-identical.  M3_HFUSE=0: off.
 static bool stages_fusable(const Stage& a, const Stage& b) {
-  if (a.fuse_kind == FuseKind::None || a.fuse_kind != b.fuse_kind) return false;
-  if (a.fuse_kind == FuseKind::Gemm) return gemm_dual_fusable(a.gemm_plan, b.gemm_plan);
-  if (a.fuse_kind == FuseKind::Dwconv) return dwconv_dual_fusable(a.dw, b.dw);
-  if (a.fuse_kind == FuseKind::Attention) return relpos_attention_dual_fusable(a.att, b.att);
-  if (a.fuse_kind == FuseKind::Conv1) return conv1_dual_fusable(a.c1, b.c1);
-  if (a.fuse_kind == FuseKind::SplitK) return gemm_splitk_dual_fusable(a.gemm_plan, b.gemm_plan) && a.gemm_ws != b.gemm_ws;
-  return false;
+  if (!a.pairable || !b.pairable || a.launch.index() != b.launch.index()) return false;
+  if (std::holds_alternative<GemmLaunch>(a.launch))   // (one launch each, or split-K + reduce each)
+    return is_splitk(a) ? gemm_splitk_dual_fusable(gemm_of(a), gemm_of(b)) : gemm_dual_fusable(gemm_of(a), gemm_of(b));
+  if (auto* d = std::get_if<DwArgs>(&a.launch)) return dwconv_dual_fusable(*d, std::get<DwArgs>(b.launch));
+  if (auto* t = std::get_if<AttArgs>(&a.launch)) return relpos_attention_dual_fusable(*t, std::get<AttArgs>(b.launch));
+  return conv1_dual_fusable(std::get<Conv1Args>(a.launch), std::get<Conv1Args>(b.launch));
 }
+// The pair of two fusable stages as one closure stage (never pairable again), from the records the two would have run.
 // (a split-K pair is two stages, the GEMM launch and the reduce launch -- `reduce_half`, named a.reduce+b.reduce: every stage
 //  named a+b is one launch that replaces two)
 static Stage fused_stage(const Stage& a, const Stage& b, bool reduce_half = false) {
   Stage d;
   d.name = reduce_half ? a.name + ".reduce+" + b.name + ".reduce" : a.name + "+" + b.name;
   const char* label = "";
-  if (a.fuse_kind == FuseKind::Conv1) {
-    const Conv1Args pa = a.c1, pb = b.c1;
-    d.run = [pa, pb](hipStream_t s) { return launch_conv1_relu_dual(pa, pb, s); };
-    label = "conv1_relu_dual_kernel";
-  } else if (a.fuse_kind == FuseKind::SplitK) {
-    const GemmParams pa = a.gemm, pb = b.gemm;
-    const GemmPlan qa = a.gemm_plan, qb = b.gemm_plan;
-    float* const wa = a.gemm_ws; float* const wb = b.gemm_ws;
-    const int which = reduce_half ? 2 : 1;
-    d.run = [qa, pa, wa, qb, pb, wb, which](hipStream_t s) { return launch_gemm_f32_splitk_dual(qa, pa, wa, qb, pb, wb, s, which); };
-    label = "gemm_f32_splitk_dual_kernel";   // (both halves: the unpaired stage carries its reduce under the GEMM's label too)
-  } else if (a.fuse_kind == FuseKind::Gemm) {
-    const GemmParams pa = a.gemm, pb = b.gemm;
-    const GemmPlan qa = a.gemm_plan, qb = b.gemm_plan;
-    d.run = [qa, pa, qb, pb](hipStream_t s) { return launch_gemm_f32_dual(qa, pa, qb, pb, s); };
-    label = "gemm_f32_dual_kernel";
-  } else if (a.fuse_kind == FuseKind::Dwconv) {
-    const DwArgs pa = a.dw, pb = b.dw;
-    d.run = [pa, pb](hipStream_t s) { return launch_dwconv_ln_silu_dual(pa, pb, s); };
-    label = "dwconv_ln_silu_dual_kernel";
-  } else {
-    const AttArgs pa = a.att, pb = b.att;
-    d.run = [pa, pb](hipStream_t s) { return launch_relpos_attention_dual(pa, pb, s); };
-    label = "relpos_attention_dual_kernel";
-  }
+  std::visit([&](const auto& pa) {
+    using R = std::decay_t<decltype(pa)>;
+    if constexpr (std::is_same_v<R, GemmLaunch>) {
+      const GemmLaunch& pb = gemm_of(b);
+      if (is_splitk(a)) {
+        d.run = [pa, pb, which = reduce_half ? 2 : 1](hipStream_t s) { return launch_gemm_f32_splitk_dual(pa, pb, s, which); };
+        label = "gemm_f32_splitk_dual_kernel";   // (both halves: the unpaired stage carries its reduce under the GEMM's label too)
+      } else {
+        d.run = [pa, pb](hipStream_t s) { return launch_gemm_f32_dual(pa, pb, s); };
+        label = "gemm_f32_dual_kernel";
+      }
+    } else if constexpr (std::is_same_v<R, Conv1Args>) {
+      d.run = [pa, pb = std::get<R>(b.launch)](hipStream_t s) { return launch_conv1_relu_dual(pa, pb, s); };
+      label = "conv1_relu_dual_kernel";
+    } else if constexpr (std::is_same_v<R, DwArgs>) {
+      d.run = [pa, pb = std::get<R>(b.launch)](hipStream_t s) { return launch_dwconv_ln_silu_dual(pa, pb, s); };
+      label = "dwconv_ln_silu_dual_kernel";
+    } else if constexpr (std::is_same_v<R, AttArgs>) {
+      d.run = [pa, pb = std::get<R>(b.launch)](hipStream_t s) { return launch_relpos_attention_dual(pa, pb, s); };
+      label = "relpos_attention_dual_kernel";
+    }
+  }, a.launch);
   // (the algorithmic bytes and FLOPs of a split-K pair stand with its GEMM stage; the partial tiles are not algorithmic traffic)
   d.info = reduce_half ? stage_info(label, 1, 0.0, 0.0, a.info.per_row != 0)
                        : stage_info(label, 1, a.info.alg_bytes + b.info.alg_bytes, a.info.flops + b.info.flops, a.info.per_row != 0);
@@ -737,9 +734,9 @@ static void fuse_independent_pairs(StageBuilder& sb, int first, int mid, int joi
   for (int m = mid; m < join; ++m) {
     assert(!st[m].reads_embed);                       // (moved ahead of embed stages: must not need the embedding)
     int partner = -1;
-    if (st[m].fuse_kind != FuseKind::None)
+    if (st[m].pairable)
       // (the first embed stage pairs only as the subsamplers' conv1: no main-prefix stage is then in front of it either)
-      for (int k = st[m].fuse_kind == FuseKind::Conv1 ? i : std::max(i, first + 1); k < mid; ++k)
+      for (int k = std::holds_alternative<Conv1Args>(st[m].launch) ? i : std::max(i, first + 1); k < mid; ++k)
         if (stages_fusable(st[k], st[m])) { partner = k; break; }
     if (partner < 0) { pending.push_back(st[m]); continue; }
     for (; i < partner; ++i) out.push_back(st[i]);
@@ -747,7 +744,7 @@ static void fuse_independent_pairs(StageBuilder& sb, int first, int mid, int joi
     pending.clear();
     out.push_back(fused_stage(st[partner], st[m]));
     saved += st[partner].info.launches + st[m].info.launches - 1;
-    if (st[m].fuse_kind == FuseKind::SplitK) {
+    if (is_splitk(st[m])) {
       out.push_back(fused_stage(st[partner], st[m], true));
       saved -= 1;
     }
@@ -784,8 +781,8 @@ static void build_subsample(StageBuilder& sb, const std::string& pfx, const SubW
   Conv1Args ca;
   ca.feat = feat; ca.w9c = w.c1w; ca.bias = w.c1b; ca.cmvn_mean = cm; ca.cmvn_istd = ci; ca.B = B; ca.T = T; ca.idim = idim; ca.C = D; ca.out = c1;
   ca.relu = 1; ca.out_bf16 = a16; ca.feat_len = flen; ca.lens_out = lens_out;
-  add_stage(sb, pfx + "conv1", 1, [ca](hipStream_t s) { return launch_conv1_relu(ca, s); },
-            stage_info("conv1_relu_kernel", 1, (double)B * T * idim * 4 + (double)B * T1 * F1 * D * (a16 ? 2 : 4), 18.0 * B * T1 * F1 * D, false));
+  add_launch(sb, pfx + "conv1", ca,
+             stage_info("conv1_relu_kernel", 1, (double)B * T * idim * 4 + (double)B * T1 * F1 * D * (a16 ? 2 : 4), 18.0 * B * T1 * F1 * D, false));
   const size_t conv1_at = sb.bd.stages.size() - 1;
   GemmParams g;
   g.a_bf16 = a16; g.y_bf16 = a16;
@@ -796,13 +793,9 @@ static void build_subsample(StageBuilder& sb, const std::string& pfx, const SubW
   add_gemm(sb, pfx + "conv2", g);
   // The front-end stages may share launches with the other subsampler's (fuse_independent_pairs) where this conv2 is a split-K
   // problem (C >= 512): below that the launches are short, and the stage lists of the small models stay what they were.
-  const bool pairable = switches().front_pair && !a16 && !sb.bd.packed && sb.bd.stages.back().gemm_plan.kernel == GemmKernel::SplitKF32 &&
-                        sb.bd.stages.back().gemm_ws != nullptr;
-  if (pairable) {
-    sb.bd.stages[conv1_at].fuse_kind = FuseKind::Conv1;
-    sb.bd.stages[conv1_at].c1 = ca;
-    sb.bd.stages.back().fuse_kind = FuseKind::SplitK;
-  }
+  auto splitk_with_ws = [&] { return is_splitk(sb.bd.stages.back()) && gemm_of(sb.bd.stages.back()).ws != nullptr; };
+  const bool pairable = switches().front_pair && !a16 && !sb.bd.packed && splitk_with_ws();
+  if (pairable) sb.bd.stages[conv1_at].pairable = sb.bd.stages.back().pairable = true;
   // Linear(C*F2 -> D) on the (f, c)-ordered flatten, with the positional-encoding scale sqrt(D)
   // (rel_positional_encoding_kernel.cu:62-69) folded into the epilogue.
   // packed ragged batch: the subsampler works on the padded (B, T) input; its rows are packed right after it
@@ -813,7 +806,7 @@ static void build_subsample(StageBuilder& sb, const std::string& pfx, const SubW
   l.a_bf16 = a16;
   if (a16) { l.Yb = packed ? pl.xbpad : pl.xb; l.ldyb = D; }
   add_gemm(sb, pfx + "linear", l);
-  if (pairable && sb.bd.stages.back().gemm_ws != nullptr) sb.bd.stages.back().fuse_kind = FuseKind::SplitK;
+  if (pairable && splitk_with_ws()) sb.bd.stages.back().pairable = true;
   if (packed) {
     const float* xpad = pl.xpad; const void* xbpad = pl.xbpad; void* xb = pl.xb; const int32_t* pad_of = pl.pad_of;
     const int S = B * T2;
@@ -888,7 +881,7 @@ static void add_moe_router(StageBuilder& sb, const MoeLayer& m, const MoeRoute& 
       // (what moved to the prefix stage: the embed rows, the embed columns of the weight, their FLOPs; what came: the prefix read)
       st.info.alg_bytes += 4.0 * pl.rprefix_layer - 4.0 * De * (Etot + S);
       st.info.flops -= 2.0 * S * Etot * De;
-      const GemmPlan plan = st.gemm_plan;
+      const GemmPlan plan = gemm_of(st).plan;
       float* prefix = pl.rprefix; const int layer = m.layer;
       st.refresh_prefix = [plan, g, prefix, layer](hipStream_t s) {
         const float* wt[kRouterPrefixMaxLayers] = {};
@@ -1103,12 +1096,8 @@ static void build_block(StageBuilder& sb, const std::string& pfx, const BlockW& 
     } else {
       aa.rows_bf16 = att16; aa.out_bf16 = a16; aa.row0 = row0; aa.chunk = chunk;
     }
-    add_stage(sb, pfx + "att.core", 1, [aa](hipStream_t s) { return launch_relpos_attention(aa, s); },
-              stage_info(label, 1, (double)S * D * row_bytes + (double)Tp * D * 4, 6.0 * Tp * D * S));
-    if (!streaming && !att16) {   // (the fp32 core: a candidate for sharing a launch with the other encoder's, fuse_independent_pairs)
-      sb.bd.stages.back().fuse_kind = FuseKind::Attention;
-      sb.bd.stages.back().att = aa;
-    }
+    // (pairable: the fp32 core is a candidate for sharing a launch with the other encoder's, fuse_independent_pairs)
+    add_launch(sb, pfx + "att.core", aa, stage_info(label, 1, (double)S * D * row_bytes + (double)Tp * D * 4, 6.0 * Tp * D * S), !streaming && !att16);
     GemmParams o;
     o.A = pl.ctx; o.lda = D; o.W = w.out.w; o.bias = w.out.b; o.Y = x; o.ldy = D; o.M = S; o.N = D; o.K = D;
     o.resid = x; o.ldr = D;
@@ -1155,13 +1144,8 @@ static void build_block(StageBuilder& sb, const std::string& pfx, const BlockW& 
       da.pad_of = pad_of; da.row0 = row0; da.row_len = lens; da.causal_left_fill = lfill;
       da.glu_ldz = glu_deferred ? 2 * D : 0; da.glu_sig = glu_sig;
     }
-    add_stage(sb, pfx + "conv.dw_ln_silu", 1, [da](hipStream_t s) { return launch_dwconv_ln_silu(da, s); },
-              stage_info("dwconv_ln_silu_kernel", 1, (double)S * D * row_bytes + (double)K * D * 4 + cache_bytes,
-                         2.0 * K * D * S));
-    if (!streaming) {
-      sb.bd.stages.back().fuse_kind = FuseKind::Dwconv;
-      sb.bd.stages.back().dw = da;
-    }
+    add_launch(sb, pfx + "conv.dw_ln_silu", da,
+               stage_info("dwconv_ln_silu_kernel", 1, (double)S * D * row_bytes + (double)K * D * 4 + cache_bytes, 2.0 * K * D * S), !streaming);
     GemmParams h;
     h.A = pl.dw; h.lda = D; h.W = w.pw2.w; h.bias = w.pw2.b; h.Y = x; h.ldy = D; h.M = S; h.N = D; h.K = D;
     h.row_len = live_len; h.rows_per_batch = live_rpb; h.mask_out = 1; h.resid = x; h.ldr = D;
@@ -1421,7 +1405,7 @@ static int build_binding(m3_engine* e, const BindKey& k, m3_engine::Bound& bd) {
         pf = std::shared_ptr<float>(dev, [](float* q) { (void)hipFree(q); });
         pp.Y = dev;
         pp.w_bf16 = c.weight_dtype != M3_F32;
-        if (int rc = launch_gemm(plan_gemm(pp, 0), pp, nullptr, nullptr)) return rc;
+        if (int rc = launch_gemm(gemm_launch(pp, nullptr, 0), nullptr)) return rc;
         M3_CHECK_HIP(hipStreamSynchronize(nullptr));
         // (nothing below can fail: from here on the engine may change)
         for (auto it = e->pfold_by_tp.begin(); it != e->pfold_by_tp.end();)      // tables no binding holds any more
@@ -1475,7 +1459,7 @@ static int build_binding(m3_engine* e, const BindKey& k, m3_engine::Bound& bd) {
     const double Etot = g.N;
     add_stage(sb, "router_e_prefix", 1, [plan, g, wt, prefix, L](hipStream_t s) { return launch_router_embed_prefix(plan, g, wt.data(), 0, L, prefix, s); },
               stage_info("router_embed_prefix_kernel", 1, 4.0 * De * (L * Etot + S) + 4.0 * L * pl.rprefix_layer, 2.0 * S * Etot * De * L));
-    bd.stages.back().reads_embed = true;
+    bd.stages.back().reads_embed = bd.stages.back().router_prefix = true;
   }
   // ---- main MoE encoder (conformer_fmoe_localComm_catEmbed_domain_acc_hier.py:198-234) ----
   const int main_start = (int)bd.stages.size();     // ... and the main encoder here
@@ -1529,7 +1513,7 @@ static int build_binding(m3_engine* e, const BindKey& k, m3_engine::Bound& bd) {
               stage_info("advance_counter_kernel", 1, 8.0, 0.0, false));
   }
   for (int i = 0; i < (int)bd.stages.size(); ++i)
-    if (bd.stages[i].name == "router_e_prefix") bd.prefix_stage = i;
+    if (bd.stages[i].router_prefix) bd.prefix_stage = i;   // (its index after fuse_independent_pairs has reordered the list)
   bd.buffers["x"] = Buf{pl.x, (size_t)S * D * 4};
   bd.buffers["dw"] = Buf{pl.dw, (size_t)S * D * 4};   // the main encoder's depthwise conv + LayerNorm + SiLU output (last block run)
   if (!bd.xn_skipped) bd.buffers["xn"] = Buf{pl.xn, (size_t)S * D * 4};
@@ -1645,13 +1629,20 @@ int m3_engine_num_kernels(const m3_engine* engine) { return engine ? engine->cur
 // without the prefix stage in front of it IN THIS CALL first recomputes its own layer's slice, on the same stream: the stage
 // then computes what the whole-K GEMM would, whatever happened between the calls.  `whole`: the ranges are the pieces of one
 // forward (forked capture), the prefix stage has run in an earlier piece.
+static int run_stage(const Stage& st, hipStream_t stream) {
+  if (auto* g = std::get_if<GemmLaunch>(&st.launch)) return launch_gemm(*g, stream);
+  if (auto* c = std::get_if<Conv1Args>(&st.launch)) return launch_conv1_relu(*c, stream);
+  if (auto* d = std::get_if<DwArgs>(&st.launch)) return launch_dwconv_ln_silu(*d, stream);
+  if (auto* t = std::get_if<AttArgs>(&st.launch)) return launch_relpos_attention(*t, stream);
+  return st.run(stream);
+}
 static int run_stage_range(m3_engine* engine, int first_stage, int last_stage, hipStream_t stream, bool whole) {
   const int ps = engine->cur.prefix_stage;
   for (int i = first_stage; i < last_stage; ++i) {
     const Stage& st = engine->cur.stages[i];
     if (st.refresh_prefix && !whole && !(ps >= first_stage && ps < i))
       if (int rc = st.refresh_prefix(stream)) return rc;
-    if (int rc = st.run(stream)) return rc;
+    if (int rc = run_stage(st, stream)) return rc;
   }
   return 0;
 }

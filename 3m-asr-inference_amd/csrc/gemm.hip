@@ -532,11 +532,12 @@ __global__ __launch_bounds__(64 * NW) void gemm_f32_dual_kernel(const GemmParams
   }
 }
 
-// two independent problems of one instantiation in ONE launch (gemm_dual_fusable holds for the two plans)
-int launch_gemm_f32_dual(const GemmPlan& pa, const GemmParams& a_in, const GemmPlan& pb, const GemmParams& b_in, hipStream_t stream) {
-  M3_REQUIRE(gemm_dual_fusable(pa, pb), "gemm dual: the two problems do not share an instantiation");
-  GemmParams q[2] = {a_in, b_in};
-  const GemmPlan* const plans[2] = {&pa, &pb};
+// two independent problems of one instantiation in ONE launch (gemm_dual_fusable holds for the two records)
+int launch_gemm_f32_dual(const GemmLaunch& a, const GemmLaunch& b, hipStream_t stream) {
+  M3_REQUIRE(gemm_dual_fusable(a, b), "gemm dual: the two problems do not share an instantiation");
+  GemmParams q[2] = {a.p, b.p};
+  const GemmPlan& pa = a.plan;
+  const GemmPlan* const plans[2] = {&a.plan, &b.plan};
   for (int i = 0; i < 2; ++i) {
     q[i].n_tiles = plans[i]->n_tiles; q[i].m_tiles = plans[i]->m_tiles; q[i].xcd_swizzle = plans[i]->xcd_swizzle;
   }

@@ -229,19 +229,20 @@ int launch_gemm_f32_splitk(const GemmPlan& plan, const GemmParams& pin, float* w
 // two independent split-K problems (both implicit convs or both plain) in ONE GEMM launch and ONE reduce launch: each keeps its
 // split count, its partial tiles and its reduce order, so each result is what launch_gemm_f32_splitk gives, bit for bit.
 // `which`: 1 = the GEMM launch, 2 = the reduce launch, 3 = both (the engine lists them as two stages)
-bool gemm_splitk_dual_fusable(const GemmPlan& a, const GemmPlan& b) {
-  return a.launches == 2 && b.launches == 2 && a.kernel == GemmKernel::SplitKF32 && b.kernel == GemmKernel::SplitKF32 && a.conv == b.conv;
+bool gemm_splitk_dual_fusable(const GemmLaunch& ga, const GemmLaunch& gb) {
+  const GemmPlan &a = ga.plan, &b = gb.plan;
+  return a.launches == 2 && b.launches == 2 && a.kernel == GemmKernel::SplitKF32 && b.kernel == GemmKernel::SplitKF32 && a.conv == b.conv &&
+         ga.ws != nullptr && gb.ws != nullptr && ga.ws != gb.ws;
 }
-int launch_gemm_f32_splitk_dual(const GemmPlan& pa, const GemmParams& a_in, float* ws_a, const GemmPlan& pb, const GemmParams& b_in,
-                                float* ws_b, hipStream_t stream, int which) {
-  M3_REQUIRE(gemm_splitk_dual_fusable(pa, pb), "gemm split-K dual: the two problems do not share an instantiation");
-  M3_REQUIRE(ws_a != nullptr && ws_b != nullptr && ws_a != ws_b, "gemm split-K dual: each problem needs its own workspace");
+int launch_gemm_f32_splitk_dual(const GemmLaunch& a, const GemmLaunch& b, hipStream_t stream, int which) {
+  M3_REQUIRE(a.ws != nullptr && b.ws != nullptr && a.ws != b.ws, "gemm split-K dual: each problem needs its own workspace");
+  M3_REQUIRE(gemm_splitk_dual_fusable(a, b), "gemm split-K dual: the two problems do not share an instantiation");
   if (int rc = init_gemm_f32_splitk_kernels()) return rc;
-  GemmParams q[2] = {a_in, b_in};
-  const GemmPlan* const plans[2] = {&pa, &pb};
+  GemmParams q[2] = {a.p, b.p};
+  const GemmPlan* const plans[2] = {&a.plan, &b.plan};
   int per[2], live[2];
   SplitkReduceArgs r[2];
-  float* const ws[2] = {ws_a, ws_b};
+  float* const ws[2] = {a.ws, b.ws};
   for (int i = 0; i < 2; ++i) {
     q[i].m_tiles = plans[i]->m_tiles; q[i].n_tiles = plans[i]->n_tiles;
     per[i] = cdiv(q[i].K / SBK, plans[i]->splits);
@@ -251,7 +252,7 @@ int launch_gemm_f32_splitk_dual(const GemmPlan& pa, const GemmParams& a_in, floa
   }
   const int n0 = (int)align_up((size_t)live[0], 8);
   const dim3 grid(n0 + live[1]);
-  if ((which & 1) && pa.conv)
+  if ((which & 1) && a.plan.conv)
     hipLaunchKernelGGL((gemm_f32_splitk_dual_kernel<true>), grid, dim3(256), kSplitLdsBytes, stream, q[0], ws[0], per[0], live[0], q[1], ws[1], per[1], n0);
   else if (which & 1)
     hipLaunchKernelGGL((gemm_f32_splitk_dual_kernel<false>), grid, dim3(256), kSplitLdsBytes, stream, q[0], ws[0], per[0], live[0], q[1], ws[1], per[1], n0);

@@ -1,5 +1,5 @@
 // The dense GEMM's form, decided once (host only): plan_gemm checks the operands and picks the kernel, its instantiation, its
-// grid and its workspace; launch_gemm runs the plan.  kernels.h has the table of form against condition.
+// grid and its workspace; launch_gemm runs the record of the two (GemmLaunch).  kernels.h has the table of form against condition.
 #include <stdlib.h>
 
 #include "common.h"
@@ -195,11 +195,14 @@ GemmPlan plan_gemm(const GemmParams& p, size_t workspace_bytes_available) {
   return plan;
 }
 
-bool gemm_dual_fusable(const GemmPlan& a, const GemmPlan& b) {
+GemmLaunch gemm_launch(const GemmParams& p, float* ws, size_t ws_bytes) { return GemmLaunch{p, plan_gemm(p, ws != nullptr ? ws_bytes : 0), ws}; }
+bool gemm_dual_fusable(const GemmLaunch& ga, const GemmLaunch& gb) {
+  const GemmPlan &a = ga.plan, &b = gb.plan;
   return a.launches == 1 && b.launches == 1 && a.dual_ok && b.dual_ok && a.nw == b.nw && a.ln == b.ln && a.glu == b.glu;
 }
 
-int launch_gemm(const GemmPlan& plan, const GemmParams& p, float* ws, hipStream_t stream) {
+int launch_gemm(const GemmLaunch& g, hipStream_t stream) {
+  const GemmPlan& plan = g.plan; const GemmParams& p = g.p; float* const ws = g.ws;
   M3_REQUIRE(plan.launches > 0, "%s", plan.reason);
   switch (plan.kernel) {
     case GemmKernel::SkinnyF32: return launch_gemm_f32_skinny(plan, p, stream);

@@ -63,8 +63,9 @@ struct GemmParams {
 };
 // ---- the dense GEMM family (gemm_plan.hip) ----
 // The family has six kernels.  plan_gemm is the ONE place that checks a problem's operands and says which kernel runs it, in
-// which instantiation, over which grid and with how much workspace; launch_gemm runs a plan, and the engine's stage list, its
-// workspace sizing and the observability entries (m3_linear_kernel, m3_engine_stage_info) read the same plan.  First match wins:
+// which instantiation, over which grid and with how much workspace.  One launch is one record, GemmLaunch: the problem, its plan and
+// the workspace the plan was made against (gemm_launch).  launch_gemm runs a record, the pair launchers and *_dual_fusable read two; the
+// engine's stage list, its workspace sizing and the observability entries (m3_linear_kernel, m3_engine_stage_info) read the same plan.  First match wins:
 //   SplitKF32   fp32 W, K >= 4096, K % 64 == 0, N, lda, ldy % 4 == 0, at most 160 tiles of 64 x 64, plain epilogue (bias /
 //               ReLU / SiLU / scale), >= 2 K ranges of >= 4 k-steps, and the caller's workspace holds them      2 launches
 //   DmaBf16     bf16 W and bf16 A, M >= 4096 (M3_DMA_MIN_ROWS), plain A, K % 64 == 0, lda % 8 == 0, operands < 4 GB,
@@ -91,9 +92,11 @@ struct GemmPlan {
   char reason[192];
 };
 GemmPlan plan_gemm(const GemmParams& p, size_t workspace_bytes_available);
-int launch_gemm(const GemmPlan& plan, const GemmParams& p, float* ws, hipStream_t stream);
-bool gemm_dual_fusable(const GemmPlan& a, const GemmPlan& b);   // two independent skinny fp32 GEMMs of one instantiation
-int launch_gemm_f32_dual(const GemmPlan& pa, const GemmParams& a, const GemmPlan& pb, const GemmParams& b, hipStream_t stream);   // ... in ONE launch
+struct GemmLaunch { GemmParams p; GemmPlan plan; float* ws = nullptr; };
+GemmLaunch gemm_launch(const GemmParams& p, float* ws, size_t ws_bytes);   // p planned against ws (a null ws: against 0 bytes)
+int launch_gemm(const GemmLaunch& g, hipStream_t stream);
+bool gemm_dual_fusable(const GemmLaunch& a, const GemmLaunch& b);   // two independent skinny fp32 GEMMs of one instantiation
+int launch_gemm_f32_dual(const GemmLaunch& a, const GemmLaunch& b, hipStream_t stream);   // ... in ONE launch
 // The A (embed) half of up to kRouterPrefixMaxLayers concat GEMMs that share A, M, N, K, K1 and differ in W: the accumulator
 // pairs GemmParams::acc_init takes, layer l's at prefix + l * router_prefix_floats(plan).  `plan`: the consumers' plan (a form
 // that takes acc_init); layers [layer0, layer0 + n_layers) of w[] are computed, one launch.
@@ -119,9 +122,8 @@ int launch_gemm_bf16_dma(const GemmPlan& plan, const GemmParams& p, hipStream_t 
 // deep-K, few-tile fp32 problems (conv2 / subsampling Linear at short inputs): split-K tiled kernel + reduce
 int launch_gemm_f32_splitk(const GemmPlan& plan, const GemmParams& p, float* ws, hipStream_t stream);   // gemm_f32_splitk.hip
 // two independent split-K problems (both implicit convs or both plain), each with its own workspace, in one GEMM + one reduce launch
-bool gemm_splitk_dual_fusable(const GemmPlan& a, const GemmPlan& b);
-int launch_gemm_f32_splitk_dual(const GemmPlan& pa, const GemmParams& a, float* ws_a, const GemmPlan& pb, const GemmParams& b, float* ws_b,
-                                hipStream_t stream, int which = 3);   // which: 1 the GEMM launch, 2 the reduce launch, 3 both
+bool gemm_splitk_dual_fusable(const GemmLaunch& a, const GemmLaunch& b);
+int launch_gemm_f32_splitk_dual(const GemmLaunch& a, const GemmLaunch& b, hipStream_t stream, int which = 3);   // which: 1 the GEMM launch, 2 the reduce launch, 3 both
 // once, outside graph capture (dynamic-LDS opt-in of the tiled kernels)
 int init_gemm_f32_splitk_kernels();
 int init_gemm_bf16_tiled_kernels();

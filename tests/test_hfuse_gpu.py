@@ -53,7 +53,8 @@ def _child(out_path):
         feat = torch.randn(B, T, cfg.input_dim, generator=g).cuda()
         flen = torch.tensor([lengths], dtype=torch.int32).cuda()
         logits = eng.bind(feat, flen)
-        meta[key] = dict(stages=[[s["name"], s["kernel"], s["launches"]] for s in eng.stage_info()], num_kernels=eng.num_kernels())
+        meta[key] = dict(stages=[[s["name"], s["kernel"], s["launches"], s["alg_bytes"], s["flops"]] for s in eng.stage_info()],
+                         num_kernels=eng.num_kernels())
         eng.forward(use_graph=False)
         torch.cuda.synchronize()
         arrays[key + ".logits"] = logits.cpu().numpy().copy()
@@ -106,10 +107,12 @@ def test_hfuse_stage_lists(runs, model, inp):
     for kernel in DUAL_KERNELS:
         assert any(s[1] == kernel for s in fused), "%s: no a+b stage runs %s" % (key, kernel)
     # both halves of every pair are stages of the unfused list, the embed encoder's first
-    names_off = {s[0] for s in off["stages"]}
+    by_name_off = {s[0]: s for s in off["stages"]}
     for s in fused:
         a, b = s[0].split("+")
-        assert a.startswith("embed.") and not b.startswith("embed.") and {a, b} <= names_off, s[0]
+        assert a.startswith("embed.") and not b.startswith("embed.") and {a, b} <= set(by_name_off), s[0]
+        # ... and a pair's algorithmic bytes and FLOPs are its halves' (exact: the same doubles summed in the same order)
+        assert s[3] == by_name_off[a][3] + by_name_off[b][3] and s[4] == by_name_off[a][4] + by_name_off[b][4], s[0]
     assert off["num_kernels"] - on["num_kernels"] == len(fused)
     assert sum(s[2] for s in off["stages"]) - sum(s[2] for s in on["stages"]) == len(fused)
 
