@@ -45,7 +45,7 @@ int moe_expert_ffn_dt(const float* x, const int32_t* gate_idx, const float* w1, 
                       const float* b2, int S, int E, int D, int F, const float* gate_value, const float* resid,
                       float alpha, const float* ln_gamma, const float* ln_beta, float ln_eps, float* y, void* ws,
                       size_t ws_bytes, hipStream_t stream, ExpertWeights weights, const float* s1 = nullptr, const float* s2 = nullptr, float h_scale = 0.f, const void* xq = nullptr,
-                      const float* xq_scale = nullptr) {
+                      const float* xq_scale = nullptr, int ldx = 0) {
   M3_REQUIRE(S >= 0 && E > 0 && D > 0 && F > 0, "fmoe_expert: bad sizes S=%d E=%d D=%d F=%d", S, E, D, F);
   if (S == 0) return 0;
   MoeWorkspace w = carve_moe_workspace(ws, S, E, D, F);
@@ -55,7 +55,7 @@ int moe_expert_ffn_dt(const float* x, const int32_t* gate_idx, const float* w1, 
   if (rc) return rc;
   const ExpertFfnPlan plan = plan_expert_ffn(weights, S, E, D, F);
   ExpertFfnArgs a{};
-  a.x = x; a.ldx = D; a.pos = w.pos; a.acc_hist = w.acc; a.w1 = w1; a.w2 = w2; a.s1 = s1; a.s2 = s2; a.b1 = b1;
+  a.x = x; a.ldx = ldx > 0 ? ldx : D; a.pos = w.pos; a.acc_hist = w.acc; a.w1 = w1; a.w2 = w2; a.s1 = s1; a.s2 = s2; a.b1 = b1;
   a.h_scale = h_scale; a.slab = w.slab; a.xq = xq; a.xq_scale = xq_scale;
   rc = launch_expert_ffn(plan, S, E, D, F, a, stream);
   if (rc) return rc;
@@ -123,6 +123,30 @@ int m3_moe_expert_ffn_fp8(const float* x, const int32_t* gate_idx, const void* w
                            gate_value, resid, alpha, ln_gamma, ln_beta, ln_eps, y, workspace, workspace_bytes,
                            (hipStream_t)stream, ExpertWeights::FP8, w1_scale, w2_scale);
 }
+int m3_moe_expert_ffn_mxfp4_ldx(const float* x, int ldx, const int32_t* gate_idx, const void* w1, const void* w1_scale, const float* b1,
+                                const void* w2, const void* w2_scale, const float* b2, int S, int num_expert, int idim,
+                                int hidden_units, const float* gate_value, const float* resid, float alpha,
+                                const float* ln_gamma, const float* ln_beta, float ln_eps, float* y, void* workspace,
+                                size_t workspace_bytes, m3_stream stream) {
+  M3_REQUIRE(x && gate_idx && w1 && w2 && b1 && y, "fmoe_expert mxfp4: null pointer");
+  M3_REQUIRE(w1_scale && w2_scale, "fmoe_expert mxfp4: null scale");
+  M3_REQUIRE(idim > 0 && idim % 128 == 0 && hidden_units > 0 && hidden_units % 64 == 0,
+             "fmoe_expert mxfp4: idim=%d must be a multiple of 128 and hidden_units=%d of 64", idim, hidden_units);
+  M3_REQUIRE(ldx >= idim && (ldx & 3) == 0, "fmoe_expert mxfp4: ldx=%d must be a multiple of 4 and at least idim=%d", ldx, idim);
+  M3_REQUIRE(aligned16(x) && aligned16(w1) && aligned16(w2), "fmoe_expert mxfp4: x / w1 / w2 must be 16-byte aligned");
+  return moe_expert_ffn_dt(x, gate_idx, (const float*)w1, b1, (const float*)w2, b2, S, num_expert, idim, hidden_units,
+                           gate_value, resid, alpha, ln_gamma, ln_beta, ln_eps, y, workspace, workspace_bytes,
+                           (hipStream_t)stream, ExpertWeights::MXFP4, (const float*)w1_scale, (const float*)w2_scale, 0.f, nullptr,
+                           nullptr, ldx);
+}
+int m3_moe_expert_ffn_mxfp4(const float* x, const int32_t* gate_idx, const void* w1, const void* w1_scale, const float* b1,
+                            const void* w2, const void* w2_scale, const float* b2, int S, int num_expert, int idim,
+                            int hidden_units, const float* gate_value, const float* resid, float alpha,
+                            const float* ln_gamma, const float* ln_beta, float ln_eps, float* y, void* workspace,
+                            size_t workspace_bytes, m3_stream stream) {
+  return m3_moe_expert_ffn_mxfp4_ldx(x, idim, gate_idx, w1, w1_scale, b1, w2, w2_scale, b2, S, num_expert, idim, hidden_units,
+                                     gate_value, resid, alpha, ln_gamma, ln_beta, ln_eps, y, workspace, workspace_bytes, stream);
+}
 int m3_moe_expert_ffn_fp8a8(const float* x, const int32_t* gate_idx, const void* w1, const float* w1_scale, const float* b1,
                             const void* w2, const float* w2_scale, const float* b2, float h_scale, int S, int num_expert, int idim,
                             int hidden_units, const float* gate_value, const float* resid, float alpha,
@@ -162,6 +186,7 @@ const char* m3_moe_expert_ffn_kernel(int weight_dtype, int fp8_activations, int 
   if (weight_dtype == M3_F32 && !fp8_activations) w = ExpertWeights::F32;
   else if (weight_dtype == M3_BF16 && !fp8_activations) w = ExpertWeights::BF16;
   else if (weight_dtype == M3_FP8) w = fp8_activations ? ExpertWeights::FP8A8 : ExpertWeights::FP8;
+  else if (weight_dtype == M3_MXFP4 && !fp8_activations) w = ExpertWeights::MXFP4;
   else return nullptr;
   const ExpertFfnPlan plan = plan_expert_ffn(w, S, num_expert, idim, hidden_units);
   if (plan.launches == 0) return nullptr;

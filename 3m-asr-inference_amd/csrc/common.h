@@ -185,4 +185,26 @@ __device__ __forceinline__ bf16x8 fp8x8_to_bf16(unsigned int lo, unsigned int hi
   return r;
 }
 
+// ---- OCP MXFP4 weights (e2m1 code pairs + one e8m0 scale per 32 k, m3asr/plan.py quantize_mxfp4): decoded to bf16, exactly ----
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ u32x2 ldg8b_w(const void* p) {      // once-read weights, see ldg4_w
+#if M3_NT_WEIGHTS
+  return __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p));
+#else
+  return *reinterpret_cast<const u32x2*>(p);
+#endif
+}
+// e8m0 code -> the power of two as a float (codes 1..254; the quantiser stores 63..191), the conversion's scale operand
+__device__ __forceinline__ float e8m0_to_f32(unsigned int code) { return __uint_as_float(code << 23); }
+// 8 consecutive e2m1 codes (one dword, element 2 i in the low nibble of byte i) times scale -> bf16x8, element order preserved
+__device__ __forceinline__ bf16x8 mxfp4x8_to_bf16(unsigned int w, float scale) {
+  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0), b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1);
+  const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2), d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3);
+  bf16x8 r;
+  r[0] = a[0]; r[1] = a[1]; r[2] = b[0]; r[3] = b[1];
+  r[4] = c[0]; r[5] = c[1]; r[6] = d[0]; r[7] = d[1];
+  return r;
+}
+
 }  // namespace m3

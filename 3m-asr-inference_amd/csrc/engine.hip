@@ -49,7 +49,7 @@ struct BlockW {
   Lin router;                       // w: [E_total][D + De]  (unfused route path)
   Lin router_x;                     // w: [E][D] x-half with norm_ff folded (+ wsum, bias)  (fused route path)
   const float *ew1 = nullptr, *eb1 = nullptr, *ew2 = nullptr, *eb2 = nullptr;
-  const float *es1 = nullptr, *es2 = nullptr;   // fp8 experts: per-row scales [E][F], [E][D]
+  const float *es1 = nullptr, *es2 = nullptr;   // fp8 experts: per-row scales [E][F], [E][D]; mxfp4 experts: the e8m0 scale BYTES [E][F][D/32], [E][F/64][D][2]
   float h_scale = 0.f;                          // fp8 arithmetic: static scale of the hidden activations (0 = weight-only)
 };
 
@@ -242,7 +242,7 @@ bool lookup(const m3_engine* e, const std::string& name, int64_t numel, const fl
 
 #define GET(dst, name, numel) \
   do { if (!lookup(e, (name), (numel), &(dst))) return false; } while (0)
-// dense GEMM weights: fp32, or bf16 in both 16-bit and fp8 modes; expert weights follow weight_dtype itself
+// dense GEMM weights: fp32, or bf16 in the 16-bit, fp8 and mxfp4 modes; expert weights follow weight_dtype itself
 #define GETW(dst, name, numel) \
   do { if (!lookup(e, (name), (numel), &(dst), e->cfg.weight_dtype == M3_F32 ? M3_F32 : M3_BF16)) return false; } while (0)
 #define GETE(dst, name, numel) \
@@ -301,7 +301,13 @@ bool load_block(const m3_engine* e, const std::string& p, int D, int F, int K, b
     if (c.router_with_bias) GET(b->router.b, p + "feed_forward.router_bias", Etot);
     if (c.fuse_route && !load_lin_ln(e, p + "feed_forward.router_x.", Etot, D, false, &b->router_x, true)) return false;
     const int64_t E = c.num_experts;
-    GETE(b->ew1, p + "feed_forward.experts.w_1.weight", E * F * D);
+    // (mxfp4: two codes per byte, one scale byte per 32 k -- the tensors are bytes)
+    const int64_t ew_numel = c.weight_dtype == M3_MXFP4 ? E * F * D / 2 : E * F * D;
+    GETE(b->ew1, p + "feed_forward.experts.w_1.weight", ew_numel);
+    if (c.weight_dtype == M3_MXFP4) {
+      GETE(b->es1, p + "feed_forward.experts.w_1.scale", E * F * D / 32);
+      GETE(b->es2, p + "feed_forward.experts.w_2.scale", E * F * D / 32);
+    }
     if (c.weight_dtype == M3_FP8) {
       GET(b->es1, p + "feed_forward.experts.w_1.scale", E * F);
       GET(b->es2, p + "feed_forward.experts.w_2.scale", E * D);
@@ -315,7 +321,7 @@ bool load_block(const m3_engine* e, const std::string& p, int D, int F, int K, b
       }
     }
     GET(b->eb1, p + "feed_forward.experts.w_1.bias", E * F);
-    GETE(b->ew2, p + "feed_forward.experts.w_2.weight_sliced", E * D * F);
+    GETE(b->ew2, p + "feed_forward.experts.w_2.weight_sliced", ew_numel);
     GET(b->eb2, p + "feed_forward.experts.w_2.bias", E * D);
   }
   return true;
@@ -563,6 +569,7 @@ struct MoeRoute {
 static ExpertWeights expert_weights(const m3_engine_config& c, const BlockW& w) {
   if (c.weight_dtype == M3_F32) return ExpertWeights::F32;
   if (c.weight_dtype == M3_BF16) return ExpertWeights::BF16;
+  if (c.weight_dtype == M3_MXFP4) return ExpertWeights::MXFP4;
   return w.h_scale > 0.f ? ExpertWeights::FP8A8 : ExpertWeights::FP8;
 }
 
@@ -1233,8 +1240,12 @@ m3_engine* m3_engine_create(const m3_engine_config* config, const m3_weight_entr
   if (c.attention_dim % 16 || c.embed_dim % 16 || c.hidden_units % 64 || c.embed_linear_units % 16)
     return fail("engine_create: dims must be multiples of 16 (hidden_units of 64)");
   if (c.embed_dim != c.attention_dim) return fail("engine_create: embed_dim != attention_dim is not supported");
-  if (c.weight_dtype != M3_F32 && c.weight_dtype != M3_BF16 && c.weight_dtype != M3_FP8)
-    return fail("engine_create: weight_dtype must be f32, bf16 or fp8");
+  if (c.weight_dtype != M3_F32 && c.weight_dtype != M3_BF16 && c.weight_dtype != M3_FP8 && c.weight_dtype != M3_MXFP4)
+    return fail("engine_create: weight_dtype must be f32, bf16, fp8 or mxfp4");
+  if (c.weight_dtype == M3_MXFP4 && (c.attention_dim % 128 || c.hidden_units % 64))
+    return fail("engine_create: mxfp4 experts need an attention_dim that is a multiple of 128 and hidden_units that are a multiple of 64");
+  if (c.weight_dtype == M3_MXFP4 && (c.ep_world_size > 1 || c.ep_stages > 0))
+    return fail("engine_create: expert parallelism (ep_world_size > 1, ep_stages) is not supported with mxfp4 expert weights");
   if (c.weight_dtype == M3_FP8 && (c.attention_dim % 64 || c.hidden_units % 64))
     return fail("engine_create: fp8 experts need attention_dim and hidden_units that are multiples of 64");
   if (c.fp8_activations && c.weight_dtype != M3_FP8) return fail("engine_create: fp8_activations needs weight_dtype fp8");
@@ -1317,7 +1328,7 @@ static int init_engine_kernels() {
   int (*const inits[])() = {init_expert_ffn_kernels, init_expert_ffn_bf16_kernels, init_expert_ffn_w8_kernels, init_gemm_bf16_tiled_kernels,
                             init_expert_ffn_f32_tiled_kernels, init_expert_ffn_fused_fp8_kernels, init_gemm_f32_tiled_kernels,
                             init_gemm_bf16_dma_kernels, init_expert_gemm_g256_kernels, init_moe_router_kernels,
-                            init_relpos_attention_bf16_kernels, init_gemm_f32_splitk_kernels};
+                            init_relpos_attention_bf16_kernels, init_gemm_f32_splitk_kernels, init_expert_ffn_w4_kernels};
   for (auto init : inits)
     if (int rc = init()) return rc;
   return 0;

@@ -39,11 +39,15 @@ constexpr int tiled_lds_bytes(int BM, int BN, int BK) {
 //   2: A = H (bf16, no conversion while staging), W2 in the plan's slice-major layout or [D][F], fp32 rows out.
 // W8 (grouped forms only): W holds fp8 e4m3 with a per-output-row scale (p.w_scale); the staging threads dequantise it to
 // bf16 on the way into LDS (exact) and the scale is applied to the accumulator in the epilogue.
+// W4 (grouped forms only): W holds OCP MXFP4 (two e2m1 codes per byte, one e8m0 scale byte per 32 k in p.w_scale; plan.py
+// quantize_mxfp4).  A staging thread's 16-byte chunk is 32 k = one block: it fetches the block's scale byte with the chunk and
+// decodes to bf16 on the way into LDS (exact); the block scale is applied at decode, nothing scales the accumulator.
 // A16: the A operand is already bf16 in memory (activation copies written by the producing kernels in the 16-bit modes:
 // half the A traffic, which is what bounds these GEMMs); LayerNorm statistics are then taken from the bf16 values, i.e.
 // from exactly the numbers the MFMA multiplies.  GRP = 2 implies A16.
-template <int TBM, int TBN, int TBK, bool GLU, bool CONV, bool LN, int GRP, bool W8 = false, bool A16IN = false>
+template <int TBM, int TBN, int TBK, bool GLU, bool CONV, bool LN, int GRP, bool W8 = false, bool A16IN = false, bool W4 = false>
 __global__ __launch_bounds__(256, 2) void gemm_bf16w_tiled_kernel(const GemmParams p) {
+  static_assert(!W4 || (GRP != 0 && !W8 && TBK % 32 == 0), "MXFP4 weights: grouped expert GEMMs only, whole blocks per k-step");
   static_assert(GRP == 0 || (!GLU && !CONV && !LN), "grouped form is a plain GEMM");
   static_assert(!W8 || GRP != 0, "fp8 weights: grouped expert GEMMs only");
   constexpr int T_LD = TBK + 8;                     // bf16 elements per LDS row (144 / 272 B: conflict-free 16-B reads)
@@ -56,7 +60,11 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16w_tiled_kernel(const GemmPara
   constexpr bool EARLY_EPI = TBM <= 64 && GRP == 0; // epilogue operands requested before the k loop (see below)
 #endif
   constexpr int CA = A16 ? TBK / 8 : TBK / 4, RA = 256 / CA, JA = TBM / RA;   // A staging: chunks per row, rows per pass, passes
-  constexpr int WCE = W8 ? 16 : 8, WSZ = W8 ? 1 : 2;          // W elements per 16-B chunk, bytes per element
+  constexpr int WCE = W4 ? 32 : W8 ? 16 : 8;                  // W elements per 16-B chunk
+  constexpr int WSZ = W8 ? 1 : 2;                             // bytes per element (W4: half a byte, see wbytes)
+  auto wbytes = [](size_t elems) -> size_t {                  // byte offset of element `elems` (W4: always an even count)
+    if constexpr (W4) return elems >> 1; else return elems * WSZ;
+  };
   constexpr int CB = TBK / WCE, RB = 256 / CB, JB = TBN / RB;  // W staging: 16-B chunks per row, rows per pass, passes
   extern __shared__ __attribute__((aligned(16))) unsigned char tiled_lds[];
   bf16_t* As = reinterpret_cast<bf16_t*>(tiled_lds);                // [2][TBM][T_LD]
@@ -157,7 +165,9 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16w_tiled_kernel(const GemmPara
   }
   // W: thread t brings 16-B chunk (t % CB) of tile rows (t / CB) + RB j
   const int bc = tid % CB, br0 = tid / CB;
-  const unsigned char* W = reinterpret_cast<const unsigned char*>(p.W) + (GRP ? (size_t)expert * p.N * p.K * WSZ : 0);
+  const unsigned char* W = reinterpret_cast<const unsigned char*>(p.W) + (GRP ? wbytes((size_t)expert * p.N * p.K) : 0);
+  const unsigned char* wsb = nullptr;                // W4: this expert's scale bytes
+  if constexpr (W4) wsb = reinterpret_cast<const unsigned char*>(p.w_scale) + (size_t)expert * p.N * (p.K >> 5);
   const unsigned char* bptr[JB];
   int brow_n[JB];
 #pragma unroll
@@ -165,15 +175,21 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16w_tiled_kernel(const GemmPara
     const int tr = br0 + RB * j;
     const int n = GLU ? (tr / (TBN / 2)) * Nout + min(n0 + (tr % (TBN / 2)), Nout - 1) : min(n0 + tr, p.N - 1);
     brow_n[j] = n;
-    bptr[j] = W + ((size_t)n * p.K + WCE * bc) * WSZ;
+    bptr[j] = W + wbytes((size_t)n * p.K + WCE * bc);
   }
   // slice-major W (plan's expert w_2: [K/64][N][64]): element k of row n sits at ((k>>6)*N + n)*64 + (k&63)
   auto w_ptr = [&](int j, int s) -> const unsigned char* {
     if (GRP == 2 && p.w_sliced) {
       const int k0 = (s * CB + bc) * WCE;
-      return W + (((size_t)(k0 >> 6) * p.N + brow_n[j]) * 64 + (k0 & 63)) * WSZ;
+      return W + wbytes(((size_t)(k0 >> 6) * p.N + brow_n[j]) * 64 + (k0 & 63));
     }
-    return bptr[j] + (size_t)s * TBK * WSZ;
+    return bptr[j] + wbytes((size_t)s * TBK);
+  };
+  // W4: the scale byte of the chunk w_ptr(j, s) names (block k0 / 32 of row n; slice-major: [K/64][N][2])
+  auto ws_ptr = [&](int j, int s) -> const unsigned char* {
+    const int k0 = (s * CB + bc) * WCE;
+    if (GRP == 2 && p.w_sliced) return wsb + ((size_t)(k0 >> 6) * p.N + brow_n[j]) * 2 + ((k0 & 63) >> 5);
+    return wsb + (size_t)brow_n[j] * (p.K >> 5) + (k0 >> 5);
   };
   auto a_offset = [&](int k) -> int {
     if (CONV) {
@@ -241,13 +257,18 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16w_tiled_kernel(const GemmPara
 
   const int nsteps = p.K / TBK;
   f32x4 areg[JA];                                   // A16: the 16 bytes are 8 bf16, carried as they are
-  u32x4 breg[JB];                                   // 16 bytes of W: 8 bf16, or 16 fp8 (W8)
+  u32x4 breg[JB];                                   // 16 bytes of W: 8 bf16, 16 fp8 (W8) or 32 e2m1 (W4)
+  unsigned int bsc[JB];                             // W4: the e8m0 code of that block
   auto load_tiles = [&](int s) {
     const int ko = A16 ? a_offset(s * TBK) / 2 : a_offset(s * TBK);       // in floats (A16: two bf16 per float slot)
 #pragma unroll
     for (int j = 0; j < JA; ++j) areg[j] = ldg4(aptr[j] + ko);
 #pragma unroll
     for (int j = 0; j < JB; ++j) breg[j] = ldg16b(w_ptr(j, s));
+    if constexpr (W4) {
+#pragma unroll
+      for (int j = 0; j < JB; ++j) bsc[j] = *ws_ptr(j, s);
+    }
   };
   // `on` = 0 for the redundant store after the last k-step (the store stays unconditional, see the header)
   auto store_tiles = [&](int buf, float on) {
@@ -283,7 +304,11 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16w_tiled_kernel(const GemmPara
     }
 #pragma unroll
     for (int j = 0; j < JB; ++j) {
-      if (W8) {
+      if constexpr (W4) {
+        const float scale = e8m0_to_f32(bsc[j]);
+#pragma unroll
+        for (int d = 0; d < 4; ++d) *reinterpret_cast<bf16x8*>(b_dst + RB * j * T_LD + 8 * d) = mxfp4x8_to_bf16(breg[j][d], scale);
+      } else if (W8) {
         *reinterpret_cast<bf16x8*>(b_dst + RB * j * T_LD) = fp8x8_to_bf16(breg[j][0], breg[j][1]);
         *reinterpret_cast<bf16x8*>(b_dst + RB * j * T_LD + 8) = fp8x8_to_bf16(breg[j][2], breg[j][3]);
       } else {
@@ -416,6 +441,11 @@ int init_gemm_bf16_tiled_kernels() {
                                    hipFuncAttributeMaxDynamicSharedMemorySize, tiled_lds_bytes(BM_, BN_, BK_)))
   M3_GRP8_ATTR(128, 128, 64, 1); M3_GRP8_ATTR(128, 128, 64, 2); M3_GRP8_ATTR(64, 64, 128, 1); M3_GRP8_ATTR(64, 64, 128, 2);
 #undef M3_GRP8_ATTR
+#define M3_GRP4_ATTR(BM_, BN_, BK_, P_)                                                                                              \
+  M3_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_bf16w_tiled_kernel<BM_, BN_, BK_, false, false, false, P_, false, false, true>, \
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, tiled_lds_bytes(BM_, BN_, BK_)))
+  M3_GRP4_ATTR(128, 128, 64, 1); M3_GRP4_ATTR(128, 128, 64, 2); M3_GRP4_ATTR(64, 64, 128, 1); M3_GRP4_ATTR(64, 64, 128, 2);
+#undef M3_GRP4_ATTR
   once.mark();
   return 0;
 }
@@ -458,8 +488,9 @@ int launch_gemm_bf16w_tiled(const GemmPlan& plan, const GemmParams& pin, hipStre
 // ---- grouped expert FFN on the tiled core (long batches) ----
 // H = SiLU(X[pos] W1[e]^T + b1[e]) (bf16, sorted rows), Y = H W2[e]^T (fp32, sorted rows; b2, gate, residual and
 // LayerNorm are applied by moe_combine_kernel with one "slab").  hbuf: S*F bf16, ybuf: S*D fp32.
-// w_fp8: fp8 expert weights + per-row scales s1 / s2 (W8A16, see moe_expert_fp8.hip), else bf16 weights.
-int launch_expert_tiled_w16(bool w_fp8, const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D,
+// w_fp8 = 1: fp8 expert weights + per-row scales s1 / s2 (W8A16, see moe_expert_fp8.hip); 2: MXFP4 expert weights, s1 / s2 carry
+// the e8m0 scale bytes (W4A16, see moe_expert_mxfp4.hip); 0: bf16 weights.
+int launch_expert_tiled_w16(int w_fp8, const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D,
                             int F, const void* w1, const float* s1, const float* b1, const void* w2, const float* s2,
                             int w2_sliced, void* hbuf, float* ybuf, hipStream_t stream, const float* b2, float* y_scatter) {
   M3_REQUIRE((D & 127) == 0 && (F & 127) == 0, "expert_ffn tiled: idim=%d / hidden=%d must be multiples of 128", D, F);
@@ -483,14 +514,16 @@ int launch_expert_tiled_w16(bool w_fp8, const float* x, int ldx, const int32_t* 
   if (y_scatter != nullptr) {   // the expert-parallel receive side: + b2, and every sorted row straight back to the wire row it came from
     g2.Y = y_scatter; g2.y_rows = pos; g2.bias = b2;
   }
-#define M3_GRP_LAUNCH(BM_, BN_, BK_, W8_)                                                                                 \
-  do {                                                                                                                    \
-    hipLaunchKernelGGL((gemm_bf16w_tiled_kernel<BM_, BN_, BK_, false, false, false, 1, W8_>), dim3(m_slots * g1.n_tiles), \
-                       dim3(256), tiled_lds_bytes(BM_, BN_, BK_), stream, g1);                                            \
-    hipLaunchKernelGGL((gemm_bf16w_tiled_kernel<BM_, BN_, BK_, false, false, false, 2, W8_>), dim3(m_slots * g2.n_tiles), \
-                       dim3(256), tiled_lds_bytes(BM_, BN_, BK_), stream, g2);                                            \
+#define M3_GRP_LAUNCH(BM_, BN_, BK_, W8_, ...)                                                                                        \
+  do {                                                                                                                                \
+    hipLaunchKernelGGL((gemm_bf16w_tiled_kernel<BM_, BN_, BK_, false, false, false, 1, W8_, ##__VA_ARGS__>), dim3(m_slots * g1.n_tiles), \
+                       dim3(256), tiled_lds_bytes(BM_, BN_, BK_), stream, g1);                                                        \
+    hipLaunchKernelGGL((gemm_bf16w_tiled_kernel<BM_, BN_, BK_, false, false, false, 2, W8_, ##__VA_ARGS__>), dim3(m_slots * g2.n_tiles), \
+                       dim3(256), tiled_lds_bytes(BM_, BN_, BK_), stream, g2);                                                        \
   } while (0)
-  if (w_fp8) {
+  if (w_fp8 == 2) {
+    if (big) M3_GRP_LAUNCH(128, 128, 64, false, false, true); else M3_GRP_LAUNCH(64, 64, 128, false, false, true);
+  } else if (w_fp8) {
     if (big) M3_GRP_LAUNCH(128, 128, 64, true); else M3_GRP_LAUNCH(64, 64, 128, true);
   } else {
     if (big) M3_GRP_LAUNCH(128, 128, 64, false); else M3_GRP_LAUNCH(64, 64, 128, false);

@@ -36,7 +36,8 @@ struct GemmParams {
   const float* resid = nullptr; int ldr = 0;
   // grouped (per-expert) form of the tiled bf16 kernel: row tiles cut from acc_hist, optional row gather, slice-major W
   const int32_t* grp_acc = nullptr; int grp_E = 0; const int32_t* grp_pos = nullptr; int w_sliced = 0;
-  const float* w_scale = nullptr;                         // fp8 weights (grouped forms): per-output-row scale [E][N]
+  const float* w_scale = nullptr;                         // fp8 weights (grouped forms): per-output-row scale [E][N]; MXFP4 weights: the
+                                                          // e8m0 scale BYTES, [E][N][K/32] or slice-major [E][K/64][N][2] (w_sliced)
   // bf16 activation copies (16-bit modes, tiled kernel only): A given as bf16 [M][lda], Y written as bf16, and / or an
   // additional bf16 copy Yb of the fp32 output (the residual stream stays fp32, its GEMM consumers read the copy)
   int a_bf16 = 0, y_bf16 = 0; void* Yb = nullptr; int ldyb = 0;
@@ -172,20 +173,21 @@ int launch_ep_recv_gate(const void* wire, int world, int e_loc, int capacity, in
 constexpr int kExpertSliceW16 = 64;            // the bf16 / e4m3 slab kernels are laid out for 64-wide slices
 constexpr int kExpertSlice = M3_EXPERT_SLICE;  // hidden units per workgroup (16 per wave); m3asr/plan.py EXPERT_SLICE must match
 size_t expert_ffn_slab_bytes(int S, int D, int F);   // the slab region: F / kExpertSlice partial-result slabs of [S][D] fp32
-// The operator runs in eight forms.  plan_expert_ffn (moe_expert_plan.hip) is the ONE place that says which of them runs for a
+// The operator runs in ten forms.  plan_expert_ffn (moe_expert_plan.hip) is the ONE place that says which of them runs for a
 // weight dtype and shape, in how many launches, and where in the slab region its sections are; launch_expert_ffn runs a plan,
 // and the combine step, the launch accounting and the observability entries read the same plan.  First match wins:
 //   FusedFp8   FP8A8, D = 512, F % 128 == 0, F <= 4096, E <= 1024, S >= 4096 (M3_EXPERT_FUSED_FP8_MIN_ROWS), S >= 64 E,
 //              and an F split exists (expert_ffn_fused_fp8_fsplit)          1 launch,   fsplit slabs of sorted rows at offset 0
 //   G256Bf16   BF16, a TiledBf16 shape with E <= 64, S / E >= 512 (M3_G256_MIN_ROWS_PER_EXPERT), D, F % 256 == 0,
 //              not EXPERT_SCATTER_ROWS                                      3 launches, H | sorted rows | bf16 row copy
-//   Tiled*     S >= 1024 (M3_EXPERT_TILED_MIN_ROWS), D, F % 64 == 0 (fp32) or % 128 == 0 (bf16, fp8; FP8A8 where the fused
-//              form does not apply), not EXPERT_NORM_IN_KERNEL              2 launches, H | sorted rows (one slab)
-//   Slab*      everything else                                              1 launch,   F / 64 partial-result slabs at offset 0
+//   Tiled*     S >= 1024 (M3_EXPERT_TILED_MIN_ROWS), D, F % 64 == 0 (fp32) or % 128 == 0 (bf16, fp8, mxfp4; FP8A8 where the
+//              fused form does not apply), not EXPERT_NORM_IN_KERNEL        2 launches, H | sorted rows (one slab)
+//   Slab*      everything else: D % 16 == 0 (fp32), % 32 (bf16), % 64 (fp8), % 128 (mxfp4: SlabW4), D <= 2048, F % 64 == 0
+//                                                                           1 launch,   F / 64 partial-result slabs at offset 0
 // A form is taken only if all its sections fit into expert_ffn_slab_bytes.  The thresholds are read once per process.
 // (SlabF32's weight stream keeps the default cache policy also where every byte has one reader: non-temporal loads there lost)
-enum class ExpertWeights { F32, BF16, FP8, FP8A8 };   // FP8A8: fp8 weights + fp8 activations where FusedFp8 applies, else the weight-only forms
-enum class ExpertKernel { SlabF32, TiledF32, SlabBf16, TiledBf16, G256Bf16, SlabW8, TiledW8, FusedFp8 };
+enum class ExpertWeights { F32, BF16, FP8, FP8A8, MXFP4 };   // FP8A8: fp8 weights + fp8 activations where FusedFp8 applies, else the weight-only forms
+enum class ExpertKernel { SlabF32, TiledF32, SlabBf16, TiledBf16, G256Bf16, SlabW8, TiledW8, FusedFp8, SlabW4, TiledW4 };
 struct ExpertFfnPlan {
   ExpertWeights weights; ExpertKernel kernel;
   const char* label;      // the kernel's name as rocprofv3 shows it
@@ -198,7 +200,8 @@ enum { EXPERT_NORM_IN_KERNEL = 1,    // norm_ff applied while gathering rows: fp
        EXPERT_SCATTER_ROWS = 2 };    // GEMM-2 writes b2 + rows to y_scatter[pos[i]]: bf16 tiled form only, never g256
 ExpertFfnPlan plan_expert_ffn(ExpertWeights w, int S, int E, int D, int F, unsigned flags = 0);
 // x [S][ldx] fp32 rows, sorted by expert through (pos, acc_hist); w1 [E][F][D], w2 [E][D][F] or slice-major (w2_sliced) in the
-// plan's weight dtype; s1 [E][F] / s2 [E][D]: fp8 per-row scales.  ln_*: SlabF32 under EXPERT_NORM_IN_KERNEL.  h_scale, xq /
+// plan's weight dtype; s1 [E][F] / s2 [E][D]: fp8 per-row scales.  MXFP4: w1 [E][F][D/2], w2 [E][D][F/2] or slice-major
+// [E][F/64][D][32] code bytes, s1 / s2 carry the e8m0 scale BYTES ([E][F][D/32]; [E][D][F/32] or [E][F/64][D][2]).  ln_*: SlabF32 under EXPERT_NORM_IN_KERNEL.  h_scale, xq /
 // xq_scale (rows already quantised by the router kernel), fs_dev (the kernel may split F finer than the plan and leaves the
 // slab count there): FusedFp8.  b2 / y_scatter: TiledBf16 under EXPERT_SCATTER_ROWS (the un-permute of the expert-parallel
 // receive side, folded into GEMM-2's epilogue).
@@ -226,6 +229,11 @@ int init_expert_ffn_w8_kernels();
 int launch_expert_ffn_w8_slab(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D, int F,
                               const void* w1, const float* s1, const float* b1, const void* w2, const float* s2, int w2_sliced,
                               float* slab, hipStream_t stream);
+// MXFP4 expert weights (e2m1 code pairs + e8m0 block scales), decoded to bf16 at the MFMA input (moe_expert_mxfp4.hip); same result layout
+int init_expert_ffn_w4_kernels();
+int launch_expert_ffn_w4_slab(const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E, int D, int F,
+                              const void* w1, const void* s1, const float* b1, const void* w2, const void* s2, int w2_sliced,
+                              float* slab, hipStream_t stream);
 // fp8 arithmetic (e4m3 weights x e4m3 activations, fp8 MFMA), long batches (D = 512): moe_expert_fused_fp8.hip.
 // The F split its cost model picks for a shape the kernel takes, 0 where it does not apply (the row threshold is the plan's)
 constexpr int kExpertFusedFp8MaxSplit = 4;     // ... at most this (what the combine allots when the kernel picks the split on the device)
@@ -236,10 +244,10 @@ int launch_expert_ffn_fused_fp8(const float* x, int ldx, const int32_t* pos, con
                                 float h_scale, int fsplit, float* ybuf, hipStream_t stream, const void* xq = nullptr,
                                 const float* xq_scale = nullptr, int32_t* fs_dev = nullptr);
 int launch_quantize_rows_e4m3(const float* x, int ldx, int S, int D, void* xq, float* scale, hipStream_t stream);   // moe_expert_fused_fp8.hip
-// long batches, bf16 or fp8 (w_fp8: s1 / s2 per-row scales) weights: two grouped GEMMs on the LDS-tiled bf16 core
-// (gemm_bf16_tiled.hip); hbuf S*F bf16, ybuf S*D fp32.  b2 / y_scatter (optional, bf16 weights): GEMM-2 adds the expert's b2
+// long batches, bf16, fp8 (w_fp8 = 1: s1 / s2 per-row scales) or MXFP4 (w_fp8 = 2: s1 / s2 the scale bytes) weights: two grouped GEMMs
+// on the LDS-tiled bf16 core (gemm_bf16_tiled.hip); hbuf S*F bf16, ybuf S*D fp32.  b2 / y_scatter (optional, bf16 weights): GEMM-2 adds the expert's b2
 // and writes row i of the sorted order to row pos[i] of y_scatter
-int launch_expert_tiled_w16(bool w_fp8, const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E,
+int launch_expert_tiled_w16(int w_fp8, const float* x, int ldx, const int32_t* pos, const int32_t* acc_hist, int S, int E,
                             int D, int F, const void* w1, const float* s1, const float* b1, const void* w2, const float* s2,
                             int w2_sliced, void* hbuf, float* ybuf, hipStream_t stream, const float* b2 = nullptr,
                             float* y_scatter = nullptr);

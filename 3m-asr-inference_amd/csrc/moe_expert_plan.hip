@@ -17,7 +17,7 @@ ExpertFfnPlan plan_expert_ffn(ExpertWeights w, int S, int E, int D, int F, unsig
   static const int tiled_min_rows = env_int("M3_EXPERT_TILED_MIN_ROWS", 1024);
   static const int fused_min_rows = env_int("M3_EXPERT_FUSED_FP8_MIN_ROWS", 4096);
   static const int g256_min_rows_per_expert = env_int("M3_G256_MIN_ROWS_PER_EXPERT", 512);
-  const bool f32 = w == ExpertWeights::F32, bf16 = w == ExpertWeights::BF16;
+  const bool f32 = w == ExpertWeights::F32, bf16 = w == ExpertWeights::BF16, w4 = w == ExpertWeights::MXFP4;
   ExpertFfnPlan p{};
   p.weights = w;
   p.label = "";
@@ -46,15 +46,15 @@ ExpertFfnPlan plan_expert_ffn(ExpertWeights w, int S, int E, int D, int F, unsig
     } else if (f32) {
       p.kernel = ExpertKernel::TiledF32; p.label = "expert_gemm_f32_tiled_kernel";
     } else {
-      p.kernel = bf16 ? ExpertKernel::TiledBf16 : ExpertKernel::TiledW8;
-      p.label = bf16 ? "gemm_bf16w_tiled_kernel<grouped>" : "gemm_bf16w_tiled_kernel<grouped,fp8>";
+      p.kernel = bf16 ? ExpertKernel::TiledBf16 : w4 ? ExpertKernel::TiledW4 : ExpertKernel::TiledW8;
+      p.label = bf16 ? "gemm_bf16w_tiled_kernel<grouped>" : w4 ? "gemm_bf16w_tiled_kernel<grouped,mxfp4>" : "gemm_bf16w_tiled_kernel<grouped,fp8>";
     }
     return p;
   }
   // one launch, every 64-wide slice of F leaves a partial result: F / 64 slabs of [S][D]
-  p.kernel = f32 ? ExpertKernel::SlabF32 : bf16 ? ExpertKernel::SlabBf16 : ExpertKernel::SlabW8;
-  p.label = f32 ? "expert_ffn_f32_kernel" : bf16 ? "expert_ffn_bf16w_kernel" : "expert_ffn_w8_kernel";
-  const int slice = f32 ? kExpertSlice : kExpertSliceW16, d_mult = f32 ? 16 : bf16 ? 32 : 64;
+  p.kernel = f32 ? ExpertKernel::SlabF32 : bf16 ? ExpertKernel::SlabBf16 : w4 ? ExpertKernel::SlabW4 : ExpertKernel::SlabW8;
+  p.label = f32 ? "expert_ffn_f32_kernel" : bf16 ? "expert_ffn_bf16w_kernel" : w4 ? "expert_ffn_w4_kernel" : "expert_ffn_w8_kernel";
+  const int slice = f32 ? kExpertSlice : kExpertSliceW16, d_mult = f32 ? 16 : bf16 ? 32 : w4 ? 128 : 64;
   p.slices = F / slice;
   p.launches = D % d_mult == 0 && D <= 2048 && F % slice == 0 ? 1 : 0;   // 0: dimensions the slab launchers reject (they say why)
   return p;
@@ -76,7 +76,7 @@ int launch_expert_ffn(const ExpertFfnPlan& plan, int S, int E, int D, int F, con
     case ExpertKernel::SlabBf16:
       return launch_expert_ffn_bf16w_slab(a.x, a.ldx, a.pos, a.acc_hist, S, E, D, F, a.w1, a.b1, a.w2, a.w2_sliced, ybuf, stream);
     case ExpertKernel::TiledBf16:
-      return launch_expert_tiled_w16(false, a.x, a.ldx, a.pos, a.acc_hist, S, E, D, F, a.w1, nullptr, a.b1, a.w2, nullptr, a.w2_sliced,
+      return launch_expert_tiled_w16(0, a.x, a.ldx, a.pos, a.acc_hist, S, E, D, F, a.w1, nullptr, a.b1, a.w2, nullptr, a.w2_sliced,
                                      hbuf, ybuf, stream, a.b2, a.y_scatter);
     case ExpertKernel::G256Bf16: {
       void* const xb = region + plan.xb_off;
@@ -86,7 +86,12 @@ int launch_expert_ffn(const ExpertFfnPlan& plan, int S, int E, int D, int F, con
     case ExpertKernel::SlabW8:
       return launch_expert_ffn_w8_slab(a.x, a.ldx, a.pos, a.acc_hist, S, E, D, F, a.w1, a.s1, a.b1, a.w2, a.s2, a.w2_sliced, ybuf, stream);
     case ExpertKernel::TiledW8:
-      return launch_expert_tiled_w16(true, a.x, a.ldx, a.pos, a.acc_hist, S, E, D, F, a.w1, a.s1, a.b1, a.w2, a.s2, a.w2_sliced, hbuf,
+      return launch_expert_tiled_w16(1, a.x, a.ldx, a.pos, a.acc_hist, S, E, D, F, a.w1, a.s1, a.b1, a.w2, a.s2, a.w2_sliced, hbuf,
+                                     ybuf, stream);
+    case ExpertKernel::SlabW4:
+      return launch_expert_ffn_w4_slab(a.x, a.ldx, a.pos, a.acc_hist, S, E, D, F, a.w1, a.s1, a.b1, a.w2, a.s2, a.w2_sliced, ybuf, stream);
+    case ExpertKernel::TiledW4:
+      return launch_expert_tiled_w16(2, a.x, a.ldx, a.pos, a.acc_hist, S, E, D, F, a.w1, a.s1, a.b1, a.w2, a.s2, a.w2_sliced, hbuf,
                                      ybuf, stream);
     case ExpertKernel::FusedFp8:
       // (xq / xq_scale: only this kernel takes them; x stays valid for the other forms)

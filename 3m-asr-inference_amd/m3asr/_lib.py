@@ -115,7 +115,7 @@ class WeightEntry(C.Structure):  # m3_weight_entry
 
 
 FIELD_FLOAT32, FIELD_INT32 = 1, 5
-F32, F16, I8, I32, BF16, FP8 = 0, 1, 2, 3, 4, 5
+F32, F16, I8, I32, BF16, FP8, MXFP4 = 0, 1, 2, 3, 4, 5, 6
 ACT_NONE, ACT_RELU, ACT_SILU, ACT_GLU, ACT_SIGMOID, ACT_LOG = 0, 1, 2, 3, 4, 5
 OP_SUM, OP_PROD = 0, 1
 
@@ -157,6 +157,10 @@ SIGNATURES = {
                                     _vp, _sz, _vp]),
     "m3_moe_expert_ffn_fp8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _f, _vp,
                                    _vp, _sz, _vp]),
+    "m3_moe_expert_ffn_mxfp4": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _f, _vp,
+                                     _vp, _sz, _vp]),
+    "m3_moe_expert_ffn_mxfp4_ldx": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _f, _vp,
+                                         _vp, _sz, _vp]),
     "m3_moe_expert_ffn_fp8a8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _f, _vp,
                                      _vp, _sz, _vp]),
     "m3_moe_expert_ffn_fp8a8_active": (_i, [_i, _i, _i, _i]),

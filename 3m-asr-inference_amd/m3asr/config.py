@@ -36,6 +36,8 @@ class EncoderConfig:
     # storage of the GEMM weights: "f32" (exact fp32 MFMA) or "bf16" (bf16 MFMA, fp32 accumulate; activations stay
     # fp32) = the reference's --fp16 / plugin_data_type 1 (builder.py:160, builder_helper.py:47-57); "fp8" = bf16 dense
     # weights + e4m3 expert weights with per-row scales, dequantised to bf16 at the MFMA input (the --int8 slot of the reference)
+    # "mxfp4" = bf16 dense weights + OCP MXFP4 expert weights (e2m1 elements, one e8m0 scale per 32 along K; plan.quantize_mxfp4),
+    # decoded to bf16 at the MFMA input (W4A16): half the expert bytes of "fp8"
     weight_dtype: str = "f32"
     # weight_dtype "fp8" only: fp8 ARITHMETIC (e4m3 x e4m3 MFMA) in the grouped expert FFN of long batches -- rows quantised
     # with a per-row dynamic scale, H with the calibrated per-layer scale "blocks.N.feed_forward.experts.h_scale" of the
@@ -53,6 +55,10 @@ class EncoderConfig:
     # Together with static_chunk_size > 0 this is the configuration that can be decoded chunk by chunk (Engine.streaming).
     causal: bool = False
     embed_causal: bool = False
+
+    def __post_init__(self):
+        if self.weight_dtype == "mxfp4" and self.fp8_activations:
+            raise ValueError("EncoderConfig: fp8_activations needs weight_dtype 'fp8'; 'mxfp4' is a weight-only mode (W4A16)")
 
     def fp8_label(self):
         """What the fp8 mode of this config computes in (for reports: a weight-only mode must not read as fp8 MFMA)."""

@@ -16,7 +16,8 @@ from .config import EncoderConfig, subsampled_len
 from .plan import pack_weights
 
 
-_TORCH_DTYPE = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.int32: _lib.I32, torch.float8_e4m3fn: _lib.FP8}
+_TORCH_DTYPE = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.int32: _lib.I32, torch.float8_e4m3fn: _lib.FP8,
+                torch.uint8: _lib.MXFP4}    # uint8: packed e2m1 code pairs and e8m0 scale bytes of an mxfp4 plan
 
 
 def _engine_config(cfg: EncoderConfig, fold_pos_proj, debug_taps, fuse_route=False, bf16_activations=True, packed_rows=None,
@@ -35,7 +36,7 @@ def _engine_config(cfg: EncoderConfig, fold_pos_proj, debug_taps, fuse_route=Fal
     ec.fold_pos_proj, ec.debug_taps, ec.fuse_route = int(fold_pos_proj), int(debug_taps), int(fuse_route)
     ec.log_softmax_out = int(cfg.log_softmax_out)
     ec.bf16_activations = 0 if bf16_activations else -1
-    ec.weight_dtype = {"f32": _lib.F32, "bf16": _lib.BF16, "fp8": _lib.FP8}[cfg.weight_dtype]
+    ec.weight_dtype = {"f32": _lib.F32, "bf16": _lib.BF16, "fp8": _lib.FP8, "mxfp4": _lib.MXFP4}[cfg.weight_dtype]
     ec.packed_rows = 0 if packed_rows is None else (1 if packed_rows else -1)
     ec.fp8_activations = int(bool(getattr(cfg, "fp8_activations", False)) and cfg.weight_dtype == "fp8")
     ec.ep_stages = int(bool(ep_stages))

@@ -114,7 +114,8 @@ def moe_expert_ffn(x, gate_idx, w1, b1, w2, b2, gate_value=None, resid=None, alp
                    w1_scale=None, w2_scale=None, out=None, h_scale=None, xq=None, xq_scale=None):
     """FMoEExpert: x (S,D) f32, gate_idx (S,) i32 -> y (S,D).  Optional fused epilogue (gate, residual, LayerNorm).
     The expert weights pick the kernel family: fp32; bf16 (bf16 MFMA, fp32 accumulate); e4m3 with per-row scales
-    w1_scale [E,F] / w2_scale [E,D] (dequantised to bf16 at the MFMA input; with h_scale: fp8 arithmetic, activations
+    w1_scale [E,F] / w2_scale [E,D]; uint8 MXFP4 code pairs with uint8 block scales (decoded to bf16 at the MFMA input,
+    m3_moe_expert_ffn_mxfp4) (fp8: dequantised to bf16 at the MFMA input; with h_scale: fp8 arithmetic, activations
     quantised too -- m3_moe_expert_ffn_fp8a8; xq / xq_scale: the rows already quantised by quantize_rows_e4m3, read instead
     of x where the fused kernel applies -- m3_moe_expert_ffn_fp8a8_xq).  Biases are fp32 in every mode."""
     lib = _lib.load()
@@ -143,6 +144,15 @@ def moe_expert_ffn(x, gate_idx, w1, b1, w2, b2, gate_value=None, resid=None, alp
         assert w1_scale is not None and w2_scale is not None, "fp8 expert weights need their per-row scales"
         check(lib.m3_moe_expert_ffn_fp8(xi, gi, _p(w1), _f32(w1_scale), _f32(b1), _p(w2), _f32(w2_scale), _f32(b2), *tail),
               "m3_moe_expert_ffn_fp8")
+    elif w1.dtype == torch.uint8:
+        # MXFP4 (plan.quantize_mxfp4 along K): w1 [E,F,D/2] + w1_scale [E,F,D/32], w2 [E,D,F/2] + w2_scale [E,D,F/32], all uint8
+        assert w1_scale is not None and w2_scale is not None and w1_scale.dtype == torch.uint8 and w2_scale.dtype == torch.uint8, \
+            "mxfp4 expert weights need their uint8 block scales"
+        assert w1.shape[2] * 2 == D and tuple(w2.shape) == (E, D, F // 2), "mxfp4 expert weights: two codes per byte along K"
+        assert tuple(w1_scale.shape) == (E, F, D // 32) and tuple(w2_scale.shape) == (E, D, F // 32)
+        assert w1_scale.is_contiguous() and w2_scale.is_contiguous()
+        check(lib.m3_moe_expert_ffn_mxfp4(xi, gi, _p(w1), _p(w1_scale), _f32(b1), _p(w2), _p(w2_scale), _f32(b2), *tail),
+              "m3_moe_expert_ffn_mxfp4")
     elif w1.dtype == torch.bfloat16:
         check(lib.m3_moe_expert_ffn_bf16(xi, gi, _p(w1), _f32(b1), _p(w2), _f32(b2), *tail), "m3_moe_expert_ffn_bf16")
     else:

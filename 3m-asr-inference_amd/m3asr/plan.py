@@ -328,18 +328,67 @@ def quantize_fp8_rows(w, dims):
     return q, scale.squeeze(dims).contiguous()
 
 
+MX_BLOCK = 32      # elements per OCP MX block (one e8m0 scale each), along the GEMM's K
+_E2M1_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def quantize_mxfp4(w, dim):
+    """OCP MXFP4 along `dim` (the GEMM's K, a multiple of 32): e2m1 elements, one e8m0 scale byte per 32 consecutive elements.
+    -> (q uint8, `dim` halved: two codes per byte, the even-k element in the low nibble; scale uint8, `dim` / 32).
+    Scale code s = clamp(floor(log2(amax)) - 2, -64, 64) + 127 (the clamp keeps every decoded value a normal bf16 and the code
+    away from 0 and 255; an all-zero block stores 127).  Elements: w / 2^(s - 127) rounded to the nearest of
+    {0, 0.5, 1, 1.5, 2, 3, 4, 6}, ties to the even code, saturating at +-6; sign in bit 3 (a zero carries none).
+    This is the ONE definition of the format: the kernels (csrc/moe_expert_mxfp4.hip) decode exactly this."""
+    dim = dim % w.dim()
+    K = w.shape[dim]
+    assert K % MX_BLOCK == 0, "mxfp4: K = %d must be a multiple of %d" % (K, MX_BLOCK)
+    v = w.detach()
+    v = (v if v.dtype in (torch.float32, torch.float64) else v.float()).movedim(dim, -1)   # powers of two: exact in either
+    blk = v.reshape(*v.shape[:-1], K // MX_BLOCK, MX_BLOCK)
+    amax = blk.abs().amax(-1)
+    _, ex = torch.frexp(amax)                                  # amax = m 2^ex, m in [0.5, 1): floor(log2 amax) = ex - 1
+    e = (ex.long() - 3).clamp(-64, 64)
+    e = torch.where(amax > 0, e, torch.zeros_like(e))
+    a = torch.ldexp(blk.abs(), (-e).unsqueeze(-1).expand_as(blk).to(torch.int32))
+    # midpoints of neighbouring grid values; a tie goes to the even code
+    code = ((a > 0.25).to(torch.uint8) + (a >= 0.75).to(torch.uint8) + (a > 1.25).to(torch.uint8) + (a >= 1.75).to(torch.uint8) +
+            (a > 2.5).to(torch.uint8) + (a >= 3.5).to(torch.uint8) + (a > 5.0).to(torch.uint8))
+    code = code + (((blk < 0) & (code > 0)).to(torch.uint8) << 3)
+    code = code.reshape(*v.shape[:-1], K // 2, 2)
+    q = (code[..., 0] | (code[..., 1] << 4)).movedim(-1, dim).contiguous()
+    scale = (e + 127).to(torch.uint8).movedim(-1, dim).contiguous()
+    return q, scale
+
+
+def dequantize_mxfp4(q, scale, dim):
+    """Inverse of quantize_mxfp4 on its own output: fp32 values (every one exact in bf16), `dim` doubled."""
+    dim = dim % q.dim()
+    qv, sv = q.movedim(dim, -1), scale.movedim(dim, -1)
+    code = torch.stack([qv & 15, qv >> 4], -1).reshape(*qv.shape[:-1], qv.shape[-1] * 2).long()
+    mag = torch.tensor(_E2M1_GRID, dtype=torch.float32)[code & 7]
+    val = torch.where((code & 8) != 0, -mag, mag)
+    ex = (sv.to(torch.int32) - 127).repeat_interleave(MX_BLOCK, -1)
+    return torch.ldexp(val, ex).float().movedim(-1, dim).contiguous()
+
+
 def cast_gemm_weights(packed, cfg: EncoderConfig):
     """Store the GEMM weights in cfg.weight_dtype ("f32" = no-op, "bf16" = round to nearest even).  The reference
     wires --fp16 / plugin_data_type = 1 (builder.py:160, builder_helper.py:47-57,109-123) without finishing it; bf16 is
     the 16-bit type on CDNA4.  "fp8": additionally the expert weights (94 % of the parameters) become e4m3 with one scale per
-    output row (W8A16: dequantised to bf16 at the MFMA input).  The folded LayerNorm's column sums are recomputed from the ROUNDED weights, so that
+    output row (W8A16: dequantised to bf16 at the MFMA input); "mxfp4": the expert weights become MXFP4 instead (quantize_mxfp4 along
+    each GEMM's K: uint8 code pairs + uint8 scale bytes, W4A16), everything else as in "fp8".  The folded LayerNorm's column sums are recomputed from the ROUNDED weights, so that
     y = rstd * (a . W'^T - mean * wsum) stays an exact identity for the weights the kernel really multiplies by."""
     if cfg.weight_dtype == "f32":
         return packed
-    assert cfg.weight_dtype in ("bf16", "fp8"), cfg.weight_dtype
+    assert cfg.weight_dtype in ("bf16", "fp8", "mxfp4"), cfg.weight_dtype
     out = OrderedDict()
     for k, v in packed.items():
-        if cfg.weight_dtype == "fp8" and v.dtype == torch.float32 and k.endswith("experts.w_1.weight"):
+        if cfg.weight_dtype == "mxfp4" and v.dtype == torch.float32 and k.endswith("experts.w_1.weight"):
+            out[k], out[k[:-len("weight")] + "scale"] = quantize_mxfp4(v, dim=2)          # [E][F][D/2] + [E][F][D/32]
+        elif cfg.weight_dtype == "mxfp4" and v.dtype == torch.float32 and k.endswith("experts.w_2.weight_sliced"):
+            # [E][F/64][D][64]: K = F runs along the last axis inside a slice -> [E][F/64][D][32] + [E][F/64][D][2]
+            out[k], out[k[:-len("weight_sliced")] + "scale"] = quantize_mxfp4(v, dim=3)
+        elif cfg.weight_dtype == "fp8" and v.dtype == torch.float32 and k.endswith("experts.w_1.weight"):
             q, sc = quantize_fp8_rows(v, dims=(2,))                       # [E][F][D]: one scale per (e, f)
             out[k], out[k[:-len("weight")] + "scale"] = q, sc
         elif cfg.weight_dtype == "fp8" and v.dtype == torch.float32 and k.endswith("experts.w_2.weight_sliced"):
@@ -356,8 +405,8 @@ def cast_gemm_weights(packed, cfg: EncoderConfig):
 
 
 _DTYPES = {"f32": (torch.float32, "<f4", 4), "bf16": (torch.bfloat16, "<u2", 2), "i32": (torch.int32, "<i4", 4),
-           "fp8": (torch.float8_e4m3fn, "u1", 1)}
-_DTYPE_NAME = {torch.float32: "f32", torch.bfloat16: "bf16", torch.int32: "i32", torch.float8_e4m3fn: "fp8"}
+           "fp8": (torch.float8_e4m3fn, "u1", 1), "u8": (torch.uint8, "u1", 1)}
+_DTYPE_NAME = {torch.float32: "f32", torch.bfloat16: "bf16", torch.int32: "i32", torch.float8_e4m3fn: "fp8", torch.uint8: "u8"}
 
 
 def save_plan(path, cfg: EncoderConfig, packed, extra=None):

@@ -85,6 +85,10 @@ class BuilderHelper:
             self.weight_dtype, self.fp8_activations = "fp8", True
         elif getattr(config, "use_fp8", False):
             self.weight_dtype = "fp8"
+        if getattr(config, "use_mxfp4", False):     # 4-bit block-scaled expert weights, weight-only: excludes the other modes
+            if self.weight_dtype != "f32":
+                raise RuntimeError("use_mxfp4 excludes use_fp16 / use_int8 / use_fp8")
+            self.weight_dtype = "mxfp4"
         self.device = torch.device(device)
         self.profiles = {}
         self.model, self.model_cfg = None, None

@@ -44,6 +44,8 @@ def build_trt(model, args, input_dim, plan_name, prior=None, profile=None, decod
         cfg.use_fp16, cfg.plugin_data_type = True, trt.DataType.HALF
     if args.fp8:
         cfg.use_fp8 = True                          # e4m3 expert weights + bf16 dense weights (W8A16), no calibration needed
+    if args.mxfp4:
+        cfg.use_mxfp4 = True                        # MXFP4 expert weights + bf16 dense weights (W4A16), no calibration needed
     calibrator = None
     if args.int8:
         # the reference's 8-bit slot (builder.py:43-47 there: plugin_data_type, use_int8 and an AsrCalibrator over lists of
@@ -125,6 +127,8 @@ if __name__ == "__main__":
     p.add_argument("-f", "--fp16", action="store_true")
     p.add_argument("-i", "--int8", action="store_true")
     p.add_argument("--fp8", action="store_true", help="expert weights as fp8 e4m3 with per-row scales, dense weights bf16")
+    p.add_argument("--mxfp4", action="store_true",
+                   help="expert weights as OCP MXFP4 (e2m1, one e8m0 scale per 32 along K), dense weights bf16; not with --fp16 / --int8 / --fp8")
     p.add_argument("--calib-feat-list", default="np_inputs/np_feat.list", help="--int8: text file, one .npy feature batch per line")
     p.add_argument("--calib-feat-len-list", default="np_inputs/np_feat_len.list", help="--int8: matching .npy length files")
     p.add_argument("--calib-cache", default="conformer.int8.cache", help="--int8: calibration cache (JSON of the scales)")
@@ -134,4 +138,7 @@ if __name__ == "__main__":
     p.add_argument("-tcf", "--timing-cache-file", required=False)
     p.add_argument("--verbose", action="store_true")
     p.add_argument("--opt-shape", default=None, help="BxT of the dummy batch the emission runs on (default 4x500)")
-    main(p.parse_args())
+    args = p.parse_args()
+    if args.mxfp4 and (args.fp16 or args.int8 or args.fp8):
+        p.error("--mxfp4 is mutually exclusive with --fp16 / --int8 / --fp8")
+    main(args)

@@ -35,7 +35,8 @@ extern "C" {
 
 typedef void* m3_stream; /* hipStream_t */
 
-enum m3_dtype { M3_F32 = 0, M3_F16 = 1, M3_I8 = 2, M3_I32 = 3, M3_BF16 = 4, M3_FP8 = 5 /* OCP e4m3 */ };
+enum m3_dtype { M3_F32 = 0, M3_F16 = 1, M3_I8 = 2, M3_I32 = 3, M3_BF16 = 4, M3_FP8 = 5 /* OCP e4m3 */,
+                M3_MXFP4 = 6 /* bytes of an OCP MXFP4 tensor: e2m1 code pairs, or its e8m0 block scales */ };
 
 /* activation / element-wise codes shared by several entry points */
 enum m3_act { M3_ACT_NONE = 0, M3_ACT_RELU = 1, M3_ACT_SILU = 2, M3_ACT_GLU = 3, M3_ACT_SIGMOID = 4, M3_ACT_LOG = 5 };
@@ -141,6 +142,22 @@ int m3_moe_expert_ffn_fp8(const float* x, const int32_t* gate_idx, const void* w
                           int idim, int hidden_units, const float* gate_value, const float* resid, float alpha,
                           const float* ln_gamma, const float* ln_beta, float ln_eps, float* y, void* workspace,
                           size_t workspace_bytes, m3_stream stream);
+/* MXFP4 expert weights (W4A16; added under ABI 10): OCP e2m1 elements, two codes per byte with the even-k element in the low
+ * nibble, and one e8m0 scale byte per 32 consecutive k (m3asr/plan.py quantize_mxfp4 is the definition).  w1 [E][F][idim/2],
+ * w1_scale [E][F][idim/32], w2 [E][idim][F/2], w2_scale [E][idim][F/32], all bytes, 16-byte aligned.  idim % 128 == 0,
+ * hidden_units % 64 == 0.  The weights are decoded to bf16 at the MFMA input (exact), rows and H are rounded to bf16 as in
+ * the bf16 form, accumulation fp32.  0.53 MB per touched expert at D=512, F=1024.  _ldx: the same on rows of stride ldx
+ * (a multiple of 4, >= idim). */
+int m3_moe_expert_ffn_mxfp4(const float* x, const int32_t* gate_idx, const void* w1, const void* w1_scale,
+                            const float* b1, const void* w2, const void* w2_scale, const float* b2, int S, int num_expert,
+                            int idim, int hidden_units, const float* gate_value, const float* resid, float alpha,
+                            const float* ln_gamma, const float* ln_beta, float ln_eps, float* y, void* workspace,
+                            size_t workspace_bytes, m3_stream stream);
+int m3_moe_expert_ffn_mxfp4_ldx(const float* x, int ldx, const int32_t* gate_idx, const void* w1, const void* w1_scale,
+                                const float* b1, const void* w2, const void* w2_scale, const float* b2, int S, int num_expert,
+                                int idim, int hidden_units, const float* gate_value, const float* resid, float alpha,
+                                const float* ln_gamma, const float* ln_beta, float ln_eps, float* y, void* workspace,
+                                size_t workspace_bytes, m3_stream stream);
 /* fp8 ARITHMETIC (A8W8; the path the reference's --int8 flag names, builder.py:39-49): e4m3 weights as above, the rows
  * quantised to e4m3 with a per-row dynamic scale (amax / 448) while they are loaded, H quantised with the static per-layer
  * scale h_scale (calibrated: amax of H x 1.25 / 448), products on v_mfma_f32_32x32x16_fp8_fp8, fp32 accumulation.  Taken
@@ -153,7 +170,7 @@ int m3_moe_expert_ffn_fp8a8(const float* x, const int32_t* gate_idx, const void*
                             float alpha, const float* ln_gamma, const float* ln_beta, float ln_eps, float* y,
                             void* workspace, size_t workspace_bytes, m3_stream stream);
 int m3_moe_expert_ffn_fp8a8_active(int S, int num_expert, int idim, int hidden_units);
-/* Host only: the kernel the grouped expert FFN runs for this weight dtype (M3_F32 / M3_BF16 / M3_FP8, fp8_activations 0/1) and shape,
+/* Host only: the kernel the grouped expert FFN runs for this weight dtype (M3_F32 / M3_BF16 / M3_FP8 / M3_MXFP4, fp8_activations 0/1: fp8 only) and shape,
  * its launch count and the number of partial-result slabs; NULL for a shape the operator rejects.  No pointer is dereferenced. */
 const char* m3_moe_expert_ffn_kernel(int weight_dtype, int fp8_activations, int S, int num_expert, int idim, int hidden_units,
                                      int32_t* launches, int32_t* slices);
@@ -776,7 +793,9 @@ typedef struct m3_engine_config {
   int32_t weight_dtype;          /* M3_F32 / M3_BF16: storage of the GEMM weights (linear / point-wise conv /
                                   * conv2 / expert w_1, w_2 / pos_all); router, norms, biases, conv1, depthwise stay fp32.
                                   * M3_FP8: expert w_1 / w_2 in e4m3 with per-row scales ("...w_1.scale", "...w_2.scale"),
-                                  * the other GEMM weights bf16 */
+                                  * the other GEMM weights bf16.  M3_MXFP4: expert w_1 / w_2 as MXFP4 code bytes with block
+                                  * scale bytes ("...w_1.scale", "...w_2.scale"; every such entry has dtype M3_MXFP4), the
+                                  * other GEMM weights bf16; attention_dim % 128 == 0, one rank only */
   int32_t packed_rows;           /* ragged batches (B > 1): run every row-wise kernel of the blocks on the sum of the valid
                                   * frames instead of B x T' padded rows (0 = automatic: on for B > 1 on one rank without
                                   * debug taps / fused routing, -1 = never, 1 = also for B = 1).  The interface does not
