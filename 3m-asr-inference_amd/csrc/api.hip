@@ -902,4 +902,53 @@ int m3_fbank(const void* tables, const void* pcm, int pcm_is_int16, int ld_pcm, 
                       (hipStream_t)stream);
 }
 
+static int resample_rates_ok(const char* who, int rate_in, int rate_out) {
+  M3_REQUIRE(rate_in >= 1000 && rate_in <= 384000, "%s: rate_in=%d outside [1000, 384000]", who, rate_in);
+  M3_REQUIRE(rate_out >= 1000 && rate_out <= 384000, "%s: rate_out=%d outside [1000, 384000]", who, rate_out);
+  return 0;
+}
+size_t m3_resample_tables_bytes(int rate_in, int rate_out) { return resample_tables_bytes(rate_in, rate_out); }
+int m3_resample_tables_host(int rate_in, int rate_out, void* host_tables) {
+  M3_REQUIRE(host_tables != nullptr, "resample_tables_host: null pointer");
+  return resample_tables_build(rate_in, rate_out, host_tables);
+}
+int m3_resample_tables_init(int rate_in, int rate_out, void* tables, m3_stream stream) {
+  M3_REQUIRE(tables != nullptr && aligned16(tables), "resample_tables_init: tables must be non-null and 16-byte aligned");
+  const size_t bytes = resample_tables_bytes(rate_in, rate_out);
+  if (bytes == 0) return -2;
+  std::vector<char> image(bytes);
+  if (int rc = resample_tables_build(rate_in, rate_out, image.data())) return rc;
+  M3_CHECK_HIP(hipMemcpyAsync(tables, image.data(), image.size(), hipMemcpyHostToDevice, (hipStream_t)stream));
+  M3_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));     // the host image dies with this call
+  return 0;
+}
+int64_t m3_resample_num_samples(int rate_in, int rate_out, int64_t n_in, int flush) {
+  if (resample_rates_ok("resample_num_samples", rate_in, rate_out)) return -1;
+  return resample_num_samples(rate_in, rate_out, n_in, flush);
+}
+int m3_resample_input_span(int rate_in, int rate_out, int64_t out0, int64_t n_out, int64_t* first_in, int64_t* end_in) {
+  M3_REQUIRE(first_in && end_in, "resample_input_span: null pointer");
+  if (int rc = resample_rates_ok("resample_input_span", rate_in, rate_out)) return rc;
+  M3_REQUIRE(out0 >= 0, "resample_input_span: out0=%lld is negative", (long long)out0);
+  long f = 0, e = 0;
+  resample_input_span(rate_in, rate_out, out0, n_out, &f, &e);
+  *first_in = f;
+  *end_in = e;
+  return 0;
+}
+int m3_resample(const void* tables, const void* pcm, int pcm_is_int16, int channels, int channel, int ld_pcm, const int64_t* in0,
+                const int32_t* n_in, const int64_t* out0, const int32_t* n_out, int B, int N_out, float* out, int ld_out,
+                m3_stream stream) {
+  M3_REQUIRE(tables && pcm && in0 && n_in && out0 && n_out && out, "resample: null pointer");
+  M3_REQUIRE(channels >= 1 && channels <= 8, "resample: channels=%d outside [1, 8]", channels);
+  M3_REQUIRE(channel >= -1 && channel < channels, "resample: channel=%d outside [-1, %d)", channel, channels);
+  M3_REQUIRE(B >= 0 && B <= 65535 && N_out >= 0, "resample: bad sizes B=%d N_out=%d", B, N_out);
+  M3_REQUIRE(ld_out >= N_out, "resample: ld_out=%d is shorter than a row of %d", ld_out, N_out);
+  const int per16 = pcm_is_int16 ? 8 : 4;
+  M3_REQUIRE(ld_pcm >= 0 && ld_pcm % per16 == 0, "resample: ld_pcm=%d must be a multiple of %d samples (16 bytes)", ld_pcm, per16);
+  M3_REQUIRE(aligned16(tables) && aligned16(pcm) && aligned16(out), "resample: tables / pcm / out must be 16-byte aligned");
+  return launch_resample(tables, pcm, pcm_is_int16, channels, channel, ld_pcm, in0, n_in, out0, n_out, B, N_out, out, ld_out,
+                         (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -589,4 +589,13 @@ int fbank_tables_build(int num_mel_bins, double sample_rate, double low_freq, do
 int launch_fbank(const void* tables, const void* pcm, int pcm_is_int16, int ld_pcm, const int32_t* n_samples, int B, int T,
                  int num_mel_bins, float* feat, int ld_feat, int32_t* feat_len, hipStream_t stream);
 
+// resample.hip: Kaldi LinearResample, samples at any rate -> samples at the feature rate
+size_t resample_tables_bytes(int rate_in, int rate_out);                  // 0 (and the error string) when the pair is refused
+int resample_tables_build(int rate_in, int rate_out, void* host_image);
+long resample_num_samples(int rate_in, int rate_out, long n_in, int flush);
+void resample_input_span(int rate_in, int rate_out, long out0, long n_out, long* first_in, long* end_in);
+int launch_resample(const void* tables, const void* pcm, int pcm_is_int16, int channels, int channel, int ld_pcm,
+                    const int64_t* in0, const int32_t* n_in, const int64_t* out0, const int32_t* n_out, int B, int N_out,
+                    float* out, int ld_out, hipStream_t stream);
+
 }  // namespace m3

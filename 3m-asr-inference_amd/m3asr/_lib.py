@@ -287,6 +287,12 @@ SIGNATURES = {
     "m3_fbank_tables_init": (_i, [_i, _f, _f, _f, _vp, _vp]),
     "m3_fbank_num_frames": (_i, [_i]),
     "m3_fbank": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "m3_resample_tables_bytes": (_sz, [_i, _i]),
+    "m3_resample_tables_host": (_i, [_i, _i, _vp]),
+    "m3_resample_tables_init": (_i, [_i, _i, _vp, _vp]),
+    "m3_resample_num_samples": (_i64, [_i, _i, _i64, _i]),
+    "m3_resample_input_span": (_i, [_i, _i, _i64, _i64, _P(_i64), _P(_i64)]),
+    "m3_resample": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp]),
     "m3_aed_embed": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "m3_aed_attention": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp]),
     "m3_aed_score": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -188,17 +188,24 @@ class Engine:
         self.stream.synchronize()
         return out
 
-    def infer_audio(self, pcm, n_samples=None):
+    def infer_audio(self, pcm, n_samples=None, sample_rate=16000, channels=1, channel=-1):
         """infer() from samples: pcm (B, N) or (N,) 16 kHz mono, int16 or float32 in the int16 value range, n_samples (B,) real
         samples per row (default N).  The log-Mel front end (m3asr.frontend.Fbank for cfg.input_dim, one launch on the engine
         stream) writes the (B, T = num_frames(N)) shape's static input buffers directly, then that shape's graph is replayed
-        exactly as infer() does after its copy.  Returns the shape's logits buffer, valid until the next call of that shape."""
+        exactly as infer() does after its copy.  Returns the shape's logits buffer, valid until the next call of that shape.
+        With another sample_rate, or channels > 1 (pcm (B, N, channels) or interleaved (B, N * channels); channel = -1: the
+        mean of all, k: channel k alone; n_samples per channel), one launch of m3asr.frontend.Resampler (Kaldi's
+        LinearResample, cached per (sample_rate, channels, channel)) on the engine stream first writes the 16 kHz mono
+        samples into a float32 staging tensor, which the front end then reads; T = num_frames(num_resampled(N))."""
         from .frontend import Fbank, num_frames
         if getattr(self, "_fbank", None) is None:
             self._fbank = Fbank(self.cfg.input_dim, self.device)
         pcm = torch.as_tensor(pcm)
         pcm = pcm.unsqueeze(0) if pcm.dim() == 1 else pcm
-        B, T = int(pcm.shape[0]), num_frames(pcm.shape[1])
+        N = int(pcm.shape[1])
+        if (int(sample_rate), int(channels), int(channel)) != (16000, 1, -1):
+            pcm, n_samples, N = self._resampled(pcm, n_samples, int(sample_rate), int(channels), int(channel))
+        B, T = int(pcm.shape[0]), num_frames(N)
         f, l, out = self._lru(self._static, (B, T), lambda: (
             torch.empty(B, T, self.cfg.input_dim, dtype=torch.float32, device=self.device),
             torch.empty(1, B, dtype=torch.int32, device=self.device),
@@ -207,6 +214,22 @@ class Engine:
         self.forward(f, l, out, use_graph=True)
         self.stream.synchronize()
         return out
+
+    def _resampled(self, pcm, n_samples, rate, channels, channel):
+        """infer_audio at another rate / channel count: one resampler launch on the engine stream into a float32 staging
+        tensor whose rows are whole 16 bytes (the front end reads it in place).
+        -> (staging (B, ld), n_out (B,) int32 device, N_out = num_resampled(N))"""
+        from .frontend import Resampler
+        cache = self.__dict__.setdefault("_resamplers", {})
+        key = (rate, channels, channel)
+        if key not in cache:
+            cache[key] = Resampler(rate, self.device, channels=channels, channel=channel)
+        rs = cache[key]
+        N = int(pcm.shape[1]) if pcm.dim() == 3 else int(pcm.shape[1]) // channels
+        N_out = rs.num_samples(N)
+        stage = torch.empty(int(pcm.shape[0]), max(-(-N_out // 4) * 4, 4), dtype=torch.float32, device=self.device)
+        _, n_out = rs(pcm, n_samples, out=stage, stream=self.stream)
+        return stage, n_out, N_out
 
     def num_captures(self):
         return self.lib.m3_engine_num_captures(self.handle)

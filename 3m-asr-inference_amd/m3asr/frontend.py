@@ -130,12 +130,242 @@ class Fbank:
         return out, out_len
 
 
+def _check_rates(rate_in, rate_out):
+    lib = _lib.load()
+    if lib.m3_resample_tables_bytes(int(rate_in), int(rate_out)) == 0:
+        raise _lib.M3Error("m3_resample_tables_bytes failed: " + _lib.last_error())
+    return lib
+
+
+def num_resampled(n, rate_in, rate_out=SAMPLE_RATE, flush=True):
+    """Samples at rate_out that n samples at rate_in give (m3_resample_num_samples).  flush=False: those that can be computed
+    now, while more input may come -- none of them reads a sample at or beyond n; flush=True: the stream has ended."""
+    got = _lib.load().m3_resample_num_samples(int(rate_in), int(rate_out), int(n), int(bool(flush)))
+    if got < 0:
+        raise _lib.M3Error("m3_resample_num_samples failed: " + _lib.last_error())
+    return int(got)
+
+
+def resample_span(out0, n_out, rate_in, rate_out=SAMPLE_RATE):
+    """[first_in, end_in): the absolute input samples that outputs [out0, out0 + n_out) read; first_in may be negative."""
+    f, e = C.c_int64(0), C.c_int64(0)
+    check(_lib.load().m3_resample_input_span(int(rate_in), int(rate_out), int(out0), int(n_out), C.byref(f), C.byref(e)),
+          "m3_resample_input_span")
+    return int(f.value), int(e.value)
+
+
+def resample_tables(rate_in, rate_out=SAMPLE_RATE):
+    """The resampler's tables as the library builds them (float64 on the host, every weight rounded once to float32), without
+    a GPU: dict(first (phases,) int32, n (phases,) int32, weights (phases, max_taps) float32 with zeros behind n[p], in_unit,
+    out_unit, image = the raw table image (uint8) that is uploaded)."""
+    lib = _check_rates(rate_in, rate_out)
+    image = np.zeros(lib.m3_resample_tables_bytes(int(rate_in), int(rate_out)), dtype=np.uint8)
+    check(lib.m3_resample_tables_host(int(rate_in), int(rate_out), image.ctypes.data_as(C.c_void_p)), "m3_resample_tables_host")
+    i32, f32 = image.view(np.int32), image.view(np.float32)
+    assert (int(i32[0]), int(i32[1])) == (int(rate_in), int(rate_out))
+    in_unit, out_unit, max_taps, w_off = (int(v) for v in i32[2:6])
+    first, n = i32[8:8 + out_unit].copy(), i32[8 + out_unit:8 + 2 * out_unit].copy()
+    weights = f32[w_off:w_off + max_taps * out_unit].reshape(max_taps, out_unit).T.copy()
+    return dict(first=first, n=n, weights=weights, in_unit=in_unit, out_unit=out_unit, image=image)
+
+
+class Resampler:
+    """Kaldi's LinearResample on one device (m3_resample* in include/m3asr.h): owns the uploaded table of one
+    rate pair; every call is one kernel launch.  channels: interleaved channels per sample of the input; channel: -1 = the
+    mean of all channels, k = channel k alone."""
+
+    def __init__(self, rate_in, device="cuda:0", rate_out=SAMPLE_RATE, channels=1, channel=-1):
+        self.lib = _check_rates(rate_in, rate_out)
+        self.rate_in, self.rate_out = int(rate_in), int(rate_out)
+        self.channels, self.channel = int(channels), int(channel)
+        if not 1 <= self.channels <= 8:
+            raise ValueError("Resampler: channels=%d outside [1, 8]" % self.channels)
+        if not -1 <= self.channel < self.channels:
+            raise ValueError("Resampler: channel=%d outside [-1, %d)" % (self.channel, self.channels))
+        self.device = torch.device(device)
+        g = int(np.gcd(self.rate_in, self.rate_out))
+        self.in_unit, self.out_unit = self.rate_in // g, self.rate_out // g
+        nbytes = self.lib.m3_resample_tables_bytes(self.rate_in, self.rate_out)
+        with torch.cuda.device(self.device):
+            self.tables = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            st = torch.cuda.current_stream()
+            check(self.lib.m3_resample_tables_init(self.rate_in, self.rate_out, self.tables.data_ptr(), C.c_void_p(st.cuda_stream)),
+                  "m3_resample_tables_init")
+
+    def num_samples(self, n, flush=True):
+        return num_resampled(n, self.rate_in, self.rate_out, flush)
+
+    def _device_pcm(self, pcm):
+        """pcm as a (B, ld) int16 / float32 device tensor of interleaved channels that the kernel can read with 16-byte loads,
+        and its samples per channel N (the staging rule of Fbank._device_pcm)."""
+        pcm = torch.as_tensor(pcm)
+        if pcm.dim() == 1:
+            pcm = pcm.unsqueeze(0)
+        if pcm.dim() == 3:
+            if pcm.shape[2] != self.channels:
+                raise ValueError("Resampler: pcm has %d channels, the resampler was built for %d" % (pcm.shape[2], self.channels))
+            if pcm.stride(2) != 1 or pcm.stride(1) != self.channels:
+                pcm = pcm.contiguous()
+            pcm = pcm.as_strided((pcm.shape[0], pcm.shape[1] * self.channels), (pcm.stride(0), 1))
+        if pcm.dim() != 2 or pcm.shape[1] % self.channels:
+            raise ValueError("Resampler: pcm must be (B, N * %d), (B, N, %d) or (N,), got %s" % (
+                self.channels, self.channels, tuple(pcm.shape)))
+        if pcm.dtype != torch.int16:
+            pcm = pcm.to(torch.float32)
+        B, W = int(pcm.shape[0]), int(pcm.shape[1])
+        per16 = 16 // pcm.element_size()
+        if pcm.device == self.device and W % per16 == 0 and pcm.stride(1) == 1 and pcm.stride(0) % per16 == 0 and \
+                pcm.stride(0) >= W and pcm.data_ptr() % 16 == 0:
+            return pcm, W // self.channels
+        ld = max(-(-W // per16) * per16, per16)
+        dev = torch.empty(B, ld, dtype=pcm.dtype, device=self.device)
+        dev[:, :W].copy_(pcm, non_blocking=True)
+        return dev, W // self.channels
+
+    def launch(self, pcm, in0, n_in, out0, n_out, out, stream=None):
+        """The launch itself, for the streaming path: pcm (B, ld) int16 / float32 DEVICE tensor of interleaved channels (16-byte
+        aligned rows), in0 / out0 (B,) int64 and n_in / n_out (B,) int32 device vectors (the m3_resample block of
+        include/m3asr.h), out (B, N_out) float32 device tensor with unit column stride.  -> out"""
+        with torch.cuda.device(self.device), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            st = torch.cuda.current_stream()
+            B = int(pcm.shape[0])
+            if pcm.dim() != 2 or pcm.device != self.device or pcm.dtype not in (torch.int16, torch.float32) or pcm.stride(1) != 1:
+                raise ValueError("Resampler.launch: pcm must be a (B, ld) int16 / float32 device tensor with dense rows")
+            if out.dim() != 2 or out.shape[0] != B or out.dtype != torch.float32 or out.device != self.device or out.stride(1) != 1:
+                raise ValueError("Resampler.launch: out must be a (B, N_out) float32 device tensor with dense rows")
+            for name, v, dt in (("in0", in0, torch.int64), ("n_in", n_in, torch.int32), ("out0", out0, torch.int64),
+                                ("n_out", n_out, torch.int32)):
+                if v.dtype != dt or v.device != self.device or v.numel() != B or not v.is_contiguous():
+                    raise ValueError("Resampler.launch: %s must be a contiguous %s device tensor of %d entries" % (name, dt, B))
+            if B == 0 or out.shape[1] == 0:
+                return out
+            check(self.lib.m3_resample(self.tables.data_ptr(), pcm.data_ptr(), int(pcm.dtype == torch.int16), self.channels,
+                                       self.channel, int(pcm.stride(0)), in0.data_ptr(), n_in.data_ptr(), out0.data_ptr(),
+                                       n_out.data_ptr(), B, int(out.shape[1]), out.data_ptr(), int(out.stride(0)),
+                                       C.c_void_p(st.cuda_stream)), "m3_resample")
+        return out
+
+    def __call__(self, pcm, n_samples=None, out=None, stream=None):
+        """The offline resample, one launch: pcm (B, N), (N,) or (B, N, channels) (interleaved: (B, N * channels)), int16 or
+        float32, tensor or array on any device; n_samples (B,) real samples per channel and row (default N).  The signal is
+        flushed: its future is zeros.  out: destination (B, N_out) float32 on the device (default a new
+        (B, num_samples(N)) tensor); columns behind a row's count are written as zeros.
+        -> (out, n_out (B,) int32 on the device)"""
+        with torch.cuda.device(self.device), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            dev, N = self._device_pcm(pcm)
+            B = int(dev.shape[0])
+            if n_samples is None:
+                n_in = torch.full((B,), N, dtype=torch.int32, device=self.device)
+            else:
+                n_in = torch.as_tensor(n_samples).reshape(-1).to(self.device, torch.int32, non_blocking=True).clamp(min=0, max=N)
+                if n_in.numel() != B:
+                    raise ValueError("Resampler: n_samples has %d entries for %d rows" % (n_in.numel(), B))
+            if out is None:
+                out = torch.empty(B, self.num_samples(N), dtype=torch.float32, device=self.device)
+            if self.rate_in == self.rate_out:
+                n_out = n_in.clone()
+            else:                                      # the flushed count: ceil(n * out_unit / in_unit)
+                n_out = ((n_in.to(torch.int64) * self.out_unit + (self.in_unit - 1)) // self.in_unit).to(torch.int32)
+            n_out = n_out.clamp(max=int(out.shape[1])) if out.dim() == 2 else n_out
+            zero = torch.zeros(B, dtype=torch.int64, device=self.device)
+            self.launch(dev, zero, n_in, zero, n_out, out, stream=torch.cuda.current_stream())
+        return out, n_out
+
+
+class ResampledWindowBuffer:
+    """AudioWindowBuffer for a stream at another rate or with several channels: what AudioWindowBuffer(chunk, dtype,
+    sample_rate, channels) returns unless both have their defaults.  It buffers INPUT-rate interleaved samples and keeps
+    absolute clocks: the 16 kHz signal is resample(whole session) (m3_resample's contract makes a sample depend on its
+    absolute index only), window n of the open segment holds its samples [origin + hop n, origin + hop n + window), and take()
+    hands back the input samples that window reads together with the four index entries of its row of the launch."""
+
+    def __init__(self, chunk, dtype=torch.int16, sample_rate=SAMPLE_RATE, channels=1):
+        self.c = int(chunk)
+        self.hop = FRAME_SHIFT * 4 * self.c
+        self.window = (4 * self.c + 2) * FRAME_SHIFT + FRAME_LENGTH
+        self.dtype = dtype
+        self.rate, self.channels = int(sample_rate), int(channels)
+        _check_rates(self.rate, SAMPLE_RATE)
+        if not 1 <= self.channels <= 8:
+            raise ValueError("AudioWindowBuffer: channels=%d outside [1, 8]" % self.channels)
+        lo, hi = resample_span(0, self.window, self.rate)
+        self.span = hi - lo + 1                        # input samples a window reads, at any phase of its first output
+        self.buf = torch.zeros(0, self.channels, dtype=dtype)   # input samples from absolute input sample self.base on
+        self.base = 0
+        self.total = 0                                 # input samples per channel received since the session began
+        self.origin = 0                                # absolute 16 kHz sample at which the open segment starts
+        self.chunks = 0
+        self.ended = False
+
+    def push(self, pcm):
+        """(n, channels) or interleaved (n * channels,) samples at the input rate: int16, or float32 in the int16 value range
+        (rounded to the nearest int16 when the buffer holds int16)."""
+        if self.ended:
+            raise ValueError("push after end")
+        pcm = torch.as_tensor(pcm).cpu()
+        if pcm.numel() % self.channels:
+            raise ValueError("push: %d values are no whole samples of %d channels" % (pcm.numel(), self.channels))
+        pcm = pcm.reshape(-1, self.channels)
+        if pcm.dtype.is_floating_point and not self.dtype.is_floating_point:
+            pcm = pcm.round().clamp(-32768, 32767)
+        self.buf = torch.cat([self.buf, pcm.to(self.dtype)])
+        self.total += int(pcm.shape[0])
+
+    def end(self):
+        self.ended = True
+
+    def rebase(self):
+        """Start the next segment at the next window.  Only the 16 kHz origin moves: the sample clocks run on and nothing is
+        zeroed at the cut, so the next segment's samples are exactly resample(whole session)[origin:].  `ended` stays."""
+        self.origin += self.hop * self.chunks
+        self.chunks = 0
+
+    def _available(self):
+        """16 kHz samples of the open segment that can be computed now"""
+        return max(num_resampled(self.total, self.rate, SAMPLE_RATE, flush=self.ended) - self.origin, 0)
+
+    def ready(self):
+        """Real FRAMES of the next window if it can run now, else 0 (serve.next_window_valid on the frames of the resampled
+        samples there are)."""
+        return next_window_valid(num_frames(self._available()), self.chunks, self.c, self.ended)
+
+    def drained(self):
+        return self.ended and self.ready() == 0
+
+    def take(self, out=None):
+        """The next window as (input samples (span, channels) zero filled behind the real ones, in0, n_in, out0, n_out): the
+        row's entries of the resampler launch that produces the window's n_out real 16 kHz samples; advances by one chunk.
+        num_frames(n_out) is what ready() returned.  out: a (span * channels,) or (span, channels) destination."""
+        if self.ready() == 0:
+            raise ValueError("no window ready")
+        out0 = self.origin + self.hop * self.chunks
+        n_out = min(self._available() - self.hop * self.chunks, self.window)
+        lo, hi = resample_span(out0, n_out, self.rate)
+        in0, end = max(lo, self.base), min(hi, self.total)
+        n_in = max(end - in0, 0)
+        win = torch.zeros(self.span, self.channels, dtype=self.dtype) if out is None else out
+        win.zero_()
+        win.view(-1, self.channels)[:n_in] = self.buf[in0 - self.base:in0 - self.base + n_in]
+        self.chunks += 1
+        drop = resample_span(out0 + self.hop, 1, self.rate)[0] - self.base   # input left of the next window is never read again
+        if drop > 0:
+            self.buf = self.buf[min(drop, self.buf.shape[0]):]
+            self.base += drop
+        return win, in0, n_in, out0, n_out
+
+
 class AudioWindowBuffer:
     """Samples of one stream, pushed in arbitrary pieces, handed back as the sample windows of chunked decoding: the
     sample-domain twin of serve.WindowBuffer.  Window n starts at sample 160 * 4 c n and holds the (4 c + 2) * 160 + 400
-    samples of feature frames [4 c n, 4 c n + 4 c + 3)."""
+    samples of feature frames [4 c n, 4 c n + 4 c + 3).  With another sample_rate or channels > 1 the constructor hands out
+    a ResampledWindowBuffer instead, which keeps the input-rate samples."""
 
-    def __init__(self, chunk, dtype=torch.int16):
+    def __new__(cls, chunk, dtype=torch.int16, sample_rate=SAMPLE_RATE, channels=1):
+        if cls is AudioWindowBuffer and (int(sample_rate) != SAMPLE_RATE or int(channels) != 1):
+            return ResampledWindowBuffer(chunk, dtype, sample_rate, channels)
+        return super().__new__(cls)
+
+    def __init__(self, chunk, dtype=torch.int16, sample_rate=SAMPLE_RATE, channels=1):
         self.c = int(chunk)
         self.hop = FRAME_SHIFT * 4 * self.c
         self.window = (4 * self.c + 2) * FRAME_SHIFT + FRAME_LENGTH

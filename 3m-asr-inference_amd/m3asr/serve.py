@@ -18,6 +18,10 @@ float32 in the int16 range).  step() gathers the live slots' sample windows into
 runs the log-Mel front end (m3asr.frontend.Fbank, one launch on the engine stream) straight into the encoder's window
 buffer; the chunk itself is the same graph replay as in feature mode.
 
+Audio at another rate or with several channels, `StreamPool(decoder, audio=True, sample_rate=44100, channels=2)`: the
+sessions push interleaved samples in that format and step() resamples on the device (m3asr.frontend.Resampler, Kaldi's
+LinearResample, one more launch) before the front end; a session's 16 kHz samples do not depend on how it was cut.
+
 Segmenting, `StreamPool(decoder, segment=True)` over a decoder with an endpoint config
 (StreamingCtcDecoder(..., endpoint=EndpointConfig())): after every step() the pool asks the device-side endpoint detector
 which live sessions' utterances are over, files each one's n-best as a `Segment` (`pool.segments(sid)`) and restarts the
@@ -137,7 +141,10 @@ class StreamPool:
     (B,))`, `reset(slots=[...])`, `partial(slots=[...])`, `finish(slots=[...])`; B, chunk and input_dim are read from
     `decoder.st` unless given.  audio=True: the sessions are fed samples (push_audio) and step() featurises them on the device;
     fbank: the front end, `fbank(pcm (B, n) int16, n_samples (B,), out=, out_len=, stream=)` (default: an
-    m3asr.frontend.Fbank for input_dim on the engine's device).
+    m3asr.frontend.Fbank for input_dim on the engine's device).  sample_rate / channels / channel (audio=True): what the
+    sessions push, one format per pool; unless they are 16000 / 1 / -1 every step() first runs ONE launch of `resampler`
+    (default: an m3asr.frontend.Resampler for them on the engine's device; channel = -1: the mean of all channels, k: channel
+    k alone) that turns the live slots' input spans into their 16 kHz float32 windows on the device, which the front end reads.
 
     segment=True: continuous decoding.  The decoder needs an endpoint config (`decoder.endpoint`, an
     m3asr.decode.EndpointConfig, and `decoder.endpoints(slots=[...])`).  After the engine call of a step() the pool reads the
@@ -161,7 +168,7 @@ class StreamPool:
     TimedSegments; close(sid, timed=True) aligns the open segment."""
 
     def __init__(self, decoder, B=None, chunk=None, input_dim=None, audio=False, fbank=None, segment=False, max_frames=None,
-                 rescore=False, timestamps=False):
+                 rescore=False, timestamps=False, sample_rate=16000, channels=1, channel=-1, resampler=None):
         self.dec = decoder
         self.rescore = bool(rescore)
         self.timestamps = bool(timestamps)
@@ -201,8 +208,37 @@ class StreamPool:
             self.offset = {}                     # sid -> output frames of the session before its open segment
             self.finished = {}                   # sid -> [Segment] not handed out yet
         self.audio = bool(audio)
+        self.sample_rate, self.channels, self.channel = int(sample_rate), int(channels), int(channel)
+        self.resampled = self.audio and (self.sample_rate, self.channels, self.channel) != (16000, 1, -1)
+        if not self.audio and (self.sample_rate, self.channels, self.channel) != (16000, 1, -1):
+            raise ValueError("StreamPool: sample_rate / channels / channel belong to a pool fed samples (audio=True)")
         if self.audio:
             self._init_audio(st, fbank)
+        if self.resampled:
+            self._init_resampler(st, resampler)
+
+    def _init_resampler(self, st, resampler):
+        """The buffers of a pool whose sessions push samples at another rate or with several channels: per slot the input
+        span of a window (pinned, then device) and ONE index block (in0, out0 int64; n_in, n_out int32) that goes up in one
+        copy; the resampler writes the 16 kHz windows as float32 into res_dev, which the front end reads."""
+        from .frontend import AudioWindowBuffer, Resampler
+        self._new_audio_buffer = lambda: AudioWindowBuffer(self.c, sample_rate=self.sample_rate, channels=self.channels)
+        eng = getattr(st, "eng", None)
+        dev = eng.device if eng is not None else torch.device("cpu")
+        pin = dev.type == "cuda"
+        self.resampler = resampler if resampler is not None else Resampler(self.sample_rate, dev, channels=self.channels,
+                                                                           channel=self.channel)
+        B, width = self.B, -(-self._new_audio_buffer().span * self.channels // 8) * 8
+        self.span_win = torch.zeros(B, width, dtype=torch.int16, pin_memory=pin)
+        self.span_dev = torch.zeros(B, width, dtype=torch.int16, device=dev)
+        self.idx = torch.zeros(3 * B, dtype=torch.int64, pin_memory=pin)         # in0 | out0 | n_in, n_out (int32 pairs)
+        self.idx_dev = torch.zeros(3 * B, dtype=torch.int64, device=dev)
+        self.res_dev = torch.zeros(B, self.window_samples, dtype=torch.float32, device=dev)
+
+    def _index_views(self, idx):
+        B = self.B
+        n = idx[2 * B:].view(torch.int32)
+        return idx[:B], n[:B], idx[B:2 * B], n[B:]
 
     def _init_audio(self, st, fbank):
         from .frontend import AudioWindowBuffer, Fbank
@@ -265,7 +301,10 @@ class StreamPool:
         self._get(sid)[1].push(frames)
 
     def push_audio(self, sid, pcm):
-        """Samples of the stream (16 kHz mono, int16 or float32 in the int16 value range), any number."""
+        """Samples of the stream, any number: int16 or float32 in the int16 value range, at the POOL's sample_rate (16 kHz unless
+        the pool was built with another) and with the pool's channels, (n, channels) or interleaved (n * channels,); mono
+        pools take (n,).  A pool at another rate or with several channels resamples on the device (Kaldi's LinearResample,
+        DESIGN.md 31), so the session's 16 kHz samples are those of the whole session resampled at once, however it is cut."""
         if not self.audio:
             raise ValueError("StreamPool.push_audio: this pool is fed feature frames, build it with audio=True")
         self._get(sid)[1].push(pcm)
@@ -352,6 +391,8 @@ class StreamPool:
     def _step_audio(self):
         """step() of a pool fed samples: one small int16 upload, one front-end launch into the encoder's window buffer, then
         the chunk.  An idle slot has 0 samples: its rows of the window buffer are zeroed and its `valid` is 0."""
+        if self.resampled:
+            return self._step_resampled()
         if self.uploaded is not None:
             self.uploaded.synchronize()
         valid = torch.zeros(self.B, dtype=torch.int32)
@@ -375,6 +416,43 @@ class StreamPool:
             self.pcm_dev.copy_(self.pcm_win)
             self.n_real_dev.copy_(self.n_real)
         self.fbank(self.pcm_dev, self.n_real_dev, out=self.feat, out_len=self.feat_len_dev, stream=self.stream)
+        self.dec.step(self.feat, valid)
+        self.steps += 1
+        if self.segment:
+            self._cut(live)
+        return live
+
+    def _step_resampled(self):
+        """step() of a pool fed samples at another rate: the live slots' input spans and the index block go up, ONE resampler
+        launch writes every slot's 16 kHz window (an idle slot has n_out = 0: zeros), then the front end and the chunk run
+        as in _step_audio.  One launch more per step, no host round trip."""
+        from .frontend import num_frames
+        if self.uploaded is not None:
+            self.uploaded.synchronize()
+        valid = torch.zeros(self.B, dtype=torch.int32)
+        self.idx.zero_()
+        in0, n_in, out0, n_out = self._index_views(self.idx)
+        live = []
+        for sid, (b, ab) in self.streams.items():
+            v = ab.ready()
+            if v > 0:
+                _, in0[b], n_in[b], out0[b], n_out[b] = ab.take(out=self.span_win[b, :ab.span * self.channels])
+                assert num_frames(int(n_out[b])) == v
+                valid[b] = v
+                live.append(sid)
+        if not live:
+            return live
+        if self.stream is not None:
+            with torch.cuda.stream(self.stream):
+                self.span_dev.copy_(self.span_win, non_blocking=True)
+                self.idx_dev.copy_(self.idx, non_blocking=True)
+                self.uploaded.record(self.stream)
+        else:
+            self.span_dev.copy_(self.span_win)
+            self.idx_dev.copy_(self.idx)
+        d_in0, d_n_in, d_out0, d_n_out = self._index_views(self.idx_dev)
+        self.resampler.launch(self.span_dev, d_in0, d_n_in, d_out0, d_n_out, self.res_dev, stream=self.stream)
+        self.fbank(self.res_dev, d_n_out, out=self.feat, out_len=self.feat_len_dev, stream=self.stream)
         self.dec.step(self.feat, valid)
         self.steps += 1
         if self.segment:

@@ -956,6 +956,51 @@ int m3_fbank_num_frames(int n_samples);
 int m3_fbank(const void* tables, const void* pcm, int pcm_is_int16, int ld_pcm, const int32_t* n_samples, int B, int T,
              int num_mel_bins, float* feat, int ld_feat, int32_t* feat_len_out, m3_stream stream);
 
+/* Audio in at any sample rate: Kaldi's LinearResample on the device (csrc/resample.hip) -- what
+ * compute-fbank-feats does (ResampleWaveform) when a wave's rate is not the feature rate.  With ri = rate_in, ro = rate_out,
+ * g = gcd(ri, ro), in_unit = ri / g, out_unit = ro / g, cutoff = 0.99 * 0.5 * min(ri, ro), Z = 6, ww = Z / (2 cutoff): output o
+ * has phase p = o % out_unit and unit u = o / out_unit and is
+ *     y[o] = sum_{j < n[p]} w[p][j] * x[first[p] + u * in_unit + j],         x = 0 outside the signal,
+ * with, for t = p / ro: first[p] = ceil((t - ww) ri), n[p] = floor((t + ww) ri) - first[p] + 1,
+ * w[p][j] = window(dt) filt(dt) / ri at dt = (first[p] + j) / ri - t, window(dt) = 0.5 (1 + cos(2 pi cutoff / Z dt)) for
+ * |dt| < ww, else 0, filt(dt) = sin(2 pi cutoff dt) / (pi dt), 2 cutoff at dt = 0.  Two deliberate departures: ri == ro is the
+ * IDENTITY (one phase, one tap of 1.0; the feature pipeline does not resample then), and interleaved channels are reduced on
+ * the way in: the mono sample is (x_0 + ... + x_{C-1}) / (float)C, summed in fp32 in channel order, or channel k alone.
+ * Arithmetic: the tables are built on the HOST in float64 and every weight is rounded once to float32; an output is one fp32
+ * accumulator from 0, its taps in ascending j, multiply then add (never fused); it is float32, neither rounded nor clamped to
+ * int16 (m3_fbank reads it as it is).  An output's bits depend on its absolute index o, its tap inputs and the table only:
+ * not on B, the row, where a launch's window starts, or on int16 against float32 input.  So a stream resampled piece by
+ * piece equals the whole resampled at once.
+ * m3_resample_tables_bytes: size of the table image, host-only; 0 (and m3_last_error) when the pair is refused: a rate outside
+ *   [1000, 384000], more than 512 taps per output (max_taps), or more than 2^20 weights (out_unit * max_taps).
+ * m3_resample_tables_host: builds the image into HOST memory of that size (host-only, needs no device).  Image: int32
+ *   rate_in, rate_out, in_unit, out_unit, max_taps, w_offset (of the weights, in 4-byte words), 2 reserved; int32
+ *   first[out_unit], n[out_unit], padded to 16 bytes; float w[max_taps][out_unit] (phase-minor, zero where j >= n[p]).
+ * m3_resample_tables_init: builds the same image and uploads it to DEVICE memory `tables` (16-byte aligned) on `stream`; the
+ *   upload has finished when the call returns.
+ * m3_resample_num_samples: outputs that n_in input samples admit (host-only; -1 on bad rates).  tick = lcm(ri, ro),
+ *   L = n_in * (tick / ri), without flush L -= floor(ww * tick); 0 if L <= 0, else last = L / (tick / ro), one less if that
+ *   divides exactly, count = last + 1.  flush != 0: the stream has ended and the missing future is zeros.  Without flush no
+ *   admitted output reads an input at or beyond n_in.  ri == ro: n_in.
+ * m3_resample_input_span: the half-open range [first_in, end_in) of absolute input indices that outputs
+ *   [out0, out0 + n_out) read (host-only); first_in may be negative; empty (end_in = first_in) for n_out <= 0.
+ * m3_resample: ONE launch resamples a ragged batch.  pcm (B, ld_pcm) int16 (pcm_is_int16 != 0) or float32, `channels` in
+ *   [1, 8] interleaved, 16-byte aligned with a row stride of whole 16 bytes (ld_pcm, in elements, a multiple of 8 / 4);
+ *   channel = -1: the mean of all channels, k in [0, channels): channel k alone.  Per row b (device vectors): in0[b] int64 =
+ *   absolute index of the row's first input sample, n_in[b] int32 = samples per channel in the row, clamped to
+ *   [0, ld_pcm / channels]; input outside [in0, in0 + n_in) reads as 0; out0[b] int64 >= 0 = absolute index of the first
+ *   output, n_out[b] int32 = outputs wanted, clamped to [0, N_out].  out (B, ld_out) float32, 16-byte aligned, ld_out >= N_out:
+ *   out[b][i] = y[out0[b] + i] for i < n_out[b], columns n_out[b] <= i < N_out are written as ZEROS, columns >= N_out are not
+ *   touched.  All index arithmetic on absolute positions is 64-bit. */
+size_t m3_resample_tables_bytes(int rate_in, int rate_out);
+int m3_resample_tables_host(int rate_in, int rate_out, void* host_tables);
+int m3_resample_tables_init(int rate_in, int rate_out, void* tables, m3_stream stream);
+int64_t m3_resample_num_samples(int rate_in, int rate_out, int64_t n_in, int flush);
+int m3_resample_input_span(int rate_in, int rate_out, int64_t out0, int64_t n_out, int64_t* first_in, int64_t* end_in);
+int m3_resample(const void* tables, const void* pcm, int pcm_is_int16, int channels, int channel, int ld_pcm, const int64_t* in0,
+                const int32_t* n_in, const int64_t* out0, const int32_t* n_out, int B, int N_out, float* out, int ld_out,
+                m3_stream stream);
+
 /* Attention rescoring: the AED decoder's second pass over the CTC n-best (csrc/aed_rescore.hip).  The decoder
  * runs teacher-forced on PACKED hypothesis rows: hypothesis slot h = b * beam + i owns rows [hyp_row0[h], hyp_row0[h + 1]) of
  * every row buffer, len + 1 of them for a live slot (sos, then its tokens) and none for a slot i >= n_hyps[b] (n_hyps < 0, a

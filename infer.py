@@ -5,8 +5,10 @@
     python3 infer.py -p encoder.plan -w speech.wav [-o compare.npy]
 
 feat.npy is (B,T,idim) float32; feat_len = feat.shape[1] for every utterance, as in the reference (infer.py:111-113).
-speech.wav (-w, instead of -i) is a 16 kHz mono 16-bit RIFF file; its log-Mel frames are computed on the device by the
-library's Kaldi-style front end (m3asr.frontend.Fbank with the plan's input_dim mel bins) and run as a batch of one.
+speech.wav (-w, instead of -i) is a 16-bit PCM RIFF file at any sample rate from 1 to 384 kHz with up to 8 channels; unless
+it is 16 kHz mono it is first resampled on the device as Kaldi's compute-fbank-feats would (m3asr.frontend.Resampler;
+--channel K takes channel K alone, the default is the mean of all channels).  Its log-Mel frames are computed on the device by
+the library's Kaldi-style front end (m3asr.frontend.Fbank with the plan's input_dim mel bins) and run as a batch of one.
 Prints ``time=...ms`` for one forward after a warm-up and the output's shape / sum (reference :81-103).
 
     python3 infer.py -p encoder.plan -w speech.wav --hotwords words.txt [--hotword-score 3.0] [--beam 10]
@@ -56,13 +58,33 @@ from trt_helper import trt
 
 
 def read_wav(path):
-    """16 kHz mono 16-bit PCM -> (1, N) int16"""
+    """16-bit PCM -> ((1, N, channels) int16, sample rate, channels)"""
     import wave
     with wave.open(path, "rb") as w:
-        if (w.getframerate(), w.getnchannels(), w.getsampwidth()) != (16000, 1, 2):
+        if w.getsampwidth() != 2:
             raise SystemExit("%s: need 16 kHz mono 16-bit PCM, got %d Hz, %d channel(s), %d-bit" % (
                 path, w.getframerate(), w.getnchannels(), 8 * w.getsampwidth()))
-        return np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").astype(np.int16).reshape(1, -1)
+        if not 1 <= w.getnchannels() <= 8:
+            raise SystemExit("%s: need 1 to 8 channels, got %d" % (path, w.getnchannels()))
+        pcm = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").astype(np.int16)
+        return pcm.reshape(1, -1, w.getnchannels()), w.getframerate(), w.getnchannels()
+
+
+def wav_features(path, channel, input_dim, device):
+    """The wav's log-Mel frames (1, T, input_dim), computed on the device; resampled there first unless it is 16 kHz mono."""
+    from m3asr._lib import M3Error
+    from m3asr.frontend import Fbank, Resampler
+    pcm, rate, channels = read_wav(path)
+    if not -1 <= channel < channels:
+        raise SystemExit("%s: --channel %d, the file has %d channel(s)" % (path, channel, channels))
+    fb = Fbank(input_dim, device)
+    if (rate, channels) == (16000, 1):
+        return fb(pcm[:, :, 0])[0]
+    try:
+        samples, n = Resampler(rate, device, channels=channels, channel=channel)(pcm)
+    except M3Error as e:
+        raise SystemExit("%s: %s" % (path, e))
+    return fb(samples, n)[0]
 
 
 def print_times(scores, device, mode, hyps):
@@ -194,8 +216,7 @@ def main(args):
     logger = trt_helper.init_trt_plugin(trt.Logger.INFO, "libm3asr_hip.so")
     helper = trt_helper.InferHelper(args.plan_name, logger)
     if args.wav_file:
-        from m3asr.frontend import Fbank
-        feat = Fbank(helper.cfg.input_dim, helper.engine.device)(read_wav(args.wav_file))[0].cpu().numpy()
+        feat = wav_features(args.wav_file, args.channel, helper.cfg.input_dim, helper.engine.device).cpu().numpy()
     else:
         feat = np.load(args.input_file).astype(np.float32)
     feat_len = np.full((1, feat.shape[0]), feat.shape[1], dtype=np.int32)
@@ -227,7 +248,8 @@ if __name__ == "__main__":
     p.add_argument("-p", "--plan_name", required=True, help="The plan file path.")
     src = p.add_mutually_exclusive_group(required=True)
     src.add_argument("-i", "--input_file", help="The input feat.npy file path.")
-    src.add_argument("-w", "--wav", dest="wav_file", help="A 16 kHz mono 16-bit wav file, instead of feat.npy.")
+    src.add_argument("-w", "--wav", dest="wav_file", help="A 16-bit PCM wav file (any rate, up to 8 channels), instead of feat.npy.")
+    p.add_argument("--channel", type=int, default=-1, help="-w: take this channel alone (default: the mean of all channels).")
     p.add_argument("-o", "--compare_output_file", required=False, help="The compare output .npy file path.")
     p.add_argument("--hotwords", help="Phrase list: one phrase of space-separated token ids per line.")
     p.add_argument("--hotword-score", type=float, default=3.0, help="Bonus per matched token (log domain).")

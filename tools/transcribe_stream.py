@@ -21,7 +21,9 @@ on the device and aligns a segment's final best hypothesis -- the rescored one w
 checkpoint has one); the decoder keeps every session's encoder memory on the device and the plan's attention decoder rescores
 a segment's n-best when its utterance ends (StreamPool(rescore=True)).
 
-The plan must be a streaming one (static_chunk_size > 0, causal conv modules).  speech.wav is 16 kHz mono 16-bit PCM.  The
+The plan must be a streaming one (static_chunk_size > 0, causal conv modules).  speech.wav is 16-bit PCM at any sample rate from 1 to
+384 kHz with up to 8 channels: unless it is 16 kHz mono the pool resamples it on the device (StreamPool(sample_rate=,
+channels=, channel=)); --channel K takes channel K alone, the default is the mean of all channels.  The
 last line (rule 0) is what was still open when the file ended.  --synthetic N pushes N seconds of a generated signal instead
 of a file (no plan either: a small random streaming model, with --rescore plus a small random attention decoder), to see
 the mechanics on a machine without a model."""
@@ -38,9 +40,6 @@ import torch
 from m3asr.decode import EndpointConfig, StreamingCtcDecoder
 from m3asr.serve import StreamPool
 
-PIECE = 1600          # 100 ms of samples
-
-
 def rescored(best, scores):
     """att=<a> final=<f> tokens=<ids> of the hypothesis the second pass chose (nothing decoded: the scores are missing)"""
     chosen = next((h for h in scores if tuple(h[0]) == tuple(best)), None)
@@ -50,12 +49,16 @@ def rescored(best, scores):
 
 
 def read_wav(path):
+    """16-bit PCM -> ((N, channels) int16, sample rate, channels)"""
     import wave
     with wave.open(path, "rb") as w:
-        if (w.getframerate(), w.getnchannels(), w.getsampwidth()) != (16000, 1, 2):
+        if w.getsampwidth() != 2:
             raise SystemExit("%s: need 16 kHz mono 16-bit PCM, got %d Hz, %d channel(s), %d-bit" % (
                 path, w.getframerate(), w.getnchannels(), 8 * w.getsampwidth()))
-        return np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").astype(np.int16)
+        if not 1 <= w.getnchannels() <= 8:
+            raise SystemExit("%s: need 1 to 8 channels, got %d" % (path, w.getnchannels()))
+        pcm = np.frombuffer(w.readframes(w.getnframes()), dtype="<i2").astype(np.int16)
+        return pcm.reshape(-1, w.getnchannels()), w.getframerate(), w.getnchannels()
 
 
 def load_engine(a):
@@ -111,12 +114,23 @@ def main(a):
     bound = ep.length_bound()
     max_frames = a.max_frames or (bound if bound is not None else 2000) + eng.cfg.static_chunk_size
     dec = StreamingCtcDecoder(eng.streaming(1, max_frames, independent=True), beam=a.beam, endpoint=ep, **kw)
-    pool = StreamPool(dec, audio=True, segment=True, rescore=rescorer is not None, timestamps=a.timestamps)
+    rate, channels = 16000, 1
     if a.synthetic:
         rng = np.random.default_rng(1)
         pcm = np.clip(np.cumsum(rng.normal(0, 1, int(16000 * a.synthetic))) * 50 % 20000 - 10000, -32768, 32767).astype(np.int16)
     else:
-        pcm = read_wav(a.wav_file)
+        pcm, rate, channels = read_wav(a.wav_file)
+        if not -1 <= a.channel < channels:
+            raise SystemExit("%s: --channel %d, the file has %d channel(s)" % (a.wav_file, a.channel, channels))
+        if (rate, channels) == (16000, 1):
+            pcm = pcm[:, 0]
+    from m3asr._lib import M3Error
+    try:
+        pool = StreamPool(dec, audio=True, segment=True, rescore=rescorer is not None, timestamps=a.timestamps, sample_rate=rate,
+                          channels=channels, channel=a.channel if channels > 1 else -1)
+    except M3Error as e:
+        raise SystemExit("%s: %s" % (a.wav_file, e))
+    piece = rate // 10                                            # 100 ms of samples
     sid = pool.open(context=0 if a.hotwords else None)
 
     def show_times(times):
@@ -133,8 +147,8 @@ def main(a):
             if a.timestamps:
                 show_times(s.times)
 
-    for pos in range(0, len(pcm), PIECE):
-        pool.push_audio(sid, torch.from_numpy(pcm[pos:pos + PIECE].copy()))
+    for pos in range(0, len(pcm), piece):
+        pool.push_audio(sid, torch.from_numpy(pcm[pos:pos + piece].copy()))
         while pool.step():
             show()
     pool.end(sid)
@@ -151,13 +165,14 @@ def main(a):
         print("%d- ms rule 0 rescored: %s" % (start, rescored(best, scores)))
     if a.timestamps:
         show_times(times)
-    print("%d engine steps, %.1f s of audio" % (pool.steps, len(pcm) / 16000.0))
+    print("%d engine steps, %.1f s of audio" % (pool.steps, len(pcm) / float(rate)))
 
 
 if __name__ == "__main__":
     p = argparse.ArgumentParser(description="Continuous streaming decoding of a wav file with endpoint detection (MI355X)")
     src = p.add_mutually_exclusive_group(required=True)
-    src.add_argument("-w", "--wav", dest="wav_file", help="A 16 kHz mono 16-bit wav file.")
+    src.add_argument("-w", "--wav", dest="wav_file", help="A 16-bit PCM wav file (any rate, up to 8 channels).")
+    p.add_argument("--channel", type=int, default=-1, help="-w: take this channel alone (default: the mean of all channels).")
     src.add_argument("--synthetic", type=float, default=0.0, help="Seconds of a generated signal through a small random model.")
     p.add_argument("-p", "--plan_name", help="The plan file of a streaming encoder (with -w).")
     p.add_argument("--beam", type=int, default=10)
