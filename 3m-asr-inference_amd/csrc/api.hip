@@ -471,24 +471,31 @@ int m3_dwconv_ln_silu_causal(const float* z, const float* w_kc, const float* bia
 }
 // The first conv at the boundary: the record from the ABI descriptor plus what only the boundary asks.  pair < 0: a single entry
 // (`who` in its messages), which takes an empty batch as a launch of nothing; pair = 0 / 1: a problem of m3_subsample_conv1_pair.
-static int conv1_args_from_desc(const m3_conv1_desc* d, const char* who, int pair, Conv1Args* q) {
+static int conv1_args_from_desc(const m3_conv1_ch_desc* d, const char* who, int pair, Conv1Args* q) {
+  M3_REQUIRE(d->in_ch >= 1 && d->in_ch <= 3, "%s: in_ch=%d outside [1, 3]", who, d->in_ch);
+  M3_REQUIRE(d->idim % d->in_ch == 0, "%s: idim=%d is no multiple of in_ch=%d", who, d->idim, d->in_ch);
   M3_REQUIRE((pair < 0 && d->B <= 0) || (d->feat && d->w9c && d->bias && d->out), "%s: null feat / w9c / bias / out", who);
   M3_REQUIRE(d->act == M3_ACT_NONE || d->act == M3_ACT_RELU, "%s: act %d (none / relu)", who, d->act);
   M3_REQUIRE((d->cmvn_mean == nullptr) == (d->cmvn_istd == nullptr), "%s: cmvn mean and istd go together", who);
   M3_REQUIRE((d->feat_len == nullptr) == (d->lens_out == nullptr) && (pair <= 0 || d->feat_len == nullptr),
              "%s: feat_len and lens_out go together, on the first problem only", who);
   if (pair >= 0) {   // (the words of the pair entry; a single entry hears the launcher's)
-    M3_REQUIRE(d->B > 0 && d->T >= 3 && d->idim >= 3, "%s: input (B=%d, T=%d, idim=%d) shorter than the 3x3 kernel", who, d->B, d->T, d->idim);
+    M3_REQUIRE(d->B > 0 && d->T >= 3 && d->idim / d->in_ch >= 3, "%s: input (B=%d, T=%d, idim=%d) shorter than the 3x3 kernel", who, d->B, d->T,
+               d->idim / d->in_ch);
     M3_REQUIRE(d->C > 0 && (d->C & 3) == 0 && d->C <= 1024, "%s: channels=%d must be a multiple of 4 (<= 1024)", who, d->C);
   }
   q->feat = d->feat; q->w9c = d->w9c; q->bias = d->bias; q->cmvn_mean = d->cmvn_mean; q->cmvn_istd = d->cmvn_istd;
   q->B = d->B; q->T = d->T; q->idim = d->idim; q->C = d->C; q->out = d->out; q->relu = d->act == M3_ACT_RELU;
-  q->feat_len = d->feat_len; q->lens_out = d->lens_out;
+  q->feat_len = d->feat_len; q->lens_out = d->lens_out; q->in_ch = d->in_ch; q->out_bf16 = d->out_bf16 != 0;
   return 0;
+}
+// the one-channel descriptor as the record's: in_ch = 1, fp32 out
+static m3_conv1_ch_desc conv1_ch_desc(const m3_conv1_desc& d) {
+  return {d.feat, d.w9c, d.bias, d.cmvn_mean, d.cmvn_istd, d.B, d.T, d.idim, d.C, d.act, d.out, d.feat_len, d.lens_out, 1, 0};
 }
 static int conv1_single(const char* who, const float* feat, const float* w9c, const float* bias, const float* cmvn_mean, const float* cmvn_istd,
                         int B, int T, int idim, int C, int act, float* out, m3_stream stream) {
-  const m3_conv1_desc d = {feat, w9c, bias, cmvn_mean, cmvn_istd, B, T, idim, C, act, out, nullptr, nullptr};
+  const m3_conv1_ch_desc d = {feat, w9c, bias, cmvn_mean, cmvn_istd, B, T, idim, C, act, out, nullptr, nullptr, 1, 0};
   Conv1Args q;
   if (int rc = conv1_args_from_desc(&d, who, -1, &q)) return rc;
   return launch_conv1_relu(q, (hipStream_t)stream);
@@ -500,6 +507,12 @@ int m3_subsample_conv1(const float* feat, const float* w9c, const float* bias, i
 int m3_subsample_conv1_cmvn(const float* feat, const float* w9c, const float* bias, const float* cmvn_mean,
                             const float* cmvn_istd, int B, int T, int idim, int C, float* out, m3_stream stream) {
   return conv1_single("subsample_conv1", feat, w9c, bias, cmvn_mean, cmvn_istd, B, T, idim, C, M3_ACT_RELU, out, stream);
+}
+int m3_subsample_conv1_ch(const m3_conv1_ch_desc* d, m3_stream stream) {
+  M3_REQUIRE(d != nullptr, "subsample_conv1_ch: null descriptor");
+  Conv1Args q;
+  if (int rc = conv1_args_from_desc(d, "subsample_conv1_ch", -1, &q)) return rc;
+  return launch_conv1_relu(q, (hipStream_t)stream);
 }
 int m3_conv2d_3x3s2_first(const float* feat, const float* w9c, const float* bias, int B, int T, int idim, int C, int act,
                           float* out, m3_stream stream) {
@@ -652,16 +665,27 @@ int m3_dwconv_ln_silu_pair(const m3_dwconv_desc* a, const m3_dwconv_desc* b, m3_
   M3_REQUIRE(!ranges_overlap(a->out, (size_t)a->B * a->T * a->D * 4, b->out, (size_t)b->B * b->T * b->D * 4), "dwconv pair: the two outputs overlap");
   return launch_dwconv_ln_silu_dual(qa, qb, (hipStream_t)stream);
 }
-int m3_subsample_conv1_pair(const m3_conv1_desc* a, const m3_conv1_desc* b, m3_stream stream) {
-  M3_REQUIRE(a != nullptr && b != nullptr, "conv1 pair: null descriptor");
+static int conv1_pair(const m3_conv1_ch_desc* a, const m3_conv1_ch_desc* b, m3_stream stream) {
   Conv1Args qa, qb;
   if (int rc = conv1_args_from_desc(a, "conv1 pair", 0, &qa)) return rc;
   if (int rc = conv1_args_from_desc(b, "conv1 pair", 1, &qb)) return rc;
-  auto bytes = [](const m3_conv1_desc* d) { return (size_t)d->B * ((d->T - 3) / 2 + 1) * ((d->idim - 3) / 2 + 1) * d->C * sizeof(float); };
+  auto bytes = [](const m3_conv1_ch_desc* d) {
+    return (size_t)d->B * ((d->T - 3) / 2 + 1) * ((d->idim / d->in_ch - 3) / 2 + 1) * d->C * (d->out_bf16 ? 2 : sizeof(float));
+  };
   M3_REQUIRE(a->B == b->B && a->T == b->T && a->idim == b->idim, "conv1 pair: the two problems do not share an input shape (B %d / %d, T %d / %d, idim %d / %d)",
              a->B, b->B, a->T, b->T, a->idim, b->idim);
+  M3_REQUIRE(a->in_ch == b->in_ch, "conv1 pair: the two problems do not share in_ch (%d / %d); run them as two launches", a->in_ch, b->in_ch);
   M3_REQUIRE(!ranges_overlap(a->out, bytes(a), b->out, bytes(b)), "conv1 pair: the two outputs overlap");
   return launch_conv1_relu_dual(qa, qb, (hipStream_t)stream);
+}
+int m3_subsample_conv1_pair(const m3_conv1_desc* a, const m3_conv1_desc* b, m3_stream stream) {
+  M3_REQUIRE(a != nullptr && b != nullptr, "conv1 pair: null descriptor");
+  const m3_conv1_ch_desc ca = conv1_ch_desc(*a), cb = conv1_ch_desc(*b);
+  return conv1_pair(&ca, &cb, stream);
+}
+int m3_subsample_conv1_ch_pair(const m3_conv1_ch_desc* a, const m3_conv1_ch_desc* b, m3_stream stream) {
+  M3_REQUIRE(a != nullptr && b != nullptr, "conv1 pair: null descriptor");
+  return conv1_pair(a, b, stream);
 }
 
 int m3_att_masked_softmax(const float* scores, const int32_t* len, int B, int H, int T1, int T2, float scale,
@@ -900,6 +924,29 @@ int m3_fbank(const void* tables, const void* pcm, int pcm_is_int16, int ld_pcm, 
   M3_REQUIRE(aligned16(tables) && aligned16(pcm), "fbank: tables / pcm must be 16-byte aligned");
   return launch_fbank(tables, pcm, pcm_is_int16, ld_pcm, n_samples, B, T, num_mel_bins, feat, ld_feat, feat_len_out,
                       (hipStream_t)stream);
+}
+
+int m3_deltas_tables_host(int order, int window, float* scales) {
+  M3_REQUIRE(scales != nullptr, "deltas_tables_host: null pointer");
+  return deltas_tables_build(order, window, scales);
+}
+int m3_add_deltas(const float* feat, int ld_feat, int64_t batch_stride_feat, int T_in, const int32_t* n_in, const int32_t* lead,
+                  const int32_t* n_out, int B, int T_out, int bins, int order, int window, float* out, int ld_out,
+                  int64_t batch_stride_out, int32_t* out_len, m3_stream stream) {
+  if (int rc = deltas_options_ok(order, window)) return rc;
+  M3_REQUIRE(B >= 0 && B <= 65535 && T_in >= 0 && T_out >= 0, "add_deltas: bad sizes B=%d T_in=%d T_out=%d", B, T_in, T_out);
+  M3_REQUIRE(bins >= 1 && bins <= 256, "add_deltas: bins=%d outside [1, 256]", bins);
+  if (B == 0 || T_out == 0) return 0;
+  M3_REQUIRE(feat && n_in && n_out && out, "add_deltas: null pointer");
+  M3_REQUIRE(ld_feat >= bins && batch_stride_feat >= 0, "add_deltas: ld_feat=%d is shorter than a row of %d, or a negative batch stride",
+             ld_feat, bins);
+  M3_REQUIRE(ld_out >= (order + 1) * bins && batch_stride_out >= 0,
+             "add_deltas: ld_out=%d is shorter than a row of %d columns, or a negative batch stride", ld_out, (order + 1) * bins);
+  // the in-place form writes beside the static columns it reads; any other overlap would read what it has written
+  M3_REQUIRE(out != feat || (ld_out == ld_feat && batch_stride_out == batch_stride_feat && lead == nullptr),
+             "add_deltas: out == feat is the in-place form: it needs equal strides and lead == nullptr");
+  return launch_add_deltas(feat, ld_feat, batch_stride_feat, T_in, n_in, lead, n_out, B, T_out, bins, order, window, out, ld_out,
+                           batch_stride_out, out_len, (hipStream_t)stream);
 }
 
 static int resample_rates_ok(const char* who, int rate_in, int rate_out) {

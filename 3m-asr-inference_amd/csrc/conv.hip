@@ -285,7 +285,7 @@ int launch_dwconv_ln_silu_dual(const DwArgs& a, const DwArgs& b, hipStream_t str
   return 0;
 }
 
-// feat [B][T][idim] -> out [B][T1][F1][C] (channel-last), w9c [9][C] (repacked from (C,1,3,3)), ReLU.
+// feat [B][T][idim] -> out [B][T1][F1][C] (channel-last), w9c [in_ch * 9][C] (repacked from (C,in_ch,3,3)), ReLU.
 // Optional global CMVN folded into the read: x <- (x - mean[f]) * istd[f]   (the reference's unfinished CmvnPlugin,
 // incomplete_plugin/cmvn_plugin/cmvn_plugin.cu:17-43; builder.sh:9 passes --cmvn_file but builder.py ignores it).
 // One work-group per output row (b, t1): thread = 4 channels.  The thread's 9 x 4 weights and bias stay in registers,
@@ -293,6 +293,11 @@ int launch_dwconv_ln_silu_dual(const DwArgs& a, const DwArgs& b, hipStream_t str
 // output columns writing C contiguous channels each -- no per-element index arithmetic, no weight reloads, 1-2 KB stores.
 // (the body as a device function of the work-group's output row and column chunk: conv1_relu_dual_kernel runs the embed and the
 //  main subsampler's first conv, which read the same features, in one launch)
+// IN_CH > 1 (conv_subsample_in_ch of the reference, layer/subsampling.py:23-36): the idim columns of a frame are IN_CH blocks of
+// Fc = idim / IN_CH bins (static | delta | delta-delta), read as the input channels of Conv2d(IN_CH, C, 3, 2): F1 counts on Fc,
+// w9c is [IN_CH * 9][C] with row ch * 9 + kh * 3 + kw, the LDS tile stays [3][idim] and a tap sits at kh * idim + ch * Fc +
+// 2 f1 + kw.  The thread keeps IN_CH * 9 f32x4 weights (27 at IN_CH = 3).  IN_CH = 1 is the one-channel code, tap for tap.
+template <int IN_CH>
 __device__ __forceinline__ void conv1_relu_body(const float* __restrict__ feat, const float* __restrict__ w9c,
                                                 const float* __restrict__ bias, const float* __restrict__ cmvn_mean,
                                                 const float* __restrict__ cmvn_istd, int T, int idim, int T1, int F1, int C,
@@ -315,11 +320,11 @@ __device__ __forceinline__ void conv1_relu_body(const float* __restrict__ feat, 
   }
   const int c = threadIdx.x * 4;
   const bool live = c < C;
-  f32x4 w[9], bv = f32x4{0.f, 0.f, 0.f, 0.f};
+  f32x4 w[9 * IN_CH], bv = f32x4{0.f, 0.f, 0.f, 0.f};
   if (live) {
     bv = ldg4(bias + c);
 #pragma unroll
-    for (int k = 0; k < 9; ++k) w[k] = ldg4(w9c + (size_t)k * C + c);
+    for (int k = 0; k < 9 * IN_CH; ++k) w[k] = ldg4(w9c + (size_t)k * C + c);
   }
   __syncthreads();
   if (!live) return;
@@ -327,16 +332,19 @@ __device__ __forceinline__ void conv1_relu_body(const float* __restrict__ feat, 
   // short inputs: the F1 columns of a row are split over blockIdx.y so that a single utterance still fills the chip
   const int fchunk = (F1 + gridDim.y - 1) / gridDim.y;
   const int f_lo = blockIdx.y * fchunk, f_hi = min(F1, f_lo + fchunk);
+  const int Fc = idim / IN_CH;
   for (int f1 = f_lo; f1 < f_hi; ++f1) {
     f32x4 acc = bv;
 #pragma unroll
-    for (int kh = 0; kh < 3; ++kh)
+    for (int ch = 0; ch < IN_CH; ++ch)
 #pragma unroll
-      for (int kw = 0; kw < 3; ++kw) {
-        const float xv = xs[kh * idim + 2 * f1 + kw];
+      for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = fmaf(xv, w[kh * 3 + kw][j], acc[j]);
-      }
+        for (int kw = 0; kw < 3; ++kw) {
+          const float xv = xs[kh * idim + ch * Fc + 2 * f1 + kw];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[j] = fmaf(xv, w[ch * 9 + kh * 3 + kw][j], acc[j]);
+        }
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[j] = relu ? fmaxf(acc[j], 0.f) : acc[j];
     if (out_bf16) {
@@ -358,28 +366,33 @@ struct Conv1KernArgs {
   int rows, fsplit, threads;   // the launch: B * T1 output rows, grid.y, block
 };
 #define M3_CONV1_SPREAD(a) a.feat, a.w9c, a.bias, a.cmvn_mean, a.cmvn_istd, a.T, a.idim, a.T1, a.F1, a.C, a.out, a.relu, a.out_bf16, a.feat_len, a.lens_out, a.B
-__global__ __launch_bounds__(256) void conv1_relu_kernel(const Conv1KernArgs a) { conv1_relu_body(M3_CONV1_SPREAD(a), (int)blockIdx.x); }
-// both problems: the same input shape (B, T, idim), so the same T1, F1 and column split; the second problem's rows start at n0,
-// a multiple of 8
+template <int IN_CH>
+__global__ __launch_bounds__(256) void conv1_relu_kernel(const Conv1KernArgs a) { conv1_relu_body<IN_CH>(M3_CONV1_SPREAD(a), (int)blockIdx.x); }
+// both problems: the same input shape (B, T, idim) and the same in_ch, so the same T1, F1 and column split; the second
+// problem's rows start at n0, a multiple of 8
+template <int IN_CH>
 __global__ __launch_bounds__(256) void conv1_relu_dual_kernel(const Conv1KernArgs a, const Conv1KernArgs b, int n0) {
   const int id = (int)blockIdx.x;
   if (id < n0) {
-    if (id < a.rows) conv1_relu_body(M3_CONV1_SPREAD(a), id);
+    if (id < a.rows) conv1_relu_body<IN_CH>(M3_CONV1_SPREAD(a), id);
   } else {
-    conv1_relu_body(M3_CONV1_SPREAD(b), id - n0);
+    conv1_relu_body<IN_CH>(M3_CONV1_SPREAD(b), id - n0);
   }
 }
 #undef M3_CONV1_SPREAD
 
 static int check_conv1(const Conv1Args& a, bool say = true) {
-  M3_REQUIRE_SAY(say, a.T >= 3 && a.idim >= 3, "subsampling: input (T=%d, idim=%d) shorter than the 3x3 kernel", a.T, a.idim);
+  M3_REQUIRE_SAY(say, a.in_ch >= 1 && a.in_ch <= 3, "subsampling: in_ch=%d outside [1, 3]", a.in_ch);
+  M3_REQUIRE_SAY(say, a.idim % a.in_ch == 0, "subsampling: idim=%d is no multiple of in_ch=%d", a.idim, a.in_ch);
+  M3_REQUIRE_SAY(say, a.T >= 3 && a.idim / a.in_ch >= 3, "subsampling: input (T=%d, idim=%d / in_ch=%d) shorter than the 3x3 kernel", a.T, a.idim,
+                 a.in_ch);
   M3_REQUIRE_SAY(say, (a.C & 3) == 0 && a.C > 0 && a.C <= 1024, "subsampling: channels=%d must be a multiple of 4 (<= 1024)", a.C);
   return 0;
 }
 static Conv1KernArgs conv1_pack(const Conv1Args& q) {
   Conv1KernArgs k;
   k.feat = q.feat; k.w9c = q.w9c; k.bias = q.bias; k.cmvn_mean = q.cmvn_mean; k.cmvn_istd = q.cmvn_istd; k.T = q.T; k.idim = q.idim;
-  k.T1 = (q.T - 3) / 2 + 1; k.F1 = (q.idim - 3) / 2 + 1; k.C = q.C; k.out = q.out; k.relu = q.relu; k.out_bf16 = q.out_bf16;
+  k.T1 = (q.T - 3) / 2 + 1; k.F1 = (q.idim / q.in_ch - 3) / 2 + 1; k.C = q.C; k.out = q.out; k.relu = q.relu; k.out_bf16 = q.out_bf16;
   k.feat_len = q.feat_len; k.lens_out = q.lens_out; k.B = q.B;
   k.rows = q.B * k.T1;
   k.fsplit = k.rows >= 2048 ? 1 : (k.rows >= 512 ? 2 : 5);
@@ -391,20 +404,27 @@ int launch_conv1_relu(const Conv1Args& a, hipStream_t stream) {
   if (int rc = check_conv1(a)) return rc;
   const Conv1KernArgs k = conv1_pack(a);
   if (k.rows == 0) return 0;
-  hipLaunchKernelGGL(conv1_relu_kernel, dim3(k.rows, k.fsplit), dim3(k.threads), 3 * a.idim * sizeof(float), stream, k);
+  const dim3 grid(k.rows, k.fsplit), block(k.threads);
+  const size_t lds = 3 * a.idim * sizeof(float);
+  if (a.in_ch == 1) hipLaunchKernelGGL(conv1_relu_kernel<1>, grid, block, lds, stream, k);
+  else if (a.in_ch == 2) hipLaunchKernelGGL(conv1_relu_kernel<2>, grid, block, lds, stream, k);
+  else hipLaunchKernelGGL(conv1_relu_kernel<3>, grid, block, lds, stream, k);
   M3_LAUNCH_CHECK();
   return 0;
 }
 bool conv1_dual_fusable(const Conv1Args& a, const Conv1Args& b) {
   return check_conv1(a, false) == 0 && check_conv1(b, false) == 0 && a.B == b.B && a.T == b.T && a.idim == b.idim &&
-         a.B * ((a.T - 3) / 2 + 1) > 0 && a.out != b.out;
+         a.in_ch == b.in_ch && a.B * ((a.T - 3) / 2 + 1) > 0 && a.out != b.out;
 }
 int launch_conv1_relu_dual(const Conv1Args& a, const Conv1Args& b, hipStream_t stream) {
-  M3_REQUIRE(conv1_dual_fusable(a, b), "subsampling conv1 dual: the two problems do not share an input shape");
+  M3_REQUIRE(conv1_dual_fusable(a, b), "subsampling conv1 dual: the two problems do not share an input shape and in_ch");
   const Conv1KernArgs ka = conv1_pack(a), kb = conv1_pack(b);
   const int n0 = (int)align_up((size_t)ka.rows, 8);
-  hipLaunchKernelGGL(conv1_relu_dual_kernel, dim3(n0 + kb.rows, ka.fsplit), dim3(ka.threads > kb.threads ? ka.threads : kb.threads),
-                     3 * a.idim * sizeof(float), stream, ka, kb, n0);
+  const dim3 grid(n0 + kb.rows, ka.fsplit), block(ka.threads > kb.threads ? ka.threads : kb.threads);
+  const size_t lds = 3 * a.idim * sizeof(float);
+  if (a.in_ch == 1) hipLaunchKernelGGL(conv1_relu_dual_kernel<1>, grid, block, lds, stream, ka, kb, n0);
+  else if (a.in_ch == 2) hipLaunchKernelGGL(conv1_relu_dual_kernel<2>, grid, block, lds, stream, ka, kb, n0);
+  else hipLaunchKernelGGL(conv1_relu_dual_kernel<3>, grid, block, lds, stream, ka, kb, n0);
   M3_LAUNCH_CHECK();
   return 0;
 }

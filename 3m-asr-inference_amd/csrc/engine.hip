@@ -53,7 +53,7 @@ struct BlockW {
   float h_scale = 0.f;                          // fp8 arithmetic: static scale of the hidden activations (0 = weight-only)
 };
 
-struct SubW { const float* c1w; const float* c1b; const float* c2w; const float* c2b; Lin out; };
+struct SubW { const float* c1w; const float* c1b; const float* c2w; const float* c2b; Lin out; int in_ch = 1; };
 
 // One launch of a kernel family, as the family's host record (kernels.h).  A stage that is one such launch holds the record and
 // nothing else: run_stage runs it from the record, and horizontal fusion (fuse_independent_pairs) pairs two stages by reading
@@ -327,9 +327,28 @@ bool load_block(const m3_engine* e, const std::string& p, int D, int F, int K, b
   return true;
 }
 
+// bins per input channel of a subsampler's first conv, and what the two stride-2 3x3 convs leave of them
+inline int sub_fc(int idim, int in_ch) { return idim / in_ch; }
+inline int sub_f1(int fc) { return (fc - 3) / 2 + 1; }
+inline int sub_f2(int fc) { return (sub_f1(fc) - 3) / 2 + 1; }
+
+// The first conv's input channels are read off its weight: conv.0.weight_9c holds 9 * in_ch * D numbers (m3_engine_config does
+// not change for them).  The idim columns of a frame are then in_ch blocks of Fc = idim / in_ch bins.
 bool load_sub(const m3_engine* e, const std::string& p, int D, int idim, SubW* s) {
-  const int F2 = ((idim - 1) / 2 - 1) / 2;
-  GET(s->c1w, p + "conv.0.weight_9c", 9 * (int64_t)D);
+  auto it = e->table.find(p + "conv.0.weight_9c");
+  const int64_t numel = it == e->table.end() ? 9 * (int64_t)D : it->second.numel;
+  s->in_ch = (int)(numel / (9 * (int64_t)D));
+  if (numel % (9 * (int64_t)D) || s->in_ch < 1 || s->in_ch > 3) {
+    set_error("engine: '%sconv.0.weight_9c' has %lld elements: 9 * in_ch * %d with 1 to 3 input channels expected", p.c_str(), (long long)numel, D);
+    return false;
+  }
+  if (idim % s->in_ch || sub_fc(idim, s->in_ch) < 7) {
+    set_error("engine: '%sconv.0.weight_9c' has %d input channels: input_dim=%d must be a multiple of it with at least 7 bins per channel",
+              p.c_str(), s->in_ch, idim);
+    return false;
+  }
+  const int F2 = sub_f2(sub_fc(idim, s->in_ch));
+  GET(s->c1w, p + "conv.0.weight_9c", 9 * (int64_t)s->in_ch * D);
   GET(s->c1b, p + "conv.0.bias", D);
   GETW(s->c2w, p + "conv.2.weight_ohwi", 9 * (int64_t)D * D);
   GET(s->c2b, p + "conv.2.bias", D);
@@ -398,11 +417,14 @@ bool use_hfuse(const m3_engine_config& c, int B, int S) {
 
 size_t router_prefix_layer_floats(const m3_engine_config& c, int S, const Plan& pl);
 
-Plan make_plan(const m3_engine_config& c, void* base, int B, int T, int ep_capacity = 0) {
+Plan make_plan(const m3_engine& eng, void* base, int B, int T, int ep_capacity = 0) {
+  const m3_engine_config& c = eng.cfg;
   Plan p;
   Carver cv(base);
   const int Tp = sub_len(T), S = B * Tp;
-  const int T1 = (T - 3) / 2 + 1, F1 = (c.input_dim - 3) / 2 + 1, F2 = (F1 - 3) / 2 + 1;
+  // the subsamplers' buffers hold either encoder's: sized by the one with fewer input channels (more bins per channel)
+  const int fc_m = sub_fc(c.input_dim, eng.sub_m.in_ch), fc_e = sub_fc(c.input_dim, eng.sub_e.in_ch), fc = fc_m > fc_e ? fc_m : fc_e;
+  const int T1 = (T - 3) / 2 + 1, F1 = sub_f1(fc), F2 = sub_f2(fc);
   const int D = c.attention_dim > c.embed_dim ? c.attention_dim : c.embed_dim;
   const int F = c.hidden_units > c.embed_linear_units ? c.hidden_units : c.embed_linear_units;
   const int world = c.ep_world_size > 0 ? c.ep_world_size : 1;
@@ -455,12 +477,14 @@ Plan make_plan(const m3_engine_config& c, void* base, int B, int T, int ep_capac
   {
     size_t n1 = 0, n2 = 0;
     if (c.weight_dtype == M3_F32) {
-      GemmParams g;   // conv2 as implicit GEMM
-      g.mode = GEMM_A_CONV3X3S2; g.lda = 4; g.conv_C = D; g.M = S * F2; g.N = D; g.K = 9 * D; g.ldy = D;
-      n1 = plan_gemm(g, SIZE_MAX).ws_bytes;
-      GemmParams l;   // Linear(C*F2 -> D)
-      l.lda = F2 * D; l.M = S; l.N = D; l.K = F2 * D; l.ldy = D;
-      n2 = plan_gemm(l, SIZE_MAX).ws_bytes;
+      for (const int f2 : {sub_f2(fc_m), sub_f2(fc_e)}) {   // (one problem twice unless the encoders differ in in_ch)
+        GemmParams g;   // conv2 as implicit GEMM
+        g.mode = GEMM_A_CONV3X3S2; g.lda = 4; g.conv_C = D; g.M = S * f2; g.N = D; g.K = 9 * D; g.ldy = D;
+        n1 = std::max(n1, plan_gemm(g, SIZE_MAX).ws_bytes);
+        GemmParams l;   // Linear(C*F2 -> D)
+        l.lda = f2 * D; l.M = S; l.N = D; l.K = f2 * D; l.ldy = D;
+        n2 = std::max(n2, plan_gemm(l, SIZE_MAX).ws_bytes);
+      }
     }
     p.splitk_bytes = n1 > n2 ? n1 : n2;
     p.splitk = p.splitk_bytes ? cv.take<float>(p.splitk_bytes / sizeof(float)) : nullptr;
@@ -775,7 +799,8 @@ static int embed_join(const std::vector<Stage>& st, int from) {
 static void build_subsample(StageBuilder& sb, const std::string& pfx, const SubW& w, int D, const Plan& pl, float* xout) {
   const m3_engine_config& c = sb.eng.cfg;
   const int B = sb.bd.key.B, T = sb.bd.key.T;
-  const int T1 = (T - 3) / 2 + 1, F1 = (c.input_dim - 3) / 2 + 1, F2 = (F1 - 3) / 2 + 1, T2 = (T1 - 3) / 2 + 1;
+  const int fc = sub_fc(c.input_dim, w.in_ch);   // bins per input channel of this encoder's first conv
+  const int T1 = (T - 3) / 2 + 1, F1 = sub_f1(fc), F2 = sub_f2(fc), T2 = (T1 - 3) / 2 + 1;
   const float* feat = sb.bd.key.feat;
   float* c1 = pl.c1; float* c2 = pl.c2;
   const int idim = c.input_dim;
@@ -787,9 +812,9 @@ static void build_subsample(StageBuilder& sb, const std::string& pfx, const SubW
   sb.lens_in_conv1 = false;
   Conv1Args ca;
   ca.feat = feat; ca.w9c = w.c1w; ca.bias = w.c1b; ca.cmvn_mean = cm; ca.cmvn_istd = ci; ca.B = B; ca.T = T; ca.idim = idim; ca.C = D; ca.out = c1;
-  ca.relu = 1; ca.out_bf16 = a16; ca.feat_len = flen; ca.lens_out = lens_out;
+  ca.relu = 1; ca.out_bf16 = a16; ca.feat_len = flen; ca.lens_out = lens_out; ca.in_ch = w.in_ch;
   add_launch(sb, pfx + "conv1", ca,
-             stage_info("conv1_relu_kernel", 1, (double)B * T * idim * 4 + (double)B * T1 * F1 * D * (a16 ? 2 : 4), 18.0 * B * T1 * F1 * D, false));
+             stage_info("conv1_relu_kernel", 1, (double)B * T * idim * 4 + (double)B * T1 * F1 * D * (a16 ? 2 : 4), 18.0 * w.in_ch * B * T1 * F1 * D, false));
   const size_t conv1_at = sb.bd.stages.size() - 1;
   GemmParams g;
   g.a_bf16 = a16; g.y_bf16 = a16;
@@ -1320,7 +1345,7 @@ void m3_engine_destroy(m3_engine* engine) {
 
 size_t m3_engine_workspace_size(const m3_engine* engine, int B, int T) {
   if (!engine || B <= 0 || T < 7) return 0;
-  return make_plan(engine->cfg, nullptr, B, T, engine->ep_capacity).bytes;
+  return make_plan(*engine, nullptr, B, T, engine->ep_capacity).bytes;
 }
 
 // once, outside graph capture (idempotent): the dynamic-LDS opt-ins and the like of every kernel family a stage list can hold
@@ -1346,7 +1371,7 @@ static int build_binding(m3_engine* e, const BindKey& k, m3_engine::Bound& bd) {
              (long long)e->pe_rows);  // rel_positional_encoding_plugin.cpp:139-142
   if (int rc = init_engine_kernels()) return rc;
   const bool streaming = k.sstate != nullptr;
-  StageBuilder sb{*e, make_plan(c, k.ws, B, T, k.ep_cap), bd,
+  StageBuilder sb{*e, make_plan(*e, k.ws, B, T, k.ep_cap), bd,
                   streaming ? carve_stream_state(c, k.sstate, B, k.s_hist) : StreamState()};
   Plan& pl = sb.pl;
   M3_REQUIRE(k.ws_bytes >= pl.bytes, "engine_prepare: workspace %zu bytes < required %zu", k.ws_bytes, pl.bytes);

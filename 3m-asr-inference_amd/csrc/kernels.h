@@ -363,6 +363,9 @@ struct Conv1Args {
   const float *feat = nullptr, *w9c = nullptr, *bias = nullptr, *cmvn_mean = nullptr, *cmvn_istd = nullptr;
   int B = 0, T = 0, idim = 0, C = 0; float* out = nullptr; int relu = 1, out_bf16 = 0;
   const int32_t* feat_len = nullptr; int32_t* lens_out = nullptr;   // feat_len: the launch also forms the subsampled lengths
+  // input channels (1..3): a frame's idim columns are in_ch blocks of Fc = idim / in_ch bins, w9c is [in_ch * 9][C] with row
+  // ch * 9 + kh * 3 + kw, the output has F1 = (Fc - 3) / 2 + 1 columns
+  int in_ch = 1;
 };
 int launch_conv1_relu(const Conv1Args& a, hipStream_t stream);
 bool conv1_dual_fusable(const Conv1Args& a, const Conv1Args& b);
@@ -597,5 +600,13 @@ void resample_input_span(int rate_in, int rate_out, long out0, long n_out, long*
 int launch_resample(const void* tables, const void* pcm, int pcm_is_int16, int channels, int channel, int ld_pcm,
                     const int64_t* in0, const int32_t* n_in, const int64_t* out0, const int32_t* n_out, int B, int N_out,
                     float* out, int ld_out, hipStream_t stream);
+
+// deltas.hip: Kaldi DeltaFeatures (add-deltas), static frames -> static | delta | delta-delta
+constexpr int DELTAS_MAX_CONTEXT = 8;                                     // order * window at most
+int deltas_options_ok(int order, int window);
+int deltas_tables_build(int order, int window, float* scales);           // (order + 1) rows of 2 * DELTAS_MAX_CONTEXT + 1 floats
+int launch_add_deltas(const float* feat, long ld_feat, long bs_feat, int T_in, const int32_t* n_in, const int32_t* lead,
+                      const int32_t* n_out, int B, int T_out, int bins, int order, int window, float* out, long ld_out,
+                      long bs_out, int32_t* out_len, hipStream_t stream);
 
 }  // namespace m3

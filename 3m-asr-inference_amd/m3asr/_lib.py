@@ -64,6 +64,10 @@ class Conv1Desc(C.Structure):  # m3_conv1_desc
                 ("feat_len", C.c_void_p), ("lens_out", C.c_void_p)]
 
 
+class Conv1ChDesc(C.Structure):  # m3_conv1_ch_desc
+    _fields_ = Conv1Desc._fields_ + [("in_ch", C.c_int32), ("out_bf16", C.c_int32)]
+
+
 class EngineConfig(C.Structure):  # m3_engine_config
     _fields_ = [(n, C.c_int32) for n in (
         "input_dim", "output_dim", "attention_dim", "attention_heads", "num_blocks",
@@ -190,6 +194,8 @@ SIGNATURES = {
     "m3_relpos_attention_pair": (_i, [_P(AttentionDesc), _P(AttentionDesc), _vp]),
     "m3_dwconv_ln_silu_pair": (_i, [_P(DwconvDesc), _P(DwconvDesc), _vp]),
     "m3_subsample_conv1_pair": (_i, [_P(Conv1Desc), _P(Conv1Desc), _vp]),
+    "m3_subsample_conv1_ch": (_i, [_P(Conv1ChDesc), _vp]),
+    "m3_subsample_conv1_ch_pair": (_i, [_P(Conv1ChDesc), _P(Conv1ChDesc), _vp]),
     "m3_conv2d_3x3s2_first": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "m3_conv2d_3x3s2": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "m3_layer_norm": (_i, [_vp, _vp, _vp, _f, _vp, _i, _i, _vp]),
@@ -287,6 +293,8 @@ SIGNATURES = {
     "m3_fbank_tables_init": (_i, [_i, _f, _f, _f, _vp, _vp]),
     "m3_fbank_num_frames": (_i, [_i]),
     "m3_fbank": (_i, [_vp, _vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "m3_deltas_tables_host": (_i, [_i, _i, _vp]),
+    "m3_add_deltas": (_i, [_vp, _i, _i64, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _i64, _vp, _vp]),
     "m3_resample_tables_bytes": (_sz, [_i, _i]),
     "m3_resample_tables_host": (_i, [_i, _i, _vp]),
     "m3_resample_tables_init": (_i, [_i, _i, _vp, _vp]),

@@ -55,8 +55,36 @@ class EncoderConfig:
     # Together with static_chunk_size > 0 this is the configuration that can be decoded chunk by chunk (Engine.streaming).
     causal: bool = False
     embed_causal: bool = False
+    # input channels of the subsamplers' first conv (conv_subsample_in_ch of every Net, embed_conf['conv_subsample_in_ch'] of
+    # the embed encoder; layer/subsampling.py:23-36 views (B, T, idim) as (B, in_ch, T, idim / in_ch)): with 3 the static |
+    # delta | delta-delta blocks of a frame are the three image channels of Conv2d(in_ch, C, 3, 2).  1 to 3.
+    conv_subsample_in_ch: int = 1
+    embed_conv_subsample_in_ch: int = 1
+    # delta features of the loader (add_deltas / delta_window, trainer_3m_fix/loader/*.py): the model reads static | delta |
+    # delta-delta, input_dim = num_mel_bins * (1 + delta_order) columns.  The encoder itself does not care; the audio front
+    # end does (m3asr.frontend.DeltaFbank).  0 = static features only.
+    delta_order: int = 0
+    delta_window: int = 2
+
+    # fields that are left out of to_json() while they hold their defaults: a header or fixture written before they existed
+    # and one written now for the same model are the same bytes
+    _LATE_FIELDS = ("conv_subsample_in_ch", "embed_conv_subsample_in_ch", "delta_order", "delta_window")
 
     def __post_init__(self):
+        if not 0 <= self.delta_order <= 2:
+            raise ValueError("EncoderConfig: delta_order=%d outside [0, 2]" % self.delta_order)
+        if not 1 <= self.delta_window <= 4:
+            raise ValueError("EncoderConfig: delta_window=%d outside [1, 4]" % self.delta_window)
+        if self.input_dim % (1 + self.delta_order):
+            raise ValueError("EncoderConfig: input_dim=%d is no multiple of 1 + delta_order = %d blocks of mel bins" % (
+                self.input_dim, 1 + self.delta_order))
+        for name in ("conv_subsample_in_ch", "embed_conv_subsample_in_ch"):
+            ch = getattr(self, name)
+            if not 1 <= ch <= 3:
+                raise ValueError("EncoderConfig: %s=%d outside [1, 3]" % (name, ch))
+            if self.input_dim % ch or self.input_dim // ch < 7:
+                raise ValueError("EncoderConfig: %s=%d: input_dim=%d must be a multiple of it with at least 7 bins per channel" % (
+                    name, ch, self.input_dim))
         if self.weight_dtype == "mxfp4" and self.fp8_activations:
             raise ValueError("EncoderConfig: fp8_activations needs weight_dtype 'fp8'; 'mxfp4' is a weight-only mode (W4A16)")
 
@@ -73,11 +101,27 @@ class EncoderConfig:
 
     @property
     def sub_freq(self):
-        """Frequency bins left after the two stride-2 3x3 convs (subsampling.py:94)."""
-        return ((self.input_dim - 1) // 2 - 1) // 2
+        """Frequency bins left after the two stride-2 3x3 convs (subsampling.py:94), of the input_dim / conv_subsample_in_ch
+        bins of a channel."""
+        return ((self.input_dim // self.conv_subsample_in_ch - 1) // 2 - 1) // 2
+
+    @property
+    def embed_sub_freq(self):
+        """sub_freq of the embed encoder's subsampler (its own embed_conv_subsample_in_ch)."""
+        return ((self.input_dim // self.embed_conv_subsample_in_ch - 1) // 2 - 1) // 2
+
+    @property
+    def num_mel_bins(self):
+        """Mel bins of the static block: what the fbank front end computes per frame."""
+        return self.input_dim // (1 + self.delta_order)
 
     def to_json(self):
-        return json.dumps(asdict(self), sort_keys=True)
+        d = asdict(self)
+        default = EncoderConfig()
+        for name in self._LATE_FIELDS:
+            if d[name] == getattr(default, name):
+                del d[name]
+        return json.dumps(d, sort_keys=True)
 
     @staticmethod
     def from_json(s):
@@ -93,8 +137,9 @@ class EncoderConfig:
         return EncoderConfig(**base)
 
     @staticmethod
-    def from_reference_conf(input_dim, output_dim, encoder_conf):
-        """Map a reference yaml ``model_conf['encoder_conf']`` dict onto EncoderConfig."""
+    def from_reference_conf(input_dim, output_dim, encoder_conf, delta_order=0, delta_window=2):
+        """Map a reference yaml ``model_conf['encoder_conf']`` dict onto EncoderConfig.  delta_order / delta_window: the
+        loader's add_deltas / delta_window the model was trained with (they live in the data config, not in encoder_conf)."""
         ec = dict(encoder_conf or {})
         emb = dict(ec.get("embed_conf") or {})
         moe = dict(ec.get("moe_conf") or {})
@@ -117,6 +162,9 @@ class EncoderConfig:
             ep_world_size=moe.get("world_size", 1), ep_rank=moe.get("rank", 0),
             static_chunk_size=ec.get("static_chunk_size", 0),
             causal=bool(ec.get("causal", False)), embed_causal=bool(emb.get("causal", False)),
+            conv_subsample_in_ch=int(ec.get("conv_subsample_in_ch", 1)),
+            embed_conv_subsample_in_ch=int(emb.get("conv_subsample_in_ch", 1)),
+            delta_order=int(delta_order), delta_window=int(delta_window),
         )
 
 

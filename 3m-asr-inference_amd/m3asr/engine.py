@@ -196,10 +196,12 @@ class Engine:
         With another sample_rate, or channels > 1 (pcm (B, N, channels) or interleaved (B, N * channels); channel = -1: the
         mean of all, k: channel k alone; n_samples per channel), one launch of m3asr.frontend.Resampler (Kaldi's
         LinearResample, cached per (sample_rate, channels, channel)) on the engine stream first writes the 16 kHz mono
-        samples into a float32 staging tensor, which the front end then reads; T = num_frames(num_resampled(N))."""
-        from .frontend import Fbank, num_frames
+        samples into a float32 staging tensor, which the front end then reads; T = num_frames(num_resampled(N)).
+        A config with delta_order > 0 (a model trained on the loader's add_deltas) gets m3asr.frontend.DeltaFbank: the log-Mel
+        frames go into columns [0, num_mel_bins) of the input buffer and one more launch fills in the delta blocks beside them."""
+        from .frontend import make_frontend, num_frames
         if getattr(self, "_fbank", None) is None:
-            self._fbank = Fbank(self.cfg.input_dim, self.device)
+            self._fbank = make_frontend(self.cfg, self.device)   # cfg.delta_order > 0: DeltaFbank, one more launch fills in the deltas
         pcm = torch.as_tensor(pcm)
         pcm = pcm.unsqueeze(0) if pcm.dim() == 1 else pcm
         N = int(pcm.shape[1])

@@ -8,7 +8,13 @@ no CMVN (that stays folded into conv1).
     fb = Fbank(cfg.input_dim, "cuda:0")
     feat, feat_len = fb(pcm)                       # pcm (B, N) or (N,) -> (B, T, bins) float32, (B,) int32 on the device
 
-`num_frames`, `fbank_tables` and `AudioWindowBuffer` are host-only and need no GPU.
+Delta features (m3_add_deltas, csrc/deltas.hip): a model trained on the loader's add_deltas reads
+static | delta | delta-delta columns; DeltaFbank is Fbank followed by one more launch that fills them in.
+
+    fb = DeltaFbank(cfg.num_mel_bins, cfg.delta_order, cfg.delta_window, "cuda:0")
+    feat, feat_len = fb(pcm)                       # (B, T, (order + 1) * bins)
+
+`num_frames`, `fbank_tables`, `delta_tables` and `AudioWindowBuffer` are host-only and need no GPU.
 """
 import ctypes as C
 
@@ -21,6 +27,7 @@ from .serve import next_window_valid
 
 SAMPLE_RATE, FRAME_LENGTH, FRAME_SHIFT, LOW_FREQ = 16000, 400, 160, 20.0
 MAX_MEL_BINS = 128
+MAX_DELTA_CONTEXT = 8
 
 
 def num_frames(n):
@@ -128,6 +135,130 @@ class Fbank:
                                     n_dev.data_ptr(), B, T, self.bins, out.data_ptr(), int(out.stride(1)), out_len.data_ptr(),
                                     C.c_void_p(st.cuda_stream)), "m3_fbank")
         return out, out_len
+
+
+def delta_context(order, window):
+    """Frames of context on either side that a delta frame reads: order * window (0 for order 0)."""
+    return int(order) * int(window)
+
+
+def delta_tables(order, window):
+    """Kaldi's DeltaFeatures filters as the library builds them (float64 on the host, rounded once to float32), without a
+    GPU: [scales_0, ..., scales_order], scales_i a float32 array of 2 i window + 1 taps for offsets -i window .. i window."""
+    rows = np.zeros((int(order) + 1, 2 * MAX_DELTA_CONTEXT + 1), dtype=np.float32)
+    check(_lib.load().m3_deltas_tables_host(int(order), int(window), rows.ctypes.data_as(C.c_void_p)), "m3_deltas_tables_host")
+    return [rows[i, MAX_DELTA_CONTEXT - i * int(window): MAX_DELTA_CONTEXT + i * int(window) + 1].copy() for i in range(int(order) + 1)]
+
+
+def add_deltas(feat, n_in, order, window, out=None, lead=None, n_out=None, out_len=None, bins=None, stream=None):
+    """m3_add_deltas on device tensors: feat (B, T_in, >= bins) float32 static frames (bins: default feat.shape[2]), n_in (B,)
+    int32 frames present; lead (B,) int32 frames in front that are context only (None = 0), n_out (B,) int32 frames to
+    produce (None = n_in).  out (B, T_out, >= (order + 1) * bins) (default a new dense (B, T_in, (order + 1) * bins) tensor);
+    out is feat: the in-place form, only the delta columns are written.  out_len (B,) int32 receives the clipped n_out.
+    -> out"""
+    lib = _lib.load()
+    bins = int(feat.shape[2] if bins is None else bins)
+    B = int(feat.shape[0])
+    width = (int(order) + 1) * bins
+    if feat.dim() != 3 or feat.dtype != torch.float32 or not feat.is_cuda or (feat.shape[2] > 1 and feat.stride(2) != 1) or feat.shape[2] < bins:
+        raise ValueError("add_deltas: feat must be a (B, T, >= %d) float32 device tensor with dense rows" % bins)
+    if out is None:
+        out = torch.empty(B, int(feat.shape[1]), width, dtype=torch.float32, device=feat.device)
+    if out.dim() != 3 or out.shape[0] != B or out.shape[2] < width or out.dtype != torch.float32 or out.device != feat.device or \
+            out.stride(2) != 1:
+        raise ValueError("add_deltas: out must be a (B, T, >= %d) float32 device tensor with dense rows" % width)
+    n_out = n_in if n_out is None else n_out
+    for name, v in (("n_in", n_in), ("lead", lead), ("n_out", n_out), ("out_len", out_len)):
+        if v is None and name in ("lead", "out_len"):
+            continue
+        if v.dtype != torch.int32 or v.device != feat.device or v.numel() != B or not v.is_contiguous():
+            raise ValueError("add_deltas: %s must be a contiguous int32 device tensor of %d entries" % (name, B))
+    ptr = lambda v: None if v is None else v.data_ptr()
+    with torch.cuda.device(feat.device), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        st = torch.cuda.current_stream()
+        check(lib.m3_add_deltas(feat.data_ptr(), int(feat.stride(1)), int(feat.stride(0)), int(feat.shape[1]), n_in.data_ptr(),
+                                ptr(lead), n_out.data_ptr(), B, int(out.shape[1]), bins, int(order), int(window),
+                                out.data_ptr(), int(out.stride(1)), int(out.stride(0)), ptr(out_len), C.c_void_p(st.cuda_stream)),
+              "m3_add_deltas")
+    return out
+
+
+class DeltaFbank:
+    """Fbank followed by Kaldi's add-deltas on one device: what the loader's add_deltas / delta_window feed a
+    model.  It has Fbank's call signature and makes two launches: the log-Mel frames go into columns [0, bins) of `out`, whose
+    rows are (order + 1) * bins wide or wider, then m3_add_deltas in its in-place form fills in the delta blocks beside them."""
+
+    def __init__(self, num_mel_bins, order=2, window=2, device="cuda:0"):
+        self.order, self.delta_window = int(order), int(window)
+        delta_tables(self.order, self.delta_window)              # refuses a bad (order, window) here, with the library's message
+        self.fbank = Fbank(num_mel_bins, device)
+        self.bins, self.device, self.lib = self.fbank.bins, self.fbank.device, self.fbank.lib
+        self.width = (self.order + 1) * self.bins
+        self.context = delta_context(self.order, self.delta_window)
+
+    def __call__(self, pcm, n_samples=None, out=None, out_len=None, stream=None, lead=None, n_out=None):
+        """Fbank.__call__ with rows of (order + 1) * bins columns: out (B, T, >= width), default a new (B, num_frames(N), width)
+        tensor.  lead / n_out (B,) int32, host or device (the streaming form): the samples are a window whose first lead[b]
+        frames are context only and of which n_out[b] delta frames are wanted; the static frames then go through a scratch
+        tensor and out may have fewer rows than the window has frames.  Without them every frame is produced, with Kaldi's edge
+        replication at both ends.  -> (out, out_len)"""
+        with torch.cuda.device(self.device), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            st = torch.cuda.current_stream()
+            if lead is None and n_out is None:
+                if out is None:
+                    pcm = torch.as_tensor(pcm)
+                    shape = (1, pcm.shape[0]) if pcm.dim() == 1 else tuple(pcm.shape)
+                    out = torch.empty(int(shape[0]), num_frames(shape[1]), self.width, dtype=torch.float32, device=self.device)
+                if out.dim() != 3 or out.shape[2] < self.width:
+                    raise ValueError("DeltaFbank: out must be a (B, T, >= %d) float32 device tensor with dense rows" % self.width)
+                out, out_len = self.fbank(pcm, n_samples, out=out, out_len=out_len, stream=st)
+                if out.shape[0] and out.shape[1]:
+                    add_deltas(out, out_len.view(-1), self.order, self.delta_window, out=out, bins=self.bins, stream=st)
+                return out, out_len
+            if lead is None or n_out is None or out is None:
+                raise ValueError("DeltaFbank: the streaming form needs lead, n_out and out")
+            dev, N = self.fbank._device_pcm(pcm)
+            B, T_in = int(dev.shape[0]), max(num_frames(N), 1)
+            key = (B, T_in)
+            if getattr(self, "_scratch_key", None) != key:
+                self._scratch = torch.empty(B, T_in, -(-self.bins // 4) * 4, dtype=torch.float32, device=self.device)
+                self._scratch_len = torch.zeros(B, dtype=torch.int32, device=self.device)
+                self._scratch_key = key
+            lead = torch.as_tensor(lead).reshape(-1).to(self.device, torch.int32, non_blocking=True)
+            n_out = torch.as_tensor(n_out).reshape(-1).to(self.device, torch.int32, non_blocking=True)
+            if out_len is None:
+                out_len = torch.zeros(B, dtype=torch.int32, device=self.device)
+            if num_frames(N) == 0 or B == 0:
+                out[..., :self.width].zero_()
+                out_len.zero_()
+                return out, out_len
+            self.fbank(dev, n_samples, out=self._scratch, out_len=self._scratch_len, stream=st)
+            add_deltas(self._scratch, self._scratch_len, self.order, self.delta_window, out=out, lead=lead, n_out=n_out,
+                       out_len=out_len.view(-1), bins=self.bins, stream=st)
+        return out, out_len
+
+
+def make_frontend(cfg, device):
+    """The front end a config's encoder reads: Fbank(cfg.input_dim), or DeltaFbank when the model was trained on delta features
+    (cfg.delta_order > 0)."""
+    if cfg.delta_order > 0:
+        return DeltaFbank(cfg.num_mel_bins, cfg.delta_order, cfg.delta_window, device)
+    return Fbank(cfg.input_dim, device)
+
+
+def _checked_context(context):
+    context = int(context)
+    if not 0 <= context <= MAX_DELTA_CONTEXT:
+        raise ValueError("AudioWindowBuffer: context=%d outside [0, %d]" % (context, MAX_DELTA_CONTEXT))
+    return context
+
+
+def _context_window(frames, n, c, v, R):
+    """The static frames [s0, s1) that window n of v delta frames reads out of `frames` there are, and its lead (DESIGN.md
+    32.5): R frames of context on either side where the segment has them."""
+    s0 = max(4 * c * n - R, 0)
+    s1 = min(4 * c * n + v + R, frames)
+    return s0, s1, 4 * c * n - s0
 
 
 def _check_rates(rate_in, rate_out):
@@ -277,12 +408,15 @@ class ResampledWindowBuffer:
     sample_rate, channels) returns unless both have their defaults.  It buffers INPUT-rate interleaved samples and keeps
     absolute clocks: the 16 kHz signal is resample(whole session) (m3_resample's contract makes a sample depend on its
     absolute index only), window n of the open segment holds its samples [origin + hop n, origin + hop n + window), and take()
-    hands back the input samples that window reads together with the four index entries of its row of the launch."""
+    hands back the input samples that window reads together with the four index entries of its row of the launch.
+    context=R: as in AudioWindowBuffer, in 16 kHz frames of the open segment."""
 
-    def __init__(self, chunk, dtype=torch.int16, sample_rate=SAMPLE_RATE, channels=1):
+    def __init__(self, chunk, dtype=torch.int16, sample_rate=SAMPLE_RATE, channels=1, context=0):
         self.c = int(chunk)
+        self.context = _checked_context(context)
+        self.lead = 0
         self.hop = FRAME_SHIFT * 4 * self.c
-        self.window = (4 * self.c + 2) * FRAME_SHIFT + FRAME_LENGTH
+        self.window = (4 * self.c + 2 + 2 * self.context) * FRAME_SHIFT + FRAME_LENGTH
         self.dtype = dtype
         self.rate, self.channels = int(sample_rate), int(channels)
         _check_rates(self.rate, SAMPLE_RATE)
@@ -327,7 +461,8 @@ class ResampledWindowBuffer:
     def ready(self):
         """Real FRAMES of the next window if it can run now, else 0 (serve.next_window_valid on the frames of the resampled
         samples there are)."""
-        return next_window_valid(num_frames(self._available()), self.chunks, self.c, self.ended)
+        frames = num_frames(self._available())
+        return next_window_valid(frames if self.ended else max(frames - self.context, 0), self.chunks, self.c, self.ended)
 
     def drained(self):
         return self.ended and self.ready() == 0
@@ -335,11 +470,15 @@ class ResampledWindowBuffer:
     def take(self, out=None):
         """The next window as (input samples (span, channels) zero filled behind the real ones, in0, n_in, out0, n_out): the
         row's entries of the resampler launch that produces the window's n_out real 16 kHz samples; advances by one chunk.
-        num_frames(n_out) is what ready() returned.  out: a (span * channels,) or (span, channels) destination."""
-        if self.ready() == 0:
+        num_frames(n_out) is what ready() returned -- with context > 0, that plus the frames of context in front (self.lead
+        after the call) and behind.  out: a (span * channels,) or (span, channels) destination."""
+        v = self.ready()
+        if v == 0:
             raise ValueError("no window ready")
-        out0 = self.origin + self.hop * self.chunks
-        n_out = min(self._available() - self.hop * self.chunks, self.window)
+        avail = self._available()
+        s0, s1, self.lead = _context_window(num_frames(avail), self.chunks, self.c, v, self.context)
+        out0 = self.origin + FRAME_SHIFT * s0
+        n_out = min(avail - FRAME_SHIFT * s0 if s1 == num_frames(avail) else FRAME_SHIFT * (s1 - s0 - 1) + FRAME_LENGTH, self.window)
         lo, hi = resample_span(out0, n_out, self.rate)
         in0, end = max(lo, self.base), min(hi, self.total)
         n_in = max(end - in0, 0)
@@ -347,7 +486,8 @@ class ResampledWindowBuffer:
         win.zero_()
         win.view(-1, self.channels)[:n_in] = self.buf[in0 - self.base:in0 - self.base + n_in]
         self.chunks += 1
-        drop = resample_span(out0 + self.hop, 1, self.rate)[0] - self.base   # input left of the next window is never read again
+        keep = self.origin + FRAME_SHIFT * max(4 * self.c * self.chunks - self.context, 0)
+        drop = resample_span(keep, 1, self.rate)[0] - self.base   # input left of the next window is never read again
         if drop > 0:
             self.buf = self.buf[min(drop, self.buf.shape[0]):]
             self.base += drop
@@ -358,17 +498,29 @@ class AudioWindowBuffer:
     """Samples of one stream, pushed in arbitrary pieces, handed back as the sample windows of chunked decoding: the
     sample-domain twin of serve.WindowBuffer.  Window n starts at sample 160 * 4 c n and holds the (4 c + 2) * 160 + 400
     samples of feature frames [4 c n, 4 c n + 4 c + 3).  With another sample_rate or channels > 1 the constructor hands out
-    a ResampledWindowBuffer instead, which keeps the input-rate samples."""
+    a ResampledWindowBuffer instead, which keeps the input-rate samples.
 
-    def __new__(cls, chunk, dtype=torch.int16, sample_rate=SAMPLE_RATE, channels=1):
+    context=R > 0, for a front end with delta features (DeltaFbank, R = order * window): a delta frame exists once its R frames
+    of lookahead do, or the stream has ended, so ready() counts F - R of the F frames there are until then.  take() hands back
+    the samples of static frames [s0, s1), s0 = max(4 c n - R, 0), s1 = min(4 c n + v + R, F), and leaves in self.lead the
+    4 c n - s0 frames in front that are context only: 0 for the first window of a segment, R later (fewer while 4 c n < R).
+    The window then holds up to (4 c + 2 + 2 R) * 160 + 400 samples, and the buffer keeps its samples from frame
+    max(4 c (n + 1) - R, 0) on.  After rebase() the segment is a fresh stream: no context in front of the cut."""
+
+    def __new__(cls, chunk, dtype=torch.int16, sample_rate=SAMPLE_RATE, channels=1, context=0):
         if cls is AudioWindowBuffer and (int(sample_rate) != SAMPLE_RATE or int(channels) != 1):
-            return ResampledWindowBuffer(chunk, dtype, sample_rate, channels)
+            return ResampledWindowBuffer(chunk, dtype, sample_rate, channels, context)
         return super().__new__(cls)
 
-    def __init__(self, chunk, dtype=torch.int16, sample_rate=SAMPLE_RATE, channels=1):
+    context = 0       # frames of context on either side (an instance field only where it is not 0: the plain buffer keeps its fields)
+    lead = 0          # frames of context in front of the window take() handed out last
+
+    def __init__(self, chunk, dtype=torch.int16, sample_rate=SAMPLE_RATE, channels=1, context=0):
         self.c = int(chunk)
+        if _checked_context(context):
+            self.context = int(context)
         self.hop = FRAME_SHIFT * 4 * self.c
-        self.window = (4 * self.c + 2) * FRAME_SHIFT + FRAME_LENGTH
+        self.window = (4 * self.c + 2 + 2 * self.context) * FRAME_SHIFT + FRAME_LENGTH
         self.dtype = dtype
         self.buf = torch.zeros(0, dtype=dtype)        # samples from sample self.base on
         self.base = 0
@@ -400,7 +552,8 @@ class AudioWindowBuffer:
 
     def ready(self):
         """Real FRAMES of the next window if it can run now, else 0 (the rule of serve.next_window_valid on frame counts)."""
-        return next_window_valid(num_frames(self.total), self.chunks, self.c, self.ended)
+        frames = num_frames(self.total)
+        return next_window_valid(frames if self.ended else max(frames - self.context, 0), self.chunks, self.c, self.ended)
 
     def drained(self):
         """The stream has ended and no further window will run."""
@@ -408,16 +561,20 @@ class AudioWindowBuffer:
 
     def take(self, out=None):
         """The next window as (samples (window,) zero filled behind the real ones, count of real samples); advances by one
-        chunk.  num_frames(count) is what ready() returned."""
-        if self.ready() == 0:
+        chunk.  num_frames(count) is what ready() returned -- with context > 0, that plus the frames of context in front
+        (self.lead after the call) and behind."""
+        v = self.ready()
+        if v == 0:
             raise ValueError("no window ready")
-        start = self.hop * self.chunks - self.base
-        real = min(self.total - self.hop * self.chunks, self.window)
+        frames = num_frames(self.total)
+        s0, s1, self.lead = _context_window(frames, self.chunks, self.c, v, self.context)
+        start = FRAME_SHIFT * s0 - self.base
+        real = min(self.total - FRAME_SHIFT * s0 if s1 == frames else FRAME_SHIFT * (s1 - s0 - 1) + FRAME_LENGTH, self.window)
         win = torch.zeros(self.window, dtype=self.dtype) if out is None else out
         win.zero_()
         win[:real] = self.buf[start:start + real]
         self.chunks += 1
-        drop = self.hop * self.chunks - self.base       # samples left of the next window are never read again
+        drop = FRAME_SHIFT * max(4 * self.c * self.chunks - self.context, 0) - self.base   # samples left of the next window are never read again
         if drop > 0:
             self.buf = self.buf[min(drop, self.buf.shape[0]):]
             self.base += drop

@@ -451,6 +451,39 @@ def _conv1_desc(feat, w9c, bias, act=_lib.ACT_RELU, cmvn=None, out=None, feat_le
     return d, out
 
 
+def _conv1_ch_desc(feat, w9c, bias, in_ch=1, act=_lib.ACT_RELU, cmvn=None, out=None, feat_len=None, lens_out=None, out_bf16=False):
+    """m3_conv1_ch_desc: feat (B, T, idim) read as in_ch blocks of idim / in_ch bins, w9c [in_ch * 9][C]"""
+    B, T, idim = feat.shape
+    Cc = w9c.shape[1]
+    if out is None:
+        out = torch.empty(B, (T - 3) // 2 + 1, (idim // max(int(in_ch), 1) - 3) // 2 + 1, Cc,
+                          dtype=torch.bfloat16 if out_bf16 else torch.float32, device=feat.device)
+    d = _lib.Conv1ChDesc()
+    d.feat, d.w9c, d.bias, d.out = _f32(feat).value, _f32(w9c).value, _f32(bias).value, out.data_ptr()
+    if cmvn is not None:
+        d.cmvn_mean, d.cmvn_istd = _f32(cmvn[0]).value, _f32(cmvn[1]).value
+    d.B, d.T, d.idim, d.C, d.act, d.in_ch, d.out_bf16 = B, T, idim, Cc, int(act), int(in_ch), int(out.dtype == torch.bfloat16)
+    if feat_len is not None:
+        d.feat_len, d.lens_out = _i32(feat_len).value, _i32(lens_out).value
+    return d, out
+
+
+def subsample_conv1_ch(feat, w9c, bias, in_ch, **kw):
+    """the first conv with in_ch input channels (m3_subsample_conv1_ch): feat (B, T, idim) -> channel-last (B, T1, F1, C) with
+    F1 counted on idim / in_ch; optionally act, cmvn = (mean, istd), out (float32 or bfloat16), out_bf16, feat_len + lens_out"""
+    d, out = _conv1_ch_desc(feat, w9c, bias, in_ch, **kw)
+    check(_lib.load().m3_subsample_conv1_ch(C.byref(d), _stream()), "m3_subsample_conv1_ch")
+    return out
+
+
+def subsample_conv1_ch_pair(a, b):
+    """two such convs on one input shape with one in_ch in one launch (m3_subsample_conv1_ch_pair); a / b: the keyword
+    arguments of subsample_conv1_ch (feat_len + lens_out on a only)"""
+    (da, oa), (db, ob) = _conv1_ch_desc(**a), _conv1_ch_desc(**b)
+    check(_lib.load().m3_subsample_conv1_ch_pair(C.byref(da), C.byref(db), _stream()), "m3_subsample_conv1_ch_pair")
+    return oa, ob
+
+
 def subsample_conv1_pair(a, b):
     """two first convs on inputs of one shape in one launch (m3_subsample_conv1_pair).  Keys of a / b: feat, w9c, bias and
     optionally act, cmvn = (mean, istd), out, feat_len + lens_out (a only)."""

@@ -54,9 +54,9 @@ def slice_major_w2(t):
 
 
 def _pack_subsampling(sd, p, out):
-    w0 = sd[p + "conv.0.weight"]                         # (C,1,3,3)
+    w0 = sd[p + "conv.0.weight"]                         # (C,in_ch,3,3) -> [in_ch * 9][C], row ch * 9 + kh * 3 + kw
     C = w0.shape[0]
-    out[p + "conv.0.weight_9c"] = w0.reshape(C, 9).t().contiguous()
+    out[p + "conv.0.weight_9c"] = w0.reshape(C, w0.shape[1] * 9).t().contiguous()
     out[p + "conv.0.bias"] = sd[p + "conv.0.bias"]
     out[p + "conv.2.weight_ohwi"] = sd[p + "conv.2.weight"].permute(0, 2, 3, 1).contiguous()
     out[p + "conv.2.bias"] = sd[p + "conv.2.bias"]

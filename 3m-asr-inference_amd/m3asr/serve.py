@@ -18,6 +18,12 @@ float32 in the int16 range).  step() gathers the live slots' sample windows into
 runs the log-Mel front end (m3asr.frontend.Fbank, one launch on the engine stream) straight into the encoder's window
 buffer; the chunk itself is the same graph replay as in feature mode.
 
+Delta features: when the engine's config has delta_order > 0 the front end is an m3asr.frontend.DeltaFbank and every
+session's buffer keeps R = delta_order * delta_window frames of context: a window also carries up to R static frames in front
+of and behind the frames it produces, and a frame is produced once its R frames of lookahead have arrived (or the stream has
+ended).  That is R * 10 ms of added latency, one more launch per step and no host round trip; the frames are those of the
+whole utterance featurised at once.
+
 Audio at another rate or with several channels, `StreamPool(decoder, audio=True, sample_rate=44100, channels=2)`: the
 sessions push interleaved samples in that format and step() resamples on the device (m3asr.frontend.Resampler, Kaldi's
 LinearResample, one more launch) before the front end; a session's 16 kHz samples do not depend on how it was cut.
@@ -141,7 +147,8 @@ class StreamPool:
     (B,))`, `reset(slots=[...])`, `partial(slots=[...])`, `finish(slots=[...])`; B, chunk and input_dim are read from
     `decoder.st` unless given.  audio=True: the sessions are fed samples (push_audio) and step() featurises them on the device;
     fbank: the front end, `fbank(pcm (B, n) int16, n_samples (B,), out=, out_len=, stream=)` (default: an
-    m3asr.frontend.Fbank for input_dim on the engine's device).  sample_rate / channels / channel (audio=True): what the
+    m3asr.frontend.Fbank for input_dim on the engine's device; a DeltaFbank when the engine's config has delta_order > 0, or
+    any front end with a `context` attribute: it is then also passed lead= and n_out=).  sample_rate / channels / channel (audio=True): what the
     sessions push, one format per pool; unless they are 16000 / 1 / -1 every step() first runs ONE launch of `resampler`
     (default: an m3asr.frontend.Resampler for them on the engine's device; channel = -1: the mean of all channels, k: channel
     k alone) that turns the live slots' input spans into their 16 kHz float32 windows on the device, which the front end reads.
@@ -222,7 +229,8 @@ class StreamPool:
         span of a window (pinned, then device) and ONE index block (in0, out0 int64; n_in, n_out int32) that goes up in one
         copy; the resampler writes the 16 kHz windows as float32 into res_dev, which the front end reads."""
         from .frontend import AudioWindowBuffer, Resampler
-        self._new_audio_buffer = lambda: AudioWindowBuffer(self.c, sample_rate=self.sample_rate, channels=self.channels)
+        self._new_audio_buffer = lambda: AudioWindowBuffer(self.c, sample_rate=self.sample_rate, channels=self.channels,
+                                                           context=self.context)
         eng = getattr(st, "eng", None)
         dev = eng.device if eng is not None else torch.device("cpu")
         pin = dev.type == "cuda"
@@ -241,18 +249,23 @@ class StreamPool:
         return idx[:B], n[:B], idx[B:2 * B], n[B:]
 
     def _init_audio(self, st, fbank):
-        from .frontend import AudioWindowBuffer, Fbank
-        self._new_audio_buffer = lambda: AudioWindowBuffer(self.c)
+        from .frontend import AudioWindowBuffer, Fbank, make_frontend
         eng = getattr(st, "eng", None)
-        self.fbank = fbank if fbank is not None else Fbank(self.idim, eng.device)
+        if fbank is None:
+            fbank = make_frontend(eng.cfg, eng.device) if getattr(eng, "cfg", None) is not None else Fbank(self.idim, eng.device)
+        self.fbank = fbank
+        self.context = int(getattr(fbank, "context", 0))        # frames of context a delta front end reads on either side
+        self._new_audio_buffer = lambda: AudioWindowBuffer(self.c, context=self.context)
         self.stream = eng.stream if eng is not None else None
         dev = eng.device if eng is not None else torch.device("cpu")
         pin = dev.type == "cuda"
         self.window_samples = self._new_audio_buffer().window
         self.pcm_win = torch.zeros(self.B, self.window_samples, dtype=torch.int16, pin_memory=pin)
-        self.n_real = torch.zeros(self.B, dtype=torch.int32, pin_memory=pin)
+        # per slot: real samples | frames of context in front | frames to produce -- one upload
+        self.counts = torch.zeros(3, self.B, dtype=torch.int32, pin_memory=pin)
+        self.counts_dev = torch.zeros(3, self.B, dtype=torch.int32, device=dev)
+        self.n_real, self.n_real_dev = self.counts[0], self.counts_dev[0]
         self.pcm_dev = torch.zeros(self.B, self.window_samples, dtype=torch.int16, device=dev)
-        self.n_real_dev = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self.feat_len_dev = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self.feat = st.feat if st is not None else self.win      # where the frames land: the encoder's own window buffer
         self.uploaded = torch.cuda.Event() if pin else None     # the pinned buffers may be refilled once this has passed
@@ -396,13 +409,13 @@ class StreamPool:
         if self.uploaded is not None:
             self.uploaded.synchronize()
         valid = torch.zeros(self.B, dtype=torch.int32)
-        self.n_real.zero_()
+        self.counts.zero_()
         live = []
         for sid, (b, ab) in self.streams.items():
             v = ab.ready()
             if v > 0:
                 _, n = ab.take(out=self.pcm_win[b])
-                self.n_real[b] = n
+                self.counts[0, b], self.counts[1, b], self.counts[2, b] = n, ab.lead, v
                 valid[b] = v
                 live.append(sid)
         if not live:
@@ -410,17 +423,26 @@ class StreamPool:
         if self.stream is not None:
             with torch.cuda.stream(self.stream):
                 self.pcm_dev.copy_(self.pcm_win, non_blocking=True)
-                self.n_real_dev.copy_(self.n_real, non_blocking=True)
+                self.counts_dev.copy_(self.counts, non_blocking=True)
                 self.uploaded.record(self.stream)
         else:
             self.pcm_dev.copy_(self.pcm_win)
-            self.n_real_dev.copy_(self.n_real)
-        self.fbank(self.pcm_dev, self.n_real_dev, out=self.feat, out_len=self.feat_len_dev, stream=self.stream)
+            self.counts_dev.copy_(self.counts)
+        self._featurise(self.pcm_dev, self.n_real_dev)
         self.dec.step(self.feat, valid)
         self.steps += 1
         if self.segment:
             self._cut(live)
         return live
+
+    def _featurise(self, pcm_dev, n_dev):
+        """The front-end launch(es) of a step into the encoder's window buffer; with delta features the windows carry
+        counts_dev[1] frames of context in front and counts_dev[2] frames are produced."""
+        if self.context > 0:
+            self.fbank(pcm_dev, n_dev, out=self.feat, out_len=self.feat_len_dev, stream=self.stream, lead=self.counts_dev[1],
+                       n_out=self.counts_dev[2])
+        else:
+            self.fbank(pcm_dev, n_dev, out=self.feat, out_len=self.feat_len_dev, stream=self.stream)
 
     def _step_resampled(self):
         """step() of a pool fed samples at another rate: the live slots' input spans and the index block go up, ONE resampler
@@ -431,13 +453,15 @@ class StreamPool:
             self.uploaded.synchronize()
         valid = torch.zeros(self.B, dtype=torch.int32)
         self.idx.zero_()
+        self.counts.zero_()
         in0, n_in, out0, n_out = self._index_views(self.idx)
         live = []
         for sid, (b, ab) in self.streams.items():
             v = ab.ready()
             if v > 0:
                 _, in0[b], n_in[b], out0[b], n_out[b] = ab.take(out=self.span_win[b, :ab.span * self.channels])
-                assert num_frames(int(n_out[b])) == v
+                assert num_frames(int(n_out[b])) >= v and (self.context > 0 or num_frames(int(n_out[b])) == v)
+                self.counts[1, b], self.counts[2, b] = ab.lead, v
                 valid[b] = v
                 live.append(sid)
         if not live:
@@ -446,13 +470,16 @@ class StreamPool:
             with torch.cuda.stream(self.stream):
                 self.span_dev.copy_(self.span_win, non_blocking=True)
                 self.idx_dev.copy_(self.idx, non_blocking=True)
+                if self.context > 0:
+                    self.counts_dev.copy_(self.counts, non_blocking=True)
                 self.uploaded.record(self.stream)
         else:
             self.span_dev.copy_(self.span_win)
             self.idx_dev.copy_(self.idx)
+            self.counts_dev.copy_(self.counts)
         d_in0, d_n_in, d_out0, d_n_out = self._index_views(self.idx_dev)
         self.resampler.launch(self.span_dev, d_in0, d_n_in, d_out0, d_n_out, self.res_dev, stream=self.stream)
-        self.fbank(self.res_dev, d_n_out, out=self.feat, out_len=self.feat_len_dev, stream=self.stream)
+        self._featurise(self.res_dev, d_n_out)
         self.dec.step(self.feat, valid)
         self.steps += 1
         if self.segment:

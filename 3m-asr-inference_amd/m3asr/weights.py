@@ -40,12 +40,12 @@ def encoder_param_shapes(cfg, ep_slice=True):
     K = cfg.cnn_module_kernel
     sh = OrderedDict()
 
-    def subsampling(p, d):
-        sh[p + "conv.0.weight"] = (d, 1, 3, 3)
+    def subsampling(p, d, in_ch, sub_freq):
+        sh[p + "conv.0.weight"] = (d, in_ch, 3, 3)
         sh[p + "conv.0.bias"] = (d,)
         sh[p + "conv.2.weight"] = (d, d, 3, 3)
         sh[p + "conv.2.bias"] = (d,)
-        sh[p + "out.0.weight"] = (d, d * cfg.sub_freq)
+        sh[p + "out.0.weight"] = (d, d * sub_freq)
         sh[p + "out.0.bias"] = (d,)
 
     def norm(p, d):
@@ -85,7 +85,7 @@ def encoder_param_shapes(cfg, ep_slice=True):
         sh[p + "concat_linear.bias"] = (d,)
 
     De = cfg.embed_dim
-    subsampling("embed.subsampling.", De)
+    subsampling("embed.subsampling.", De, cfg.embed_conv_subsample_in_ch, cfg.embed_sub_freq)
     norm("embed.after_norm.", De)
     for i in range(cfg.embed_blocks):
         p = "embed.blocks.%d." % i
@@ -97,7 +97,7 @@ def encoder_param_shapes(cfg, ep_slice=True):
     sh["embed.out_linear.weight"] = (V, De)
     sh["embed.out_linear.bias"] = (V,)
 
-    subsampling("subsampling.", D)
+    subsampling("subsampling.", D, cfg.conv_subsample_in_ch, cfg.sub_freq)
     norm("after_norm.", D)
     norm("after_norm_6.", D)
     norm("after_norm_12.", D)

@@ -58,8 +58,8 @@ def _dtype(nh):
 
 def emit_subsampling(nh, sd, p, x, x_len):
     """Conv2dSubsampling4.forward (layer/subsampling.py:103-145)."""
-    layer = nh.network.add_shuffle(x)                       # (B,T,idim) -> (B,1,T,idim), trans_3d_to_4d_trt :29-36
-    layer.reshape_dims = (0, 0, 1, -1)
+    layer = nh.network.add_shuffle(x)                       # (B,T,idim) -> (B,in_ch,T,idim/in_ch), trans_3d_to_4d_trt :29-36
+    layer.reshape_dims = (0, 0, int(sd[p + "conv.0.weight"].shape[1]), -1)
     layer.second_transpose = (0, 2, 1, 3)
     nh.set_layer_name(layer, "trans_3d_to_4d")
     x = layer.get_output(0)

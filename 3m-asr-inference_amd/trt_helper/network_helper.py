@@ -294,6 +294,14 @@ class NetworkHelper:
             if wp is None:
                 wp = self._const_cache[key] = w.reshape(O, 9).t().contiguous().to(self.device)
             y = ops.subsample_conv1(x.reshape(x.shape[0], x.shape[2], x.shape[3]).contiguous(), wp, b, act=_lib.ACT_NONE)
+        elif I <= 3 and I != O:
+            # the first conv of a subsampler with conv_subsample_in_ch = I: (B,I,T,Fc) -> frames of I blocks of Fc bins
+            key = ("c1", w.data_ptr())
+            wp = self._const_cache.get(key)
+            if wp is None:
+                wp = self._const_cache[key] = w.reshape(O, I * 9).t().contiguous().to(self.device)
+            rows = ops.permute_copy(x, (0, 2, 1, 3)).reshape(x.shape[0], x.shape[2], I * x.shape[3])
+            y = ops.subsample_conv1_ch(rows, wp, b, I, act=_lib.ACT_NONE)
         else:
             key = ("c2", w.data_ptr())
             wp = self._const_cache.get(key)

@@ -90,10 +90,16 @@ def build_trt(model, args, input_dim, plan_name, prior=None, profile=None, decod
 def main(args):
     with open(args.config, "r") as f:
         configs = yaml.load(f, Loader=yaml.SafeLoader)
-    configs["input_dim"] = 40                                           # reference builder.py:124
+    if not 0 <= args.add_deltas <= 2 or not 1 <= args.delta_window <= 4:
+        raise SystemExit("--add-deltas must be 0, 1 or 2 and --delta-window 1 to 4")
+    # 40 mel bins (reference builder.py:124); with the loader's add_deltas the model reads static | delta | delta-delta
+    configs["input_dim"] = 40 * (1 + args.add_deltas)
     nnet_module = importlib.import_module("model." + configs.get("nnet_proto"))
     input_dim, output_dim = configs["input_dim"], configs["output_dim"]
     model = nnet_module.Net(input_dim, output_dim, **configs["model_conf"])
+    if args.add_deltas:                             # travels in the plan's config: infer.py -w then computes the deltas too
+        import dataclasses
+        model.encoder.cfg = dataclasses.replace(model.encoder.cfg, delta_order=args.add_deltas, delta_window=args.delta_window)
     # checkpoints are tensors-only state_dicts: never unpickle arbitrary objects
     param_dict = torch.load(args.load_path, map_location="cpu", weights_only=True)
     model.load_state_dict(param_dict)
@@ -121,6 +127,9 @@ if __name__ == "__main__":
     p.add_argument("-o", "--output", required=True, help="The plan file to write")
     p.add_argument("-c", "--config", required=True, help="config file")
     p.add_argument("-prior", "--prior_file", required=False, help="prior file")
+    p.add_argument("--add-deltas", type=int, default=0, help="the loader's add_deltas the model was trained with (0, 1 or 2): "
+                   "input_dim = 40 * (1 + N) columns, static | delta | delta-delta")
+    p.add_argument("--delta-window", type=int, default=2, help="the loader's delta_window (1 to 4)")
     p.add_argument("-cmvn", "--cmvn_file", required=False, help="global CMVN stats (Kaldi text matrix or 2xD .npy); fused into the first conv")
     p.add_argument("--log-softmax", dest="log_softmax", action="store_true",
                    help="output log_softmax(logits) (- log prior) instead of raw logits (reference builder.py:77-81)")

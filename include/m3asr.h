@@ -475,6 +475,22 @@ typedef struct m3_conv1_desc {
   const int32_t* feat_len; int32_t* lens_out;
 } m3_conv1_desc;
 int m3_subsample_conv1_pair(const m3_conv1_desc* a, const m3_conv1_desc* b, m3_stream stream);
+/* The first conv with input channels (conv_subsample_in_ch of the reference, layer/subsampling.py:23-36: (B, T, idim) viewed as
+ * (B, in_ch, T, idim / in_ch) -- e.g. static | delta | delta-delta blocks as three image channels of Conv2d(in_ch, C, 3, 2)).
+ * m3_conv1_ch_desc is m3_conv1_desc plus in_ch (1..3, idim % in_ch == 0, Fc = idim / in_ch >= 3) and out_bf16 (!= 0: out
+ * holds bf16).  idim stays the row width of feat and of cmvn_mean / cmvn_istd; w9c is [in_ch * 9][C] with row ch * 9 + kh * 3 +
+ * kw (the (C, in_ch, 3, 3) weight reshaped to (C, in_ch * 9) and transposed); out is [B][T1][F1][C] with F1 = (Fc - 3) / 2 + 1.
+ * in_ch = 1 is m3_subsample_conv1_cmvn / m3_conv2d_3x3s2_first bit for bit.  m3_subsample_conv1_ch_pair: the two problems also
+ * share in_ch, or the call is refused (run two launches). */
+typedef struct m3_conv1_ch_desc {
+  const float* feat; const float* w9c; const float* bias; const float* cmvn_mean; const float* cmvn_istd;
+  int32_t B, T, idim, C, act;
+  float* out;
+  const int32_t* feat_len; int32_t* lens_out;
+  int32_t in_ch, out_bf16;
+} m3_conv1_ch_desc;
+int m3_subsample_conv1_ch(const m3_conv1_ch_desc* d, m3_stream stream);
+int m3_subsample_conv1_ch_pair(const m3_conv1_ch_desc* a, const m3_conv1_ch_desc* b, m3_stream stream);
 
 /* Front / back end of the acoustic score.  Global CMVN: y = (x - mean[d]) * istd[d] on frames
  * t < len[b] (the reference's unfinished CmvnPlugin, incomplete_plugin/cmvn_plugin/cmvn_plugin.cu:17-43).
@@ -955,6 +971,36 @@ int m3_fbank_tables_init(int num_mel_bins, float sample_rate, float low_freq, fl
 int m3_fbank_num_frames(int n_samples);
 int m3_fbank(const void* tables, const void* pcm, int pcm_is_int16, int ld_pcm, const int32_t* n_samples, int B, int T,
              int num_mel_bins, float* feat, int ld_feat, int32_t* feat_len_out, m3_stream stream);
+
+/* Delta features in: Kaldi's DeltaFeatures (add-deltas, feat/feature-functions.cc) on the device (csrc/deltas.hip, DESIGN.md
+ * 32): static frames -> static | delta | delta-delta, the columns a model trained with the loader's add_deltas reads.
+ * scales_0 = [1], scales_i = conv(scales_{i-1}, [-W..W]) / sum_j j^2 (2 i W + 1 taps); block i of output frame t of row b is
+ *     sum_{j = -iW..iW} scales_i[j] x[clamp(lead[b] + t + j, 0, n_in[b] - 1)]
+ * -- the clamp is on the COMPOSITE filter's taps on the static frames (Kaldi's edge replication; iterating a first-order delta
+ * with replicate padding gives other values in the first and last W frames).  order in {1, 2}, window W in [1, 4], so the
+ * context is R = order * W <= M3_DELTAS_MAX_CONTEXT frames; anything else is refused.  Tables are built on the HOST in float64
+ * and rounded once to float32.
+ * m3_deltas_tables_host: host-only, needs no device.  scales: (order + 1) rows of 2 * M3_DELTAS_MAX_CONTEXT + 1 floats, row i
+ *   holds scales_i[j] at column M3_DELTAS_MAX_CONTEXT + j and zeros elsewhere.
+ * m3_add_deltas: ONE launch for a ragged batch.  feat (B, T_in, ld_feat) float32 with row stride ld_feat >= bins and batch
+ *   stride batch_stride_feat (floats), 1 <= bins <= 256.  Device vectors of B int32: n_in = static frames present (clamped to
+ *   [0, T_in]); lead (nullable = 0) = frames in front that are context only (clamped to [0, n_in]); n_out = frames to
+ *   produce, clipped to n_in - lead and to T_out.  Output frame t is the filter centred on input frame lead + t: offline is
+ *   lead = 0, n_out = n_in; in a streaming window real history and lookahead are used where the window holds them, and where
+ *   it starts or ends at the utterance's edge the clamp is Kaldi's.  out (B, T_out, ld_out) float32, ld_out >= (order + 1) *
+ *   bins, batch stride batch_stride_out: columns [0, bins) get the static frame bit for bit, [i bins, (i + 1) bins) block i;
+ *   frames t >= n_out[b] are written as ZEROS; columns >= (order + 1) * bins are not touched.  out_len (nullable) [B] int32
+ *   receives the clipped n_out.  IN-PLACE form: out == feat with equal strides and lead == NULL leaves the static columns
+ *   alone and writes the delta columns only (m3_fbank writes an engine input buffer, this fills in beside it); any other
+ *   overlap of out and feat is the caller's error, out == feat otherwise is refused.  16-byte accesses are used when bins,
+ *   all four strides and both pointers are multiples of 4 floats.  Each value is one fp32 fma chain from 0 over its taps in
+ *   ascending j and depends on its taps and the table only -- not on B, T_out, lead or which path ran -- so a stream computed
+ *   window by window equals the utterance computed at once.  B == 0 or T_out == 0 launches nothing. */
+#define M3_DELTAS_MAX_CONTEXT 8
+int m3_deltas_tables_host(int order, int window, float* scales);
+int m3_add_deltas(const float* feat, int ld_feat, int64_t batch_stride_feat, int T_in, const int32_t* n_in, const int32_t* lead,
+                  const int32_t* n_out, int B, int T_out, int bins, int order, int window, float* out, int ld_out,
+                  int64_t batch_stride_out, int32_t* out_len, m3_stream stream);
 
 /* Audio in at any sample rate: Kaldi's LinearResample on the device (csrc/resample.hip) -- what
  * compute-fbank-feats does (ResampleWaveform) when a wave's rate is not the feature rate.  With ri = rate_in, ro = rate_out,

@@ -8,7 +8,8 @@ feat.npy is (B,T,idim) float32; feat_len = feat.shape[1] for every utterance, as
 speech.wav (-w, instead of -i) is a 16-bit PCM RIFF file at any sample rate from 1 to 384 kHz with up to 8 channels; unless
 it is 16 kHz mono it is first resampled on the device as Kaldi's compute-fbank-feats would (m3asr.frontend.Resampler;
 --channel K takes channel K alone, the default is the mean of all channels).  Its log-Mel frames are computed on the device by
-the library's Kaldi-style front end (m3asr.frontend.Fbank with the plan's input_dim mel bins) and run as a batch of one.
+the library's Kaldi-style front end (m3asr.frontend.Fbank with the plan's mel bins, and Kaldi's add-deltas behind it for a plan
+built with builder.py --add-deltas) and run as a batch of one.
 Prints ``time=...ms`` for one forward after a warm-up and the output's shape / sum (reference :81-103).
 
     python3 infer.py -p encoder.plan -w speech.wav --hotwords words.txt [--hotword-score 3.0] [--beam 10]
@@ -70,14 +71,15 @@ def read_wav(path):
         return pcm.reshape(1, -1, w.getnchannels()), w.getframerate(), w.getnchannels()
 
 
-def wav_features(path, channel, input_dim, device):
-    """The wav's log-Mel frames (1, T, input_dim), computed on the device; resampled there first unless it is 16 kHz mono."""
+def wav_features(path, channel, cfg, device):
+    """The wav's feature frames (1, T, input_dim), computed on the device: log-Mel, with Kaldi's add-deltas behind it when the
+    plan's config says the model was trained on delta features; resampled there first unless it is 16 kHz mono."""
     from m3asr._lib import M3Error
-    from m3asr.frontend import Fbank, Resampler
+    from m3asr.frontend import make_frontend, Resampler
     pcm, rate, channels = read_wav(path)
     if not -1 <= channel < channels:
         raise SystemExit("%s: --channel %d, the file has %d channel(s)" % (path, channel, channels))
-    fb = Fbank(input_dim, device)
+    fb = make_frontend(cfg, device)
     if (rate, channels) == (16000, 1):
         return fb(pcm[:, :, 0])[0]
     try:
@@ -216,7 +218,7 @@ def main(args):
     logger = trt_helper.init_trt_plugin(trt.Logger.INFO, "libm3asr_hip.so")
     helper = trt_helper.InferHelper(args.plan_name, logger)
     if args.wav_file:
-        feat = wav_features(args.wav_file, args.channel, helper.cfg.input_dim, helper.engine.device).cpu().numpy()
+        feat = wav_features(args.wav_file, args.channel, helper.cfg, helper.engine.device).cpu().numpy()
     else:
         feat = np.load(args.input_file).astype(np.float32)
     feat_len = np.full((1, feat.shape[0]), feat.shape[1], dtype=np.int32)

@@ -2,7 +2,9 @@
 """Write a synthetic checkpoint + yaml config in the reference's formats (the real ones are not shipped,
 README.md:6,13): ``python tools/make_synthetic_checkpoint.py --out-dir /tmp/m3 [--tiny] [--layers 18] [--decoder-blocks N [--r-decoder-blocks M]]``.
 --decoder-blocks adds the attention decoder of a joint CTC/attention model (`decoder.*`; with --r-decoder-blocks a
-BiTransformerDecoder's left_decoder / right_decoder)."""
+BiTransformerDecoder's left_decoder / right_decoder).  --add-deltas N: a model trained on the loader's delta features, 40 * (1 + N)
+input columns (build it with builder.py --add-deltas N); --in-ch / --embed-in-ch: conv_subsample_in_ch of the main / embed
+subsampler (e.g. 3 with --add-deltas 2: static | delta | delta-delta as image channels)."""
 import argparse
 import os
 import sys
@@ -28,6 +30,15 @@ def reference_yaml(cfg, dcfg=None):
 
 
 def _encoder_yaml(cfg):
+    y = _encoder_yaml_base(cfg)
+    if cfg.conv_subsample_in_ch != 1:
+        y["model_conf"]["encoder_conf"]["conv_subsample_in_ch"] = cfg.conv_subsample_in_ch
+    if cfg.embed_conv_subsample_in_ch != 1:
+        y["model_conf"]["encoder_conf"]["embed_conf"]["conv_subsample_in_ch"] = cfg.embed_conv_subsample_in_ch
+    return y
+
+
+def _encoder_yaml_base(cfg):
     return {"nnet_proto": "conformer_aed_fmoe_localComm_catEmbed_domain_acc_hier", "output_dim": cfg.output_dim,
             "model_conf": {"encoder_conf": {
                 "attention_heads": cfg.attention_heads, "attention_dim": cfg.attention_dim, "num_blocks": cfg.num_blocks,
@@ -47,8 +58,13 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--decoder-blocks", type=int, default=0, help="add an attention decoder of this many blocks")
     ap.add_argument("--r-decoder-blocks", type=int, default=0, help="and a right-to-left decoder of this many blocks")
+    ap.add_argument("--add-deltas", type=int, default=0, help="delta order of the features: 40 * (1 + N) input columns")
+    ap.add_argument("--in-ch", type=int, default=1, help="conv_subsample_in_ch of the main encoder's subsampler")
+    ap.add_argument("--embed-in-ch", type=int, default=1, help="conv_subsample_in_ch of the embed encoder's subsampler")
     a = ap.parse_args()
-    cfg = EncoderConfig.tiny() if a.tiny else EncoderConfig(num_blocks=a.layers)
+    front = dict(input_dim=40 * (1 + a.add_deltas), delta_order=a.add_deltas, conv_subsample_in_ch=a.in_ch,
+                 embed_conv_subsample_in_ch=a.embed_in_ch)
+    cfg = EncoderConfig.tiny(**front) if a.tiny else EncoderConfig(num_blocks=a.layers, **front)
     os.makedirs(a.out_dir, exist_ok=True)
     sd = {"encoder." + k: v for k, v in make_weights(cfg, seed=a.seed).items()}
     dcfg = None
