@@ -32,6 +32,19 @@
 //
 // Prune copies the survivors' (lm_state', lm') from the scratch: nothing is walked twice.  An utterance whose lm_on is 0 (or
 // whose image fails lm_view) adds nothing: its keys, parts, records and scorer states are the joint step's bits.
+//
+// HOTWORD BIASING (m3_aed_bias_*).  A third template flag: <CTC, LM, CTX>.  With CTX every candidate also takes one arc
+// of its utterance's context graph (kernels.h ctx_graph_view; the image, its compiler and its validator are the CTC search's) and
+//   key = jkey + (float)extra,   extra = (alpha lm' + beta n') + bonus' with an LM, bonus' without,   in double, rounded once.
+// A token adds delta[state][cls[token]] and moves to next[state][..]; eos hands back pot[state] and ends in state 0.  The four
+// CTX = false instantiations are the code they were.  Two more blobs, sized by B, beam and pre_beam alone:
+//
+//   context state (int32 words), per row, double-buffered like the records:  [ ctx_state, att, bonus (double, 2 words) ]
+//     att is kept here only by the <false, false, true> form, which has neither a scorer state nor an LM state to keep it in.
+//   context scratch: [R][K] of [ ctx_state', 0, bonus' (double) ], then [R][K][4] candidate records of the <false, false, true> form.
+//
+// Prune copies the survivors' (ctx_state', bonus') from the scratch.  An utterance whose graph_of is outside [0, G) (or whose
+// image fails ctx_graph_view or was built for another V) adds nothing and carries (0, 0.0) along.
 #include "aed_search_state.h"
 #include "kernels.h"
 
@@ -57,6 +70,20 @@ struct LmFuse {
   int32_t* lscr;           // LM scratch: score writes, prune reads
   double alpha, beta;
   int use_eos;
+};
+// hotword biasing: what the CTX instantiations take besides their NoLm / LmFuse, which they inherit as they are
+enum { CS_STATE = 0, CS_ATT = 1, CS_BONUS = 2, CS_WORDS = 4 };          // context state of a row's buffer; CS_BONUS: a double
+enum { CC_STATE = 0, CC_BONUS = 2, CC_WORDS = 4 };                      // context scratch of a candidate; CC_BONUS: a double
+struct CtxFuse {
+  const int32_t* image;    // the device context image and its words
+  long long words;
+  const int32_t* graph_of; // [B]
+  int32_t* cstate;         // context state: score reads buffer step & 1, prune writes the other
+  int32_t* cscr;           // context scratch: score writes, prune reads
+};
+template <class L>
+struct Biased : L {
+  CtxFuse cx;
 };
 
 int check_joint_desc(const m3_aed_joint_desc* d) {
@@ -232,7 +259,38 @@ __device__ __forceinline__ void lm_extend(const LmView& lm, int state, double su
   *out = sum + lm_walk(lm, ch, tok, next);
 }
 
-template <bool CTC, bool LM, class Lx>
+// CTX: the attention part of a row of the <false, false, true> form, which the context state keeps
+__device__ __forceinline__ float ctx_att(const CtxFuse& cx, int row, int buf) {
+  return __builtin_bit_cast(float, cx.cstate[((size_t)row * 2 + buf) * CS_WORDS + CS_ATT]);
+}
+// (ctx_state', bonus') of a hypothesis in `state` with the credit `bonus`, extended by tok.  `state` is the same for the whole wave
+// and is made uniform, so every lane gathers from ONE row of next / delta: cls[tok], then delta[state A + col] and next[state A + col].
+// eos is never walked: it hands back pot[state], the credit of a phrase the hypothesis did not complete, and ends in state 0.
+// No address is formed from an unchecked word: a stored state or a next entry outside [0, n_states) reads as state 0, a token
+// outside [0, V) or a cls entry outside [0, A) as column 0.
+__device__ __forceinline__ void ctx_extend(const CtxGraph& g, int state, double bonus, int tok, int eos, int* next, double* out) {
+  const int st0 = __builtin_amdgcn_readfirstlane(state >= 0 && state < g.n_states ? state : 0);
+  if (tok == eos) {
+    *next = 0;
+    *out = bonus - (double)g.pot[st0];
+    return;
+  }
+  int col = tok >= 0 && tok < g.V ? g.cls[tok] : 0;
+  col = col >= 0 && col < g.A ? col : 0;
+  const size_t arc = (size_t)st0 * g.A + col;
+  const int nx = g.next[arc];
+  *out = bonus + (double)g.delta[arc];
+  *next = nx >= 0 && nx < g.n_states ? nx : 0;
+}
+
+// the attention part a row starts from: the scorer state's, else the LM state's, else (CTX alone) the context state's
+template <bool CTC, bool LM, bool CTX, class Lx>
+__device__ __forceinline__ float row_att(const float* jr, const Lx& lx, int row, int buf) {
+  if constexpr (CTX && !CTC && !LM) return ctx_att(lx.cx, row, buf);
+  else return CTC ? jr[JS_ATT] : lm_att(lx, row, buf);
+}
+
+template <bool CTC, bool LM, bool CTX, class Lx>
 __global__ __launch_bounds__(64) void aed_joint_score_kernel(const int32_t* __restrict__ st, int B, int N, int P, int rec_words, int V,
                                                              int K, int F, const float* __restrict__ js, int32_t* __restrict__ cand,
                                                              float* __restrict__ scr, const float* __restrict__ logits, int ldl,
@@ -244,7 +302,7 @@ __global__ __launch_bounds__(64) void aed_joint_score_kernel(const int32_t* __re
   const int eos = V - 1;
   const int32_t* rec = as_record(st, B, rec_words, r, s & 1);
   const float* jr = CTC ? js_row(const_cast<float*>(js), F, r, s & 1) : nullptr;
-  const float att = CTC ? jr[JS_ATT] : lm_att(lx, r, s & 1), psi = CTC ? jr[JS_CTC] : 0.f;
+  const float att = row_att<CTC, LM, CTX>(jr, lx, r, s & 1), psi = CTC ? jr[JS_CTC] : 0.f;
   int32_t* crow = cand + ((size_t)r * K + lane) * JC_WORDS;       // lane j's candidate record (lanes below K)
   // LM only: the parent's (state, n, sum) as stored, lane j's scratch entry, and whether this utterance is fused at all
   [[maybe_unused]] int l_state = 0, l_n = 0;
@@ -260,6 +318,19 @@ __global__ __launch_bounds__(64) void aed_joint_score_kernel(const int32_t* __re
     lc = lx.lscr + ((size_t)r * K + lane) * LC_WORDS;
     fused = lx.lm_on[u] != 0 && lm_view(lx.image, lx.words, &lm) && lm.V == V;   // uniform
   }
+  // CTX only: the parent's (ctx_state, bonus) as stored, lane j's scratch entry, and the utterance's graph (one view per wave)
+  [[maybe_unused]] int c_state = 0;
+  [[maybe_unused]] double c_bonus = 0.0;
+  [[maybe_unused]] int32_t* cc = nullptr;
+  [[maybe_unused]] bool biased = false;
+  [[maybe_unused]] CtxGraph cg{};
+  if constexpr (CTX) {
+    const int32_t* cs = lx.cx.cstate + ((size_t)r * 2 + (s & 1)) * CS_WORDS;
+    c_state = cs[CS_STATE];
+    c_bonus = *reinterpret_cast<const double*>(cs + CS_BONUS);
+    cc = lx.cx.cscr + ((size_t)r * K + lane) * CC_WORDS;
+    biased = ctx_graph_view(lx.cx.image, lx.cx.words, lx.cx.graph_of[u], &cg) && cg.V == V;   // uniform
+  }
   if (rec[AS_FINISHED] != 0) {                                    // one candidate: increment 0, eos, the parts as they are
     if (lane < K) {
       crow[JC_TOK] = eos;
@@ -270,6 +341,11 @@ __global__ __launch_bounds__(64) void aed_joint_score_kernel(const int32_t* __re
         lc[LC_STATE] = lane == 0 ? l_state : 0;
         lc[LC_STATE + 1] = 0;
         *reinterpret_cast<double*>(lc + LC_LM) = lane == 0 ? l_sum : 0.0;
+      }
+      if constexpr (CTX) {                                        // ... and (ctx_state, bonus) as they are
+        cc[CC_STATE] = lane == 0 ? c_state : 0;
+        cc[CC_STATE + 1] = 0;
+        *reinterpret_cast<double*>(cc + CC_BONUS) = lane == 0 ? c_bonus : 0.0;
       }
     }
     return;
@@ -302,6 +378,12 @@ __global__ __launch_bounds__(64) void aed_joint_score_kernel(const int32_t* __re
   [[maybe_unused]] double l_new = l_sum;
   if constexpr (LM && (M3_AED_LM_WALK_FIRST || !CTC))
     if (fused) lm_extend(lm, l_state, l_sum, is_cand ? my_tok : eos, eos, lx.use_eos, &l_next, &l_new);   // idle lanes: no walk
+  // CTX: candidate j's arc from the parent's state, where the LM walk sits: ahead of the frame chain, whose time covers the two
+  // dependent gathers.  An utterance that is not biased carries (state, bonus) along as they are; idle lanes take no arc
+  [[maybe_unused]] int c_next = c_state;
+  [[maybe_unused]] double c_new = c_bonus;
+  if constexpr (CTX)
+    if (biased && is_cand) ctx_extend(cg, c_state, c_bonus, my_tok, eos, &c_next, &c_new);
   const int m = CTC ? usable_frames(hdr, F, x_rows) : 0, row0 = hdr[AS_MEM_ROW0];   // CTC = false: no frame, no chain
   const int last = s > 0 ? rec[AS_TOKENS + s] : -1;
   const int c = is_cand ? my_tok : 0;                             // idle lanes walk column 0: in bounds, their results unused
@@ -369,10 +451,25 @@ __global__ __launch_bounds__(64) void aed_joint_score_kernel(const int32_t* __re
       if (is_cand) key = att2;
     }
     if constexpr (LM) {                                           // two products and one sum in double, rounded once
-      if (fused && is_cand && key != -INFINITY) key = key + (float)(lx.alpha * l_new + lx.beta * (double)(l_n + 1));
+      if constexpr (!CTX)
+        if (fused && is_cand && key != -INFINITY) key = key + (float)(lx.alpha * l_new + lx.beta * (double)(l_n + 1));
       lc[LC_STATE] = is_cand ? l_next : 0;
       lc[LC_STATE + 1] = 0;
       *reinterpret_cast<double*>(lc + LC_LM) = is_cand ? l_new : 0.0;
+    }
+    if constexpr (CTX) {                                          // extra = (alpha lm' + beta n') + bonus' in double, rounded once
+      if (is_cand && key != -INFINITY) {
+        if constexpr (LM) {
+          if (fused && biased) key = key + (float)((lx.alpha * l_new + lx.beta * (double)(l_n + 1)) + c_new);
+          else if (fused) key = key + (float)(lx.alpha * l_new + lx.beta * (double)(l_n + 1));
+          else if (biased) key = key + (float)c_new;
+        } else {
+          if (biased) key = key + (float)c_new;
+        }
+      }
+      cc[CC_STATE] = is_cand ? c_next : 0;
+      cc[CC_STATE + 1] = 0;
+      *reinterpret_cast<double*>(cc + CC_BONUS) = is_cand ? c_new : 0.0;
     }
     crow[JC_TOK] = is_cand ? my_tok : eos;
     crow[JC_ATT] = __builtin_bit_cast(int32_t, is_cand ? att2 : -INFINITY);
@@ -386,7 +483,7 @@ __global__ __launch_bounds__(64) void aed_joint_score_kernel(const int32_t* __re
 // NaN key is no candidate), all threads copy the parents' token and ancestry paths into the other record exactly as
 // aed_search_prune_kernel does and the survivors' scorer states from the scratch into the other buffer, thread 0 moves the step.
 // LM: a survivor's (lm_state, lm) is copied from the LM scratch, its n is the parent's plus one unless the parent was finished.
-template <bool CTC, bool LM, class Lx>
+template <bool CTC, bool LM, bool CTX, class Lx>
 __global__ __launch_bounds__(256) void aed_joint_prune_kernel(int32_t* st, int B, int N, int P, int rec_words, int V, int K, int F,
                                                               float* js, const int32_t* __restrict__ cand,
                                                               const float* __restrict__ scr, int32_t* __restrict__ done_out, Lx lx) {
@@ -460,6 +557,13 @@ __global__ __launch_bounds__(256) void aed_joint_prune_kernel(int32_t* st, int B
       ld[LS_N] = c >= 0 ? lp[LS_N] + (grew ? 1 : 0) : 0;
       *reinterpret_cast<double*>(ld + LS_LM) = c >= 0 ? *reinterpret_cast<const double*>(lcs + LC_LM) : 0.0;
       ld[LS_ATT] = CTC ? 0 : (c >= 0 ? cr[JC_ATT] : __builtin_bit_cast(int32_t, -INFINITY));
+    }
+    if constexpr (CTX) {                                          // the survivor's (ctx_state', bonus') as score left them
+      const int32_t* ccs = lx.cx.cscr + ((size_t)u * N * K + (c >= 0 ? c : 0)) * CC_WORDS;
+      int32_t* cd = lx.cx.cstate + ((size_t)(u * N + j) * 2 + nxt) * CS_WORDS;
+      cd[CS_STATE] = c >= 0 ? ccs[CC_STATE] : 0;
+      cd[CS_ATT] = (CTC || LM) ? 0 : (c >= 0 ? cr[JC_ATT] : __builtin_bit_cast(int32_t, -INFINITY));
+      *reinterpret_cast<double*>(cd + CS_BONUS) = c >= 0 ? *reinterpret_cast<const double*>(ccs + CC_BONUS) : 0.0;
     }
   }
   if (tid == 0) {
@@ -566,6 +670,77 @@ __global__ __launch_bounds__(64) void aed_lm_result_kernel(const int32_t* __rest
   }
 }
 
+// -------------------------------------------------------------------------------------------------------------- context
+// What a descriptor must hold for the bias entry points: check_lm_desc's (with CTC the joint descriptor's, without it the
+// search's and the pre-beam's), then the int32 offsets of the two context blobs.
+int check_bias_desc(const m3_aed_joint_desc* d, bool ctc) {
+  M3_REQUIRE(d != nullptr, "aed_bias: null descriptor");
+  if (int rc = check_lm_desc(d, ctc)) return rc;
+  const size_t R = (size_t)d->search.B * d->search.beam, K = (size_t)d->pre_beam;
+  M3_REQUIRE(R * 2 * CS_WORDS <= (size_t)INT_MAX, "aed_bias: %zu rows overflow the int32 offsets of the context state", R);
+  M3_REQUIRE(R * K * (CC_WORDS + JC_WORDS) <= (size_t)INT_MAX, "aed_bias: %zu rows x %zu candidates overflow the int32 offsets of the context scratch", R, K);
+  return 0;
+}
+size_t bias_state_bytes(const m3_aed_joint_desc* d) { return align_up(4 * (size_t)d->search.B * d->search.beam * 2 * CS_WORDS, 256); }
+size_t bias_scratch_bytes(const m3_aed_joint_desc* d) {
+  return align_up(4 * (size_t)d->search.B * d->search.beam * d->pre_beam * (CC_WORDS + JC_WORDS), 256);
+}
+
+// the bias record of an entry point: the image (where the call reads it), graph_of, the context state and (with_scratch) scratch
+int check_bias(const m3_aed_joint_desc* d, const m3_aed_bias* b, bool with_image, bool with_scratch, const char* what) {
+  M3_REQUIRE(b != nullptr, "%s: null bias record", what);
+  const int B = d->search.B;
+  if (with_image) {
+    M3_REQUIRE(b->image_bytes % 4 == 0 && b->image_bytes >= CTX_HDR_WORDS * 4 && b->image_bytes <= kCtxMaxBytes && b->image != nullptr,
+               "%s: context image of %zu bytes (a multiple of 4 in [%d, %zu])", what, b->image_bytes, CTX_HDR_WORDS * 4, kCtxMaxBytes);
+    M3_REQUIRE(B == 0 || b->graph_of != nullptr, "%s: null graph_of", what);
+  }
+  M3_REQUIRE(b->state_bytes >= bias_state_bytes(d), "%s: context state %zu bytes < required %zu", what, b->state_bytes, bias_state_bytes(d));
+  M3_REQUIRE(B == 0 || (b->state != nullptr && ((uintptr_t)b->state & 15) == 0), "%s: the context state must be 16-byte aligned device memory", what);
+  if (with_scratch) {
+    M3_REQUIRE(b->scratch_bytes >= bias_scratch_bytes(d), "%s: context scratch %zu bytes < required %zu", what, b->scratch_bytes, bias_scratch_bytes(d));
+    M3_REQUIRE(B == 0 || (b->scratch != nullptr && ((uintptr_t)b->scratch & 15) == 0), "%s: the context scratch must be 16-byte aligned device memory", what);
+  }
+  return 0;
+}
+
+// the search's own blobs of a bias score / prune call: search state, (CTC) scorer state and joint scratch, (LM) LM state and scratch
+int check_bias_blobs(const m3_aed_joint_desc* d, bool ctc, bool lm, const void* st, size_t st_bytes, const void* js, size_t js_bytes,
+                     const void* scr, size_t scr_bytes, const void* ls, size_t ls_bytes, const void* lscr, size_t lscr_bytes, const char* what) {
+  if (int rc = check_bias_desc(d, ctc)) return rc;
+  if (lm) return check_lm(d, ctc, st, st_bytes, js, js_bytes, scr, scr_bytes, ls, ls_bytes, lscr, lscr_bytes, true, what);
+  M3_REQUIRE(ls == nullptr && lscr == nullptr, "%s: an LM blob without the other (LM state and LM scratch are NULL exactly when there is no LM)", what);
+  if (ctc) return check_joint(d, st, st_bytes, js, js_bytes, scr, scr_bytes, true, what);
+  return check_search_state(&d->search, st, st_bytes, what);
+}
+
+// the candidate records of the <false, false, true> form live behind the context scratch's (state, bonus) pairs
+int32_t* bias_cand(const m3_aed_joint_desc* d, void* cscr) {
+  return (int32_t*)cscr + (size_t)d->search.B * d->search.beam * d->pre_beam * CC_WORDS;
+}
+
+// one thread per row, after m3_aed_search_reset: [sos] is in state 0 with bonus 0.0; buffer 1 is 0
+__global__ __launch_bounds__(256) void aed_bias_reset_kernel(int R, int N, int32_t* cs) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= R) return;
+  int32_t* row = cs + (size_t)r * 2 * CS_WORDS;
+  for (int w = 0; w < 2 * CS_WORDS; ++w) row[w] = 0;
+  row[CS_ATT] = __builtin_bit_cast(int32_t, r % N == 0 ? 0.f : -INFINITY);
+}
+
+__global__ __launch_bounds__(64) void aed_bias_result_kernel(const int32_t* __restrict__ st, int N, int P, const int32_t* __restrict__ cs,
+                                                             float* __restrict__ bonus, int32_t* __restrict__ ctx_state,
+                                                             float* __restrict__ att) {
+  const int u = blockIdx.x, j = threadIdx.x;
+  const int s = min(max(as_header(st, u)[AS_STEP], 0), P - 1);
+  if (j < N) {
+    const int32_t* row = cs + ((size_t)(u * N + j) * 2 + (s & 1)) * CS_WORDS;
+    bonus[u * N + j] = (float)*reinterpret_cast<const double*>(row + CS_BONUS);
+    ctx_state[u * N + j] = row[CS_STATE];
+    if (att) att[u * N + j] = __builtin_bit_cast(float, row[CS_ATT]);
+  }
+}
+
 }  // namespace
 }  // namespace m3
 
@@ -605,7 +780,7 @@ int m3_aed_joint_score(const m3_aed_joint_desc* desc, const void* search_state, 
   if (s->B == 0) return 0;
   M3_REQUIRE(logits != nullptr, "aed_joint_score: null pointer");
   const SearchLayout l = search_layout(s);
-  hipLaunchKernelGGL((aed_joint_score_kernel<true, false, NoLm>), dim3((unsigned)(s->B * s->beam)), dim3(64), 0, (hipStream_t)stream, (const int32_t*)search_state,
+  hipLaunchKernelGGL((aed_joint_score_kernel<true, false, false, NoLm>), dim3((unsigned)(s->B * s->beam)), dim3(64), 0, (hipStream_t)stream, (const int32_t*)search_state,
                      s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames, (const float*)joint_state, (int32_t*)scratch,
                      (float*)scratch, logits, ldl, ctc, ldc, ctc_rows, ctc_weight, NoLm{});
   M3_LAUNCH_CHECK();
@@ -618,7 +793,7 @@ int m3_aed_joint_prune(const m3_aed_joint_desc* desc, void* search_state, size_t
   const m3_aed_search_desc* s = &desc->search;
   if (s->B == 0) return 0;
   const SearchLayout l = search_layout(s);
-  hipLaunchKernelGGL((aed_joint_prune_kernel<true, false, NoLm>), dim3((unsigned)s->B), dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state, s->B, s->beam,
+  hipLaunchKernelGGL((aed_joint_prune_kernel<true, false, false, NoLm>), dim3((unsigned)s->B), dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state, s->B, s->beam,
                      l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames, (float*)joint_state, (const int32_t*)scratch,
                      (const float*)scratch, done, NoLm{});
   M3_LAUNCH_CHECK();
@@ -689,11 +864,11 @@ int m3_aed_ngram_score(const m3_aed_joint_desc* desc, const void* search_state, 
   const SearchLayout l = search_layout(s);
   const LmFuse lx{(const int32_t*)lm_image, (long long)(lm_bytes / 4), lm_on, (int32_t*)const_cast<void*>(lm_state), (int32_t*)lm_scratch, alpha, beta, use_eos};
   if (with_ctc)
-    hipLaunchKernelGGL((aed_joint_score_kernel<true, true, LmFuse>), dim3((unsigned)(s->B * s->beam)), dim3(64), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL((aed_joint_score_kernel<true, true, false, LmFuse>), dim3((unsigned)(s->B * s->beam)), dim3(64), 0, (hipStream_t)stream,
                        (const int32_t*)search_state, s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames,
                        (const float*)joint_state, (int32_t*)scratch, (float*)scratch, logits, ldl, ctc, ldc, ctc_rows, ctc_weight, lx);
   else
-    hipLaunchKernelGGL((aed_joint_score_kernel<false, true, LmFuse>), dim3((unsigned)(s->B * s->beam)), dim3(64), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL((aed_joint_score_kernel<false, true, false, LmFuse>), dim3((unsigned)(s->B * s->beam)), dim3(64), 0, (hipStream_t)stream,
                        (const int32_t*)search_state, s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, 0, (const float*)nullptr,
                        lm_cand(desc, lm_scratch), (float*)nullptr, logits, ldl, (const float*)nullptr, 0, 0, 0.f, lx);
   M3_LAUNCH_CHECK();
@@ -711,11 +886,11 @@ int m3_aed_ngram_prune(const m3_aed_joint_desc* desc, void* search_state, size_t
   const SearchLayout l = search_layout(s);
   const LmFuse lx{nullptr, 0, nullptr, (int32_t*)lm_state, (int32_t*)const_cast<void*>(lm_scratch), 0.0, 0.0, 0};
   if (with_ctc)
-    hipLaunchKernelGGL((aed_joint_prune_kernel<true, true, LmFuse>), dim3((unsigned)s->B), dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state,
+    hipLaunchKernelGGL((aed_joint_prune_kernel<true, true, false, LmFuse>), dim3((unsigned)s->B), dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state,
                        s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames, (float*)joint_state, (const int32_t*)scratch,
                        (const float*)scratch, done, lx);
   else
-    hipLaunchKernelGGL((aed_joint_prune_kernel<false, true, LmFuse>), dim3((unsigned)s->B), dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state,
+    hipLaunchKernelGGL((aed_joint_prune_kernel<false, true, false, LmFuse>), dim3((unsigned)s->B), dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state,
                        s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, 0, (float*)nullptr,
                        (const int32_t*)lm_cand(desc, const_cast<void*>(lm_scratch)), (const float*)nullptr, done, lx);
   M3_LAUNCH_CHECK();
@@ -730,6 +905,151 @@ int m3_aed_ngram_result(const m3_aed_joint_desc* desc, const void* search_state,
   M3_REQUIRE(lm && lm_state_out, "aed_ngram_result: null pointer");
   hipLaunchKernelGGL(aed_lm_result_kernel, dim3((unsigned)desc->search.B), dim3(64), 0, (hipStream_t)stream, (const int32_t*)search_state,
                      desc->search.beam, search_layout(&desc->search).P, (const int32_t*)lm_state, lm, lm_state_out, n, att);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+size_t m3_aed_bias_state_size(const m3_aed_joint_desc* desc) {
+  if (check_bias_desc(desc, false)) return 0;
+  return bias_state_bytes(desc);
+}
+
+size_t m3_aed_bias_scratch_size(const m3_aed_joint_desc* desc) {
+  if (check_bias_desc(desc, false)) return 0;
+  return bias_scratch_bytes(desc);
+}
+
+int m3_aed_bias_reset(const m3_aed_joint_desc* desc, const m3_aed_bias* bias, m3_stream stream) {
+  if (int rc = check_bias_desc(desc, false)) return rc;
+  if (int rc = check_bias(desc, bias, true, false, "aed_bias_reset")) return rc;
+  // the image's header, read back once per search: what ctx_graph_view refuses here the kernels would run as "unbiased"
+  int32_t head[CTX_HDR_WORDS];
+  M3_CHECK_HIP(hipMemcpy(head, bias->image, sizeof(head), hipMemcpyDeviceToHost));
+  M3_REQUIRE(head[CTX_MAGIC] == kCtxMagic && head[CTX_G] >= 0 && head[CTX_G] <= kCtxMaxGraphs &&
+                 CTX_HDR_WORDS + (long long)head[CTX_G] * CTXG_WORDS <= (long long)(bias->image_bytes / 4),
+             "aed_bias_reset: the image's header does not describe a context set of %zu bytes", bias->image_bytes);
+  M3_REQUIRE(head[CTX_V] == desc->search.V, "aed_bias_reset: the context image was built for V = %d, the search has V = %d", head[CTX_V],
+             desc->search.V);
+  if (desc->search.B == 0) return 0;
+  const int R = desc->search.B * desc->search.beam;
+  hipLaunchKernelGGL(aed_bias_reset_kernel, dim3((unsigned)cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream, R, desc->search.beam, (int32_t*)bias->state);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+int m3_aed_bias_score(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, const void* joint_state,
+                      size_t joint_state_bytes, void* scratch, size_t scratch_bytes, const void* lm_state, size_t lm_state_bytes,
+                      void* lm_scratch, size_t lm_scratch_bytes, const float* logits, int ldl, const float* ctc, int ldc, int ctc_rows,
+                      float ctc_weight, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha, double beta, int use_eos,
+                      const m3_aed_bias* bias, m3_stream stream) {
+  M3_REQUIRE(ctc_weight >= 0.f && ctc_weight <= 1.f, "aed_bias_score: ctc_weight = %g outside [0, 1]", (double)ctc_weight);
+  const bool with_ctc = ctc_weight > 0.f, with_lm = lm_image != nullptr;
+  const bool empty = desc && desc->search.B == 0;
+  M3_REQUIRE((ctc != nullptr) == with_ctc || empty, "aed_bias_score: the CTC log-probabilities are given exactly when ctc_weight > 0 (ctc_weight = %g)",
+             (double)ctc_weight);
+  M3_REQUIRE(((joint_state != nullptr) == with_ctc && (scratch != nullptr) == with_ctc) || empty,
+             "aed_bias_score: the scorer state and the joint scratch are given exactly when ctc_weight > 0 (ctc_weight = %g)", (double)ctc_weight);
+  M3_REQUIRE(((lm_state != nullptr) == with_lm && (lm_scratch != nullptr) == with_lm && (lm_on != nullptr) == with_lm) || empty,
+             "aed_bias_score: the LM image, lm_on, the LM state and the LM scratch are NULL exactly when there is no LM");
+  if (int rc = check_bias_blobs(desc, with_ctc, with_lm, search_state, search_state_bytes, joint_state, joint_state_bytes, scratch, scratch_bytes,
+                                lm_state, lm_state_bytes, lm_scratch, lm_scratch_bytes, "aed_bias_score")) return rc;
+  if (int rc = check_bias(desc, bias, true, true, "aed_bias_score")) return rc;
+  if (with_ctc)
+    if (int rc = check_ctc(desc, ctc, ldc, ctc_rows, "aed_bias_score")) return rc;
+  const m3_aed_search_desc* s = &desc->search;
+  M3_REQUIRE(ldl >= s->V, "aed_bias_score: ldl = %d < V = %d", ldl, s->V);
+  if (with_lm) {
+    if (int rc = check_lm_args("aed_bias_score", lm_image, lm_bytes, lm_on, alpha, beta, s->B)) return rc;
+    M3_REQUIRE(use_eos == 0 || use_eos == 1, "aed_bias_score: use_eos = %d", use_eos);
+  } else {
+    M3_REQUIRE(std::isfinite(alpha) && std::isfinite(beta), "aed_bias_score: alpha or beta is not finite");
+  }
+  if (s->B == 0) return 0;
+  M3_REQUIRE(logits != nullptr, "aed_bias_score: null pointer");
+  const SearchLayout l = search_layout(s);
+  const CtxFuse cx{(const int32_t*)bias->image, (long long)(bias->image_bytes / 4), bias->graph_of, (int32_t*)bias->state, (int32_t*)bias->scratch};
+  const dim3 grid((unsigned)(s->B * s->beam));
+  if (with_lm) {
+    Biased<LmFuse> lx;
+    static_cast<LmFuse&>(lx) = LmFuse{(const int32_t*)lm_image, (long long)(lm_bytes / 4), lm_on, (int32_t*)const_cast<void*>(lm_state),
+                                      (int32_t*)lm_scratch, alpha, beta, use_eos};
+    lx.cx = cx;
+    if (with_ctc)
+      hipLaunchKernelGGL((aed_joint_score_kernel<true, true, true, Biased<LmFuse>>), grid, dim3(64), 0, (hipStream_t)stream,
+                         (const int32_t*)search_state, s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames,
+                         (const float*)joint_state, (int32_t*)scratch, (float*)scratch, logits, ldl, ctc, ldc, ctc_rows, ctc_weight, lx);
+    else
+      hipLaunchKernelGGL((aed_joint_score_kernel<false, true, true, Biased<LmFuse>>), grid, dim3(64), 0, (hipStream_t)stream,
+                         (const int32_t*)search_state, s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, 0, (const float*)nullptr,
+                         lm_cand(desc, lm_scratch), (float*)nullptr, logits, ldl, (const float*)nullptr, 0, 0, 0.f, lx);
+  } else {
+    Biased<NoLm> lx;
+    lx.cx = cx;
+    if (with_ctc)
+      hipLaunchKernelGGL((aed_joint_score_kernel<true, false, true, Biased<NoLm>>), grid, dim3(64), 0, (hipStream_t)stream,
+                         (const int32_t*)search_state, s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames,
+                         (const float*)joint_state, (int32_t*)scratch, (float*)scratch, logits, ldl, ctc, ldc, ctc_rows, ctc_weight, lx);
+    else
+      hipLaunchKernelGGL((aed_joint_score_kernel<false, false, true, Biased<NoLm>>), grid, dim3(64), 0, (hipStream_t)stream,
+                         (const int32_t*)search_state, s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, 0, (const float*)nullptr,
+                         bias_cand(desc, bias->scratch), (float*)nullptr, logits, ldl, (const float*)nullptr, 0, 0, 0.f, lx);
+  }
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+int m3_aed_bias_prune(const m3_aed_joint_desc* desc, void* search_state, size_t search_state_bytes, void* joint_state, size_t joint_state_bytes,
+                      const void* scratch, size_t scratch_bytes, void* lm_state, size_t lm_state_bytes, const void* lm_scratch,
+                      size_t lm_scratch_bytes, const m3_aed_bias* bias, int32_t* done, m3_stream stream) {
+  const bool with_ctc = joint_state != nullptr, with_lm = lm_state != nullptr;   // as the score call of the same search had them
+  const bool empty = desc && desc->search.B == 0;
+  M3_REQUIRE((scratch != nullptr) == with_ctc || empty, "aed_bias_prune: the scorer state and the joint scratch are given together or not at all");
+  M3_REQUIRE((lm_scratch != nullptr) == with_lm || empty, "aed_bias_prune: the LM state and the LM scratch are given together or not at all");
+  if (int rc = check_bias_blobs(desc, with_ctc, with_lm, search_state, search_state_bytes, joint_state, joint_state_bytes, scratch, scratch_bytes,
+                                lm_state, lm_state_bytes, lm_scratch, lm_scratch_bytes, "aed_bias_prune")) return rc;
+  if (int rc = check_bias(desc, bias, false, true, "aed_bias_prune")) return rc;
+  const m3_aed_search_desc* s = &desc->search;
+  if (s->B == 0) return 0;
+  const SearchLayout l = search_layout(s);
+  const CtxFuse cx{nullptr, 0, nullptr, (int32_t*)bias->state, (int32_t*)bias->scratch};
+  const dim3 grid((unsigned)s->B);
+  if (with_lm) {
+    Biased<LmFuse> lx;
+    static_cast<LmFuse&>(lx) = LmFuse{nullptr, 0, nullptr, (int32_t*)lm_state, (int32_t*)const_cast<void*>(lm_scratch), 0.0, 0.0, 0};
+    lx.cx = cx;
+    if (with_ctc)
+      hipLaunchKernelGGL((aed_joint_prune_kernel<true, true, true, Biased<LmFuse>>), grid, dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state,
+                         s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames, (float*)joint_state, (const int32_t*)scratch,
+                         (const float*)scratch, done, lx);
+    else
+      hipLaunchKernelGGL((aed_joint_prune_kernel<false, true, true, Biased<LmFuse>>), grid, dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state,
+                         s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, 0, (float*)nullptr,
+                         (const int32_t*)lm_cand(desc, const_cast<void*>(lm_scratch)), (const float*)nullptr, done, lx);
+  } else {
+    Biased<NoLm> lx;
+    lx.cx = cx;
+    if (with_ctc)
+      hipLaunchKernelGGL((aed_joint_prune_kernel<true, false, true, Biased<NoLm>>), grid, dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state,
+                         s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames, (float*)joint_state, (const int32_t*)scratch,
+                         (const float*)scratch, done, lx);
+    else
+      hipLaunchKernelGGL((aed_joint_prune_kernel<false, false, true, Biased<NoLm>>), grid, dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state,
+                         s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, 0, (float*)nullptr,
+                         (const int32_t*)bias_cand(desc, bias->scratch), (const float*)nullptr, done, lx);
+  }
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+int m3_aed_bias_result(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, const m3_aed_bias* bias,
+                       float* bonus, int32_t* ctx_state, float* att, m3_stream stream) {
+  if (int rc = check_bias_desc(desc, false)) return rc;
+  if (int rc = check_search_state(&desc->search, search_state, search_state_bytes, "aed_bias_result")) return rc;
+  if (int rc = check_bias(desc, bias, false, false, "aed_bias_result")) return rc;
+  if (desc->search.B == 0) return 0;
+  M3_REQUIRE(bonus && ctx_state, "aed_bias_result: null pointer");
+  hipLaunchKernelGGL(aed_bias_result_kernel, dim3((unsigned)desc->search.B), dim3(64), 0, (hipStream_t)stream, (const int32_t*)search_state,
+                     desc->search.beam, search_layout(&desc->search).P, (const int32_t*)bias->state, bonus, ctx_state, att);
   M3_LAUNCH_CHECK();
   return 0;
 }

@@ -114,6 +114,11 @@ class AedJointDesc(C.Structure):  # m3_aed_joint_desc
     _fields_ = [("search", AedSearchDesc), ("pre_beam", C.c_int32), ("max_frames", C.c_int32)]
 
 
+class AedBias(C.Structure):  # m3_aed_bias
+    _fields_ = [("image", C.c_void_p), ("image_bytes", C.c_size_t), ("graph_of", C.c_void_p), ("state", C.c_void_p),
+                ("state_bytes", C.c_size_t), ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
+
+
 class WeightEntry(C.Structure):  # m3_weight_entry
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64), ("dtype", C.c_int32)]
 
@@ -330,6 +335,13 @@ SIGNATURES = {
                              _d, _d, _i, _vp]),
     "m3_aed_ngram_prune": (_i, [_P(AedJointDesc), _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     "m3_aed_ngram_result": (_i, [_P(AedJointDesc), _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "m3_aed_bias_state_size": (_sz, [_P(AedJointDesc)]),
+    "m3_aed_bias_scratch_size": (_sz, [_P(AedJointDesc)]),
+    "m3_aed_bias_reset": (_i, [_P(AedJointDesc), _P(AedBias), _vp]),
+    "m3_aed_bias_score": (_i, [_P(AedJointDesc), _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _i, _vp, _i, _i, _f, _vp, _sz, _vp,
+                               _d, _d, _i, _P(AedBias), _vp]),
+    "m3_aed_bias_prune": (_i, [_P(AedJointDesc), _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _P(AedBias), _vp, _vp]),
+    "m3_aed_bias_result": (_i, [_P(AedJointDesc), _vp, _sz, _P(AedBias), _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -32,7 +32,20 @@ N-GRAM LM FUSION AND A LENGTH BONUS (lm=; the contract is restated
 m3_aed_ngram_score and m3_aed_ngram_prune stand where the joint calls stood: still 8 L + 4.  ctc_weight = 0 with an LM is attention
 plus LM: no CTC input, no scorer state; the rows still offer `pre_beam` candidates, because the LM scores the pre-beam only.
 lm_on (per call, per utterance) switches the LM off for single utterances, which then get the bits of the search without it.
-Without lm nothing of this exists."""
+Without lm nothing of this exists.
+
+HOTWORD BIASING (context=; the contract is restated in tests/aed_ctx_ref.py).  With a ContextSet (m3asr.context,
+built with device=) every candidate also takes one arc of its utterance's context graph and the rank gains the hypothesis's
+bonus: key = jkey + (float)((lm_weight lm + length_bonus n) + bonus), the parenthesis without an LM being bonus alone.  The
+graph's own score is the weight.  A token adds delta[state][cls[token]], eos hands back pot[state] (the credit of a phrase that
+was not completed), so a finished hypothesis's bonus is the context contract's `final`; a hypothesis cut at the step limit
+keeps its provisional credit and detail reports final = bonus - pot[state] next to it.  graph_ids (per call, per utterance)
+picks the graph: default graph 0 for all, -1 = unbiased, and an unbiased utterance gets the bits of the search without a
+context.  m3_aed_bias_score and m3_aed_bias_prune stand where the joint / ngram calls stood: still 8 L + 4, also with ctc_weight
+= 0 and no LM.  The context is a PARTIAL scorer over the pre-beam, like the LM: the rows offer `pre_beam` candidates whenever a
+context is given, whatever ctc_weight and lm are, and a hotword token outside a row's `pre_beam` largest attention
+log-probabilities is not rescued.  A set in which eos is part of a phrase is refused: eos is never walked.  Without context
+nothing of this exists."""
 import math
 
 import torch
@@ -43,7 +56,7 @@ from .rescore import LN_EPS
 
 class AttentionBeamSearch:
     def __init__(self, rescorer, B, beam, max_steps, poll=8, use_graph=False, ctc_weight=0.0, pre_beam=None, lm=None, lm_weight=0.0,
-                 length_bonus=0.0, lm_eos=True):
+                 length_bonus=0.0, lm_eos=True, context=None):
         """rescorer: the AttentionRescorer whose uploaded weights and config the search shares; B utterances per call, `beam`
         hypotheses each (1 <= beam <= min(64, vocab)); max_steps: the most tokens a hypothesis can get (it sizes the state and
         the K / V cache, see the module docstring; more than max_len - 1 steps are never taken).  poll: steps between two reads of
@@ -56,6 +69,10 @@ class AttentionBeamSearch:
         lm: an NgramLm over the decoder's vocabulary, already moved with .to(device) (which validates it); lm_weight and
         length_bonus: the weights of its log-probability and of the token count in the key; lm_eos: a hypothesis that ends also
         takes log P(</s> | its LM state).  pre_beam applies whenever lm is given, whatever ctc_weight.
+        context: a ContextSet over the decoder's vocabulary, built with device= this search's device (its constructor validates
+        it); the phrases' score is the weight of the bonus in the key.  pre_beam applies whenever context is given, whatever
+        ctc_weight and lm: the context scores the pre-beam only, a hotword outside a row's pre_beam best is not rescued.  A set
+        on the host, on another device, over another vocabulary, or with eos in a phrase is refused.
         Raises M3Error before anything is allocated for a beam or a head size the kernels do not take."""
         cfg = rescorer.cfg
         self.rescorer, self.cfg, self.device = rescorer, cfg, rescorer.device
@@ -76,8 +93,23 @@ class AttentionBeamSearch:
             if lm.vocab_size != cfg.vocab:
                 raise _lib.M3Error("AttentionBeamSearch: the LM was built for a vocabulary of %d, the attention decoder has %d" % (
                     lm.vocab_size, cfg.vocab))
+        self.context = context
+        if context is not None:
+            if context.dev is None or not context.dev.is_cuda or context.dev.device != torch.device(self.device):
+                raise _lib.M3Error("AttentionBeamSearch: the context set is not on %s; build it with ContextSet(graphs, device=...)" % (
+                    self.device,))
+            if context.vocab_size != cfg.vocab:
+                raise _lib.M3Error("AttentionBeamSearch: the context set was built for a vocabulary of %d, the attention decoder has %d" % (
+                    context.vocab_size, cfg.vocab))
+            for i, g in enumerate(context.graphs):
+                if int(g.cls[cfg.vocab - 1]) != 0:
+                    raise _lib.M3Error("AttentionBeamSearch: graph %d of the context set has eos (%d) in a phrase; eos is never walked" % (
+                        i, cfg.vocab - 1))
+            if context.dev is None or not context.dev.is_cuda or context.dev.device != torch.device(self.device):
+                raise _lib.M3Error("AttentionBeamSearch: the context set is not on %s; build it with ContextSet(graphs, device=...)" % (
+                    self.device,))
         self.pre_beam = 0
-        if self.ctc_weight > 0 or lm is not None:
+        if self.ctc_weight > 0 or lm is not None or context is not None:
             self.pre_beam = min(max(self.beam, math.ceil(1.5 * self.beam)), 64, cfg.vocab) if pre_beam is None else int(pre_beam)
             if not self.beam <= self.pre_beam <= min(64, cfg.vocab):
                 raise _lib.M3Error("AttentionBeamSearch: pre_beam = %d, need beam = %d <= pre_beam <= min(64, vocab = %d)" % (
@@ -104,13 +136,22 @@ class AttentionBeamSearch:
             self.lstate = torch.zeros(ops.aed_lm_state_size(self.ldesc), dtype=torch.uint8, device=dev)
             self.lscratch = torch.zeros(ops.aed_lm_scratch_size(self.ldesc), dtype=torch.uint8, device=dev)
             self.lm_on = torch.ones(self.B, dtype=torch.int32, device=dev)
-        self.kvp = None           # the memory's K / V projection of the current call, (rows, num_blocks * 2 D)
+        # hotword biasing only: its descriptor without a CTC part, the context state and scratch (sized by B, beam and pre_beam
+        # alone), graph_of, and the m3_aed_bias record that names them (the same addresses for every step and every call)
+        self.bdesc = self.cstate = self.cscratch = self.graph_of = self.bias = None
+        if context is not None:
+            self.bdesc = ops.aed_bias_desc(self.desc, self.pre_beam)
+            self.cstate = torch.zeros(ops.aed_bias_state_size(self.bdesc), dtype=torch.uint8, device=dev)
+            self.cscratch = torch.zeros(ops.aed_bias_scratch_size(self.bdesc), dtype=torch.uint8, device=dev)
+            self.graph_of = torch.zeros(self.B, dtype=torch.int32, device=dev)
+            self.bias = ops.aed_bias_record(context.dev, self.graph_of, self.cstate, self.cscratch)
+        self.kvp = None          # the memory's K / V projection of the current call, (rows, num_blocks * 2 D)
         self._graph = None
         self.steps_issued = 0     # of the last call
         self.last = None          # device tensors of the last call: m3_aed_search_result's, plus state and done
 
     def launches_per_step(self):
-        return 8 * self.cfg.num_blocks + (4 if self.ctc_weight > 0 or self.lm is not None else 3)
+        return 8 * self.cfg.num_blocks + (4 if self.ctc_weight > 0 or self.lm is not None or self.context is not None else 3)
 
     # ---- one step: the same launches with the same arguments, whatever the step
     def _step(self):
@@ -131,7 +172,14 @@ class AttentionBeamSearch:
             ops.linear(self.h, w[q + "feed_forward.w_2.weight"], w[q + "feed_forward.w_2.bias"], resid=x, out=x)
         ops.linear(x, w["decoder.output_layer.weight"], w["decoder.output_layer.bias"],
                    ln=(w["decoder.after_norm.weight"], w["decoder.after_norm.bias"], LN_EPS), out=self.logits)
-        if self.lm is not None:
+        if self.context is not None:
+            jd = self.jdesc if self.ctc_weight > 0 else self.bdesc
+            lm = self.lm.dev if self.lm is not None else None
+            ops.aed_bias_score(jd, st, self.jstate, self.jscratch, self.lstate, self.lscratch, self.logits, self.ctc, self.ctc_weight,
+                               lm, self.lm_on, self.lm_weight if lm is not None else 0.0, self.length_bonus if lm is not None else 0.0,
+                               self.lm_eos, self.bias)
+            ops.aed_bias_prune(jd, st, self.jstate, self.jscratch, self.lstate, self.lscratch, self.bias, self.done)
+        elif self.lm is not None:
             jd = self.jdesc if self.ctc_weight > 0 else self.ldesc
             ops.aed_lm_score(jd, st, self.jstate, self.jscratch, self.lstate, self.lscratch, self.logits, self.ctc, self.ctc_weight,
                              self.lm.dev, self.lm_on, self.lm_weight, self.length_bonus, self.lm_eos)
@@ -148,6 +196,8 @@ class AttentionBeamSearch:
             ops.aed_joint_reset(self.jdesc, self.state, self.jstate, self.ctc)
         if self.lm is not None:
             ops.aed_lm_reset(self.ldesc, self.lstate, self.lm.dev)
+        if self.context is not None:
+            ops.aed_bias_reset(self.bdesc, self.bias)
         self.done.zero_()
 
     def _take_ctc(self, ctc, n_rows, frames, log_probs):
@@ -200,9 +250,23 @@ class AttentionBeamSearch:
             raise _lib.M3Error("search: lm_on has %d entries for %d utterances" % (len(on), self.B))
         self.lm_on.copy_(torch.tensor(on, dtype=torch.int32))
 
-    def _run(self, rows, row0, lens, raw_memory, detail, max_steps, poll, ctc=None, ctc_log_probs=False, lm_on=None):
+    def _take_graph_ids(self, graph_ids):
+        """the per-utterance graph of the call -> self.graph_of (kept across calls: a captured step reads the same address);
+        -> the ids as Python ints, -1 for every utterance the kernels treat as unbiased"""
+        if self.context is None:
+            if graph_ids is not None:
+                raise _lib.M3Error("search: graph_ids given, but the search was built without a context")
+            return None
+        ids = [0] * self.B if graph_ids is None else [int(v) for v in torch.as_tensor(graph_ids).reshape(-1).tolist()]
+        if len(ids) != self.B:
+            raise _lib.M3Error("search: graph_ids has %d entries for %d utterances" % (len(ids), self.B))
+        ids = [min(max(g, -(2 ** 31)), 2 ** 31 - 1) for g in ids]
+        self.graph_of.copy_(torch.tensor(ids, dtype=torch.int32))
+        return [g if 0 <= g < len(self.context) else -1 for g in ids]
+
+    def _run(self, rows, row0, lens, raw_memory, detail, max_steps, poll, ctc=None, ctc_log_probs=False, lm_on=None, graph_ids=None):
         """rows (n, D) memory rows on the device; row0 / lens: B Python ints each, validated by the caller; ctc: None or the
-        CTC output of the same n rows; lm_on: None or B switches"""
+        CTC output of the same n rows; lm_on: None or B switches; graph_ids: None or B graph ids"""
         cfg, d = self.cfg, self.desc
         cap = self.max_steps if max_steps is None else int(max_steps)
         if not 1 <= cap <= self.max_steps:
@@ -210,7 +274,8 @@ class AttentionBeamSearch:
         poll = self.poll if poll is None else max(int(poll), 1)
         self._take_ctc(ctc, rows.shape[0], max(lens), ctc_log_probs)
         self._take_lm_on(lm_on)
-        meta = torch.tensor([row0, lens], dtype=torch.int32).to(self.device)
+        graphs = self._take_graph_ids(graph_ids)
+        meta =torch.tensor([row0, lens], dtype=torch.int32).to(self.device)
         self._project(rows, raw_memory)
         self._reset(meta, cap)
         most = min(max(lens), cfg.max_len - 1, cap)
@@ -238,8 +303,17 @@ class AttentionBeamSearch:
                 self.last.update(att=lres["lm_att"], ctc=torch.zeros_like(lres["lm_att"]))
                 parts = [self.last["att"].reshape(-1).view(torch.int32), self.last["ctc"].reshape(-1).view(torch.int32)]
             parts.append(lres["lm"].reshape(-1).view(torch.int32))
+        tail = []
+        if self.context is not None:
+            cres = ops.aed_bias_result(self.bdesc, self.state, self.bias)
+            self.last.update(bonus=cres["bonus"], ctx_state=cres["ctx_state"], ctx_blob=self.cstate)
+            if not parts:                                           # attention + context: the att part rides in the context state
+                self.last.update(att=cres["ctx_att"], ctc=torch.zeros_like(cres["ctx_att"]))
+                parts = [self.last["att"].reshape(-1).view(torch.int32), self.last["ctc"].reshape(-1).view(torch.int32)]
+            parts.append(cres["bonus"].reshape(-1).view(torch.int32))
+            tail = [cres["ctx_state"].reshape(-1)]                  # int32 as it is, behind the float parts
         host = torch.cat([res["hyp_tokens"].reshape(-1), res["hyp_len"].reshape(-1), res["finished"].reshape(-1), res["best"],
-                          res["score"].reshape(-1).view(torch.int32)] + parts).cpu()
+                          res["score"].reshape(-1).view(torch.int32)] + parts + tail).cpu()
         B, N, S = self.B, self.beam, self.max_steps
         toks = host[:B * N * S].view(B, N, S)
         o = B * N * S
@@ -250,6 +324,11 @@ class AttentionBeamSearch:
             hyps = [(tuple(toks[b, i, :hlen[b * N + i]].tolist()), score[b * N + i], bool(fin[b * N + i])) for i in range(N)]
             if parts:
                 hyps = [h + tuple(score[(k + 1) * B * N + b * N + i] for k in range(len(parts))) for i, h in enumerate(hyps)]
+            if tail:                                                # final = bonus - pot[ctx_state]: what is no longer provisional
+                pot = self.context.graphs[graphs[b]].pot if graphs[b] >= 0 else None
+                states = host[-B * N:].tolist()
+                hyps = [h + (h[-1] - float(pot[states[b * N + i]]) if pot is not None and 0 <= states[b * N + i] < len(pot) else h[-1],)
+                        for i, h in enumerate(hyps)]
             out.append((list(hyps[best[b]][0]), hyps) if detail else list(hyps[best[b]][0]))
         return out
 
@@ -273,7 +352,7 @@ class AttentionBeamSearch:
 
     # ---- the public calls
     def search(self, memory, mem_len, raw_memory=False, detail=False, max_steps=None, poll=None, ctc_logits=None,
-               ctc_log_probs=False, lm_on=None):
+               ctc_log_probs=False, lm_on=None, graph_ids=None):
         """memory (B, T', D) on the device: the encoder's normalised hidden states (Engine.hidden()), or with raw_memory the
         residual stream before after_norm (Engine.hidden(normalized=False)), the LayerNorm then riding in the K / V GEMM's
         prologue; mem_len (B,) valid frames.  Utterance b stops once its `beam` hypotheses have all ended in eos, or after
@@ -285,6 +364,10 @@ class AttentionBeamSearch:
         joint key and detail gives (tokens, key, finished, att, ctc).
         LM fusion (lm given): lm_on, None or B flags, 0 = this utterance is searched without the LM; detail appends lm, the LM's
         log-probability of the hypothesis: (tokens, key, finished, att, ctc, lm), ctc = 0.0 when ctc_weight = 0.
+        Hotword biasing (context given): graph_ids, None (graph 0 for all) or B graph ids, -1 (or any id outside the set) = this
+        utterance is searched unbiased; detail appends the context part after the parts above: bonus, what the key holds, and
+        final = bonus - pot[ctx_state], what is no longer provisional (equal for a finished hypothesis):
+        (tokens, key, finished, att, ctc[, lm], bonus, final).
         mem_len < 1 is refused before anything is launched.  The device tensors of the call stay in self.last."""
         cfg, B = self.cfg, self.B
         memory = memory.to(self.device, torch.float32)
@@ -300,14 +383,15 @@ class AttentionBeamSearch:
         if ctc_logits is not None and self.ctc_weight > 0 and (ctc_logits.dim() != 3 or ctc_logits.shape[0] != B or ctc_logits.shape[1] != Tm):
             raise _lib.M3Error("search: the CTC output %s does not cover the memory's %d x %d frames" % (tuple(ctc_logits.shape), B, Tm))
         return self._run(memory.contiguous().view(B * Tm, cfg.dim), [b * Tm for b in range(B)], lens, raw_memory, detail, max_steps, poll,
-                         ctc_logits, ctc_log_probs, lm_on)
+                         ctc_logits, ctc_log_probs, lm_on, graph_ids)
 
     def search_rows(self, rows, row0, raw_memory=True, detail=False, max_steps=None, poll=None, ctc_rows=None, ctc_log_probs=False,
-                    lm_on=None):
+                    lm_on=None, graph_ids=None):
         """The search over PACKED memory rows, as AttentionRescorer.rescore_rows takes them: rows (>= R, D) on the device,
         row0 (B + 1,) int32 (m3_aed_memory_gather leaves them so): utterance b owns rows [row0[b], row0[b + 1]).  raw_memory:
         the rows are the residual stream before after_norm (what the streaming store keeps).  An utterance without a row is
-        refused before anything is launched.  Joint decoding: ctc_rows (>= row0[B], V), the CTC output of the same packed rows."""
+        refused before anything is launched.  Joint decoding: ctc_rows (>= row0[B], V), the CTC output of the same packed rows.
+        lm_on and graph_ids: as search takes them."""
         cfg, B = self.cfg, self.B
         if rows.dim() != 2 or rows.shape[1] != cfg.dim or not rows.is_contiguous() or row0.numel() != B + 1:
             raise ValueError("search_rows: rows %s / row0 (%d,) for %d utterances of dim %d" % (tuple(rows.shape), row0.numel(), B, cfg.dim))
@@ -321,4 +405,4 @@ class AttentionBeamSearch:
         if ctc_rows is not None and self.ctc_weight > 0 and ctc_rows.dim() != 2:
             raise _lib.M3Error("search_rows: the CTC output %s is not (rows, vocab)" % (tuple(ctc_rows.shape),))
         return self._run(rows[:r0[-1]].to(self.device, torch.float32), r0[:-1], lens, raw_memory, detail, max_steps, poll,
-                         ctc_rows, ctc_log_probs, lm_on)
+                         ctc_rows, ctc_log_probs, lm_on, graph_ids)

@@ -375,7 +375,7 @@ class CtcDecoder:
 
     def attention(self, xs: torch.Tensor, xs_lens: torch.Tensor, beam_size: int, decoding_chunk_size: int = -1,
                   num_decoding_left_chunks: int = -1, max_steps=None, detail=False, ctc_weight: float = 0.0, pre_beam=None,
-                  lm=None, lm_weight: float = 0.0, length_bonus: float = 0.0):
+                  lm=None, lm_weight: float = 0.0, length_bonus: float = 0.0, context=None, graph_ids=None):
         """The reference's decoding mode `attention` for any batch size, all on the device: encoder forward, then the attention
         decoder's own autoregressive beam search over the encoder's hidden states (m3asr.aed_search).  There is
         no first pass, and the right-to-left decoder takes no part.  ctc_weight = 0: CTC scores take no part either.
@@ -386,7 +386,10 @@ class CtcDecoder:
         -> the best token list per utterance; detail: (best tokens, [(tokens, score, finished)]) per utterance, and
         (tokens, key, finished, att, ctc) per hypothesis in joint mode.
         lm: an NgramLm on the engine's device (NgramLm.to): n-gram LM fusion and a length bonus inside the search,
-        the rank (1 - ctc_weight) att + ctc_weight ctc + lm_weight lm + length_bonus |y|; detail then appends lm to each hypothesis."""
+        the rank (1 - ctc_weight) att + ctc_weight ctc + lm_weight lm + length_bonus |y|; detail then appends lm to each hypothesis.
+        context: a ContextSet on the engine's device: hotword biasing inside the search, the rank gains the
+        hypothesis's bonus; graph_ids: one graph id per utterance (default graph 0 for all, -1 = unbiased); detail then appends
+        bonus and final.  The context scores the pre-beam only: a hotword outside a row's pre_beam best is not rescued."""
         if self.rescorer is None:
             raise _lib.M3Error("CtcDecoder.attention: built without a rescorer (CtcDecoder(engine, rescorer=AttentionRescorer(...)))")
         from .aed_search import AttentionBeamSearch
@@ -399,15 +402,16 @@ class CtcDecoder:
             raise _lib.M3Error("CtcDecoder.attention: max_steps = %d, need at least 1" % steps)
         # the searcher (state, K / V cache, work buffers) is kept across calls: sized by the step bound rounded up to a multiple
         # of 64 and re-allocated only when a call needs more; the call's own bound goes to search()
-        key = (B, int(beam_size), float(ctc_weight), pre_beam, id(lm), float(lm_weight), float(length_bonus))
+        key = (B, int(beam_size), float(ctc_weight), pre_beam, id(lm), float(lm_weight), float(length_bonus), id(context))
         kept = getattr(self, "_attention_search", None)
         if kept is None or kept[0] != key or kept[1].max_steps < steps:
             bound = min(-(-steps // 64) * 64, self.rescorer.cfg.max_len - 1)
             kept = self._attention_search = (key, AttentionBeamSearch(self.rescorer, B, beam_size, bound, ctc_weight=ctc_weight,
                                                                              pre_beam=pre_beam, lm=lm, lm_weight=lm_weight,
-                                                                             length_bonus=length_bonus))
+                                                                             length_bonus=length_bonus, context=context))
         ctc = res["out_nosm"][:, :frames] if float(ctc_weight) > 0 else None
-        return kept[1].search(memory, res["out_lens"].cpu(), raw_memory=True, detail=detail, max_steps=steps, ctc_logits=ctc)
+        return kept[1].search(memory, res["out_lens"].cpu(), raw_memory=True, detail=detail, max_steps=steps, ctc_logits=ctc,
+                              graph_ids=graph_ids)
 
     def align(self, xs: torch.Tensor, xs_lens: torch.Tensor, tokens, frame_ms=40):
         """Encoder forward, then the best CTC alignment of tokens[b] to utterance b's frames (m3asr.align): one

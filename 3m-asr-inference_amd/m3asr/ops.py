@@ -1332,6 +1332,78 @@ def aed_lm_result(desc, state, lstate):
     return out
 
 
+# ---- hotword biasing in that search (m3_aed_bias_*)
+def aed_bias_desc(search_desc, pre_beam, max_frames=0):
+    """The descriptor of the biased search: m3_aed_joint_desc; max_frames = 0 where there is no CTC part (ctc_weight = 0).
+    Raises M3Error on what the library rejects."""
+    d = _lib.AedJointDesc(search_desc, int(pre_beam), int(max_frames))
+    if _lib.load().m3_aed_bias_state_size(C.byref(d)) == 0:
+        raise _lib.M3Error("m3_aed_bias_state_size failed: " + _lib.last_error())
+    return d
+
+
+def aed_bias_state_size(desc):
+    return _lib.load().m3_aed_bias_state_size(C.byref(desc))
+
+
+def aed_bias_scratch_size(desc):
+    return _lib.load().m3_aed_bias_scratch_size(C.byref(desc))
+
+
+def aed_bias_record(image, graph_of, cstate, cscratch):
+    """m3_aed_bias: the device context image (int32 words), graph_of (B,) int32 on the device (either may be None where the call
+    does not read it), the context state and scratch (uint8 blobs)"""
+    img, nbytes = _image(image)
+    b = _lib.AedBias()
+    b.image, b.image_bytes = (img.value if img is not None else None), nbytes
+    b.graph_of = graph_of.data_ptr() if graph_of is not None else None
+    if graph_of is not None:
+        assert graph_of.is_cuda and graph_of.dtype == torch.int32 and graph_of.is_contiguous()
+    b.state, b.state_bytes = (cstate.data_ptr(), _nbytes(cstate)) if cstate is not None else (None, 0)
+    b.scratch, b.scratch_bytes = (cscratch.data_ptr(), _nbytes(cscratch)) if cscratch is not None else (None, 0)
+    return b
+
+
+def aed_bias_reset(desc, bias):
+    """after aed_search_reset (and the joint / LM resets): every slot in state 0 with bonus 0.0; refuses an image of another V"""
+    check(_lib.load().m3_aed_bias_reset(C.byref(desc), C.byref(bias), _stream()), "m3_aed_bias_reset")
+
+
+def aed_bias_score(desc, state, jstate, scratch, lstate, lscratch, logits, ctc, ctc_weight, lm_image, lm_on, alpha, beta, use_eos, bias):
+    """aed_lm_score with every candidate's context arc and the biased key; lm_image / lm_on / lstate / lscratch None exactly when
+    there is no LM, ctc / jstate / scratch None exactly when ctc_weight = 0"""
+    lp, ldl = _rows(logits)
+    cp, ldc = _rows(ctc) if ctc is not None else (None, 0)
+    assert tuple(logits.shape) == (desc.search.B * desc.search.beam, desc.search.V)
+    assert lm_on is None or lm_on.numel() == desc.search.B
+    lmi, lm_bytes = _image(lm_image)
+    nb = lambda t: _nbytes(t) if t is not None else 0   # noqa: E731
+    check(_lib.load().m3_aed_bias_score(C.byref(desc), _p(state), _nbytes(state), _p(jstate), nb(jstate), _p(scratch), nb(scratch),
+                                        _p(lstate), nb(lstate), _p(lscratch), nb(lscratch), lp, ldl, cp, ldc,
+                                        ctc.shape[0] if ctc is not None else 0, float(ctc_weight), lmi, lm_bytes, _i32(lm_on),
+                                        float(alpha), float(beta), int(bool(use_eos)), C.byref(bias), _stream()), "m3_aed_bias_score")
+
+
+def aed_bias_prune(desc, state, jstate, scratch, lstate, lscratch, bias, done=None):
+    """aed_lm_prune, the survivors' context state copied from the context scratch; jstate / scratch None: no CTC; lstate / lscratch
+    None: no LM"""
+    assert done is None or done.numel() == desc.search.B
+    nb = lambda t: _nbytes(t) if t is not None else 0   # noqa: E731
+    check(_lib.load().m3_aed_bias_prune(C.byref(desc), _p(state), _nbytes(state), _p(jstate), nb(jstate), _p(scratch), nb(scratch),
+                                        _p(lstate), nb(lstate), _p(lscratch), nb(lscratch), C.byref(bias), _i32(done), _stream()),
+          "m3_aed_bias_prune")
+
+
+def aed_bias_result(desc, state, bias):
+    """-> dict(bonus (B, beam) float32, ctx_state (B, beam) int32, ctx_att (B, beam) float32) on the device"""
+    B, N, dev = desc.search.B, desc.search.beam, state.device
+    out = dict(bonus=torch.empty(B, N, dtype=torch.float32, device=dev), ctx_state=torch.empty(B, N, dtype=torch.int32, device=dev),
+               ctx_att=torch.empty(B, N, dtype=torch.float32, device=dev))
+    check(_lib.load().m3_aed_bias_result(C.byref(desc), _p(state), _nbytes(state), C.byref(bias), _p(out["bonus"]), _p(out["ctx_state"]),
+                                         _p(out["ctx_att"]), _stream()), "m3_aed_bias_result")
+    return out
+
+
 # ---------------------------------------------------------------------------------------- streaming operators
 def cat_split_cache(in_cache, inp):
     """CatSplitCache plugin: (output (B, cache+input), out_cache (B, cache)); f32 or i32 rows."""

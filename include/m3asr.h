@@ -1257,6 +1257,63 @@ int m3_aed_ngram_prune(const m3_aed_joint_desc* desc, void* search_state, size_t
 int m3_aed_ngram_result(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, const void* lm_state,
                      size_t lm_state_bytes, float* lm, int32_t* lm_state_out, int32_t* n, float* att, m3_stream stream);
 
+/* Hotword biasing in that search (csrc/aed_joint.hip): every candidate also takes one arc of its utterance's graph
+ * in a context set ("context set" above: the image, its limits and m3_ctc_context_validate are the CTC search's, unchanged) and
+ * is ranked by
+ *   key = jkey + (float)extra,   extra = (alpha * lm + beta * n) + bonus with an LM, bonus without,
+ * in double, rounded once; jkey as above (att when ctc_weight = 0).  A -inf jkey stays -inf.  The graph's own score is the
+ * weight: there is no further multiplier.  A hypothesis carries ctx_state (0 for [sos]) and bonus (double, 0.0).  A token c that
+ * is not eos adds delta[ctx_state][cls[c]] and moves to next[ctx_state][cls[c]]; eos (V - 1) is never walked: it subtracts
+ * pot[ctx_state], the credit of a phrase the hypothesis did not complete, and ends in state 0, so a finished hypothesis's bonus is
+ * the context contract's `final`.  A hypothesis cut at the step limit keeps its provisional credit in its key; final is then
+ * bonus - pot[ctx_state], which the caller forms from what the result call returns.  A finished slot keeps key, bonus and state.
+ * The context scores the PRE-BEAM, like the LM: a row offers its pre_beam largest attention log-probabilities whatever ctc_weight
+ * and the LM are, and a hotword token outside them is not rescued.
+ * graph_of (device int32 [B]) picks a graph per utterance; -1, a value outside [0, G), an image whose header fails its checks or
+ * one built for another V mean "unbiased": that utterance's records, keys, parts, scorer state and LM state are, bit for bit,
+ * those of the same search without a context, and its context state stays (0, 0.0).
+ * The calls below stand where the joint / ngram score and prune calls stood, so the step keeps its 8 L + 4 launches.  They take
+ * what the m3_aed_ngram_* calls take, with two freedoms: lm_image, lm_on, lm_state and lm_scratch are NULL exactly when there is
+ * no LM (alpha, beta and use_eos are then not used but must be finite), and ctc, joint_state and scratch are NULL exactly when
+ * ctc_weight == 0.  With neither, the context state keeps the att part and the context scratch the candidate records.
+ * m3_aed_bias: image / image_bytes: the DEVICE context image; graph_of; state: caller-owned, m3_aed_bias_state_size bytes,
+ *   16-byte aligned: per row, double-buffered by the parity of the utterance's step: ctx_state, att, bonus (double); scratch:
+ *   caller-owned, m3_aed_bias_scratch_size bytes, 16-byte aligned, rewritten by every step: every candidate's (ctx_state, bonus),
+ *   from which prune copies the survivors' (nothing is walked twice), and the candidate records of the form without CTC and LM.
+ *   Both sizes depend on B, beam and pre_beam only.
+ * reset: after the search's (and the joint and ngram) reset, once per search.  Reads the image's 4-word header back (a
+ *   synchronous copy: call it outside a stream capture) and refuses an image that is not a context set or was built for another
+ *   V; every slot then holds state 0, bonus 0.0.  The image itself must have passed m3_ctc_context_validate on the host.
+ * score: one wave per row; the row's ctx_state is wave-uniform, so all lanes gather cls[token], then one row of delta / next.  The
+ *   kernel range-checks every word it forms an address from (a bad state or next entry means state 0, a bad class column 0).
+ * prune: the survivors' (ctx_state, bonus) go to the other buffer.  image / graph_of of the record are not read.
+ * result: bonus [B][beam] (the float32 rounding of the double) and ctx_state of the hypotheses the search's result call returns;
+ *   att (NULL or [B][beam]): the attention parts as the context state holds them for the form without CTC and LM.
+ * Every call refuses, before any launch: a bad descriptor, a blob that is too small or misaligned, a NULL mismatch, a weight that
+ * is not finite. */
+typedef struct m3_aed_bias {
+  const void* image;       /* device context image */
+  size_t image_bytes;
+  const int32_t* graph_of; /* device, [B] */
+  void* state;
+  size_t state_bytes;
+  void* scratch;
+  size_t scratch_bytes;
+} m3_aed_bias;
+size_t m3_aed_bias_state_size(const m3_aed_joint_desc* desc);
+size_t m3_aed_bias_scratch_size(const m3_aed_joint_desc* desc);
+int m3_aed_bias_reset(const m3_aed_joint_desc* desc, const m3_aed_bias* bias, m3_stream stream);
+int m3_aed_bias_score(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, const void* joint_state,
+                      size_t joint_state_bytes, void* scratch, size_t scratch_bytes, const void* lm_state, size_t lm_state_bytes,
+                      void* lm_scratch, size_t lm_scratch_bytes, const float* logits, int ldl, const float* ctc, int ldc, int ctc_rows,
+                      float ctc_weight, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha, double beta, int use_eos,
+                      const m3_aed_bias* bias, m3_stream stream);
+int m3_aed_bias_prune(const m3_aed_joint_desc* desc, void* search_state, size_t search_state_bytes, void* joint_state, size_t joint_state_bytes,
+                      const void* scratch, size_t scratch_bytes, void* lm_state, size_t lm_state_bytes, const void* lm_scratch,
+                      size_t lm_scratch_bytes, const m3_aed_bias* bias, int32_t* done, m3_stream stream);
+int m3_aed_bias_result(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, const m3_aed_bias* bias,
+                       float* bonus, int32_t* ctx_state, float* att, m3_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -38,6 +38,9 @@ best hypothesis of each utterance.  With --ctc-weight W > 0 the search is the on
 is also scored by its CTC prefix probability on the forward's own CTC output and ranked by (1 - W) att + W ctc; --pre-beam P
 candidates per hypothesis go to the CTC scorer.  Both parts are printed.  With --lm the n-gram LM is fused into this search
 (not into a prefix beam search): the rank gains lm_weight log P_LM + length_bonus per token, and the LM part is printed too.
+With --hotwords words.txt [--hotword-score S] the phrase list also biases this search (it scores the pre-beam, so a
+hotword outside a hypothesis's --pre-beam best is not rescued) and the line ends its parts with bonus=; the separate biased
+prefix beam search of the list is still run and printed.
 
     python3 infer.py -p encoder.plan -i feat.npy --timestamps [any of the modes above]
 
@@ -202,14 +205,21 @@ def print_attention(helper, feat, feat_len, args):
     rescorer = AttentionRescorer(helper.decoder_packed, decoder_config_of(helper.extra), helper.engine.device)
     dec = CtcDecoder(helper.engine, rescorer=rescorer)
     lm = load_lm(args, rescorer.cfg.vocab, helper.engine.device) if args.lm else None
+    ctx = None
+    if args.hotwords:                                             # the list also goes into the attention search
+        from m3asr.context import ContextGraph, ContextSet, read_phrases
+        V = rescorer.cfg.vocab
+        ctx = ContextSet([ContextGraph(read_phrases(args.hotwords), V, score=args.hotword_score)], device=helper.engine.device)
     out = dec.attention(torch.from_numpy(feat), torch.from_numpy(feat_len), args.beam, max_steps=args.max_steps, detail=True,
                         ctc_weight=args.ctc_weight, pre_beam=args.pre_beam, lm=lm, lm_weight=args.lm_weight,
-                        length_bonus=args.length_bonus)
+                        length_bonus=args.length_bonus, context=ctx)
     for b, (best, hyps) in enumerate(out):
         chosen = next(h for h in hyps if list(h[0]) == best)
-        parts = " att=%.4f ctc=%.4f" % (chosen[3], chosen[4]) if args.ctc_weight > 0 or lm is not None else ""
+        parts = " att=%.4f ctc=%.4f" % (chosen[3], chosen[4]) if args.ctc_weight > 0 or lm is not None or ctx is not None else ""
         if lm is not None:
             parts += " lm=%.4f" % chosen[5]
+        if ctx is not None:                                       # what the key holds; equal to the final credit once finished
+            parts += " bonus=%.4f" % chosen[-2]
         print("utt %d attention: score=%.4f%s finished=%d tokens=%s" % (b, chosen[1], parts, chosen[2], " ".join(str(t) for t in best)))
     return [list(best) for best, _ in out]
 

@@ -21,6 +21,11 @@ beside "device_*"), and reports the fused hypotheses' lengths.  --table also pri
 in {0, --lm-weight} x {0, 1, 2, 4, 6} with the lengths (all hypotheses and the best of each beam) and the finished count: one search
 each, nothing timed.  The weights are synthetic: the table shows lengths, not accuracy.
 
+--context N times the search biased by a context graph of N random phrases of 2 to 4 tokens (--context-score per
+token) NEXT TO the plain search of the same build, model, memories and --ctc-weight ("biased_*" beside "device_*"); with --lm
+the biased search is fused with the LM too.  With --ctc-weight 0 and no LM the plain search has no pre-beam (8 L + 3 launches),
+the biased one has (8 L + 4).
+
 "device": wall time of AttentionBeamSearch.search() per call -- the K / V GEMM, every step's launches, the polls of the done
 flags and the read of the results -- median over the rounds after a warm-up; us per step = that over the steps issued.
 "eager": the same search as tests/aed_search_ref.py states it -- every hypothesis on its own, the prefix recomputed at every
@@ -94,6 +99,8 @@ def main():
     ap.add_argument("--lm-weight", type=float, default=0.5)
     ap.add_argument("--length-bonus", type=float, default=0.0)
     ap.add_argument("--table", action="store_true", help="--lm: the hypothesis-length table over lm_weight x length_bonus")
+    ap.add_argument("--context", type=int, default=None, metavar="N_PHRASES", help="also time the search biased by N random phrases of 2 to 4 tokens")
+    ap.add_argument("--context-score", type=float, default=2.0)
     a = ap.parse_args()
     import aed_search_ref
     from m3asr.aed_search import AttentionBeamSearch
@@ -172,8 +179,28 @@ def main():
                     row = lengths_of(fused.search(mem_d, mem_len, detail=True, **call))
                     print(json.dumps(dict(table="hypothesis lengths", eos_bias=a.eos_bias, ctc_weight=a.ctc_weight, max_steps=steps,
                                           lm_weight=lw, length_bonus=lb, steps_issued=fused.steps_issued, **row)))
+    if a.context is not None:
+        import numpy as np
+        from m3asr.context import ContextGraph, ContextSet
+        rng = np.random.default_rng(7)
+        phrases = set()
+        while len(phrases) < a.context:
+            phrases.add(tuple(int(t) for t in rng.integers(1, dcfg.vocab - 1, size=int(rng.integers(2, 5)))))
+        graph = ContextGraph([list(p) for p in sorted(phrases)], dcfg.vocab, score=a.context_score)
+        ctx = ContextSet([graph], device="cuda:0")
+        lmkw = dict(lm=lm, lm_weight=a.lm_weight, length_bonus=a.length_bonus) if lm is not None else {}
+        biased = AttentionBeamSearch(res, B, beam, steps, poll=a.poll, ctc_weight=a.ctc_weight, pre_beam=a.pre_beam, context=ctx, **lmkw)
+        bout = biased.search(mem_d, mem_len, detail=True, **call)
+        bonus = [h[-2] for u in bout for h in u[1]]
+        record["context"] = dict(phrases=len(graph.phrases), states=graph.n_states, columns=graph.A, image_bytes=int(ctx.image.nbytes),
+                                 score=a.context_score, pre_beam=biased.pre_beam, launches_per_step=biased.launches_per_step(),
+                                 with_lm=lm is not None, hyps_with_bonus="%d/%d" % (sum(1 for v in bonus if v != 0), len(bonus)),
+                                 finished="%d/%d" % (sum(int(h[2]) for u in bout for h in u[1]), B * beam))
+        timed(lambda: biased.search(mem_d, mem_len, **call), 3)
+        add("biased", biased, timed(lambda: biased.search(mem_d, mem_len, **call), a.rounds))
+        record["biased_over_device"] = round(record["biased_ms_median"] / record["device_ms_median"], 3)
     if a.graph:
-        graphed = AttentionBeamSearch(res, B, beam, steps, poll=a.poll, use_graph=True, **joint)
+        graphed =AttentionBeamSearch(res, B, beam, steps, poll=a.poll, use_graph=True, **joint)
         same = graphed.search(mem_d, mem_len, detail=True, **call) == out
         same = same and torch.equal(graphed.last["score"].view(torch.int32), search.last["score"].view(torch.int32))
         record["graph_same_bits"] = bool(same)
