@@ -45,7 +45,7 @@ int moe_expert_ffn_dt(const float* x, const int32_t* gate_idx, const float* w1, 
                       const float* b2, int S, int E, int D, int F, const float* gate_value, const float* resid,
                       float alpha, const float* ln_gamma, const float* ln_beta, float ln_eps, float* y, void* ws,
                       size_t ws_bytes, hipStream_t stream, ExpertWeights weights, const float* s1 = nullptr, const float* s2 = nullptr, float h_scale = 0.f, const void* xq = nullptr,
-                      const float* xq_scale = nullptr, int ldx = 0) {
+                      const float* xq_scale = nullptr, int ldx = 0, int w_layout = EXPERT_W_REF) {
   M3_REQUIRE(S >= 0 && E > 0 && D > 0 && F > 0, "fmoe_expert: bad sizes S=%d E=%d D=%d F=%d", S, E, D, F);
   if (S == 0) return 0;
   MoeWorkspace w = carve_moe_workspace(ws, S, E, D, F);
@@ -56,7 +56,7 @@ int moe_expert_ffn_dt(const float* x, const int32_t* gate_idx, const float* w1, 
   const ExpertFfnPlan plan = plan_expert_ffn(weights, S, E, D, F);
   ExpertFfnArgs a{};
   a.x = x; a.ldx = ldx > 0 ? ldx : D; a.pos = w.pos; a.acc_hist = w.acc; a.w1 = w1; a.w2 = w2; a.s1 = s1; a.s2 = s2; a.b1 = b1;
-  a.h_scale = h_scale; a.slab = w.slab; a.xq = xq; a.xq_scale = xq_scale;
+  a.h_scale = h_scale; a.slab = w.slab; a.xq = xq; a.xq_scale = xq_scale; a.w2_sliced = w_layout;
   rc = launch_expert_ffn(plan, S, E, D, F, a, stream);
   if (rc) return rc;
   return launch_moe_combine(plan.rows(w.slab), plan.slices, w.mapping, gate_idx, gate_value, b2, resid, alpha, ln_gamma, ln_beta, ln_eps,
@@ -104,6 +104,15 @@ int m3_moe_expert_ffn(const float* x, const int32_t* gate_idx, const float* w1, 
                       float* y, void* workspace, size_t workspace_bytes, m3_stream stream) {
   return moe_expert_ffn(x, gate_idx, w1, b1, w2, b2, S, num_expert, idim, hidden_units, gate_value, resid, alpha,
                         ln_gamma, ln_beta, ln_eps, y, workspace, workspace_bytes, (hipStream_t)stream);
+}
+// w1 / w2 in fragment order (launch_expert_ffn takes them on the fp32 slab form alone and refuses the rest)
+int m3_moe_expert_ffn_wfrag(const float* x, const int32_t* gate_idx, const float* w1, const float* b1, const float* w2,
+                            const float* b2, int S, int num_expert, int idim, int hidden_units, const float* gate_value,
+                            const float* resid, float alpha, const float* ln_gamma, const float* ln_beta, float ln_eps,
+                            float* y, void* workspace, size_t workspace_bytes, m3_stream stream) {
+  return moe_expert_ffn_dt(x, gate_idx, w1, b1, w2, b2, S, num_expert, idim, hidden_units, gate_value, resid, alpha, ln_gamma, ln_beta,
+                           ln_eps, y, workspace, workspace_bytes, (hipStream_t)stream, ExpertWeights::F32, nullptr, nullptr, 0.f, nullptr,
+                           nullptr, 0, EXPERT_W_FRAG);
 }
 int m3_moe_expert_ffn_bf16(const float* x, const int32_t* gate_idx, const void* w1, const float* b1, const void* w2,
                            const float* b2, int S, int num_expert, int idim, int hidden_units, const float* gate_value,
@@ -371,6 +380,35 @@ int m3_linear_ws(const m3_linear_desc* d, void* workspace, size_t workspace_byte
   if (int rc = linear_pointers(d)) return rc;
   return launch_gemm(gemm_launch(p, (float*)workspace, workspace_bytes), (hipStream_t)stream);
 }
+// desc->w in fragment order (m3_pack_wfrag_host): the plan takes it on the skinny fp32 kernel alone and refuses the rest
+int m3_linear_wfrag(const m3_linear_desc* d, m3_stream stream) {
+  GemmParams p;
+  if (int rc = linear_params(d, &p)) return rc;
+  if (int rc = linear_pointers(d)) return rc;
+  M3_REQUIRE(aligned16(d->w), "linear: fragment-ordered w must be 16-byte aligned");
+  p.w_frag = 1;
+  return launch_gemm(gemm_launch(p, nullptr, 0), (hipStream_t)stream);
+}
+const char* m3_linear_wfrag_kernel(const m3_linear_desc* d) {
+  GemmParams p;
+  if (linear_params(d, &p)) return nullptr;
+  p.w_frag = 1;
+  const GemmPlan plan = plan_gemm(p, 0);
+  if (plan.launches == 0) set_error("%s", plan.reason);
+  return plan.launches ? plan.label : nullptr;
+}
+int m3_pack_wfrag_host(const float* w, int N, int K, float* wf) {
+  M3_REQUIRE(w != nullptr && wf != nullptr && N > 0 && K > 0 && N % 16 == 0 && K % 16 == 0,
+             "pack_wfrag: N=%d and K=%d must be positive multiples of 16", N, K);
+  const int nsteps = K / 16;
+  for (int nt = 0; nt < N / 16; ++nt)
+    for (int s = 0; s < nsteps; ++s)
+      for (int kq = 0; kq < 4; ++kq)
+        for (int col = 0; col < 16; ++col)
+          for (int j = 0; j < 4; ++j)
+            wf[((((size_t)nt * nsteps + s) * 4 + kq) * 16 + col) * 4 + j] = w[(size_t)(16 * nt + col) * K + 16 * s + 4 * kq + j];
+  return 0;
+}
 
 int m3_layer_norm(const float* x, const float* gamma, const float* beta, float eps, float* y, int rows, int dim,
                   m3_stream stream) {
@@ -616,6 +654,20 @@ int m3_linear_pair(const m3_linear_desc* a, const m3_linear_desc* b, m3_stream s
   if (int rc = linear_params(b, &pb)) return rc;
   if (int rc = linear_pointers(a)) return rc;
   if (int rc = linear_pointers(b)) return rc;
+  const GemmLaunch qa = gemm_launch(pa, nullptr, 0), qb = gemm_launch(pb, nullptr, 0);
+  if (int rc = linear_pair_plans(qa, qb)) return rc;
+  M3_REQUIRE(!ranges_overlap(a->y, linear_out_bytes(a), b->y, linear_out_bytes(b)), "linear pair: the two outputs overlap");
+  return launch_gemm_f32_dual(qa, qb, (hipStream_t)stream);
+}
+// both w in fragment order (gemm_dual_fusable: the two problems agree on the layout)
+int m3_linear_pair_wfrag(const m3_linear_desc* a, const m3_linear_desc* b, m3_stream stream) {
+  GemmParams pa, pb;
+  if (int rc = linear_params(a, &pa)) return rc;
+  if (int rc = linear_params(b, &pb)) return rc;
+  if (int rc = linear_pointers(a)) return rc;
+  if (int rc = linear_pointers(b)) return rc;
+  M3_REQUIRE(aligned16(a->w) && aligned16(b->w), "linear pair: fragment-ordered w must be 16-byte aligned");
+  pa.w_frag = pb.w_frag = 1;
   const GemmLaunch qa = gemm_launch(pa, nullptr, 0), qb = gemm_launch(pb, nullptr, 0);
   if (int rc = linear_pair_plans(qa, qb)) return rc;
   M3_REQUIRE(!ranges_overlap(a->y, linear_out_bytes(a), b->y, linear_out_bytes(b)), "linear pair: the two outputs overlap");

@@ -38,7 +38,8 @@ using namespace m3;
 namespace {
 
 struct Norm { const float* g = nullptr; const float* b = nullptr; };
-struct Lin { const float* w = nullptr; const float* b = nullptr; const float* wsum = nullptr; const float* wbeta = nullptr; };
+// wf: the same weight in MFMA-fragment order (kernels.h GemmParams::w_frag), where the plan holds one: what the skinny fp32 form reads
+struct Lin { const float* w = nullptr; const float* b = nullptr; const float* wsum = nullptr; const float* wbeta = nullptr; const float* wf = nullptr; };
 
 struct BlockW {
   Norm n_ffm, n_mha, n_conv, n_ff, n_final, n_cnn;
@@ -49,6 +50,7 @@ struct BlockW {
   Lin router;                       // w: [E_total][D + De]  (unfused route path)
   Lin router_x;                     // w: [E][D] x-half with norm_ff folded (+ wsum, bias)  (fused route path)
   const float *ew1 = nullptr, *eb1 = nullptr, *ew2 = nullptr, *eb2 = nullptr;
+  const float *ew1f = nullptr, *ew2f = nullptr;   // fp32 experts in fragment order (both or neither): what expert_ffn_f32_kernel reads
   const float *es1 = nullptr, *es2 = nullptr;   // fp8 experts: per-row scales [E][F], [E][D]; mxfp4 experts: the e8m0 scale BYTES [E][F][D/32], [E][F/64][D][2]
   float h_scale = 0.f;                          // fp8 arithmetic: static scale of the hidden activations (0 = weight-only)
 };
@@ -198,6 +200,9 @@ struct Switches {
   // M3_GLU_SIG_EPI (1): 0 = a deferred GLU's gate columns leave pointwise_conv1 raw and the depthwise kernel sigmoids them per
   // tap.  1: pointwise_conv1's epilogue stores sigmoid(gate) (GemmParams::sig_col0), the depthwise kernel multiplies
   bool glu_sig_epi;
+  // M3_W_FRAG (1): 0 = the fragment-ordered copies of the fp32 weights (names ending in "_frag") are ignored: the skinny GEMMs and
+  // the one-launch expert kernel read the row-major / slice-major tensors, as every other form always does
+  bool w_frag;
 };
 const Switches& switches() {
   static const Switches sw = [] {
@@ -214,6 +219,7 @@ const Switches& switches() {
     w.front_pair = num("M3_FRONT_PAIR", 1) != 0;
     w.router_prefix = num("M3_ROUTER_PREFIX", 1) != 0;
     w.glu_sig_epi = num("M3_GLU_SIG_EPI", 1) != 0;
+    w.w_frag = num("M3_W_FRAG", 1) != 0;
     return w;
   }();
   return sw;
@@ -253,8 +259,15 @@ bool load_norm(const m3_engine* e, const std::string& p, int d, Norm* n) {
   GET(n->b, p + "bias", d);
   return true;
 }
+// the optional fragment-ordered copy of an fp32 tensor (Engine.__init__ derives it; absent: the stages read `name` itself)
+const float* lookup_frag(const m3_engine* e, const std::string& name, int64_t numel) {
+  if (!switches().w_frag || e->cfg.weight_dtype != M3_F32) return nullptr;
+  auto it = e->table.find(name + "_frag");
+  return it != e->table.end() && it->second.numel == numel && it->second.dtype == M3_F32 ? (const float*)it->second.data : nullptr;
+}
 bool load_lin(const m3_engine* e, const std::string& p, int64_t n_out, int64_t n_in, bool bias, Lin* l) {
   GETW(l->w, p + "weight", n_out * n_in);
+  l->wf = lookup_frag(e, p + "weight", n_out * n_in);
   if (bias) GET(l->b, p + "bias", n_out);
   return true;
 }
@@ -266,6 +279,7 @@ bool load_lin_ln(const m3_engine* e, const std::string& p, int64_t n_out, int64_
   } else {
     GETW(l->w, p + "ln.weight", n_out * n_in);
   }
+  if (!fp32_only) l->wf = lookup_frag(e, p + "ln.weight", n_out * n_in);
   GET(l->b, p + "ln.bias", n_out);
   GET(l->wsum, p + "ln.wsum", n_out);
   if (wbeta) GET(l->wbeta, p + "ln.wbeta", n_out);
@@ -323,6 +337,9 @@ bool load_block(const m3_engine* e, const std::string& p, int D, int F, int K, b
     GET(b->eb1, p + "feed_forward.experts.w_1.bias", E * F);
     GETE(b->ew2, p + "feed_forward.experts.w_2.weight_sliced", ew_numel);
     GET(b->eb2, p + "feed_forward.experts.w_2.bias", E * D);
+    b->ew1f = lookup_frag(e, p + "feed_forward.experts.w_1.weight", ew_numel);
+    b->ew2f = lookup_frag(e, p + "feed_forward.experts.w_2.weight", ew_numel);
+    if (!b->ew1f || !b->ew2f) b->ew1f = b->ew2f = nullptr;
   }
   return true;
 }
@@ -699,10 +716,18 @@ static void add_launch(StageBuilder& sb, const std::string& name, Launch record,
 }
 
 // fp32_weights: the router GEMMs keep fp32 weights in every mode (a flipped top-1 is a discrete error)
-static void add_gemm(StageBuilder& sb, const std::string& name, GemmParams p, bool fp32_weights = false) {
+// wfrag: p.W in fragment order (Lin::wf), read instead where the bound shape plans as the skinny fp32 form and the plan takes the
+// layout -- the same form, instantiation and grid, only the weight addresses differ; every other form reads the row-major p.W
+static void add_gemm(StageBuilder& sb, const std::string& name, GemmParams p, bool fp32_weights = false, const float* wfrag = nullptr) {
   p.w_bf16 = (!fp32_weights && sb.eng.cfg.weight_dtype != M3_F32) ? 1 : 0;
   // planned once, when the shape is bound: the stage runs the record made here (a plan no kernel takes fails there, with its reason)
-  const GemmLaunch g = gemm_launch(p, sb.splitk_ws, sb.splitk_bytes);
+  GemmLaunch g = gemm_launch(p, sb.splitk_ws, sb.splitk_bytes);
+  if (wfrag != nullptr && g.plan.launches == 1 && g.plan.kernel == GemmKernel::SkinnyF32) {
+    GemmParams q = p;
+    q.W = wfrag; q.w_frag = 1;
+    const GemmLaunch gf = gemm_launch(q, sb.splitk_ws, sb.splitk_bytes);
+    if (gf.plan.launches == 1) g = gf;
+  }
   m3_stage_info info = gemm_info(p, g.plan);
   info.launches = g.plan.launches ? g.plan.launches : 1;
   add_launch(sb, name, g, info, g.plan.launches == 1);   // (a split-K stage: build_subsample decides whether it may pair)
@@ -949,7 +974,7 @@ static void add_moe_local_index(StageBuilder& sb, const MoeLayer& m) {
 static ExpertFfnArgs expert_args(const BlockW& w, const float* x, const MoeWorkspace& mw, int D) {
   ExpertFfnArgs a{};
   a.x = x; a.ldx = D; a.pos = mw.pos; a.acc_hist = mw.acc; a.w1 = w.ew1; a.w2 = w.ew2; a.s1 = w.es1; a.s2 = w.es2; a.b1 = w.eb1;
-  a.w2_sliced = 1; a.h_scale = w.h_scale; a.slab = mw.slab;
+  a.w2_sliced = EXPERT_W2_SLICED; a.h_scale = w.h_scale; a.slab = mw.slab;
   return a;
 }
 
@@ -964,11 +989,13 @@ static void add_moe_local_expert(StageBuilder& sb, const MoeLayer& m, const MoeR
     const float* ln_g = norm ? w.n_ff.g : nullptr; const float* ln_b = norm ? w.n_ff.b : nullptr; const float ln_eps = norm ? m.eps : 0.f;
     // short inputs, fp32: SoftmaxTopK + ScatterMapping happen inside the expert launch (every work-group derives its expert's
     // rows from the router logits; moe_expert.hip "self-routing form"); its slabs hold ORIGINAL rows, b2 inside
+    const bool wf = w.ew1f != nullptr;   // (fp32 experts in fragment order: the one-launch kernel's two forms read them)
     if (self_route)
-      return launch_expert_route_ffn_f32(xin, m.D, m.rl, m.live_len, m.live_rpb, m.S, m.E, m.D, m.F, w.ew1, w.eb1, w.ew2, 1, w.eb2,
-                                         m.mw.slab, m.gidx, m.gval, m.mw.mapping, m.mw.acc, m.mw.pos, s, ln_g, ln_b, ln_eps);
+      return launch_expert_route_ffn_f32(xin, m.D, m.rl, m.live_len, m.live_rpb, m.S, m.E, m.D, m.F, wf ? w.ew1f : w.ew1, w.eb1,
+                                         wf ? w.ew2f : w.ew2, wf ? EXPERT_W_FRAG : EXPERT_W2_SLICED, w.eb2, m.mw.slab, m.gidx, m.gval, m.mw.mapping, m.mw.acc, m.mw.pos, s, ln_g, ln_b, ln_eps);
     ExpertFfnArgs a = expert_args(w, xin, m.mw, m.D);
     a.ln_gamma = ln_g; a.ln_beta = ln_b; a.ln_eps = ln_eps; a.xq = xq; a.xq_scale = xqs; a.fs_dev = fs;
+    if (wf && f.kernel == ExpertKernel::SlabF32) { a.w1 = w.ew1f; a.w2 = w.ew2f; a.w2_sliced = EXPERT_W_FRAG; }
     return launch_expert_ffn(f, m.S, m.E, m.D, m.F, a, s);
   }, stage_info(f.label, 1, -1.0, 4.0 * m.D * m.F * m.S));
 }
@@ -1047,9 +1074,9 @@ static void add_moe_ep(StageBuilder& sb, const MoeLayer& m, const MoeRoute& r, c
 static void build_block(StageBuilder& sb, const std::string& pfx, const BlockW& w, int D, int F, int H, int K, bool cnn_ln,
                         bool moe, int layer, int tap_index, const Plan& pl, bool causal) {
   // every GEMM of a block is row-wise over the S rows of the batch: packed batches pass the live-row count
-  auto add_gemm = [&](StageBuilder&, const std::string& name, GemmParams g, bool fp32_weights = false) {
+  auto add_gemm = [&](StageBuilder&, const std::string& name, GemmParams g, bool fp32_weights = false, const float* wfrag = nullptr) {
     if (sb.bd.packed) g.m_dev = pl.row0 + sb.bd.key.B;
-    ::add_gemm(sb, name, g, fp32_weights);
+    ::add_gemm(sb, name, g, fp32_weights, wfrag);
   };
   const m3_engine_config& c = sb.eng.cfg;
   const BindKey& key = sb.bd.key;
@@ -1091,12 +1118,12 @@ static void build_block(StageBuilder& sb, const std::string& pfx, const BlockW& 
     g.A = x; g.lda = D; g.W = w.mac1.w; g.bias = w.mac1.b; g.Y = pl.h1; g.ldy = F; g.M = S; g.N = F; g.K = D;
     g.ln_wsum = w.mac1.wsum; g.ln_eps = eps; g.act = ACT_SILU;   // norm_ff_macaron is folded into w_1 (plan.py)
     from_xb(g); g.y_bf16 = a16;
-    add_gemm(sb, pfx + "ffn_macaron.w1", g);
+    add_gemm(sb, pfx + "ffn_macaron.w1", g, false, w.mac1.wf);
     GemmParams h;
     h.A = pl.h1; h.lda = F; h.W = w.mac2.w; h.bias = w.mac2.b; h.Y = x; h.ldy = D; h.M = S; h.N = D; h.K = F;
     h.alpha = 0.5f; h.resid = x; h.ldr = D;
     h.a_bf16 = a16; also_xb(h);
-    add_gemm(sb, pfx + "ffn_macaron.w2", h);
+    add_gemm(sb, pfx + "ffn_macaron.w2", h, false, w.mac2.wf);
   }
   {  // x += MHA(LN(x))
     GemmParams g;
@@ -1107,7 +1134,7 @@ static void build_block(StageBuilder& sb, const std::string& pfx, const BlockW& 
     // K / P / V of a head staged once per (utterance, head) (attention.hip, second kernel)
     const bool att16 = a16 && relpos_attention_bf16_supports(Tp, D / H);
     g.y_bf16 = att16;
-    add_gemm(sb, pfx + "att.qkv", g);
+    add_gemm(sb, pfx + "att.qkv", g, false, w.qkv.wf);
     // p = linear_pos(pos_emb) of all blocks comes from ONE GEMM per forward ("pos_all" stage):
     // block i's slice is columns [i*D, (i+1)*D) of pbuf [T'][n_blocks*D]
     const int ldp = (c.num_blocks + c.embed_blocks) * D;
@@ -1134,7 +1161,7 @@ static void build_block(StageBuilder& sb, const std::string& pfx, const BlockW& 
     o.A = pl.ctx; o.lda = D; o.W = w.out.w; o.bias = w.out.b; o.Y = x; o.ldy = D; o.M = S; o.N = D; o.K = D;
     o.resid = x; o.ldr = D;
     o.a_bf16 = a16; also_xb(o);
-    add_gemm(sb, pfx + "att.out", o);
+    add_gemm(sb, pfx + "att.out", o, false, w.out.wf);
   }
   {  // x += ConvModule(LN(x))
     GemmParams g;
@@ -1160,7 +1187,7 @@ static void build_block(StageBuilder& sb, const std::string& pfx, const BlockW& 
     // kernel's taps are then one multiply each
     const bool glu_sig = glu_deferred && switches().glu_sig_epi && (D & 15) == 0;
     if (glu_sig) g.sig_col0 = D;
-    add_gemm(sb, pfx + "conv.pw1_glu", g);
+    add_gemm(sb, pfx + "conv.pw1_glu", g, false, w.pw1.wf);
     const float* glu = pl.glu; float* dw = pl.dw;
     const float* dww = w.dw_w; const float* dwb = w.dw_b;
     const float* ng = cnn_ln ? w.n_cnn.g : nullptr; const float* nb = cnn_ln ? w.n_cnn.b : nullptr;
@@ -1182,19 +1209,19 @@ static void build_block(StageBuilder& sb, const std::string& pfx, const BlockW& 
     h.A = pl.dw; h.lda = D; h.W = w.pw2.w; h.bias = w.pw2.b; h.Y = x; h.ldy = D; h.M = S; h.N = D; h.K = D;
     h.row_len = live_len; h.rows_per_batch = live_rpb; h.mask_out = 1; h.resid = x; h.ldr = D;
     h.a_bf16 = a16; also_xb(h);
-    add_gemm(sb, pfx + "conv.pw2", h);
+    add_gemm(sb, pfx + "conv.pw2", h, false, w.pw2.wf);
   }
   if (!moe) {  // x = LN_final(x + 0.5 * FFN(LN(x)))
     GemmParams g;
     g.A = x; g.lda = D; g.W = w.ff1.w; g.bias = w.ff1.b; g.Y = pl.h1; g.ldy = F; g.M = S; g.N = F; g.K = D;
     g.ln_wsum = w.ff1.wsum; g.ln_eps = eps; g.act = ACT_SILU;   // norm_ff is folded into w_1
     from_xb(g); g.y_bf16 = a16;
-    add_gemm(sb, pfx + "ffn.w1", g);
+    add_gemm(sb, pfx + "ffn.w1", g, false, w.ff1.wf);
     GemmParams h;
     h.A = pl.h1; h.lda = F; h.W = w.ff2.w; h.bias = w.ff2.b; h.Y = x; h.ldy = D; h.M = S; h.N = D; h.K = F;
     h.alpha = 0.5f; h.resid = x; h.ldr = D;
     h.a_bf16 = a16;                                   // (x is rewritten by norm_final below: no bf16 copy here)
-    add_gemm(sb, pfx + "ffn.w2", h);
+    add_gemm(sb, pfx + "ffn.w2", h, false, w.ff2.wf);
     const float* fg = w.n_final.g; const float* fb = w.n_final.b;
     void* xbo = a16 ? xb : nullptr;
     float* xso = dma ? xstats : nullptr;

@@ -57,8 +57,11 @@ enum { LN_NONE = GEMM_LN_NONE, LN_EPI = GEMM_LN_EPI, LN_PRO = GEMM_LN_PRO };
 // group, K1 == K / 2 == 8 * NW * G by the plan's check -- were run by router_embed_prefix_kernel, which left (acc, acc2) as they
 // stand after them.  The wave loads the pair with its operand group and starts at step G / 2: the skipped steps are not in the
 // instantiation at all.  wave w walks steps w, w + NW, ... in increasing order, so an MFMA chain cut there yields the same bits.
-template <int MT, bool GLU, int NW, bool CONV, int LN, int NBUF, bool ACCI = false>
+// WF (GemmParams::w_frag; the plan: plain A, N (GLU: N / 2) and K multiples of 16): W in MFMA-fragment order.  Only the weight
+// addresses of load_group differ; a template argument, so that the row-major instantiations are the code they were.
+template <int MT, bool GLU, int NW, bool CONV, int LN, int NBUF, bool ACCI = false, bool WF = false>
 __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid) {
+  static_assert(!WF || (!CONV && !ACCI), "fragment-ordered W: plain A only");
   constexpr int NT = GLU ? 2 : 1;
   constexpr int G = gemm_group_steps(MT, NT, NW);
   constexpr int I0 = ACCI ? G / 2 : 0;   // first K-step of the load group this instantiation runs
@@ -123,10 +126,14 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
       if (p.mode == GEMM_A_CONCAT2) arow2[mt] = p.A2 + (size_t)m * p.lda2 + 4 * kq;
     }
   }
+  // Row-major W: lane (col, kq) streams row n0 + col from column 4 * kq, 16 floats per K-step -- one wave instruction is 16 pieces
+  // of 64 B from 16 rows.  Fragment order (WF): the lane streams its 16 bytes of the KB of (column tile, K-step), 256 floats per
+  // K-step -- one instruction is one contiguous KB.  The same 16 bytes either way.
   const float* wrow[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t)
-    wrow[t] = p.W + (size_t)min(n0 + t * Nout + col, p.N - 1) * p.K + 4 * kq;
+    wrow[t] = WF ? p.W + (size_t)(n_tile + t * (Nout >> 4)) * ((size_t)p.K << 4) + 4 * lane
+                 : p.W + (size_t)min(n0 + t * Nout + col, p.N - 1) * p.K + 4 * kq;
 
   f32x4 acc[MT][NT];
 #pragma unroll
@@ -162,7 +169,7 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
       const int s = min(wave + NW * (G * g + i), nsteps - 1);
       const int k = s << 4;
 #pragma unroll
-      for (int t = 0; t < NT; ++t) wbuf[buf][i][t] = ldg4_w(wrow[t] + k);
+      for (int t = 0; t < NT; ++t) wbuf[buf][i][t] = ldg4_w(wrow[t] + (WF ? (s << 8) : k));
       const bool second = ACCI || (!CONV && p.mode == GEMM_A_CONCAT2 && k >= p.K1);
       const int off = second ? (k - p.K1) : a_offset(k);
 #pragma unroll
@@ -173,8 +180,11 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
   const int ngroups = (nsteps + NW * G - 1) / (NW * G);
   M3_GDIAG(dg[1] = __builtin_amdgcn_s_memtime();)
   // (Compile-time load offsets for the common exact shape -- one base address per row, no per-load address arithmetic -- were
-  //  tried: issue-to-data time unchanged (4 830 vs 4 650 cycles).  The loads are not issue-bound: a CU keeps ~16 KB of misses in
-  //  flight whatever the instruction stream, so 64 KB per work-group take ~4 latencies.)
+  //  tried: issue-to-data time unchanged (4 830 vs 4 650 cycles): the loads are not bound by address arithmetic.  What they are
+  //  bound by is WHICH bytes one instruction touches: row-major W gives 16 pieces of 64 B from 16 rows per wave instruction, and
+  //  the group's issue-to-data span at M = 50, K = 512, cold W is 4 150-4 330 cycles; with W in fragment order (WF: one contiguous
+  //  KB per instruction) it is 2 670-2 800 and the launch 4.40 us instead of 4.95.  The A loads keep the 16 x 64 B
+  //  shape; the earlier reading "a CU keeps ~16 KB of misses in flight whatever the instruction stream" was wrong.)
   // ACCI: the LayerNorm statistics pass's row loads go out AHEAD of the operand group.  Loads return in issue order, and the
   // pass (two reductions, LDS, a barrier) stands between the last load and the first MFMA: behind the operand group it waited
   // for all of it.  Load order only; the arithmetic below is the same.
@@ -444,9 +454,9 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
            })
 }
 
-template <int MT, bool GLU, int NW, bool CONV, int LN, int NBUF, bool ACCI = false>
+template <int MT, bool GLU, int NW, bool CONV, int LN, int NBUF, bool ACCI = false, bool WF = false>
 __global__ __launch_bounds__(64 * NW) void gemm_f32_kernel(const GemmParams p) {
-  gemm_f32_body<MT, GLU, NW, CONV, LN, NBUF, ACCI>(p, (int)blockIdx.x);
+  gemm_f32_body<MT, GLU, NW, CONV, LN, NBUF, ACCI, WF>(p, (int)blockIdx.x);
 }
 
 // The A half of the concat GEMMs gemm_f32_kernel<1, false, NW, false, LN_PRO, 1, true> finishes, for several weight matrices over
@@ -523,12 +533,12 @@ int launch_router_embed_prefix(const GemmPlan& plan, const GemmParams& p, const 
   return 0;
 }
 // (the second problem's work-group ids start at a multiple of 8, so that "id % 8 = XCD" holds for its XCD-aware tile order too)
-template <int MT, bool GLU, int NW, int LN>
+template <int MT, bool GLU, int NW, int LN, bool WF = false>
 __global__ __launch_bounds__(64 * NW) void gemm_f32_dual_kernel(const GemmParams p0, const GemmParams p1, const int n0) {
   if ((int)blockIdx.x < n0) {
-    if ((int)blockIdx.x < p0.n_tiles * p0.m_tiles) gemm_f32_body<MT, GLU, NW, false, LN, 1>(p0, (int)blockIdx.x);
+    if ((int)blockIdx.x < p0.n_tiles * p0.m_tiles) gemm_f32_body<MT, GLU, NW, false, LN, 1, false, WF>(p0, (int)blockIdx.x);
   } else {
-    gemm_f32_body<MT, GLU, NW, false, LN, 1>(p1, (int)blockIdx.x - n0);
+    gemm_f32_body<MT, GLU, NW, false, LN, 1, false, WF>(p1, (int)blockIdx.x - n0);
   }
 }
 
@@ -544,7 +554,10 @@ int launch_gemm_f32_dual(const GemmLaunch& a, const GemmLaunch& b, hipStream_t s
   const int n0 = (int)align_up((size_t)q[0].n_tiles * q[0].m_tiles, 8);
   dim3 grid(n0 + q[1].n_tiles * q[1].m_tiles);
 #define M3_DUAL(GLU_, NW_, LN_)                                                                                             \
-  hipLaunchKernelGGL((gemm_f32_dual_kernel<1, GLU_, NW_, LN_>), grid, dim3(64 * NW_), 0, stream, q[0], q[1], n0)
+  do {                                                                                                                      \
+    if (q[0].w_frag) hipLaunchKernelGGL((gemm_f32_dual_kernel<1, GLU_, NW_, LN_, true>), grid, dim3(64 * NW_), 0, stream, q[0], q[1], n0); \
+    else hipLaunchKernelGGL((gemm_f32_dual_kernel<1, GLU_, NW_, LN_>), grid, dim3(64 * NW_), 0, stream, q[0], q[1], n0);    \
+  } while (0)
   if (pa.glu) {
     if (pa.nw == 8) { if (pa.ln == LN_EPI) M3_DUAL(true, 8, LN_EPI); else M3_DUAL(true, 8, LN_NONE); }
     else { if (pa.ln == LN_EPI) M3_DUAL(true, 4, LN_EPI); else M3_DUAL(true, 4, LN_NONE); }
@@ -571,7 +584,12 @@ int launch_gemm_f32_skinny(const GemmPlan& plan, const GemmParams& pin, hipStrea
 
 #define M3_GEMM_LAUNCH(MT_, GLU_, NW_, CONV_, LN_)                                                              \
   do {                                                                                                          \
-    if (plan.nbuf == 1)                                                                                         \
+    constexpr bool kWf = !(CONV_);   /* (the plan: fragment-ordered W never comes with an implicit conv) */      \
+    if (p.w_frag && plan.nbuf == 1)                                                                              \
+      hipLaunchKernelGGL((gemm_f32_kernel<MT_, GLU_, NW_, CONV_, LN_, 1, false, kWf>), grid, dim3(64 * NW_), 0, stream, p); \
+    else if (p.w_frag)                                                                                           \
+      hipLaunchKernelGGL((gemm_f32_kernel<MT_, GLU_, NW_, CONV_, LN_, 2, false, kWf>), grid, dim3(64 * NW_), 0, stream, p); \
+    else if (plan.nbuf == 1)                                                                                    \
       hipLaunchKernelGGL((gemm_f32_kernel<MT_, GLU_, NW_, CONV_, LN_, 1>), grid, dim3(64 * NW_), 0, stream, p); \
     else                                                                                                        \
       hipLaunchKernelGGL((gemm_f32_kernel<MT_, GLU_, NW_, CONV_, LN_, 2>), grid, dim3(64 * NW_), 0, stream, p); \

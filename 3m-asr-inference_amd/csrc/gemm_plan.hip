@@ -181,6 +181,15 @@ static bool extras_ok(const GemmParams& p, GemmPlan& plan) {
                     "gemm: acc_init is built for K1 = K / 2 = %d with the LayerNorm prologue on the A2 half (K1=%d K=%d)",
                     8 * plan.nw * gemm_group_steps(1, 1, plan.nw), p.K1, p.K);
   }
+  if (p.w_frag) {   // fragment-ordered W: only gemm_f32_body's load_group knows the layout
+    M3_PLAN_REQUIRE(!p.w_bf16, "gemm: fragment-ordered weights are fp32-only");
+    M3_PLAN_REQUIRE(p.mode == GEMM_A_PLAIN, "gemm: fragment-ordered weights need plain A (no concat, no implicit conv)");
+    const int Nout = plan.glu ? p.N / 2 : p.N;
+    M3_PLAN_REQUIRE((Nout & 15) == 0 && (p.K & 15) == 0, "gemm: fragment-ordered weights need N%s=%d and K=%d to be multiples of 16",
+                    plan.glu ? " / 2" : "", Nout, p.K);
+    M3_PLAN_REQUIRE(plan.kernel == GemmKernel::SkinnyF32, "gemm: fragment-ordered weights need the skinny fp32 kernel; M=%d N=%d K=%d plans as %s",
+                    p.M, p.N, p.K, plan.label);
+  }
   return true;
 }
 
@@ -198,7 +207,8 @@ GemmPlan plan_gemm(const GemmParams& p, size_t workspace_bytes_available) {
 GemmLaunch gemm_launch(const GemmParams& p, float* ws, size_t ws_bytes) { return GemmLaunch{p, plan_gemm(p, ws != nullptr ? ws_bytes : 0), ws}; }
 bool gemm_dual_fusable(const GemmLaunch& ga, const GemmLaunch& gb) {
   const GemmPlan &a = ga.plan, &b = gb.plan;
-  return a.launches == 1 && b.launches == 1 && a.dual_ok && b.dual_ok && a.nw == b.nw && a.ln == b.ln && a.glu == b.glu;
+  return a.launches == 1 && b.launches == 1 && a.dual_ok && b.dual_ok && a.nw == b.nw && a.ln == b.ln && a.glu == b.glu &&
+         !ga.p.w_frag == !gb.p.w_frag;
 }
 
 int launch_gemm(const GemmLaunch& g, hipStream_t stream) {

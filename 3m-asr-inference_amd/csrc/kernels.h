@@ -59,6 +59,11 @@ struct GemmParams {
   // holds after its A-half K-steps, [m_tile][n_tile][wave][2][64 lanes] float4, as router_embed_prefix_kernel leaves it.  The wave
   // starts from it and runs its A2-half steps only (an MFMA chain cut and resumed from the stored registers: the same bits)
   const float* acc_init = nullptr;
+  // skinny fp32 kernel, plain A, N (GLU: N / 2) and K multiples of 16: W is in MFMA-fragment order (include/m3asr.h "fragment
+  // order"), Wf[N/16][K/16][4 (kq)][16 (col)][4] -- lane 16 * kq + col reads bytes [16 * lane, 16 * lane + 16) of the KB of
+  // (column tile, K-step), so one wave load instruction is one contiguous KB.  Every lane receives the same 16 bytes as from
+  // the row-major matrix: same bits.  plan_gemm refuses it everywhere else.
+  int w_frag = 0;
   // filled by the launchers from the GemmPlan
   int n_tiles = 0, m_tiles = 0, xcd_swizzle = 0;
 };
@@ -205,6 +210,9 @@ ExpertFfnPlan plan_expert_ffn(ExpertWeights w, int S, int E, int D, int F, unsig
 // xq_scale (rows already quantised by the router kernel), fs_dev (the kernel may split F finer than the plan and leaves the
 // slab count there): FusedFp8.  b2 / y_scatter: TiledBf16 under EXPERT_SCATTER_ROWS (the un-permute of the expert-parallel
 // receive side, folded into GEMM-2's epilogue).
+// w2_sliced, as the launchers take it: EXPERT_W_FRAG -- w1 AND w2 in MFMA-fragment order (pack_wfrag of w1 and of the slice-major w2;
+// include/m3asr.h "fragment order") -- is read by expert_ffn_f32_kernel alone: the SlabF32 form and the self-routing launch
+enum { EXPERT_W_REF = 0, EXPERT_W2_SLICED = 1, EXPERT_W_FRAG = 2 };
 struct ExpertFfnArgs { const float* x; int ldx; const int32_t *pos, *acc_hist; const void *w1, *w2; const float *s1, *s2, *b1, *b2;
                        int w2_sliced; float h_scale; float* slab; const float *ln_gamma, *ln_beta; float ln_eps;
                        const void* xq; const float* xq_scale; int32_t* fs_dev; float* y_scatter; };

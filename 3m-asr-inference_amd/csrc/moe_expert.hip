@@ -19,6 +19,8 @@
 // pure weight streaming: 4.2 MB per touched expert, E*F/64 = 512 workgroups of 256 KB each.
 // Measured dead ends: a persistent work-queue form (atomic item counter) was 30 % slower,
 // 32-wide slices and 3-4 deep load rings did not move the time: the kernel sits at the ~24 GB/s a CU can pull.
+// (Weights in fragment order, WF below -- every weight load one contiguous KB -- shorten the B = 1 launch by 0.9 us of 27.6,
+// the shape of the load instructions is not what holds this kernel either.)
 #include <stdlib.h>
 
 #include "common.h"
@@ -61,7 +63,11 @@ static const ExpertSwitches& expert_switches() {
 
 // LNS: apply the layer's LayerNorm while gathering rows (fused-route engines); a separate instantiation so the
 // default path does not carry its registers.
-template <int MT, bool LNS, int RE = 0>
+// WF: w1 and w2 in MFMA-fragment order (include/m3asr.h "fragment order"; m3asr/plan.py pack_wfrag of w1 [E][F][D] and of the
+// slice-major w2): w1 [E][F/16][D/16][4][16][4], w2 [E][F/64][D/16][4 (st)][4][16][4].  Every weight load instruction of a wave
+// is one contiguous KB in lane order, the four of a phase-2 output tile one contiguous 4 KB; each lane receives the same 16 bytes
+// as from the row-major / slice-major tensors, so the arithmetic and its bits are the same.  Only the addresses differ.
+template <int MT, bool LNS, int RE = 0, bool WF = false>
 __global__ __launch_bounds__(64 * (kExpertSlice / 16)) void expert_ffn_f32_kernel(const float* __restrict__ x, int ldx,
                                                              const int32_t* __restrict__ pos,
                                                              const int32_t* __restrict__ acc_hist, int S, int D,
@@ -88,7 +94,8 @@ __global__ __launch_bounds__(64 * (kExpertSlice / 16)) void expert_ffn_f32_kerne
   const int f0 = slice * kExpertSlice;
   const int ksteps1 = D >> 4;
 
-  const float* w1row = w1 + ((size_t)e * F + f0 + 16 * wave + col) * D + 4 * kq;
+  const float* w1row = WF ? w1 + (size_t)e * F * D + (size_t)((f0 >> 4) + wave) * ((size_t)D << 4) + 4 * lane
+                          : w1 + ((size_t)e * F + f0 + 16 * wave + col) * D + 4 * kq;
   const float bias1 = b1[(size_t)e * F + f0 + 16 * wave + col];
   const int nsub = D >> 4;                   // 16-column output tiles of phase 2
   // W2[e][:, slice]: reference layout [E][D][F] (row stride F, slices 64 floats apart) or the plan's
@@ -109,15 +116,15 @@ __global__ __launch_bounds__(64 * (kExpertSlice / 16)) void expert_ffn_f32_kerne
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const int s = min(8 * g + i, ksteps1 - 1);   // clamped, not branched: loads stay back to back
-        wb[buf][i] = ldg4_w(w1row + (s << 4));
+        wb[buf][i] = ldg4_w(w1row + (s << (WF ? 8 : 4)));
       }
     } else {
 #pragma unroll
       for (int j = 0; j < SPG; ++j) {
         const int sub = min(wave + NWV * (SPG * (g - g1) + j), nsub - 1);
-        const float* p = w2_slice + (size_t)(16 * sub + col) * w2_row_stride + 4 * kq;
+        const float* p = WF ? w2_slice + (size_t)sub * (KS2 * 256) + 4 * lane : w2_slice + (size_t)(16 * sub + col) * w2_row_stride + 4 * kq;
 #pragma unroll
-        for (int st = 0; st < KS2; ++st) wb[buf][KS2 * j + st] = ldg4_w(p + 16 * st);
+        for (int st = 0; st < KS2; ++st) wb[buf][KS2 * j + st] = ldg4_w(p + (WF ? 256 : 16) * st);
         if (RE > 0) bb[buf][j] = add_b2 ? rt.b2[(size_t)e * D + 16 * sub + col] : 0.f;
       }
     }
@@ -378,6 +385,10 @@ int init_expert_ffn_kernels() {
   M3_CHECK_HIP(hipFuncSetAttribute((const void*)expert_ffn_f32_kernel<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   M3_CHECK_HIP(hipFuncSetAttribute((const void*)expert_ffn_f32_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   M3_CHECK_HIP(hipFuncSetAttribute((const void*)expert_ffn_f32_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  M3_CHECK_HIP(hipFuncSetAttribute((const void*)expert_ffn_f32_kernel<2, false, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  M3_CHECK_HIP(hipFuncSetAttribute((const void*)expert_ffn_f32_kernel<4, false, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  M3_CHECK_HIP(hipFuncSetAttribute((const void*)expert_ffn_f32_kernel<2, true, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  M3_CHECK_HIP(hipFuncSetAttribute((const void*)expert_ffn_f32_kernel<4, true, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   once.mark();
   return 0;
 }
@@ -401,12 +412,16 @@ int launch_expert_ffn_f32_slab(const float* x, int ldx, const int32_t* pos, cons
   dim3 grid(F / kExpertSlice, E, zt < 8 ? zt : 8);
   const int w2_row_stride = w2_sliced ? kExpertSlice : F;
   const int w2_slice_stride = w2_sliced ? D * kExpertSlice : kExpertSlice;
+  const bool wf = w2_sliced == EXPERT_W_FRAG;
+  M3_REQUIRE(!wf || (((uintptr_t)w1 | (uintptr_t)w2) & 15) == 0, "expert_ffn: fragment-ordered weights must be 16-byte aligned");
   if (int rc = init_expert_ffn_kernels()) return rc;
-#define M3_EXPERT_CASE2(MT_, LNS_)                                                                      \
-  hipLaunchKernelGGL((expert_ffn_f32_kernel<MT_, LNS_>), grid, dim3(64 * (kExpertSlice / 16)), lds_bytes, stream, x, ldx, pos,    \
+#define M3_EXPERT_CASE2(MT_, LNS_, WF_)                                                                      \
+  hipLaunchKernelGGL((expert_ffn_f32_kernel<MT_, LNS_, 0, WF_>), grid, dim3(64 * (kExpertSlice / 16)), lds_bytes, stream, x, ldx, pos,    \
                      acc_hist, S, D, F, w1, b1, w2, w2_row_stride, w2_slice_stride, slab, ln_gamma, ln_beta, ln_eps, ExpertRoute())
-#define M3_EXPERT_CASE(MT_) do { if (ln_gamma) M3_EXPERT_CASE2(MT_, true); else M3_EXPERT_CASE2(MT_, false); } while (0)
+#define M3_EXPERT_CASE3(MT_, WF_) do { if (ln_gamma) M3_EXPERT_CASE2(MT_, true, WF_); else M3_EXPERT_CASE2(MT_, false, WF_); } while (0)
+#define M3_EXPERT_CASE(MT_) do { if (wf) M3_EXPERT_CASE3(MT_, true); else M3_EXPERT_CASE3(MT_, false); } while (0)
   if (mt == 1) M3_EXPERT_CASE(1); else if (mt == 2) M3_EXPERT_CASE(2); else M3_EXPERT_CASE(4);
+#undef M3_EXPERT_CASE3
 #undef M3_EXPERT_CASE
 #undef M3_EXPERT_CASE2
   M3_LAUNCH_CHECK();
@@ -435,7 +450,9 @@ int launch_expert_route_ffn_f32(const float* x, int ldx, const float* logits, co
   if (!once.done()) {
 #define M3_ROUTE_ATTR(MT_, E_)                                                                                                                            \
   M3_CHECK_HIP(hipFuncSetAttribute((const void*)expert_ffn_f32_kernel<MT_, false, E_>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); \
-  M3_CHECK_HIP(hipFuncSetAttribute((const void*)expert_ffn_f32_kernel<MT_, true, E_>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024))
+  M3_CHECK_HIP(hipFuncSetAttribute((const void*)expert_ffn_f32_kernel<MT_, true, E_>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); \
+  M3_CHECK_HIP(hipFuncSetAttribute((const void*)expert_ffn_f32_kernel<MT_, false, E_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024)); \
+  M3_CHECK_HIP(hipFuncSetAttribute((const void*)expert_ffn_f32_kernel<MT_, true, E_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024))
     M3_ROUTE_ATTR(2, 8); M3_ROUTE_ATTR(2, 16); M3_ROUTE_ATTR(2, 32); M3_ROUTE_ATTR(2, 64);
 #undef M3_ROUTE_ATTR
     once.mark();
@@ -447,16 +464,19 @@ int launch_expert_route_ffn_f32(const float* x, int ldx, const float* logits, co
   dim3 grid(F / kExpertSlice, E, 1);
   const int w2_row_stride = w2_sliced ? kExpertSlice : F;
   const int w2_slice_stride = w2_sliced ? D * kExpertSlice : kExpertSlice;
-#define M3_ROUTE_CASE(MT_, E_)                                                                                              \
+  const bool wf = w2_sliced == EXPERT_W_FRAG;
+  M3_REQUIRE(!wf || (((uintptr_t)w1 | (uintptr_t)w2) & 15) == 0, "expert_route_ffn: fragment-ordered weights must be 16-byte aligned");
+#define M3_ROUTE_CASE(MT_, E_, WF_)                                                                                         \
   do {                                                                                                                      \
     if (ln_gamma != nullptr)                                                                                                \
-      hipLaunchKernelGGL((expert_ffn_f32_kernel<MT_, true, E_>), grid, dim3(64 * (kExpertSlice / 16)), lds_bytes, stream, x, ldx, \
+      hipLaunchKernelGGL((expert_ffn_f32_kernel<MT_, true, E_, WF_>), grid, dim3(64 * (kExpertSlice / 16)), lds_bytes, stream, x, ldx, \
                          nullptr, nullptr, S, D, F, w1, b1, w2, w2_row_stride, w2_slice_stride, slab, ln_gamma, ln_beta, ln_eps, rt); \
     else                                                                                                                    \
-      hipLaunchKernelGGL((expert_ffn_f32_kernel<MT_, false, E_>), grid, dim3(64 * (kExpertSlice / 16)), lds_bytes, stream, x, ldx, \
+      hipLaunchKernelGGL((expert_ffn_f32_kernel<MT_, false, E_, WF_>), grid, dim3(64 * (kExpertSlice / 16)), lds_bytes, stream, x, ldx, \
                          nullptr, nullptr, S, D, F, w1, b1, w2, w2_row_stride, w2_slice_stride, slab, nullptr, nullptr, 0.f, rt); \
   } while (0)
-#define M3_ROUTE_E(E_) do { if (mt == 1) M3_ROUTE_CASE(1, E_); else M3_ROUTE_CASE(2, E_); } while (0)
+#define M3_ROUTE_MT(MT_, E_) do { if (wf) M3_ROUTE_CASE(MT_, E_, true); else M3_ROUTE_CASE(MT_, E_, false); } while (0)
+#define M3_ROUTE_E(E_) do { if (mt == 1) M3_ROUTE_MT(1, E_); else M3_ROUTE_MT(2, E_); } while (0)
   switch (E) {
     case 8: M3_ROUTE_E(8); break;
     case 16: M3_ROUTE_E(16); break;
@@ -464,6 +484,7 @@ int launch_expert_route_ffn_f32(const float* x, int ldx, const float* logits, co
     default: M3_ROUTE_E(64); break;
   }
 #undef M3_ROUTE_E
+#undef M3_ROUTE_MT
 #undef M3_ROUTE_CASE
   M3_LAUNCH_CHECK();
   return 0;

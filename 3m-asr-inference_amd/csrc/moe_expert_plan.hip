@@ -63,6 +63,8 @@ ExpertFfnPlan plan_expert_ffn(ExpertWeights w, int S, int E, int D, int F, unsig
 int launch_expert_ffn(const ExpertFfnPlan& plan, int S, int E, int D, int F, const ExpertFfnArgs& a, hipStream_t stream) {
   M3_REQUIRE(a.ln_gamma == nullptr || plan.kernel == ExpertKernel::SlabF32, "expert_ffn: LayerNorm while gathering exists in the fp32 slab form only (S=%d E=%d)", S, E);
   M3_REQUIRE(a.y_scatter == nullptr || plan.kernel == ExpertKernel::TiledBf16, "expert_ffn: the scattering epilogue exists in the bf16 tiled form only (S=%d E=%d)", S, E);
+  M3_REQUIRE(a.w2_sliced != EXPERT_W_FRAG || plan.kernel == ExpertKernel::SlabF32,
+             "expert_ffn: fragment-ordered weights exist for the fp32 slab form only; S=%d E=%d D=%d F=%d runs %s", S, E, D, F, plan.label);
   char* const region = (char*)a.slab;
   void* const hbuf = region + plan.h_off;
   float* const ybuf = (float*)(region + plan.rows_off);

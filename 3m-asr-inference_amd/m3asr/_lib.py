@@ -162,6 +162,8 @@ SIGNATURES = {
     "m3_moe_expert_workspace_size": (_sz, [_i, _i, _i, _i]),
     "m3_moe_expert_ffn": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _f, _vp,
                                _vp, _sz, _vp]),
+    "m3_moe_expert_ffn_wfrag": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _f, _vp,
+                                     _vp, _sz, _vp]),
     "m3_moe_expert_ffn_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _f, _vp,
                                     _vp, _sz, _vp]),
     "m3_moe_expert_ffn_fp8": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _f, _vp,
@@ -190,6 +192,10 @@ SIGNATURES = {
     "m3_linear_workspace_size": (_sz, [_P(LinearDesc)]),
     "m3_linear_kernel": (C.c_char_p, [_P(LinearDesc), _i]),
     "m3_linear_ws": (_i, [_P(LinearDesc), _vp, _sz, _vp]),
+    "m3_pack_wfrag_host": (_i, [_vp, _i, _i, _vp]),
+    "m3_linear_wfrag": (_i, [_P(LinearDesc), _vp]),
+    "m3_linear_wfrag_kernel": (C.c_char_p, [_P(LinearDesc)]),
+    "m3_linear_pair_wfrag": (_i, [_P(LinearDesc), _P(LinearDesc), _vp]),
     "m3_linear_pair": (_i, [_P(LinearDesc), _P(LinearDesc), _vp]),
     "m3_linear_ws_pair": (_i, [_P(LinearDesc), _vp, _sz, _P(LinearDesc), _vp, _sz, _i, _vp]),
     "m3_linear_pair_kernel": (C.c_char_p, [_P(LinearDesc), _P(LinearDesc), _i]),

@@ -65,10 +65,15 @@ class EncoderConfig:
     # end does (m3asr.frontend.DeltaFbank).  0 = static features only.
     delta_order: int = 0
     delta_window: int = 2
+    # fp32, attention_dim >= 256: the engine keeps a second copy of the block GEMM weights and of the expert weights in
+    # MFMA-fragment order (plan.pack_wfrag), derived on the device when an Engine is made and read by the skinny
+    # fp32 GEMM and the one-launch expert kernel.  Same results bit for bit; costs the size of those weights again in device
+    # memory.  The process switch M3_W_FRAG=0 turns it off as well.
+    weights_frag: bool = True
 
     # fields that are left out of to_json() while they hold their defaults: a header or fixture written before they existed
     # and one written now for the same model are the same bytes
-    _LATE_FIELDS = ("conv_subsample_in_ch", "embed_conv_subsample_in_ch", "delta_order", "delta_window")
+    _LATE_FIELDS = ("conv_subsample_in_ch", "embed_conv_subsample_in_ch", "delta_order", "delta_window", "weights_frag")
 
     def __post_init__(self):
         if not 0 <= self.delta_order <= 2:

@@ -6,6 +6,7 @@ memory owned by this object (torch tensors), activations in a caller-visible wor
 forward is one C call that replays a hipGraph.
 """
 import collections
+import os
 import ctypes as C
 
 import torch
@@ -13,7 +14,7 @@ import torch
 from . import _lib
 from ._lib import check
 from .config import EncoderConfig, subsampled_len
-from .plan import pack_weights
+from .plan import add_frag_weights, pack_weights
 
 
 _TORCH_DTYPE = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.int32: _lib.I32, torch.float8_e4m3fn: _lib.FP8,
@@ -47,6 +48,10 @@ def _engine_config(cfg: EncoderConfig, fold_pos_proj, debug_taps, fuse_route=Fal
     return ec
 
 
+# M3_W_FRAG (default 1), read once per process: 0 = no fragment-ordered weight copies (plan.add_frag_weights)
+_W_FRAG_SWITCH = os.environ.get("M3_W_FRAG", "1") != "0"
+
+
 class Engine:
     def __init__(self, cfg: EncoderConfig, packed, device="cuda:0", fold_pos_proj=True, debug_taps=False,
                  fuse_route=False, bf16_activations=True, packed_rows=None, max_shapes=8, ep_stages=False, fork_embed=None):
@@ -74,6 +79,10 @@ class Engine:
         # uploads nor names them; after_norm.* (the encoder's final LayerNorm as vectors) stays here for hidden()
         self.weights = {k: (v if v.is_cuda else v.to(self.device, non_blocking=False)).contiguous() for k, v in packed.items()
                         if not k.startswith("decoder.")}
+        # fragment-ordered copies of the fp32 block GEMM and expert weights, made on the device unless the dict (another context's)
+        # holds them already; M3_W_FRAG=0 or cfg.weights_frag = False: none, the model runs on the row-major tensors alone
+        if _W_FRAG_SWITCH:
+            add_frag_weights(self.weights, cfg)
         names = [n for n in self.weights if not n.startswith("after_norm.")]
         table = (_lib.WeightEntry * len(names))()
         self._keep = [n.encode() for n in names]

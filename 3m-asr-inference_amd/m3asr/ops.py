@@ -117,11 +117,15 @@ def moe_expert_ffn(x, gate_idx, w1, b1, w2, b2, gate_value=None, resid=None, alp
     w1_scale [E,F] / w2_scale [E,D]; uint8 MXFP4 code pairs with uint8 block scales (decoded to bf16 at the MFMA input,
     m3_moe_expert_ffn_mxfp4) (fp8: dequantised to bf16 at the MFMA input; with h_scale: fp8 arithmetic, activations
     quantised too -- m3_moe_expert_ffn_fp8a8; xq / xq_scale: the rows already quantised by quantize_rows_e4m3, read instead
-    of x where the fused kernel applies -- m3_moe_expert_ffn_fp8a8_xq).  Biases are fp32 in every mode."""
+    of x where the fused kernel applies -- m3_moe_expert_ffn_fp8a8_xq).  Biases are fp32 in every mode.
+    fp32 w1 (E, F/16, D/16, 4, 16, 4) with w2 (E, F/slice, D/16, slice/16, 4, 16, 4): fragment order (plan.pack_wfrag of w1 and
+    of the slice-major w2), m3_moe_expert_ffn_wfrag."""
     lib = _lib.load()
     assert w1.dtype == w2.dtype and w1.is_contiguous() and w2.is_contiguous()
     S, D = x.shape
-    E, F = w1.shape[0], w1.shape[1]
+    wfrag = w1.dim() == 6
+    assert not wfrag or (w1.dtype == torch.float32 and w2.dim() == 7)
+    E, F = w1.shape[0], w1.shape[1] * (16 if wfrag else 1)
     if workspace is None:
         workspace = torch.empty(max(moe_expert_workspace_size(S, E, D, F), 1), dtype=torch.uint8, device=x.device)
     y = out if out is not None else torch.empty_like(x)
@@ -155,6 +159,8 @@ def moe_expert_ffn(x, gate_idx, w1, b1, w2, b2, gate_value=None, resid=None, alp
               "m3_moe_expert_ffn_mxfp4")
     elif w1.dtype == torch.bfloat16:
         check(lib.m3_moe_expert_ffn_bf16(xi, gi, _p(w1), _f32(b1), _p(w2), _f32(b2), *tail), "m3_moe_expert_ffn_bf16")
+    elif wfrag:
+        check(lib.m3_moe_expert_ffn_wfrag(xi, gi, _f32(w1), _f32(b1), _f32(w2), _f32(b2), *tail), "m3_moe_expert_ffn_wfrag")
     else:
         check(lib.m3_moe_expert_ffn(xi, gi, _f32(w1), _f32(b1), _f32(w2), _f32(b2), *tail), "m3_moe_expert_ffn")
     return y
@@ -256,11 +262,14 @@ def moe_route_expert_ffn(x, logits, w1, b1, w2, b2, row_len=None, rows_per_batch
     """The self-routing expert launch + its combine (m3_moe_route_expert_ffn): router logits (S, E) -> top-1 routing, grouped
     fp32 expert FFN, y = LN(resid + alpha * gate * ffn(x)) in two launches, S <= 256.  x (S, D) may be a row-strided view;
     norm = (gamma, beta, eps): LayerNorm applied to x inside the expert kernel.  w2 (E, D, F); w2_sliced: the kernel reads
-    the slice-major layout of m3asr/plan.py (w2 already 4-D: taken as repacked).  -> (y, (gate_idx, gate_value, mapping,
+    the slice-major layout of m3asr/plan.py (w2 already 4-D: taken as repacked).  A 6-D w1 with a 7-D w2: both in fragment order
+    (plan.pack_wfrag of w1 and of the slice-major w2; w2_sliced = 2 at the ABI).  -> (y, (gate_idx, gate_value, mapping,
     acc_histogram, pos))"""
     lib = _lib.load()
     S, D = x.shape
-    E, F = w1.shape[0], w1.shape[1]
+    wfrag = w1.dim() == 6
+    assert not wfrag or (w2.dim() == 7 and w2.is_contiguous())
+    E, F = w1.shape[0], w1.shape[1] * (16 if wfrag else 1)
     assert tuple(logits.shape) == (S, E) and w1.is_contiguous()
     if w2_sliced and w2.dim() == 3:
         from .plan import slice_major_w2
@@ -273,7 +282,7 @@ def moe_route_expert_ffn(x, logits, w1, b1, w2, b2, row_len=None, rows_per_batch
     g, b, eps = ln if ln is not None else (None, None, 0.0)
     taps, ptrs = _route_taps(S, E, x.device, taps)
     check(lib.m3_moe_route_expert_ffn(xp, ldx, _f32(logits), _i32(row_len), rows_per_batch, _f32(w1), _f32(b1), _f32(w2),
-                                      1 if w2_sliced else 0, _f32(b2), S, E, D, F, _f32(ng), _f32(nb), float(neps),
+                                      2 if wfrag else (1 if w2_sliced else 0), _f32(b2), S, E, D, F, _f32(ng), _f32(nb), float(neps),
                                       1 if use_gate_value else 0, _f32(resid), float(alpha), _f32(g), _f32(b), float(eps),
                                       *ptrs, _p(y), _p(workspace), workspace.numel() * workspace.element_size(), _stream()),
           "m3_moe_route_expert_ffn")
@@ -291,10 +300,16 @@ def linear(a, w, bias=None, act=_lib.ACT_NONE, a2=None, ln=None, lens=None, rows
     copy_bf16 (M, n_out) bf16 receives an extra bf16 copy of y, copy_stats (M, n_out/128, 2) f32 its per-tile row statistics;
     ln_stats (M, parts, 2): such statistics of a bf16 `a`, which the folded LayerNorm then uses.
     a, a2, y (= out), resid and copy_bf16 may be row-strided views (unit column stride); their row strides go to the ABI.
-    workspace (split_k only): caller-owned uint8 scratch of at least m3_linear_workspace_size bytes."""
+    workspace (split_k only): caller-owned uint8 scratch of at least m3_linear_workspace_size bytes.
+    A 5-D w (N/16, K/16, 4, 16, 4) is taken as fragment-ordered (plan.pack_wfrag) and runs m3_linear_wfrag."""
     lib = _lib.load()
     M, K1 = a.shape
-    N, K = w.shape
+    wfrag = w.dim() == 5
+    if wfrag:
+        assert tuple(w.shape[2:]) == (4, 16, 4) and w.dtype == torch.float32 and not split_k
+        N, K = 16 * w.shape[0], 16 * w.shape[1]
+    else:
+        N, K = w.shape
     n_out = N // 2 if act == _lib.ACT_GLU else N
     y = out if out is not None else torch.empty(M, n_out, dtype=out_dtype, device=a.device)
     for t in (a, a2, y, resid, copy_bf16):
@@ -339,8 +354,11 @@ def linear(a, w, bias=None, act=_lib.ACT_NONE, a2=None, ln=None, lens=None, rows
     if _desc_only:
         return d, y
     if _kernel_only:
-        name = lib.m3_linear_kernel(C.byref(d), int(bool(split_k)))
+        name = lib.m3_linear_wfrag_kernel(C.byref(d)) if wfrag else lib.m3_linear_kernel(C.byref(d), int(bool(split_k)))
         return name.decode() if name else None
+    if wfrag:
+        check(lib.m3_linear_wfrag(C.byref(d), _stream()), "m3_linear_wfrag")
+        return y
     if split_k:        # deep-K / few-tile problems: split-K kernel + reduce through a scratch workspace
         need = lib.m3_linear_workspace_size(C.byref(d))
         ws = workspace if workspace is not None else torch.empty(max(need, 1), dtype=torch.uint8, device=a.device)
@@ -368,9 +386,13 @@ def linear_workspace_size(**kw):
 
 
 def linear_pair(a, b):
-    """linear(**a) and linear(**b) in one launch (m3_linear_pair); returns (y_a, y_b)"""
+    """linear(**a) and linear(**b) in one launch (m3_linear_pair; m3_linear_pair_wfrag when both w are fragment-ordered);
+    returns (y_a, y_b)"""
     (da, ya), (db, yb) = _linear_desc(a), _linear_desc(b)
-    check(_lib.load().m3_linear_pair(C.byref(da), C.byref(db), _stream()), "m3_linear_pair")
+    nfrag = (a["w"].dim() == 5) + (b["w"].dim() == 5)
+    assert nfrag != 1, "linear_pair: the two problems must agree on the weight layout"
+    fn = "m3_linear_pair_wfrag" if nfrag else "m3_linear_pair"
+    check(getattr(_lib.load(), fn)(C.byref(da), C.byref(db), _stream()), fn)
     return ya, yb
 
 

@@ -53,6 +53,58 @@ def slice_major_w2(t):
     return t.reshape(E_, D_, F_ // EXPERT_SLICE, EXPERT_SLICE).permute(0, 2, 1, 3).contiguous()
 
 
+def pack_wfrag(t):
+    """row-major fp32 [..., N, K] (N, K multiples of 16) -> MFMA-fragment order [..., N/16, K/16, 4 (kq), 16 (col), 4]
+    (include/m3asr.h "fragment order"): Wf[nt][s][kq][col][j] = W[16 nt + col][16 s + 4 kq + j], the KB of one (column tile,
+    K-step) in the lane order of the skinny fp32 kernels' weight loads.  Expert w_1 [E, F, D] packs as it stands; the slice-major
+    w_2 [E, F/S, D, S] gives [E, F/S, D/16, S/16, 4, 16, 4]: the S/16 loads of one output tile are one contiguous run."""
+    *lead, N_, K_ = t.shape
+    assert N_ % 16 == 0 and K_ % 16 == 0, "pack_wfrag: N=%d and K=%d must be multiples of 16" % (N_, K_)
+    n = len(lead)
+    v = t.reshape(*lead, N_ // 16, 16, K_ // 16, 4, 4)                       # [.., nt, col, s, kq, j]
+    return v.permute(*range(n), n, n + 2, n + 3, n + 1, n + 4).contiguous()  # [.., nt, s, kq, col, j]
+
+
+def unpack_wfrag(t):
+    """inverse of pack_wfrag: [..., N/16, K/16, 4, 16, 4] -> [..., N, K]"""
+    *lead, nt, ns, kq, col, j = t.shape
+    assert (kq, col, j) == (4, 16, 4)
+    n = len(lead)
+    return t.permute(*range(n), n, n + 3, n + 1, n + 2, n + 4).reshape(*lead, nt * 16, ns * 16).contiguous()
+
+
+# the block GEMM weights the skinny fp32 form streams (not the router, out_linear, the convs or the subsampling Linear)
+_FRAG_DENSE = ("feed_forward_macaron.w_1.ln.weight", "feed_forward_macaron.w_2.weight", "self_attn.qkv.ln.weight",
+               "self_attn.linear_out.weight", "conv_module.pointwise_conv1.ln.weight", "conv_module.pointwise_conv2.weight",
+               "feed_forward.w_1.ln.weight", "feed_forward.w_2.weight")
+
+
+def add_frag_weights(weights, cfg: EncoderConfig):
+    """Adds to `weights` (packed names -> tensors, any device) the fragment-ordered copies (pack_wfrag) of the fp32 block GEMM
+    weights and expert weights as NAME_frag, beside the tensors they are made from, which every long-batch form keeps reading
+    (experts: ...w_1.weight_frag from w_1.weight, ...w_2.weight_frag from w_2.weight_sliced).  fp32 models with attention_dim >=
+    256 and cfg.weights_frag only; names already present are kept.  Returns the names added.  save_plan never writes them."""
+    if not getattr(cfg, "weights_frag", True) or cfg.weight_dtype != "f32" or cfg.attention_dim < 256:
+        return []
+    added = []
+    for name in list(weights):
+        if not (name.startswith("blocks.") or name.startswith("embed.blocks.")):
+            continue
+        w, dst = weights[name], None
+        if w.dtype != torch.float32:
+            continue
+        if name.endswith(_FRAG_DENSE) and w.dim() == 2 and w.shape[0] % 16 == 0 and w.shape[1] % 16 == 0:
+            dst = name + "_frag"
+        elif name.endswith("feed_forward.experts.w_1.weight") and w.dim() == 3 and w.shape[1] % 16 == 0 and w.shape[2] % 16 == 0:
+            dst = name + "_frag"
+        elif name.endswith("feed_forward.experts.w_2.weight_sliced") and w.dim() == 4 and w.shape[2] % 16 == 0 and w.shape[3] % 16 == 0:
+            dst = name[:-len("_sliced")] + "_frag"
+        if dst is not None and dst not in weights:
+            weights[dst] = pack_wfrag(w)
+            added.append(dst)
+    return added
+
+
 def _pack_subsampling(sd, p, out):
     w0 = sd[p + "conv.0.weight"]                         # (C,in_ch,3,3) -> [in_ch * 9][C], row ch * 9 + kh * 3 + kw
     C = w0.shape[0]
@@ -410,6 +462,8 @@ _DTYPE_NAME = {torch.float32: "f32", torch.bfloat16: "bf16", torch.int32: "i32",
 
 
 def save_plan(path, cfg: EncoderConfig, packed, extra=None):
+    # (the fragment-ordered copies an Engine derives, NAME_frag, are never written: a plan's bytes do not depend on them)
+    packed = {k: v for k, v in packed.items() if not k.endswith("_frag")}
     index, off = {}, 0
     for k, v in packed.items():
         name = _DTYPE_NAME[v.dtype]

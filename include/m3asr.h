@@ -126,6 +126,15 @@ int m3_moe_expert_ffn(const float* x, const int32_t* gate_idx, const float* w1, 
                       const float* gate_value, const float* resid, float alpha, const float* ln_gamma,
                       const float* ln_beta, float ln_eps, float* y, void* workspace, size_t workspace_bytes,
                       m3_stream stream);
+/* The same with w1 and w2 in fragment order (see m3_linear_wfrag below for the layout): w1 [E][F][D] packed per expert with N = F,
+ * K = D, i.e. [E][F/16][D/16][4][16][4]; w2 packed from its slice-major form [E][F/slice][D][slice] with N = D, K = slice, i.e.
+ * [E][F/slice][D/16][slice/16][4][16][4] -- the loads of one output tile are one contiguous run.  Both 16-byte aligned.  Same bits
+ * as m3_moe_expert_ffn.  Exists for the one-launch fp32 form (S < 1024 rows); a shape that runs another form FAILS. */
+int m3_moe_expert_ffn_wfrag(const float* x, const int32_t* gate_idx, const float* w1, const float* b1,
+                            const float* w2, const float* b2, int S, int num_expert, int idim, int hidden_units,
+                            const float* gate_value, const float* resid, float alpha, const float* ln_gamma,
+                            const float* ln_beta, float ln_eps, float* y, void* workspace, size_t workspace_bytes,
+                            m3_stream stream);
 /* The same with bf16 expert weights (w1 / w2 point at bf16 [E][F][D] / [E][D][F]; biases, rows, epilogue fp32):
  * the half-precision mode the reference declares (`data_type` plugin field, fmoe_expert_plugin.cpp:331-354) but
  * asserts on (:264-266).  Rows and H are rounded to bf16 at the MFMA inputs, accumulation is fp32. */
@@ -253,7 +262,8 @@ int m3_moe_route(const float* x, int ldx, int idim, const float* wx, const float
  *                 rows with gate_idx < 0 contribute 0.  xn = x, or LayerNorm(x; norm_gamma, norm_beta, norm_eps) applied while
  *                 the rows are gathered when norm_gamma != NULL.  use_gate_value = 0: the factor gate_value[s] is left out (the
  *                 tap is written all the same).  resid / ln_gamma / ln_beta may be NULL.  Weights as m3_moe_expert_ffn;
- *                 w2_sliced = 1: w2 is slice-major [E][F / slice][D][slice] (m3_moe_expert_slice).  1 <= S <= 256, num_expert
+ *                 w2_sliced = 1: w2 is slice-major [E][F / slice][D][slice] (m3_moe_expert_slice); w2_sliced = 2: w1 AND w2 are
+ *                 in fragment order, as m3_moe_expert_ffn_wfrag takes them (same bits).  1 <= S <= 256, num_expert
  *                 8 / 16 / 32 / 64, idim a multiple of 16 (<= 2048; with S > 64 the row tile must fit the LDS), hidden_units a
  *                 multiple of the slice, ldx >= idim a multiple of 4; x / logits 16-byte aligned.  workspace: the partial
  *                 results, m3_moe_route_expert_workspace_size bytes (0 for a shape the operator does not take). */
@@ -325,6 +335,21 @@ size_t m3_linear_workspace_size(const m3_linear_desc* desc);
  * count, y_copy_stats below the LDS-DMA kernel's): m3_last_error() then holds the reason m3_linear would give. */
 const char* m3_linear_kernel(const m3_linear_desc* desc, int with_workspace);
 int m3_linear_ws(const m3_linear_desc* desc, void* workspace, size_t workspace_bytes, m3_stream stream);
+/* Fragment order: a constant fp32 weight matrix W[N][K] (N % 16 == 0, K % 16 == 0) stored in the order the skinny fp32 kernel's
+ * v_mfma_f32_16x16x4_f32 fragments consume it,
+ *     Wf[N/16][K/16][4 (kq)][16 (col)][4]   with   Wf[nt][s][kq][col][j] = W[16*nt + col][16*s + 4*kq + j],
+ * so that lane l = 16*kq + col of a wave reads bytes [16*l, 16*l + 16) of the 1 KB that belongs to (column tile nt, K-step s):
+ * one wave load instruction is one contiguous KB in lane order, not 16 pieces of 64 B from 16 rows.  Every lane receives the 16
+ * bytes it receives from the row-major matrix, so results are bit for bit the same.
+ * m3_pack_wfrag_host: host only, w[N][K] -> wf (N*K floats, must not overlap w).
+ * m3_linear_wfrag: m3_linear with desc->w in fragment order (16-byte aligned).  Taken where desc plans as the skinny fp32 kernel
+ * with plain A (no a2), fp32 weights, N (M3_ACT_GLU: N / 2) and K multiples of 16; every other descriptor FAILS with the reason
+ * in m3_last_error().  m3_linear_wfrag_kernel: host only, the kernel's name or NULL with that reason.
+ * m3_linear_pair_wfrag: m3_linear_pair with both w in fragment order. */
+int m3_pack_wfrag_host(const float* w, int N, int K, float* wf);
+int m3_linear_wfrag(const m3_linear_desc* desc, m3_stream stream);
+const char* m3_linear_wfrag_kernel(const m3_linear_desc* desc);
+int m3_linear_pair_wfrag(const m3_linear_desc* a, const m3_linear_desc* b, m3_stream stream);
 
 /* LayerNormPluginDynamic (layer_norm_plugin.cpp:78-113) -- with eps, as PyTorch. */
 int m3_layer_norm(const float* x, const float* gamma, const float* beta, float eps, float* y, int rows, int dim,
