@@ -1050,4 +1050,49 @@ int m3_resample(const void* tables, const void* pcm, int pcm_is_int16, int chann
                          (hipStream_t)stream);
 }
 
+int m3_vad_log_energy(const void* pcm, int pcm_is_int16, int ld_pcm, const int32_t* n_samples, int B, int T, float* log_energy,
+                      int ld_out, int32_t* len_out, m3_stream stream) {
+  M3_REQUIRE(B >= 0 && T >= 0, "vad_log_energy: bad sizes B=%d T=%d", B, T);
+  if (B == 0 || T == 0) return 0;
+  M3_REQUIRE(pcm && n_samples && log_energy && len_out, "vad_log_energy: null pointer");
+  M3_REQUIRE(ld_out >= T, "vad_log_energy: ld_out=%d is shorter than a row of %d", ld_out, T);
+  const int per16 = pcm_is_int16 ? 8 : 4;
+  M3_REQUIRE(ld_pcm >= 0 && ld_pcm % per16 == 0, "vad_log_energy: ld_pcm=%d must be a multiple of %d samples (16 bytes)", ld_pcm, per16);
+  M3_REQUIRE(aligned16(pcm), "vad_log_energy: pcm must be 16-byte aligned");
+  return launch_vad_log_energy(pcm, pcm_is_int16, ld_pcm, n_samples, B, T, log_energy, ld_out, len_out, (hipStream_t)stream);
+}
+int m3_vad_decide(const float* log_energy, int ld_e, const int32_t* lens, int B, int T, float energy_threshold,
+                  float energy_mean_scale, int context, float proportion_threshold, uint8_t* flags, int ld_flags,
+                  float* threshold_out, m3_stream stream) {
+  if (int rc = vad_options_ok(energy_mean_scale, context, proportion_threshold)) return rc;
+  M3_REQUIRE(energy_threshold == energy_threshold, "vad_decide: energy_threshold is not a number");
+  M3_REQUIRE(B >= 0 && B <= 65535 && T >= 0, "vad_decide: bad sizes B=%d T=%d", B, T);
+  if (B == 0 || T == 0) return 0;
+  M3_REQUIRE(log_energy && lens && flags && threshold_out, "vad_decide: null pointer");
+  M3_REQUIRE(ld_e >= T && ld_flags >= T, "vad_decide: ld_e=%d or ld_flags=%d is shorter than a row of %d", ld_e, ld_flags, T);
+  return launch_vad_decide(log_energy, ld_e, lens, B, T, energy_threshold, energy_mean_scale, context, proportion_threshold, flags,
+                           ld_flags, threshold_out, (hipStream_t)stream);
+}
+int m3_vad_segments(const uint8_t* flags, int ld_flags, const float* log_energy, int ld_e, const int32_t* lens, int B, int T,
+                    int min_silence, int min_speech, int pad, int max_segment, int split_search, int32_t* segments,
+                    int capacity, int32_t* n_segments, m3_stream stream) {
+  if (int rc = segment_options_ok(min_silence, min_speech, pad, max_segment, split_search)) return rc;
+  M3_REQUIRE(B >= 0 && T >= 0 && capacity >= 0, "vad_segments: bad sizes B=%d T=%d capacity=%d", B, T, capacity);
+  if (B == 0 || T == 0) return 0;
+  M3_REQUIRE(flags && log_energy && lens && n_segments && (segments || capacity == 0), "vad_segments: null pointer");
+  M3_REQUIRE(ld_e >= T && ld_flags >= T, "vad_segments: ld_e=%d or ld_flags=%d is shorter than a row of %d", ld_e, ld_flags, T);
+  return launch_vad_segments(flags, ld_flags, log_energy, ld_e, lens, B, T, min_silence, min_speech, pad, max_segment,
+                             split_search, segments, capacity, n_segments, (hipStream_t)stream);
+}
+int m3_segment_gather(const float* src, int ld_src, int T_all, const int32_t* jobs, int B, int T_max, int cols, float* dst,
+                      int ld_dst, int64_t batch_stride_dst, int32_t* len_out, m3_stream stream) {
+  M3_REQUIRE(B >= 0 && B <= 65535 && T_max >= 0 && T_all >= 0, "segment_gather: bad sizes B=%d T_max=%d T_all=%d", B, T_max, T_all);
+  M3_REQUIRE(cols >= 1, "segment_gather: cols=%d", cols);
+  if (B == 0 || T_max == 0) return 0;
+  M3_REQUIRE(jobs && dst && len_out && (src || T_all == 0), "segment_gather: null pointer");
+  M3_REQUIRE(ld_src >= cols && ld_dst >= cols && batch_stride_dst >= 0,
+             "segment_gather: ld_src=%d or ld_dst=%d is shorter than a row of %d columns, or a negative batch stride", ld_src, ld_dst, cols);
+  return launch_segment_gather(src, ld_src, T_all, jobs, B, T_max, cols, dst, ld_dst, batch_stride_dst, len_out, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -617,4 +617,20 @@ int launch_add_deltas(const float* feat, long ld_feat, long bs_feat, int T_in, c
                       const int32_t* n_out, int B, int T_out, int bins, int order, int window, float* out, long ld_out,
                       long bs_out, int32_t* out_len, hipStream_t stream);
 
+// vad.hip: Kaldi compute-vad on frame log-energy, a segmenter on its flags, and the cut of feature rows into an engine batch
+// 
+constexpr int VAD_MAX_CONTEXT = 32;
+int vad_options_ok(float energy_mean_scale, int context, float proportion_threshold);
+int segment_options_ok(int min_silence, int min_speech, int pad, int max_segment, int split_search);
+int launch_vad_log_energy(const void* pcm, int pcm_is_int16, long ld_pcm, const int32_t* n_samples, int B, int T, float* log_energy,
+                          long ld_out, int32_t* len_out, hipStream_t stream);
+int launch_vad_decide(const float* log_energy, long ld_e, const int32_t* lens, int B, int T, float energy_threshold,
+                      float energy_mean_scale, int context, float proportion_threshold, uint8_t* flags, long ld_flags,
+                      float* threshold_out, hipStream_t stream);
+int launch_vad_segments(const uint8_t* flags, long ld_flags, const float* log_energy, long ld_e, const int32_t* lens, int B, int T,
+                        int min_silence, int min_speech, int pad, int max_segment, int split_search, int32_t* segments,
+                        int capacity, int32_t* n_segments, hipStream_t stream);
+int launch_segment_gather(const float* src, long ld_src, int T_all, const int32_t* jobs, int B, int T_max, int cols, float* dst,
+                          long ld_dst, long bs_dst, int32_t* len_out, hipStream_t stream);
+
 }  // namespace m3

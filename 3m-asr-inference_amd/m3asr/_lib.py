@@ -312,6 +312,10 @@ SIGNATURES = {
     "m3_resample_num_samples": (_i64, [_i, _i, _i64, _i]),
     "m3_resample_input_span": (_i, [_i, _i, _i64, _i64, _P(_i64), _P(_i64)]),
     "m3_resample": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _vp]),
+    "m3_vad_log_energy": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _i, _vp, _vp]),
+    "m3_vad_decide": (_i, [_vp, _i, _vp, _i, _i, _f, _f, _i, _f, _vp, _i, _vp, _vp]),
+    "m3_vad_segments": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "m3_segment_gather": (_i, [_vp, _i, _i, _vp, _i, _i, _i, _vp, _i, _i64, _vp, _vp]),
     "m3_aed_embed": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "m3_aed_attention": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp]),
     "m3_aed_score": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),

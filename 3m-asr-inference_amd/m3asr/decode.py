@@ -339,12 +339,15 @@ class CtcDecoder:
         return self.batch_prefix_beam_from_logits(res["out_nosm"], res["out_lens"], beam_size), res["out_nosm"]
 
     def batch_prefix_beam_from_logits(self, logits: torch.Tensor, lens: torch.Tensor, beam_size: int, lm=None, lm_weight=0.5,
-                                      length_bonus=0.0, lm_eos=True):
+                                      length_bonus=0.0, lm_eos=True, context=None, graph_ids=None):
         """logits (B,T',V) on the device, lens (B,) valid frames per utterance -> n-best per utterance (device search).
-        lm: a m3asr.lm.NgramLm on the logits' device -- shallow fusion, as CtcBeamSearch(lm=)."""
+        lm: a m3asr.lm.NgramLm on the logits' device -- shallow fusion, as CtcBeamSearch(lm=).  context: a ContextSet on that
+        device -- hotword biasing, as CtcBeamSearch(context=); graph_ids: one graph id per utterance (default graph 0 for all)."""
         B, T = int(logits.shape[0]), int(logits.shape[1])
-        search = CtcBeamSearch(B, beam_size, T, self.blank_idx, logits.device, lm=lm, lm_weight=lm_weight,
+        search = CtcBeamSearch(B, beam_size, T, self.blank_idx, logits.device, context=context, lm=lm, lm_weight=lm_weight,
                                length_bonus=length_bonus, lm_eos=lm_eos)
+        if context is not None:
+            search.reset(graph_ids=[0] * B if graph_ids is None else graph_ids)
         search.advance(logits, lens)
         return search.nbest()
 
@@ -362,7 +365,17 @@ class CtcDecoder:
             raise _lib.M3Error("CtcDecoder.attention_rescoring: built without a rescorer (CtcDecoder(engine, rescorer=AttentionRescorer(...)))")
         self._full_context(decoding_chunk_size, num_decoding_left_chunks)
         res = self.forward(xs, xs_lens)
-        logits, lens = res["out_nosm"], res["out_lens"]
+        return self.rescore_from_logits(res["out_nosm"], res["out_lens"], beam_size, ctc_weight=ctc_weight, reverse_weight=reverse_weight,
+                                        context=context, graph_ids=graph_ids, lm=lm, lm_weight=lm_weight, length_bonus=length_bonus,
+                                        lm_eos=lm_eos, detail=detail)
+
+    def rescore_from_logits(self, logits: torch.Tensor, lens: torch.Tensor, beam_size: int, ctc_weight: float = 0.0,
+                            reverse_weight: float = 0.0, context=None, graph_ids=None, lm=None, lm_weight=0.5, length_bonus=0.0,
+                            lm_eos=True, detail=False):
+        """attention_rescoring() behind the encoder: logits (B,T',V) and lens (B,) of the engine's LAST forward (its hidden states
+        are read from the engine), however that forward was fed."""
+        if self.rescorer is None:
+            raise _lib.M3Error("CtcDecoder.attention_rescoring: built without a rescorer (CtcDecoder(engine, rescorer=AttentionRescorer(...)))")
         search = CtcBeamSearch(int(logits.shape[0]), beam_size, int(logits.shape[1]), self.blank_idx, logits.device, context=context,
                                lm=lm, lm_weight=lm_weight, length_bonus=length_bonus, lm_eos=lm_eos)
         if graph_ids is not None:
@@ -392,9 +405,21 @@ class CtcDecoder:
         bonus and final.  The context scores the pre-beam only: a hotword outside a row's pre_beam best is not rescued."""
         if self.rescorer is None:
             raise _lib.M3Error("CtcDecoder.attention: built without a rescorer (CtcDecoder(engine, rescorer=AttentionRescorer(...)))")
-        from .aed_search import AttentionBeamSearch
         self._full_context(decoding_chunk_size, num_decoding_left_chunks)
         res = self.forward(xs, xs_lens)
+        return self.attention_from_logits(res["out_nosm"], res["out_lens"], beam_size, max_steps=max_steps, detail=detail,
+                                          ctc_weight=ctc_weight, pre_beam=pre_beam, lm=lm, lm_weight=lm_weight,
+                                          length_bonus=length_bonus, context=context, graph_ids=graph_ids)
+
+    def attention_from_logits(self, logits: torch.Tensor, out_lens: torch.Tensor, beam_size: int, max_steps=None, detail=False,
+                              ctc_weight: float = 0.0, pre_beam=None, lm=None, lm_weight: float = 0.0, length_bonus: float = 0.0,
+                              context=None, graph_ids=None):
+        """attention() behind the encoder: logits (B,T',V) and out_lens (B,) of the engine's LAST forward (its hidden states are
+        read from the engine), however that forward was fed."""
+        if self.rescorer is None:
+            raise _lib.M3Error("CtcDecoder.attention: built without a rescorer (CtcDecoder(engine, rescorer=AttentionRescorer(...)))")
+        from .aed_search import AttentionBeamSearch
+        res = {"out_nosm": logits, "out_lens": out_lens}
         memory = self.engine.hidden(normalized=False)     # after_norm rides in the prologue of the search's K / V GEMM
         B, frames = int(memory.shape[0]), int(memory.shape[1])
         steps = min(frames, self.rescorer.cfg.max_len - 1) if max_steps is None else int(max_steps)

@@ -14,9 +14,15 @@ static | delta | delta-delta columns; DeltaFbank is Fbank followed by one more l
     fb = DeltaFbank(cfg.num_mel_bins, cfg.delta_order, cfg.delta_window, "cuda:0")
     feat, feat_len = fb(pcm)                       # (B, T, (order + 1) * bins)
 
-`num_frames`, `fbank_tables`, `delta_tables` and `AudioWindowBuffer` are host-only and need no GPU.
+Long recordings (m3_vad_*, m3_segment_gather, csrc/vad.hip): EnergyVad is Kaldi's compute-vad on frame
+log-energy plus a segmenter, three launches; segment_gather cuts feature rows into an engine batch (m3asr.longform drives both).
+
+    segs = EnergyVad(VadConfig(), "cuda:0")(pcm)   # [(start, end)] in frames per row
+
+`num_frames`, `fbank_tables`, `delta_tables`, `VadConfig` and `AudioWindowBuffer` are host-only and need no GPU.
 """
 import ctypes as C
+import dataclasses
 
 import numpy as np
 import torch
@@ -579,3 +585,208 @@ class AudioWindowBuffer:
             self.buf = self.buf[min(drop, self.buf.shape[0]):]
             self.base += drop
         return win, real
+
+
+MAX_VAD_CONTEXT = 32
+FRAME_MS = 1000 * FRAME_SHIFT // SAMPLE_RATE
+
+
+@dataclasses.dataclass
+class VadConfig:
+    """Energy VAD and segmenter options (m3_vad_* in include/m3asr.h).  The first four are Kaldi's compute-vad
+    options with Kaldi's defaults; the segmenter's are in 10-ms feature frames (`frames(ms)` converts) and nobody has tuned
+    them: min_silence = a pause shorter than this does not cut, min_speech = a voiced run shorter than this is dropped, pad =
+    frames kept on either side of a run, max_segment = the longest segment, split_search = how far back from max_segment the
+    quietest frame is looked for when a run has to be cut.  Refused: context outside [0, 32], proportion_threshold outside
+    (0, 1), a negative energy_mean_scale, min_silence or pad, min_speech < 7, 2 pad > min_silence, split_search outside
+    [1, max_segment - 7]."""
+    energy_threshold: float = 5.0
+    energy_mean_scale: float = 0.5
+    context: int = 0
+    proportion_threshold: float = 0.6
+    min_silence: int = 30
+    min_speech: int = 20
+    pad: int = 10
+    max_segment: int = 3000
+    split_search: int = 500
+    frame_ms: int = FRAME_MS
+
+    def __post_init__(self):
+        self.energy_threshold, self.energy_mean_scale = float(self.energy_threshold), float(self.energy_mean_scale)
+        self.context, self.proportion_threshold = int(self.context), float(self.proportion_threshold)
+        self.min_silence, self.min_speech, self.pad = int(self.min_silence), int(self.min_speech), int(self.pad)
+        self.max_segment, self.split_search = int(self.max_segment), int(self.split_search)
+        if self.energy_threshold != self.energy_threshold:
+            raise ValueError("VadConfig: energy_threshold is not a number")
+        if not 0 <= self.context <= MAX_VAD_CONTEXT:
+            raise ValueError("VadConfig: context=%d outside [0, %d]" % (self.context, MAX_VAD_CONTEXT))
+        if not 0.0 < self.proportion_threshold < 1.0:
+            raise ValueError("VadConfig: proportion_threshold=%g outside (0, 1)" % self.proportion_threshold)
+        if not 0.0 <= self.energy_mean_scale < float("inf"):
+            raise ValueError("VadConfig: energy_mean_scale=%g is negative or not finite" % self.energy_mean_scale)
+        if self.min_silence < 0 or self.pad < 0:
+            raise ValueError("VadConfig: min_silence=%d or pad=%d is negative" % (self.min_silence, self.pad))
+        if self.min_speech < 7:
+            raise ValueError("VadConfig: min_speech=%d is below 7 frames (the encoder's shortest input)" % self.min_speech)
+        if 2 * self.pad > self.min_silence:
+            raise ValueError("VadConfig: 2 * pad=%d exceeds min_silence=%d (padded runs could touch)" % (2 * self.pad, self.min_silence))
+        if not 1 <= self.split_search <= self.max_segment - 7:
+            raise ValueError("VadConfig: split_search=%d outside [1, max_segment - 7 = %d]" % (self.split_search, self.max_segment - 7))
+
+    def frames(self, ms):
+        """ceil(ms / frame_ms)"""
+        return int(-(-ms // self.frame_ms)) if isinstance(ms, int) else int(np.ceil(ms / self.frame_ms))
+
+    def segment_options(self):
+        return self.min_silence, self.min_speech, self.pad, self.max_segment, self.split_search
+
+
+class EnergyVad:
+    """Kaldi's energy VAD and the segmenter on one device (m3_vad_* in include/m3asr.h, csrc/vad.hip).
+    log_energy, decide and segments each wrap one launch; __call__ runs the three and brings the segment lists to the host."""
+
+    def __init__(self, cfg=None, device="cuda:0"):
+        self.cfg = VadConfig() if cfg is None else cfg
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+
+    def _on(self, stream):
+        return torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream())
+
+    def _lens(self, name, v, B):
+        if v.dtype != torch.int32 or v.device != self.device or v.numel() != B or not v.is_contiguous():
+            raise ValueError("EnergyVad: %s must be a contiguous int32 device tensor of %d entries" % (name, B))
+        return v.view(-1)
+
+    def _matrix(self, name, m, dtype, B=None):
+        if m.dim() != 2 or m.dtype != dtype or m.device != self.device or (m.shape[1] > 1 and m.stride(1) != 1) or \
+                (B is not None and m.shape[0] != B):
+            raise ValueError("EnergyVad: %s must be a (B, T) %s device tensor with dense rows" % (name, dtype))
+        return m
+
+    def log_energy(self, pcm, n_samples=None, out=None, out_len=None, stream=None):
+        """pcm (B, N) or (N,), int16 or float32 in the int16 range, on any device; n_samples (B,) real samples per row.
+        -> (logE (B, T = num_frames(N)) float32, lens (B,) int32) on the device; frames behind a row's last are zeros."""
+        with torch.cuda.device(self.device), self._on(stream):
+            st = torch.cuda.current_stream()
+            dev, N = Fbank._device_pcm(self, pcm)           # the staging rule of the feature front end
+            B = int(dev.shape[0])
+            if n_samples is None:
+                n_dev = torch.full((B,), N, dtype=torch.int32, device=self.device)
+            else:
+                n_dev = torch.as_tensor(n_samples).reshape(-1).to(self.device, torch.int32, non_blocking=True).clamp(max=N)
+                if n_dev.numel() != B:
+                    raise ValueError("EnergyVad: n_samples has %d entries for %d rows" % (n_dev.numel(), B))
+            if out is None:
+                out = torch.empty(B, num_frames(N), dtype=torch.float32, device=self.device)
+            self._matrix("out", out, torch.float32, B)
+            if out_len is None:
+                out_len = torch.zeros(B, dtype=torch.int32, device=self.device)
+            self._lens("out_len", out_len, B)
+            T = int(out.shape[1])
+            if B == 0 or T == 0:
+                out_len.zero_()
+                return out, out_len
+            check(self.lib.m3_vad_log_energy(dev.data_ptr(), int(dev.dtype == torch.int16), int(dev.stride(0)), n_dev.data_ptr(), B, T,
+                                             out.data_ptr(), int(out.stride(0)), out_len.data_ptr(), C.c_void_p(st.cuda_stream)),
+                  "m3_vad_log_energy")
+        return out, out_len
+
+    def decide(self, logE, lens, flags=None, threshold=None, stream=None):
+        """logE (B, T) float32, lens (B,) int32 on the device -> (flags (B, T) uint8, threshold (B,) float32)"""
+        c = self.cfg
+        B, T = int(logE.shape[0]), int(logE.shape[1])
+        self._matrix("logE", logE, torch.float32)
+        self._lens("lens", lens, B)
+        with torch.cuda.device(self.device), self._on(stream):
+            st = torch.cuda.current_stream()
+            if flags is None:
+                flags = torch.empty(B, T, dtype=torch.uint8, device=self.device)
+            if threshold is None:
+                threshold = torch.zeros(B, dtype=torch.float32, device=self.device)
+            self._matrix("flags", flags, torch.uint8, B)
+            if flags.shape[1] != T or threshold.dtype != torch.float32 or threshold.numel() != B or not threshold.is_contiguous():
+                raise ValueError("EnergyVad: flags must be (B, T), threshold a contiguous float32 tensor of B entries")
+            check(self.lib.m3_vad_decide(logE.data_ptr(), int(logE.stride(0)), lens.data_ptr(), B, T, c.energy_threshold,
+                                         c.energy_mean_scale, c.context, c.proportion_threshold, flags.data_ptr(),
+                                         int(flags.stride(0)), threshold.data_ptr(), C.c_void_p(st.cuda_stream)), "m3_vad_decide")
+        return flags, threshold
+
+    def segments(self, flags, logE, lens, capacity, segments=None, n_segments=None, stream=None):
+        """flags (B, T) uint8, logE (B, T) float32, lens (B,) int32 on the device -> (segments (B, capacity, 2) int32 [start, end)
+        in ascending order, n_segments (B,) int32: the true count, of which only the first `capacity` are written)."""
+        B, T = int(flags.shape[0]), int(flags.shape[1])
+        self._matrix("flags", flags, torch.uint8)
+        self._matrix("logE", logE, torch.float32, B)
+        self._lens("lens", lens, B)
+        capacity = int(capacity)
+        if logE.shape[1] != T or capacity < 0:
+            raise ValueError("EnergyVad: flags and logE must both be (B, T), capacity >= 0")
+        with torch.cuda.device(self.device), self._on(stream):
+            st = torch.cuda.current_stream()
+            if segments is None:
+                segments = torch.zeros(B, capacity, 2, dtype=torch.int32, device=self.device)
+            if n_segments is None:
+                n_segments = torch.zeros(B, dtype=torch.int32, device=self.device)
+            if segments.dtype != torch.int32 or segments.device != self.device or tuple(segments.shape) != (B, capacity, 2) or \
+                    not segments.is_contiguous():
+                raise ValueError("EnergyVad: segments must be a contiguous (B, %d, 2) int32 device tensor" % capacity)
+            self._lens("n_segments", n_segments, B)
+            check(self.lib.m3_vad_segments(flags.data_ptr(), int(flags.stride(0)), logE.data_ptr(), int(logE.stride(0)), lens.data_ptr(),
+                                           B, T, *self.cfg.segment_options(), segments.data_ptr(), capacity, n_segments.data_ptr(),
+                                           C.c_void_p(st.cuda_stream)), "m3_vad_segments")
+        return segments, n_segments
+
+    def __call__(self, pcm, n_samples=None, capacity=64, stream=None, detail=False):
+        """The three launches and ONE copy back (counts and lists in one buffer) -> [(start, end)] in frames per row.  A row
+        with more than `capacity` segments reports its true count; the segmenter then runs once more with room for it (one
+        retry, never a loop).  detail: -> (lists, logE, lens) with the device tensors of the first two launches."""
+        with torch.cuda.device(self.device), self._on(stream):
+            logE, lens = self.log_energy(pcm, n_samples)
+            B, T = int(logE.shape[0]), int(logE.shape[1])
+            if B == 0 or T == 0:
+                return ([[] for _ in range(B)], logE, lens) if detail else [[] for _ in range(B)]
+            flags, _ = self.decide(logE, lens)
+            host = self._segments_host(flags, logE, lens, int(capacity))
+            most = int(host[:, 0].max())
+            if most > int(capacity):
+                host = self._segments_host(flags, logE, lens, most)
+            out = [[(int(s), int(e)) for s, e in host[b, 1:1 + 2 * int(host[b, 0])].view(-1, 2).tolist()] for b in range(B)]
+        return (out, logE, lens) if detail else out
+
+    def _segments_host(self, flags, logE, lens, capacity):
+        B = int(flags.shape[0])
+        buf = torch.zeros(B, 1 + 2 * capacity, dtype=torch.int32, device=self.device)     # count | list: one copy brings both
+        seg = torch.zeros(B, capacity, 2, dtype=torch.int32, device=self.device)
+        n = torch.zeros(B, dtype=torch.int32, device=self.device)
+        self.segments(flags, logE, lens, capacity, seg, n)
+        buf[:, 0] = n
+        buf[:, 1:] = seg.view(B, -1)
+        host = buf.cpu()
+        host[:, 0].clamp_(min=0)
+        return host
+
+
+def segment_gather(src, jobs, dst, len_out, cols=None, stream=None):
+    """m3_segment_gather on device tensors: src (T_all, >= cols) float32, the features of whole recordings; jobs (B, 3) int32 =
+    (src_row, start, end) per segment: rows src_row + [start, end) of src; dst (B, T_max, >= cols) float32 (e.g. an engine
+    input buffer): frames behind a segment are written as zeros, columns >= cols are not touched; len_out (B,) / (1, B) int32
+    receives min(end - start, T_max).  cols: default src.shape[1].  The copy is a kernel: the product path does no torch
+    arithmetic.  -> dst"""
+    cols = int(src.shape[1] if cols is None else cols)
+    if src.dim() != 2 or src.dtype != torch.float32 or not src.is_cuda or (src.shape[1] > 1 and src.stride(1) != 1) or src.shape[1] < cols:
+        raise ValueError("segment_gather: src must be a (T_all, >= %d) float32 device tensor with dense rows" % cols)
+    B = int(dst.shape[0])
+    if dst.dim() != 3 or dst.dtype != torch.float32 or dst.device != src.device or dst.shape[2] < cols or \
+            (dst.shape[2] > 1 and dst.stride(2) != 1):
+        raise ValueError("segment_gather: dst must be a (B, T_max, >= %d) float32 device tensor with dense rows" % cols)
+    if jobs.dtype != torch.int32 or jobs.device != src.device or tuple(jobs.shape) != (B, 3) or not jobs.is_contiguous():
+        raise ValueError("segment_gather: jobs must be a contiguous (%d, 3) int32 device tensor" % B)
+    if len_out.dtype != torch.int32 or len_out.device != src.device or len_out.numel() != B or not len_out.is_contiguous():
+        raise ValueError("segment_gather: len_out must be a contiguous int32 device tensor of %d entries" % B)
+    with torch.cuda.device(src.device), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+        st = torch.cuda.current_stream()
+        check(_lib.load().m3_segment_gather(src.data_ptr(), int(src.stride(0)), int(src.shape[0]), jobs.data_ptr(), B,
+                                            int(dst.shape[1]), cols, dst.data_ptr(), int(dst.stride(1)), int(dst.stride(0)),
+                                            len_out.data_ptr(), C.c_void_p(st.cuda_stream)), "m3_segment_gather")
+    return dst

@@ -1072,6 +1072,54 @@ int m3_resample(const void* tables, const void* pcm, int pcm_is_int16, int chann
                 const int32_t* n_in, const int64_t* out0, const int32_t* n_out, int B, int N_out, float* out, int ld_out,
                 m3_stream stream);
 
+/* Long recordings in: energy VAD, a segmenter and the cut of feature rows into an engine batch (csrc/vad.hip)
+ * -- what a Kaldi-style pipeline puts between the features and the decoder (compute-vad, a segmenter, batching), so that a
+ * full-context model whose positional table ends at max_len can be run on a recording of any length.  Four launches, all
+ * on ragged batches with device length vectors; no result depends on B, T or the launch geometry; all options travel by
+ * value; B == 0 or T == 0 (gather: T_max == 0) launches nothing.
+ * m3_vad_log_energy: Kaldi's raw frame energy with the framing of m3_fbank (400 samples every 160, snip_edges), so frame k
+ *   here is frame k of the features.  Per frame: mean = (sum x) / 400, E = sum (x - mean)^2, log(max(E, FLT_EPSILON)) -- after
+ *   DC removal, before pre-emphasis and window.  pcm (B, ld_pcm) int16 (pcm_is_int16 != 0) or float32 in the int16 range, with
+ *   the alignment rules of m3_fbank (16-byte aligned, ld_pcm a multiple of 8 / 4 samples); n_samples [B] int32 (device),
+ *   clamped to [0, ld_pcm].  log_energy (B, ld_out >= T) float32: frames t < len_out[b] hold the value, frames len_out[b] <= t
+ *   < T are written as ZEROS, columns >= T are not touched.  len_out [B] int32 = min(m3_fbank_num_frames(n_samples[b]), T).
+ *   Both sums are fp32 in one fixed lane order, so int16 and float32 input give the same bits.
+ * m3_vad_decide: Kaldi's ComputeVadEnergy on a log-energy matrix (B, ld_e >= T), lens [B] int32 (device, clamped to [0, T]).
+ *   threshold_b = (float)(energy_threshold + energy_mean_scale * mean_b), mean_b = the float64 mean of the fp32 values
+ *   logE[b][t < lens[b]] (0 for an empty row), the expression evaluated in float64 and rounded once.  Frame t is voiced iff
+ *   (float)num >= (float)den * proportion_threshold (fp32, as Kaldi), den = frames of [t - context, t + context] inside
+ *   [0, lens[b]), num = those of them with logE > threshold_b.  flags (B, ld_flags >= T) uint8: 1 / 0, ZEROS for lens[b] <= t <
+ *   T, columns >= T not touched; threshold_out [B] float32.  Refused unless 0 <= context <= M3_VAD_MAX_CONTEXT, 0 <
+ *   proportion_threshold < 1, energy_mean_scale >= 0.  Kaldi's defaults are 5.0, 0.5, 0, 0.6.
+ * m3_vad_segments: flags + log-energy -> the sorted segment list of every row.  Options in frames; refused unless
+ *   min_silence >= 0, pad >= 0, min_speech >= 7, 2 pad <= min_silence, 1 <= split_search <= max_segment - 7.  Applied in this
+ *   order: CLOSE a silence run strictly between two voiced runs and shorter than min_silence becomes voiced; OPEN a voiced
+ *   run shorter than min_speech is dropped; PAD run [s, e) becomes [max(s - pad, 0), min(e + pad, len)) (runs cannot touch,
+ *   by 2 pad <= min_silence); SPLIT while a run is longer than max_segment it is cut at the frame of lowest logE in
+ *   [s + max_segment - split_search, s + max_segment), the lowest index on a tie; [s, cut) is emitted and the rest goes on
+ *   from cut.  A flag counts only for t < lens[b].  segments (B, capacity, 2) int32 [start, end), ascending; n_segments [B]
+ *   int32 = the TRUE count even when it exceeds capacity: only the first `capacity` are written and nothing behind them (the
+ *   overflow report of the bounded EP wire).  A row is streamed by one wave, whatever its length.
+ * m3_segment_gather: cuts rows of ONE long feature matrix src (T_all, ld_src >= cols) float32 into an engine batch.  jobs
+ *   [B][3] int32 (device) = (src_row, start, end): segment b is rows src_row + [start, end) of src.  dst (B, T_max, ld_dst >=
+ *   cols) with batch stride batch_stride_dst: frame t < n_b = min(end - start, T_max) gets its row bit for bit in columns
+ *   [0, cols), frames n_b <= t < T_max are written as ZEROS, columns >= cols are not touched; len_out [B] int32 = n_b.  A job
+ *   that leaves [0, T_all) is cut short where it leaves (to nothing if it starts outside) and reports the shortened count.
+ *   16-byte accesses when cols, the three strides and both pointers are multiples of 4 floats.  Features are computed once
+ *   over the whole recording and THEN cut, so the delta columns at a segment's edges come from the real neighbouring frames,
+ *   not from a replicated edge: the deliberate difference from featurising cut audio. */
+#define M3_VAD_MAX_CONTEXT 32
+int m3_vad_log_energy(const void* pcm, int pcm_is_int16, int ld_pcm, const int32_t* n_samples, int B, int T, float* log_energy,
+                      int ld_out, int32_t* len_out, m3_stream stream);
+int m3_vad_decide(const float* log_energy, int ld_e, const int32_t* lens, int B, int T, float energy_threshold,
+                  float energy_mean_scale, int context, float proportion_threshold, uint8_t* flags, int ld_flags,
+                  float* threshold_out, m3_stream stream);
+int m3_vad_segments(const uint8_t* flags, int ld_flags, const float* log_energy, int ld_e, const int32_t* lens, int B, int T,
+                    int min_silence, int min_speech, int pad, int max_segment, int split_search, int32_t* segments,
+                    int capacity, int32_t* n_segments, m3_stream stream);
+int m3_segment_gather(const float* src, int ld_src, int T_all, const int32_t* jobs, int B, int T_max, int cols, float* dst,
+                      int ld_dst, int64_t batch_stride_dst, int32_t* len_out, m3_stream stream);
+
 /* Attention rescoring: the AED decoder's second pass over the CTC n-best (csrc/aed_rescore.hip).  The decoder
  * runs teacher-forced on PACKED hypothesis rows: hypothesis slot h = b * beam + i owns rows [hyp_row0[h], hyp_row0[h + 1]) of
  * every row buffer, len + 1 of them for a live slot (sos, then its tokens) and none for a slot i >= n_hyps[b] (n_hyps < 0, a

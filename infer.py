@@ -47,7 +47,18 @@ prefix beam search of the list is still run and printed.
 Token times (m3asr.align): after a mode has chosen its best hypothesis -- without a mode, the CTC greedy search's -- the
 hypothesis is aligned to the forward's CTC output and one line per token follows an `utt <b> <mode> times:` line,
 `<token> <start ms> <end ms> <conf>`, conf being the token's largest posterior inside its span; `no alignment` for a
-hypothesis that CTC cannot align.  Without the flag nothing is added to the output."""
+hypothesis that CTC cannot align.  Without the flag nothing is added to the output.
+
+    python3 infer.py -p encoder.plan -w meeting.wav --vad [--vad-max-segment 3000 ...] [--max-batch 16] [any of the modes above]
+
+Long recordings (m3asr.longform): the engine refuses an utterance whose subsampled length reaches the plan's
+positional table (about 200 s), so with --vad the 16 kHz signal is first cut on the device by Kaldi's energy VAD (compute-vad;
+--vad-energy-threshold, --vad-energy-mean-scale, --vad-frames-context, --vad-proportion-threshold) and a segmenter whose options
+are in 10-ms frames (--vad-min-silence, --vad-min-speech, --vad-pad, --vad-max-segment, --vad-split-search); the segments run
+through the engine in batches of at most --max-batch.  One line per segment, `seg <i> <start>-<end> ms <mode>: <tokens>`, in
+time order; the mode is greedy, or biased / fused (--hotwords / --lm: the prefix beam search), rescored (--rescore) or
+attention (--attention).  With --timestamps every segment is followed by `seg <i> <mode> times:` and its token lines, on
+the recording's clock.  Without --vad nothing changes."""
 import argparse
 import os
 import sys
@@ -224,16 +235,73 @@ def print_attention(helper, feat, feat_len, args):
     return [list(best) for best, _ in out]
 
 
+def print_long_form(helper, args):
+    """--vad: the recording cut by the energy VAD, its segments batched through the engine and decoded in the mode asked for"""
+    from m3asr._lib import M3Error
+    from m3asr.frontend import VadConfig
+    from m3asr.longform import LongFormTranscriber
+    pcm, rate, channels = read_wav(args.wav_file)
+    if not -1 <= args.channel < channels:
+        raise SystemExit("%s: --channel %d, the file has %d channel(s)" % (args.wav_file, args.channel, channels))
+    dev, kw, rescorer = helper.engine.device, {}, None
+    if args.rescore or args.attention:
+        from m3asr.plan import decoder_config_of
+        from m3asr.rescore import AttentionRescorer
+        rescorer = AttentionRescorer(helper.decoder_packed, decoder_config_of(helper.extra), dev)
+    V = rescorer.cfg.vocab if rescorer is not None else helper.cfg.output_dim
+    lm = load_lm(args, V, dev) if args.lm else None
+    ctx = None
+    if args.hotwords:
+        from m3asr.context import ContextGraph, ContextSet, read_phrases
+        ctx = ContextSet([ContextGraph(read_phrases(args.hotwords), V, score=args.hotword_score)], device=dev)
+    if args.attention:
+        mode, name = "attention", "attention"
+        kw = dict(beam_size=args.beam, max_steps=args.max_steps, ctc_weight=args.ctc_weight, pre_beam=args.pre_beam, lm=lm,
+                  lm_weight=args.lm_weight, length_bonus=args.length_bonus, context=ctx)
+    elif args.rescore:
+        mode, name = "rescore", "rescored"
+        kw = dict(beam_size=args.beam, ctc_weight=args.ctc_weight, reverse_weight=args.reverse_weight)
+    elif lm is not None or ctx is not None:
+        mode, name = "beam", "fused" if lm is not None else "biased"
+        kw = dict(beam_size=args.beam, lm=lm, lm_weight=args.lm_weight, length_bonus=args.length_bonus, context=ctx)
+    else:
+        mode, name = "greedy", "greedy"
+    try:
+        vad = VadConfig(args.vad_energy_threshold, args.vad_energy_mean_scale, args.vad_frames_context, args.vad_proportion_threshold,
+                        args.vad_min_silence, args.vad_min_speech, args.vad_pad, args.vad_max_segment, args.vad_split_search)
+        lf = LongFormTranscriber(helper.engine, vad=vad, max_batch=args.max_batch, rescorer=rescorer)
+        segs = lf.transcribe(pcm, sample_rate=rate, channels=channels, channel=args.channel, mode=mode, timestamps=args.timestamps, **kw)
+    except (ValueError, M3Error) as e:
+        raise SystemExit("%s: %s" % (args.wav_file, e))
+    for i, s in enumerate(segs):
+        print("seg %d %d-%d ms %s: %s" % (i, s.start_ms, s.end_ms, name, " ".join(str(t) for t in s.tokens)))
+        if args.timestamps:
+            print("seg %d %s times:" % (i, name))
+            if s.times is None:
+                print("no alignment")
+            for tok, a, b, c in s.times or []:
+                print("%d %d %d %.4f" % (tok, a, b, c))
+
+
 def main(args):
     logger = trt_helper.init_trt_plugin(trt.Logger.INFO, "libm3asr_hip.so")
     helper = trt_helper.InferHelper(args.plan_name, logger)
+    if args.vad:
+        if not args.wav_file:
+            raise SystemExit("--vad cuts a recording: it needs -w, not -i")
+        return print_long_form(helper, args)
     if args.wav_file:
         feat = wav_features(args.wav_file, args.channel, helper.cfg, helper.engine.device).cpu().numpy()
     else:
         feat = np.load(args.input_file).astype(np.float32)
     feat_len = np.full((1, feat.shape[0]), feat.shape[1], dtype=np.int32)
     base = [np.load(args.compare_output_file)] if args.compare_output_file else None
-    outputs = helper.infer([feat, feat_len], base)
+    try:
+        outputs = helper.infer([feat, feat_len], base)
+    except Exception as e:
+        if args.wav_file and "exceeds the positional table" in str(e):    # the engine's refusal of an over-long utterance
+            raise type(e)("%s  A recording this long has to be cut first: add --vad." % e) from None
+        raise
     for o in outputs:
         print("outputs.shape:" + str(o.shape))
         print("outputs.sum:" + str(o.sum()))
@@ -278,4 +346,15 @@ if __name__ == "__main__":
     p.add_argument("--max-steps", type=int, default=None, help="--attention: the most tokens per hypothesis.")
     p.add_argument("--pre-beam", type=int, default=None, help="--attention --ctc-weight W: candidates per hypothesis that the CTC scorer sees.")
     p.add_argument("--timestamps", action="store_true", help="Token times: align the chosen hypothesis to the CTC output (start / end ms, confidence).")
+    p.add_argument("--vad", action="store_true", help="-w: cut a long recording on the device (energy VAD + segmenter) and decode its segments in batches.")
+    p.add_argument("--vad-energy-threshold", type=float, default=5.0, help="--vad: Kaldi's vad-energy-threshold.")
+    p.add_argument("--vad-energy-mean-scale", type=float, default=0.5, help="--vad: Kaldi's vad-energy-mean-scale.")
+    p.add_argument("--vad-frames-context", type=int, default=0, help="--vad: Kaldi's vad-frames-context (0 to 32).")
+    p.add_argument("--vad-proportion-threshold", type=float, default=0.6, help="--vad: Kaldi's vad-proportion-threshold.")
+    p.add_argument("--vad-min-silence", type=int, default=30, help="--vad: a pause shorter than this many 10-ms frames does not cut.")
+    p.add_argument("--vad-min-speech", type=int, default=20, help="--vad: a voiced run shorter than this many frames is dropped (at least 7).")
+    p.add_argument("--vad-pad", type=int, default=10, help="--vad: frames kept on either side of a run (at most half of --vad-min-silence).")
+    p.add_argument("--vad-max-segment", type=int, default=3000, help="--vad: the longest segment in frames; a longer run is cut at its quietest frame.")
+    p.add_argument("--vad-split-search", type=int, default=500, help="--vad: frames back from --vad-max-segment in which the quietest frame is looked for.")
+    p.add_argument("--max-batch", type=int, default=16, help="--vad: the most segments per engine batch.")
     main(p.parse_args())
