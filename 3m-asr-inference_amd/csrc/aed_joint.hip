@@ -310,13 +310,15 @@ __global__ __launch_bounds__(64) void aed_joint_score_kernel(const int32_t* __re
   [[maybe_unused]] int32_t* lc = nullptr;
   [[maybe_unused]] bool fused = false;
   [[maybe_unused]] LmView lm{};
+  [[maybe_unused]] double l_alpha = 0.0;                          // the utterance's LM weight: a set member's scale is folded in here, once
   if constexpr (LM) {
     const int32_t* lrow = lx.lstate + ((size_t)r * 2 + (s & 1)) * LS_WORDS;
     l_state = lrow[LS_STATE];
     l_n = lrow[LS_N];
     l_sum = *reinterpret_cast<const double*>(lrow + LS_LM);
     lc = lx.lscr + ((size_t)r * K + lane) * LC_WORDS;
-    fused = lx.lm_on[u] != 0 && lm_view(lx.image, lx.words, &lm) && lm.V == V;   // uniform
+    l_alpha = lx.alpha;
+    fused = lm_select(lx.image, lx.words, lx.lm_on[u], &lm, &l_alpha) && lm.V == V;   // uniform; a set: the utterance's member
   }
   // CTX only: the parent's (ctx_state, bonus) as stored, lane j's scratch entry, and the utterance's graph (one view per wave)
   [[maybe_unused]] int c_state = 0;
@@ -452,7 +454,7 @@ __global__ __launch_bounds__(64) void aed_joint_score_kernel(const int32_t* __re
     }
     if constexpr (LM) {                                           // two products and one sum in double, rounded once
       if constexpr (!CTX)
-        if (fused && is_cand && key != -INFINITY) key = key + (float)(lx.alpha * l_new + lx.beta * (double)(l_n + 1));
+        if (fused && is_cand && key != -INFINITY) key = key + (float)(l_alpha * l_new + lx.beta * (double)(l_n + 1));
       lc[LC_STATE] = is_cand ? l_next : 0;
       lc[LC_STATE + 1] = 0;
       *reinterpret_cast<double*>(lc + LC_LM) = is_cand ? l_new : 0.0;
@@ -460,8 +462,8 @@ __global__ __launch_bounds__(64) void aed_joint_score_kernel(const int32_t* __re
     if constexpr (CTX) {                                          // extra = (alpha lm' + beta n') + bonus' in double, rounded once
       if (is_cand && key != -INFINITY) {
         if constexpr (LM) {
-          if (fused && biased) key = key + (float)((lx.alpha * l_new + lx.beta * (double)(l_n + 1)) + c_new);
-          else if (fused) key = key + (float)(lx.alpha * l_new + lx.beta * (double)(l_n + 1));
+          if (fused && biased) key = key + (float)((l_alpha * l_new + lx.beta * (double)(l_n + 1)) + c_new);
+          else if (fused) key = key + (float)(l_alpha * l_new + lx.beta * (double)(l_n + 1));
           else if (biased) key = key + (float)c_new;
         } else {
           if (biased) key = key + (float)c_new;
@@ -635,8 +637,9 @@ int check_lm(const m3_aed_joint_desc* d, bool ctc, const void* st, size_t st_byt
 int check_lm_args(const char* what, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha, double beta, int B) {
   M3_REQUIRE(B == 0 || lm_on != nullptr, "%s: null lm_on", what);
   M3_REQUIRE(B == 0 || lm_image != nullptr, "%s: null LM image", what);
-  M3_REQUIRE(lm_bytes % 4 == 0 && lm_bytes >= LM_HDR_WORDS * 4 && lm_bytes <= kLmMaxBytes, "%s: LM image of %zu bytes (a multiple of 4 in [%d, %zu])",
-             what, lm_bytes, LM_HDR_WORDS * 4, kLmMaxBytes);
+  // a single image or a set: which one only the device copy says, so the bound is the set's
+  M3_REQUIRE(lm_bytes % 4 == 0 && lm_bytes >= LM_HDR_WORDS * 4 && lm_bytes <= kLmSetMaxBytes, "%s: LM image of %zu bytes (a multiple of 4 in [%d, %zu])",
+             what, lm_bytes, LM_HDR_WORDS * 4, kLmSetMaxBytes);
   M3_REQUIRE(std::isfinite(alpha) && std::isfinite(beta), "%s: alpha or beta is not finite", what);
   return 0;
 }
@@ -653,6 +656,21 @@ __global__ __launch_bounds__(256) void aed_lm_reset_kernel(int R, int N, int32_t
   int32_t* row = ls + (size_t)r * 2 * LS_WORDS;
   for (int w = 0; w < 2 * LS_WORDS; ++w) row[w] = 0;
   row[LS_STATE] = start;
+  row[LS_ATT] = __builtin_bit_cast(int32_t, r % N == 0 ? 0.f : -INFINITY);
+}
+
+// the same with the start state of each utterance's own LM: the member lm_on picks from a set (or the single image, lm_on != 0);
+// an utterance that runs without the LM holds state 0
+__global__ __launch_bounds__(256) void aed_lm_reset_set_kernel(int R, int N, int V, int32_t* ls, const int32_t* __restrict__ image,
+                                                               long long words, const int32_t* __restrict__ lm_on) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= R) return;
+  LmView lm;
+  double alpha = 0.0;
+  const bool fused = lm_select(image, words, lm_on[r / N], &lm, &alpha) && lm.V == V;
+  int32_t* row = ls + (size_t)r * 2 * LS_WORDS;
+  for (int w = 0; w < 2 * LS_WORDS; ++w) row[w] = 0;
+  row[LS_STATE] = fused ? lm.start : 0;
   row[LS_ATT] = __builtin_bit_cast(int32_t, r % N == 0 ? 0.f : -INFINITY);
 }
 
@@ -838,6 +856,38 @@ int m3_aed_ngram_reset(const m3_aed_joint_desc* desc, void* lm_state, size_t lm_
   const int R = desc->search.B * desc->search.beam;
   hipLaunchKernelGGL(aed_lm_reset_kernel, dim3((unsigned)cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream, R, desc->search.beam, (int32_t*)lm_state,
                      view.start);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+int m3_aed_ngram_reset_set(const m3_aed_joint_desc* desc, void* lm_state, size_t lm_state_bytes, const void* lm_image, size_t lm_bytes,
+                           const int32_t* lm_on, m3_stream stream) {
+  if (int rc = check_lm_desc(desc, false)) return rc;
+  M3_REQUIRE(lm_state_bytes >= m3::lm_state_bytes(desc), "aed_ngram_reset_set: LM state %zu bytes < required %zu", lm_state_bytes, m3::lm_state_bytes(desc));
+  M3_REQUIRE(desc->search.B == 0 || (lm_state != nullptr && ((uintptr_t)lm_state & 15) == 0), "aed_ngram_reset_set: the LM state must be 16-byte aligned device memory");
+  M3_REQUIRE(lm_bytes % 4 == 0 && lm_bytes >= LM_HDR_WORDS * 4 && lm_bytes <= kLmSetMaxBytes && lm_image != nullptr,
+             "aed_ngram_reset_set: LM image of %zu bytes (a multiple of 4 in [%d, %zu])", lm_bytes, LM_HDR_WORDS * 4, kLmSetMaxBytes);
+  M3_REQUIRE(desc->search.B == 0 || lm_on != nullptr, "aed_ngram_reset_set: null lm_on");
+  // the header, read back once per search: a set's 8 words or a single image's 20; what is refused here the kernels would run as "LM off"
+  int32_t head[LM_HDR_WORDS];
+  M3_CHECK_HIP(hipMemcpy(head, lm_image, sizeof(head), hipMemcpyDeviceToHost));
+  const long long words = (long long)(lm_bytes / 4);
+  int image_V = 0;
+  if (lm_is_set(head, words)) {
+    M3_REQUIRE(head[LMS_VERSION] == kLmSetVersion && head[LMS_G] >= 1 && head[LMS_G] <= kLmSetMaxMembers && head[LMS_WORDS] == words,
+               "aed_ngram_reset_set: the LM set's header (version %d, G = %d, %d words) does not describe a set of %zu bytes", head[LMS_VERSION],
+               head[LMS_G], head[LMS_WORDS], lm_bytes);
+    image_V = head[LMS_V];
+  } else {
+    LmView view;
+    M3_REQUIRE(lm_view(head, words, &view), "aed_ngram_reset_set: the LM image's header does not describe an image of %zu bytes", lm_bytes);
+    image_V = view.V;
+  }
+  M3_REQUIRE(image_V == desc->search.V, "aed_ngram_reset_set: the LM image was built for V = %d, the search has V = %d", image_V, desc->search.V);
+  if (desc->search.B == 0) return 0;
+  const int R = desc->search.B * desc->search.beam;
+  hipLaunchKernelGGL(aed_lm_reset_set_kernel, dim3((unsigned)cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream, R, desc->search.beam, desc->search.V,
+                     (int32_t*)lm_state, (const int32_t*)lm_image, words, lm_on);
   M3_LAUNCH_CHECK();
   return 0;
 }

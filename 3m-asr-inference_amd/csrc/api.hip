@@ -813,6 +813,9 @@ int m3_ctc_beam_ctx_nbest(const m3_ctc_beam_desc* desc, const void* state, size_
                                    hyp_bonus, n_hyps, (hipStream_t)stream);
 }
 int m3_ctc_lm_validate(const void* image, size_t image_bytes, int V) { return ctc_lm_validate(image, image_bytes, V); }
+int m3_ctc_ngram_set_member(const void* image, size_t image_bytes, int j, const void** member, size_t* member_bytes, float* scale) {
+  return ctc_lm_set_member(image, image_bytes, j, member, member_bytes, scale);
+}
 int m3_ctc_prefix_beam_search_lm(const float* top_logp, const int32_t* top_idx, int T, int k, int beam, int blank,
                                  const void* image, size_t image_bytes, int graph, const void* lm_image, size_t lm_bytes,
                                  double alpha, double beta, int use_eos, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score,

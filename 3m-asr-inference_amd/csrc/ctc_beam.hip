@@ -214,11 +214,13 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
   double* lsm = nullptr;
   LmView lm{};
   bool fused = false;
-  if constexpr (LM) {                             // uniform: the header goes through the scalar cache
+  [[maybe_unused]] double alpha = 0.0;            // the utterance's LM weight: a set member's scale is folded in here, once
+  if constexpr (LM) {                             // uniform: the header (a set's: and the directory entry) goes through the scalar cache
     char* c = state + cx.M.base + (size_t)b * cx.M.stride;
     ls = (int32_t*)c;
     lsm = (double*)(c + cx.M.bonus);
-    fused = cx.lm_on[b] != 0 && lm_view(cx.lm, cx.lm_words, &lm);
+    alpha = cx.alpha;
+    fused = lm_select(cx.lm, cx.lm_words, cx.lm_on[b], &lm, &alpha);
   }
   // current beam (best first) and its nodes
   __shared__ int s_node[kBeamMax], s_par[kBeamMax], s_tok[kBeamMax], s_dep[kBeamMax];
@@ -346,7 +348,7 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
       if (first != 0x7fffffff) {
         if constexpr (LM) {                       // ... and its LM sum
           double key = log_add2(pb, pnb) + s_bonus[q];
-          if (fused) key = key + (cx.alpha * s_lsum[q] + cx.beta * (double)s_dep[q]);
+          if (fused) key = key + (alpha * s_lsum[q] + cx.beta * (double)s_dep[q]);
           c_score[q] = key;
         } else if constexpr (CTX) c_score[q] = log_add2(pb, pnb) + s_bonus[q];     // a beam entry's node holds its bonus
         else c_score[q] = log_add2(pb, pnb);
@@ -397,7 +399,7 @@ __global__ __launch_bounds__(kBeamThreads) void ctc_beam_advance_kernel(BeamLayo
             const double lsum = s_lsum[h] + lp;
             c_lst[i] = nx;
             c_lsum[i] = lsum;
-            key = key + (cx.alpha * lsum + cx.beta * (double)(s_dep[h] + 1));
+            key = key + (alpha * lsum + cx.beta * (double)(s_dep[h] + 1));
           }
           c_score[c] = key;
         } else {
@@ -624,7 +626,11 @@ __global__ __launch_bounds__(64) void ctc_beam_ctx_nbest_kernel(BeamLayout L, Ct
   int nd = 0;
   LmView lm{};
   bool fused = false;
-  if constexpr (LM) fused = lx.lm_on[b] != 0 && lm_view(lx.lm, lx.lm_words, &lm);
+  [[maybe_unused]] double alpha = 0.0;
+  if constexpr (LM) {
+    alpha = lx.alpha;
+    fused = lm_select(lx.lm, lx.lm_words, lx.lm_on[b], &lm, &alpha);
+  }
   if (lane < n) {
     nd = p.node[lane];
     score = log_add2(p.pb[lane], p.pnb[lane]);
@@ -636,7 +642,7 @@ __global__ __launch_bounds__(64) void ctc_beam_ctx_nbest_kernel(BeamLayout L, Ct
         const char* c2 = state + lx.M.base + (size_t)b * lx.M.stride;
         const int st = nd == 0 ? lm.start : lm_in_range(((const int32_t*)c2)[nd], lm.n_states);
         lmf = ((const double*)(c2 + lx.M.bonus))[nd] + (lx.use_eos ? (double)lm.fin[st] : 0.0);
-        key[lane] = key[lane] + (lx.alpha * lmf + lx.beta * (double)p.depth[nd]);
+        key[lane] = key[lane] + (alpha * lmf + lx.beta * (double)p.depth[nd]);
       }
     }
   }
@@ -1021,8 +1027,9 @@ int launch_ctc_beam_lm_reset(const m3_ctc_beam_desc* d, void* state, size_t byte
 static int check_lm_image(const char* who, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha, double beta) {
   M3_REQUIRE(lm_on != nullptr, "%s: null lm_on", who);
   M3_REQUIRE(lm_image != nullptr || lm_bytes == 0, "%s: null LM image of %zu bytes", who, lm_bytes);
-  M3_REQUIRE(lm_bytes % 4 == 0 && lm_bytes <= kLmMaxBytes && (lm_image == nullptr || lm_bytes >= LM_HDR_WORDS * 4),
-             "%s: LM image of %zu bytes (a multiple of 4 in [%d, %zu])", who, lm_bytes, LM_HDR_WORDS * 4, kLmMaxBytes);
+  // a single image or a set: which one only the device copy says, so the bound is the set's
+  M3_REQUIRE(lm_bytes % 4 == 0 && lm_bytes <= kLmSetMaxBytes && (lm_image == nullptr || lm_bytes >= LM_HDR_WORDS * 4),
+             "%s: LM image of %zu bytes (a multiple of 4 in [%d, %zu])", who, lm_bytes, LM_HDR_WORDS * 4, kLmSetMaxBytes);
   M3_REQUIRE(std::isfinite(alpha) && std::isfinite(beta), "%s: alpha or beta is not finite", who);
   return 0;
 }

@@ -17,6 +17,7 @@
 #include <limits>
 #include <cmath>
 #include <map>
+#include <string>
 #include <vector>
 
 #include "common.h"
@@ -287,9 +288,11 @@ int ctc_context_validate(const void* image, size_t bytes, int V) {
 // ---------------------------------------------------------------- n-gram LM shallow fusion, host side
 // Structure of an LM image (kernels.h): the header and limits, every table inside the image, and every table entry that the
 // searches use as an index or add to a score.  Limits: order <= 8, n_states <= 2^26, image <= 1 GiB.
+static int ctc_lm_set_validate(const int32_t* w, size_t bytes, int V);
 int ctc_lm_validate(const void* image, size_t bytes, int V) {
   M3_REQUIRE(image != nullptr, "ctc_lm_validate: null image");
   M3_REQUIRE(V >= 1, "ctc_lm_validate: V = %d < 1", V);
+  if (bytes % 4 == 0 && lm_is_set((const int32_t*)image, (long long)(bytes / 4))) return ctc_lm_set_validate((const int32_t*)image, bytes, V);
   M3_REQUIRE(bytes % 4 == 0 && bytes >= LM_HDR_WORDS * 4 && bytes <= kLmMaxBytes,
              "ctc_lm_validate: image of %zu bytes (a multiple of 4 in [%d, %zu])", bytes, LM_HDR_WORDS * 4, kLmMaxBytes);
   const int32_t* w = (const int32_t*)image;
@@ -336,6 +339,59 @@ int ctc_lm_validate(const void* image, size_t bytes, int V) {
     M3_REQUIRE(std::isfinite(m.bo_weight[s]), "ctc_lm_validate: bo_weight[%d] is not finite", s);
     M3_REQUIRE(std::isfinite(m.fin[s]), "ctc_lm_validate: final[%d] is not finite", s);
   }
+  return 0;
+}
+
+// Structure of an LM set (kernels.h): the header, the directory -- every member 16-byte aligned, behind the directory, in
+// ascending order without overlap, inside the set, its scale finite and positive -- and every member by the rules above.
+static int ctc_lm_set_validate(const int32_t* w, size_t bytes, int V) {
+  const long long words = (long long)(bytes / 4);
+  M3_REQUIRE(bytes <= kLmSetMaxBytes, "ctc_lm_validate: LM set of %zu bytes > %zu", bytes, kLmSetMaxBytes);
+  M3_REQUIRE(w[LMS_VERSION] == kLmSetVersion, "ctc_lm_validate: LM set version %d, this library reads version %d", w[LMS_VERSION],
+             kLmSetVersion);
+  M3_REQUIRE(w[LMS_V] == V, "ctc_lm_validate: LM set built for V = %d, asked for V = %d", w[LMS_V], V);
+  const int G = w[LMS_G];
+  M3_REQUIRE(G >= 1 && G <= kLmSetMaxMembers, "ctc_lm_validate: LM set with G = %d members outside [1, %d]", G, kLmSetMaxMembers);
+  M3_REQUIRE(w[LMS_WORDS] == words, "ctc_lm_validate: LM set says %d words, has %lld", w[LMS_WORDS], words);
+  M3_REQUIRE(w[5] == 0 && w[6] == 0 && w[7] == 0, "ctc_lm_validate: LM set header words 5..7 are not 0");
+  long long end = LMS_HDR_WORDS + (long long)G * LMS_ENTRY_WORDS;            // the first word a member may take
+  M3_REQUIRE(end <= words, "ctc_lm_validate: LM set of %lld words cannot hold a directory of %d entries", words, G);
+  for (int j = 0; j < G; ++j) {
+    const int32_t* e = w + LMS_HDR_WORDS + (size_t)j * LMS_ENTRY_WORDS;
+    const long long off = e[LMS_E_OFFSET], n = e[LMS_E_WORDS];
+    const float scale = ((const float*)e)[LMS_E_SCALE];
+    M3_REQUIRE(off >= 0 && off % 4 == 0, "ctc_lm_validate: LM set member %d: offset of %lld words is not a multiple of 4 (16-byte alignment)",
+               j, off);
+    M3_REQUIRE(off >= end, "ctc_lm_validate: LM set member %d at word %lld overlaps what ends at word %lld (the directory or member %d)",
+               j, off, end, j - 1);
+    M3_REQUIRE(n >= LM_HDR_WORDS && off <= words && n <= words - off,
+               "ctc_lm_validate: LM set member %d: words [%lld, %lld) reach past the end of the set (%lld words) or hold no header", j, off,
+               off + n, words);
+    M3_REQUIRE(std::isfinite(scale) && scale > 0.f, "ctc_lm_validate: LM set member %d: scale = %g is not finite and positive", j,
+               (double)scale);
+    M3_REQUIRE(e[3] == 0, "ctc_lm_validate: LM set member %d: directory word 3 is not 0", j);
+    M3_REQUIRE(w[off + LM_MAGIC] == kLmMagic, "ctc_lm_validate: LM set member %d is not an LM image", j);
+    if (int rc = ctc_lm_validate(w + off, (size_t)n * 4, V)) {
+      const std::string why = last_error();
+      set_error("ctc_lm_validate: LM set member %d: %s", j, why.c_str());
+      return rc;
+    }
+    end = off + n;
+  }
+  return 0;
+}
+
+// Member j of a host set that passes ctc_lm_validate (run here): where it lies, its bytes and its scale.
+int ctc_lm_set_member(const void* image, size_t bytes, int j, const void** member, size_t* member_bytes, float* scale) {
+  M3_REQUIRE(image != nullptr && member != nullptr && member_bytes != nullptr, "ctc_lm_set_member: null pointer");
+  M3_REQUIRE(bytes % 4 == 0 && lm_is_set((const int32_t*)image, (long long)(bytes / 4)), "ctc_lm_set_member: not an LM set");
+  const int32_t* w = (const int32_t*)image;
+  if (int rc = ctc_lm_set_validate(w, bytes, w[LMS_V])) return rc;
+  M3_REQUIRE(j >= 0 && j < w[LMS_G], "ctc_lm_set_member: member %d outside [0, %d)", j, w[LMS_G]);
+  const int32_t* e = w + LMS_HDR_WORDS + (size_t)j * LMS_ENTRY_WORDS;
+  *member = w + e[LMS_E_OFFSET];
+  *member_bytes = (size_t)e[LMS_E_WORDS] * 4;
+  if (scale) *scale = ((const float*)e)[LMS_E_SCALE];
   return 0;
 }
 

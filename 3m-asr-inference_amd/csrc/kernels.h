@@ -506,6 +506,62 @@ __host__ __device__ inline bool lm_view(const int32_t* image, long long words, L
   out->unk_logp = ((const float*)image)[LM_UNK];
   return true;
 }
+// An LM SET (include/m3asr.h, "LM set"): G complete LM images behind one header and a directory, one device image.
+//   [magic, version, V, G, total words, 0, 0, 0]   G x [offset words, n words, scale (float bits), 0]   the member images
+constexpr int32_t kLmSetMagic = 0x534c334d;   // "M3LS"
+constexpr int32_t kLmSetVersion = 1;
+constexpr int kLmSetMaxMembers = 64;
+constexpr size_t kLmSetMaxBytes = (size_t)1 << 31;
+enum { LMS_MAGIC = 0, LMS_VERSION = 1, LMS_V = 2, LMS_G = 3, LMS_WORDS = 4, LMS_HDR_WORDS = 8 };
+enum { LMS_E_OFFSET = 0, LMS_E_WORDS = 1, LMS_E_SCALE = 2, LMS_ENTRY_WORDS = 4 };
+__host__ __device__ inline bool lm_is_set(const int32_t* image, long long words) {
+  return image != nullptr && words >= LMS_HDR_WORDS && image[LMS_MAGIC] == kLmSetMagic;
+}
+// Member j of a set of `words` words as (first word, word count, scale).  False unless the set's header, the directory entry
+// and the member's extent pass their range checks: no address is formed from a value that failed one.  (What lies INSIDE the
+// member is lm_view's to check.)
+__host__ __device__ inline bool lm_set_entry(const int32_t* image, long long words, long long j, const int32_t** member,
+                                             long long* member_words, float* scale) {
+  if (!lm_is_set(image, words) || image[LMS_VERSION] != kLmSetVersion) return false;
+  const long long V = image[LMS_V], G = image[LMS_G], total = image[LMS_WORDS];
+  if (V < 1 || G < 1 || G > kLmSetMaxMembers || total > words || total < LMS_HDR_WORDS + G * LMS_ENTRY_WORDS) return false;
+  if (j < 0 || j >= G) return false;
+  const int32_t* e = image + LMS_HDR_WORDS + j * LMS_ENTRY_WORDS;
+  const long long off = e[LMS_E_OFFSET], n = e[LMS_E_WORDS];
+  const float s = ((const float*)e)[LMS_E_SCALE];
+  if (off < LMS_HDR_WORDS + G * LMS_ENTRY_WORDS || (off & 3) != 0 || n < LM_HDR_WORDS || off > total || n > total - off) return false;
+  if (!(s > 0.f) || !(s <= 3.4028234663852886e38f)) return false;          // finite and positive; NaN fails both
+  *member = image + off;
+  *member_words = n;
+  *scale = s;
+  return true;
+}
+// The tables an utterance with the switch `on` walks, resolved ONCE per utterance (all loads are uniform): false = it runs
+// without the LM.  A single image: on != 0 and lm_view, as ever.  A set: on = j in [1, G] picks member j - 1, whose view must
+// also be over the set's V; *alpha then becomes *alpha * (double)scale, one double product.  Any other value: off.
+// (base, words, scale) are picked FIRST and lm_view runs once, on the chosen base: one copy of the header checks in the
+// kernel, and from there on the walk cannot tell a member from a single image.  A single image above the single image's
+// size limit is off, as the launch checks had it before they had to admit a set's size.
+#ifndef M3_LM_SET_PICK_ATTR
+#define M3_LM_SET_PICK_ATTR inline
+#endif
+#ifndef M3_LM_SET_EXPECT
+#define M3_LM_SET_EXPECT 0
+#endif
+__host__ __device__ M3_LM_SET_PICK_ATTR bool lm_select(const int32_t* image, long long words, int on, LmView* out, double* alpha) {
+  if (on == 0) return false;
+  const int32_t* base = image;
+  long long n = words, want_V = 0;
+  if (__builtin_expect(lm_is_set(image, words), M3_LM_SET_EXPECT)) {
+    float scale;
+    if (!lm_set_entry(image, words, (long long)on - 1, &base, &n, &scale)) return false;
+    want_V = image[LMS_V];
+    *alpha = *alpha * (double)scale;
+  } else if (words > (long long)(kLmMaxBytes / 4)) {
+    return false;
+  }
+  return lm_view(base, n, out) && (want_V == 0 || out->V == want_V);
+}
 __host__ __device__ inline int lm_in_range(int v, int n) { return (unsigned)v < (unsigned)n ? v : 0; }
 // position of tok among the arcs [lo, hi) (0 <= lo <= hi <= n_arcs, checked by the caller), or -1
 __host__ __device__ inline int lm_find(const LmView& m, int lo, int hi, int tok) {
@@ -554,7 +610,8 @@ __host__ __device__ inline double lm_step(const LmView& m, int state, int tok, i
   if (backoffs) *backoffs = lvl;
   return lm_step_root(m, w, tok, next);
 }
-int ctc_lm_validate(const void* image, size_t bytes, int V);   // decode.hip, host only
+int ctc_lm_validate(const void* image, size_t bytes, int V);   // decode.hip, host only; a single image or a set
+int ctc_lm_set_member(const void* image, size_t bytes, int j, const void** member, size_t* member_bytes, float* scale);   // host only
 int ctc_prefix_beam_search_lm_host(const float* top_logp, const int32_t* top_idx, int T, int k, int beam, int blank,
                                    const void* image, size_t image_bytes, int graph, const void* lm_image, size_t lm_bytes,
                                    double alpha, double beta, int use_eos, int32_t* hyp_tokens, int32_t* hyp_len,

@@ -239,6 +239,7 @@ SIGNATURES = {
     "m3_ctc_beam_ctx_advance": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp]),
     "m3_ctc_beam_ctx_nbest": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "m3_ctc_lm_validate": (_i, [_vp, _sz, _i]),
+    "m3_ctc_ngram_set_member": (_i, [_vp, _sz, _i, _P(_vp), _P(_sz), _P(_f)]),
     "m3_ctc_prefix_beam_search_lm": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _i, _vp, _sz, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _vp]),
     "m3_ctc_beam_lm_state_size": (_sz, [_P(CtcBeamDesc)]),
@@ -341,6 +342,7 @@ SIGNATURES = {
     "m3_aed_ngram_state_size": (_sz, [_P(AedJointDesc)]),
     "m3_aed_ngram_scratch_size": (_sz, [_P(AedJointDesc)]),
     "m3_aed_ngram_reset": (_i, [_P(AedJointDesc), _vp, _sz, _vp, _sz, _vp]),
+    "m3_aed_ngram_reset_set": (_i, [_P(AedJointDesc), _vp, _sz, _vp, _sz, _vp, _vp]),
     "m3_aed_ngram_score": (_i, [_P(AedJointDesc), _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _i, _vp, _i, _i, _f, _vp, _sz, _vp,
                              _d, _d, _i, _vp]),
     "m3_aed_ngram_prune": (_i, [_P(AedJointDesc), _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),

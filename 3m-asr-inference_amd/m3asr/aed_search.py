@@ -32,6 +32,8 @@ N-GRAM LM FUSION AND A LENGTH BONUS (lm=; the contract is restated
 m3_aed_ngram_score and m3_aed_ngram_prune stand where the joint calls stood: still 8 L + 4.  ctc_weight = 0 with an LM is attention
 plus LM: no CTC input, no scorer state; the rows still offer `pre_beam` candidates, because the LM scores the pre-beam only.
 lm_on (per call, per utterance) switches the LM off for single utterances, which then get the bits of the search without it.
+With an NgramLmSet lm_on holds ints: 0 = off, j = member j - 1, whose scale multiplies lm_weight; an utterance gets
+the bits of the search with that member alone and lm_weight * scale.
 Without lm nothing of this exists.
 
 HOTWORD BIASING (context=; the contract is restated in tests/aed_ctx_ref.py).  With a ContextSet (m3asr.context,
@@ -51,6 +53,7 @@ import math
 import torch
 
 from . import _lib, ops
+from .lm import NgramLmSet, lm_flags
 from .rescore import LN_EPS
 
 
@@ -194,7 +197,9 @@ class AttentionBeamSearch:
         ops.aed_search_reset(self.desc, self.state, meta[0], meta[1], cap)
         if self.ctc_weight > 0:
             ops.aed_joint_reset(self.jdesc, self.state, self.jstate, self.ctc)
-        if self.lm is not None:
+        if isinstance(self.lm, NgramLmSet):                       # every utterance starts in its own member's start state
+            ops.aed_lm_reset_set(self.ldesc, self.lstate, self.lm.dev, self.lm_on)
+        elif self.lm is not None:
             ops.aed_lm_reset(self.ldesc, self.lstate, self.lm.dev)
         if self.context is not None:
             ops.aed_bias_reset(self.bdesc, self.bias)
@@ -245,7 +250,13 @@ class AttentionBeamSearch:
             if lm_on is not None:
                 raise _lib.M3Error("search: lm_on given, but the search was built without an LM")
             return
-        on = [1] * self.B if lm_on is None else [int(bool(v)) for v in torch.as_tensor(lm_on).reshape(-1).tolist()]
+        if isinstance(self.lm, NgramLmSet):                       # ints: 0 = off, j = member j - 1 (True / 1 = member 0)
+            vals = None if lm_on is None else torch.as_tensor(lm_on).reshape(-1).tolist()
+            if vals is not None and len(vals) != self.B:
+                raise _lib.M3Error("search: lm_on has %d entries for %d utterances" % (len(vals), self.B))
+            on = lm_flags(self.lm, vals, self.B, "search", _lib.M3Error)
+        else:
+            on = [1] * self.B if lm_on is None else [int(bool(v)) for v in torch.as_tensor(lm_on).reshape(-1).tolist()]
         if len(on) != self.B:
             raise _lib.M3Error("search: lm_on has %d entries for %d utterances" % (len(on), self.B))
         self.lm_on.copy_(torch.tensor(on, dtype=torch.int32))

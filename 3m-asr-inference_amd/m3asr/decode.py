@@ -35,6 +35,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from . import lm as _lm
 from .config import subsampled_len
 
 
@@ -46,6 +47,13 @@ def _same_device(a, b):
         return a.index == b.index
     cur = torch.cuda.current_device() if a.index is None or b.index is None else 0
     return (cur if a.index is None else a.index) == (cur if b.index is None else b.index)
+
+
+def _per_utterance(lm_on, B):
+    """lm_on of a decoding call: None, one value per utterance, or one value (bool / int) for all B of them"""
+    if lm_on is None or torch.is_tensor(lm_on) or isinstance(lm_on, (list, tuple)):
+        return lm_on
+    return [lm_on] * B
 
 
 class EndpointConfig:
@@ -111,7 +119,8 @@ class CtcBeamSearch:
         lm: a m3asr.lm.NgramLm uploaded to `device` (lm.to(device)) -- the search then ranks a prefix y by
         (CTC score + bonus) + (lm_weight log P_LM(y) + length_bonus |y|) (shallow fusion, m3_ctc_beam_lm_*); lm_eos: the
         n-best is ordered with log P(</s> | y) added to the LM score.  Every utterance starts with the LM on; reset(lm_on=)
-        switches it per utterance."""
+        switches it per utterance.  lm may also be a m3asr.lm.NgramLmSet (one device image of several LMs): reset(lm_on=)
+        then picks a member per utterance, whose scale multiplies lm_weight; every utterance starts with member 0."""
         self.desc = ops.ctc_beam_desc(B, beam, max_frames, blank, k)
         self.device = torch.device(device)
         self.context = context
@@ -141,6 +150,14 @@ class CtcBeamSearch:
     def beam(self):
         return self.desc.beam
 
+    def lm_weights(self):
+        """The weight of log P_LM in each utterance's key: lm_weight, or with an NgramLmSet a (B, 1) float32 device tensor of
+        lm_weight * scale of the utterance's member (an utterance without the LM has hyp_lm = 0, whatever stands here)."""
+        if not isinstance(self.lm, _lm.NgramLmSet):
+            return self.lm_weight
+        w = [self.lm_weight * self.lm.scales[j - 1] if 1 <= j <= len(self.lm) else 0.0 for j in self.lm_flags]
+        return torch.tensor(w, dtype=torch.float32).to(self.device).view(-1, 1)
+
     def set_context(self, slots, graph_ids):
         """Graph (position in the ContextSet, -1 = unbiased) of each listed utterance.  It takes effect at the utterance's
         next reset: a search keeps one graph from a reset to the next, because its nodes hold the context state and bonus
@@ -165,7 +182,9 @@ class CtcBeamSearch:
         """slots: None = all B searches; else the utterances to restart (a list, or an int32 device tensor).
         graph_ids (biased search): the graphs the restarted utterances take, one per slot (all B when slots is None).
         lm_on (fused search): whether each restarted utterance runs with the LM, one flag per slot; an utterance keeps its
-        setting from a reset to the next, because its nodes hold the LM state and sum of their prefixes."""
+        setting from a reset to the next, because its nodes hold the LM state and sum of their prefixes.  With an NgramLmSet
+        the flags are ints: 0 / False = off, j = member j - 1 (True / 1 = member 0); a value above len(set) is refused.  A
+        restarted utterance begins from its new member's start state."""
         which = None
         if graph_ids is not None and self.context is None:
             raise _lib.M3Error("CtcBeamSearch.reset: graph_ids without a context")
@@ -181,8 +200,8 @@ class CtcBeamSearch:
             if lm_on is not None:
                 if len(lm_on) != len(which):
                     raise ValueError("reset: %d slots, %d lm_on flags" % (len(which), len(lm_on)))
-                for b, f in zip(which, lm_on):
-                    self.lm_flags[b] = 1 if f else 0
+                for b, f in zip(which, _lm.lm_flags(self.lm, lm_on, len(which), "CtcBeamSearch.reset")):
+                    self.lm_flags[b] = f
         with torch.cuda.stream(stream or torch.cuda.current_stream(self.device)):
             if slots is not None and not torch.is_tensor(slots):
                 slots = torch.tensor([int(b) for b in slots], dtype=torch.int32).to(self.device)
@@ -339,15 +358,18 @@ class CtcDecoder:
         return self.batch_prefix_beam_from_logits(res["out_nosm"], res["out_lens"], beam_size), res["out_nosm"]
 
     def batch_prefix_beam_from_logits(self, logits: torch.Tensor, lens: torch.Tensor, beam_size: int, lm=None, lm_weight=0.5,
-                                      length_bonus=0.0, lm_eos=True, context=None, graph_ids=None):
+                                      length_bonus=0.0, lm_eos=True, context=None, graph_ids=None, lm_on=None):
         """logits (B,T',V) on the device, lens (B,) valid frames per utterance -> n-best per utterance (device search).
         lm: a m3asr.lm.NgramLm on the logits' device -- shallow fusion, as CtcBeamSearch(lm=).  context: a ContextSet on that
-        device -- hotword biasing, as CtcBeamSearch(context=); graph_ids: one graph id per utterance (default graph 0 for all)."""
+        device -- hotword biasing, as CtcBeamSearch(context=); graph_ids: one graph id per utterance (default graph 0 for all).
+        lm_on: as CtcBeamSearch.reset takes it, one value per utterance, or one value for all of them (with an NgramLmSet as
+        lm: 0 = off, j = member j - 1)."""
         B, T = int(logits.shape[0]), int(logits.shape[1])
         search = CtcBeamSearch(B, beam_size, T, self.blank_idx, logits.device, context=context, lm=lm, lm_weight=lm_weight,
                                length_bonus=length_bonus, lm_eos=lm_eos)
-        if context is not None:
-            search.reset(graph_ids=[0] * B if graph_ids is None else graph_ids)
+        if context is not None or lm_on is not None:
+            search.reset(graph_ids=([0] * B if graph_ids is None else graph_ids) if context is not None else None,
+                         lm_on=_per_utterance(lm_on, B))
         search.advance(logits, lens)
         return search.nbest()
 
@@ -371,15 +393,15 @@ class CtcDecoder:
 
     def rescore_from_logits(self, logits: torch.Tensor, lens: torch.Tensor, beam_size: int, ctc_weight: float = 0.0,
                             reverse_weight: float = 0.0, context=None, graph_ids=None, lm=None, lm_weight=0.5, length_bonus=0.0,
-                            lm_eos=True, detail=False):
+                            lm_eos=True, detail=False, lm_on=None):
         """attention_rescoring() behind the encoder: logits (B,T',V) and lens (B,) of the engine's LAST forward (its hidden states
-        are read from the engine), however that forward was fed."""
+        are read from the engine), however that forward was fed.  lm_on: as batch_prefix_beam_from_logits takes it."""
         if self.rescorer is None:
             raise _lib.M3Error("CtcDecoder.attention_rescoring: built without a rescorer (CtcDecoder(engine, rescorer=AttentionRescorer(...)))")
         search = CtcBeamSearch(int(logits.shape[0]), beam_size, int(logits.shape[1]), self.blank_idx, logits.device, context=context,
                                lm=lm, lm_weight=lm_weight, length_bonus=length_bonus, lm_eos=lm_eos)
-        if graph_ids is not None:
-            search.reset(graph_ids=graph_ids)
+        if graph_ids is not None or lm_on is not None:
+            search.reset(graph_ids=graph_ids, lm_on=_per_utterance(lm_on, int(logits.shape[0])))
         search.advance(logits, lens)
         # the residual stream as it is: after_norm rides in the prologue of the rescorer's K / V GEMM
         out = self.rescorer.rescore(self.engine.hidden(normalized=False), lens, search, ctc_weight=ctc_weight,
@@ -388,7 +410,7 @@ class CtcDecoder:
 
     def attention(self, xs: torch.Tensor, xs_lens: torch.Tensor, beam_size: int, decoding_chunk_size: int = -1,
                   num_decoding_left_chunks: int = -1, max_steps=None, detail=False, ctc_weight: float = 0.0, pre_beam=None,
-                  lm=None, lm_weight: float = 0.0, length_bonus: float = 0.0, context=None, graph_ids=None):
+                  lm=None, lm_weight: float = 0.0, length_bonus: float = 0.0, context=None, graph_ids=None, lm_on=None):
         """The reference's decoding mode `attention` for any batch size, all on the device: encoder forward, then the attention
         decoder's own autoregressive beam search over the encoder's hidden states (m3asr.aed_search).  There is
         no first pass, and the right-to-left decoder takes no part.  ctc_weight = 0: CTC scores take no part either.
@@ -402,18 +424,20 @@ class CtcDecoder:
         the rank (1 - ctc_weight) att + ctc_weight ctc + lm_weight lm + length_bonus |y|; detail then appends lm to each hypothesis.
         context: a ContextSet on the engine's device: hotword biasing inside the search, the rank gains the
         hypothesis's bonus; graph_ids: one graph id per utterance (default graph 0 for all, -1 = unbiased); detail then appends
-        bonus and final.  The context scores the pre-beam only: a hotword outside a row's pre_beam best is not rescued."""
+        bonus and final.  The context scores the pre-beam only: a hotword outside a row's pre_beam best is not rescued.
+        lm_on: None or one value per utterance, as AttentionBeamSearch.search takes it: 0 / False = without the LM, and with an
+        NgramLmSet as lm, j = member j - 1."""
         if self.rescorer is None:
             raise _lib.M3Error("CtcDecoder.attention: built without a rescorer (CtcDecoder(engine, rescorer=AttentionRescorer(...)))")
         self._full_context(decoding_chunk_size, num_decoding_left_chunks)
         res = self.forward(xs, xs_lens)
         return self.attention_from_logits(res["out_nosm"], res["out_lens"], beam_size, max_steps=max_steps, detail=detail,
                                           ctc_weight=ctc_weight, pre_beam=pre_beam, lm=lm, lm_weight=lm_weight,
-                                          length_bonus=length_bonus, context=context, graph_ids=graph_ids)
+                                          length_bonus=length_bonus, context=context, graph_ids=graph_ids, lm_on=lm_on)
 
     def attention_from_logits(self, logits: torch.Tensor, out_lens: torch.Tensor, beam_size: int, max_steps=None, detail=False,
                               ctc_weight: float = 0.0, pre_beam=None, lm=None, lm_weight: float = 0.0, length_bonus: float = 0.0,
-                              context=None, graph_ids=None):
+                              context=None, graph_ids=None, lm_on=None):
         """attention() behind the encoder: logits (B,T',V) and out_lens (B,) of the engine's LAST forward (its hidden states are
         read from the engine), however that forward was fed."""
         if self.rescorer is None:
@@ -436,7 +460,7 @@ class CtcDecoder:
                                                                              length_bonus=length_bonus, context=context))
         ctc = res["out_nosm"][:, :frames] if float(ctc_weight) > 0 else None
         return kept[1].search(memory, res["out_lens"].cpu(), raw_memory=True, detail=detail, max_steps=steps, ctc_logits=ctc,
-                              graph_ids=graph_ids)
+                              graph_ids=graph_ids, lm_on=_per_utterance(lm_on, B))
 
     def align(self, xs: torch.Tensor, xs_lens: torch.Tensor, tokens, frame_ms=40):
         """Encoder forward, then the best CTC alignment of tokens[b] to utterance b's frames (m3asr.align): one
@@ -553,7 +577,8 @@ class StreamingCtcDecoder:
         """Restart all streams, or (slot-mode encoder) the listed slots: encoder state, beam search, greedy search,
         endpoint state, (decoder with a rescorer) the encoder memory and (decoder with an aligner) the kept logits.
         graph_ids (decoder with a context): the graph each restarted stream takes, one per slot; a stream restarted without
-        one keeps the graph it had.  lm_on (decoder with an LM): whether each restarted stream runs with the LM."""
+        one keeps the graph it had.  lm_on (decoder with an LM): whether each restarted stream runs with the LM; with an
+        NgramLmSet an int per stream, 0 = off, j = member j - 1 (CtcBeamSearch.reset)."""
         kw = {} if lm_on is None else {"lm_on": lm_on}
         e = self.st.eng
         if slots is None:

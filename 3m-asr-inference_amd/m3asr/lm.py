@@ -30,6 +30,9 @@ import numpy as np
 MAGIC, VERSION = 0x4D4C334D, 1
 MAX_ORDER, MAX_STATES, MAX_BYTES = 8, 1 << 26, 1 << 30
 _HDR_WORDS, _TABLES_AT, _WORDS_AT = 20, 8, 17
+# an LM set: [SET_MAGIC, SET_VERSION, V, G, words, 0, 0, 0], G x [offset words, n words, scale (float32 bits), 0], the members
+SET_MAGIC, SET_VERSION, SET_MAX_MEMBERS, SET_MAX_BYTES = 0x534C334D, 1, 64, 1 << 31
+_SET_HDR_WORDS, _SET_ENTRY_WORDS = 8, 4
 _TABLES = ("uni_logp", "uni_next", "arc_begin", "arc_tok", "arc_next", "arc_logp", "bo_state", "bo_weight", "final")
 BOS, EOS, UNK = -1, -2, -3                         # ids of <s>, </s>, <unk> inside n-gram tuples
 _SPECIAL = {"<s>": BOS, "</s>": EOS, "<unk>": UNK}
@@ -298,6 +301,11 @@ class NgramLm:
             raise ValueError("%s is not an LM image" % path)
         from . import ops
         ops.ctc_lm_validate(image, int(image[2]))
+        return cls._from_image(image, blank)
+
+    @classmethod
+    def _from_image(cls, image, blank=0):
+        """The object over an image that the library has validated: the tables are views into it."""
         self = cls.__new__(cls)
         self.image, self.dev, self.blank = image, None, int(blank)
         self.vocab_size, self.order, self.n_states, self.n_arcs, self.start = (int(v) for v in image[2:7])
@@ -316,3 +324,153 @@ class NgramLm:
         self.validate()
         self.dev = torch.from_numpy(self.image).to(device)
         return self
+
+
+class NgramLmSet:
+    """Several NgramLm over one vocabulary in ONE device image (the LM set of include/m3asr.h), so that every utterance of a
+    batch, every stream of a pool picks its own: lm_on = j in [1, len(set)] is member j - 1, 0 is "without the LM".  scales[j]
+    multiplies the search's lm_weight for member j (in double; 1.0 changes no bit).  The searches take a set wherever they take
+    an NgramLm.
+
+        lms = NgramLmSet([general, medical, legal], scales=[1.0, 0.5, 2.0]).to("cuda")
+        search = CtcBeamSearch(B, beam, max_frames, lm=lms, lm_weight=0.5)
+        search.reset(lm_on=[3, 0, 1, 2])                         # utterance 0: legal, 1: no LM, 2: general, 3: medical
+    """
+
+    def __init__(self, lms, scales=None):
+        lms = list(lms)
+        if not lms:
+            raise ValueError("NgramLmSet: no members")
+        if len(lms) > SET_MAX_MEMBERS:
+            raise ValueError("NgramLmSet: %d members > %d" % (len(lms), SET_MAX_MEMBERS))
+        for j, m in enumerate(lms):
+            if not isinstance(m, NgramLm):
+                raise ValueError("NgramLmSet: member %d is not an NgramLm" % j)
+            if m.vocab_size != lms[0].vocab_size:
+                raise ValueError("NgramLmSet: member %d is over a vocabulary of %d, member 0 over %d" % (j, m.vocab_size, lms[0].vocab_size))
+        scales = [1.0] * len(lms) if scales is None else [float(s) for s in scales]
+        if len(scales) != len(lms):
+            raise ValueError("NgramLmSet: %d scales for %d members" % (len(scales), len(lms)))
+        for j, s in enumerate(scales):
+            with np.errstate(over="ignore", under="ignore"):
+                s32 = float(np.float32(s)) if math.isfinite(s) else s
+            if not (math.isfinite(s32) and s32 > 0.0):
+                raise ValueError("NgramLmSet: scale %r of member %d is not finite and positive (as float32)" % (s, j))
+        self.lms, self.scales = lms, [float(np.float32(s)) for s in scales]      # the scale the kernels see: the float32
+        self.vocab_size, self.blank = lms[0].vocab_size, lms[0].blank
+        self.image = self.pack()
+        self.dev = None
+
+    def __len__(self):
+        return len(self.lms)
+
+    def __getitem__(self, j):
+        return self.lms[j]
+
+    def pack(self):
+        """The set image as a numpy int32 array (not validated): header, directory, then the members' images, byte for byte,
+        each at a multiple of 4 words."""
+        G = len(self.lms)
+        head = np.zeros(_SET_HDR_WORDS + _SET_ENTRY_WORDS * G, dtype=np.int32)
+        off, parts = head.size, []
+        for j, (m, s) in enumerate(zip(self.lms, self.scales)):
+            pad = -off % 4
+            if pad:
+                parts.append(np.zeros(pad, dtype=np.int32))
+                off += pad
+            e = _SET_HDR_WORDS + _SET_ENTRY_WORDS * j
+            head[e], head[e + 1] = off, m.image.size
+            head[e + 2] = np.float32(s).view(np.int32)
+            parts.append(m.image)
+            off += m.image.size
+        if off * 4 > SET_MAX_BYTES:
+            raise ValueError("NgramLmSet: image of %d bytes > %d" % (off * 4, SET_MAX_BYTES))
+        head[:5] = [SET_MAGIC, SET_VERSION, self.vocab_size, G, off]
+        return np.concatenate([head] + parts)
+
+    def validate(self):
+        from . import ops
+        ops.ctc_lm_validate(self.image, self.vocab_size)
+        return self
+
+    def save(self, path):
+        """The set image as .npy."""
+        with open(path, "wb") as f:
+            np.save(f, self.image)
+
+    @classmethod
+    def load(cls, path, blank=0):
+        """A set written by save() (checked by the library before anything is read from it)."""
+        image = np.ascontiguousarray(np.load(path, allow_pickle=False))
+        if image.dtype != np.int32 or image.ndim != 1 or image.size < _SET_HDR_WORDS or int(image[0]) != SET_MAGIC:
+            raise ValueError("%s is not an LM set" % path)
+        from . import ops
+        ops.ctc_lm_validate(image, int(image[2]))
+        self = cls.__new__(cls)
+        self.image, self.dev, self.blank, self.vocab_size = image, None, int(blank), int(image[2])
+        self.lms, self.scales = [], []
+        for j in range(int(image[3])):
+            e = _SET_HDR_WORDS + _SET_ENTRY_WORDS * j
+            self.lms.append(NgramLm._from_image(image[int(image[e]):int(image[e]) + int(image[e + 1])], blank))
+            self.scales.append(float(image[e + 2:e + 3].view(np.float32)[0]))
+        return self
+
+    def to(self, device):
+        """Upload the set (one tensor, .dev) after the library has validated the host copy."""
+        import torch
+        self.validate()
+        self.dev = torch.from_numpy(self.image).to(device)
+        return self
+
+
+def load_lms(specs, units=None, vocab_size=None, use=None):
+    """What the command-line tools make of their --lm options: specs, a list of `PATH` or `PATH:SCALE` (an ARPA file, or an
+    image saved by NgramLm.save, *.npy), and use, the member --lm-use picks.  One PATH without a scale and without use: a plain
+    NgramLm, lm_on None.  Otherwise an NgramLmSet of all of them, and lm_on = use + 1 (use defaults to 0) for every utterance
+    of the run.  -> (lm, lm_on), still on the host."""
+    if isinstance(specs, str):
+        specs = [specs]
+    paths, scales = [], []
+    for spec in specs:
+        path, sep, tail = spec.rpartition(":")
+        try:
+            scale = float(tail) if sep and path else None
+        except ValueError:
+            scale = None
+        paths.append(spec if scale is None else path)
+        scales.append(scale)
+    lms = [NgramLm.load(p) if p.endswith(".npy") else NgramLm.from_arpa(p, units, vocab_size=vocab_size) for p in paths]
+    if len(lms) == 1 and scales[0] is None and use is None:
+        return lms[0], None
+    use = 0 if use is None else int(use)
+    if not 0 <= use < len(lms):
+        raise ValueError("load_lms: use = %d, but %d LM(s) were given" % (use, len(lms)))
+    return NgramLmSet(lms, [1.0 if s is None else s for s in scales]), use + 1
+
+
+def lm_flags(lm, lm_on, n, who, error=ValueError):
+    """The lm_on values of a call as n ints.  None: every utterance runs with the LM (a set: with member 0).  A bool or an int
+    per utterance: True / 1 = on (a set: member 0), False / 0 = off, j = member j - 1 of a set; a value above len(set) is
+    refused here (the kernels would run it as "off", as they run a negative one), and so is a value that is no whole number.
+    error: the exception class of the caller's other refusals."""
+    if lm_on is None:
+        return [1] * n
+    vals = lm_on.reshape(-1).tolist() if hasattr(lm_on, "reshape") else list(lm_on)
+    if len(vals) != n:
+        raise error("%s: lm_on has %d entries for %d utterances" % (who, len(vals), n))
+    out = []
+    for v in vals:
+        if isinstance(lm, NgramLmSet):
+            try:
+                j = int(v)
+                whole = j == v
+            except (TypeError, ValueError):
+                whole = False
+            if not whole:
+                raise error("%s: lm_on = %r is not a whole number (0 = off, j = member j - 1)" % (who, v))
+            if j > len(lm):
+                raise error("%s: lm_on = %r above %d, the set's size (0 = off, j = member j - 1)" % (who, v, len(lm)))
+            out.append(max(j, -1))
+        else:
+            out.append(1 if v else 0)
+    return out

@@ -849,6 +849,17 @@ def ctc_lm_validate(image, V):
     check(_lib.load().m3_ctc_lm_validate(img.ctypes.data_as(C.c_void_p), img.nbytes, int(V)), "m3_ctc_lm_validate")
 
 
+def ctc_lm_set_member(image, j):
+    """m3_ctc_ngram_set_member on a HOST set (numpy int32 words): (member j's image, a view into `image`; its scale)."""
+    import numpy as np
+    img = np.ascontiguousarray(image)
+    member, nbytes, scale = C.c_void_p(), C.c_size_t(0), C.c_float(0.0)
+    check(_lib.load().m3_ctc_ngram_set_member(img.ctypes.data_as(C.c_void_p), img.nbytes, int(j), C.byref(member), C.byref(nbytes),
+                                           C.byref(scale)), "m3_ctc_ngram_set_member")
+    off = (member.value - img.ctypes.data) // 4
+    return img[off:off + nbytes.value // 4], float(scale.value)
+
+
 def ctc_prefix_beam_search_lm_host(top_logp, top_idx, beam, blank=0, image=None, graph=0, lm_image=None, alpha=0.5, beta=0.0,
                                    use_eos=True):
     """ctc_prefix_beam_search_ctx_host with the fused ranking of a HOST LM image (numpy int32 words; None = no LM):
@@ -1321,6 +1332,15 @@ def aed_lm_reset(desc, lstate, lm_image):
     """after aed_search_reset (and aed_joint_reset): every slot in the image's start state; refuses an image of another V"""
     lmi, lm_bytes = _image(lm_image)
     check(_lib.load().m3_aed_ngram_reset(C.byref(desc), _p(lstate), _nbytes(lstate), lmi, lm_bytes, _stream()), "m3_aed_ngram_reset")
+
+
+def aed_lm_reset_set(desc, lstate, lm_image, lm_on):
+    """m3_aed_ngram_reset_set: aed_lm_reset for an LM set; lm_on (B,) int32 on the device picks each utterance's member, whose
+    start state its slots get."""
+    assert lm_on.numel() == desc.search.B
+    lmi, lm_bytes = _image(lm_image)
+    check(_lib.load().m3_aed_ngram_reset_set(C.byref(desc), _p(lstate), _nbytes(lstate), lmi, lm_bytes, _i32(lm_on), _stream()),
+          "m3_aed_ngram_reset_set")
 
 
 def aed_lm_score(desc, state, jstate, scratch, lstate, lscratch, logits, ctc, ctc_weight, lm_image, lm_on, alpha, beta, use_eos=True):

@@ -51,7 +51,8 @@ class AttentionRescorer:
             toks, hlen, score, bonus, n = t[0], t[1], t[2], t[3], t[-1]
             prior = score + bonus
             if len(t) == 6:       # fused search: + lm_weight * log P_LM + length_bonus * |y|
-                prior = prior + (source.lm_weight * t[4] + source.length_bonus * hlen.to(torch.float32))
+                w = source.lm_weights() if hasattr(source, "lm_weights") else source.lm_weight   # an LM set: one weight per utterance
+                prior = prior + (w * t[4] + source.length_bonus * hlen.to(torch.float32))
             return toks, hlen, prior.contiguous(), n
         toks, hlen, score, n = source
         return toks, hlen, score, n

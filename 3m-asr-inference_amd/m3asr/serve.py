@@ -284,7 +284,9 @@ class StreamPool:
     def open(self, context=None, lm=None):
         """Take a free slot and restart it; -> stream id.  Raises M3Error when all B slots are taken.
         context: graph id in the decoder's ContextSet for this session's beam search (None = unbiased).
-        lm: whether this session's beam search runs with the decoder's LM (None = yes if the decoder has one)."""
+        lm: whether this session's beam search runs with the decoder's LM (None = yes if the decoder has one).  A decoder built
+        with an NgramLmSet takes an int as well: lm=j is member j - 1 of the set (True / 1 / None: member 0), 0 / False none;
+        the segments a session is cut into all keep its member."""
         biased = getattr(self.dec, "context", None) is not None
         fused = getattr(self.dec, "lm", None) is not None
         if context is not None and not biased:
@@ -297,7 +299,7 @@ class StreamPool:
                 if biased:
                     kw["graph_ids"] = [-1 if context is None else int(context)]
                 if fused:
-                    kw["lm_on"] = [lm is None or bool(lm)]
+                    kw["lm_on"] = [1 if lm is None else int(lm)]   # True = 1: the LM, or member 0 of a set; an id above the set is refused
                 self.dec.reset(slots=[b], **kw)
                 sid = self.next_sid
                 self.next_sid += 1

@@ -635,8 +635,27 @@ int m3_ctc_beam_ctx_nbest(const m3_ctc_beam_desc* desc, const void* state, size_
  *   _advance / _nbest take both DEVICE images (either may be NULL, 0), graph_of [B] as m3_ctc_beam_ctx_*, lm_on [B] (device
  *   int32; 0 = this utterance runs without the LM, and its result is m3_ctc_beam_ctx_*'s bit for bit) and alpha, beta (and
  *   _nbest use_eos): run-time arguments, not part of the image.  An utterance keeps its lm_on, alpha and beta from a reset to
- *   the next.  _nbest additionally writes hyp_lm [B][beam]. */
+ *   the next.  _nbest additionally writes hyp_lm [B][beam].
+ * AN LM SET is one image of 4-byte little-endian words holding G complete LM images, so that every utterance of
+ * a batch or a pool of streams picks its own LM:
+ *   [0x534c334d, version = 1, V, G, total words, 0, 0, 0]   G x [offset words, n words, scale (float bits), 0]   the members
+ * Each member is an LM image as above, byte for byte, over the set's V; it starts at `offset words` from the start of the set,
+ * a multiple of 4 (members stay 16-byte aligned); members come in ascending order and do not overlap.  Limits: 1 <= G <= 64,
+ * every member within the single image's limits, the set <= 2 GiB; scale finite and > 0.
+ * Every DEVICE entry point that takes an lm_image (m3_ctc_beam_lm_advance / _nbest, m3_aed_ngram_score, m3_aed_bias_score)
+ * takes either kind, told apart by word 0.  With a single image lm_on[b] != 0 means "on", as above.  With a set lm_on[b] = j,
+ * 1 <= j <= G, picks member j - 1; 0 and every other value mean "off" (the rule of graph_of).  The utterance's LM weight is
+ * alpha * (double)scale_j, one double product (scale 1.0 changes no bit); beta and use_eos are the call's.  The kernels resolve
+ * (member, words, scale) once per utterance and range-check the set's header and the directory entry like a single header: a
+ * bad set header means "LM off" for every utterance, a bad entry or member header for that utterance, a bad index inside a
+ * member state 0.  The device calls admit lm_bytes up to the set's 2 GiB, since only the device copy says which kind it is; a
+ * SINGLE image above its own 1 GiB limit runs as "LM off" (the kernels check it where they read word 0).  The start state is the member's: a search restarted with another member begins from that member's start.
+ * m3_ctc_lm_validate takes either kind of HOST image; of a set it checks the header, the directory (alignment, order, bounds,
+ *   scale) and every member by the rules above.
+ * m3_ctc_ngram_set_member: host only; member j in [0, G) of a host set (validated inside the call): *member points into `image`,
+ *   *member_bytes is its size, *scale (may be NULL) its scale -- what m3_ctc_prefix_beam_search_lm takes as its lm_image. */
 int m3_ctc_lm_validate(const void* image, size_t image_bytes, int V);
+int m3_ctc_ngram_set_member(const void* image, size_t image_bytes, int j, const void** member, size_t* member_bytes, float* scale);
 int m3_ctc_prefix_beam_search_lm(const float* top_logp, const int32_t* top_idx, int T, int k, int beam, int blank,
                                  const void* image, size_t image_bytes, int graph, const void* lm_image, size_t lm_bytes,
                                  double alpha, double beta, int use_eos, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score,
@@ -1309,6 +1328,9 @@ int m3_aed_joint_result(const m3_aed_joint_desc* desc, const void* search_state,
  * reset: after the search's (and the joint search's) reset, once per search.  Reads the image's header back (a synchronous
  *   20-word copy: call it outside a stream capture) and refuses an image that is not one or was built for another V; every
  *   slot then holds the image's start state, lm = 0.0, n = 0.
+ * reset_set: reset for an LM set ("LM set" above; a single image is taken too): lm_on (device int32 [B], the values the score
+ *   calls of this search will get) picks each utterance's member, and its slots hold THAT member's start state; an utterance
+ *   that runs without the LM holds state 0.  Reads the header back like reset and refuses a set built for another V.
  * score: the joint score call plus the walk.  ctc is NULL exactly when ctc_weight == 0.  lm_image / lm_bytes: the DEVICE
  *   image; lm_on: device int32 [B]; alpha, beta finite; use_eos 0 or 1.  The kernel range-checks every word of the image it
  *   forms an address from (a bad state or next state means state 0, a bad arc range "no arcs", a token outside [0, V) unk_logp).
@@ -1319,6 +1341,8 @@ size_t m3_aed_ngram_state_size(const m3_aed_joint_desc* desc);
 size_t m3_aed_ngram_scratch_size(const m3_aed_joint_desc* desc);
 int m3_aed_ngram_reset(const m3_aed_joint_desc* desc, void* lm_state, size_t lm_state_bytes, const void* lm_image, size_t lm_bytes,
                     m3_stream stream);
+int m3_aed_ngram_reset_set(const m3_aed_joint_desc* desc, void* lm_state, size_t lm_state_bytes, const void* lm_image, size_t lm_bytes,
+                           const int32_t* lm_on, m3_stream stream);
 int m3_aed_ngram_score(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, const void* joint_state,
                     size_t joint_state_bytes, void* scratch, size_t scratch_bytes, const void* lm_state, size_t lm_state_bytes,
                     void* lm_scratch, size_t lm_scratch_bytes, const float* logits, int ldl, const float* ctc, int ldc, int ctc_rows,

@@ -21,7 +21,9 @@ searched twice on the device, plain and biased towards the phrases (m3asr.contex
 
 lm.arpa is an n-gram LM in ARPA format (or an image saved by m3asr.lm.NgramLm.save, *.npy); units.txt maps its words to
 token ids (`token id` per line; without it the words are token ids).  The scores are searched plain and with the LM fused into
-the ranking (m3asr.lm), together with --hotwords if both are given.
+the ranking (m3asr.lm), together with --hotwords if both are given.  --lm may be given several times, each as PATH or
+PATH:SCALE (SCALE multiplies --lm-weight for that LM): the LMs then travel as ONE device image (m3asr.lm.NgramLmSet) and
+--lm-use K (default 0) picks the one this run decodes with.  One --lm without a scale and without --lm-use is a plain NgramLm.
 
     python3 infer.py -p aed.plan -i feat.npy --rescore [--beam 10] [--ctc-weight 0.5] [--reverse-weight 0.3]
 
@@ -153,10 +155,14 @@ def print_hotword_search(scores, device, args):
 
 
 def load_lm(args, V, device):
-    """--lm [--units]: an ARPA file compiled for V tokens, or a saved image; validated and uploaded"""
-    from m3asr.lm import NgramLm
-    lm = NgramLm.load(args.lm) if args.lm.endswith(".npy") else NgramLm.from_arpa(args.lm, args.units, vocab_size=V)
-    return lm.to(device)
+    """--lm [--units] [--lm-use]: ARPA files compiled for V tokens, or saved images; validated and uploaded.  One --lm without a
+    scale and without --lm-use: (NgramLm, None).  Else (NgramLmSet of all of them, the member --lm-use picks as lm_on)."""
+    from m3asr.lm import load_lms
+    try:
+        lm, lm_on = load_lms(args.lm, args.units, V, args.lm_use)
+    except ValueError as e:
+        raise SystemExit("--lm / --lm-use: %s" % e)
+    return lm.to(device), lm_on
 
 
 def print_lm_search(scores, device, args):
@@ -166,7 +172,7 @@ def print_lm_search(scores, device, args):
     x = torch.from_numpy(np.ascontiguousarray(scores, dtype=np.float32)).to(device)
     x = x.reshape(-1, x.shape[-2], x.shape[-1])
     B, T, V = x.shape
-    lm = load_lm(args, V, device)
+    lm, lm_on = load_lm(args, V, device)
     ctx = None
     if args.hotwords:
         from m3asr.context import ContextGraph, ContextSet, read_phrases
@@ -176,8 +182,8 @@ def print_lm_search(scores, device, args):
     plain.advance(x, lens)
     fused = CtcBeamSearch(B, args.beam, T, device=device, context=ctx, lm=lm, lm_weight=args.lm_weight,
                           length_bonus=args.length_bonus)
-    if ctx is not None:
-        fused.reset(graph_ids=[0] * B)
+    if ctx is not None or lm_on is not None:
+        fused.reset(graph_ids=[0] * B if ctx is not None else None, lm_on=None if lm_on is None else [lm_on] * B)
     fused.advance(x, lens)
     chosen = fused.nbest(detail=True)
     for b, (u, h) in enumerate(zip(plain.nbest(), chosen)):
@@ -215,7 +221,7 @@ def print_attention(helper, feat, feat_len, args):
     from m3asr.rescore import AttentionRescorer
     rescorer = AttentionRescorer(helper.decoder_packed, decoder_config_of(helper.extra), helper.engine.device)
     dec = CtcDecoder(helper.engine, rescorer=rescorer)
-    lm = load_lm(args, rescorer.cfg.vocab, helper.engine.device) if args.lm else None
+    lm, lm_on = load_lm(args, rescorer.cfg.vocab, helper.engine.device) if args.lm else (None, None)
     ctx = None
     if args.hotwords:                                             # the list also goes into the attention search
         from m3asr.context import ContextGraph, ContextSet, read_phrases
@@ -223,7 +229,7 @@ def print_attention(helper, feat, feat_len, args):
         ctx = ContextSet([ContextGraph(read_phrases(args.hotwords), V, score=args.hotword_score)], device=helper.engine.device)
     out = dec.attention(torch.from_numpy(feat), torch.from_numpy(feat_len), args.beam, max_steps=args.max_steps, detail=True,
                         ctc_weight=args.ctc_weight, pre_beam=args.pre_beam, lm=lm, lm_weight=args.lm_weight,
-                        length_bonus=args.length_bonus, context=ctx)
+                        length_bonus=args.length_bonus, context=ctx, lm_on=lm_on)
     for b, (best, hyps) in enumerate(out):
         chosen = next(h for h in hyps if list(h[0]) == best)
         parts = " att=%.4f ctc=%.4f" % (chosen[3], chosen[4]) if args.ctc_weight > 0 or lm is not None or ctx is not None else ""
@@ -249,7 +255,7 @@ def print_long_form(helper, args):
         from m3asr.rescore import AttentionRescorer
         rescorer = AttentionRescorer(helper.decoder_packed, decoder_config_of(helper.extra), dev)
     V = rescorer.cfg.vocab if rescorer is not None else helper.cfg.output_dim
-    lm = load_lm(args, V, dev) if args.lm else None
+    lm, lm_on = load_lm(args, V, dev) if args.lm else (None, None)
     ctx = None
     if args.hotwords:
         from m3asr.context import ContextGraph, ContextSet, read_phrases
@@ -257,13 +263,13 @@ def print_long_form(helper, args):
     if args.attention:
         mode, name = "attention", "attention"
         kw = dict(beam_size=args.beam, max_steps=args.max_steps, ctc_weight=args.ctc_weight, pre_beam=args.pre_beam, lm=lm,
-                  lm_weight=args.lm_weight, length_bonus=args.length_bonus, context=ctx)
+                  lm_weight=args.lm_weight, length_bonus=args.length_bonus, context=ctx, lm_on=lm_on)
     elif args.rescore:
         mode, name = "rescore", "rescored"
         kw = dict(beam_size=args.beam, ctc_weight=args.ctc_weight, reverse_weight=args.reverse_weight)
     elif lm is not None or ctx is not None:
         mode, name = "beam", "fused" if lm is not None else "biased"
-        kw = dict(beam_size=args.beam, lm=lm, lm_weight=args.lm_weight, length_bonus=args.length_bonus, context=ctx)
+        kw = dict(beam_size=args.beam, lm=lm, lm_weight=args.lm_weight, length_bonus=args.length_bonus, context=ctx, lm_on=lm_on)
     else:
         mode, name = "greedy", "greedy"
     try:
@@ -334,7 +340,9 @@ if __name__ == "__main__":
     p.add_argument("--hotwords", help="Phrase list: one phrase of space-separated token ids per line.")
     p.add_argument("--hotword-score", type=float, default=3.0, help="Bonus per matched token (log domain).")
     p.add_argument("--beam", type=int, default=10, help="Beam size of the prefix beam searches run with --hotwords / --lm.")
-    p.add_argument("--lm", help="n-gram LM: an ARPA file, or a compiled image (*.npy) saved by m3asr.lm.NgramLm.save.")
+    p.add_argument("--lm", action="append", metavar="PATH[:SCALE]", help="n-gram LM: an ARPA file, or a compiled image (*.npy) saved by "
+                   "m3asr.lm.NgramLm.save.  Given several times (each with an optional :SCALE on --lm-weight), the LMs become one LM set.")
+    p.add_argument("--lm-use", type=int, default=None, metavar="K", help="Several --lm: the one this run decodes with (default 0).")
     p.add_argument("--units", help="`token id` per line: the ARPA's words as token ids (default: the words are token ids).")
     p.add_argument("--lm-weight", type=float, default=0.5, help="Weight of log P_LM in the ranking.")
     p.add_argument("--length-bonus", type=float, default=0.0, help="Bonus per token of a prefix in the ranking.")

@@ -11,6 +11,8 @@ graph, the cost of the biased kernel alone), next to the unbiased one; its host 
 --lm N: the fused search (m3_ctc_beam_lm_advance) with a synthetic trigram LM of about N n-grams (tools/lm_synth.py; or
 --lm-image: an image saved by m3asr.lm.NgramLm.save), with the --context graph if one is given, next to the plain search: its
 figures, their ratio to the plain ones of the same run, the same kernel with lm_on = 0, and m3_ctc_prefix_beam_search_lm.
+--lm-set G (with --lm): the same advance over an NgramLmSet of G such LMs (scales 1.0 / 0.5 / 2.0 in turn): every utterance
+on member 0, the members cycling over the utterances, and every utterance off.
 
 Device: one advance over all frames, and the same frames in chunks of --chunk (one advance per chunk), timed with hipEvents
 (top-k excluded: it is the same launch for both searches); run under `rocprofv3 --kernel-trace --stats` for kernel times.
@@ -43,6 +45,7 @@ def main():
     ap.add_argument("--lm", type=int, default=None, metavar="N_NGRAMS")
     ap.add_argument("--lm-image", default=None, metavar="FILE.npy")
     ap.add_argument("--lm-weight", type=float, default=0.5)
+    ap.add_argument("--lm-set", type=int, default=0, metavar="G", help="--lm: also time the fused advance over an LM set of G members")
     args = ap.parse_args()
     B, T, V, beam = args.batch, args.frames, args.vocab, args.beam
     g = torch.Generator().manual_seed(0)
@@ -135,6 +138,18 @@ def main():
         out["lm"] = {"n_grams": lm.n_grams, "order": lm.order, "states": lm.n_states, "arcs": lm.n_arcs,
                      "image_bytes": int(lm.image.nbytes), "weight": a, "with_context": cs is not None, **res,
                      "host_routine_ms": round(float(np.median(hs)), 4)}
+        if args.lm_set:                                # the same advance over an LM set of G members
+            from lm_synth import synthetic_lm
+            from m3asr.lm import NgramLmSet
+            G = args.lm_set
+            lms = [lm] + [synthetic_lm(args.lm or lm.n_grams or 20000, V, seed=j) for j in range(1, G)]
+            lset = NgramLmSet(lms, [(1.0, 0.5, 2.0)[j % 3] for j in range(G)]).to("cuda")
+            sres = {}
+            for name, flags in (("member0", [1] * B), ("mixed", [1 + b % G for b in range(B)]), ("all_off", [0] * B)):
+                on = torch.tensor(flags, dtype=torch.int32, device="cuda")
+                sres[name + "_one_advance_ms"] = round(timed(lambda: ops.ctc_beam_lm_advance(desc, lstate, image, go, lset.dev, on, a, w,
+                                                                                            lp, ix, nf), lreset), 4)
+            out["lm_set"] = {"members": G, "image_bytes": int(lset.image.nbytes), **sres}
     print(json.dumps(out))
 
 

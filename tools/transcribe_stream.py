@@ -102,9 +102,13 @@ def main(a):
     if a.hotwords:
         from m3asr.context import ContextGraph, ContextSet, read_phrases
         kw["context"] = ContextSet([ContextGraph(read_phrases(a.hotwords), V, score=a.hotword_score)], device=eng.device)
+    lm_on = None                                                  # several --lm (an LM set): the member --lm-use picks
     if a.lm:
-        from m3asr.lm import NgramLm
-        lm = NgramLm.load(a.lm) if a.lm.endswith(".npy") else NgramLm.from_arpa(a.lm, a.units, vocab_size=V)
+        from m3asr.lm import load_lms
+        try:
+            lm, lm_on = load_lms(a.lm, a.units, V, a.lm_use)
+        except ValueError as e:
+            raise SystemExit("--lm / --lm-use: %s" % e)
         kw.update(lm=lm.to(eng.device), lm_weight=a.lm_weight, length_bonus=a.length_bonus)
     if a.timestamps:
         from m3asr.align import CtcAligner
@@ -131,7 +135,7 @@ def main(a):
     except M3Error as e:
         raise SystemExit("%s: %s" % (a.wav_file, e))
     piece = rate // 10                                            # 100 ms of samples
-    sid = pool.open(context=0 if a.hotwords else None)
+    sid = pool.open(context=0 if a.hotwords else None, lm=lm_on)
 
     def show_times(times):
         if times is None:
@@ -181,7 +185,9 @@ if __name__ == "__main__":
     p.add_argument("--rule", action="append", help="must_decoded (0/1),min trailing blank ms,min length ms; up to four, in order.")
     p.add_argument("--hotwords", help="Phrase list: one phrase of space-separated token ids per line.")
     p.add_argument("--hotword-score", type=float, default=3.0)
-    p.add_argument("--lm", help="n-gram LM: an ARPA file, or a compiled image (*.npy).")
+    p.add_argument("--lm", action="append", metavar="PATH[:SCALE]", help="n-gram LM: an ARPA file, or a compiled image (*.npy).  Given "
+                   "several times (each with an optional :SCALE on --lm-weight), the LMs become one LM set.")
+    p.add_argument("--lm-use", type=int, default=None, metavar="K", help="Several --lm: the one the session decodes with (default 0).")
     p.add_argument("--units", help="`token id` per line: the ARPA's words as token ids.")
     p.add_argument("--lm-weight", type=float, default=0.5)
     p.add_argument("--length-bonus", type=float, default=0.0)
