@@ -77,30 +77,42 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
   // ONE batch of kernel-argument loads.  hipcc fetches each field of the by-value parameter block where it is first used: the
   // prologue was ~8 dependent rounds of s_load + s_waitcnt (2 400 cycles = 1.1 us before the first global load was issued,
   // in-kernel stamps, tools/diag_gemm_f32.py).  Naming the fields as scalar operands of one empty asm statement makes it load
-  // them together, one wait.
-  asm volatile("" ::"s"(p.A), "s"(p.lda), "s"(p.W), "s"(p.bias), "s"(p.Y), "s"(p.ldy), "s"(p.M), "s"(p.N), "s"(p.K), "s"(p.mode),
-               "s"(p.n_tiles), "s"(p.m_tiles), "s"(p.xcd_swizzle), "s"(p.m_dev), "s"(p.resid), "s"(p.ldr), "s"(p.act), "s"(p.alpha),
-               "s"(p.mask_in), "s"(p.mask_out), "s"(p.row_len), "s"(p.rows_per_batch), "s"(p.sig_col0));
-  if (ACCI) asm volatile("" ::"s"(p.acc_init));
-  if (LN == LN_EPI) asm volatile("" ::"s"(p.ln_wsum), "s"(p.ln_wbeta), "s"(p.ln_eps));
-  if (LN == LN_PRO) asm volatile("" ::"s"(p.ln_gamma), "s"(p.ln_beta), "s"(p.ln_eps), "s"(p.ln_out), "s"(p.ld_ln_out), "s"(p.ln_on_a2));
-  if (!CONV) asm volatile("" ::"s"(p.A2), "s"(p.lda2), "s"(p.K1));
-  if (CONV) asm volatile("" ::"s"(p.conv_T1), "s"(p.conv_F1), "s"(p.conv_T2), "s"(p.conv_F2), "s"(p.conv_C));
+  // them together, one wait.  ONE statement: with the fields an instantiation adds in statements of their own the loads came out
+  // as two batches with a wait between them.  A statement takes 30 operands, so the 32-bit fields go in pairs;
+  // a field the instantiation never reads is a constant 0 here and is not loaded.
+  {
+    auto pk = [](int lo, int hi) { return (unsigned long long)(unsigned)lo | ((unsigned long long)(unsigned)hi << 32); };
+    constexpr bool EPI = LN == LN_EPI, PRO = LN == LN_PRO;
+    asm volatile("" ::"s"(p.A), "s"(p.W), "s"(p.bias), "s"(p.Y), "s"(p.m_dev), "s"(p.resid), "s"(p.row_len),
+                 "s"(pk(p.lda, p.ldy)), "s"(pk(p.M, p.N)), "s"(pk(p.K, p.mode)), "s"(pk(p.n_tiles, p.m_tiles)),
+                 "s"(pk(p.xcd_swizzle, p.ldr)), "s"(pk(p.act, __float_as_int(p.alpha))), "s"(pk(p.mask_in, p.mask_out)),
+                 "s"(pk(p.rows_per_batch, p.sig_col0)), "s"(pk(p.one_run, LN != LN_NONE ? __float_as_int(p.ln_eps) : 0)),
+                 "s"(pk((int)p.div_m_tiles.mul, p.div_m_tiles.shift)), "s"(pk((int)p.div_n_tiles.mul, p.div_n_tiles.shift)),
+                 "s"(pk((int)p.div_rpb.mul, p.div_rpb.shift)),
+                 "s"(ACCI ? p.acc_init : nullptr), "s"(EPI ? p.ln_wsum : PRO ? p.ln_gamma : nullptr),
+                 "s"(EPI ? p.ln_wbeta : PRO ? p.ln_beta : nullptr), "s"(PRO ? p.ln_out : nullptr),
+                 "s"(PRO ? pk(p.ld_ln_out, p.ln_on_a2) : 0ull), "s"(CONV ? nullptr : p.A2),
+                 "s"(CONV ? pk(p.conv_T1, p.conv_F1) : pk(p.lda2, p.K1)), "s"(CONV ? pk(p.conv_T2, p.conv_F2) : 0ull),
+                 "s"(CONV ? p.conv_C : 0));
+  }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int col = lane & 15, kq = lane >> 4;
   const int Nout = GLU ? (p.N >> 1) : p.N;
 
   // ---- workgroup -> (column tile, row tile); XCD-aware when the column-tile count allows ----
+  // (the same order as `j % m_tiles, j / m_tiles` and `id % n_tiles, id / n_tiles`, on the scalar unit: the launcher's multiplier
+  //  instead of a 30-instruction division sequence in front of the first address)
   int n_tile, m_tile;
   {
     const int id = bid;
     if (p.xcd_swizzle) {
       const int j = id >> 3;
-      m_tile = j % p.m_tiles;
-      n_tile = (j / p.m_tiles) * 8 + (id & 7);
+      const int q = gemm_div_by(j, p.div_m_tiles);
+      m_tile = j - q * p.m_tiles;
+      n_tile = q * 8 + (id & 7);
     } else {
-      n_tile = id % p.n_tiles;
-      m_tile = id / p.n_tiles;
+      m_tile = gemm_div_by(id, p.div_n_tiles);
+      n_tile = id - m_tile * p.n_tiles;
     }
   }
   const int n0 = n_tile * 16;
@@ -215,10 +227,19 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
   // (everything below is issued behind the first group of operand loads: it is needed at epilogue time only)
   // the epilogue wave's bias / residual are requested up front (they would otherwise be a dependent
   // memory round trip at the very end of a microsecond-scale kernel)
-  const int ep_mt = wave;              // wave w finishes row sub-tile w (w < MT)
-  const bool is_ep = wave < MT;
+  // MT >= 2: wave w < MT finishes row sub-tile w, four accumulator rows per lane.  MT == 1 (SPREAD): the one sub-tile's four
+  // accumulator rows go to waves 0 .. 3 -- wave w finishes row w of every quad (rows 4 kq + w), one epilogue and one store per
+  // lane, instead of four epilogues in sequence on wave 0 while the other waves idle.  Same operands, same order, per element.
+  constexpr bool SPREAD = MT == 1;
+  constexpr int ER = SPREAD ? 1 : 4;   // accumulator rows a lane finishes
+  static_assert(NW >= 4, "the spread epilogue needs four waves");
+  const int ep_mt = SPREAD ? 0 : wave;
+  const int ep_r0 = SPREAD ? wave : 0;   // (wave-uniform) the first of them
+  const bool is_ep = SPREAD ? (NW == 4 || wave < 4) : wave < MT;
   const int ep_n = n0 + col;
-  float bias0 = 0.f, bias1 = 0.f, wsum0 = 0.f, wsum1 = 0.f, wbeta0 = 0.f, wbeta1 = 0.f, res[4] = {0.f, 0.f, 0.f, 0.f};
+  float bias0 = 0.f, bias1 = 0.f, wsum0 = 0.f, wsum1 = 0.f, wbeta0 = 0.f, wbeta1 = 0.f, res[ER];
+#pragma unroll
+  for (int r = 0; r < ER; ++r) res[r] = 0.f;
   if (is_ep && ep_n < Nout) {
     if (p.bias) {
       bias0 = p.bias[ep_n];
@@ -234,24 +255,33 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
     }
     if (p.resid) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = min(m0 + 16 * ep_mt + 4 * kq + r, p.M - 1);
+      for (int r = 0; r < ER; ++r) {
+        const int m = min(m0 + 16 * ep_mt + 4 * kq + ep_r0 + r, p.M - 1);
         res[r] = p.resid[(size_t)m * p.ldr + ep_n];
       }
     }
   }
-  // padded frames (masked_fill(0) before / after the layer, masked_fill_kernel.cu:27-54): resolved here for the rows this lane
-  // finishes.  An input-masked row has a zero A row, i.e. a zero accumulator: the epilogue writes that instead of zeroing the
-  // A fragments in front of every MFMA (a select + hazard nop per MFMA on the critical path of a one-tile wave)
+  // padded frames (masked_fill(0) before / after the layer, masked_fill_kernel.cu:27-54), for the rows this lane finishes.  An
+  // input-masked row has a zero A row, i.e. a zero accumulator: the epilogue writes that instead of zeroing the A fragments in
+  // front of every MFMA (a select + hazard nop per MFMA on the critical path of a one-tile wave).
+  // MT == 1: only the REQUEST for the utterance's length stands here, behind the operand group like bias and residual, and
+  // `frame >= length` is formed in the epilogue.  Resolved here, each row was a memory round trip of its own in front of the
+  // epilogue wave's first MFMA, and the first of them drained the whole operand group.
+  // MT >= 2: four lengths held across the MFMAs cost those forms a wave per SIMD; they ask for the four together and resolve
+  // them here, one wait instead of four.
+  int pad_len = 0;
   bool pad4[4] = {false, false, false, false};
   if (is_ep && (p.mask_in || p.mask_out)) {
+    if (SPREAD) {
+      pad_len = gemm_row_len_request(p, min(m0 + 4 * kq + ep_r0, p.M - 1));
+    } else {
+      int len4[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int m = min(m0 + 16 * ep_mt + 4 * kq + r, p.M - 1);
-      pad4[r] = gemm_row_padded(p, m);
+      for (int r = 0; r < 4; ++r) len4[r] = gemm_row_len_request(p, min(m0 + 16 * ep_mt + 4 * kq + r, p.M - 1));
+#pragma unroll
+      for (int r = 0; r < 4; ++r) pad4[r] = gemm_row_frame(p, min(m0 + 16 * ep_mt + 4 * kq + r, p.M - 1)) >= len4[r];
     }
   }
-
 
   // ---- LN_PRO: row statistics (two-pass) + gamma/beta to LDS, while the first loads are in flight ----
   float a_mean[MT], a_rstd[MT];
@@ -331,6 +361,8 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
           if (LN == LN_PRO && in_ln) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) a[j] = (a[j] - a_mean[mt]) * a_rstd[mt] * g4[j] + b4[j];
+            // (holding the normalised fragments and storing them behind the last MFMA, so that no store acknowledgement is waited
+            //  for between MFMAs, was built for the ACCI form and measured: no shorter)
             if (ln_out_row[mt] != nullptr) stg4(ln_out_row[mt] + (k - ln_k0), a);
           }
           if (LN == LN_EPI && in_ln) {
@@ -377,7 +409,7 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
       for (int t = 0; t < NT; ++t) acc[mt][t] += acc2[mt][t];
   }
   M3_GDIAG(asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); dg[4] = __builtin_amdgcn_s_memtime();)
-  // ---- cross-wave K reduction through LDS, then epilogue (wave w finishes row sub-tile w) ----
+  // ---- cross-wave K reduction through LDS, then epilogue (MT >= 2: wave w finishes row sub-tile w; MT == 1: accumulator row w) ----
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -403,26 +435,27 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
 
   if (is_ep) {
     const int mt = ep_mt;
-    f32x4 v[NT];
+    float v[NT][ER];
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
+      for (int r = 0; r < ER; ++r) {
+        const int e = (ep_r0 + r) * 64 + lane;
         float sum = 0.f;   // fixed summation order over the K-split -> bitwise reproducible
 #pragma unroll
         for (int w = 0; w < NW; w += 4)
-          sum += (red[w][mt * NT + t][r * 64 + lane] + red[w + 1][mt * NT + t][r * 64 + lane]) +
-                 (red[w + 2][mt * NT + t][r * 64 + lane] + red[w + 3][mt * NT + t][r * 64 + lane]);
+          sum += (red[w][mt * NT + t][e] + red[w + 1][mt * NT + t][e]) + (red[w + 2][mt * NT + t][e] + red[w + 3][mt * NT + t][e]);
         v[t][r] = sum;
       }
     if (ep_n < Nout) {
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 16 * mt + 4 * kq + r;
+      for (int r = 0; r < ER; ++r) {
+        const int row = 16 * mt + 4 * kq + ep_r0 + r;
         const int m = m0 + row;
         if (m >= p.M) continue;
         float y0 = v[0][r], y1 = v[NT - 1][r];
-        const bool pad = pad4[r];
+        bool pad = pad4[r];
+        if (SPREAD && (p.mask_in || p.mask_out)) pad = gemm_row_frame(p, m) >= pad_len;
         if (LN != LN_EPI && p.mask_in && pad) y0 = y1 = 0.f;      // zero A row -> zero accumulator
         float mean = 0.f, rstd = 1.f;
         if (LN == LN_EPI) {
@@ -454,8 +487,15 @@ __device__ __forceinline__ void gemm_f32_body(const GemmParams& p, const int bid
            })
 }
 
+// Waves per SIMD an instantiation has to keep (the second argument of __launch_bounds__; 1 asks for nothing).  The two forms
+// named here came out two VGPRs above the 96 that five waves allow, with no value more to hold than their neighbours, which fit
+// (register allocation, not need): asked for, they fit as well, with no scratch.
+constexpr int gemm_f32_min_waves(int MT, bool GLU, int NW, bool CONV, int LN, int NBUF, bool WF, bool dual) {
+  return (MT == 1 && !GLU && NW == 8 && LN == LN_NONE && NBUF == 1 && ((dual && WF) || (!dual && CONV))) ? 5 : 1;
+}
+
 template <int MT, bool GLU, int NW, bool CONV, int LN, int NBUF, bool ACCI = false, bool WF = false>
-__global__ __launch_bounds__(64 * NW) void gemm_f32_kernel(const GemmParams p) {
+__global__ __launch_bounds__(64 * NW, gemm_f32_min_waves(MT, GLU, NW, CONV, LN, NBUF, WF, false)) void gemm_f32_kernel(const GemmParams p) {
   gemm_f32_body<MT, GLU, NW, CONV, LN, NBUF, ACCI, WF>(p, (int)blockIdx.x);
 }
 
@@ -534,12 +574,21 @@ int launch_router_embed_prefix(const GemmPlan& plan, const GemmParams& p, const 
 }
 // (the second problem's work-group ids start at a multiple of 8, so that "id % 8 = XCD" holds for its XCD-aware tile order too)
 template <int MT, bool GLU, int NW, int LN, bool WF = false>
-__global__ __launch_bounds__(64 * NW) void gemm_f32_dual_kernel(const GemmParams p0, const GemmParams p1, const int n0) {
+__global__ __launch_bounds__(64 * NW, gemm_f32_min_waves(MT, GLU, NW, false, LN, 1, WF, true)) void gemm_f32_dual_kernel(const GemmParams p0, const GemmParams p1, const int n0) {
   if ((int)blockIdx.x < n0) {
     if ((int)blockIdx.x < p0.n_tiles * p0.m_tiles) gemm_f32_body<MT, GLU, NW, false, LN, 1, false, WF>(p0, (int)blockIdx.x);
   } else {
     gemm_f32_body<MT, GLU, NW, false, LN, 1, false, WF>(p1, (int)blockIdx.x - n0);
   }
+}
+
+// the fields of the parameter block the skinny fp32 launchers fill: the plan's tile order, the multipliers of its divisors, one_run
+static void gemm_fill_tiles(GemmParams& p, const GemmPlan& plan) {
+  p.n_tiles = plan.n_tiles; p.m_tiles = plan.m_tiles; p.xcd_swizzle = plan.xcd_swizzle;
+  p.div_m_tiles = gemm_div(plan.m_tiles);
+  p.div_n_tiles = gemm_div(plan.n_tiles);
+  p.div_rpb = gemm_div(p.rows_per_batch > 0 ? p.rows_per_batch : 1);
+  p.one_run = p.rows_per_batch >= p.M ? 1 : 0;
 }
 
 // two independent problems of one instantiation in ONE launch (gemm_dual_fusable holds for the two records)
@@ -548,9 +597,7 @@ int launch_gemm_f32_dual(const GemmLaunch& a, const GemmLaunch& b, hipStream_t s
   GemmParams q[2] = {a.p, b.p};
   const GemmPlan& pa = a.plan;
   const GemmPlan* const plans[2] = {&a.plan, &b.plan};
-  for (int i = 0; i < 2; ++i) {
-    q[i].n_tiles = plans[i]->n_tiles; q[i].m_tiles = plans[i]->m_tiles; q[i].xcd_swizzle = plans[i]->xcd_swizzle;
-  }
+  for (int i = 0; i < 2; ++i) gemm_fill_tiles(q[i], *plans[i]);
   const int n0 = (int)align_up((size_t)q[0].n_tiles * q[0].m_tiles, 8);
   dim3 grid(n0 + q[1].n_tiles * q[1].m_tiles);
 #define M3_DUAL(GLU_, NW_, LN_)                                                                                             \
@@ -572,7 +619,7 @@ int launch_gemm_f32_dual(const GemmLaunch& a, const GemmLaunch& b, hipStream_t s
 
 int launch_gemm_f32_skinny(const GemmPlan& plan, const GemmParams& pin, hipStream_t stream) {
   GemmParams p = pin;
-  p.n_tiles = plan.n_tiles; p.m_tiles = plan.m_tiles; p.xcd_swizzle = plan.xcd_swizzle;
+  gemm_fill_tiles(p, plan);
   dim3 grid(p.n_tiles * p.m_tiles);
   const int mt = plan.mt, nw = plan.nw, ln = plan.ln;
   if (p.acc_init != nullptr) {        // (plan_gemm: 16-row tiles, 4 / 8 waves, one load group, affine LayerNorm on the A2 half)

@@ -11,6 +11,19 @@ __device__ __forceinline__ bool gemm_row_padded(const GemmParams& p, int m) {
   return (m % p.rows_per_batch) >= p.row_len[m / p.rows_per_batch];
 }
 
+// x / d by the host's multiplier (kernels.h GemmDiv): exact for 0 <= x < 2^31
+__device__ __forceinline__ int gemm_div_by(int x, const GemmDiv& d) { return (int)(((unsigned long long)(unsigned)x * d.mul) >> d.shift); }
+
+// The same test in two halves, for a kernel that must not wait for row_len where it asks for it (gemm_f32_body): the request
+// up front (the utterance's length, in flight), the comparison `gemm_row_frame(p, m) >= len` where the row is finished.
+// one_run (rows_per_batch >= M, set by the launcher): utterance 0, frame == m.
+__device__ __forceinline__ int gemm_row_len_request(const GemmParams& p, int m) {
+  return p.row_len[p.one_run ? 0 : gemm_div_by(m, p.div_rpb)];
+}
+__device__ __forceinline__ int gemm_row_frame(const GemmParams& p, int m) {
+  return p.one_run ? m : m - gemm_div_by(m, p.div_rpb) * p.rows_per_batch;
+}
+
 // folded LayerNorm: mean and 1 / std of a K-wide row from its sum and sum of squares
 __device__ __forceinline__ void ln_mean_rstd(float sum, float sumsq, int K, float eps, float& mean, float& rstd) {
   mean = sum / (float)K;

@@ -10,6 +10,19 @@ namespace m3 {
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2, ACT_GLU = 3 };
 enum { GEMM_A_PLAIN = 0, GEMM_A_CONCAT2 = 1, GEMM_A_CONV3X3S2 = 2 };
 
+// x / d for 0 <= x < 2^31 as (x * mul) >> shift in 64 bits, exact: shift = 31 + l with l = ceil(log2 d), mul = ceil(2^shift / d)
+// < 2^32 (Granlund & Montgomery, "Division by invariant integers using multiplication", 1994, theorem 4.2 with N = 31:
+// 2^shift <= mul * d <= 2^shift + 2^l).  On the device two multiplications and a shift instead of a ~30-instruction sequence.
+struct GemmDiv { unsigned mul = 0; int shift = 0; };
+inline GemmDiv gemm_div(int d) {
+  int l = 0;
+  while (l < 31 && (1u << l) < (unsigned)d) ++l;
+  GemmDiv r;
+  r.shift = 31 + l;
+  r.mul = (unsigned)(((1ull << r.shift) + (unsigned)d - 1) / (unsigned)d);
+  return r;
+}
+
 struct GemmParams {
   // operands: Y[M,Nout] = epi( pro(A)[M,K] . W[N,K]^T )
   const float* A = nullptr; int lda = 0;
@@ -66,6 +79,11 @@ struct GemmParams {
   int w_frag = 0;
   // filled by the launchers from the GemmPlan
   int n_tiles = 0, m_tiles = 0, xcd_swizzle = 0;
+  // skinny fp32 kernel only (gemm_fill_tiles, gemm.hip).  one_run: rows_per_batch >= M, so every row belongs to utterance 0 and its
+  // frame is its row (B = 1, and a packed batch whose rows_per_batch is its row count): the masks need no division at all.
+  // div_m_tiles / div_n_tiles / div_rpb: the divisors of the tile order and of the masks as multiplications (GemmDiv)
+  int one_run = 0;
+  GemmDiv div_m_tiles, div_n_tiles, div_rpb;
 };
 // ---- the dense GEMM family (gemm_plan.hip) ----
 // The family has six kernels.  plan_gemm is the ONE place that checks a problem's operands and says which kernel runs it, in
