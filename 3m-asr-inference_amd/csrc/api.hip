@@ -847,6 +847,22 @@ int m3_ctc_beam_lm_nbest(const m3_ctc_beam_desc* desc, const void* state, size_t
   return launch_ctc_beam_lm_nbest(desc, state, state_bytes, image, image_bytes, graph_of, lm_image, lm_bytes, lm_on, alpha, beta,
                                   use_eos, hyp_tokens, hyp_len, hyp_score, hyp_bonus, hyp_lm, n_hyps, (hipStream_t)stream);
 }
+int m3_wfst_validate(const void* image, size_t image_bytes, int V) { return wfst_validate(image, image_bytes, V); }
+size_t m3_wfst_search_state_size(const m3_wfst_search_desc* desc) { return wfst_search_state_size(desc); }
+int m3_wfst_search_reset(const m3_wfst_search_desc* desc, void* state, size_t state_bytes, const void* graph, size_t graph_bytes,
+                         const int32_t* slots, int n, m3_stream stream) {
+  return launch_wfst_search_reset(desc, state, state_bytes, graph, graph_bytes, slots, n, (hipStream_t)stream);
+}
+int m3_wfst_search_advance(const m3_wfst_search_desc* desc, void* state, size_t state_bytes, const void* graph, size_t graph_bytes,
+                           const float* logp, int ld, int T_chunk, const int32_t* n_frames, m3_stream stream) {
+  return launch_wfst_search_advance(desc, state, state_bytes, graph, graph_bytes, logp, ld, T_chunk, n_frames, (hipStream_t)stream);
+}
+int m3_wfst_search_result(const m3_wfst_search_desc* desc, const void* state, size_t state_bytes, const void* graph,
+                          size_t graph_bytes, int final, int max_words, int32_t* words, int32_t* frames, int32_t* n_words,
+                          float* cost, int32_t* flags, int32_t* status, m3_stream stream) {
+  return launch_wfst_search_result(desc, state, state_bytes, graph, graph_bytes, final, max_words, words, frames, n_words, cost,
+                                   flags, status, (hipStream_t)stream);
+}
 size_t m3_ctc_greedy_stream_state_size(const m3_ctc_greedy_desc* desc) { return ctc_greedy_stream_state_size(desc); }
 int m3_ctc_greedy_stream_reset(const m3_ctc_greedy_desc* desc, void* state, size_t state_bytes, m3_stream stream) {
   return launch_ctc_greedy_stream_reset(desc, state, state_bytes, (hipStream_t)stream);

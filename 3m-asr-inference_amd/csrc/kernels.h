@@ -652,6 +652,16 @@ int launch_ctc_greedy_stream_advance(const m3_ctc_greedy_desc* d, void* state, s
                                      int V, const int32_t* n_frames, int32_t* frame_ids, hipStream_t stream);
 int launch_ctc_greedy_stream_tokens(const m3_ctc_greedy_desc* d, const void* state, size_t bytes, int32_t* tokens,
                                     int32_t* n_tokens, hipStream_t stream);
+// ctc_wfst.hip: token-passing beam search over a compiled graph
+int wfst_validate(const void* image, size_t bytes, int V);   // host only
+size_t wfst_search_state_size(const m3_wfst_search_desc* d);
+int launch_wfst_search_reset(const m3_wfst_search_desc* d, void* state, size_t bytes, const void* image, size_t image_bytes,
+                             const int32_t* slots, int n, hipStream_t stream);
+int launch_wfst_search_advance(const m3_wfst_search_desc* d, void* state, size_t bytes, const void* image, size_t image_bytes,
+                               const float* logp, int ld, int T_chunk, const int32_t* n_frames, hipStream_t stream);
+int launch_wfst_search_result(const m3_wfst_search_desc* d, const void* state, size_t bytes, const void* image, size_t image_bytes,
+                              int final, int max_words, int32_t* words, int32_t* frames, int32_t* n_words, float* cost,
+                              int32_t* flags, int32_t* status, hipStream_t stream);
 // endpoint detection next to the two searches (ctc_beam.hip)
 size_t ctc_endpoint_state_size(const m3_ctc_endpoint_desc* d);
 int launch_ctc_endpoint_reset(const m3_ctc_endpoint_desc* d, void* state, size_t bytes, hipStream_t stream,

@@ -102,6 +102,11 @@ class CtcEndpointDesc(C.Structure):  # m3_ctc_endpoint_desc
                 ("rule", CtcEndpointRule * 4)]
 
 
+class WfstSearchDesc(C.Structure):  # m3_wfst_search_desc
+    _fields_ = [(n, C.c_int32) for n in ("B", "max_frames", "token_cap", "record_cap", "max_active", "n_states", "n_levels", "V")] + [
+        ("beam", C.c_float), ("acoustic_scale", C.c_float)]
+
+
 class AedMemoryDesc(C.Structure):  # m3_aed_memory_desc
     _fields_ = [("B", C.c_int32), ("max_frames", C.c_int32), ("D", C.c_int32)]
 
@@ -248,6 +253,11 @@ SIGNATURES = {
     "m3_ctc_beam_lm_advance": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _d, _d, _vp, _vp, _i, _vp, _vp]),
     "m3_ctc_beam_lm_nbest": (_i, [_P(CtcBeamDesc), _vp, _sz, _vp, _sz, _vp, _vp, _sz, _vp, _d, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                   _vp]),
+    "m3_wfst_validate": (_i, [_vp, _sz, _i]),
+    "m3_wfst_search_state_size": (_sz, [_P(WfstSearchDesc)]),
+    "m3_wfst_search_reset": (_i, [_P(WfstSearchDesc), _vp, _sz, _vp, _sz, _vp, _i, _vp]),
+    "m3_wfst_search_advance": (_i, [_P(WfstSearchDesc), _vp, _sz, _vp, _sz, _vp, _i, _i, _vp, _vp]),
+    "m3_wfst_search_result": (_i, [_P(WfstSearchDesc), _vp, _sz, _vp, _sz, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "m3_ctc_greedy_stream_state_size": (_sz, [_P(CtcGreedyDesc)]),
     "m3_ctc_greedy_stream_reset": (_i, [_P(CtcGreedyDesc), _vp, _sz, _vp]),
     "m3_ctc_greedy_stream_reset_slots": (_i, [_P(CtcGreedyDesc), _vp, _sz, _vp, _i, _vp]),

@@ -17,6 +17,9 @@ and return types), running on the device through libm3asr_hip.so:
   two passes,   StreamingCtcDecoder(..., rescorer=...) keeps every stream's encoder memory on the device (m3_aed_memory_*) and
   streaming     rescore() runs the second pass over a stream's n-best when its utterance ends; StreamPool(rescore=True).
 
+  graph         CtcDecoder.ctc_wfst_search: token passing over a compiled decoding graph (TLG) -- word LMs, a closed vocabulary,
+                pronunciation variants -- returning words (m3_wfst_*, m3asr.wfst: DecodingGraph, CtcWfstSearch).
+
   token times   when each token of a hypothesis was spoken (m3_ctc_align_*, m3asr.align): CtcDecoder.align for the hypotheses of
                 any mode above, StreamingCtcDecoder(..., aligner=CtcAligner(...)).align() on the logits the decoder kept per
                 stream; StreamPool(timestamps=True).
@@ -373,6 +376,20 @@ class CtcDecoder:
         search.advance(logits, lens)
         return search.nbest()
 
+
+    def ctc_wfst_search(self, xs: torch.Tensor, xs_lens: torch.Tensor, graph, decoding_chunk_size: int = -1,
+                        num_decoding_left_chunks: int = -1, **kw):
+        """WeNet's ctc_wfst_beam_search on the device: the forward, then token passing over `graph`, a m3asr.wfst.DecodingGraph
+        on the engine's device.  -> word ids per utterance.  kw: CtcWfstSearch's options (beam, max_active, acoustic_scale,
+        token_cap, record_cap, max_state_bytes) and detail= (a dict per utterance: words, frames, cost, reached_final, status)."""
+        self._full_context(decoding_chunk_size, num_decoding_left_chunks)
+        res = self.forward(xs, xs_lens)
+        return self.wfst_from_logits(res["out_nosm"], res["out_lens"], graph, **kw)
+
+    def wfst_from_logits(self, logits: torch.Tensor, lens: torch.Tensor, graph, **kw):
+        """logits (B,T',V) on the device, lens (B,) valid frames per utterance -> word ids per utterance (device search)."""
+        from .wfst import wfst_from_logits
+        return wfst_from_logits(logits, lens, graph, **kw)
 
     def attention_rescoring(self, xs: torch.Tensor, xs_lens: torch.Tensor, beam_size: int, decoding_chunk_size: int = -1,
                             num_decoding_left_chunks: int = -1, ctc_weight: float = 0.0, reverse_weight: float = 0.0,

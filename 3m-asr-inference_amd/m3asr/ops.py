@@ -943,6 +943,54 @@ def ctc_beam_lm_nbest(desc, state, image, graph_of, lm_image, lm_on, alpha, beta
     return toks, hlen, score, bonus, lm, n
 
 
+# ---- WFST decoding (m3asr.wfst builds the graph images)
+def wfst_validate(image, V):
+    """m3_wfst_validate on a HOST image (numpy int32 words); raises M3Error naming the first offence."""
+    import numpy as np
+    img = np.ascontiguousarray(image)
+    check(_lib.load().m3_wfst_validate(img.ctypes.data_as(C.c_void_p), img.nbytes, int(V)), "m3_wfst_validate")
+
+
+def wfst_search_state_size(desc):
+    """bytes of device state for desc (host-only call); M3Error on a bad descriptor."""
+    n = _lib.load().m3_wfst_search_state_size(C.byref(desc))
+    if n == 0 and desc.B > 0:
+        raise _lib.M3Error("m3_wfst_search_state_size failed: " + _lib.last_error())
+    return n
+
+
+def wfst_search_reset(desc, state, graph, slots=None):
+    """graph: the device image (int32 words); slots: None = every utterance, else an int32 device tensor."""
+    check(_lib.load().m3_wfst_search_reset(C.byref(desc), _p(state), state.numel() * state.element_size(), _i32(graph),
+                                           graph.numel() * 4, _i32(slots), 0 if slots is None else slots.numel(), _stream()),
+          "m3_wfst_search_reset")
+
+
+def wfst_search_advance(desc, state, graph, logp, n_frames):
+    """logp (B, T_chunk, V) float32 log-probabilities with unit column stride and dense frames, n_frames (B,) int32, device."""
+    B, Tc, V = logp.shape
+    assert B == desc.B and V == desc.V and n_frames.numel() == B and logp.is_cuda and logp.dtype == torch.float32
+    assert logp.stride(2) == 1 and logp.stride(0) == Tc * logp.stride(1), "logp: (B, T, V) rows with one leading dimension"
+    check(_lib.load().m3_wfst_search_advance(C.byref(desc), _p(state), state.numel() * state.element_size(), _i32(graph),
+                                             graph.numel() * 4, C.c_void_p(logp.data_ptr()), logp.stride(1), Tc, _i32(n_frames),
+                                             _stream()), "m3_wfst_search_advance")
+
+
+def wfst_search_result(desc, state, graph, final=True, max_words=1, out=None):
+    """-> (words (B, max_words) -1 padded, frames (B, max_words), n_words (B,), cost (B,) f32, reached_final (B,), status (B,)),
+    device.  out: the six tensors to write into (the tests pass guarded ones)."""
+    dev, B = state.device, desc.B
+    if out is None:
+        out = (torch.empty(B, max_words, dtype=torch.int32, device=dev), torch.empty(B, max_words, dtype=torch.int32, device=dev),
+               torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.float32, device=dev),
+               torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+    words, frames, n_words, cost, flags, status = out
+    check(_lib.load().m3_wfst_search_result(C.byref(desc), _p(state), state.numel() * state.element_size(), _i32(graph),
+                                            graph.numel() * 4, int(bool(final)), int(max_words), _i32(words), _i32(frames),
+                                            _i32(n_words), _f32(cost), _i32(flags), _i32(status), _stream()), "m3_wfst_search_result")
+    return out
+
+
 def ctc_greedy_stream_desc(B, max_frames, blank=0):
     d = _lib.CtcGreedyDesc(int(B), int(max_frames), int(blank))
     if _lib.load().m3_ctc_greedy_stream_state_size(C.byref(_lib.CtcGreedyDesc(1, d.max_frames, d.blank))) == 0:

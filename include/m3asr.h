@@ -1411,6 +1411,90 @@ int m3_aed_bias_prune(const m3_aed_joint_desc* desc, void* search_state, size_t 
 int m3_aed_bias_result(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, const m3_aed_bias* bias,
                        float* bonus, int32_t* ctx_state, float* att, m3_stream stream);
 
+/* WFST decoding: CTC token-passing beam search over a compiled graph (TLG) on the device (csrc/ctc_wfst.hip, DESIGN.md 38;
+ * restated on the host in tests/wfst_ref.py).  The searches above work on tokens; this one walks a weighted transducer in
+ * the tropical semiring -- a lexicon composed with a word-level LM and a CTC token topology -- and returns WORDS.
+ *
+ * Graph image (m3asr.wfst.DecodingGraph builds it; m3_wfst_validate checks a HOST copy before it is uploaded): 4-byte
+ * little-endian words.
+ *   header, 20 words: [0] magic "M3FS" (0x5346334D)  [1] version 1  [2] V  [3] n_states  [4] n_arcs  [5] start  [6] n_levels
+ *     [7] 0  [8..15] word offsets of the tables below, in that order  [16] words in the image  [17..19] 0
+ *   arc_begin[n_states + 1], eps_begin[n_states]: the arcs of state s are [arc_begin[s], arc_begin[s + 1]), the emitting
+ *     ones first, its epsilon-input arcs from eps_begin[s]; both groups sorted by (ilabel, dst)
+ *   arc_ilabel, arc_olabel, arc_dst (int32), arc_weight (float32) [n_arcs];  final (float32), eps_level (int32) [n_states]
+ *   ilabel 0 is epsilon and consumes no frame; ilabel i >= 1 consumes one frame of CTC output id i - 1.  olabel 0 is "no
+ *   output", olabel >= 1 a word id.  Weights are float32 costs; final = +inf means "not final"; no weight is -0.0.
+ *   eps_level[s] is the length of the longest path of epsilon-input arcs ending in s; n_levels = max eps_level + 1.
+ * m3_wfst_validate refuses, naming the first offence: a size that is no multiple of 4 or above 1 GiB, a wrong magic, version, V
+ *   or word count, n_states outside [1, 2^26], a table outside the image, arc_begin that is not monotone from 0 to n_arcs,
+ *   eps_begin outside its state's arcs, an ilabel outside [0, V] or on the wrong side of eps_begin, unsorted arcs, a negative
+ *   olabel, a dst outside [0, n_states), an arc weight that is not finite or is -0.0, a final weight that is NaN, -inf or -0.0,
+ *   no final state, a cycle of epsilon-input arcs (a state on it is named), a wrong eps_level, n_levels wrong or above 64.
+ *
+ * The search is Viterbi token passing with one token per graph state.  All cost arithmetic is float32, every add and multiply
+ * rounded on its own (no fused multiply-add).  Per utterance: a cost and a history index per live state, and a pool of history
+ * records (prev, olabel, frame); a record is made only when an arc with olabel != 0 wins.
+ * Ranking.  Everywhere "min" is the minimum of the 64-bit key (ordered bits of cost) << 32 | arc id: on equal cost the smaller
+ *   arc index wins; on the device a 64-bit atomic min per destination state, so nothing depends on thread order.  A candidate
+ *   whose cost is not finite is dropped.  Costs are never -0.0: the start cost is +0.0, no weight is -0.0 and a sum rounded to
+ *   nearest is -0.0 only when both terms are; the ordered-bits key would tell the two zeros apart, a float comparison does not.
+ * Start (reset).  A token on the start state, cost +0.0, no history, no arc; then the epsilon closure (d) with frame 0 and
+ *   cutoff 0.0 + beam.
+ * Frame t, logp its log-softmax row:
+ *   (a) best = the smallest live cost; a token is expandable when cost <= best + beam; if more than max_active are, exactly the
+ *       max_active smallest by (cost, state id) stay expandable (a radix select over that key).
+ *   (b) for every expandable token (s, c) and emitting arc a of s: cand = (c + w_a) + ((-acoustic_scale) * logp[ilabel_a - 1]),
+ *       min into next[dst_a].
+ *   (c) best_e = the smallest cost in next, cutoff = best_e + beam; a token above cutoff is dropped (not live).  If next is
+ *       empty the search is dead: M3_WFST_DEAD, sticky; the frame and all later ones are no-ops and the result is empty.
+ *   (d) for L = 0 .. n_levels - 1: every state of next with eps_level L and cost <= cutoff has its final cost (its epsilon
+ *       predecessors have lower levels).  Its history is resolved from its winning arc: the source's history of the frame
+ *       before for an emitting winner, of this frame for an epsilon winner; if the winner's olabel != 0 a record
+ *       (that history, olabel, t) is appended and becomes the state's history.  Then its epsilon arcs are relaxed:
+ *       cand = c + w_a, kept only if finite and <= cutoff, min into next[dst_a].  Every token is expanded once, with its final
+ *       cost; there is no iteration to a fixed point.  Record indices may differ from run to run, the sequences they encode not.
+ *   After (d) next is the live set (its states with cost <= cutoff).
+ * Result.  partial (final = 0): the words of the live token with the smallest (cost, state).  final = 1: the smallest
+ *   (cost + final[state], state) over live states whose sum is finite, reached_final = 1; if there is none, the partial with
+ *   reached_final = 0.  Per utterance: the words, the frame of each word's record, the cost, reached_final, the status.
+ * Capacities fail soft.  token_cap bounds the states touched per frame (dropped ones included; checked after (b) and after every
+ *   level of (d)), record_cap the record pool (checked when a closure ends), max_frames the frames between resets (a frame
+ *   beyond it is not taken).  Exceeding one sets M3_WFST_TOKEN_CAP / RECORD_CAP / MAX_FRAMES in the sticky status; the utterance
+ *   stops advancing until its reset and its result is n_words = -1, cost +inf.  Nothing is written out of bounds.
+ *
+ * m3_wfst_search_desc: n_states, n_levels and V are the graph's (a graph with other values is refused per utterance with
+ *   M3_WFST_BAD_GRAPH); beam > 0 (+inf allowed), max_active >= 1, acoustic_scale finite; V <= 12288 (the row is staged in LDS).
+ * state: caller-owned device memory, m3_wfst_search_state_size bytes (0 = bad descriptor), 16-byte aligned; per utterance a
+ *   16-word header, two dense state-indexed arrays of 64-bit keys and two of history indices (24 bytes per graph state), two
+ *   touched lists [token_cap], n_levels worklists [token_cap], the record pool [3][record_cap].  The dense arrays are cleared
+ *   through the touched list, never per frame as a whole; reset clears them whole.
+ * reset: slots NULL = all B utterances, else n utterance indices (device int32).  Other utterances' bytes are not touched.
+ * advance: logp [B][T_chunk][ld] float32 on the device (ld >= V), n_frames[B] (device) frames of each row that count.  One
+ *   work-group of 1024 threads per utterance, all frames in one launch, no host sync.
+ * result: words / frames [B][max_words] int32 (-1 padded), n_words / flags (reached_final) / status [B] int32, cost [B] float32,
+ *   all on the device.  A word sequence longer than max_words gives n_words = -1 and M3_WFST_WORD_CAP in the returned status.
+ * Every call refuses, before any launch: a bad descriptor, a state that is too small or misaligned, a null pointer. */
+#define M3_WFST_DEAD 1
+#define M3_WFST_TOKEN_CAP 2
+#define M3_WFST_RECORD_CAP 4
+#define M3_WFST_MAX_FRAMES 8
+#define M3_WFST_BAD_GRAPH 16
+#define M3_WFST_WORD_CAP 32
+typedef struct m3_wfst_search_desc {
+  int32_t B, max_frames, token_cap, record_cap, max_active;
+  int32_t n_states, n_levels, V;
+  float beam, acoustic_scale;
+} m3_wfst_search_desc;
+int m3_wfst_validate(const void* image, size_t image_bytes, int V);
+size_t m3_wfst_search_state_size(const m3_wfst_search_desc* desc);
+int m3_wfst_search_reset(const m3_wfst_search_desc* desc, void* state, size_t state_bytes, const void* graph, size_t graph_bytes,
+                         const int32_t* slots, int n, m3_stream stream);
+int m3_wfst_search_advance(const m3_wfst_search_desc* desc, void* state, size_t state_bytes, const void* graph, size_t graph_bytes,
+                           const float* logp, int ld, int T_chunk, const int32_t* n_frames, m3_stream stream);
+int m3_wfst_search_result(const m3_wfst_search_desc* desc, const void* state, size_t state_bytes, const void* graph,
+                          size_t graph_bytes, int final, int max_words, int32_t* words, int32_t* frames, int32_t* n_words,
+                          float* cost, int32_t* flags, int32_t* status, m3_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,14 @@ hypothesis is aligned to the forward's CTC output and one line per token follows
 `<token> <start ms> <end ms> <conf>`, conf being the token's largest posterior inside its span; `no alignment` for a
 hypothesis that CTC cannot align.  Without the flag nothing is added to the output.
 
+    python3 infer.py -p encoder.plan -i feat.npy --wfst graph.txt|graph.npy [--words words.txt] [--wfst-beam 16] [--wfst-max-active 7000]
+                     [--acoustic-scale 1.0]
+
+WFST decoding (m3asr.wfst): the CTC output is searched through a decoding graph (TLG) on the device and the words
+are printed.  graph.txt is AT&T text with numeric labels, as `fstprint TLG.fst` writes it (ilabel = token id + 1, 0 = epsilon);
+graph.npy an image saved by DecodingGraph.save (tools/make_lexicon_graph.py writes one from a lexicon).  words.txt (`word id`
+per line) turns the word ids into words.  With --timestamps every word is followed by the time of its record, `<word> <ms>`.
+
     python3 infer.py -p encoder.plan -w meeting.wav --vad [--vad-max-segment 3000 ...] [--max-batch 16] [any of the modes above]
 
 Long recordings (m3asr.longform): the engine refuses an utterance whose subsampled length reaches the plan's
@@ -193,6 +201,32 @@ def print_lm_search(scores, device, args):
     return [list(h[0][0]) for h in chosen]
 
 
+def print_wfst_search(scores, device, args, frame_ms=40):
+    """--wfst: the words of every utterance (all T' frames), found by token passing over the decoding graph."""
+    import torch
+    from m3asr._lib import M3Error
+    from m3asr.wfst import DecodingGraph, read_words, wfst_from_logits
+    x = torch.from_numpy(np.ascontiguousarray(scores, dtype=np.float32)).to(device)
+    x = x.reshape(-1, x.shape[-2], x.shape[-1])
+    B, T, V = x.shape
+    try:
+        graph = (DecodingGraph.load(args.wfst) if args.wfst.endswith(".npy") else DecodingGraph.from_fst_text(args.wfst, V)).to(device)
+        if graph.vocab_size != V:
+            raise ValueError("the graph was built for %d tokens, the plan has %d" % (graph.vocab_size, V))
+        names = read_words(args.words) if args.words else {}
+        out = wfst_from_logits(x, torch.full((B,), T, dtype=torch.int32), graph, beam=args.wfst_beam, max_active=args.wfst_max_active,
+                               acoustic_scale=args.acoustic_scale, detail=True)
+    except (ValueError, OSError, M3Error) as e:
+        raise SystemExit("--wfst: %s" % e)
+    for b, r in enumerate(out):
+        words = [names.get(w, str(w)) for w in r["words"]]
+        print("utt %d wfst: cost=%.4f final=%d words=%s" % (b, r["cost"], r["reached_final"], " ".join(words)))
+        if args.timestamps:
+            print("utt %d wfst times:" % b)
+            for w, f in zip(words, r["frames"]):
+                print("%s %d" % (w, f * frame_ms))
+
+
 def print_rescore(helper, feat, feat_len, args):
     """Best hypothesis of every utterance after the first pass and after attention rescoring."""
     import torch
@@ -321,7 +355,9 @@ def main(args):
         chosen.append(("fused", print_lm_search(outputs[0], helper.engine.device, args)))
     elif args.hotwords:
         chosen.append(("biased", print_hotword_search(outputs[0], helper.engine.device, args)))
-    if args.timestamps:
+    if args.wfst:
+        print_wfst_search(outputs[0], helper.engine.device, args)
+    if args.timestamps and (chosen or not args.wfst):
         for mode, hyps in chosen or [("greedy", greedy_hyps(outputs[0], helper.engine.device))]:
             print_times(outputs[0], helper.engine.device, mode, hyps)
     if base is not None:
@@ -354,6 +390,11 @@ if __name__ == "__main__":
     p.add_argument("--max-steps", type=int, default=None, help="--attention: the most tokens per hypothesis.")
     p.add_argument("--pre-beam", type=int, default=None, help="--attention --ctc-weight W: candidates per hypothesis that the CTC scorer sees.")
     p.add_argument("--timestamps", action="store_true", help="Token times: align the chosen hypothesis to the CTC output (start / end ms, confidence).")
+    p.add_argument("--wfst", metavar="GRAPH", help="WFST decoding: a decoding graph as AT&T text (fstprint) or a saved image (*.npy).")
+    p.add_argument("--words", help="--wfst: `word id` per line, to print words instead of word ids.")
+    p.add_argument("--wfst-beam", type=float, default=16.0, help="--wfst: the beam, in cost.")
+    p.add_argument("--wfst-max-active", type=int, default=7000, help="--wfst: the most tokens expanded per frame.")
+    p.add_argument("--acoustic-scale", type=float, default=1.0, help="--wfst: multiplies the log-probabilities.")
     p.add_argument("--vad", action="store_true", help="-w: cut a long recording on the device (energy VAD + segmenter) and decode its segments in batches.")
     p.add_argument("--vad-energy-threshold", type=float, default=5.0, help="--vad: Kaldi's vad-energy-threshold.")
     p.add_argument("--vad-energy-mean-scale", type=float, default=0.5, help="--vad: Kaldi's vad-energy-mean-scale.")
