@@ -1,8 +1,12 @@
-// Joint CTC/attention decoding: the attention beam search of DESIGN.md 21 with every candidate also scored by its
-// CTC PREFIX probability (Watanabe et al. 2017) and ranked by  key = (1 - w) att + w ctc.  The step keeps the launches of
-// aed_search.hip up to the output layer; m3_aed_joint_score and m3_aed_joint_prune then take the place of m3_aed_search_prune.
-// They work on the SAME search state (aed_search_state.h: headers, double-buffered records, token and ancestry paths; the
-// record's score word holds the joint key) plus two blobs of their own:
+// The fused step of the attention beam search: a score and a prune launch that take the place of
+// m3_aed_search_prune behind the output layer and rank every candidate by its attention log-probability plus up to three parts:
+// its CTC prefix probability (CTC), an n-gram LM's (LM), a context graph's bonus (CTX).  ONE score and ONE prune kernel template on
+// <CTC, LM, CTX, Lx> serve the seven forms with at least one part; three families of entry points (m3_aed_joint_*, m3_aed_ngram_*,
+// m3_aed_bias_*) reach them through one call record, one check and one launch table (the host half at the end of this file).
+//
+// CTC (m3_aed_joint_*): every candidate is also scored by its CTC PREFIX probability (Watanabe et al. 2017) and
+// ranked by  key = (1 - w) att + w ctc.  The kernels work on the SAME search state (aed_search_state.h: headers, double-buffered
+// records, token and ancestry paths; the record's score word holds the joint key) plus two blobs of their own:
 //
 //   scorer state (fp32 words), per row r, double-buffered by the parity of its utterance's step like the records:
 //       [ att, ctc (= psi of the hypothesis), 0, 0, rn[F], rb[F] ]      F = max_frames
@@ -20,9 +24,8 @@
 // reads a word that another one writes in the same launch: score reads buffer `step & 1` and writes only its row's scratch;
 // prune reads the scratch and writes the other buffer.  A done utterance is left bit for bit alone in all blobs.
 //
-// N-GRAM LM FUSION AND THE LENGTH BONUS (m3_aed_ngram_*).  The score and prune kernels are templates on <CTC, LM>:
-// <true, false> is the joint step above, unchanged; with LM every candidate also takes one step through the LM image of
-// kernels.h (lm_step's terms in lm_step's order) and  key = jkey + (float)(alpha lm' + beta n'),  jkey the joint key above;
+// LM: N-GRAM LM FUSION AND THE LENGTH BONUS (m3_aed_ngram_*).  Every candidate also takes one step through the LM
+// image of kernels.h (lm_step's terms in lm_step's order) and  key = jkey + (float)(alpha lm' + beta n'),  jkey the joint key above;
 // with CTC = false (ctc_weight = 0) there is no scorer state, no frame chain, the ctc part is 0 and jkey = att'.  Two more blobs:
 //
 //   LM state (int32 words), per row, double-buffered like the records:  [ lm_state, n, lm (double, 2 words), att, 0, 0, 0 ]
@@ -33,11 +36,11 @@
 // Prune copies the survivors' (lm_state', lm') from the scratch: nothing is walked twice.  An utterance whose lm_on is 0 (or
 // whose image fails lm_view) adds nothing: its keys, parts, records and scorer states are the joint step's bits.
 //
-// HOTWORD BIASING (m3_aed_bias_*).  A third template flag: <CTC, LM, CTX>.  With CTX every candidate also takes one arc
-// of its utterance's context graph (kernels.h ctx_graph_view; the image, its compiler and its validator are the CTC search's) and
+// CTX: HOTWORD BIASING (m3_aed_bias_*).  Every candidate also takes one arc of its utterance's context graph
+// (kernels.h ctx_graph_view; the image, its compiler and its validator are the CTC search's) and
 //   key = jkey + (float)extra,   extra = (alpha lm' + beta n') + bonus' with an LM, bonus' without,   in double, rounded once.
-// A token adds delta[state][cls[token]] and moves to next[state][..]; eos hands back pot[state] and ends in state 0.  The four
-// CTX = false instantiations are the code they were.  Two more blobs, sized by B, beam and pre_beam alone:
+// A token adds delta[state][cls[token]] and moves to next[state][..]; eos hands back pot[state] and ends in state 0.
+// Two more blobs, sized by B, beam and pre_beam alone:
 //
 //   context state (int32 words), per row, double-buffered like the records:  [ ctx_state, att, bonus (double, 2 words) ]
 //     att is kept here only by the <false, false, true> form, which has neither a scorer state nor an LM state to keep it in.
@@ -45,6 +48,12 @@
 //
 // Prune copies the survivors' (ctx_state', bonus') from the scratch.  An utterance whose graph_of is outside [0, G) (or whose
 // image fails ctx_graph_view or was built for another V) adds nothing and carries (0, 0.0) along.
+//
+// WHERE THE FORM IS DECIDED.  An entry point says which parts its call has (FusedCall::ctc / lm / ctx, from its family,
+// ctc_weight and which optional pointers are given); check_call checks exactly those parts' blobs, and launch_fused picks the
+// instantiation by  ctc | lm << 1 | ctx << 2  from a table whose slot 0 is empty.  Nothing else in this file branches on the form.
+#include <type_traits>
+
 #include "aed_search_state.h"
 #include "kernels.h"
 
@@ -85,51 +94,6 @@ template <class L>
 struct Biased : L {
   CtxFuse cx;
 };
-
-int check_joint_desc(const m3_aed_joint_desc* d) {
-  M3_REQUIRE(d != nullptr, "aed_joint: null descriptor");
-  if (int rc = check_search_desc(&d->search)) return rc;
-  const m3_aed_search_desc* s = &d->search;
-  M3_REQUIRE(s->V >= 2, "aed_joint: V = %d, blank and eos need two different ids", s->V);
-  M3_REQUIRE(d->pre_beam >= s->beam && d->pre_beam <= AS_MAX_BEAM && d->pre_beam <= s->V,
-             "aed_joint: pre_beam = %d, need beam = %d <= pre_beam <= min(%d, V = %d)", d->pre_beam, s->beam, AS_MAX_BEAM, s->V);
-  M3_REQUIRE(d->max_frames >= 1 && d->max_frames <= (1 << 20), "aed_joint: max_frames = %d outside [1, 2^20]", d->max_frames);
-  const size_t R = (size_t)s->B * s->beam, F = (size_t)d->max_frames, K = (size_t)d->pre_beam;
-  M3_REQUIRE(R * 2 * (JS_HDR + 2 * F) <= (size_t)INT_MAX, "aed_joint: %zu rows of %zu frames overflow the int32 offsets of the scorer state", R, F);
-  M3_REQUIRE(R * K * (JC_WORDS + 2 * F) <= (size_t)INT_MAX,
-             "aed_joint: %zu rows x %zu candidates x %zu frames overflow the int32 offsets of the candidate scratch", R, K, F);
-  return 0;
-}
-
-size_t joint_row_words(const m3_aed_joint_desc* d) { return 2 * (JS_HDR + 2 * (size_t)d->max_frames); }
-size_t joint_state_bytes(const m3_aed_joint_desc* d) {
-  return align_up(4 * (size_t)d->search.B * d->search.beam * joint_row_words(d), 256);
-}
-size_t joint_scratch_bytes(const m3_aed_joint_desc* d) {
-  const size_t R = (size_t)d->search.B * d->search.beam;
-  return align_up(4 * R * d->pre_beam * (JC_WORDS + 2 * (size_t)d->max_frames), 256);
-}
-
-// everything a joint entry point checks before it launches: descriptor, the three blobs
-int check_joint(const m3_aed_joint_desc* d, const void* st, size_t st_bytes, const void* js, size_t js_bytes, const void* scr,
-                size_t scr_bytes, bool with_scratch, const char* what) {
-  if (int rc = check_joint_desc(d)) return rc;
-  if (int rc = check_search_state(&d->search, st, st_bytes, what)) return rc;
-  M3_REQUIRE(js_bytes >= joint_state_bytes(d), "%s: scorer state %zu bytes < required %zu", what, js_bytes, joint_state_bytes(d));
-  M3_REQUIRE(d->search.B == 0 || (js != nullptr && ((uintptr_t)js & 15) == 0), "%s: the scorer state must be 16-byte aligned device memory", what);
-  if (with_scratch) {
-    M3_REQUIRE(scr_bytes >= joint_scratch_bytes(d), "%s: scratch %zu bytes < required %zu", what, scr_bytes, joint_scratch_bytes(d));
-    M3_REQUIRE(d->search.B == 0 || (scr != nullptr && ((uintptr_t)scr & 15) == 0), "%s: the scratch must be 16-byte aligned device memory", what);
-  }
-  return 0;
-}
-
-int check_ctc(const m3_aed_joint_desc* d, const float* ctc, int ldc, int ctc_rows, const char* what) {
-  M3_REQUIRE(ldc >= d->search.V, "%s: ldc = %d < V = %d", what, ldc, d->search.V);
-  M3_REQUIRE(ctc_rows >= 0, "%s: ctc_rows = %d", what, ctc_rows);
-  M3_REQUIRE(d->search.B == 0 || ctc != nullptr, "%s: null CTC log-probabilities", what);
-  return 0;
-}
 
 // max + log(exp(a - max) + exp(b - max)); -inf when both are: no -inf - -inf is ever formed.  exp(max - max) is exactly 1, so the
 // sum is 1 + exp(min - max): one exponential, no branch (the chain of m3_aed_joint_score is one wave alone on its SIMD, its time is
@@ -593,62 +557,6 @@ __global__ __launch_bounds__(64) void aed_joint_result_kernel(const int32_t* __r
 }
 
 // ------------------------------------------------------------------------------------------------------------------- LM
-// What a descriptor must hold for the LM entry points: with CTC everything check_joint_desc asks; without, the search's own
-// checks and the pre-beam's (no scorer state, so max_frames is not looked at).  Then the int32 offsets of the two LM blobs.
-int check_lm_desc(const m3_aed_joint_desc* d, bool ctc) {
-  M3_REQUIRE(d != nullptr, "aed_ngram: null descriptor");
-  if (ctc) {
-    if (int rc = check_joint_desc(d)) return rc;
-  } else {
-    if (int rc = check_search_desc(&d->search)) return rc;
-    const m3_aed_search_desc* s = &d->search;
-    M3_REQUIRE(s->V >= 2, "aed_ngram: V = %d, a token and eos need two different ids", s->V);
-    M3_REQUIRE(d->pre_beam >= s->beam && d->pre_beam <= AS_MAX_BEAM && d->pre_beam <= s->V,
-               "aed_ngram: pre_beam = %d, need beam = %d <= pre_beam <= min(%d, V = %d)", d->pre_beam, s->beam, AS_MAX_BEAM, s->V);
-  }
-  const size_t R = (size_t)d->search.B * d->search.beam, K = (size_t)d->pre_beam;
-  M3_REQUIRE(R * 2 * LS_WORDS <= (size_t)INT_MAX, "aed_ngram: %zu rows overflow the int32 offsets of the LM state", R);
-  M3_REQUIRE(R * K * (LC_WORDS + JC_WORDS) <= (size_t)INT_MAX, "aed_ngram: %zu rows x %zu candidates overflow the int32 offsets of the LM scratch", R, K);
-  return 0;
-}
-size_t lm_state_bytes(const m3_aed_joint_desc* d) { return align_up(4 * (size_t)d->search.B * d->search.beam * 2 * LS_WORDS, 256); }
-size_t lm_scratch_bytes(const m3_aed_joint_desc* d) {
-  return align_up(4 * (size_t)d->search.B * d->search.beam * d->pre_beam * (LC_WORDS + JC_WORDS), 256);
-}
-
-// everything an LM entry point checks before it launches: descriptor, search state, (CTC) scorer state and joint scratch, LM blobs
-int check_lm(const m3_aed_joint_desc* d, bool ctc, const void* st, size_t st_bytes, const void* js, size_t js_bytes, const void* scr,
-             size_t scr_bytes, const void* ls, size_t ls_bytes, const void* lscr, size_t lscr_bytes, bool with_scratch, const char* what) {
-  if (int rc = check_lm_desc(d, ctc)) return rc;
-  if (ctc) {
-    if (int rc = check_joint(d, st, st_bytes, js, js_bytes, scr, scr_bytes, with_scratch, what)) return rc;
-  } else {
-    if (int rc = check_search_state(&d->search, st, st_bytes, what)) return rc;
-  }
-  M3_REQUIRE(ls_bytes >= lm_state_bytes(d), "%s: LM state %zu bytes < required %zu", what, ls_bytes, lm_state_bytes(d));
-  M3_REQUIRE(d->search.B == 0 || (ls != nullptr && ((uintptr_t)ls & 15) == 0), "%s: the LM state must be 16-byte aligned device memory", what);
-  if (with_scratch) {
-    M3_REQUIRE(lscr_bytes >= lm_scratch_bytes(d), "%s: LM scratch %zu bytes < required %zu", what, lscr_bytes, lm_scratch_bytes(d));
-    M3_REQUIRE(d->search.B == 0 || (lscr != nullptr && ((uintptr_t)lscr & 15) == 0), "%s: the LM scratch must be 16-byte aligned device memory", what);
-  }
-  return 0;
-}
-
-int check_lm_args(const char* what, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha, double beta, int B) {
-  M3_REQUIRE(B == 0 || lm_on != nullptr, "%s: null lm_on", what);
-  M3_REQUIRE(B == 0 || lm_image != nullptr, "%s: null LM image", what);
-  // a single image or a set: which one only the device copy says, so the bound is the set's
-  M3_REQUIRE(lm_bytes % 4 == 0 && lm_bytes >= LM_HDR_WORDS * 4 && lm_bytes <= kLmSetMaxBytes, "%s: LM image of %zu bytes (a multiple of 4 in [%d, %zu])",
-             what, lm_bytes, LM_HDR_WORDS * 4, kLmSetMaxBytes);
-  M3_REQUIRE(std::isfinite(alpha) && std::isfinite(beta), "%s: alpha or beta is not finite", what);
-  return 0;
-}
-
-// the candidate records of the CTC = false form live behind the LM scratch's (state, sum) pairs
-int32_t* lm_cand(const m3_aed_joint_desc* d, void* lscr) {
-  return (int32_t*)lscr + (size_t)d->search.B * d->search.beam * d->pre_beam * LC_WORDS;
-}
-
 // one thread per row, after m3_aed_search_reset: [sos] is in the image's start state with sum 0.0 and n = 0; buffer 1 is 0
 __global__ __launch_bounds__(256) void aed_lm_reset_kernel(int R, int N, int32_t* ls, int start) {
   const int r = blockIdx.x * 256 + threadIdx.x;
@@ -689,54 +597,6 @@ __global__ __launch_bounds__(64) void aed_lm_result_kernel(const int32_t* __rest
 }
 
 // -------------------------------------------------------------------------------------------------------------- context
-// What a descriptor must hold for the bias entry points: check_lm_desc's (with CTC the joint descriptor's, without it the
-// search's and the pre-beam's), then the int32 offsets of the two context blobs.
-int check_bias_desc(const m3_aed_joint_desc* d, bool ctc) {
-  M3_REQUIRE(d != nullptr, "aed_bias: null descriptor");
-  if (int rc = check_lm_desc(d, ctc)) return rc;
-  const size_t R = (size_t)d->search.B * d->search.beam, K = (size_t)d->pre_beam;
-  M3_REQUIRE(R * 2 * CS_WORDS <= (size_t)INT_MAX, "aed_bias: %zu rows overflow the int32 offsets of the context state", R);
-  M3_REQUIRE(R * K * (CC_WORDS + JC_WORDS) <= (size_t)INT_MAX, "aed_bias: %zu rows x %zu candidates overflow the int32 offsets of the context scratch", R, K);
-  return 0;
-}
-size_t bias_state_bytes(const m3_aed_joint_desc* d) { return align_up(4 * (size_t)d->search.B * d->search.beam * 2 * CS_WORDS, 256); }
-size_t bias_scratch_bytes(const m3_aed_joint_desc* d) {
-  return align_up(4 * (size_t)d->search.B * d->search.beam * d->pre_beam * (CC_WORDS + JC_WORDS), 256);
-}
-
-// the bias record of an entry point: the image (where the call reads it), graph_of, the context state and (with_scratch) scratch
-int check_bias(const m3_aed_joint_desc* d, const m3_aed_bias* b, bool with_image, bool with_scratch, const char* what) {
-  M3_REQUIRE(b != nullptr, "%s: null bias record", what);
-  const int B = d->search.B;
-  if (with_image) {
-    M3_REQUIRE(b->image_bytes % 4 == 0 && b->image_bytes >= CTX_HDR_WORDS * 4 && b->image_bytes <= kCtxMaxBytes && b->image != nullptr,
-               "%s: context image of %zu bytes (a multiple of 4 in [%d, %zu])", what, b->image_bytes, CTX_HDR_WORDS * 4, kCtxMaxBytes);
-    M3_REQUIRE(B == 0 || b->graph_of != nullptr, "%s: null graph_of", what);
-  }
-  M3_REQUIRE(b->state_bytes >= bias_state_bytes(d), "%s: context state %zu bytes < required %zu", what, b->state_bytes, bias_state_bytes(d));
-  M3_REQUIRE(B == 0 || (b->state != nullptr && ((uintptr_t)b->state & 15) == 0), "%s: the context state must be 16-byte aligned device memory", what);
-  if (with_scratch) {
-    M3_REQUIRE(b->scratch_bytes >= bias_scratch_bytes(d), "%s: context scratch %zu bytes < required %zu", what, b->scratch_bytes, bias_scratch_bytes(d));
-    M3_REQUIRE(B == 0 || (b->scratch != nullptr && ((uintptr_t)b->scratch & 15) == 0), "%s: the context scratch must be 16-byte aligned device memory", what);
-  }
-  return 0;
-}
-
-// the search's own blobs of a bias score / prune call: search state, (CTC) scorer state and joint scratch, (LM) LM state and scratch
-int check_bias_blobs(const m3_aed_joint_desc* d, bool ctc, bool lm, const void* st, size_t st_bytes, const void* js, size_t js_bytes,
-                     const void* scr, size_t scr_bytes, const void* ls, size_t ls_bytes, const void* lscr, size_t lscr_bytes, const char* what) {
-  if (int rc = check_bias_desc(d, ctc)) return rc;
-  if (lm) return check_lm(d, ctc, st, st_bytes, js, js_bytes, scr, scr_bytes, ls, ls_bytes, lscr, lscr_bytes, true, what);
-  M3_REQUIRE(ls == nullptr && lscr == nullptr, "%s: an LM blob without the other (LM state and LM scratch are NULL exactly when there is no LM)", what);
-  if (ctc) return check_joint(d, st, st_bytes, js, js_bytes, scr, scr_bytes, true, what);
-  return check_search_state(&d->search, st, st_bytes, what);
-}
-
-// the candidate records of the <false, false, true> form live behind the context scratch's (state, bonus) pairs
-int32_t* bias_cand(const m3_aed_joint_desc* d, void* cscr) {
-  return (int32_t*)cscr + (size_t)d->search.B * d->search.beam * d->pre_beam * CC_WORDS;
-}
-
 // one thread per row, after m3_aed_search_reset: [sos] is in state 0 with bonus 0.0; buffer 1 is 0
 __global__ __launch_bounds__(256) void aed_bias_reset_kernel(int R, int N, int32_t* cs) {
   const int r = blockIdx.x * 256 + threadIdx.x;
@@ -759,6 +619,271 @@ __global__ __launch_bounds__(64) void aed_bias_result_kernel(const int32_t* __re
   }
 }
 
+// ------------------------------------------------------------------------------------------------------- the host half
+//   Every entry point fills a FusedCall, states the pre-conditions that are its own, and hands it to check_call and,
+// for the two kernel templates, to launch_fused.  Nothing below knows which family it was called through beyond FusedCall::family.
+size_t rows_of(const m3_aed_joint_desc* d) { return (size_t)d->search.B * d->search.beam; }
+size_t joint_state_bytes(const m3_aed_joint_desc* d) { return align_up(4 * rows_of(d) * 2 * (JS_HDR + 2 * (size_t)d->max_frames), 256); }
+size_t joint_scratch_bytes(const m3_aed_joint_desc* d) {
+  return align_up(4 * rows_of(d) * d->pre_beam * (JC_WORDS + 2 * (size_t)d->max_frames), 256);
+}
+size_t lm_state_bytes(const m3_aed_joint_desc* d) { return align_up(4 * rows_of(d) * 2 * LS_WORDS, 256); }
+size_t lm_scratch_bytes(const m3_aed_joint_desc* d) { return align_up(4 * rows_of(d) * d->pre_beam * (LC_WORDS + JC_WORDS), 256); }
+size_t bias_state_bytes(const m3_aed_joint_desc* d) { return align_up(4 * rows_of(d) * 2 * CS_WORDS, 256); }
+size_t bias_scratch_bytes(const m3_aed_joint_desc* d) { return align_up(4 * rows_of(d) * d->pre_beam * (CC_WORDS + JC_WORDS), 256); }
+
+enum Family { JOINT = 0, NGRAM = 1, BIAS = 2 };                   // the entry point's family: each asks what the one before it asks
+const char* const kFamily[] = {"aed_joint", "aed_ngram", "aed_bias"};
+
+// What a descriptor must hold.  The search's own checks; V and the pre-beam; with CTC the frames and the int32 offsets of the
+// scorer state and the joint scratch (without it there is no scorer state and max_frames is not looked at); from the LM family on
+// the offsets of the two LM blobs, in the bias family those of the two context blobs.  A rule speaks as the family that brought it.
+int check_desc(const m3_aed_joint_desc* d, Family family, bool ctc) {
+  M3_REQUIRE(d != nullptr, "%s: null descriptor", kFamily[family]);
+  if (int rc = check_search_desc(&d->search)) return rc;
+  const m3_aed_search_desc* s = &d->search;
+  const char* who = kFamily[ctc ? JOINT : NGRAM];
+  M3_REQUIRE(s->V >= 2, "%s: V = %d, %s and eos need two different ids", who, s->V, ctc ? "blank" : "a token");
+  M3_REQUIRE(d->pre_beam >= s->beam && d->pre_beam <= AS_MAX_BEAM && d->pre_beam <= s->V,
+             "%s: pre_beam = %d, need beam = %d <= pre_beam <= min(%d, V = %d)", who, d->pre_beam, s->beam, AS_MAX_BEAM, s->V);
+  const size_t R = rows_of(d), K = (size_t)d->pre_beam;
+  if (ctc) {
+    M3_REQUIRE(d->max_frames >= 1 && d->max_frames <= (1 << 20), "aed_joint: max_frames = %d outside [1, 2^20]", d->max_frames);
+    const size_t F = (size_t)d->max_frames;
+    M3_REQUIRE(R * 2 * (JS_HDR + 2 * F) <= (size_t)INT_MAX, "aed_joint: %zu rows of %zu frames overflow the int32 offsets of the scorer state", R, F);
+    M3_REQUIRE(R * K * (JC_WORDS + 2 * F) <= (size_t)INT_MAX,
+               "aed_joint: %zu rows x %zu candidates x %zu frames overflow the int32 offsets of the candidate scratch", R, K, F);
+  }
+  if (family >= NGRAM) {
+    M3_REQUIRE(R * 2 * LS_WORDS <= (size_t)INT_MAX, "aed_ngram: %zu rows overflow the int32 offsets of the LM state", R);
+    M3_REQUIRE(R * K * (LC_WORDS + JC_WORDS) <= (size_t)INT_MAX, "aed_ngram: %zu rows x %zu candidates overflow the int32 offsets of the LM scratch", R, K);
+  }
+  if (family == BIAS) {
+    M3_REQUIRE(R * 2 * CS_WORDS <= (size_t)INT_MAX, "aed_bias: %zu rows overflow the int32 offsets of the context state", R);
+    M3_REQUIRE(R * K * (CC_WORDS + JC_WORDS) <= (size_t)INT_MAX, "aed_bias: %zu rows x %zu candidates overflow the int32 offsets of the context scratch", R, K);
+  }
+  return 0;
+}
+
+// a blob of a call: at least `need` bytes, non-null unless the batch is empty, 16-byte aligned
+int check_blob(const char* what, const char* noun, const void* p, size_t bytes, size_t need, int B) {
+  M3_REQUIRE(bytes >= need, "%s: %s %zu bytes < required %zu", what, noun, bytes, need);
+  M3_REQUIRE(B == 0 || (p != nullptr && ((uintptr_t)p & 15) == 0), "%s: the %s must be 16-byte aligned device memory", what, noun);
+  return 0;
+}
+
+// the bias record of an entry point: the image (where the call reads it), graph_of, the context state and (with_scratch) scratch
+int check_bias(const m3_aed_joint_desc* d, const m3_aed_bias* b, bool with_image, bool with_scratch, const char* what) {
+  M3_REQUIRE(b != nullptr, "%s: null bias record", what);
+  const int B = d->search.B;
+  if (with_image) {
+    M3_REQUIRE(b->image_bytes % 4 == 0 && b->image_bytes >= CTX_HDR_WORDS * 4 && b->image_bytes <= kCtxMaxBytes && b->image != nullptr,
+               "%s: context image of %zu bytes (a multiple of 4 in [%d, %zu])", what, b->image_bytes, CTX_HDR_WORDS * 4, kCtxMaxBytes);
+    M3_REQUIRE(B == 0 || b->graph_of != nullptr, "%s: null graph_of", what);
+  }
+  if (int rc = check_blob(what, "context state", b->state, b->state_bytes, bias_state_bytes(d), B)) return rc;
+  return with_scratch ? check_blob(what, "context scratch", b->scratch, b->scratch_bytes, bias_scratch_bytes(d), B) : 0;
+}
+
+// Everything a score / prune / result / reset entry point receives.  ctc, lm and ctx say which parts this call has; the members of
+// a part the call does not have, and the inputs an entry point does not take (prune has no image and no weights), stay zero.
+// The blobs are const here whoever writes them: the launch casts, as the entry points did.
+struct FusedCall {
+  const char* what;                              // the entry point's name, for the messages
+  Family family;
+  bool ctc, lm, ctx;
+  const m3_aed_joint_desc* d;
+  const void* st;                                // search state
+  size_t st_bytes;
+  const void *js, *scr;                          // CTC: scorer state, joint scratch; the log-probabilities and ctc_weight
+  size_t js_bytes, scr_bytes;
+  const float* x;
+  int ldx, x_rows;
+  float lam;
+  const void *ls, *lscr;                         // LM: state, scratch; the image, lm_on and the weights
+  size_t ls_bytes, lscr_bytes;
+  const void* image;
+  size_t image_bytes;
+  const int32_t* lm_on;
+  double alpha, beta;
+  int use_eos;
+  const m3_aed_bias* bias;                       // context: the caller's record
+  const float* logits;
+  int ldl;
+  int32_t* done;
+  hipStream_t stream;
+  bool empty() const { return d != nullptr && d->search.B == 0; }
+};
+// what every entry point has; the rest zero
+FusedCall fused_call(const char* what, Family family, bool ctc, bool lm, bool ctx, const m3_aed_joint_desc* d, const void* st, size_t st_bytes,
+                     m3_stream stream) {
+  FusedCall c{};
+  c.what = what, c.family = family, c.ctc = ctc, c.lm = lm, c.ctx = ctx, c.d = d, c.st = st, c.st_bytes = st_bytes, c.stream = (hipStream_t)stream;
+  return c;
+}
+
+// Everything an entry point checks about its descriptor and its blobs, in this order: the descriptor; no LM blob without an LM;
+// the search state; with CTC the scorer state; with an LM the LM state; with a context the caller's record.  with_scratch: the
+// scratch blobs are part of this call (score and prune); with_image: so is the context image (score).
+int check_call(const FusedCall& c, bool with_scratch, bool with_image) {
+  const m3_aed_joint_desc* d = c.d;
+  if (int rc = check_desc(d, c.family, c.ctc)) return rc;
+  const int B = d->search.B;
+  if (!c.lm) M3_REQUIRE(c.ls == nullptr && c.lscr == nullptr, "%s: an LM blob without the other (LM state and LM scratch are NULL exactly when there is no LM)", c.what);
+  if (int rc = check_search_state(&d->search, c.st, c.st_bytes, c.what)) return rc;
+  if (c.ctc) {
+    if (int rc = check_blob(c.what, "scorer state", c.js, c.js_bytes, joint_state_bytes(d), B)) return rc;
+    if (with_scratch)
+      if (int rc = check_blob(c.what, "scratch", c.scr, c.scr_bytes, joint_scratch_bytes(d), B)) return rc;
+  }
+  if (c.lm) {
+    if (int rc = check_blob(c.what, "LM state", c.ls, c.ls_bytes, lm_state_bytes(d), B)) return rc;
+    if (with_scratch)
+      if (int rc = check_blob(c.what, "LM scratch", c.lscr, c.lscr_bytes, lm_scratch_bytes(d), B)) return rc;
+  }
+  return c.ctx ? check_bias(d, c.bias, with_image, with_scratch, c.what) : 0;
+}
+
+int check_ctc(const FusedCall& c) {
+  M3_REQUIRE(c.ldx >= c.d->search.V, "%s: ldc = %d < V = %d", c.what, c.ldx, c.d->search.V);
+  M3_REQUIRE(c.x_rows >= 0, "%s: ctc_rows = %d", c.what, c.x_rows);
+  M3_REQUIRE(c.d->search.B == 0 || c.x != nullptr, "%s: null CTC log-probabilities", c.what);
+  return 0;
+}
+
+int check_lm_args(const FusedCall& c) {
+  const int B = c.d->search.B;
+  M3_REQUIRE(B == 0 || c.lm_on != nullptr, "%s: null lm_on", c.what);
+  M3_REQUIRE(B == 0 || c.image != nullptr, "%s: null LM image", c.what);
+  // a single image or a set: which one only the device copy says, so the bound is the set's
+  M3_REQUIRE(c.image_bytes % 4 == 0 && c.image_bytes >= LM_HDR_WORDS * 4 && c.image_bytes <= kLmSetMaxBytes,
+             "%s: LM image of %zu bytes (a multiple of 4 in [%d, %zu])", c.what, c.image_bytes, LM_HDR_WORDS * 4, kLmSetMaxBytes);
+  return 0;
+}
+
+// ---- the launch table: THE launch of each kernel template, and the form's index  ctc | lm << 1 | ctx << 2  into eight pointers.
+// What a form passes follows from its flags alone.  Lx: NoLm or LmFuse, inside Biased<> with a context.  The candidate records:
+// the joint scratch with CTC, else behind the LM scratch's (state, sum) pairs, else behind the context scratch's (state, bonus)
+// pairs.  Without CTC there is no scorer state and no frame: F, js, scr, x, ldx, x_rows and lam are zero.  score: the launch reads
+// the context image and graph_of (prune gets the state and scratch pointers alone; its LM inputs are zero in the record already).
+template <bool LM, bool CTX>
+auto make_lx(const FusedCall& c, bool score) {
+  std::conditional_t<LM, LmFuse, NoLm> l{};
+  if constexpr (LM)
+    l = LmFuse{(const int32_t*)c.image, (long long)(c.image_bytes / 4), c.lm_on, (int32_t*)c.ls, (int32_t*)c.lscr, c.alpha, c.beta, c.use_eos};
+  if constexpr (CTX) {
+    const m3_aed_bias* b = c.bias;
+    const CtxFuse cx{score ? (const int32_t*)b->image : nullptr, score ? (long long)(b->image_bytes / 4) : 0, score ? b->graph_of : nullptr,
+                     (int32_t*)b->state, (int32_t*)b->scratch};
+    return Biased<decltype(l)>{l, cx};
+  } else {
+    return l;
+  }
+}
+template <bool CTC, bool LM>
+int32_t* cand_of(const FusedCall& c) {
+  const size_t RK = rows_of(c.d) * c.d->pre_beam;
+  if (CTC) return (int32_t*)c.scr;
+  return LM ? (int32_t*)c.lscr + RK * LC_WORDS : (int32_t*)c.bias->scratch + RK * CC_WORDS;
+}
+
+template <bool CTC, bool LM, bool CTX>
+void launch_score(const FusedCall& c) {
+  const m3_aed_search_desc* s = &c.d->search;
+  const SearchLayout l = search_layout(s);
+  auto lx = make_lx<LM, CTX>(c, true);
+  hipLaunchKernelGGL((aed_joint_score_kernel<CTC, LM, CTX, decltype(lx)>), dim3((unsigned)(s->B * s->beam)), dim3(64), 0, c.stream,
+                     (const int32_t*)c.st, s->B, s->beam, l.P, l.rec_words, s->V, c.d->pre_beam, CTC ? c.d->max_frames : 0,
+                     CTC ? (const float*)c.js : nullptr, cand_of<CTC, LM>(c), CTC ? (float*)c.scr : nullptr, c.logits, c.ldl,
+                     CTC ? c.x : nullptr, CTC ? c.ldx : 0, CTC ? c.x_rows : 0, CTC ? c.lam : 0.f, lx);
+}
+template <bool CTC, bool LM, bool CTX>
+void launch_prune(const FusedCall& c) {
+  const m3_aed_search_desc* s = &c.d->search;
+  const SearchLayout l = search_layout(s);
+  auto lx = make_lx<LM, CTX>(c, false);
+  hipLaunchKernelGGL((aed_joint_prune_kernel<CTC, LM, CTX, decltype(lx)>), dim3((unsigned)s->B), dim3(256), 0, c.stream, (int32_t*)c.st, s->B,
+                     s->beam, l.P, l.rec_words, s->V, c.d->pre_beam, CTC ? c.d->max_frames : 0, CTC ? (float*)c.js : nullptr,
+                     (const int32_t*)cand_of<CTC, LM>(c), CTC ? (const float*)c.scr : nullptr, c.done, lx);
+}
+
+// slot 0, no CTC, no LM and no context, is empty: that step is m3_aed_search_prune in aed_search.hip, and no entry point here
+// can ask for it.  Reaching it is a refusal, not a launch.
+using FusedLaunch = void (*)(const FusedCall&);
+const FusedLaunch kScore[8] = {nullptr, launch_score<true, false, false>, launch_score<false, true, false>, launch_score<true, true, false>,
+                               launch_score<false, false, true>, launch_score<true, false, true>, launch_score<false, true, true>, launch_score<true, true, true>};
+const FusedLaunch kPrune[8] = {nullptr, launch_prune<true, false, false>, launch_prune<false, true, false>, launch_prune<true, true, false>,
+                               launch_prune<false, false, true>, launch_prune<true, false, true>, launch_prune<false, true, true>, launch_prune<true, true, true>};
+
+int launch_fused(const FusedLaunch (&table)[8], const FusedCall& c) {
+  if (c.d->search.B == 0) return 0;
+  const FusedLaunch launch = table[(int)c.ctc | (int)c.lm << 1 | (int)c.ctx << 2];
+  M3_REQUIRE(launch != nullptr, "%s: a step without CTC, LM and context is m3_aed_search_prune", c.what);
+  launch(c);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
+// score: the blobs, then the inputs in the order CTC, logits, LM.  The weights are looked at with an LM or a context; a call with
+// neither is the joint step alone, whose ctc_weight cannot be 0.
+int fused_score(const FusedCall& c) {
+  if (int rc = check_call(c, true, true)) return rc;
+  const m3_aed_search_desc* s = &c.d->search;
+  if (c.ctc)
+    if (int rc = check_ctc(c)) return rc;
+  M3_REQUIRE(c.ldl >= s->V, "%s: ldl = %d < V = %d", c.what, c.ldl, s->V);
+  if (c.lm)
+    if (int rc = check_lm_args(c)) return rc;
+  if (c.lm || c.ctx)
+    M3_REQUIRE(std::isfinite(c.alpha) && std::isfinite(c.beta), "%s: alpha or beta is not finite", c.what);
+  else
+    M3_REQUIRE(c.lam > 0.f && c.lam <= 1.f, "%s: ctc_weight = %g outside (0, 1] (0 is m3_aed_search_prune)", c.what, (double)c.lam);
+  M3_REQUIRE(!c.lm || c.use_eos == 0 || c.use_eos == 1, "%s: use_eos = %d", c.what, c.use_eos);
+  M3_REQUIRE(s->B == 0 || c.logits != nullptr, "%s: null pointer", c.what);
+  return launch_fused(kScore, c);
+}
+
+int fused_prune(const FusedCall& c) {
+  if (int rc = check_call(c, true, false)) return rc;
+  return launch_fused(kPrune, c);
+}
+
+// Both m3_aed_ngram_reset entries.  set: the image may be an LM set (its bound, lm_on picks each utterance's member).  The header is
+// read back once per search, a set's 8 words or a single image's 20: what is refused here the kernels would run as "LM off".
+int lm_reset(const char* what, bool set, const m3_aed_joint_desc* d, void* ls, size_t ls_bytes, const void* image, size_t bytes,
+             const int32_t* lm_on, m3_stream stream) {
+  const size_t max_bytes = set ? kLmSetMaxBytes : kLmMaxBytes;
+  if (int rc = check_desc(d, NGRAM, false)) return rc;
+  if (int rc = check_blob(what, "LM state", ls, ls_bytes, lm_state_bytes(d), d->search.B)) return rc;
+  M3_REQUIRE(bytes % 4 == 0 && bytes >= LM_HDR_WORDS * 4 && bytes <= max_bytes && image != nullptr, "%s: LM image of %zu bytes (a multiple of 4 in [%d, %zu])",
+             what, bytes, LM_HDR_WORDS * 4, max_bytes);
+  M3_REQUIRE(!set || d->search.B == 0 || lm_on != nullptr, "%s: null lm_on", what);
+  int32_t head[LM_HDR_WORDS];
+  M3_CHECK_HIP(hipMemcpy(head, image, sizeof(head), hipMemcpyDeviceToHost));
+  const long long words = (long long)(bytes / 4);
+  LmView view;
+  int image_V = 0;
+  if (set && lm_is_set(head, words)) {
+    M3_REQUIRE(head[LMS_VERSION] == kLmSetVersion && head[LMS_G] >= 1 && head[LMS_G] <= kLmSetMaxMembers && head[LMS_WORDS] == words,
+               "%s: the LM set's header (version %d, G = %d, %d words) does not describe a set of %zu bytes", what, head[LMS_VERSION], head[LMS_G],
+               head[LMS_WORDS], bytes);
+    image_V = head[LMS_V];
+  } else {
+    M3_REQUIRE(lm_view(head, words, &view), "%s: the LM image's header does not describe an image of %zu bytes", what, bytes);
+    image_V = view.V;
+  }
+  M3_REQUIRE(image_V == d->search.V, "%s: the LM image was built for V = %d, the search has V = %d", what, image_V, d->search.V);
+  if (d->search.B == 0) return 0;
+  const int R = d->search.B * d->search.beam;
+  if (set)
+    hipLaunchKernelGGL(aed_lm_reset_set_kernel, dim3((unsigned)cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream, R, d->search.beam, d->search.V,
+                       (int32_t*)ls, (const int32_t*)image, words, lm_on);
+  else
+    hipLaunchKernelGGL(aed_lm_reset_kernel, dim3((unsigned)cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream, R, d->search.beam, (int32_t*)ls, view.start);
+  M3_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace
 }  // namespace m3
 
@@ -766,22 +891,23 @@ using namespace m3;
 
 extern "C" {
 
-size_t m3_aed_joint_state_size(const m3_aed_joint_desc* desc) {
-  if (check_joint_desc(desc)) return 0;
-  return joint_state_bytes(desc);
-}
+size_t m3_aed_joint_state_size(const m3_aed_joint_desc* desc) { return check_desc(desc, JOINT, true) ? 0 : joint_state_bytes(desc); }
+size_t m3_aed_joint_scratch_size(const m3_aed_joint_desc* desc) { return check_desc(desc, JOINT, true) ? 0 : joint_scratch_bytes(desc); }
+size_t m3_aed_ngram_state_size(const m3_aed_joint_desc* desc) { return check_desc(desc, NGRAM, false) ? 0 : lm_state_bytes(desc); }
+size_t m3_aed_ngram_scratch_size(const m3_aed_joint_desc* desc) { return check_desc(desc, NGRAM, false) ? 0 : lm_scratch_bytes(desc); }
+size_t m3_aed_bias_state_size(const m3_aed_joint_desc* desc) { return check_desc(desc, BIAS, false) ? 0 : bias_state_bytes(desc); }
+size_t m3_aed_bias_scratch_size(const m3_aed_joint_desc* desc) { return check_desc(desc, BIAS, false) ? 0 : bias_scratch_bytes(desc); }
 
-size_t m3_aed_joint_scratch_size(const m3_aed_joint_desc* desc) {
-  if (check_joint_desc(desc)) return 0;
-  return joint_scratch_bytes(desc);
-}
-
+// ---- m3_aed_joint_*: always the CTC part, nothing else
 int m3_aed_joint_reset(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, void* joint_state,
                        size_t joint_state_bytes, const float* ctc, int ldc, int ctc_rows, m3_stream stream) {
-  if (int rc = check_joint(desc, search_state, search_state_bytes, joint_state, joint_state_bytes, nullptr, 0, false, "aed_joint_reset")) return rc;
-  if (int rc = check_ctc(desc, ctc, ldc, ctc_rows, "aed_joint_reset")) return rc;
+  FusedCall c = fused_call("aed_joint_reset", JOINT, true, false, false, desc, search_state, search_state_bytes, stream);
+  c.js = joint_state, c.js_bytes = joint_state_bytes;
+  c.x = ctc, c.ldx = ldc, c.x_rows = ctc_rows;
+  if (int rc = check_call(c, false, false)) return rc;
+  if (int rc = check_ctc(c)) return rc;
   if (desc->search.B == 0) return 0;
-  hipLaunchKernelGGL(aed_joint_reset_kernel, dim3((unsigned)desc->search.B), dim3(64), 0, (hipStream_t)stream, (const int32_t*)search_state,
+  hipLaunchKernelGGL(aed_joint_reset_kernel, dim3((unsigned)desc->search.B), dim3(64), 0, c.stream, (const int32_t*)search_state,
                      desc->search.beam, desc->max_frames, (float*)joint_state, ctc, ldc, ctc_rows);
   M3_LAUNCH_CHECK();
   return 0;
@@ -790,106 +916,43 @@ int m3_aed_joint_reset(const m3_aed_joint_desc* desc, const void* search_state, 
 int m3_aed_joint_score(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, const void* joint_state,
                        size_t joint_state_bytes, void* scratch, size_t scratch_bytes, const float* logits, int ldl, const float* ctc,
                        int ldc, int ctc_rows, float ctc_weight, m3_stream stream) {
-  if (int rc = check_joint(desc, search_state, search_state_bytes, joint_state, joint_state_bytes, scratch, scratch_bytes, true, "aed_joint_score")) return rc;
-  if (int rc = check_ctc(desc, ctc, ldc, ctc_rows, "aed_joint_score")) return rc;
-  const m3_aed_search_desc* s = &desc->search;
-  M3_REQUIRE(ldl >= s->V, "aed_joint_score: ldl = %d < V = %d", ldl, s->V);
-  M3_REQUIRE(ctc_weight > 0.f && ctc_weight <= 1.f, "aed_joint_score: ctc_weight = %g outside (0, 1] (0 is m3_aed_search_prune)", (double)ctc_weight);
-  if (s->B == 0) return 0;
-  M3_REQUIRE(logits != nullptr, "aed_joint_score: null pointer");
-  const SearchLayout l = search_layout(s);
-  hipLaunchKernelGGL((aed_joint_score_kernel<true, false, false, NoLm>), dim3((unsigned)(s->B * s->beam)), dim3(64), 0, (hipStream_t)stream, (const int32_t*)search_state,
-                     s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames, (const float*)joint_state, (int32_t*)scratch,
-                     (float*)scratch, logits, ldl, ctc, ldc, ctc_rows, ctc_weight, NoLm{});
-  M3_LAUNCH_CHECK();
-  return 0;
+  FusedCall c = fused_call("aed_joint_score", JOINT, true, false, false, desc, search_state, search_state_bytes, stream);
+  c.js = joint_state, c.js_bytes = joint_state_bytes, c.scr = scratch, c.scr_bytes = scratch_bytes;
+  c.x = ctc, c.ldx = ldc, c.x_rows = ctc_rows, c.lam = ctc_weight;
+  c.logits = logits, c.ldl = ldl;
+  return fused_score(c);
 }
 
 int m3_aed_joint_prune(const m3_aed_joint_desc* desc, void* search_state, size_t search_state_bytes, void* joint_state,
                        size_t joint_state_bytes, const void* scratch, size_t scratch_bytes, int32_t* done, m3_stream stream) {
-  if (int rc = check_joint(desc, search_state, search_state_bytes, joint_state, joint_state_bytes, scratch, scratch_bytes, true, "aed_joint_prune")) return rc;
-  const m3_aed_search_desc* s = &desc->search;
-  if (s->B == 0) return 0;
-  const SearchLayout l = search_layout(s);
-  hipLaunchKernelGGL((aed_joint_prune_kernel<true, false, false, NoLm>), dim3((unsigned)s->B), dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state, s->B, s->beam,
-                     l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames, (float*)joint_state, (const int32_t*)scratch,
-                     (const float*)scratch, done, NoLm{});
-  M3_LAUNCH_CHECK();
-  return 0;
+  FusedCall c = fused_call("aed_joint_prune", JOINT, true, false, false, desc, search_state, search_state_bytes, stream);
+  c.js = joint_state, c.js_bytes = joint_state_bytes, c.scr = scratch, c.scr_bytes = scratch_bytes;
+  c.done = done;
+  return fused_prune(c);
 }
 
 int m3_aed_joint_result(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, const void* joint_state,
                         size_t joint_state_bytes, float* att, float* ctc, m3_stream stream) {
-  if (int rc = check_joint(desc, search_state, search_state_bytes, joint_state, joint_state_bytes, nullptr, 0, false, "aed_joint_result")) return rc;
+  FusedCall c = fused_call("aed_joint_result", JOINT, true, false, false, desc, search_state, search_state_bytes, stream);
+  c.js = joint_state, c.js_bytes = joint_state_bytes;
+  if (int rc = check_call(c, false, false)) return rc;
   if (desc->search.B == 0) return 0;
   M3_REQUIRE(att && ctc, "aed_joint_result: null pointer");
-  hipLaunchKernelGGL(aed_joint_result_kernel, dim3((unsigned)desc->search.B), dim3(64), 0, (hipStream_t)stream, (const int32_t*)search_state,
+  hipLaunchKernelGGL(aed_joint_result_kernel, dim3((unsigned)desc->search.B), dim3(64), 0, c.stream, (const int32_t*)search_state,
                      desc->search.beam, search_layout(&desc->search).P, desc->max_frames, (const float*)joint_state, att, ctc);
   M3_LAUNCH_CHECK();
   return 0;
 }
 
-size_t m3_aed_ngram_state_size(const m3_aed_joint_desc* desc) {
-  if (check_lm_desc(desc, false)) return 0;
-  return lm_state_bytes(desc);
-}
-
-size_t m3_aed_ngram_scratch_size(const m3_aed_joint_desc* desc) {
-  if (check_lm_desc(desc, false)) return 0;
-  return lm_scratch_bytes(desc);
-}
-
+// ---- m3_aed_ngram_*: always the LM part; the CTC part when ctc_weight > 0 (score) or a scorer state is given (prune)
 int m3_aed_ngram_reset(const m3_aed_joint_desc* desc, void* lm_state, size_t lm_state_bytes, const void* lm_image, size_t lm_bytes,
                     m3_stream stream) {
-  if (int rc = check_lm_desc(desc, false)) return rc;
-  M3_REQUIRE(lm_state_bytes >= m3::lm_state_bytes(desc), "aed_ngram_reset: LM state %zu bytes < required %zu", lm_state_bytes, m3::lm_state_bytes(desc));
-  M3_REQUIRE(desc->search.B == 0 || (lm_state != nullptr && ((uintptr_t)lm_state & 15) == 0), "aed_ngram_reset: the LM state must be 16-byte aligned device memory");
-  M3_REQUIRE(lm_bytes % 4 == 0 && lm_bytes >= LM_HDR_WORDS * 4 && lm_bytes <= kLmMaxBytes && lm_image != nullptr,
-             "aed_ngram_reset: LM image of %zu bytes (a multiple of 4 in [%d, %zu])", lm_bytes, LM_HDR_WORDS * 4, kLmMaxBytes);
-  // the image's header, read back once per search: what lm_view refuses here the kernels would run as "LM off"
-  int32_t head[LM_HDR_WORDS];
-  M3_CHECK_HIP(hipMemcpy(head, lm_image, sizeof(head), hipMemcpyDeviceToHost));
-  LmView view;
-  M3_REQUIRE(lm_view(head, (long long)(lm_bytes / 4), &view), "aed_ngram_reset: the LM image's header does not describe an image of %zu bytes", lm_bytes);
-  M3_REQUIRE(view.V == desc->search.V, "aed_ngram_reset: the LM image was built for V = %d, the search has V = %d", view.V, desc->search.V);
-  if (desc->search.B == 0) return 0;
-  const int R = desc->search.B * desc->search.beam;
-  hipLaunchKernelGGL(aed_lm_reset_kernel, dim3((unsigned)cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream, R, desc->search.beam, (int32_t*)lm_state,
-                     view.start);
-  M3_LAUNCH_CHECK();
-  return 0;
+  return lm_reset("aed_ngram_reset", false, desc, lm_state, lm_state_bytes, lm_image, lm_bytes, nullptr, stream);
 }
 
 int m3_aed_ngram_reset_set(const m3_aed_joint_desc* desc, void* lm_state, size_t lm_state_bytes, const void* lm_image, size_t lm_bytes,
                            const int32_t* lm_on, m3_stream stream) {
-  if (int rc = check_lm_desc(desc, false)) return rc;
-  M3_REQUIRE(lm_state_bytes >= m3::lm_state_bytes(desc), "aed_ngram_reset_set: LM state %zu bytes < required %zu", lm_state_bytes, m3::lm_state_bytes(desc));
-  M3_REQUIRE(desc->search.B == 0 || (lm_state != nullptr && ((uintptr_t)lm_state & 15) == 0), "aed_ngram_reset_set: the LM state must be 16-byte aligned device memory");
-  M3_REQUIRE(lm_bytes % 4 == 0 && lm_bytes >= LM_HDR_WORDS * 4 && lm_bytes <= kLmSetMaxBytes && lm_image != nullptr,
-             "aed_ngram_reset_set: LM image of %zu bytes (a multiple of 4 in [%d, %zu])", lm_bytes, LM_HDR_WORDS * 4, kLmSetMaxBytes);
-  M3_REQUIRE(desc->search.B == 0 || lm_on != nullptr, "aed_ngram_reset_set: null lm_on");
-  // the header, read back once per search: a set's 8 words or a single image's 20; what is refused here the kernels would run as "LM off"
-  int32_t head[LM_HDR_WORDS];
-  M3_CHECK_HIP(hipMemcpy(head, lm_image, sizeof(head), hipMemcpyDeviceToHost));
-  const long long words = (long long)(lm_bytes / 4);
-  int image_V = 0;
-  if (lm_is_set(head, words)) {
-    M3_REQUIRE(head[LMS_VERSION] == kLmSetVersion && head[LMS_G] >= 1 && head[LMS_G] <= kLmSetMaxMembers && head[LMS_WORDS] == words,
-               "aed_ngram_reset_set: the LM set's header (version %d, G = %d, %d words) does not describe a set of %zu bytes", head[LMS_VERSION],
-               head[LMS_G], head[LMS_WORDS], lm_bytes);
-    image_V = head[LMS_V];
-  } else {
-    LmView view;
-    M3_REQUIRE(lm_view(head, words, &view), "aed_ngram_reset_set: the LM image's header does not describe an image of %zu bytes", lm_bytes);
-    image_V = view.V;
-  }
-  M3_REQUIRE(image_V == desc->search.V, "aed_ngram_reset_set: the LM image was built for V = %d, the search has V = %d", image_V, desc->search.V);
-  if (desc->search.B == 0) return 0;
-  const int R = desc->search.B * desc->search.beam;
-  hipLaunchKernelGGL(aed_lm_reset_set_kernel, dim3((unsigned)cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream, R, desc->search.beam, desc->search.V,
-                     (int32_t*)lm_state, (const int32_t*)lm_image, words, lm_on);
-  M3_LAUNCH_CHECK();
-  return 0;
+  return lm_reset("aed_ngram_reset_set", true, desc, lm_state, lm_state_bytes, lm_image, lm_bytes, lm_on, stream);
 }
 
 int m3_aed_ngram_score(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, const void* joint_state,
@@ -898,79 +961,44 @@ int m3_aed_ngram_score(const m3_aed_joint_desc* desc, const void* search_state, 
                     float ctc_weight, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha, double beta, int use_eos,
                     m3_stream stream) {
   M3_REQUIRE(ctc_weight >= 0.f && ctc_weight <= 1.f, "aed_ngram_score: ctc_weight = %g outside [0, 1]", (double)ctc_weight);
-  const bool with_ctc = ctc_weight > 0.f;
-  M3_REQUIRE((ctc != nullptr) == with_ctc || (desc && desc->search.B == 0), "aed_ngram_score: the CTC log-probabilities are given exactly when ctc_weight > 0 (ctc_weight = %g)",
+  FusedCall c = fused_call("aed_ngram_score", NGRAM, ctc_weight > 0.f, true, false, desc, search_state, search_state_bytes, stream);
+  M3_REQUIRE((ctc != nullptr) == c.ctc || c.empty(), "aed_ngram_score: the CTC log-probabilities are given exactly when ctc_weight > 0 (ctc_weight = %g)",
              (double)ctc_weight);
-  if (int rc = check_lm(desc, with_ctc, search_state, search_state_bytes, joint_state, joint_state_bytes, scratch, scratch_bytes, lm_state,
-                        lm_state_bytes, lm_scratch, lm_scratch_bytes, true, "aed_ngram_score")) return rc;
-  if (with_ctc)
-    if (int rc = check_ctc(desc, ctc, ldc, ctc_rows, "aed_ngram_score")) return rc;
-  const m3_aed_search_desc* s = &desc->search;
-  M3_REQUIRE(ldl >= s->V, "aed_ngram_score: ldl = %d < V = %d", ldl, s->V);
-  if (int rc = check_lm_args("aed_ngram_score", lm_image, lm_bytes, lm_on, alpha, beta, s->B)) return rc;
-  M3_REQUIRE(use_eos == 0 || use_eos == 1, "aed_ngram_score: use_eos = %d", use_eos);
-  if (s->B == 0) return 0;
-  M3_REQUIRE(logits != nullptr, "aed_ngram_score: null pointer");
-  const SearchLayout l = search_layout(s);
-  const LmFuse lx{(const int32_t*)lm_image, (long long)(lm_bytes / 4), lm_on, (int32_t*)const_cast<void*>(lm_state), (int32_t*)lm_scratch, alpha, beta, use_eos};
-  if (with_ctc)
-    hipLaunchKernelGGL((aed_joint_score_kernel<true, true, false, LmFuse>), dim3((unsigned)(s->B * s->beam)), dim3(64), 0, (hipStream_t)stream,
-                       (const int32_t*)search_state, s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames,
-                       (const float*)joint_state, (int32_t*)scratch, (float*)scratch, logits, ldl, ctc, ldc, ctc_rows, ctc_weight, lx);
-  else
-    hipLaunchKernelGGL((aed_joint_score_kernel<false, true, false, LmFuse>), dim3((unsigned)(s->B * s->beam)), dim3(64), 0, (hipStream_t)stream,
-                       (const int32_t*)search_state, s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, 0, (const float*)nullptr,
-                       lm_cand(desc, lm_scratch), (float*)nullptr, logits, ldl, (const float*)nullptr, 0, 0, 0.f, lx);
-  M3_LAUNCH_CHECK();
-  return 0;
+  c.js = joint_state, c.js_bytes = joint_state_bytes, c.scr = scratch, c.scr_bytes = scratch_bytes;
+  c.x = ctc, c.ldx = ldc, c.x_rows = ctc_rows, c.lam = ctc_weight;
+  c.ls = lm_state, c.ls_bytes = lm_state_bytes, c.lscr = lm_scratch, c.lscr_bytes = lm_scratch_bytes;
+  c.image = lm_image, c.image_bytes = lm_bytes, c.lm_on = lm_on, c.alpha = alpha, c.beta = beta, c.use_eos = use_eos;
+  c.logits = logits, c.ldl = ldl;
+  return fused_score(c);
 }
 
 int m3_aed_ngram_prune(const m3_aed_joint_desc* desc, void* search_state, size_t search_state_bytes, void* joint_state, size_t joint_state_bytes,
                     const void* scratch, size_t scratch_bytes, void* lm_state, size_t lm_state_bytes, const void* lm_scratch,
                     size_t lm_scratch_bytes, int32_t* done, m3_stream stream) {
-  const bool with_ctc = joint_state != nullptr;                  // the CTC = false form has no scorer state
-  if (int rc = check_lm(desc, with_ctc, search_state, search_state_bytes, joint_state, joint_state_bytes, scratch, scratch_bytes, lm_state,
-                        lm_state_bytes, lm_scratch, lm_scratch_bytes, true, "aed_ngram_prune")) return rc;
-  const m3_aed_search_desc* s = &desc->search;
-  if (s->B == 0) return 0;
-  const SearchLayout l = search_layout(s);
-  const LmFuse lx{nullptr, 0, nullptr, (int32_t*)lm_state, (int32_t*)const_cast<void*>(lm_scratch), 0.0, 0.0, 0};
-  if (with_ctc)
-    hipLaunchKernelGGL((aed_joint_prune_kernel<true, true, false, LmFuse>), dim3((unsigned)s->B), dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state,
-                       s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames, (float*)joint_state, (const int32_t*)scratch,
-                       (const float*)scratch, done, lx);
-  else
-    hipLaunchKernelGGL((aed_joint_prune_kernel<false, true, false, LmFuse>), dim3((unsigned)s->B), dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state,
-                       s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, 0, (float*)nullptr,
-                       (const int32_t*)lm_cand(desc, const_cast<void*>(lm_scratch)), (const float*)nullptr, done, lx);
-  M3_LAUNCH_CHECK();
-  return 0;
+  // the CTC = false form has no scorer state
+  FusedCall c = fused_call("aed_ngram_prune", NGRAM, joint_state != nullptr, true, false, desc, search_state, search_state_bytes, stream);
+  c.js = joint_state, c.js_bytes = joint_state_bytes, c.scr = scratch, c.scr_bytes = scratch_bytes;
+  c.ls = lm_state, c.ls_bytes = lm_state_bytes, c.lscr = lm_scratch, c.lscr_bytes = lm_scratch_bytes;
+  c.done = done;
+  return fused_prune(c);
 }
 
 int m3_aed_ngram_result(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, const void* lm_state,
                      size_t lm_state_bytes, float* lm, int32_t* lm_state_out, int32_t* n, float* att, m3_stream stream) {
-  if (int rc = check_lm(desc, false, search_state, search_state_bytes, nullptr, 0, nullptr, 0, lm_state, lm_state_bytes, nullptr, 0, false,
-                        "aed_ngram_result")) return rc;
+  FusedCall c = fused_call("aed_ngram_result", NGRAM, false, true, false, desc, search_state, search_state_bytes, stream);
+  c.ls = lm_state, c.ls_bytes = lm_state_bytes;
+  if (int rc = check_call(c, false, false)) return rc;
   if (desc->search.B == 0) return 0;
   M3_REQUIRE(lm && lm_state_out, "aed_ngram_result: null pointer");
-  hipLaunchKernelGGL(aed_lm_result_kernel, dim3((unsigned)desc->search.B), dim3(64), 0, (hipStream_t)stream, (const int32_t*)search_state,
+  hipLaunchKernelGGL(aed_lm_result_kernel, dim3((unsigned)desc->search.B), dim3(64), 0, c.stream, (const int32_t*)search_state,
                      desc->search.beam, search_layout(&desc->search).P, (const int32_t*)lm_state, lm, lm_state_out, n, att);
   M3_LAUNCH_CHECK();
   return 0;
 }
 
-size_t m3_aed_bias_state_size(const m3_aed_joint_desc* desc) {
-  if (check_bias_desc(desc, false)) return 0;
-  return bias_state_bytes(desc);
-}
-
-size_t m3_aed_bias_scratch_size(const m3_aed_joint_desc* desc) {
-  if (check_bias_desc(desc, false)) return 0;
-  return bias_scratch_bytes(desc);
-}
-
+// ---- m3_aed_bias_*: always the context part; the CTC and LM parts as ctc_weight and the pointers say
 int m3_aed_bias_reset(const m3_aed_joint_desc* desc, const m3_aed_bias* bias, m3_stream stream) {
-  if (int rc = check_bias_desc(desc, false)) return rc;
+  if (int rc = check_desc(desc, BIAS, false)) return rc;
   if (int rc = check_bias(desc, bias, true, false, "aed_bias_reset")) return rc;
   // the image's header, read back once per search: what ctx_graph_view refuses here the kernels would run as "unbiased"
   int32_t head[CTX_HDR_WORDS];
@@ -993,112 +1021,42 @@ int m3_aed_bias_score(const m3_aed_joint_desc* desc, const void* search_state, s
                       float ctc_weight, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha, double beta, int use_eos,
                       const m3_aed_bias* bias, m3_stream stream) {
   M3_REQUIRE(ctc_weight >= 0.f && ctc_weight <= 1.f, "aed_bias_score: ctc_weight = %g outside [0, 1]", (double)ctc_weight);
-  const bool with_ctc = ctc_weight > 0.f, with_lm = lm_image != nullptr;
-  const bool empty = desc && desc->search.B == 0;
-  M3_REQUIRE((ctc != nullptr) == with_ctc || empty, "aed_bias_score: the CTC log-probabilities are given exactly when ctc_weight > 0 (ctc_weight = %g)",
+  FusedCall c = fused_call("aed_bias_score", BIAS, ctc_weight > 0.f, lm_image != nullptr, true, desc, search_state, search_state_bytes, stream);
+  M3_REQUIRE((ctc != nullptr) == c.ctc || c.empty(), "aed_bias_score: the CTC log-probabilities are given exactly when ctc_weight > 0 (ctc_weight = %g)",
              (double)ctc_weight);
-  M3_REQUIRE(((joint_state != nullptr) == with_ctc && (scratch != nullptr) == with_ctc) || empty,
+  M3_REQUIRE(((joint_state != nullptr) == c.ctc && (scratch != nullptr) == c.ctc) || c.empty(),
              "aed_bias_score: the scorer state and the joint scratch are given exactly when ctc_weight > 0 (ctc_weight = %g)", (double)ctc_weight);
-  M3_REQUIRE(((lm_state != nullptr) == with_lm && (lm_scratch != nullptr) == with_lm && (lm_on != nullptr) == with_lm) || empty,
+  M3_REQUIRE(((lm_state != nullptr) == c.lm && (lm_scratch != nullptr) == c.lm && (lm_on != nullptr) == c.lm) || c.empty(),
              "aed_bias_score: the LM image, lm_on, the LM state and the LM scratch are NULL exactly when there is no LM");
-  if (int rc = check_bias_blobs(desc, with_ctc, with_lm, search_state, search_state_bytes, joint_state, joint_state_bytes, scratch, scratch_bytes,
-                                lm_state, lm_state_bytes, lm_scratch, lm_scratch_bytes, "aed_bias_score")) return rc;
-  if (int rc = check_bias(desc, bias, true, true, "aed_bias_score")) return rc;
-  if (with_ctc)
-    if (int rc = check_ctc(desc, ctc, ldc, ctc_rows, "aed_bias_score")) return rc;
-  const m3_aed_search_desc* s = &desc->search;
-  M3_REQUIRE(ldl >= s->V, "aed_bias_score: ldl = %d < V = %d", ldl, s->V);
-  if (with_lm) {
-    if (int rc = check_lm_args("aed_bias_score", lm_image, lm_bytes, lm_on, alpha, beta, s->B)) return rc;
-    M3_REQUIRE(use_eos == 0 || use_eos == 1, "aed_bias_score: use_eos = %d", use_eos);
-  } else {
-    M3_REQUIRE(std::isfinite(alpha) && std::isfinite(beta), "aed_bias_score: alpha or beta is not finite");
-  }
-  if (s->B == 0) return 0;
-  M3_REQUIRE(logits != nullptr, "aed_bias_score: null pointer");
-  const SearchLayout l = search_layout(s);
-  const CtxFuse cx{(const int32_t*)bias->image, (long long)(bias->image_bytes / 4), bias->graph_of, (int32_t*)bias->state, (int32_t*)bias->scratch};
-  const dim3 grid((unsigned)(s->B * s->beam));
-  if (with_lm) {
-    Biased<LmFuse> lx;
-    static_cast<LmFuse&>(lx) = LmFuse{(const int32_t*)lm_image, (long long)(lm_bytes / 4), lm_on, (int32_t*)const_cast<void*>(lm_state),
-                                      (int32_t*)lm_scratch, alpha, beta, use_eos};
-    lx.cx = cx;
-    if (with_ctc)
-      hipLaunchKernelGGL((aed_joint_score_kernel<true, true, true, Biased<LmFuse>>), grid, dim3(64), 0, (hipStream_t)stream,
-                         (const int32_t*)search_state, s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames,
-                         (const float*)joint_state, (int32_t*)scratch, (float*)scratch, logits, ldl, ctc, ldc, ctc_rows, ctc_weight, lx);
-    else
-      hipLaunchKernelGGL((aed_joint_score_kernel<false, true, true, Biased<LmFuse>>), grid, dim3(64), 0, (hipStream_t)stream,
-                         (const int32_t*)search_state, s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, 0, (const float*)nullptr,
-                         lm_cand(desc, lm_scratch), (float*)nullptr, logits, ldl, (const float*)nullptr, 0, 0, 0.f, lx);
-  } else {
-    Biased<NoLm> lx;
-    lx.cx = cx;
-    if (with_ctc)
-      hipLaunchKernelGGL((aed_joint_score_kernel<true, false, true, Biased<NoLm>>), grid, dim3(64), 0, (hipStream_t)stream,
-                         (const int32_t*)search_state, s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames,
-                         (const float*)joint_state, (int32_t*)scratch, (float*)scratch, logits, ldl, ctc, ldc, ctc_rows, ctc_weight, lx);
-    else
-      hipLaunchKernelGGL((aed_joint_score_kernel<false, false, true, Biased<NoLm>>), grid, dim3(64), 0, (hipStream_t)stream,
-                         (const int32_t*)search_state, s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, 0, (const float*)nullptr,
-                         bias_cand(desc, bias->scratch), (float*)nullptr, logits, ldl, (const float*)nullptr, 0, 0, 0.f, lx);
-  }
-  M3_LAUNCH_CHECK();
-  return 0;
+  c.js = joint_state, c.js_bytes = joint_state_bytes, c.scr = scratch, c.scr_bytes = scratch_bytes;
+  c.x = ctc, c.ldx = ldc, c.x_rows = ctc_rows, c.lam = ctc_weight;
+  c.ls = lm_state, c.ls_bytes = lm_state_bytes, c.lscr = lm_scratch, c.lscr_bytes = lm_scratch_bytes;
+  c.image = lm_image, c.image_bytes = lm_bytes, c.lm_on = lm_on, c.alpha = alpha, c.beta = beta, c.use_eos = use_eos;
+  c.bias = bias, c.logits = logits, c.ldl = ldl;
+  return fused_score(c);
 }
 
 int m3_aed_bias_prune(const m3_aed_joint_desc* desc, void* search_state, size_t search_state_bytes, void* joint_state, size_t joint_state_bytes,
                       const void* scratch, size_t scratch_bytes, void* lm_state, size_t lm_state_bytes, const void* lm_scratch,
                       size_t lm_scratch_bytes, const m3_aed_bias* bias, int32_t* done, m3_stream stream) {
-  const bool with_ctc = joint_state != nullptr, with_lm = lm_state != nullptr;   // as the score call of the same search had them
-  const bool empty = desc && desc->search.B == 0;
-  M3_REQUIRE((scratch != nullptr) == with_ctc || empty, "aed_bias_prune: the scorer state and the joint scratch are given together or not at all");
-  M3_REQUIRE((lm_scratch != nullptr) == with_lm || empty, "aed_bias_prune: the LM state and the LM scratch are given together or not at all");
-  if (int rc = check_bias_blobs(desc, with_ctc, with_lm, search_state, search_state_bytes, joint_state, joint_state_bytes, scratch, scratch_bytes,
-                                lm_state, lm_state_bytes, lm_scratch, lm_scratch_bytes, "aed_bias_prune")) return rc;
-  if (int rc = check_bias(desc, bias, false, true, "aed_bias_prune")) return rc;
-  const m3_aed_search_desc* s = &desc->search;
-  if (s->B == 0) return 0;
-  const SearchLayout l = search_layout(s);
-  const CtxFuse cx{nullptr, 0, nullptr, (int32_t*)bias->state, (int32_t*)bias->scratch};
-  const dim3 grid((unsigned)s->B);
-  if (with_lm) {
-    Biased<LmFuse> lx;
-    static_cast<LmFuse&>(lx) = LmFuse{nullptr, 0, nullptr, (int32_t*)lm_state, (int32_t*)const_cast<void*>(lm_scratch), 0.0, 0.0, 0};
-    lx.cx = cx;
-    if (with_ctc)
-      hipLaunchKernelGGL((aed_joint_prune_kernel<true, true, true, Biased<LmFuse>>), grid, dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state,
-                         s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames, (float*)joint_state, (const int32_t*)scratch,
-                         (const float*)scratch, done, lx);
-    else
-      hipLaunchKernelGGL((aed_joint_prune_kernel<false, true, true, Biased<LmFuse>>), grid, dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state,
-                         s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, 0, (float*)nullptr,
-                         (const int32_t*)lm_cand(desc, const_cast<void*>(lm_scratch)), (const float*)nullptr, done, lx);
-  } else {
-    Biased<NoLm> lx;
-    lx.cx = cx;
-    if (with_ctc)
-      hipLaunchKernelGGL((aed_joint_prune_kernel<true, false, true, Biased<NoLm>>), grid, dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state,
-                         s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, desc->max_frames, (float*)joint_state, (const int32_t*)scratch,
-                         (const float*)scratch, done, lx);
-    else
-      hipLaunchKernelGGL((aed_joint_prune_kernel<false, false, true, Biased<NoLm>>), grid, dim3(256), 0, (hipStream_t)stream, (int32_t*)search_state,
-                         s->B, s->beam, l.P, l.rec_words, s->V, desc->pre_beam, 0, (float*)nullptr,
-                         (const int32_t*)bias_cand(desc, bias->scratch), (const float*)nullptr, done, lx);
-  }
-  M3_LAUNCH_CHECK();
-  return 0;
+  // the parts as the score call of the same search had them
+  FusedCall c = fused_call("aed_bias_prune", BIAS, joint_state != nullptr, lm_state != nullptr, true, desc, search_state, search_state_bytes, stream);
+  M3_REQUIRE((scratch != nullptr) == c.ctc || c.empty(), "aed_bias_prune: the scorer state and the joint scratch are given together or not at all");
+  M3_REQUIRE((lm_scratch != nullptr) == c.lm || c.empty(), "aed_bias_prune: the LM state and the LM scratch are given together or not at all");
+  c.js = joint_state, c.js_bytes = joint_state_bytes, c.scr = scratch, c.scr_bytes = scratch_bytes;
+  c.ls = lm_state, c.ls_bytes = lm_state_bytes, c.lscr = lm_scratch, c.lscr_bytes = lm_scratch_bytes;
+  c.bias = bias, c.done = done;
+  return fused_prune(c);
 }
 
 int m3_aed_bias_result(const m3_aed_joint_desc* desc, const void* search_state, size_t search_state_bytes, const m3_aed_bias* bias,
                        float* bonus, int32_t* ctx_state, float* att, m3_stream stream) {
-  if (int rc = check_bias_desc(desc, false)) return rc;
-  if (int rc = check_search_state(&desc->search, search_state, search_state_bytes, "aed_bias_result")) return rc;
-  if (int rc = check_bias(desc, bias, false, false, "aed_bias_result")) return rc;
+  FusedCall c = fused_call("aed_bias_result", BIAS, false, false, true, desc, search_state, search_state_bytes, stream);
+  c.bias = bias;
+  if (int rc = check_call(c, false, false)) return rc;
   if (desc->search.B == 0) return 0;
   M3_REQUIRE(bonus && ctx_state, "aed_bias_result: null pointer");
-  hipLaunchKernelGGL(aed_bias_result_kernel, dim3((unsigned)desc->search.B), dim3(64), 0, (hipStream_t)stream, (const int32_t*)search_state,
+  hipLaunchKernelGGL(aed_bias_result_kernel, dim3((unsigned)desc->search.B), dim3(64), 0, c.stream, (const int32_t*)search_state,
                      desc->search.beam, search_layout(&desc->search).P, (const int32_t*)bias->state, bonus, ctx_state, att);
   M3_LAUNCH_CHECK();
   return 0;

@@ -108,9 +108,6 @@ class AttentionBeamSearch:
                 if int(g.cls[cfg.vocab - 1]) != 0:
                     raise _lib.M3Error("AttentionBeamSearch: graph %d of the context set has eos (%d) in a phrase; eos is never walked" % (
                         i, cfg.vocab - 1))
-            if context.dev is None or not context.dev.is_cuda or context.dev.device != torch.device(self.device):
-                raise _lib.M3Error("AttentionBeamSearch: the context set is not on %s; build it with ContextSet(graphs, device=...)" % (
-                    self.device,))
         self.pre_beam = 0
         if self.ctc_weight > 0 or lm is not None or context is not None:
             self.pre_beam = min(max(self.beam, math.ceil(1.5 * self.beam)), 64, cfg.vocab) if pre_beam is None else int(pre_beam)
@@ -152,9 +149,41 @@ class AttentionBeamSearch:
         self._graph = None
         self.steps_issued = 0     # of the last call
         self.last = None          # device tensors of the last call: m3_aed_search_result's, plus state and done
+        self._bind_form()
+
+    def _bind_form(self):
+        """The form of the search, decided once; every call reads self when it runs: _take_ctc replaces jdesc and the
+        scorer blobs, lm_weight and length_bonus are launch arguments.  self._tail: a step's calls behind the output layer: without
+        CTC, LM and context m3_aed_search_prune, else the score and prune of the family that takes every part present, on jdesc
+        with CTC, else on the context's or the LM's descriptor.  self._parts: the parts present in the order joint, LM, context,
+        each (reset call, result call, the result's key of its att part, the floats it alone adds to detail)."""
+        ctc, lm, ctx = self.ctc_weight > 0, self.lm is not None, self.context is not None
+        blobs = lambda: (self.jdesc if ctc else self.bdesc if ctx else self.ldesc, self.state, self.jstate, self.jscratch,   # noqa: E731
+                         self.lstate, self.lscratch)
+        inputs = lambda: (self.logits, self.ctc, self.ctc_weight) + (   # noqa: E731
+            (self.lm.dev, self.lm_on, self.lm_weight, self.length_bonus) if lm else (None, None, 0.0, 0.0)) + (self.lm_eos,)
+        if ctx:
+            self._tail = [lambda: ops.aed_bias_score(*blobs(), *inputs(), self.bias), lambda: ops.aed_bias_prune(*blobs(), self.bias, self.done)]
+        elif lm:
+            self._tail = [lambda: ops.aed_lm_score(*blobs(), *inputs()), lambda: ops.aed_lm_prune(*blobs(), self.done)]
+        elif ctc:                                                  # the joint family takes neither the LM blobs nor the LM inputs
+            self._tail = [lambda: ops.aed_joint_score(*blobs()[:4], *inputs()[:3]), lambda: ops.aed_joint_prune(*blobs()[:4], self.done)]
+        else:
+            self._tail = [lambda: ops.aed_search_prune(self.desc, self.state, self.logits, self.done)]
+        self._parts = []
+        if ctc:
+            self._parts.append((lambda: ops.aed_joint_reset(self.jdesc, self.state, self.jstate, self.ctc),
+                                lambda: dict(ops.aed_joint_result(self.jdesc, self.state, self.jstate), joint_state=self.jstate), "att", []))
+        if lm:                                                    # a set: every utterance starts in its own member's start state
+            lm_reset = ((lambda: ops.aed_lm_reset_set(self.ldesc, self.lstate, self.lm.dev, self.lm_on)) if isinstance(self.lm, NgramLmSet)
+                        else (lambda: ops.aed_lm_reset(self.ldesc, self.lstate, self.lm.dev)))
+            self._parts.append((lm_reset, lambda: dict(ops.aed_lm_result(self.ldesc, self.state, self.lstate), lm_blob=self.lstate), "lm_att", ["lm"]))
+        if ctx:
+            self._parts.append((lambda: ops.aed_bias_reset(self.bdesc, self.bias),
+                                lambda: dict(ops.aed_bias_result(self.bdesc, self.state, self.bias), ctx_blob=self.cstate), "ctx_att", ["bonus"]))
 
     def launches_per_step(self):
-        return 8 * self.cfg.num_blocks + (4 if self.ctc_weight > 0 or self.lm is not None or self.context is not None else 3)
+        return 8 * self.cfg.num_blocks + 2 + len(self._tail)
 
     # ---- one step: the same launches with the same arguments, whatever the step
     def _step(self):
@@ -175,34 +204,13 @@ class AttentionBeamSearch:
             ops.linear(self.h, w[q + "feed_forward.w_2.weight"], w[q + "feed_forward.w_2.bias"], resid=x, out=x)
         ops.linear(x, w["decoder.output_layer.weight"], w["decoder.output_layer.bias"],
                    ln=(w["decoder.after_norm.weight"], w["decoder.after_norm.bias"], LN_EPS), out=self.logits)
-        if self.context is not None:
-            jd = self.jdesc if self.ctc_weight > 0 else self.bdesc
-            lm = self.lm.dev if self.lm is not None else None
-            ops.aed_bias_score(jd, st, self.jstate, self.jscratch, self.lstate, self.lscratch, self.logits, self.ctc, self.ctc_weight,
-                               lm, self.lm_on, self.lm_weight if lm is not None else 0.0, self.length_bonus if lm is not None else 0.0,
-                               self.lm_eos, self.bias)
-            ops.aed_bias_prune(jd, st, self.jstate, self.jscratch, self.lstate, self.lscratch, self.bias, self.done)
-        elif self.lm is not None:
-            jd = self.jdesc if self.ctc_weight > 0 else self.ldesc
-            ops.aed_lm_score(jd, st, self.jstate, self.jscratch, self.lstate, self.lscratch, self.logits, self.ctc, self.ctc_weight,
-                             self.lm.dev, self.lm_on, self.lm_weight, self.length_bonus, self.lm_eos)
-            ops.aed_lm_prune(jd, st, self.jstate, self.jscratch, self.lstate, self.lscratch, self.done)
-        elif self.ctc_weight > 0:
-            ops.aed_joint_score(self.jdesc, st, self.jstate, self.jscratch, self.logits, self.ctc, self.ctc_weight)
-            ops.aed_joint_prune(self.jdesc, st, self.jstate, self.jscratch, self.done)
-        else:
-            ops.aed_search_prune(d, st, self.logits, self.done)
+        for call in self._tail:
+            call()
 
     def _reset(self, meta, cap):
         ops.aed_search_reset(self.desc, self.state, meta[0], meta[1], cap)
-        if self.ctc_weight > 0:
-            ops.aed_joint_reset(self.jdesc, self.state, self.jstate, self.ctc)
-        if isinstance(self.lm, NgramLmSet):                       # every utterance starts in its own member's start state
-            ops.aed_lm_reset_set(self.ldesc, self.lstate, self.lm.dev, self.lm_on)
-        elif self.lm is not None:
-            ops.aed_lm_reset(self.ldesc, self.lstate, self.lm.dev)
-        if self.context is not None:
-            ops.aed_bias_reset(self.bdesc, self.bias)
+        for reset, *_ in self._parts:
+            reset()
         self.done.zero_()
 
     def _take_ctc(self, ctc, n_rows, frames, log_probs):
@@ -302,27 +310,19 @@ class AttentionBeamSearch:
         self.steps_issued = issued
         res = ops.aed_search_result(d, self.state)
         self.last = dict(res, state=self.state, done=self.done)
-        parts = []
-        if self.ctc_weight > 0:
-            jres = ops.aed_joint_result(self.jdesc, self.state, self.jstate)
-            self.last.update(jres, joint_state=self.jstate)
-            parts = [jres["att"].reshape(-1).view(torch.int32), jres["ctc"].reshape(-1).view(torch.int32)]
-        if self.lm is not None:
-            lres = ops.aed_lm_result(self.ldesc, self.state, self.lstate)
-            self.last.update(lm=lres["lm"], lm_state=lres["lm_state"], lm_n=lres["lm_n"], lm_blob=self.lstate)
-            if not parts:                                           # attention + LM: the att part rides in the LM state, ctc is 0
-                self.last.update(att=lres["lm_att"], ctc=torch.zeros_like(lres["lm_att"]))
-                parts = [self.last["att"].reshape(-1).view(torch.int32), self.last["ctc"].reshape(-1).view(torch.int32)]
-            parts.append(lres["lm"].reshape(-1).view(torch.int32))
-        tail = []
-        if self.context is not None:
-            cres = ops.aed_bias_result(self.bdesc, self.state, self.bias)
-            self.last.update(bonus=cres["bonus"], ctx_state=cres["ctx_state"], ctx_blob=self.cstate)
-            if not parts:                                           # attention + context: the att part rides in the context state
-                self.last.update(att=cres["ctx_att"], ctc=torch.zeros_like(cres["ctx_att"]))
-                parts = [self.last["att"].reshape(-1).view(torch.int32), self.last["ctc"].reshape(-1).view(torch.int32)]
-            parts.append(cres["bonus"].reshape(-1).view(torch.int32))
-            tail = [cres["ctx_state"].reshape(-1)]                  # int32 as it is, behind the float parts
+        # the float parts behind the score: att, ctc, then what each part alone adds.  The att part comes from the FIRST part
+        # present, the one whose state stores it (scorer state, else LM state, else context state); ctc is zeros without CTC
+        floats = []
+        for _, result, att_key, adds in self._parts:
+            gained = result()
+            att = gained.pop(att_key)
+            self.last.update(gained)
+            if not floats:
+                self.last.update(att=att, ctc=gained["ctc"] if "ctc" in gained else torch.zeros_like(att))
+                floats = ["att", "ctc"]
+            floats += adds
+        parts = [self.last[k].reshape(-1).view(torch.int32) for k in floats]
+        tail = [self.last["ctx_state"].reshape(-1)] if self.context is not None else []   # int32 as it is, behind the float parts
         host = torch.cat([res["hyp_tokens"].reshape(-1), res["hyp_len"].reshape(-1), res["finished"].reshape(-1), res["best"],
                           res["score"].reshape(-1).view(torch.int32)] + parts + tail).cpu()
         B, N, S = self.B, self.beam, self.max_steps

@@ -1309,13 +1309,28 @@ def aed_search_result(desc, state):
 
 
 # ---- joint CTC/attention decoding: CTC prefix scores inside that search (m3_aed_joint_*)
+def _aed_fused_desc(search_desc, pre_beam, max_frames, size_fn):
+    """m3_aed_joint_desc around a search descriptor, validated by the size function of the family that will use it"""
+    d = _lib.AedJointDesc(search_desc, int(pre_beam), int(max_frames))
+    if getattr(_lib.load(), size_fn)(C.byref(d)) == 0:
+        raise _lib.M3Error(size_fn + " failed: " + _lib.last_error())
+    return d
+
+
+def _blobs(*blobs):
+    """optional uint8 blobs -> pointer, bytes, pointer, bytes, ...; None: NULL, 0"""
+    return [v for t in blobs for v in (_p(t), _nbytes(t) if t is not None else 0)]
+
+
+def _opt_rows(t):
+    """an optional row-strided (rows, n) float input -> pointer, ld, rows; None: NULL, 0, 0"""
+    return (None, 0, 0) if t is None else _rows(t) + (t.shape[0],)
+
+
 def aed_joint_desc(search_desc, pre_beam, max_frames):
     """m3_aed_joint_desc around a search descriptor.  Raises M3Error on what the library rejects (pre_beam outside
     [beam, min(64, V)], max_frames < 1, V < 2, sizes that overflow the int32 offsets of the scorer state or the scratch)."""
-    d = _lib.AedJointDesc(search_desc, int(pre_beam), int(max_frames))
-    if _lib.load().m3_aed_joint_state_size(C.byref(d)) == 0:
-        raise _lib.M3Error("m3_aed_joint_state_size failed: " + _lib.last_error())
-    return d
+    return _aed_fused_desc(search_desc, pre_beam, max_frames, "m3_aed_joint_state_size")
 
 
 def aed_joint_state_size(desc):
@@ -1362,10 +1377,7 @@ def aed_joint_result(desc, state, jstate):
 def aed_lm_desc(search_desc, pre_beam, max_frames=0):
     """The descriptor of the fused search: m3_aed_joint_desc; max_frames = 0 where there is no CTC part (ctc_weight = 0).
     Raises M3Error on what the library rejects."""
-    d = _lib.AedJointDesc(search_desc, int(pre_beam), int(max_frames))
-    if _lib.load().m3_aed_ngram_state_size(C.byref(d)) == 0:
-        raise _lib.M3Error("m3_aed_ngram_state_size failed: " + _lib.last_error())
-    return d
+    return _aed_fused_desc(search_desc, pre_beam, max_frames, "m3_aed_ngram_state_size")
 
 
 def aed_lm_state_size(desc):
@@ -1393,23 +1405,17 @@ def aed_lm_reset_set(desc, lstate, lm_image, lm_on):
 
 def aed_lm_score(desc, state, jstate, scratch, lstate, lscratch, logits, ctc, ctc_weight, lm_image, lm_on, alpha, beta, use_eos=True):
     """aed_joint_score with every candidate's LM step and the fused key; ctc / jstate / scratch None exactly when ctc_weight = 0"""
-    lp, ldl = _rows(logits)
-    cp, ldc = _rows(ctc) if ctc is not None else (None, 0)
     assert tuple(logits.shape) == (desc.search.B * desc.search.beam, desc.search.V) and lm_on.numel() == desc.search.B
-    lmi, lm_bytes = _image(lm_image)
-    check(_lib.load().m3_aed_ngram_score(C.byref(desc), _p(state), _nbytes(state), _p(jstate), _nbytes(jstate) if jstate is not None else 0,
-                                      _p(scratch), _nbytes(scratch) if scratch is not None else 0, _p(lstate), _nbytes(lstate),
-                                      _p(lscratch), _nbytes(lscratch), lp, ldl, cp, ldc, ctc.shape[0] if ctc is not None else 0,
-                                      float(ctc_weight), lmi, lm_bytes, _i32(lm_on), float(alpha), float(beta), int(bool(use_eos)),
+    check(_lib.load().m3_aed_ngram_score(C.byref(desc), *_blobs(state, jstate, scratch, lstate, lscratch), *_rows(logits), *_opt_rows(ctc),
+                                      float(ctc_weight), *_image(lm_image), _i32(lm_on), float(alpha), float(beta), int(bool(use_eos)),
                                       _stream()), "m3_aed_ngram_score")
 
 
 def aed_lm_prune(desc, state, jstate, scratch, lstate, lscratch, done=None):
     """aed_joint_prune, the survivors' LM state copied from the LM scratch; jstate / scratch None: the search without CTC"""
     assert done is None or done.numel() == desc.search.B
-    check(_lib.load().m3_aed_ngram_prune(C.byref(desc), _p(state), _nbytes(state), _p(jstate), _nbytes(jstate) if jstate is not None else 0,
-                                      _p(scratch), _nbytes(scratch) if scratch is not None else 0, _p(lstate), _nbytes(lstate),
-                                      _p(lscratch), _nbytes(lscratch), _i32(done), _stream()), "m3_aed_ngram_prune")
+    check(_lib.load().m3_aed_ngram_prune(C.byref(desc), *_blobs(state, jstate, scratch, lstate, lscratch), _i32(done), _stream()),
+          "m3_aed_ngram_prune")
 
 
 def aed_lm_result(desc, state, lstate):
@@ -1426,10 +1432,7 @@ def aed_lm_result(desc, state, lstate):
 def aed_bias_desc(search_desc, pre_beam, max_frames=0):
     """The descriptor of the biased search: m3_aed_joint_desc; max_frames = 0 where there is no CTC part (ctc_weight = 0).
     Raises M3Error on what the library rejects."""
-    d = _lib.AedJointDesc(search_desc, int(pre_beam), int(max_frames))
-    if _lib.load().m3_aed_bias_state_size(C.byref(d)) == 0:
-        raise _lib.M3Error("m3_aed_bias_state_size failed: " + _lib.last_error())
-    return d
+    return _aed_fused_desc(search_desc, pre_beam, max_frames, "m3_aed_bias_state_size")
 
 
 def aed_bias_state_size(desc):
@@ -1462,26 +1465,19 @@ def aed_bias_reset(desc, bias):
 def aed_bias_score(desc, state, jstate, scratch, lstate, lscratch, logits, ctc, ctc_weight, lm_image, lm_on, alpha, beta, use_eos, bias):
     """aed_lm_score with every candidate's context arc and the biased key; lm_image / lm_on / lstate / lscratch None exactly when
     there is no LM, ctc / jstate / scratch None exactly when ctc_weight = 0"""
-    lp, ldl = _rows(logits)
-    cp, ldc = _rows(ctc) if ctc is not None else (None, 0)
     assert tuple(logits.shape) == (desc.search.B * desc.search.beam, desc.search.V)
     assert lm_on is None or lm_on.numel() == desc.search.B
-    lmi, lm_bytes = _image(lm_image)
-    nb = lambda t: _nbytes(t) if t is not None else 0   # noqa: E731
-    check(_lib.load().m3_aed_bias_score(C.byref(desc), _p(state), _nbytes(state), _p(jstate), nb(jstate), _p(scratch), nb(scratch),
-                                        _p(lstate), nb(lstate), _p(lscratch), nb(lscratch), lp, ldl, cp, ldc,
-                                        ctc.shape[0] if ctc is not None else 0, float(ctc_weight), lmi, lm_bytes, _i32(lm_on),
-                                        float(alpha), float(beta), int(bool(use_eos)), C.byref(bias), _stream()), "m3_aed_bias_score")
+    check(_lib.load().m3_aed_bias_score(C.byref(desc), *_blobs(state, jstate, scratch, lstate, lscratch), *_rows(logits), *_opt_rows(ctc),
+                                        float(ctc_weight), *_image(lm_image), _i32(lm_on), float(alpha), float(beta), int(bool(use_eos)),
+                                        C.byref(bias), _stream()), "m3_aed_bias_score")
 
 
 def aed_bias_prune(desc, state, jstate, scratch, lstate, lscratch, bias, done=None):
     """aed_lm_prune, the survivors' context state copied from the context scratch; jstate / scratch None: no CTC; lstate / lscratch
     None: no LM"""
     assert done is None or done.numel() == desc.search.B
-    nb = lambda t: _nbytes(t) if t is not None else 0   # noqa: E731
-    check(_lib.load().m3_aed_bias_prune(C.byref(desc), _p(state), _nbytes(state), _p(jstate), nb(jstate), _p(scratch), nb(scratch),
-                                        _p(lstate), nb(lstate), _p(lscratch), nb(lscratch), C.byref(bias), _i32(done), _stream()),
-          "m3_aed_bias_prune")
+    check(_lib.load().m3_aed_bias_prune(C.byref(desc), *_blobs(state, jstate, scratch, lstate, lscratch), C.byref(bias), _i32(done),
+                                        _stream()), "m3_aed_bias_prune")
 
 
 def aed_bias_result(desc, state, bias):
