@@ -863,6 +863,22 @@ int m3_wfst_search_result(const m3_wfst_search_desc* desc, const void* state, si
   return launch_wfst_search_result(desc, state, state_bytes, graph, graph_bytes, final, max_words, words, frames, n_words, cost,
                                    flags, status, (hipStream_t)stream);
 }
+size_t m3_wfst_skip_state_size(const m3_wfst_skip_desc* desc) { return wfst_skip_state_size(desc); }
+int m3_wfst_skip_reset(const m3_wfst_skip_desc* desc, void* state, size_t state_bytes, const int32_t* slots, int n, m3_stream stream) {
+  return launch_wfst_skip_reset(desc, state, state_bytes, slots, n, (hipStream_t)stream);
+}
+int m3_wfst_skip_select(const m3_wfst_skip_desc* desc, void* state, size_t state_bytes, const float* logp, int ld, int T_chunk,
+                        const int32_t* n_frames, float* out, int ld_out, int32_t* n_kept, m3_stream stream) {
+  return launch_wfst_skip_select(desc, state, state_bytes, logp, ld, T_chunk, n_frames, out, ld_out, n_kept, (hipStream_t)stream);
+}
+int m3_wfst_skip_map_frames(const m3_wfst_skip_desc* desc, const void* state, size_t state_bytes, int32_t* frames, int ld_frames,
+                            const int32_t* n_words, m3_stream stream) {
+  return launch_wfst_skip_map_frames(desc, state, state_bytes, frames, ld_frames, n_words, (hipStream_t)stream);
+}
+int m3_wfst_skip_counts(const m3_wfst_skip_desc* desc, const void* state, size_t state_bytes, int32_t* seen, int32_t* kept,
+                        m3_stream stream) {
+  return launch_wfst_skip_counts(desc, state, state_bytes, seen, kept, (hipStream_t)stream);
+}
 size_t m3_ctc_greedy_stream_state_size(const m3_ctc_greedy_desc* desc) { return ctc_greedy_stream_state_size(desc); }
 int m3_ctc_greedy_stream_reset(const m3_ctc_greedy_desc* desc, void* state, size_t state_bytes, m3_stream stream) {
   return launch_ctc_greedy_stream_reset(desc, state, state_bytes, (hipStream_t)stream);

@@ -662,6 +662,15 @@ int launch_wfst_search_advance(const m3_wfst_search_desc* d, void* state, size_t
 int launch_wfst_search_result(const m3_wfst_search_desc* d, const void* state, size_t bytes, const void* image, size_t image_bytes,
                               int final, int max_words, int32_t* words, int32_t* frames, int32_t* n_words, float* cost,
                               int32_t* flags, int32_t* status, hipStream_t stream);
+// ctc_wfst_skip.hip: CTC blank-frame skipping in front of that search
+size_t wfst_skip_state_size(const m3_wfst_skip_desc* d);
+int launch_wfst_skip_reset(const m3_wfst_skip_desc* d, void* state, size_t bytes, const int32_t* slots, int n, hipStream_t stream);
+int launch_wfst_skip_select(const m3_wfst_skip_desc* d, void* state, size_t bytes, const float* logp, int ld, int T_chunk,
+                            const int32_t* n_frames, float* out, int ld_out, int32_t* n_kept, hipStream_t stream);
+int launch_wfst_skip_map_frames(const m3_wfst_skip_desc* d, const void* state, size_t bytes, int32_t* frames, int ld_frames,
+                                const int32_t* n_words, hipStream_t stream);
+int launch_wfst_skip_counts(const m3_wfst_skip_desc* d, const void* state, size_t bytes, int32_t* seen, int32_t* kept,
+                            hipStream_t stream);
 // endpoint detection next to the two searches (ctc_beam.hip)
 size_t ctc_endpoint_state_size(const m3_ctc_endpoint_desc* d);
 int launch_ctc_endpoint_reset(const m3_ctc_endpoint_desc* d, void* state, size_t bytes, hipStream_t stream,

@@ -107,6 +107,10 @@ class WfstSearchDesc(C.Structure):  # m3_wfst_search_desc
         ("beam", C.c_float), ("acoustic_scale", C.c_float)]
 
 
+class WfstSkipDesc(C.Structure):  # m3_wfst_skip_desc
+    _fields_ = [(n, C.c_int32) for n in ("B", "V", "blank", "max_frames")] + [("log_blank_thresh", C.c_float)]
+
+
 class AedMemoryDesc(C.Structure):  # m3_aed_memory_desc
     _fields_ = [("B", C.c_int32), ("max_frames", C.c_int32), ("D", C.c_int32)]
 
@@ -258,6 +262,11 @@ SIGNATURES = {
     "m3_wfst_search_reset": (_i, [_P(WfstSearchDesc), _vp, _sz, _vp, _sz, _vp, _i, _vp]),
     "m3_wfst_search_advance": (_i, [_P(WfstSearchDesc), _vp, _sz, _vp, _sz, _vp, _i, _i, _vp, _vp]),
     "m3_wfst_search_result": (_i, [_P(WfstSearchDesc), _vp, _sz, _vp, _sz, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "m3_wfst_skip_state_size": (_sz, [_P(WfstSkipDesc)]),
+    "m3_wfst_skip_reset": (_i, [_P(WfstSkipDesc), _vp, _sz, _vp, _i, _vp]),
+    "m3_wfst_skip_select": (_i, [_P(WfstSkipDesc), _vp, _sz, _vp, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "m3_wfst_skip_map_frames": (_i, [_P(WfstSkipDesc), _vp, _sz, _vp, _i, _vp, _vp]),
+    "m3_wfst_skip_counts": (_i, [_P(WfstSkipDesc), _vp, _sz, _vp, _vp, _vp]),
     "m3_ctc_greedy_stream_state_size": (_sz, [_P(CtcGreedyDesc)]),
     "m3_ctc_greedy_stream_reset": (_i, [_P(CtcGreedyDesc), _vp, _sz, _vp]),
     "m3_ctc_greedy_stream_reset_slots": (_i, [_P(CtcGreedyDesc), _vp, _sz, _vp, _i, _vp]),

@@ -381,7 +381,8 @@ class CtcDecoder:
                         num_decoding_left_chunks: int = -1, **kw):
         """WeNet's ctc_wfst_beam_search on the device: the forward, then token passing over `graph`, a m3asr.wfst.DecodingGraph
         on the engine's device.  -> word ids per utterance.  kw: CtcWfstSearch's options (beam, max_active, acoustic_scale,
-        token_cap, record_cap, max_state_bytes) and detail= (a dict per utterance: words, frames, cost, reached_final, status)."""
+        token_cap, record_cap, max_state_bytes, blank_skip: CTC blank-frame skipping with the decoder's blank id) and detail= (a
+        dict per utterance: words, frames, cost, reached_final, status)."""
         self._full_context(decoding_chunk_size, num_decoding_left_chunks)
         res = self.forward(xs, xs_lens)
         return self.wfst_from_logits(res["out_nosm"], res["out_lens"], graph, **kw)
@@ -389,6 +390,8 @@ class CtcDecoder:
     def wfst_from_logits(self, logits: torch.Tensor, lens: torch.Tensor, graph, **kw):
         """logits (B,T',V) on the device, lens (B,) valid frames per utterance -> word ids per utterance (device search)."""
         from .wfst import wfst_from_logits
+        if kw.get("blank_skip") is not None:
+            kw.setdefault("blank", self.blank_idx)
         return wfst_from_logits(logits, lens, graph, **kw)
 
     def attention_rescoring(self, xs: torch.Tensor, xs_lens: torch.Tensor, beam_size: int, decoding_chunk_size: int = -1,
@@ -528,10 +531,15 @@ class StreamingCtcDecoder:
     With aligner=CtcAligner(...) the decoder also keeps every stream's logits, in a second store of the same kind: each step()
     copies the chunk's (B c, V) logits into a (B c, Vp) buffer (Vp = V rounded up to a multiple of 4, what the store's 16-byte
     row copies need; the pad columns are never read) and appends it with the same frame counts, and align() gives the token
-    times of a stream's hypothesis on exactly the frames it was searched over."""
+    times of a stream's hypothesis on exactly the frames it was searched over.
+
+    With graph=DecodingGraph(...) the decoder also runs the WFST search (m3asr.wfst.CtcWfstSearch) over
+    every stream: each step() advances it on the chunk's logits with the same frame counts the other searches consume (its
+    launches on the engine's stream, no sync, the chunk's graph is unchanged), reset() restarts it with the slot, and words()
+    reads each stream's word sequence.  The prefix beam search keeps running: the endpoint detector reads its top-k."""
 
     def __init__(self, streaming_encoder, beam, blank=0, context=None, lm=None, lm_weight=0.5, length_bonus=0.0, lm_eos=True,
-                 endpoint=None, rescorer=None, ctc_weight=0.5, reverse_weight=0.0, aligner=None):
+                 endpoint=None, rescorer=None, ctc_weight=0.5, reverse_weight=0.0, aligner=None, graph=None, wfst=None):
         """context: a m3asr.context.ContextSet on the engine's device (hotword biasing of the beam search; the greedy
         search is not biased); reset(graph_ids=) chooses each stream's graph, -1 = unbiased.
         lm: a m3asr.lm.NgramLm on the engine's device (shallow fusion in the beam search, as CtcBeamSearch(lm=); the walk
@@ -542,8 +550,28 @@ class StreamingCtcDecoder:
         weights of the first pass and of the right-to-left decoder in its final score.  None = no second pass (nothing is
         allocated for it, step() launches nothing for it, rescore() raises).
         aligner: a m3asr.align.CtcAligner for the engine's vocabulary, blank and device, for align().  None = no token times
-        (nothing is allocated for them, step() launches nothing for them, align() raises)."""
+        (nothing is allocated for them, step() launches nothing for them, align() raises).
+        graph: a m3asr.wfst.DecodingGraph on the engine's device for words(); wfst: a dict of CtcWfstSearch's options (beam,
+        max_active, acoustic_scale, blank_skip, token_cap, record_cap, max_state_bytes); the search's B, max_frames and blank
+        are the decoder's.  None = no graph search (nothing is allocated for it, step() launches nothing for it, words()
+        raises)."""
         self.st = streaming_encoder
+        self.graph, self.wfst = graph, None
+        if wfst is not None and graph is None:            # refuse before anything is allocated or launched
+            raise _lib.M3Error("StreamingCtcDecoder: wfst= options without graph=")
+        if graph is not None:
+            ecfg = streaming_encoder.eng.cfg
+            if graph.vocab_size != ecfg.output_dim:
+                raise _lib.M3Error("StreamingCtcDecoder: the graph was compiled for V = %d, the encoder's output_dim is %d"
+                                   % (graph.vocab_size, ecfg.output_dim))
+            if graph.dev is None:
+                raise _lib.M3Error("StreamingCtcDecoder: the graph is not on a device (graph.to(device))")
+            if not _same_device(graph.dev.device, streaming_encoder.eng.device):
+                raise _lib.M3Error("StreamingCtcDecoder: the graph is on %s, the engine on %s" % (graph.dev.device, streaming_encoder.eng.device))
+            known = ("beam", "max_active", "acoustic_scale", "blank_skip", "token_cap", "record_cap", "max_state_bytes")
+            unknown = sorted(set(wfst or ()) - set(known))
+            if unknown:
+                raise _lib.M3Error("StreamingCtcDecoder: wfst= has unknown options %s (known: %s)" % (unknown, ", ".join(known)))
         self.aligner = aligner
         if aligner is not None:           # refuse before anything is allocated or launched
             ecfg = streaming_encoder.eng.cfg
@@ -588,6 +616,10 @@ class StreamingCtcDecoder:
             self.ldesc = ops.aed_memory_desc(B, max_frames, vp)
             self.lstate = torch.empty(max(ops.aed_memory_state_size(self.ldesc), 1), dtype=torch.uint8, device=e.device)
             self.lrows = torch.zeros(B * self.c, vp, dtype=torch.float32, device=e.device)      # the chunk's logits, padded to Vp
+        if graph is not None:
+            from .wfst import CtcWfstSearch
+            with torch.cuda.stream(e.stream):          # its constructor resets it: on the stream every later call uses
+                self.wfst = CtcWfstSearch(graph, B, max_frames, blank=int(blank), **dict(wfst or {}))
         self.reset()
 
     def reset(self, slots=None, graph_ids=None, lm_on=None):
@@ -612,6 +644,8 @@ class StreamingCtcDecoder:
                     ops.aed_memory_reset(self.mdesc, self.mstate)
                 if self.aligner is not None:
                     ops.aed_memory_reset(self.ldesc, self.lstate)
+                if self.wfst is not None:
+                    self.wfst.reset()
             elif len(slots) > 0:
                 lst = torch.tensor([int(b) for b in slots], dtype=torch.int32).to(e.device)
                 if self.context is None and self.lm is None:
@@ -625,6 +659,8 @@ class StreamingCtcDecoder:
                     ops.aed_memory_reset(self.mdesc, self.mstate, lst)
                 if self.aligner is not None:
                     ops.aed_memory_reset(self.ldesc, self.lstate, lst)
+                if self.wfst is not None:
+                    self.wfst.reset(lst)
 
     def frames_of(self, valid):
         """Output frames of this chunk that count, from the real feature frames in its window."""
@@ -652,7 +688,35 @@ class StreamingCtcDecoder:
             if self.aligner is not None:
                 self.lrows[:, :self.aligner.V].copy_(logits.reshape(-1, self.aligner.V))
                 ops.aed_memory_append(self.ldesc, self.lstate, self.lrows, self.n_out)
+            if self.wfst is not None:
+                self.wfst.advance(logits, self.n_out)
         return logits
+
+    def words(self, slots=None, final=False, detail=False):
+        """Decoder with a graph: the word ids of every stream's best token after the chunks so far (slots: only the listed
+        streams, in that order), with the meaning of CtcWfstSearch.result -- final: the graph's final weights count; detail:
+        a dict per stream with words, frames (output frames counted from the stream's last reset, real ones with blank_skip
+        too), cost, reached_final and status.  Raises M3Error for a listed stream that overflowed a capacity.  The streams go
+        on as they were.  Waits for the engine's stream."""
+        if self.wfst is None:
+            raise _lib.M3Error("StreamingCtcDecoder.words: the decoder was built without a graph "
+                               "(StreamingCtcDecoder(..., graph=DecodingGraph(...)))")
+        B = self.wfst.B
+        which = list(range(B)) if slots is None else [int(b) for b in slots]
+        if any(not 0 <= b < B for b in which):
+            raise ValueError("StreamingCtcDecoder.words: slots %s outside [0, %d)" % (which, B))
+        if not which:
+            return []
+        with torch.cuda.stream(self.st.eng.stream):
+            return self.wfst.result(final=final, detail=detail, slots=which)
+
+    def decode_words(self, feat, feat_len, use_graph=True):
+        """Whole utterances chunk by chunk, as decode() -> words(final=True)."""
+        if self.wfst is None:
+            raise _lib.M3Error("StreamingCtcDecoder.decode_words: the decoder was built without a graph "
+                               "(StreamingCtcDecoder(..., graph=DecodingGraph(...)))")
+        self.decode(feat, feat_len, use_graph)
+        return self.words(final=True)
 
     def align(self, slots=None, tokens=None):
         """Token times of the streams' hypotheses on the frames they were searched over (slots: only the listed streams, in

@@ -991,6 +991,61 @@ def wfst_search_result(desc, state, graph, final=True, max_words=1, out=None):
     return out
 
 
+# ---- CTC blank-frame skipping in front of the WFST search (m3_wfst_skip_*; m3asr.wfst.CtcWfstSearch(blank_skip=) drives these)
+def wfst_skip_desc(B, V, blank, max_frames, log_blank_thresh):
+    """m3_wfst_skip_desc.  Raises M3Error on a descriptor the library refuses (host-only call)."""
+    d = _lib.WfstSkipDesc(int(B), int(V), int(blank), int(max_frames), float(log_blank_thresh))
+    one = _lib.WfstSkipDesc.from_buffer_copy(d)                        # B = 0 is a valid (empty) size
+    one.B = 1
+    if d.B < 0 or _lib.load().m3_wfst_skip_state_size(C.byref(one)) == 0:
+        raise _lib.M3Error("m3_wfst_skip_state_size failed: " + (_lib.last_error() if d.B >= 0 else "B = %d" % d.B))
+    return d
+
+
+def wfst_skip_state_size(desc):
+    """bytes of device state for desc (host-only call); M3Error on a bad descriptor."""
+    n = _lib.load().m3_wfst_skip_state_size(C.byref(desc))
+    if n == 0 and desc.B > 0:
+        raise _lib.M3Error("m3_wfst_skip_state_size failed: " + _lib.last_error())
+    return n
+
+
+def wfst_skip_reset(desc, state, slots=None):
+    """slots: None = every utterance, else an int32 device tensor."""
+    check(_lib.load().m3_wfst_skip_reset(C.byref(desc), _p(state), state.numel() * state.element_size(), _i32(slots),
+                                         0 if slots is None else slots.numel(), _stream()), "m3_wfst_skip_reset")
+
+
+def wfst_skip_select(desc, state, logp, n_frames, out, n_kept):
+    """logp (B, T_chunk, >= V) and out (B, T_chunk + 1, >= V) float32 device views with unit column stride and dense frames (the
+    row stride is passed as ld / ld_out), n_frames / n_kept (B,) int32 on the device.  Enqueues, no host sync."""
+    B, Tc = logp.shape[0], logp.shape[1]
+    assert B == desc.B and n_frames.numel() == B and n_kept.numel() == B and logp.is_cuda and out.is_cuda
+    assert logp.dtype == torch.float32 and out.dtype == torch.float32 and out.shape[0] == B and out.shape[1] == Tc + 1
+    for t, rows in ((logp, Tc), (out, Tc + 1)):
+        assert t.stride(2) == 1 and (B <= 1 or t.stride(0) == rows * t.stride(1)), "(B, T, V) rows with one leading dimension"
+    check(_lib.load().m3_wfst_skip_select(C.byref(desc), _p(state), state.numel() * state.element_size(),
+                                          C.c_void_p(logp.data_ptr()), logp.stride(1), Tc, _i32(n_frames),
+                                          C.c_void_p(out.data_ptr()), out.stride(1), _i32(n_kept), _stream()), "m3_wfst_skip_select")
+
+
+def wfst_skip_map_frames(desc, state, frames, n_words):
+    """frames (B, ld_frames) int32 in place, n_words (B,) int32, device: decoded frame numbers -> real ones."""
+    assert frames.dim() == 2 and frames.shape[0] == desc.B and n_words.numel() == desc.B
+    check(_lib.load().m3_wfst_skip_map_frames(C.byref(desc), _p(state), state.numel() * state.element_size(), _i32(frames),
+                                              frames.shape[1], _i32(n_words), _stream()), "m3_wfst_skip_map_frames")
+    return frames
+
+
+def wfst_skip_counts(desc, state, out=None):
+    """-> (seen (B,), kept (B,)) int32 on the device: frames seen / emitted since each utterance's reset."""
+    if out is None:
+        out = (torch.empty(desc.B, dtype=torch.int32, device=state.device), torch.empty(desc.B, dtype=torch.int32, device=state.device))
+    check(_lib.load().m3_wfst_skip_counts(C.byref(desc), _p(state), state.numel() * state.element_size(), _i32(out[0]), _i32(out[1]),
+                                          _stream()), "m3_wfst_skip_counts")
+    return out
+
+
 def ctc_greedy_stream_desc(B, max_frames, blank=0):
     d = _lib.CtcGreedyDesc(int(B), int(max_frames), int(blank))
     if _lib.load().m3_ctc_greedy_stream_state_size(C.byref(_lib.CtcGreedyDesc(1, d.max_frames, d.blank))) == 0:

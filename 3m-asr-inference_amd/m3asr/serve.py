@@ -68,6 +68,12 @@ RescoredSegment = collections.namedtuple("RescoredSegment", "rule start_ms end_m
 # posterior inside its span; None when CTC cannot align the hypothesis (m3asr.align).
 TimedSegment = collections.namedtuple("TimedSegment", "rule start_ms end_ms nbest end_frame best scores times")
 
+# The same of a pool with words=True: the five fields of Segment, then what the graph search (m3asr.wfst) found on
+# the segment's frames, read with the graph's final weights: words: word ids; word_ms: where each word's record was made, in
+# SESSION time, (the segment's offset in frames + frame) * frame_ms; cost: the best token's cost; reached_final: whether that
+# token stood on a final state.
+WordSegment = collections.namedtuple("WordSegment", "rule start_ms end_ms nbest end_frame words word_ms cost reached_final")
+
 
 def next_window_valid(buffered, chunks_done, chunk, ended):
     """Real frames in the next window of a stream, or 0 when that window cannot run yet (or never will).
@@ -172,13 +178,26 @@ class StreamPool:
     timestamps=True: token times.  The decoder needs an aligner (`decoder.aligner`, `decoder.align(slots=[...],
     tokens=[...])`) and the pool must segment (the times are session times, frame_ms is the endpoint config's).  All slots whose
     rule fired in a step are aligned by ONE decoder.align call before they are restarted, and segments(sid) hands out
-    TimedSegments; close(sid, timed=True) aligns the open segment."""
+    TimedSegments; close(sid, timed=True) aligns the open segment.
+
+    words=True: graph decoding.  The decoder needs a graph (`decoder.graph`, `decoder.words(slots=[...], final=, detail=)`:
+    StreamingCtcDecoder(..., graph=DecodingGraph(...))).  words(sid) reads the open segment's words and their session times.
+    With segment=True all slots whose rule fired in a step are read by ONE decoder.words(final=True, detail=True) call before
+    any is restarted, segments(sid) hands out WordSegments, and a segment is filed when its best prefix OR its word list is not
+    empty.  Not together with rescore=True or timestamps=True: the second pass needs token hypotheses out of the graph."""
 
     def __init__(self, decoder, B=None, chunk=None, input_dim=None, audio=False, fbank=None, segment=False, max_frames=None,
-                 rescore=False, timestamps=False, sample_rate=16000, channels=1, channel=-1, resampler=None):
+                 rescore=False, timestamps=False, sample_rate=16000, channels=1, channel=-1, resampler=None, words=False):
         self.dec = decoder
         self.rescore = bool(rescore)
         self.timestamps = bool(timestamps)
+        self.with_words = bool(words)
+        if self.with_words and (getattr(decoder, "graph", None) is None or not hasattr(decoder, "words")):
+            raise _lib.M3Error("StreamPool(words=True) needs a decoder with a graph: "
+                               "StreamingCtcDecoder(..., graph=DecodingGraph(...))")
+        if self.with_words and (self.rescore or self.timestamps):
+            raise _lib.M3Error("StreamPool(words=True) does not go with %s=True: the second pass and the aligner need token "
+                               "hypotheses, which the graph search does not give" % ("rescore" if self.rescore else "timestamps"))
         if self.timestamps and (getattr(decoder, "aligner", None) is None or not hasattr(decoder, "align")):
             raise _lib.M3Error("StreamPool(timestamps=True) needs a decoder with an aligner: "
                                "StreamingCtcDecoder(..., aligner=CtcAligner(...))")
@@ -214,6 +233,9 @@ class StreamPool:
                                    "to %d + c = %d > max_frames = %d" % (bound, bound, bound + self.c, int(max_frames)))
             self.offset = {}                     # sid -> output frames of the session before its open segment
             self.finished = {}                   # sid -> [Segment] not handed out yet
+        elif self.with_words:                    # word times of a pool that does not segment: the session is one segment
+            ep = getattr(decoder, "endpoint", None)
+            self.frame_ms = int(ep.frame_ms) if ep is not None else 40
         self.audio = bool(audio)
         self.sample_rate, self.channels, self.channel = int(sample_rate), int(channels), int(channel)
         self.resampled = self.audio and (self.sample_rate, self.channels, self.channel) != (16000, 1, -1)
@@ -362,10 +384,12 @@ class StreamPool:
         if self.timestamps:               # one alignment pass over everything that ended in this step, likewise
             nbests = [self.dec.finish(slots=[b])[0] for _, b, _ in fired]
             times = self._times(fired, nbests, second)
+        # graph decoding: one read of every finished slot's words, likewise
+        found = self.dec.words(slots=[b for _, b, _ in fired], final=True, detail=True) if self.with_words else None
         for j, (sid, b, info) in enumerate(fired):
             nbest = nbests[j] if times is not None else self.dec.finish(slots=[b])[0]
             buf, off = self.streams[sid][1], self.offset[sid]
-            if nbest and len(nbest[0][0]) > 0:
+            if (nbest and len(nbest[0][0]) > 0) or (found is not None and found[j]["words"]):
                 first = info.first_speech if info.first_speech >= 0 else 0
                 last = info.last_speech if info.last_speech >= 0 else info.frame
                 seg = Segment(info.rule, (off + first) * self.frame_ms, (off + last + 1) * self.frame_ms, nbest, off + info.frame)
@@ -373,6 +397,10 @@ class StreamPool:
                     seg = RescoredSegment(*seg, tuple(second[j][0]), second[j][1])
                 if times is not None:
                     seg = TimedSegment(*(tuple(seg) + (None, None))[:7], times[j])
+                if found is not None:
+                    w = found[j]
+                    seg = WordSegment(*seg, list(w["words"]), [(off + f) * self.frame_ms for f in w["frames"]], w["cost"],
+                                      w["reached_final"])
                 self.finished[sid].append(seg)
             self.offset[sid] = off + buf.chunks * self.c
             self.dec.reset(slots=[b])
@@ -493,6 +521,17 @@ class StreamPool:
         b = self.slot_of(sid)
         best, greedy = self.dec.partial(slots=[b])
         return best[0], greedy[0]
+
+    def words(self, sid, final=False):
+        """(word ids, word_ms) of what the graph search has found in the stream so far (segment=True: in its open segment);
+        word_ms in session time, (the open segment's offset in frames + the word's frame) * frame_ms (the endpoint config's,
+        40 without one).  final: the graph's final weights count, as at an utterance's end (words=True)."""
+        b = self.slot_of(sid)
+        if not self.with_words:
+            raise _lib.M3Error("StreamPool.words: this pool does not decode through a graph, build it with words=True")
+        w = self.dec.words(slots=[b], final=final, detail=True)[0]
+        off = self.offset[sid] if self.segment else 0
+        return list(w["words"]), [(off + f) * self.frame_ms for f in w["frames"]]
 
     def close(self, sid, rescored=False, timed=False):
         """n-best [(prefix, score)] of what the stream has decoded (segment=True: of its open segment; read segments(sid)

@@ -12,6 +12,7 @@ OpenFst's job, offline: print the result with fstprint and read it with from_fst
     search = CtcWfstSearch(graph, B, max_frames, beam=16.0, max_active=7000)
     search.advance(logits_chunk, n_frames)                                   # (B, Tc, V) device logits; chunk after chunk
     search.partial(); search.result()                                        # word ids per utterance
+    CtcWfstSearch(graph, B, max_frames, blank_skip=0.98)                     # frames with a sure blank never reach the search
 
 Conventions.  ilabel 0 is epsilon and consumes no frame; ilabel i >= 1 consumes one frame of CTC output id i - 1 (so <blank>
 is ilabel 1 when blank is id 0).  olabel 0 is "no output", olabel >= 1 a word id.  Arc and final weights are float32 costs in
@@ -367,15 +368,31 @@ class CtcWfstSearch:
     log-probabilities.  token_cap: states touched per frame; record_cap: word-history records between resets; max_frames:
     frames between resets -- exceeding one stops that utterance (result() raises, result_tensors() reports n_words = -1 and
     the status).  max_state_bytes: the constructor refuses a configuration whose device state is larger (24 bytes per graph
-    state and utterance, plus the lists)."""
+    state and utterance, plus the lists).
+
+    blank_skip=p, 0 < p < 1: CTC blank-frame skipping (m3_wfst_skip_*).  A frame whose blank posterior is above
+    p is not given to the search (the rule of include/m3asr.h keeps the blank between two equal tokens); the selection runs
+    on the device in front of every advance, carries over from chunk to chunk and is reset with the search.  max_frames then
+    bounds the DECODED frames between resets, the word frames of result() are still real frame numbers, and frames() tells
+    how many frames were seen and decoded.  It is an approximation: costs differ from the unskipped search's and, away from
+    peaked posteriors, words may.  blank: the CTC blank id the rule tests.  None (default): no skipping, nothing is allocated
+    or launched for it."""
 
     def __init__(self, graph, B, max_frames, beam=16.0, max_active=7000, acoustic_scale=1.0, token_cap=None, record_cap=None,
-                 max_state_bytes=1 << 32):
+                 max_state_bytes=1 << 32, blank_skip=None, blank=0):
         import torch
         from . import _lib, ops
         if graph.dev is None:
             raise _lib.M3Error("CtcWfstSearch: the graph is not on a device (graph.to(device))")
         self.graph, self.device = graph, graph.dev.device
+        self.blank_skip, self.skip = None, None
+        if blank_skip is not None:
+            p = float(blank_skip)
+            if not 0.0 < p < 1.0:
+                raise _lib.M3Error("CtcWfstSearch: blank_skip = %r outside (0, 1)" % (blank_skip,))
+            self.blank_skip = p
+            self.log_blank_thresh = float(np.float32(math.log(p)))
+            self.skip = ops.wfst_skip_desc(B, graph.vocab_size, blank, max_frames, self.log_blank_thresh)
         N = graph.n_states
         token_cap = min(N, max(65536, 8 * int(max_active))) if token_cap is None else int(token_cap)
         record_cap = (int(max_frames) + 1) * min(N, 2048) if record_cap is None else int(record_cap)
@@ -390,6 +407,10 @@ class CtcWfstSearch:
                                % (n, self.bytes_per_utterance, N, int(max_state_bytes)))
         self.max_words = max(1, min(record_cap, (int(max_frames) + 1) * graph.n_levels))
         self.state = torch.empty(max(n, 16), dtype=torch.uint8, device=self.device)
+        if self.skip is not None:
+            self.skip_state = torch.empty(max(ops.wfst_skip_state_size(self.skip), 16), dtype=torch.uint8, device=self.device)
+            self.skip_out = torch.empty(0, dtype=torch.float32, device=self.device)     # grown to the largest (Tc + 1) seen
+            self.n_kept = torch.zeros(int(B), dtype=torch.int32, device=self.device)
         self.reset()
 
     @property
@@ -404,6 +425,8 @@ class CtcWfstSearch:
             slots = torch.tensor([int(b) for b in slots], dtype=torch.int32).to(self.device)
         if self.B > 0 and (slots is None or slots.numel() > 0):
             ops.wfst_search_reset(self.desc, self.state, self.graph.dev, slots)
+            if self.skip is not None:
+                ops.wfst_skip_reset(self.skip, self.skip_state, slots)
 
     def advance(self, logits_or_logp, n_frames, log_softmax=True):
         """(B, Tc, V) float32 on the device -- logits (log_softmax=True: m3_log_softmax_bias over the rows first) or
@@ -422,20 +445,43 @@ class CtcWfstSearch:
             x = ops.log_softmax_bias(x.contiguous())
         elif not (x.stride(2) == 1 and x.stride(0) == Tc * x.stride(1)):
             x = x.contiguous()
+        if self.skip is not None:
+            need = B * (Tc + 1) * V
+            if self.skip_out.numel() < need:
+                self.skip_out = torch.empty(need, dtype=torch.float32, device=self.device)
+            kept = self.skip_out[:need].view(B, Tc + 1, V)
+            ops.wfst_skip_select(self.skip, self.skip_state, x, nf, kept, self.n_kept)
+            x, nf = kept, self.n_kept
         ops.wfst_search_advance(self.desc, self.state, self.graph.dev, x, nf)
 
     def result_tensors(self, final=True, out=None):
-        """(words (B, max_words) -1 padded, frames, n_words (B,), cost (B,), reached_final (B,), status (B,)) on the device."""
+        """(words (B, max_words) -1 padded, frames, n_words (B,), cost (B,), reached_final (B,), status (B,)) on the device.
+        With blank_skip the frames are mapped back to real frame numbers (m3_wfst_skip_map_frames)."""
         from . import ops
-        return ops.wfst_search_result(self.desc, self.state, self.graph.dev, final, self.max_words, out)
+        out = ops.wfst_search_result(self.desc, self.state, self.graph.dev, final, self.max_words, out)
+        if self.skip is not None and self.B > 0:
+            ops.wfst_skip_map_frames(self.skip, self.skip_state, out[1], out[2])
+        return out
 
-    def result(self, final=True, detail=False):
-        """Word ids per utterance; detail: a dict per utterance with words, frames (the frame of each word's record: times the
-        frame shift it is a time), cost, reached_final and status.  Raises for an utterance that overflowed a capacity."""
+    def frames(self):
+        """[(seen, decoded)] per utterance since its reset: the frames advance() was given and those the search took (a search
+        with blank_skip; without it the two are equal and nothing counts them: M3Error).  Waits for the device."""
+        from . import _lib, ops
+        if self.skip is None:
+            raise _lib.M3Error("CtcWfstSearch.frames: the search was built without blank_skip")
+        if self.B == 0:
+            return []
+        seen, kept = ops.wfst_skip_counts(self.skip, self.skip_state)
+        return list(zip(seen.cpu().tolist(), kept.cpu().tolist()))
+
+    def result(self, final=True, detail=False, slots=None):
+        """Word ids per utterance (slots: only the listed utterances, in that order); detail: a dict per utterance with words,
+        frames (the frame of each word's record: times the frame shift it is a time), cost, reached_final and status.  Raises
+        for a (listed) utterance that overflowed a capacity."""
         from . import _lib
         words, frames, n_words, cost, flags, status = (t.cpu() for t in self.result_tensors(final))
         out = []
-        for b in range(self.B):
+        for b in (range(self.B) if slots is None else slots):
             n, st = int(n_words[b]), int(status[b])
             if n < 0:
                 why = [name for bit, name in ((TOKEN_CAP, "token_cap = %d" % self.desc.token_cap),
@@ -455,7 +501,7 @@ class CtcWfstSearch:
 
 def wfst_from_logits(logits, lens, graph, **kw):
     """logits (B, T', V) on the graph's device, lens (B,) valid frames per utterance -> word ids per utterance (one-shot
-    CtcWfstSearch; kw: its options, and detail=)."""
+    CtcWfstSearch; kw: its options -- blank_skip= / blank= among them -- and detail=)."""
     detail = kw.pop("detail", False)
     B, T = int(logits.shape[0]), int(logits.shape[1])
     search = CtcWfstSearch(graph, B, max(T, 1), **kw)

@@ -1495,6 +1495,61 @@ int m3_wfst_search_result(const m3_wfst_search_desc* desc, const void* state, si
                           size_t graph_bytes, int final, int max_words, int32_t* words, int32_t* frames, int32_t* n_words,
                           float* cost, int32_t* flags, int32_t* status, m3_stream stream);
 
+/* m3_wfst_skip: CTC blank-frame skipping in front of the graph search (csrc/ctc_wfst_skip.hip; restated on the
+ * host in tests/wfst_skip_ref.py).  The search above costs time in proportion to the frames it is given; a frame whose blank
+ * posterior is near 1 moves no token anywhere but along blank arcs.  These calls choose, on the device, the rows of a chunk
+ * that the search has to see, copy them to a dense buffer for m3_wfst_search_advance, and keep what is needed to go on in the
+ * next chunk and to turn the search's word frames (numbers of DECODED frames) back into real frame numbers.  Skipping is an
+ * approximation: the search's costs and, away from peaked posteriors, its words may differ from the unskipped search's.
+ *
+ * m3_wfst_skip_desc: B utterances, V columns, blank in [0, V), max_frames >= 0 entries of the frame map per utterance,
+ *   log_blank_thresh = log of the blank posterior above which a frame is skipped (a float32; any value but NaN: +inf skips
+ *   nothing).
+ * state: caller-owned device memory, m3_wfst_skip_state_size bytes (0 = bad descriptor, or B = 0), 16-byte aligned.  Per
+ *   utterance, at multiples of the per-utterance size (8 words + V + max_frames words, rounded up to 16 bytes):
+ *     header, 8 int32 words: [0] last_blank  [1] last_best  [2] saved_frame  [3] n_seen  [4] n_kept  [5..7] 0
+ *     saved row [V] float32: the last skipped row, valid while last_blank != 0
+ *     map [max_frames] int32: map[j] = the real frame of the j-th row emitted since the reset
+ *   reset: last_blank = 0, last_best = blank, saved_frame = n_seen = n_kept = 0 for all B utterances (slots NULL) or the n
+ *   listed ones (device int32; an index outside [0, B) is skipped).  The saved row, the map and other utterances' bytes are
+ *   not touched.
+ * The rule.  The frames of an utterance in order, over all calls since its reset; row = the frame's log-probabilities,
+ *   t = n_seen++ its number:
+ *     row[blank] > log_blank_thresh (one float32 comparison in the log domain; false for a NaN): the frame is SKIPPED --
+ *       last_blank = 1, and (row, t) is saved, replacing what was saved.
+ *     otherwise best = the smallest index of the row's maximum, a NaN entry counting as -inf (0 when every entry does).
+ *       If best != blank and last_blank != 0 and best == last_best, the saved row is emitted first, under its own frame
+ *       number: two equal tokens that a blank separated stay two tokens.  Then row is emitted under t, last_best = best,
+ *       last_blank = 0.
+ *   emit (row, frame): the row's V values are copied, bit for bit, to the next row of out[b]; map[n_kept] = frame is stored
+ *     only while n_kept < max_frames; n_kept++ counts on regardless.
+ * select: logp [B][T_chunk][ld] float32 (ld >= V), n_frames[B] frames of each utterance that count, clamped to [0, T_chunk];
+ *   out [B][T_chunk + 1][ld_out] float32 (ld_out >= V; a call emits at most n_frames + 1 rows, the + 1 being a row saved by
+ *   an earlier call; rows behind the emitted ones and columns >= V are not written; out must not overlap logp);
+ *   n_kept[B] = rows emitted by THIS call -- what m3_wfst_search_advance takes as n_frames with out as logp.  When the chunk
+ *   ends with last_blank set by one of its own frames, that row is copied into the state.  One work-group of 1024 threads per
+ *   utterance, one launch, no host sync, capturable.
+ * map_frames: frames [B][ld_frames] int32 in place, n_words[B]: for i < min(n_words[b], ld_frames) a value r becomes map[r]
+ *   when 0 <= r < min(n_kept, max_frames), else n_seen (with nothing seen that is 0, the frame the unskipped search gives a
+ *   word made at reset; with frames seen but none kept it is the number of frames seen).  Other entries, and utterances
+ *   with n_words < 0, are left alone.
+ * counts: seen[B] = n_seen, kept[B] = n_kept (since the reset, over all calls).
+ * Every call refuses, before any launch: a null descriptor, B outside [0, 32768], V outside [1, 2^24], blank outside [0, V),
+ *   max_frames outside [0, 2^28], a NaN threshold, a state that is null, misaligned or too small, a null pointer, ld < V,
+ *   ld_out < V, T_chunk < 0, ld_frames < 0, more slots than B. */
+typedef struct m3_wfst_skip_desc {
+  int32_t B, V, blank, max_frames;
+  float log_blank_thresh;
+} m3_wfst_skip_desc;
+size_t m3_wfst_skip_state_size(const m3_wfst_skip_desc* desc);
+int m3_wfst_skip_reset(const m3_wfst_skip_desc* desc, void* state, size_t state_bytes, const int32_t* slots, int n, m3_stream stream);
+int m3_wfst_skip_select(const m3_wfst_skip_desc* desc, void* state, size_t state_bytes, const float* logp, int ld, int T_chunk,
+                        const int32_t* n_frames, float* out, int ld_out, int32_t* n_kept, m3_stream stream);
+int m3_wfst_skip_map_frames(const m3_wfst_skip_desc* desc, const void* state, size_t state_bytes, int32_t* frames, int ld_frames,
+                            const int32_t* n_words, m3_stream stream);
+int m3_wfst_skip_counts(const m3_wfst_skip_desc* desc, const void* state, size_t state_bytes, int32_t* seen, int32_t* kept,
+                        m3_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

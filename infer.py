@@ -52,10 +52,10 @@ hypothesis is aligned to the forward's CTC output and one line per token follows
 hypothesis that CTC cannot align.  Without the flag nothing is added to the output.
 
     python3 infer.py -p encoder.plan -i feat.npy --wfst graph.txt|graph.npy [--words words.txt] [--wfst-beam 16] [--wfst-max-active 7000]
-                     [--acoustic-scale 1.0]
+                     [--acoustic-scale 1.0] [--wfst-blank-skip P]
 
 WFST decoding (m3asr.wfst): the CTC output is searched through a decoding graph (TLG) on the device and the words
-are printed.  graph.txt is AT&T text with numeric labels, as `fstprint TLG.fst` writes it (ilabel = token id + 1, 0 = epsilon);
+are printed.  --wfst-blank-skip P keeps frames whose blank posterior is above P from the search (DESIGN.md 40; off by default).graph.txt is AT&T text with numeric labels, as `fstprint TLG.fst` writes it (ilabel = token id + 1, 0 = epsilon);
 graph.npy an image saved by DecodingGraph.save (tools/make_lexicon_graph.py writes one from a lexicon).  words.txt (`word id`
 per line) turns the word ids into words.  With --timestamps every word is followed by the time of its record, `<word> <ms>`.
 
@@ -215,7 +215,7 @@ def print_wfst_search(scores, device, args, frame_ms=40):
             raise ValueError("the graph was built for %d tokens, the plan has %d" % (graph.vocab_size, V))
         names = read_words(args.words) if args.words else {}
         out = wfst_from_logits(x, torch.full((B,), T, dtype=torch.int32), graph, beam=args.wfst_beam, max_active=args.wfst_max_active,
-                               acoustic_scale=args.acoustic_scale, detail=True)
+                               acoustic_scale=args.acoustic_scale, blank_skip=args.wfst_blank_skip, detail=True)
     except (ValueError, OSError, M3Error) as e:
         raise SystemExit("--wfst: %s" % e)
     for b, r in enumerate(out):
@@ -395,6 +395,8 @@ if __name__ == "__main__":
     p.add_argument("--wfst-beam", type=float, default=16.0, help="--wfst: the beam, in cost.")
     p.add_argument("--wfst-max-active", type=int, default=7000, help="--wfst: the most tokens expanded per frame.")
     p.add_argument("--acoustic-scale", type=float, default=1.0, help="--wfst: multiplies the log-probabilities.")
+    p.add_argument("--wfst-blank-skip", type=float, default=None, metavar="P",
+                   help="--wfst: skip frames whose blank posterior is above P, 0 < P < 1 (an approximation, DESIGN.md 40); default off.")
     p.add_argument("--vad", action="store_true", help="-w: cut a long recording on the device (energy VAD + segmenter) and decode its segments in batches.")
     p.add_argument("--vad-energy-threshold", type=float, default=5.0, help="--vad: Kaldi's vad-energy-threshold.")
     p.add_argument("--vad-energy-mean-scale", type=float, default=0.5, help="--vad: Kaldi's vad-energy-mean-scale.")

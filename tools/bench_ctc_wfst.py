@@ -4,6 +4,7 @@ over the from_lexicon graph of --words synthetic words, next to the prefix beam 
 logits in the same process, as context.
 
   python tools/bench_ctc_wfst.py [--words 1000] [--batch 16] [--frames 125] [--chunk 16] [--beam 16] [--max-active 7000] [--reps 5]
+                                  [--blank-skip P]
 
 One advance over all frames, and the same frames in chunks of --chunk (one advance per chunk), timed with hipEvents; the
 log-softmax is excluded (one launch, the same for every search).  Run under `rocprofv3 --kernel-trace --stats` for kernel times.
@@ -47,6 +48,9 @@ def main():
     ap.add_argument("--beam", type=float, default=16.0)
     ap.add_argument("--max-active", type=int, default=7000)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--blank-skip", type=float, default=None, metavar="P",
+                    help="also time CtcWfstSearch(blank_skip=P) on the same logits: the share of frames kept, the select launch "
+                         "alone, and the total next to the unskipped search's (DESIGN.md 40)")
     args = ap.parse_args()
     B, T, V = args.batch, args.frames, args.vocab
     rng = np.random.default_rng(0)
@@ -100,6 +104,25 @@ def main():
            "reached_final": int(sum(r["reached_final"] for r in res)),
            "prefix_beam_10_one_advance_ms": round(p_one, 4), "prefix_beam_per_frame_us": round(p_one * 1e3 / T, 2),
            "data": "synthetic"}
+    if args.blank_skip is not None:
+        skip = CtcWfstSearch(graph, B, T, beam=args.beam, max_active=args.max_active, blank_skip=args.blank_skip)
+        s_one = timed(lambda: skip.advance(logp, nf, log_softmax=False), skip.reset)
+        s_res, counts = skip.result(detail=True), skip.frames()
+        s_per = timed(lambda: [skip.advance(a, n, log_softmax=False) for a, n in lpc], skip.reset)
+        assert [r["words"] for r in skip.result(detail=True)] == [r["words"] for r in s_res], "skipped: chunked != one-shot"
+        assert skip.frames() == counts
+        kept_buf, n_kept = torch.empty(B, T + 1, V, dtype=torch.float32, device="cuda"), torch.empty(B, dtype=torch.int32, device="cuda")
+        sel = timed(lambda: ops.wfst_skip_select(skip.skip, skip.skip_state, logp, nf, kept_buf, n_kept),
+                    lambda: ops.wfst_skip_reset(skip.skip, skip.skip_state))
+        seen, kept = sum(c[0] for c in counts), sum(c[1] for c in counts)
+        share = kept / max(seen, 1)
+        out["blank_skip"] = {"p": args.blank_skip, "frames_seen": seen, "frames_decoded": kept, "kept_share": round(share, 4),
+                             "one_advance_ms": round(s_one, 4), "per_frame_us": round(s_one * 1e3 / T, 2),
+                             "select_ms": round(sel, 4), "unskipped_one_advance_ms": round(one, 4),
+                             "predicted_ms": round(share * one + sel, 4),
+                             "chunked_ms": {"chunk": args.chunk, "total": round(s_per, 4), "per_advance": round(s_per / len(chunks), 4)},
+                             "same_words_as_unskipped": int(sum(a["words"] == b["words"] for a, b in zip(s_res, res))),
+                             "reached_final": int(sum(r["reached_final"] for r in s_res))}
     print(json.dumps(out))
 
 
