@@ -598,6 +598,116 @@ int m3_conv2d_3x3s2_ws(const float* in, const float* w, const float* bias, int B
   return launch_gemm(gemm_launch(p, (float*)workspace, workspace_bytes), (hipStream_t)stream);
 }
 
+// ---- the packed-row and bf16-row operand forms at the boundary (include/m3asr.h): the record the engine fills, checked as the
+// single entry of the operator checks it, one launcher call
+static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+int m3_pack_plan(int32_t* len, int B, int T, int32_t* row0, int32_t* pad_of, const int32_t* feat_len, m3_stream stream) {
+  M3_REQUIRE(len && row0 && pad_of, "pack_plan: null len / row0 / pad_of");
+  M3_REQUIRE(aligned4(len) && aligned4(row0) && aligned4(pad_of) && aligned4(feat_len), "pack_plan: every operand must be 4-byte aligned");
+  return launch_pack_plan(len, B, T, row0, pad_of, (hipStream_t)stream, feat_len);
+}
+int m3_unpack_rows(const float* in, const int32_t* row0, int B, int T, int n, float* out, m3_stream stream) {
+  M3_REQUIRE(B >= 0 && T >= 0 && n >= 1, "unpack_rows: bad sizes B=%d T=%d n=%d", B, T, n);
+  M3_REQUIRE((long)B * T == 0 || (in && row0 && out), "unpack_rows: null in / row0 / out");
+  M3_REQUIRE(aligned4(in) && aligned4(row0) && aligned4(out), "unpack_rows: every operand must be 4-byte aligned");
+  return launch_unpack_rows(in, row0, B, T, n, out, (hipStream_t)stream);
+}
+int m3_linear_live_rows(const m3_linear_desc* d, const int32_t* live_rows_dev, void* workspace, size_t workspace_bytes, m3_stream stream) {
+  GemmParams p;
+  if (int rc = linear_params(d, &p)) return rc;
+  if (int rc = linear_pointers(d)) return rc;
+  M3_REQUIRE(live_rows_dev != nullptr && aligned4(live_rows_dev), "linear (live rows): live_rows_dev must be a 4-byte aligned device pointer");
+  p.m_dev = live_rows_dev;
+  return launch_gemm(gemm_launch(p, (float*)workspace, workspace_bytes), (hipStream_t)stream);
+}
+const char* m3_linear_live_rows_kernel(const m3_linear_desc* d, int with_workspace) { return m3_linear_kernel(d, with_workspace); }
+int m3_moe_router_live_rows(const float* embed, int ld_embed, int embed_dim, const float* x, int ldx, int idim, const float* w,
+                            const float* bias, const float* ln_gamma, const float* ln_beta, float ln_eps, float* xn, int ld_xn,
+                            float* logits, int ld_logits, int S, int num_expert, const int32_t* live_rows_dev, m3_stream stream) {
+  M3_REQUIRE(S <= 1 || (ld_embed >= embed_dim && ldx >= idim), "moe_router (live rows): ld_embed=%d / ldx=%d shorter than the rows (%d / %d)",
+             ld_embed, ldx, embed_dim, idim);
+  M3_REQUIRE(S <= 1 || xn == nullptr || ld_xn >= idim, "moe_router (live rows): ld_xn=%d is shorter than a row of %d", ld_xn, idim);
+  M3_REQUIRE(S <= 1 || ld_logits >= num_expert, "moe_router (live rows): ld_logits=%d is shorter than a row of %d", ld_logits, num_expert);
+  M3_REQUIRE(aligned16(embed) && aligned16(x) && aligned16(xn), "moe_router (live rows): embed / x / xn must be 16-byte aligned");
+  M3_REQUIRE(live_rows_dev != nullptr && aligned4(live_rows_dev), "moe_router (live rows): live_rows_dev must be a 4-byte aligned device pointer");
+  return launch_moe_router(embed, ld_embed, embed_dim, x, ldx, idim, w, bias, ln_gamma, ln_beta, ln_eps, xn, ld_xn, logits, ld_logits, S,
+                           num_expert, live_rows_dev, (hipStream_t)stream);
+}
+static int conv2d_frames_params(const float* in, const void* w, const float* bias, int B, int T1, int F1, int C, int act, int w_bf16, float* out,
+                                GemmParams* q) {
+  M3_REQUIRE(B > 0 && C > 0, "conv2d (frames): empty problem B=%d C=%d", B, C);
+  if (int rc = conv2d_params(in, (const float*)w, bias, B, T1, F1, C, act, out, q)) return rc;
+  q->w_bf16 = w_bf16 != 0;
+  return 0;
+}
+int m3_conv2d_3x3s2_frames(const float* in, const void* w, const float* bias, int B, int T1, int F1, int C, int act,
+                           const int32_t* frames_dev, int w_bf16, float* out, m3_stream stream) {
+  GemmParams p;
+  if (int rc = conv2d_frames_params(in, w, bias, B, T1, F1, C, act, w_bf16, out, &p)) return rc;
+  M3_REQUIRE(in && w && out, "conv2d (frames): null in / w / out");
+  M3_REQUIRE(aligned16(in) && aligned16(w) && aligned16(out) && aligned4(frames_dev), "conv2d (frames): in / w / out must be 16-byte, frames_dev 4-byte aligned");
+  p.conv_len = frames_dev;
+  return launch_gemm(gemm_launch(p, nullptr, 0), (hipStream_t)stream);
+}
+const char* m3_conv2d_3x3s2_kernel(int B, int T1, int F1, int C, int act, int w_bf16, int with_workspace) {
+  GemmParams p;
+  if (conv2d_frames_params(nullptr, nullptr, nullptr, B, T1, F1, C, act, w_bf16, nullptr, &p)) return nullptr;
+  const GemmPlan plan = plan_gemm(p, with_workspace ? SIZE_MAX : 0);
+  if (plan.launches == 0) set_error("%s", plan.reason);
+  return plan.launches ? plan.label : nullptr;
+}
+static int attention_packed(const char* who, const m3_attention_desc* d, const int32_t* row0, int out_bf16, int rows_bf16, m3_stream stream) {
+  M3_REQUIRE(d != nullptr, "%s: null descriptor", who);
+  M3_REQUIRE(d->B > 0 && d->T > 0 && d->H > 0 && d->dk > 0, "%s: empty problem", who);
+  AttArgs a;
+  if (int rc = attention_args_from_desc(d, who, -1, &a)) return rc;
+  M3_REQUIRE(row0 == nullptr || d->len != nullptr, "%s: packed rows (row0) need len", who);
+  M3_REQUIRE(aligned4(row0) && aligned4(d->len), "%s: row0 / len must be 4-byte aligned", who);
+  a.row0 = row0; a.out_bf16 = out_bf16 != 0; a.rows_bf16 = rows_bf16;
+  return launch_relpos_attention(a, (hipStream_t)stream);
+}
+int m3_relpos_attention_packed(const m3_attention_desc* d, const int32_t* row0, int out_bf16, m3_stream stream) {
+  return attention_packed("attention (packed)", d, row0, out_bf16, 0, stream);
+}
+int m3_relpos_attention_bf16_packed(const m3_attention_desc* d, const int32_t* row0, m3_stream stream) {
+  return attention_packed("attention (bf16 rows, packed)", d, row0, 0, 1, stream);
+}
+int m3_dwconv_ln_silu_packed(const m3_dwconv_desc* d, const int32_t* pad_of, const int32_t* row0, const int32_t* row_len, int out_bf16,
+                             m3_stream stream) {
+  M3_REQUIRE(d != nullptr, "dwconv (packed): null descriptor");
+  DwArgs a;
+  if (int rc = dwconv_args_from_desc(d, "dwconv (packed)", "z", 0, true, &a)) return rc;
+  M3_REQUIRE((pad_of != nullptr) == (row0 != nullptr) && (pad_of != nullptr) == (row_len != nullptr),
+             "dwconv (packed): pad_of, row0 and row_len go together (all three, or none for the padded layout)");
+  M3_REQUIRE(aligned4(pad_of) && aligned4(row0) && aligned4(row_len), "dwconv (packed): pad_of / row0 / row_len must be 4-byte aligned");
+  a.pad_of = pad_of; a.row0 = row0; a.row_len = row_len; a.out_bf16 = out_bf16 != 0;
+  return launch_dwconv_ln_silu(a, (hipStream_t)stream);
+}
+int m3_layer_norm_ex(const float* x, const float* gamma, const float* beta, float eps, float* y, int rows, int dim, void* y_bf16,
+                     float* y_stats, const float* gamma2, const float* beta2, float eps2, float* y2, m3_stream stream) {
+  M3_REQUIRE(rows >= 0 && dim > 0, "layer_norm_ex: bad sizes rows=%d dim=%d", rows, dim);
+  M3_REQUIRE(rows == 0 || (x && gamma && beta && y), "layer_norm_ex: null x / gamma / beta / y");
+  M3_REQUIRE(y_stats == nullptr || y_bf16 != nullptr, "layer_norm_ex: y_stats are the statistics of y_bf16, which is null");
+  M3_REQUIRE((gamma2 != nullptr) == (beta2 != nullptr) && (gamma2 != nullptr) == (y2 != nullptr),
+             "layer_norm_ex: the second LayerNorm needs gamma2, beta2 and y2 (all three, or none)");
+  M3_REQUIRE(aligned16(x) && aligned16(gamma) && aligned16(beta) && aligned16(y) && aligned16(y_bf16) && aligned16(y_stats) &&
+             aligned16(gamma2) && aligned16(beta2) && aligned16(y2), "layer_norm_ex: every operand must be 16-byte aligned");
+  return launch_layernorm(x, gamma, beta, eps, y, rows, dim, (hipStream_t)stream, y_bf16, y_stats, gamma2, beta2, eps2, y2);
+}
+int m3_row_stats_bf16(const void* xb, int rows, int dim, float* stats, m3_stream stream) {
+  M3_REQUIRE(rows >= 0 && dim > 0, "row_stats_bf16: bad sizes rows=%d dim=%d", rows, dim);
+  M3_REQUIRE(rows == 0 || (xb && stats), "row_stats_bf16: null xb / stats");
+  M3_REQUIRE(aligned16(xb) && aligned16(stats), "row_stats_bf16: xb / stats must be 16-byte aligned");
+  return launch_row_stats_bf16(xb, rows, dim, stats, (hipStream_t)stream);
+}
+int m3_rows_to_bf16(const float* x, int ldx, int S, int dim, void* xb, m3_stream stream) {
+  M3_REQUIRE(S >= 0 && dim > 0, "rows_to_bf16: bad sizes S=%d dim=%d", S, dim);
+  M3_REQUIRE(S == 0 || (x && xb), "rows_to_bf16: null x / xb");
+  M3_REQUIRE(S <= 1 || ldx >= dim, "rows_to_bf16: ldx=%d is shorter than a row of %d", ldx, dim);
+  M3_REQUIRE(aligned16(x) && (reinterpret_cast<uintptr_t>(xb) & 7) == 0, "rows_to_bf16: x must be 16-byte, xb 8-byte aligned");
+  return launch_rows_to_bf16(x, ldx, S, dim, xb, (hipStream_t)stream);
+}
+
 // ---- the paired launches at the boundary (include/m3asr.h): both problems checked as their single entries check them, outputs
 // apart, one launcher call
 static bool ranges_overlap(const void* a, size_t bytes_a, const void* b, size_t bytes_b) {

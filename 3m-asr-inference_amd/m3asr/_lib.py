@@ -216,6 +216,19 @@ SIGNATURES = {
     "m3_subsample_conv1_pair": (_i, [_P(Conv1Desc), _P(Conv1Desc), _vp]),
     "m3_subsample_conv1_ch": (_i, [_P(Conv1ChDesc), _vp]),
     "m3_subsample_conv1_ch_pair": (_i, [_P(Conv1ChDesc), _P(Conv1ChDesc), _vp]),
+    "m3_pack_plan": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "m3_unpack_rows": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "m3_linear_live_rows": (_i, [_P(LinearDesc), _vp, _vp, _sz, _vp]),
+    "m3_linear_live_rows_kernel": (C.c_char_p, [_P(LinearDesc), _i]),
+    "m3_moe_router_live_rows": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _i, _vp, _i, _i, _i, _vp, _vp]),
+    "m3_conv2d_3x3s2_frames": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "m3_conv2d_3x3s2_kernel": (C.c_char_p, [_i, _i, _i, _i, _i, _i, _i]),
+    "m3_relpos_attention_packed": (_i, [_P(AttentionDesc), _vp, _i, _vp]),
+    "m3_relpos_attention_bf16_packed": (_i, [_P(AttentionDesc), _vp, _vp]),
+    "m3_dwconv_ln_silu_packed": (_i, [_P(DwconvDesc), _vp, _vp, _vp, _i, _vp]),
+    "m3_layer_norm_ex": (_i, [_vp, _vp, _vp, _f, _vp, _i, _i, _vp, _vp, _vp, _vp, _f, _vp, _vp]),
+    "m3_row_stats_bf16": (_i, [_vp, _i, _i, _vp, _vp]),
+    "m3_rows_to_bf16": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "m3_conv2d_3x3s2_first": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "m3_conv2d_3x3s2": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "m3_layer_norm": (_i, [_vp, _vp, _vp, _f, _vp, _i, _i, _vp]),

@@ -185,9 +185,10 @@ def moe_combine(rows, mapping, gate_value=None, resid=None, alpha=1.0, ln=None, 
     return y
 
 
-def moe_router(embed, x, w, ln, bias=None, want_xn=True, out=None, xn_out=None):
+def moe_router(embed, x, w, ln, bias=None, want_xn=True, out=None, xn_out=None, live_rows=None):
     """logits (S, E) = cat([embed, LayerNorm(x)]) @ w^T (+ bias), xn = LayerNorm(x); w (E, De + D) fp32, ln = (gamma, beta, eps).
-    embed / x and the optional result buffers out (S, E) / xn_out (S, D) may be row-strided views."""
+    embed / x and the optional result buffers out (S, E) / xn_out (S, D) may be row-strided views.
+    live_rows: one int32 on the device, the count of live rows of a packed ragged batch (m3_moe_router_live_rows)."""
     lib = _lib.load()
     S, De = embed.shape
     D = x.shape[1]
@@ -198,6 +199,10 @@ def moe_router(embed, x, w, ln, bias=None, want_xn=True, out=None, xn_out=None):
     assert tuple(logits.shape) == (S, E) and (xn is None or tuple(xn.shape) == (S, D))
     (ep, lde), (xp, ldx), (lp, ldl) = _rows(embed), _rows(x), _rows(logits)
     xnp, ldxn = _rows(xn) if xn is not None else (None, D)
+    if live_rows is not None:
+        check(lib.m3_moe_router_live_rows(ep, lde, De, xp, ldx, D, _f32(w), _f32(bias), _f32(ln[0]), _f32(ln[1]), float(ln[2]),
+                                          xnp, ldxn, lp, ldl, S, E, _i32(live_rows), _stream()), "m3_moe_router_live_rows")
+        return logits, xn
     check(lib.m3_moe_router(ep, lde, De, xp, ldx, D, _f32(w), _f32(bias), _f32(ln[0]), _f32(ln[1]), float(ln[2]),
                             xnp, ldxn, lp, ldl, S, E, _stream()), "m3_moe_router")
     return logits, xn
@@ -292,7 +297,7 @@ def moe_route_expert_ffn(x, logits, w1, b1, w2, b2, row_len=None, rows_per_batch
 # ---------------------------------------------------------------------------------------- dense
 def linear(a, w, bias=None, act=_lib.ACT_NONE, a2=None, ln=None, lens=None, rows_per_batch=0, mask_in=False,
            mask_out=False, alpha=1.0, resid=None, out=None, ln_folded=None, split_k=False, out_dtype=torch.float32,
-           copy_bf16=None, copy_stats=None, ln_stats=None, workspace=None, _kernel_only=False, _desc_only=False):
+           copy_bf16=None, copy_stats=None, ln_stats=None, workspace=None, live_rows=None, _kernel_only=False, _desc_only=False):
     """y = resid + alpha * mask_out(act(LN(mask_in(cat[a,a2])) @ w^T + bias)); a (M,K1), w (N,K).
     ln = (gamma, beta, eps): affine LayerNorm prologue.  ln_folded = (wsum, wbeta or None, eps): w / bias already
     contain the LayerNorm affine (plan.fold_layernorm) and the kernel normalises its output.
@@ -301,7 +306,8 @@ def linear(a, w, bias=None, act=_lib.ACT_NONE, a2=None, ln=None, lens=None, rows
     ln_stats (M, parts, 2): such statistics of a bf16 `a`, which the folded LayerNorm then uses.
     a, a2, y (= out), resid and copy_bf16 may be row-strided views (unit column stride); their row strides go to the ABI.
     workspace (split_k only): caller-owned uint8 scratch of at least m3_linear_workspace_size bytes.
-    A 5-D w (N/16, K/16, 4, 16, 4) is taken as fragment-ordered (plan.pack_wfrag) and runs m3_linear_wfrag."""
+    A 5-D w (N/16, K/16, 4, 16, 4) is taken as fragment-ordered (plan.pack_wfrag) and runs m3_linear_wfrag.
+    live_rows: one int32 on the device, the count of live rows of a packed ragged batch (m3_linear_live_rows)."""
     lib = _lib.load()
     M, K1 = a.shape
     wfrag = w.dim() == 5
@@ -354,8 +360,18 @@ def linear(a, w, bias=None, act=_lib.ACT_NONE, a2=None, ln=None, lens=None, rows
     if _desc_only:
         return d, y
     if _kernel_only:
-        name = lib.m3_linear_wfrag_kernel(C.byref(d)) if wfrag else lib.m3_linear_kernel(C.byref(d), int(bool(split_k)))
+        if live_rows is not None:
+            assert not wfrag
+            name = lib.m3_linear_live_rows_kernel(C.byref(d), int(bool(split_k)))
+        else:
+            name = lib.m3_linear_wfrag_kernel(C.byref(d)) if wfrag else lib.m3_linear_kernel(C.byref(d), int(bool(split_k)))
         return name.decode() if name else None
+    if live_rows is not None:
+        assert not wfrag and live_rows.numel() == 1
+        need = lib.m3_linear_workspace_size(C.byref(d)) if split_k else 0
+        ws = workspace if workspace is not None else (torch.empty(max(need, 1), dtype=torch.uint8, device=a.device) if split_k else None)
+        check(lib.m3_linear_live_rows(C.byref(d), _i32(live_rows), _p(ws), need, _stream()), "m3_linear_live_rows")
+        return y
     if wfrag:
         check(lib.m3_linear_wfrag(C.byref(d), _stream()), "m3_linear_wfrag")
         return y
@@ -1623,6 +1639,117 @@ def subsample_conv2(x, w, bias, act=_lib.ACT_RELU):
     out = torch.empty(B, T2, F2, Cc, dtype=torch.float32, device=x.device)
     check(lib.m3_conv2d_3x3s2(_f32(x), _f32(w), _f32(bias), B, T1, F1, Cc, int(act), _p(out), _stream()),
           "m3_conv2d_3x3s2")
+    return out
+
+
+# ---- the packed-row and bf16-row operand forms (include/m3asr.h "Packed rows")
+def pack_plan(lens, T, feat_len=None, row0=None, pad_of=None):
+    """row plan of a ragged batch (m3_pack_plan): lens (B,) int32 -> row0 (B + 1,), pad_of (B * T,).  feat_len (B,) int32: lens is
+    an output too (the subsampled lengths)."""
+    B = lens.numel()
+    row0 = row0 if row0 is not None else torch.empty(B + 1, dtype=torch.int32, device=lens.device)
+    pad_of = pad_of if pad_of is not None else torch.empty(B * T, dtype=torch.int32, device=lens.device)
+    assert row0.numel() == B + 1 and pad_of.numel() == B * T and (feat_len is None or feat_len.numel() == B)
+    check(_lib.load().m3_pack_plan(_i32(lens), B, T, _i32(row0), _i32(pad_of), _i32(feat_len), _stream()), "m3_pack_plan")
+    return row0, pad_of
+
+
+def unpack_rows(rows, row0, B, T, out=None):
+    """padded (B * T, n) <- packed rows (P, n) (m3_unpack_rows): zeros behind every utterance's last frame"""
+    n = rows.shape[1]
+    if out is None:
+        out = torch.empty(B * T, n, dtype=torch.float32, device=rows.device)
+    assert tuple(out.shape) == (B * T, n) and row0.numel() == B + 1
+    check(_lib.load().m3_unpack_rows(_f32(rows), _i32(row0), B, T, n, _f32(out), _stream()), "m3_unpack_rows")
+    return out
+
+
+def conv2d_kernel(B, T1, F1, Cc, act=_lib.ACT_RELU, w_bf16=False, with_workspace=False):
+    """name of the device kernel the 3x3 / stride-2 conv runs for a shape (host-only query, m3_conv2d_3x3s2_kernel); None if refused"""
+    name = _lib.load().m3_conv2d_3x3s2_kernel(B, T1, F1, Cc, int(act), int(bool(w_bf16)), int(bool(with_workspace)))
+    return name.decode() if name else None
+
+
+def conv2d_frames(x, w, bias, frames=None, act=_lib.ACT_RELU, out=None):
+    """subsample_conv2 with the valid output frames per utterance on the device (m3_conv2d_3x3s2_frames); w fp32 or bf16"""
+    B, T1, F1, Cc = x.shape
+    if out is None:
+        out = torch.empty(B, (T1 - 3) // 2 + 1, (F1 - 3) // 2 + 1, Cc, dtype=torch.float32, device=x.device)
+    assert w.dtype in (torch.float32, torch.bfloat16)
+    check(_lib.load().m3_conv2d_3x3s2_frames(_f32(x), _p(w), _f32(bias), B, T1, F1, Cc, int(act), _i32(frames),
+                                             int(w.dtype == torch.bfloat16), _f32(out), _stream()), "m3_conv2d_3x3s2_frames")
+    return out
+
+
+def relpos_attention_packed(qkv, p, pos_u, pos_v, lens, B, T, H, dk, out, row0=None, chunk=0, left_chunks=-1):
+    """the attention core on packed rows (m3_relpos_attention_packed; m3_relpos_attention_bf16_packed for a bf16 qkv): qkv
+    (rows, 3 * H * dk) and out (rows, H * dk) hold the packed rows of the plan row0 (None: the B * T padded rows); a bf16 out on
+    fp32 rows asks for the rounded copy (out_bf16)."""
+    lib = _lib.load()
+    D = H * dk
+    assert qkv.shape[1] == 3 * D and out.shape[1] == D and p.shape[1] == D and p.shape[0] >= T
+    d = _lib.AttentionDesc()
+    (d.qkv, d.ldq), (d.p, d.ldp), (d.out, d.ldo) = [(q.value, ld) for q, ld in (_rows(qkv, qkv.dtype), _rows(p), _rows(out, out.dtype))]
+    d.pos_u, d.pos_v, d.len = _f32(pos_u).value, _f32(pos_v).value, (_i32(lens).value if lens is not None else None)
+    d.B, d.T, d.H, d.dk, d.scale, d.chunk, d.left_chunks = B, T, H, dk, 1.0 / math.sqrt(dk), int(chunk), int(left_chunks)
+    if qkv.dtype == torch.bfloat16:
+        assert out.dtype == torch.bfloat16
+        check(lib.m3_relpos_attention_bf16_packed(C.byref(d), _i32(row0), _stream()), "m3_relpos_attention_bf16_packed")
+    else:
+        check(lib.m3_relpos_attention_packed(C.byref(d), _i32(row0), int(out.dtype == torch.bfloat16), _stream()), "m3_relpos_attention_packed")
+    return out
+
+
+def dwconv_ln_silu_packed(z, w_kc, bias, gamma, beta, eps, B, T, out, plan=None, left_fill=None, glu=False, gate_sigmoided=False):
+    """the depthwise conv on packed rows (m3_dwconv_ln_silu_packed).  plan = (pad_of, row0, lens) of pack_plan, None: the padded
+    layout.  z: the packed rows and the pad row behind them; glu: value | gate rows (may be row-strided).  out (rows, D) fp32, or
+    bf16 for the rounded result."""
+    K, D = w_kc.shape
+    d = _lib.DwconvDesc()
+    if glu:
+        assert z.shape[1] == 2 * D
+        zp, d.ldz = _rows(z)
+        d.z = zp.value
+    else:
+        d.z = _f32(z).value
+    d.gate_sigmoided = int(bool(gate_sigmoided))
+    d.w_kc, d.bias, d.out = _f32(w_kc).value, _f32(bias).value, _p(out).value
+    d.gamma, d.beta = (_f32(gamma).value if gamma is not None else None), (_f32(beta).value if beta is not None else None)
+    d.left_fill = _f32(left_fill).value if left_fill is not None else None
+    d.eps, d.B, d.T, d.D, d.K = float(eps), B, T, D, K
+    pad_of, row0, lens = plan if plan is not None else (None, None, None)
+    check(_lib.load().m3_dwconv_ln_silu_packed(C.byref(d), _i32(pad_of), _i32(row0), _i32(lens), int(out.dtype == torch.bfloat16), _stream()),
+          "m3_dwconv_ln_silu_packed")
+    return out
+
+
+def layer_norm_ex(x, gamma, beta, eps, y=None, y_bf16=None, y_stats=None, ln2=None, y2=None):
+    """layer_norm with its side results (m3_layer_norm_ex): y_bf16 the rounded copy, y_stats (rows, 4, 2) its row statistics,
+    ln2 = (gamma2, beta2, eps2) with y2 = LN2(y).  y may be x."""
+    D = x.shape[-1]
+    y = y if y is not None else torch.empty_like(x)
+    g2, b2, e2 = ln2 if ln2 is not None else (None, None, 0.0)
+    check(_lib.load().m3_layer_norm_ex(_f32(x), _f32(gamma), _f32(beta), float(eps), _f32(y), x.numel() // D, D, _p(y_bf16), _f32(y_stats),
+                                       _f32(g2), _f32(b2), float(e2), _f32(y2), _stream()), "m3_layer_norm_ex")
+    return y
+
+
+def row_stats_bf16(xb, stats=None):
+    """(sum, sum of squares) of every row of a dense bf16 matrix -> (rows, 4, 2), total in part 0 (m3_row_stats_bf16)"""
+    rows, D = xb.shape
+    assert xb.dtype == torch.bfloat16
+    stats = stats if stats is not None else torch.empty(rows, 4, 2, dtype=torch.float32, device=xb.device)
+    check(_lib.load().m3_row_stats_bf16(_p(xb), rows, D, _f32(stats), _stream()), "m3_row_stats_bf16")
+    return stats
+
+
+def rows_to_bf16(x, out=None):
+    """dense bf16 copy of the fp32 rows x (may be a row-strided view) (m3_rows_to_bf16)"""
+    S, D = x.shape
+    out = out if out is not None else torch.empty(S, D, dtype=torch.bfloat16, device=x.device)
+    assert out.dtype == torch.bfloat16 and tuple(out.shape) == (S, D)
+    xp, ldx = _rows(x)
+    check(_lib.load().m3_rows_to_bf16(xp, ldx, S, D, _p(out), _stream()), "m3_rows_to_bf16")
     return out
 
 

@@ -517,6 +517,71 @@ typedef struct m3_conv1_ch_desc {
 int m3_subsample_conv1_ch(const m3_conv1_ch_desc* d, m3_stream stream);
 int m3_subsample_conv1_ch_pair(const m3_conv1_ch_desc* a, const m3_conv1_ch_desc* b, m3_stream stream);
 
+/* The packed-row and bf16-row operand forms of the block kernels (what the engine runs on ragged batches, packed_rows, and in
+ * the 16-bit modes of long batches), exposed so that they can be tested at the boundary (additions only;
+ * tests/test_packed_forms_gpu.py).  Each entry fills the record the engine fills and makes ONE call of the launcher the single
+ * entry of its operator makes: no new kernel, no new decision.
+ *
+ * Packed rows.  A ragged batch of B utterances with len[b] valid frames out of T keeps its live frames back to back: utterance
+ * b owns rows [row0[b], row0[b] + min(max(len[b], 0), T)), P = row0[B] rows in all (a device value), and pad_of[p] = b T + t
+ * names the padded row of packed row p (-1 for P <= p < B T).
+ * m3_pack_plan: len [B] -> row0 [B + 1], pad_of [B * T]; one work-group, 1 <= B <= 1024, T >= 1.  feat_len != NULL: len is an
+ * OUTPUT too, len[b] = ((feat_len[b] - 3) / 2 + 1 - 3) / 2 + 1 in C int arithmetic (as m3_subsample_conv1_pair writes lens_out),
+ * stored as computed; the clamp to [0, T] applies to the rows alone.
+ * m3_unpack_rows: out [B * T][n] dense <- in [P][n] dense: out[b T + t] = in[row0[b] + t] for t < row0[b + 1] - row0[b], zeros
+ * beyond.  n >= 1, any value (element copies). */
+int m3_pack_plan(int32_t* len, int B, int T, int32_t* row0, int32_t* pad_of, const int32_t* feat_len, m3_stream stream);
+int m3_unpack_rows(const float* in, const int32_t* row0, int B, int T, int n, float* out, m3_stream stream);
+/* m3_linear_live_rows: m3_linear_ws with a device-side count of live rows, *live_rows_dev = P (0 <= P <= M).  Work-groups whose
+ * first row lies beyond P exit: rows 0 .. P (the row AT the count included) hold what m3_linear_ws gives, bit for bit, and
+ * every later row either holds that too or is left unwritten -- from the first multiple of the kernel's row tile (16 .. 128
+ * rows) above P on, unwritten.  Rows up to M must exist in every operand all the same (their loads may be requested).  The
+ * split-K form (a workspace of m3_linear_workspace_size bytes) computes every row.  live_rows_dev: 4-byte aligned, not NULL.
+ * m3_linear_live_rows_kernel: host only, as m3_linear_kernel (the count does not change the choice). */
+int m3_linear_live_rows(const m3_linear_desc* desc, const int32_t* live_rows_dev, void* workspace, size_t workspace_bytes,
+                        m3_stream stream);
+const char* m3_linear_live_rows_kernel(const m3_linear_desc* desc, int with_workspace);
+/* m3_moe_router_live_rows: m3_moe_router with such a count; its row tile has 16 rows. */
+int m3_moe_router_live_rows(const float* embed, int ld_embed, int embed_dim, const float* x, int ldx, int idim, const float* w,
+                            const float* bias, const float* ln_gamma, const float* ln_beta, float ln_eps, float* xn, int ld_xn,
+                            float* logits, int ld_logits, int S, int num_expert, const int32_t* live_rows_dev, m3_stream stream);
+/* m3_conv2d_3x3s2_frames: m3_conv2d_3x3s2 (w_bf16 != 0: w holds bf16, C a multiple of 32) with frames_dev [B], the valid OUTPUT
+ * frames per utterance (device int32; NULL: every frame).  The rows (b, t2, f2) with t2 < frames_dev[b] hold what the call
+ * without frames_dev gives, bit for bit; a row tile of the LDS-tiled kernels that lies inside one utterance and starts at a frame
+ * t2 >= frames_dev[b] is left unwritten (the other kernels of the family compute every row).  in / w / out 16-byte aligned.
+ * m3_conv2d_3x3s2_kernel: host only, the name of the kernel the conv runs (with_workspace: as m3_linear_kernel), NULL with the
+ * reason in m3_last_error() for a shape the family does not take. */
+int m3_conv2d_3x3s2_frames(const float* in, const void* w, const float* bias, int B, int T1, int F1, int C, int act,
+                           const int32_t* frames_dev, int w_bf16, float* out, m3_stream stream);
+const char* m3_conv2d_3x3s2_kernel(int B, int T1, int F1, int C, int act, int w_bf16, int with_workspace);
+/* m3_relpos_attention_packed: m3_relpos_attention_chunk on packed rows.  desc as m3_relpos_attention_pair takes it (len not
+ * NULL); with row0 [B + 1] (m3_pack_plan) qkv and out hold the P packed rows, utterance b at rows row0[b] ..., and nothing past
+ * an utterance's last frame is read or written; row0 NULL: the padded layout.  out_bf16 != 0: out receives bf16 ([rows][ldo],
+ * ldo in elements), the bf16 rounding of the fp32 result.  Strides as m3_relpos_attention.
+ * m3_relpos_attention_bf16_packed: m3_relpos_attention_bf16 likewise (desc->qkv and desc->out point at bf16 rows; T <= 128). */
+int m3_relpos_attention_packed(const m3_attention_desc* desc, const int32_t* row0, int out_bf16, m3_stream stream);
+int m3_relpos_attention_bf16_packed(const m3_attention_desc* desc, const int32_t* row0, m3_stream stream);
+/* m3_dwconv_ln_silu_packed: the depthwise conv of m3_dwconv_ln_silu_pair's descriptor (one problem; ldz, gate_sigmoided and
+ * left_fill as there) on packed rows.  pad_of / row0 / row_len (= len) as m3_pack_plan leaves them, all three or none (none:
+ * the padded layout).  z holds the P packed rows AND, at row P, the pad row: what every frame len[b] <= t < T of the padded
+ * layout holds (taps outside [0, T) are the conv's zeros, or left_fill on the left of the causal form), so z has P + 1 rows
+ * (B T + 1 when every frame is live); out [P][D] dense, rows at and past P are not written.  out_bf16 != 0: out receives bf16
+ * (not with ldz > 0).  Every operand 16-byte aligned. */
+int m3_dwconv_ln_silu_packed(const m3_dwconv_desc* desc, const int32_t* pad_of, const int32_t* row0, const int32_t* row_len,
+                             int out_bf16, m3_stream stream);
+/* m3_layer_norm_ex: m3_layer_norm (dim a multiple of 4, <= 2048; y may alias x) with its optional side results, each NULL or
+ * given: y_bf16 [rows][dim] the bf16 rounding of y; y_stats [rows][4][2] (needs y_bf16) the (sum, sum of squares) of the bf16
+ * values of a row in part 0 and zeros in parts 1 .. 3 (the ln_stats operand of m3_linear_desc, ln_stat_parts = 4); gamma2 /
+ * beta2 / eps2 / y2: a second LayerNorm of the fp32 values y holds, y2 = LN2(y), in the same launch (all of gamma2, beta2, y2
+ * or none).  Every operand dense and 16-byte aligned.
+ * m3_row_stats_bf16: such statistics of a dense bf16 matrix xb [rows][dim], dim a multiple of 8.
+ * m3_rows_to_bf16: xb [S][dim] dense bf16 <- x [S][ldx] fp32, round to nearest even; dim a multiple of 4, ldx >= dim a multiple
+ * of 4; x 16-byte, xb 8-byte aligned. */
+int m3_layer_norm_ex(const float* x, const float* gamma, const float* beta, float eps, float* y, int rows, int dim, void* y_bf16,
+                     float* y_stats, const float* gamma2, const float* beta2, float eps2, float* y2, m3_stream stream);
+int m3_row_stats_bf16(const void* xb, int rows, int dim, float* stats, m3_stream stream);
+int m3_rows_to_bf16(const float* x, int ldx, int S, int dim, void* xb, m3_stream stream);
+
 /* Front / back end of the acoustic score.  Global CMVN: y = (x - mean[d]) * istd[d] on frames
  * t < len[b] (the reference's unfinished CmvnPlugin, incomplete_plugin/cmvn_plugin/cmvn_plugin.cu:17-43).
  * Score: y = log_softmax(x) + bias per row, bias = -log(prior) (builder.py:77-88, prior_prob_kernel.cu:11-26). */

@@ -15,8 +15,9 @@ LayerNorm (m3_linear has no ln_on_a2, so the affine LayerNorm next to a concat i
 reachable) and the affine LayerNorm on plain rows; bf16 `a` at 4095 / 4096 rows (M3_DMA_MIN_ROWS), with the folded LayerNorm
 with and without ln_stats, below 384 rows (no kernel), fp32 `a` at 4096 rows; y_copy_stats below the LDS-DMA threshold; split-K
 at K = 4096 / 4032, 160 / 176 tiles, N % 4 != 0, a residual, bf16 weights, each with and without a workspace; the model's own
-B = 1 rows (M = 50).  The implicit-conv path (m3_conv2d_3x3s2) has no host-only query: its rows are left to the GPU tier
-(tests/test_kernels_gpu.py, tests/test_strided_operands_gpu.py)."""
+B = 1 rows (M = 50).  The implicit-conv path is not in this table (its rows were left to the GPU tier when the table was
+made, tests/test_kernels_gpu.py, tests/test_strided_operands_gpu.py); its host-only query, m3_conv2d_3x3s2_kernel, is pinned in
+tests/test_packed_forms_host.py."""
 import ctypes as C
 
 import pytest
