@@ -77,6 +77,20 @@ using namespace m3;
 
 static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }   // (NULL counts as aligned)
 
+// The prefix beam search's entry points say which form they are, fill a BeamCall (kernels.h) and call.
+static BeamCall beam_call(const char* who, BeamForm form, const m3_ctc_beam_desc* d, const void* state, size_t bytes, m3_stream stream) {
+  BeamCall c{};
+  c.who = who; c.form = form; c.d = d; c.state = const_cast<void*>(state); c.bytes = bytes; c.stream = (hipStream_t)stream;
+  return c;
+}
+// *_reset_slots on a *_reset record: an empty list is no work, whatever else stands in the call
+static int beam_reset_slots(BeamCall c, const int32_t* slots, int n) {
+  M3_REQUIRE(n == 0 || slots != nullptr, "%s_slots: null slot list", c.who);
+  if (n == 0) return 0;
+  c.slots = slots; c.n = n;
+  return beam_reset(c);
+}
+
 extern "C" {
 
 int m3_abi_version(void) { return M3ASR_ABI_VERSION; }
@@ -865,22 +879,78 @@ int m3_ctc_prefix_beam_search(const float* top_logp, const int32_t* top_idx, int
                               int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score, int32_t* n_hyps) {
   return ctc_prefix_beam_search_host(top_logp, top_idx, T, k, beam, blank, hyp_tokens, hyp_len, hyp_score, n_hyps);
 }
-size_t m3_ctc_beam_state_size(const m3_ctc_beam_desc* desc) { return ctc_beam_state_size(desc); }
+// ---- the device prefix beam search: plain, biased (ctx), fused (lm)
+size_t m3_ctc_beam_state_size(const m3_ctc_beam_desc* desc) { return beam_state_need(desc, BeamForm::Plain); }
+size_t m3_ctc_beam_ctx_state_size(const m3_ctc_beam_desc* desc) { return beam_state_need(desc, BeamForm::Ctx); }
+size_t m3_ctc_beam_lm_state_size(const m3_ctc_beam_desc* desc) { return beam_state_need(desc, BeamForm::Lm); }
 int m3_ctc_beam_reset(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, m3_stream stream) {
-  return launch_ctc_beam_reset(desc, state, state_bytes, (hipStream_t)stream);
+  return beam_reset(beam_call("ctc_beam_reset", BeamForm::Plain, desc, state, state_bytes, stream));
+}
+int m3_ctc_beam_ctx_reset(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, m3_stream stream) {
+  return beam_reset(beam_call("ctc_beam_ctx_reset", BeamForm::Ctx, desc, state, state_bytes, stream));
+}
+int m3_ctc_beam_lm_reset(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, m3_stream stream) {
+  return beam_reset(beam_call("ctc_beam_lm_reset", BeamForm::Lm, desc, state, state_bytes, stream));
 }
 int m3_ctc_beam_reset_slots(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const int32_t* slots, int n, m3_stream stream) {
-  M3_REQUIRE(n == 0 || slots != nullptr, "ctc_beam_reset_slots: null slot list");
-  if (n == 0) return 0;
-  return launch_ctc_beam_reset(desc, state, state_bytes, (hipStream_t)stream, slots, n);
+  return beam_reset_slots(beam_call("ctc_beam_reset", BeamForm::Plain, desc, state, state_bytes, stream), slots, n);
+}
+int m3_ctc_beam_ctx_reset_slots(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const int32_t* slots, int n,
+                                m3_stream stream) {
+  return beam_reset_slots(beam_call("ctc_beam_ctx_reset", BeamForm::Ctx, desc, state, state_bytes, stream), slots, n);
+}
+int m3_ctc_beam_lm_reset_slots(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const int32_t* slots, int n,
+                               m3_stream stream) {
+  return beam_reset_slots(beam_call("ctc_beam_lm_reset", BeamForm::Lm, desc, state, state_bytes, stream), slots, n);
 }
 int m3_ctc_beam_advance(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const float* top_logp,
                         const int32_t* top_idx, int T_chunk, const int32_t* n_frames, m3_stream stream) {
-  return launch_ctc_beam_advance(desc, state, state_bytes, top_logp, top_idx, T_chunk, n_frames, (hipStream_t)stream);
+  BeamCall c = beam_call("ctc_beam_advance", BeamForm::Plain, desc, state, state_bytes, stream);
+  c.top_logp = top_logp; c.top_idx = top_idx; c.T_chunk = T_chunk; c.n_frames = n_frames;
+  return beam_advance(c);
+}
+int m3_ctc_beam_ctx_advance(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const void* image, size_t image_bytes,
+                            const int32_t* graph_of, const float* top_logp, const int32_t* top_idx, int T_chunk,
+                            const int32_t* n_frames, m3_stream stream) {
+  BeamCall c = beam_call("ctc_beam_ctx_advance", BeamForm::Ctx, desc, state, state_bytes, stream);
+  c.image = image; c.image_bytes = image_bytes; c.graph_of = graph_of;
+  c.top_logp = top_logp; c.top_idx = top_idx; c.T_chunk = T_chunk; c.n_frames = n_frames;
+  return beam_advance(c);
+}
+int m3_ctc_beam_lm_advance(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const void* image, size_t image_bytes,
+                           const int32_t* graph_of, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha,
+                           double beta, const float* top_logp, const int32_t* top_idx, int T_chunk, const int32_t* n_frames,
+                           m3_stream stream) {
+  BeamCall c = beam_call("ctc_beam_lm_advance", BeamForm::Lm, desc, state, state_bytes, stream);
+  c.image = image; c.image_bytes = image_bytes; c.graph_of = graph_of;
+  c.lm_image = lm_image; c.lm_bytes = lm_bytes; c.lm_on = lm_on; c.alpha = alpha; c.beta = beta;
+  c.top_logp = top_logp; c.top_idx = top_idx; c.T_chunk = T_chunk; c.n_frames = n_frames;
+  return beam_advance(c);
 }
 int m3_ctc_beam_nbest(const m3_ctc_beam_desc* desc, const void* state, size_t state_bytes, int32_t* hyp_tokens,
                       int32_t* hyp_len, float* hyp_score, int32_t* n_hyps, m3_stream stream) {
-  return launch_ctc_beam_nbest(desc, state, state_bytes, hyp_tokens, hyp_len, hyp_score, n_hyps, (hipStream_t)stream);
+  BeamCall c = beam_call("ctc_beam_nbest", BeamForm::Plain, desc, state, state_bytes, stream);
+  c.hyp_tokens = hyp_tokens; c.hyp_len = hyp_len; c.hyp_score = hyp_score; c.n_hyps = n_hyps;
+  return beam_nbest(c);
+}
+int m3_ctc_beam_ctx_nbest(const m3_ctc_beam_desc* desc, const void* state, size_t state_bytes, const void* image,
+                          size_t image_bytes, const int32_t* graph_of, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score,
+                          float* hyp_bonus, int32_t* n_hyps, m3_stream stream) {
+  BeamCall c = beam_call("ctc_beam_ctx_nbest", BeamForm::Ctx, desc, state, state_bytes, stream);
+  c.image = image; c.image_bytes = image_bytes; c.graph_of = graph_of;
+  c.hyp_tokens = hyp_tokens; c.hyp_len = hyp_len; c.hyp_score = hyp_score; c.hyp_bonus = hyp_bonus; c.n_hyps = n_hyps;
+  return beam_nbest(c);
+}
+int m3_ctc_beam_lm_nbest(const m3_ctc_beam_desc* desc, const void* state, size_t state_bytes, const void* image, size_t image_bytes,
+                         const int32_t* graph_of, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha,
+                         double beta, int use_eos, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score, float* hyp_bonus,
+                         float* hyp_lm, int32_t* n_hyps, m3_stream stream) {
+  BeamCall c = beam_call("ctc_beam_lm_nbest", BeamForm::Lm, desc, state, state_bytes, stream);
+  c.image = image; c.image_bytes = image_bytes; c.graph_of = graph_of;
+  c.lm_image = lm_image; c.lm_bytes = lm_bytes; c.lm_on = lm_on; c.alpha = alpha; c.beta = beta; c.use_eos = use_eos;
+  c.hyp_tokens = hyp_tokens; c.hyp_len = hyp_len; c.hyp_score = hyp_score; c.hyp_bonus = hyp_bonus; c.hyp_lm = hyp_lm;
+  c.n_hyps = n_hyps;
+  return beam_nbest(c);
 }
 size_t m3_ctc_align_workspace_size(const m3_ctc_align_desc* desc) { return ctc_align_workspace_size(desc); }
 int m3_ctc_align_emit(const m3_ctc_align_desc* desc, const float* logits, int ldl, const int32_t* row0, const int32_t* n_frames,
@@ -900,28 +970,6 @@ int m3_ctc_prefix_beam_search_ctx(const float* top_logp, const int32_t* top_idx,
   return ctc_prefix_beam_search_ctx_host(top_logp, top_idx, T, k, beam, blank, image, image_bytes, graph, hyp_tokens, hyp_len,
                                          hyp_score, hyp_bonus, hyp_state, n_hyps);
 }
-size_t m3_ctc_beam_ctx_state_size(const m3_ctc_beam_desc* desc) { return ctc_beam_ctx_state_size(desc); }
-int m3_ctc_beam_ctx_reset(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, m3_stream stream) {
-  return launch_ctc_beam_ctx_reset(desc, state, state_bytes, (hipStream_t)stream);
-}
-int m3_ctc_beam_ctx_reset_slots(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const int32_t* slots, int n,
-                                m3_stream stream) {
-  M3_REQUIRE(n == 0 || slots != nullptr, "ctc_beam_ctx_reset_slots: null slot list");
-  if (n == 0) return 0;
-  return launch_ctc_beam_ctx_reset(desc, state, state_bytes, (hipStream_t)stream, slots, n);
-}
-int m3_ctc_beam_ctx_advance(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const void* image, size_t image_bytes,
-                            const int32_t* graph_of, const float* top_logp, const int32_t* top_idx, int T_chunk,
-                            const int32_t* n_frames, m3_stream stream) {
-  return launch_ctc_beam_ctx_advance(desc, state, state_bytes, image, image_bytes, graph_of, top_logp, top_idx, T_chunk, n_frames,
-                                     (hipStream_t)stream);
-}
-int m3_ctc_beam_ctx_nbest(const m3_ctc_beam_desc* desc, const void* state, size_t state_bytes, const void* image,
-                          size_t image_bytes, const int32_t* graph_of, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score,
-                          float* hyp_bonus, int32_t* n_hyps, m3_stream stream) {
-  return launch_ctc_beam_ctx_nbest(desc, state, state_bytes, image, image_bytes, graph_of, hyp_tokens, hyp_len, hyp_score,
-                                   hyp_bonus, n_hyps, (hipStream_t)stream);
-}
 int m3_ctc_lm_validate(const void* image, size_t image_bytes, int V) { return ctc_lm_validate(image, image_bytes, V); }
 int m3_ctc_ngram_set_member(const void* image, size_t image_bytes, int j, const void** member, size_t* member_bytes, float* scale) {
   return ctc_lm_set_member(image, image_bytes, j, member, member_bytes, scale);
@@ -932,30 +980,6 @@ int m3_ctc_prefix_beam_search_lm(const float* top_logp, const int32_t* top_idx, 
                                  float* hyp_bonus, int32_t* hyp_state, float* hyp_lm, int32_t* n_hyps) {
   return ctc_prefix_beam_search_lm_host(top_logp, top_idx, T, k, beam, blank, image, image_bytes, graph, lm_image, lm_bytes, alpha,
                                         beta, use_eos, hyp_tokens, hyp_len, hyp_score, hyp_bonus, hyp_state, hyp_lm, n_hyps);
-}
-size_t m3_ctc_beam_lm_state_size(const m3_ctc_beam_desc* desc) { return ctc_beam_lm_state_size(desc); }
-int m3_ctc_beam_lm_reset(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, m3_stream stream) {
-  return launch_ctc_beam_lm_reset(desc, state, state_bytes, (hipStream_t)stream);
-}
-int m3_ctc_beam_lm_reset_slots(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const int32_t* slots, int n,
-                               m3_stream stream) {
-  M3_REQUIRE(n == 0 || slots != nullptr, "ctc_beam_lm_reset_slots: null slot list");
-  if (n == 0) return 0;
-  return launch_ctc_beam_lm_reset(desc, state, state_bytes, (hipStream_t)stream, slots, n);
-}
-int m3_ctc_beam_lm_advance(const m3_ctc_beam_desc* desc, void* state, size_t state_bytes, const void* image, size_t image_bytes,
-                           const int32_t* graph_of, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha,
-                           double beta, const float* top_logp, const int32_t* top_idx, int T_chunk, const int32_t* n_frames,
-                           m3_stream stream) {
-  return launch_ctc_beam_lm_advance(desc, state, state_bytes, image, image_bytes, graph_of, lm_image, lm_bytes, lm_on, alpha, beta,
-                                    top_logp, top_idx, T_chunk, n_frames, (hipStream_t)stream);
-}
-int m3_ctc_beam_lm_nbest(const m3_ctc_beam_desc* desc, const void* state, size_t state_bytes, const void* image, size_t image_bytes,
-                         const int32_t* graph_of, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha,
-                         double beta, int use_eos, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score, float* hyp_bonus,
-                         float* hyp_lm, int32_t* n_hyps, m3_stream stream) {
-  return launch_ctc_beam_lm_nbest(desc, state, state_bytes, image, image_bytes, graph_of, lm_image, lm_bytes, lm_on, alpha, beta,
-                                  use_eos, hyp_tokens, hyp_len, hyp_score, hyp_bonus, hyp_lm, n_hyps, (hipStream_t)stream);
 }
 int m3_wfst_validate(const void* image, size_t image_bytes, int V) { return wfst_validate(image, image_bytes, V); }
 size_t m3_wfst_search_state_size(const m3_wfst_search_desc* desc) { return wfst_search_state_size(desc); }

@@ -890,78 +890,19 @@ __global__ __launch_bounds__(256) void ctc_endpoint_read_kernel(const int32_t* _
   if (i < n) info[i] = state[i];
 }
 
-}  // namespace
+// ---------------------------------------------------------------- the host half of the prefix beam search
+// An entry point (api.hip) says which form it is and fills a BeamCall; check_call holds every rule of the twelve launching entry
+// points in the order each of them had, and beam_reset / beam_advance / beam_nbest hold the launches.
 
-size_t ctc_beam_state_size(const m3_ctc_beam_desc* d) {
-  if (check_beam_desc(d)) return 0;
-  return (size_t)d->B * beam_layout(d->beam, d->max_frames).stride;
+// bytes of state: the B slices; behind them (Ctx) a context block per utterance; behind those (Lm) an LM block per utterance
+size_t state_need(const m3_ctc_beam_desc& d, BeamForm form) {
+  const BeamLayout L = beam_layout(d.beam, d.max_frames);
+  if (form == BeamForm::Plain) return (size_t)d.B * L.stride;
+  const CtxLayout last = form == BeamForm::Ctx ? ctx_layout(L, d.B) : lm_layout(L, d.B);
+  return last.base + (size_t)d.B * last.stride;
 }
 
-int launch_ctc_beam_reset(const m3_ctc_beam_desc* d, void* state, size_t bytes, hipStream_t stream, const int32_t* slots, int n) {
-  if (int rc = check_beam_desc(d)) return rc;
-  M3_REQUIRE(n >= 0 && (slots != nullptr || n == 0), "ctc_beam_reset: bad slot list");
-  if (slots != nullptr && n == 0) return 0;
-  const BeamLayout L = beam_layout(d->beam, d->max_frames);
-  M3_REQUIRE(state != nullptr && bytes >= (size_t)d->B * L.stride, "ctc_beam_reset: state %zu bytes < required %zu", bytes,
-             (size_t)d->B * L.stride);
-  if (d->B == 0) return 0;
-  const unsigned gx = (unsigned)std::min((L.hcap + 255) / 256, 64);
-  hipLaunchKernelGGL(ctc_beam_reset_kernel, dim3(gx, slots ? n : d->B), dim3(256), 0, stream, L, (char*)state, slots, d->B);
-  M3_LAUNCH_CHECK();
-  return 0;
-}
-
-int launch_ctc_beam_advance(const m3_ctc_beam_desc* d, void* state, size_t bytes, const float* top_logp, const int32_t* top_idx,
-                            int T_chunk, const int32_t* n_frames, hipStream_t stream) {
-  if (int rc = check_beam_desc(d)) return rc;
-  const BeamLayout L = beam_layout(d->beam, d->max_frames);
-  M3_REQUIRE(state != nullptr && bytes >= (size_t)d->B * L.stride, "ctc_beam_advance: state %zu bytes < required %zu", bytes,
-             (size_t)d->B * L.stride);
-  M3_REQUIRE(T_chunk >= 0, "ctc_beam_advance: T_chunk = %d < 0", T_chunk);
-  if (d->B == 0 || T_chunk == 0) return 0;
-  M3_REQUIRE(top_logp && top_idx && n_frames, "ctc_beam_advance: null pointer");
-  hipLaunchKernelGGL((ctc_beam_advance_kernel<false, NoCtx>), dim3(d->B), dim3(kBeamThreads), 0, stream, L, d->beam, d->k,
-                     d->blank, d->max_frames, (char*)state, top_logp, top_idx, T_chunk, n_frames, NoCtx{});
-  M3_LAUNCH_CHECK();
-  return 0;
-}
-
-int launch_ctc_beam_nbest(const m3_ctc_beam_desc* d, const void* state, size_t bytes, int32_t* hyp_tokens, int32_t* hyp_len,
-                          float* hyp_score, int32_t* n_hyps, hipStream_t stream) {
-  if (int rc = check_beam_desc(d)) return rc;
-  const BeamLayout L = beam_layout(d->beam, d->max_frames);
-  M3_REQUIRE(state != nullptr && bytes >= (size_t)d->B * L.stride, "ctc_beam_nbest: state %zu bytes < required %zu", bytes,
-             (size_t)d->B * L.stride);
-  if (d->B == 0) return 0;
-  M3_REQUIRE(hyp_len && hyp_score && n_hyps && (hyp_tokens || d->max_frames == 0), "ctc_beam_nbest: null pointer");
-  hipLaunchKernelGGL(ctc_beam_nbest_kernel, dim3(d->B), dim3(64), 0, stream, L, d->beam, d->max_frames, (const char*)state,
-                     hyp_tokens, hyp_len, hyp_score, n_hyps);
-  M3_LAUNCH_CHECK();
-  return 0;
-}
-
-size_t ctc_beam_ctx_state_size(const m3_ctc_beam_desc* d) {
-  if (check_beam_desc(d)) return 0;
-  const BeamLayout L = beam_layout(d->beam, d->max_frames);
-  const CtxLayout C = ctx_layout(L, d->B);
-  return C.base + (size_t)d->B * C.stride;
-}
-
-int launch_ctc_beam_ctx_reset(const m3_ctc_beam_desc* d, void* state, size_t bytes, hipStream_t stream, const int32_t* slots,
-                              int n) {
-  if (int rc = check_beam_desc(d)) return rc;
-  const size_t need = ctc_beam_ctx_state_size(d);
-  M3_REQUIRE(state != nullptr && bytes >= need, "ctc_beam_ctx_reset: state %zu bytes < required %zu", bytes, need);
-  if (int rc = launch_ctc_beam_reset(d, state, bytes, stream, slots, n)) return rc;
-  if (d->B == 0 || (slots != nullptr && n == 0)) return 0;
-  const int cnt = slots ? n : d->B;
-  hipLaunchKernelGGL(ctc_beam_ctx_reset_kernel, dim3((cnt + 255) / 256), dim3(256), 0, stream,
-                     ctx_layout(beam_layout(d->beam, d->max_frames), d->B), (char*)state, slots, d->B, cnt);
-  M3_LAUNCH_CHECK();
-  return 0;
-}
-
-static int check_ctx_image(const char* who, const void* image, size_t image_bytes, const int32_t* graph_of) {
+int check_ctx_image(const char* who, const void* image, size_t image_bytes, const int32_t* graph_of) {
   M3_REQUIRE(graph_of != nullptr, "%s: null graph_of", who);
   M3_REQUIRE(image != nullptr || image_bytes == 0, "%s: null image of %zu bytes", who, image_bytes);
   M3_REQUIRE(image_bytes % 4 == 0 && image_bytes <= kCtxMaxBytes && (image == nullptr || image_bytes >= CTX_HDR_WORDS * 4),
@@ -969,62 +910,7 @@ static int check_ctx_image(const char* who, const void* image, size_t image_byte
   return 0;
 }
 
-int launch_ctc_beam_ctx_advance(const m3_ctc_beam_desc* d, void* state, size_t bytes, const void* image, size_t image_bytes,
-                                const int32_t* graph_of, const float* top_logp, const int32_t* top_idx, int T_chunk,
-                                const int32_t* n_frames, hipStream_t stream) {
-  if (int rc = check_beam_desc(d)) return rc;
-  const size_t need = ctc_beam_ctx_state_size(d);
-  M3_REQUIRE(state != nullptr && bytes >= need, "ctc_beam_ctx_advance: state %zu bytes < required %zu", bytes, need);
-  M3_REQUIRE(T_chunk >= 0, "ctc_beam_ctx_advance: T_chunk = %d < 0", T_chunk);
-  if (d->B == 0 || T_chunk == 0) return 0;
-  M3_REQUIRE(top_logp && top_idx && n_frames, "ctc_beam_ctx_advance: null pointer");
-  if (int rc = check_ctx_image("ctc_beam_ctx_advance", image, image_bytes, graph_of)) return rc;
-  const BeamLayout L = beam_layout(d->beam, d->max_frames);
-  const CtxArgs cx{ctx_layout(L, d->B), (const int32_t*)image, (long long)(image_bytes / 4), graph_of};
-  hipLaunchKernelGGL((ctc_beam_advance_kernel<true, CtxArgs>), dim3(d->B), dim3(kBeamThreads), 0, stream, L, d->beam, d->k,
-                     d->blank, d->max_frames, (char*)state, top_logp, top_idx, T_chunk, n_frames, cx);
-  M3_LAUNCH_CHECK();
-  return 0;
-}
-
-int launch_ctc_beam_ctx_nbest(const m3_ctc_beam_desc* d, const void* state, size_t bytes, const void* image, size_t image_bytes,
-                              const int32_t* graph_of, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score,
-                              float* hyp_bonus, int32_t* n_hyps, hipStream_t stream) {
-  if (int rc = check_beam_desc(d)) return rc;
-  const size_t need = ctc_beam_ctx_state_size(d);
-  M3_REQUIRE(state != nullptr && bytes >= need, "ctc_beam_ctx_nbest: state %zu bytes < required %zu", bytes, need);
-  if (d->B == 0) return 0;
-  M3_REQUIRE(hyp_len && hyp_score && hyp_bonus && n_hyps && (hyp_tokens || d->max_frames == 0), "ctc_beam_ctx_nbest: null pointer");
-  if (int rc = check_ctx_image("ctc_beam_ctx_nbest", image, image_bytes, graph_of)) return rc;
-  const BeamLayout L = beam_layout(d->beam, d->max_frames);
-  hipLaunchKernelGGL((ctc_beam_ctx_nbest_kernel<false, NoLm>), dim3(d->B), dim3(64), 0, stream, L, ctx_layout(L, d->B), d->beam,
-                     d->max_frames, (const char*)state, (const int32_t*)image, (long long)(image_bytes / 4), graph_of, hyp_tokens,
-                     hyp_len, hyp_score, hyp_bonus, n_hyps, NoLm{});
-  M3_LAUNCH_CHECK();
-  return 0;
-}
-
-size_t ctc_beam_lm_state_size(const m3_ctc_beam_desc* d) {
-  if (check_beam_desc(d)) return 0;
-  const CtxLayout M = lm_layout(beam_layout(d->beam, d->max_frames), d->B);
-  return M.base + (size_t)d->B * M.stride;
-}
-
-int launch_ctc_beam_lm_reset(const m3_ctc_beam_desc* d, void* state, size_t bytes, hipStream_t stream, const int32_t* slots,
-                             int n) {
-  if (int rc = check_beam_desc(d)) return rc;
-  const size_t need = ctc_beam_lm_state_size(d);
-  M3_REQUIRE(state != nullptr && bytes >= need, "ctc_beam_lm_reset: state %zu bytes < required %zu", bytes, need);
-  if (int rc = launch_ctc_beam_ctx_reset(d, state, bytes, stream, slots, n)) return rc;
-  if (d->B == 0 || (slots != nullptr && n == 0)) return 0;
-  const int cnt = slots ? n : d->B;              // the root's (LM state, LM sum): the context block's kernel on the LM blocks
-  hipLaunchKernelGGL(ctc_beam_ctx_reset_kernel, dim3((cnt + 255) / 256), dim3(256), 0, stream,
-                     lm_layout(beam_layout(d->beam, d->max_frames), d->B), (char*)state, slots, d->B, cnt);
-  M3_LAUNCH_CHECK();
-  return 0;
-}
-
-static int check_lm_image(const char* who, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha, double beta) {
+int check_lm_image(const char* who, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha, double beta) {
   M3_REQUIRE(lm_on != nullptr, "%s: null lm_on", who);
   M3_REQUIRE(lm_image != nullptr || lm_bytes == 0, "%s: null LM image of %zu bytes", who, lm_bytes);
   // a single image or a set: which one only the device copy says, so the bound is the set's
@@ -1034,54 +920,120 @@ static int check_lm_image(const char* who, const void* lm_image, size_t lm_bytes
   return 0;
 }
 
-int launch_ctc_beam_lm_advance(const m3_ctc_beam_desc* d, void* state, size_t bytes, const void* image, size_t image_bytes,
-                               const int32_t* graph_of, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha,
-                               double beta, const float* top_logp, const int32_t* top_idx, int T_chunk, const int32_t* n_frames,
-                               hipStream_t stream) {
-  if (int rc = check_beam_desc(d)) return rc;
-  const size_t need = ctc_beam_lm_state_size(d);
-  M3_REQUIRE(state != nullptr && bytes >= need, "ctc_beam_lm_advance: state %zu bytes < required %zu", bytes, need);
-  M3_REQUIRE(T_chunk >= 0, "ctc_beam_lm_advance: T_chunk = %d < 0", T_chunk);
-  if (d->B == 0 || T_chunk == 0) return 0;
-  M3_REQUIRE(top_logp && top_idx && n_frames, "ctc_beam_lm_advance: null pointer");
-  if (int rc = check_ctx_image("ctc_beam_lm_advance", image, image_bytes, graph_of)) return rc;
-  if (int rc = check_lm_image("ctc_beam_lm_advance", lm_image, lm_bytes, lm_on, alpha, beta)) return rc;
-  const BeamLayout L = beam_layout(d->beam, d->max_frames);
-  LmArgs cx;
-  cx.C = ctx_layout(L, d->B);
-  cx.image = (const int32_t*)image;
-  cx.words = (long long)(image_bytes / 4);
-  cx.graph_of = graph_of;
-  cx.M = lm_layout(L, d->B);
-  cx.lm = (const int32_t*)lm_image;
-  cx.lm_words = (long long)(lm_bytes / 4);
-  cx.lm_on = lm_on;
-  cx.alpha = alpha;
-  cx.beta = beta;
-  hipLaunchKernelGGL((ctc_beam_advance_kernel<true, LmArgs, true>), dim3(d->B), dim3(kBeamThreads), 0, stream, L, d->beam, d->k,
-                     d->blank, d->max_frames, (char*)state, top_logp, top_idx, T_chunk, n_frames, cx);
+enum class BeamOp { Reset, Advance, Nbest };
+constexpr int kLaunch = 1;
+// < 0: refused; 0: nothing to do (no utterance, no frame, an empty slot list); kLaunch: go on.
+// The order and the words are the exports' (tests/test_ctc_beam_refusals_host.py pins them).  Two of them are not what one would
+// write today: the plain reset looks at the slot list before the state, the biased and the fused reset at their state first; and
+// all three refuse a bad slot list in the plain reset's name.
+int check_call(const BeamCall& c, BeamOp op) {
+  if (int rc = check_beam_desc(c.d)) return rc;
+  const m3_ctc_beam_desc& d = *c.d;
+  const bool ctx = c.form != BeamForm::Plain, lm = c.form == BeamForm::Lm;
+  const bool slots_ok = c.n >= 0 && (c.slots != nullptr || c.n == 0);
+  if (op == BeamOp::Reset && !ctx) M3_REQUIRE(slots_ok, "ctc_beam_reset: bad slot list");
+  const size_t need = state_need(d, c.form);
+  M3_REQUIRE(c.state != nullptr && c.bytes >= need, "%s: state %zu bytes < required %zu", c.who, c.bytes, need);
+  if (op == BeamOp::Reset) M3_REQUIRE(slots_ok, "ctc_beam_reset: bad slot list");
+  if (op == BeamOp::Advance) M3_REQUIRE(c.T_chunk >= 0, "%s: T_chunk = %d < 0", c.who, c.T_chunk);
+  if (d.B == 0 || (op == BeamOp::Advance && c.T_chunk == 0) || (op == BeamOp::Reset && c.slots != nullptr && c.n == 0)) return 0;
+  if (op == BeamOp::Reset) return kLaunch;
+  if (op == BeamOp::Advance) M3_REQUIRE(c.top_logp && c.top_idx && c.n_frames, "%s: null pointer", c.who);
+  if (op == BeamOp::Nbest)
+    M3_REQUIRE(c.hyp_len && c.hyp_score && (c.hyp_bonus || !ctx) && (c.hyp_lm || !lm) && c.n_hyps && (c.hyp_tokens || d.max_frames == 0),
+               "%s: null pointer", c.who);
+  if (ctx)
+    if (int rc = check_ctx_image(c.who, c.image, c.image_bytes, c.graph_of)) return rc;
+  if (lm)
+    if (int rc = check_lm_image(c.who, c.lm_image, c.lm_bytes, c.lm_on, c.alpha, c.beta)) return rc;
+  return kLaunch;
+}
+
+}  // namespace
+
+size_t beam_state_need(const m3_ctc_beam_desc* d, BeamForm form) { return check_beam_desc(d) ? 0 : state_need(*d, form); }
+
+int beam_reset(const BeamCall& c) {
+  const int rc = check_call(c, BeamOp::Reset);
+  if (rc != kLaunch) return rc;
+  const m3_ctc_beam_desc& d = *c.d;
+  const BeamLayout L = beam_layout(d.beam, d.max_frames);
+  const int cnt = c.slots ? c.n : d.B;
+  const unsigned gx = (unsigned)std::min((L.hcap + 255) / 256, 64);
+  hipLaunchKernelGGL(ctc_beam_reset_kernel, dim3(gx, cnt), dim3(256), 0, c.stream, L, (char*)c.state, c.slots, d.B);
+  M3_LAUNCH_CHECK();
+  // the root's (context state, bonus), then its (LM state, LM sum): the context block's kernel, on the LM blocks too
+  const CtxLayout blocks[2] = {ctx_layout(L, d.B), lm_layout(L, d.B)};
+  const int n_blocks = c.form == BeamForm::Plain ? 0 : c.form == BeamForm::Ctx ? 1 : 2;
+  for (int i = 0; i < n_blocks; ++i) {
+    hipLaunchKernelGGL(ctc_beam_ctx_reset_kernel, dim3((cnt + 255) / 256), dim3(256), 0, c.stream, blocks[i], (char*)c.state, c.slots,
+                       d.B, cnt);
+    M3_LAUNCH_CHECK();
+  }
+  return 0;
+}
+
+int beam_advance(const BeamCall& c) {
+  const int rc = check_call(c, BeamOp::Advance);
+  if (rc != kLaunch) return rc;
+  const m3_ctc_beam_desc& d = *c.d;
+  const BeamLayout L = beam_layout(d.beam, d.max_frames);
+  LmArgs cx;                                      // the biased form takes the CtxArgs in it
+  cx.C = ctx_layout(L, d.B);
+  cx.image = (const int32_t*)c.image;
+  cx.words = (long long)(c.image_bytes / 4);
+  cx.graph_of = c.graph_of;
+  cx.M = lm_layout(L, d.B);
+  cx.lm = (const int32_t*)c.lm_image;
+  cx.lm_words = (long long)(c.lm_bytes / 4);
+  cx.lm_on = c.lm_on;
+  cx.alpha = c.alpha;
+  cx.beta = c.beta;
+  const dim3 grid(d.B), block(kBeamThreads);
+  char* state = (char*)c.state;
+  switch (c.form) {
+    case BeamForm::Plain:
+      hipLaunchKernelGGL((ctc_beam_advance_kernel<false, NoCtx>), grid, block, 0, c.stream, L, d.beam, d.k, d.blank, d.max_frames, state,
+                         c.top_logp, c.top_idx, c.T_chunk, c.n_frames, NoCtx{});
+      break;
+    case BeamForm::Ctx:
+      hipLaunchKernelGGL((ctc_beam_advance_kernel<true, CtxArgs>), grid, block, 0, c.stream, L, d.beam, d.k, d.blank, d.max_frames, state,
+                         c.top_logp, c.top_idx, c.T_chunk, c.n_frames, (const CtxArgs&)cx);
+      break;
+    case BeamForm::Lm:
+      hipLaunchKernelGGL((ctc_beam_advance_kernel<true, LmArgs, true>), grid, block, 0, c.stream, L, d.beam, d.k, d.blank, d.max_frames,
+                         state, c.top_logp, c.top_idx, c.T_chunk, c.n_frames, cx);
+      break;
+  }
   M3_LAUNCH_CHECK();
   return 0;
 }
 
-int launch_ctc_beam_lm_nbest(const m3_ctc_beam_desc* d, const void* state, size_t bytes, const void* image, size_t image_bytes,
-                             const int32_t* graph_of, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha,
-                             double beta, int use_eos, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score, float* hyp_bonus,
-                             float* hyp_lm, int32_t* n_hyps, hipStream_t stream) {
-  if (int rc = check_beam_desc(d)) return rc;
-  const size_t need = ctc_beam_lm_state_size(d);
-  M3_REQUIRE(state != nullptr && bytes >= need, "ctc_beam_lm_nbest: state %zu bytes < required %zu", bytes, need);
-  if (d->B == 0) return 0;
-  M3_REQUIRE(hyp_len && hyp_score && hyp_bonus && hyp_lm && n_hyps && (hyp_tokens || d->max_frames == 0),
-             "ctc_beam_lm_nbest: null pointer");
-  if (int rc = check_ctx_image("ctc_beam_lm_nbest", image, image_bytes, graph_of)) return rc;
-  if (int rc = check_lm_image("ctc_beam_lm_nbest", lm_image, lm_bytes, lm_on, alpha, beta)) return rc;
-  const BeamLayout L = beam_layout(d->beam, d->max_frames);
-  const LmNbest lx{lm_layout(L, d->B), (const int32_t*)lm_image, (long long)(lm_bytes / 4), lm_on, alpha, beta, use_eos ? 1 : 0,
-                   hyp_lm};
-  hipLaunchKernelGGL((ctc_beam_ctx_nbest_kernel<true, LmNbest>), dim3(d->B), dim3(64), 0, stream, L, ctx_layout(L, d->B), d->beam,
-                     d->max_frames, (const char*)state, (const int32_t*)image, (long long)(image_bytes / 4), graph_of, hyp_tokens,
-                     hyp_len, hyp_score, hyp_bonus, n_hyps, lx);
+int beam_nbest(const BeamCall& c) {
+  const int rc = check_call(c, BeamOp::Nbest);
+  if (rc != kLaunch) return rc;
+  const m3_ctc_beam_desc& d = *c.d;
+  const BeamLayout L = beam_layout(d.beam, d.max_frames);
+  const CtxLayout C = ctx_layout(L, d.B);
+  const int32_t* image = (const int32_t*)c.image;
+  const long long words = (long long)(c.image_bytes / 4);
+  const char* state = (const char*)c.state;
+  const LmNbest lx{lm_layout(L, d.B), (const int32_t*)c.lm_image, (long long)(c.lm_bytes / 4), c.lm_on, c.alpha, c.beta,
+                   c.use_eos ? 1 : 0, c.hyp_lm};
+  switch (c.form) {
+    case BeamForm::Plain:
+      hipLaunchKernelGGL(ctc_beam_nbest_kernel, dim3(d.B), dim3(64), 0, c.stream, L, d.beam, d.max_frames, state, c.hyp_tokens, c.hyp_len,
+                         c.hyp_score, c.n_hyps);
+      break;
+    case BeamForm::Ctx:
+      hipLaunchKernelGGL((ctc_beam_ctx_nbest_kernel<false, NoLm>), dim3(d.B), dim3(64), 0, c.stream, L, C, d.beam, d.max_frames, state,
+                         image, words, c.graph_of, c.hyp_tokens, c.hyp_len, c.hyp_score, c.hyp_bonus, c.n_hyps, NoLm{});
+      break;
+    case BeamForm::Lm:
+      hipLaunchKernelGGL((ctc_beam_ctx_nbest_kernel<true, LmNbest>), dim3(d.B), dim3(64), 0, c.stream, L, C, d.beam, d.max_frames, state,
+                         image, words, c.graph_of, c.hyp_tokens, c.hyp_len, c.hyp_score, c.hyp_bonus, c.n_hyps, lx);
+      break;
+  }
   M3_LAUNCH_CHECK();
   return 0;
 }

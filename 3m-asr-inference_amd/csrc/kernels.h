@@ -407,13 +407,38 @@ int ctc_prefix_beam_search_host(const float* top_logp, const int32_t* top_idx, i
                                 int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score, int32_t* n_hyps);
 int launch_ctc_argmax(const float* logits, size_t rows, int V, int32_t* ids, hipStream_t stream);
 // ctc_beam.hip: batched resumable prefix beam search and the streaming greedy search on the device
-size_t ctc_beam_state_size(const m3_ctc_beam_desc* d);
-int launch_ctc_beam_reset(const m3_ctc_beam_desc* d, void* state, size_t bytes, hipStream_t stream,
-                          const int32_t* slots = nullptr, int n = 0);   // slots (device, n entries): only those utterances
-int launch_ctc_beam_advance(const m3_ctc_beam_desc* d, void* state, size_t bytes, const float* top_logp, const int32_t* top_idx,
-                            int T_chunk, const int32_t* n_frames, hipStream_t stream);
-int launch_ctc_beam_nbest(const m3_ctc_beam_desc* d, const void* state, size_t bytes, int32_t* hyp_tokens, int32_t* hyp_len,
-                          float* hyp_score, int32_t* n_hyps, hipStream_t stream);
+// The prefix beam search has three forms: m3_ctc_beam_*, m3_ctc_beam_ctx_* (context biasing) and m3_ctc_beam_lm_*
+// (biasing and an n-gram LM).  BeamCall names everything any of their entry points receives; what a call does not have stays zero.
+enum class BeamForm { Plain, Ctx, Lm };
+struct BeamCall {
+  const char* who;               // the entry point's name in messages
+  BeamForm form;
+  const m3_ctc_beam_desc* d;
+  void* state;                   // (nbest only reads it)
+  size_t bytes;
+  const int32_t* slots;          // reset: a device list of n utterances; nullptr = every utterance
+  int n;
+  const void* image;             // the context image, and each utterance's graph in it
+  size_t image_bytes;
+  const int32_t* graph_of;
+  const void* lm_image;          // the LM image (or set), each utterance's switch (or member), the weights of the key
+  size_t lm_bytes;
+  const int32_t* lm_on;
+  double alpha, beta;
+  int use_eos;
+  const float* top_logp;         // advance: [B][T_chunk][k] of m3_ctc_topk, and each row's real frames
+  const int32_t* top_idx;
+  int T_chunk;
+  const int32_t* n_frames;
+  int32_t *hyp_tokens, *hyp_len; // nbest
+  float *hyp_score, *hyp_bonus, *hyp_lm;
+  int32_t* n_hyps;
+  hipStream_t stream;
+};
+size_t beam_state_need(const m3_ctc_beam_desc* d, BeamForm form);   // 0 (and the error set) on a bad descriptor
+int beam_reset(const BeamCall& c);
+int beam_advance(const BeamCall& c);
+int beam_nbest(const BeamCall& c);
 // ctc_align.hip: CTC forced alignment: emissions of the asked-for tokens, then trellis + backtrace + spans
 size_t ctc_align_workspace_size(const m3_ctc_align_desc* d);
 int launch_ctc_align_emit(const m3_ctc_align_desc* d, const float* logits, int ldl, const int32_t* row0, const int32_t* n_frames,
@@ -462,15 +487,6 @@ int ctc_context_validate(const void* image, size_t bytes, int V);   // decode.hi
 int ctc_prefix_beam_search_ctx_host(const float* top_logp, const int32_t* top_idx, int T, int k, int beam, int blank,
                                     const void* image, size_t image_bytes, int graph, int32_t* hyp_tokens, int32_t* hyp_len,
                                     float* hyp_score, float* hyp_bonus, int32_t* hyp_state, int32_t* n_hyps);
-size_t ctc_beam_ctx_state_size(const m3_ctc_beam_desc* d);
-int launch_ctc_beam_ctx_reset(const m3_ctc_beam_desc* d, void* state, size_t bytes, hipStream_t stream,
-                              const int32_t* slots = nullptr, int n = 0);
-int launch_ctc_beam_ctx_advance(const m3_ctc_beam_desc* d, void* state, size_t bytes, const void* image, size_t image_bytes,
-                                const int32_t* graph_of, const float* top_logp, const int32_t* top_idx, int T_chunk,
-                                const int32_t* n_frames, hipStream_t stream);
-int launch_ctc_beam_ctx_nbest(const m3_ctc_beam_desc* d, const void* state, size_t bytes, const void* image, size_t image_bytes,
-                              const int32_t* graph_of, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score,
-                              float* hyp_bonus, int32_t* n_hyps, hipStream_t stream);
 // n-gram LM shallow fusion of the prefix beam search (include/m3asr.h, "LM image"): one image of 4-byte words,
 //   [magic, version, V, order, n_states, n_arcs, start, unk_logp bits, the tables' word offsets (LMT_* order), words, 0, 0]
 // then the tables of a deterministic back-off automaton over context states (m3asr/lm.py compiles ARPA files into it).
@@ -634,17 +650,6 @@ int ctc_prefix_beam_search_lm_host(const float* top_logp, const int32_t* top_idx
                                    const void* image, size_t image_bytes, int graph, const void* lm_image, size_t lm_bytes,
                                    double alpha, double beta, int use_eos, int32_t* hyp_tokens, int32_t* hyp_len,
                                    float* hyp_score, float* hyp_bonus, int32_t* hyp_state, float* hyp_lm, int32_t* n_hyps);
-size_t ctc_beam_lm_state_size(const m3_ctc_beam_desc* d);
-int launch_ctc_beam_lm_reset(const m3_ctc_beam_desc* d, void* state, size_t bytes, hipStream_t stream,
-                             const int32_t* slots = nullptr, int n = 0);
-int launch_ctc_beam_lm_advance(const m3_ctc_beam_desc* d, void* state, size_t bytes, const void* image, size_t image_bytes,
-                               const int32_t* graph_of, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha,
-                               double beta, const float* top_logp, const int32_t* top_idx, int T_chunk, const int32_t* n_frames,
-                               hipStream_t stream);
-int launch_ctc_beam_lm_nbest(const m3_ctc_beam_desc* d, const void* state, size_t bytes, const void* image, size_t image_bytes,
-                             const int32_t* graph_of, const void* lm_image, size_t lm_bytes, const int32_t* lm_on, double alpha,
-                             double beta, int use_eos, int32_t* hyp_tokens, int32_t* hyp_len, float* hyp_score, float* hyp_bonus,
-                             float* hyp_lm, int32_t* n_hyps, hipStream_t stream);
 size_t ctc_greedy_stream_state_size(const m3_ctc_greedy_desc* d);
 int launch_ctc_greedy_stream_reset(const m3_ctc_greedy_desc* d, void* state, size_t bytes, hipStream_t stream,
                                    const int32_t* slots = nullptr, int n = 0);

@@ -132,18 +132,32 @@ class CtcBeamSearch:
             raise _lib.M3Error("CtcBeamSearch: the ContextSet is not on %s" % self.device)
         if lm is not None and (lm.dev is None or not _same_device(lm.dev.device, self.device)):
             raise _lib.M3Error("CtcBeamSearch: the NgramLm is not on %s (lm.to(device))" % self.device)
-        if context is not None or lm is not None:
-            n = ops.ctc_beam_ctx_state_size(self.desc) if lm is None else ops.ctc_beam_lm_state_size(self.desc)
+        self._bind_form()
+        if not self._plain:
             self.graph_ids = [-1] * self.desc.B               # what each utterance's next reset installs
             self.graph_of = torch.full((max(self.desc.B, 1),), -1, dtype=torch.int32, device=self.device)[:self.desc.B]
             self.used = [False] * self.desc.B                 # advanced since its last reset
             self.lm_flags = [1] * self.desc.B
             self.lm_on = torch.ones(max(self.desc.B, 1), dtype=torch.int32, device=self.device)[:self.desc.B]
-        else:
-            n = ops.ctc_beam_state_size(self.desc)
-        self.state = torch.empty(max(n, 1), dtype=torch.uint8, device=self.device)
+        self.state = torch.empty(max(self._size(self.desc), 1), dtype=torch.uint8, device=self.device)
         self.last_topk = None                                 # (top_logp, top_idx) of the last advance, for the endpointer
         self.reset()
+
+    def _bind_form(self):
+        """The form is decided once, here: the plain search (m3_ctc_beam_*), with a context and no LM the biased one
+        (m3_ctc_beam_ctx_*), with an LM the fused one (m3_ctc_beam_lm_*, whose context image may be absent).  self._size, _reset,
+        _advance, _nbest: the form's ops calls; self._args(): what its advance takes between the state and the frames, and its
+        n-best behind the state (there followed by lm_eos), read from self when a call runs."""
+        self._plain = self.context is None and self.lm is None
+        ctx = lambda: (None if self.context is None else self.context.dev, self.graph_of)
+        if self._plain:
+            family, self._args = "ctc_beam_", lambda: ()
+        elif self.lm is None:
+            family, self._args = "ctc_beam_ctx_", ctx
+        else:
+            family, self._args = "ctc_beam_lm_", lambda: ctx() + (self.lm.dev, self.lm_on, self.lm_weight, self.length_bonus)
+        self._size, self._reset, self._advance, self._nbest = (getattr(ops, family + op)
+                                                               for op in ("state_size", "reset", "advance", "nbest"))
 
     @property
     def B(self):
@@ -188,12 +202,11 @@ class CtcBeamSearch:
         setting from a reset to the next, because its nodes hold the LM state and sum of their prefixes.  With an NgramLmSet
         the flags are ints: 0 / False = off, j = member j - 1 (True / 1 = member 0); a value above len(set) is refused.  A
         restarted utterance begins from its new member's start state."""
-        which = None
         if graph_ids is not None and self.context is None:
             raise _lib.M3Error("CtcBeamSearch.reset: graph_ids without a context")
         if lm_on is not None and self.lm is None:
             raise _lib.M3Error("CtcBeamSearch.reset: lm_on without an LM")
-        if self.context is not None or self.lm is not None:
+        if not self._plain:
             which = list(range(self.B)) if slots is None else [int(b) for b in (slots.tolist() if torch.is_tensor(slots) else slots)]
             which = [b for b in which if 0 <= b < self.B]
             for b in which:
@@ -209,16 +222,10 @@ class CtcBeamSearch:
             if slots is not None and not torch.is_tensor(slots):
                 slots = torch.tensor([int(b) for b in slots], dtype=torch.int32).to(self.device)
             if slots is None or slots.numel() > 0:
-                if self.context is None and self.lm is None:
-                    ops.ctc_beam_reset(self.desc, self.state, slots)
-                    return
-                if self.lm is None:
-                    ops.ctc_beam_ctx_reset(self.desc, self.state, slots)
-                else:
-                    ops.ctc_beam_lm_reset(self.desc, self.state, slots)
-                    if self.B > 0:
-                        self.lm_on.copy_(torch.tensor(self.lm_flags, dtype=torch.int32))
-                if self.B > 0:
+                self._reset(self.desc, self.state, slots)
+                if self.lm is not None and self.B > 0:
+                    self.lm_on.copy_(torch.tensor(self.lm_flags, dtype=torch.int32))
+                if not self._plain and self.B > 0:
                     self.graph_of.copy_(torch.tensor(self.graph_ids, dtype=torch.int32))
 
     def advance(self, logits, n_frames, stream=None):
@@ -232,30 +239,19 @@ class CtcBeamSearch:
                 return
             nf = n_frames.reshape(-1).to(self.device, torch.int32, non_blocking=True)
             top_logp, top_idx = self.last_topk = ops.ctc_topk(logits.contiguous(), self.desc.k)
-            if self.context is None and self.lm is None:
-                ops.ctc_beam_advance(self.desc, self.state, top_logp, top_idx, nf)
-                return
             assert self.context is None or V == self.context.vocab_size, "the ContextSet was built for another vocabulary size"
             assert self.lm is None or V == self.lm.vocab_size, "the NgramLm was built for another vocabulary size"
-            self.used = [True] * self.B                   # without a sync the host cannot tell which rows had frames
-            image = None if self.context is None else self.context.dev
-            if self.lm is None:
-                ops.ctc_beam_ctx_advance(self.desc, self.state, image, self.graph_of, top_logp, top_idx, nf)
-            else:
-                ops.ctc_beam_lm_advance(self.desc, self.state, image, self.graph_of, self.lm.dev, self.lm_on, self.lm_weight,
-                                        self.length_bonus, top_logp, top_idx, nf)
+            if not self._plain:
+                self.used = [True] * self.B               # without a sync the host cannot tell which rows had frames
+            self._advance(self.desc, self.state, *self._args(), top_logp, top_idx, nf)
 
     def _nbest_tensors(self):
-        """(hyp_tokens, hyp_len, hyp_score, hyp_bonus or None, hyp_lm or None, n_hyps)"""
-        if self.context is None and self.lm is None:
-            toks, hlen, score, n = ops.ctc_beam_nbest(self.desc, self.state)
-            return toks, hlen, score, None, None, n
-        image = None if self.context is None else self.context.dev
-        if self.lm is None:
-            toks, hlen, score, bonus, n = ops.ctc_beam_ctx_nbest(self.desc, self.state, image, self.graph_of)
-            return toks, hlen, score, bonus, None, n
-        return ops.ctc_beam_lm_nbest(self.desc, self.state, image, self.graph_of, self.lm.dev, self.lm_on, self.lm_weight,
-                                     self.length_bonus, self.lm_eos)
+        """(hyp_tokens, hyp_len, hyp_score, hyp_bonus or None, hyp_lm or None, n_hyps): the plain form has no hyp_bonus, only the
+        fused form a hyp_lm"""
+        eos = () if self.lm is None else (self.lm_eos,)
+        toks, hlen, score, *more, n = self._nbest(self.desc, self.state, *self._args(), *eos)
+        bonus, lm = (more + [None, None])[:2]
+        return toks, hlen, score, bonus, lm, n
 
     def nbest_tensors(self, stream=None, detail=False):
         """(hyp_tokens (B,beam,max_frames), hyp_len (B,beam), hyp_score (B,beam), n_hyps (B,)) on the device; detail: with
@@ -648,10 +644,9 @@ class StreamingCtcDecoder:
                     self.wfst.reset()
             elif len(slots) > 0:
                 lst = torch.tensor([int(b) for b in slots], dtype=torch.int32).to(e.device)
-                if self.context is None and self.lm is None:
-                    self.beam.reset(e.stream, slots=lst, graph_ids=graph_ids)
-                else:
-                    self.beam.reset(e.stream, slots=[int(b) for b in slots], graph_ids=graph_ids, **kw)
+                # known inconsistency: a plain search restarted by slots is not shown lm_on, so it does not refuse it
+                self.beam.reset(e.stream, slots=[int(b) for b in slots], graph_ids=graph_ids,
+                                **({} if self.context is None and self.lm is None else kw))
                 ops.ctc_greedy_stream_reset(self.gdesc, self.gstate, lst)
                 if self.endpoint is not None:
                     ops.ctc_endpoint_reset(self.edesc, self.estate, lst)

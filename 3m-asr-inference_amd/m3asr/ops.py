@@ -735,43 +735,116 @@ def ctc_beam_desc(B, beam, max_frames, blank=0, k=None):
     return d
 
 
+# The device search has three forms, each a family of exports: m3_ctc_beam_* (plain), m3_ctc_beam_ctx_* (context biasing, m3asr.context
+# builds the images) and m3_ctc_beam_lm_* (biasing + n-gram LM shallow fusion, m3asr.lm builds the images).
+def _beam_state_size(name, desc):
+    n = getattr(_lib.load(), name)(C.byref(desc))
+    if n == 0 and desc.B > 0:
+        raise _lib.M3Error(name + " failed: " + _lib.last_error())
+    return n
+
+
+def _beam_reset(family, desc, state, slots):
+    """slots: None = every utterance; else an int32 device tensor listing the utterances to restart."""
+    name, tail = (family + "_reset", ()) if slots is None else (family + "_reset_slots", (_i32(slots), slots.numel()))
+    check(getattr(_lib.load(), name)(C.byref(desc), _p(state), _nbytes(state), *tail, _stream()), name)
+
+
+def _beam_frames(desc, top_logp, top_idx, n_frames, *per_utterance):
+    """the marshalled tail of an advance (top_logp, top_idx, T_chunk, n_frames), behind its shape checks"""
+    B, Tc, k = top_logp.shape
+    assert B == desc.B and k == desc.k and tuple(top_idx.shape) == (B, Tc, k)
+    assert all(t.numel() == B for t in (n_frames,) + per_utterance)
+    return _f32(top_logp), _i32(top_idx), Tc, _i32(n_frames)
+
+
+def _beam_hyps(desc, dev, bonus=False, lm=False):
+    """the n-best outputs, in the exports' order: [hyp_tokens, hyp_len, hyp_score, hyp_bonus if bonus, hyp_lm if lm, n_hyps]"""
+    B, beam = desc.B, desc.beam
+    return ([torch.empty(B, beam, desc.max_frames, dtype=torch.int32, device=dev), torch.empty(B, beam, dtype=torch.int32, device=dev)]
+            + [torch.empty(B, beam, dtype=torch.float32, device=dev) for _ in range(1 + bool(bonus) + bool(lm))]
+            + [torch.empty(B, dtype=torch.int32, device=dev)])
+
+
+def _image(image):
+    """(pointer, bytes) of a device context image (int32 words; None = no graphs)"""
+    return (None, 0) if image is None else (_i32(image), image.numel() * 4)
+
+
 def ctc_beam_state_size(desc):
     """bytes of device state for desc (host-only call); M3Error on a bad descriptor."""
-    n = _lib.load().m3_ctc_beam_state_size(C.byref(desc))
-    if n == 0 and desc.B > 0:
-        raise _lib.M3Error("m3_ctc_beam_state_size failed: " + _lib.last_error())
-    return n
+    return _beam_state_size("m3_ctc_beam_state_size", desc)
+
+
+def ctc_beam_ctx_state_size(desc):
+    """bytes of device state of the biased search: the unbiased layout, then every node's context state and bonus."""
+    return _beam_state_size("m3_ctc_beam_ctx_state_size", desc)
+
+
+def ctc_beam_lm_state_size(desc):
+    """bytes of device state of the fused search: the biased layout, then every node's LM state and LM sum."""
+    return _beam_state_size("m3_ctc_beam_lm_state_size", desc)
 
 
 def ctc_beam_reset(desc, state, slots=None):
     """slots: None = every utterance; else an int32 device tensor listing the utterances to restart."""
-    if slots is not None:
-        check(_lib.load().m3_ctc_beam_reset_slots(C.byref(desc), _p(state), state.numel() * state.element_size(), _i32(slots),
-                                                  slots.numel(), _stream()), "m3_ctc_beam_reset_slots")
-        return
-    check(_lib.load().m3_ctc_beam_reset(C.byref(desc), _p(state), state.numel() * state.element_size(), _stream()),
-          "m3_ctc_beam_reset")
+    _beam_reset("m3_ctc_beam", desc, state, slots)
+
+
+def ctc_beam_ctx_reset(desc, state, slots=None):
+    _beam_reset("m3_ctc_beam_ctx", desc, state, slots)
+
+
+def ctc_beam_lm_reset(desc, state, slots=None):
+    _beam_reset("m3_ctc_beam_lm", desc, state, slots)
 
 
 def ctc_beam_advance(desc, state, top_logp, top_idx, n_frames):
     """top_logp / top_idx (B, T_chunk, k) from ctc_topk, n_frames (B,) int32 on the device: enqueue, no host sync."""
-    B, Tc, k = top_logp.shape
-    assert B == desc.B and k == desc.k and tuple(top_idx.shape) == (B, Tc, k) and n_frames.numel() == B
-    check(_lib.load().m3_ctc_beam_advance(C.byref(desc), _p(state), state.numel() * state.element_size(), _f32(top_logp),
-                                          _i32(top_idx), Tc, _i32(n_frames), _stream()), "m3_ctc_beam_advance")
+    frames = _beam_frames(desc, top_logp, top_idx, n_frames)
+    check(_lib.load().m3_ctc_beam_advance(C.byref(desc), _p(state), _nbytes(state), *frames, _stream()), "m3_ctc_beam_advance")
+
+
+def ctc_beam_ctx_advance(desc, state, image, graph_of, top_logp, top_idx, n_frames):
+    """ctc_beam_advance with the device image (int32 words, or None) and graph_of (B,) int32 on the device (-1 = unbiased)."""
+    frames = _beam_frames(desc, top_logp, top_idx, n_frames, graph_of)
+    check(_lib.load().m3_ctc_beam_ctx_advance(C.byref(desc), _p(state), _nbytes(state), *_image(image), _i32(graph_of), *frames,
+                                              _stream()), "m3_ctc_beam_ctx_advance")
+
+
+def ctc_beam_lm_advance(desc, state, image, graph_of, lm_image, lm_on, alpha, beta, top_logp, top_idx, n_frames):
+    """ctc_beam_ctx_advance with the device LM image (int32 words, or None), lm_on (B,) int32 on the device (0 = this
+    utterance runs without the LM) and the run-time weights alpha (LM) and beta (per token)."""
+    frames = _beam_frames(desc, top_logp, top_idx, n_frames, graph_of, lm_on)
+    check(_lib.load().m3_ctc_beam_lm_advance(C.byref(desc), _p(state), _nbytes(state), *_image(image), _i32(graph_of),
+                                             *_image(lm_image), _i32(lm_on), float(alpha), float(beta), *frames, _stream()),
+          "m3_ctc_beam_lm_advance")
 
 
 def ctc_beam_nbest(desc, state):
     """-> (hyp_tokens (B,beam,max_frames) -1 padded, hyp_len (B,beam), hyp_score (B,beam), n_hyps (B,) -1 = failed), device."""
-    dev = state.device
-    B, beam, F = desc.B, desc.beam, desc.max_frames
-    toks = torch.empty(B, beam, F, dtype=torch.int32, device=dev)
-    hlen = torch.empty(B, beam, dtype=torch.int32, device=dev)
-    score = torch.empty(B, beam, dtype=torch.float32, device=dev)
-    n = torch.empty(B, dtype=torch.int32, device=dev)
-    check(_lib.load().m3_ctc_beam_nbest(C.byref(desc), _p(state), state.numel() * state.element_size(), _p(toks), _p(hlen),
-                                        _p(score), _p(n), _stream()), "m3_ctc_beam_nbest")
-    return toks, hlen, score, n
+    out = _beam_hyps(desc, state.device)
+    check(_lib.load().m3_ctc_beam_nbest(C.byref(desc), _p(state), _nbytes(state), *map(_p, out), _stream()), "m3_ctc_beam_nbest")
+    return tuple(out)
+
+
+def ctc_beam_ctx_nbest(desc, state, image, graph_of):
+    """-> (hyp_tokens, hyp_len, hyp_score (the CTC score), hyp_bonus (B,beam), n_hyps), ordered by CTC score + bonus; device."""
+    assert graph_of.numel() == desc.B
+    out = _beam_hyps(desc, state.device, bonus=True)
+    check(_lib.load().m3_ctc_beam_ctx_nbest(C.byref(desc), _p(state), _nbytes(state), *_image(image), _i32(graph_of), *map(_p, out),
+                                            _stream()), "m3_ctc_beam_ctx_nbest")
+    return tuple(out)
+
+
+def ctc_beam_lm_nbest(desc, state, image, graph_of, lm_image, lm_on, alpha, beta, use_eos=True):
+    """-> (hyp_tokens, hyp_len, hyp_score (the CTC score), hyp_bonus, hyp_lm (B,beam), n_hyps), ordered by the fused key."""
+    assert graph_of.numel() == desc.B and lm_on.numel() == desc.B
+    out = _beam_hyps(desc, state.device, bonus=True, lm=True)
+    check(_lib.load().m3_ctc_beam_lm_nbest(C.byref(desc), _p(state), _nbytes(state), *_image(image), _i32(graph_of), *_image(lm_image),
+                                           _i32(lm_on), float(alpha), float(beta), int(bool(use_eos)), *map(_p, out), _stream()),
+          "m3_ctc_beam_lm_nbest")
+    return tuple(out)
 
 
 # ---- context biasing (m3asr.context builds the images)
@@ -806,55 +879,6 @@ def ctc_prefix_beam_search_ctx_host(top_logp, top_idx, beam, blank=0, image=None
                                             vp(bonus), vp(state), C.cast(C.byref(n), C.c_void_p)),
           "m3_ctc_prefix_beam_search_ctx")
     return [(tuple(int(v) for v in toks[i, :hlen[i]]), float(score[i]), float(bonus[i]), int(state[i])) for i in range(n.value)]
-
-
-def ctc_beam_ctx_state_size(desc):
-    """bytes of device state of the biased search: the unbiased layout, then every node's context state and bonus."""
-    n = _lib.load().m3_ctc_beam_ctx_state_size(C.byref(desc))
-    if n == 0 and desc.B > 0:
-        raise _lib.M3Error("m3_ctc_beam_ctx_state_size failed: " + _lib.last_error())
-    return n
-
-
-def ctc_beam_ctx_reset(desc, state, slots=None):
-    if slots is not None:
-        check(_lib.load().m3_ctc_beam_ctx_reset_slots(C.byref(desc), _p(state), state.numel() * state.element_size(), _i32(slots),
-                                                      slots.numel(), _stream()), "m3_ctc_beam_ctx_reset_slots")
-        return
-    check(_lib.load().m3_ctc_beam_ctx_reset(C.byref(desc), _p(state), state.numel() * state.element_size(), _stream()),
-          "m3_ctc_beam_ctx_reset")
-
-
-def _image(image):
-    """(pointer, bytes) of a device context image (int32 words; None = no graphs)"""
-    return (None, 0) if image is None else (_i32(image), image.numel() * 4)
-
-
-def ctc_beam_ctx_advance(desc, state, image, graph_of, top_logp, top_idx, n_frames):
-    """ctc_beam_advance with the device image (int32 words, or None) and graph_of (B,) int32 on the device (-1 = unbiased)."""
-    B, Tc, k = top_logp.shape
-    assert B == desc.B and k == desc.k and tuple(top_idx.shape) == (B, Tc, k) and n_frames.numel() == B and graph_of.numel() == B
-    img, nbytes = _image(image)
-    check(_lib.load().m3_ctc_beam_ctx_advance(C.byref(desc), _p(state), state.numel() * state.element_size(), img, nbytes,
-                                              _i32(graph_of), _f32(top_logp), _i32(top_idx), Tc, _i32(n_frames), _stream()),
-          "m3_ctc_beam_ctx_advance")
-
-
-def ctc_beam_ctx_nbest(desc, state, image, graph_of):
-    """-> (hyp_tokens, hyp_len, hyp_score (the CTC score), hyp_bonus (B,beam), n_hyps), ordered by CTC score + bonus; device."""
-    dev = state.device
-    B, beam, F = desc.B, desc.beam, desc.max_frames
-    assert graph_of.numel() == B
-    toks = torch.empty(B, beam, F, dtype=torch.int32, device=dev)
-    hlen = torch.empty(B, beam, dtype=torch.int32, device=dev)
-    score = torch.empty(B, beam, dtype=torch.float32, device=dev)
-    bonus = torch.empty(B, beam, dtype=torch.float32, device=dev)
-    n = torch.empty(B, dtype=torch.int32, device=dev)
-    img, nbytes = _image(image)
-    check(_lib.load().m3_ctc_beam_ctx_nbest(C.byref(desc), _p(state), state.numel() * state.element_size(), img, nbytes,
-                                            _i32(graph_of), _p(toks), _p(hlen), _p(score), _p(bonus), _p(n), _stream()),
-          "m3_ctc_beam_ctx_nbest")
-    return toks, hlen, score, bonus, n
 
 
 # ---- n-gram LM shallow fusion (m3asr.lm builds the images)
@@ -906,57 +930,6 @@ def ctc_prefix_beam_search_lm_host(top_logp, top_idx, beam, blank=0, image=None,
                                            C.cast(C.byref(n), C.c_void_p)), "m3_ctc_prefix_beam_search_lm")
     return [(tuple(int(v) for v in toks[i, :hlen[i]]), float(score[i]), float(bonus[i]), float(lm[i]), int(state[i]))
             for i in range(n.value)]
-
-
-def ctc_beam_lm_state_size(desc):
-    """bytes of device state of the fused search: the biased layout, then every node's LM state and LM sum."""
-    n = _lib.load().m3_ctc_beam_lm_state_size(C.byref(desc))
-    if n == 0 and desc.B > 0:
-        raise _lib.M3Error("m3_ctc_beam_lm_state_size failed: " + _lib.last_error())
-    return n
-
-
-def ctc_beam_lm_reset(desc, state, slots=None):
-    if slots is not None:
-        check(_lib.load().m3_ctc_beam_lm_reset_slots(C.byref(desc), _p(state), state.numel() * state.element_size(), _i32(slots),
-                                                     slots.numel(), _stream()), "m3_ctc_beam_lm_reset_slots")
-        return
-    check(_lib.load().m3_ctc_beam_lm_reset(C.byref(desc), _p(state), state.numel() * state.element_size(), _stream()),
-          "m3_ctc_beam_lm_reset")
-
-
-def ctc_beam_lm_advance(desc, state, image, graph_of, lm_image, lm_on, alpha, beta, top_logp, top_idx, n_frames):
-    """ctc_beam_ctx_advance with the device LM image (int32 words, or None), lm_on (B,) int32 on the device (0 = this
-    utterance runs without the LM) and the run-time weights alpha (LM) and beta (per token)."""
-    B, Tc, k = top_logp.shape
-    assert B == desc.B and k == desc.k and tuple(top_idx.shape) == (B, Tc, k) and n_frames.numel() == B
-    assert graph_of.numel() == B and lm_on.numel() == B
-    img, nbytes = _image(image)
-    lmi, lm_bytes = _image(lm_image)
-    check(_lib.load().m3_ctc_beam_lm_advance(C.byref(desc), _p(state), state.numel() * state.element_size(), img, nbytes,
-                                             _i32(graph_of), lmi, lm_bytes, _i32(lm_on), float(alpha), float(beta),
-                                             _f32(top_logp), _i32(top_idx), Tc, _i32(n_frames), _stream()),
-          "m3_ctc_beam_lm_advance")
-
-
-def ctc_beam_lm_nbest(desc, state, image, graph_of, lm_image, lm_on, alpha, beta, use_eos=True):
-    """-> (hyp_tokens, hyp_len, hyp_score (the CTC score), hyp_bonus, hyp_lm (B,beam), n_hyps), ordered by the fused key."""
-    dev = state.device
-    B, beam, F = desc.B, desc.beam, desc.max_frames
-    assert graph_of.numel() == B and lm_on.numel() == B
-    toks = torch.empty(B, beam, F, dtype=torch.int32, device=dev)
-    hlen = torch.empty(B, beam, dtype=torch.int32, device=dev)
-    score = torch.empty(B, beam, dtype=torch.float32, device=dev)
-    bonus = torch.empty(B, beam, dtype=torch.float32, device=dev)
-    lm = torch.empty(B, beam, dtype=torch.float32, device=dev)
-    n = torch.empty(B, dtype=torch.int32, device=dev)
-    img, nbytes = _image(image)
-    lmi, lm_bytes = _image(lm_image)
-    check(_lib.load().m3_ctc_beam_lm_nbest(C.byref(desc), _p(state), state.numel() * state.element_size(), img, nbytes,
-                                           _i32(graph_of), lmi, lm_bytes, _i32(lm_on), float(alpha), float(beta),
-                                           int(bool(use_eos)), _p(toks), _p(hlen), _p(score), _p(bonus), _p(lm), _p(n), _stream()),
-          "m3_ctc_beam_lm_nbest")
-    return toks, hlen, score, bonus, lm, n
 
 
 # ---- WFST decoding (m3asr.wfst builds the graph images)
