@@ -13,11 +13,99 @@
 // One workgroup (4 waves) per (batch, head, 16-query tile): wave w walks key tiles w, w+4, ... with an
 // online softmax (so a 50-frame utterance is one key tile per wave = one memory round trip), the
 // probability tile goes C-layout -> A-layout through a 1 KB LDS patch per wave, and the four partial
-// (max, sum, O) states are merged through LDS.
+// (max, sum, O) states are merged through LDS.  A wave's FIRST key tile skips the online-softmax rescale (its state
+// is m = -inf, l = o = +0: the rescale is the identity bit for bit), so at T' <= 64 no wave rescales at all.  The merge
+// (att_merge_store, shared with the chunk-by-chunk kernel) computes a row's total max, its four factors exp(m_w - m_tot) and
+// its total sum once per row in every wave, and per output element only the four multiply-adds and the division.
+// Per work-group the operands are 52 KB (dk = 64) / 100 KB (dk = 128) pulled by ONE CU: at T' = 50 that pull, not the
+// instruction stream, is the longest phase.
+#include <algorithm>
+#include <type_traits>
+
 #include "common.h"
 #include "kernels.h"
 
+// -DM3_ATT_DIAG: phase stamps (s_memtime) of wave 0 of every work-group of the fp32 kernels into a debug buffer
+// (tools/diag_attention.py).  No stamp executes in the normal build.
+#ifdef M3_ATT_DIAG
+#define M3_ADIAG(...) __VA_ARGS__
+#else
+#define M3_ADIAG(...)
+#endif
+
 namespace m3 {
+
+#ifdef M3_ATT_DIAG
+__device__ unsigned long long g_att_dbg[2048 * 8];
+// (one statement: the wait belongs to the stamp; the fences keep the compiler from moving work across it)
+__device__ __forceinline__ unsigned long long att_stamp() {
+  unsigned long long t;
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+  __builtin_amdgcn_sched_barrier(0);
+  return t;
+}
+// stamps: 0 entry | 1 arguments loaded | 2 operands landed | 3 scores done | 4 softmax done | 5 P.V done | 6 barrier passed | 7 merge stored
+__device__ __forceinline__ void att_diag_write(const unsigned long long (&dg)[8], int wg_id, int wave, int lane) {
+  if (lane == 0 && wave == 0 && wg_id < 2048)
+    for (int i = 0; i < 8; ++i) g_att_dbg[(size_t)wg_id * 8 + i] = dg[i];
+}
+#endif
+
+// ---- shared by the full-utterance and the chunk-by-chunk kernel ----
+// The partial O of a wave lies in LDS as [16 rows][MLD], column col of output tile n being channel 16 n + col.  MLD = dk + 4: the
+// two row groups (kq, kq + 1) that share a 32-lane half of a ds_write_b32 sit 16 banks apart, columns 0..15 against 16..31; the
+// merge reads 32 consecutive channels of a row.  Neither side has a bank conflict.  (A lane map with consecutive channels per
+// lane -- V rows as 16-byte loads -- was built and measured: the operand phase did not move)
+constexpr int att_mo_ld(int dk) { return dk + 4; }
+// a load at a wave-uniform base plus a 32-bit element offset (the byte offset stays below 2^32: kAttMaxRowSpan)
+template <typename V>
+__device__ __forceinline__ V att_ld(const float* base, unsigned off) {
+  return *reinterpret_cast<const V*>(reinterpret_cast<const char*>(base) + (off << 2));
+}
+// n / d as the high half of n * magic, magic = 2^32 / d + 1 (att_magic; 0 stands for d = 1): exact while n d < 2^32
+__device__ __forceinline__ int att_div(int n, unsigned magic) { return magic ? (int)__umulhi((unsigned)n, magic) : n; }
+
+// The four waves' partial (max, sum, O) states of 16 query rows -> the context rows, after the work-group's barrier.
+// Per row, once: m_tot, the four factors f[w] = exp(m[w] - m_tot) (0 for a wave without a visible key) and l_tot, by lane
+// (w, i) = (lane / 16, lane % 16) of EVERY wave -- redundant, but wave-private: no second barrier.  Per output element only
+// acc = (((0 + O0 f0) + O1 f1) + O2 f2) + O3 f3  and the division.  dk >= 64: the 64 elements of a wave in one trip are one
+// row, so the row's factors are read with v_readlane (the multiplies take them as scalar operands); below that by ds_bpermute.
+// Every lane stays active up to the store: a bpermute reads nothing from an inactive lane.
+template <int DK>
+__device__ __forceinline__ void att_merge_store(const float (*mm)[16], const float (*ml)[16], const float* mo, int q0, int q_end,
+                                                size_t brow, int h, float* __restrict__ out, int ldo, int out_bf16) {
+  constexpr int MLD = att_mo_ld(DK);
+  const int lane = threadIdx.x & 63, fw = lane >> 4, fi = lane & 15;
+  const float m_tot = fmaxf(fmaxf(mm[0][fi], mm[1][fi]), fmaxf(mm[2][fi], mm[3][fi]));
+  const float mw = mm[fw][fi];
+  const float f = (mw == -INFINITY) ? 0.f : expf(mw - m_tot);   // waves without a (visible) key tile: factor 0
+  const float lf = ml[fw][fi] * f;
+  float l_tot = 0.f;                                            // of row fi, in every lane (w, fi)
+#pragma unroll
+  for (int w = 0; w < 4; ++w) l_tot += __shfl(lf, 16 * w + fi, 64);
+  auto row_value = [&](float v, int src) {
+    if constexpr (DK >= 64) return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), __builtin_amdgcn_readfirstlane(src)));
+    else return __shfl(v, src, 64);
+  };
+  float* orow = out + (brow * ldo + h * DK);
+  bf16_t* orow16 = reinterpret_cast<bf16_t*>(out) + (brow * ldo + h * DK);
+  for (int idx = threadIdx.x; idx < 16 * DK; idx += 256) {
+    const int i = idx / DK, d = idx - i * DK;
+    const float* mrow = mo + i * MLD + d;
+    float acc = 0.f;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) acc += mrow[w * 16 * MLD] * row_value(f, 16 * w + i);
+    const float lt = row_value(l_tot, i);
+    const float o = lt > 0.f ? acc / lt : 0.f;       // a row with no visible key (padded query under a chunk mask): zeros
+    const int qrow = q0 + i;
+    if (qrow < q_end) {
+      const unsigned off = (unsigned)qrow * (unsigned)ldo + d;
+      if (out_bf16) orow16[off] = (bf16_t)o;
+      else orow[off] = o;
+    }
+  }
+}
 
 // (the body as a device function of the work-group id: relpos_attention_dual_kernel runs two independent attention problems --
 //  the embed encoder's and the main encoder's first block, different head widths -- in one launch; engine.hip "horizontal fusion")
@@ -26,13 +114,17 @@ __device__ __forceinline__ void relpos_attention_body(const float* __restrict__ 
                                                       const float* __restrict__ pos_u, const float* __restrict__ pos_v,
                                                       const int32_t* __restrict__ row_len, int T, int D, float scale,
                                                       float* __restrict__ out, int ldo, int out_bf16, const int32_t* __restrict__ row0,
-                                                      int QT, int H, int xcd_map, int chunk, int left_chunks, const int wg_id) {
-  constexpr int KS = DK / 16;
+                                                      int QT, int H, int xcd_map, int chunk, int left_chunks, unsigned qt_magic, unsigned h_magic,
+                                                      const int wg_id) {
+  constexpr int KS = DK / 16, MLD = att_mo_ld(DK);
+  M3_ADIAG(unsigned long long dg[8] = {0, 0, 0, 0, 0, 0, 0, 0}; dg[0] = att_stamp();)
   // one batch of kernel-argument loads instead of one per first use (see gemm.hip: ~5 dependent s_load rounds otherwise)
   asm volatile("" ::"s"(qkv), "s"(ldq), "s"(pmat), "s"(ldp), "s"(pos_u), "s"(pos_v), "s"(row_len), "s"(T), "s"(D), "s"(scale),
-               "s"(out), "s"(ldo), "s"(out_bf16), "s"(row0), "s"(QT), "s"(H), "s"(xcd_map), "s"(chunk), "s"(left_chunks));
+               "s"(out), "s"(ldo), "s"(out_bf16), "s"(row0), "s"(QT), "s"(H), "s"(xcd_map), "s"(chunk), "s"(left_chunks), "s"(qt_magic),
+               "s"(h_magic));
+  M3_ADIAG(dg[1] = att_stamp();)
   __shared__ __attribute__((aligned(16))) float ps_all[4][16][20];
-  __shared__ float mo[4][16][DK + 1];   // per-wave partial O
+  __shared__ float mo[4][16][MLD];   // per-wave partial O
   __shared__ float mm[4][16], ml[4][16];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, kq = lane >> 4;
   float (*ps)[20] = ps_all[wave];
@@ -44,34 +136,78 @@ __device__ __forceinline__ void relpos_attention_body(const float* __restrict__ 
   {
     const int id = wg_id;
     int bh, qt;
+    // (quotients by multiplication: att_pack's magic numbers, exact for every work-group id of the launch)
     if (xcd_map) {
-      const int g = id & 7, slot = id >> 3;
-      bh = (slot / QT) * 8 + g;
-      qt = slot - (slot / QT) * QT;
+      const int g = id & 7, slot = id >> 3, sq = att_div(slot, qt_magic);
+      bh = sq * 8 + g;
+      qt = slot - sq * QT;
     } else {
-      bh = id / QT;
+      bh = att_div(id, qt_magic);
       qt = id - bh * QT;
     }
-    b = bh / H;
+    b = att_div(bh, h_magic);
     h = bh - b * H;
     q0 = qt * 16;
   }
-  const int len = min(row_len ? row_len[b] : T, T);
   // packed rows (row0 != null): utterance b owns rows [row0[b], row0[b] + len) -- nothing beyond its last frame may be
-  // read (it is another utterance's) or written; padded rows: [b T, (b+1) T), frames >= len hold defined values
-  if (row0 != nullptr && q0 >= len) return;
-  const size_t brow = row0 ? (size_t)row0[b] : (size_t)b * T;
-  const int last = row0 ? len - 1 : T - 1;          // clamp for the addresses of masked lanes
-  const int q_end = row0 ? len : T;                 // query rows this utterance owns
+  // read (it is another utterance's) or written; padded rows: [b T, (b+1) T), frames >= len hold defined values.
+  // In the padded form brow, last and q_end come from the arguments alone: row_len[b] is requested here and waited for behind
+  // the operand requests.
+  int len_in = T;
+  if (row_len) len_in = row_len[b];
+  size_t brow = (size_t)b * T;
+  int last = T - 1;                                 // clamp for the addresses of masked lanes
+  int q_end = T;                                    // query rows this utterance owns
+  if (row0 != nullptr) {
+    const int len_p = min(__builtin_amdgcn_readfirstlane(len_in), T);
+    if (q0 >= len_p) return;
+    brow = (size_t)__builtin_amdgcn_readfirstlane(row0[b]);
+    last = len_p - 1;
+    q_end = len_p;
+  }
+  // this utterance's rows, this head's columns: a wave-uniform 64-bit base plus a 32-bit byte offset per lane (a row index
+  // below T times a row stride: check_relpos_attention keeps T ld under 2^30 elements)
+  const float* qb = qkv + brow * ldq + h * DK;      // q | k at + D | v at + 2 D
+  const float* pb0 = pmat + h * DK;
 
-  const int qi = min(q0 + col, last);
-  const float* qrow = qkv + (brow + qi) * ldq + h * DK + 4 * kq;
-  f32x4 qu[KS], qv[KS];
+  // K / P fragments of the key tile at j0, and its V fragments: B[k = key 4kq+jj][n = channel 16n+col]
+  auto load_tile = [&](const int j0, f32x4 (&kb)[KS], f32x4 (&pb)[KS], float (&vb)[4][KS]) {
+    const unsigned kj = (unsigned)min(j0 + col, last);
+    const unsigned koff = kj * (unsigned)ldq + 4 * kq, poff = kj * (unsigned)ldp + 4 * kq;
 #pragma unroll
-  for (int s = 0; s < KS; ++s) {
-    const f32x4 q4 = ldg4(qrow + 16 * s);
-    qu[s] = q4 + ldg4(pos_u + h * DK + 16 * s + 4 * kq);
-    qv[s] = q4 + ldg4(pos_v + h * DK + 16 * s + 4 * kq);
+    for (int s = 0; s < KS; ++s) {
+      kb[s] = att_ld<f32x4>(qb + D, koff + 16 * s);
+      pb[s] = att_ld<f32x4>(pb0, poff + 16 * s);
+    }
+#pragma unroll
+    for (int jj = 0; jj < 4; ++jj) {
+      const unsigned voff = (unsigned)min(j0 + 4 * kq + jj, last) * (unsigned)ldq + col;
+#pragma unroll
+      for (int n = 0; n < KS; ++n) vb[jj][n] = att_ld<float>(qb + 2 * D, voff + 16 * n);
+    }
+  };
+
+  // Q and the position biases, then -- behind the additions -- the operands of the wave's first key tile (a wave without a key
+  // in that tile reads clamped rows for nothing).  Requesting the tile before the wait for Q was measured and is no faster
+  // (the work-group's operands arrive at the rate one CU pulls, in either order); the fence keeps the order measured.
+  f32x4 qu[KS], qv[KS], kb[KS], pb[KS];
+  float vb[4][KS];
+  {
+    const unsigned qoff = (unsigned)min(q0 + col, last) * (unsigned)ldq + 4 * kq;
+    f32x4 q4[KS], pu[KS], pv[KS];
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      q4[s] = att_ld<f32x4>(qb, qoff + 16 * s);
+      pu[s] = ldg4(pos_u + h * DK + 16 * s + 4 * kq);
+      pv[s] = ldg4(pos_v + h * DK + 16 * s + 4 * kq);
+    }
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+      qu[s] = q4[s] + pu[s];
+      qv[s] = q4[s] + pv[s];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    load_tile(16 * wave, kb, pb, vb);
   }
   f32x4 o[KS];
 #pragma unroll
@@ -86,6 +222,7 @@ __device__ __forceinline__ void relpos_attention_body(const float* __restrict__ 
   // static chunk mask (utils/mask.py:42-75 subsequent_chunk_mask, :127-134 static_chunk_size): query i sees keys
   // [max((i / chunk - left_chunks) chunk, 0), min((i / chunk + 1) chunk, T)) -- all left chunks when left_chunks < 0 --
   // besides the padding mask key < len.  chunk <= 0: full context.  Rows of this lane's accumulators: 4 kq + r.
+  const int len = min(__builtin_amdgcn_readfirstlane(len_in), T);
   int klo[4], khi[4];
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -98,25 +235,12 @@ __device__ __forceinline__ void relpos_attention_body(const float* __restrict__ 
       khi[r] = min(min((c + 1) * chunk, T), len);
     }
   }
-  for (int j0 = 16 * wave; j0 < len; j0 += 64) {
-    const int kj = min(j0 + col, last);
-    const float* krow = qkv + (brow + kj) * ldq + D + h * DK + 4 * kq;
-    const float* prow = pmat + (size_t)kj * ldp + h * DK + 4 * kq;
-    f32x4 kb[KS], pb[KS];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      kb[s] = ldg4(krow + 16 * s);
-      pb[s] = ldg4(prow + 16 * s);
-    }
-    // V fragments for this key tile: B[k = key 4kq+jj][n = channel 16n+col]
-    float vb[KS][4];
-#pragma unroll
-    for (int jj = 0; jj < 4; ++jj) {
-      const int vj = min(j0 + 4 * kq + jj, last);
-      const float* vrow = qkv + (brow + vj) * ldq + 2 * D + h * DK + col;
-#pragma unroll
-      for (int n = 0; n < KS; ++n) vb[n][jj] = vrow[16 * n];
-    }
+  // One key tile: scores (the alternating K / P chain), online softmax, P.V.  FIRST: the wave's first tile.  Its state is
+  // m_run = -inf, l_run = +0, o = +0, so the rescale is the identity bit for bit and is left out: corr is 1 or expf(-inf) = +0,
+  // (+0) corr = +0, and (+0) + s = s for the sum s >= 0 of the probabilities.  At T' <= 64 that is the only tile of every wave.
+  auto run_tile = [&](auto first, const int j0) {
+    constexpr bool FIRST = decltype(first)::value;
+    M3_ADIAG(if (FIRST) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); dg[2] = att_stamp(); })
     f32x4 sc = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < KS; ++s)
@@ -125,19 +249,25 @@ __device__ __forceinline__ void relpos_attention_body(const float* __restrict__ 
         sc = mfma16(qu[s][j], kb[s][j], sc);
         sc = mfma16(qv[s][j], pb[s][j], sc);
       }
+    M3_ADIAG(if (FIRST) { asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); dg[3] = att_stamp(); })
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const bool valid = (j0 + col) >= klo[r] && (j0 + col) < khi[r];
       const float sv = valid ? sc[r] * scale : -INFINITY;
       const float m_new = fmaxf(m_run[r], group16_max(sv));
       const float pexp = valid ? expf(sv - m_new) : 0.f;
-      const float corr = (m_new == -INFINITY) ? 1.f : expf(m_run[r] - m_new);   // (a key tile wholly outside the row's chunk window)
-      l_run[r] = l_run[r] * corr + group16_sum(pexp);
-      m_run[r] = m_new;
+      if constexpr (FIRST) {
+        l_run[r] = group16_sum(pexp);
+      } else {
+        const float corr = (m_new == -INFINITY) ? 1.f : expf(m_run[r] - m_new);   // (a key tile wholly outside the row's chunk window)
+        l_run[r] = l_run[r] * corr + group16_sum(pexp);
 #pragma unroll
-      for (int n = 0; n < KS; ++n) o[n][r] *= corr;
+        for (int n = 0; n < KS; ++n) o[n][r] *= corr;
+      }
+      m_run[r] = m_new;
       ps[4 * kq + r][col] = pexp;
     }
+    M3_ADIAG(if (FIRST) dg[4] = att_stamp();)
     // ps is private to this wave and a wave's LDS operations execute in order: only the compiler has
     // to be kept from moving the transposed read across the writes (no s_barrier needed)
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -148,7 +278,15 @@ __device__ __forceinline__ void relpos_attention_body(const float* __restrict__ 
 #pragma unroll
     for (int n = 0; n < KS; ++n)
 #pragma unroll
-      for (int jj = 0; jj < 4; ++jj) o[n] = mfma16(pa[jj], vb[n][jj], o[n]);
+      for (int jj = 0; jj < 4; ++jj) o[n] = mfma16(pa[jj], vb[jj][n], o[n]);
+    M3_ADIAG(if (FIRST) { asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); dg[5] = att_stamp(); })
+  };
+  if (16 * wave < len) {
+    run_tile(std::true_type{}, 16 * wave);
+    for (int j0 = 16 * wave + 64; j0 < len; j0 += 64) {
+      load_tile(j0, kb, pb, vb);
+      run_tile(std::false_type{}, j0);
+    }
   }
 
   // ---- merge the four waves' partial softmax states ----
@@ -162,31 +300,18 @@ __device__ __forceinline__ void relpos_attention_body(const float* __restrict__ 
     for (int n = 0; n < KS; ++n) mo[wave][4 * kq + r][16 * n + col] = o[n][r];
   }
   __syncthreads();
-  for (int idx = threadIdx.x; idx < 16 * DK; idx += 256) {
-    const int i = idx / DK, d = idx - i * DK;
-    const int qrow = q0 + i;
-    if (qrow >= q_end) continue;
-    const float m_tot = fmaxf(fmaxf(mm[0][i], mm[1][i]), fmaxf(mm[2][i], mm[3][i]));
-    float l_tot = 0.f, acc = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const float f = (mm[w][i] == -INFINITY) ? 0.f : expf(mm[w][i] - m_tot);   // waves without a (visible) key tile: factor 0
-      l_tot += ml[w][i] * f;
-      acc += mo[w][i][d] * f;
-    }
-    const float o = l_tot > 0.f ? acc / l_tot : 0.f;       // a row with no visible key (padded query under a chunk mask): zeros
-    if (out_bf16) reinterpret_cast<bf16_t*>(out)[(brow + qrow) * ldo + h * DK + d] = (bf16_t)o;
-    else out[(brow + qrow) * ldo + h * DK + d] = o;
-  }
+  M3_ADIAG(dg[6] = att_stamp();)
+  att_merge_store<DK>(mm, ml, &mo[0][0][0], q0, q_end, brow, h, out, ldo, out_bf16);
+  M3_ADIAG(asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); dg[7] = att_stamp(); att_diag_write(dg, wg_id, wave, lane);)
 }
 
 // One record per problem, filled by att_pack: the single kernel takes one, the dual kernel two.  QT, the XCD mapping and the
 // work-group count are derived there, once.
 struct AttKernArgs {
   const float *qkv; int ldq; const float* pmat; int ldp; const float *pos_u, *pos_v; const int32_t* row_len; int T, D; float scale;
-  float* out; int ldo, out_bf16; const int32_t* row0; int QT, H, xcd_map, chunk, left_chunks, n_wg;
+  float* out; int ldo, out_bf16; const int32_t* row0; int QT, H, xcd_map, chunk, left_chunks; unsigned qt_magic, h_magic; int n_wg;
 };
-#define M3_ATT_SPREAD(a) a.qkv, a.ldq, a.pmat, a.ldp, a.pos_u, a.pos_v, a.row_len, a.T, a.D, a.scale, a.out, a.ldo, a.out_bf16, a.row0, a.QT, a.H, a.xcd_map, a.chunk, a.left_chunks
+#define M3_ATT_SPREAD(a) a.qkv, a.ldq, a.pmat, a.ldp, a.pos_u, a.pos_v, a.row_len, a.T, a.D, a.scale, a.out, a.ldo, a.out_bf16, a.row0, a.QT, a.H, a.xcd_map, a.chunk, a.left_chunks, a.qt_magic, a.h_magic
 template <int DK>
 __global__ __launch_bounds__(256) void relpos_attention_kernel(const AttKernArgs a) {
   relpos_attention_body<DK>(M3_ATT_SPREAD(a), (int)blockIdx.x);
@@ -233,7 +358,7 @@ __global__ __launch_bounds__(256) void relpos_attention_stream_kernel(const floa
   asm volatile("" ::"s"(qkv), "s"(ldq), "s"(hist), "s"(cap), "s"(pmat), "s"(ldp), "s"(pos_u), "s"(pos_v), "s"(chunk_len), "s"(step),
                "s"(C), "s"(D), "s"(scale), "s"(out), "s"(ldo), "s"(QT), "s"(H), "s"(left_chunks));
   __shared__ __attribute__((aligned(16))) float ps_all[4][16][20];
-  __shared__ float mo[4][16][DK + 1];
+  __shared__ float mo[4][16][att_mo_ld(DK)];
   __shared__ float mm[4][16], ml[4][16];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 15, kq = lane >> 4;
   float (*ps)[20] = ps_all[wave];
@@ -346,20 +471,7 @@ __global__ __launch_bounds__(256) void relpos_attention_stream_kernel(const floa
     for (int n = 0; n < KS; ++n) mo[wave][4 * kq + r][16 * n + col] = o[n][r];
   }
   __syncthreads();
-  for (int idx = threadIdx.x; idx < 16 * DK; idx += 256) {
-    const int i = idx / DK, d = idx - i * DK;
-    const int qrow = q0 + i;
-    if (qrow >= C) continue;
-    const float m_tot = fmaxf(fmaxf(mm[0][i], mm[1][i]), fmaxf(mm[2][i], mm[3][i]));
-    float l_tot = 0.f, acc = 0.f;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-      const float f = (mm[w][i] == -INFINITY) ? 0.f : expf(mm[w][i] - m_tot);
-      l_tot += ml[w][i] * f;
-      acc += mo[w][i][d] * f;
-    }
-    out[(brow + qrow) * ldo + h * DK + d] = l_tot > 0.f ? acc / l_tot : 0.f;
-  }
+  att_merge_store<DK>(mm, ml, &mo[0][0][0], q0, C, brow, h, out, ldo, 0);
 }
 
 // (a.T: the C frames of a chunk, a.row_len: their valid count per utterance; checked by check_relpos_attention)
@@ -608,14 +720,19 @@ static int launch_relpos_attention_bf16(const AttArgs& a, hipStream_t stream) {
 
 // ------------------------------------------------------------------------------------------------------------------------
 // The host side of the three cores: one record (AttArgs), one check, one launcher; att_pack serves the fp32 single and dual kernels.
+// the kernel's divisions by QT and H as multiplications (att_div): floor(2^32 / d) + 1, exact for n d < 2^32 -- n < the work-group
+// count, which check_relpos_attention bounds; 0 marks d = 1
+static unsigned att_magic(int d) { return d == 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)d + 1); }
 static AttKernArgs att_pack(const AttArgs& q) {
   AttKernArgs k;
   k.qkv = (const float*)q.qkv; k.ldq = q.ldq; k.pmat = q.pmat; k.ldp = q.ldp; k.pos_u = q.pos_u; k.pos_v = q.pos_v; k.row_len = q.row_len; k.T = q.T;
   k.D = q.H * q.dk; k.scale = q.scale; k.out = (float*)q.out; k.ldo = q.ldo; k.out_bf16 = q.out_bf16; k.row0 = q.row0; k.QT = cdiv(q.T, 16); k.H = q.H;
   k.xcd_map = ((q.H * q.B) % 8 == 0) ? 1 : 0; k.chunk = q.chunk; k.left_chunks = q.left_chunks; k.n_wg = k.QT * q.H * q.B;
+  k.qt_magic = att_magic(k.QT); k.h_magic = att_magic(q.H);
   return k;
 }
 static bool att_dk(int dk) { return dk == 16 || dk == 32 || dk == 64 || dk == 128; }
+constexpr size_t kAttMaxRowSpan = (size_t)1 << 30;   // elements: 32-bit byte offsets within one utterance's rows
 static bool att_dual_dk(int dk) { return dk == 64 || dk == 128; }
 
 // the three cores' argument checks (fp32 rows, bf16 rows, chunk-by-chunk), for the single and the dual launcher
@@ -627,6 +744,7 @@ static int check_relpos_attention(const AttArgs& a, bool say = true) {
     M3_REQUIRE_SAY(say, (a.ldq & 3) == 0 && (a.ldp & 3) == 0 && (a.dk & 3) == 0, "attention (stream): row strides must be multiples of 4");
     M3_REQUIRE_SAY(say, a.hist && a.row_len && a.step, "attention (stream): null state");
     M3_REQUIRE_SAY(say, att_dk(a.dk), "attention (stream): d_k=%d unsupported (16/32/64/128)", a.dk);
+    M3_REQUIRE_SAY(say, (size_t)a.T * (size_t)a.ldo < kAttMaxRowSpan, "attention (stream): a chunk's rows span %zu elements (limit 2^30)", (size_t)a.T * (size_t)a.ldo);
     return 0;
   }
   M3_REQUIRE_SAY(say, a.B > 0 && a.T > 0 && a.H > 0, "attention: empty problem");
@@ -637,6 +755,11 @@ static int check_relpos_attention(const AttArgs& a, bool say = true) {
   }
   M3_REQUIRE_SAY(say, (a.ldq & 3) == 0 && (a.ldp & 3) == 0, "attention: row strides must be multiples of 4");
   M3_REQUIRE_SAY(say, att_dk(a.dk), "attention: d_k=%d unsupported (16/32/64/128)", a.dk);
+  // the kernel adds a 32-bit byte offset (a row below T' times a row stride) to an utterance's 64-bit base
+  const size_t span = (size_t)a.T * (size_t)std::max(std::max(a.ldq, a.ldp), a.ldo);
+  const size_t n_wg = (size_t)cdiv(a.T, 16) * a.H * a.B;       // (the ids divided by QT and by H in the kernel: att_div)
+  M3_REQUIRE_SAY(say, n_wg * (size_t)std::max(cdiv(a.T, 16), a.H) < ((size_t)1 << 32), "attention: %zu work-groups are more than the kernel's id arithmetic holds", n_wg);
+  M3_REQUIRE_SAY(say, span < kAttMaxRowSpan, "attention: the rows of one utterance span %zu elements (T' times the largest row stride; limit 2^30)", span);
   return 0;
 }
 
@@ -677,3 +800,9 @@ int launch_relpos_attention_dual(const AttArgs& a, const AttArgs& b, hipStream_t
 }
 
 }  // namespace m3
+
+#ifdef M3_ATT_DIAG
+extern "C" int m3_debug_att_read(void* dst, size_t bytes) {
+  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(m3::g_att_dbg), bytes < sizeof(m3::g_att_dbg) ? bytes : sizeof(m3::g_att_dbg));
+}
+#endif
